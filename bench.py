@@ -9,7 +9,8 @@ gate] -> final norm -> lm_head (151936 x 2048 INT4) -> greedy argmax.  Same prot
 value distributions (router gate from the reference's xorshift64 stream), generated on the GPU.  Everything is resident in HBM before
 the timed region.
 
-Side measurements on the N = 1 line (never the headline `value`): the whole-model prompt pass at the reference benchmark's prompt
+A plain run builds the model, warms up, times --steps decode steps and prints the line (--dump-outputs DIR: the last step's logits and token too).
+With --full, side measurements on the N = 1 line (never the headline `value`): the whole-model prompt pass at the reference benchmark's prompt
 lengths (--prefill-tokens, default 8192,20434,35139,49863: benchmark.py:434-505 / SURVEY 8d), the expert path alone, the same decode
 step late in a long cache, the other BASELINE configurations that fit one GPU (--side-configs: V2-Lite-shaped MLA model = config 2,
 QCN with INT8-g128 weights = config 5), and the CPU baseline (oracle port, incl. the V2-Lite Q4_K CPU expert pass = config 1).
@@ -289,12 +290,12 @@ def silence_stdout():
         pass
 
 
-def emit_line(res, args):
-    """write the full result dict to the detail file (and to stderr), print the compact line as the LAST stdout line"""
+def emit_line(res, args, detail=True):
+    """write the full result dict to the detail file (detail=False: none unless --detail-file names one), print the compact line as the LAST stdout line"""
     detail_path = None
     full = json.dumps(res)
     for cand in (getattr(args, "detail_file", None), os.path.join(ROOT, "gpurun_out", "bench_detail.json"), "/tmp/bench_detail.json"):
-        if not cand:
+        if not cand or not (detail or getattr(args, "detail_file", None)):
             continue
         try:
             os.makedirs(os.path.dirname(cand) or ".", exist_ok=True)
@@ -308,7 +309,8 @@ def emit_line(res, args):
     rel = os.path.relpath(detail_path, ROOT) if detail_path and detail_path.startswith(ROOT) else detail_path
     out, text = compact_line(res, rel)
     assert len(text) <= LINE_HARD_CAP_BYTES, "bench line is %d bytes" % len(text)
-    sys.stderr.write("bench.py: full detail (%d bytes) -> %s; compact line %d bytes\n" % (len(full), detail_path, len(text)))
+    if detail_path:
+        sys.stderr.write("bench.py: full detail (%d bytes) -> %s; compact line %d bytes\n" % (len(full), detail_path, len(text)))
     sys.stderr.flush()
     flush_native_stdout()      # buffered text of native libraries goes out BEFORE the line
     print(text, flush=True)
@@ -342,6 +344,13 @@ def parse():
     ap.add_argument("--flip-tokens", type=int, default=2000, help="tokens of the exact-vs-KR_DECODE_FAST router-id comparison on the N = 1 line (0 = skip)")
     ap.add_argument("--detail-file", default="", help="where the full (un-abridged) result dict goes; default gpurun_out/bench_detail.json")
     ap.add_argument("--side-configs", default="v2lite-q4,v2lite-q4k-gguf,qcn-q8,qcn-q4k-gguf,qwen3-235b-q4", help="other single-GPU BASELINE configurations measured as side legs of the N = 1 line ('' = none)")
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: run every side measurement as well -- the other decode mode, the generate loops, the per-kernel roofline, the router-id comparison, "
+                         "the other KV type, the prompt pass, the long cache, the GGUF experts, --side-configs and the CPU baseline -- and write the detail file. "
+                         "Without it the run builds the model, warms up, times the --steps decode steps and prints the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="N = 1: after the timed steps, write what the last timed step computed to DIR/logits.npy (float32 [vocab]) and DIR/token.npy "
+                         "(float64 [1], the greedy sample); the inputs are seeded, so the same arguments give the same inputs")
     return ap.parse_args()
 
 
@@ -744,6 +753,32 @@ def time_decode(st, steps, warmup, kvm, torch, dist, world):
     if world > 1:
         t = torch.tensor([dt], device="cuda"); dist.all_reduce(t, op=dist.ReduceOp.MAX); dt = float(t.item())
     return dt
+
+
+def dump_outputs(out_dir, st, dims, kvm, n_steps, seed, torch):
+    """--dump-outputs: what the LAST timed decode step computed -- the logits a caller passing an output pointer receives (float32 [vocab]) and the greedy
+    sample (float64 [1]) -- as out_dir/logits.npy and out_dir/token.npy.  The timed steps keep their logits on the device (no copy in the timed region),
+    so the same n_steps steps of time_decode are replayed from the same initial state (fill_state_synthetic(kvm, seed)) with the last one copying its
+    logits out.  The replay must leave the buffers the timed run left -- greedy token, hidden state, router logits of the last MoE layer -- bit for bit."""
+    import numpy as np
+
+    def snapshot():
+        torch.cuda.synchronize()
+        snap = [np.array([st.last_token()], np.int64), st.read_hidden(dims["hidden"])]
+        if dims.get("experts"):
+            snap.append(st.read_router(dims["experts"], dims["topk"])[0])
+        return snap
+    timed = snapshot()
+    st.fill_state_synthetic(kvm, seed=seed)
+    logits = np.empty(dims["vocab"], np.float32)
+    for i in range(n_steps):                                  # time_decode's token and positions
+        st.decode_step(0, (10 + i) % (kvm - 1), logits.ctypes.data if i == n_steps - 1 else 0)
+    replay = snapshot()
+    if not all(np.array_equal(a.view(np.uint8), b.view(np.uint8)) for a, b in zip(timed, replay)):
+        raise RuntimeError("--dump-outputs: replaying the decode steps did not reproduce the buffers of the last timed step")
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "logits.npy"), logits)
+    np.save(os.path.join(out_dir, "token.npy"), timed[0].astype(np.float64))
 
 
 def decode_generate(st, kvm, n_tokens=64, runs=3, lookahead=False):
@@ -1300,8 +1335,42 @@ def main_multi(args, torch, dist, world, rank, local_rank):
             pass
 
 
+def headline_result(args, name, L, bits, kv_fp8, kvm, fast_mode, dt, other):
+    """the N = 1 line's contract fields: the timed decode steps of the headline mode (`other`: the other mode's leg of --full, or {})"""
+    qcn = name.startswith("qcn"); q235 = name.startswith("qwen3-235b")
+    tok_s = args.steps / dt
+    model = "Qwen3-Coder-Next Q%d" % bits if qcn else ("Qwen3-235B-A22B Q4" if q235 else "DeepSeek-V2-Lite Q4")
+    mode_tag = "KR_DECODE_FAST tolerance mode" if fast_mode else "bit-exact mode"
+    exact_tok_s = other.get("tok_s") if fast_mode else tok_s
+    fast_tok_s = tok_s if fast_mode else other.get("tok_s")
+    return {
+        "metric": "decode tok/s, %s @1 MI355X (%s; both modes: value_exact / value_fast)" % (model, mode_tag),
+        "value": tok_s, "value_exact": exact_tok_s, "value_fast": fast_tok_s, "unit": "tok/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "int%d-g128 w x int16 act -> i32, f32 scales" % bits,
+        "dtype_note": ("int%d-g128 weights x int16 activations -> i32 group sums, f32 scales" % bits) +
+                 (" (KR_DECODE_FAST: the reference's products, f32 sums as lane / wave / workgroup trees -- logits within 2e-3 of the bit-exact mode, "
+                  "router ids identical for identical logits; tests/test_decode_fast_gpu.py)" if fast_mode else " (reference CPU-decode numerics, bit-exact)"),
+        "data": "synthetic",
+        "config": {"workload": WORKLOAD[name],
+                   "scope": "full decode_step: embedding, %d layers (attention + MoE + shared expert), final norm, lm_head, greedy sample" % L,
+                   "kv": ("FP8-E4M3" if kv_fp8 else "FP16") + " KV cache, kv_max_seq %d" % kvm, "layers": L,
+                   "parallelism": "one GPU holds the whole model (N > 1 lines: expert parallelism, see main_multi)",
+                   "hip_graph": not args.no_graph, "target_tok_s": 200,
+                   "decode_mode": "`value` = fast (KR_DECODE_FAST, opt-in tolerance mode; the library default is the bit-exact graph = `value_exact`)" if fast_mode else "`value` = exact (library default); `value_fast` = KR_DECODE_FAST",
+                   "prefill_modes": "`prefill` = the library default (exact: bit-identical to token-by-token decode); `prefill_fast` (KR_ATTN_FAST) and "
+                                    "`prefill_fast_gemm` (KR_ATTN_FAST | KR_GEMM_FAST) are the opt-in throughput modes a serving deployment would run -- "
+                                    "the one to compare with the reference's GPU prompt pass (bf16 flash attention + Marlin GEMM) is prefill_fast_gemm; protocol: one un-timed pass of the "
+                                    "same prompt in the same mode, then >= 2 timed passes (median), allocation counter checked",
+                   "decode_token_protocol": "`value`: token 0 at positions 10.. like bench_decode_synthetic (decode.rs:5450), K graph replays back to back; `decode_generate`: the "
+                                            "reference's generate_batch protocol (benchmark.py:434-505): 3 x 64 tokens, the sampled token fed back"},
+    }
+
+
 def main():
     args = parse()
+    if args.dump_outputs and args.gpus > 1:
+        sys.exit("bench.py --dump-outputs writes the N = 1 decode step's outputs: run it with --gpus 1")
     import torch
     import torch.distributed as dist
 
@@ -1342,23 +1411,30 @@ def main():
     st.set_use_graph(not args.no_graph)
     kvm = dims["kv_max_seq"]
     fast_mode = args.decode_mode == "fast"
-    # the mode that is NOT the headline first (side leg, fewer steps), then the headline: K timed steps with the barrier / max-over-ranks protocol
+    # --full: the mode that is NOT the headline first (side leg, fewer steps), then the headline: K timed steps with the barrier / max-over-ranks protocol
     other, gen = {}, {}
-    try:
-        st.set_attention_mode(False, decode_fast=not fast_mode)
-        n_o = min(args.steps, 50)
-        d_o = time_decode(st, n_o, args.warmup, kvm, torch, None, 1)
-        other = {"tok_s": n_o / d_o, "ms_per_step": d_o / n_o * 1e3, "steps": n_o,
-                 "numerics": "KR_DECODE_FAST (tolerance mode)" if not fast_mode else "exact: bit-identical to the reference's CPU decode (tests/test_decode_gpu.py compares logits and every state tensor with array_equal)"}
-        st.fill_state_synthetic(kvm, seed=4242)
-        gen["exact" if fast_mode else "fast"] = decode_generate(st, kvm)
-    except Exception as ex:
-        other = {"error": repr(ex)}
+    if args.full:
+        try:
+            st.set_attention_mode(False, decode_fast=not fast_mode)
+            n_o = min(args.steps, 50)
+            d_o = time_decode(st, n_o, args.warmup, kvm, torch, None, 1)
+            other = {"tok_s": n_o / d_o, "ms_per_step": d_o / n_o * 1e3, "steps": n_o,
+                     "numerics": "KR_DECODE_FAST (tolerance mode)" if not fast_mode else "exact: bit-identical to the reference's CPU decode (tests/test_decode_gpu.py compares logits and every state tensor with array_equal)"}
+            st.fill_state_synthetic(kvm, seed=4242)
+            gen["exact" if fast_mode else "fast"] = decode_generate(st, kvm)
+        except Exception as ex:
+            other = {"error": repr(ex)}
     st.set_attention_mode(False, decode_fast=fast_mode)
     st.fill_state_synthetic(kvm, seed=4242 + rank)
     a0 = alloc_count()
     dt = time_decode(st, args.steps, args.warmup, kvm, torch, dist, world)
     decode_allocs = alloc_count() - a0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, st, dims, kvm, args.warmup + args.steps, 4242 + rank, torch)
+    if not args.full:          # the plain run: the headline decode steps and nothing else
+        res = headline_result(args, name, L, bits, kv_fp8, kvm, fast_mode, dt, other)
+        emit_line({k_: v for k_, v in res.items() if v is not None or k_ not in ("value_exact", "value_fast")}, args, detail=False)
+        return
     # the reference's own decode protocol next to the back-to-back number: generate_batch, 3 x 64 tokens, the sampled token fed back
     try:
         st.fill_state_synthetic(kvm, seed=4242)
@@ -1455,33 +1531,9 @@ def main():
         dom = max(sym_us, key=lambda s: sym_us[s])
         achieved = sym_bytes[dom] / (sym_us[dom] * 1e-6) / 1e9 if sym_us[dom] > 0 else 0.0
         achieved_raw = sym_bytes[dom] / (sym_raw[dom] * 1e-6) / 1e9 if sym_raw.get(dom, 0.0) > 0 else None
-        tok_s = args.steps / dt
         traffic, traffic_src = pmc_traffic(dom)
-        model = "Qwen3-Coder-Next Q%d" % bits if qcn else ("Qwen3-235B-A22B Q4" if q235 else "DeepSeek-V2-Lite Q4")
-        mode_tag = "KR_DECODE_FAST tolerance mode" if fast_mode else "bit-exact mode"
-        exact_tok_s = other.get("tok_s") if fast_mode else tok_s
-        fast_tok_s = tok_s if fast_mode else other.get("tok_s")
-        res = {
-            "metric": "decode tok/s, %s @1 MI355X (%s; both modes: value_exact / value_fast)" % (model, mode_tag),
-            "value": tok_s, "value_exact": exact_tok_s, "value_fast": fast_tok_s, "unit": "tok/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "int%d-g128 w x int16 act -> i32, f32 scales" % bits,
-            "dtype_note": ("int%d-g128 weights x int16 activations -> i32 group sums, f32 scales" % bits) +
-                     (" (KR_DECODE_FAST: the reference's products, f32 sums as lane / wave / workgroup trees -- logits within 2e-3 of the bit-exact mode, "
-                      "router ids identical for identical logits; tests/test_decode_fast_gpu.py)" if fast_mode else " (reference CPU-decode numerics, bit-exact)"),
-            "data": "synthetic",
-            "config": {"workload": WORKLOAD[name],
-                       "scope": "full decode_step: embedding, %d layers (attention + MoE + shared expert), final norm, lm_head, greedy sample" % L,
-                       "kv": ("FP8-E4M3" if kv_fp8 else "FP16") + " KV cache, kv_max_seq %d" % kvm, "layers": L,
-                       "parallelism": "one GPU holds the whole model (N > 1 lines: expert parallelism, see main_multi)",
-                       "hip_graph": not args.no_graph, "target_tok_s": 200,
-                       "decode_mode": "`value` = fast (KR_DECODE_FAST, opt-in tolerance mode; the library default is the bit-exact graph = `value_exact`)" if fast_mode else "`value` = exact (library default); `value_fast` = KR_DECODE_FAST",
-                       "prefill_modes": "`prefill` = the library default (exact: bit-identical to token-by-token decode); `prefill_fast` (KR_ATTN_FAST) and "
-                                        "`prefill_fast_gemm` (KR_ATTN_FAST | KR_GEMM_FAST) are the opt-in throughput modes a serving deployment would run -- "
-                                        "the one to compare with the reference's GPU prompt pass (bf16 flash attention + Marlin GEMM) is prefill_fast_gemm; protocol: one un-timed pass of the "
-                                        "same prompt in the same mode, then >= 2 timed passes (median), allocation counter checked",
-                       "decode_token_protocol": "`value`: token 0 at positions 10.. like bench_decode_synthetic (decode.rs:5450), K graph replays back to back; `decode_generate`: the "
-                                                "reference's generate_batch protocol (benchmark.py:434-505): 3 x 64 tokens, the sampled token fed back"},
+        res = headline_result(args, name, L, bits, kv_fp8, kvm, fast_mode, dt, other)
+        res.update({
             ("decode_exact" if fast_mode else "decode_fast"): other,
             "decode_generate": gen,
             "roofline": {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
@@ -1499,7 +1551,7 @@ def main():
                          "per_kind_us_per_step": {k_: round(v, 2) for k_, v in per_kind_us.items()},
                          "per_kind_us_per_step_raw_events": {k_: round(v, 2) for k_, v in raw_us.items()},
                          "per_kind_us_per_launch": {k_: round(v, 2) for k_, v in per_launch_us.items()}},
-        }
+        })
         res.update(side)
         res.update(ep_legs)
         if not args.no_cpu_baseline:

@@ -133,3 +133,31 @@ print("python text after the line")
     back = json.loads(lines[-1])                                  # the LAST stdout line is the compact object
     assert "value" in back and "roofline" in back
     assert len(lines) == 2
+
+
+def test_plain_run_options(monkeypatch):
+    """`bench.py --gpus 1 --steps N --warmup W` is the lean headline run: --full (every side leg) and --dump-outputs are off unless asked for"""
+    import sys
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, "", 7, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "out"
+
+
+def test_plain_line_without_side_legs():
+    """the plain run's result (contract fields of the timed steps only) still formats to a line with the contract keys"""
+    import json
+    import types
+    import bench
+    args = types.SimpleNamespace(steps=20, warmup=5, no_graph=False)
+    res = bench.headline_result(args, "qcn-q4", 48, 4, True, 256, True, 20 * 1.5e-3, {})
+    assert res["value"] == 20 / (20 * 1.5e-3) and abs(res["ms_per_step"] - 1.5) < 1e-9 and res["value_fast"] == res["value"] and res["value_exact"] is None
+    out, text = bench.compact_line({k: v for k, v in res.items() if v is not None or k not in ("value_exact", "value_fast")})
+    back = json.loads(text)
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config"):
+        assert k in back, k
+    assert "value_exact" not in back and "roofline" not in back and "cpu_baseline" not in back
+    assert back["metric"].startswith("decode tok/s, Qwen3-Coder-Next Q4 @1 MI355X")

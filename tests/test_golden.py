@@ -14,6 +14,18 @@ from oracle import oracle as O
 G = os.path.join(os.path.dirname(__file__), "golden")
 
 
+def load_fixture(name):
+    """<name>.npz, plus the row blocks <name>.0.npz, <name>.1.npz, ... of its largest arrays (kept apart so that no fixture file passes 1 MiB) joined back"""
+    d = dict(np.load(os.path.join(G, name + ".npz")))
+    i, blocks = 0, {}
+    while os.path.exists(os.path.join(G, "%s.%d.npz" % (name, i))):
+        for k, v in np.load(os.path.join(G, "%s.%d.npz" % (name, i))).items():
+            blocks.setdefault(k, []).append(v)
+        i += 1
+    d.update({k: np.concatenate(v) for k, v in blocks.items()})
+    return d
+
+
 def _bf16_round(x):
     u = np.ascontiguousarray(x, np.float32).view(np.uint32)
     r = ((u >> 16) & 1) + 0x7FFF
@@ -44,7 +56,7 @@ def test_la_recurrent_matches_reference_python():
 
 def test_la_recurrent_equals_chunked_reference():
     """The oracle's token-by-token recurrence reproduces the reference's CHUNKED prefill form (linear_attention.py:695) on 150 tokens."""
-    d = np.load(os.path.join(G, "la_chunked.npz"))
+    d = load_fixture("la_chunked")
     nk, nv, dk, dv, kd, M = [int(x) for x in d["dims"]]
     conv_state = np.zeros((2 * nk * dk + nv * dv) * kd, np.float32)
     state = np.zeros(nv * dk * dv, np.float32)
@@ -124,7 +136,7 @@ def test_la_state_per_step_matches_reference_python():
     state: f32 on both sides; the oracle walks the reference Rust order (decode.rs:1293: one fma chain over dk per column), torch contracts with its
     own order, and the Rust decode path (hence the oracle) uses the degree-5 polynomial sigmoid in the conv's SiLU where torch calls the exact one
     (~5e-5 relative on q / k / v, SURVEY appendix A #3) -- so the states agree to a few 1e-5 of their largest entry at EVERY step, without growth."""
-    d = np.load(os.path.join(G, "la_steps.npz"))
+    d = load_fixture("la_steps")
     nk, nv, dk, dv, kd, steps = [int(x) for x in d["dims"]]
     conv_state = np.zeros((2 * nk * dk + nv * dv) * kd, np.float32)
     state = np.zeros(nv * dk * dv, np.float32)

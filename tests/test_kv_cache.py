@@ -1,9 +1,7 @@
 """krasis_amd.kv_cache: the reference's paged-KV bookkeeping classes (python/krasis/kv_cache.py:38-272) on CPU tensors -- pool sizing, page allocation
-order, exhaustion message, FlashInfer / TRTLLM index arrays, the combined-MLA store -- and the unpaging gather of decode_setup.py:653-711.  When the
-reference package is importable (this container: /root/reference/python) the two implementations are driven side by side and must agree call by call."""
+order, exhaustion message, FlashInfer / TRTLLM index arrays, the combined-MLA store -- and the unpaging gather of decode_setup.py:653-711.  The
+reference classes' own results, recorded call by call (tests/golden/kv_cache_paging.npz), must be reproduced."""
 import os
-import sys
-import types
 
 import numpy as np
 import pytest
@@ -81,30 +79,27 @@ def test_unpage_matches_the_reference_copy_loop_and_feeds_a_store():
     assert held8[0][1].dtype == np.uint8 and np.array_equal(held8[0][1][:37], s.unpage(c.v_cache[0], None).view(torch.uint8).numpy())
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/python/krasis"), reason="reference checkout not present")
 def test_side_by_side_with_the_reference_classes():
-    sys.modules.setdefault("krasis", types.ModuleType("krasis")).__path__ = ["/root/reference/python/krasis"]
-    cfgmod = types.ModuleType("krasis.config"); cfgmod.ModelConfig = object; sys.modules["krasis.config"] = cfgmod
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("krasis.kv_cache", "/root/reference/python/krasis/kv_cache.py")
-    ref = importlib.util.module_from_spec(spec); spec.loader.exec_module(ref)
-    for mla, combined in ((False, False), (True, False), (True, True)):
-        a = ref.PagedKVCache(Cfg(mla), 2, torch.device("cpu"), max_pages=48, kv_dtype=torch.float16, combined=combined)
+    """the reference's classes driven through one allocation sequence per layout, recorded call by call in tests/golden/kv_cache_paging.npz
+    (tests/golden/make_golden_kv_cache.py); the same calls on this implementation must give the same pages, index arrays, cache and messages"""
+    ref = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "kv_cache_paging.npz"))
+    steps = [int(x) for x in ref["steps"]]
+    for c, (mla, combined) in enumerate(ref["configs"].astype(bool).tolist()):
         b = PagedKVCache(Cfg(mla), 2, "cpu", max_pages=48, kv_dtype=torch.float16, combined=combined)
-        sa, sb = ref.SequenceKVState(a), SequenceKVState(b)
-        for step in (1, 15, 1, 40, 100):
-            sa.ensure_capacity(step); sb.ensure_capacity(step); sa.advance(step); sb.advance(step)
-            assert sa.pages == sb.pages and sa.seq_len == sb.seq_len and sa.last_page_len() == sb.last_page_len()
-            assert torch.equal(sa.kv_indices("cpu"), sb.kv_indices("cpu")) and torch.equal(sa.block_tables("cpu"), sb.block_tables("cpu"))
-            assert a.free_page_count == b.free_page_count and a.max_context_tokens == b.max_context_tokens
+        sb = SequenceKVState(b)
+        for j, step in enumerate(steps):
+            sb.ensure_capacity(step); sb.advance(step)
+            assert sb.pages == ref["c%d_s%d_pages" % (c, j)].tolist()
+            assert [sb.seq_len, sb.last_page_len(), b.free_page_count, b.max_context_tokens] == ref["c%d_scalars" % c][j].tolist()
+            assert np.array_equal(sb.kv_indices("cpu").numpy(), ref["c%d_s%d_kv_indices" % (c, j)])
+            assert np.array_equal(sb.block_tables("cpu").numpy(), ref["c%d_s%d_block_tables" % (c, j)])
         if combined:
-            rows = torch.randn(sa.seq_len, 576).to(torch.float16); pos = torch.arange(sa.seq_len)
-            sa.store_kv_combined(1, rows, pos); sb.store_kv_combined(1, rows, pos)
-            assert torch.equal(a.kv_cache, b.kv_cache)
-        with pytest.raises(RuntimeError) as ea:
-            sa.ensure_capacity(10_000)
+            n = sb.seq_len
+            rows = (((torch.arange(n * 576, dtype=torch.int64) % 2039) - 1019).to(torch.float32) / 8).reshape(n, 576).to(torch.float16)
+            sb.store_kv_combined(1, rows, torch.arange(n))
+            assert np.array_equal(b.kv_cache.view(torch.int16).numpy().view(np.uint16), ref["c%d_kv_cache" % c])
         with pytest.raises(RuntimeError) as eb:
             sb.ensure_capacity(10_000)
-        assert str(ea.value) == str(eb.value)
-        sa.free(); sb.free()
-        assert a.free_page_count == b.free_page_count == 48
+        assert str(eb.value) == str(ref["c%d_exhausted" % c])
+        sb.free()
+        assert b.free_page_count == int(ref["c%d_free_after" % c]) == 48

@@ -113,7 +113,7 @@ stamps)
     ;;
 r4a)        # round 4, first contact: the whole GPU suite (all failures listed), then the driver's bench line
     timeout 1500 python -m pytest tests/ -q -m gpu -x --maxfail=8 2>&1 | tail -40
-    timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $R/r04_bench_line.json 2> $R/r04_bench_line.err; echo "bench rc=$?"; tail -c 1500 $R/r04_bench_line.err
+    timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $R/r04_bench_line.json 2> $R/r04_bench_line.err; echo "bench rc=$?"; tail -c 1500 $R/r04_bench_line.err
     python tools/bench_summary.py $R/r04_bench_line.json
     ;;
 pf4)        # round 4: kernel trace of the tolerance prompt pass (8192 tokens) and of the decode step
@@ -144,7 +144,7 @@ r4final)    # round 4 closing run: the whole GPU suite as the driver runs it, th
     # (raw rocprof directories are removed on the box once summarised: gpurun merges at most 64 MiB back)
     timeout 1800 python -m pytest tests/ -x -q -m gpu > $R/r04_gpu_tests_full.txt 2>&1; echo "pytest rc=$?"
     grep -E " passed| failed| error|skipped" $R/r04_gpu_tests_full.txt | tail -3 | tee $R/r04_gpu_tests_tail.txt
-    timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $R/r04_bench_line.json 2> $R/r04_bench_line.err; echo "bench rc=$?"; tail -c 400 $R/r04_bench_line.err
+    timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $R/r04_bench_line.json 2> $R/r04_bench_line.err; echo "bench rc=$?"; tail -c 400 $R/r04_bench_line.err
     python tools/bench_summary.py $R/r04_bench_line.json
     rm -rf $R/pmc_fast
     (cd /tmp && timeout 400 rocprofv3 --pmc FETCH_SIZE -d $R/pmc_fast --output-format csv -- python /root/repo/tools/probes/decode_fast_bench.py --only fast --steps 12 --route-tokens 0 --out /root/repo/gpurun_out/r04_decode_fast_pmcrun > $R/pmc_fast.log 2>&1)
@@ -168,12 +168,12 @@ r4c)        # round 4: lean select, MLA tolerance wiring, tolerance router logit
     ;;
 r4b)        # round 4: tests that failed / are new since r4a, the bench line, the kernel trace of the bench command
     timeout 900 python -m pytest tests/test_ep_gpu.py tests/test_sampler_gpu.py tests/test_decode_gpu.py tests/test_gguf_gpu.py tests/test_prefill_model_gpu.py -q -x 2>&1 | tail -6
-    timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $R/r04_bench_line.json 2> $R/r04_bench_line.err; echo "bench rc=$?"; tail -c 600 $R/r04_bench_line.err
+    timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $R/r04_bench_line.json 2> $R/r04_bench_line.err; echo "bench rc=$?"; tail -c 600 $R/r04_bench_line.err
     python tools/bench_summary.py $R/r04_bench_line.json
     ;;
 r5a)        # round 5, first contact: ADVICE r4 fixes (their tests), the compact bench line as the driver reads it, cache-residency upper bound of the decode step, kernel trace
     timeout 900 python -m pytest tests/test_sampler_gpu.py tests/test_ep_gpu.py tests/test_decode_fast_gpu.py tests/test_prefill_model_gpu.py -q -x 2>&1 | tail -5
-    timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $R/r05_bench_stdout.txt 2> $R/r05_bench_stderr.txt; echo "bench rc=$?"
+    timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $R/r05_bench_stdout.txt 2> $R/r05_bench_stderr.txt; echo "bench rc=$?"
     tail -1 $R/r05_bench_stdout.txt > $R/r05_bench_line.json; echo "last stdout line: $(wc -c < $R/r05_bench_line.json) bytes, stdout lines: $(wc -l < $R/r05_bench_stdout.txt)"
     python -c "import json,sys; d=json.load(open('$R/r05_bench_line.json')); print({k: d[k] for k in ('value','value_exact','ms_per_step')}, d['roofline'])"
     cp $R/bench_detail.json $R/r05_bench_detail.json 2>/dev/null
@@ -192,7 +192,7 @@ r5final)    # round 5 closing run: GPU suite as the driver runs it; PMC fetch pa
     python tools/rocprof_csv_summary.py pmc $R/pmc_fast $R/r05_decode_fast_pmc_fetch_size.txt "QCN Q4 decode step, KR_DECODE_FAST: HBM fetch per launch (rocprofv3 --pmc FETCH_SIZE, counters-only pass; x2 = gfx950 correction)" 2>&1 | tail -2
     cp $R/r05_decode_fast_pmc_fetch_size.json $R/r05_decode_fast_pmc_fetch_size.txt profiles/ 2>/dev/null
     head -14 $R/r05_decode_fast_pmc_fetch_size.txt
-    timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $R/r05_bench_stdout.txt 2> $R/r05_bench_stderr.txt; echo "bench rc=$?"
+    timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $R/r05_bench_stdout.txt 2> $R/r05_bench_stderr.txt; echo "bench rc=$?"
     tail -1 $R/r05_bench_stdout.txt > $R/r05_bench_line.json; echo "last stdout line: $(wc -c < $R/r05_bench_line.json) bytes, stdout lines: $(wc -l < $R/r05_bench_stdout.txt)"
     cp $R/bench_detail.json $R/r05_bench_detail.json 2>/dev/null
     python tools/bench_summary.py $R/r05_bench_detail.json
@@ -216,7 +216,7 @@ r6final)    # round 6 closing run: GPU suite as the driver runs it; PMC fetch pa
     python tools/rocprof_csv_summary.py pmc $R/pmc_fast $R/r06_decode_fast_pmc_fetch_size.txt "QCN Q4 decode step, KR_DECODE_FAST: HBM fetch per launch (rocprofv3 --pmc FETCH_SIZE, counters-only pass; x2 = gfx950 correction)" 2>&1 | tail -2
     cp $R/r06_decode_fast_pmc_fetch_size.json $R/r06_decode_fast_pmc_fetch_size.txt profiles/ 2>/dev/null
     head -14 $R/r06_decode_fast_pmc_fetch_size.txt
-    timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $R/r06_bench_stdout.txt 2> $R/r06_bench_stderr.txt; echo "bench rc=$?"
+    timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $R/r06_bench_stdout.txt 2> $R/r06_bench_stderr.txt; echo "bench rc=$?"
     tail -1 $R/r06_bench_stdout.txt > $R/r06_bench_line.json; echo "last stdout line: $(wc -c < $R/r06_bench_line.json) bytes, stdout lines: $(wc -l < $R/r06_bench_stdout.txt)"
     cp $R/bench_detail.json $R/r06_bench_detail.json 2>/dev/null
     python tools/bench_summary.py $R/r06_bench_detail.json
@@ -246,7 +246,7 @@ r5line)     # round 5: PMC fetch pass (json into profiles/ on the box) -> the dr
     python tools/rocprof_csv_summary.py pmc $R/pmc_fast $R/r05_decode_fast_pmc_fetch_size.txt "QCN Q4 decode step, KR_DECODE_FAST: HBM fetch per launch (rocprofv3 --pmc FETCH_SIZE, counters-only pass; x2 = gfx950 correction)" 2>&1 | tail -2
     cp $R/r05_decode_fast_pmc_fetch_size.json $R/r05_decode_fast_pmc_fetch_size.txt profiles/ 2>/dev/null
     head -16 $R/r05_decode_fast_pmc_fetch_size.txt
-    timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $R/r05_bench_stdout.txt 2> $R/r05_bench_stderr.txt; echo "bench rc=$?"
+    timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $R/r05_bench_stdout.txt 2> $R/r05_bench_stderr.txt; echo "bench rc=$?"
     tail -1 $R/r05_bench_stdout.txt > $R/r05_bench_line.json; echo "last stdout line: $(wc -c < $R/r05_bench_line.json) bytes, stdout lines: $(wc -l < $R/r05_bench_stdout.txt)"
     cp $R/bench_detail.json $R/r05_bench_detail.json 2>/dev/null
     python tools/bench_summary.py $R/r05_bench_detail.json
@@ -261,7 +261,7 @@ tests)      # the whole GPU suite, as the driver runs it
     timeout 2400 python -m pytest tests/ -x -q -m gpu "$@" 2>&1 | tail -15
     ;;
 bench)      # the driver's bench line
-    timeout 1200 python bench.py --gpus 1 --steps 20 --warmup 5 "$@" > $R/bench_line.json 2> $R/bench_line.err; echo "bench rc=$?"; tail -c 3000 $R/bench_line.json
+    timeout 1200 python bench.py --gpus 1 --steps 20 --warmup 5 --full "$@" > $R/bench_line.json 2> $R/bench_line.err; echo "bench rc=$?"; tail -c 3000 $R/bench_line.json
     ;;
 exact1)     # round 6: exact decode step after the router / ADVICE changes: bit-exact tests, then the exact-vs-fast bench probe and the kernel trace of the exact graph
     timeout 1500 python -m pytest tests/test_decode_gpu.py tests/test_router_gpu.py tests/test_prefill_model_gpu.py -x -q 2>&1 | tail -5
