@@ -322,6 +322,30 @@ int kr_decode_cancel(kr_decode_store* s);
 int kr_decode_reset_cancel(kr_decode_store* s);
 double kr_decode_last_elapsed_s(kr_decode_store* s);
 
+/* ---- exact speculative greedy decoding (docs/design/12-speculative.md).  Exact mode only: any tolerance bit of kr_decode_set_attention_mode, a
+ * native-GGUF MoE layer or expert parallelism is refused (KR_ERR_STATE), never run in another form. */
+#define KR_VERIFY_MAX 16
+#define KR_LOOKUP_NGRAM_MAX 32   /* largest ngram_max kr_decode_generate_lookup indexes */
+/* tokens[0] = the token at start_pos (sampled, not yet consumed); tokens[1..n) = draft.  Runs all n through the model on top of the current state
+ * (the exact prompt pass).  greedy_out[i] = first-maximum argmax of the logits after tokens[0..i] (the rule of kr_launch_argmax).
+ * *n_match_out = largest m <= n-1 with tokens[i] == greedy_out[i-1] for 1 <= i <= m.  Leaves a PENDING verify: exactly one kr_decode_commit follows. */
+int kr_decode_verify(kr_decode_store* s, const int32_t* tokens, int n_tokens, int start_pos, int32_t* greedy_out, int* n_match_out, void* stream);
+/* 1 <= n_keep <= n_match + 1: afterwards the store is bit-identical to n_keep kr_decode_step calls on tokens[0..n_keep) from the pre-verify state
+ * (KV rows [0, start_pos + n_keep), conv + recurrent states, s->logits = row n_keep-1, kr_decode_last_token = greedy_out[n_keep-1]).
+ * KV rows at >= start_pos + n_keep are unspecified (the next pass overwrites them). */
+int kr_decode_commit(kr_decode_store* s, int n_keep);
+/* greedy generation with prompt-lookup drafts: tokens_out / *n_out / return code / state afterwards IDENTICAL to
+ * kr_decode_generate_greedy(s, first_token, start_pos, max_tokens, stop_ids, n_stop, ...).  context = earlier tokens to search (e.g. the prompt).
+ * max_draft in [0, KR_VERIFY_MAX-1] (0 = plain loop), ngram_max in [1, KR_LOOKUP_NGRAM_MAX].  *n_passes_out = model passes (verify passes + plain steps),
+ * *n_accepted_out = accepted draft tokens (either may be NULL). */
+int kr_decode_generate_lookup(kr_decode_store* s, const int32_t* context, int n_context, int first_token, int start_pos, int max_tokens,
+                              int max_draft, int ngram_max, const int* stop_ids, int n_stop, int* tokens_out, int* n_out,
+                              int* n_passes_out, int* n_accepted_out, void* stream);
+/* host-only (test aid, like kr_sample_order): the draft the loop would propose after history[0..n).  For g = min(ngram_max, n-1) down to 1: the largest
+ * j with j + g <= n-1 and history[j..j+g) == history[n-g..n); the first g that matches gives history[j+g .. min(j+g+max_draft, n)).  Returns the
+ * draft length (0: no match), or a negative KR_ERR_* on bad arguments. */
+int kr_lookup_draft(const int32_t* history, int n_history, int ngram_max, int max_draft, int32_t* draft_out);
+
 /* ---- stand-alone CpuDecodeStore operators (decode.rs:328-1086).  Every pointer may be a host or a device pointer; host buffers are staged and
  * the call returns after the results are back.  Bit-identical to the reference methods (tests/test_standalone_ops_gpu.py against the oracle's
  * kro_op_* restatements); several differ from the decode graph's arithmetic exactly as they do in the reference (scalar loops, libm exp). */
@@ -345,7 +369,7 @@ int kr_decode_num_route_weights(kr_decode_store* s);                            
 size_t kr_decode_weight_bytes(kr_decode_store* s, int weight_id);                                                             /* decode.rs:1107 */
 int kr_decode_last_token(kr_decode_store* s, int* token);
 int kr_decode_set_use_graph(kr_decode_store* s, int enable);
-int kr_decode_read_buffer(kr_decode_store* s, int which /* 0 hidden, 1 residual, 2 router ids (i32 bits), 3 router weights, 4 router logits, 5 second residual (KR_DECODE_FAST) */, float* out, int n);
+int kr_decode_read_buffer(kr_decode_store* s, int which /* 0 hidden, 1 residual, 2 router ids (i32 bits), 3 router weights, 4 router logits, 5 second residual (KR_DECODE_FAST), 6 logits [vocab] */, float* out, int n);
 size_t kr_decode_device_bytes(const kr_decode_store* s);
 /* measurement hook (bench.py): one un-graphed step with HIP events around every launch; per-kind totals (ms) and launch counts.
  * kinds: 0 embed 1 fused_add_rmsnorm 2 projection matvec 3 la_conv 4 la_recurrent 5 gated_rmsnorm_silu 6 gqa 7 route_logits

@@ -11,6 +11,7 @@ KR_OK, KR_ERR_STATE, KR_ERR_VALUE, KR_ERR_IO, KR_ERR_HIP = 0, 1, 2, 3, 4
 KR_OUT_F32, KR_OUT_BF16 = 0, 1
 KR_SCORE_SIGMOID, KR_SCORE_SOFTMAX, KR_SCORE_TOPK_SOFTMAX = 0, 1, 2
 KR_ROUTE_RULE_ENGINE, KR_ROUTE_RULE_DECODE = 0, 1
+KR_VERIFY_MAX, KR_LOOKUP_NGRAM_MAX = 16, 32    # exact speculative decoding: tokens per verify pass, longest indexed n-gram
 
 # every symbol include/krasis_hip.h declares (checked by tests/test_abi.py without a GPU)
 SYMBOLS = [
@@ -26,7 +27,7 @@ SYMBOLS = [
     "kr_decode_generate_stream", "kr_decode_cancel", "kr_decode_reset_cancel", "kr_decode_last_elapsed_s", "kr_decode_matmul", "kr_decode_matmul_batch",
     "kr_decode_fused_add_rmsnorm", "kr_decode_rmsnorm", "kr_decode_silu_mul", "kr_decode_fused_shared_expert", "kr_decode_linear_attention_recurrent",
     "kr_decode_gated_rmsnorm_silu", "kr_decode_linear_attention_conv", "kr_decode_store_route_weight", "kr_decode_moe_route", "kr_decode_num_route_weights",
-    "kr_decode_weight_bytes",
+    "kr_decode_weight_bytes", "kr_decode_verify", "kr_decode_commit", "kr_decode_generate_lookup", "kr_lookup_draft",
 ]
 TOKEN_CB = C.CFUNCTYPE(C.c_int, C.c_int, C.c_int, C.c_void_p)      # kr_token_cb(token, finish_reason, user) -> continue?
 
@@ -164,6 +165,10 @@ def load_library() -> C.CDLL:
     lib.kr_decode_moe_route.argtypes = [vp, ci, vp, vp, vp, ci, ci, ci]
     lib.kr_decode_num_route_weights.argtypes = [vp]
     lib.kr_decode_weight_bytes.argtypes = [vp, ci]; lib.kr_decode_weight_bytes.restype = C.c_size_t
+    lib.kr_decode_verify.argtypes = [vp, vp, ci, ci, vp, C.POINTER(ci), vp]
+    lib.kr_decode_commit.argtypes = [vp, ci]
+    lib.kr_decode_generate_lookup.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, vp, ci, vp, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), vp]
+    lib.kr_lookup_draft.argtypes = [vp, ci, ci, ci, vp]
     _lib = lib
     return lib
 

@@ -84,7 +84,8 @@ extern "C" void kr_decode_destroy(kr_decode_store* s) {
                            &l.w_kc, &l.w_vc, &l.kv_a_norm, &l.q_a_norm, &l.mla_cos, &l.mla_sin}) b->release();
     for (DevBuf* b : {&s->embedding, &s->rope_cos, &s->rope_sin, &s->hid, &s->res, &s->proj_a, &s->proj_b, &s->qbuf, &s->kbuf, &s->vbuf, &s->zbuf,
                       &s->gbuf, &s->betabuf, &s->gatebuf, &s->latbuf, &s->recur_out, &s->attn_out, &s->logits, &s->gate_val, &s->tok, &s->step_dev,
-                      &s->hid2, &s->res2, &s->f_qk, &s->r_counter, &s->gqa_scores, &s->fd_o, &s->fd_ml, &s->argmax_scratch, &s->img_in, &s->img_post, &s->img_post_bf16, &s->img_attn, &s->smp_seen, &s->smp_keys, &s->smp_temp, &s->smp_probs, &s->smp_rng, &s->pf_scratch, &s->pf_scores, &s->pf_vlogits, &s->pf_nll, &s->pf_tokens, &s->moe_gu, &s->moe_eo, &s->r_logits, &s->r_ids, &s->r_w, &s->dense_gu}) b->release();
+                      &s->hid2, &s->res2, &s->f_qk, &s->r_counter, &s->gqa_scores, &s->fd_o, &s->fd_ml, &s->argmax_scratch, &s->img_in, &s->img_post, &s->img_post_bf16, &s->img_attn, &s->smp_seen, &s->smp_keys, &s->smp_temp, &s->smp_probs, &s->smp_rng, &s->pf_scratch, &s->pf_scores, &s->pf_vlogits, &s->pf_nll, &s->pf_tokens, &s->moe_gu, &s->moe_eo, &s->r_logits, &s->r_ids, &s->r_w, &s->dense_gu,
+                      &s->spec_buf, &s->spec_tab, &s->spec_logits, &s->spec_out, &s->spec_part}) b->release();
     for (hipEvent_t ev : s->pf_events) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : s->gen_ev) if (ev) (void)hipEventDestroy(ev);
     if (s->gen_ring) (void)hipHostFree(s->gen_ring);
@@ -399,6 +400,7 @@ extern "C" int kr_decode_set_state(kr_decode_store* s, int seq_len, int kv_max_s
     KR_HIP(hipSetDevice(s->eng->device));
     KR_HIP(hipDeviceSynchronize());          // steps still in flight on the engine's (non-blocking) streams write these buffers
     s->kv_max_seq = kv_max_seq;
+    s->spec_pending = false;                 // a new state discards a pending kr_decode_verify
     for (size_t i = 0; i < s->layers.size(); i++) {
         DLayer& L = s->layers[i];
         if (L.attn == ATTN_GQA) {
@@ -440,6 +442,7 @@ extern "C" int kr_decode_fill_state_synthetic(kr_decode_store* s, int kv_max_seq
     if (int rc = need_cfg(s)) return rc;
     KR_HIP(hipSetDevice(s->eng->device));
     s->kv_max_seq = kv_max_seq;
+    s->spec_pending = false;
     for (size_t i = 0; i < s->layers.size(); i++) {
         DLayer& L = s->layers[i];
         if (L.attn == ATTN_GQA || L.attn == ATTN_MLA) {
@@ -1074,6 +1077,7 @@ static int decode_step_on(kr_decode_store* s, int token_id, int position, float*
 extern "C" int kr_decode_step(kr_decode_store* s, int token_id, int position, float* logits_out, void* stream) {
     if (int rc = need_cfg(s)) return rc;
     if (token_id < 0) return kr_fail(KR_ERR_VALUE, "token id %d out of range (vocab %d)", token_id, s->vocab);
+    if (int rc = kr_spec_pending_fail(s)) return rc;
     KR_HIP(hipSetDevice(s->eng->device));
     return decode_step_on(s, token_id, position, logits_out, kr_pick_stream(s->eng, stream));
 }
@@ -1142,6 +1146,7 @@ static int generate_core(kr_decode_store* s, int first_token, int start_pos, int
                          kr_token_cb on_token, void* user) {
     if (int rc = need_cfg(s)) return rc;
     if (!n_out || (!tokens_out && !on_token)) return kr_fail(KR_ERR_VALUE, "null output pointer");
+    if (int rc = kr_spec_pending_fail(s)) return rc;
     if (temperature < 0.0f) return kr_fail(KR_ERR_VALUE, "temperature must be >= 0");
     KR_HIP(hipSetDevice(s->eng->device));
     hipStream_t st = kr_pick_stream(s->eng, stream);
@@ -1261,8 +1266,10 @@ extern "C" int kr_decode_read_buffer(kr_decode_store* s, int which, float* out, 
     if (int rc = need_cfg(s)) return rc;
     KR_HIP(hipSetDevice(s->eng->device));
     KR_HIP(hipStreamSynchronize(s->eng->stream));
-    // 0 hidden, 1 residual, 2 router ids (int32 bits), 3 router weights, 4 router logits of the LAST MoE layer of the last step, 5 second residual buffer
-    DevBuf* b = which == 0 ? &s->hid : which == 1 ? &s->res : which == 2 ? &s->r_ids : which == 3 ? &s->r_w : which == 4 ? &s->r_logits : which == 5 ? &s->res2 : nullptr;
+    // 0 hidden, 1 residual, 2 router ids (int32 bits), 3 router weights, 4 router logits of the LAST MoE layer of the last step, 5 second residual buffer,
+    // 6 the logits the next sample draws from (last step, prompt pass or kr_decode_commit)
+    DevBuf* b = which == 0 ? &s->hid : which == 1 ? &s->res : which == 2 ? &s->r_ids : which == 3 ? &s->r_w : which == 4 ? &s->r_logits : which == 5 ? &s->res2 :
+                which == 6 ? &s->logits : nullptr;
     if (!b || !b->p || (size_t)n * 4 > b->bytes) return kr_fail(KR_ERR_VALUE, "read_buffer: buffer %d unknown or shorter than %d words", which, n);
     if (s->last_stream) KR_HIP(hipStreamSynchronize(s->last_stream));
     KR_HIP(hipMemcpy(out, b->p, (size_t)n * 4, hipMemcpyDeviceToHost));

@@ -7,6 +7,7 @@
 
 #include "kr_decode_ops.h"
 #include "kr_engine_internal.h"
+#include "kr_spec.h"
 
 struct DWeight { MatSet ms; int rows = 0, cols = 0; };
 
@@ -70,6 +71,10 @@ struct kr_decode_store {
     DevBuf moe_gu, moe_eo, r_logits, r_ids, r_w;  // store-owned so a captured graph never sees them reallocated
     DevBuf step_dev; hipStream_t last_stream = nullptr;   // stream of the most recent step / prompt pass (kr_decode_last_token waits on it)
     size_t weight_bytes = 0;
+    // exact speculative decoding (kr_decode_verify / kr_decode_commit, kr_decode_prefill.cpp): per linear-attention layer the snapshot of its states and
+    // what a verify pass fed the recurrence (spec_la[i] = the store layer of table entry i), the all-row logits, [greedy ids, n_match], accept partials
+    std::vector<int> spec_la, spec_la_of; std::vector<KrSpecLa> spec_host; DevBuf spec_buf, spec_tab, spec_logits, spec_out, spec_part;
+    bool spec_pending = false; int spec_n = 0, spec_match = 0, spec_nv_max = 0, spec_dv_max = 0; bool spec_has64 = false, spec_has128 = false; size_t spec_floats = 0; hipStream_t spec_st = nullptr;
     // captured graph of one decode step
     hipGraphExec_t graph_exec = nullptr; bool graph_ok = false; bool use_graph = true;
     // profiling pass (kr_decode_profile_step): HIP events around every launch, accumulated per kernel kind
@@ -84,5 +89,7 @@ static inline KrMatDev mv(kr_decode_store* s, int wid) { return s->weights[wid]-
 int kr_ensure_wsum(kr_engine* e, MatSet& ms, hipStream_t st);
 int kr_moe_prefill_prepare(kr_engine* e, int layer, int fast, int routed_only, hipStream_t st);   // kr_engine.cpp: the lazily derived data of a native-GGUF layer, built on `st` now
 void kr_standalone_release(kr_decode_store* s);
+int kr_spec_refuse(kr_decode_store* s);          // kr_decode_prefill.cpp: KR_OK when exact speculative decoding can run on this store
+int kr_spec_pending_fail(kr_decode_store* s);    // KR_ERR_STATE while a verify waits for its commit
 int kr_standalone_cancelled(kr_decode_store* s);
 void kr_standalone_set_elapsed(kr_decode_store* s, double sec);   // kr_engine.cpp: per (group, column) nibble sums for the int8-MFMA GEMM

@@ -10,6 +10,7 @@
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -38,6 +39,7 @@ Act Y(const Scratch& B) { return Act{B.yh, B.yl, B.ys, B.yf, B.yfm}; }
 struct Chunk {      // one chunk of the prompt in flight: its arena, stream and running flags
     Scratch B; float* scores; const int* tok; int Cc, pos0, set; bool first, add_is_emb; hipStream_t st;
     KrPfSync sy;      // this (chunk, layer)'s hand-overs with the previous / next chunk (set by the scheduler before every run_layer)
+    bool verify = false;      // kr_decode_verify's pass: linear-attention layers write their recurrence inputs into the store's verify buffers (kr_spec.h)
 };
 size_t al(size_t n) { return (n + 255) & ~(size_t)255; }
 }  // namespace
@@ -95,12 +97,16 @@ static int run_layer(kr_decode_store* s, Chunk& cx, size_t li) {
     cx.first = false; cx.add_is_emb = false;
     if (L.attn == ATTN_LA) {
         const int nq = s->weights[L.qkvz_wid]->rows, nb = s->weights[L.ba_wid]->rows, oc = s->weights[L.out_wid]->cols;
-        { const int wids[2] = {L.qkvz_wid, L.ba_wid}; float* outs[2] = {B.pa, B.pb}; const int lds[2] = {nq, nb};
+        // verify pass: the in-projection rows (the conv inputs) and k / v / e^g / beta land in this layer's slice of the verify buffers -- what a rollback replays
+        const KrSpecLa* vc = cx.verify ? &s->spec_host[(size_t)s->spec_la_of[li]] : nullptr;
+        float* qkvz = vc ? (float*)vc->qkvz : B.pa;
+        { const int wids[2] = {L.qkvz_wid, L.ba_wid}; float* outs[2] = {qkvz, B.pb}; const int lds[2] = {nq, nb};
           if (int rc = pf_gemm_multi(s, wids, outs, lds, 2, X(B), Cc, st)) return rc; }
         KrPfmLaArgs a{};
-        a.qkvz = B.pa; a.ld_qkvz = nq; a.ba = B.pb; a.ld_ba = nb; a.conv_state = (float*)L.conv_state.p; a.conv_w = (const float*)L.conv_w.p;
+        a.qkvz = qkvz; a.ld_qkvz = nq; a.ba = B.pb; a.ld_ba = nb; a.conv_state = (float*)L.conv_state.p; a.conv_w = (const float*)L.conv_w.p;
         a.a_log = (const float*)L.a_log.p; a.dt_bias = (const float*)L.dt_bias.p; a.scale = L.la_scale; a.q = B.q; a.k = B.k; a.v = B.v; a.z = B.z;
         a.gexp = B.gexp; a.beta = B.beta; a.nk = L.nk; a.nv = L.nv; a.dk = L.dk; a.dv = L.dv; a.hr = L.nv / L.nk;
+        if (vc) { a.k = (float*)vc->k; a.v = (float*)vc->v; a.gexp = (float*)vc->gexp; a.beta = (float*)vc->beta; }
         a.lac = B.lac; a.fast = s->attn_fast; a.conv_fused = s->opt_la_conv_fused;
         if (kr_launch_pfm_la(a, (float*)L.recur_state.p, B.recur, (const float*)L.la_norm_w.p, B.attn, Cc, s->eps, st, &cx.sy))
             return kr_fail(KR_ERR_VALUE, "unsupported linear-attention geometry");
@@ -233,9 +239,8 @@ static void run_final(kr_decode_store* s, Chunk& cx) {
     kr_launch_argmax((const float*)s->logits.p, s->vocab, (int*)s->tok.p, (float*)s->argmax_scratch.p, cx.st);
 }
 
-// scoring mode (kr_decode_prefill_nll): final norm + lm_head GEMM for EVERY token of the chunk, then the next-token negative log-likelihood
-// per row; the last chunk also leaves the last row's logits and greedy sample where run_final would
-static int run_final_all(kr_decode_store* s, Chunk& cx, float* vlogits, int first_tok, int n_tokens, bool last) {
+// final norm + lm_head GEMM for EVERY token of the chunk into vlogits [Cc][V] (the decode step's logits bit for bit)
+static int final_rows(kr_decode_store* s, Chunk& cx, float* vlogits) {
     Scratch& B = cx.B; const int H = s->hidden; const size_t V = (size_t)s->vocab;
     KrPfmNormArgs na{};
     na.mode = cx.add_is_emb ? 1 : 0; na.add_in = B.hid; na.emb = (const float*)s->embedding.p; na.tokens = cx.tok; na.res = B.res;
@@ -245,7 +250,14 @@ static int run_final_all(kr_decode_store* s, Chunk& cx, float* vlogits, int firs
     if (s->gemm_fast && s->opt_norm_rows) { na.xf = B.xf; na.xfm = B.xfm; }
     kr_launch_pfm_norm(na, cx.Cc, cx.st);
     if (s->gemm_fast && !s->opt_norm_rows) kr_launch_pfh_rows_f32(B.normed, cx.Cc, H, H, B.xf, B.xfm, cx.st);
-    if (int rc = pf_gemm(s, s->lm_head, X(B), cx.Cc, vlogits, (int)V, cx.st)) return rc;
+    return pf_gemm(s, s->lm_head, X(B), cx.Cc, vlogits, (int)V, cx.st);
+}
+
+// scoring mode (kr_decode_prefill_nll): all-row logits, then the next-token negative log-likelihood per row; the last chunk also leaves the last
+// row's logits and greedy sample where run_final would
+static int run_final_all(kr_decode_store* s, Chunk& cx, float* vlogits, int first_tok, int n_tokens, bool last) {
+    const size_t V = (size_t)s->vocab;
+    if (int rc = final_rows(s, cx, vlogits)) return rc;
     const int scored = std::min(cx.Cc, n_tokens - 1 - first_tok);      // the last prompt token has no label
     kr_launch_pfm_nll(vlogits, V, cx.tok + 1, (float*)s->pf_nll.p + first_tok, scored, (int)V, cx.st);
     if (last) {
@@ -255,9 +267,19 @@ static int run_final_all(kr_decode_store* s, Chunk& cx, float* vlogits, int firs
     return KR_OK;
 }
 
-static int prefill_impl(kr_decode_store* s, const int32_t* tokens, int n_tokens, int start_pos, float* logits_out, float* nll_out, void* stream) {
+// verify mode (kr_decode_verify): all-row logits into spec_logits, then the accept kernel -> spec_out = [greedy ids, n_match]; s->logits / s->tok are
+// left to kr_decode_commit
+static int run_final_verify(kr_decode_store* s, Chunk& cx) {
+    if (int rc = final_rows(s, cx, (float*)s->spec_logits.p)) return rc;
+    kr_launch_spec_accept((const float*)s->spec_logits.p, (size_t)s->vocab, s->vocab, cx.Cc, cx.tok, (int*)s->spec_out.p, (float*)s->spec_part.p,
+                          (unsigned*)((float*)s->spec_part.p + 2 * KR_VERIFY_MAX), cx.st);
+    return KR_OK;
+}
+
+static int prefill_impl(kr_decode_store* s, const int32_t* tokens, int n_tokens, int start_pos, float* logits_out, float* nll_out, void* stream, bool verify = false) {
     if (!s) return kr_fail(KR_ERR_VALUE, "null decode store");
     if (!s->configured) return kr_fail(KR_ERR_STATE, "Call configure_decode first");
+    if (!verify) if (int rc = kr_spec_pending_fail(s)) return rc;
     if (!tokens || n_tokens <= 0) return kr_fail(KR_ERR_VALUE, "kr_decode_prefill: empty prompt");
     if ((int)s->layers.size() != s->n_layers) return kr_fail(KR_ERR_STATE, "finalize_decode was not called");
     if (start_pos < 0 || (s->kv_max_seq > 0 && start_pos + n_tokens > s->kv_max_seq))
@@ -282,7 +304,7 @@ static int prefill_impl(kr_decode_store* s, const int32_t* tokens, int n_tokens,
     // (8192 tokens: 8 x 1024 = 3 + 3 + 2 chunks 382.9 ms, 6 x 1366 355.8; 20 434: 20 x 1024 1207.9, 18 x 1136 1180.1; 49 863: unchanged, attention-bound)
     const int q1k = (n_tokens + KR_PFM_CHUNK - 1) / KR_PFM_CHUNK, nc_exact = q1k >= depth ? (q1k / depth) * depth : q1k;
     const int exact_chunk = (n_tokens + nc_exact - 1) / nc_exact;
-    const int CH = std::min(n_tokens, s->pf_chunk > 0 ? s->pf_chunk : (s->attn_fast ? tol_chunk : exact_chunk));
+    const int CH = verify ? n_tokens : std::min(n_tokens, s->pf_chunk > 0 ? s->pf_chunk : (s->attn_fast ? tol_chunk : exact_chunk));     // verify: one chunk
     // expert parallelism: every rank must walk the SAME (chunk, layer) schedule -- the exchanges are collectives -- so the schedule is built from the chunk
     // count of the longest prompt shard (agreed below, before the first exchange); chunks a rank does not have run as empty shards
     int n_chunks_max = (n_tokens + CH - 1) / CH;
@@ -330,7 +352,7 @@ static int prefill_impl(kr_decode_store* s, const int32_t* tokens, int n_tokens,
             for (int w : {Ly.gate_wid, Ly.up_wid, Ly.down_wid}) wids.push_back(w);
         }
     }
-    if (nll_out) wids.push_back(s->lm_head);
+    if (nll_out || verify) wids.push_back(s->lm_head);
     for (int w : wids) {
         DWeight& W = *s->weights[w];
         if (int rc = kr_ensure_wsum(e, W.ms, st)) return rc;
@@ -393,7 +415,7 @@ static int prefill_impl(kr_decode_store* s, const int32_t* tokens, int n_tokens,
         Chunk& cx = chunks[c];
         cx.set = c % D; cx.B = carve(cx.set); cx.scores = sc_rows ? (float*)((char*)s->pf_scores.p + (size_t)cx.set * sc_bytes) : nullptr;
         cx.Cc = std::min(CH, n_tokens - c * CH); cx.pos0 = start_pos + c * CH; cx.tok = (const int*)s->pf_tokens.p + (size_t)c * CH;
-        cx.first = true; cx.add_is_emb = true; cx.st = streams[cx.set];
+        cx.first = true; cx.add_is_emb = true; cx.st = streams[cx.set]; cx.verify = verify;
     }
     // D chunks in flight (one per stream / arena): groups of D chunks are enqueued layer-interleaved; chunk c + D follows chunk c on the same
     // stream, so its arena is free, and it waits layer by layer for chunk c + D - 1 -- the pipeline never drains between groups
@@ -424,11 +446,13 @@ static int prefill_impl(kr_decode_store* s, const int32_t* tokens, int n_tokens,
                 if (int rc = run_layer(s, cx, (size_t)l)) return rc;
                 if (nll_out && l == L - 1)
                     if (int rc = run_final_all(s, cx, (float*)((char*)s->pf_vlogits.p + (size_t)cx.set * vl_bytes), c * CH, n_tokens, c == n_chunks - 1)) return rc;
+                if (verify && l == L - 1)
+                    if (int rc = run_final_verify(s, cx)) return rc;
             }
         }
     }
     Chunk& last = chunks[n_chunks - 1];
-    if (!nll_out) run_final(s, last);
+    if (!nll_out && !verify) run_final(s, last);
     for (int i = 1; i < D; i++) {                                          // results become visible on the caller's stream
         KR_HIP(hipEventRecord(s->pf_events[ev_end + i], streams[i]));
         KR_HIP(hipStreamWaitEvent(st, s->pf_events[ev_end + i], 0));
@@ -475,5 +499,122 @@ extern "C" int kr_decode_set_prefill_chunk(kr_decode_store* s, int chunk) {
     if (!s) return kr_fail(KR_ERR_VALUE, "null decode store");
     if (chunk < 0 || chunk > 8192) return kr_fail(KR_ERR_VALUE, "prefill chunk %d out of range [0, 8192]", chunk);
     s->pf_chunk = chunk;
+    return KR_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// exact speculative greedy decoding: verify / commit (docs/design/12-speculative.md)
+// ------------------------------------------------------------------------------------------------
+int kr_spec_pending_fail(kr_decode_store* s) {
+    return s && s->spec_pending ? kr_fail(KR_ERR_STATE, "a kr_decode_verify is pending: kr_decode_commit must come first") : KR_OK;
+}
+
+int kr_spec_refuse(kr_decode_store* s) {
+    if (s->attn_fast || s->gemm_fast || s->decode_fast)
+        return kr_fail(KR_ERR_STATE, "speculative decoding is exact-mode only: the attention mode has tolerance bits set (%d)", s->attn_fast | s->gemm_fast << 1 | s->decode_fast << 2);
+    kr_engine* e = s->eng;
+    if (e->ep) return kr_fail(KR_ERR_STATE, "speculative decoding does not run under expert parallelism");
+    for (const DLayer& L : s->layers) {
+        if (L.mlp == MLP_MOE) {
+            if (s->own_eng || L.moe_layer >= (int)e->layers.size()) return kr_fail(KR_ERR_STATE, "set_moe_store was not called (MoE layer %d has no engine)", L.moe_layer);
+            if (e->layers[L.moe_layer].gguf)
+                return kr_fail(KR_ERR_STATE, "speculative decoding is exact-mode only: MoE layer %d holds native GGUF experts (their prompt pass is tolerance-only)", L.moe_layer);
+        }
+        if (L.attn == ATTN_LA && (L.kd != 4 || (L.dk != 64 && L.dk != 128) || L.dv > 256 || L.dv % 8))
+            return kr_fail(KR_ERR_VALUE, "speculative decoding: linear-attention geometry kd %d dk %d dv %d not covered (kd 4, dk 64 / 128, dv <= 256)", L.kd, L.dk, L.dv);
+    }
+    return KR_OK;
+}
+
+// verify buffers of every linear-attention layer (KR_VERIFY_MAX rows) + the device table the snapshot / rollback kernels walk
+static int spec_prepare(kr_decode_store* s, hipStream_t st) {
+    s->spec_la.clear(); s->spec_la_of.assign(s->layers.size(), -1);
+    size_t total = 0, max_floats = 0;
+    auto take = [&](size_t floats) { const size_t o = total; total += (floats + 63) & ~(size_t)63; return o; };
+    struct Off { size_t qkvz, k, v, ge, be, sr, sc; };
+    std::vector<Off> offs;
+    s->spec_nv_max = 0; s->spec_dv_max = 0; s->spec_has64 = false; s->spec_has128 = false;
+    for (size_t li = 0; li < s->layers.size(); li++) {
+        const DLayer& L = s->layers[li];
+        if (L.attn != ATTN_LA) continue;
+        s->spec_la_of[li] = (int)s->spec_la.size(); s->spec_la.push_back((int)li);
+        const size_t R = KR_VERIFY_MAX, nq = (size_t)s->weights[L.qkvz_wid]->rows, rec = (size_t)L.nv * L.dk * L.dv, conv = (size_t)(2 * L.nk * L.dk + L.nv * L.dv) * 4;
+        Off o;
+        o.qkvz = take(R * nq); o.k = take(R * L.nv * L.dk); o.v = take(R * L.nv * L.dv); o.ge = take(R * L.nv); o.be = take(R * L.nv); o.sr = take(rec); o.sc = take(conv);
+        offs.push_back(o);
+        max_floats = std::max(max_floats, rec + conv);
+        s->spec_nv_max = std::max(s->spec_nv_max, L.nv); s->spec_dv_max = std::max(s->spec_dv_max, L.dv);
+        (L.dk == 64 ? s->spec_has64 : s->spec_has128) = true;
+    }
+    const bool fresh_part = s->spec_part.bytes == 0;
+    if (s->spec_buf.ensure(std::max(total, (size_t)64) * 4) || s->spec_logits.ensure((size_t)KR_VERIFY_MAX * s->vocab * 4) || s->spec_out.ensure(64 * 4) ||
+        s->spec_part.ensure(64 * 4) || s->spec_tab.ensure(std::max(offs.size(), (size_t)1) * sizeof(KrSpecLa)))
+        return kr_fail(KR_ERR_HIP, "hipMalloc of the verify buffers (%zu MiB) failed", (total * 4 + (size_t)KR_VERIFY_MAX * s->vocab * 4) >> 20);
+    if (fresh_part) KR_HIP(hipMemsetAsync(s->spec_part.p, 0, s->spec_part.bytes, st));     // the accept kernel's counter starts at 0 and resets itself
+    std::vector<KrSpecLa> tab(offs.size());
+    float* base = (float*)s->spec_buf.p;
+    for (size_t i = 0; i < offs.size(); i++) {
+        DLayer& L = s->layers[(size_t)s->spec_la[i]];
+        KrSpecLa& E = tab[i];
+        E.recur = (float*)L.recur_state.p; E.conv = (float*)L.conv_state.p; E.snap_recur = base + offs[i].sr; E.snap_conv = base + offs[i].sc;
+        E.qkvz = base + offs[i].qkvz; E.k = base + offs[i].k; E.v = base + offs[i].v; E.gexp = base + offs[i].ge; E.beta = base + offs[i].be;
+        E.nk = L.nk; E.nv = L.nv; E.dk = L.dk; E.dv = L.dv; E.hr = L.nv / L.nk; E.ld_qkvz = s->weights[L.qkvz_wid]->rows;
+    }
+    if (tab.size() != s->spec_host.size() || (!tab.empty() && memcmp(tab.data(), s->spec_host.data(), tab.size() * sizeof(KrSpecLa)))) {
+        KR_HIP(hipStreamSynchronize(st));            // an earlier pass may still read the old table
+        if (!tab.empty()) KR_HIP(hipMemcpy(s->spec_tab.p, tab.data(), tab.size() * sizeof(KrSpecLa), hipMemcpyHostToDevice));
+        s->spec_host = tab;
+    }
+    s->spec_floats = max_floats;
+    return KR_OK;
+}
+
+extern "C" int kr_decode_verify(kr_decode_store* s, const int32_t* tokens, int n_tokens, int start_pos, int32_t* greedy_out, int* n_match_out, void* stream) {
+    if (!s) return kr_fail(KR_ERR_VALUE, "null decode store");
+    if (!s->configured) return kr_fail(KR_ERR_STATE, "Call configure_decode first");
+    if ((int)s->layers.size() != s->n_layers) return kr_fail(KR_ERR_STATE, "finalize_decode was not called");
+    if (int rc = kr_spec_pending_fail(s)) return rc;
+    if (int rc = kr_spec_refuse(s)) return rc;
+    if (!tokens || !greedy_out || !n_match_out) return kr_fail(KR_ERR_VALUE, "kr_decode_verify: null pointer");
+    if (n_tokens < 1 || n_tokens > KR_VERIFY_MAX) return kr_fail(KR_ERR_VALUE, "kr_decode_verify: %d tokens, must be in [1, %d]", n_tokens, KR_VERIFY_MAX);
+    for (int i = 0; i < n_tokens; i++) if (tokens[i] < 0 || tokens[i] >= s->vocab) return kr_fail(KR_ERR_VALUE, "token id %d out of range (vocab %d)", tokens[i], s->vocab);
+    const int end = start_pos + n_tokens;
+    if (start_pos < 0 || (s->kv_max_seq > 0 && end > s->kv_max_seq)) return kr_fail(KR_ERR_VALUE, "verify [%d, %d) does not fit kv_max_seq %d", start_pos, end, s->kv_max_seq);
+    if (s->max_rope_seq > 0 && end > s->max_rope_seq) return kr_fail(KR_ERR_VALUE, "verify [%d, %d) exceeds the rope table (%d)", start_pos, end, s->max_rope_seq);
+    for (const DLayer& L : s->layers)
+        if (L.attn == ATTN_MLA && L.mla_rope_seq < end) return kr_fail(KR_ERR_VALUE, "verify [%d, %d) exceeds the MLA rope table (%d)", start_pos, end, L.mla_rope_seq);
+    KR_HIP(hipSetDevice(s->eng->device));
+    hipStream_t st = kr_pick_stream(s->eng, stream);
+    if (int rc = spec_prepare(s, st)) return rc;
+    const int n_la = (int)s->spec_la.size();
+    const KrSpecLa* tab = (const KrSpecLa*)s->spec_tab.p;
+    if (n_la) kr_launch_spec_snapshot(tab, n_la, (int)s->spec_floats, st);
+    if (int rc = prefill_impl(s, tokens, n_tokens, start_pos, nullptr, nullptr, stream, true)) {
+        if (n_la) kr_launch_spec_rollback(tab, n_la, s->spec_has64, s->spec_has128, s->spec_nv_max, s->spec_dv_max, 0, st);     // back to the snapshot
+        return rc;
+    }
+    int32_t res[KR_VERIFY_MAX + 1];
+    KR_HIP(hipMemcpyAsync(res, s->spec_out.p, (size_t)(n_tokens + 1) * 4, hipMemcpyDeviceToHost, st));
+    KR_HIP(hipStreamSynchronize(st));
+    for (int i = 0; i < n_tokens; i++) greedy_out[i] = res[i];
+    *n_match_out = res[n_tokens];
+    s->spec_pending = true; s->spec_n = n_tokens; s->spec_match = res[n_tokens]; s->spec_st = st; s->last_stream = st;
+    return KR_OK;
+}
+
+extern "C" int kr_decode_commit(kr_decode_store* s, int n_keep) {
+    if (!s) return kr_fail(KR_ERR_VALUE, "null decode store");
+    if (!s->spec_pending) return kr_fail(KR_ERR_STATE, "kr_decode_commit without a pending kr_decode_verify");
+    if (n_keep < 1 || n_keep > s->spec_match + 1) return kr_fail(KR_ERR_VALUE, "n_keep %d out of range [1, %d] (n_match %d)", n_keep, s->spec_match + 1, s->spec_match);
+    KR_HIP(hipSetDevice(s->eng->device));
+    hipStream_t st = s->spec_st;
+    const int n_la = (int)s->spec_la.size();
+    if (n_keep < s->spec_n && n_la)
+        kr_launch_spec_rollback((const KrSpecLa*)s->spec_tab.p, n_la, s->spec_has64, s->spec_has128, s->spec_nv_max, s->spec_dv_max, n_keep, st);
+    const size_t V = (size_t)s->vocab;
+    KR_HIP(hipMemcpyAsync(s->logits.p, (const float*)s->spec_logits.p + (size_t)(n_keep - 1) * V, V * 4, hipMemcpyDeviceToDevice, st));
+    KR_HIP(hipMemcpyAsync(s->tok.p, (const int*)s->spec_out.p + (n_keep - 1), 4, hipMemcpyDeviceToDevice, st));
+    KR_HIP(hipGetLastError());
+    s->spec_pending = false; s->last_stream = st;
     return KR_OK;
 }

@@ -15,6 +15,21 @@ from . import _lib
 from ._lib import check, load_library
 from .engine import KrasisEngine, _addr
 
+# default draft length of generate_lookup: chosen from the verify-cost table of tools/probes/spec_verify_cost.py (docs/design/12-speculative.md)
+LOOKUP_MAX_DRAFT = 8
+
+
+def lookup_draft(history: Sequence[int], ngram_max: int, max_draft: int) -> List[int]:
+    """The draft generate_lookup proposes after `history` (kr_lookup_draft; host only): for g = min(ngram_max, n-1) down to 1, the continuation of
+    the LATEST earlier occurrence of the trailing g-gram that has one, at most max_draft tokens; [] when no g-gram recurs."""
+    lib = load_library()
+    h = (C.c_int32 * max(len(history), 1))(*history)
+    out = (C.c_int32 * max(max_draft, 1))()
+    n = lib.kr_lookup_draft(h, len(history), ngram_max, max_draft, out)
+    if n < 0:
+        check(-n)
+    return list(out[:n])
+
 
 class CpuDecodeStore:
     def __init__(self, group_size: int = 128, parallel: bool = True, norm_bias_one: bool = False, device: Optional[int] = None):
@@ -348,6 +363,37 @@ class CpuDecodeStore:
                                            presence_penalty, rng_seed, out, C.byref(n), None))
         return list(out[: n.value])
 
+    def verify(self, tokens: Sequence[int], start_pos: int):
+        """kr_decode_verify: runs tokens[0] (the last sampled token, not yet consumed) and the draft tokens[1:] through the exact prompt pass at
+        start_pos.. -> (greedy, n_match): greedy[i] = the greedy token after tokens[0..i]; n_match = how many leading drafts equal the greedy choice.
+        Exactly one commit() must follow."""
+        self._need()
+        n = len(tokens)
+        arr = (C.c_int32 * max(n, 1))(*tokens)
+        g = (C.c_int32 * max(n, 1))(); m = C.c_int()
+        check(self._lib.kr_decode_verify(self._h, arr, n, start_pos, g, C.byref(m), None))
+        return list(g[:n]), m.value
+
+    def commit(self, n_keep: int) -> None:
+        """kr_decode_commit: keep the first n_keep tokens of the pending verify (1 <= n_keep <= n_match + 1); the state is then bit-identical to
+        n_keep decode_step calls (logits, last_token, KV rows below start_pos + n_keep, conv and recurrent states)."""
+        self._need()
+        check(self._lib.kr_decode_commit(self._h, n_keep))
+
+    def generate_lookup(self, first_token: int, start_pos: int, max_tokens: int, context: Sequence[int] = (), max_draft: int = LOOKUP_MAX_DRAFT,
+                        ngram_max: int = 3, stop_ids: Sequence[int] = ()) -> List[int]:
+        """Greedy generation with prompt-lookup drafts (kr_decode_generate_lookup): the same tokens and final state as
+        generate_batch(first_token, start_pos, max_tokens, stop_ids=stop_ids) at temperature 0, in fewer model passes when the text repeats
+        `context` (e.g. the prompt) or itself.  last_lookup_stats = {"passes": model passes, "accepted": accepted draft tokens}."""
+        self._need()
+        ctx = (C.c_int32 * max(len(context), 1))(*context)
+        out = (C.c_int * max(max_tokens, 1))(); n = C.c_int(); passes = C.c_int(); acc = C.c_int()
+        stops = (C.c_int * max(len(stop_ids), 1))(*stop_ids)
+        check(self._lib.kr_decode_generate_lookup(self._h, ctx, len(context), first_token, start_pos, max_tokens, max_draft, ngram_max, stops, len(stop_ids),
+                                                  out, C.byref(n), C.byref(passes), C.byref(acc), None))
+        self.last_lookup_stats = {"passes": passes.value, "accepted": acc.value}
+        return list(out[: n.value])
+
     def generate_stream(self, first_token: int, start_position: int, max_tokens: int, temperature: float, top_k: int, top_p: float,
                         stop_ids: Sequence[int], tokenizer, presence_penalty: float, on_token, rng_seed: int = 0) -> int:
         """decode.rs:3611 -- the cancellable loop of the reference's Rust server.  on_token(token_id, text, finish_reason) -> bool (False cancels);
@@ -395,6 +441,10 @@ class CpuDecodeStore:
 
     def read_hidden(self, n: int) -> np.ndarray:
         out = np.empty(n, np.float32); check(self._lib.kr_decode_read_buffer(self._h, 0, _addr(out), n)); return out
+
+    def read_logits(self) -> np.ndarray:
+        """the f32 [vocab] logits the next sample() draws from (last decode_step, prefill or commit)"""
+        out = np.empty(self._vocab, np.float32); check(self._lib.kr_decode_read_buffer(self._h, 6, _addr(out), self._vocab)); return out
 
     def read_router(self, n_experts: int, topk: int):
         """(logits [E], ids [k], weights [k]) the router of the LAST MoE layer produced in the most recent decode step (test / debug aid)"""
