@@ -346,6 +346,30 @@ int kr_decode_generate_lookup(kr_decode_store* s, const int32_t* context, int n_
  * draft length (0: no match), or a negative KR_ERR_* on bad arguments. */
 int kr_lookup_draft(const int32_t* history, int n_history, int ngram_max, int max_draft, int32_t* draft_out);
 
+/* ---- exact batched decode of many sequences held in device slots (docs/design/13-multi-sequence.md).  Row i of a step is bit-identical to
+ * kr_decode_step on that sequence alone (logits, greedy id, the KV row it appends, conv and recurrent state).  Exact mode only: a tolerance bit of
+ * kr_decode_set_attention_mode, MLA layers, native-GGUF MoE layers, expert parallelism and a pending verify are refused; a refused call changes
+ * nothing.  The steps touch only the named slots and their own scratch (never the store's own sequence, logits, last token or decode graph);
+ * reset_state / set_state / fill_state_synthetic / prefill / verify never touch slots; kr_decode_destroy frees them. */
+#define KR_MULTI_MAX 256
+/* n_slots sequences of up to max_seq positions each, zero-initialised (like kr_decode_reset_state); replaces existing slots; n_slots == 0 frees
+   them.  KV element type = the store's at this call.  *bytes_out (may be NULL) = device bytes of all slots. */
+int kr_decode_slots_create(kr_decode_store* s, int n_slots, int max_seq, size_t* bytes_out);
+/* the store's own sequence -> slot: KV rows [0, seq_len) of every GQA layer, conv + recurrent state of every linear-attention layer.
+   0 <= seq_len <= min(store kv_max_seq, slot max_seq) */
+int kr_decode_slot_save(kr_decode_store* s, int slot, int seq_len);
+/* slot -> the store's own sequence (the same parts): decode_step / prefill / verify then continue it at position seq_len */
+int kr_decode_slot_load(kr_decode_store* s, int slot, int seq_len);
+/* row i: slot slots[i] consumes tokens[i] at positions[i].  next_out[i] = first-maximum argmax of row i's logits (the rule of kr_launch_argmax);
+   logits_out (NULL, host or device) = [n][vocab] f32.  Distinct slots, 1 <= n <= KR_MULTI_MAX.  Returns once next_out is written. */
+int kr_decode_step_multi(kr_decode_store* s, int n, const int32_t* slots, const int32_t* tokens, const int32_t* positions,
+                         int32_t* next_out, float* logits_out, void* stream);
+/* greedy generation of n slots together.  Row i's tokens_out[i*max_tokens ...], n_out[i] and its slot's state afterwards are exactly those of
+   kr_decode_generate_greedy(first_tokens[i], start_positions[i], max_tokens, stop ids) run on that sequence alone.  A row that finishes (stop id,
+   max_tokens) leaves the batch; its slot is not stepped again.  start_positions[i] + max_tokens > slot max_seq is refused before the first step. */
+int kr_decode_generate_multi(kr_decode_store* s, int n, const int32_t* slots, const int32_t* first_tokens, const int32_t* start_positions,
+                             int max_tokens, const int* stop_ids, int n_stop, int32_t* tokens_out, int32_t* n_out, void* stream);
+
 /* ---- stand-alone CpuDecodeStore operators (decode.rs:328-1086).  Every pointer may be a host or a device pointer; host buffers are staged and
  * the call returns after the results are back.  Bit-identical to the reference methods (tests/test_standalone_ops_gpu.py against the oracle's
  * kro_op_* restatements); several differ from the decode graph's arithmetic exactly as they do in the reference (scalar loops, libm exp). */

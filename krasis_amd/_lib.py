@@ -12,6 +12,7 @@ KR_OUT_F32, KR_OUT_BF16 = 0, 1
 KR_SCORE_SIGMOID, KR_SCORE_SOFTMAX, KR_SCORE_TOPK_SOFTMAX = 0, 1, 2
 KR_ROUTE_RULE_ENGINE, KR_ROUTE_RULE_DECODE = 0, 1
 KR_VERIFY_MAX, KR_LOOKUP_NGRAM_MAX = 16, 32    # exact speculative decoding: tokens per verify pass, longest indexed n-gram
+KR_MULTI_MAX = 256                             # multi-sequence decode: rows per step
 
 # every symbol include/krasis_hip.h declares (checked by tests/test_abi.py without a GPU)
 SYMBOLS = [
@@ -28,6 +29,7 @@ SYMBOLS = [
     "kr_decode_fused_add_rmsnorm", "kr_decode_rmsnorm", "kr_decode_silu_mul", "kr_decode_fused_shared_expert", "kr_decode_linear_attention_recurrent",
     "kr_decode_gated_rmsnorm_silu", "kr_decode_linear_attention_conv", "kr_decode_store_route_weight", "kr_decode_moe_route", "kr_decode_num_route_weights",
     "kr_decode_weight_bytes", "kr_decode_verify", "kr_decode_commit", "kr_decode_generate_lookup", "kr_lookup_draft",
+    "kr_decode_slots_create", "kr_decode_slot_save", "kr_decode_slot_load", "kr_decode_step_multi", "kr_decode_generate_multi",
 ]
 TOKEN_CB = C.CFUNCTYPE(C.c_int, C.c_int, C.c_int, C.c_void_p)      # kr_token_cb(token, finish_reason, user) -> continue?
 
@@ -169,6 +171,11 @@ def load_library() -> C.CDLL:
     lib.kr_decode_commit.argtypes = [vp, ci]
     lib.kr_decode_generate_lookup.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, vp, ci, vp, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), vp]
     lib.kr_lookup_draft.argtypes = [vp, ci, ci, ci, vp]
+    lib.kr_decode_slots_create.argtypes = [vp, ci, ci, C.POINTER(C.c_size_t)]
+    lib.kr_decode_slot_save.argtypes = [vp, ci, ci]
+    lib.kr_decode_slot_load.argtypes = [vp, ci, ci]
+    lib.kr_decode_step_multi.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp]
+    lib.kr_decode_generate_multi.argtypes = [vp, ci, vp, vp, vp, ci, vp, ci, vp, vp, vp]
     _lib = lib
     return lib
 

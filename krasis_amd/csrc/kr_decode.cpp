@@ -90,6 +90,7 @@ extern "C" void kr_decode_destroy(kr_decode_store* s) {
     for (hipEvent_t ev : s->gen_ev) if (ev) (void)hipEventDestroy(ev);
     if (s->gen_ring) (void)hipHostFree(s->gen_ring);
     for (hipStream_t ps : s->pf_side) { (void)hipStreamSynchronize(ps); (void)hipStreamDestroy(ps); }
+    s->multi.reset();                   // sequence slots + the multi-sequence step's buffers
     if (s->own_eng) kr_engine_destroy(s->eng);
     delete s;
     (void)hipGetLastError();      // a failure while tearing down must not surface as the "last error" of an unrelated later call

@@ -7,6 +7,7 @@
 
 #include "kr_decode_ops.h"
 #include "kr_engine_internal.h"
+#include "kr_multi.h"
 #include "kr_spec.h"
 
 struct DWeight { MatSet ms; int rows = 0, cols = 0; };
@@ -29,6 +30,17 @@ struct DLayer {
     // MLP
     int moe_layer = -1, sgu_wid = -1, sd_wid = -1, sg_wid = -1;
     int gate_wid = -1, up_wid = -1, down_wid = -1;
+};
+
+// sequence slots of the multi-sequence step (kr_decode_multi.cpp, docs/design/13-multi-sequence.md): per store layer one buffer of n slots --
+// linear attention: conv state [n][conv_dim][4] (conv) and recurrent state [n][nv][dk][dv] (recur); GQA: K / V caches [n][max_seq][nkv][hd] (conv / recur)
+struct kr_multi_state {
+    int n_slots = 0, max_seq = 0, kv_fp8 = 0;
+    std::vector<DevBuf> a, b;                  // per layer: LA conv / recurrent state, GQA K / V
+    std::vector<size_t> a_stride, b_stride;    // per layer: bytes per slot
+    DevBuf rows, ids, logits, scores, scratch; // step: [slots | tokens | positions] (device), greedy ids, [n][vocab] logits, attention scores, the arena
+    hipEvent_t ev = nullptr;
+    ~kr_multi_state() { if (ev) (void)hipEventDestroy(ev); }
 };
 
 struct kr_standalone_state;   // kr_decode_standalone.cpp: staging buffers, stand-alone router gates, cancel flag, elapsed time
@@ -74,6 +86,7 @@ struct kr_decode_store {
     // exact speculative decoding (kr_decode_verify / kr_decode_commit, kr_decode_prefill.cpp): per linear-attention layer the snapshot of its states and
     // what a verify pass fed the recurrence (spec_la[i] = the store layer of table entry i), the all-row logits, [greedy ids, n_match], accept partials
     std::vector<int> spec_la, spec_la_of; std::vector<KrSpecLa> spec_host; DevBuf spec_buf, spec_tab, spec_logits, spec_out, spec_part;
+    std::unique_ptr<kr_multi_state> multi;       // sequence slots + the multi-sequence step's buffers (kr_decode_slots_create)
     bool spec_pending = false; int spec_n = 0, spec_match = 0, spec_nv_max = 0, spec_dv_max = 0; bool spec_has64 = false, spec_has128 = false; size_t spec_floats = 0; hipStream_t spec_st = nullptr;
     // captured graph of one decode step
     hipGraphExec_t graph_exec = nullptr; bool graph_ok = false; bool use_graph = true;
@@ -92,4 +105,7 @@ void kr_standalone_release(kr_decode_store* s);
 int kr_spec_refuse(kr_decode_store* s);          // kr_decode_prefill.cpp: KR_OK when exact speculative decoding can run on this store
 int kr_spec_pending_fail(kr_decode_store* s);    // KR_ERR_STATE while a verify waits for its commit
 int kr_standalone_cancelled(kr_decode_store* s);
+// kr_decode_prefill.cpp: the layers + final norm + lm_head GEMM of the multi-sequence step, one row per slot, on `st` in s->multi's arena;
+// d_rows = [slots | tokens | positions] on the device, logits -> s->multi->logits [n][vocab]
+int kr_multi_pass(kr_decode_store* s, int n, const int32_t* d_rows, int max_pos, hipStream_t st);
 void kr_standalone_set_elapsed(kr_decode_store* s, double sec);   // kr_engine.cpp: per (group, column) nibble sums for the int8-MFMA GEMM

@@ -32,6 +32,7 @@ struct Scratch {   // carved from one allocation per arena (grown on demand)
     int8_t *xh, *xl, *yh, *yl; float *xs, *ys;
     uint16_t *xf, *yf; float *xfm, *yfm;     // KR_GEMM_FAST: the same two activation slots as f16 rows + row multipliers (kr_prefill_h.hip)
     uint16_t* xb; int32_t* ids; float* w;
+    float* cv;                               // multi-sequence step: conv + SiLU outputs [rows][conv_dim] of a linear-attention layer
 };
 struct Act { const int8_t* h; const int8_t* l; const float* s; const uint16_t* f; const float* fm; };   // one GEMM input: INT16 digits or f16 rows
 Act X(const Scratch& B) { return Act{B.xh, B.xl, B.xs, B.xf, B.xfm}; }
@@ -40,6 +41,7 @@ struct Chunk {      // one chunk of the prompt in flight: its arena, stream and 
     Scratch B; float* scores; const int* tok; int Cc, pos0, set; bool first, add_is_emb; hipStream_t st;
     KrPfSync sy;      // this (chunk, layer)'s hand-overs with the previous / next chunk (set by the scheduler before every run_layer)
     bool verify = false;      // kr_decode_verify's pass: linear-attention layers write their recurrence inputs into the store's verify buffers (kr_spec.h)
+    const int32_t* m_slots = nullptr; const int32_t* m_pos = nullptr; int m_sc_ld = 0;   // the multi-sequence step: row b = slot m_slots[b] at m_pos[b] (device)
 };
 size_t al(size_t n) { return (n + 255) & ~(size_t)255; }
 }  // namespace
@@ -102,43 +104,68 @@ static int run_layer(kr_decode_store* s, Chunk& cx, size_t li) {
         float* qkvz = vc ? (float*)vc->qkvz : B.pa;
         { const int wids[2] = {L.qkvz_wid, L.ba_wid}; float* outs[2] = {qkvz, B.pb}; const int lds[2] = {nq, nb};
           if (int rc = pf_gemm_multi(s, wids, outs, lds, 2, X(B), Cc, st)) return rc; }
-        KrPfmLaArgs a{};
-        a.qkvz = qkvz; a.ld_qkvz = nq; a.ba = B.pb; a.ld_ba = nb; a.conv_state = (float*)L.conv_state.p; a.conv_w = (const float*)L.conv_w.p;
-        a.a_log = (const float*)L.a_log.p; a.dt_bias = (const float*)L.dt_bias.p; a.scale = L.la_scale; a.q = B.q; a.k = B.k; a.v = B.v; a.z = B.z;
-        a.gexp = B.gexp; a.beta = B.beta; a.nk = L.nk; a.nv = L.nv; a.dk = L.dk; a.dv = L.dv; a.hr = L.nv / L.nk;
-        if (vc) { a.k = (float*)vc->k; a.v = (float*)vc->v; a.gexp = (float*)vc->gexp; a.beta = (float*)vc->beta; }
-        a.lac = B.lac; a.fast = s->attn_fast; a.conv_fused = s->opt_la_conv_fused;
-        if (kr_launch_pfm_la(a, (float*)L.recur_state.p, B.recur, (const float*)L.la_norm_w.p, B.attn, Cc, s->eps, st, &cx.sy))
-            return kr_fail(KR_ERR_VALUE, "unsupported linear-attention geometry");
+        if (cx.m_slots) {      // multi-sequence step: every row advances its own slot's conv / recurrent state (kr_multi.hip)
+            kr_multi_state& M = *s->multi;
+            KrMultiLaArgs m{};
+            m.slots = cx.m_slots; m.qkvz = qkvz; m.ld_qkvz = nq; m.ba = B.pb; m.ld_ba = nb;
+            m.conv_w = (const float*)L.conv_w.p; m.a_log = (const float*)L.a_log.p; m.dt_bias = (const float*)L.dt_bias.p; m.norm_w = (const float*)L.la_norm_w.p;
+            m.conv_state = (float*)M.a[li].p; m.conv_stride = M.a_stride[li] / 4; m.recur = (float*)M.b[li].p; m.recur_stride = M.b_stride[li] / 4;
+            m.conv_out = B.cv; m.out = B.attn; m.ld_out = oc; m.nk = L.nk; m.nv = L.nv; m.dk = L.dk; m.dv = L.dv; m.hr = L.nv / L.nk; m.scale = L.la_scale; m.eps = s->eps;
+            if (oc != L.nv * L.dv) return kr_fail(KR_ERR_VALUE, "out_proj cols %d != nv*dv", oc);
+            if (kr_launch_multi_la(m, Cc, st)) return kr_fail(KR_ERR_VALUE, "unsupported linear-attention geometry for the multi-sequence step");
+        } else {
+            KrPfmLaArgs a{};
+            a.qkvz = qkvz; a.ld_qkvz = nq; a.ba = B.pb; a.ld_ba = nb; a.conv_state = (float*)L.conv_state.p; a.conv_w = (const float*)L.conv_w.p;
+            a.a_log = (const float*)L.a_log.p; a.dt_bias = (const float*)L.dt_bias.p; a.scale = L.la_scale; a.q = B.q; a.k = B.k; a.v = B.v; a.z = B.z;
+            a.gexp = B.gexp; a.beta = B.beta; a.nk = L.nk; a.nv = L.nv; a.dk = L.dk; a.dv = L.dv; a.hr = L.nv / L.nk;
+            if (vc) { a.k = (float*)vc->k; a.v = (float*)vc->v; a.gexp = (float*)vc->gexp; a.beta = (float*)vc->beta; }
+            a.lac = B.lac; a.fast = s->attn_fast; a.conv_fused = s->opt_la_conv_fused;
+            if (kr_launch_pfm_la(a, (float*)L.recur_state.p, B.recur, (const float*)L.la_norm_w.p, B.attn, Cc, s->eps, st, &cx.sy))
+                return kr_fail(KR_ERR_VALUE, "unsupported linear-attention geometry");
+        }
         if (oc != L.nv * L.dv) return kr_fail(KR_ERR_VALUE, "out_proj cols %d != nv*dv", oc);
         pf_rows(s, B.attn, Cc, oc, oc, B, true, st);
         if (int rc = pf_gemm(s, L.out_wid, Y(B), Cc, B.hid, H, st)) return rc;
     } else if (L.attn == ATTN_GQA) {
-        if (!L.kv_k.p) return kr_fail(KR_ERR_STATE, "set_decode_state was not called (no KV cache for layer %zu)", li);
+        if (!L.kv_k.p && !cx.m_slots) return kr_fail(KR_ERR_STATE, "set_decode_state was not called (no KV cache for layer %zu)", li);
         const int nq = s->weights[L.q_wid]->rows, nk_ = s->weights[L.k_wid]->rows, nv_ = s->weights[L.v_wid]->rows, oc = s->weights[L.o_wid]->cols;
         { const int wids[3] = {L.q_wid, L.k_wid, L.v_wid}; float* outs[3] = {B.pa, B.pb, B.pc}; const int lds[3] = {nq, nk_, nv_};
           if (int rc = pf_gemm_multi(s, wids, outs, lds, 3, X(B), Cc, st)) return rc; }
-        KrPfmGqaArgs a{};
-        a.q_in = B.pa; a.k_in = B.pb; a.v_in = B.pc; a.ld_q = nq; a.ld_k = nk_; a.ld_v = nv_;
-        a.q_norm = L.q_norm_len ? (const float*)L.q_norm.p : nullptr; a.k_norm = L.k_norm_len ? (const float*)L.k_norm.p : nullptr;
-        a.q_norm_per_head = L.q_norm_len == L.nh * L.hd; a.k_norm_per_head = L.k_norm_len == L.nkv * L.hd;
-        a.rope_cos = (const float*)s->rope_cos.p; a.rope_sin = (const float*)s->rope_sin.p; a.rope_half = s->rope_half;
-        a.k_cache = L.kv_k.p; a.v_cache = L.kv_v.p; a.kv_fp8 = s->kv_fp8; a.q_out = B.q; a.gate = B.gate; a.attn_out = B.attn;
-        a.gated = L.gated; a.nh = L.nh; a.nkv = L.nkv; a.hd = L.hd; a.pos0 = pos0; a.eps = s->eps; a.sm_scale = L.sm_scale;
-        if (s->max_rope_seq > 0 && pos0 + Cc > s->max_rope_seq) return kr_fail(KR_ERR_VALUE, "prompt exceeds the rope table (%d)", s->max_rope_seq);
-        bool flash = false, flash_tried = false;
-        if (s->attn_fast && kr_pfm_gqa_flash_ok(L.nh, L.nkv, L.hd)) {      // tolerance mode: flash attention on the matrix cores (same prep launch)
-            kr_launch_pfm_gqa_prep(a, Cc, st);
-            kr_pf_wait(st, cx.sy.wait_b); kr_pf_rec(st, cx.sy.rec_b);      // own rows appended; the previous chunks' rows are read from here on
-            flash = 0 == kr_launch_pfm_gqa_flash(a, Cc, st);
-            flash_tried = true;
-        }
-        if (!flash) {
-            if (flash_tried) return kr_fail(KR_ERR_HIP, "KR_ATTN_FAST: the flash-attention launch was refused (LDS window of head_dim %d)", L.hd);
-            if (!cx.scores) return kr_fail(KR_ERR_STATE, "internal: no score scratch for the exact attention passes");
-            const int sc_ld = (pos0 + Cc + 63) & ~63;
-            float* scp = cx.scores;   // this chunk's arena (chunks in flight on other streams have their own)
-            if (kr_launch_pfm_gqa(a, Cc, scp, sc_ld, scp + (size_t)Cc * L.nh * sc_ld, st, &cx.sy)) return kr_fail(KR_ERR_VALUE, "unsupported GQA geometry for the prompt pass");
+        if (cx.m_slots) {      // multi-sequence step: each row appends to and attends over its own slot at its own position (kr_multi.hip)
+            kr_multi_state& M = *s->multi;
+            if (oc != L.nh * L.hd) return kr_fail(KR_ERR_VALUE, "o_proj cols %d != nh*hd", oc);
+            KrMultiGqaArgs m{};
+            m.slots = cx.m_slots; m.positions = cx.m_pos; m.q_in = B.pa; m.k_in = B.pb; m.v_in = B.pc; m.ld_q = nq; m.ld_k = nk_; m.ld_v = nv_;
+            m.q_norm = L.q_norm_len ? (const float*)L.q_norm.p : nullptr; m.k_norm = L.k_norm_len ? (const float*)L.k_norm.p : nullptr;
+            m.q_norm_per_head = L.q_norm_len == L.nh * L.hd; m.k_norm_per_head = L.k_norm_len == L.nkv * L.hd;
+            m.rope_cos = (const float*)s->rope_cos.p; m.rope_sin = (const float*)s->rope_sin.p; m.rope_half = s->rope_half;
+            m.k_cache = M.a[li].p; m.v_cache = M.b[li].p; m.slot_elems = M.a_stride[li] / (M.kv_fp8 ? 1 : 2); m.kv_fp8 = M.kv_fp8;
+            m.q_out = B.q; m.gate = B.gate; m.attn_out = B.attn; m.scores = (float*)M.scores.p; m.sc_ld = cx.m_sc_ld;
+            m.gated = L.gated; m.nh = L.nh; m.nkv = L.nkv; m.hd = L.hd; m.eps = s->eps; m.sm_scale = L.sm_scale;
+            if (kr_launch_multi_gqa(m, Cc, st)) return kr_fail(KR_ERR_VALUE, "unsupported GQA geometry for the multi-sequence step");
+        } else {
+            KrPfmGqaArgs a{};
+            a.q_in = B.pa; a.k_in = B.pb; a.v_in = B.pc; a.ld_q = nq; a.ld_k = nk_; a.ld_v = nv_;
+            a.q_norm = L.q_norm_len ? (const float*)L.q_norm.p : nullptr; a.k_norm = L.k_norm_len ? (const float*)L.k_norm.p : nullptr;
+            a.q_norm_per_head = L.q_norm_len == L.nh * L.hd; a.k_norm_per_head = L.k_norm_len == L.nkv * L.hd;
+            a.rope_cos = (const float*)s->rope_cos.p; a.rope_sin = (const float*)s->rope_sin.p; a.rope_half = s->rope_half;
+            a.k_cache = L.kv_k.p; a.v_cache = L.kv_v.p; a.kv_fp8 = s->kv_fp8; a.q_out = B.q; a.gate = B.gate; a.attn_out = B.attn;
+            a.gated = L.gated; a.nh = L.nh; a.nkv = L.nkv; a.hd = L.hd; a.pos0 = pos0; a.eps = s->eps; a.sm_scale = L.sm_scale;
+            if (s->max_rope_seq > 0 && pos0 + Cc > s->max_rope_seq) return kr_fail(KR_ERR_VALUE, "prompt exceeds the rope table (%d)", s->max_rope_seq);
+            bool flash = false, flash_tried = false;
+            if (s->attn_fast && kr_pfm_gqa_flash_ok(L.nh, L.nkv, L.hd)) {      // tolerance mode: flash attention on the matrix cores (same prep launch)
+                kr_launch_pfm_gqa_prep(a, Cc, st);
+                kr_pf_wait(st, cx.sy.wait_b); kr_pf_rec(st, cx.sy.rec_b);      // own rows appended; the previous chunks' rows are read from here on
+                flash = 0 == kr_launch_pfm_gqa_flash(a, Cc, st);
+                flash_tried = true;
+            }
+            if (!flash) {
+                if (flash_tried) return kr_fail(KR_ERR_HIP, "KR_ATTN_FAST: the flash-attention launch was refused (LDS window of head_dim %d)", L.hd);
+                if (!cx.scores) return kr_fail(KR_ERR_STATE, "internal: no score scratch for the exact attention passes");
+                const int sc_ld = (pos0 + Cc + 63) & ~63;
+                float* scp = cx.scores;   // this chunk's arena (chunks in flight on other streams have their own)
+                if (kr_launch_pfm_gqa(a, Cc, scp, sc_ld, scp + (size_t)Cc * L.nh * sc_ld, st, &cx.sy)) return kr_fail(KR_ERR_VALUE, "unsupported GQA geometry for the prompt pass");
+            }
         }
         if (oc != L.nh * L.hd) return kr_fail(KR_ERR_VALUE, "o_proj cols %d != nh*hd", oc);
         pf_rows(s, B.attn, Cc, oc, oc, B, true, st);
@@ -276,6 +303,91 @@ static int run_final_verify(kr_decode_store* s, Chunk& cx) {
     return KR_OK;
 }
 
+struct PfLayout {   // one arena: byte offsets of the Scratch buffers, total bytes; score-scratch rows (exact attention) and chunked-LA floats
+    size_t total = 0, sc_rows = 0, lac_floats = 0;
+    size_t o_res, o_hid, o_nrm, o_pa, o_pb, o_pc, o_q, o_k, o_v, o_z, o_ge, o_be, o_rec, o_att, o_gate, o_moe, o_sh, o_gv, o_sgu, o_xh, o_xl, o_xs, o_yh,
+           o_yl, o_ys, o_xb, o_ids, o_w, o_lg, o_lac, o_xf, o_xfm, o_yf, o_yfm, o_cv;
+};
+// geometry of the widest layer -> the arena of a chunk of C rows; nibble sums of every weight the GEMMs will touch (lm_rows: the all-row lm_head GEMM
+// too); multi: the conv-output rows of the multi-sequence step
+static int pf_layout(kr_decode_store* s, size_t C, bool lm_rows, bool multi, hipStream_t st, PfLayout& Lo) {
+    kr_engine* e = s->eng;
+    const size_t H = (size_t)s->hidden;
+    size_t cvd = 0, pa = H, pb = 64, pc = 64, qd = 64, kd = 64, vd = 64, zd = 64, nvmax = 1, ad = H, sid = 0, kmax = H, sc_rows = 0;
+    std::vector<int> wids;
+    for (auto& Ly : s->layers) {
+        if (Ly.attn == ATTN_LA) {
+            if (multi) cvd = std::max(cvd, (size_t)(2 * Ly.nk * Ly.dk + Ly.nv * Ly.dv));
+            pa = std::max(pa, (size_t)s->weights[Ly.qkvz_wid]->rows); pb = std::max(pb, (size_t)s->weights[Ly.ba_wid]->rows);
+            qd = std::max(qd, (size_t)Ly.nv * Ly.dk); kd = std::max(kd, (size_t)Ly.nv * Ly.dk); vd = std::max(vd, (size_t)Ly.nv * Ly.dv); zd = std::max(zd, (size_t)Ly.nv * Ly.dv);
+            nvmax = std::max(nvmax, (size_t)Ly.nv); ad = std::max(ad, (size_t)s->weights[Ly.out_wid]->cols);
+            for (int w : {Ly.qkvz_wid, Ly.ba_wid, Ly.out_wid}) wids.push_back(w);
+        } else if (Ly.attn == ATTN_GQA) {
+            pa = std::max(pa, (size_t)s->weights[Ly.q_wid]->rows); pb = std::max(pb, (size_t)s->weights[Ly.k_wid]->rows); pc = std::max(pc, (size_t)s->weights[Ly.v_wid]->rows);
+            qd = std::max(qd, (size_t)Ly.nh * Ly.hd); zd = std::max(zd, (size_t)Ly.nh * Ly.hd); ad = std::max(ad, (size_t)s->weights[Ly.o_wid]->cols);
+            // the score scratch (rows x context f32, per arena) serves the EXACT attention passes only: under KR_ATTN_FAST the flash kernel has none.  Sizing it
+            // regardless made a 49 863-token tolerance pass allocate 3 x 13.5 GB it never touched (VERDICT r3 weak #5: 16.7 k instead of ~45 k tok/s)
+            if (!(s->attn_fast && kr_pfm_gqa_flash_ok(Ly.nh, Ly.nkv, Ly.hd))) sc_rows = std::max(sc_rows, (size_t)Ly.nh);
+            for (int w : {Ly.q_wid, Ly.k_wid, Ly.v_wid, Ly.o_wid}) wids.push_back(w);
+        } else if (Ly.attn == ATTN_MLA) {
+            const size_t nq = (size_t)Ly.nh * (Ly.nd + Ly.rd);
+            pa = std::max(pa, nq); pb = std::max(pb, (size_t)s->weights[Ly.kva_wid]->rows);
+            qd = std::max(qd, (size_t)Ly.nh * Ly.klr); vd = std::max(vd, (size_t)Ly.nh * Ly.klr); zd = std::max(zd, (size_t)Ly.nh * Ly.rd);
+            ad = std::max(ad, (size_t)s->weights[Ly.o_wid]->cols);
+            if (!s->attn_fast && kr_mla_exact_mfma_ok(Ly.nh, Ly.klr, Ly.rd)) sc_rows = std::max(sc_rows, (size_t)Ly.nh);     // score scratch of the exact matrix-core passes
+            wids.push_back(Ly.kva_wid); wids.push_back(Ly.o_wid);
+            if (Ly.mq_wid >= 0) wids.push_back(Ly.mq_wid);
+            else { pc = std::max(pc, (size_t)s->weights[Ly.mqa_wid]->rows); kmax = std::max(kmax, (size_t)s->weights[Ly.mqa_wid]->rows); wids.push_back(Ly.mqa_wid); wids.push_back(Ly.mqb_wid); }
+        }
+        if (Ly.mlp == MLP_MOE) {
+            if (Ly.sgu_wid >= 0) { sid = std::max(sid, (size_t)s->weights[Ly.sgu_wid]->rows); kmax = std::max(kmax, (size_t)s->weights[Ly.sd_wid]->cols); wids.push_back(Ly.sgu_wid); wids.push_back(Ly.sd_wid); }
+            if (Ly.sgu_wid >= 0 && Ly.sg_wid >= 0) wids.push_back(Ly.sg_wid);
+            if (s->own_eng || Ly.moe_layer >= (int)e->layers.size()) return kr_fail(KR_ERR_STATE, "set_moe_store was not called (MoE layer %d has no engine)", Ly.moe_layer);
+            Layer& EL = e->layers[Ly.moe_layer];
+            if (int rc = kr_ensure_gate_row(e, Ly.moe_layer)) return rc;
+            if (int rc = kr_ensure_wsum(e, EL.w13, st)) return rc;
+            if (int rc = kr_ensure_wsum(e, EL.w2, st)) return rc;
+            if (int rc = kr_moe_prefill_prepare(e, Ly.moe_layer, s->gemm_fast ? 1 : 0, 1, st)) return rc;     // native-GGUF layers: block sums / tolerance copies, before any chunk stream runs
+        } else if (Ly.mlp == MLP_DENSE) {
+            sid = std::max(sid, 2 * (size_t)s->weights[Ly.down_wid]->cols); kmax = std::max(kmax, (size_t)s->weights[Ly.down_wid]->cols);
+            for (int w : {Ly.gate_wid, Ly.up_wid, Ly.down_wid}) wids.push_back(w);
+        }
+    }
+    if (lm_rows) wids.push_back(s->lm_head);
+    for (int w : wids) {
+        DWeight& W = *s->weights[w];
+        if (int rc = kr_ensure_wsum(e, W.ms, st)) return rc;
+    }
+    kmax = std::max(kmax, ad);
+    if (s->gemm_fast && C * std::max(kmax, (size_t)H) * 2 >= (1ull << 32)) return kr_fail(KR_ERR_VALUE, "KR_GEMM_FAST: chunk of %zu tokens x %zu values exceeds 4 GiB of f16 activations; lower the chunk", C, std::max(kmax, (size_t)H));
+    size_t& total = Lo.total; size_t& lac_floats = Lo.lac_floats; Lo.sc_rows = sc_rows;
+    if (s->attn_fast)
+        for (auto& Ly : s->layers) if (Ly.attn == ATTN_LA && kr_pfm_la_chunk_ok(Ly.dk, Ly.dv, (int)C)) lac_floats = std::max(lac_floats, kr_pfm_la_chunk_scratch_floats((int)C, Ly.nv));
+    auto take = [&](size_t bytes) { const size_t o = total; total += al(bytes); return o; };
+    Lo.o_res = take(C * H * 4); Lo.o_hid = take(C * H * 4); Lo.o_nrm = take(C * H * 4); Lo.o_pa = take(C * pa * 4); Lo.o_pb = take(C * pb * 4); Lo.o_pc = take(C * pc * 4);
+    Lo.o_q = take(C * qd * 4); Lo.o_k = take(C * kd * 4); Lo.o_v = take(C * vd * 4); Lo.o_z = take(C * zd * 4); Lo.o_ge = take(C * nvmax * 4); Lo.o_be = take(C * nvmax * 4);
+    Lo.o_rec = take(C * vd * 4); Lo.o_att = take(C * ad * 4); Lo.o_gate = take(C * zd * 4); Lo.o_moe = take(C * H * 4); Lo.o_sh = take(C * H * 4); Lo.o_gv = take(C * 4);
+    Lo.o_sgu = take(C * std::max(sid, (size_t)64) * 4); Lo.o_xh = take(C * H); Lo.o_xl = take(C * H); Lo.o_xs = take(C * (H / 128) * 4); Lo.o_yh = take(C * kmax);
+    Lo.o_yl = take(C * kmax); Lo.o_ys = take(C * (kmax / 128 + 1) * 4); Lo.o_xb = take(C * H * 2); Lo.o_ids = take(C * 32 * 4); Lo.o_w = take(C * 32 * 4);
+    Lo.o_lg = take(C * (size_t)std::max(e->r_ne, 64) * 4); Lo.o_lac = take(lac_floats * 4);
+    Lo.o_xf = take(C * H * 2); Lo.o_xfm = take(C * 4); Lo.o_yf = take(C * kmax * 2); Lo.o_yfm = take(C * 4);
+    Lo.o_cv = take(C * cvd * 4);      // multi-sequence step: conv outputs of every linear-attention channel (0 bytes in the prompt pass)
+    return KR_OK;
+}
+static Scratch pf_carve(const PfLayout& Lo, char* base) {
+    Scratch B{};
+    B.res = (float*)(base + Lo.o_res); B.hid = (float*)(base + Lo.o_hid); B.normed = (float*)(base + Lo.o_nrm); B.pa = (float*)(base + Lo.o_pa); B.pb = (float*)(base + Lo.o_pb);
+    B.pc = (float*)(base + Lo.o_pc); B.q = (float*)(base + Lo.o_q); B.k = (float*)(base + Lo.o_k); B.v = (float*)(base + Lo.o_v); B.z = (float*)(base + Lo.o_z);
+    B.gexp = (float*)(base + Lo.o_ge); B.beta = (float*)(base + Lo.o_be); B.recur = (float*)(base + Lo.o_rec); B.attn = (float*)(base + Lo.o_att); B.gate = (float*)(base + Lo.o_gate);
+    B.moe = (float*)(base + Lo.o_moe); B.sh = (float*)(base + Lo.o_sh); B.gv = (float*)(base + Lo.o_gv); B.sgu = (float*)(base + Lo.o_sgu); B.xh = (int8_t*)(base + Lo.o_xh);
+    B.xl = (int8_t*)(base + Lo.o_xl); B.xs = (float*)(base + Lo.o_xs); B.yh = (int8_t*)(base + Lo.o_yh); B.yl = (int8_t*)(base + Lo.o_yl); B.ys = (float*)(base + Lo.o_ys);
+    B.xb = (uint16_t*)(base + Lo.o_xb); B.ids = (int32_t*)(base + Lo.o_ids); B.w = (float*)(base + Lo.o_w); B.logits = (float*)(base + Lo.o_lg);
+    B.lac = Lo.lac_floats ? (float*)(base + Lo.o_lac) : nullptr;
+    B.xf = (uint16_t*)(base + Lo.o_xf); B.xfm = (float*)(base + Lo.o_xfm); B.yf = (uint16_t*)(base + Lo.o_yf); B.yfm = (float*)(base + Lo.o_yfm);
+    B.cv = (float*)(base + Lo.o_cv);
+    return B;
+}
+
 static int prefill_impl(kr_decode_store* s, const int32_t* tokens, int n_tokens, int start_pos, float* logits_out, float* nll_out, void* stream, bool verify = false) {
     if (!s) return kr_fail(KR_ERR_VALUE, "null decode store");
     if (!s->configured) return kr_fail(KR_ERR_STATE, "Call configure_decode first");
@@ -312,65 +424,10 @@ static int prefill_impl(kr_decode_store* s, const int32_t* tokens, int n_tokens,
     const int n_chunks = (n_tokens + CH - 1) / CH, n_arenas = std::min(e->ep ? n_chunks_max : n_chunks, depth), D = n_arenas;
     const int L = (int)s->layers.size();
 
-    // ---- geometry of the widest layer -> scratch sizes (floats per token); nibble sums of every weight the GEMMs will touch
-    size_t pa = H, pb = 64, pc = 64, qd = 64, kd = 64, vd = 64, zd = 64, nvmax = 1, ad = H, sid = 0, kmax = H, sc_rows = 0;
-    std::vector<int> wids;
-    for (auto& Ly : s->layers) {
-        if (Ly.attn == ATTN_LA) {
-            pa = std::max(pa, (size_t)s->weights[Ly.qkvz_wid]->rows); pb = std::max(pb, (size_t)s->weights[Ly.ba_wid]->rows);
-            qd = std::max(qd, (size_t)Ly.nv * Ly.dk); kd = std::max(kd, (size_t)Ly.nv * Ly.dk); vd = std::max(vd, (size_t)Ly.nv * Ly.dv); zd = std::max(zd, (size_t)Ly.nv * Ly.dv);
-            nvmax = std::max(nvmax, (size_t)Ly.nv); ad = std::max(ad, (size_t)s->weights[Ly.out_wid]->cols);
-            for (int w : {Ly.qkvz_wid, Ly.ba_wid, Ly.out_wid}) wids.push_back(w);
-        } else if (Ly.attn == ATTN_GQA) {
-            pa = std::max(pa, (size_t)s->weights[Ly.q_wid]->rows); pb = std::max(pb, (size_t)s->weights[Ly.k_wid]->rows); pc = std::max(pc, (size_t)s->weights[Ly.v_wid]->rows);
-            qd = std::max(qd, (size_t)Ly.nh * Ly.hd); zd = std::max(zd, (size_t)Ly.nh * Ly.hd); ad = std::max(ad, (size_t)s->weights[Ly.o_wid]->cols);
-            // the score scratch (rows x context f32, per arena) serves the EXACT attention passes only: under KR_ATTN_FAST the flash kernel has none.  Sizing it
-            // regardless made a 49 863-token tolerance pass allocate 3 x 13.5 GB it never touched (VERDICT r3 weak #5: 16.7 k instead of ~45 k tok/s)
-            if (!(s->attn_fast && kr_pfm_gqa_flash_ok(Ly.nh, Ly.nkv, Ly.hd))) sc_rows = std::max(sc_rows, (size_t)Ly.nh);
-            for (int w : {Ly.q_wid, Ly.k_wid, Ly.v_wid, Ly.o_wid}) wids.push_back(w);
-        } else if (Ly.attn == ATTN_MLA) {
-            const size_t nq = (size_t)Ly.nh * (Ly.nd + Ly.rd);
-            pa = std::max(pa, nq); pb = std::max(pb, (size_t)s->weights[Ly.kva_wid]->rows);
-            qd = std::max(qd, (size_t)Ly.nh * Ly.klr); vd = std::max(vd, (size_t)Ly.nh * Ly.klr); zd = std::max(zd, (size_t)Ly.nh * Ly.rd);
-            ad = std::max(ad, (size_t)s->weights[Ly.o_wid]->cols);
-            if (!s->attn_fast && kr_mla_exact_mfma_ok(Ly.nh, Ly.klr, Ly.rd)) sc_rows = std::max(sc_rows, (size_t)Ly.nh);     // score scratch of the exact matrix-core passes
-            wids.push_back(Ly.kva_wid); wids.push_back(Ly.o_wid);
-            if (Ly.mq_wid >= 0) wids.push_back(Ly.mq_wid);
-            else { pc = std::max(pc, (size_t)s->weights[Ly.mqa_wid]->rows); kmax = std::max(kmax, (size_t)s->weights[Ly.mqa_wid]->rows); wids.push_back(Ly.mqa_wid); wids.push_back(Ly.mqb_wid); }
-        }
-        if (Ly.mlp == MLP_MOE) {
-            if (Ly.sgu_wid >= 0) { sid = std::max(sid, (size_t)s->weights[Ly.sgu_wid]->rows); kmax = std::max(kmax, (size_t)s->weights[Ly.sd_wid]->cols); wids.push_back(Ly.sgu_wid); wids.push_back(Ly.sd_wid); }
-            if (Ly.sgu_wid >= 0 && Ly.sg_wid >= 0) wids.push_back(Ly.sg_wid);
-            if (s->own_eng || Ly.moe_layer >= (int)e->layers.size()) return kr_fail(KR_ERR_STATE, "set_moe_store was not called (MoE layer %d has no engine)", Ly.moe_layer);
-            Layer& EL = e->layers[Ly.moe_layer];
-            if (int rc = kr_ensure_gate_row(e, Ly.moe_layer)) return rc;
-            if (int rc = kr_ensure_wsum(e, EL.w13, st)) return rc;
-            if (int rc = kr_ensure_wsum(e, EL.w2, st)) return rc;
-            if (int rc = kr_moe_prefill_prepare(e, Ly.moe_layer, s->gemm_fast ? 1 : 0, 1, st)) return rc;     // native-GGUF layers: block sums / tolerance copies, before any chunk stream runs
-        } else if (Ly.mlp == MLP_DENSE) {
-            sid = std::max(sid, 2 * (size_t)s->weights[Ly.down_wid]->cols); kmax = std::max(kmax, (size_t)s->weights[Ly.down_wid]->cols);
-            for (int w : {Ly.gate_wid, Ly.up_wid, Ly.down_wid}) wids.push_back(w);
-        }
-    }
-    if (nll_out || verify) wids.push_back(s->lm_head);
-    for (int w : wids) {
-        DWeight& W = *s->weights[w];
-        if (int rc = kr_ensure_wsum(e, W.ms, st)) return rc;
-    }
-    kmax = std::max(kmax, ad);
     const size_t C = CH;
-    if (s->gemm_fast && C * std::max(kmax, (size_t)H) * 2 >= (1ull << 32)) return kr_fail(KR_ERR_VALUE, "KR_GEMM_FAST: chunk of %d tokens x %zu values exceeds 4 GiB of f16 activations; lower the chunk", CH, std::max(kmax, (size_t)H));
-    size_t total = 0, lac_floats = 0;
-    if (s->attn_fast)
-        for (auto& Ly : s->layers) if (Ly.attn == ATTN_LA && kr_pfm_la_chunk_ok(Ly.dk, Ly.dv, CH)) lac_floats = std::max(lac_floats, kr_pfm_la_chunk_scratch_floats(CH, Ly.nv));
-    auto take = [&](size_t bytes) { const size_t o = total; total += al(bytes); return o; };
-    const size_t o_res = take(C * H * 4), o_hid = take(C * H * 4), o_nrm = take(C * H * 4), o_pa = take(C * pa * 4), o_pb = take(C * pb * 4), o_pc = take(C * pc * 4),
-                 o_q = take(C * qd * 4), o_k = take(C * kd * 4), o_v = take(C * vd * 4), o_z = take(C * zd * 4), o_ge = take(C * nvmax * 4), o_be = take(C * nvmax * 4),
-                 o_rec = take(C * vd * 4), o_att = take(C * ad * 4), o_gate = take(C * zd * 4), o_moe = take(C * H * 4), o_sh = take(C * H * 4), o_gv = take(C * 4),
-                 o_sgu = take(C * std::max(sid, (size_t)64) * 4), o_xh = take(C * H), o_xl = take(C * H), o_xs = take(C * (H / 128) * 4), o_yh = take(C * kmax),
-                 o_yl = take(C * kmax), o_ys = take(C * (kmax / 128 + 1) * 4), o_xb = take(C * H * 2), o_ids = take(C * 32 * 4), o_w = take(C * 32 * 4),
-                 o_lg = take(C * (size_t)std::max(e->r_ne, 64) * 4), o_lac = take(lac_floats * 4),
-                 o_xf = take(C * H * 2), o_xfm = take(C * 4), o_yf = take(C * kmax * 2), o_yfm = take(C * 4);
+    PfLayout Lo;
+    if (int rc = pf_layout(s, C, nll_out || verify, false, st, Lo)) return rc;
+    const size_t total = Lo.total, sc_rows = Lo.sc_rows;
     const size_t sc_ld_max = (size_t)((start_pos + n_tokens + 63) & ~63), sc_bytes = al(C * sc_rows * (sc_ld_max + 1 + sc_ld_max / 32) * 4);     // scores + 1 / sum per row + row maxima per 32 positions
     if (s->pf_scratch.ensure(total * n_arenas) || s->pf_tokens.ensure((size_t)n_tokens * 4) || (sc_rows && s->pf_scores.ensure(sc_bytes * n_arenas)))
         return kr_fail(KR_ERR_HIP, "hipMalloc of prefill scratch (%zu MiB) failed", (total * n_arenas + sc_bytes * n_arenas) >> 20);
@@ -378,19 +435,7 @@ static int prefill_impl(kr_decode_store* s, const int32_t* tokens, int n_tokens,
     if (nll_out && (s->pf_vlogits.ensure(vl_bytes * n_arenas) || s->pf_nll.ensure((size_t)n_tokens * 4)))
         return kr_fail(KR_ERR_HIP, "hipMalloc of the all-position logits (%zu MiB) failed", (vl_bytes * n_arenas) >> 20);
     KR_HIP(hipMemcpyAsync(s->pf_tokens.p, tokens, (size_t)n_tokens * 4, hipMemcpyHostToDevice, st));
-    auto carve = [&](int arena) {
-        char* base = (char*)s->pf_scratch.p + (size_t)arena * total;
-        Scratch B{};
-        B.res = (float*)(base + o_res); B.hid = (float*)(base + o_hid); B.normed = (float*)(base + o_nrm); B.pa = (float*)(base + o_pa); B.pb = (float*)(base + o_pb);
-        B.pc = (float*)(base + o_pc); B.q = (float*)(base + o_q); B.k = (float*)(base + o_k); B.v = (float*)(base + o_v); B.z = (float*)(base + o_z);
-        B.gexp = (float*)(base + o_ge); B.beta = (float*)(base + o_be); B.recur = (float*)(base + o_rec); B.attn = (float*)(base + o_att); B.gate = (float*)(base + o_gate);
-        B.moe = (float*)(base + o_moe); B.sh = (float*)(base + o_sh); B.gv = (float*)(base + o_gv); B.sgu = (float*)(base + o_sgu); B.xh = (int8_t*)(base + o_xh);
-        B.xl = (int8_t*)(base + o_xl); B.xs = (float*)(base + o_xs); B.yh = (int8_t*)(base + o_yh); B.yl = (int8_t*)(base + o_yl); B.ys = (float*)(base + o_ys);
-        B.xb = (uint16_t*)(base + o_xb); B.ids = (int32_t*)(base + o_ids); B.w = (float*)(base + o_w); B.logits = (float*)(base + o_lg);
-        B.lac = lac_floats ? (float*)(base + o_lac) : nullptr;
-        B.xf = (uint16_t*)(base + o_xf); B.xfm = (float*)(base + o_xfm); B.yf = (uint16_t*)(base + o_yf); B.yfm = (float*)(base + o_yfm);
-        return B;
-    };
+    auto carve = [&](int arena) { return pf_carve(Lo, (char*)s->pf_scratch.p + (size_t)arena * total); };
 
     // ---- streams: chunk c runs on stream c % D with arena c % D.  Cell (chunk c, layer l) needs (c, l-1) [same stream] and, from (c-1, l) on another
     // stream, exactly two things: the carried conv slots before its conv launch, and the recurrent state before its scan (linear attention) or the
@@ -617,4 +662,27 @@ extern "C" int kr_decode_commit(kr_decode_store* s, int n_keep) {
     KR_HIP(hipGetLastError());
     s->spec_pending = false; s->last_stream = st;
     return KR_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// the multi-sequence step (kr_decode_multi.cpp, docs/design/13-multi-sequence.md): one chunk of n rows, row b = the next token of slot slots[b].
+// Every row-wise section of run_layer runs unchanged; the linear-attention and GQA sections take the per-slot kernels (kr_multi.hip).  All-row
+// logits as in the verify pass.  Engine buffer set KR_PF_MAX_DEPTH - 1; the caller has ordered this pass after everything the store queued.
+// ------------------------------------------------------------------------------------------------
+int kr_multi_pass(kr_decode_store* s, int n, const int32_t* d_rows, int max_pos, hipStream_t st) {
+    kr_multi_state& M = *s->multi;
+    PfLayout Lo;
+    if (int rc = pf_layout(s, (size_t)n, true, true, st, Lo)) return rc;
+    int nh_max = 1;
+    for (const DLayer& L : s->layers) if (L.attn == ATTN_GQA) nh_max = std::max(nh_max, L.nh);
+    const int sc_ld = (max_pos + 1 + 31) & ~31;
+    if (M.scratch.ensure(Lo.total) || M.scores.ensure((size_t)n * nh_max * sc_ld * 4) || M.logits.ensure((size_t)n * s->vocab * 4))
+        return kr_fail(KR_ERR_HIP, "hipMalloc of the multi-sequence step's scratch (%zu MiB) failed", (Lo.total + (size_t)n * (nh_max * sc_ld + s->vocab) * 4) >> 20);
+    Chunk cx{};
+    cx.B = pf_carve(Lo, (char*)M.scratch.p); cx.scores = nullptr; cx.tok = d_rows + n; cx.Cc = n; cx.pos0 = 0; cx.set = KR_PF_MAX_DEPTH - 1;
+    cx.first = true; cx.add_is_emb = true; cx.st = st;
+    cx.m_slots = d_rows; cx.m_pos = d_rows + 2 * n; cx.m_sc_ld = sc_ld;
+    for (size_t l = 0; l < s->layers.size(); l++)
+        if (int rc = run_layer(s, cx, l)) return rc;
+    return final_rows(s, cx, (float*)M.logits.p);
 }

@@ -1,0 +1,37 @@
+// kr_multi.h -- kernels of the exact multi-sequence decode step (kr_multi.hip; host side in kr_decode_multi.cpp, docs/design/13-multi-sequence.md).
+// Row b of a step belongs to sequence slot slots[b] at position positions[b]; every per-slot buffer is [n_slots][per-slot elements].
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+// linear attention, one token per row (the decode step's kr_la_step_kernel arithmetic)
+struct KrMultiLaArgs {
+    const int* slots;               // [B] device
+    const float* qkvz; int ld_qkvz; // in-projection rows [B][ld_qkvz]
+    const float* ba; int ld_ba;     // [B][ld_ba]
+    const float *conv_w, *a_log, *dt_bias, *norm_w;
+    float* conv_state; size_t conv_stride;     // slot s: conv_state + s * conv_stride, [conv_dim][4]
+    float* recur; size_t recur_stride;         // slot s: recur + s * recur_stride, [nv][dk][dv]
+    float* conv_out;                           // scratch [B][conv_dim]: conv + SiLU outputs
+    float* out; int ld_out;                    // [B][ld_out]: gated RMSNorm output, the out-projection's input
+    int nk, nv, dk, dv, hr; float scale, eps;
+};
+// 0: launched; 1: geometry not covered (kd 4 is the caller's check; dk 64 / 128, dv <= 256, dv % 8 == 0)
+int kr_launch_multi_la(const KrMultiLaArgs& a, int B, hipStream_t st);
+
+// GQA, one token per row: QK-norm + RoPE at the row's position, K / V appended to the row's slot, attention over the slot's rows [0, pos]
+struct KrMultiGqaArgs {
+    const int* slots; const int* positions;    // [B] device
+    const float *q_in, *k_in, *v_in; int ld_q, ld_k, ld_v;
+    const float *q_norm, *k_norm; int q_norm_per_head, k_norm_per_head;
+    const float *rope_cos, *rope_sin; int rope_half;
+    void *k_cache, *v_cache; size_t slot_elems; int kv_fp8;   // slot s: cache + s * slot_elems elements, [max_seq][nkv * hd]
+    float *q_out, *gate, *attn_out;            // [B][nh * hd]
+    float* scores; int sc_ld;                  // scratch [B][nh][sc_ld], sc_ld >= the longest row's pos + 1 rounded up to 32
+    int gated, nh, nkv, hd; float eps, sm_scale;
+};
+// 0: launched; 1: geometry not covered (hd 64 / 128 / 256, nh % nkv == 0)
+int kr_launch_multi_gqa(const KrMultiGqaArgs& a, int B, hipStream_t st);
+
+// per row b < B of logits [B][ld]: out[b] = first-maximum argmax of the row's first V values (kr_argmax_kernel's rule)
+void kr_launch_multi_argmax(const float* logits, size_t ld, int V, int B, int* out, hipStream_t st);

@@ -394,6 +394,47 @@ class CpuDecodeStore:
         self.last_lookup_stats = {"passes": passes.value, "accepted": acc.value}
         return list(out[: n.value])
 
+    # ------------------------------------------------------------------ sequence slots (docs/design/13-multi-sequence.md)
+    def create_slots(self, n: int, max_seq: int) -> int:
+        """kr_decode_slots_create: n zeroed sequence slots of up to max_seq positions (replacing any earlier ones; n = 0 frees them), KV rows of
+        the store's current element type.  Returns their device bytes."""
+        self._need()
+        b = C.c_size_t()
+        check(self._lib.kr_decode_slots_create(self._h, n, max_seq, C.byref(b)))
+        return b.value
+
+    def save_slot(self, slot: int, seq_len: int) -> None:
+        """the store's own sequence -> slot: KV rows [0, seq_len) of every GQA layer, conv + recurrent state of every linear-attention layer"""
+        self._need(); check(self._lib.kr_decode_slot_save(self._h, slot, seq_len))
+
+    def load_slot(self, slot: int, seq_len: int) -> None:
+        """slot -> the store's own sequence (the same parts); decode_step / prefill / verify then continue it at position seq_len"""
+        self._need(); check(self._lib.kr_decode_slot_load(self._h, slot, seq_len))
+
+    def step_multi(self, slots: Sequence[int], tokens: Sequence[int], positions: Sequence[int], logits: bool = False):
+        """kr_decode_step_multi: row i = slot slots[i] consumes tokens[i] at positions[i], bit-identical to decode_step on that sequence alone.
+        Returns the greedy ids, or (ids, logits f32 [n, vocab]) with logits=True."""
+        self._need()
+        n = len(slots)
+        arr = lambda xs: (C.c_int32 * max(n, 1))(*xs)
+        ids = (C.c_int32 * max(n, 1))()
+        out = np.empty((n, self._vocab), np.float32) if logits else None
+        check(self._lib.kr_decode_step_multi(self._h, n, arr(slots), arr(tokens), arr(positions), ids, out.ctypes.data if logits else None, None))
+        return (list(ids[:n]), out) if logits else list(ids[:n])
+
+    def generate_multi(self, slots: Sequence[int], first_tokens: Sequence[int], start_positions: Sequence[int], max_tokens: int,
+                       stop_ids: Sequence[int] = ()) -> List[List[int]]:
+        """kr_decode_generate_multi: greedy generation of the slots together; row i's tokens (and its slot afterwards) are those of
+        generate_batch(first_tokens[i], start_positions[i], max_tokens, stop_ids=stop_ids) at temperature 0 on that sequence alone."""
+        self._need()
+        n = len(slots)
+        arr = lambda xs: (C.c_int32 * max(n, 1))(*xs)
+        out = (C.c_int32 * max(n * max_tokens, 1))(); cnt = (C.c_int32 * max(n, 1))()
+        stops = (C.c_int * max(len(stop_ids), 1))(*stop_ids)
+        check(self._lib.kr_decode_generate_multi(self._h, n, arr(slots), arr(first_tokens), arr(start_positions), max_tokens, stops, len(stop_ids),
+                                                 out, cnt, None))
+        return [list(out[i * max_tokens: i * max_tokens + cnt[i]]) for i in range(n)]
+
     def generate_stream(self, first_token: int, start_position: int, max_tokens: int, temperature: float, top_k: int, top_p: float,
                         stop_ids: Sequence[int], tokenizer, presence_penalty: float, on_token, rng_seed: int = 0) -> int:
         """decode.rs:3611 -- the cancellable loop of the reference's Rust server.  on_token(token_id, text, finish_reason) -> bool (False cancels);
