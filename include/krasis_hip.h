@@ -369,6 +369,31 @@ int kr_decode_step_multi(kr_decode_store* s, int n, const int32_t* slots, const 
    max_tokens) leaves the batch; its slot is not stepped again.  start_positions[i] + max_tokens > slot max_seq is refused before the first step. */
 int kr_decode_generate_multi(kr_decode_store* s, int n, const int32_t* slots, const int32_t* first_tokens, const int32_t* start_positions,
                              int max_tokens, const int* stop_ids, int n_stop, int32_t* tokens_out, int32_t* n_out, void* stream);
+/* per-row sampling (docs/design/14-multi-sampling.md).  Each slot carries its own sampler: parameters, seen-token bitmap, xorshift64 state.
+   Allocated for every slot on the first kr_decode_slot_sampler call; kr_decode_slots_create drops it (a fresh slot samples greedily).  Never
+   touches the store's own sampler state (kr_decode_sample / kr_decode_generate behave as if no sampled multi step had run).
+   The start of kr_decode_generate on a slot: seen-token set = {first_token} (if in range), xorshift64 state = rng_seed (0: a wall-clock seed,
+   distinct per slot -- not reproducible), parameters kept with the slot.  temperature 0 and presence_penalty 0 = greedy (first maximum). */
+int kr_decode_slot_sampler(kr_decode_store* s, int slot, int first_token, float temperature, int top_k, float top_p,
+                           float presence_penalty, uint64_t rng_seed);
+/* kr_decode_step_multi, but next_out[i] is drawn by slot slots[i]'s sampler, and the slot's RNG state and seen set advance as kr_decode_generate's
+   do for that token.  logits_out (optional) = the model's logits before the penalty and temperature (bit-identical to kr_decode_step_multi's).
+   Rows drawing from more than 4096 candidates (top_k 0 or > 4096), or every sampled row under kr_decode_set_option("multi_sample_loop", 1),
+   run the single-row sampler one row after another: same tokens. */
+int kr_decode_step_multi_sample(kr_decode_store* s, int n, const int32_t* slots, const int32_t* tokens, const int32_t* positions,
+                                int32_t* next_out, float* logits_out, void* stream);
+/* kr_decode_generate_multi with per-row sampler parameters (arrays of n): sets every row's slot sampler, then loops.  Row i equals
+   kr_decode_generate(first_tokens[i], start_positions[i], max_tokens, temperature[i], top_k[i], top_p[i], stop ids, presence_penalty[i],
+   rng_seeds[i]) on that sequence alone: tokens, count, stop id as the last element, slot state afterwards. */
+int kr_decode_generate_multi_sample(kr_decode_store* s, int n, const int32_t* slots, const int32_t* first_tokens,
+                                    const int32_t* start_positions, int max_tokens, const float* temperature, const int* top_k,
+                                    const float* top_p, const float* presence_penalty, const uint64_t* rng_seeds,
+                                    const int* stop_ids, int n_stop, int32_t* tokens_out, int32_t* n_out, void* stream);
+/* test aid (like kr_sample_order): the batched sampler on host logits [n][vocab] with per-row parameters, seen bitmaps [n][(vocab+31)/32]
+   (may be NULL: none seen) and xorshift64 states (in / out); tokens_out[n].  force_loop != 0: every sampled row takes the single-row sampler
+   (the "multi_sample_loop" form). */
+int kr_sample_rows(const float* logits, int n, int vocab, const float* temperature, const int* top_k, const float* top_p,
+                   const float* presence_penalty, const uint32_t* seen, uint64_t* rng_state, int32_t* tokens_out, int force_loop);
 
 /* ---- stand-alone CpuDecodeStore operators (decode.rs:328-1086).  Every pointer may be a host or a device pointer; host buffers are staged and
  * the call returns after the results are back.  Bit-identical to the reference methods (tests/test_standalone_ops_gpu.py against the oracle's

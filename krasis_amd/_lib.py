@@ -30,6 +30,7 @@ SYMBOLS = [
     "kr_decode_gated_rmsnorm_silu", "kr_decode_linear_attention_conv", "kr_decode_store_route_weight", "kr_decode_moe_route", "kr_decode_num_route_weights",
     "kr_decode_weight_bytes", "kr_decode_verify", "kr_decode_commit", "kr_decode_generate_lookup", "kr_lookup_draft",
     "kr_decode_slots_create", "kr_decode_slot_save", "kr_decode_slot_load", "kr_decode_step_multi", "kr_decode_generate_multi",
+    "kr_decode_slot_sampler", "kr_decode_step_multi_sample", "kr_decode_generate_multi_sample", "kr_sample_rows",
 ]
 TOKEN_CB = C.CFUNCTYPE(C.c_int, C.c_int, C.c_int, C.c_void_p)      # kr_token_cb(token, finish_reason, user) -> continue?
 
@@ -176,6 +177,10 @@ def load_library() -> C.CDLL:
     lib.kr_decode_slot_load.argtypes = [vp, ci, ci]
     lib.kr_decode_step_multi.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp]
     lib.kr_decode_generate_multi.argtypes = [vp, ci, vp, vp, vp, ci, vp, ci, vp, vp, vp]
+    lib.kr_decode_slot_sampler.argtypes = [vp, ci, ci, cf, ci, cf, cf, C.c_uint64]
+    lib.kr_decode_step_multi_sample.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp]
+    lib.kr_decode_generate_multi_sample.argtypes = [vp, ci, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp]
+    lib.kr_sample_rows.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp, vp, vp, ci]
     _lib = lib
     return lib
 

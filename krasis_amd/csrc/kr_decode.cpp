@@ -1043,6 +1043,7 @@ extern "C" int kr_decode_set_option(kr_decode_store* s, const char* name, int va
     if (!strcmp(name, "norm_rows")) { s->opt_norm_rows = value != 0; return KR_OK; }                        // KR_GEMM_FAST prompt pass: 0 = the f16 row image of a norm's output by its own launch (A/B and test hook; same bits)
     if (!strcmp(name, "pfm_timing")) { s->opt_pfm_timing = value != 0; return KR_OK; }
     if (!strcmp(name, "generate_lookahead")) { s->opt_gen_lookahead = value != 0; return KR_OK; }
+    if (!strcmp(name, "multi_sample_loop")) { s->opt_multi_sample_loop = value != 0; return KR_OK; }
     if (!strcmp(name, "ep_graph")) { s->opt_ep_graph = value != 0; s->graph_ok = false; return KR_OK; }
     return kr_fail(KR_ERR_VALUE, "unknown option '%s'", name);
 }

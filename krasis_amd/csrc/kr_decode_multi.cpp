@@ -7,11 +7,14 @@
 // per-slot kernels (kr_multi.hip) with the decode step's arithmetic.  So row i of a step carries exactly the bits kr_decode_step gives on
 // that sequence alone.  The store's own sequence is the hand-over point: prompt pass -> kr_decode_slot_save -> steps -> kr_decode_slot_load.
 #include <algorithm>
+#include <chrono>
 #include <cstring>
 #include <vector>
 
 #include "../../include/krasis_hip.h"
 #include "kr_decode_internal.h"
+#include "kr_multi_sample.h"
+#include "kr_sampler.h"
 
 namespace {
 int multi_ready(kr_decode_store* s) {
@@ -65,17 +68,64 @@ int check_rows(kr_decode_store* s, int n, const int32_t* slots, const int32_t* t
     }
     return KR_OK;
 }
-// one step, arguments checked: rows -> device, the pass, per-row argmax, ids (and logits) back; returns once next_out is written
-int step_impl(kr_decode_store* s, int n, const int32_t* slots, const int32_t* tokens, const int32_t* positions, int32_t* next_out, float* logits_out, hipStream_t st) {
+// what row b of a sampled step does: the three paths of kr_decode_generate's loop (kr_decode.cpp generate_core) for its slot's sampler
+KrMsRow sample_row(kr_decode_store* s, int slot) {
+    const kr_multi_state& M = *s->multi;
+    KrMsRow r{KR_MS_GREEDY, slot, 0, 0, 0.0f, 0.0f, 1.0f, 0.0f};
+    if (M.smp.empty()) return r;
+    const kr_multi_state::Sampler& p = M.smp[(size_t)slot];
+    r.temperature = p.temperature; r.top_k = p.top_k; r.top_p = p.top_p; r.penalty = p.penalty;
+    r.k = (p.top_k > 0 && p.top_k < s->vocab) ? p.top_k : s->vocab;
+    if (p.temperature == 0.0f) r.mode = p.penalty != 0.0f ? KR_MS_PENALTY : KR_MS_GREEDY;
+    else { r.mode = (r.k <= KR_MS_SEL_CAP && !s->opt_multi_sample_loop) ? KR_MS_SAMPLE : KR_MS_LOOP; r.inv_temp = 1.0f / p.temperature; }
+    return r;
+}
+// device scratch of the batched sampler for n rows of these modes (kr_sample_rows and the sampled step)
+int sampler_scratch(kr_multi_state& M, int vocab, int n, const std::vector<KrMsRow>& rows) {
+    bool prep = false, sample = false, loop = false;
+    for (const KrMsRow& r : rows) { prep |= r.mode != KR_MS_GREEDY; sample |= r.mode == KR_MS_SAMPLE; loop |= r.mode == KR_MS_LOOP; }
+    const size_t V = (size_t)vocab;
+    if (M.smp_rows.ensure((size_t)KR_MULTI_MAX * sizeof(KrMsRow))) return 1;
+    if (prep && M.smp_work.ensure((size_t)n * V * 4)) return 1;
+    if (sample && M.smp_sorted.ensure((size_t)n * KR_MS_SEL_CAP * 8)) return 1;
+    if (loop) {
+        if (M.smp_temp_bytes == 0) M.smp_temp_bytes = kr_sampler_temp_bytes(vocab);
+        if (M.smp_keys.ensure(2 * V * 8) || M.smp_temp.ensure(M.smp_temp_bytes + 256) || M.smp_probs.ensure(V * 4)) return 1;
+    }
+    return 0;
+}
+KrMsArgs sampler_args(kr_multi_state& M, const float* logits, int vocab, int n, const std::vector<KrMsRow>& rows, uint32_t* seen, size_t words, uint64_t* rng, int* ids) {
+    KrMsArgs a{};
+    a.logits = logits; a.ld = (size_t)vocab; a.V = vocab; a.B = n;
+    a.rows_dev = (const KrMsRow*)M.smp_rows.p; a.rows_host = rows.data();
+    a.work = (float*)M.smp_work.p; a.sorted = (uint64_t*)M.smp_sorted.p;
+    a.seen = seen; a.seen_words = words; a.rng = rng; a.ids = ids;
+    a.loop_keys = (uint64_t*)M.smp_keys.p; a.loop_temp = M.smp_temp.p; a.loop_temp_bytes = M.smp_temp_bytes; a.loop_probs = (float*)M.smp_probs.p;
+    return a;
+}
+// one step, arguments checked: rows -> device, the pass, per-row argmax (sample: each slot's sampler), ids (and logits) back; returns once next_out is written
+int step_impl(kr_decode_store* s, int n, const int32_t* slots, const int32_t* tokens, const int32_t* positions, int32_t* next_out, float* logits_out, hipStream_t st,
+              bool sample = false) {
     kr_multi_state& M = *s->multi;
     if (M.rows.ensure((size_t)3 * KR_MULTI_MAX * 4) || M.ids.ensure((size_t)KR_MULTI_MAX * 4)) return kr_fail(KR_ERR_HIP, "hipMalloc of the step's row buffers failed");
+    std::vector<KrMsRow> sr;
+    bool greedy = true;
+    if (sample) {
+        for (int i = 0; i < n; i++) { sr.push_back(sample_row(s, slots[i])); greedy &= sr.back().mode == KR_MS_GREEDY; }
+        if (!greedy && sampler_scratch(M, s->vocab, n, sr)) return kr_fail(KR_ERR_HIP, "hipMalloc of the sampled step's scratch failed");
+    }
     std::vector<int32_t> h((size_t)3 * n);
     int max_pos = 0;
     for (int i = 0; i < n; i++) { h[(size_t)i] = slots[i]; h[(size_t)n + i] = tokens[i]; h[(size_t)2 * n + i] = positions[i]; max_pos = std::max(max_pos, positions[i]); }
     KR_HIP(hipMemcpyAsync(M.rows.p, h.data(), h.size() * 4, hipMemcpyHostToDevice, st));
+    if (!greedy) KR_HIP(hipMemcpyAsync(M.smp_rows.p, sr.data(), sr.size() * sizeof(KrMsRow), hipMemcpyHostToDevice, st));
     if (int rc = kr_multi_pass(s, n, (const int32_t*)M.rows.p, max_pos, st)) { (void)hipStreamSynchronize(st); return rc; }
     const size_t V = (size_t)s->vocab;
-    kr_launch_multi_argmax((const float*)M.logits.p, V, (int)V, n, (int*)M.ids.p, st);
+    if (greedy) kr_launch_multi_argmax((const float*)M.logits.p, V, (int)V, n, (int*)M.ids.p, st);
+    else if (kr_launch_multi_sample(sampler_args(M, (const float*)M.logits.p, s->vocab, n, sr, (uint32_t*)M.smp_seen.p, M.smp_words, (uint64_t*)M.smp_rng.p, (int*)M.ids.p), st)) {
+        (void)hipStreamSynchronize(st);
+        return kr_fail(KR_ERR_HIP, "batched sampler launch failed");
+    }
     KR_HIP(hipGetLastError());
     KR_HIP(hipMemcpyAsync(next_out, M.ids.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
     if (logits_out) KR_HIP(hipMemcpyAsync(logits_out, M.logits.p, (size_t)n * V * 4, is_device_ptr(logits_out) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
@@ -117,6 +167,77 @@ int slot_copy(kr_decode_store* s, int slot, int seq_len, bool save) {
         if (nb) KR_HIP(hipMemcpyAsync(save ? (void*)b : sb, save ? sb : (void*)b, nb, hipMemcpyDeviceToDevice, st));
     }
     KR_HIP(hipStreamSynchronize(st));
+    return KR_OK;
+}
+// the start of kr_decode_generate for one slot (generate_core): seen = {first_token} (if in range), xorshift64 state = rng_seed (0: the wall clock,
+// distinct per slot), parameters kept.  Arguments checked; allocates every slot's sampler state on the first call.
+int set_sampler(kr_decode_store* s, int slot, int first_token, float temperature, int top_k, float top_p, float presence_penalty, uint64_t rng_seed, hipStream_t st) {
+    kr_multi_state& M = *s->multi;
+    if (M.smp.empty()) {
+        const size_t words = ((size_t)s->vocab + 31) / 32;
+        if (M.smp_seen.ensure((size_t)M.n_slots * words * 4) || M.smp_rng.ensure((size_t)M.n_slots * 8)) return kr_fail(KR_ERR_HIP, "hipMalloc of the slot samplers failed");
+        KR_HIP(hipMemsetAsync(M.smp_seen.p, 0, M.smp_seen.bytes, st));
+        KR_HIP(hipMemsetAsync(M.smp_rng.p, 0, M.smp_rng.bytes, st));
+        M.smp_words = words;
+        M.smp.assign((size_t)M.n_slots, kr_multi_state::Sampler());
+    }
+    std::vector<uint32_t> seen(M.smp_words, 0u);
+    if (first_token >= 0 && first_token < s->vocab) seen[(size_t)first_token >> 5] |= 1u << (first_token & 31);
+    if (rng_seed == 0) {
+        rng_seed = (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::system_clock::now().time_since_epoch()).count() + 0x9E3779B97F4A7C15ull * (uint64_t)(slot + 1);
+        if (rng_seed == 0) rng_seed = 0xDEADBEEFull;
+    }
+    KR_HIP(hipMemcpyAsync((uint32_t*)M.smp_seen.p + (size_t)slot * M.smp_words, seen.data(), M.smp_words * 4, hipMemcpyHostToDevice, st));
+    KR_HIP(hipMemcpyAsync((uint64_t*)M.smp_rng.p + slot, &rng_seed, 8, hipMemcpyHostToDevice, st));
+    KR_HIP(hipStreamSynchronize(st));
+    kr_multi_state::Sampler& p = M.smp[(size_t)slot];
+    p.temperature = temperature; p.top_k = top_k; p.top_p = top_p; p.penalty = presence_penalty;
+    return KR_OK;
+}
+// kr_decode_generate_multi and its sampled form: every row's sampler set first (sample), then the steps; a finished row leaves the batch
+int generate_impl(kr_decode_store* s, int n, const int32_t* slots, const int32_t* first_tokens, const int32_t* start_positions, int max_tokens, const float* temperature,
+                  const int* top_k, const float* top_p, const float* presence_penalty, const uint64_t* rng_seeds, const int* stop_ids, int n_stop,
+                  int32_t* tokens_out, int32_t* n_out, void* stream) {
+    const bool sample = temperature != nullptr;
+    if (int rc = multi_ready(s)) return rc;
+    if (int rc = need_slots(s)) return rc;
+    if (int rc = multi_refuse(s)) return rc;
+    if (max_tokens < 0) return kr_fail(KR_ERR_VALUE, "max_tokens %d < 0", max_tokens);
+    if (n_stop < 0 || (n_stop > 0 && !stop_ids)) return kr_fail(KR_ERR_VALUE, "bad stop ids (%d)", n_stop);
+    if (!n_out || (max_tokens > 0 && !tokens_out)) return kr_fail(KR_ERR_VALUE, "null output pointer");
+    // every row's last step (position start + max_tokens - 1) must fit its slot: checked here, before the first step
+    if (int rc = check_rows(s, n, slots, first_tokens, start_positions, std::max(max_tokens - 1, 0))) return rc;
+    if (sample) {
+        if (!top_k || !top_p || !presence_penalty || !rng_seeds) return kr_fail(KR_ERR_VALUE, "null sampler parameter array");
+        for (int i = 0; i < n; i++) if (!(temperature[i] >= 0.0f)) return kr_fail(KR_ERR_VALUE, "row %d: temperature must be >= 0", i);
+    }
+    for (int i = 0; i < n; i++) n_out[i] = 0;
+    if (max_tokens == 0 && !sample) return KR_OK;
+    KR_HIP(hipSetDevice(s->eng->device));
+    hipStream_t st = kr_pick_stream(s->eng, stream);
+    if (int rc = order_after_store(s, st)) return rc;
+    if (sample)
+        for (int i = 0; i < n; i++)
+            if (int rc = set_sampler(s, slots[i], first_tokens[i], temperature[i], top_k[i], top_p[i], presence_penalty[i], rng_seeds[i], st)) return rc;
+    if (max_tokens == 0) return KR_OK;
+    auto is_stop = [&](int t) { for (int j = 0; j < n_stop; j++) if (stop_ids[j] == t) return true; return false; };
+    std::vector<int> act((size_t)n);                           // rows still generating, in caller order
+    std::vector<int32_t> sl((size_t)n), tk((size_t)n), ps((size_t)n), nx((size_t)n);
+    for (int i = 0; i < n; i++) { act[(size_t)i] = i; tk[(size_t)i] = first_tokens[i]; ps[(size_t)i] = start_positions[i]; }
+    while (!act.empty()) {
+        const int m = (int)act.size();
+        std::vector<int32_t> rt((size_t)m), rp((size_t)m);
+        for (int k = 0; k < m; k++) { const int i = act[(size_t)k]; sl[(size_t)k] = slots[i]; rt[(size_t)k] = tk[(size_t)i]; rp[(size_t)k] = ps[(size_t)i]; }
+        if (int rc = step_impl(s, m, sl.data(), rt.data(), rp.data(), nx.data(), nullptr, st, sample)) return rc;
+        std::vector<int> keep;
+        for (int k = 0; k < m; k++) {
+            const int i = act[(size_t)k], t = nx[(size_t)k];
+            tokens_out[(size_t)i * max_tokens + n_out[i]++] = t;
+            tk[(size_t)i] = t; ps[(size_t)i]++;
+            if (!is_stop(t) && n_out[i] < max_tokens) keep.push_back(i);   // a finished row leaves the batch: its slot is not stepped again
+        }
+        act.swap(keep);
+    }
     return KR_OK;
 }
 }  // namespace
@@ -173,36 +294,73 @@ extern "C" int kr_decode_step_multi(kr_decode_store* s, int n, const int32_t* sl
 
 extern "C" int kr_decode_generate_multi(kr_decode_store* s, int n, const int32_t* slots, const int32_t* first_tokens, const int32_t* start_positions,
                                         int max_tokens, const int* stop_ids, int n_stop, int32_t* tokens_out, int32_t* n_out, void* stream) {
+    return generate_impl(s, n, slots, first_tokens, start_positions, max_tokens, nullptr, nullptr, nullptr, nullptr, nullptr, stop_ids, n_stop, tokens_out, n_out, stream);
+}
+
+// ---- per-row sampling (docs/design/14-multi-sampling.md)
+extern "C" int kr_decode_slot_sampler(kr_decode_store* s, int slot, int first_token, float temperature, int top_k, float top_p, float presence_penalty,
+                                      uint64_t rng_seed) {
     if (int rc = multi_ready(s)) return rc;
     if (int rc = need_slots(s)) return rc;
     if (int rc = multi_refuse(s)) return rc;
-    if (max_tokens < 0) return kr_fail(KR_ERR_VALUE, "max_tokens %d < 0", max_tokens);
-    if (n_stop < 0 || (n_stop > 0 && !stop_ids)) return kr_fail(KR_ERR_VALUE, "bad stop ids (%d)", n_stop);
-    if (!n_out || (max_tokens > 0 && !tokens_out)) return kr_fail(KR_ERR_VALUE, "null output pointer");
-    // every row's last step (position start + max_tokens - 1) must fit its slot: checked here, before the first step
-    if (int rc = check_rows(s, n, slots, first_tokens, start_positions, std::max(max_tokens - 1, 0))) return rc;
-    for (int i = 0; i < n; i++) n_out[i] = 0;
-    if (max_tokens == 0) return KR_OK;
+    if (slot < 0 || slot >= s->multi->n_slots) return kr_fail(KR_ERR_VALUE, "slot %d out of range [0, %d)", slot, s->multi->n_slots);
+    if (!(temperature >= 0.0f)) return kr_fail(KR_ERR_VALUE, "temperature must be >= 0");
+    KR_HIP(hipSetDevice(s->eng->device));
+    return set_sampler(s, slot, first_token, temperature, top_k, top_p, presence_penalty, rng_seed, s->eng->stream);
+}
+
+extern "C" int kr_decode_step_multi_sample(kr_decode_store* s, int n, const int32_t* slots, const int32_t* tokens, const int32_t* positions,
+                                           int32_t* next_out, float* logits_out, void* stream) {
+    if (int rc = multi_ready(s)) return rc;
+    if (int rc = need_slots(s)) return rc;
+    if (int rc = multi_refuse(s)) return rc;
+    if (int rc = check_rows(s, n, slots, tokens, positions, 0)) return rc;
+    if (!next_out) return kr_fail(KR_ERR_VALUE, "null next_out");
     KR_HIP(hipSetDevice(s->eng->device));
     hipStream_t st = kr_pick_stream(s->eng, stream);
     if (int rc = order_after_store(s, st)) return rc;
-    auto is_stop = [&](int t) { for (int j = 0; j < n_stop; j++) if (stop_ids[j] == t) return true; return false; };
-    std::vector<int> act((size_t)n);                           // rows still generating, in caller order
-    std::vector<int32_t> sl((size_t)n), tk((size_t)n), ps((size_t)n), nx((size_t)n);
-    for (int i = 0; i < n; i++) { act[(size_t)i] = i; tk[(size_t)i] = first_tokens[i]; ps[(size_t)i] = start_positions[i]; }
-    while (!act.empty()) {
-        const int m = (int)act.size();
-        std::vector<int32_t> rt((size_t)m), rp((size_t)m);
-        for (int k = 0; k < m; k++) { const int i = act[(size_t)k]; sl[(size_t)k] = slots[i]; rt[(size_t)k] = tk[(size_t)i]; rp[(size_t)k] = ps[(size_t)i]; }
-        if (int rc = step_impl(s, m, sl.data(), rt.data(), rp.data(), nx.data(), nullptr, st)) return rc;
-        std::vector<int> keep;
-        for (int k = 0; k < m; k++) {
-            const int i = act[(size_t)k], t = nx[(size_t)k];
-            tokens_out[(size_t)i * max_tokens + n_out[i]++] = t;
-            tk[(size_t)i] = t; ps[(size_t)i]++;
-            if (!is_stop(t) && n_out[i] < max_tokens) keep.push_back(i);   // a finished row leaves the batch: its slot is not stepped again
-        }
-        act.swap(keep);
+    return step_impl(s, n, slots, tokens, positions, next_out, logits_out, st, true);
+}
+
+extern "C" int kr_decode_generate_multi_sample(kr_decode_store* s, int n, const int32_t* slots, const int32_t* first_tokens, const int32_t* start_positions,
+                                               int max_tokens, const float* temperature, const int* top_k, const float* top_p, const float* presence_penalty,
+                                               const uint64_t* rng_seeds, const int* stop_ids, int n_stop, int32_t* tokens_out, int32_t* n_out, void* stream) {
+    if (!temperature) return kr_fail(KR_ERR_VALUE, "null sampler parameter array");
+    return generate_impl(s, n, slots, first_tokens, start_positions, max_tokens, temperature, top_k, top_p, presence_penalty, rng_seeds, stop_ids, n_stop,
+                         tokens_out, n_out, stream);
+}
+
+// test aid: the batched sampler on host rows, row b = "slot" b (its own seen bitmap and xorshift64 state)
+extern "C" int kr_sample_rows(const float* logits, int n, int vocab, const float* temperature, const int* top_k, const float* top_p,
+                              const float* presence_penalty, const uint32_t* seen, uint64_t* rng_state, int32_t* tokens_out, int force_loop) {
+    if (!logits || !temperature || !top_k || !top_p || !presence_penalty || !rng_state || !tokens_out || vocab <= 0)
+        return kr_fail(KR_ERR_VALUE, "kr_sample_rows: null pointer or empty vocabulary");
+    if (n < 1 || n > KR_MULTI_MAX) return kr_fail(KR_ERR_VALUE, "%d rows, must be in [1, %d]", n, KR_MULTI_MAX);
+    for (int i = 0; i < n; i++) if (!(temperature[i] >= 0.0f)) return kr_fail(KR_ERR_VALUE, "row %d: temperature must be >= 0", i);
+    int dev_count = 0;
+    if (hipGetDeviceCount(&dev_count) != hipSuccess || dev_count == 0) return kr_fail(KR_ERR_HIP, "no HIP device");
+    std::vector<KrMsRow> rows((size_t)n);
+    for (int b = 0; b < n; b++) {
+        KrMsRow& r = rows[(size_t)b];
+        r = KrMsRow{KR_MS_GREEDY, b, 0, top_k[b], temperature[b], 0.0f, top_p[b], presence_penalty[b]};
+        r.k = (top_k[b] > 0 && top_k[b] < vocab) ? top_k[b] : vocab;
+        if (temperature[b] == 0.0f) r.mode = presence_penalty[b] != 0.0f ? KR_MS_PENALTY : KR_MS_GREEDY;
+        else { r.mode = (r.k <= KR_MS_SEL_CAP && !force_loop) ? KR_MS_SAMPLE : KR_MS_LOOP; r.inv_temp = 1.0f / temperature[b]; }
     }
+    const size_t V = (size_t)vocab, words = (V + 31) / 32;
+    kr_multi_state M;
+    DevBuf lg, sn, rg, ids;
+    if (sampler_scratch(M, vocab, n, rows) || lg.ensure((size_t)n * V * 4) || sn.ensure((size_t)n * words * 4) || rg.ensure((size_t)n * 8) || ids.ensure((size_t)n * 4))
+        return kr_fail(KR_ERR_HIP, "hipMalloc failed");
+    KR_HIP(hipMemcpy(lg.p, logits, (size_t)n * V * 4, hipMemcpyHostToDevice));
+    if (seen) KR_HIP(hipMemcpy(sn.p, seen, (size_t)n * words * 4, hipMemcpyHostToDevice));
+    else KR_HIP(hipMemset(sn.p, 0, (size_t)n * words * 4));
+    KR_HIP(hipMemcpy(rg.p, rng_state, (size_t)n * 8, hipMemcpyHostToDevice));
+    KR_HIP(hipMemcpy(M.smp_rows.p, rows.data(), (size_t)n * sizeof(KrMsRow), hipMemcpyHostToDevice));
+    if (kr_launch_multi_sample(sampler_args(M, (const float*)lg.p, vocab, n, rows, (uint32_t*)sn.p, words, (uint64_t*)rg.p, (int*)ids.p), nullptr))
+        return kr_fail(KR_ERR_HIP, "batched sampler launch failed");
+    KR_HIP(hipDeviceSynchronize());
+    KR_HIP(hipMemcpy(tokens_out, ids.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    KR_HIP(hipMemcpy(rng_state, rg.p, (size_t)n * 8, hipMemcpyDeviceToHost));
     return KR_OK;
 }

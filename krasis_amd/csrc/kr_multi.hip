@@ -5,6 +5,7 @@
 #include "kr_device.h"
 #include "kr_libm.h"
 #include "kr_multi.h"
+#include "kr_sample_dev.h"
 
 // hsum over 8 consecutive lanes in the order of the reference's hsum (kr_decode_ops.hip kr_hsum8)
 __device__ __forceinline__ float kr_m_hsum8(float v) {
@@ -290,23 +291,10 @@ int kr_launch_multi_gqa(const KrMultiGqaArgs& a, int B, hipStream_t st) {
 }
 
 // ---- per-row greedy id ---------------------------------------------------------------------------------------------------------------------------
-// grid B, 1024 threads per row.  (value desc, index asc) is a total order on the row's values, so this tree returns kr_argmax_kernel's first maximum.
+// grid B, 1024 threads per row: kr_argmax_kernel's first maximum (kr_row_argmax_1024)
 __global__ void __launch_bounds__(1024) kr_multi_argmax_kernel(const float* __restrict__ x, size_t ld, int V, int* __restrict__ out) {
-    __shared__ float bv[16]; __shared__ int bi[16];
-    const float* row = x + (size_t)blockIdx.x * ld;
-    float v = -__builtin_inff(); int idx = 0x7FFFFFFF;
-    for (int i = threadIdx.x; i < V; i += 1024) { const float t = row[i]; if (t > v || (t == v && i < idx)) { v = t; idx = i; } }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const float ov = __shfl_xor(v, off); const int oi = __shfl_xor(idx, off);
-        if (ov > v || (ov == v && oi < idx)) { v = ov; idx = oi; }
-    }
-    if ((threadIdx.x & 63) == 0) { bv[threadIdx.x >> 6] = v; bi[threadIdx.x >> 6] = idx; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < 16; w++) if (bv[w] > v || (bv[w] == v && bi[w] < idx)) { v = bv[w]; idx = bi[w]; }
-        out[blockIdx.x] = idx;
-    }
+    const int idx = kr_row_argmax_1024(x + (size_t)blockIdx.x * ld, V);
+    if (threadIdx.x == 0) out[blockIdx.x] = idx;
 }
 void kr_launch_multi_argmax(const float* logits, size_t ld, int V, int B, int* out, hipStream_t st) {
     hipLaunchKernelGGL(kr_multi_argmax_kernel, dim3(B), dim3(1024), 0, st, logits, ld, V, out);

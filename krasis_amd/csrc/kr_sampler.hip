@@ -15,6 +15,7 @@
 #include <stdint.h>
 
 #include "kr_libm.h"
+#include "kr_sample_dev.h"
 #include "kr_sampler.h"
 
 __global__ void kr_sample_prepare_kernel(float* __restrict__ logits, int vocab, float inv_temp, float penalty, const uint32_t* __restrict__ seen,
@@ -25,10 +26,7 @@ __global__ void kr_sample_prepare_kernel(float* __restrict__ logits, int vocab, 
     if (penalty != 0.0f && ((seen[i >> 5] >> (i & 31)) & 1u)) v -= penalty;
     v *= inv_temp;
     logits[i] = v;
-    float o = v == 0.0f ? 0.0f : v;                  // -0 == +0 for partial_cmp
-    uint32_t u = __float_as_uint(o);
-    u ^= (u >> 31) ? 0xFFFFFFFFu : 0x80000000u;      // monotone float -> uint
-    keys[i] = ((uint64_t)u << 32) | (uint32_t)(0xFFFFFFFFu - (uint32_t)i);
+    keys[i] = kr_sample_key(v, i);
 }
 
 
@@ -163,8 +161,10 @@ int kr_launch_sample(float* logits, int vocab, float temperature, int top_k, flo
     hipLaunchKernelGGL(kr_sample_prepare_kernel, dim3((vocab + 255) / 256), dim3(256), 0, st, logits, vocab, inv_temp, penalty, seen, keys_in);
     if (hipGetLastError() != hipSuccess) return 1;
     const int k = (top_k > 0 && top_k < vocab) ? top_k : vocab;
-    if (k <= KR_SEL_CAP) hipLaunchKernelGGL(kr_sample_select_kernel, dim3(1), dim3(1024), 0, st, (const uint64_t*)keys_in, vocab, k, keys_sorted);
-    else {
+    if (k <= KR_SEL_CAP) {
+        hipLaunchKernelGGL(kr_sample_select_kernel, dim3(1), dim3(1024), 0, st, (const uint64_t*)keys_in, vocab, k, keys_sorted);
+        if (hipGetLastError() != hipSuccess) return 1;
+    } else {
         if (hipcub::DeviceRadixSort::SortKeysDescending(temp, temp_bytes, keys_in, keys_sorted, vocab, 0, 64, st) != hipSuccess) return 1;
         (void)hipGetLastError();   // rocPRIM probes device attributes; a benign failed query must not surface as the next launch's error
     }

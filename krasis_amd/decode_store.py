@@ -423,17 +423,52 @@ class CpuDecodeStore:
         return (list(ids[:n]), out) if logits else list(ids[:n])
 
     def generate_multi(self, slots: Sequence[int], first_tokens: Sequence[int], start_positions: Sequence[int], max_tokens: int,
-                       stop_ids: Sequence[int] = ()) -> List[List[int]]:
+                       stop_ids: Sequence[int] = (), temperature=None, top_k=None, top_p=None, presence_penalty=None, rng_seeds=None) -> List[List[int]]:
         """kr_decode_generate_multi: greedy generation of the slots together; row i's tokens (and its slot afterwards) are those of
-        generate_batch(first_tokens[i], start_positions[i], max_tokens, stop_ids=stop_ids) at temperature 0 on that sequence alone."""
+        generate_batch(first_tokens[i], start_positions[i], max_tokens, stop_ids=stop_ids) at temperature 0 on that sequence alone.
+        Any of temperature / top_k / top_p / presence_penalty / rng_seeds given (a scalar or one value per row; the others default to 0, 0, 1.0,
+        0, 0): kr_decode_generate_multi_sample, row i = generate_batch(..., temperature[i], top_k[i], top_p[i], stop_ids, presence_penalty[i],
+        rng_seeds[i]) on that sequence alone."""
         self._need()
         n = len(slots)
         arr = lambda xs: (C.c_int32 * max(n, 1))(*xs)
         out = (C.c_int32 * max(n * max_tokens, 1))(); cnt = (C.c_int32 * max(n, 1))()
         stops = (C.c_int * max(len(stop_ids), 1))(*stop_ids)
-        check(self._lib.kr_decode_generate_multi(self._h, n, arr(slots), arr(first_tokens), arr(start_positions), max_tokens, stops, len(stop_ids),
-                                                 out, cnt, None))
+        params = (temperature, top_k, top_p, presence_penalty, rng_seeds)
+        if all(p is None for p in params):
+            check(self._lib.kr_decode_generate_multi(self._h, n, arr(slots), arr(first_tokens), arr(start_positions), max_tokens, stops, len(stop_ids),
+                                                     out, cnt, None))
+        else:
+            def rows(v, default, ctype):
+                v = default if v is None else v
+                v = list(v) if isinstance(v, (list, tuple, np.ndarray)) else [v] * n
+                if len(v) != n:
+                    raise ValueError(f"{len(v)} sampler values for {n} rows")
+                return (ctype * max(n, 1))(*v)
+            check(self._lib.kr_decode_generate_multi_sample(self._h, n, arr(slots), arr(first_tokens), arr(start_positions), max_tokens,
+                                                            rows(temperature, 0.0, C.c_float), rows(top_k, 0, C.c_int), rows(top_p, 1.0, C.c_float),
+                                                            rows(presence_penalty, 0.0, C.c_float), rows(rng_seeds, 0, C.c_uint64), stops, len(stop_ids),
+                                                            out, cnt, None))
         return [list(out[i * max_tokens: i * max_tokens + cnt[i]]) for i in range(n)]
+
+    def set_slot_sampler(self, slot: int, first_token: int, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0,
+                         presence_penalty: float = 0.0, rng_seed: int = 0) -> None:
+        """kr_decode_slot_sampler: start a request's sampler on a slot, as generate_batch starts its own: seen tokens = {first_token},
+        xorshift64 state = rng_seed (0 = wall clock), parameters kept with the slot for step_multi_sample (temperature 0, penalty 0 = greedy)."""
+        self._need()
+        check(self._lib.kr_decode_slot_sampler(self._h, slot, first_token, temperature, top_k, top_p, presence_penalty, rng_seed))
+
+    def step_multi_sample(self, slots: Sequence[int], tokens: Sequence[int], positions: Sequence[int], logits: bool = False):
+        """kr_decode_step_multi_sample: step_multi, but row i's id is drawn by slot slots[i]'s sampler (set_slot_sampler), exactly as
+        generate_batch draws it for that sequence alone.  Returns the ids, or (ids, logits f32 [n, vocab]) with logits=True (the model's
+        logits, before penalty and temperature)."""
+        self._need()
+        n = len(slots)
+        arr = lambda xs: (C.c_int32 * max(n, 1))(*xs)
+        ids = (C.c_int32 * max(n, 1))()
+        out = np.empty((n, self._vocab), np.float32) if logits else None
+        check(self._lib.kr_decode_step_multi_sample(self._h, n, arr(slots), arr(tokens), arr(positions), ids, out.ctypes.data if logits else None, None))
+        return (list(ids[:n]), out) if logits else list(ids[:n])
 
     def generate_stream(self, first_token: int, start_position: int, max_tokens: int, temperature: float, top_k: int, top_p: float,
                         stop_ids: Sequence[int], tokenizer, presence_penalty: float, on_token, rng_seed: int = 0) -> int:
