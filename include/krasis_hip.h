@@ -347,15 +347,17 @@ int kr_decode_generate_lookup(kr_decode_store* s, const int32_t* context, int n_
 int kr_lookup_draft(const int32_t* history, int n_history, int ngram_max, int max_draft, int32_t* draft_out);
 
 /* ---- exact batched decode of many sequences held in device slots (docs/design/13-multi-sequence.md).  Row i of a step is bit-identical to
- * kr_decode_step on that sequence alone (logits, greedy id, the KV row it appends, conv and recurrent state).  Exact mode only: a tolerance bit of
- * kr_decode_set_attention_mode, MLA layers, native-GGUF MoE layers, expert parallelism and a pending verify are refused; a refused call changes
- * nothing.  The steps touch only the named slots and their own scratch (never the store's own sequence, logits, last token or decode graph);
+ * kr_decode_step on that sequence alone (logits, greedy id, the KV row it appends -- for an MLA layer the compressed-KV row [kv_lora_rank] and the
+ * rope-key row [rope dim], docs/design/15-multi-mla.md -- conv and recurrent state).  Exact mode only: a tolerance bit of
+ * kr_decode_set_attention_mode, native-GGUF MoE layers, expert parallelism, an MLA geometry other than kv_lora_rank 512 / 256 with rope dim 64 and
+ * a pending verify are refused; a refused call changes nothing.  The steps touch only the named slots and their own scratch (never the store's own sequence, logits, last token or decode graph);
  * reset_state / set_state / fill_state_synthetic / prefill / verify never touch slots; kr_decode_destroy frees them. */
 #define KR_MULTI_MAX 256
 /* n_slots sequences of up to max_seq positions each, zero-initialised (like kr_decode_reset_state); replaces existing slots; n_slots == 0 frees
    them.  KV element type = the store's at this call.  *bytes_out (may be NULL) = device bytes of all slots. */
 int kr_decode_slots_create(kr_decode_store* s, int n_slots, int max_seq, size_t* bytes_out);
-/* the store's own sequence -> slot: KV rows [0, seq_len) of every GQA layer, conv + recurrent state of every linear-attention layer.
+/* the store's own sequence -> slot: KV rows [0, seq_len) of every GQA layer, compressed-KV and rope-key rows [0, seq_len) of every MLA layer,
+   conv + recurrent state of every linear-attention layer.
    0 <= seq_len <= min(store kv_max_seq, slot max_seq) */
 int kr_decode_slot_save(kr_decode_store* s, int slot, int seq_len);
 /* slot -> the store's own sequence (the same parts): decode_step / prefill / verify then continue it at position seq_len */

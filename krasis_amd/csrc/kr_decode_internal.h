@@ -33,10 +33,11 @@ struct DLayer {
 };
 
 // sequence slots of the multi-sequence step (kr_decode_multi.cpp, docs/design/13-multi-sequence.md): per store layer one buffer of n slots --
-// linear attention: conv state [n][conv_dim][4] (conv) and recurrent state [n][nv][dk][dv] (recur); GQA: K / V caches [n][max_seq][nkv][hd] (conv / recur)
+// linear attention: conv state [n][conv_dim][4] (conv) and recurrent state [n][nv][dk][dv] (recur); GQA: K / V caches [n][max_seq][nkv][hd];
+// MLA: compressed-KV rows [n][max_seq][klr] and rope-key rows [n][max_seq][rd] (docs/design/15-multi-mla.md)
 struct kr_multi_state {
     int n_slots = 0, max_seq = 0, kv_fp8 = 0;
-    std::vector<DevBuf> a, b;                  // per layer: LA conv / recurrent state, GQA K / V
+    std::vector<DevBuf> a, b;                  // per layer: LA conv / recurrent state, GQA K / V, MLA latent / rope-key rows
     std::vector<size_t> a_stride, b_stride;    // per layer: bytes per slot
     DevBuf rows, ids, logits, scores, scratch; // step: [slots | tokens | positions] (device), greedy ids, [n][vocab] logits, attention scores, the arena
     // per-slot samplers (kr_decode_slot_sampler, docs/design/14-multi-sampling.md): allocated for every slot on the first call; empty = every slot greedy

@@ -1,9 +1,9 @@
 // kr_decode_multi.cpp -- exact batched decode of many sequences held in device slots (docs/design/13-multi-sequence.md).
 //
-// A slot holds one sequence's per-layer state on the device: the KV rows of every GQA layer, the conv + recurrent state of every
-// linear-attention layer.  kr_decode_step_multi advances B slots by one token each in one pass through the prompt pass's per-layer sequence
+// A slot holds one sequence's per-layer state on the device: the KV rows of every GQA layer, the compressed-KV and rope-key rows of every MLA
+// layer (docs/design/15-multi-mla.md), the conv + recurrent state of every linear-attention layer.  kr_decode_step_multi advances B slots by one token each in one pass through the prompt pass's per-layer sequence
 // (kr_multi_pass, kr_decode_prefill.cpp): the row-wise sections (norms, projection GEMMs, router, experts, lm_head) are the prompt pass's own,
-// and each row of them equals the decode step bit for bit whatever rows share the pass; the two sections that tie rows to one sequence run
+// and each row of them equals the decode step bit for bit whatever rows share the pass; the sections that tie rows to one sequence (linear attention, GQA, MLA) run
 // per-slot kernels (kr_multi.hip) with the decode step's arithmetic.  So row i of a step carries exactly the bits kr_decode_step gives on
 // that sequence alone.  The store's own sequence is the hand-over point: prompt pass -> kr_decode_slot_save -> steps -> kr_decode_slot_load.
 #include <algorithm>
@@ -23,7 +23,7 @@ int multi_ready(kr_decode_store* s) {
     if ((int)s->layers.size() != s->n_layers) return kr_fail(KR_ERR_STATE, "finalize_decode was not called");
     return KR_OK;
 }
-// what the multi-sequence step does not run (cf. kr_spec_refuse): tolerance modes, MLA, native-GGUF MoE layers, expert parallelism, geometries
+// what the multi-sequence step does not run (cf. kr_spec_refuse): tolerance modes, native-GGUF MoE layers, expert parallelism, geometries
 // the per-slot kernels do not cover; a pending verify
 int multi_refuse(kr_decode_store* s) {
     if (int rc = kr_spec_pending_fail(s)) return rc;
@@ -33,7 +33,8 @@ int multi_refuse(kr_decode_store* s) {
     if (e->ep) return kr_fail(KR_ERR_STATE, "the multi-sequence step does not run under expert parallelism");
     for (size_t i = 0; i < s->layers.size(); i++) {
         const DLayer& L = s->layers[i];
-        if (L.attn == ATTN_MLA) return kr_fail(KR_ERR_STATE, "the multi-sequence step does not cover MLA layers (layer %zu)", i);
+        if (L.attn == ATTN_MLA && !kr_multi_mla_ok(L.klr, L.nd, L.rd))
+            return kr_fail(KR_ERR_VALUE, "multi-sequence step: MLA geometry kv_lora_rank %d nope %d rope %d not covered (kv_lora_rank 512 / 256, rope 64)", L.klr, L.nd, L.rd);
         if (L.mlp == MLP_MOE) {
             if (s->own_eng || L.moe_layer >= (int)e->layers.size()) return kr_fail(KR_ERR_STATE, "set_moe_store was not called (MoE layer %d has no engine)", L.moe_layer);
             if (e->layers[L.moe_layer].gguf)
@@ -52,12 +53,15 @@ int need_slots(kr_decode_store* s) {
         return kr_fail(KR_ERR_STATE, "the slots hold %s KV rows but the store uses %s now: create them again", s->multi->kv_fp8 ? "E4M3" : "FP16", s->kv_fp8 ? "E4M3" : "FP16");
     return KR_OK;
 }
-// the rows of one step: distinct slots in range, tokens in the vocabulary, positions inside the slot and the rope table
+// the rows of one step: distinct slots in range, tokens in the vocabulary, positions inside the slot and the rope tables (the store's, and every MLA
+// layer's own: the shortest bounds the step)
 int check_rows(kr_decode_store* s, int n, const int32_t* slots, const int32_t* tokens, const int32_t* positions, int extra) {
     const kr_multi_state& M = *s->multi;
     if (n < 1 || n > KR_MULTI_MAX) return kr_fail(KR_ERR_VALUE, "%d rows, must be in [1, %d]", n, KR_MULTI_MAX);
     if (!slots || !tokens || !positions) return kr_fail(KR_ERR_VALUE, "null slots / tokens / positions");
     std::vector<char> seen((size_t)M.n_slots, 0);
+    int mla_rope = 0; bool has_mla = false;
+    for (const DLayer& L : s->layers) if (L.attn == ATTN_MLA) { mla_rope = has_mla ? std::min(mla_rope, L.mla_rope_seq) : L.mla_rope_seq; has_mla = true; }
     for (int i = 0; i < n; i++) {
         if (slots[i] < 0 || slots[i] >= M.n_slots) return kr_fail(KR_ERR_VALUE, "row %d: slot %d out of range [0, %d)", i, slots[i], M.n_slots);
         if (seen[(size_t)slots[i]]++) return kr_fail(KR_ERR_VALUE, "slot %d is named twice", slots[i]);
@@ -65,6 +69,7 @@ int check_rows(kr_decode_store* s, int n, const int32_t* slots, const int32_t* t
         const int last = positions[i] + extra;     // the last position this call consumes
         if (positions[i] < 0 || last >= M.max_seq) return kr_fail(KR_ERR_VALUE, "row %d: positions [%d, %d] outside the slot's [0, %d)", i, positions[i], last, M.max_seq);
         if (s->max_rope_seq > 0 && last >= s->max_rope_seq) return kr_fail(KR_ERR_VALUE, "row %d: position %d past the rope table (%d)", i, last, s->max_rope_seq);
+        if (has_mla && last >= mla_rope) return kr_fail(KR_ERR_VALUE, "row %d: position %d past the MLA rope table (%d)", i, last, mla_rope);
     }
     return KR_OK;
 }
@@ -141,7 +146,8 @@ int order_after_store(kr_decode_store* s, hipStream_t st) {
     KR_HIP(hipStreamWaitEvent(st, M.ev, 0));
     return KR_OK;
 }
-// slot <-> the store's own sequence: KV rows [0, seq_len) of every GQA layer, conv + recurrent state of every linear-attention layer
+// slot <-> the store's own sequence: KV rows [0, seq_len) of every GQA layer, compressed-KV and rope-key rows [0, seq_len) of every MLA layer, conv +
+// recurrent state of every linear-attention layer
 int slot_copy(kr_decode_store* s, int slot, int seq_len, bool save) {
     if (int rc = multi_ready(s)) return rc;
     if (int rc = need_slots(s)) return rc;
@@ -151,7 +157,8 @@ int slot_copy(kr_decode_store* s, int slot, int seq_len, bool save) {
     const int lim = std::min(s->kv_max_seq, M.max_seq);
     if (seq_len < 0 || seq_len > lim) return kr_fail(KR_ERR_VALUE, "seq_len %d outside [0, %d] (store kv_max_seq %d, slot max_seq %d)", seq_len, lim, s->kv_max_seq, M.max_seq);
     for (size_t i = 0; i < s->layers.size(); i++)
-        if (s->layers[i].attn == ATTN_GQA && !s->layers[i].kv_k.p) return kr_fail(KR_ERR_STATE, "set_decode_state was not called (no KV cache for layer %zu)", i);
+        if ((s->layers[i].attn == ATTN_GQA || s->layers[i].attn == ATTN_MLA) && (!s->layers[i].kv_k.p || !s->layers[i].kv_v.p))
+            return kr_fail(KR_ERR_STATE, "set_decode_state was not called (no %s cache for layer %zu)", s->layers[i].attn == ATTN_MLA ? "MLA" : "KV", i);
     KR_HIP(hipSetDevice(s->eng->device));
     KR_HIP(hipDeviceSynchronize());          // steps / prompt passes still in flight on any stream read or write both sides
     hipStream_t st = s->eng->stream;
@@ -162,6 +169,7 @@ int slot_copy(kr_decode_store* s, int slot, int seq_len, bool save) {
         void *sa, *sb; size_t na, nb;
         if (L.attn == ATTN_LA) { sa = L.conv_state.p; sb = L.recur_state.p; na = M.a_stride[i]; nb = M.b_stride[i]; }
         else if (L.attn == ATTN_GQA) { sa = L.kv_k.p; sb = L.kv_v.p; na = nb = (size_t)seq_len * L.nkv * L.hd * (M.kv_fp8 ? 1 : 2); }
+        else if (L.attn == ATTN_MLA) { sa = L.kv_k.p; sb = L.kv_v.p; na = (size_t)seq_len * L.klr * (M.kv_fp8 ? 1 : 2); nb = (size_t)seq_len * L.rd * (M.kv_fp8 ? 1 : 2); }
         else continue;
         if (na) KR_HIP(hipMemcpyAsync(save ? (void*)a : sa, save ? sa : (void*)a, na, hipMemcpyDeviceToDevice, st));
         if (nb) KR_HIP(hipMemcpyAsync(save ? (void*)b : sb, save ? sb : (void*)b, nb, hipMemcpyDeviceToDevice, st));
@@ -245,8 +253,6 @@ int generate_impl(kr_decode_store* s, int n, const int32_t* slots, const int32_t
 extern "C" int kr_decode_slots_create(kr_decode_store* s, int n_slots, int max_seq, size_t* bytes_out) {
     if (int rc = multi_ready(s)) return rc;
     if (n_slots < 0 || (n_slots > 0 && max_seq < 1)) return kr_fail(KR_ERR_VALUE, "bad slot geometry: %d slots of %d positions", n_slots, max_seq);
-    for (size_t i = 0; i < s->layers.size(); i++)
-        if (s->layers[i].attn == ATTN_MLA) return kr_fail(KR_ERR_STATE, "sequence slots do not cover MLA layers (layer %zu)", i);
     KR_HIP(hipSetDevice(s->eng->device));
     KR_HIP(hipDeviceSynchronize());          // a step in flight may still use the old slots
     s->multi.reset();
@@ -261,6 +267,7 @@ extern "C" int kr_decode_slots_create(kr_decode_store* s, int n_slots, int max_s
         const DLayer& L = s->layers[i];
         if (L.attn == ATTN_LA) { M->a_stride[i] = (size_t)(2 * L.nk * L.dk + L.nv * L.dv) * L.kd * 4; M->b_stride[i] = (size_t)L.nv * L.dk * L.dv * 4; }
         else if (L.attn == ATTN_GQA) M->a_stride[i] = M->b_stride[i] = (size_t)max_seq * L.nkv * L.hd * (s->kv_fp8 ? 1 : 2);
+        else if (L.attn == ATTN_MLA) { M->a_stride[i] = (size_t)max_seq * L.klr * (s->kv_fp8 ? 1 : 2); M->b_stride[i] = (size_t)max_seq * L.rd * (s->kv_fp8 ? 1 : 2); }
         for (int h = 0; h < 2; h++) {
             DevBuf& d = h ? M->b[i] : M->a[i];
             const size_t bytes = (h ? M->b_stride[i] : M->a_stride[i]) * (size_t)n_slots;

@@ -58,6 +58,7 @@ struct KrMlaArgs {   // decode.rs:2993-3252
     float* pf_sc; int pf_sc_ld;   // prompt pass, exact mode: score scratch [n_tok * nh][pf_sc_ld] + n_tok * nh * (1 + pf_sc_ld / 32) floats (1 / sum, row maxima) for the matrix-core passes; null: per-token launches
 };
 void kr_launch_mla(const KrMlaArgs& a, int max_seq, hipStream_t s, int n_tok = 1);
+void kr_launch_mla_wvc(const KrMlaArgs& a, hipStream_t s, int n_tok);   // launch 3 alone, token dimension (a.step == nullptr): the multi-sequence step below 32 rows
 size_t kr_mla_flash_decode_chunks(int max_seq);   // chunks of the FAST split-KV decode (sizes the partial buffers)
 void kr_mla_attn_prepare(const KrMlaArgs& a, int max_seq);   // outside graph capture: LDS window of the staged attention kernel
 void kr_launch_rmsnorm_seq(float* x, const float* w, int n, float eps, hipStream_t s, int rows = 1, int ld = 0);

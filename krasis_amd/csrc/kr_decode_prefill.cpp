@@ -174,8 +174,8 @@ static int run_layer(kr_decode_store* s, Chunk& cx, size_t li) {
         // MLA (decode.rs:2993-3252): batched projections on the GEMM, then the three decode launches with a token dimension.  The
         // prep launch appends every token's latent / rope rows before the attention launch reads them, so token t of the chunk
         // sees exactly the cache decode_step would have built.
-        if (!L.kv_k.p) return kr_fail(KR_ERR_STATE, "set_decode_state was not called (no MLA cache for layer %zu)", li);
-        if (L.mla_rope_seq < pos0 + Cc) return kr_fail(KR_ERR_VALUE, "prompt exceeds the MLA rope table (%d)", L.mla_rope_seq);
+        if (!L.kv_k.p && !cx.m_slots) return kr_fail(KR_ERR_STATE, "set_decode_state was not called (no MLA cache for layer %zu)", li);
+        if (!cx.m_slots && L.mla_rope_seq < pos0 + Cc) return kr_fail(KR_ERR_VALUE, "prompt exceeds the MLA rope table (%d)", L.mla_rope_seq);
         const int nkv = s->weights[L.kva_wid]->rows, nq = L.nh * (L.nd + L.rd), oc = s->weights[L.o_wid]->cols;
         if (int rc = pf_gemm(s, L.kva_wid, X(B), Cc, B.pb, nkv, st)) return rc;
         if (L.mq_wid >= 0) {
@@ -188,16 +188,31 @@ static int run_layer(kr_decode_store* s, Chunk& cx, size_t li) {
             pf_rows(s, B.pc, Cc, qlr, qlr, B, true, st);
             if (int rc = pf_gemm(s, L.mqb_wid, Y(B), Cc, B.pa, nq, st)) return rc;
         }
-        KrMlaArgs a{};
-        a.step = nullptr; a.pos0 = pos0; a.kv_out = B.pb; a.ld_kv = nkv; a.q_full = B.pa; a.ld_q = nq;
-        a.kv_a_norm = (const float*)L.kv_a_norm.p; a.w_kc = (const float*)L.w_kc.p; a.w_vc = (const float*)L.w_vc.p;
-        a.rope_cos = (const float*)L.mla_cos.p; a.rope_sin = (const float*)L.mla_sin.p;
-        a.ckv_cache = L.kv_k.p; a.kpe_cache = L.kv_v.p; a.kv_fp8 = s->kv_fp8; a.q_abs = B.q; a.q_pe = B.z; a.attn_lat = B.recur; a.v_proj = B.attn;
-        a.nh = L.nh; a.klr = L.klr; a.nd = L.nd; a.rd = L.rd; a.vhd = L.vhd; a.eps = s->eps; a.sm_scale = L.sm_scale; a.fast = s->attn_fast;
-        if (!s->attn_fast && cx.scores) { a.pf_sc = cx.scores; a.pf_sc_ld = (pos0 + Cc + 63) & ~63; }      // exact mode: this chunk's score scratch for the matrix-core passes
-        kr_pf_wait(st, cx.sy.wait_b);            // the latent / rope rows of the earlier chunks (the three MLA launches append and read in one go)
-        kr_launch_mla(a, s->kv_max_seq, st, Cc);
-        kr_pf_rec(st, cx.sy.rec_b);
+        if (cx.m_slots) {      // multi-sequence step: each row appends to and attends over its own slot at its own position (kr_multi.hip); row positions
+                               // were bounded by the shortest MLA rope table before the pass (check_rows, kr_decode_multi.cpp)
+            kr_multi_state& M = *s->multi;
+            KrMultiMlaArgs m{};
+            m.slots = cx.m_slots; m.positions = cx.m_pos; m.kv_out = B.pb; m.ld_kv = nkv; m.q_full = B.pa; m.ld_q = nq;
+            m.kv_a_norm = (const float*)L.kv_a_norm.p; m.w_kc = (const float*)L.w_kc.p; m.w_vc = (const float*)L.w_vc.p;
+            m.rope_cos = (const float*)L.mla_cos.p; m.rope_sin = (const float*)L.mla_sin.p;
+            m.ckv_cache = M.a[li].p; m.kpe_cache = M.b[li].p; m.ckv_stride = M.a_stride[li]; m.kpe_stride = M.b_stride[li]; m.kv_fp8 = M.kv_fp8;
+            m.q_abs = B.q; m.q_pe = B.z; m.attn_lat = B.recur; m.v_proj = B.attn; m.scores = (float*)M.scores.p; m.sc_ld = cx.m_sc_ld;
+            m.nh = L.nh; m.klr = L.klr; m.nd = L.nd; m.rd = L.rd; m.vhd = L.vhd; m.eps = s->eps; m.sm_scale = L.sm_scale;
+            if (nkv < L.klr + L.rd) return kr_fail(KR_ERR_VALUE, "kv_a_proj rows %d < kv_lora_rank + rope dim", nkv);
+            if (oc != L.nh * L.vhd) return kr_fail(KR_ERR_VALUE, "o_proj cols %d != nh*v_head_dim", oc);
+            if (kr_launch_multi_mla(m, Cc, st)) return kr_fail(KR_ERR_VALUE, "unsupported MLA geometry for the multi-sequence step");
+        } else {
+            KrMlaArgs a{};
+            a.step = nullptr; a.pos0 = pos0; a.kv_out = B.pb; a.ld_kv = nkv; a.q_full = B.pa; a.ld_q = nq;
+            a.kv_a_norm = (const float*)L.kv_a_norm.p; a.w_kc = (const float*)L.w_kc.p; a.w_vc = (const float*)L.w_vc.p;
+            a.rope_cos = (const float*)L.mla_cos.p; a.rope_sin = (const float*)L.mla_sin.p;
+            a.ckv_cache = L.kv_k.p; a.kpe_cache = L.kv_v.p; a.kv_fp8 = s->kv_fp8; a.q_abs = B.q; a.q_pe = B.z; a.attn_lat = B.recur; a.v_proj = B.attn;
+            a.nh = L.nh; a.klr = L.klr; a.nd = L.nd; a.rd = L.rd; a.vhd = L.vhd; a.eps = s->eps; a.sm_scale = L.sm_scale; a.fast = s->attn_fast;
+            if (!s->attn_fast && cx.scores) { a.pf_sc = cx.scores; a.pf_sc_ld = (pos0 + Cc + 63) & ~63; }      // exact mode: this chunk's score scratch for the matrix-core passes
+            kr_pf_wait(st, cx.sy.wait_b);            // the latent / rope rows of the earlier chunks (the three MLA launches append and read in one go)
+            kr_launch_mla(a, s->kv_max_seq, st, Cc);
+            kr_pf_rec(st, cx.sy.rec_b);
+        }
         if (oc != L.nh * L.vhd) return kr_fail(KR_ERR_VALUE, "o_proj cols %d != nh*v_head_dim", oc);
         pf_rows(s, B.attn, Cc, oc, oc, B, true, st);
         if (int rc = pf_gemm(s, L.o_wid, Y(B), Cc, B.hid, H, st)) return rc;
@@ -666,7 +681,7 @@ extern "C" int kr_decode_commit(kr_decode_store* s, int n_keep) {
 
 // ------------------------------------------------------------------------------------------------
 // the multi-sequence step (kr_decode_multi.cpp, docs/design/13-multi-sequence.md): one chunk of n rows, row b = the next token of slot slots[b].
-// Every row-wise section of run_layer runs unchanged; the linear-attention and GQA sections take the per-slot kernels (kr_multi.hip).  All-row
+// Every row-wise section of run_layer runs unchanged; the linear-attention, GQA and MLA sections take the per-slot kernels (kr_multi.hip).  All-row
 // logits as in the verify pass.  Engine buffer set KR_PF_MAX_DEPTH - 1; the caller has ordered this pass after everything the store queued.
 // ------------------------------------------------------------------------------------------------
 int kr_multi_pass(kr_decode_store* s, int n, const int32_t* d_rows, int max_pos, hipStream_t st) {
@@ -674,7 +689,7 @@ int kr_multi_pass(kr_decode_store* s, int n, const int32_t* d_rows, int max_pos,
     PfLayout Lo;
     if (int rc = pf_layout(s, (size_t)n, true, true, st, Lo)) return rc;
     int nh_max = 1;
-    for (const DLayer& L : s->layers) if (L.attn == ATTN_GQA) nh_max = std::max(nh_max, L.nh);
+    for (const DLayer& L : s->layers) if (L.attn == ATTN_GQA || L.attn == ATTN_MLA) nh_max = std::max(nh_max, L.nh);      // a score row per query head of either kind
     const int sc_ld = (max_pos + 1 + 31) & ~31;
     if (M.scratch.ensure(Lo.total) || M.scores.ensure((size_t)n * nh_max * sc_ld * 4) || M.logits.ensure((size_t)n * s->vocab * 4))
         return kr_fail(KR_ERR_HIP, "hipMalloc of the multi-sequence step's scratch (%zu MiB) failed", (Lo.total + (size_t)n * (nh_max * sc_ld + s->vocab) * 4) >> 20);

@@ -12,6 +12,7 @@
 #include "kr_lds_optin.h"
 #include "kr_router.h"
 #include "kr_device.h"
+#include "kr_mla_dev.h"
 #include "kr_libm.h"
 #include "kr_decode_ops.h"
 #include "kr_decode_fast.h"
@@ -26,40 +27,7 @@ __device__ unsigned long long kr_mstamps[32];
 #define KR_MSTAMP(i) do { } while (0)
 #endif
 
-__device__ __forceinline__ float kr_mla_hsum8(float v) {   // lo+hi, movehdup, movehl (same tree as every hsum in decode.rs)
-    v = v + __shfl_xor(v, 4);
-    v = v + __shfl_xor(v, 1);
-    v = v + __shfl_xor(v, 2);
-    return v;
-}
-__device__ __forceinline__ float kr_h2f(uint16_t h) { return __half2float(__ushort_as_half(h)); }
-// cache element i of a row / of the whole cache: FP16 (reference CPU decode) or E4M3 (the GPU cache dtype, extended to the latent cache)
-template <bool FP8> __device__ __forceinline__ float kr_mla_ld(const void* base, size_t i) {
-    if (FP8) return kr_e4m3_to_f32(reinterpret_cast<const uint8_t*>(base)[i]);
-    return kr_h2f(reinterpret_cast<const uint16_t*>(base)[i]);
-}
-template <bool FP8> __device__ __forceinline__ float kr_stage_val(const unsigned char* row, int i) {   // element i of a staged (LDS) row
-    if (FP8) return kr_e4m3_to_f32(row[i]);
-    _Float16 hv; __builtin_memcpy(&hv, row + 2 * i, 2);
-    return (float)hv;
-}
-template <bool FP8> __device__ __forceinline__ void kr_mla_st(void* base, size_t i, float v) {
-    if (FP8) reinterpret_cast<uint8_t*>(base)[i] = kr_f32_to_e4m3(v);
-    else reinterpret_cast<uint16_t*>(base)[i] = __half_as_ushort(__float2half_rn(v));
-}
-
-// 16 cooperating lanes (c = lane & 15) evaluate mla_attn_dot_fp16_avx2 / the w_vc row dot: chain (a = c >> 3, l = c & 7) owns the
-// 8-blocks i with i % 2 == a (an odd trailing block goes to accumulator 0), ascending.  Every lane of the 16 returns the result.
-template <typename LoadB>
-__device__ __forceinline__ float kr_dot2acc(const float* q, LoadB loadb, int dim, int c) {
-    const int n8 = dim >> 3, a = c >> 3, l = c & 7, paired = (n8 >> 1) << 1;
-    float acc = 0.0f;
-    for (int i = a; i < paired; i += 2) acc = __builtin_fmaf(q[i * 8 + l], loadb(i * 8 + l), acc);
-    if ((n8 & 1) && a == 0) acc = __builtin_fmaf(q[(n8 - 1) * 8 + l], loadb((n8 - 1) * 8 + l), acc);
-    const float other = __shfl_xor(acc, 8);
-    const float s8 = a == 0 ? acc + other : other + acc;   // _mm256_add_ps(acc0, acc1)
-    return kr_mla_hsum8(s8);
-}
+// cache element codecs, kr_dot2acc and the sections of the prep launch: kr_mla_dev.h (shared with the multi-sequence step, kr_multi.hip)
 
 // ---- launch 1: prep --------------------------------------------------------------------------------------------------
 // blocks [0, nh*klr/64): absorb tile (h, jt); the jt == 0 block of each head also de-interleaves + ropes q_pe[h].
@@ -75,63 +43,16 @@ template <bool FP8>
 __global__ void __launch_bounds__(64) kr_mla_prep_kernel(KrMlaArgs a) {
     __shared__ float sh[640];
     const int pos = kr_mla_token(a, blockIdx.y);
-    const int tiles = a.absorb_done ? 1 : a.klr / 64, nb_abs = a.nh * tiles, hd = a.nd + a.rd, half = a.rd / 2;      // absorb_done: one workgroup per head (rope of q_pe only)
-    const int t = threadIdx.x;
+    const int tiles = a.absorb_done ? 1 : a.klr / 64, nb_abs = a.nh * tiles, hd = a.nd + a.rd;      // absorb_done: one workgroup per head (rope of q_pe only)
     if ((int)blockIdx.x < nb_abs) {
-        const int h = blockIdx.x / tiles, jt = blockIdx.x % tiles, j = jt * 64 + t;
+        const int h = blockIdx.x / tiles, jt = blockIdx.x % tiles;
         const float* qh = a.q_full + (size_t)h * hd;
-        if (!a.absorb_done) {
-        for (int i = t; i < a.nd; i += 64) sh[i] = qh[i];
-        __syncthreads();
-        const float* w = a.w_kc + (size_t)h * a.nd * a.klr + j;
-        float o = 0.0f;
-        int i = 0;
-        for (; i + 16 <= a.nd; i += 16) {
-            float wv[16];
-#pragma unroll
-            for (int u = 0; u < 16; u++) wv[u] = __builtin_nontemporal_load(w + (size_t)(i + u) * a.klr);
-#pragma unroll
-            for (int u = 0; u < 16; u++) o = __builtin_fmaf(sh[i + u], wv[u], o);
-        }
-        for (; i < a.nd; i++) o = __builtin_fmaf(sh[i], w[(size_t)i * a.klr], o);
-        a.q_abs[(size_t)h * a.klr + j] = o;
-        }
-        if (jt == 0 && t < half) {   // decode.rs:3113-3128
-            const float x1 = qh[a.nd + 2 * t], x2 = qh[a.nd + 2 * t + 1];
-            const float c = a.rope_cos[(size_t)pos * half + t], s = a.rope_sin[(size_t)pos * half + t];
-            a.q_pe[(size_t)h * a.rd + t] = x1 * c - x2 * s;
-            a.q_pe[(size_t)h * a.rd + half + t] = x2 * c + x1 * s;
-        }
+        if (!a.absorb_done) kr_mla_absorb_tile(qh, a.w_kc + (size_t)h * a.nd * a.klr, a.q_abs + (size_t)h * a.klr, jt * 64 + (int)threadIdx.x, a.nd, a.klr, sh);
+        if (jt == 0) kr_mla_rope_qpe(qh, a.q_pe + (size_t)h * a.rd, a.rope_cos, a.rope_sin, pos, a.nd, a.rd / 2);
         return;
     }
-    // ---- compressed KV ----
-    float* x = sh;                                  // klr <= 576 values + 1 slot for rms
-    for (int i = t; i < a.klr; i += 64) x[i] = a.kv_out[i];
-    __syncthreads();
-    if (t == 0) {                                   // decode.rs:3025-3028: scalar sequential sum, mul and add separate
-        float ss = 0.0f; int i = 0;
-        for (; i + 8 <= a.klr; i += 8) {
-            float v[8];
-#pragma unroll
-            for (int u = 0; u < 8; u++) { v[u] = x[i + u]; v[u] = v[u] * v[u]; }
-#pragma unroll
-            for (int u = 0; u < 8; u++) ss += v[u];
-        }
-        for (; i < a.klr; i++) ss += x[i] * x[i];
-        sh[639] = 1.0f / sqrtf(ss / (float)a.klr + a.eps);
-    }
-    __syncthreads();
-    const float rms = sh[639];
-    for (int i = t; i < a.klr; i += 64) {
-        const float v = x[i] * (rms * a.kv_a_norm[i]);                                     // x *= rms * w (decode.rs:3030)
-        kr_mla_st<FP8>(a.ckv_cache, (size_t)pos * a.klr + i, v);
-    }
-    if (t < half) {                                                                        // decode.rs:3098-3107, 3131-3140
-        const float x1 = a.kv_out[a.klr + 2 * t], x2 = a.kv_out[a.klr + 2 * t + 1];
-        const float c = a.rope_cos[(size_t)pos * half + t], s = a.rope_sin[(size_t)pos * half + t];
-        kr_mla_st<FP8>(a.kpe_cache, (size_t)pos * a.rd + t, x1 * c - x2 * s);
-        kr_mla_st<FP8>(a.kpe_cache, (size_t)pos * a.rd + half + t, x2 * c + x1 * s);
-    }
+    // ---- compressed KV: RMSNorm, k_pe de-interleave + RoPE, cache append at `pos`
+    kr_mla_append_row<FP8>(a.kv_out, a.kv_a_norm, a.rope_cos, a.rope_sin, a.ckv_cache, a.kpe_cache, pos, a.klr, a.rd, a.eps, sh);
 }
 
 // ---- launch 2: attention, one workgroup (512 threads) per head.  dynamic LDS: klr + rd + seq_max + 8 floats --------------
@@ -810,6 +731,10 @@ void kr_launch_mla(const KrMlaArgs& a_in, int max_seq, hipStream_t s, int n_tok)
     // kr_route_mfma.hip), bit-identical to the per-token launch below
     if (!a.step && n_tok >= 32 && kr_launch_mla_wvc_mfma(a.w_vc, a.attn_lat, a.v_proj, n_tok, a.nh, a.vhd, a.klr, s) == 0) return;
     if (dfast) { hipLaunchKernelGGL(kr_mla_wvc_fast_kernel, dim3((a.vhd + 7) / 8, a.nh), dim3(256), 0, s, a); return; }
+    hipLaunchKernelGGL(kr_mla_wvc_kernel, dim3((a.vhd + 7) / 8, a.nh, n_tok), dim3(128), (size_t)a.klr * 4, s, a);
+}
+// the per-token w_vc launch on its own (the multi-sequence step below 32 rows): a.step == nullptr, row t of attn_lat / v_proj at t * their natural size
+void kr_launch_mla_wvc(const KrMlaArgs& a, hipStream_t s, int n_tok) {
     hipLaunchKernelGGL(kr_mla_wvc_kernel, dim3((a.vhd + 7) / 8, a.nh, n_tok), dim3(128), (size_t)a.klr * 4, s, a);
 }
 void kr_launch_rmsnorm_seq(float* x, const float* w, int n, float eps, hipStream_t s, int rows, int ld) {

@@ -33,5 +33,23 @@ struct KrMultiGqaArgs {
 // 0: launched; 1: geometry not covered (hd 64 / 128 / 256, nh % nkv == 0)
 int kr_launch_multi_gqa(const KrMultiGqaArgs& a, int B, hipStream_t st);
 
+// MLA, one token per row: rope of q_pe, latent RMSNorm + rope of k_pe, both rows appended to the row's slot, attention over the slot's rows [0, pos]
+// in the latent space, w_kc absorption before and w_vc projection after (the row-wise launches of the prompt pass)
+struct KrMultiMlaArgs {
+    const int* slots; const int* positions;    // [B] device
+    const float* kv_out; int ld_kv;            // kv_a projection rows [B][ld_kv], [klr | rd] each
+    const float* q_full; int ld_q;             // q (or q_b) projection rows [B][ld_q], per head [nd | rd]
+    const float *kv_a_norm, *w_kc, *w_vc, *rope_cos, *rope_sin;
+    void *ckv_cache, *kpe_cache; size_t ckv_stride, kpe_stride; int kv_fp8;   // slot s: cache + s * stride BYTES, [max_seq][klr] / [max_seq][rd], FP16 or E4M3
+    float *q_abs, *q_pe, *attn_lat, *v_proj;   // [B][nh * klr], [B][nh * rd], [B][nh * klr], [B][nh * vhd]
+    float* scores; int sc_ld;                  // scratch [B][nh][sc_ld], sc_ld >= the longest row's pos + 1 rounded up to 32
+    int nh, klr, nd, rd, vhd; float eps, sm_scale;
+    int absorb_done;                           // set by the launch: q_abs came from the matrix-core absorption, the prep launch skips its tiles
+};
+// the geometries the per-slot MLA kernels are specialised for (klr 512 / 256 with rd 64; nd within the prep launch's LDS row)
+int kr_multi_mla_ok(int klr, int nd, int rd);
+// 0: launched (absorption, prep, attention, w_vc projection); 1: geometry not covered
+int kr_launch_multi_mla(const KrMultiMlaArgs& a, int B, hipStream_t st);
+
 // per row b < B of logits [B][ld]: out[b] = first-maximum argmax of the row's first V values (kr_argmax_kernel's rule)
 void kr_launch_multi_argmax(const float* logits, size_t ld, int V, int B, int* out, hipStream_t st);

@@ -5,6 +5,9 @@
 #include "kr_device.h"
 #include "kr_libm.h"
 #include "kr_multi.h"
+#include "kr_mla_dev.h"
+#include "kr_decode_ops.h"
+#include "kr_router.h"
 #include "kr_sample_dev.h"
 
 // hsum over 8 consecutive lanes in the order of the reference's hsum (kr_decode_ops.hip kr_hsum8)
@@ -287,6 +290,210 @@ int kr_launch_multi_gqa(const KrMultiGqaArgs& a, int B, hipStream_t st) {
     if (a.kv_fp8) { if (a.hd == 256) KR_MGA(32, true); else if (a.hd == 128) KR_MGA(16, true); else KR_MGA(8, true); }
     else { if (a.hd == 256) KR_MGA(32, false); else if (a.hd == 128) KR_MGA(16, false); else KR_MGA(8, false); }
 #undef KR_MGA
+    return 0;
+}
+
+// ---- MLA (docs/design/15-multi-mla.md) -----------------------------------------------------------------------------------------------------------
+// The arithmetic specification is kr_mla_prep_kernel / kr_mla_attn_kernel (kr_mla.hip); the sections of the prep launch are the shared device
+// functions of kr_mla_dev.h.  grid (nh * klr / 64 + 1, B) -- or (nh + 1, B) when the matrix-core absorption has produced q_abs -- 64 threads:
+// workgroups below the last: absorption tile (h, jt) of row b, the jt == 0 one also ropes q_pe[h] at the row's position; the last: latent RMSNorm,
+// k_pe rope, both rows stored at the row's position of the row's slot.
+template <bool FP8>
+__global__ void __launch_bounds__(64) kr_multi_mla_prep_kernel(const KrMultiMlaArgs a) {
+    __shared__ float sh[640];
+    const int row = blockIdx.y, pos = a.positions[row];
+    const int tiles = a.absorb_done ? 1 : a.klr / 64, nb_abs = a.nh * tiles, hd = a.nd + a.rd;
+    if ((int)blockIdx.x < nb_abs) {
+        const int h = blockIdx.x / tiles, jt = blockIdx.x % tiles;
+        const float* qh = a.q_full + (size_t)row * a.ld_q + (size_t)h * hd;
+        if (!a.absorb_done) kr_mla_absorb_tile(qh, a.w_kc + (size_t)h * a.nd * a.klr, a.q_abs + ((size_t)row * a.nh + h) * a.klr, jt * 64 + (int)threadIdx.x, a.nd, a.klr, sh);
+        if (jt == 0) kr_mla_rope_qpe(qh, a.q_pe + ((size_t)row * a.nh + h) * a.rd, a.rope_cos, a.rope_sin, pos, a.nd, a.rd / 2);
+        return;
+    }
+    const size_t slot = (size_t)a.slots[row];
+    kr_mla_append_row<FP8>(a.kv_out + (size_t)row * a.ld_kv, a.kv_a_norm, a.rope_cos, a.rope_sin, (char*)a.ckv_cache + slot * a.ckv_stride,
+                           (char*)a.kpe_cache + slot * a.kpe_stride, pos, a.klr, a.rd, a.eps, sh);
+}
+
+// Attention of KR_MM_HG heads of row b over the slot's rows [0, pos].  grid (ceil(nh / KR_MM_HG), B), 512 threads.  The latent + rope rows are
+// shared by every head of the row: KR_MM_ROWS of them at a time are fetched with 16-byte buffer loads (num_records = the row's current length: rows
+// past it read as zero), committed to LDS while the next stage's loads are in flight, and serve all heads of the group.
+//   scores: 16 lanes per (position, head) pair -- kr_dot2acc over klr + kr_dot2acc over rd, x sm_scale (the query slice stays in registers) -- into the
+//           row's global score rows, so the form (and its bits) does not depend on the slot capacity
+//   softmax: one wave per head: max, libm exp in place, the position-ordered sum over LDS tiles by one lane, x 1 / sum (kr_multi_gqa_attn_kernel's)
+//   weighted sum: the rows staged again; thread t owns latent element t % klr of heads t / klr + k * (512 / klr): one fma per position, ascending
+#define KR_MM_ROWS 32
+#define KR_MM_HG 4
+template <bool FP8, int NBC>
+__global__ void __launch_bounds__(512) kr_multi_mla_attn_kernel(const KrMultiMlaArgs a) {
+    constexpr int klr = NBC * 8, NBR = 8, rd = NBR * 8, esz = FP8 ? 1 : 2, HG = KR_MM_HG, ROWS = KR_MM_ROWS;
+    constexpr int CPR_C = klr * esz / 16, CPR_R = rd * esz / 16, pitch = (klr + rd) * esz + 16, NLC = ROWS * CPR_C / 512;
+    static_assert(ROWS * CPR_C % 512 == 0 && ROWS * CPR_R <= 512 && 512 % klr == 0 && HG % (512 / klr) == 0 && ROWS * HG <= 512 && 32 % HG == 0, "work split");
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    float* qa = sm;                                  // [HG][klr]
+    float* qp = qa + HG * klr;                       // [HG][rd]
+    float* tile = qp + HG * rd;                      // [4][KR_MG_TILE]
+    float* pt = tile + 4 * KR_MG_TILE;               // [ROWS][HG]
+    unsigned char* stage = reinterpret_cast<unsigned char*>(pt + ROWS * HG);      // [ROWS][pitch]
+    const int row = blockIdx.y, hg0 = blockIdx.x * HG, nhg = min(HG, a.nh - hg0), t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int seq = a.positions[row] + 1, nst = (seq + ROWS - 1) / ROWS;
+    const size_t slot = (size_t)a.slots[row];
+    float* sc = a.scores + ((size_t)row * a.nh + hg0) * a.sc_ld;                  // [nhg][sc_ld]
+    const __amdgpu_buffer_rsrc_t srd_c = __builtin_amdgcn_make_buffer_rsrc((char*)a.ckv_cache + slot * a.ckv_stride, 0, seq * klr * esz, 0x00020000);
+    const __amdgpu_buffer_rsrc_t srd_r = __builtin_amdgcn_make_buffer_rsrc((char*)a.kpe_cache + slot * a.kpe_stride, 0, seq * rd * esz, 0x00020000);
+    // unconditional loads: rows at or past the current length are outside the descriptors and read as zero
+    struct Regs { u32x4 c[NLC]; u32x4 r; };
+    const int rrow = t / CPR_R, rcol = t % CPR_R;
+    const bool has_r = t < ROWS * CPR_R;
+    auto issue_c = [&](Regs& R, int s0) {
+#pragma unroll
+        for (int i = 0; i < NLC; i++) {
+            const int c = t + 512 * i, r = c / CPR_C, col = c % CPR_C;
+            R.c[i] = __builtin_amdgcn_raw_buffer_load_b128(srd_c, (s0 + r) * klr * esz + col * 16, 0, 0);
+        }
+    };
+    auto issue_r = [&](Regs& R, int s0) { R.r = __builtin_amdgcn_raw_buffer_load_b128(srd_r, has_r ? (s0 + rrow) * rd * esz + rcol * 16 : 0x7FFFFFF0, 0, 0); };
+    auto commit_c = [&](const Regs& R) {
+#pragma unroll
+        for (int i = 0; i < NLC; i++) {
+            const int c = t + 512 * i, r = c / CPR_C, col = c % CPR_C;
+            *reinterpret_cast<u32x4*>(stage + r * pitch + col * 16) = R.c[i];
+        }
+    };
+    auto commit_r = [&](const Regs& R) { if (has_r) *reinterpret_cast<u32x4*>(stage + rrow * pitch + klr * esz + rcol * 16) = R.r; };
+    Regs rg;
+    issue_c(rg, 0); issue_r(rg, 0);
+    for (int i = t; i < nhg * klr; i += 512) qa[i] = a.q_abs[((size_t)row * a.nh + hg0) * klr + i];
+    for (int i = t; i < nhg * rd; i += 512) qp[i] = a.q_pe[((size_t)row * a.nh + hg0) * rd + i];
+    __syncthreads();
+    // ---- scores (kr_mla_scores_kernel's lane roles): lane c16 = (accumulator a2, AVX lane l) owns the 8-blocks i % 2 == a2, ascending
+    {
+        const int c16 = t & 15, a2 = c16 >> 3, l = c16 & 7, g = t >> 4, hh = g % HG, prow = g / HG;
+        const bool hon = hh < nhg;
+        constexpr int NQC = NBC / 2, NQR = NBR / 2;
+        float qc[NQC], qr[NQR];
+#pragma unroll
+        for (int u = 0; u < NQC; u++) qc[u] = hon ? qa[hh * klr + (2 * u + a2) * 8 + l] : 0.0f;
+#pragma unroll
+        for (int u = 0; u < NQR; u++) qr[u] = hon ? qp[hh * rd + (2 * u + a2) * 8 + l] : 0.0f;
+        float* out = sc + (size_t)(hon ? hh : 0) * a.sc_ld;
+        for (int st = 0; st < nst; st++) {
+            if (st) __syncthreads();                 // the previous stage has been consumed
+            commit_c(rg); commit_r(rg);
+            issue_c(rg, (st + 1) * ROWS); issue_r(rg, (st + 1) * ROWS);      // past the end: zeros, never used
+            __syncthreads();
+            const int s0 = st * ROWS;
+#pragma unroll 1
+            for (int pass = 0; pass < ROWS / (32 / HG); pass++) {
+                const int r = prow + (32 / HG) * pass;
+                if (!hon || s0 + r >= seq) continue;          // uniform over the 16 lanes of a pair
+                const unsigned char* srow = stage + r * pitch;
+                float kc[NQC], kr[NQR];
+#pragma unroll
+                for (int u = 0; u < NQC; u++) kc[u] = kr_stage_val<FP8>(srow, (2 * u + a2) * 8 + l);
+#pragma unroll
+                for (int u = 0; u < NQR; u++) kr[u] = kr_stage_val<FP8>(srow + klr * esz, (2 * u + a2) * 8 + l);
+                float acc = 0.0f;
+#pragma unroll
+                for (int u = 0; u < NQC; u++) acc = __builtin_fmaf(qc[u], kc[u], acc);
+                float oth = __shfl_xor(acc, 8);
+                float v = kr_mla_hsum8(a2 == 0 ? acc + oth : oth + acc);
+                acc = 0.0f;
+#pragma unroll
+                for (int u = 0; u < NQR; u++) acc = __builtin_fmaf(qr[u], kr[u], acc);
+                oth = __shfl_xor(acc, 8);
+                v += kr_mla_hsum8(a2 == 0 ? acc + oth : oth + acc);
+                v *= a.sm_scale;
+                if (c16 == 0) out[s0 + r] = v;
+            }
+        }
+    }
+    issue_c(rg, 0);                                  // the first stage of the weighted sum rides under the softmax
+    __syncthreads();
+    // ---- softmax: wave w < nhg takes head hg0 + w
+    {
+        const int seq32 = (seq + 31) & ~31;
+        const bool on = w < nhg;
+        float* rowp = sc + (size_t)(on ? w : 0) * a.sc_ld;
+        float* tw = tile + (w & 3) * KR_MG_TILE;
+        float mx = -__builtin_inff();
+        if (on) for (int s = lane; s < seq; s += 64) mx = fmaxf(mx, rowp[s]);
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
+        if (on) for (int s = lane; s < seq; s += 64) rowp[s] = kr_expf(rowp[s] - mx);
+        __syncthreads();
+        float se = 0.0f;
+        for (int s0 = 0; s0 < seq32; s0 += KR_MG_TILE) {
+            const int n = min(KR_MG_TILE, seq32 - s0);
+            if (on) for (int i = lane; i < n; i += 64) tw[i] = s0 + i < seq ? rowp[s0 + i] : 0.0f;      // zero padding leaves a sum of exponentials unchanged
+            __syncthreads();
+            if (on && lane == 0) se = kr_seq_sum(tw, n, se);
+            __syncthreads();
+        }
+        se = __shfl(se, 0);
+        const float inv = 1.0f / se;
+        if (on) for (int s = lane; s < seq; s += 64) rowp[s] *= inv;
+    }
+    // ---- weighted sum
+    constexpr int TPH = 512 / klr, KH = HG / TPH;    // threads per latent element; heads per thread: hq + k * TPH
+    const int j = t % klr, hq = t / klr;
+    float o[KH];
+#pragma unroll
+    for (int k = 0; k < KH; k++) o[k] = 0.0f;
+    for (int st = 0; st < nst; st++) {
+        __syncthreads();                             // the scaled score rows are written / the previous stage has been consumed
+        commit_c(rg);
+        issue_c(rg, (st + 1) * ROWS);
+        const int s0 = st * ROWS, n = min(ROWS, seq - s0);
+        if (t < ROWS * HG) { const int r = t / HG, h = t % HG; pt[t] = (r < n && h < nhg) ? sc[(size_t)h * a.sc_ld + s0 + r] : 0.0f; }
+        __syncthreads();
+        for (int r = 0; r < n; r += 8) {             // n <= ROWS and r % 8 == 0: rows r .. r + 7 are inside the stage
+            float vv[8], pp[8][KH];
+#pragma unroll
+            for (int u = 0; u < 8; u++) {
+                vv[u] = kr_stage_val<FP8>(stage + (r + u) * pitch, j);
+#pragma unroll
+                for (int k = 0; k < KH; k++) pp[u][k] = pt[(r + u) * HG + hq + k * TPH];
+            }
+#pragma unroll
+            for (int u = 0; u < 8; u++)
+                if (r + u < n) {
+#pragma unroll
+                    for (int k = 0; k < KH; k++) o[k] = __builtin_fmaf(pp[u][k], vv[u], o[k]);
+                }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < KH; k++) {
+        const int h = hq + k * TPH;
+        if (h < nhg) a.attn_lat[((size_t)row * a.nh + hg0 + h) * klr + j] = o[k];
+    }
+}
+template <bool FP8, int NBC> static constexpr size_t kr_multi_mla_lds() {
+    return ((size_t)KR_MM_HG * (NBC * 8 + 64) + 4 * KR_MG_TILE + KR_MM_ROWS * KR_MM_HG) * 4 + (size_t)KR_MM_ROWS * ((NBC * 8 + 64) * (FP8 ? 1 : 2) + 16);
+}
+
+int kr_multi_mla_ok(int klr, int nd, int rd) { return (klr == 512 || klr == 256) && rd == 64 && nd >= 1 && nd <= 640; }
+
+int kr_launch_multi_mla(const KrMultiMlaArgs& a_in, int B, hipStream_t st) {
+    KrMultiMlaArgs a = a_in;
+    if (!kr_multi_mla_ok(a.klr, a.nd, a.rd) || a.nh < 1 || a.sc_ld % 32) return 1;
+    static_assert(kr_multi_mla_lds<false, 64>() <= 64 * 1024, "the attention kernel stays inside the default 64 KiB LDS window");
+    // the w_kc absorption, row-wise: from 32 rows on the matrix cores (one fma chain per output, the prompt pass's launch), the prep launch's tiles below
+    a.absorb_done = B >= 32 && kr_launch_mla_absorb_mfma(a.q_full, a.ld_q, a.nd + a.rd, a.nd, a.w_kc, a.klr, a.q_abs, B, a.nh, st) == 0;
+    const dim3 pg(a.nh * (a.absorb_done ? 1 : a.klr / 64) + 1, B), ag((a.nh + KR_MM_HG - 1) / KR_MM_HG, B);
+    if (a.kv_fp8) hipLaunchKernelGGL(kr_multi_mla_prep_kernel<true>, pg, dim3(64), 0, st, a);
+    else hipLaunchKernelGGL(kr_multi_mla_prep_kernel<false>, pg, dim3(64), 0, st, a);
+#define KR_MMA(F_, NBC_) hipLaunchKernelGGL((kr_multi_mla_attn_kernel<F_, NBC_>), ag, dim3(512), (kr_multi_mla_lds<F_, NBC_>()), st, a)
+    if (a.kv_fp8) { if (a.klr == 512) KR_MMA(true, 64); else KR_MMA(true, 32); }
+    else { if (a.klr == 512) KR_MMA(false, 64); else KR_MMA(false, 32); }
+#undef KR_MMA
+    // the w_vc projection, row-wise: the prompt pass's matrix-core launch from 32 rows, the decode launch with a token dimension below
+    if (B >= 32 && kr_launch_mla_wvc_mfma(a.w_vc, a.attn_lat, a.v_proj, B, a.nh, a.vhd, a.klr, st) == 0) return 0;
+    KrMlaArgs m{};
+    m.step = nullptr; m.pos0 = 0; m.kv_out = a.kv_out; m.ld_kv = a.ld_kv; m.q_full = a.q_full; m.ld_q = a.ld_q; m.w_vc = a.w_vc;
+    m.q_abs = a.q_abs; m.q_pe = a.q_pe; m.attn_lat = a.attn_lat; m.v_proj = a.v_proj; m.nh = a.nh; m.klr = a.klr; m.nd = a.nd; m.rd = a.rd; m.vhd = a.vhd;
+    kr_launch_mla_wvc(m, st, B);
     return 0;
 }
 

@@ -396,15 +396,16 @@ class CpuDecodeStore:
 
     # ------------------------------------------------------------------ sequence slots (docs/design/13-multi-sequence.md)
     def create_slots(self, n: int, max_seq: int) -> int:
-        """kr_decode_slots_create: n zeroed sequence slots of up to max_seq positions (replacing any earlier ones; n = 0 frees them), KV rows of
-        the store's current element type.  Returns their device bytes."""
+        """kr_decode_slots_create: n zeroed sequence slots of up to max_seq positions (replacing any earlier ones; n = 0 frees them), KV rows
+        (for an MLA layer: compressed-KV rows [kv_lora_rank] and rope-key rows [rope dim]) of the store's current element type.  Returns their device bytes."""
         self._need()
         b = C.c_size_t()
         check(self._lib.kr_decode_slots_create(self._h, n, max_seq, C.byref(b)))
         return b.value
 
     def save_slot(self, slot: int, seq_len: int) -> None:
-        """the store's own sequence -> slot: KV rows [0, seq_len) of every GQA layer, conv + recurrent state of every linear-attention layer"""
+        """the store's own sequence -> slot: KV rows [0, seq_len) of every GQA layer, compressed-KV and rope-key rows [0, seq_len) of every MLA
+        layer, conv + recurrent state of every linear-attention layer"""
         self._need(); check(self._lib.kr_decode_slot_save(self._h, slot, seq_len))
 
     def load_slot(self, slot: int, seq_len: int) -> None:
@@ -412,8 +413,8 @@ class CpuDecodeStore:
         self._need(); check(self._lib.kr_decode_slot_load(self._h, slot, seq_len))
 
     def step_multi(self, slots: Sequence[int], tokens: Sequence[int], positions: Sequence[int], logits: bool = False):
-        """kr_decode_step_multi: row i = slot slots[i] consumes tokens[i] at positions[i], bit-identical to decode_step on that sequence alone.
-        Returns the greedy ids, or (ids, logits f32 [n, vocab]) with logits=True."""
+        """kr_decode_step_multi: row i = slot slots[i] consumes tokens[i] at positions[i], bit-identical to decode_step on that sequence alone
+        (logits, id, the KV row -- or MLA latent and rope-key rows -- it appends to the slot).  Returns the greedy ids, or (ids, logits f32 [n, vocab]) with logits=True."""
         self._need()
         n = len(slots)
         arr = lambda xs: (C.c_int32 * max(n, 1))(*xs)
