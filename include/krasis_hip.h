@@ -363,7 +363,12 @@ int kr_decode_slot_save(kr_decode_store* s, int slot, int seq_len);
 /* slot -> the store's own sequence (the same parts): decode_step / prefill / verify then continue it at position seq_len */
 int kr_decode_slot_load(kr_decode_store* s, int slot, int seq_len);
 /* row i: slot slots[i] consumes tokens[i] at positions[i].  next_out[i] = first-maximum argmax of row i's logits (the rule of kr_launch_argmax);
-   logits_out (NULL, host or device) = [n][vocab] f32.  Distinct slots, 1 <= n <= KR_MULTI_MAX.  Returns once next_out is written. */
+   logits_out (NULL, host or device) = [n][vocab] f32.  Distinct slots, 1 <= n <= KR_MULTI_MAX.  Returns once next_out is written.
+   Under kr_decode_set_option(s, "multi_attn_fast", 1) (default 0; docs/design/16-multi-attn-fast.md) the GQA layers of this and every other batched
+   entry point below run split-KV flash-decode over slots of max_seq > 1024: row i then carries the bits of kr_decode_step under KR_ATTN_FAST on that
+   sequence alone (logits within 1e-3 of the exact step, relative to their largest magnitude), whatever rows share the step; shorter slots keep the
+   exact step.  The option changes nothing else in the store; the mode bits of kr_decode_set_attention_mode stay refused here, and with the option
+   set a store with MLA layers is refused (KR_ERR_STATE). */
 int kr_decode_step_multi(kr_decode_store* s, int n, const int32_t* slots, const int32_t* tokens, const int32_t* positions,
                          int32_t* next_out, float* logits_out, void* stream);
 /* greedy generation of n slots together.  Row i's tokens_out[i*max_tokens ...], n_out[i] and its slot's state afterwards are exactly those of
@@ -381,7 +386,7 @@ int kr_decode_slot_sampler(kr_decode_store* s, int slot, int first_token, float 
 /* kr_decode_step_multi, but next_out[i] is drawn by slot slots[i]'s sampler, and the slot's RNG state and seen set advance as kr_decode_generate's
    do for that token.  logits_out (optional) = the model's logits before the penalty and temperature (bit-identical to kr_decode_step_multi's).
    Rows drawing from more than 4096 candidates (top_k 0 or > 4096), or every sampled row under kr_decode_set_option("multi_sample_loop", 1),
-   run the single-row sampler one row after another: same tokens. */
+   run the single-row sampler one row after another: same tokens.  kr_decode_set_option("multi_attn_fast", 1): see kr_decode_step_multi. */
 int kr_decode_step_multi_sample(kr_decode_store* s, int n, const int32_t* slots, const int32_t* tokens, const int32_t* positions,
                                 int32_t* next_out, float* logits_out, void* stream);
 /* kr_decode_generate_multi with per-row sampler parameters (arrays of n): sets every row's slot sampler, then loops.  Row i equals

@@ -1044,6 +1044,7 @@ extern "C" int kr_decode_set_option(kr_decode_store* s, const char* name, int va
     if (!strcmp(name, "pfm_timing")) { s->opt_pfm_timing = value != 0; return KR_OK; }
     if (!strcmp(name, "generate_lookahead")) { s->opt_gen_lookahead = value != 0; return KR_OK; }
     if (!strcmp(name, "multi_sample_loop")) { s->opt_multi_sample_loop = value != 0; return KR_OK; }
+    if (!strcmp(name, "multi_attn_fast")) { s->opt_multi_attn_fast = value != 0; return KR_OK; }
     if (!strcmp(name, "ep_graph")) { s->opt_ep_graph = value != 0; s->graph_ok = false; return KR_OK; }
     return kr_fail(KR_ERR_VALUE, "unknown option '%s'", name);
 }

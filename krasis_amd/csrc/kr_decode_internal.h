@@ -40,6 +40,7 @@ struct kr_multi_state {
     std::vector<DevBuf> a, b;                  // per layer: LA conv / recurrent state, GQA K / V, MLA latent / rope-key rows
     std::vector<size_t> a_stride, b_stride;    // per layer: bytes per slot
     DevBuf rows, ids, logits, scores, scratch; // step: [slots | tokens | positions] (device), greedy ids, [n][vocab] logits, attention scores, the arena
+    DevBuf fd_o, fd_ml; bool fd_ready = false; // "multi_attn_fast": split-KV partials [n][nkv][chunks][G][hd] and (max, sum) [n][nh][chunks][2] of one GQA layer, sized by the step's longest row; the kernels' LDS windows are raised
     // per-slot samplers (kr_decode_slot_sampler, docs/design/14-multi-sampling.md): allocated for every slot on the first call; empty = every slot greedy
     struct Sampler { float temperature = 0.0f, top_p = 1.0f, penalty = 0.0f; int top_k = 0; };
     std::vector<Sampler> smp; size_t smp_words = 0;   // host: parameters per slot; seen-bitmap words per slot
@@ -71,6 +72,7 @@ struct kr_decode_store {
     DevBuf img_in, img_post, img_post_bf16, img_attn; bool use_images = true;   // pre-built INT16 activation images (input norm, post-attention norm f32 / bf16, attention output)
     int opt_gqa_stream = 0, opt_pfm_timing = 0, opt_norm_rows = 1, opt_la_conv_fused = 1, opt_gqa_fused = 1, opt_lm_fused = 1, opt_la_heads = 1, opt_w2_combine = 1, opt_dense_fast = 1;   // kr_decode_set_option: test / tuning hooks (no environment lookups on launch paths)
     int opt_multi_sample_loop = 0;               // kr_decode_set_option("multi_sample_loop"): every sampled row of a multi-sequence step takes the single-row sampler, one row after another (A/B and test hook; same tokens)
+    int opt_multi_attn_fast = 0;                 // kr_decode_set_option("multi_attn_fast"): the GQA layers of every batched multi-sequence step run split-KV flash-decode over slots longer than gqa_split_min (tolerance form, docs/design/16-multi-attn-fast.md); the mode bits stay refused
     int opt_gen_lookahead = 0;                    // kr_decode_set_option("generate_lookahead"): generate_batch feeds the sampled token back ON THE DEVICE and queues step i + 1 before the host has read token i
     int opt_ep_graph = 0;                         // kr_decode_set_option("ep_graph"): expert-parallel decode over RCCL replays a captured graph (the all-reduce is captured with the kernels)
     uint64_t ep_generation_seen = 0;               // kr_engine::ep_generation at the last step: a new / destroyed communicator invalidates the graph and restarts the warm-up

@@ -29,6 +29,10 @@ int multi_refuse(kr_decode_store* s) {
     if (int rc = kr_spec_pending_fail(s)) return rc;
     if (s->attn_fast || s->gemm_fast || s->decode_fast)
         return kr_fail(KR_ERR_STATE, "the multi-sequence step is exact-mode only: the attention mode has tolerance bits set (%d)", s->attn_fast | s->gemm_fast << 1 | s->decode_fast << 2);
+    if (s->opt_multi_attn_fast)
+        for (size_t i = 0; i < s->layers.size(); i++)
+            if (s->layers[i].attn == ATTN_MLA)
+                return kr_fail(KR_ERR_STATE, "the \"multi_attn_fast\" option covers GQA layers only: layer %zu is MLA (set the option to 0 for the exact step)", i);
     kr_engine* e = s->eng;
     if (e->ep) return kr_fail(KR_ERR_STATE, "the multi-sequence step does not run under expert parallelism");
     for (size_t i = 0; i < s->layers.size(); i++) {

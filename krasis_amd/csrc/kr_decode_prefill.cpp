@@ -41,7 +41,7 @@ struct Chunk {      // one chunk of the prompt in flight: its arena, stream and 
     Scratch B; float* scores; const int* tok; int Cc, pos0, set; bool first, add_is_emb; hipStream_t st;
     KrPfSync sy;      // this (chunk, layer)'s hand-overs with the previous / next chunk (set by the scheduler before every run_layer)
     bool verify = false;      // kr_decode_verify's pass: linear-attention layers write their recurrence inputs into the store's verify buffers (kr_spec.h)
-    const int32_t* m_slots = nullptr; const int32_t* m_pos = nullptr; int m_sc_ld = 0;   // the multi-sequence step: row b = slot m_slots[b] at m_pos[b] (device)
+    const int32_t* m_slots = nullptr; const int32_t* m_pos = nullptr; int m_sc_ld = 0; int m_fd_chunk = 0, m_fd_chunks = 0;   // the multi-sequence step: row b = slot m_slots[b] at m_pos[b] (device)
 };
 size_t al(size_t n) { return (n + 255) & ~(size_t)255; }
 }  // namespace
@@ -142,6 +142,7 @@ static int run_layer(kr_decode_store* s, Chunk& cx, size_t li) {
             m.k_cache = M.a[li].p; m.v_cache = M.b[li].p; m.slot_elems = M.a_stride[li] / (M.kv_fp8 ? 1 : 2); m.kv_fp8 = M.kv_fp8;
             m.q_out = B.q; m.gate = B.gate; m.attn_out = B.attn; m.scores = (float*)M.scores.p; m.sc_ld = cx.m_sc_ld;
             m.gated = L.gated; m.nh = L.nh; m.nkv = L.nkv; m.hd = L.hd; m.eps = s->eps; m.sm_scale = L.sm_scale;
+            if (cx.m_fd_chunks) { m.fd_o = (float*)M.fd_o.p; m.fd_ml = (float*)M.fd_ml.p; m.fd_chunk = cx.m_fd_chunk; m.fd_chunks = cx.m_fd_chunks; }      // "multi_attn_fast", long slots
             if (kr_launch_multi_gqa(m, Cc, st)) return kr_fail(KR_ERR_VALUE, "unsupported GQA geometry for the multi-sequence step");
         } else {
             KrPfmGqaArgs a{};
@@ -688,15 +689,38 @@ int kr_multi_pass(kr_decode_store* s, int n, const int32_t* d_rows, int max_pos,
     kr_multi_state& M = *s->multi;
     PfLayout Lo;
     if (int rc = pf_layout(s, (size_t)n, true, true, st, Lo)) return rc;
-    int nh_max = 1;
-    for (const DLayer& L : s->layers) if (L.attn == ATTN_GQA || L.attn == ATTN_MLA) nh_max = std::max(nh_max, L.nh);      // a score row per query head of either kind
+    int nh_max = 1; size_t gqa_row = 0; bool has_gqa = false, has_mla = false;
+    for (const DLayer& L : s->layers) {
+        if (L.attn == ATTN_GQA || L.attn == ATTN_MLA) nh_max = std::max(nh_max, L.nh);      // a score row per query head of either kind
+        if (L.attn == ATTN_GQA) { has_gqa = true; gqa_row = std::max(gqa_row, (size_t)L.nh * L.hd); }
+        has_mla |= L.attn == ATTN_MLA;
+    }
+    // "multi_attn_fast": over slots longer than gqa_split_min (the capacity rule of the store's own KR_ATTN_FAST step) every GQA layer takes the split-KV
+    // flash-decode; the partials are sized by this step's longest row, and the score rows are not needed unless another kind of layer reads them
+    const bool flash = s->opt_multi_attn_fast && has_gqa && M.max_seq > s->gqa_split_min;
+    int fd_chunk = 0, fd_chunks = 0;
+    if (flash) {
+        fd_chunk = kr_fd_flash_chunk(M.max_seq); fd_chunks = (max_pos + fd_chunk) / fd_chunk;
+        if (fd_chunks > 1024) return kr_fail(KR_ERR_VALUE, "multi_attn_fast: position %d needs %d chunks of %d positions (at most 1024)", max_pos, fd_chunks, fd_chunk);
+        if (!M.fd_ready) {
+            for (const DLayer& L : s->layers) {
+                if (L.attn != ATTN_GQA) continue;
+                if (!kr_multi_fd_ok(L.nh, L.nkv, L.hd)) return kr_fail(KR_ERR_VALUE, "multi_attn_fast: GQA geometry nh %d nkv %d head_dim %d not covered (head_dim 64 / 128 / 256, at most 32 heads per KV head)", L.nh, L.nkv, L.hd);
+                if (kr_multi_fd_prepare(L.hd, M.kv_fp8)) return kr_fail(KR_ERR_HIP, "multi_attn_fast: LDS window of the flash-decode kernel refused (head_dim %d)", L.hd);
+            }
+            M.fd_ready = true;
+        }
+        if (M.fd_o.ensure((size_t)n * fd_chunks * gqa_row * 4) || M.fd_ml.ensure((size_t)n * nh_max * fd_chunks * 8))
+            return kr_fail(KR_ERR_HIP, "hipMalloc of the multi-sequence step's split-KV partials (%zu MiB) failed", ((size_t)n * fd_chunks * (gqa_row * 4 + nh_max * 8)) >> 20);
+    }
+    const bool need_scores = (has_gqa && !flash) || has_mla;
     const int sc_ld = (max_pos + 1 + 31) & ~31;
-    if (M.scratch.ensure(Lo.total) || M.scores.ensure((size_t)n * nh_max * sc_ld * 4) || M.logits.ensure((size_t)n * s->vocab * 4))
+    if (M.scratch.ensure(Lo.total) || (need_scores && M.scores.ensure((size_t)n * nh_max * sc_ld * 4)) || M.logits.ensure((size_t)n * s->vocab * 4))
         return kr_fail(KR_ERR_HIP, "hipMalloc of the multi-sequence step's scratch (%zu MiB) failed", (Lo.total + (size_t)n * (nh_max * sc_ld + s->vocab) * 4) >> 20);
     Chunk cx{};
     cx.B = pf_carve(Lo, (char*)M.scratch.p); cx.scores = nullptr; cx.tok = d_rows + n; cx.Cc = n; cx.pos0 = 0; cx.set = KR_PF_MAX_DEPTH - 1;
     cx.first = true; cx.add_is_emb = true; cx.st = st;
-    cx.m_slots = d_rows; cx.m_pos = d_rows + 2 * n; cx.m_sc_ld = sc_ld;
+    cx.m_slots = d_rows; cx.m_pos = d_rows + 2 * n; cx.m_sc_ld = sc_ld; cx.m_fd_chunk = fd_chunk; cx.m_fd_chunks = fd_chunks;
     for (size_t l = 0; l < s->layers.size(); l++)
         if (int rc = run_layer(s, cx, l)) return rc;
     return final_rows(s, cx, (float*)M.logits.p);

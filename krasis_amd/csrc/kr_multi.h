@@ -29,9 +29,17 @@ struct KrMultiGqaArgs {
     float *q_out, *gate, *attn_out;            // [B][nh * hd]
     float* scores; int sc_ld;                  // scratch [B][nh][sc_ld], sc_ld >= the longest row's pos + 1 rounded up to 32
     int gated, nh, nkv, hd; float eps, sm_scale;
+    // "multi_attn_fast" (kr_multi_flash.hip): split-KV partials [B][nkv][fd_chunks][G][hd] and (max, sum) [B][nh][fd_chunks][2]; fd_chunk positions per
+    // chunk, fd_chunks = the longest row's chunk count.  Null: the exact per-slot kernel (scores is not read when they are set)
+    float *fd_o, *fd_ml; int fd_chunk, fd_chunks;
 };
 // 0: launched; 1: geometry not covered (hd 64 / 128 / 256, nh % nkv == 0)
 int kr_launch_multi_gqa(const KrMultiGqaArgs& a, int B, hipStream_t st);
+// the flash-decode form of the attention launch (after the prep launch): geometry test, the LDS window of its kernel (once, outside the step; non-zero =
+// refused), the chunk pass + merge over n_chunks chunks (0: launched)
+int kr_multi_fd_ok(int nh, int nkv, int hd);
+int kr_multi_fd_prepare(int hd, int fp8);
+int kr_launch_multi_fd(const KrMultiGqaArgs& a, int B, int n_chunks, hipStream_t st);
 
 // MLA, one token per row: rope of q_pe, latent RMSNorm + rope of k_pe, both rows appended to the row's slot, attention over the slot's rows [0, pos]
 // in the latent space, w_kc absorption before and w_vc projection after (the row-wise launches of the prompt pass)

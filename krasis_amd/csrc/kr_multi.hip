@@ -284,6 +284,11 @@ int kr_launch_multi_gqa(const KrMultiGqaArgs& a, int B, hipStream_t st) {
     if ((a.hd != 64 && a.hd != 128 && a.hd != 256) || a.nkv < 1 || a.nh % a.nkv || a.sc_ld % 32) return 1;
     const int G = a.nh / a.nkv;
     const size_t lds = ((size_t)G * a.hd + 4 * KR_MG_TILE + (size_t)G * KR_MG_PT) * 4;
+    if (a.fd_o) {      // "multi_attn_fast": the same prep launch, then split-KV flash-decode over the slots (kr_multi_flash.hip)
+        if (!kr_multi_fd_ok(a.nh, a.nkv, a.hd) || !a.fd_ml || a.fd_chunks < 1 || a.fd_chunks > 1024) return 1;
+        hipLaunchKernelGGL(kr_multi_gqa_prep_kernel, dim3(a.nh + a.nkv, B), dim3(256), 0, st, a);
+        return kr_launch_multi_fd(a, B, a.fd_chunks, st);
+    }
     if (lds > 64 * 1024) return 1;
     hipLaunchKernelGGL(kr_multi_gqa_prep_kernel, dim3(a.nh + a.nkv, B), dim3(256), 0, st, a);
 #define KR_MGA(NB_, F_) hipLaunchKernelGGL((kr_multi_gqa_attn_kernel<NB_, F_>), dim3(a.nkv, B), dim3(256), lds, st, a)

@@ -288,7 +288,10 @@ class CpuDecodeStore:
         self._need(); check(self._lib.kr_decode_set_attention_mode(self._h, (1 if fast else 0) | (2 if gemm_fast else 0) | (4 if decode_fast else 0)))
 
     def set_option(self, name: str, value: int) -> None:
-        """test / tuning hooks by name ("gqa_stream", "pfm_timing")"""
+        """options by name.  Test / tuning hooks ("gqa_stream", "pfm_timing", "multi_sample_loop", ...), and "multi_attn_fast" (default 0): with 1
+        the GQA layers of every batched step (step_multi, step_multi_sample, generate_multi) run split-KV flash-decode over slots of max_seq > 1024
+        -- tolerance form, row i bit-identical to decode_step under set_attention_mode(True) on that sequence alone; shorter slots keep the exact
+        step; nothing else in the store changes; a store with MLA layers is then refused by the batched calls (docs/design/16-multi-attn-fast.md)"""
         self._need(); check(self._lib.kr_decode_set_option(self._h, name.encode(), int(value)))
 
     def finalize_decode(self) -> None:
@@ -414,7 +417,9 @@ class CpuDecodeStore:
 
     def step_multi(self, slots: Sequence[int], tokens: Sequence[int], positions: Sequence[int], logits: bool = False):
         """kr_decode_step_multi: row i = slot slots[i] consumes tokens[i] at positions[i], bit-identical to decode_step on that sequence alone
-        (logits, id, the KV row -- or MLA latent and rope-key rows -- it appends to the slot).  Returns the greedy ids, or (ids, logits f32 [n, vocab]) with logits=True."""
+        (logits, id, the KV row -- or MLA latent and rope-key rows -- it appends to the slot).  Returns the greedy ids, or (ids, logits f32 [n, vocab]) with logits=True.
+        After set_option("multi_attn_fast", 1), over slots of max_seq > 1024: row i is bit-identical to decode_step under set_attention_mode(True) on that
+        sequence alone instead (GQA attention as split-KV flash-decode; logits within 1e-3 of the exact step relative to their largest magnitude)."""
         self._need()
         n = len(slots)
         arr = lambda xs: (C.c_int32 * max(n, 1))(*xs)
