@@ -396,6 +396,21 @@ int kr_decode_generate_multi_sample(kr_decode_store* s, int n, const int32_t* sl
                                     const int32_t* start_positions, int max_tokens, const float* temperature, const int* top_k,
                                     const float* top_p, const float* presence_penalty, const uint64_t* rng_seeds,
                                     const int* stop_ids, int n_stop, int32_t* tokens_out, int32_t* n_out, void* stream);
+/* multi-token extend of slots (docs/design/17-multi-extend.md): kr_decode_step_multi with a run of counts[i] >= 1 tokens per row.  Row i: slot slots[i]
+   consumes the next counts[i] entries of tokens (rows concatenated in order, T = sum of counts <= KR_EXTEND_MAX_TOKENS) at positions positions[i] ...
+   positions[i] + counts[i] - 1.  Row i is bit-identical to counts[i] successive kr_decode_step calls on that sequence alone: every K / V row (MLA: latent
+   and rope-key row) the tokens append, the conv and recurrent state afterwards, the last token's logits and the id -- so the result does not depend on how
+   a token stream is cut into calls (one run of 12 = runs of 5 + 7 = twelve kr_decode_step_multi calls), on the rows that share the pass, on their order
+   or on T.  next_out[i] = first-maximum argmax of the logits after row i's LAST token; logits_out (NULL, host or device) = [n][vocab] f32, those
+   logits (the lm_head runs for n rows, not T).  sample != 0: next_out[i] is drawn by slot slots[i]'s sampler as kr_decode_step_multi_sample draws it,
+   one draw per row on the last token's logits (seen set and RNG advance once).  A prompt enters a slot by calls of this alone, chunk by chunk, beside
+   decode rows (counts 1) of other slots; the store's own sequence is never touched.  Distinct slots, 1 <= n <= KR_MULTI_MAX.  Refused as
+   kr_decode_step_multi refuses (same codes), and as KR_ERR_VALUE naming the row: a count < 1, T > KR_EXTEND_MAX_TOKENS, a token of a run outside the
+   vocabulary, a run that ends outside the slot or past a rope table; a refused call changes nothing.  Under "multi_attn_fast" over slots of
+   max_seq > 1024 every token carries the bits kr_decode_step_multi gives it under the option. */
+#define KR_EXTEND_MAX_TOKENS 1024      /* = the exact prompt pass's chunk */
+int kr_decode_extend_multi(kr_decode_store* s, int n, const int32_t* slots, const int32_t* counts, const int32_t* tokens, const int32_t* positions,
+                           int32_t* next_out, float* logits_out, int sample, void* stream);
 /* test aid (like kr_sample_order): the batched sampler on host logits [n][vocab] with per-row parameters, seen bitmaps [n][(vocab+31)/32]
    (may be NULL: none seen) and xorshift64 states (in / out); tokens_out[n].  force_loop != 0: every sampled row takes the single-row sampler
    (the "multi_sample_loop" form). */

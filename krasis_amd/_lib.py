@@ -13,6 +13,7 @@ KR_SCORE_SIGMOID, KR_SCORE_SOFTMAX, KR_SCORE_TOPK_SOFTMAX = 0, 1, 2
 KR_ROUTE_RULE_ENGINE, KR_ROUTE_RULE_DECODE = 0, 1
 KR_VERIFY_MAX, KR_LOOKUP_NGRAM_MAX = 16, 32    # exact speculative decoding: tokens per verify pass, longest indexed n-gram
 KR_MULTI_MAX = 256                             # multi-sequence decode: rows per step
+KR_EXTEND_MAX_TOKENS = 1024                    # multi-sequence extend: tokens per call, all rows together
 
 # every symbol include/krasis_hip.h declares (checked by tests/test_abi.py without a GPU)
 SYMBOLS = [
@@ -31,6 +32,7 @@ SYMBOLS = [
     "kr_decode_weight_bytes", "kr_decode_verify", "kr_decode_commit", "kr_decode_generate_lookup", "kr_lookup_draft",
     "kr_decode_slots_create", "kr_decode_slot_save", "kr_decode_slot_load", "kr_decode_step_multi", "kr_decode_generate_multi",
     "kr_decode_slot_sampler", "kr_decode_step_multi_sample", "kr_decode_generate_multi_sample", "kr_sample_rows",
+    "kr_decode_extend_multi",
 ]
 TOKEN_CB = C.CFUNCTYPE(C.c_int, C.c_int, C.c_int, C.c_void_p)      # kr_token_cb(token, finish_reason, user) -> continue?
 
@@ -180,6 +182,7 @@ def load_library() -> C.CDLL:
     lib.kr_decode_slot_sampler.argtypes = [vp, ci, ci, cf, ci, cf, cf, C.c_uint64]
     lib.kr_decode_step_multi_sample.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp]
     lib.kr_decode_generate_multi_sample.argtypes = [vp, ci, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp]
+    lib.kr_decode_extend_multi.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, ci, vp]
     lib.kr_sample_rows.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp, vp, vp, ci]
     _lib = lib
     return lib

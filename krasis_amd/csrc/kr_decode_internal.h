@@ -117,4 +117,7 @@ int kr_standalone_cancelled(kr_decode_store* s);
 // kr_decode_prefill.cpp: the layers + final norm + lm_head GEMM of the multi-sequence step, one row per slot, on `st` in s->multi's arena;
 // d_rows = [slots | tokens | positions] on the device, logits -> s->multi->logits [n][vocab]
 int kr_multi_pass(kr_decode_store* s, int n, const int32_t* d_rows, int max_pos, hipStream_t st);
+// the same over n_rows token rows in n_runs runs of consecutive tokens per slot (kr_decode_extend_multi): d_rows = [slots | tokens | positions] of n_rows each, the
+// last token of run i in row i; d_runs = n_runs x [slot, off, cnt] (kr_multi.h); logits of the first n_runs rows only
+int kr_multi_pass_runs(kr_decode_store* s, int n_rows, int n_runs, const int32_t* d_rows, const int32_t* d_runs, int max_pos, hipStream_t st);
 void kr_standalone_set_elapsed(kr_decode_store* s, double sec);   // kr_engine.cpp: per (group, column) nibble sums for the int8-MFMA GEMM

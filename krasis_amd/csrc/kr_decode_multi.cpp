@@ -6,6 +6,8 @@
 // and each row of them equals the decode step bit for bit whatever rows share the pass; the sections that tie rows to one sequence (linear attention, GQA, MLA) run
 // per-slot kernels (kr_multi.hip) with the decode step's arithmetic.  So row i of a step carries exactly the bits kr_decode_step gives on
 // that sequence alone.  The store's own sequence is the hand-over point: prompt pass -> kr_decode_slot_save -> steps -> kr_decode_slot_load.
+// kr_decode_extend_multi (docs/design/17-multi-extend.md) is the same pass with a run of tokens per row: a prompt enters a slot chunk by chunk beside the
+// decode rows of other slots, each run bit-identical to that many kr_decode_step calls, without the store's own sequence.
 #include <algorithm>
 #include <chrono>
 #include <cstring>
@@ -77,6 +79,37 @@ int check_rows(kr_decode_store* s, int n, const int32_t* slots, const int32_t* t
     }
     return KR_OK;
 }
+// the rows of one extend call (kr_decode_extend_multi): check_rows' tests for runs of counts[i] tokens per row, every refusal naming its row
+int check_runs(kr_decode_store* s, int n, const int32_t* slots, const int32_t* counts, const int32_t* tokens, const int32_t* positions) {
+    const kr_multi_state& M = *s->multi;
+    if (n < 1 || n > KR_MULTI_MAX) return kr_fail(KR_ERR_VALUE, "%d rows, must be in [1, %d]", n, KR_MULTI_MAX);
+    if (!slots || !counts || !tokens || !positions) return kr_fail(KR_ERR_VALUE, "null slots / counts / tokens / positions");
+    std::vector<char> seen((size_t)M.n_slots, 0);
+    int mla_rope = 0; bool has_mla = false;
+    for (const DLayer& L : s->layers) if (L.attn == ATTN_MLA) { mla_rope = has_mla ? std::min(mla_rope, L.mla_rope_seq) : L.mla_rope_seq; has_mla = true; }
+    int total = 0;
+    for (int i = 0; i < n; i++) {      // the runs first: everything below indexes tokens by them
+        if (counts[i] < 1) return kr_fail(KR_ERR_VALUE, "row %d: a run of %d tokens, must be at least 1", i, counts[i]);
+        if (counts[i] > KR_EXTEND_MAX_TOKENS - total)
+            return kr_fail(KR_ERR_VALUE, "row %d: its run of %d tokens brings the call past %d tokens (KR_EXTEND_MAX_TOKENS)", i, counts[i], KR_EXTEND_MAX_TOKENS);
+        total += counts[i];
+    }
+    total = 0;
+    for (int i = 0; i < n; i++) {
+        if (slots[i] < 0 || slots[i] >= M.n_slots) return kr_fail(KR_ERR_VALUE, "row %d: slot %d out of range [0, %d)", i, slots[i], M.n_slots);
+        if (seen[(size_t)slots[i]]++) return kr_fail(KR_ERR_VALUE, "row %d: slot %d is named twice", i, slots[i]);
+        for (int t = 0; t < counts[i]; t++) {
+            const int tk = tokens[(size_t)total + t];
+            if (tk < 0 || tk >= s->vocab) return kr_fail(KR_ERR_VALUE, "row %d: token %d of its run, id %d, out of range (vocab %d)", i, t, tk, s->vocab);
+        }
+        total += counts[i];
+        const long long last = (long long)positions[i] + counts[i] - 1;     // the last position this row consumes
+        if (positions[i] < 0 || last >= M.max_seq) return kr_fail(KR_ERR_VALUE, "row %d: positions [%d, %lld] outside the slot's [0, %d)", i, positions[i], last, M.max_seq);
+        if (s->max_rope_seq > 0 && last >= s->max_rope_seq) return kr_fail(KR_ERR_VALUE, "row %d: position %lld past the rope table (%d)", i, last, s->max_rope_seq);
+        if (has_mla && last >= mla_rope) return kr_fail(KR_ERR_VALUE, "row %d: position %lld past the MLA rope table (%d)", i, last, mla_rope);
+    }
+    return KR_OK;
+}
 // what row b of a sampled step does: the three paths of kr_decode_generate's loop (kr_decode.cpp generate_core) for its slot's sampler
 KrMsRow sample_row(kr_decode_store* s, int slot) {
     const kr_multi_state& M = *s->multi;
@@ -112,23 +145,43 @@ KrMsArgs sampler_args(kr_multi_state& M, const float* logits, int vocab, int n, 
     a.loop_keys = (uint64_t*)M.smp_keys.p; a.loop_temp = M.smp_temp.p; a.loop_temp_bytes = M.smp_temp_bytes; a.loop_probs = (float*)M.smp_probs.p;
     return a;
 }
-// one step, arguments checked: rows -> device, the pass, per-row argmax (sample: each slot's sampler), ids (and logits) back; returns once next_out is written
+// one step, arguments checked: rows -> device, the pass, per-row argmax (sample: each slot's sampler), ids (and logits) back; returns once next_out is written.
+// counts (kr_decode_extend_multi): row i is a run of counts[i] tokens at positions[i] ...; the pass then has one row per token, the last token of run i in row i
+// and the others from row n on in call order, so everything after the pass (logits, argmax, sampler) sees the same n rows as a step
 int step_impl(kr_decode_store* s, int n, const int32_t* slots, const int32_t* tokens, const int32_t* positions, int32_t* next_out, float* logits_out, hipStream_t st,
-              bool sample = false) {
+              bool sample = false, const int32_t* counts = nullptr) {
     kr_multi_state& M = *s->multi;
-    if (M.rows.ensure((size_t)3 * KR_MULTI_MAX * 4) || M.ids.ensure((size_t)KR_MULTI_MAX * 4)) return kr_fail(KR_ERR_HIP, "hipMalloc of the step's row buffers failed");
+    if (M.rows.ensure((size_t)3 * (counts ? KR_EXTEND_MAX_TOKENS + KR_MULTI_MAX : KR_MULTI_MAX) * 4) || M.ids.ensure((size_t)KR_MULTI_MAX * 4))
+        return kr_fail(KR_ERR_HIP, "hipMalloc of the step's row buffers failed");
     std::vector<KrMsRow> sr;
     bool greedy = true;
     if (sample) {
         for (int i = 0; i < n; i++) { sr.push_back(sample_row(s, slots[i])); greedy &= sr.back().mode == KR_MS_GREEDY; }
         if (!greedy && sampler_scratch(M, s->vocab, n, sr)) return kr_fail(KR_ERR_HIP, "hipMalloc of the sampled step's scratch failed");
     }
-    std::vector<int32_t> h((size_t)3 * n);
+    size_t T = (size_t)n;
+    if (counts) { T = 0; for (int i = 0; i < n; i++) T += (size_t)counts[i]; }
+    std::vector<int32_t> h(3 * T + (counts ? (size_t)3 * n : 0));      // [slots | tokens | positions] of T rows (| runs [n][slot, off, cnt])
     int max_pos = 0;
-    for (int i = 0; i < n; i++) { h[(size_t)i] = slots[i]; h[(size_t)n + i] = tokens[i]; h[(size_t)2 * n + i] = positions[i]; max_pos = std::max(max_pos, positions[i]); }
+    if (!counts)
+        for (int i = 0; i < n; i++) { h[(size_t)i] = slots[i]; h[(size_t)n + i] = tokens[i]; h[(size_t)2 * n + i] = positions[i]; max_pos = std::max(max_pos, positions[i]); }
+    else {
+        size_t src = 0, off = (size_t)n;
+        for (int i = 0; i < n; i++) {
+            int32_t* run = &h[3 * T + (size_t)3 * i];
+            run[0] = slots[i]; run[1] = (int32_t)off; run[2] = counts[i];
+            for (int t = 0; t < counts[i]; t++) {
+                const size_t row = t == counts[i] - 1 ? (size_t)i : off + t;
+                h[row] = slots[i]; h[T + row] = tokens[src + t]; h[2 * T + row] = positions[i] + t;
+            }
+            src += (size_t)counts[i]; off += (size_t)counts[i] - 1;
+            max_pos = std::max(max_pos, positions[i] + counts[i] - 1);
+        }
+    }
     KR_HIP(hipMemcpyAsync(M.rows.p, h.data(), h.size() * 4, hipMemcpyHostToDevice, st));
     if (!greedy) KR_HIP(hipMemcpyAsync(M.smp_rows.p, sr.data(), sr.size() * sizeof(KrMsRow), hipMemcpyHostToDevice, st));
-    if (int rc = kr_multi_pass(s, n, (const int32_t*)M.rows.p, max_pos, st)) { (void)hipStreamSynchronize(st); return rc; }
+    if (int rc = counts ? kr_multi_pass_runs(s, (int)T, n, (const int32_t*)M.rows.p, (const int32_t*)M.rows.p + 3 * T, max_pos, st)
+                        : kr_multi_pass(s, n, (const int32_t*)M.rows.p, max_pos, st)) { (void)hipStreamSynchronize(st); return rc; }
     const size_t V = (size_t)s->vocab;
     if (greedy) kr_launch_multi_argmax((const float*)M.logits.p, V, (int)V, n, (int*)M.ids.p, st);
     else if (kr_launch_multi_sample(sampler_args(M, (const float*)M.logits.p, s->vocab, n, sr, (uint32_t*)M.smp_seen.p, M.smp_words, (uint64_t*)M.smp_rng.p, (int*)M.ids.p), st)) {
@@ -331,6 +384,20 @@ extern "C" int kr_decode_step_multi_sample(kr_decode_store* s, int n, const int3
     hipStream_t st = kr_pick_stream(s->eng, stream);
     if (int rc = order_after_store(s, st)) return rc;
     return step_impl(s, n, slots, tokens, positions, next_out, logits_out, st, true);
+}
+
+// ---- multi-token extend of slots (docs/design/17-multi-extend.md)
+extern "C" int kr_decode_extend_multi(kr_decode_store* s, int n, const int32_t* slots, const int32_t* counts, const int32_t* tokens, const int32_t* positions,
+                                      int32_t* next_out, float* logits_out, int sample, void* stream) {
+    if (int rc = multi_ready(s)) return rc;
+    if (int rc = need_slots(s)) return rc;
+    if (int rc = multi_refuse(s)) return rc;
+    if (int rc = check_runs(s, n, slots, counts, tokens, positions)) return rc;
+    if (!next_out) return kr_fail(KR_ERR_VALUE, "null next_out");
+    KR_HIP(hipSetDevice(s->eng->device));
+    hipStream_t st = kr_pick_stream(s->eng, stream);
+    if (int rc = order_after_store(s, st)) return rc;
+    return step_impl(s, n, slots, tokens, positions, next_out, logits_out, st, sample != 0, counts);
 }
 
 extern "C" int kr_decode_generate_multi_sample(kr_decode_store* s, int n, const int32_t* slots, const int32_t* first_tokens, const int32_t* start_positions,

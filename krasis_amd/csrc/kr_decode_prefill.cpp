@@ -42,6 +42,7 @@ struct Chunk {      // one chunk of the prompt in flight: its arena, stream and 
     KrPfSync sy;      // this (chunk, layer)'s hand-overs with the previous / next chunk (set by the scheduler before every run_layer)
     bool verify = false;      // kr_decode_verify's pass: linear-attention layers write their recurrence inputs into the store's verify buffers (kr_spec.h)
     const int32_t* m_slots = nullptr; const int32_t* m_pos = nullptr; int m_sc_ld = 0; int m_fd_chunk = 0, m_fd_chunks = 0;   // the multi-sequence step: row b = slot m_slots[b] at m_pos[b] (device)
+    const int32_t* m_runs = nullptr; int m_nruns = 0;      // kr_decode_extend_multi: m_nruns x [slot, off, cnt] (device), the runs of token rows per slot (kr_multi.h); null: one token per slot
 };
 size_t al(size_t n) { return (n + 255) & ~(size_t)255; }
 }  // namespace
@@ -112,7 +113,7 @@ static int run_layer(kr_decode_store* s, Chunk& cx, size_t li) {
             m.conv_state = (float*)M.a[li].p; m.conv_stride = M.a_stride[li] / 4; m.recur = (float*)M.b[li].p; m.recur_stride = M.b_stride[li] / 4;
             m.conv_out = B.cv; m.out = B.attn; m.ld_out = oc; m.nk = L.nk; m.nv = L.nv; m.dk = L.dk; m.dv = L.dv; m.hr = L.nv / L.nk; m.scale = L.la_scale; m.eps = s->eps;
             if (oc != L.nv * L.dv) return kr_fail(KR_ERR_VALUE, "out_proj cols %d != nv*dv", oc);
-            if (kr_launch_multi_la(m, Cc, st)) return kr_fail(KR_ERR_VALUE, "unsupported linear-attention geometry for the multi-sequence step");
+            if (cx.m_runs ? kr_launch_multi_la_run(m, cx.m_runs, cx.m_nruns, Cc, st) : kr_launch_multi_la(m, Cc, st)) return kr_fail(KR_ERR_VALUE, "unsupported linear-attention geometry for the multi-sequence step");
         } else {
             KrPfmLaArgs a{};
             a.qkvz = qkvz; a.ld_qkvz = nq; a.ba = B.pb; a.ld_ba = nb; a.conv_state = (float*)L.conv_state.p; a.conv_w = (const float*)L.conv_w.p;
@@ -684,8 +685,10 @@ extern "C" int kr_decode_commit(kr_decode_store* s, int n_keep) {
 // the multi-sequence step (kr_decode_multi.cpp, docs/design/13-multi-sequence.md): one chunk of n rows, row b = the next token of slot slots[b].
 // Every row-wise section of run_layer runs unchanged; the linear-attention, GQA and MLA sections take the per-slot kernels (kr_multi.hip).  All-row
 // logits as in the verify pass.  Engine buffer set KR_PF_MAX_DEPTH - 1; the caller has ordered this pass after everything the store queued.
+// kr_multi_pass_runs (kr_decode_extend_multi, docs/design/17-multi-extend.md): n token rows in n_final runs of consecutive tokens per slot, d_runs =
+// n_final x [slot, off, cnt] after kr_multi.h; the last token of run i is row i, so the final norm, lm_head GEMM and M.logits cover the first n_final rows only.
 // ------------------------------------------------------------------------------------------------
-int kr_multi_pass(kr_decode_store* s, int n, const int32_t* d_rows, int max_pos, hipStream_t st) {
+static int multi_pass(kr_decode_store* s, int n, int n_final, const int32_t* d_rows, const int32_t* d_runs, int max_pos, hipStream_t st) {
     kr_multi_state& M = *s->multi;
     PfLayout Lo;
     if (int rc = pf_layout(s, (size_t)n, true, true, st, Lo)) return rc;
@@ -715,13 +718,19 @@ int kr_multi_pass(kr_decode_store* s, int n, const int32_t* d_rows, int max_pos,
     }
     const bool need_scores = (has_gqa && !flash) || has_mla;
     const int sc_ld = (max_pos + 1 + 31) & ~31;
-    if (M.scratch.ensure(Lo.total) || (need_scores && M.scores.ensure((size_t)n * nh_max * sc_ld * 4)) || M.logits.ensure((size_t)n * s->vocab * 4))
-        return kr_fail(KR_ERR_HIP, "hipMalloc of the multi-sequence step's scratch (%zu MiB) failed", (Lo.total + (size_t)n * (nh_max * sc_ld + s->vocab) * 4) >> 20);
+    if (M.scratch.ensure(Lo.total) || (need_scores && M.scores.ensure((size_t)n * nh_max * sc_ld * 4)) || M.logits.ensure((size_t)n_final * s->vocab * 4))
+        return kr_fail(KR_ERR_HIP, "hipMalloc of the multi-sequence step's scratch (%zu MiB) failed", (Lo.total + ((size_t)n * nh_max * sc_ld + (size_t)n_final * s->vocab) * 4) >> 20);
     Chunk cx{};
     cx.B = pf_carve(Lo, (char*)M.scratch.p); cx.scores = nullptr; cx.tok = d_rows + n; cx.Cc = n; cx.pos0 = 0; cx.set = KR_PF_MAX_DEPTH - 1;
     cx.first = true; cx.add_is_emb = true; cx.st = st;
     cx.m_slots = d_rows; cx.m_pos = d_rows + 2 * n; cx.m_sc_ld = sc_ld; cx.m_fd_chunk = fd_chunk; cx.m_fd_chunks = fd_chunks;
+    cx.m_runs = d_runs; cx.m_nruns = d_runs ? n_final : 0;
     for (size_t l = 0; l < s->layers.size(); l++)
         if (int rc = run_layer(s, cx, l)) return rc;
+    cx.Cc = n_final;
     return final_rows(s, cx, (float*)M.logits.p);
+}
+int kr_multi_pass(kr_decode_store* s, int n, const int32_t* d_rows, int max_pos, hipStream_t st) { return multi_pass(s, n, n, d_rows, nullptr, max_pos, st); }
+int kr_multi_pass_runs(kr_decode_store* s, int n_rows, int n_runs, const int32_t* d_rows, const int32_t* d_runs, int max_pos, hipStream_t st) {
+    return multi_pass(s, n_rows, n_runs, d_rows, d_runs, max_pos, st);
 }

@@ -18,6 +18,11 @@ struct KrMultiLaArgs {
 };
 // 0: launched; 1: geometry not covered (kd 4 is the caller's check; dk 64 / 128, dv <= 256, dv % 8 == 0)
 int kr_launch_multi_la(const KrMultiLaArgs& a, int B, hipStream_t st);
+// the same over runs of consecutive tokens per slot (kr_decode_extend_multi, docs/design/17-multi-extend.md).  runs (device) = n_runs x
+// [slot, off, cnt]: run i's tokens are, in order, rows off .. off + cnt - 2 and then row i of qkvz / ba / conv_out / out; a.slots is not read.  The
+// slot's conv and recurrent state are loaded once, carried in registers through the run and stored once.  Slots distinct across runs; max_cnt = a bound
+// on every cnt, at most 1024 (the gate rows the recurrence kernel keeps in LDS).  Returns as above (1 also for max_cnt out of range).
+int kr_launch_multi_la_run(const KrMultiLaArgs& a, const int* runs, int n_runs, int max_cnt, hipStream_t st);
 
 // GQA, one token per row: QK-norm + RoPE at the row's position, K / V appended to the row's slot, attention over the slot's rows [0, pos]
 struct KrMultiGqaArgs {

@@ -476,6 +476,41 @@ class CpuDecodeStore:
         check(self._lib.kr_decode_step_multi_sample(self._h, n, arr(slots), arr(tokens), arr(positions), ids, out.ctypes.data if logits else None, None))
         return (list(ids[:n]), out) if logits else list(ids[:n])
 
+    def extend_multi(self, slots: Sequence[int], token_lists: Sequence[Sequence[int]], positions: Sequence[int], logits: bool = False,
+                     sample: bool = False):
+        """kr_decode_extend_multi: row i = slot slots[i] consumes the tokens token_lists[i] (at least one) at positions[i], positions[i] + 1, ...,
+        bit-identical to that many decode_step calls on that sequence alone (every KV row -- or MLA latent and rope-key row -- they append, conv and
+        recurrent state, the last token's logits and id), however a token stream is cut into calls and whatever rows share the pass.  At most
+        KR_EXTEND_MAX_TOKENS tokens per call, all rows together.  Returns one id per row -- the greedy id after its last token, or with sample=True the
+        draw of the slot's sampler (set_slot_sampler) on those logits, as step_multi_sample draws it -- or (ids, logits f32 [n, vocab]) with logits=True."""
+        self._need()
+        n = len(slots)
+        if len(token_lists) != n or len(positions) != n:
+            raise ValueError(f"{n} slots, {len(token_lists)} token lists, {len(positions)} positions")
+        flat = [int(t) for run in token_lists for t in run]
+        arr = lambda xs: (C.c_int32 * max(len(xs), 1))(*xs)
+        ids = (C.c_int32 * max(n, 1))()
+        out = np.empty((n, self._vocab), np.float32) if logits else None
+        check(self._lib.kr_decode_extend_multi(self._h, n, arr(list(slots)), arr([len(run) for run in token_lists]), arr(flat), arr(list(positions)), ids,
+                                               out.ctypes.data if logits else None, 1 if sample else 0, None))
+        return (list(ids[:n]), out) if logits else list(ids[:n])
+
+    def prefill_slot(self, slot: int, tokens: Sequence[int], start_pos: int = 0, chunk: Optional[int] = None) -> int:
+        """A prompt straight into a slot: extend_multi over chunks of `chunk` tokens (default KR_EXTEND_MAX_TOKENS).  The slot afterwards equals
+        prefill(tokens, start_pos) + save_slot bit for bit, and the store's own sequence, logits and last token are never touched.  Returns the greedy id
+        after the last token."""
+        from ._lib import KR_EXTEND_MAX_TOKENS
+        chunk = KR_EXTEND_MAX_TOKENS if chunk is None else int(chunk)
+        if not 1 <= chunk <= KR_EXTEND_MAX_TOKENS:
+            raise ValueError(f"chunk {chunk} outside [1, {KR_EXTEND_MAX_TOKENS}]")
+        tokens = list(tokens)
+        if not tokens:
+            raise ValueError("prefill_slot: empty prompt")
+        last = -1
+        for i in range(0, len(tokens), chunk):
+            last = self.extend_multi([slot], [tokens[i:i + chunk]], [start_pos + i])[0]
+        return last
+
     def generate_stream(self, first_token: int, start_position: int, max_tokens: int, temperature: float, top_k: int, top_p: float,
                         stop_ids: Sequence[int], tokenizer, presence_penalty: float, on_token, rng_seed: int = 0) -> int:
         """decode.rs:3611 -- the cancellable loop of the reference's Rust server.  on_token(token_id, text, finish_reason) -> bool (False cancels);
