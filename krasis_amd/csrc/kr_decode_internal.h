@@ -114,10 +114,8 @@ void kr_standalone_release(kr_decode_store* s);
 int kr_spec_refuse(kr_decode_store* s);          // kr_decode_prefill.cpp: KR_OK when exact speculative decoding can run on this store
 int kr_spec_pending_fail(kr_decode_store* s);    // KR_ERR_STATE while a verify waits for its commit
 int kr_standalone_cancelled(kr_decode_store* s);
-// kr_decode_prefill.cpp: the layers + final norm + lm_head GEMM of the multi-sequence step, one row per slot, on `st` in s->multi's arena;
-// d_rows = [slots | tokens | positions] on the device, logits -> s->multi->logits [n][vocab]
-int kr_multi_pass(kr_decode_store* s, int n, const int32_t* d_rows, int max_pos, hipStream_t st);
-// the same over n_rows token rows in n_runs runs of consecutive tokens per slot (kr_decode_extend_multi): d_rows = [slots | tokens | positions] of n_rows each, the
-// last token of run i in row i; d_runs = n_runs x [slot, off, cnt] (kr_multi.h); logits of the first n_runs rows only
-int kr_multi_pass_runs(kr_decode_store* s, int n_rows, int n_runs, const int32_t* d_rows, const int32_t* d_runs, int max_pos, hipStream_t st);
+// kr_decode_prefill.cpp: the layers + final norm + lm_head GEMM of the multi-sequence pass on `st` in s->multi's arena: n_rows token rows in n_runs runs of
+// consecutive tokens per slot (a step: runs of one).  d_rows = [slots | tokens | positions] of n_rows each on the device, the last token of run i in row i;
+// d_runs = n_runs x [slot, off, cnt] (kr_multi.h); logits of the first n_runs rows -> s->multi->logits [n_runs][vocab]
+int kr_multi_pass(kr_decode_store* s, int n_rows, int n_runs, const int32_t* d_rows, const int32_t* d_runs, int max_pos, hipStream_t st);
 void kr_standalone_set_elapsed(kr_decode_store* s, double sec);   // kr_engine.cpp: per (group, column) nibble sums for the int8-MFMA GEMM

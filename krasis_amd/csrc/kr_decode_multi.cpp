@@ -7,7 +7,8 @@
 // per-slot kernels (kr_multi.hip) with the decode step's arithmetic.  So row i of a step carries exactly the bits kr_decode_step gives on
 // that sequence alone.  The store's own sequence is the hand-over point: prompt pass -> kr_decode_slot_save -> steps -> kr_decode_slot_load.
 // kr_decode_extend_multi (docs/design/17-multi-extend.md) is the same pass with a run of tokens per row: a prompt enters a slot chunk by chunk beside the
-// decode rows of other slots, each run bit-identical to that many kr_decode_step calls, without the store's own sequence.
+// decode rows of other slots, each run bit-identical to that many kr_decode_step calls, without the store's own sequence.  A step is an extend whose every
+// run has one token: both take one argument check, one flatten and one pass (step_entry / step_impl below).
 #include <algorithm>
 #include <chrono>
 #include <cstring>
@@ -59,68 +60,60 @@ int need_slots(kr_decode_store* s) {
         return kr_fail(KR_ERR_STATE, "the slots hold %s KV rows but the store uses %s now: create them again", s->multi->kv_fp8 ? "E4M3" : "FP16", s->kv_fp8 ? "E4M3" : "FP16");
     return KR_OK;
 }
-// the rows of one step: distinct slots in range, tokens in the vocabulary, positions inside the slot and the rope tables (the store's, and every MLA
-// layer's own: the shortest bounds the step)
-int check_rows(kr_decode_store* s, int n, const int32_t* slots, const int32_t* tokens, const int32_t* positions, int extra) {
-    const kr_multi_state& M = *s->multi;
-    if (n < 1 || n > KR_MULTI_MAX) return kr_fail(KR_ERR_VALUE, "%d rows, must be in [1, %d]", n, KR_MULTI_MAX);
-    if (!slots || !tokens || !positions) return kr_fail(KR_ERR_VALUE, "null slots / tokens / positions");
-    std::vector<char> seen((size_t)M.n_slots, 0);
-    int mla_rope = 0; bool has_mla = false;
-    for (const DLayer& L : s->layers) if (L.attn == ATTN_MLA) { mla_rope = has_mla ? std::min(mla_rope, L.mla_rope_seq) : L.mla_rope_seq; has_mla = true; }
-    for (int i = 0; i < n; i++) {
-        if (slots[i] < 0 || slots[i] >= M.n_slots) return kr_fail(KR_ERR_VALUE, "row %d: slot %d out of range [0, %d)", i, slots[i], M.n_slots);
-        if (seen[(size_t)slots[i]]++) return kr_fail(KR_ERR_VALUE, "slot %d is named twice", slots[i]);
-        if (tokens[i] < 0 || tokens[i] >= s->vocab) return kr_fail(KR_ERR_VALUE, "row %d: token id %d out of range (vocab %d)", i, tokens[i], s->vocab);
-        const int last = positions[i] + extra;     // the last position this call consumes
-        if (positions[i] < 0 || last >= M.max_seq) return kr_fail(KR_ERR_VALUE, "row %d: positions [%d, %d] outside the slot's [0, %d)", i, positions[i], last, M.max_seq);
-        if (s->max_rope_seq > 0 && last >= s->max_rope_seq) return kr_fail(KR_ERR_VALUE, "row %d: position %d past the rope table (%d)", i, last, s->max_rope_seq);
-        if (has_mla && last >= mla_rope) return kr_fail(KR_ERR_VALUE, "row %d: position %d past the MLA rope table (%d)", i, last, mla_rope);
-    }
-    return KR_OK;
+// what every entry point that touches the slots starts with
+int multi_begin(kr_decode_store* s) {
+    if (int rc = multi_ready(s)) return rc;
+    if (int rc = need_slots(s)) return rc;
+    return multi_refuse(s);
 }
-// the rows of one extend call (kr_decode_extend_multi): check_rows' tests for runs of counts[i] tokens per row, every refusal naming its row
-int check_runs(kr_decode_store* s, int n, const int32_t* slots, const int32_t* counts, const int32_t* tokens, const int32_t* positions) {
+// the rows of one call, every refusal naming its row: distinct slots in range, tokens in the vocabulary, positions inside the slot and the rope tables (the
+// store's, and every MLA layer's own: the shortest bounds the call).  Row i is a run of counts[i] tokens at positions[i] ... (counts null: one token per
+// row); extra = further positions the caller will consume after the run (generate_impl)
+int check_args(kr_decode_store* s, int n, const int32_t* slots, const int32_t* counts, const int32_t* tokens, const int32_t* positions, int extra) {
     const kr_multi_state& M = *s->multi;
     if (n < 1 || n > KR_MULTI_MAX) return kr_fail(KR_ERR_VALUE, "%d rows, must be in [1, %d]", n, KR_MULTI_MAX);
-    if (!slots || !counts || !tokens || !positions) return kr_fail(KR_ERR_VALUE, "null slots / counts / tokens / positions");
+    if (!slots || !tokens || !positions) return kr_fail(KR_ERR_VALUE, "null slots / counts / tokens / positions");
     std::vector<char> seen((size_t)M.n_slots, 0);
     int mla_rope = 0; bool has_mla = false;
     for (const DLayer& L : s->layers) if (L.attn == ATTN_MLA) { mla_rope = has_mla ? std::min(mla_rope, L.mla_rope_seq) : L.mla_rope_seq; has_mla = true; }
+    auto cnt = [&](int i) { return counts ? counts[i] : 1; };
     int total = 0;
     for (int i = 0; i < n; i++) {      // the runs first: everything below indexes tokens by them
-        if (counts[i] < 1) return kr_fail(KR_ERR_VALUE, "row %d: a run of %d tokens, must be at least 1", i, counts[i]);
-        if (counts[i] > KR_EXTEND_MAX_TOKENS - total)
-            return kr_fail(KR_ERR_VALUE, "row %d: its run of %d tokens brings the call past %d tokens (KR_EXTEND_MAX_TOKENS)", i, counts[i], KR_EXTEND_MAX_TOKENS);
-        total += counts[i];
+        if (cnt(i) < 1) return kr_fail(KR_ERR_VALUE, "row %d: a run of %d tokens, must be at least 1", i, cnt(i));
+        if (cnt(i) > KR_EXTEND_MAX_TOKENS - total)
+            return kr_fail(KR_ERR_VALUE, "row %d: its run of %d tokens brings the call past %d tokens (KR_EXTEND_MAX_TOKENS)", i, cnt(i), KR_EXTEND_MAX_TOKENS);
+        total += cnt(i);
     }
     total = 0;
     for (int i = 0; i < n; i++) {
         if (slots[i] < 0 || slots[i] >= M.n_slots) return kr_fail(KR_ERR_VALUE, "row %d: slot %d out of range [0, %d)", i, slots[i], M.n_slots);
         if (seen[(size_t)slots[i]]++) return kr_fail(KR_ERR_VALUE, "row %d: slot %d is named twice", i, slots[i]);
-        for (int t = 0; t < counts[i]; t++) {
+        for (int t = 0; t < cnt(i); t++) {
             const int tk = tokens[(size_t)total + t];
             if (tk < 0 || tk >= s->vocab) return kr_fail(KR_ERR_VALUE, "row %d: token %d of its run, id %d, out of range (vocab %d)", i, t, tk, s->vocab);
         }
-        total += counts[i];
-        const long long last = (long long)positions[i] + counts[i] - 1;     // the last position this row consumes
+        total += cnt(i);
+        const long long last = (long long)positions[i] + cnt(i) - 1 + extra;     // the last position this row consumes
         if (positions[i] < 0 || last >= M.max_seq) return kr_fail(KR_ERR_VALUE, "row %d: positions [%d, %lld] outside the slot's [0, %d)", i, positions[i], last, M.max_seq);
         if (s->max_rope_seq > 0 && last >= s->max_rope_seq) return kr_fail(KR_ERR_VALUE, "row %d: position %lld past the rope table (%d)", i, last, s->max_rope_seq);
         if (has_mla && last >= mla_rope) return kr_fail(KR_ERR_VALUE, "row %d: position %lld past the MLA rope table (%d)", i, last, mla_rope);
     }
     return KR_OK;
 }
-// what row b of a sampled step does: the three paths of kr_decode_generate's loop (kr_decode.cpp generate_core) for its slot's sampler
+// what a row with these sampler parameters does: the three paths of kr_decode_generate's loop (kr_decode.cpp generate_core)
+KrMsRow mode_row(int slot, float temperature, int top_k, float top_p, float penalty, int vocab, bool force_loop) {
+    KrMsRow r{KR_MS_GREEDY, slot, 0, top_k, temperature, 0.0f, top_p, penalty};
+    r.k = (top_k > 0 && top_k < vocab) ? top_k : vocab;
+    if (temperature == 0.0f) r.mode = penalty != 0.0f ? KR_MS_PENALTY : KR_MS_GREEDY;
+    else { r.mode = (r.k <= KR_MS_SEL_CAP && !force_loop) ? KR_MS_SAMPLE : KR_MS_LOOP; r.inv_temp = 1.0f / temperature; }
+    return r;
+}
+// row b of a sampled step: its slot's sampler (greedy while no slot has one)
 KrMsRow sample_row(kr_decode_store* s, int slot) {
     const kr_multi_state& M = *s->multi;
-    KrMsRow r{KR_MS_GREEDY, slot, 0, 0, 0.0f, 0.0f, 1.0f, 0.0f};
-    if (M.smp.empty()) return r;
+    if (M.smp.empty()) return KrMsRow{KR_MS_GREEDY, slot, 0, 0, 0.0f, 0.0f, 1.0f, 0.0f};
     const kr_multi_state::Sampler& p = M.smp[(size_t)slot];
-    r.temperature = p.temperature; r.top_k = p.top_k; r.top_p = p.top_p; r.penalty = p.penalty;
-    r.k = (p.top_k > 0 && p.top_k < s->vocab) ? p.top_k : s->vocab;
-    if (p.temperature == 0.0f) r.mode = p.penalty != 0.0f ? KR_MS_PENALTY : KR_MS_GREEDY;
-    else { r.mode = (r.k <= KR_MS_SEL_CAP && !s->opt_multi_sample_loop) ? KR_MS_SAMPLE : KR_MS_LOOP; r.inv_temp = 1.0f / p.temperature; }
-    return r;
+    return mode_row(slot, p.temperature, p.top_k, p.top_p, p.penalty, s->vocab, s->opt_multi_sample_loop != 0);
 }
 // device scratch of the batched sampler for n rows of these modes (kr_sample_rows and the sampled step)
 int sampler_scratch(kr_multi_state& M, int vocab, int n, const std::vector<KrMsRow>& rows) {
@@ -145,13 +138,13 @@ KrMsArgs sampler_args(kr_multi_state& M, const float* logits, int vocab, int n, 
     a.loop_keys = (uint64_t*)M.smp_keys.p; a.loop_temp = M.smp_temp.p; a.loop_temp_bytes = M.smp_temp_bytes; a.loop_probs = (float*)M.smp_probs.p;
     return a;
 }
-// one step, arguments checked: rows -> device, the pass, per-row argmax (sample: each slot's sampler), ids (and logits) back; returns once next_out is written.
-// counts (kr_decode_extend_multi): row i is a run of counts[i] tokens at positions[i] ...; the pass then has one row per token, the last token of run i in row i
-// and the others from row n on in call order, so everything after the pass (logits, argmax, sampler) sees the same n rows as a step
+// one pass, arguments checked: rows -> device, the pass, per-row argmax (sample: each slot's sampler), ids (and logits) back; returns once next_out is written.
+// Row i is a run of counts[i] tokens at positions[i] ... (counts null: one token per row, a step); the pass has one row per token, the last token of run i in
+// row i and the others from row n on in call order, so everything after the pass (logits, argmax, sampler) sees n rows
 int step_impl(kr_decode_store* s, int n, const int32_t* slots, const int32_t* tokens, const int32_t* positions, int32_t* next_out, float* logits_out, hipStream_t st,
               bool sample = false, const int32_t* counts = nullptr) {
     kr_multi_state& M = *s->multi;
-    if (M.rows.ensure((size_t)3 * (counts ? KR_EXTEND_MAX_TOKENS + KR_MULTI_MAX : KR_MULTI_MAX) * 4) || M.ids.ensure((size_t)KR_MULTI_MAX * 4))
+    if (M.rows.ensure((size_t)3 * (KR_EXTEND_MAX_TOKENS + KR_MULTI_MAX) * 4) || M.ids.ensure((size_t)KR_MULTI_MAX * 4))
         return kr_fail(KR_ERR_HIP, "hipMalloc of the step's row buffers failed");
     std::vector<KrMsRow> sr;
     bool greedy = true;
@@ -159,29 +152,25 @@ int step_impl(kr_decode_store* s, int n, const int32_t* slots, const int32_t* to
         for (int i = 0; i < n; i++) { sr.push_back(sample_row(s, slots[i])); greedy &= sr.back().mode == KR_MS_GREEDY; }
         if (!greedy && sampler_scratch(M, s->vocab, n, sr)) return kr_fail(KR_ERR_HIP, "hipMalloc of the sampled step's scratch failed");
     }
-    size_t T = (size_t)n;
-    if (counts) { T = 0; for (int i = 0; i < n; i++) T += (size_t)counts[i]; }
-    std::vector<int32_t> h(3 * T + (counts ? (size_t)3 * n : 0));      // [slots | tokens | positions] of T rows (| runs [n][slot, off, cnt])
+    auto cnt = [&](int i) { return counts ? counts[i] : 1; };
+    size_t T = 0;
+    for (int i = 0; i < n; i++) T += (size_t)cnt(i);
+    std::vector<int32_t> h(3 * T + (size_t)3 * n);      // [slots | tokens | positions] of T rows | runs [n][slot, off, cnt] (unit counts: row i = token i, off = n)
     int max_pos = 0;
-    if (!counts)
-        for (int i = 0; i < n; i++) { h[(size_t)i] = slots[i]; h[(size_t)n + i] = tokens[i]; h[(size_t)2 * n + i] = positions[i]; max_pos = std::max(max_pos, positions[i]); }
-    else {
-        size_t src = 0, off = (size_t)n;
-        for (int i = 0; i < n; i++) {
-            int32_t* run = &h[3 * T + (size_t)3 * i];
-            run[0] = slots[i]; run[1] = (int32_t)off; run[2] = counts[i];
-            for (int t = 0; t < counts[i]; t++) {
-                const size_t row = t == counts[i] - 1 ? (size_t)i : off + t;
-                h[row] = slots[i]; h[T + row] = tokens[src + t]; h[2 * T + row] = positions[i] + t;
-            }
-            src += (size_t)counts[i]; off += (size_t)counts[i] - 1;
-            max_pos = std::max(max_pos, positions[i] + counts[i] - 1);
+    size_t src = 0, off = (size_t)n;
+    for (int i = 0; i < n; i++) {
+        int32_t* run = &h[3 * T + (size_t)3 * i];
+        run[0] = slots[i]; run[1] = (int32_t)off; run[2] = cnt(i);
+        for (int t = 0; t < cnt(i); t++) {
+            const size_t row = t == cnt(i) - 1 ? (size_t)i : off + t;
+            h[row] = slots[i]; h[T + row] = tokens[src + t]; h[2 * T + row] = positions[i] + t;
         }
+        src += (size_t)cnt(i); off += (size_t)cnt(i) - 1;
+        max_pos = std::max(max_pos, positions[i] + cnt(i) - 1);
     }
     KR_HIP(hipMemcpyAsync(M.rows.p, h.data(), h.size() * 4, hipMemcpyHostToDevice, st));
     if (!greedy) KR_HIP(hipMemcpyAsync(M.smp_rows.p, sr.data(), sr.size() * sizeof(KrMsRow), hipMemcpyHostToDevice, st));
-    if (int rc = counts ? kr_multi_pass_runs(s, (int)T, n, (const int32_t*)M.rows.p, (const int32_t*)M.rows.p + 3 * T, max_pos, st)
-                        : kr_multi_pass(s, n, (const int32_t*)M.rows.p, max_pos, st)) { (void)hipStreamSynchronize(st); return rc; }
+    if (int rc = kr_multi_pass(s, (int)T, n, (const int32_t*)M.rows.p, (const int32_t*)M.rows.p + 3 * T, max_pos, st)) { (void)hipStreamSynchronize(st); return rc; }
     const size_t V = (size_t)s->vocab;
     if (greedy) kr_launch_multi_argmax((const float*)M.logits.p, V, (int)V, n, (int*)M.ids.p, st);
     else if (kr_launch_multi_sample(sampler_args(M, (const float*)M.logits.p, s->vocab, n, sr, (uint32_t*)M.smp_seen.p, M.smp_words, (uint64_t*)M.smp_rng.p, (int*)M.ids.p), st)) {
@@ -203,12 +192,21 @@ int order_after_store(kr_decode_store* s, hipStream_t st) {
     KR_HIP(hipStreamWaitEvent(st, M.ev, 0));
     return KR_OK;
 }
+// the three stepping entry points: refusals, then the pass on the caller's stream
+int step_entry(kr_decode_store* s, int n, const int32_t* slots, const int32_t* counts, const int32_t* tokens, const int32_t* positions,
+               int32_t* next_out, float* logits_out, bool sample, void* stream) {
+    if (int rc = multi_begin(s)) return rc;
+    if (int rc = check_args(s, n, slots, counts, tokens, positions, 0)) return rc;
+    if (!next_out) return kr_fail(KR_ERR_VALUE, "null next_out");
+    KR_HIP(hipSetDevice(s->eng->device));
+    hipStream_t st = kr_pick_stream(s->eng, stream);
+    if (int rc = order_after_store(s, st)) return rc;
+    return step_impl(s, n, slots, tokens, positions, next_out, logits_out, st, sample, counts);
+}
 // slot <-> the store's own sequence: KV rows [0, seq_len) of every GQA layer, compressed-KV and rope-key rows [0, seq_len) of every MLA layer, conv +
 // recurrent state of every linear-attention layer
 int slot_copy(kr_decode_store* s, int slot, int seq_len, bool save) {
-    if (int rc = multi_ready(s)) return rc;
-    if (int rc = need_slots(s)) return rc;
-    if (int rc = multi_refuse(s)) return rc;
+    if (int rc = multi_begin(s)) return rc;
     kr_multi_state& M = *s->multi;
     if (slot < 0 || slot >= M.n_slots) return kr_fail(KR_ERR_VALUE, "slot %d out of range [0, %d)", slot, M.n_slots);
     const int lim = std::min(s->kv_max_seq, M.max_seq);
@@ -264,14 +262,12 @@ int generate_impl(kr_decode_store* s, int n, const int32_t* slots, const int32_t
                   const int* top_k, const float* top_p, const float* presence_penalty, const uint64_t* rng_seeds, const int* stop_ids, int n_stop,
                   int32_t* tokens_out, int32_t* n_out, void* stream) {
     const bool sample = temperature != nullptr;
-    if (int rc = multi_ready(s)) return rc;
-    if (int rc = need_slots(s)) return rc;
-    if (int rc = multi_refuse(s)) return rc;
+    if (int rc = multi_begin(s)) return rc;
     if (max_tokens < 0) return kr_fail(KR_ERR_VALUE, "max_tokens %d < 0", max_tokens);
     if (n_stop < 0 || (n_stop > 0 && !stop_ids)) return kr_fail(KR_ERR_VALUE, "bad stop ids (%d)", n_stop);
     if (!n_out || (max_tokens > 0 && !tokens_out)) return kr_fail(KR_ERR_VALUE, "null output pointer");
     // every row's last step (position start + max_tokens - 1) must fit its slot: checked here, before the first step
-    if (int rc = check_rows(s, n, slots, first_tokens, start_positions, std::max(max_tokens - 1, 0))) return rc;
+    if (int rc = check_args(s, n, slots, nullptr, first_tokens, start_positions, std::max(max_tokens - 1, 0))) return rc;
     if (sample) {
         if (!top_k || !top_p || !presence_penalty || !rng_seeds) return kr_fail(KR_ERR_VALUE, "null sampler parameter array");
         for (int i = 0; i < n; i++) if (!(temperature[i] >= 0.0f)) return kr_fail(KR_ERR_VALUE, "row %d: temperature must be >= 0", i);
@@ -345,15 +341,7 @@ extern "C" int kr_decode_slot_load(kr_decode_store* s, int slot, int seq_len) { 
 
 extern "C" int kr_decode_step_multi(kr_decode_store* s, int n, const int32_t* slots, const int32_t* tokens, const int32_t* positions,
                                     int32_t* next_out, float* logits_out, void* stream) {
-    if (int rc = multi_ready(s)) return rc;
-    if (int rc = need_slots(s)) return rc;
-    if (int rc = multi_refuse(s)) return rc;
-    if (int rc = check_rows(s, n, slots, tokens, positions, 0)) return rc;
-    if (!next_out) return kr_fail(KR_ERR_VALUE, "null next_out");
-    KR_HIP(hipSetDevice(s->eng->device));
-    hipStream_t st = kr_pick_stream(s->eng, stream);
-    if (int rc = order_after_store(s, st)) return rc;
-    return step_impl(s, n, slots, tokens, positions, next_out, logits_out, st);
+    return step_entry(s, n, slots, nullptr, tokens, positions, next_out, logits_out, false, stream);
 }
 
 extern "C" int kr_decode_generate_multi(kr_decode_store* s, int n, const int32_t* slots, const int32_t* first_tokens, const int32_t* start_positions,
@@ -364,9 +352,7 @@ extern "C" int kr_decode_generate_multi(kr_decode_store* s, int n, const int32_t
 // ---- per-row sampling (docs/design/14-multi-sampling.md)
 extern "C" int kr_decode_slot_sampler(kr_decode_store* s, int slot, int first_token, float temperature, int top_k, float top_p, float presence_penalty,
                                       uint64_t rng_seed) {
-    if (int rc = multi_ready(s)) return rc;
-    if (int rc = need_slots(s)) return rc;
-    if (int rc = multi_refuse(s)) return rc;
+    if (int rc = multi_begin(s)) return rc;
     if (slot < 0 || slot >= s->multi->n_slots) return kr_fail(KR_ERR_VALUE, "slot %d out of range [0, %d)", slot, s->multi->n_slots);
     if (!(temperature >= 0.0f)) return kr_fail(KR_ERR_VALUE, "temperature must be >= 0");
     KR_HIP(hipSetDevice(s->eng->device));
@@ -375,29 +361,14 @@ extern "C" int kr_decode_slot_sampler(kr_decode_store* s, int slot, int first_to
 
 extern "C" int kr_decode_step_multi_sample(kr_decode_store* s, int n, const int32_t* slots, const int32_t* tokens, const int32_t* positions,
                                            int32_t* next_out, float* logits_out, void* stream) {
-    if (int rc = multi_ready(s)) return rc;
-    if (int rc = need_slots(s)) return rc;
-    if (int rc = multi_refuse(s)) return rc;
-    if (int rc = check_rows(s, n, slots, tokens, positions, 0)) return rc;
-    if (!next_out) return kr_fail(KR_ERR_VALUE, "null next_out");
-    KR_HIP(hipSetDevice(s->eng->device));
-    hipStream_t st = kr_pick_stream(s->eng, stream);
-    if (int rc = order_after_store(s, st)) return rc;
-    return step_impl(s, n, slots, tokens, positions, next_out, logits_out, st, true);
+    return step_entry(s, n, slots, nullptr, tokens, positions, next_out, logits_out, true, stream);
 }
 
 // ---- multi-token extend of slots (docs/design/17-multi-extend.md)
 extern "C" int kr_decode_extend_multi(kr_decode_store* s, int n, const int32_t* slots, const int32_t* counts, const int32_t* tokens, const int32_t* positions,
                                       int32_t* next_out, float* logits_out, int sample, void* stream) {
-    if (int rc = multi_ready(s)) return rc;
-    if (int rc = need_slots(s)) return rc;
-    if (int rc = multi_refuse(s)) return rc;
-    if (int rc = check_runs(s, n, slots, counts, tokens, positions)) return rc;
-    if (!next_out) return kr_fail(KR_ERR_VALUE, "null next_out");
-    KR_HIP(hipSetDevice(s->eng->device));
-    hipStream_t st = kr_pick_stream(s->eng, stream);
-    if (int rc = order_after_store(s, st)) return rc;
-    return step_impl(s, n, slots, tokens, positions, next_out, logits_out, st, sample != 0, counts);
+    // null counts are refused with the other null arguments (to the pass they would mean one token per row)
+    return step_entry(s, n, counts ? slots : nullptr, counts, tokens, positions, next_out, logits_out, sample != 0, stream);
 }
 
 extern "C" int kr_decode_generate_multi_sample(kr_decode_store* s, int n, const int32_t* slots, const int32_t* first_tokens, const int32_t* start_positions,
@@ -418,13 +389,7 @@ extern "C" int kr_sample_rows(const float* logits, int n, int vocab, const float
     int dev_count = 0;
     if (hipGetDeviceCount(&dev_count) != hipSuccess || dev_count == 0) return kr_fail(KR_ERR_HIP, "no HIP device");
     std::vector<KrMsRow> rows((size_t)n);
-    for (int b = 0; b < n; b++) {
-        KrMsRow& r = rows[(size_t)b];
-        r = KrMsRow{KR_MS_GREEDY, b, 0, top_k[b], temperature[b], 0.0f, top_p[b], presence_penalty[b]};
-        r.k = (top_k[b] > 0 && top_k[b] < vocab) ? top_k[b] : vocab;
-        if (temperature[b] == 0.0f) r.mode = presence_penalty[b] != 0.0f ? KR_MS_PENALTY : KR_MS_GREEDY;
-        else { r.mode = (r.k <= KR_MS_SEL_CAP && !force_loop) ? KR_MS_SAMPLE : KR_MS_LOOP; r.inv_temp = 1.0f / temperature[b]; }
-    }
+    for (int b = 0; b < n; b++) rows[(size_t)b] = mode_row(b, temperature[b], top_k[b], top_p[b], presence_penalty[b], vocab, force_loop != 0);
     const size_t V = (size_t)vocab, words = (V + 31) / 32;
     kr_multi_state M;
     DevBuf lg, sn, rg, ids;

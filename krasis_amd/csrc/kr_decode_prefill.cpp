@@ -42,7 +42,7 @@ struct Chunk {      // one chunk of the prompt in flight: its arena, stream and 
     KrPfSync sy;      // this (chunk, layer)'s hand-overs with the previous / next chunk (set by the scheduler before every run_layer)
     bool verify = false;      // kr_decode_verify's pass: linear-attention layers write their recurrence inputs into the store's verify buffers (kr_spec.h)
     const int32_t* m_slots = nullptr; const int32_t* m_pos = nullptr; int m_sc_ld = 0; int m_fd_chunk = 0, m_fd_chunks = 0;   // the multi-sequence step: row b = slot m_slots[b] at m_pos[b] (device)
-    const int32_t* m_runs = nullptr; int m_nruns = 0;      // kr_decode_extend_multi: m_nruns x [slot, off, cnt] (device), the runs of token rows per slot (kr_multi.h); null: one token per slot
+    const int32_t* m_runs = nullptr; int m_nruns = 0;      // ... and m_nruns x [slot, off, cnt] (device), the runs of token rows per slot (kr_multi.h); set whenever m_slots is
 };
 size_t al(size_t n) { return (n + 255) & ~(size_t)255; }
 }  // namespace
@@ -108,12 +108,12 @@ static int run_layer(kr_decode_store* s, Chunk& cx, size_t li) {
         if (cx.m_slots) {      // multi-sequence step: every row advances its own slot's conv / recurrent state (kr_multi.hip)
             kr_multi_state& M = *s->multi;
             KrMultiLaArgs m{};
-            m.slots = cx.m_slots; m.qkvz = qkvz; m.ld_qkvz = nq; m.ba = B.pb; m.ld_ba = nb;
+            m.qkvz = qkvz; m.ld_qkvz = nq; m.ba = B.pb; m.ld_ba = nb;
             m.conv_w = (const float*)L.conv_w.p; m.a_log = (const float*)L.a_log.p; m.dt_bias = (const float*)L.dt_bias.p; m.norm_w = (const float*)L.la_norm_w.p;
             m.conv_state = (float*)M.a[li].p; m.conv_stride = M.a_stride[li] / 4; m.recur = (float*)M.b[li].p; m.recur_stride = M.b_stride[li] / 4;
             m.conv_out = B.cv; m.out = B.attn; m.ld_out = oc; m.nk = L.nk; m.nv = L.nv; m.dk = L.dk; m.dv = L.dv; m.hr = L.nv / L.nk; m.scale = L.la_scale; m.eps = s->eps;
             if (oc != L.nv * L.dv) return kr_fail(KR_ERR_VALUE, "out_proj cols %d != nv*dv", oc);
-            if (cx.m_runs ? kr_launch_multi_la_run(m, cx.m_runs, cx.m_nruns, Cc, st) : kr_launch_multi_la(m, Cc, st)) return kr_fail(KR_ERR_VALUE, "unsupported linear-attention geometry for the multi-sequence step");
+            if (kr_launch_multi_la(m, cx.m_runs, cx.m_nruns, Cc, st)) return kr_fail(KR_ERR_VALUE, "unsupported linear-attention geometry for the multi-sequence step");
         } else {
             KrPfmLaArgs a{};
             a.qkvz = qkvz; a.ld_qkvz = nq; a.ba = B.pb; a.ld_ba = nb; a.conv_state = (float*)L.conv_state.p; a.conv_w = (const float*)L.conv_w.p;
@@ -191,7 +191,7 @@ static int run_layer(kr_decode_store* s, Chunk& cx, size_t li) {
             if (int rc = pf_gemm(s, L.mqb_wid, Y(B), Cc, B.pa, nq, st)) return rc;
         }
         if (cx.m_slots) {      // multi-sequence step: each row appends to and attends over its own slot at its own position (kr_multi.hip); row positions
-                               // were bounded by the shortest MLA rope table before the pass (check_rows, kr_decode_multi.cpp)
+                               // were bounded by the shortest MLA rope table before the pass (check_args, kr_decode_multi.cpp)
             kr_multi_state& M = *s->multi;
             KrMultiMlaArgs m{};
             m.slots = cx.m_slots; m.positions = cx.m_pos; m.kv_out = B.pb; m.ld_kv = nkv; m.q_full = B.pa; m.ld_q = nq;
@@ -682,13 +682,13 @@ extern "C" int kr_decode_commit(kr_decode_store* s, int n_keep) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// the multi-sequence step (kr_decode_multi.cpp, docs/design/13-multi-sequence.md): one chunk of n rows, row b = the next token of slot slots[b].
-// Every row-wise section of run_layer runs unchanged; the linear-attention, GQA and MLA sections take the per-slot kernels (kr_multi.hip).  All-row
-// logits as in the verify pass.  Engine buffer set KR_PF_MAX_DEPTH - 1; the caller has ordered this pass after everything the store queued.
-// kr_multi_pass_runs (kr_decode_extend_multi, docs/design/17-multi-extend.md): n token rows in n_final runs of consecutive tokens per slot, d_runs =
-// n_final x [slot, off, cnt] after kr_multi.h; the last token of run i is row i, so the final norm, lm_head GEMM and M.logits cover the first n_final rows only.
+// the multi-sequence pass (kr_decode_multi.cpp, docs/design/13-multi-sequence.md, 17-multi-extend.md): one chunk of n token rows in n_final runs of
+// consecutive tokens per slot, row b = a token of slot slots[b] at positions[b]; d_runs = n_final x [slot, off, cnt] after kr_multi.h (a step: runs of one).
+// Every row-wise section of run_layer runs unchanged; the linear-attention, GQA and MLA sections take the per-slot kernels (kr_multi.hip).  The last
+// token of run i is row i, so the final norm, lm_head GEMM and M.logits cover the first n_final rows only.  Engine buffer set KR_PF_MAX_DEPTH - 1; the
+// caller has ordered this pass after everything the store queued.
 // ------------------------------------------------------------------------------------------------
-static int multi_pass(kr_decode_store* s, int n, int n_final, const int32_t* d_rows, const int32_t* d_runs, int max_pos, hipStream_t st) {
+int kr_multi_pass(kr_decode_store* s, int n, int n_final, const int32_t* d_rows, const int32_t* d_runs, int max_pos, hipStream_t st) {
     kr_multi_state& M = *s->multi;
     PfLayout Lo;
     if (int rc = pf_layout(s, (size_t)n, true, true, st, Lo)) return rc;
@@ -724,13 +724,9 @@ static int multi_pass(kr_decode_store* s, int n, int n_final, const int32_t* d_r
     cx.B = pf_carve(Lo, (char*)M.scratch.p); cx.scores = nullptr; cx.tok = d_rows + n; cx.Cc = n; cx.pos0 = 0; cx.set = KR_PF_MAX_DEPTH - 1;
     cx.first = true; cx.add_is_emb = true; cx.st = st;
     cx.m_slots = d_rows; cx.m_pos = d_rows + 2 * n; cx.m_sc_ld = sc_ld; cx.m_fd_chunk = fd_chunk; cx.m_fd_chunks = fd_chunks;
-    cx.m_runs = d_runs; cx.m_nruns = d_runs ? n_final : 0;
+    cx.m_runs = d_runs; cx.m_nruns = n_final;
     for (size_t l = 0; l < s->layers.size(); l++)
         if (int rc = run_layer(s, cx, l)) return rc;
     cx.Cc = n_final;
     return final_rows(s, cx, (float*)M.logits.p);
-}
-int kr_multi_pass(kr_decode_store* s, int n, const int32_t* d_rows, int max_pos, hipStream_t st) { return multi_pass(s, n, n, d_rows, nullptr, max_pos, st); }
-int kr_multi_pass_runs(kr_decode_store* s, int n_rows, int n_runs, const int32_t* d_rows, const int32_t* d_runs, int max_pos, hipStream_t st) {
-    return multi_pass(s, n_rows, n_runs, d_rows, d_runs, max_pos, st);
 }

@@ -1,28 +1,25 @@
 // kr_multi.h -- kernels of the exact multi-sequence decode step (kr_multi.hip; host side in kr_decode_multi.cpp, docs/design/13-multi-sequence.md).
-// Row b of a step belongs to sequence slot slots[b] at position positions[b]; every per-slot buffer is [n_slots][per-slot elements].
+// Row b of a pass belongs to sequence slot slots[b] at position positions[b]; every per-slot buffer is [n_slots][per-slot elements].
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-// linear attention, one token per row (the decode step's kr_la_step_kernel arithmetic)
+// linear attention over runs of consecutive tokens per slot (the decode step's kr_la_step_kernel arithmetic per token); a step is runs of one token
 struct KrMultiLaArgs {
-    const int* slots;               // [B] device
-    const float* qkvz; int ld_qkvz; // in-projection rows [B][ld_qkvz]
-    const float* ba; int ld_ba;     // [B][ld_ba]
+    const float* qkvz; int ld_qkvz; // in-projection rows [rows][ld_qkvz]
+    const float* ba; int ld_ba;     // [rows][ld_ba]
     const float *conv_w, *a_log, *dt_bias, *norm_w;
     float* conv_state; size_t conv_stride;     // slot s: conv_state + s * conv_stride, [conv_dim][4]
     float* recur; size_t recur_stride;         // slot s: recur + s * recur_stride, [nv][dk][dv]
-    float* conv_out;                           // scratch [B][conv_dim]: conv + SiLU outputs
-    float* out; int ld_out;                    // [B][ld_out]: gated RMSNorm output, the out-projection's input
+    float* conv_out;                           // scratch [rows][conv_dim]: conv + SiLU outputs
+    float* out; int ld_out;                    // [rows][ld_out]: gated RMSNorm output, the out-projection's input
     int nk, nv, dk, dv, hr; float scale, eps;
 };
-// 0: launched; 1: geometry not covered (kd 4 is the caller's check; dk 64 / 128, dv <= 256, dv % 8 == 0)
-int kr_launch_multi_la(const KrMultiLaArgs& a, int B, hipStream_t st);
-// the same over runs of consecutive tokens per slot (kr_decode_extend_multi, docs/design/17-multi-extend.md).  runs (device) = n_runs x
-// [slot, off, cnt]: run i's tokens are, in order, rows off .. off + cnt - 2 and then row i of qkvz / ba / conv_out / out; a.slots is not read.  The
-// slot's conv and recurrent state are loaded once, carried in registers through the run and stored once.  Slots distinct across runs; max_cnt = a bound
-// on every cnt, at most 1024 (the gate rows the recurrence kernel keeps in LDS).  Returns as above (1 also for max_cnt out of range).
-int kr_launch_multi_la_run(const KrMultiLaArgs& a, const int* runs, int n_runs, int max_cnt, hipStream_t st);
+// runs (device) = n_runs x [slot, off, cnt]: run i's tokens are, in order, rows off .. off + cnt - 2 and then row i of qkvz / ba / conv_out / out (cnt 1:
+// row i alone).  The slot's conv and recurrent state are loaded once, carried in registers through the run and stored once.  Slots distinct across runs;
+// max_cnt = a bound on every cnt, at most 1024 (the gate rows the recurrence kernel keeps in LDS).
+// 0: launched; 1: max_cnt out of range or geometry not covered (kd 4 is the caller's check; dk 64 / 128, dv <= 256, dv % 8 == 0)
+int kr_launch_multi_la(const KrMultiLaArgs& a, const int* runs, int n_runs, int max_cnt, hipStream_t st);
 
 // GQA, one token per row: QK-norm + RoPE at the row's position, K / V appended to the row's slot, attention over the slot's rows [0, pos]
 struct KrMultiGqaArgs {

@@ -25,120 +25,16 @@ __device__ __forceinline__ float kr_m_sumsq8(const float* x, int n, int l) {
 }
 
 // ---- linear attention ----------------------------------------------------------------------------------------------------------------------------
-// conv1d (kernel 4) + SiLU of every channel of row b, and the shift of the slot's carried inputs.  grid (conv_dim / 256, B), 256 threads.
-// Channel layout (decode.rs:3815): q [0, key_dim), k [key_dim, 2 key_dim), v [2 key_dim, conv_dim); the in-projection row holds per key head
-// [q (dk) | k (dk) | v (hr dv) | z (hr dv)].
-__global__ void __launch_bounds__(256) kr_multi_la_conv_kernel(const KrMultiLaArgs a) {
-    const int b = blockIdx.y, ch = blockIdx.x * 256 + threadIdx.x;
-    const int dk = a.dk, dv = a.dv, hr = a.hr, key_dim = a.nk * dk, conv_dim = 2 * key_dim + a.nv * dv, group_dim = 2 * dk + 2 * dv * hr;
-    if (ch >= conv_dim) return;
-    int kh, off;
-    if (ch < key_dim) { kh = ch / dk; off = ch % dk; }
-    else if (ch < 2 * key_dim) { kh = (ch - key_dim) / dk; off = dk + (ch - key_dim) % dk; }
-    else { const int vh = (ch - 2 * key_dim) / dv, i = (ch - 2 * key_dim) % dv; kh = vh / hr; off = 2 * dk + (vh % hr) * dv + i; }
-    const float x = a.qkvz[(size_t)b * a.ld_qkvz + (size_t)kh * group_dim + off];
-    float4* cs = reinterpret_cast<float4*>(a.conv_state + (size_t)a.slots[b] * a.conv_stride) + ch;
-    const float4 s = *cs, w = reinterpret_cast<const float4*>(a.conv_w)[ch];
-    *cs = float4{s.y, s.z, s.w, x};
-    const float co = s.y * w.x + s.z * w.y + s.w * w.z + x * w.w;
-    a.conv_out[(size_t)b * conv_dim + ch] = co * kr_sigmoid_poly5(co);      // fast_silu_avx2
-}
-
-// gates, L2 norms, the gated delta rule on the slot's state and the head's gated RMSNorm.  grid (nv, B), dv threads: thread j owns column j of
-// value head h of row b's slot, the whole column (DK values) in registers.  The operations and order of kr_la_step_kernel (kr_decode_ops.hip).
-template <int DK>
-__global__ void __launch_bounds__(256) kr_multi_la_recur_kernel(const KrMultiLaArgs a) {
-    __shared__ float qc[DK], kc[DK], rr[256], nrm[2], gb[2], rms_s;
-    const int h = blockIdx.x, b = blockIdx.y, j = threadIdx.x, dv = a.dv, hr = a.hr, kh = h / hr, r = h - kh * hr;
-    const int key_dim = a.nk * DK, conv_dim = 2 * key_dim + a.nv * dv, group_dim = 2 * DK + 2 * dv * hr;
-    // the head's state slice through one buffer descriptor (workgroup-uniform): voffset = the thread's column, row i by scalar offset -- no
-    // per-row address registers next to the DK-register column
-    const __amdgpu_buffer_rsrc_t srd = __builtin_amdgcn_make_buffer_rsrc(a.recur + (size_t)a.slots[b] * a.recur_stride + (size_t)h * DK * dv, 0, DK * dv * 4, 0x00020000);
-    float c[DK];
-#pragma unroll
-    for (int i = 0; i < DK; i++) c[i] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(srd, j * 4, i * dv * 4, 0));
-    const float* co = a.conv_out + (size_t)b * conv_dim;
-    for (int i = j; i < DK; i += dv) { qc[i] = co[kh * DK + i]; kc[i] = co[key_dim + kh * DK + i]; }
-    const float vj = co[2 * key_dim + h * dv + j];
-    const float* src = a.qkvz + (size_t)b * a.ld_qkvz + (size_t)kh * group_dim;
-    const float zz = src[2 * DK + hr * dv + r * dv + j], wn = a.norm_w[(size_t)h * dv + j];
-    if (j == 0) {      // gates (decode.rs:3891-3901)
-        const float* ba = a.ba + (size_t)b * a.ld_ba;
-        const float b_raw = ba[kh * 2 * hr + r], a_p = ba[kh * 2 * hr + hr + r];
-        gb[1] = 1.0f / (1.0f + kr_expf(-b_raw));
-        const float ap_dt = a_p + a.dt_bias[h];
-        const float softplus = ap_dt > 20.0f ? ap_dt : kr_logf(1.0f + kr_expf(ap_dt));
-        const float g = -(kr_expf(a.a_log[h])) * softplus;
-        gb[0] = kr_expf(g);
-    }
-    __syncthreads();
-    if (j < 16) {      // L2 norms: lanes 0-7 -> q, lanes 8-15 -> k (decode.rs:3909-3945)
-        const int which = j >> 3, l = j & 7;
-        const float ss = kr_m_sumsq8(which ? kc : qc, DK, l);
-        if (l == 0) nrm[which] = ss > 0.0f ? 1.0f / sqrtf(ss) : 0.0f;
-    }
-    __syncthreads();
-    {
-        const float inv_q = nrm[0] * a.scale, inv_k = nrm[1] * 1.0f;
-        for (int i = j; i < DK; i += dv) { qc[i] = qc[i] * inv_q; kc[i] = kc[i] * inv_k; }
-    }
-    __syncthreads();
-    // kv = sum_i fma(S[i] e^g, k[i]); delta = (v - kv) beta; S' = fma(k, delta, S e^g); o = sum_i fma(S', q)
-    const float g_exp = gb[0], beta_h = gb[1];
-    // 16 elements of k (and q) per block out of LDS; the scheduling barriers keep the compiler from hoisting every read next to the column
-    float kv = 0.0f;
-#pragma unroll
-    for (int i0 = 0; i0 < DK; i0 += 16) {
-        float kk[16];
-#pragma unroll
-        for (int u = 0; u < 16; u++) kk[u] = kc[i0 + u];
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int u = 0; u < 16; u++) { c[i0 + u] = c[i0 + u] * g_exp; kv = __builtin_fmaf(c[i0 + u], kk[u], kv); }
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    const float delta = (vj - kv) * beta_h;
-    float ob = 0.0f;
-#pragma unroll
-    for (int i0 = 0; i0 < DK; i0 += 16) {
-        float kk[16], qq[16];
-#pragma unroll
-        for (int u = 0; u < 16; u++) { kk[u] = kc[i0 + u]; qq[u] = qc[i0 + u]; }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int u = 0; u < 16; u++) {
-            const float sn = __builtin_fmaf(kk[u], delta, c[i0 + u]);
-            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(sn), srd, j * 4, (i0 + u) * dv * 4, 0);
-            ob = __builtin_fmaf(sn, qq[u], ob);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    rr[j] = ob;
-    __syncthreads();
-    if (j < 8) { const float ss = kr_m_sumsq8(rr, dv, j); if (j == 0) rms_s = 1.0f / sqrtf(ss / (float)dv + a.eps); }
-    __syncthreads();
-    const float normed = (ob * rms_s) * wn;
-    a.out[(size_t)b * a.ld_out + (size_t)h * dv + j] = (zz * kr_sigmoid_poly5(zz)) * normed;
-}
-
-int kr_launch_multi_la(const KrMultiLaArgs& a, int B, hipStream_t st) {
-    if ((a.dk != 64 && a.dk != 128) || a.dv < 8 || a.dv > 256 || a.dv % 8 || a.nv != a.nk * a.hr) return 1;
-    const int conv_dim = 2 * a.nk * a.dk + a.nv * a.dv;
-    hipLaunchKernelGGL(kr_multi_la_conv_kernel, dim3((conv_dim + 255) / 256, B), dim3(256), 0, st, a);
-    if (a.dk == 128) hipLaunchKernelGGL(kr_multi_la_recur_kernel<128>, dim3(a.nv, B), dim3(a.dv), 0, st, a);
-    else hipLaunchKernelGGL(kr_multi_la_recur_kernel<64>, dim3(a.nv, B), dim3(a.dv), 0, st, a);
-    return 0;
-}
-
-// ---- linear attention over runs of tokens (kr_decode_extend_multi, docs/design/17-multi-extend.md) ------------------------------------------------
-// Run i of an extend pass is `cnt` consecutive tokens of one slot: runs[3 i] = the slot, runs[3 i + 1] = off, runs[3 i + 2] = cnt.  Its tokens sit, in
-// order, in pass rows off .. off + cnt - 2 and, the last one, in row i (the pass keeps every run's last token in the first rows for the lm_head).  The two
-// kernels below carry the slot's state through the run in registers: the operations of kr_multi_la_conv_kernel / kr_multi_la_recur_kernel per token, in
-// the same order, the state loaded once before the first token and stored once after the last.
+// Run i of a pass is `cnt` consecutive tokens of one slot: runs[3 i] = the slot, runs[3 i + 1] = off, runs[3 i + 2] = cnt.  Its tokens sit, in order, in
+// pass rows off .. off + cnt - 2 and, the last one, in row i (the pass keeps every run's last token in the first rows for the lm_head); a step is runs of
+// one token, row i alone.  The two kernels below carry the slot's state through the run in registers: per token the operations and order of
+// kr_la_step_kernel (kr_decode_ops.hip), the state loaded once before the first token and stored once after the last.
 __device__ __forceinline__ int kr_m_run_row(int i, int off, int cnt, int t) { return t == cnt - 1 ? i : off + t; }
 
-// grid (conv_dim / 256, runs), 256 threads: thread = channel, the slot's four carried inputs in registers for the whole run
-__global__ void __launch_bounds__(256) kr_multi_la_conv_run_kernel(const KrMultiLaArgs a, const int* __restrict__ runs) {
+// conv1d (kernel 4) + SiLU of every channel of the run's rows, and the shift of the slot's carried inputs.  grid (conv_dim / 256, runs), 256 threads:
+// thread = channel, the slot's four carried inputs in registers for the whole run.  Channel layout (decode.rs:3815): q [0, key_dim), k [key_dim, 2 key_dim),
+// v [2 key_dim, conv_dim); the in-projection row holds per key head [q (dk) | k (dk) | v (hr dv) | z (hr dv)].
+__global__ void __launch_bounds__(256) kr_multi_la_conv_kernel(const KrMultiLaArgs a, const int* __restrict__ runs) {
     const int i = blockIdx.y, ch = blockIdx.x * 256 + threadIdx.x;
     const int dk = a.dk, dv = a.dv, hr = a.hr, key_dim = a.nk * dk, conv_dim = 2 * key_dim + a.nv * dv, group_dim = 2 * dk + 2 * dv * hr;
     if (ch >= conv_dim) return;
@@ -161,15 +57,16 @@ __global__ void __launch_bounds__(256) kr_multi_la_conv_run_kernel(const KrMulti
     *cs = s;
 }
 
-// grid (nv, runs), dv threads: thread j keeps column j of value head h of the run's slot (DK registers) from the first token to the last.  Per token the
-// operations and order of kr_multi_la_recur_kernel.  The gates of all the run's tokens (e^g, beta: exp / log chains that depend on the ba row alone) are
+// gates, L2 norms, the gated delta rule on the slot's state and the head's gated RMSNorm.  grid (nv, runs), dv threads: thread j keeps column j of value
+// head h of the run's slot (DK registers) from the first token to the last, read and written through one buffer descriptor (workgroup-uniform: voffset =
+// the thread's column, row i by scalar offset -- no per-row address registers next to the column).  The gates of all the run's tokens (e^g, beta: exp / log chains that depend on the ba row alone) are
 // computed first, a token per thread, into LDS -- before the column is loaded, so their temporaries never sit next to it.  Barriers of the token loop (five
 // per token): a token's reads of qc / kc / nrm all precede its fourth barrier (after rr is written) and its reads of rr precede the fifth; every thread passes
 // both before any thread starts the next token, whose first LDS writes are qc / kc.  rms_s is read after the fifth barrier and next written after the next
 // token's fourth, by which time every thread has passed that token's first.
 #define KR_M_RUN_MAX 1024      // tokens per run (LDS gate rows); = KR_EXTEND_MAX_TOKENS
 template <int DK>
-__global__ void __launch_bounds__(256) kr_multi_la_recur_run_kernel(const KrMultiLaArgs a, const int* __restrict__ runs) {
+__global__ void __launch_bounds__(256) kr_multi_la_recur_kernel(const KrMultiLaArgs a, const int* __restrict__ runs) {
     __shared__ float qc[DK], kc[DK], rr[256], nrm[2], rms_s, ge[KR_M_RUN_MAX], be[KR_M_RUN_MAX];
     const int h = blockIdx.x, ri = blockIdx.y, j = threadIdx.x, dv = a.dv, hr = a.hr, kh = h / hr, r = h - kh * hr;
     const int key_dim = a.nk * DK, conv_dim = 2 * key_dim + a.nv * dv, group_dim = 2 * DK + 2 * dv * hr;
@@ -250,13 +147,13 @@ __global__ void __launch_bounds__(256) kr_multi_la_recur_run_kernel(const KrMult
     for (int i = 0; i < DK; i++) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(c[i]), srd, j * 4, i * dv * 4, 0);
 }
 
-int kr_launch_multi_la_run(const KrMultiLaArgs& a, const int* runs, int n_runs, int max_cnt, hipStream_t st) {
+int kr_launch_multi_la(const KrMultiLaArgs& a, const int* runs, int n_runs, int max_cnt, hipStream_t st) {
     if (max_cnt < 1 || max_cnt > KR_M_RUN_MAX) return 1;
     if ((a.dk != 64 && a.dk != 128) || a.dv < 8 || a.dv > 256 || a.dv % 8 || a.nv != a.nk * a.hr) return 1;
     const int conv_dim = 2 * a.nk * a.dk + a.nv * a.dv;
-    hipLaunchKernelGGL(kr_multi_la_conv_run_kernel, dim3((conv_dim + 255) / 256, n_runs), dim3(256), 0, st, a, runs);
-    if (a.dk == 128) hipLaunchKernelGGL(kr_multi_la_recur_run_kernel<128>, dim3(a.nv, n_runs), dim3(a.dv), 0, st, a, runs);
-    else hipLaunchKernelGGL(kr_multi_la_recur_run_kernel<64>, dim3(a.nv, n_runs), dim3(a.dv), 0, st, a, runs);
+    hipLaunchKernelGGL(kr_multi_la_conv_kernel, dim3((conv_dim + 255) / 256, n_runs), dim3(256), 0, st, a, runs);
+    if (a.dk == 128) hipLaunchKernelGGL(kr_multi_la_recur_kernel<128>, dim3(a.nv, n_runs), dim3(a.dv), 0, st, a, runs);
+    else hipLaunchKernelGGL(kr_multi_la_recur_kernel<64>, dim3(a.nv, n_runs), dim3(a.dv), 0, st, a, runs);
     return 0;
 }
 

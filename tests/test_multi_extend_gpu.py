@@ -9,13 +9,13 @@ import pytest
 from krasis_amd._lib import KR_EXTEND_MAX_TOKENS
 from tests.test_decode_gpu import build
 from tests.test_speculative_gpu import CFGS, _same, _snap
+from tests.test_multi_seq_gpu import DV64, LA4
 from tests import test_multi_mla_gpu as mla
 
 pytestmark = pytest.mark.gpu
 F = np.float32
 U = np.uint32
 
-LA4 = dict(kinds=["la", "la", "la", "la"], la_heads=(4, 16))      # linear attention alone, four value heads per key head
 # (tokens already in the slot, tokens of the run): an empty slot with one token; a run that crosses the conv kernel's four carried inputs twice; a
 # prompt + run; a plain decode row; a short run on a short prompt
 SEQS = [(0, 1), (0, 9), (7, 5), (23, 1), (2, 3)]
@@ -56,7 +56,7 @@ def _slot_state(st, d, slot, pos, snap=_snap):
     return snap(st, d, pos)
 
 
-def _check_rows(st, d, refs, slots, ids, lg, same=_same, snap=_snap):
+def _assert_rows(st, d, refs, slots, ids, lg, same=_same, snap=_snap):
     for i, (ref, s) in enumerate(zip(refs, slots)):
         assert np.array_equal(lg[i].view(U), ref["lg"]), ("logits", i)
         assert ids[i] == ref["tok"], ("id", i)
@@ -70,14 +70,14 @@ def _setup(st, d, rng, seqs, slots):
     return prompts, runs, refs
 
 
-@pytest.mark.parametrize("cfg", CFGS + [LA4])
+@pytest.mark.parametrize("cfg", CFGS + [LA4, DV64])
 def test_extend_equals_decode_step_alone(cfg):
     st, eng, orc, keep, d = build(kv_max=64, **cfg)
     st.create_slots(8, 60)
     prompts, runs, refs = _setup(st, d, np.random.default_rng(5), SEQS, SLOTS)
     assert sum(len(r) for r in runs) == 19
     ids, lg = st.extend_multi(SLOTS, runs, [len(p) for p in prompts], logits=True)
-    _check_rows(st, d, refs, SLOTS, ids, lg)
+    _assert_rows(st, d, refs, SLOTS, ids, lg)
     ids2, lg2 = st.step_multi(SLOTS, ids, [r["pos"] for r in refs], logits=True)      # the slots continue as the sequences do
     for i, ref in enumerate(refs):
         assert np.array_equal(lg2[i].view(U), ref["next"][0]) and ids2[i] == ref["next"][1], i
@@ -93,7 +93,7 @@ def test_router_forms_and_row_order():
     order = [5, 2, 0, 4, 1, 3]
     pick = lambda xs: [xs[i] for i in order]
     ids, lg = st.extend_multi(pick(slots), pick(runs), pick([len(p) for p in prompts]), logits=True)
-    _check_rows(st, d, pick(refs), pick(slots), ids, lg)
+    _assert_rows(st, d, pick(refs), pick(slots), ids, lg)
 
 
 @pytest.mark.parametrize("cfg", [dict(), LA4])
@@ -111,7 +111,7 @@ def test_cut_invariance(cfg):
     for k, t in enumerate(stream):
         c = st.step_multi([2], [t], [p0 + k], logits=True)
     for slot, (ids, lg) in enumerate((a, b, c)):
-        _check_rows(st, d, [ref], [slot], ids, lg)
+        _assert_rows(st, d, [ref], [slot], ids, lg)
 
 
 def test_positions_across_1024_e4m3_head_dim_256():
@@ -125,7 +125,7 @@ def test_positions_across_1024_e4m3_head_dim_256():
     pos = [len(p) for p in prompts]
     assert pos[0] + len(runs[0]) - 1 == 1027
     ids, lg = st.extend_multi([0, 1], runs, pos, logits=True)
-    _check_rows(st, d, refs, [0, 1], ids, lg)
+    _assert_rows(st, d, refs, [0, 1], ids, lg)
     st.set_option("multi_attn_fast", 1)      # slots of max_seq > 1024: every token carries the bits step_multi gives it under the option
     try:
         got = st.extend_multi([2, 3], runs, pos, logits=True)
@@ -154,7 +154,7 @@ def test_mla(cfg, fp8):
     runs = [_toks(rng, d, r) for _, r in seqs]
     refs = [_reference(st, d, p, r, [s], snap=mla._snap) for p, r, s in zip(prompts, runs, slots)]
     ids, lg = st.extend_multi(slots, runs, [len(p) for p in prompts], logits=True)
-    _check_rows(st, d, refs, slots, ids, lg, same=mla._same, snap=mla._snap)
+    _assert_rows(st, d, refs, slots, ids, lg, same=mla._same, snap=mla._snap)
 
 
 def test_sampled_row_draws_once_on_the_last_token():

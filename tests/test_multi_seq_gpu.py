@@ -17,10 +17,13 @@ def _prompt(rng, d, n):
 
 
 def _start(st, d, prompt):
-    """the store's own sequence = prompt (zero state, then the prompt pass)"""
+    """the store's own sequence = prompt (zero state, then the prompt pass; decode_step token by token where the prompt pass refuses the geometry, dv < dk)"""
     st.reset_decode_state(d["kv_max"])
-    if prompt:
+    if prompt and d["dv"] >= d["dk"]:
         st.prefill(prompt, 0)
+    else:
+        for i, t in enumerate(prompt):
+            st.decode_step(t, i)
 
 
 def _reference(st, d, prompt, first, n_steps):
@@ -42,7 +45,11 @@ def _fill_slots(st, d, prompts, slot_lists):
             st.save_slot(s, len(p))
 
 
-@pytest.mark.parametrize("cfg", CFGS)
+LA4 = dict(kinds=["la", "la", "la", "la"], la_heads=(4, 16))      # linear attention alone, four value heads per key head
+DV64 = dict(la_dkdv=(128, 64), la_heads=(2, 2), seed=5)          # dv < dk: the strided qc / kc fills loop twice, the RMS sum runs over 64 values
+
+
+@pytest.mark.parametrize("cfg", CFGS + [LA4, DV64])
 def test_step_multi_equals_decode_step_alone(cfg):
     st, eng, orc, keep, d = build(kv_max=64, **cfg)
     rng = np.random.default_rng(5)
