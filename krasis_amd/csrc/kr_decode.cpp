@@ -33,6 +33,9 @@ static void prof_mark(kr_decode_store* s, int kind, hipStream_t st) {
     (void)hipEventRecord(s->ev_pool[s->ev_used++], st);
 }
 #define PROF(kind, stmt) do { prof_mark(s, kind, st); stmt; prof_mark(s, -1, st); } while (0)
+// the same pair of marks around a launcher whose return value the caller consumes (a refusal selects the fall-back launches, or fails the step)
+static int prof_end(kr_decode_store* s, hipStream_t st, int rc) { prof_mark(s, -1, st); return rc; }
+#define PROF_RC(kind, call) (prof_mark(s, kind, st), prof_end(s, st, (call)))
 
 static int chk_store(kr_decode_store* s) { return s ? KR_OK : kr_fail(KR_ERR_VALUE, "null decode store"); }
 static int chk_wid(kr_decode_store* s, int id, const char* what) {
@@ -492,462 +495,468 @@ extern "C" int kr_decode_get_state(kr_decode_store* s, int layer, uint16_t* kv_k
 }
 
 // ------------------------------------------------------------------------------------------------
-// one decode step: the launch sequence of decode_step (decode.rs:2690-3520)
+// one decode step: the launch sequence of decode_step (decode.rs:2690-3520), as sections that enqueue_step calls in order (docs/design/05-decode-step.md)
 // ------------------------------------------------------------------------------------------------
+// What the sections share.  `src`: the value the next fused add+RMSNorm adds to the residual: embedding row, attention output, or the previous MoE epilogue.
+// `res_cur`: where the residual stream currently lives: a launch whose workgroups all read the residual writes the OTHER buffer.
+// `fast`: KR_DECODE_FAST (kr_decode_fast.hip), tolerance-mode kernels for the pieces whose geometry they cover; everything else stays exact.
+struct StepCtx {
+    kr_decode_store* s; kr_engine* e; hipStream_t st; int H;
+    float* hid; float* res; float* res_b; float* res_cur;
+    KrNormSrc src; bool first, fast, ep_dec;
+    bool in_img = false, did_in = false, la_conv_done = false;   // per layer: the input norm leaves an INT16 image; in_proj_fast ran; with the LA conv + gates as its epilogue
+    float* other() const { return res_cur == res ? res_b : res; }
+    // INT16 activation images: built once by the kernel that produces an activation, copied by every workgroup of the
+    // matvec launch that consumes it (instead of being re-quantised per workgroup).  INT4 consumers only.
+    bool img_ok() const { return H % 128 == 0; }
+};
 
-static int enqueue_step(kr_decode_store* s, hipStream_t st) {
-    kr_engine* e = s->eng;
-    const int H = s->hidden;
-    float* hid = (float*)s->hid.p; float* res = (float*)s->res.p;
-    const KrStep* step = (const KrStep*)s->step_dev.p;
-    // the value the next fused add+RMSNorm adds to the residual: embedding row, attention output, or the previous MoE epilogue
-    KrNormSrc src{}; src.mode = 1; src.emb = (const float*)s->embedding.p; src.step = step;
-    const KrNormSrc from_hidden{};  // mode 0
-    bool first = true;
-    float* res_cur = res;   // where the residual stream currently lives: a launch whose workgroups all read the residual writes the OTHER buffer
-    float* const res_b = (float*)s->res2.p;
-    auto other = [&](float* r) { return r == res ? res_b : res; };
-    // KR_DECODE_FAST (kr_decode_fast.hip): tolerance-mode kernels for the pieces whose geometry they cover; everything else stays exact
-    // expert-parallel decode: router, attention, norms and the shared expert are replicated; every rank runs the routed experts of ITS slice
-    // and the k expert rows are summed over the ranks (each row is non-zero on exactly one rank, so the sum is exact: logits equal single-engine decode
-    // bit for bit) before the combine in routing order.  Reference analogue: python/krasis/gpu_prefill.py:3700-3790 (local subset + partial-sum reduce).
-    // Under KR_DECODE_FAST the expert-parallel form is lighter: every rank's down launch leaves its PARTIAL combine (rsf * sum over its own slots; the layer's
-    // shared expert is evaluated by ONE rank, layer mod world, and added there) in the hidden buffer and ONE all-reduce of [hidden] f32 per MoE layer sums the
-    // partials -- 1 / k of the bytes of the exact form, and no combine left for the next norm.  The sum order over the ranks is RCCL's: tolerance mode.
-    const bool ep_dec = kr_ep_decode_active(e);
-    const bool fast = s->decode_fast && s->use_images && H % 128 == 0 && H <= 4096 && s->f_qk.p;
-    for (size_t li = 0; li < s->layers.size(); li++) {
-        DLayer& L = s->layers[li];
-        // INT16 activation images: built once by the kernel that produces an activation, copied by every workgroup of the
-        // matvec launch that consumes it (instead of being re-quantised per workgroup).  INT4 consumers only.
-        const bool img_ok = s->use_images && H % 128 == 0;
-        // a launch takes one weight width: the matrices that share an activation image must agree (INT4 or INT8)
-        auto img_w = [&](int wid, int like = -1) { return wid >= 0 && (like < 0 || s->weights[wid]->ms.bits == s->weights[like]->ms.bits); };
-        bool in_img = false;
-        if (img_ok) {
-            if (L.attn == ATTN_LA) in_img = img_w(L.qkvz_wid) && img_w(L.ba_wid, L.qkvz_wid);
-            else if (L.attn == ATTN_GQA) in_img = img_w(L.q_wid) && img_w(L.k_wid, L.q_wid) && img_w(L.v_wid, L.q_wid);
+// a launch takes one weight width: the matrices that share an activation image must agree (INT4 or INT8)
+static bool img_w(kr_decode_store* s, int wid, int like = -1) { return wid >= 0 && (like < 0 || s->weights[wid]->ms.bits == s->weights[like]->ms.bits); }
+static const float* route_bias(const Layer& EL) { return EL.has_bias ? (const float*)EL.bias.p : nullptr; }
+static const float* route_esc(const Layer& EL) { return EL.has_esc ? (const float*)EL.esc.p : nullptr; }
+
+static KrFdmArgs fdm_one(kr_decode_store* s, int mode, int wid, float* y) {
+    KrFdmArgs a{}; a.mode = mode; a.mm.n = 1; a.mm.m[0] = mv(s, wid); a.mm.y[0] = y; a.mm.tile_end[0] = (a.mm.m[0].N + 7) / 8;
+    return a;
+}
+// mode 1: the add + RMSNorm with weight `norm_id` folded into the projection launch; reads hid / res_cur, leaves the residual in the other buffer
+static void fdm_norm(const StepCtx& cx, int norm_id, KrFdmArgs& a) {
+    a.mode = 1; a.hid_in = cx.hid; a.res_in = cx.res_cur; a.res_out = cx.other(); a.norm_w = (const float*)cx.s->norms[norm_id]->p; a.eps = cx.s->eps; a.bias_one = cx.s->norm_bias_one;
+}
+static KrFrtArgs frt_args(const StepCtx& cx, const DLayer& L, const Layer& EL) {
+    kr_decode_store* s = cx.s;
+    KrFrtArgs ra{};
+    ra.gate_cm = EL.gate_cm.p; ra.gate_bf16 = EL.gate_bf16_exact; ra.bias = route_bias(EL); ra.logits = (float*)s->r_logits.p;
+    ra.E = cx.e->r_ne; ra.H = cx.H; ra.hid_in = cx.hid; ra.res_in = cx.res_cur; ra.norm_w = (const float*)s->norms[L.post_norm]->p; ra.hid_out = (float*)s->hid2.p;
+    ra.res_out = cx.other(); ra.eps = s->eps; ra.bias_one = s->norm_bias_one; ra.img_f32 = s->img_post.p; ra.img_bf16 = s->img_post_bf16.p;
+    return ra;
+}
+static void launch_select(StepCtx& cx, const Layer& EL) {
+    kr_decode_store* s = cx.s; hipStream_t st = cx.st;
+    PROF(PK_ROUTE_SELECT, kr_launch_route_select((const float*)s->r_logits.p, route_esc(EL), (int32_t*)s->r_ids.p, (float*)s->r_w.p, 1, cx.e->r_ne, s->topk,
+                                                 s->scoring, s->norm_topk, KR_ROUTE_RULE_DECODE, 0, st));
+}
+// a MoE layer's slots: k routed + the decode store's shared expert (slot k); the row pitch of the gate|up scratch is 2 * imax
+struct MoeShape { bool has_shared, has_gate; int I_shared, imax, n_slots; };
+static MoeShape moe_shape(kr_decode_store* s, const DLayer& L, const Layer& EL) {
+    MoeShape m{};
+    m.has_shared = L.sgu_wid >= 0; m.has_gate = m.has_shared && L.sg_wid >= 0;
+    m.I_shared = m.has_shared ? s->weights[L.sgu_wid]->rows / 2 : 0;
+    m.imax = m.I_shared > EL.inter ? m.I_shared : EL.inter;
+    m.n_slots = s->topk + (m.has_shared ? 1 : 0);
+    return m;
+}
+// the KrMoeArgs fields every MoE path of the step fills alike; experts, slots, scratch rows and activation are the caller's
+static void moe_args_common(const StepCtx& cx, const DLayer& L, const MoeShape& m, KrMoeArgs& a) {
+    kr_decode_store* s = cx.s;
+    a.shared_decode = 1; a.B = 1; a.H = cx.H;
+    if (m.has_shared) { a.sw13 = mv(s, L.sgu_wid); a.sw2 = mv(s, L.sd_wid); a.I_shared = m.I_shared; }
+    a.gu_ld = 2 * m.imax;
+    a.rsf = s->rsf; a.swiglu_limit = cx.e->cfg.swiglu_limit; a.alpha = cx.e->cfg.activation_alpha;
+    a.act_mode = cx.e->cfg.swiglu_limit > 0.0f ? KR_ACT_GPTOSS : KR_ACT_SILU_FUSED;
+}
+// the MoE epilogue (weighted sum in routing order, rsf, shared * sigmoid(gate)) folded into the next fused add+RMSNorm
+static KrNormSrc norm_src_moe(kr_decode_store* s, const MoeShape& m) {
+    KrNormSrc src{}; src.mode = 2; src.eo = (float*)s->moe_eo.p; src.ids = (const int32_t*)s->r_ids.p; src.wts = (const float*)s->r_w.p; src.topk = s->topk;
+    src.has_shared = m.has_shared ? 1 : 0; src.gate_val = m.has_gate ? (const float*)s->gate_val.p : nullptr; src.rsf = s->rsf;
+    return src;
+}
+
+// matrices that read one activation: one kr_launch_multi_matvec when they have one width.  Otherwise one launch each from the f32 hidden vector: a caller's
+// image input (x_kind 2) implies equal widths (in_img), so whenever this branch runs x IS `hid` / kind 1 -- it does not read (x, x_kind)
+static void proj_group(StepCtx& cx, const int* wids, float* const* ys, int n, const void* x, int x_kind) {
+    kr_decode_store* s = cx.s; hipStream_t st = cx.st;
+    KrMatDev mats[3]; bool same = true;
+    for (int i = 0; i < n; i++) { mats[i] = mv(s, wids[i]); same = same && mats[i].bits == mats[0].bits; }
+    if (same) PROF(PK_MATVEC, kr_launch_multi_matvec(mats, ys, n, x, x_kind, st));
+    else for (int i = 0; i < n; i++) PROF(PK_MATVEC, kr_launch_matvec(mats[i], cx.hid, 1, ys[i], st));
+}
+
+// KR_DECODE_FAST: the input add+RMSNorm folded into the first projection launch (every workgroup rebuilds the normalised vector with tree sums).  On MLA layers
+// (round 4) that launch is kv_a | q, or kv_a | q_a on the LoRA path.  Sets did_in / la_conv_done; the caller runs the norm launch when it is not taken.
+static void in_proj_fast(StepCtx& cx, DLayer& L) {
+    kr_decode_store* s = cx.s; hipStream_t st = cx.st;
+    const int mla_w2 = L.attn == ATTN_MLA ? (L.mq_wid >= 0 ? L.mq_wid : L.mqa_wid) : -1;
+    const bool mla_in = L.attn == ATTN_MLA && img_w(s, L.kva_wid) && img_w(s, mla_w2, L.kva_wid);
+    cx.did_in = cx.la_conv_done = false;
+    if (!(cx.fast && (cx.in_img || mla_in) && cx.src.mode != 2)) return;
+    KrFdmArgs fa{};
+    fdm_norm(cx, L.input_norm, fa); fa.first = cx.first ? 1 : 0;
+    if (cx.src.mode == 1) { fa.emb = cx.src.emb; fa.step = cx.src.step; }
+    int total = 0;
+    auto add = [&](int wid, float* y) { fa.mm.m[fa.mm.n] = mv(s, wid); fa.mm.y[fa.mm.n] = y; total += (fa.mm.m[fa.mm.n].N + 7) / 8; fa.mm.tile_end[fa.mm.n] = total; fa.mm.n++; };
+    if (L.attn == ATTN_LA) {
+        add(L.ba_wid, (float*)s->proj_b.p); add(L.qkvz_wid, (float*)s->proj_a.p);   // the ba tiles first: their lanes carry the libm gate epilogue, the first workgroups start earliest
+        const int hr = L.nv / L.nk;
+        if (L.dv == 128 && (L.dk == 128 || L.dk == 64) && L.nv == L.nk * hr && L.kd == 4 && img_w(s, L.out_wid)) {
+            fa.conv_state = (float*)L.conv_state.p; fa.conv_w = (const float*)L.conv_w.p; fa.qk_out = (float*)s->f_qk.p; fa.v_out = (float*)s->vbuf.p; fa.z_out = (float*)s->zbuf.p;
+            fa.nk = L.nk; fa.dk = L.dk; fa.hr = hr; fa.dv = L.dv; fa.conv_mi = 1; fa.gate_mi = 0;
+            fa.a_log = (const float*)L.a_log.p; fa.dt_bias = (const float*)L.dt_bias.p; fa.ge_out = (float*)s->gbuf.p; fa.beta_out = (float*)s->betabuf.p;
         }
-        // KR_DECODE_FAST on MLA layers (round 4): the input add + RMSNorm folded into the first projection launch (kv_a | q, or kv_a | q_a on the LoRA path) and
-        // the o projection on the K-split tree-sum matvec; the attention launches themselves (absorb, scores, weighted sum, w_vc) keep the reference's order
-        const int mla_w2 = L.attn == ATTN_MLA ? (L.mq_wid >= 0 ? L.mq_wid : L.mqa_wid) : -1;
-        const bool mla_in = fast && L.attn == ATTN_MLA && img_w(L.kva_wid) && img_w(mla_w2, L.kva_wid);
-        // FAST: the input add+RMSNorm folded into the first projection launch (every workgroup rebuilds the normalised vector with tree sums)
-        bool did_in = false, la_conv_done = false;
-        if (fast && (in_img || mla_in) && src.mode != 2) {
-            KrFdmArgs fa{};
-            fa.mode = 1; fa.hid_in = hid; fa.res_in = res_cur; fa.res_out = other(res_cur); fa.norm_w = (const float*)s->norms[L.input_norm]->p;
-            fa.first = first ? 1 : 0; fa.eps = s->eps; fa.bias_one = s->norm_bias_one;
-            if (src.mode == 1) { fa.emb = src.emb; fa.step = src.step; }
-            int total = 0;
-            auto add = [&](int wid, float* y) { fa.mm.m[fa.mm.n] = mv(s, wid); fa.mm.y[fa.mm.n] = y; total += (fa.mm.m[fa.mm.n].N + 7) / 8; fa.mm.tile_end[fa.mm.n] = total; fa.mm.n++; };
-            if (L.attn == ATTN_LA) {
-                add(L.ba_wid, (float*)s->proj_b.p); add(L.qkvz_wid, (float*)s->proj_a.p);   // the ba tiles first: their lanes carry the libm gate epilogue, the first workgroups start earliest
-                const int hr = L.nv / L.nk;
-                if (L.dv == 128 && (L.dk == 128 || L.dk == 64) && L.nv == L.nk * hr && L.kd == 4 && img_w(L.out_wid)) {
-                    fa.conv_state = (float*)L.conv_state.p; fa.conv_w = (const float*)L.conv_w.p; fa.qk_out = (float*)s->f_qk.p; fa.v_out = (float*)s->vbuf.p; fa.z_out = (float*)s->zbuf.p;
-                    fa.nk = L.nk; fa.dk = L.dk; fa.hr = hr; fa.dv = L.dv; fa.conv_mi = 1; fa.gate_mi = 0;
-                    fa.a_log = (const float*)L.a_log.p; fa.dt_bias = (const float*)L.dt_bias.p; fa.ge_out = (float*)s->gbuf.p; fa.beta_out = (float*)s->betabuf.p;
-                }
-            } else if (L.attn == ATTN_MLA) { add(L.kva_wid, (float*)s->kbuf.p); add(mla_w2, L.mq_wid >= 0 ? (float*)s->proj_a.p : (float*)s->proj_b.p); }
-            else { add(L.q_wid, (float*)s->proj_a.p); add(L.k_wid, (float*)s->kbuf.p); add(L.v_wid, (float*)s->vbuf.p); }
-            prof_mark(s, PK_MATVEC, st);
-            did_in = 0 == kr_launch_fdm(fa, st);
-            prof_mark(s, -1, st);
-            if (did_in) { la_conv_done = fa.conv_state != nullptr; res_cur = other(res_cur); }
+    } else if (L.attn == ATTN_MLA) { add(L.kva_wid, (float*)s->kbuf.p); add(mla_w2, L.mq_wid >= 0 ? (float*)s->proj_a.p : (float*)s->proj_b.p); }
+    else { add(L.q_wid, (float*)s->proj_a.p); add(L.k_wid, (float*)s->kbuf.p); add(L.v_wid, (float*)s->vbuf.p); }
+    cx.did_in = 0 == PROF_RC(PK_MATVEC, kr_launch_fdm(fa, st));
+    if (cx.did_in) { cx.la_conv_done = fa.conv_state != nullptr; cx.res_cur = cx.other(); }
+}
+
+// out / o projection, from the attention output's INT16 image where the attention launch left one.  KR_DECODE_FAST: K split over the waves of a workgroup, tree sums
+static void out_proj(StepCtx& cx, int wid, bool img) {
+    kr_decode_store* s = cx.s; hipStream_t st = cx.st;
+    if (img && cx.fast) {
+        KrFdmArgs fo = fdm_one(s, 0, wid, cx.hid); fo.img = s->img_attn.p;
+        if (PROF_RC(PK_OUT_PROJ, kr_launch_fdm(fo, st)) == 0) return;
+    }
+    if (img) PROF(PK_MATVEC, kr_launch_matvec(mv(s, wid), s->img_attn.p, 2, cx.hid, st));
+    else PROF(PK_MATVEC, kr_launch_matvec(mv(s, wid), s->attn_out.p, 1, cx.hid, st));
+}
+
+static int attn_la(StepCtx& cx, DLayer& L) {
+    kr_decode_store* s = cx.s; hipStream_t st = cx.st;
+    if (cx.la_conv_done) {      // KR_DECODE_FAST: conv + gates came out of the folded norm + projection launch
+        KrFlaArgs a{};
+        a.qk = (const float*)s->f_qk.p; a.v = (const float*)s->vbuf.p; a.z = (const float*)s->zbuf.p; a.ge = (const float*)s->gbuf.p; a.beta = (const float*)s->betabuf.p;
+        a.scale = L.la_scale; a.state = (float*)L.recur_state.p;
+        a.norm_w = (const float*)L.la_norm_w.p; a.out = (float*)s->attn_out.p; a.img_out = s->img_attn.p; a.img_k = s->weights[L.out_wid]->ms.view().ng * 128;
+        a.nk = L.nk; a.nv = L.nv; a.hr = L.nv / L.nk; a.dk = L.dk; a.dv = L.dv; a.eps = s->eps;
+        if (PROF_RC(PK_LA_RECUR, kr_launch_fla(a, st))) return kr_fail(KR_ERR_VALUE, "unsupported linear-attention geometry (fast mode)");
+        out_proj(cx, L.out_wid, true);
+        return KR_OK;
+    }
+    bool la_heads = false;      // exact step: conv + gates ran as the in-projection's epilogue, the recurrence runs one workgroup per value head
+    if (!cx.did_in) {
+        const int wids[2] = {L.qkvz_wid, L.ba_wid};
+        float* ys[2] = {(float*)s->proj_a.p, (float*)s->proj_b.p};
+        const void* xin = cx.in_img ? (const void*)s->img_in.p : (const void*)cx.hid;
+        if (s->opt_la_heads && cx.in_img && s->f_qk.p && L.kd == 4 && L.nv == L.nk * (L.nv / L.nk) &&
+            (L.dk == 128 || L.dk == 64) && (L.dv == 128 || L.dv == 64)) {
+            const KrMatDev mats[2] = {mv(s, wids[0]), mv(s, wids[1])};
+            KrCoLa la{};
+            la.conv_state = (float*)L.conv_state.p; la.conv_w = (const float*)L.conv_w.p; la.qk_out = (float*)s->f_qk.p; la.v_out = (float*)s->vbuf.p; la.z_out = (float*)s->zbuf.p;
+            la.nk = L.nk; la.dk = L.dk; la.hr = L.nv / L.nk; la.dv = L.dv; la.conv_mi = 0;
+            la_heads = 0 == PROF_RC(PK_MATVEC, kr_launch_multi_matvec_la(mats, ys, 2, xin, la, st));
         }
-        if (!did_in) {
-            PROF(PK_RMSNORM, kr_launch_fused_add_rmsnorm(src, hid, res_cur, res, (const float*)s->norms[L.input_norm]->p, H, s->eps, first ? 1 : 0, s->norm_bias_one, st,
-                                                         in_img ? s->img_in.p : nullptr));
-            res_cur = res;
-        }
-        first = false; src = from_hidden;
-        const void* xin = in_img ? (const void*)s->img_in.p : (const void*)hid; const int xin_kind = in_img ? 2 : 1;
-        // FAST out / o projection from the attention output's INT16 image: K split over the waves of a workgroup, tree sums
-        auto out_proj = [&](int wid) {
-            if (fast) {
-                KrFdmArgs fo{}; fo.mode = 0; fo.img = s->img_attn.p; fo.mm.n = 1; fo.mm.m[0] = mv(s, wid); fo.mm.y[0] = hid; fo.mm.tile_end[0] = (fo.mm.m[0].N + 7) / 8;
-                prof_mark(s, PK_OUT_PROJ, st);
-                const int rc = kr_launch_fdm(fo, st);
-                prof_mark(s, -1, st);
-                if (rc == 0) return;
-            }
-            PROF(PK_MATVEC, kr_launch_matvec(mv(s, wid), s->img_attn.p, 2, hid, st));
-        };
-        if (L.attn == ATTN_LA && la_conv_done) {
-            KrFlaArgs a{};
-            a.qk = (const float*)s->f_qk.p; a.v = (const float*)s->vbuf.p; a.z = (const float*)s->zbuf.p; a.ge = (const float*)s->gbuf.p; a.beta = (const float*)s->betabuf.p;
-            a.scale = L.la_scale; a.state = (float*)L.recur_state.p;
-            a.norm_w = (const float*)L.la_norm_w.p; a.out = (float*)s->attn_out.p; a.img_out = s->img_attn.p; a.img_k = s->weights[L.out_wid]->ms.view().ng * 128;
-            a.nk = L.nk; a.nv = L.nv; a.hr = L.nv / L.nk; a.dk = L.dk; a.dv = L.dv; a.eps = s->eps;
-            prof_mark(s, PK_LA_RECUR, st);
-            if (kr_launch_fla(a, st)) return kr_fail(KR_ERR_VALUE, "unsupported linear-attention geometry (fast mode)");
-            prof_mark(s, -1, st);
-            out_proj(L.out_wid);
-        } else if (L.attn == ATTN_LA) {
-            bool la_heads = false;      // exact step: conv + gates ran as the in-projection's epilogue, the recurrence runs one workgroup per value head
-            if (!did_in) {
-                const KrMatDev mats[2] = {mv(s, L.qkvz_wid), mv(s, L.ba_wid)};
-                float* ys[2] = {(float*)s->proj_a.p, (float*)s->proj_b.p};
-                if (s->opt_la_heads && s->fuse_la && xin_kind == 2 && mats[0].bits == mats[1].bits && s->f_qk.p && L.kd == 4 && L.nv == L.nk * (L.nv / L.nk) &&
-                    (L.dk == 128 || L.dk == 64) && (L.dv == 128 || L.dv == 64)) {
-                    KrCoLa la{};
-                    la.conv_state = (float*)L.conv_state.p; la.conv_w = (const float*)L.conv_w.p; la.qk_out = (float*)s->f_qk.p; la.v_out = (float*)s->vbuf.p; la.z_out = (float*)s->zbuf.p;
-                    la.nk = L.nk; la.dk = L.dk; la.hr = L.nv / L.nk; la.dv = L.dv; la.conv_mi = 0;
-                    prof_mark(s, PK_MATVEC, st);
-                    la_heads = 0 == kr_launch_multi_matvec_la(mats, ys, 2, xin, la, st);
-                    prof_mark(s, -1, st);
-                }
-                if (la_heads) {}
-                else if (mats[0].bits == mats[1].bits) PROF(PK_MATVEC, kr_launch_multi_matvec(mats, ys, 2, xin, xin_kind, st));
-                else { PROF(PK_MATVEC, kr_launch_matvec(mats[0], hid, 1, ys[0], st)); PROF(PK_MATVEC, kr_launch_matvec(mats[1], hid, 1, ys[1], st)); }
-            }
-            KrLaArgs a{};
-            a.qkvz = (const float*)s->proj_a.p; a.ba = (const float*)s->proj_b.p; a.conv_state = (float*)L.conv_state.p;
-            a.conv_w = (const float*)L.conv_w.p; a.a_log = (const float*)L.a_log.p; a.dt_bias = (const float*)L.dt_bias.p; a.scale = L.la_scale;
-            a.q = (float*)s->qbuf.p; a.k = (float*)s->kbuf.p; a.v = (float*)s->vbuf.p; a.z = (float*)s->zbuf.p; a.g = (float*)s->gbuf.p; a.beta = (float*)s->betabuf.p;
-            a.nk = L.nk; a.nv = L.nv; a.dk = L.dk; a.dv = L.dv; a.hr = L.nv / L.nk;
-            void* la_img = (img_ok && img_w(L.out_wid) && L.dv == 128) ? s->img_attn.p : nullptr;
-            const int nt_la = a.hr * L.dv;
-            const bool la_fused = s->fuse_la && nt_la <= 256 && nt_la % 64 == 0 && (L.dv == 128 || L.dv == 64) && L.nv == L.nk * a.hr && (L.dk == 128 || L.dk == 64);
-            if (la_heads) {
-                a.q = (float*)s->f_qk.p;      // [nk][2 dk] conv + SiLU outputs of q | k (normalised inside the launch)
-                prof_mark(s, PK_LA_RECUR, st);
-                if (kr_launch_la_step_heads(a, (float*)L.recur_state.p, (const float*)L.la_norm_w.p, (float*)s->attn_out.p, s->eps, st, la_img))
-                    return kr_fail(KR_ERR_VALUE, "unsupported linear-attention geometry");
-                prof_mark(s, -1, st);
-            } else if (la_fused) {
-                prof_mark(s, PK_LA_RECUR, st);
-                (void)kr_launch_la_step(a, (float*)L.recur_state.p, (const float*)L.la_norm_w.p, (float*)s->attn_out.p, s->eps, st, la_img);
-                prof_mark(s, -1, st);
-            } else {
-                PROF(PK_LA_CONV, kr_launch_la_conv(a, st));
-                prof_mark(s, PK_LA_RECUR, st);
-                if (kr_launch_la_recurrent_gnorm((float*)L.recur_state.p, a.q, a.k, a.v, a.g, a.beta, a.z, (const float*)L.la_norm_w.p, (float*)s->attn_out.p,
-                                                 L.nv, L.dk, L.dv, s->eps, st, la_img))
-                    return kr_fail(KR_ERR_VALUE, "unsupported linear-attention geometry");
-                prof_mark(s, -1, st);
-            }
-            if (img_ok && img_w(L.out_wid) && L.dv == 128) out_proj(L.out_wid);
-            else PROF(PK_MATVEC, kr_launch_matvec(mv(s, L.out_wid), s->attn_out.p, 1, hid, st));
-        } else if (L.attn == ATTN_GQA) {
-            if (!L.kv_k.p) return kr_fail(KR_ERR_STATE, "set_decode_state was not called (no KV cache for layer %zu)", li);
-            if (!did_in) {
-                const KrMatDev mats[3] = {mv(s, L.q_wid), mv(s, L.k_wid), mv(s, L.v_wid)};
-                float* ys[3] = {(float*)s->proj_a.p, (float*)s->kbuf.p, (float*)s->vbuf.p};
-                if (mats[0].bits == mats[1].bits && mats[0].bits == mats[2].bits) PROF(PK_MATVEC, kr_launch_multi_matvec(mats, ys, 3, xin, xin_kind, st));
-                else for (int i = 0; i < 3; i++) PROF(PK_MATVEC, kr_launch_matvec(mats[i], hid, 1, ys[i], st));
-            }
-            KrGqaArgs a{};
-            a.step = step; a.q_in = (const float*)s->proj_a.p; a.k_in = (const float*)s->kbuf.p; a.v_in = (const float*)s->vbuf.p;
-            a.q_norm = L.q_norm_len ? (const float*)L.q_norm.p : nullptr; a.k_norm = L.k_norm_len ? (const float*)L.k_norm.p : nullptr;
-            a.q_norm_per_head = L.q_norm_len == L.nh * L.hd; a.k_norm_per_head = L.k_norm_len == L.nkv * L.hd;
-            a.rope_cos = (const float*)s->rope_cos.p; a.rope_sin = (const float*)s->rope_sin.p; a.rope_half = s->rope_half;
-            a.k_cache = L.kv_k.p; a.v_cache = L.kv_v.p; a.kv_fp8 = s->kv_fp8; a.q_out = (float*)s->qbuf.p; a.gate = (float*)s->gatebuf.p;
-            a.attn_out = (float*)s->attn_out.p; a.gated = L.gated; a.nh = L.nh; a.nkv = L.nkv; a.hd = L.hd; a.eps = s->eps; a.sm_scale = L.sm_scale;
-            const bool o_img = img_ok && img_w(L.o_wid) && L.hd % 128 == 0 && s->weights[L.o_wid]->cols == L.nh * L.hd;
-            a.img_out = o_img ? s->img_attn.p : nullptr;
-            a.sc_g = s->kv_max_seq > s->gqa_split_min ? (float*)s->gqa_scores.p : nullptr;
-            a.force_stream = s->opt_gqa_stream; a.tree_norm = fast ? 1 : 0;
-            if (s->attn_fast && a.sc_g) { a.fd_o = (float*)s->fd_o.p; a.fd_ml = (float*)s->fd_ml.p; }
-            PROF(PK_GQA, { if (!(fast && s->opt_gqa_fused && !a.sc_g && kr_launch_fgqa(a, s->kv_max_seq, st) == 0)) kr_launch_gqa(a, s->kv_max_seq, st); });      // KR_DECODE_FAST, short cache: one launch
-            if (o_img) out_proj(L.o_wid);
-            else PROF(PK_MATVEC, kr_launch_matvec(mv(s, L.o_wid), s->attn_out.p, 1, hid, st));
-        }
-        else if (L.attn == ATTN_MLA) {
-            if (!L.kv_k.p) return kr_fail(KR_ERR_STATE, "set_decode_state was not called (no MLA cache for layer %zu)", li);
-            if (L.mla_rope_seq < s->kv_max_seq) return kr_fail(KR_ERR_VALUE, "MLA rope table (%d) shorter than kv_max_seq (%d)", L.mla_rope_seq, s->kv_max_seq);
-            float* kv_out = (float*)s->kbuf.p; float* q_full = (float*)s->proj_a.p;
-            if (did_in) {          // KR_DECODE_FAST: kv_a | q (or kv_a | q_a) came out of the folded norm + projection launch above
-                if (L.mq_wid < 0) {
-                    if (L.q_a_norm_len) PROF(PK_RMSNORM, kr_launch_rmsnorm_seq((float*)s->proj_b.p, (const float*)L.q_a_norm.p, s->weights[L.mqa_wid]->rows, s->eps, st));
-                    PROF(PK_MATVEC, kr_launch_matvec(mv(s, L.mqb_wid), s->proj_b.p, 1, q_full, st));
-                }
-            } else
-            if (L.mq_wid >= 0) {   // direct query projection shares the activation with kv_a_proj: one launch
-                const KrMatDev mats[2] = {mv(s, L.kva_wid), mv(s, L.mq_wid)};
-                float* ys[2] = {kv_out, q_full};
-                if (mats[0].bits == mats[1].bits) PROF(PK_MATVEC, kr_launch_multi_matvec(mats, ys, 2, hid, 1, st));
-                else { PROF(PK_MATVEC, kr_launch_matvec(mats[0], hid, 1, ys[0], st)); PROF(PK_MATVEC, kr_launch_matvec(mats[1], hid, 1, ys[1], st)); }
-            } else {               // LoRA: q_a_proj -> sequential RMSNorm -> q_b_proj (decode.rs:3036-3079)
-                const KrMatDev mats[2] = {mv(s, L.kva_wid), mv(s, L.mqa_wid)};
-                float* ys[2] = {kv_out, (float*)s->proj_b.p};
-                if (mats[0].bits == mats[1].bits) PROF(PK_MATVEC, kr_launch_multi_matvec(mats, ys, 2, hid, 1, st));
-                else { PROF(PK_MATVEC, kr_launch_matvec(mats[0], hid, 1, ys[0], st)); PROF(PK_MATVEC, kr_launch_matvec(mats[1], hid, 1, ys[1], st)); }
-                if (L.q_a_norm_len) PROF(PK_RMSNORM, kr_launch_rmsnorm_seq((float*)s->proj_b.p, (const float*)L.q_a_norm.p, s->weights[L.mqa_wid]->rows, s->eps, st));
-                PROF(PK_MATVEC, kr_launch_matvec(mv(s, L.mqb_wid), s->proj_b.p, 1, q_full, st));
-            }
-            KrMlaArgs a{};
-            a.step = step; a.kv_out = kv_out; a.q_full = q_full; a.kv_a_norm = (const float*)L.kv_a_norm.p; a.w_kc = (const float*)L.w_kc.p;
-            a.w_vc = (const float*)L.w_vc.p; a.rope_cos = (const float*)L.mla_cos.p; a.rope_sin = (const float*)L.mla_sin.p;
-            a.ckv_cache = L.kv_k.p; a.kpe_cache = L.kv_v.p; a.kv_fp8 = s->kv_fp8; a.q_abs = (float*)s->qbuf.p; a.q_pe = (float*)s->zbuf.p;
-            a.attn_lat = (float*)s->latbuf.p; a.v_proj = (float*)s->attn_out.p;
-            a.nh = L.nh; a.klr = L.klr; a.nd = L.nd; a.rd = L.rd; a.vhd = L.vhd; a.eps = s->eps; a.sm_scale = L.sm_scale;
-            a.sc_g = s->kv_max_seq > s->mla_split_min ? (float*)s->gqa_scores.p : nullptr;
-            if (s->attn_fast && a.sc_g) { a.fast = 1; a.fd_o = (float*)s->fd_o.p; a.fd_ml = (float*)s->fd_ml.p; }
-            a.decode_fast = fast ? 1 : 0; a.decode_fused = fast && s->opt_gqa_fused ? 1 : 0;
-            PROF(PK_GQA, kr_launch_mla(a, s->kv_max_seq, st));
-            bool o_done = false;
-            if (fast && s->weights[L.o_wid]->cols == L.nh * L.vhd) {      // o projection straight from the f32 w_vc output: every workgroup quantises it, K split over the waves
-                KrFdmArgs fo{}; fo.mode = 2; fo.hid_in = (const float*)s->attn_out.p; fo.mm.n = 1; fo.mm.m[0] = mv(s, L.o_wid); fo.mm.y[0] = hid; fo.mm.tile_end[0] = (fo.mm.m[0].N + 7) / 8;
-                prof_mark(s, PK_OUT_PROJ, st);
-                o_done = 0 == kr_launch_fdm(fo, st);
-                prof_mark(s, -1, st);
-            }
-            if (!o_done) PROF(PK_MATVEC, kr_launch_matvec(mv(s, L.o_wid), s->attn_out.p, 1, hid, st));
-        }
-        // post-attention fused add+RMSNorm: folded into the router launch of MoE layers, its own launch otherwise
-        const float* act = hid;   // normalised hidden the MLP block reads
-        bool routed = false, moe_done = false;
-        if (L.mlp == MLP_MOE) {
-            if (s->own_eng || L.moe_layer >= (int)e->layers.size()) return kr_fail(KR_ERR_STATE, "set_moe_store was not called (MoE layer %d has no engine)", L.moe_layer);
-            Layer& EL = e->layers[L.moe_layer];
-            if (!EL.routing_present) return kr_fail(KR_ERR_STATE, "Routing weights not set for layer %d", L.moe_layer);
-            if (!EL.w13.allocated() && !EL.gguf) return kr_fail(KR_ERR_STATE, "Model not loaded (MoE layer %d has no experts)", L.moe_layer);
-            if (EL.gguf && ep_dec) return kr_fail(KR_ERR_STATE, "expert-parallel decode on native GGUF layers is not implemented (MoE layer %d)", L.moe_layer);
-            if (fast && !EL.gguf) {   // norm + gate GEMV | select + gate|up + silu*up | down + combine: three launches, the MoE output lands in `hid`
-                const bool has_shared = L.sgu_wid >= 0, has_gate = has_shared && L.sg_wid >= 0;
-                KrFmoeArgs fa{}; KrMoeArgs& a = fa.m;
-                a.shared_decode = 1; a.act_img = s->img_post.p; a.act_img_bf16 = s->img_post_bf16.p;
-                a.ids = (const int32_t*)s->r_ids.p; a.wts = (const float*)s->r_w.p;
-                a.B = 1; a.topk = s->topk; a.n_slots = s->topk + (has_shared ? 1 : 0); a.E = e->r_ne; a.H = H; a.I = EL.inter;
-                a.w13 = EL.w13.view(); a.w2 = EL.w2.view();
-                if (has_shared) { a.sw13 = mv(s, L.sgu_wid); a.sw2 = mv(s, L.sd_wid); a.I_shared = s->weights[L.sgu_wid]->rows / 2; }
-                const int imax = has_shared && a.I_shared > a.I ? a.I_shared : a.I;
-                a.gu_ld = 2 * imax; a.gu = (float*)s->moe_gu.p; a.eo = (float*)s->moe_eo.p;
-                a.rsf = s->rsf; a.swiglu_limit = e->cfg.swiglu_limit; a.alpha = e->cfg.activation_alpha;
-                a.act_mode = e->cfg.swiglu_limit > 0.0f ? KR_ACT_GPTOSS : KR_ACT_SILU_FUSED;
-                bool ok = true;
-                if (has_gate) {
-                    if (a.w13.bits == a.sw13.bits && mv(s, L.sg_wid).bits == a.w13.bits) { a.sgate = mv(s, L.sg_wid); a.gate_out = (float*)s->gate_val.p; }
-                    else ok = false;
-                }
-                fa.logits = (const float*)s->r_logits.p; fa.esc = EL.has_esc ? (const float*)EL.esc.p : nullptr; fa.scoring = s->scoring; fa.norm_topk = s->norm_topk;
-                fa.hid_out = hid;
-                if (ep_dec) {
-                    kr_ep_slice(e, &a.e_lo, &a.e_hi, &a.e_sub);
-                    fa.shared_skip = has_shared && kr_ep_rank(e) != (int)(li % (size_t)kr_ep_world(e)) ? 1 : 0;
-                }
-                if (ok && kr_fmoe_check(fa) == 0) {
-                    KrFrtArgs ra{};
-                    ra.gate_cm = EL.gate_cm.p; ra.gate_bf16 = EL.gate_bf16_exact; ra.bias = EL.has_bias ? (const float*)EL.bias.p : nullptr; ra.logits = (float*)s->r_logits.p;
-                    ra.E = e->r_ne; ra.H = H; ra.hid_in = hid; ra.res_in = res_cur; ra.norm_w = (const float*)s->norms[L.post_norm]->p; ra.hid_out = (float*)s->hid2.p;
-                    ra.res_out = other(res_cur); ra.eps = s->eps; ra.bias_one = s->norm_bias_one; ra.img_f32 = s->img_post.p; ra.img_bf16 = s->img_post_bf16.p;
-                    prof_mark(s, PK_ROUTE_LOGITS, st);
-                    const int rc = kr_launch_frt(ra, st);
-                    prof_mark(s, -1, st);
-                    if (rc == 0) {
-                        // kr_fmoe_check above covers every refusal of these two launchers; a non-zero return here would leave the layer half-run
-                        prof_mark(s, PK_MOE_W13, st); const int r13 = kr_launch_fw13(fa, st); prof_mark(s, -1, st);
-                        prof_mark(s, PK_MOE_W2, st); const int r2 = kr_launch_fw2(fa, st); prof_mark(s, -1, st);
-                        if (r13 || r2) return kr_fail(KR_ERR_STATE, "internal: KR_DECODE_FAST expert launch refused after kr_fmoe_check accepted layer %zu", li);
-                        if (ep_dec) if (int rc = kr_ep_allreduce_on(e, hid, (size_t)H, st)) return rc;
-                        res_cur = other(res_cur); src = from_hidden; moe_done = true;
-                    }
-                }
-            }
-            // KR_DECODE_FAST on a native-GGUF layer: the same three launches as for transposed experts -- the routed slots of the gate|up and down launches walk the
-            // GGUF blocks (kr_gguf_dev.h: the block kernels' products, a row's blocks split over two waves), the shared expert keeps its transposed form
-            if (!moe_done && fast && EL.gguf && src.mode != 2) {
-                const bool has_shared = L.sgu_wid >= 0, has_gate = has_shared && L.sg_wid >= 0;
-                KrFmoeArgs fa{}; KrMoeArgs& a = fa.m;
-                fa.gguf = 1; fa.ggate = EL.g_gate.view(); fa.gup = EL.g_up.view(); fa.gdown = EL.g_down.view(); fa.act_f32 = (const float*)s->hid2.p;
-                a.shared_decode = 1; a.act_img = s->img_post.p; a.act_img_bf16 = s->img_post_bf16.p;
-                a.ids = (const int32_t*)s->r_ids.p; a.wts = (const float*)s->r_w.p;
-                a.B = 1; a.topk = s->topk; a.n_slots = s->topk + (has_shared ? 1 : 0); a.E = e->cfg.n_routed_experts; a.H = H; a.I = EL.inter;
-                if (has_shared) { a.sw13 = mv(s, L.sgu_wid); a.sw2 = mv(s, L.sd_wid); a.I_shared = s->weights[L.sgu_wid]->rows / 2; }
-                const int imax = has_shared && a.I_shared > a.I ? a.I_shared : a.I;
-                a.gu_ld = 2 * imax; a.gu = (float*)s->moe_gu.p; a.eo = (float*)s->moe_eo.p;
-                a.rsf = s->rsf; a.swiglu_limit = e->cfg.swiglu_limit; a.alpha = e->cfg.activation_alpha;
-                a.act_mode = e->cfg.swiglu_limit > 0.0f ? KR_ACT_GPTOSS : KR_ACT_SILU_FUSED;
-                bool ok = e->r_ne == e->cfg.n_routed_experts;
-                if (has_gate) {
-                    if (mv(s, L.sg_wid).bits == a.sw13.bits) { a.sgate = mv(s, L.sg_wid); a.gate_out = (float*)s->gate_val.p; }
-                    else ok = false;
-                }
-                fa.logits = (const float*)s->r_logits.p; fa.esc = EL.has_esc ? (const float*)EL.esc.p : nullptr; fa.scoring = s->scoring; fa.norm_topk = s->norm_topk;
-                fa.hid_out = hid;
-                if (ok && kr_fmoe_check(fa) == 0) {
-                    KrFrtArgs ra{};
-                    ra.gate_cm = EL.gate_cm.p; ra.gate_bf16 = EL.gate_bf16_exact; ra.bias = EL.has_bias ? (const float*)EL.bias.p : nullptr; ra.logits = (float*)s->r_logits.p;
-                    ra.E = e->r_ne; ra.H = H; ra.hid_in = hid; ra.res_in = res_cur; ra.norm_w = (const float*)s->norms[L.post_norm]->p; ra.hid_out = (float*)s->hid2.p;
-                    ra.res_out = other(res_cur); ra.eps = s->eps; ra.bias_one = s->norm_bias_one; ra.img_f32 = s->img_post.p; ra.img_bf16 = s->img_post_bf16.p;
-                    prof_mark(s, PK_ROUTE_LOGITS, st);
-                    const int rc = kr_launch_frt(ra, st);
-                    prof_mark(s, -1, st);
-                    if (rc == 0) {
-                        prof_mark(s, PK_MOE_W13, st); const int r13 = kr_launch_fw13(fa, st); prof_mark(s, -1, st);
-                        prof_mark(s, PK_MOE_W2, st); const int r2 = kr_launch_fw2(fa, st); prof_mark(s, -1, st);
-                        if (r13 || r2) return kr_fail(KR_ERR_STATE, "internal: KR_DECODE_FAST expert launch refused after kr_fmoe_check accepted GGUF layer %zu", li);
-                        res_cur = other(res_cur); src = from_hidden; moe_done = true;
-                    }
-                }
-            }
-            // ... and, for GGUF geometries those launches do not cover: the mode's norm + gate GEMV launch and the stand-alone select in front of the (exact) block kernels
-            if (!moe_done && fast && EL.gguf && src.mode != 2) {
-                KrFrtArgs ra{};
-                ra.gate_cm = EL.gate_cm.p; ra.gate_bf16 = EL.gate_bf16_exact; ra.bias = EL.has_bias ? (const float*)EL.bias.p : nullptr; ra.logits = (float*)s->r_logits.p;
-                ra.E = e->r_ne; ra.H = H; ra.hid_in = hid; ra.res_in = res_cur; ra.norm_w = (const float*)s->norms[L.post_norm]->p; ra.hid_out = (float*)s->hid2.p;
-                ra.res_out = other(res_cur); ra.eps = s->eps; ra.bias_one = s->norm_bias_one; ra.img_f32 = s->img_post.p; ra.img_bf16 = s->img_post_bf16.p;
-                prof_mark(s, PK_ROUTE_LOGITS, st);
-                const int rc = kr_launch_frt(ra, st);
-                prof_mark(s, -1, st);
-                if (rc == 0) {
-                    PROF(PK_ROUTE_SELECT, kr_launch_route_select((const float*)s->r_logits.p, EL.has_esc ? (const float*)EL.esc.p : nullptr, (int32_t*)s->r_ids.p, (float*)s->r_w.p, 1, e->r_ne, s->topk,
-                                                                 s->scoring, s->norm_topk, KR_ROUTE_RULE_DECODE, 0, st));
-                    routed = true; act = (const float*)s->hid2.p; res_cur = other(res_cur);
-                }
-            }
-            if (!moe_done && !routed && s->fuse_router) {
-                prof_mark(s, PK_ROUTE_LOGITS, st);
-                routed = 0 == kr_launch_route_fused_decode(EL.gate_cm.p, EL.gate_bf16_exact, EL.has_bias ? (const float*)EL.bias.p : nullptr, (float*)s->r_logits.p,
-                                                           (unsigned*)s->r_counter.p, EL.has_esc ? (const float*)EL.esc.p : nullptr, (int32_t*)s->r_ids.p,
-                                                           (float*)s->r_w.p, e->r_ne, H, s->topk, s->scoring, s->norm_topk, nullptr, hid, res_cur,
-                                                           (const float*)s->norms[L.post_norm]->p, (float*)s->hid2.p, other(res_cur), s->eps,
-                                                           s->norm_bias_one, st, img_ok ? s->img_post.p : nullptr, img_ok ? s->img_post_bf16.p : nullptr);
-                prof_mark(s, -1, st);
-                if (routed) { act = (const float*)s->hid2.p; res_cur = other(res_cur); }
-            }
-        }
-        if (moe_done) continue;
-        // KR_DECODE_FAST on a dense MLP layer (V2-Lite's first, decode.rs:1693-1741; round 6): the post-attention add + RMSNorm folded into the gate | up projection launch
-        // (every workgroup rebuilds the normalised vector with tree sums, as the attention in-projections of the mode do); the down projection keeps the exact kernel with
-        // its silu * up + INT16 prologue -- its K (10 944) is beyond what a folded prologue holds
-        if (fast && !routed && L.mlp == MLP_DENSE && src.mode == 0 && s->opt_dense_fast) {
-            const KrMatDev g = mv(s, L.gate_wid), u = mv(s, L.up_wid);
-            const int K = s->weights[L.down_wid]->cols;
-            if (g.bits == u.bits && (g.bits == 4 || g.bits == 8)) {
-                KrFdmArgs fd{};
-                fd.mode = 1; fd.hid_in = hid; fd.res_in = res_cur; fd.res_out = other(res_cur); fd.norm_w = (const float*)s->norms[L.post_norm]->p; fd.eps = s->eps; fd.bias_one = s->norm_bias_one;
-                fd.mm.n = 2; fd.mm.m[0] = g; fd.mm.y[0] = (float*)s->dense_gu.p; fd.mm.tile_end[0] = (g.N + 7) / 8;
-                fd.mm.m[1] = u; fd.mm.y[1] = (float*)s->dense_gu.p + K; fd.mm.tile_end[1] = fd.mm.tile_end[0] + (u.N + 7) / 8;
-                prof_mark(s, PK_MATVEC, st);
-                const bool done = 0 == kr_launch_fdm(fd, st);
-                prof_mark(s, -1, st);
-                if (done) {
-                    res_cur = other(res_cur);
-                    PROF(PK_MATVEC, kr_launch_matvec(mv(s, L.down_wid), s->dense_gu.p, 1, hid, st, KR_ACT_SILU_MUL));
-                    continue;
-                }
+        if (!la_heads) proj_group(cx, wids, ys, 2, xin, cx.in_img ? 2 : 1);
+    }
+    KrLaArgs a{};
+    a.qkvz = (const float*)s->proj_a.p; a.ba = (const float*)s->proj_b.p; a.conv_state = (float*)L.conv_state.p;
+    a.conv_w = (const float*)L.conv_w.p; a.a_log = (const float*)L.a_log.p; a.dt_bias = (const float*)L.dt_bias.p; a.scale = L.la_scale;
+    a.q = (float*)s->qbuf.p; a.k = (float*)s->kbuf.p; a.v = (float*)s->vbuf.p; a.z = (float*)s->zbuf.p; a.g = (float*)s->gbuf.p; a.beta = (float*)s->betabuf.p;
+    a.nk = L.nk; a.nv = L.nv; a.dk = L.dk; a.dv = L.dv; a.hr = L.nv / L.nk;
+    const bool o_img = cx.img_ok() && img_w(s, L.out_wid) && L.dv == 128;
+    void* la_img = o_img ? s->img_attn.p : nullptr;
+    const int nt_la = a.hr * L.dv;
+    const bool la_fused = nt_la <= 256 && nt_la % 64 == 0 && (L.dv == 128 || L.dv == 64) && L.nv == L.nk * a.hr && (L.dk == 128 || L.dk == 64);
+    if (la_heads) {
+        a.q = (float*)s->f_qk.p;      // [nk][2 dk] conv + SiLU outputs of q | k (normalised inside the launch)
+        if (PROF_RC(PK_LA_RECUR, kr_launch_la_step_heads(a, (float*)L.recur_state.p, (const float*)L.la_norm_w.p, (float*)s->attn_out.p, s->eps, st, la_img)))
+            return kr_fail(KR_ERR_VALUE, "unsupported linear-attention geometry");
+    } else if (la_fused) {      // conv + recurrence + gated norm in one launch per KEY head (kr_la_step_kernel)
+        (void)PROF_RC(PK_LA_RECUR, kr_launch_la_step(a, (float*)L.recur_state.p, (const float*)L.la_norm_w.p, (float*)s->attn_out.p, s->eps, st, la_img));
+    } else {
+        PROF(PK_LA_CONV, kr_launch_la_conv(a, st));
+        if (PROF_RC(PK_LA_RECUR, kr_launch_la_recurrent_gnorm((float*)L.recur_state.p, a.q, a.k, a.v, a.g, a.beta, a.z, (const float*)L.la_norm_w.p,
+                                                             (float*)s->attn_out.p, L.nv, L.dk, L.dv, s->eps, st, la_img)))
+            return kr_fail(KR_ERR_VALUE, "unsupported linear-attention geometry");
+    }
+    out_proj(cx, L.out_wid, o_img);
+    return KR_OK;
+}
+
+static int attn_gqa(StepCtx& cx, DLayer& L, size_t li) {
+    kr_decode_store* s = cx.s; hipStream_t st = cx.st;
+    if (!L.kv_k.p) return kr_fail(KR_ERR_STATE, "set_decode_state was not called (no KV cache for layer %zu)", li);
+    if (!cx.did_in) {
+        const int wids[3] = {L.q_wid, L.k_wid, L.v_wid};
+        float* ys[3] = {(float*)s->proj_a.p, (float*)s->kbuf.p, (float*)s->vbuf.p};
+        proj_group(cx, wids, ys, 3, cx.in_img ? (const void*)s->img_in.p : (const void*)cx.hid, cx.in_img ? 2 : 1);
+    }
+    KrGqaArgs a{};
+    a.step = (const KrStep*)s->step_dev.p; a.q_in = (const float*)s->proj_a.p; a.k_in = (const float*)s->kbuf.p; a.v_in = (const float*)s->vbuf.p;
+    a.q_norm = L.q_norm_len ? (const float*)L.q_norm.p : nullptr; a.k_norm = L.k_norm_len ? (const float*)L.k_norm.p : nullptr;
+    a.q_norm_per_head = L.q_norm_len == L.nh * L.hd; a.k_norm_per_head = L.k_norm_len == L.nkv * L.hd;
+    a.rope_cos = (const float*)s->rope_cos.p; a.rope_sin = (const float*)s->rope_sin.p; a.rope_half = s->rope_half;
+    a.k_cache = L.kv_k.p; a.v_cache = L.kv_v.p; a.kv_fp8 = s->kv_fp8; a.q_out = (float*)s->qbuf.p; a.gate = (float*)s->gatebuf.p;
+    a.attn_out = (float*)s->attn_out.p; a.gated = L.gated; a.nh = L.nh; a.nkv = L.nkv; a.hd = L.hd; a.eps = s->eps; a.sm_scale = L.sm_scale;
+    const bool o_img = cx.img_ok() && img_w(s, L.o_wid) && L.hd % 128 == 0 && s->weights[L.o_wid]->cols == L.nh * L.hd;
+    a.img_out = o_img ? s->img_attn.p : nullptr;
+    a.sc_g = s->kv_max_seq > s->gqa_split_min ? (float*)s->gqa_scores.p : nullptr;
+    a.force_stream = s->opt_gqa_stream; a.tree_norm = cx.fast ? 1 : 0;
+    if (s->attn_fast && a.sc_g) { a.fd_o = (float*)s->fd_o.p; a.fd_ml = (float*)s->fd_ml.p; }
+    PROF(PK_GQA, { if (!(cx.fast && s->opt_gqa_fused && !a.sc_g && kr_launch_fgqa(a, s->kv_max_seq, st) == 0)) kr_launch_gqa(a, s->kv_max_seq, st); });      // KR_DECODE_FAST, short cache: one launch
+    out_proj(cx, L.o_wid, o_img);
+    return KR_OK;
+}
+
+// LoRA query path: q_a_proj output -> sequential RMSNorm -> q_b_proj (decode.rs:3036-3079)
+static void mla_lora_tail(StepCtx& cx, DLayer& L, float* q_full) {
+    kr_decode_store* s = cx.s; hipStream_t st = cx.st;
+    if (L.q_a_norm_len) PROF(PK_RMSNORM, kr_launch_rmsnorm_seq((float*)s->proj_b.p, (const float*)L.q_a_norm.p, s->weights[L.mqa_wid]->rows, s->eps, st));
+    PROF(PK_MATVEC, kr_launch_matvec(mv(s, L.mqb_wid), s->proj_b.p, 1, q_full, st));
+}
+
+// KR_DECODE_FAST keeps the attention launches themselves (absorb, scores, weighted sum, w_vc) in the reference's order; the o projection runs on the K-split tree-sum matvec
+static int attn_mla(StepCtx& cx, DLayer& L, size_t li) {
+    kr_decode_store* s = cx.s; hipStream_t st = cx.st;
+    if (!L.kv_k.p) return kr_fail(KR_ERR_STATE, "set_decode_state was not called (no MLA cache for layer %zu)", li);
+    if (L.mla_rope_seq < s->kv_max_seq) return kr_fail(KR_ERR_VALUE, "MLA rope table (%d) shorter than kv_max_seq (%d)", L.mla_rope_seq, s->kv_max_seq);
+    float* kv_out = (float*)s->kbuf.p; float* q_full = (float*)s->proj_a.p;
+    const bool lora = L.mq_wid < 0;
+    if (!cx.did_in) {      // kv_a_proj and the direct query projection (or q_a_proj) share the activation: one launch.  did_in: they came out of in_proj_fast
+        const int wids[2] = {L.kva_wid, lora ? L.mqa_wid : L.mq_wid};
+        float* ys[2] = {kv_out, lora ? (float*)s->proj_b.p : q_full};
+        proj_group(cx, wids, ys, 2, cx.hid, 1);
+    }
+    if (lora) mla_lora_tail(cx, L, q_full);
+    KrMlaArgs a{};
+    a.step = (const KrStep*)s->step_dev.p; a.kv_out = kv_out; a.q_full = q_full; a.kv_a_norm = (const float*)L.kv_a_norm.p; a.w_kc = (const float*)L.w_kc.p;
+    a.w_vc = (const float*)L.w_vc.p; a.rope_cos = (const float*)L.mla_cos.p; a.rope_sin = (const float*)L.mla_sin.p;
+    a.ckv_cache = L.kv_k.p; a.kpe_cache = L.kv_v.p; a.kv_fp8 = s->kv_fp8; a.q_abs = (float*)s->qbuf.p; a.q_pe = (float*)s->zbuf.p;
+    a.attn_lat = (float*)s->latbuf.p; a.v_proj = (float*)s->attn_out.p;
+    a.nh = L.nh; a.klr = L.klr; a.nd = L.nd; a.rd = L.rd; a.vhd = L.vhd; a.eps = s->eps; a.sm_scale = L.sm_scale;
+    a.sc_g = s->kv_max_seq > s->mla_split_min ? (float*)s->gqa_scores.p : nullptr;
+    if (s->attn_fast && a.sc_g) { a.fast = 1; a.fd_o = (float*)s->fd_o.p; a.fd_ml = (float*)s->fd_ml.p; }
+    a.decode_fast = cx.fast ? 1 : 0; a.decode_fused = cx.fast && s->opt_gqa_fused ? 1 : 0;
+    PROF(PK_GQA, kr_launch_mla(a, s->kv_max_seq, st));
+    if (cx.fast && s->weights[L.o_wid]->cols == L.nh * L.vhd) {      // o projection straight from the f32 w_vc output: every workgroup quantises it, K split over the waves
+        KrFdmArgs fo = fdm_one(s, 2, L.o_wid, cx.hid); fo.hid_in = (const float*)s->attn_out.p;
+        if (PROF_RC(PK_OUT_PROJ, kr_launch_fdm(fo, st)) == 0) return KR_OK;
+    }
+    out_proj(cx, L.o_wid, false);
+    return KR_OK;
+}
+
+// KR_DECODE_FAST MoE layer: norm + gate GEMV | select + gate|up + silu*up | down + combine -- three launches, the MoE output lands in `hid`.  On a native-GGUF
+// layer the routed slots of the gate|up and down launches walk the GGUF blocks (kr_gguf_dev.h: the block kernels' products, a row's blocks split over two waves),
+// the shared expert keeps its transposed form.  *done stays false when the geometry is not covered or the router launch refuses: the exact launches follow.
+// Expert-parallel (transposed experts only; mlp() refuses EP on a GGUF layer): every rank's down launch leaves its PARTIAL combine (rsf * sum over its own slots;
+// the layer's shared expert is evaluated by ONE rank, layer mod world, and added there) in the hidden buffer and ONE all-reduce of [hidden] f32 per MoE layer sums
+// the partials -- 1 / k of the bytes of the exact form, and no combine left for the next norm.  The sum order over the ranks is RCCL's: tolerance mode.
+static int fast_moe(StepCtx& cx, DLayer& L, Layer& EL, size_t li, bool* done) {
+    kr_decode_store* s = cx.s; kr_engine* e = cx.e; hipStream_t st = cx.st;
+    if (EL.gguf && cx.src.mode == 2) return KR_OK;
+    const MoeShape m = moe_shape(s, L, EL);
+    KrFmoeArgs fa{}; KrMoeArgs& a = fa.m;
+    moe_args_common(cx, L, m, a);
+    a.act_img = s->img_post.p; a.act_img_bf16 = s->img_post_bf16.p;
+    a.ids = (const int32_t*)s->r_ids.p; a.wts = (const float*)s->r_w.p;
+    a.topk = s->topk; a.n_slots = m.n_slots; a.I = EL.inter; a.gu = (float*)s->moe_gu.p; a.eo = (float*)s->moe_eo.p;
+    bool ok = true;
+    if (EL.gguf) {
+        fa.gguf = 1; fa.ggate = EL.g_gate.view(); fa.gup = EL.g_up.view(); fa.gdown = EL.g_down.view(); fa.act_f32 = (const float*)s->hid2.p;
+        a.E = e->cfg.n_routed_experts; ok = e->r_ne == e->cfg.n_routed_experts;
+    } else { a.E = e->r_ne; a.w13 = EL.w13.view(); a.w2 = EL.w2.view(); }
+    if (m.has_gate) {      // the sigmoid-gate row rides in the shared slot: the matrices of that launch must have one width
+        const KrMatDev sg = mv(s, L.sg_wid);
+        if (EL.gguf ? sg.bits == a.sw13.bits : (a.w13.bits == a.sw13.bits && sg.bits == a.w13.bits)) { a.sgate = sg; a.gate_out = (float*)s->gate_val.p; }
+        else ok = false;
+    }
+    fa.logits = (const float*)s->r_logits.p; fa.esc = route_esc(EL); fa.scoring = s->scoring; fa.norm_topk = s->norm_topk;
+    fa.hid_out = cx.hid;
+    if (cx.ep_dec) {
+        kr_ep_slice(e, &a.e_lo, &a.e_hi, &a.e_sub);
+        fa.shared_skip = m.has_shared && kr_ep_rank(e) != (int)(li % (size_t)kr_ep_world(e)) ? 1 : 0;
+    }
+    if (!ok || kr_fmoe_check(fa) != 0) return KR_OK;
+    if (PROF_RC(PK_ROUTE_LOGITS, kr_launch_frt(frt_args(cx, L, EL), st)) != 0) return KR_OK;
+    // kr_fmoe_check above covers every refusal of these two launchers; a non-zero return here would leave the layer half-run
+    const int r13 = PROF_RC(PK_MOE_W13, kr_launch_fw13(fa, st));
+    const int r2 = PROF_RC(PK_MOE_W2, kr_launch_fw2(fa, st));
+    if ((r13 || r2) && EL.gguf) return kr_fail(KR_ERR_STATE, "internal: KR_DECODE_FAST expert launch refused after kr_fmoe_check accepted GGUF layer %zu", li);
+    if (r13 || r2) return kr_fail(KR_ERR_STATE, "internal: KR_DECODE_FAST expert launch refused after kr_fmoe_check accepted layer %zu", li);
+    if (cx.ep_dec) if (int rc = kr_ep_allreduce_on(e, cx.hid, (size_t)cx.H, st)) return rc;
+    cx.res_cur = cx.other(); cx.src = KrNormSrc{}; *done = true;
+    return KR_OK;
+}
+
+// KR_DECODE_FAST on a dense MLP layer (V2-Lite's first, decode.rs:1693-1741; round 6): the post-attention add + RMSNorm folded into the gate | up projection launch
+// (every workgroup rebuilds the normalised vector with tree sums, as the attention in-projections of the mode do); the down projection keeps the exact kernel with
+// its silu * up + INT16 prologue -- its K (10 944) is beyond what a folded prologue holds.  false: not taken, the caller runs the exact launches
+static bool dense_fast(StepCtx& cx, DLayer& L) {
+    kr_decode_store* s = cx.s; hipStream_t st = cx.st;
+    const KrMatDev g = mv(s, L.gate_wid), u = mv(s, L.up_wid);
+    const int K = s->weights[L.down_wid]->cols;
+    if (!(g.bits == u.bits && (g.bits == 4 || g.bits == 8))) return false;
+    KrFdmArgs fd = fdm_one(s, 1, L.gate_wid, (float*)s->dense_gu.p);
+    fdm_norm(cx, L.post_norm, fd);
+    fd.mm.n = 2; fd.mm.m[1] = u; fd.mm.y[1] = (float*)s->dense_gu.p + K; fd.mm.tile_end[1] = fd.mm.tile_end[0] + (u.N + 7) / 8;
+    if (PROF_RC(PK_MATVEC, kr_launch_fdm(fd, st)) != 0) return false;
+    cx.res_cur = cx.other();
+    PROF(PK_MATVEC, kr_launch_matvec(mv(s, L.down_wid), s->dense_gu.p, 1, cx.hid, st, KR_ACT_SILU_MUL));
+    return true;
+}
+
+// NATIVE GGUF EXPERTS in the exact decode step.  The reference's Rust decode_step always calls moe_forward_unified (decode.rs:3334), its
+// native-GGUF layers decode through the per-layer Python loop -> moe_forward_gguf (moe.rs:990-1110, tests/test_gguf_native.py:47-57).  Here the same
+// arithmetic sits inside the captured step: the k routed experts through the block kernels of kr_gguf.hip on bf16(hidden) (per-32 INT16 activations, exact
+// integer dots, the AVX2 kernel's 8 lane chains + hsum per row: bit-equal to kr_moe_forward = the oracle's moe_forward_gguf); the decode store's shared
+// expert (INT4 / INT8 transposed, f32 hidden, decode.rs:3356-3378) as slot k of the same row buffer; weighted sum in routing order, rsf and
+// shared * sigmoid(gate) in the next fused add+RMSNorm, as for transposed experts.
+static int moe_exact_gguf(StepCtx& cx, DLayer& L, Layer& EL, const float* act, bool routed) {
+    kr_decode_store* s = cx.s; kr_engine* e = cx.e; hipStream_t st = cx.st;
+    const MoeShape m = moe_shape(s, L, EL);
+    const int k = s->topk, H = cx.H;
+    GgMoeArgs g{};
+    g.B = 1; g.topk = k; g.n_slots = k; g.H = H; g.E = e->cfg.n_routed_experts; g.act_f32 = act; g.ids = (const int32_t*)s->r_ids.p;
+    g.gate = EL.g_gate.view(); g.up = EL.g_up.view(); g.down = EL.g_down.view();
+    g.I_max = EL.inter; g.gu_ld = 2 * m.imax;       // row pitch of the shared gate|up scratch below
+    g.gu = (float*)s->moe_gu.p; g.eo = (float*)s->moe_eo.p;
+    PROF(PK_MOE_W13, kr_launch_gguf_moe(g, st));
+    if (m.has_shared) {
+        KrMoeArgs a{};
+        moe_args_common(cx, L, m, a);
+        a.act_f32 = act; if (routed && cx.img_ok()) { a.act_img = s->img_post.p; a.act_img_bf16 = s->img_post_bf16.p; }
+        a.topk = 0; a.n_slots = 1; a.E = 0; a.I = m.I_shared;
+        a.w13 = a.sw13; a.w2 = a.sw2;      // launch geometry follows w13 / w2 (bits, K); slot 0 is the shared slot
+        a.gu = g.gu + (size_t)k * g.gu_ld; a.eo = g.eo + (size_t)k * H;
+        const bool fuse_gate = m.has_gate && mv(s, L.sg_wid).bits == a.sw13.bits;      // the sigmoid-gate row rides in the shared slot's gate|up launch
+        if (fuse_gate) { a.sgate = mv(s, L.sg_wid); a.gate_out = (float*)s->gate_val.p; }
+        PROF(PK_MOE_W13, kr_launch_moe_w13(a, st));
+        if (m.has_gate && !fuse_gate) PROF(PK_SHARED_GATE, kr_launch_matvec(mv(s, L.sg_wid), act, 1, (float*)s->gate_val.p, st));
+        PROF(PK_MOE_W2, kr_launch_moe_w2(a, st));
+    }
+    if (cx.fast) {      // KR_DECODE_FAST: the combine as its own small launch into `hid`, so that the next layer's folded norm + projection launch applies
+        PROF(PK_MOE_COMBINE, kr_launch_moe_combine_decode(g.eo, g.ids, (const float*)s->r_w.p, k, m.has_shared ? 1 : 0, m.has_gate ? (const float*)s->gate_val.p : nullptr, s->rsf, cx.hid, H, st));
+        cx.src = KrNormSrc{};
+    } else cx.src = norm_src_moe(s, m);
+    return KR_OK;
+}
+
+// exact MoE on transposed experts.  Expert-parallel decode: router, attention, norms and the shared expert are replicated; every rank runs the routed experts of ITS slice and the k
+// expert rows are summed over the ranks (each row is non-zero on exactly one rank, so the sum is exact: logits equal single-engine decode bit for bit) before
+// the combine in routing order.  Reference analogue: python/krasis/gpu_prefill.py:3700-3790 (local subset + partial-sum reduce).
+static int moe_exact(StepCtx& cx, DLayer& L, Layer& EL, const float* act, bool routed) {
+    kr_decode_store* s = cx.s; kr_engine* e = cx.e; hipStream_t st = cx.st;
+    const MoeShape m = moe_shape(s, L, EL);
+    const int k = s->topk, H = cx.H;
+    KrMoeArgs a{};
+    moe_args_common(cx, L, m, a);
+    a.act_f32 = act; if (routed && cx.img_ok()) { a.act_img = s->img_post.p; a.act_img_bf16 = s->img_post_bf16.p; }
+    a.ids = (const int32_t*)s->r_ids.p; a.wts = (const float*)s->r_w.p;
+    a.topk = k; a.n_slots = m.n_slots; a.E = e->r_ne; a.I = EL.inter; a.gu = (float*)s->moe_gu.p; a.eo = (float*)s->moe_eo.p;
+    a.w13 = EL.w13.view(); a.w2 = EL.w2.view();
+    // the shared expert's sigmoid-gate row rides in the shared slot's w13 launch when routed, shared and gate weights have one width
+    const bool fuse_gate = m.has_gate && a.w13.bits == a.sw13.bits && mv(s, L.sg_wid).bits == a.w13.bits;
+    if (fuse_gate) { a.sgate = mv(s, L.sg_wid); a.gate_out = (float*)s->gate_val.p; }
+    const float* gate_val = m.has_gate ? (const float*)s->gate_val.p : nullptr;
+    if (cx.ep_dec) {
+        kr_ep_slice(e, &a.e_lo, &a.e_hi, &a.e_sub);
+        KR_HIP(hipMemsetAsync(a.eo, 0, (size_t)k * H * 4, st));          // rows of experts other ranks own stay 0
+    }
+    PROF(PK_MOE_W13, kr_launch_moe_w13(a, st));
+    if (m.has_gate && !fuse_gate) PROF(PK_SHARED_GATE, kr_launch_matvec(mv(s, L.sg_wid), act, 1, (float*)s->gate_val.p, st));
+    if (!cx.ep_dec && s->opt_w2_combine) {      // stage 2 + the routing-order combine in one launch: the MoE output lands in `hid`, the next norm launch reads it like any hidden vector
+        if (PROF_RC(PK_MOE_W2, kr_launch_moe_w2c(a, gate_val, cx.hid, st)) == 0) { cx.src = KrNormSrc{}; return KR_OK; }
+    }
+    PROF(PK_MOE_W2, kr_launch_moe_w2(a, st));
+    if (cx.ep_dec) if (int rc = kr_ep_allreduce_on(e, a.eo, (size_t)k * H, st)) return rc;    // the shared expert's row (slot k) is replicated, not reduced
+    cx.src = norm_src_moe(s, m);
+    return KR_OK;
+}
+
+// post-attention fused add+RMSNorm + the MLP block: the norm is folded into the router launch of MoE layers (or into the mode's launches), its own launch otherwise
+static int mlp(StepCtx& cx, DLayer& L, size_t li) {
+    kr_decode_store* s = cx.s; kr_engine* e = cx.e; hipStream_t st = cx.st;
+    const float* act = cx.hid;   // normalised hidden the MLP block reads
+    bool routed = false;
+    Layer* EL = nullptr;
+    if (L.mlp == MLP_MOE) {
+        if (s->own_eng || L.moe_layer >= (int)e->layers.size()) return kr_fail(KR_ERR_STATE, "set_moe_store was not called (MoE layer %d has no engine)", L.moe_layer);
+        EL = &e->layers[L.moe_layer];
+        if (!EL->routing_present) return kr_fail(KR_ERR_STATE, "Routing weights not set for layer %d", L.moe_layer);
+        if (!EL->w13.allocated() && !EL->gguf) return kr_fail(KR_ERR_STATE, "Model not loaded (MoE layer %d has no experts)", L.moe_layer);
+        if (EL->gguf && cx.ep_dec) return kr_fail(KR_ERR_STATE, "expert-parallel decode on native GGUF layers is not implemented (MoE layer %d)", L.moe_layer);
+        if (cx.fast) {
+            bool moe_done = false;
+            if (int rc = fast_moe(cx, L, *EL, li, &moe_done)) return rc;
+            if (moe_done) return KR_OK;
+            // for GGUF geometries fast_moe does not cover: the mode's norm + gate GEMV launch and the stand-alone select in front of the (exact) block kernels
+            if (EL->gguf && cx.src.mode != 2 && PROF_RC(PK_ROUTE_LOGITS, kr_launch_frt(frt_args(cx, L, *EL), st)) == 0) {
+                launch_select(cx, *EL);
+                routed = true; act = (const float*)s->hid2.p; cx.res_cur = cx.other();
             }
         }
-        if (!routed) PROF(PK_RMSNORM, kr_launch_fused_add_rmsnorm(src, hid, res_cur, res_cur, (const float*)s->norms[L.post_norm]->p, H, s->eps, 0, s->norm_bias_one, st));
-        if (L.mlp == MLP_MOE) {
-            Layer& EL = e->layers[L.moe_layer];
-            const int E = e->r_ne, k = s->topk;
-            if (!routed) {
-                PROF(PK_ROUTE_LOGITS, kr_launch_route_logits_decode(EL.gate_cm.p, EL.gate_bf16_exact, hid, EL.has_bias ? (const float*)EL.bias.p : nullptr, (float*)s->r_logits.p, 1, E, H, st));
-                PROF(PK_ROUTE_SELECT, kr_launch_route_select((const float*)s->r_logits.p, EL.has_esc ? (const float*)EL.esc.p : nullptr, (int32_t*)s->r_ids.p, (float*)s->r_w.p, 1, E, k,
-                                       s->scoring, s->norm_topk, KR_ROUTE_RULE_DECODE, 0, st));
-            }
-            const bool has_shared = L.sgu_wid >= 0;
-            const bool has_gate = has_shared && L.sg_wid >= 0;
-            if (EL.gguf) {
-                // NATIVE GGUF EXPERTS in the decode step.  The reference's Rust decode_step always calls moe_forward_unified (decode.rs:3334), its
-                // native-GGUF layers decode through the per-layer Python loop -> moe_forward_gguf (moe.rs:990-1110, tests/test_gguf_native.py:47-57).  Here the same
-                // arithmetic sits inside the captured step: router as above; the k routed experts through the block kernels of kr_gguf.hip on bf16(hidden)
-                // (per-32 INT16 activations, exact integer dots, the AVX2 kernel's 8 lane chains + hsum per row: bit-equal to kr_moe_forward = the oracle's
-                // moe_forward_gguf); the decode store's shared expert (INT4 / INT8 transposed, f32 hidden, decode.rs:3356-3378) as slot k of the same row
-                // buffer; weighted sum in routing order, rsf and shared * sigmoid(gate) in the next fused add+RMSNorm, as for transposed experts.
-                GgMoeArgs g{};
-                g.B = 1; g.topk = k; g.n_slots = k; g.H = H; g.E = e->cfg.n_routed_experts; g.act_f32 = act; g.ids = (const int32_t*)s->r_ids.p;
-                g.gate = EL.g_gate.view(); g.up = EL.g_up.view(); g.down = EL.g_down.view();
-                const int sI = has_shared ? s->weights[L.sgu_wid]->rows / 2 : 0;
-                g.I_max = EL.inter; g.gu_ld = 2 * (sI > EL.inter ? sI : EL.inter);       // row pitch of the shared gate|up scratch below
-                g.gu = (float*)s->moe_gu.p; g.eo = (float*)s->moe_eo.p;
-                prof_mark(s, PK_MOE_W13, st);
-                kr_launch_gguf_moe(g, st);
-                prof_mark(s, -1, st);
-                if (has_shared) {
-                    KrMoeArgs a{};
-                    a.act_f32 = act; a.shared_decode = 1; if (routed && img_ok) { a.act_img = s->img_post.p; a.act_img_bf16 = s->img_post_bf16.p; }
-                    a.B = 1; a.topk = 0; a.n_slots = 1; a.E = 0; a.H = H; a.I = sI; a.I_shared = sI;
-                    a.sw13 = mv(s, L.sgu_wid); a.sw2 = mv(s, L.sd_wid); a.w13 = a.sw13; a.w2 = a.sw2;      // launch geometry follows w13 / w2 (bits, K); slot 0 is the shared slot
-                    a.gu_ld = g.gu_ld; a.gu = g.gu + (size_t)k * g.gu_ld; a.eo = g.eo + (size_t)k * H;
-                    a.rsf = s->rsf; a.swiglu_limit = e->cfg.swiglu_limit; a.alpha = e->cfg.activation_alpha;
-                    a.act_mode = e->cfg.swiglu_limit > 0.0f ? KR_ACT_GPTOSS : KR_ACT_SILU_FUSED;
-                    const bool fuse_gate = has_gate && mv(s, L.sg_wid).bits == a.sw13.bits;      // the sigmoid-gate row rides in the shared slot's gate|up launch
-                    if (fuse_gate) { a.sgate = mv(s, L.sg_wid); a.gate_out = (float*)s->gate_val.p; }
-                    PROF(PK_MOE_W13, kr_launch_moe_w13(a, st));
-                    if (has_gate && !fuse_gate) PROF(PK_SHARED_GATE, kr_launch_matvec(mv(s, L.sg_wid), act, 1, (float*)s->gate_val.p, st));
-                    PROF(PK_MOE_W2, kr_launch_moe_w2(a, st));
-                }
-                if (fast) {      // KR_DECODE_FAST: the combine as its own small launch into `hid`, so that the next layer's folded norm + projection launch applies
-                    PROF(PK_MOE_COMBINE, kr_launch_moe_combine_decode(g.eo, g.ids, (const float*)s->r_w.p, k, has_shared ? 1 : 0, has_gate ? (const float*)s->gate_val.p : nullptr, s->rsf, hid, H, st));
-                    src = from_hidden;
-                    continue;
-                }
-                src = KrNormSrc{}; src.mode = 2; src.eo = g.eo; src.ids = g.ids; src.wts = (const float*)s->r_w.p; src.topk = k; src.has_shared = has_shared ? 1 : 0;
-                src.gate_val = has_gate ? (const float*)s->gate_val.p : nullptr; src.rsf = s->rsf;
-                continue;
-            }
-            KrMoeArgs a{};
-            a.act = nullptr; a.act_f32 = act; a.shared_decode = 1;
-            if (routed && img_ok) { a.act_img = s->img_post.p; a.act_img_bf16 = s->img_post_bf16.p; }
-            a.ids = (const int32_t*)s->r_ids.p; a.wts = (const float*)s->r_w.p;
-            a.B = 1; a.topk = k; a.n_slots = k + (has_shared ? 1 : 0); a.E = E; a.H = H; a.I = EL.inter;
-            a.w13 = EL.w13.view(); a.w2 = EL.w2.view();
-            if (has_shared) { a.sw13 = mv(s, L.sgu_wid); a.sw2 = mv(s, L.sd_wid); a.I_shared = s->weights[L.sgu_wid]->rows / 2; }
-            const int imax = has_shared && a.I_shared > a.I ? a.I_shared : a.I;
-            a.gu_ld = 2 * imax;
-            a.gu = (float*)s->moe_gu.p; a.eo = (float*)s->moe_eo.p; a.out = nullptr; a.out_bf16 = 0;
-            a.rsf = s->rsf; a.swiglu_limit = e->cfg.swiglu_limit; a.alpha = e->cfg.activation_alpha;
-            a.act_mode = e->cfg.swiglu_limit > 0.0f ? KR_ACT_GPTOSS : KR_ACT_SILU_FUSED;
-            // the shared expert's sigmoid-gate row rides in the shared slot's w13 launch when routed, shared and gate weights have one width
-            const bool fuse_gate = has_gate && a.w13.bits == a.sw13.bits && mv(s, L.sg_wid).bits == a.w13.bits;
-            if (fuse_gate) { a.sgate = mv(s, L.sg_wid); a.gate_out = (float*)s->gate_val.p; }
-            if (ep_dec) {
-                kr_ep_slice(e, &a.e_lo, &a.e_hi, &a.e_sub);
-                KR_HIP(hipMemsetAsync(a.eo, 0, (size_t)k * H * 4, st));          // rows of experts other ranks own stay 0
-            }
-            PROF(PK_MOE_W13, kr_launch_moe_w13(a, st));
-            if (has_gate && !fuse_gate) PROF(PK_SHARED_GATE, kr_launch_matvec(mv(s, L.sg_wid), act, 1, (float*)s->gate_val.p, st));
-            if (!ep_dec && s->opt_w2_combine) {      // stage 2 + the routing-order combine in one launch: the MoE output lands in `hid`, the next norm launch reads it like any hidden vector
-                prof_mark(s, PK_MOE_W2, st);
-                const bool done = 0 == kr_launch_moe_w2c(a, has_gate ? (const float*)s->gate_val.p : nullptr, hid, st);
-                prof_mark(s, -1, st);
-                if (done) { src = from_hidden; continue; }
-            }
-            PROF(PK_MOE_W2, kr_launch_moe_w2(a, st));
-            if (ep_dec) if (int rc = kr_ep_allreduce_on(e, a.eo, (size_t)k * H, st)) return rc;    // the shared expert's row (slot k) is replicated, not reduced
-            // epilogue (weighted sum, rsf, shared * sigmoid(gate)) is folded into the next fused add+RMSNorm
-            src = KrNormSrc{}; src.mode = 2; src.eo = a.eo; src.ids = a.ids; src.wts = a.wts; src.topk = k; src.has_shared = has_shared ? 1 : 0;
-            src.gate_val = has_gate ? (const float*)s->gate_val.p : nullptr; src.rsf = s->rsf;
-        } else if (L.mlp == MLP_DENSE) {
-            // gate / up into [0,K) and [K,2K) of dense_gu (K = padded intermediate), then down with the fused silu*up + quant prologue
-            const int K = s->weights[L.down_wid]->cols;
-            const KrMatDev mats[2] = {mv(s, L.gate_wid), mv(s, L.up_wid)};
-            float* ys[2] = {(float*)s->dense_gu.p, (float*)s->dense_gu.p + K};
-            if (mats[0].bits == mats[1].bits) PROF(PK_MATVEC, kr_launch_multi_matvec(mats, ys, 2, hid, 1, st));
-            else { PROF(PK_MATVEC, kr_launch_matvec(mats[0], hid, 1, ys[0], st)); PROF(PK_MATVEC, kr_launch_matvec(mats[1], hid, 1, ys[1], st)); }
-            PROF(PK_MATVEC, kr_launch_matvec(mv(s, L.down_wid), s->dense_gu.p, 1, hid, st, KR_ACT_SILU_MUL));
+        if (!routed) {      // norm + router logits + top-k in one launch: hid2 / the other residual buffer are its outputs (its inputs stay readable for every workgroup)
+            routed = 0 == PROF_RC(PK_ROUTE_LOGITS, kr_launch_route_fused_decode(EL->gate_cm.p, EL->gate_bf16_exact, route_bias(*EL), (float*)s->r_logits.p,
+                                                       (unsigned*)s->r_counter.p, route_esc(*EL), (int32_t*)s->r_ids.p,
+                                                       (float*)s->r_w.p, e->r_ne, cx.H, s->topk, s->scoring, s->norm_topk, nullptr, cx.hid, cx.res_cur,
+                                                       (const float*)s->norms[L.post_norm]->p, (float*)s->hid2.p, cx.other(), s->eps,
+                                                       s->norm_bias_one, st, cx.img_ok() ? s->img_post.p : nullptr, cx.img_ok() ? s->img_post_bf16.p : nullptr));
+            if (routed) { act = (const float*)s->hid2.p; cx.res_cur = cx.other(); }
         }
     }
-    const bool lm_img = false;   // the vocabulary projection is wide enough that per-wave tiles beat the cooperative form (measured)
+    if (cx.fast && !routed && L.mlp == MLP_DENSE && cx.src.mode == 0 && s->opt_dense_fast && dense_fast(cx, L)) return KR_OK;
+    if (!routed) PROF(PK_RMSNORM, kr_launch_fused_add_rmsnorm(cx.src, cx.hid, cx.res_cur, cx.res_cur, (const float*)s->norms[L.post_norm]->p, cx.H, s->eps, 0, s->norm_bias_one, st));
+    if (L.mlp == MLP_MOE) {
+        if (!routed) {
+            PROF(PK_ROUTE_LOGITS, kr_launch_route_logits_decode(EL->gate_cm.p, EL->gate_bf16_exact, cx.hid, route_bias(*EL), (float*)s->r_logits.p, 1, e->r_ne, cx.H, st));
+            launch_select(cx, *EL);
+        }
+        return EL->gguf ? moe_exact_gguf(cx, L, *EL, act, routed) : moe_exact(cx, L, *EL, act, routed);
+    }
+    if (L.mlp == MLP_DENSE) {
+        // gate / up into [0,K) and [K,2K) of dense_gu (K = padded intermediate), then down with the fused silu*up + quant prologue
+        const int K = s->weights[L.down_wid]->cols;
+        const int wids[2] = {L.gate_wid, L.up_wid};
+        float* ys[2] = {(float*)s->dense_gu.p, (float*)s->dense_gu.p + K};
+        proj_group(cx, wids, ys, 2, cx.hid, 1);
+        PROF(PK_MATVEC, kr_launch_matvec(mv(s, L.down_wid), s->dense_gu.p, 1, cx.hid, st, KR_ACT_SILU_MUL));
+    }
+    return KR_OK;
+}
+
+// final norm + vocabulary projection (wide enough that per-wave tiles on the f32 vector beat the cooperative image form: measured) + greedy argmax
+static int final_head(StepCtx& cx) {
+    kr_decode_store* s = cx.s; hipStream_t st = cx.st;
     bool lm_done = false;
-    if (fast && s->opt_lm_fused && src.mode == 0 && !first) {
+    if (cx.fast && s->opt_lm_fused && cx.src.mode == 0 && !cx.first) {
         // KR_DECODE_FAST: final norm + vocabulary projection as ONE launch of the projection kernel (the norm folded into every workgroup, tree sums) --
         // one launch and one boundary less per token
-        const KrMatDev lm = mv(s, s->lm_head);
-        if (lm.bits == 4 || lm.bits == 8) {
-            KrFdmArgs fl{};
-            fl.mode = 1; fl.hid_in = hid; fl.res_in = res_cur; fl.res_out = other(res_cur); fl.norm_w = (const float*)s->norms[s->final_norm]->p;
-            fl.eps = s->eps; fl.bias_one = s->norm_bias_one;
-            fl.mm.n = 1; fl.mm.m[0] = lm; fl.mm.y[0] = (float*)s->logits.p; fl.mm.tile_end[0] = (lm.N + 7) / 8;
-            prof_mark(s, PK_LM_HEAD, st);
-            lm_done = 0 == kr_launch_fdm(fl, st);
-            prof_mark(s, -1, st);
+        const int bits = mv(s, s->lm_head).bits;
+        if (bits == 4 || bits == 8) {
+            KrFdmArgs fl = fdm_one(s, 1, s->lm_head, (float*)s->logits.p);
+            fdm_norm(cx, s->final_norm, fl);
+            lm_done = 0 == PROF_RC(PK_LM_HEAD, kr_launch_fdm(fl, st));
         }
     }
     if (!lm_done) {
-        PROF(PK_RMSNORM, kr_launch_fused_add_rmsnorm(src, hid, res_cur, res, (const float*)s->norms[s->final_norm]->p, H, s->eps, first ? 1 : 0, s->norm_bias_one, st,
-                                                     lm_img ? s->img_in.p : nullptr));
-        if (lm_img) PROF(PK_LM_HEAD, kr_launch_matvec(mv(s, s->lm_head), s->img_in.p, 2, (float*)s->logits.p, st));
-        else PROF(PK_LM_HEAD, kr_launch_matvec(mv(s, s->lm_head), hid, 1, (float*)s->logits.p, st));
+        PROF(PK_RMSNORM, kr_launch_fused_add_rmsnorm(cx.src, cx.hid, cx.res_cur, cx.res, (const float*)s->norms[s->final_norm]->p, cx.H, s->eps, cx.first ? 1 : 0, s->norm_bias_one, st));
+        PROF(PK_LM_HEAD, kr_launch_matvec(mv(s, s->lm_head), cx.hid, 1, (float*)s->logits.p, st));
     }
     PROF(PK_ARGMAX, kr_launch_argmax((const float*)s->logits.p, s->vocab, (int*)s->tok.p, (float*)s->argmax_scratch.p, st));
     KR_HIP(hipGetLastError());
     return KR_OK;
+}
+
+static int enqueue_step(kr_decode_store* s, hipStream_t st) {
+    StepCtx cx{};
+    cx.s = s; cx.e = s->eng; cx.st = st; cx.H = s->hidden;
+    cx.hid = (float*)s->hid.p; cx.res = (float*)s->res.p; cx.res_b = (float*)s->res2.p; cx.res_cur = cx.res;
+    cx.src.mode = 1; cx.src.emb = (const float*)s->embedding.p; cx.src.step = (const KrStep*)s->step_dev.p;
+    cx.first = true; cx.ep_dec = kr_ep_decode_active(cx.e);
+    cx.fast = s->decode_fast && cx.H % 128 == 0 && cx.H <= 4096 && s->f_qk.p;
+    for (size_t li = 0; li < s->layers.size(); li++) {
+        DLayer& L = s->layers[li];
+        cx.in_img = false;
+        if (cx.img_ok()) {
+            if (L.attn == ATTN_LA) cx.in_img = img_w(s, L.qkvz_wid) && img_w(s, L.ba_wid, L.qkvz_wid);
+            else if (L.attn == ATTN_GQA) cx.in_img = img_w(s, L.q_wid) && img_w(s, L.k_wid, L.q_wid) && img_w(s, L.v_wid, L.q_wid);
+        }
+        in_proj_fast(cx, L);
+        if (!cx.did_in) {
+            PROF(PK_RMSNORM, kr_launch_fused_add_rmsnorm(cx.src, cx.hid, cx.res_cur, cx.res, (const float*)s->norms[L.input_norm]->p, cx.H, s->eps, cx.first ? 1 : 0, s->norm_bias_one, st,
+                                                         cx.in_img ? s->img_in.p : nullptr));
+            cx.res_cur = cx.res;
+        }
+        cx.first = false; cx.src = KrNormSrc{};   // mode 0: the attention output in the hidden buffer
+        int rc = KR_OK;
+        if (L.attn == ATTN_LA) rc = attn_la(cx, L);
+        else if (L.attn == ATTN_GQA) rc = attn_gqa(cx, L, li);
+        else if (L.attn == ATTN_MLA) rc = attn_mla(cx, L, li);
+        if (rc) return rc;
+        if (int rc2 = mlp(cx, L, li)) return rc2;
+    }
+    return final_head(cx);
 }
 
 // token == KR_TOKEN_FROM_DEVICE: the step's token is whatever the previous step's sampler left in s->tok (always a valid id)
@@ -1060,10 +1069,8 @@ static int decode_step_on(kr_decode_store* s, int token_id, int position, float*
         kr_engine* e = s->eng; size_t gu = 0, eo = 0;
         for (auto& L : s->layers) if (L.mlp == MLP_MOE) {
             if (s->own_eng || L.moe_layer >= (int)e->layers.size()) return kr_fail(KR_ERR_STATE, "set_moe_store was not called (MoE layer %d has no engine)", L.moe_layer);
-            Layer& EL = e->layers[L.moe_layer];
-            const int sI = L.sgu_wid >= 0 ? s->weights[L.sgu_wid]->rows / 2 : 0;
-            const int imax = sI > EL.inter ? sI : EL.inter; const int ns = s->topk + (L.sgu_wid >= 0 ? 1 : 0);
-            gu = maxz(gu, (size_t)ns * 2 * imax * 4); eo = maxz(eo, (size_t)ns * s->hidden * 4);
+            const MoeShape m = moe_shape(s, L, e->layers[L.moe_layer]);
+            gu = maxz(gu, (size_t)m.n_slots * 2 * m.imax * 4); eo = maxz(eo, (size_t)m.n_slots * s->hidden * 4);
         }
         if (gu && (gu > s->moe_gu.bytes || eo > s->moe_eo.bytes || (size_t)e->r_ne * 4 > s->r_logits.bytes)) s->graph_ok = false;
         if (gu && (s->moe_gu.ensure(gu) || s->moe_eo.ensure(eo) || s->r_logits.ensure((size_t)e->r_ne * 4) || s->r_ids.ensure(256) || s->r_w.ensure(256)))
@@ -1117,6 +1124,15 @@ extern "C" int kr_sample_order(const float* logits_host, int vocab, int top_k, i
     return KR_OK;
 }
 
+// the sampler on the logits of the last step: token into s->tok, seen bitmap and RNG state advanced
+static int sample_last(kr_decode_store* s, float temperature, int top_k, float top_p, float penalty, hipStream_t st) {
+    uint64_t* keys = (uint64_t*)s->smp_keys.p;
+    if (kr_launch_sample((float*)s->logits.p, s->vocab, temperature, top_k, top_p, penalty, (uint32_t*)s->smp_seen.p, keys, keys + s->vocab,
+                         s->smp_temp.p, s->smp_temp_bytes, (float*)s->smp_probs.p, (uint64_t*)s->smp_rng.p, (int*)s->tok.p, st))
+        return kr_fail(KR_ERR_HIP, "device radix sort failed");
+    return KR_OK;
+}
+
 extern "C" int kr_decode_sample(kr_decode_store* s, float temperature, int top_k, float top_p, float presence_penalty, uint64_t rng_seed,
                                 int reset_seen, int* token_out, void* stream) {
     if (int rc = need_cfg(s)) return rc;
@@ -1129,12 +1145,7 @@ extern "C" int kr_decode_sample(kr_decode_store* s, float temperature, int top_k
     if (temperature == 0.0f) {
         if (presence_penalty != 0.0f) return kr_fail(KR_ERR_VALUE, "presence_penalty with greedy sampling goes through kr_decode_generate");
         kr_launch_argmax((const float*)s->logits.p, s->vocab, (int*)s->tok.p, (float*)s->argmax_scratch.p, st);
-    } else {
-        uint64_t* keys = (uint64_t*)s->smp_keys.p;
-        if (kr_launch_sample((float*)s->logits.p, s->vocab, temperature, top_k, top_p, presence_penalty, (uint32_t*)s->smp_seen.p, keys, keys + s->vocab,
-                             s->smp_temp.p, s->smp_temp_bytes, (float*)s->smp_probs.p, (uint64_t*)s->smp_rng.p, (int*)s->tok.p, st))
-            return kr_fail(KR_ERR_HIP, "device radix sort failed");
-    }
+    } else if (int rc = sample_last(s, temperature, top_k, top_p, presence_penalty, st)) return rc;
     if (token_out) { KR_HIP(hipMemcpyAsync(token_out, s->tok.p, 4, hipMemcpyDeviceToHost, st)); KR_HIP(hipStreamSynchronize(st)); }
     return KR_OK;
 }
@@ -1167,12 +1178,8 @@ static int generate_core(kr_decode_store* s, int first_token, int start_pos, int
     // one decode step + the sampler; token < 0: the step consumes the token the previous sampler left on the device
     auto step_and_sample = [&](int token, int pos) -> int {
         if (int rc = decode_step_on(s, token, pos, nullptr, st)) return rc;     // graph replay ends with the greedy argmax into s->tok
-        if (sampled) {
-            uint64_t* keys = (uint64_t*)s->smp_keys.p;
-            if (kr_launch_sample((float*)s->logits.p, s->vocab, temperature, top_k, top_p, presence_penalty, (uint32_t*)s->smp_seen.p, keys, keys + s->vocab,
-                                 s->smp_temp.p, s->smp_temp_bytes, (float*)s->smp_probs.p, (uint64_t*)s->smp_rng.p, (int*)s->tok.p, st))
-                return kr_fail(KR_ERR_HIP, "device radix sort failed");
-        } else if (penal) {   // greedy with a presence penalty: penalise, then first maximum
+        if (sampled) { if (int rc = sample_last(s, temperature, top_k, top_p, presence_penalty, st)) return rc; }
+        else if (penal) {   // greedy with a presence penalty: penalise, then first maximum
             kr_launch_penalty((float*)s->logits.p, s->vocab, presence_penalty, (const uint32_t*)s->smp_seen.p, st);
             kr_launch_argmax((const float*)s->logits.p, s->vocab, (int*)s->tok.p, (float*)s->argmax_scratch.p, st);
             kr_launch_mark_seen((uint32_t*)s->smp_seen.p, (const int*)s->tok.p, 0, st);

@@ -69,7 +69,7 @@ struct kr_decode_store {
     DevBuf dense_gu;  // [gate(K) | up(K)] of the dense MLP; only [0,inter) of each half is ever written, the padding stays 0
     DevBuf hid2, res2, r_counter, argmax_scratch;
     int kv_fp8 = 0;            // GQA KV element type: 0 FP16 (reference CPU decode), 1 FP8-E4M3 (reference GPU cache dtype)
-    DevBuf img_in, img_post, img_post_bf16, img_attn; bool use_images = true;   // pre-built INT16 activation images (input norm, post-attention norm f32 / bf16, attention output)
+    DevBuf img_in, img_post, img_post_bf16, img_attn;   // pre-built INT16 activation images (input norm, post-attention norm f32 / bf16, attention output)
     int opt_gqa_stream = 0, opt_pfm_timing = 0, opt_norm_rows = 1, opt_la_conv_fused = 1, opt_gqa_fused = 1, opt_lm_fused = 1, opt_la_heads = 1, opt_w2_combine = 1, opt_dense_fast = 1;   // kr_decode_set_option: test / tuning hooks (no environment lookups on launch paths)
     int opt_multi_sample_loop = 0;               // kr_decode_set_option("multi_sample_loop"): every sampled row of a multi-sequence step takes the single-row sampler, one row after another (A/B and test hook; same tokens)
     int opt_multi_attn_fast = 0;                 // kr_decode_set_option("multi_attn_fast"): the GQA layers of every batched multi-sequence step run split-KV flash-decode over slots longer than gqa_split_min (tolerance form, docs/design/16-multi-attn-fast.md); the mode bits stay refused
@@ -82,8 +82,6 @@ struct kr_decode_store {
     int gemm_fast = 0;                        // KR_GEMM_FAST: prompt-pass GEMMs in the tolerance form (kr_prefill_h.hip)
     int attn_fast = 0; DevBuf fd_o, fd_ml;   // KR_ATTN_FAST: split-KV softmax + p.v with a log-sum-exp merge for long caches (tolerance mode)
     DevBuf gqa_scores; int gqa_split_min = 1024, mla_split_min = 512;   // caches longer than this split decode attention into a scores launch + softmax / p.v launch
-    bool fuse_la = true;       // conv + recurrence + gated norm of a linear-attention layer in one launch (kr_la_step_kernel)
-    bool fuse_router = true;   // hid2/res2: outputs of the fused norm+router launch (its inputs stay readable for every workgroup)
     DevBuf smp_seen, smp_keys, smp_temp, smp_probs, smp_rng; size_t smp_temp_bytes = 0;   // sampler: seen bitmap, sort keys / scratch, probabilities, xorshift64 state
     DevBuf pf_scores;          // kr_decode_prefill: attention scores [chunk*nh rows][context] f32
     DevBuf pf_vlogits, pf_nll; // kr_decode_prefill_nll: [chunk, vocab] logits per arena; per-position negative log-likelihoods

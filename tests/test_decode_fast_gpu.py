@@ -16,7 +16,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle as O
-from tests.test_decode_gpu import build
+from tests.test_decode_gpu import MIXED, build
 
 pytestmark = pytest.mark.gpu
 F = np.float32
@@ -60,6 +60,7 @@ CFGS = [
     dict(with_dense=True),                                     # dense MLP layer: its post-attention norm folded into the gate | up launch (round 6); the down projection is the exact kernel
     dict(dims=(2048, 1024, 32, 10, 512, 512), kinds=["la", "gqa"], la_heads=(4, 8), hd=256, nh=8, seed=3),   # QCN-like widths (H 2048, I 512, k 10)
     dict(dims=(4096, 512, 128, 8, 256, 256), kinds=["gqa", "gqa"], hd=128, nh=16, seed=4),                   # Qwen3-235B-like widths (H 4096: the widest the kernels take, E 128, k 8)
+    MIXED,                                                     # mixed INT4 / INT8 inside every group that shares an activation: those layers fall back to the exact launches
 ]
 
 
@@ -67,7 +68,7 @@ CFGS = [
 @pytest.mark.parametrize("graph", [True, False])
 def test_fast_decode_matches_exact_within_tolerance(ci, graph):
     cfg = CFGS[ci]
-    if graph is False and ci >= 4:
+    if graph is False and ci >= 4 and cfg is not MIXED:      # no earlier configuration has mixed widths: its eager leg runs
         pytest.skip("eager launch order is covered by the first configurations")
     toks_pos = [(7, 5), (0, 6), (0, 7), (0, 8), (0, 9), (0, 10)]
     ex, ex_state, _ = _run(cfg, False, toks_pos, graph)
@@ -85,6 +86,24 @@ def test_fast_decode_matches_exact_within_tolerance(ci, graph):
     assert worst <= 2e-3, worst
     assert sworst <= 3e-3, sworst
     assert same_tok
+
+
+def test_fast_mode_mixed_widths_take_the_exact_launches():
+    """MIXED under KR_DECODE_FAST: a group of matrices with two widths cannot run as one launch of the mode, so those pieces must take the exact launches.
+    Counted from the model (la, gqa, la with MoE; gqa with the dense MLP), not measured: the stand-alone shared-gate matvec exists only on the exact MoE path,
+    once per MoE layer = 3 (the mode's own MoE launches carry the gate row: 0); norm launches = 4 input norms (no folded in-projection: ba / k are INT8) + 1
+    post-attention norm of the dense layer (gate INT4, up INT8) = 5, the three MoE layers' norms ride in the exact fused router and the final norm in the lm_head
+    launch; the un-mixed model of the same layers runs no norm launch at all"""
+    PK_RMSNORM, PK_SHARED_GATE = 1, 14      # positions in the PK_* enum of krasis_amd/csrc/kr_decode_internal.h (= the kinds listed in include/krasis_hip.h)
+    counts = {}
+    for name, cfg in (("mixed", MIXED), ("int4", dict(MIXED, wbits=4))):
+        st, eng, orc, keep, d = build(**cfg)
+        st.set_attention_mode(False, decode_fast=True)
+        lg = np.empty(d["V"], F)
+        st.decode_step(7, 5, lg.ctypes.data)
+        counts[name] = [c for _, c in st.profile_step(int(np.argmax(lg)), 6)]
+    assert (counts["mixed"][PK_SHARED_GATE], counts["mixed"][PK_RMSNORM]) == (3, 5), counts["mixed"]
+    assert (counts["int4"][PK_SHARED_GATE], counts["int4"][PK_RMSNORM]) == (0, 0), counts["int4"]
 
 
 @pytest.mark.parametrize("scoring", [1, 0])

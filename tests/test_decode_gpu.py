@@ -19,7 +19,8 @@ def build(seed=0, norm_bias_one=True, scoring=1, rsf=1.0, with_dense=False, wbit
           la_dkdv=(128, 128)):
     """peaked=True: a model whose next-token distribution is PEAKED without training -- large embeddings, lm_head tied to them (x 0.05): the logit of the
     current token stands ~8 above the rest, the layers (attention, router, experts) perturb it by an amount comparable to the noise floor, so on a token
-    stream with repeats the perplexity is O(10) and a routing flip or a tolerance-mode rounding difference shows up in it (tests/test_tolerance_peaked_gpu.py)"""
+    stream with repeats the perplexity is O(10) and a routing flip or a tolerance-mode rounding difference shows up in it (tests/test_tolerance_peaked_gpu.py).
+    wbits: 4 | 8 for every matrix, or a callable matrix name -> 4 | 8 (names: lm_head, qkvz, ba, out, q, k, v, o, gate, up, down, experts, sgu, sd, sg)"""
     from krasis_amd import CpuDecodeStore, KrasisEngine, ModelConfig
     rng = np.random.default_rng(seed)
     H, V, E, k, I, SI = dims or (256, 512, 16, 4, 128, 128)
@@ -33,10 +34,11 @@ def build(seed=0, norm_bias_one=True, scoring=1, rsf=1.0, with_dense=False, wbit
     st = CpuDecodeStore(128, True, norm_bias_one); st.set_moe_store(eng)
     orc = OracleDecode(H, 1e-6, norm_bias_one, k, scoring, True, rsf, emb, V)
     keep = [emb]
+    bits_of = wbits if callable(wbits) else (lambda name: wbits)
 
-    def W(rows, cols, scale=0.05):
+    def W(name, rows, cols, scale=0.05):
         w = (rng.standard_normal((rows, cols)) * scale).astype(F); keep.append(w)
-        return st.store_weight_f32(_ptr(w), rows, cols, wbits), orc.store_weight_f32(w, wbits)
+        return st.store_weight_f32(_ptr(w), rows, cols, bits_of(name)), orc.store_weight_f32(w, bits_of(name))
 
     def N(n):
         w = (rng.random(n) * 0.2 + (0.0 if norm_bias_one else 0.9)).astype(F); keep.append(w)
@@ -45,9 +47,9 @@ def build(seed=0, norm_bias_one=True, scoring=1, rsf=1.0, with_dense=False, wbit
     fin = N(H)
     if peaked:
         lmw = (emb * F(0.05)).astype(F); keep.append(lmw)
-        lm = (st.store_weight_f32(_ptr(lmw), V, H, wbits), orc.store_weight_f32(lmw, wbits))
+        lm = (st.store_weight_f32(_ptr(lmw), V, H, bits_of("lm_head")), orc.store_weight_f32(lmw, bits_of("lm_head")))
     else:
-        lm = W(V, H)
+        lm = W("lm_head", V, H)
     st.configure_decode(H, nL, 1e-6, fin[0], lm[0], V, k, scoring, True, rsf, _ptr(emb))
     orc.final_norm, orc.lm_head = fin[1], lm[1]
     cos = np.cos(np.arange(kv_max)[:, None] * (1.0 / 10000.0 ** (2 * np.arange(d2) / (2 * d2)))[None, :]).astype(F)
@@ -59,7 +61,7 @@ def build(seed=0, norm_bias_one=True, scoring=1, rsf=1.0, with_dense=False, wbit
         L = dict(in_norm=n_in[1], post_norm=n_post[1], attn=kind)
         if kind == "la":
             hr = nv // nk; group_dim = 2 * dk + 2 * dv * hr; conv_dim = 2 * nk * dk + nv * dv
-            qkvz = W(nk * group_dim, H, 0.08); ba = W(nk * 2 * hr, H, 0.3); out = W(H, nv * dv)
+            qkvz = W("qkvz", nk * group_dim, H, 0.08); ba = W("ba", nk * 2 * hr, H, 0.3); out = W("out", H, nv * dv)
             conv_w = (rng.standard_normal(conv_dim * 4) * 0.4).astype(F); a_log = (rng.random(nv) * 1.5 - 1.0).astype(F)
             dt_bias = (rng.random(nv) - 0.5).astype(F); norm_w = (rng.random(nv * dv) + 0.5).astype(F)
             keep += [conv_w, a_log, dt_bias, norm_w]
@@ -71,7 +73,7 @@ def build(seed=0, norm_bias_one=True, scoring=1, rsf=1.0, with_dense=False, wbit
             L.update(qkvz=qkvz[1], ba=ba[1], out=out[1], conv_w=conv_w, a_log=a_log, dt_bias=dt_bias, norm_w=norm_w, nk=nk, nv=nv, dk=dk, dv=dv,
                      scale=scale, conv_state=cs.copy(), recur_state=rs.copy())
         else:
-            q = W(nh * hd * 2, H, 0.08); kk = W(nkv * hd, H, 0.08); v = W(nkv * hd, H, 0.08); o = W(H, nh * hd)
+            q = W("q", nh * hd * 2, H, 0.08); kk = W("k", nkv * hd, H, 0.08); v = W("v", nkv * hd, H, 0.08); o = W("o", H, nh * hd)
             qn = (rng.random(hd) + 0.5).astype(F); kn = (rng.random(nkv * hd) + 0.5).astype(F); keep += [qn, kn]   # shared vs per-head norm weights
             sm = F(1.0 / np.sqrt(hd))
             st.add_decode_gqa_layer(n_in[0], n_post[0], q[0], kk[0], v[0], o[0], _ptr(qn), qn.size, _ptr(kn), kn.size, True, nh, nkv, hd, float(sm))
@@ -80,9 +82,9 @@ def build(seed=0, norm_bias_one=True, scoring=1, rsf=1.0, with_dense=False, wbit
             L.update(q=q[1], k=kk[1], v=v[1], o=o[1], q_norm=qn, k_norm=kn, gated=True, nh=nh, nkv=nkv, hd=hd, sm_scale=sm, kv_k=kc.copy(), kv_v=vc.copy())
         if with_dense and li == nL - 1:
             DI = 384                                    # dense MLP with a padded intermediate (cols of down = 384)
-            gw = W(DI - 40, H); uw = W(DI - 40, H)
+            gw = W("gate", DI - 40, H); uw = W("up", DI - 40, H)
             wd = (rng.standard_normal((H, DI)) * 0.05).astype(F); wd[:, DI - 40:] = 0; keep.append(wd)
-            dw = (st.store_weight_f32(_ptr(wd), H, DI, wbits), orc.store_weight_f32(wd, wbits))
+            dw = (st.store_weight_f32(_ptr(wd), H, DI, bits_of("down")), orc.store_weight_f32(wd, bits_of("down")))
             st.set_decode_layer_dense(li, gw[0], uw[0], dw[0]); L.update(mlp="dense", gate_w=gw[1], up_w=uw[1], down_w=dw[1])
         else:
             if gguf:      # routed experts as native GGUF blocks (Q4_K gate / up; down Q4_K when I % 256 == 0, else Q8_0 -- the V2-Lite situation): prompt pass only
@@ -92,11 +94,11 @@ def build(seed=0, norm_bias_one=True, scoring=1, rsf=1.0, with_dense=False, wbit
                 for ei, ex in enumerate(experts):
                     eng.load_gguf_expert(li, ei, ex.gate, ex.up, ex.down, gu_t, dn_t, I)
             else:
-                experts = make_experts(rng, E, H, I, wbits); upload(eng, li, experts)
+                experts = make_experts(rng, E, H, I, bits_of("experts")); upload(eng, li, experts)
             gate = ((rng.random((E, H)) - 0.5) * 0.1).astype(F); keep.append(gate)
             esc = ((rng.random(E) - 0.5) * 0.01).astype(F) if scoring == 0 else None
             eng.set_route_weight_f32(li, gate, None, esc)
-            sgu = W(2 * SI, H); sd = W(H, SI); sg = W(1, H, 0.3)
+            sgu = W("sgu", 2 * SI, H); sd = W("sd", H, SI); sg = W("sg", 1, H, 0.3)
             st.set_decode_layer_moe(li, li, li, sgu[0], sd[0], sg[0])
             L.update(mlp="moe", gate=gate, esc=esc, experts=experts, sgu=sgu[1], sd=sd[1], sg=sg[1])
         orc.layers.append(L)
@@ -109,10 +111,21 @@ def build(seed=0, norm_bias_one=True, scoring=1, rsf=1.0, with_dense=False, wbit
                                     state=state)
 
 
+def mixed_wbits(name):
+    """INT4 everywhere except INT8 for one matrix of each group that shares an activation: the linear-attention ba projection, the GQA k projection, the shared
+    expert's sigmoid-gate row and the dense up projection.  Such a group cannot run as one launch of one width: the step takes the per-matrix matvecs from the f32
+    hidden vector, the stand-alone shared-gate matvec, and under KR_DECODE_FAST the exact launches"""
+    return 8 if name in ("ba", "k", "sg", "up") else 4
+
+
+MIXED = dict(kinds=["la", "gqa", "la", "gqa"], with_dense=True, wbits=mixed_wbits)
+
+
 @pytest.mark.parametrize("cfg", [dict(), dict(norm_bias_one=False, scoring=0, rsf=2.5), dict(with_dense=True), dict(wbits=8, with_dense=True),
                                  dict(dims=(256, 512, 16, 4, 128, 384), seed=3),       # shared expert three times as wide as the routed ones (V2-Lite has 2 x)
                                  dict(la_dkdv=(64, 64), seed=4), dict(la_dkdv=(128, 64), la_heads=(2, 2), seed=5),    # the 64-wide key / value head forms of the in-projection epilogue and the per-value-head recurrence (ADVICE r5)
-                                 dict(dims=(256, 512, 512, 10, 128, 128), seed=6), dict(dims=(256, 512, 256, 8, 128, 128), seed=7, kinds=["la", "gqa"])])   # E = 512 / 256: the fused router's selection with the exponentials on four waves (8 / 4 values per lane)
+                                 dict(dims=(256, 512, 512, 10, 128, 128), seed=6), dict(dims=(256, 512, 256, 8, 128, 128), seed=7, kinds=["la", "gqa"]),   # E = 512 / 256: the fused router's selection with the exponentials on four waves (8 / 4 values per lane)
+                                 MIXED])      # mixed widths: the per-matrix matvecs from the f32 hidden vector and the stand-alone shared-gate matvec
 @pytest.mark.parametrize("graph", [True, False])
 @pytest.mark.parametrize("round5_forms", [1, 0])
 def test_decode_step_bit_exact(cfg, graph, round5_forms):
