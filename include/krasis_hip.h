@@ -411,6 +411,39 @@ int kr_decode_generate_multi_sample(kr_decode_store* s, int n, const int32_t* sl
 #define KR_EXTEND_MAX_TOKENS 1024      /* = the exact prompt pass's chunk */
 int kr_decode_extend_multi(kr_decode_store* s, int n, const int32_t* slots, const int32_t* counts, const int32_t* tokens, const int32_t* positions,
                            int32_t* next_out, float* logits_out, int sample, void* stream);
+/* exact greedy speculation over slots (docs/design/18-multi-verify.md): another schedule of kr_decode_extend_multi's arithmetic, not a tolerance mode.
+   kr_decode_verify_multi: rows laid out as in kr_decode_extend_multi (runs concatenated in tokens, T = sum of counts <= KR_EXTEND_MAX_TOKENS), every
+   counts[i] in [1, KR_VERIFY_MAX]: the first token of run i is the row's sampled, not yet consumed token at positions[i], the rest its draft.
+   greedy_out [T], concatenated like tokens: entry (i, t) = first-maximum argmax (kr_decode_step_multi's rule, so ties agree) of the logits after the first
+   t + 1 tokens of run i -- the id and logits bits kr_decode_step gives there on that sequence alone.  n_match_out[i] = the largest m <= counts[i] - 1 such
+   that token j of the run equals greedy (i, j - 1) for 1 <= j <= m.  Greedy only: the slots' samplers are neither read nor advanced.  Returns once both
+   outputs are written and leaves a PENDING verify over these rows: the linear-attention state of the slots is untouched (nothing to restore, no snapshot),
+   the KV rows (MLA: latent and rope-key rows) of the runs are written.
+   kr_decode_commit_multi: n_keep[i] in [0, n_match[i] + 1], one entry per row of the pending call.  Afterwards slot slots[i] is bit-identical to n_keep[i]
+   kr_decode_step calls on the first n_keep[i] tokens of its run: KV rows below positions[i] + n_keep[i], conv and recurrent state of every linear-attention
+   layer (n_keep[i] == 0: the slot exactly as before the verify -- a cancelled request drops out).  KV rows at or past the committed length are unspecified,
+   as after kr_decode_commit.  Clears the pending state.  An out-of-range n_keep is KR_ERR_VALUE naming the row: nothing is applied, the verify stays
+   pending.  Without a pending verify: KR_ERR_STATE.
+   While a verify over slots is pending every other slot entry point (step_multi*, extend_multi, generate_multi*, slot_save / slot_load, slot_sampler,
+   verify_multi) is refused with KR_ERR_STATE and changes nothing; kr_decode_slots_create discards the pending verify with the slots.  The store's own
+   sequence (decode_step, prefill, verify / commit, logits, last token, graph) is never touched by either call, and its own pending verify is a separate
+   flag.  kr_decode_verify_multi is refused wherever kr_decode_extend_multi is (same codes and row-naming messages), and for a count above KR_VERIFY_MAX.
+   Under "multi_attn_fast" every token carries the bits kr_decode_extend_multi gives it under the option.  The records of a call grow on demand with T
+   (per token row and linear-attention layer: conv_dim + nk dk + nv dv + 2 nv floats) beside [T][vocab] logits. */
+int kr_decode_verify_multi(kr_decode_store* s, int n, const int32_t* slots, const int32_t* counts, const int32_t* tokens, const int32_t* positions,
+                           int32_t* greedy_out, int32_t* n_match_out, void* stream);
+int kr_decode_commit_multi(kr_decode_store* s, const int32_t* n_keep);
+/* kr_decode_generate_multi in fewer passes: row i's tokens_out[i*max_tokens ...], n_out[i] and its slot's state afterwards equal kr_decode_generate_multi's.
+   Each pass every active row drafts from its own history (contexts row i -- the rows concatenated, n_context[i] tokens each; contexts / n_context may be
+   NULL for none -- then its first token, then its generated tokens) by the rule of kr_lookup_draft, clamped as kr_decode_generate_lookup clamps it (max_draft,
+   the remaining tokens, the slot and rope limits, cut after its first stop id) and to KR_EXTEND_MAX_TOKENS / m - 1 for m active rows.  No draft anywhere:
+   a plain step.  Otherwise one kr_decode_verify_multi and one kr_decode_commit_multi over all active rows (rows without a draft ride along with count 1).
+   *n_passes_out = passes, n_accepted_out[i] = accepted draft tokens of row i (either may be NULL).  Arguments are checked before the first pass: those of
+   kr_decode_generate_multi and the max_draft / ngram_max / context checks of kr_decode_generate_lookup. */
+int kr_decode_generate_multi_lookup(kr_decode_store* s, int n, const int32_t* slots, const int32_t* contexts, const int32_t* n_context,
+                                    const int32_t* first_tokens, const int32_t* start_positions, int max_tokens, int max_draft, int ngram_max,
+                                    const int* stop_ids, int n_stop, int32_t* tokens_out, int32_t* n_out, int* n_passes_out, int32_t* n_accepted_out,
+                                    void* stream);
 /* test aid (like kr_sample_order): the batched sampler on host logits [n][vocab] with per-row parameters, seen bitmaps [n][(vocab+31)/32]
    (may be NULL: none seen) and xorshift64 states (in / out); tokens_out[n].  force_loop != 0: every sampled row takes the single-row sampler
    (the "multi_sample_loop" form). */

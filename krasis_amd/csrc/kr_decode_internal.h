@@ -46,6 +46,13 @@ struct kr_multi_state {
     std::vector<Sampler> smp; size_t smp_words = 0;   // host: parameters per slot; seen-bitmap words per slot
     DevBuf smp_seen, smp_rng;                  // [n_slots][smp_words] seen-token bitmaps, [n_slots] xorshift64 states
     DevBuf smp_rows, smp_work, smp_sorted, smp_keys, smp_temp, smp_probs; size_t smp_temp_bytes = 0;   // a sampled step: KrMsRow [n], prepared rows, top-k keys, per-row path scratch
+    // verify over slots (kr_decode_verify_multi / kr_decode_commit_multi, docs/design/18-multi-verify.md): what the verify-form linear-attention launches
+    // recorded (one allocation, a slice per layer, sized by the call's token rows), the table of those layers on the host and the device (v_la_of[store layer] =
+    // its entry), [greedy ids in caller order | n_match], the commit's n_keep.  v_pending: the rows of the last verify wait for their commit -- the run table
+    // in `rows` and the records are theirs until then
+    DevBuf v_rec, v_tab, v_out, v_keep; std::vector<KrMultiLaCommit> v_host; std::vector<int> v_la_of;
+    bool v_pending = false, v_has64 = false, v_has128 = false; int v_nv_max = 0, v_dv_max = 0; size_t v_rows = 0;
+    std::vector<int32_t> v_match; hipStream_t v_st = nullptr;
     hipEvent_t ev = nullptr;
     ~kr_multi_state() { if (ev) (void)hipEventDestroy(ev); }
 };
@@ -114,6 +121,7 @@ int kr_spec_pending_fail(kr_decode_store* s);    // KR_ERR_STATE while a verify 
 int kr_standalone_cancelled(kr_decode_store* s);
 // kr_decode_prefill.cpp: the layers + final norm + lm_head GEMM of the multi-sequence pass on `st` in s->multi's arena: n_rows token rows in n_runs runs of
 // consecutive tokens per slot (a step: runs of one).  d_rows = [slots | tokens | positions] of n_rows each on the device, the last token of run i in row i;
-// d_runs = n_runs x [slot, off, cnt] (kr_multi.h); logits of the first n_runs rows -> s->multi->logits [n_runs][vocab]
-int kr_multi_pass(kr_decode_store* s, int n_rows, int n_runs, const int32_t* d_rows, const int32_t* d_runs, int max_pos, hipStream_t st);
+// d_runs = n_runs x [slot, off, cnt] (kr_multi.h); logits of the first n_runs rows -> s->multi->logits [n_runs][vocab].  verify: the linear-attention layers
+// take the verify form (no state stored; records into the layers of s->multi->v_host), and the logits of all n_rows rows -> s->multi->logits [n_rows][vocab]
+int kr_multi_pass(kr_decode_store* s, int n_rows, int n_runs, const int32_t* d_rows, const int32_t* d_runs, int max_pos, hipStream_t st, bool verify = false);
 void kr_standalone_set_elapsed(kr_decode_store* s, double sec);   // kr_engine.cpp: per (group, column) nibble sums for the int8-MFMA GEMM

@@ -9,13 +9,18 @@
 // kr_decode_extend_multi (docs/design/17-multi-extend.md) is the same pass with a run of tokens per row: a prompt enters a slot chunk by chunk beside the
 // decode rows of other slots, each run bit-identical to that many kr_decode_step calls, without the store's own sequence.  A step is an extend whose every
 // run has one token: both take one argument check, one flatten and one pass (step_entry / step_impl below).
+// kr_decode_verify_multi / kr_decode_commit_multi (docs/design/18-multi-verify.md) are that pass once more, for exact greedy speculation: runs of [sampled token,
+// draft] whose linear-attention sections record instead of storing state, the greedy id after every token, and a commit that advances each slot by the tokens
+// kept.  kr_decode_generate_multi_lookup drives them with prompt-lookup drafts per row.
 #include <algorithm>
 #include <chrono>
+#include <climits>
 #include <cstring>
 #include <vector>
 
 #include "../../include/krasis_hip.h"
 #include "kr_decode_internal.h"
+#include "kr_lookup_index.h"
 #include "kr_multi_sample.h"
 #include "kr_sampler.h"
 
@@ -60,10 +65,12 @@ int need_slots(kr_decode_store* s) {
         return kr_fail(KR_ERR_STATE, "the slots hold %s KV rows but the store uses %s now: create them again", s->multi->kv_fp8 ? "E4M3" : "FP16", s->kv_fp8 ? "E4M3" : "FP16");
     return KR_OK;
 }
-// what every entry point that touches the slots starts with
+// what every entry point that touches the slots starts with (kr_decode_commit_multi apart): between a verify over slots and its commit nothing else runs on
+// them -- the run table and the records belong to the pending rows
 int multi_begin(kr_decode_store* s) {
     if (int rc = multi_ready(s)) return rc;
     if (int rc = need_slots(s)) return rc;
+    if (s->multi->v_pending) return kr_fail(KR_ERR_STATE, "a verify over slots is pending: call kr_decode_commit_multi first");
     return multi_refuse(s);
 }
 // the rows of one call, every refusal naming its row: distinct slots in range, tokens in the vocabulary, positions inside the slot and the rope tables (the
@@ -138,25 +145,16 @@ KrMsArgs sampler_args(kr_multi_state& M, const float* logits, int vocab, int n, 
     a.loop_keys = (uint64_t*)M.smp_keys.p; a.loop_temp = M.smp_temp.p; a.loop_temp_bytes = M.smp_temp_bytes; a.loop_probs = (float*)M.smp_probs.p;
     return a;
 }
-// one pass, arguments checked: rows -> device, the pass, per-row argmax (sample: each slot's sampler), ids (and logits) back; returns once next_out is written.
-// Row i is a run of counts[i] tokens at positions[i] ... (counts null: one token per row, a step); the pass has one row per token, the last token of run i in
-// row i and the others from row n on in call order, so everything after the pass (logits, argmax, sampler) sees n rows
-int step_impl(kr_decode_store* s, int n, const int32_t* slots, const int32_t* tokens, const int32_t* positions, int32_t* next_out, float* logits_out, hipStream_t st,
-              bool sample = false, const int32_t* counts = nullptr) {
-    kr_multi_state& M = *s->multi;
-    if (M.rows.ensure((size_t)3 * (KR_EXTEND_MAX_TOKENS + KR_MULTI_MAX) * 4) || M.ids.ensure((size_t)KR_MULTI_MAX * 4))
-        return kr_fail(KR_ERR_HIP, "hipMalloc of the step's row buffers failed");
-    std::vector<KrMsRow> sr;
-    bool greedy = true;
-    if (sample) {
-        for (int i = 0; i < n; i++) { sr.push_back(sample_row(s, slots[i])); greedy &= sr.back().mode == KR_MS_GREEDY; }
-        if (!greedy && sampler_scratch(M, s->vocab, n, sr)) return kr_fail(KR_ERR_HIP, "hipMalloc of the sampled step's scratch failed");
-    }
+// the rows of a pass -> M.rows on the device: [slots | tokens | positions] of T token rows, then the runs [n][slot, off, cnt] (kr_multi.h).  The last token of
+// run i is row i and the others follow from row n on in call order (unit counts: row i = token i, off = n)
+int put_rows(kr_multi_state& M, int n, const int32_t* slots, const int32_t* counts, const int32_t* tokens, const int32_t* positions, hipStream_t st, size_t& T,
+             int& max_pos) {
+    if (M.rows.ensure((size_t)3 * (KR_EXTEND_MAX_TOKENS + KR_MULTI_MAX) * 4)) return kr_fail(KR_ERR_HIP, "hipMalloc of the step's row buffers failed");
     auto cnt = [&](int i) { return counts ? counts[i] : 1; };
-    size_t T = 0;
+    T = 0;
     for (int i = 0; i < n; i++) T += (size_t)cnt(i);
-    std::vector<int32_t> h(3 * T + (size_t)3 * n);      // [slots | tokens | positions] of T rows | runs [n][slot, off, cnt] (unit counts: row i = token i, off = n)
-    int max_pos = 0;
+    std::vector<int32_t> h(3 * T + (size_t)3 * n);
+    max_pos = 0;
     size_t src = 0, off = (size_t)n;
     for (int i = 0; i < n; i++) {
         int32_t* run = &h[3 * T + (size_t)3 * i];
@@ -169,6 +167,23 @@ int step_impl(kr_decode_store* s, int n, const int32_t* slots, const int32_t* to
         max_pos = std::max(max_pos, positions[i] + cnt(i) - 1);
     }
     KR_HIP(hipMemcpyAsync(M.rows.p, h.data(), h.size() * 4, hipMemcpyHostToDevice, st));
+    return KR_OK;
+}
+// one pass, arguments checked: rows -> device, the pass, per-row argmax (sample: each slot's sampler), ids (and logits) back; returns once next_out is written.
+// Row i is a run of counts[i] tokens at positions[i] ... (counts null: one token per row, a step); the pass has one row per token, the last token of run i in
+// row i and the others from row n on in call order, so everything after the pass (logits, argmax, sampler) sees n rows
+int step_impl(kr_decode_store* s, int n, const int32_t* slots, const int32_t* tokens, const int32_t* positions, int32_t* next_out, float* logits_out, hipStream_t st,
+              bool sample = false, const int32_t* counts = nullptr) {
+    kr_multi_state& M = *s->multi;
+    if (M.ids.ensure((size_t)KR_MULTI_MAX * 4)) return kr_fail(KR_ERR_HIP, "hipMalloc of the step's row buffers failed");
+    std::vector<KrMsRow> sr;
+    bool greedy = true;
+    if (sample) {
+        for (int i = 0; i < n; i++) { sr.push_back(sample_row(s, slots[i])); greedy &= sr.back().mode == KR_MS_GREEDY; }
+        if (!greedy && sampler_scratch(M, s->vocab, n, sr)) return kr_fail(KR_ERR_HIP, "hipMalloc of the sampled step's scratch failed");
+    }
+    size_t T = 0; int max_pos = 0;
+    if (int rc = put_rows(M, n, slots, counts, tokens, positions, st, T, max_pos)) return rc;
     if (!greedy) KR_HIP(hipMemcpyAsync(M.smp_rows.p, sr.data(), sr.size() * sizeof(KrMsRow), hipMemcpyHostToDevice, st));
     if (int rc = kr_multi_pass(s, (int)T, n, (const int32_t*)M.rows.p, (const int32_t*)M.rows.p + 3 * T, max_pos, st)) { (void)hipStreamSynchronize(st); return rc; }
     const size_t V = (size_t)s->vocab;
@@ -301,6 +316,170 @@ int generate_impl(kr_decode_store* s, int n, const int32_t* slots, const int32_t
     }
     return KR_OK;
 }
+
+// ---- verify over slots (docs/design/18-multi-verify.md)
+// the record slices of every linear-attention layer for T token rows and the table of those layers, host and device.  Per row and layer: conv_dim + nk dk +
+// nv dv + 2 nv floats
+int verify_records(kr_decode_store* s, size_t T, hipStream_t st) {
+    kr_multi_state& M = *s->multi;
+    M.v_host.clear(); M.v_la_of.assign(s->layers.size(), -1);
+    M.v_has64 = M.v_has128 = false; M.v_nv_max = M.v_dv_max = 0;
+    size_t floats = 0;
+    for (const DLayer& L : s->layers) if (L.attn == ATTN_LA) floats += T * ((size_t)2 * L.nk * L.dk + (size_t)L.nv * L.dv + (size_t)L.nk * L.dk + (size_t)L.nv * L.dv + 2 * (size_t)L.nv);
+    if (!floats) return KR_OK;
+    if (M.v_rec.ensure(floats * 4)) return kr_fail(KR_ERR_HIP, "hipMalloc of the verify records (%zu MiB for %zu token rows) failed", (floats * 4) >> 20, T);
+    float* p = (float*)M.v_rec.p;
+    auto take = [&](size_t n) { float* r = p; p += n; return r; };
+    for (size_t li = 0; li < s->layers.size(); li++) {
+        const DLayer& L = s->layers[li];
+        if (L.attn != ATTN_LA) continue;
+        KrMultiLaCommit E{};
+        E.conv_state = (float*)M.a[li].p; E.conv_stride = M.a_stride[li] / 4; E.recur = (float*)M.b[li].p; E.recur_stride = M.b_stride[li] / 4;
+        E.nk = L.nk; E.nv = L.nv; E.dk = L.dk; E.dv = L.dv; E.hr = L.nv / L.nk;
+        E.rec_x = take(T * ((size_t)2 * L.nk * L.dk + (size_t)L.nv * L.dv)); E.rec_k = take(T * (size_t)L.nk * L.dk); E.rec_v = take(T * (size_t)L.nv * L.dv);
+        E.rec_ge = take(T * (size_t)L.nv); E.rec_be = take(T * (size_t)L.nv);
+        M.v_la_of[li] = (int)M.v_host.size(); M.v_host.push_back(E);
+        (L.dk == 128 ? M.v_has128 : M.v_has64) = true;
+        M.v_nv_max = std::max(M.v_nv_max, L.nv); M.v_dv_max = std::max(M.v_dv_max, L.dv);
+    }
+    if (M.v_tab.ensure(M.v_host.size() * sizeof(KrMultiLaCommit))) return kr_fail(KR_ERR_HIP, "hipMalloc of the verify layer table failed");
+    KR_HIP(hipMemcpyAsync(M.v_tab.p, M.v_host.data(), M.v_host.size() * sizeof(KrMultiLaCommit), hipMemcpyHostToDevice, st));
+    return KR_OK;
+}
+// one verify pass, arguments checked: rows -> device, the pass in its verify form, the greedy id of every token row, the accept kernel, one copy back.  Leaves
+// the rows pending
+int verify_impl(kr_decode_store* s, int n, const int32_t* slots, const int32_t* counts, const int32_t* tokens, const int32_t* positions, int32_t* greedy_out,
+                int32_t* n_match_out, hipStream_t st) {
+    kr_multi_state& M = *s->multi;
+    size_t T = 0; int max_pos = 0;
+    if (int rc = put_rows(M, n, slots, counts, tokens, positions, st, T, max_pos)) return rc;
+    if (M.ids.ensure((size_t)KR_EXTEND_MAX_TOKENS * 4) || M.v_out.ensure((size_t)(KR_EXTEND_MAX_TOKENS + KR_MULTI_MAX) * 4) || M.v_keep.ensure((size_t)KR_MULTI_MAX * 4))
+        return kr_fail(KR_ERR_HIP, "hipMalloc of the verify's row buffers failed");
+    if (int rc = verify_records(s, T, st)) { (void)hipStreamSynchronize(st); return rc; }
+    const int32_t* d_rows = (const int32_t*)M.rows.p;
+    if (int rc = kr_multi_pass(s, (int)T, n, d_rows, d_rows + 3 * T, max_pos, st, true)) { (void)hipStreamSynchronize(st); return rc; }
+    const size_t V = (size_t)s->vocab;
+    kr_launch_multi_argmax((const float*)M.logits.p, V, (int)V, (int)T, (int*)M.ids.p, st);
+    kr_launch_multi_accept((const int*)M.ids.p, d_rows + T, d_rows + 3 * T, n, (int)T, (int*)M.v_out.p, st);
+    KR_HIP(hipGetLastError());
+    std::vector<int32_t> out(T + (size_t)n);
+    KR_HIP(hipMemcpyAsync(out.data(), M.v_out.p, out.size() * 4, hipMemcpyDeviceToHost, st));
+    KR_HIP(hipStreamSynchronize(st));
+    std::copy(out.begin(), out.begin() + (ptrdiff_t)T, greedy_out);
+    M.v_match.assign(out.begin() + (ptrdiff_t)T, out.end());
+    std::copy(M.v_match.begin(), M.v_match.end(), n_match_out);
+    M.v_pending = true; M.v_st = st; M.v_rows = T;
+    return KR_OK;
+}
+int commit_impl(kr_decode_store* s, const int32_t* n_keep) {
+    kr_multi_state& M = *s->multi;
+    const int n = (int)M.v_match.size();
+    if (!n_keep) return kr_fail(KR_ERR_VALUE, "null n_keep");
+    for (int i = 0; i < n; i++)
+        if (n_keep[i] < 0 || n_keep[i] > M.v_match[(size_t)i] + 1)
+            return kr_fail(KR_ERR_VALUE, "row %d: n_keep %d outside [0, %d] (n_match + 1)", i, n_keep[i], M.v_match[(size_t)i] + 1);
+    if (!M.v_host.empty()) {
+        KR_HIP(hipSetDevice(s->eng->device));
+        hipStream_t st = M.v_st;
+        KR_HIP(hipMemcpyAsync(M.v_keep.p, n_keep, (size_t)n * 4, hipMemcpyHostToDevice, st));
+        const size_t T = M.v_rows;      // the run table follows the 3 T row words the verify left in M.rows
+        kr_launch_multi_la_commit((const KrMultiLaCommit*)M.v_tab.p, (int)M.v_host.size(), M.v_has64, M.v_has128, M.v_nv_max, M.v_dv_max,
+                                  (const int*)M.rows.p + 3 * T, (const int*)M.v_keep.p, n, st);
+        KR_HIP(hipGetLastError());
+        KR_HIP(hipStreamSynchronize(st));
+    }
+    M.v_pending = false;
+    return KR_OK;
+}
+// kr_decode_generate_multi_lookup: generate_impl's greedy loop with prompt-lookup drafts per row (kr_decode_generate_lookup's rule and clamps)
+int lookup_impl(kr_decode_store* s, int n, const int32_t* slots, const int32_t* contexts, const int32_t* n_context, const int32_t* first_tokens,
+                const int32_t* start_positions, int max_tokens, int max_draft, int ngram_max, const int* stop_ids, int n_stop, int32_t* tokens_out, int32_t* n_out,
+                int* n_passes_out, int32_t* n_accepted_out, void* stream) {
+    if (int rc = multi_begin(s)) return rc;
+    if (max_tokens < 0) return kr_fail(KR_ERR_VALUE, "max_tokens %d < 0", max_tokens);
+    if (n_stop < 0 || (n_stop > 0 && !stop_ids)) return kr_fail(KR_ERR_VALUE, "bad stop ids (%d)", n_stop);
+    if (!n_out || (max_tokens > 0 && !tokens_out)) return kr_fail(KR_ERR_VALUE, "null output pointer");
+    if (max_draft < 0 || max_draft > KR_VERIFY_MAX - 1) return kr_fail(KR_ERR_VALUE, "max_draft %d out of range [0, %d]", max_draft, KR_VERIFY_MAX - 1);
+    if (ngram_max < 1 || ngram_max > KR_LOOKUP_NGRAM_MAX) return kr_fail(KR_ERR_VALUE, "ngram_max %d out of range [1, %d]", ngram_max, KR_LOOKUP_NGRAM_MAX);
+    if (int rc = check_args(s, n, slots, nullptr, first_tokens, start_positions, std::max(max_tokens - 1, 0))) return rc;
+    std::vector<size_t> c0((size_t)n + 1, 0);      // row i's context = contexts[c0[i] .. c0[i + 1])
+    for (int i = 0; i < n; i++) {
+        const int nc = n_context ? n_context[i] : 0;
+        if (nc < 0 || (nc > 0 && !contexts)) return kr_fail(KR_ERR_VALUE, "row %d: bad context (%d tokens)", i, nc);
+        c0[(size_t)i + 1] = c0[(size_t)i] + (size_t)nc;
+        for (size_t j = c0[(size_t)i]; j < c0[(size_t)i + 1]; j++)      // a context token becomes a draft token: it must be a valid id
+            if (contexts[j] < 0 || contexts[j] >= s->vocab) return kr_fail(KR_ERR_VALUE, "row %d: context token id %d out of range (vocab %d)", i, contexts[j], s->vocab);
+    }
+    for (int i = 0; i < n; i++) { n_out[i] = 0; if (n_accepted_out) n_accepted_out[i] = 0; }
+    if (n_passes_out) *n_passes_out = 0;
+    if (max_tokens == 0) return KR_OK;
+    KR_HIP(hipSetDevice(s->eng->device));
+    hipStream_t st = kr_pick_stream(s->eng, stream);
+    if (int rc = order_after_store(s, st)) return rc;
+    // a run over positions [pos, pos + k] must stay inside the slot and the rope tables (check_args' limits)
+    int limit = s->multi->max_seq;
+    if (s->max_rope_seq > 0) limit = std::min(limit, s->max_rope_seq);
+    for (const DLayer& L : s->layers) if (L.attn == ATTN_MLA) limit = std::min(limit, L.mla_rope_seq);
+    std::vector<LookupIndex> ix;
+    ix.reserve((size_t)n);
+    for (int i = 0; i < n; i++) {
+        ix.emplace_back(ngram_max);
+        for (size_t j = c0[(size_t)i]; j < c0[(size_t)i + 1]; j++) ix.back().push(contexts[j]);
+        ix.back().push(first_tokens[i]);
+    }
+    auto is_stop = [&](int t) { for (int j = 0; j < n_stop; j++) if (stop_ids[j] == t) return true; return false; };
+    std::vector<int> act((size_t)n);                           // rows still generating, in caller order
+    std::vector<int32_t> tk((size_t)n), ps((size_t)n);
+    for (int i = 0; i < n; i++) { act[(size_t)i] = i; tk[(size_t)i] = first_tokens[i]; ps[(size_t)i] = start_positions[i]; }
+    int passes = 0;
+    while (!act.empty()) {
+        const int m = (int)act.size(), fit = KR_EXTEND_MAX_TOKENS / m - 1;      // m rows of 1 + fit tokens always fit a pass
+        std::vector<int32_t> sl((size_t)m), rp((size_t)m), cn((size_t)m), run, greedy, nm((size_t)m), keep((size_t)m);
+        bool any = false;
+        for (int k = 0; k < m; k++) {
+            const int i = act[(size_t)k];
+            int32_t draft[KR_VERIFY_MAX];
+            int d = max_draft > 0 ? ix[(size_t)i].draft(max_draft, draft) : 0;
+            d = std::min(d, max_tokens - n_out[i] - 1);                   // the pass yields at most d + 1 tokens
+            d = std::min(d, limit - ps[(size_t)i] - 1);
+            d = std::max(std::min(d, fit), 0);
+            for (int j = 0; j < d; j++) if (is_stop(draft[j])) { d = j + 1; break; }      // nothing after a stop id can be kept
+            sl[(size_t)k] = slots[i]; rp[(size_t)k] = ps[(size_t)i]; cn[(size_t)k] = 1 + d;
+            run.push_back(tk[(size_t)i]);
+            run.insert(run.end(), draft, draft + d);
+            any |= d > 0;
+        }
+        passes++;
+        greedy.resize(run.size());
+        if (!any) {      // the plain loop's step
+            if (int rc = step_impl(s, m, sl.data(), run.data(), rp.data(), greedy.data(), nullptr, st)) return rc;
+            std::fill(nm.begin(), nm.end(), 0);
+        } else if (int rc = verify_impl(s, m, sl.data(), cn.data(), run.data(), rp.data(), greedy.data(), nm.data(), st)) return rc;
+        // greedy[0 .. n_match] of a row is what the plain loop generates next; a stop id among them ends the row there.  After emitting greedy[j] the plain
+        // loop has consumed tokens 0 .. j of the run: that many are kept
+        std::vector<int> next;
+        size_t g0 = 0;
+        for (int k = 0; k < m; k++) {
+            const int i = act[(size_t)k], mt = nm[(size_t)k];
+            int kp = mt + 1;
+            bool stop = false;
+            for (int j = 0; j <= mt; j++) {
+                const int t = greedy[g0 + (size_t)j];
+                tokens_out[(size_t)i * max_tokens + n_out[i]++] = t; ix[(size_t)i].push(t);
+                if (is_stop(t)) { kp = j + 1; stop = true; break; }
+            }
+            if (n_accepted_out) n_accepted_out[i] += std::min(mt, kp);
+            keep[(size_t)k] = kp;
+            tk[(size_t)i] = greedy[g0 + (size_t)kp - 1]; ps[(size_t)i] += kp;
+            g0 += (size_t)cn[(size_t)k];
+            if (!stop && n_out[i] < max_tokens) next.push_back(i);      // a finished row leaves the batch: its slot is not touched again
+        }
+        if (any) if (int rc = commit_impl(s, keep.data())) return rc;
+        act.swap(next);
+    }
+    if (n_passes_out) *n_passes_out = passes;
+    return KR_OK;
+}
 }  // namespace
 
 extern "C" int kr_decode_slots_create(kr_decode_store* s, int n_slots, int max_seq, size_t* bytes_out) {
@@ -406,4 +585,32 @@ extern "C" int kr_sample_rows(const float* logits, int n, int vocab, const float
     KR_HIP(hipMemcpy(tokens_out, ids.p, (size_t)n * 4, hipMemcpyDeviceToHost));
     KR_HIP(hipMemcpy(rng_state, rg.p, (size_t)n * 8, hipMemcpyDeviceToHost));
     return KR_OK;
+}
+
+// ---- verify and commit over slots (docs/design/18-multi-verify.md)
+extern "C" int kr_decode_verify_multi(kr_decode_store* s, int n, const int32_t* slots, const int32_t* counts, const int32_t* tokens, const int32_t* positions,
+                                      int32_t* greedy_out, int32_t* n_match_out, void* stream) {
+    if (int rc = multi_begin(s)) return rc;
+    if (int rc = check_args(s, n, counts ? slots : nullptr, counts, tokens, positions, 0)) return rc;
+    if (!greedy_out || !n_match_out) return kr_fail(KR_ERR_VALUE, "null greedy_out / n_match_out");
+    for (int i = 0; i < n; i++)
+        if (counts[i] > KR_VERIFY_MAX) return kr_fail(KR_ERR_VALUE, "row %d: a run of %d tokens, at most %d (KR_VERIFY_MAX) in a verify", i, counts[i], KR_VERIFY_MAX);
+    KR_HIP(hipSetDevice(s->eng->device));
+    hipStream_t st = kr_pick_stream(s->eng, stream);
+    if (int rc = order_after_store(s, st)) return rc;
+    return verify_impl(s, n, slots, counts, tokens, positions, greedy_out, n_match_out, st);
+}
+
+extern "C" int kr_decode_commit_multi(kr_decode_store* s, const int32_t* n_keep) {
+    if (int rc = multi_ready(s)) return rc;
+    if (!s->multi || !s->multi->v_pending) return kr_fail(KR_ERR_STATE, "no verify over slots is pending");
+    return commit_impl(s, n_keep);
+}
+
+extern "C" int kr_decode_generate_multi_lookup(kr_decode_store* s, int n, const int32_t* slots, const int32_t* contexts, const int32_t* n_context,
+                                               const int32_t* first_tokens, const int32_t* start_positions, int max_tokens, int max_draft, int ngram_max,
+                                               const int* stop_ids, int n_stop, int32_t* tokens_out, int32_t* n_out, int* n_passes_out,
+                                               int32_t* n_accepted_out, void* stream) {
+    return lookup_impl(s, n, slots, contexts, n_context, first_tokens, start_positions, max_tokens, max_draft, ngram_max, stop_ids, n_stop, tokens_out, n_out,
+                       n_passes_out, n_accepted_out, stream);
 }

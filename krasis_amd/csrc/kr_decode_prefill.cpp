@@ -43,6 +43,7 @@ struct Chunk {      // one chunk of the prompt in flight: its arena, stream and 
     bool verify = false;      // kr_decode_verify's pass: linear-attention layers write their recurrence inputs into the store's verify buffers (kr_spec.h)
     const int32_t* m_slots = nullptr; const int32_t* m_pos = nullptr; int m_sc_ld = 0; int m_fd_chunk = 0, m_fd_chunks = 0;   // the multi-sequence step: row b = slot m_slots[b] at m_pos[b] (device)
     const int32_t* m_runs = nullptr; int m_nruns = 0;      // ... and m_nruns x [slot, off, cnt] (device), the runs of token rows per slot (kr_multi.h); set whenever m_slots is
+    bool m_verify = false;      // kr_decode_verify_multi's pass: linear-attention layers record instead of storing state (docs/design/18-multi-verify.md)
 };
 size_t al(size_t n) { return (n + 255) & ~(size_t)255; }
 }  // namespace
@@ -113,6 +114,10 @@ static int run_layer(kr_decode_store* s, Chunk& cx, size_t li) {
             m.conv_state = (float*)M.a[li].p; m.conv_stride = M.a_stride[li] / 4; m.recur = (float*)M.b[li].p; m.recur_stride = M.b_stride[li] / 4;
             m.conv_out = B.cv; m.out = B.attn; m.ld_out = oc; m.nk = L.nk; m.nv = L.nv; m.dk = L.dk; m.dv = L.dv; m.hr = L.nv / L.nk; m.scale = L.la_scale; m.eps = s->eps;
             if (oc != L.nv * L.dv) return kr_fail(KR_ERR_VALUE, "out_proj cols %d != nv*dv", oc);
+            if (cx.m_verify) {
+                const KrMultiLaCommit& R = M.v_host[(size_t)M.v_la_of[li]];
+                m.rec_x = (float*)R.rec_x; m.rec_k = (float*)R.rec_k; m.rec_v = (float*)R.rec_v; m.rec_ge = (float*)R.rec_ge; m.rec_be = (float*)R.rec_be;
+            }
             if (kr_launch_multi_la(m, cx.m_runs, cx.m_nruns, Cc, st)) return kr_fail(KR_ERR_VALUE, "unsupported linear-attention geometry for the multi-sequence step");
         } else {
             KrPfmLaArgs a{};
@@ -685,10 +690,11 @@ extern "C" int kr_decode_commit(kr_decode_store* s, int n_keep) {
 // the multi-sequence pass (kr_decode_multi.cpp, docs/design/13-multi-sequence.md, 17-multi-extend.md): one chunk of n token rows in n_final runs of
 // consecutive tokens per slot, row b = a token of slot slots[b] at positions[b]; d_runs = n_final x [slot, off, cnt] after kr_multi.h (a step: runs of one).
 // Every row-wise section of run_layer runs unchanged; the linear-attention, GQA and MLA sections take the per-slot kernels (kr_multi.hip).  The last
-// token of run i is row i, so the final norm, lm_head GEMM and M.logits cover the first n_final rows only.  Engine buffer set KR_PF_MAX_DEPTH - 1; the
+// token of run i is row i, so the final norm, lm_head GEMM and M.logits cover the first n_final rows only (verify: all n rows, and the linear-attention
+// sections leave records instead of state, docs/design/18-multi-verify.md).  Engine buffer set KR_PF_MAX_DEPTH - 1; the
 // caller has ordered this pass after everything the store queued.
 // ------------------------------------------------------------------------------------------------
-int kr_multi_pass(kr_decode_store* s, int n, int n_final, const int32_t* d_rows, const int32_t* d_runs, int max_pos, hipStream_t st) {
+int kr_multi_pass(kr_decode_store* s, int n, int n_final, const int32_t* d_rows, const int32_t* d_runs, int max_pos, hipStream_t st, bool verify) {
     kr_multi_state& M = *s->multi;
     PfLayout Lo;
     if (int rc = pf_layout(s, (size_t)n, true, true, st, Lo)) return rc;
@@ -718,15 +724,16 @@ int kr_multi_pass(kr_decode_store* s, int n, int n_final, const int32_t* d_rows,
     }
     const bool need_scores = (has_gqa && !flash) || has_mla;
     const int sc_ld = (max_pos + 1 + 31) & ~31;
-    if (M.scratch.ensure(Lo.total) || (need_scores && M.scores.ensure((size_t)n * nh_max * sc_ld * 4)) || M.logits.ensure((size_t)n_final * s->vocab * 4))
-        return kr_fail(KR_ERR_HIP, "hipMalloc of the multi-sequence step's scratch (%zu MiB) failed", (Lo.total + ((size_t)n * nh_max * sc_ld + (size_t)n_final * s->vocab) * 4) >> 20);
+    const int n_logits = verify ? n : n_final;      // a verify pass: the lm_head over every token row (what Chunk::verify is to the store's own pass)
+    if (M.scratch.ensure(Lo.total) || (need_scores && M.scores.ensure((size_t)n * nh_max * sc_ld * 4)) || M.logits.ensure((size_t)n_logits * s->vocab * 4))
+        return kr_fail(KR_ERR_HIP, "hipMalloc of the multi-sequence step's scratch (%zu MiB) failed", (Lo.total + ((size_t)n * nh_max * sc_ld + (size_t)n_logits * s->vocab) * 4) >> 20);
     Chunk cx{};
     cx.B = pf_carve(Lo, (char*)M.scratch.p); cx.scores = nullptr; cx.tok = d_rows + n; cx.Cc = n; cx.pos0 = 0; cx.set = KR_PF_MAX_DEPTH - 1;
     cx.first = true; cx.add_is_emb = true; cx.st = st;
     cx.m_slots = d_rows; cx.m_pos = d_rows + 2 * n; cx.m_sc_ld = sc_ld; cx.m_fd_chunk = fd_chunk; cx.m_fd_chunks = fd_chunks;
-    cx.m_runs = d_runs; cx.m_nruns = n_final;
+    cx.m_runs = d_runs; cx.m_nruns = n_final; cx.m_verify = verify;
     for (size_t l = 0; l < s->layers.size(); l++)
         if (int rc = run_layer(s, cx, l)) return rc;
-    cx.Cc = n_final;
+    cx.Cc = n_logits;
     return final_rows(s, cx, (float*)M.logits.p);
 }

@@ -14,12 +14,29 @@ struct KrMultiLaArgs {
     float* conv_out;                           // scratch [rows][conv_dim]: conv + SiLU outputs
     float* out; int ld_out;                    // [rows][ld_out]: gated RMSNorm output, the out-projection's input
     int nk, nv, dk, dv, hr; float scale, eps;
+    // the verify form (docs/design/18-multi-verify.md): rec_x set = no state is stored, and per token row b what a replay of the kept tokens needs is
+    // recorded instead: rec_x [rows][conv_dim] the pre-conv channel inputs, rec_k [rows][nk * dk] the normalised keys (once per key head), rec_v
+    // [rows][nv * dv], rec_ge / rec_be [rows][nv] e^g and beta.  Null: the run form above
+    float *rec_x, *rec_k, *rec_v, *rec_ge, *rec_be;
 };
 // runs (device) = n_runs x [slot, off, cnt]: run i's tokens are, in order, rows off .. off + cnt - 2 and then row i of qkvz / ba / conv_out / out (cnt 1:
 // row i alone).  The slot's conv and recurrent state are loaded once, carried in registers through the run and stored once.  Slots distinct across runs;
 // max_cnt = a bound on every cnt, at most 1024 (the gate rows the recurrence kernel keeps in LDS).
 // 0: launched; 1: max_cnt out of range or geometry not covered (kd 4 is the caller's check; dk 64 / 128, dv <= 256, dv % 8 == 0)
 int kr_launch_multi_la(const KrMultiLaArgs& a, const int* runs, int n_runs, int max_cnt, hipStream_t st);
+
+// commit of a verify pass (docs/design/18-multi-verify.md): one linear-attention layer's slot states and the records its verify-form launch left.  A table
+// of these lives on the device (kr_multi_state::v_tab)
+struct KrMultiLaCommit {
+    float* conv_state; size_t conv_stride;     // as KrMultiLaArgs
+    float* recur; size_t recur_stride;
+    const float *rec_x, *rec_k, *rec_v, *rec_ge, *rec_be;
+    int nk, nv, dk, dv, hr;
+};
+// every slot of runs[0 .. n_runs) advanced by the first n_keep[i] tokens of its run (0: untouched), from the records; runs as above, n_keep on the device.
+// One launch per key width present; grid (nv_max, n_runs, n_la) x dv_max threads: the caller has checked dk in {64, 128} and dv <= 256 for every layer
+void kr_launch_multi_la_commit(const KrMultiLaCommit* tab, int n_la, bool has64, bool has128, int nv_max, int dv_max, const int* runs, const int* n_keep,
+                               int n_runs, hipStream_t st);
 
 // GQA, one token per row: QK-norm + RoPE at the row's position, K / V appended to the row's slot, attention over the slot's rows [0, pos]
 struct KrMultiGqaArgs {
@@ -63,3 +80,6 @@ int kr_launch_multi_mla(const KrMultiMlaArgs& a, int B, hipStream_t st);
 
 // per row b < B of logits [B][ld]: out[b] = first-maximum argmax of the row's first V values (kr_argmax_kernel's rule)
 void kr_launch_multi_argmax(const float* logits, size_t ld, int V, int B, int* out, hipStream_t st);
+// accept of a verify pass: ids [rows] = the greedy id of every pass row, tokens [rows] = the token each row consumed.  out[0 .. T) = the ids in caller order
+// (the runs concatenated), out[T + i] = n_match of run i: the number of leading draft tokens (tokens 1 .. of the run) that equal the id of the row before
+void kr_launch_multi_accept(const int* ids, const int* tokens, const int* runs, int n_runs, int T, int* out, hipStream_t st);

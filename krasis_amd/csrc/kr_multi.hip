@@ -34,6 +34,8 @@ __device__ __forceinline__ int kr_m_run_row(int i, int off, int cnt, int t) { re
 // conv1d (kernel 4) + SiLU of every channel of the run's rows, and the shift of the slot's carried inputs.  grid (conv_dim / 256, runs), 256 threads:
 // thread = channel, the slot's four carried inputs in registers for the whole run.  Channel layout (decode.rs:3815): q [0, key_dim), k [key_dim, 2 key_dim),
 // v [2 key_dim, conv_dim); the in-projection row holds per key head [q (dk) | k (dk) | v (hr dv) | z (hr dv)].
+// VERIFY (docs/design/18-multi-verify.md): the same outputs for every token, the channel's inputs recorded per row, the slot's carried inputs left as they are.
+template <bool VERIFY>
 __global__ void __launch_bounds__(256) kr_multi_la_conv_kernel(const KrMultiLaArgs a, const int* __restrict__ runs) {
     const int i = blockIdx.y, ch = blockIdx.x * 256 + threadIdx.x;
     const int dk = a.dk, dv = a.dv, hr = a.hr, key_dim = a.nk * dk, conv_dim = 2 * key_dim + a.nv * dv, group_dim = 2 * dk + 2 * dv * hr;
@@ -52,9 +54,10 @@ __global__ void __launch_bounds__(256) kr_multi_la_conv_kernel(const KrMultiLaAr
         const float x = xin[(size_t)b * a.ld_qkvz];
         const float co = s.y * w.x + s.z * w.y + s.w * w.z + x * w.w;
         a.conv_out[(size_t)b * conv_dim + ch] = co * kr_sigmoid_poly5(co);      // fast_silu_avx2
+        if constexpr (VERIFY) a.rec_x[(size_t)b * conv_dim + ch] = x;
         s = float4{s.y, s.z, s.w, x};
     }
-    *cs = s;
+    if constexpr (!VERIFY) *cs = s;
 }
 
 // gates, L2 norms, the gated delta rule on the slot's state and the head's gated RMSNorm.  grid (nv, runs), dv threads: thread j keeps column j of value
@@ -64,8 +67,10 @@ __global__ void __launch_bounds__(256) kr_multi_la_conv_kernel(const KrMultiLaAr
 // per token): a token's reads of qc / kc / nrm all precede its fourth barrier (after rr is written) and its reads of rr precede the fifth; every thread passes
 // both before any thread starts the next token, whose first LDS writes are qc / kc.  rms_s is read after the fifth barrier and next written after the next
 // token's fourth, by which time every thread has passed that token's first.
+// VERIFY (docs/design/18-multi-verify.md): the same outputs for every token; the column is not stored, and per token row the normalised key (by the first value
+// head of each key head, each thread the elements it scaled itself: no barrier is added), the value, e^g and beta are recorded for kr_multi_la_commit_kernel.
 #define KR_M_RUN_MAX 1024      // tokens per run (LDS gate rows); = KR_EXTEND_MAX_TOKENS
-template <int DK>
+template <int DK, bool VERIFY>
 __global__ void __launch_bounds__(256) kr_multi_la_recur_kernel(const KrMultiLaArgs a, const int* __restrict__ runs) {
     __shared__ float qc[DK], kc[DK], rr[256], nrm[2], rms_s, ge[KR_M_RUN_MAX], be[KR_M_RUN_MAX];
     const int h = blockIdx.x, ri = blockIdx.y, j = threadIdx.x, dv = a.dv, hr = a.hr, kh = h / hr, r = h - kh * hr;
@@ -103,9 +108,16 @@ __global__ void __launch_bounds__(256) kr_multi_la_recur_kernel(const KrMultiLaA
         {
             const float inv_q = nrm[0] * a.scale, inv_k = nrm[1] * 1.0f;
 #pragma unroll 1
-            for (int i = j; i < DK; i += dv) { qc[i] = qc[i] * inv_q; kc[i] = kc[i] * inv_k; }
+            for (int i = j; i < DK; i += dv) {
+                qc[i] = qc[i] * inv_q; kc[i] = kc[i] * inv_k;
+                if constexpr (VERIFY) if (r == 0) a.rec_k[((size_t)b * a.nk + kh) * DK + i] = kc[i];
+            }
         }
         __syncthreads();
+        if constexpr (VERIFY) {
+            a.rec_v[((size_t)b * a.nv + h) * dv + j] = vj;
+            if (j == 0) { a.rec_ge[(size_t)b * a.nv + h] = ge[t]; a.rec_be[(size_t)b * a.nv + h] = be[t]; }
+        }
         // kv = sum_i fma(S[i] e^g, k[i]); delta = (v - kv) beta; S' = fma(k, delta, S e^g); o = sum_i fma(S', q)
         const float g_exp = ge[t], beta_h = be[t];
         float kv = 0.0f;
@@ -143,17 +155,82 @@ __global__ void __launch_bounds__(256) kr_multi_la_recur_kernel(const KrMultiLaA
         const float normed = (ob * rms_s) * wn;
         a.out[(size_t)b * a.ld_out + (size_t)h * dv + j] = (zz * kr_sigmoid_poly5(zz)) * normed;
     }
+    if constexpr (!VERIFY) {
 #pragma unroll
-    for (int i = 0; i < DK; i++) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(c[i]), srd, j * 4, i * dv * 4, 0);
+        for (int i = 0; i < DK; i++) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(c[i]), srd, j * 4, i * dv * 4, 0);
+    }
+}
+
+// commit of a verify pass: the slot of run ri advanced by the first n_keep[ri] tokens of the run, from the records of the verify-form launches above.  grid
+// (value head, run, linear-attention layer), dv_max threads, one launch per key width (a workgroup of a layer of the other width returns).  Thread j < dv of
+// head h < nv loads column j of the slot's state through the run kernel's buffer descriptor, applies per kept token the run kernel's update in its order
+// (c[i] *= e^g; kv = fma chain over ascending i from 0; delta = (v - kv) beta; c[i] = fma(k[i], delta, c[i]) -- the output chain is not needed) and stores the
+// column once.  Then the carried conv inputs: input q of a channel = x(n_keep - 4 + q), x(i < 0) = the slot's old input 4 + i (kr_spec_rollback_kernel's rule);
+// the workgroups of (run, layer) stride over the layer's channels, each channel read and written by one thread.  No LDS, no barrier; a run that keeps nothing
+// returns at once.  Bounds: rows come from the run table the verify pass itself indexed the records with (kr_m_run_row), t < n_keep <= cnt; the column's
+// descriptor covers exactly head h's [DK][dv] block of the slot.
+template <int DK>
+__global__ void __launch_bounds__(256) kr_multi_la_commit_kernel(const KrMultiLaCommit* __restrict__ tab, const int* __restrict__ runs, const int* __restrict__ n_keep) {
+    const KrMultiLaCommit E = tab[blockIdx.z];
+    if (E.dk != DK) return;
+    const int ri = blockIdx.y, keep = n_keep[ri];
+    if (keep <= 0) return;
+    const int slot = runs[3 * ri], row0 = runs[3 * ri + 1], cnt = runs[3 * ri + 2];
+    const int h = blockIdx.x, j = threadIdx.x, nv = E.nv, dv = E.dv;
+    if (h < nv && j < dv) {
+        const __amdgpu_buffer_rsrc_t srd = __builtin_amdgcn_make_buffer_rsrc(E.recur + (size_t)slot * E.recur_stride + (size_t)h * DK * dv, 0, DK * dv * 4, 0x00020000);
+        float c[DK];
+#pragma unroll
+        for (int i = 0; i < DK; i++) c[i] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(srd, j * 4, i * dv * 4, 0));
+#pragma unroll 1
+        for (int t = 0; t < keep; t++) {
+            const size_t b = (size_t)kr_m_run_row(ri, row0, cnt, t);
+            const float* kr = E.rec_k + (b * E.nk + h / E.hr) * DK;
+            const float g_exp = E.rec_ge[b * nv + h], beta_h = E.rec_be[b * nv + h], vj = E.rec_v[(b * nv + h) * dv + j];
+            float kv = 0.0f;
+#pragma unroll
+            for (int i = 0; i < DK; i++) { c[i] = c[i] * g_exp; kv = __builtin_fmaf(c[i], kr[i], kv); }
+            const float delta = (vj - kv) * beta_h;
+#pragma unroll
+            for (int i = 0; i < DK; i++) c[i] = __builtin_fmaf(kr[i], delta, c[i]);
+        }
+#pragma unroll
+        for (int i = 0; i < DK; i++) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(c[i]), srd, j * 4, i * dv * 4, 0);
+    }
+    const int conv_dim = 2 * E.nk * DK + nv * dv;
+    float4* cs = reinterpret_cast<float4*>(E.conv_state + (size_t)slot * E.conv_stride);
+    for (int ch = blockIdx.x * blockDim.x + threadIdx.x; ch < conv_dim; ch += gridDim.x * blockDim.x) {
+        const float4 o = cs[ch];
+        float ns[4];
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const int i = keep - 4 + q, p = 4 + i;      // p in [1, 3] when i < 0 (keep >= 1)
+            ns[q] = i >= 0 ? E.rec_x[(size_t)kr_m_run_row(ri, row0, cnt, i) * conv_dim + ch] : (p == 1 ? o.y : p == 2 ? o.z : o.w);
+        }
+        cs[ch] = float4{ns[0], ns[1], ns[2], ns[3]};
+    }
+}
+void kr_launch_multi_la_commit(const KrMultiLaCommit* tab, int n_la, bool has64, bool has128, int nv_max, int dv_max, const int* runs, const int* n_keep,
+                               int n_runs, hipStream_t st) {
+    if (has128) hipLaunchKernelGGL(kr_multi_la_commit_kernel<128>, dim3(nv_max, n_runs, n_la), dim3(dv_max), 0, st, tab, runs, n_keep);
+    if (has64) hipLaunchKernelGGL(kr_multi_la_commit_kernel<64>, dim3(nv_max, n_runs, n_la), dim3(dv_max), 0, st, tab, runs, n_keep);
 }
 
 int kr_launch_multi_la(const KrMultiLaArgs& a, const int* runs, int n_runs, int max_cnt, hipStream_t st) {
     if (max_cnt < 1 || max_cnt > KR_M_RUN_MAX) return 1;
     if ((a.dk != 64 && a.dk != 128) || a.dv < 8 || a.dv > 256 || a.dv % 8 || a.nv != a.nk * a.hr) return 1;
     const int conv_dim = 2 * a.nk * a.dk + a.nv * a.dv;
-    hipLaunchKernelGGL(kr_multi_la_conv_kernel, dim3((conv_dim + 255) / 256, n_runs), dim3(256), 0, st, a, runs);
-    if (a.dk == 128) hipLaunchKernelGGL(kr_multi_la_recur_kernel<128>, dim3(a.nv, n_runs), dim3(a.dv), 0, st, a, runs);
-    else hipLaunchKernelGGL(kr_multi_la_recur_kernel<64>, dim3(a.nv, n_runs), dim3(a.dv), 0, st, a, runs);
+    const dim3 cg((conv_dim + 255) / 256, n_runs), rg(a.nv, n_runs);
+    if (a.rec_x) {      // the verify form: records instead of state
+        if (!a.rec_k || !a.rec_v || !a.rec_ge || !a.rec_be) return 1;
+        hipLaunchKernelGGL(kr_multi_la_conv_kernel<true>, cg, dim3(256), 0, st, a, runs);
+        if (a.dk == 128) hipLaunchKernelGGL((kr_multi_la_recur_kernel<128, true>), rg, dim3(a.dv), 0, st, a, runs);
+        else hipLaunchKernelGGL((kr_multi_la_recur_kernel<64, true>), rg, dim3(a.dv), 0, st, a, runs);
+        return 0;
+    }
+    hipLaunchKernelGGL(kr_multi_la_conv_kernel<false>, cg, dim3(256), 0, st, a, runs);
+    if (a.dk == 128) hipLaunchKernelGGL((kr_multi_la_recur_kernel<128, false>), rg, dim3(a.dv), 0, st, a, runs);
+    else hipLaunchKernelGGL((kr_multi_la_recur_kernel<64, false>), rg, dim3(a.dv), 0, st, a, runs);
     return 0;
 }
 
@@ -537,4 +614,25 @@ __global__ void __launch_bounds__(1024) kr_multi_argmax_kernel(const float* __re
 }
 void kr_launch_multi_argmax(const float* logits, size_t ld, int V, int B, int* out, hipStream_t st) {
     hipLaunchKernelGGL(kr_multi_argmax_kernel, dim3(B), dim3(1024), 0, st, logits, ld, V, out);
+}
+
+// ---- accept of a verify pass (docs/design/18-multi-verify.md) ------------------------------------------------------------------------------------
+// one thread per run walks it through kr_m_run_row: the ids into caller order (run i starts at off - n_runs + i: off counts the n_runs last-token rows plus
+// the earlier runs' other tokens), n_match = the draft tokens before the first that differs from the id of the row before it
+__global__ void __launch_bounds__(256) kr_multi_accept_kernel(const int* __restrict__ ids, const int* __restrict__ tokens, const int* __restrict__ runs, int n_runs,
+                                                              int T, int* __restrict__ out) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_runs) return;
+    const int off = runs[3 * i + 1], cnt = runs[3 * i + 2], src = off - n_runs + i;
+    int m = cnt - 1, prev = 0;
+    for (int t = 0; t < cnt; t++) {
+        const int b = kr_m_run_row(i, off, cnt, t);
+        if (t >= 1 && m == cnt - 1 && tokens[b] != prev) m = t - 1;
+        prev = ids[b];
+        out[src + t] = prev;
+    }
+    out[T + i] = m;
+}
+void kr_launch_multi_accept(const int* ids, const int* tokens, const int* runs, int n_runs, int T, int* out, hipStream_t st) {
+    hipLaunchKernelGGL(kr_multi_accept_kernel, dim3((n_runs + 255) / 256), dim3(256), 0, st, ids, tokens, runs, n_runs, T, out);
 }

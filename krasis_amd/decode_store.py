@@ -404,6 +404,7 @@ class CpuDecodeStore:
         self._need()
         b = C.c_size_t()
         check(self._lib.kr_decode_slots_create(self._h, n, max_seq, C.byref(b)))
+        self._multi_verify_rows = None      # a pending verify_multi goes with the slots
         return b.value
 
     def save_slot(self, slot: int, seq_len: int) -> None:
@@ -494,6 +495,57 @@ class CpuDecodeStore:
         check(self._lib.kr_decode_extend_multi(self._h, n, arr(list(slots)), arr([len(run) for run in token_lists]), arr(flat), arr(list(positions)), ids,
                                                out.ctypes.data if logits else None, 1 if sample else 0, None))
         return (list(ids[:n]), out) if logits else list(ids[:n])
+
+    def verify_multi(self, slots: Sequence[int], token_lists: Sequence[Sequence[int]], positions: Sequence[int]):
+        """kr_decode_verify_multi (docs/design/18-multi-verify.md): row i = slot slots[i] runs token_lists[i] = [its sampled, not yet consumed token, its
+        draft ...] (1 to KR_VERIFY_MAX tokens) at positions[i] ....  Returns (greedy_lists, n_match): greedy_lists[i][t] = the greedy id after the first t + 1
+        tokens of the run, bit for bit decode_step's on that sequence alone; n_match[i] = the leading draft tokens the model agrees with.  The rows stay
+        PENDING until commit_multi: the slots' linear-attention state is untouched, and every other slot call is refused."""
+        self._need()
+        n = len(slots)
+        if len(token_lists) != n or len(positions) != n:
+            raise ValueError(f"{n} slots, {len(token_lists)} token lists, {len(positions)} positions")
+        flat = [int(t) for run in token_lists for t in run]
+        arr = lambda xs: (C.c_int32 * max(len(xs), 1))(*xs)
+        counts = [len(run) for run in token_lists]
+        greedy = (C.c_int32 * max(len(flat), 1))(); nm = (C.c_int32 * max(n, 1))()
+        check(self._lib.kr_decode_verify_multi(self._h, n, arr(list(slots)), arr(counts), arr(flat), arr(list(positions)), greedy, nm, None))
+        self._multi_verify_rows = n
+        out, o = [], 0
+        for c in counts:
+            out.append(list(greedy[o:o + c])); o += c
+        return out, list(nm[:n])
+
+    def commit_multi(self, n_keep: Sequence[int]) -> None:
+        """kr_decode_commit_multi: keep the first n_keep[i] tokens of row i of the pending verify_multi (0 <= n_keep[i] <= n_match[i] + 1; 0 leaves the slot
+        as it was before the verify).  Each slot is then bit-identical to n_keep[i] decode_step calls on those tokens."""
+        self._need()
+        rows = getattr(self, "_multi_verify_rows", None)
+        if rows is not None and len(n_keep) != rows:
+            raise ValueError(f"{len(n_keep)} n_keep values for the {rows} rows of the pending verify")
+        check(self._lib.kr_decode_commit_multi(self._h, (C.c_int32 * max(len(n_keep), 1))(*[int(k) for k in n_keep])))
+        self._multi_verify_rows = None
+
+    def generate_multi_lookup(self, slots: Sequence[int], first_tokens: Sequence[int], start_positions: Sequence[int], max_tokens: int,
+                              contexts: Optional[Sequence[Sequence[int]]] = None, max_draft: int = LOOKUP_MAX_DRAFT, ngram_max: int = 3,
+                              stop_ids: Sequence[int] = ()) -> List[List[int]]:
+        """kr_decode_generate_multi_lookup: the tokens and slot states of generate_multi(slots, first_tokens, start_positions, max_tokens, stop_ids) in fewer
+        passes where a row's text repeats its context (contexts[i], e.g. its prompt) or itself: prompt-lookup drafts per row, one verify_multi +
+        commit_multi per pass.  last_multi_lookup_stats = {"passes": passes, "accepted": accepted draft tokens per row}."""
+        self._need()
+        n = len(slots)
+        contexts = [[] for _ in range(n)] if contexts is None else [list(c) for c in contexts]
+        if len(contexts) != n:
+            raise ValueError(f"{len(contexts)} contexts for {n} rows")
+        arr = lambda xs: (C.c_int32 * max(len(xs), 1))(*xs)
+        flat = [int(t) for c in contexts for t in c]
+        out = (C.c_int32 * max(n * max_tokens, 1))(); cnt = (C.c_int32 * max(n, 1))(); acc = (C.c_int32 * max(n, 1))(); passes = C.c_int()
+        stops = (C.c_int * max(len(stop_ids), 1))(*stop_ids)
+        check(self._lib.kr_decode_generate_multi_lookup(self._h, n, arr(list(slots)), arr(flat), arr([len(c) for c in contexts]), arr(list(first_tokens)),
+                                                        arr(list(start_positions)), max_tokens, max_draft, ngram_max, stops, len(stop_ids), out, cnt,
+                                                        C.byref(passes), acc, None))
+        self.last_multi_lookup_stats = {"passes": passes.value, "accepted": list(acc[:n])}
+        return [list(out[i * max_tokens: i * max_tokens + cnt[i]]) for i in range(n)]
 
     def prefill_slot(self, slot: int, tokens: Sequence[int], start_pos: int = 0, chunk: Optional[int] = None) -> int:
         """A prompt straight into a slot: extend_multi over chunks of `chunk` tokens (default KR_EXTEND_MAX_TOKENS).  The slot afterwards equals
