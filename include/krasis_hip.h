@@ -416,7 +416,8 @@ int kr_decode_extend_multi(kr_decode_store* s, int n, const int32_t* slots, cons
    counts[i] in [1, KR_VERIFY_MAX]: the first token of run i is the row's sampled, not yet consumed token at positions[i], the rest its draft.
    greedy_out [T], concatenated like tokens: entry (i, t) = first-maximum argmax (kr_decode_step_multi's rule, so ties agree) of the logits after the first
    t + 1 tokens of run i -- the id and logits bits kr_decode_step gives there on that sequence alone.  n_match_out[i] = the largest m <= counts[i] - 1 such
-   that token j of the run equals greedy (i, j - 1) for 1 <= j <= m.  Greedy only: the slots' samplers are neither read nor advanced.  Returns once both
+   that token j of the run equals greedy (i, j - 1) for 1 <= j <= m.  Greedy only: the slots' samplers are neither read nor advanced (the sampled form is
+   kr_decode_verify_multi_sample below).  Returns once both
    outputs are written and leaves a PENDING verify over these rows: the linear-attention state of the slots is untouched (nothing to restore, no snapshot),
    the KV rows (MLA: latent and rope-key rows) of the runs are written.
    kr_decode_commit_multi: n_keep[i] in [0, n_match[i] + 1], one entry per row of the pending call.  Afterwards slot slots[i] is bit-identical to n_keep[i]
@@ -444,6 +445,35 @@ int kr_decode_generate_multi_lookup(kr_decode_store* s, int n, const int32_t* sl
                                     const int32_t* first_tokens, const int32_t* start_positions, int max_tokens, int max_draft, int ngram_max,
                                     const int* stop_ids, int n_stop, int32_t* tokens_out, int32_t* n_out, int* n_passes_out, int32_t* n_accepted_out,
                                     void* stream);
+/* exact sampled speculation over slots (docs/design/19-multi-verify-sample.md).
+   kr_decode_verify_multi_sample: kr_decode_verify_multi (same arguments, checks, refusals and row-naming messages, same model pass, records and KV rows) whose
+   ids are drawn by the slots' samplers.  sampled_out [T], concatenated like tokens: for t <= n_match_out[i], entry (i, t) = the id kr_decode_step_multi_sample
+   gives after the first t + 1 tokens of run i are consumed one by one; entries past n_match_out[i] are unspecified (draws of a chain that assumes the
+   rejected draft).  Row (i, t) is drawn under the hypothesis that the run's tokens 1 .. t were the sampler's t draws before it: they count as seen, the
+   xorshift64 state is the slot's advanced t times more.  n_match_out as in kr_decode_verify_multi, over these ids.  Writes no sampler state and leaves the
+   same pending verify, marked as sampled; a slot without a sampler is plain greedy and its row equals kr_decode_verify_multi's.
+   kr_decode_commit_multi after it also applies the kept draws: slot slots[i]'s seen bitmap and xorshift64 state equal n_keep[i] kr_decode_step_multi_sample
+   calls on the run's first n_keep[i] tokens (0: untouched); a refused n_keep applies nothing to either part. */
+int kr_decode_verify_multi_sample(kr_decode_store* s, int n, const int32_t* slots, const int32_t* counts, const int32_t* tokens, const int32_t* positions,
+                                  int32_t* sampled_out, int32_t* n_match_out, void* stream);
+/* kr_decode_generate_multi_sample in fewer passes: every row's sampler is set first, then kr_decode_generate_multi_lookup's loop with sampled passes (a step,
+   or one kr_decode_verify_multi_sample and one commit).  Row i's tokens, count, slot state and sampler state afterwards equal
+   kr_decode_generate_multi_sample's for the same seeds.  Rows on the per-row sampler path (more than 4096 candidates, or "multi_sample_loop") do not draft.
+   The argument checks of both functions apply before the first pass. */
+int kr_decode_generate_multi_lookup_sample(kr_decode_store* s, int n, const int32_t* slots, const int32_t* contexts, const int32_t* n_context,
+                                  const int32_t* first_tokens, const int32_t* start_positions, int max_tokens, int max_draft, int ngram_max,
+                                  const float* temperature, const int* top_k, const float* top_p, const float* presence_penalty,
+                                  const uint64_t* rng_seeds, const int* stop_ids, int n_stop, int32_t* tokens_out, int32_t* n_out,
+                                  int* n_passes_out, int32_t* n_accepted_out, void* stream);
+/* one slot's sampler state read back (a zero bitmap and a zero state before any sampler was set); refused while a verify over slots is pending */
+int kr_decode_slot_sampler_get(kr_decode_store* s, int slot, uint32_t* seen_out /* (vocab + 31) / 32 words */, uint64_t* rng_out);
+/* test aid beside kr_sample_rows: the verify-form sampler, the accept kernel and the sampler commit on host logits [T][vocab] in caller order (the runs
+   concatenated: counts[n] in [1, KR_VERIFY_MAX], tokens[T]); run i is its own "slot" with per-run parameters, seen bitmap [n][(vocab+31)/32] and xorshift64
+   state (both in / out: the state after the commit).  ids_out[T] and n_match_out[n] as kr_decode_verify_multi_sample's.  n_keep[n] in / out: the wanted
+   number of kept tokens (negative: all), clamped to n_match + 1; what was applied is written back.  force_loop as in kr_sample_rows. */
+int kr_sample_runs(const float* logits, int n, const int32_t* counts, const int32_t* tokens, int vocab, const float* temperature, const int* top_k,
+                   const float* top_p, const float* presence_penalty, uint32_t* seen, uint64_t* rng_state, int32_t* n_keep, int32_t* ids_out,
+                   int32_t* n_match_out, int force_loop);
 /* test aid (like kr_sample_order): the batched sampler on host logits [n][vocab] with per-row parameters, seen bitmaps [n][(vocab+31)/32]
    (may be NULL: none seen) and xorshift64 states (in / out); tokens_out[n].  force_loop != 0: every sampled row takes the single-row sampler
    (the "multi_sample_loop" form). */

@@ -33,6 +33,7 @@ SYMBOLS = [
     "kr_decode_slots_create", "kr_decode_slot_save", "kr_decode_slot_load", "kr_decode_step_multi", "kr_decode_generate_multi",
     "kr_decode_slot_sampler", "kr_decode_step_multi_sample", "kr_decode_generate_multi_sample", "kr_sample_rows",
     "kr_decode_extend_multi", "kr_decode_verify_multi", "kr_decode_commit_multi", "kr_decode_generate_multi_lookup",
+    "kr_decode_verify_multi_sample", "kr_decode_generate_multi_lookup_sample", "kr_decode_slot_sampler_get", "kr_sample_runs",
 ]
 TOKEN_CB = C.CFUNCTYPE(C.c_int, C.c_int, C.c_int, C.c_void_p)      # kr_token_cb(token, finish_reason, user) -> continue?
 
@@ -187,6 +188,10 @@ def load_library() -> C.CDLL:
     lib.kr_decode_commit_multi.argtypes = [vp, vp]
     lib.kr_decode_generate_multi_lookup.argtypes = [vp, ci, vp, vp, vp, vp, vp, ci, ci, ci, vp, ci, vp, vp, C.POINTER(ci), vp, vp]
     lib.kr_sample_rows.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp, vp, vp, ci]
+    lib.kr_decode_verify_multi_sample.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp]
+    lib.kr_decode_generate_multi_lookup_sample.argtypes = [vp, ci, vp, vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, ci, vp, vp, C.POINTER(ci), vp, vp]
+    lib.kr_decode_slot_sampler_get.argtypes = [vp, ci, vp, vp]
+    lib.kr_sample_runs.argtypes = [vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci]
     _lib = lib
     return lib
 

@@ -45,13 +45,14 @@ struct kr_multi_state {
     struct Sampler { float temperature = 0.0f, top_p = 1.0f, penalty = 0.0f; int top_k = 0; };
     std::vector<Sampler> smp; size_t smp_words = 0;   // host: parameters per slot; seen-bitmap words per slot
     DevBuf smp_seen, smp_rng;                  // [n_slots][smp_words] seen-token bitmaps, [n_slots] xorshift64 states
-    DevBuf smp_rows, smp_work, smp_sorted, smp_keys, smp_temp, smp_probs; size_t smp_temp_bytes = 0;   // a sampled step: KrMsRow [n], prepared rows, top-k keys, per-row path scratch
+    DevBuf smp_rows, smp_work, smp_sorted, smp_keys, smp_temp, smp_probs; size_t smp_temp_bytes = 0;   // a sampled step: KrMsRow [n] (a sampled verify: then KrMsAt [n]), prepared rows, top-k keys, per-row path scratch
+    DevBuf smp_hyp;                            // a sampled verify's per-row path: one staged seen bitmap [smp_words] + xorshift64 state (docs/design/19-multi-verify-sample.md)
     // verify over slots (kr_decode_verify_multi / kr_decode_commit_multi, docs/design/18-multi-verify.md): what the verify-form linear-attention launches
     // recorded (one allocation, a slice per layer, sized by the call's token rows), the table of those layers on the host and the device (v_la_of[store layer] =
     // its entry), [greedy ids in caller order | n_match], the commit's n_keep.  v_pending: the rows of the last verify wait for their commit -- the run table
-    // in `rows` and the records are theirs until then
+    // in `rows` and the records are theirs until then; v_sampled: it drew with the slots' samplers (smp_rows and ids are its too: the commit applies the kept draws)
     DevBuf v_rec, v_tab, v_out, v_keep; std::vector<KrMultiLaCommit> v_host; std::vector<int> v_la_of;
-    bool v_pending = false, v_has64 = false, v_has128 = false; int v_nv_max = 0, v_dv_max = 0; size_t v_rows = 0;
+    bool v_pending = false, v_sampled = false, v_has64 = false, v_has128 = false; int v_nv_max = 0, v_dv_max = 0; size_t v_rows = 0;
     std::vector<int32_t> v_match; hipStream_t v_st = nullptr;
     hipEvent_t ev = nullptr;
     ~kr_multi_state() { if (ev) (void)hipEventDestroy(ev); }

@@ -11,7 +11,9 @@
 // run has one token: both take one argument check, one flatten and one pass (step_entry / step_impl below).
 // kr_decode_verify_multi / kr_decode_commit_multi (docs/design/18-multi-verify.md) are that pass once more, for exact greedy speculation: runs of [sampled token,
 // draft] whose linear-attention sections record instead of storing state, the greedy id after every token, and a commit that advances each slot by the tokens
-// kept.  kr_decode_generate_multi_lookup drives them with prompt-lookup drafts per row.
+// kept.  kr_decode_generate_multi_lookup drives them with prompt-lookup drafts per row.  kr_decode_verify_multi_sample (docs/design/19-multi-verify-sample.md)
+// draws every token row with its slot's sampler instead, under the hypothesis that the drafts before it were the sampler's draws; the commit applies the kept
+// draws to the samplers, and kr_decode_generate_multi_lookup_sample is the same loop over both.
 #include <algorithm>
 #include <chrono>
 #include <climits>
@@ -122,20 +124,24 @@ KrMsRow sample_row(kr_decode_store* s, int slot) {
     const kr_multi_state::Sampler& p = M.smp[(size_t)slot];
     return mode_row(slot, p.temperature, p.top_k, p.top_p, p.penalty, s->vocab, s->opt_multi_sample_loop != 0);
 }
-// device scratch of the batched sampler for n rows of these modes (kr_sample_rows and the sampled step)
+// device scratch of the batched sampler for n rows of these modes (the sampled step and verify, kr_sample_rows / kr_sample_runs), grown on demand: the
+// rows and, behind them, their (run, t) table; the work copy [n][V]; the top-k keys [n][KR_MS_SEL_CAP]; the per-row path's scratch with the staged sampler
+// of the verify form
 int sampler_scratch(kr_multi_state& M, int vocab, int n, const std::vector<KrMsRow>& rows) {
     bool prep = false, sample = false, loop = false;
     for (const KrMsRow& r : rows) { prep |= r.mode != KR_MS_GREEDY; sample |= r.mode == KR_MS_SAMPLE; loop |= r.mode == KR_MS_LOOP; }
-    const size_t V = (size_t)vocab;
-    if (M.smp_rows.ensure((size_t)KR_MULTI_MAX * sizeof(KrMsRow))) return 1;
-    if (prep && M.smp_work.ensure((size_t)n * V * 4)) return 1;
-    if (sample && M.smp_sorted.ensure((size_t)n * KR_MS_SEL_CAP * 8)) return 1;
-    if (loop) {
+    const size_t V = (size_t)vocab, N = (size_t)std::max(n, KR_MULTI_MAX);
+    const size_t work = prep ? (size_t)n * V * 4 : 0, sorted = sample ? (size_t)n * KR_MS_SEL_CAP * 8 : 0;
+    bool bad = M.smp_rows.ensure(N * (sizeof(KrMsRow) + sizeof(KrMsAt))) || (work && M.smp_work.ensure(work)) || (sorted && M.smp_sorted.ensure(sorted));
+    if (!bad && loop) {
         if (M.smp_temp_bytes == 0) M.smp_temp_bytes = kr_sampler_temp_bytes(vocab);
-        if (M.smp_keys.ensure(2 * V * 8) || M.smp_temp.ensure(M.smp_temp_bytes + 256) || M.smp_probs.ensure(V * 4)) return 1;
+        bad = M.smp_keys.ensure(2 * V * 8) || M.smp_temp.ensure(M.smp_temp_bytes + 256) || M.smp_probs.ensure(V * 4) || M.smp_hyp.ensure(((V + 31) / 32) * 4 + 16);      // the staged bitmap, then its state on the next 8-byte boundary
     }
-    return 0;
+    if (bad) return kr_fail(KR_ERR_HIP, "hipMalloc of the batched sampler's scratch failed (%d rows: work copy %zu MiB, sorted keys %zu MiB)", n, work >> 20, sorted >> 20);
+    return KR_OK;
 }
+// the (run, t) table of a verify-form call sits behind the rows
+KrMsAt* sampler_at(kr_multi_state& M, int n) { return (KrMsAt*)((KrMsRow*)M.smp_rows.p + std::max(n, KR_MULTI_MAX)); }
 KrMsArgs sampler_args(kr_multi_state& M, const float* logits, int vocab, int n, const std::vector<KrMsRow>& rows, uint32_t* seen, size_t words, uint64_t* rng, int* ids) {
     KrMsArgs a{};
     a.logits = logits; a.ld = (size_t)vocab; a.V = vocab; a.B = n;
@@ -147,13 +153,14 @@ KrMsArgs sampler_args(kr_multi_state& M, const float* logits, int vocab, int n, 
 }
 // the rows of a pass -> M.rows on the device: [slots | tokens | positions] of T token rows, then the runs [n][slot, off, cnt] (kr_multi.h).  The last token of
 // run i is row i and the others follow from row n on in call order (unit counts: row i = token i, off = n)
-int put_rows(kr_multi_state& M, int n, const int32_t* slots, const int32_t* counts, const int32_t* tokens, const int32_t* positions, hipStream_t st, size_t& T,
-             int& max_pos) {
-    if (M.rows.ensure((size_t)3 * (KR_EXTEND_MAX_TOKENS + KR_MULTI_MAX) * 4)) return kr_fail(KR_ERR_HIP, "hipMalloc of the step's row buffers failed");
+// lay_rows: that layout on the host (row_of, optional: the pass row of every token in call order)
+std::vector<int32_t> lay_rows(int n, const int32_t* slots, const int32_t* counts, const int32_t* tokens, const int32_t* positions, size_t& T, int& max_pos,
+                              std::vector<int>* row_of = nullptr) {
     auto cnt = [&](int i) { return counts ? counts[i] : 1; };
     T = 0;
     for (int i = 0; i < n; i++) T += (size_t)cnt(i);
     std::vector<int32_t> h(3 * T + (size_t)3 * n);
+    if (row_of) row_of->resize(T);
     max_pos = 0;
     size_t src = 0, off = (size_t)n;
     for (int i = 0; i < n; i++) {
@@ -162,11 +169,37 @@ int put_rows(kr_multi_state& M, int n, const int32_t* slots, const int32_t* coun
         for (int t = 0; t < cnt(i); t++) {
             const size_t row = t == cnt(i) - 1 ? (size_t)i : off + t;
             h[row] = slots[i]; h[T + row] = tokens[src + t]; h[2 * T + row] = positions[i] + t;
+            if (row_of) (*row_of)[src + t] = (int)row;
         }
         src += (size_t)cnt(i); off += (size_t)cnt(i) - 1;
         max_pos = std::max(max_pos, positions[i] + cnt(i) - 1);
     }
-    KR_HIP(hipMemcpyAsync(M.rows.p, h.data(), h.size() * 4, hipMemcpyHostToDevice, st));
+    return h;
+}
+int put_rows(kr_multi_state& M, int n, const int32_t* slots, const int32_t* counts, const int32_t* tokens, const int32_t* positions, hipStream_t st, size_t& T,
+             int& max_pos, std::vector<int>* row_of = nullptr) {
+    if (M.rows.ensure((size_t)3 * (KR_EXTEND_MAX_TOKENS + KR_MULTI_MAX) * 4)) return kr_fail(KR_ERR_HIP, "hipMalloc of the step's row buffers failed");
+    const std::vector<int32_t> h = lay_rows(n, slots, counts, tokens, positions, T, max_pos, row_of);
+    KR_HIP(hipMemcpyAsync(M.rows.p, h.data(), h.size() * 4, hipMemcpyHostToDevice, st));      // pageable source: staged before the call returns
+    return KR_OK;
+}
+// the rows and (run, t) table of a verify-form sampler call in pass-row order: token t of run i draws with run i's sampler row
+void run_rows(int n, const int32_t* counts, const std::vector<int>& row_of, const std::vector<KrMsRow>& per_run, std::vector<KrMsRow>& rows, std::vector<KrMsAt>& at) {
+    rows.resize(row_of.size()); at.resize(row_of.size());
+    size_t src = 0;
+    for (int i = 0; i < n; i++)
+        for (int t = 0; t < counts[i]; t++, src++) { rows[(size_t)row_of[src]] = per_run[(size_t)i]; at[(size_t)row_of[src]] = KrMsAt{i, t}; }
+}
+// the verify-form launches over the T token rows the pass left in `logits`: rows and table to the device, then every row's draw into ids [T]
+int sample_runs(kr_multi_state& M, const float* logits, int vocab, const std::vector<KrMsRow>& rows, const std::vector<KrMsAt>& at, const int32_t* d_rows, uint32_t* seen,
+                size_t words, uint64_t* rng, int* ids, hipStream_t st) {
+    const int T = (int)rows.size();
+    KR_HIP(hipMemcpyAsync(M.smp_rows.p, rows.data(), rows.size() * sizeof(KrMsRow), hipMemcpyHostToDevice, st));
+    KR_HIP(hipMemcpyAsync(sampler_at(M, T), at.data(), at.size() * sizeof(KrMsAt), hipMemcpyHostToDevice, st));
+    KrMsArgs a = sampler_args(M, logits, vocab, T, rows, seen, words, rng, ids);
+    a.runs = d_rows + 3 * (size_t)T; a.tokens = d_rows + T; a.at_dev = sampler_at(M, T); a.at_host = at.data();
+    a.hyp_seen = (uint32_t*)M.smp_hyp.p; a.hyp_rng = M.smp_hyp.p ? (uint64_t*)((char*)M.smp_hyp.p + ((words * 4 + 7) & ~(size_t)7)) : nullptr;
+    if (kr_launch_multi_sample(a, st)) return kr_fail(KR_ERR_HIP, "batched sampler launch failed");
     return KR_OK;
 }
 // one pass, arguments checked: rows -> device, the pass, per-row argmax (sample: each slot's sampler), ids (and logits) back; returns once next_out is written.
@@ -180,7 +213,7 @@ int step_impl(kr_decode_store* s, int n, const int32_t* slots, const int32_t* to
     bool greedy = true;
     if (sample) {
         for (int i = 0; i < n; i++) { sr.push_back(sample_row(s, slots[i])); greedy &= sr.back().mode == KR_MS_GREEDY; }
-        if (!greedy && sampler_scratch(M, s->vocab, n, sr)) return kr_fail(KR_ERR_HIP, "hipMalloc of the sampled step's scratch failed");
+        if (!greedy) if (int rc = sampler_scratch(M, s->vocab, n, sr)) return rc;
     }
     size_t T = 0; int max_pos = 0;
     if (int rc = put_rows(M, n, slots, counts, tokens, positions, st, T, max_pos)) return rc;
@@ -346,20 +379,35 @@ int verify_records(kr_decode_store* s, size_t T, hipStream_t st) {
     KR_HIP(hipMemcpyAsync(M.v_tab.p, M.v_host.data(), M.v_host.size() * sizeof(KrMultiLaCommit), hipMemcpyHostToDevice, st));
     return KR_OK;
 }
-// one verify pass, arguments checked: rows -> device, the pass in its verify form, the greedy id of every token row, the accept kernel, one copy back.  Leaves
-// the rows pending
+// one verify pass, arguments checked: rows -> device, the pass in its verify form, the greedy id of every token row (sample: the draw of its slot's sampler
+// under the hypothesis that the run's drafts before it were drawn; no sampler state is written), the accept kernel, one copy back.  Leaves the rows pending
 int verify_impl(kr_decode_store* s, int n, const int32_t* slots, const int32_t* counts, const int32_t* tokens, const int32_t* positions, int32_t* greedy_out,
-                int32_t* n_match_out, hipStream_t st) {
+                int32_t* n_match_out, hipStream_t st, bool sample = false) {
     kr_multi_state& M = *s->multi;
     size_t T = 0; int max_pos = 0;
-    if (int rc = put_rows(M, n, slots, counts, tokens, positions, st, T, max_pos)) return rc;
+    std::vector<int> row_of;
+    if (int rc = put_rows(M, n, slots, counts, tokens, positions, st, T, max_pos, &row_of)) return rc;
+    std::vector<KrMsRow> sr; std::vector<KrMsAt> at;
+    bool greedy = true;
+    if (sample) {
+        std::vector<KrMsRow> per_run;
+        for (int i = 0; i < n; i++) { per_run.push_back(sample_row(s, slots[i])); greedy &= per_run.back().mode == KR_MS_GREEDY; }
+        if (!greedy) {
+            run_rows(n, counts, row_of, per_run, sr, at);
+            if (int rc = sampler_scratch(M, s->vocab, (int)T, sr)) return rc;
+        }
+    }
     if (M.ids.ensure((size_t)KR_EXTEND_MAX_TOKENS * 4) || M.v_out.ensure((size_t)(KR_EXTEND_MAX_TOKENS + KR_MULTI_MAX) * 4) || M.v_keep.ensure((size_t)KR_MULTI_MAX * 4))
         return kr_fail(KR_ERR_HIP, "hipMalloc of the verify's row buffers failed");
     if (int rc = verify_records(s, T, st)) { (void)hipStreamSynchronize(st); return rc; }
     const int32_t* d_rows = (const int32_t*)M.rows.p;
     if (int rc = kr_multi_pass(s, (int)T, n, d_rows, d_rows + 3 * T, max_pos, st, true)) { (void)hipStreamSynchronize(st); return rc; }
     const size_t V = (size_t)s->vocab;
-    kr_launch_multi_argmax((const float*)M.logits.p, V, (int)V, (int)T, (int*)M.ids.p, st);
+    if (greedy) kr_launch_multi_argmax((const float*)M.logits.p, V, (int)V, (int)T, (int*)M.ids.p, st);
+    else if (int rc = sample_runs(M, (const float*)M.logits.p, s->vocab, sr, at, d_rows, (uint32_t*)M.smp_seen.p, M.smp_words, (uint64_t*)M.smp_rng.p, (int*)M.ids.p, st)) {
+        (void)hipStreamSynchronize(st);
+        return rc;
+    }
     kr_launch_multi_accept((const int*)M.ids.p, d_rows + T, d_rows + 3 * T, n, (int)T, (int*)M.v_out.p, st);
     KR_HIP(hipGetLastError());
     std::vector<int32_t> out(T + (size_t)n);
@@ -368,7 +416,7 @@ int verify_impl(kr_decode_store* s, int n, const int32_t* slots, const int32_t* 
     std::copy(out.begin(), out.begin() + (ptrdiff_t)T, greedy_out);
     M.v_match.assign(out.begin() + (ptrdiff_t)T, out.end());
     std::copy(M.v_match.begin(), M.v_match.end(), n_match_out);
-    M.v_pending = true; M.v_st = st; M.v_rows = T;
+    M.v_pending = true; M.v_sampled = !greedy; M.v_st = st; M.v_rows = T;
     return KR_OK;
 }
 int commit_impl(kr_decode_store* s, const int32_t* n_keep) {
@@ -378,23 +426,31 @@ int commit_impl(kr_decode_store* s, const int32_t* n_keep) {
     for (int i = 0; i < n; i++)
         if (n_keep[i] < 0 || n_keep[i] > M.v_match[(size_t)i] + 1)
             return kr_fail(KR_ERR_VALUE, "row %d: n_keep %d outside [0, %d] (n_match + 1)", i, n_keep[i], M.v_match[(size_t)i] + 1);
-    if (!M.v_host.empty()) {
+    if (!M.v_host.empty() || M.v_sampled) {
         KR_HIP(hipSetDevice(s->eng->device));
         hipStream_t st = M.v_st;
         KR_HIP(hipMemcpyAsync(M.v_keep.p, n_keep, (size_t)n * 4, hipMemcpyHostToDevice, st));
         const size_t T = M.v_rows;      // the run table follows the 3 T row words the verify left in M.rows
-        kr_launch_multi_la_commit((const KrMultiLaCommit*)M.v_tab.p, (int)M.v_host.size(), M.v_has64, M.v_has128, M.v_nv_max, M.v_dv_max,
-                                  (const int*)M.rows.p + 3 * T, (const int*)M.v_keep.p, n, st);
+        const int* runs = (const int*)M.rows.p + 3 * T;
+        if (!M.v_host.empty())
+            kr_launch_multi_la_commit((const KrMultiLaCommit*)M.v_tab.p, (int)M.v_host.size(), M.v_has64, M.v_has128, M.v_nv_max, M.v_dv_max, runs,
+                                      (const int*)M.v_keep.p, n, st);
+        if (M.v_sampled)      // the kept draws, from the sampler rows and ids the verify left (nothing else has run on the slots since)
+            kr_launch_ms_commit((const KrMsRow*)M.smp_rows.p, runs, (const int*)M.v_keep.p, n, (const int*)M.ids.p, s->vocab, (uint32_t*)M.smp_seen.p, M.smp_words,
+                                (uint64_t*)M.smp_rng.p, st);
         KR_HIP(hipGetLastError());
         KR_HIP(hipStreamSynchronize(st));
     }
     M.v_pending = false;
     return KR_OK;
 }
-// kr_decode_generate_multi_lookup: generate_impl's greedy loop with prompt-lookup drafts per row (kr_decode_generate_lookup's rule and clamps)
+// kr_decode_generate_multi_lookup: generate_impl's loop with prompt-lookup drafts per row (kr_decode_generate_lookup's rule and clamps).  temperature set: the
+// sampled form -- every row's sampler set first as generate_impl sets it, the passes sampled; a row on the per-row sampler path (KR_MS_LOOP) does not draft
 int lookup_impl(kr_decode_store* s, int n, const int32_t* slots, const int32_t* contexts, const int32_t* n_context, const int32_t* first_tokens,
-                const int32_t* start_positions, int max_tokens, int max_draft, int ngram_max, const int* stop_ids, int n_stop, int32_t* tokens_out, int32_t* n_out,
+                const int32_t* start_positions, int max_tokens, int max_draft, int ngram_max, const float* temperature, const int* top_k, const float* top_p,
+                const float* presence_penalty, const uint64_t* rng_seeds, const int* stop_ids, int n_stop, int32_t* tokens_out, int32_t* n_out,
                 int* n_passes_out, int32_t* n_accepted_out, void* stream) {
+    const bool sample = temperature != nullptr;
     if (int rc = multi_begin(s)) return rc;
     if (max_tokens < 0) return kr_fail(KR_ERR_VALUE, "max_tokens %d < 0", max_tokens);
     if (n_stop < 0 || (n_stop > 0 && !stop_ids)) return kr_fail(KR_ERR_VALUE, "bad stop ids (%d)", n_stop);
@@ -410,12 +466,23 @@ int lookup_impl(kr_decode_store* s, int n, const int32_t* slots, const int32_t* 
         for (size_t j = c0[(size_t)i]; j < c0[(size_t)i + 1]; j++)      // a context token becomes a draft token: it must be a valid id
             if (contexts[j] < 0 || contexts[j] >= s->vocab) return kr_fail(KR_ERR_VALUE, "row %d: context token id %d out of range (vocab %d)", i, contexts[j], s->vocab);
     }
+    if (sample) {
+        if (!top_k || !top_p || !presence_penalty || !rng_seeds) return kr_fail(KR_ERR_VALUE, "null sampler parameter array");
+        for (int i = 0; i < n; i++) if (!(temperature[i] >= 0.0f)) return kr_fail(KR_ERR_VALUE, "row %d: temperature must be >= 0", i);
+    }
     for (int i = 0; i < n; i++) { n_out[i] = 0; if (n_accepted_out) n_accepted_out[i] = 0; }
     if (n_passes_out) *n_passes_out = 0;
-    if (max_tokens == 0) return KR_OK;
+    if (max_tokens == 0 && !sample) return KR_OK;
     KR_HIP(hipSetDevice(s->eng->device));
     hipStream_t st = kr_pick_stream(s->eng, stream);
     if (int rc = order_after_store(s, st)) return rc;
+    std::vector<char> drafts((size_t)n, 1);
+    if (sample)
+        for (int i = 0; i < n; i++) {
+            if (int rc = set_sampler(s, slots[i], first_tokens[i], temperature[i], top_k[i], top_p[i], presence_penalty[i], rng_seeds[i], st)) return rc;
+            drafts[(size_t)i] = sample_row(s, slots[i]).mode != KR_MS_LOOP;
+        }
+    if (max_tokens == 0) return KR_OK;
     // a run over positions [pos, pos + k] must stay inside the slot and the rope tables (check_args' limits)
     int limit = s->multi->max_seq;
     if (s->max_rope_seq > 0) limit = std::min(limit, s->max_rope_seq);
@@ -439,7 +506,7 @@ int lookup_impl(kr_decode_store* s, int n, const int32_t* slots, const int32_t* 
         for (int k = 0; k < m; k++) {
             const int i = act[(size_t)k];
             int32_t draft[KR_VERIFY_MAX];
-            int d = max_draft > 0 ? ix[(size_t)i].draft(max_draft, draft) : 0;
+            int d = max_draft > 0 && drafts[(size_t)i] ? ix[(size_t)i].draft(max_draft, draft) : 0;
             d = std::min(d, max_tokens - n_out[i] - 1);                   // the pass yields at most d + 1 tokens
             d = std::min(d, limit - ps[(size_t)i] - 1);
             d = std::max(std::min(d, fit), 0);
@@ -452,10 +519,10 @@ int lookup_impl(kr_decode_store* s, int n, const int32_t* slots, const int32_t* 
         passes++;
         greedy.resize(run.size());
         if (!any) {      // the plain loop's step
-            if (int rc = step_impl(s, m, sl.data(), run.data(), rp.data(), greedy.data(), nullptr, st)) return rc;
+            if (int rc = step_impl(s, m, sl.data(), run.data(), rp.data(), greedy.data(), nullptr, st, sample)) return rc;
             std::fill(nm.begin(), nm.end(), 0);
-        } else if (int rc = verify_impl(s, m, sl.data(), cn.data(), run.data(), rp.data(), greedy.data(), nm.data(), st)) return rc;
-        // greedy[0 .. n_match] of a row is what the plain loop generates next; a stop id among them ends the row there.  After emitting greedy[j] the plain
+        } else if (int rc = verify_impl(s, m, sl.data(), cn.data(), run.data(), rp.data(), greedy.data(), nm.data(), st, sample)) return rc;
+        // greedy[0 .. n_match] of a row (sample: its sampler's draws) is what the plain loop generates next; a stop id among them ends the row there.  After emitting greedy[j] the plain
         // loop has consumed tokens 0 .. j of the run: that many are kept
         std::vector<int> next;
         size_t g0 = 0;
@@ -572,7 +639,8 @@ extern "C" int kr_sample_rows(const float* logits, int n, int vocab, const float
     const size_t V = (size_t)vocab, words = (V + 31) / 32;
     kr_multi_state M;
     DevBuf lg, sn, rg, ids;
-    if (sampler_scratch(M, vocab, n, rows) || lg.ensure((size_t)n * V * 4) || sn.ensure((size_t)n * words * 4) || rg.ensure((size_t)n * 8) || ids.ensure((size_t)n * 4))
+    if (int rc = sampler_scratch(M, vocab, n, rows)) return rc;
+    if (lg.ensure((size_t)n * V * 4) || sn.ensure((size_t)n * words * 4) || rg.ensure((size_t)n * 8) || ids.ensure((size_t)n * 4))
         return kr_fail(KR_ERR_HIP, "hipMalloc failed");
     KR_HIP(hipMemcpy(lg.p, logits, (size_t)n * V * 4, hipMemcpyHostToDevice));
     if (seen) KR_HIP(hipMemcpy(sn.p, seen, (size_t)n * words * 4, hipMemcpyHostToDevice));
@@ -587,18 +655,26 @@ extern "C" int kr_sample_rows(const float* logits, int n, int vocab, const float
     return KR_OK;
 }
 
-// ---- verify and commit over slots (docs/design/18-multi-verify.md)
-extern "C" int kr_decode_verify_multi(kr_decode_store* s, int n, const int32_t* slots, const int32_t* counts, const int32_t* tokens, const int32_t* positions,
-                                      int32_t* greedy_out, int32_t* n_match_out, void* stream) {
+// ---- verify and commit over slots (docs/design/18-multi-verify.md, 19-multi-verify-sample.md)
+static int verify_entry(kr_decode_store* s, int n, const int32_t* slots, const int32_t* counts, const int32_t* tokens, const int32_t* positions, int32_t* ids_out,
+                        int32_t* n_match_out, bool sample, void* stream) {
     if (int rc = multi_begin(s)) return rc;
     if (int rc = check_args(s, n, counts ? slots : nullptr, counts, tokens, positions, 0)) return rc;
-    if (!greedy_out || !n_match_out) return kr_fail(KR_ERR_VALUE, "null greedy_out / n_match_out");
+    if (!ids_out || !n_match_out) return kr_fail(KR_ERR_VALUE, "null %s / n_match_out", sample ? "sampled_out" : "greedy_out");
     for (int i = 0; i < n; i++)
         if (counts[i] > KR_VERIFY_MAX) return kr_fail(KR_ERR_VALUE, "row %d: a run of %d tokens, at most %d (KR_VERIFY_MAX) in a verify", i, counts[i], KR_VERIFY_MAX);
     KR_HIP(hipSetDevice(s->eng->device));
     hipStream_t st = kr_pick_stream(s->eng, stream);
     if (int rc = order_after_store(s, st)) return rc;
-    return verify_impl(s, n, slots, counts, tokens, positions, greedy_out, n_match_out, st);
+    return verify_impl(s, n, slots, counts, tokens, positions, ids_out, n_match_out, st, sample);
+}
+extern "C" int kr_decode_verify_multi(kr_decode_store* s, int n, const int32_t* slots, const int32_t* counts, const int32_t* tokens, const int32_t* positions,
+                                      int32_t* greedy_out, int32_t* n_match_out, void* stream) {
+    return verify_entry(s, n, slots, counts, tokens, positions, greedy_out, n_match_out, false, stream);
+}
+extern "C" int kr_decode_verify_multi_sample(kr_decode_store* s, int n, const int32_t* slots, const int32_t* counts, const int32_t* tokens, const int32_t* positions,
+                                             int32_t* sampled_out, int32_t* n_match_out, void* stream) {
+    return verify_entry(s, n, slots, counts, tokens, positions, sampled_out, n_match_out, true, stream);
 }
 
 extern "C" int kr_decode_commit_multi(kr_decode_store* s, const int32_t* n_keep) {
@@ -611,6 +687,81 @@ extern "C" int kr_decode_generate_multi_lookup(kr_decode_store* s, int n, const 
                                                const int32_t* first_tokens, const int32_t* start_positions, int max_tokens, int max_draft, int ngram_max,
                                                const int* stop_ids, int n_stop, int32_t* tokens_out, int32_t* n_out, int* n_passes_out,
                                                int32_t* n_accepted_out, void* stream) {
-    return lookup_impl(s, n, slots, contexts, n_context, first_tokens, start_positions, max_tokens, max_draft, ngram_max, stop_ids, n_stop, tokens_out, n_out,
-                       n_passes_out, n_accepted_out, stream);
+    return lookup_impl(s, n, slots, contexts, n_context, first_tokens, start_positions, max_tokens, max_draft, ngram_max, nullptr, nullptr, nullptr, nullptr, nullptr,
+                       stop_ids, n_stop, tokens_out, n_out, n_passes_out, n_accepted_out, stream);
+}
+extern "C" int kr_decode_generate_multi_lookup_sample(kr_decode_store* s, int n, const int32_t* slots, const int32_t* contexts, const int32_t* n_context,
+                                                      const int32_t* first_tokens, const int32_t* start_positions, int max_tokens, int max_draft, int ngram_max,
+                                                      const float* temperature, const int* top_k, const float* top_p, const float* presence_penalty,
+                                                      const uint64_t* rng_seeds, const int* stop_ids, int n_stop, int32_t* tokens_out, int32_t* n_out,
+                                                      int* n_passes_out, int32_t* n_accepted_out, void* stream) {
+    if (!temperature) return kr_fail(KR_ERR_VALUE, "null sampler parameter array");
+    return lookup_impl(s, n, slots, contexts, n_context, first_tokens, start_positions, max_tokens, max_draft, ngram_max, temperature, top_k, top_p, presence_penalty,
+                       rng_seeds, stop_ids, n_stop, tokens_out, n_out, n_passes_out, n_accepted_out, stream);
+}
+
+extern "C" int kr_decode_slot_sampler_get(kr_decode_store* s, int slot, uint32_t* seen_out, uint64_t* rng_out) {
+    if (int rc = multi_begin(s)) return rc;
+    kr_multi_state& M = *s->multi;
+    if (slot < 0 || slot >= M.n_slots) return kr_fail(KR_ERR_VALUE, "slot %d out of range [0, %d)", slot, M.n_slots);
+    if (!seen_out || !rng_out) return kr_fail(KR_ERR_VALUE, "null seen_out / rng_out");
+    const size_t words = ((size_t)s->vocab + 31) / 32;
+    if (M.smp.empty()) { std::fill(seen_out, seen_out + words, 0u); *rng_out = 0; return KR_OK; }      // no sampler was ever set
+    KR_HIP(hipSetDevice(s->eng->device));
+    KR_HIP(hipDeviceSynchronize());          // a sampled step may still be in flight on the caller's stream
+    KR_HIP(hipMemcpy(seen_out, (const uint32_t*)M.smp_seen.p + (size_t)slot * words, words * 4, hipMemcpyDeviceToHost));
+    KR_HIP(hipMemcpy(rng_out, (const uint64_t*)M.smp_rng.p + slot, 8, hipMemcpyDeviceToHost));
+    return KR_OK;
+}
+
+// test aid: the verify-form sampler, the accept kernel and the sampler commit on host rows, run i = "slot" i
+extern "C" int kr_sample_runs(const float* logits, int n, const int32_t* counts, const int32_t* tokens, int vocab, const float* temperature, const int* top_k,
+                              const float* top_p, const float* presence_penalty, uint32_t* seen, uint64_t* rng_state, int32_t* n_keep, int32_t* ids_out,
+                              int32_t* n_match_out, int force_loop) {
+    if (!logits || !counts || !tokens || !temperature || !top_k || !top_p || !presence_penalty || !seen || !rng_state || !n_keep || !ids_out || !n_match_out || vocab <= 0)
+        return kr_fail(KR_ERR_VALUE, "kr_sample_runs: null pointer or empty vocabulary");
+    if (n < 1 || n > KR_MULTI_MAX) return kr_fail(KR_ERR_VALUE, "%d rows, must be in [1, %d]", n, KR_MULTI_MAX);
+    size_t total = 0;
+    for (int i = 0; i < n; i++) {
+        if (!(temperature[i] >= 0.0f)) return kr_fail(KR_ERR_VALUE, "row %d: temperature must be >= 0", i);
+        if (counts[i] < 1 || counts[i] > KR_VERIFY_MAX) return kr_fail(KR_ERR_VALUE, "row %d: a run of %d tokens, must be in [1, %d]", i, counts[i], KR_VERIFY_MAX);
+        for (int t = 0; t < counts[i]; t++)
+            if (tokens[total + t] < 0 || tokens[total + t] >= vocab) return kr_fail(KR_ERR_VALUE, "row %d: token %d of its run, id %d, out of range (vocab %d)", i, t, tokens[total + t], vocab);
+        total += (size_t)counts[i];
+    }
+    int dev_count = 0;
+    if (hipGetDeviceCount(&dev_count) != hipSuccess || dev_count == 0) return kr_fail(KR_ERR_HIP, "no HIP device");
+    std::vector<int32_t> slots((size_t)n), zeros((size_t)n, 0);
+    std::vector<KrMsRow> per_run, rows; std::vector<KrMsAt> at;
+    for (int i = 0; i < n; i++) { slots[(size_t)i] = i; per_run.push_back(mode_row(i, temperature[i], top_k[i], top_p[i], presence_penalty[i], vocab, force_loop != 0)); }
+    size_t T = 0; int max_pos = 0;
+    std::vector<int> row_of;
+    const std::vector<int32_t> h = lay_rows(n, slots.data(), counts, tokens, zeros.data(), T, max_pos, &row_of);
+    run_rows(n, counts, row_of, per_run, rows, at);
+    const size_t V = (size_t)vocab, words = (V + 31) / 32;
+    kr_multi_state M;
+    DevBuf lg, sn, rg, ids, dr, out, keep;
+    if (int rc = sampler_scratch(M, vocab, (int)T, rows)) return rc;
+    if (lg.ensure(T * V * 4) || sn.ensure((size_t)n * words * 4) || rg.ensure((size_t)n * 8) || ids.ensure(T * 4) || dr.ensure(h.size() * 4) ||
+        out.ensure((T + (size_t)n) * 4) || keep.ensure((size_t)n * 4))
+        return kr_fail(KR_ERR_HIP, "hipMalloc failed");
+    for (size_t j = 0; j < T; j++) KR_HIP(hipMemcpy((float*)lg.p + (size_t)row_of[j] * V, logits + j * V, V * 4, hipMemcpyHostToDevice));
+    KR_HIP(hipMemcpy(sn.p, seen, (size_t)n * words * 4, hipMemcpyHostToDevice));
+    KR_HIP(hipMemcpy(rg.p, rng_state, (size_t)n * 8, hipMemcpyHostToDevice));
+    KR_HIP(hipMemcpy(dr.p, h.data(), h.size() * 4, hipMemcpyHostToDevice));
+    const int32_t* d_rows = (const int32_t*)dr.p;
+    if (int rc = sample_runs(M, (const float*)lg.p, vocab, rows, at, d_rows, (uint32_t*)sn.p, words, (uint64_t*)rg.p, (int*)ids.p, nullptr)) return rc;
+    kr_launch_multi_accept((const int*)ids.p, d_rows + T, d_rows + 3 * T, n, (int)T, (int*)out.p, nullptr);
+    KR_HIP(hipGetLastError());
+    KR_HIP(hipDeviceSynchronize());
+    KR_HIP(hipMemcpy(ids_out, out.p, T * 4, hipMemcpyDeviceToHost));
+    KR_HIP(hipMemcpy(n_match_out, (const int32_t*)out.p + T, (size_t)n * 4, hipMemcpyDeviceToHost));
+    for (int i = 0; i < n; i++) n_keep[i] = n_keep[i] < 0 ? n_match_out[i] + 1 : std::min(n_keep[i], n_match_out[i] + 1);
+    KR_HIP(hipMemcpy(keep.p, n_keep, (size_t)n * 4, hipMemcpyHostToDevice));
+    kr_launch_ms_commit((const KrMsRow*)M.smp_rows.p, d_rows + 3 * T, (const int*)keep.p, n, (const int*)ids.p, vocab, (uint32_t*)sn.p, words, (uint64_t*)rg.p, nullptr);
+    KR_HIP(hipGetLastError());
+    KR_HIP(hipDeviceSynchronize());
+    KR_HIP(hipMemcpy(seen, sn.p, (size_t)n * words * 4, hipMemcpyDeviceToHost));
+    KR_HIP(hipMemcpy(rng_state, rg.p, (size_t)n * 8, hipMemcpyDeviceToHost));
+    return KR_OK;
 }

@@ -24,6 +24,8 @@ struct KrMultiLaArgs {
 // max_cnt = a bound on every cnt, at most 1024 (the gate rows the recurrence kernel keeps in LDS).
 // 0: launched; 1: max_cnt out of range or geometry not covered (kd 4 is the caller's check; dk 64 / 128, dv <= 256, dv % 8 == 0)
 int kr_launch_multi_la(const KrMultiLaArgs& a, const int* runs, int n_runs, int max_cnt, hipStream_t st);
+// the pass row of token t < cnt of run i (kernels of kr_multi.hip and kr_multi_sample.hip)
+__device__ __forceinline__ int kr_m_run_row(int i, int off, int cnt, int t) { return t == cnt - 1 ? i : off + t; }
 
 // commit of a verify pass (docs/design/18-multi-verify.md): one linear-attention layer's slot states and the records its verify-form launch left.  A table
 // of these lives on the device (kr_multi_state::v_tab)

@@ -29,7 +29,7 @@ __device__ __forceinline__ float kr_m_sumsq8(const float* x, int n, int l) {
 // pass rows off .. off + cnt - 2 and, the last one, in row i (the pass keeps every run's last token in the first rows for the lm_head); a step is runs of
 // one token, row i alone.  The two kernels below carry the slot's state through the run in registers: per token the operations and order of
 // kr_la_step_kernel (kr_decode_ops.hip), the state loaded once before the first token and stored once after the last.
-__device__ __forceinline__ int kr_m_run_row(int i, int off, int cnt, int t) { return t == cnt - 1 ? i : off + t; }
+// (kr_m_run_row, kr_multi.h, is that mapping.)
 
 // conv1d (kernel 4) + SiLU of every channel of the run's rows, and the shift of the slot's carried inputs.  grid (conv_dim / 256, runs), 256 threads:
 // thread = channel, the slot's four carried inputs in registers for the whole run.  Channel layout (decode.rs:3815): q [0, key_dim), k [key_dim, 2 key_dim),

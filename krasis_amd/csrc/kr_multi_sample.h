@@ -17,6 +17,9 @@ struct KrMsRow {
     int k, top_k;          // k = the candidates drawn from (top_k > 0 && top_k < vocab ? top_k : vocab); top_k as given (LOOP)
     float temperature, inv_temp, top_p, penalty;   // inv_temp = 1.0f / temperature, computed on the host as kr_launch_sample does
 };
+// the verify form (docs/design/19-multi-verify-sample.md): pass row b is token t of run `run` of a verify pass.  It draws as its slot's sampler would after
+// t earlier draws that were the run's tokens 1 .. t: those tokens count as seen, the xorshift64 state is advanced t times more
+struct KrMsAt { int run, t; };
 struct KrMsArgs {
     const float* logits; size_t ld; int V, B;      // the model's logits [B][ld] (read only)
     const KrMsRow* rows_dev; const KrMsRow* rows_host;   // [B], the same rows on the device and on the host
@@ -26,6 +29,13 @@ struct KrMsArgs {
     uint64_t* rng;                                 // slot s: rng[s]
     int* ids;                                      // [B] the drawn / greedy ids
     uint64_t* loop_keys; void* loop_temp; size_t loop_temp_bytes; float* loop_probs;   // LOOP rows: kr_launch_sample's scratch (keys [2][V], rocPRIM temp, probs [V])
+    // the verify form (runs set; null: a step).  B = the T token rows of the pass, rows / at per pass row, ids per pass row; seen and rng are read only
+    const int* runs; const int* tokens;            // device: the pass's run table [n][slot, off, cnt] and the token each pass row consumed [B] (kr_multi.h)
+    const KrMsAt* at_dev; const KrMsAt* at_host;   // [B], the same on the device and on the host
+    uint32_t* hyp_seen; uint64_t* hyp_rng;         // LOOP rows: one staged bitmap [seen_words] and state, reused row after row in stream order
 };
 // all B rows, in stream order; returns non-zero on a launch or sort failure
 int kr_launch_multi_sample(const KrMsArgs& a, hipStream_t st);
+// commit of a verify-form call: run i's slot sampler advanced by its first n_keep[i] draws (ids [T] as that call left them; rows [>= n_runs], row i = run i's)
+void kr_launch_ms_commit(const KrMsRow* rows, const int* runs, const int* n_keep, int n_runs, const int* ids, int V, uint32_t* seen, size_t seen_words,
+                         uint64_t* rng, hipStream_t st);

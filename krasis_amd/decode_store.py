@@ -19,6 +19,15 @@ from .engine import KrasisEngine, _addr
 LOOKUP_MAX_DRAFT = 8
 
 
+def _per_row(v, default, ctype, n):
+    """a sampler parameter of generate_multi / generate_multi_lookup_sample as a C array of n: a scalar for every row, or one value per row"""
+    v = default if v is None else v
+    v = list(v) if isinstance(v, (list, tuple, np.ndarray)) else [v] * n
+    if len(v) != n:
+        raise ValueError(f"{len(v)} sampler values for {n} rows")
+    return (ctype * max(n, 1))(*v)
+
+
 def lookup_draft(history: Sequence[int], ngram_max: int, max_draft: int) -> List[int]:
     """The draft generate_lookup proposes after `history` (kr_lookup_draft; host only): for g = min(ngram_max, n-1) down to 1, the continuation of
     the LATEST earlier occurrence of the trailing g-gram that has one, at most max_draft tokens; [] when no g-gram recurs."""
@@ -446,12 +455,7 @@ class CpuDecodeStore:
             check(self._lib.kr_decode_generate_multi(self._h, n, arr(slots), arr(first_tokens), arr(start_positions), max_tokens, stops, len(stop_ids),
                                                      out, cnt, None))
         else:
-            def rows(v, default, ctype):
-                v = default if v is None else v
-                v = list(v) if isinstance(v, (list, tuple, np.ndarray)) else [v] * n
-                if len(v) != n:
-                    raise ValueError(f"{len(v)} sampler values for {n} rows")
-                return (ctype * max(n, 1))(*v)
+            rows = lambda v, default, ctype: _per_row(v, default, ctype, n)
             check(self._lib.kr_decode_generate_multi_sample(self._h, n, arr(slots), arr(first_tokens), arr(start_positions), max_tokens,
                                                             rows(temperature, 0.0, C.c_float), rows(top_k, 0, C.c_int), rows(top_p, 1.0, C.c_float),
                                                             rows(presence_penalty, 0.0, C.c_float), rows(rng_seeds, 0, C.c_uint64), stops, len(stop_ids),
@@ -501,6 +505,10 @@ class CpuDecodeStore:
         draft ...] (1 to KR_VERIFY_MAX tokens) at positions[i] ....  Returns (greedy_lists, n_match): greedy_lists[i][t] = the greedy id after the first t + 1
         tokens of the run, bit for bit decode_step's on that sequence alone; n_match[i] = the leading draft tokens the model agrees with.  The rows stay
         PENDING until commit_multi: the slots' linear-attention state is untouched, and every other slot call is refused."""
+        return self._verify_multi(self._lib.kr_decode_verify_multi, slots, token_lists, positions)
+
+    def _verify_multi(self, entry, slots, token_lists, positions):
+        """verify_multi / verify_multi_sample: the runs flattened, the call, the ids cut back into one list per row"""
         self._need()
         n = len(slots)
         if len(token_lists) != n or len(positions) != n:
@@ -508,12 +516,12 @@ class CpuDecodeStore:
         flat = [int(t) for run in token_lists for t in run]
         arr = lambda xs: (C.c_int32 * max(len(xs), 1))(*xs)
         counts = [len(run) for run in token_lists]
-        greedy = (C.c_int32 * max(len(flat), 1))(); nm = (C.c_int32 * max(n, 1))()
-        check(self._lib.kr_decode_verify_multi(self._h, n, arr(list(slots)), arr(counts), arr(flat), arr(list(positions)), greedy, nm, None))
+        ids = (C.c_int32 * max(len(flat), 1))(); nm = (C.c_int32 * max(n, 1))()
+        check(entry(self._h, n, arr(list(slots)), arr(counts), arr(flat), arr(list(positions)), ids, nm, None))
         self._multi_verify_rows = n
         out, o = [], 0
         for c in counts:
-            out.append(list(greedy[o:o + c])); o += c
+            out.append(list(ids[o:o + c])); o += c
         return out, list(nm[:n])
 
     def commit_multi(self, n_keep: Sequence[int]) -> None:
@@ -546,6 +554,47 @@ class CpuDecodeStore:
                                                         C.byref(passes), acc, None))
         self.last_multi_lookup_stats = {"passes": passes.value, "accepted": list(acc[:n])}
         return [list(out[i * max_tokens: i * max_tokens + cnt[i]]) for i in range(n)]
+
+    # ------------------------------------------------------------------ sampled speculation over slots (docs/design/19-multi-verify-sample.md)
+    def verify_multi_sample(self, slots: Sequence[int], token_lists: Sequence[Sequence[int]], positions: Sequence[int]):
+        """kr_decode_verify_multi_sample: verify_multi whose ids are drawn by the slots' samplers (set_slot_sampler).  Returns (sampled_lists, n_match):
+        sampled_lists[i][t] for t <= n_match[i] = the id step_multi_sample gives after the first t + 1 tokens of the run are consumed one by one (entries past
+        n_match[i] are unspecified); n_match[i] = the leading draft tokens that equal those draws.  No sampler state is written; the rows stay PENDING until
+        commit_multi, which then also advances each slot's seen set and RNG state by the draws kept."""
+        return self._verify_multi(self._lib.kr_decode_verify_multi_sample, slots, token_lists, positions)
+
+    def generate_multi_lookup_sample(self, slots: Sequence[int], first_tokens: Sequence[int], start_positions: Sequence[int], max_tokens: int,
+                                     contexts: Optional[Sequence[Sequence[int]]] = None, max_draft: int = LOOKUP_MAX_DRAFT, ngram_max: int = 3,
+                                     stop_ids: Sequence[int] = (), temperature=None, top_k=None, top_p=None, presence_penalty=None,
+                                     rng_seeds=None) -> List[List[int]]:
+        """kr_decode_generate_multi_lookup_sample: the tokens, slot states and sampler states of generate_multi(..., temperature=, top_k=, top_p=,
+        presence_penalty=, rng_seeds=) (a scalar or one value per row; defaults 0, 0, 1.0, 0, 0) in fewer passes: prompt-lookup drafts per row, one
+        verify_multi_sample + commit_multi per pass.  last_multi_lookup_stats = {"passes": passes, "accepted": accepted draft tokens per row}."""
+        self._need()
+        n = len(slots)
+        contexts = [[] for _ in range(n)] if contexts is None else [list(c) for c in contexts]
+        if len(contexts) != n:
+            raise ValueError(f"{len(contexts)} contexts for {n} rows")
+        rows = lambda v, default, ctype: _per_row(v, default, ctype, n)
+        arr = lambda xs: (C.c_int32 * max(len(xs), 1))(*xs)
+        flat = [int(t) for c in contexts for t in c]
+        out = (C.c_int32 * max(n * max_tokens, 1))(); cnt = (C.c_int32 * max(n, 1))(); acc = (C.c_int32 * max(n, 1))(); passes = C.c_int()
+        stops = (C.c_int * max(len(stop_ids), 1))(*stop_ids)
+        check(self._lib.kr_decode_generate_multi_lookup_sample(
+            self._h, n, arr(list(slots)), arr(flat), arr([len(c) for c in contexts]), arr(list(first_tokens)), arr(list(start_positions)), max_tokens,
+            max_draft, ngram_max, rows(temperature, 0.0, C.c_float), rows(top_k, 0, C.c_int), rows(top_p, 1.0, C.c_float),
+            rows(presence_penalty, 0.0, C.c_float), rows(rng_seeds, 0, C.c_uint64), stops, len(stop_ids), out, cnt, C.byref(passes), acc, None))
+        self.last_multi_lookup_stats = {"passes": passes.value, "accepted": list(acc[:n])}
+        return [list(out[i * max_tokens: i * max_tokens + cnt[i]]) for i in range(n)]
+
+    def slot_sampler_state(self, slot: int):
+        """kr_decode_slot_sampler_get: (seen-token bitmap as uint32 [(vocab + 31) // 32], xorshift64 state) of the slot's sampler; zeros before any
+        sampler was set."""
+        self._need()
+        seen = np.zeros((self._vocab + 31) // 32, np.uint32)
+        rng = C.c_uint64()
+        check(self._lib.kr_decode_slot_sampler_get(self._h, slot, seen.ctypes.data, C.byref(rng)))
+        return seen, rng.value
 
     def prefill_slot(self, slot: int, tokens: Sequence[int], start_pos: int = 0, chunk: Optional[int] = None) -> int:
         """A prompt straight into a slot: extend_multi over chunks of `chunk` tokens (default KR_EXTEND_MAX_TOKENS).  The slot afterwards equals
