@@ -117,7 +117,8 @@ static inline KrMatDev mv(kr_decode_store* s, int wid) { return s->weights[wid]-
 int kr_ensure_wsum(kr_engine* e, MatSet& ms, hipStream_t st);
 int kr_moe_prefill_prepare(kr_engine* e, int layer, int fast, int routed_only, hipStream_t st);   // kr_engine.cpp: the lazily derived data of a native-GGUF layer, built on `st` now
 void kr_standalone_release(kr_decode_store* s);
-int kr_spec_refuse(kr_decode_store* s);          // kr_decode_prefill.cpp: KR_OK when exact speculative decoding can run on this store
+int kr_exact_refuse(kr_decode_store* s, bool slots);   // kr_decode_prefill.cpp: KR_OK when an exact pass can run on this store -- speculative decoding on its own sequence, or (slots) the multi-sequence step
+int kr_spec_refuse(kr_decode_store* s);          // kr_exact_refuse(s, false)
 int kr_spec_pending_fail(kr_decode_store* s);    // KR_ERR_STATE while a verify waits for its commit
 int kr_standalone_cancelled(kr_decode_store* s);
 // kr_decode_prefill.cpp: the layers + final norm + lm_head GEMM of the multi-sequence pass on `st` in s->multi's arena: n_rows token rows in n_runs runs of

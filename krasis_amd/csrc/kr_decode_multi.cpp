@@ -8,12 +8,14 @@
 // that sequence alone.  The store's own sequence is the hand-over point: prompt pass -> kr_decode_slot_save -> steps -> kr_decode_slot_load.
 // kr_decode_extend_multi (docs/design/17-multi-extend.md) is the same pass with a run of tokens per row: a prompt enters a slot chunk by chunk beside the
 // decode rows of other slots, each run bit-identical to that many kr_decode_step calls, without the store's own sequence.  A step is an extend whose every
-// run has one token: both take one argument check, one flatten and one pass (step_entry / step_impl below).
+// run has one token: both take one argument check, one flatten and one pass (step_entry / step_impl below).  The rows of a call travel as one Rows value
+// from the entry points inward.
 // kr_decode_verify_multi / kr_decode_commit_multi (docs/design/18-multi-verify.md) are that pass once more, for exact greedy speculation: runs of [sampled token,
 // draft] whose linear-attention sections record instead of storing state, the greedy id after every token, and a commit that advances each slot by the tokens
-// kept.  kr_decode_generate_multi_lookup drives them with prompt-lookup drafts per row.  kr_decode_verify_multi_sample (docs/design/19-multi-verify-sample.md)
-// draws every token row with its slot's sampler instead, under the hypothesis that the drafts before it were the sampler's draws; the commit applies the kept
-// draws to the samplers, and kr_decode_generate_multi_lookup_sample is the same loop over both.
+// kept.  kr_decode_verify_multi_sample (docs/design/19-multi-verify-sample.md) draws every token row with its slot's sampler instead, under the hypothesis
+// that the drafts before it were the sampler's draws; the commit applies the kept draws to the samplers.  All four generation entry points
+// (kr_decode_generate_multi, its _sample, _lookup and _lookup_sample forms) are one loop, generate_slots: steps where no row drafts (max_draft 0: always),
+// verify + commit where one does, with the draft rule of kr_lookup_index.h.
 #include <algorithm>
 #include <chrono>
 #include <climits>
@@ -33,33 +35,11 @@ int multi_ready(kr_decode_store* s) {
     if ((int)s->layers.size() != s->n_layers) return kr_fail(KR_ERR_STATE, "finalize_decode was not called");
     return KR_OK;
 }
-// what the multi-sequence step does not run (cf. kr_spec_refuse): tolerance modes, native-GGUF MoE layers, expert parallelism, geometries
-// the per-slot kernels do not cover; a pending verify
+// what the multi-sequence step does not run: a pending verify of the store's own sequence, then what kr_exact_refuse (kr_decode_prefill.cpp) lists for the
+// slots -- the clauses of every exact pass and, among them, those of the per-slot kernels
 int multi_refuse(kr_decode_store* s) {
     if (int rc = kr_spec_pending_fail(s)) return rc;
-    if (s->attn_fast || s->gemm_fast || s->decode_fast)
-        return kr_fail(KR_ERR_STATE, "the multi-sequence step is exact-mode only: the attention mode has tolerance bits set (%d)", s->attn_fast | s->gemm_fast << 1 | s->decode_fast << 2);
-    if (s->opt_multi_attn_fast)
-        for (size_t i = 0; i < s->layers.size(); i++)
-            if (s->layers[i].attn == ATTN_MLA)
-                return kr_fail(KR_ERR_STATE, "the \"multi_attn_fast\" option covers GQA layers only: layer %zu is MLA (set the option to 0 for the exact step)", i);
-    kr_engine* e = s->eng;
-    if (e->ep) return kr_fail(KR_ERR_STATE, "the multi-sequence step does not run under expert parallelism");
-    for (size_t i = 0; i < s->layers.size(); i++) {
-        const DLayer& L = s->layers[i];
-        if (L.attn == ATTN_MLA && !kr_multi_mla_ok(L.klr, L.nd, L.rd))
-            return kr_fail(KR_ERR_VALUE, "multi-sequence step: MLA geometry kv_lora_rank %d nope %d rope %d not covered (kv_lora_rank 512 / 256, rope 64)", L.klr, L.nd, L.rd);
-        if (L.mlp == MLP_MOE) {
-            if (s->own_eng || L.moe_layer >= (int)e->layers.size()) return kr_fail(KR_ERR_STATE, "set_moe_store was not called (MoE layer %d has no engine)", L.moe_layer);
-            if (e->layers[L.moe_layer].gguf)
-                return kr_fail(KR_ERR_STATE, "the multi-sequence step is exact-mode only: MoE layer %d holds native GGUF experts (their prompt pass is tolerance-only)", L.moe_layer);
-        }
-        if (L.attn == ATTN_LA && (L.kd != 4 || (L.dk != 64 && L.dk != 128) || L.dv > 256 || L.dv % 8 || L.nv != L.nk * (L.nv / L.nk)))
-            return kr_fail(KR_ERR_VALUE, "multi-sequence step: linear-attention geometry kd %d dk %d dv %d not covered (kd 4, dk 64 / 128, dv <= 256)", L.kd, L.dk, L.dv);
-        if (L.attn == ATTN_GQA && ((L.hd != 64 && L.hd != 128 && L.hd != 256) || L.nkv < 1 || L.nh % L.nkv || (L.nh / L.nkv) * (L.hd + 64) > 12288))
-            return kr_fail(KR_ERR_VALUE, "multi-sequence step: GQA geometry nh %d nkv %d head_dim %d not covered (head_dim 64 / 128 / 256)", L.nh, L.nkv, L.hd);
-    }
-    return KR_OK;
+    return kr_exact_refuse(s, true);
 }
 int need_slots(kr_decode_store* s) {
     if (!s->multi || s->multi->n_slots == 0) return kr_fail(KR_ERR_STATE, "no sequence slots: call kr_decode_slots_create first");
@@ -75,35 +55,43 @@ int multi_begin(kr_decode_store* s) {
     if (s->multi->v_pending) return kr_fail(KR_ERR_STATE, "a verify over slots is pending: call kr_decode_commit_multi first");
     return multi_refuse(s);
 }
-// the rows of one call, every refusal naming its row: distinct slots in range, tokens in the vocabulary, positions inside the slot and the rope tables (the
-// store's, and every MLA layer's own: the shortest bounds the call).  Row i is a run of counts[i] tokens at positions[i] ... (counts null: one token per
-// row); extra = further positions the caller will consume after the run (generate_impl)
-int check_args(kr_decode_store* s, int n, const int32_t* slots, const int32_t* counts, const int32_t* tokens, const int32_t* positions, int extra) {
+int slot_in_range(kr_decode_store* s, int slot) {
+    return slot < 0 || slot >= s->multi->n_slots ? kr_fail(KR_ERR_VALUE, "slot %d out of range [0, %d)", slot, s->multi->n_slots) : KR_OK;
+}
+// the rows of one call, as they travel from the entry points inward: row i = slot slots[i] runs cnt(i) tokens of `tokens` (the runs in call order) at
+// positions[i] ...
+struct Rows {
+    int n; const int32_t *slots, *counts, *tokens, *positions;      // counts null: one token per row
+    int cnt(int i) const { return counts ? counts[i] : 1; }
+};
+// their check, every refusal naming its row: distinct slots in range, tokens in the vocabulary, positions inside the slot and the rope tables (the store's, and
+// every MLA layer's own: the shortest bounds the call).  extra = further positions the caller will consume after the run (generate_slots)
+int check_args(kr_decode_store* s, const Rows& r, int extra) {
     const kr_multi_state& M = *s->multi;
-    if (n < 1 || n > KR_MULTI_MAX) return kr_fail(KR_ERR_VALUE, "%d rows, must be in [1, %d]", n, KR_MULTI_MAX);
-    if (!slots || !tokens || !positions) return kr_fail(KR_ERR_VALUE, "null slots / counts / tokens / positions");
+    if (r.n < 1 || r.n > KR_MULTI_MAX) return kr_fail(KR_ERR_VALUE, "%d rows, must be in [1, %d]", r.n, KR_MULTI_MAX);
+    if (!r.slots || !r.tokens || !r.positions) return kr_fail(KR_ERR_VALUE, "null slots / counts / tokens / positions");
     std::vector<char> seen((size_t)M.n_slots, 0);
     int mla_rope = 0; bool has_mla = false;
     for (const DLayer& L : s->layers) if (L.attn == ATTN_MLA) { mla_rope = has_mla ? std::min(mla_rope, L.mla_rope_seq) : L.mla_rope_seq; has_mla = true; }
-    auto cnt = [&](int i) { return counts ? counts[i] : 1; };
     int total = 0;
-    for (int i = 0; i < n; i++) {      // the runs first: everything below indexes tokens by them
-        if (cnt(i) < 1) return kr_fail(KR_ERR_VALUE, "row %d: a run of %d tokens, must be at least 1", i, cnt(i));
-        if (cnt(i) > KR_EXTEND_MAX_TOKENS - total)
-            return kr_fail(KR_ERR_VALUE, "row %d: its run of %d tokens brings the call past %d tokens (KR_EXTEND_MAX_TOKENS)", i, cnt(i), KR_EXTEND_MAX_TOKENS);
-        total += cnt(i);
+    for (int i = 0; i < r.n; i++) {      // the runs first: everything below indexes tokens by them
+        if (r.cnt(i) < 1) return kr_fail(KR_ERR_VALUE, "row %d: a run of %d tokens, must be at least 1", i, r.cnt(i));
+        if (r.cnt(i) > KR_EXTEND_MAX_TOKENS - total)
+            return kr_fail(KR_ERR_VALUE, "row %d: its run of %d tokens brings the call past %d tokens (KR_EXTEND_MAX_TOKENS)", i, r.cnt(i), KR_EXTEND_MAX_TOKENS);
+        total += r.cnt(i);
     }
     total = 0;
-    for (int i = 0; i < n; i++) {
-        if (slots[i] < 0 || slots[i] >= M.n_slots) return kr_fail(KR_ERR_VALUE, "row %d: slot %d out of range [0, %d)", i, slots[i], M.n_slots);
-        if (seen[(size_t)slots[i]]++) return kr_fail(KR_ERR_VALUE, "row %d: slot %d is named twice", i, slots[i]);
-        for (int t = 0; t < cnt(i); t++) {
-            const int tk = tokens[(size_t)total + t];
+    for (int i = 0; i < r.n; i++) {
+        const int slot = r.slots[i], pos = r.positions[i];
+        if (slot < 0 || slot >= M.n_slots) return kr_fail(KR_ERR_VALUE, "row %d: slot %d out of range [0, %d)", i, slot, M.n_slots);
+        if (seen[(size_t)slot]++) return kr_fail(KR_ERR_VALUE, "row %d: slot %d is named twice", i, slot);
+        for (int t = 0; t < r.cnt(i); t++) {
+            const int tk = r.tokens[(size_t)total + t];
             if (tk < 0 || tk >= s->vocab) return kr_fail(KR_ERR_VALUE, "row %d: token %d of its run, id %d, out of range (vocab %d)", i, t, tk, s->vocab);
         }
-        total += cnt(i);
-        const long long last = (long long)positions[i] + cnt(i) - 1 + extra;     // the last position this row consumes
-        if (positions[i] < 0 || last >= M.max_seq) return kr_fail(KR_ERR_VALUE, "row %d: positions [%d, %lld] outside the slot's [0, %d)", i, positions[i], last, M.max_seq);
+        total += r.cnt(i);
+        const long long last = (long long)pos + r.cnt(i) - 1 + extra;     // the last position this row consumes
+        if (pos < 0 || last >= M.max_seq) return kr_fail(KR_ERR_VALUE, "row %d: positions [%d, %lld] outside the slot's [0, %d)", i, pos, last, M.max_seq);
         if (s->max_rope_seq > 0 && last >= s->max_rope_seq) return kr_fail(KR_ERR_VALUE, "row %d: position %lld past the rope table (%d)", i, last, s->max_rope_seq);
         if (has_mla && last >= mla_rope) return kr_fail(KR_ERR_VALUE, "row %d: position %lld past the MLA rope table (%d)", i, last, mla_rope);
     }
@@ -154,32 +142,31 @@ KrMsArgs sampler_args(kr_multi_state& M, const float* logits, int vocab, int n, 
 // the rows of a pass -> M.rows on the device: [slots | tokens | positions] of T token rows, then the runs [n][slot, off, cnt] (kr_multi.h).  The last token of
 // run i is row i and the others follow from row n on in call order (unit counts: row i = token i, off = n)
 // lay_rows: that layout on the host (row_of, optional: the pass row of every token in call order)
-std::vector<int32_t> lay_rows(int n, const int32_t* slots, const int32_t* counts, const int32_t* tokens, const int32_t* positions, size_t& T, int& max_pos,
-                              std::vector<int>* row_of = nullptr) {
-    auto cnt = [&](int i) { return counts ? counts[i] : 1; };
+std::vector<int32_t> lay_rows(const Rows& r, size_t& T, int& max_pos, std::vector<int>* row_of = nullptr) {
+    const int n = r.n;
     T = 0;
-    for (int i = 0; i < n; i++) T += (size_t)cnt(i);
+    for (int i = 0; i < n; i++) T += (size_t)r.cnt(i);
     std::vector<int32_t> h(3 * T + (size_t)3 * n);
     if (row_of) row_of->resize(T);
     max_pos = 0;
     size_t src = 0, off = (size_t)n;
     for (int i = 0; i < n; i++) {
+        const int c = r.cnt(i);
         int32_t* run = &h[3 * T + (size_t)3 * i];
-        run[0] = slots[i]; run[1] = (int32_t)off; run[2] = cnt(i);
-        for (int t = 0; t < cnt(i); t++) {
-            const size_t row = t == cnt(i) - 1 ? (size_t)i : off + t;
-            h[row] = slots[i]; h[T + row] = tokens[src + t]; h[2 * T + row] = positions[i] + t;
+        run[0] = r.slots[i]; run[1] = (int32_t)off; run[2] = c;
+        for (int t = 0; t < c; t++) {
+            const size_t row = t == c - 1 ? (size_t)i : off + t;
+            h[row] = r.slots[i]; h[T + row] = r.tokens[src + t]; h[2 * T + row] = r.positions[i] + t;
             if (row_of) (*row_of)[src + t] = (int)row;
         }
-        src += (size_t)cnt(i); off += (size_t)cnt(i) - 1;
-        max_pos = std::max(max_pos, positions[i] + cnt(i) - 1);
+        src += (size_t)c; off += (size_t)c - 1;
+        max_pos = std::max(max_pos, r.positions[i] + c - 1);
     }
     return h;
 }
-int put_rows(kr_multi_state& M, int n, const int32_t* slots, const int32_t* counts, const int32_t* tokens, const int32_t* positions, hipStream_t st, size_t& T,
-             int& max_pos, std::vector<int>* row_of = nullptr) {
+int put_rows(kr_multi_state& M, const Rows& r, hipStream_t st, size_t& T, int& max_pos, std::vector<int>* row_of = nullptr) {
     if (M.rows.ensure((size_t)3 * (KR_EXTEND_MAX_TOKENS + KR_MULTI_MAX) * 4)) return kr_fail(KR_ERR_HIP, "hipMalloc of the step's row buffers failed");
-    const std::vector<int32_t> h = lay_rows(n, slots, counts, tokens, positions, T, max_pos, row_of);
+    const std::vector<int32_t> h = lay_rows(r, T, max_pos, row_of);
     KR_HIP(hipMemcpyAsync(M.rows.p, h.data(), h.size() * 4, hipMemcpyHostToDevice, st));      // pageable source: staged before the call returns
     return KR_OK;
 }
@@ -202,29 +189,39 @@ int sample_runs(kr_multi_state& M, const float* logits, int vocab, const std::ve
     if (kr_launch_multi_sample(a, st)) return kr_fail(KR_ERR_HIP, "batched sampler launch failed");
     return KR_OK;
 }
-// one pass, arguments checked: rows -> device, the pass, per-row argmax (sample: each slot's sampler), ids (and logits) back; returns once next_out is written.
-// Row i is a run of counts[i] tokens at positions[i] ... (counts null: one token per row, a step); the pass has one row per token, the last token of run i in
-// row i and the others from row n on in call order, so everything after the pass (logits, argmax, sampler) sees n rows
-int step_impl(kr_decode_store* s, int n, const int32_t* slots, const int32_t* tokens, const int32_t* positions, int32_t* next_out, float* logits_out, hipStream_t st,
-              bool sample = false, const int32_t* counts = nullptr) {
+// what step_impl and verify_impl open with: the rows to the device, then the pass's sampler rows -- one per run, or in the verify form one per token row
+// with the (run, t) table -- and the scratch for them.  sr stays empty when the pass is greedy: sample unset, or no slot of it has a sampler that draws
+struct Pass { size_t T = 0; int max_pos = 0; std::vector<KrMsRow> sr; std::vector<KrMsAt> at; };
+int open_pass(kr_decode_store* s, const Rows& r, bool sample, bool verify, hipStream_t st, Pass& p) {
     kr_multi_state& M = *s->multi;
-    if (M.ids.ensure((size_t)KR_MULTI_MAX * 4)) return kr_fail(KR_ERR_HIP, "hipMalloc of the step's row buffers failed");
-    std::vector<KrMsRow> sr;
+    std::vector<int> row_of;
+    if (int rc = put_rows(M, r, st, p.T, p.max_pos, verify ? &row_of : nullptr)) return rc;
+    std::vector<KrMsRow> per_run;
     bool greedy = true;
-    if (sample) {
-        for (int i = 0; i < n; i++) { sr.push_back(sample_row(s, slots[i])); greedy &= sr.back().mode == KR_MS_GREEDY; }
-        if (!greedy) if (int rc = sampler_scratch(M, s->vocab, n, sr)) return rc;
-    }
-    size_t T = 0; int max_pos = 0;
-    if (int rc = put_rows(M, n, slots, counts, tokens, positions, st, T, max_pos)) return rc;
-    if (!greedy) KR_HIP(hipMemcpyAsync(M.smp_rows.p, sr.data(), sr.size() * sizeof(KrMsRow), hipMemcpyHostToDevice, st));
-    if (int rc = kr_multi_pass(s, (int)T, n, (const int32_t*)M.rows.p, (const int32_t*)M.rows.p + 3 * T, max_pos, st)) { (void)hipStreamSynchronize(st); return rc; }
+    if (sample) for (int i = 0; i < r.n; i++) { per_run.push_back(sample_row(s, r.slots[i])); greedy &= per_run.back().mode == KR_MS_GREEDY; }
+    if (greedy) return KR_OK;
+    if (verify) run_rows(r.n, r.counts, row_of, per_run, p.sr, p.at);
+    else p.sr.swap(per_run);
+    return sampler_scratch(M, s->vocab, (int)p.sr.size(), p.sr);
+}
+// and what they close with when the pass or a sampler launch failed: nothing of it is left in flight
+int fail_pass(hipStream_t st, int rc) { (void)hipStreamSynchronize(st); return rc; }
+// one pass, arguments checked: rows -> device, the pass, per-row argmax (sample: each slot's sampler), ids (and logits) back; returns once next_out is written.
+// The pass has one row per token, the last token of run i in row i and the others from row n on in call order, so everything after the pass (logits, argmax,
+// sampler) sees n rows
+int step_impl(kr_decode_store* s, const Rows& r, int32_t* next_out, float* logits_out, hipStream_t st, bool sample) {
+    kr_multi_state& M = *s->multi;
+    const int n = r.n;
+    if (M.ids.ensure((size_t)KR_MULTI_MAX * 4)) return kr_fail(KR_ERR_HIP, "hipMalloc of the step's row buffers failed");
+    Pass p;
+    if (int rc = open_pass(s, r, sample, false, st, p)) return rc;
+    const bool greedy = p.sr.empty();
+    if (!greedy) KR_HIP(hipMemcpyAsync(M.smp_rows.p, p.sr.data(), p.sr.size() * sizeof(KrMsRow), hipMemcpyHostToDevice, st));
+    if (int rc = kr_multi_pass(s, (int)p.T, n, (const int32_t*)M.rows.p, (const int32_t*)M.rows.p + 3 * p.T, p.max_pos, st)) return fail_pass(st, rc);
     const size_t V = (size_t)s->vocab;
     if (greedy) kr_launch_multi_argmax((const float*)M.logits.p, V, (int)V, n, (int*)M.ids.p, st);
-    else if (kr_launch_multi_sample(sampler_args(M, (const float*)M.logits.p, s->vocab, n, sr, (uint32_t*)M.smp_seen.p, M.smp_words, (uint64_t*)M.smp_rng.p, (int*)M.ids.p), st)) {
-        (void)hipStreamSynchronize(st);
-        return kr_fail(KR_ERR_HIP, "batched sampler launch failed");
-    }
+    else if (kr_launch_multi_sample(sampler_args(M, (const float*)M.logits.p, s->vocab, n, p.sr, (uint32_t*)M.smp_seen.p, M.smp_words, (uint64_t*)M.smp_rng.p, (int*)M.ids.p), st))
+        return fail_pass(st, kr_fail(KR_ERR_HIP, "batched sampler launch failed"));
     KR_HIP(hipGetLastError());
     KR_HIP(hipMemcpyAsync(next_out, M.ids.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
     if (logits_out) KR_HIP(hipMemcpyAsync(logits_out, M.logits.p, (size_t)n * V * 4, is_device_ptr(logits_out) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
@@ -241,22 +238,21 @@ int order_after_store(kr_decode_store* s, hipStream_t st) {
     return KR_OK;
 }
 // the three stepping entry points: refusals, then the pass on the caller's stream
-int step_entry(kr_decode_store* s, int n, const int32_t* slots, const int32_t* counts, const int32_t* tokens, const int32_t* positions,
-               int32_t* next_out, float* logits_out, bool sample, void* stream) {
+int step_entry(kr_decode_store* s, const Rows& r, int32_t* next_out, float* logits_out, bool sample, void* stream) {
     if (int rc = multi_begin(s)) return rc;
-    if (int rc = check_args(s, n, slots, counts, tokens, positions, 0)) return rc;
+    if (int rc = check_args(s, r, 0)) return rc;
     if (!next_out) return kr_fail(KR_ERR_VALUE, "null next_out");
     KR_HIP(hipSetDevice(s->eng->device));
     hipStream_t st = kr_pick_stream(s->eng, stream);
     if (int rc = order_after_store(s, st)) return rc;
-    return step_impl(s, n, slots, tokens, positions, next_out, logits_out, st, sample, counts);
+    return step_impl(s, r, next_out, logits_out, st, sample);
 }
 // slot <-> the store's own sequence: KV rows [0, seq_len) of every GQA layer, compressed-KV and rope-key rows [0, seq_len) of every MLA layer, conv +
 // recurrent state of every linear-attention layer
 int slot_copy(kr_decode_store* s, int slot, int seq_len, bool save) {
     if (int rc = multi_begin(s)) return rc;
+    if (int rc = slot_in_range(s, slot)) return rc;
     kr_multi_state& M = *s->multi;
-    if (slot < 0 || slot >= M.n_slots) return kr_fail(KR_ERR_VALUE, "slot %d out of range [0, %d)", slot, M.n_slots);
     const int lim = std::min(s->kv_max_seq, M.max_seq);
     if (seq_len < 0 || seq_len > lim) return kr_fail(KR_ERR_VALUE, "seq_len %d outside [0, %d] (store kv_max_seq %d, slot max_seq %d)", seq_len, lim, s->kv_max_seq, M.max_seq);
     for (size_t i = 0; i < s->layers.size(); i++)
@@ -305,50 +301,6 @@ int set_sampler(kr_decode_store* s, int slot, int first_token, float temperature
     p.temperature = temperature; p.top_k = top_k; p.top_p = top_p; p.penalty = presence_penalty;
     return KR_OK;
 }
-// kr_decode_generate_multi and its sampled form: every row's sampler set first (sample), then the steps; a finished row leaves the batch
-int generate_impl(kr_decode_store* s, int n, const int32_t* slots, const int32_t* first_tokens, const int32_t* start_positions, int max_tokens, const float* temperature,
-                  const int* top_k, const float* top_p, const float* presence_penalty, const uint64_t* rng_seeds, const int* stop_ids, int n_stop,
-                  int32_t* tokens_out, int32_t* n_out, void* stream) {
-    const bool sample = temperature != nullptr;
-    if (int rc = multi_begin(s)) return rc;
-    if (max_tokens < 0) return kr_fail(KR_ERR_VALUE, "max_tokens %d < 0", max_tokens);
-    if (n_stop < 0 || (n_stop > 0 && !stop_ids)) return kr_fail(KR_ERR_VALUE, "bad stop ids (%d)", n_stop);
-    if (!n_out || (max_tokens > 0 && !tokens_out)) return kr_fail(KR_ERR_VALUE, "null output pointer");
-    // every row's last step (position start + max_tokens - 1) must fit its slot: checked here, before the first step
-    if (int rc = check_args(s, n, slots, nullptr, first_tokens, start_positions, std::max(max_tokens - 1, 0))) return rc;
-    if (sample) {
-        if (!top_k || !top_p || !presence_penalty || !rng_seeds) return kr_fail(KR_ERR_VALUE, "null sampler parameter array");
-        for (int i = 0; i < n; i++) if (!(temperature[i] >= 0.0f)) return kr_fail(KR_ERR_VALUE, "row %d: temperature must be >= 0", i);
-    }
-    for (int i = 0; i < n; i++) n_out[i] = 0;
-    if (max_tokens == 0 && !sample) return KR_OK;
-    KR_HIP(hipSetDevice(s->eng->device));
-    hipStream_t st = kr_pick_stream(s->eng, stream);
-    if (int rc = order_after_store(s, st)) return rc;
-    if (sample)
-        for (int i = 0; i < n; i++)
-            if (int rc = set_sampler(s, slots[i], first_tokens[i], temperature[i], top_k[i], top_p[i], presence_penalty[i], rng_seeds[i], st)) return rc;
-    if (max_tokens == 0) return KR_OK;
-    auto is_stop = [&](int t) { for (int j = 0; j < n_stop; j++) if (stop_ids[j] == t) return true; return false; };
-    std::vector<int> act((size_t)n);                           // rows still generating, in caller order
-    std::vector<int32_t> sl((size_t)n), tk((size_t)n), ps((size_t)n), nx((size_t)n);
-    for (int i = 0; i < n; i++) { act[(size_t)i] = i; tk[(size_t)i] = first_tokens[i]; ps[(size_t)i] = start_positions[i]; }
-    while (!act.empty()) {
-        const int m = (int)act.size();
-        std::vector<int32_t> rt((size_t)m), rp((size_t)m);
-        for (int k = 0; k < m; k++) { const int i = act[(size_t)k]; sl[(size_t)k] = slots[i]; rt[(size_t)k] = tk[(size_t)i]; rp[(size_t)k] = ps[(size_t)i]; }
-        if (int rc = step_impl(s, m, sl.data(), rt.data(), rp.data(), nx.data(), nullptr, st, sample)) return rc;
-        std::vector<int> keep;
-        for (int k = 0; k < m; k++) {
-            const int i = act[(size_t)k], t = nx[(size_t)k];
-            tokens_out[(size_t)i * max_tokens + n_out[i]++] = t;
-            tk[(size_t)i] = t; ps[(size_t)i]++;
-            if (!is_stop(t) && n_out[i] < max_tokens) keep.push_back(i);   // a finished row leaves the batch: its slot is not stepped again
-        }
-        act.swap(keep);
-    }
-    return KR_OK;
-}
 
 // ---- verify over slots (docs/design/18-multi-verify.md)
 // the record slices of every linear-attention layer for T token rows and the table of those layers, host and device.  Per row and layer: conv_dim + nk dk +
@@ -381,39 +333,28 @@ int verify_records(kr_decode_store* s, size_t T, hipStream_t st) {
 }
 // one verify pass, arguments checked: rows -> device, the pass in its verify form, the greedy id of every token row (sample: the draw of its slot's sampler
 // under the hypothesis that the run's drafts before it were drawn; no sampler state is written), the accept kernel, one copy back.  Leaves the rows pending
-int verify_impl(kr_decode_store* s, int n, const int32_t* slots, const int32_t* counts, const int32_t* tokens, const int32_t* positions, int32_t* greedy_out,
-                int32_t* n_match_out, hipStream_t st, bool sample = false) {
+int verify_impl(kr_decode_store* s, const Rows& r, int32_t* ids_out, int32_t* n_match_out, hipStream_t st, bool sample) {
     kr_multi_state& M = *s->multi;
-    size_t T = 0; int max_pos = 0;
-    std::vector<int> row_of;
-    if (int rc = put_rows(M, n, slots, counts, tokens, positions, st, T, max_pos, &row_of)) return rc;
-    std::vector<KrMsRow> sr; std::vector<KrMsAt> at;
-    bool greedy = true;
-    if (sample) {
-        std::vector<KrMsRow> per_run;
-        for (int i = 0; i < n; i++) { per_run.push_back(sample_row(s, slots[i])); greedy &= per_run.back().mode == KR_MS_GREEDY; }
-        if (!greedy) {
-            run_rows(n, counts, row_of, per_run, sr, at);
-            if (int rc = sampler_scratch(M, s->vocab, (int)T, sr)) return rc;
-        }
-    }
+    const int n = r.n;
+    Pass p;
+    if (int rc = open_pass(s, r, sample, true, st, p)) return rc;
+    const size_t T = p.T;
+    const bool greedy = p.sr.empty();
     if (M.ids.ensure((size_t)KR_EXTEND_MAX_TOKENS * 4) || M.v_out.ensure((size_t)(KR_EXTEND_MAX_TOKENS + KR_MULTI_MAX) * 4) || M.v_keep.ensure((size_t)KR_MULTI_MAX * 4))
         return kr_fail(KR_ERR_HIP, "hipMalloc of the verify's row buffers failed");
-    if (int rc = verify_records(s, T, st)) { (void)hipStreamSynchronize(st); return rc; }
+    if (int rc = verify_records(s, T, st)) return fail_pass(st, rc);
     const int32_t* d_rows = (const int32_t*)M.rows.p;
-    if (int rc = kr_multi_pass(s, (int)T, n, d_rows, d_rows + 3 * T, max_pos, st, true)) { (void)hipStreamSynchronize(st); return rc; }
+    if (int rc = kr_multi_pass(s, (int)T, n, d_rows, d_rows + 3 * T, p.max_pos, st, true)) return fail_pass(st, rc);
     const size_t V = (size_t)s->vocab;
     if (greedy) kr_launch_multi_argmax((const float*)M.logits.p, V, (int)V, (int)T, (int*)M.ids.p, st);
-    else if (int rc = sample_runs(M, (const float*)M.logits.p, s->vocab, sr, at, d_rows, (uint32_t*)M.smp_seen.p, M.smp_words, (uint64_t*)M.smp_rng.p, (int*)M.ids.p, st)) {
-        (void)hipStreamSynchronize(st);
-        return rc;
-    }
+    else if (int rc = sample_runs(M, (const float*)M.logits.p, s->vocab, p.sr, p.at, d_rows, (uint32_t*)M.smp_seen.p, M.smp_words, (uint64_t*)M.smp_rng.p, (int*)M.ids.p, st))
+        return fail_pass(st, rc);
     kr_launch_multi_accept((const int*)M.ids.p, d_rows + T, d_rows + 3 * T, n, (int)T, (int*)M.v_out.p, st);
     KR_HIP(hipGetLastError());
     std::vector<int32_t> out(T + (size_t)n);
     KR_HIP(hipMemcpyAsync(out.data(), M.v_out.p, out.size() * 4, hipMemcpyDeviceToHost, st));
     KR_HIP(hipStreamSynchronize(st));
-    std::copy(out.begin(), out.begin() + (ptrdiff_t)T, greedy_out);
+    std::copy(out.begin(), out.begin() + (ptrdiff_t)T, ids_out);
     M.v_match.assign(out.begin() + (ptrdiff_t)T, out.end());
     std::copy(M.v_match.begin(), M.v_match.end(), n_match_out);
     M.v_pending = true; M.v_sampled = !greedy; M.v_st = st; M.v_rows = T;
@@ -444,107 +385,100 @@ int commit_impl(kr_decode_store* s, const int32_t* n_keep) {
     M.v_pending = false;
     return KR_OK;
 }
-// kr_decode_generate_multi_lookup: generate_impl's loop with prompt-lookup drafts per row (kr_decode_generate_lookup's rule and clamps).  temperature set: the
-// sampled form -- every row's sampler set first as generate_impl sets it, the passes sampled; a row on the per-row sampler path (KR_MS_LOOP) does not draft
-int lookup_impl(kr_decode_store* s, int n, const int32_t* slots, const int32_t* contexts, const int32_t* n_context, const int32_t* first_tokens,
-                const int32_t* start_positions, int max_tokens, int max_draft, int ngram_max, const float* temperature, const int* top_k, const float* top_p,
-                const float* presence_penalty, const uint64_t* rng_seeds, const int* stop_ids, int n_stop, int32_t* tokens_out, int32_t* n_out,
-                int* n_passes_out, int32_t* n_accepted_out, void* stream) {
-    const bool sample = temperature != nullptr;
+// the arguments of the generation entry points that travel together: the per-row sampler columns of the sampled forms (the greedy forms pass no SamplerCols),
+// the drafting of the lookup forms (the plain forms: no contexts, max_draft 0), the outputs (the plain forms: no stats)
+struct SamplerCols { const float* temperature; const int* top_k; const float* top_p; const float* presence_penalty; const uint64_t* rng_seeds; };
+struct Drafting { const int32_t *contexts, *n_context; int max_draft, ngram_max; };
+struct GenOut { int32_t *tokens, *n; int* n_passes; int32_t* n_accepted; };
+// the one generation loop over slots, behind all four entry points: row i starts with first.tokens[i] at first.positions[i]; every row's sampler is set first
+// (smp), then passes over the rows still generating -- a finished row leaves the batch and its slot is not touched again.  A pass is a step (step_impl) where no
+// row drafts -- with max_draft 0 every pass, and then no index is kept -- and a verify + commit where one does: prompt-lookup drafts per row under the
+// rule of kr_lookup_index.h (kr_decode_generate_lookup's); a row on the per-row sampler path (KR_MS_LOOP) does not draft
+int generate_slots(kr_decode_store* s, const Rows& first, int max_tokens, const Drafting& dr, const SamplerCols* smp, const int* stop_ids, int n_stop, const GenOut& out,
+                   void* stream) {
+    if (smp && !smp->temperature) return kr_fail(KR_ERR_VALUE, "null sampler parameter array");      // ahead of every other check, the store's included
+    const int n = first.n, max_draft = dr.max_draft;
     if (int rc = multi_begin(s)) return rc;
     if (max_tokens < 0) return kr_fail(KR_ERR_VALUE, "max_tokens %d < 0", max_tokens);
     if (n_stop < 0 || (n_stop > 0 && !stop_ids)) return kr_fail(KR_ERR_VALUE, "bad stop ids (%d)", n_stop);
-    if (!n_out || (max_tokens > 0 && !tokens_out)) return kr_fail(KR_ERR_VALUE, "null output pointer");
+    if (!out.n || (max_tokens > 0 && !out.tokens)) return kr_fail(KR_ERR_VALUE, "null output pointer");
     if (max_draft < 0 || max_draft > KR_VERIFY_MAX - 1) return kr_fail(KR_ERR_VALUE, "max_draft %d out of range [0, %d]", max_draft, KR_VERIFY_MAX - 1);
-    if (ngram_max < 1 || ngram_max > KR_LOOKUP_NGRAM_MAX) return kr_fail(KR_ERR_VALUE, "ngram_max %d out of range [1, %d]", ngram_max, KR_LOOKUP_NGRAM_MAX);
-    if (int rc = check_args(s, n, slots, nullptr, first_tokens, start_positions, std::max(max_tokens - 1, 0))) return rc;
+    if (dr.ngram_max < 1 || dr.ngram_max > KR_LOOKUP_NGRAM_MAX) return kr_fail(KR_ERR_VALUE, "ngram_max %d out of range [1, %d]", dr.ngram_max, KR_LOOKUP_NGRAM_MAX);
+    // every row's last step (position start + max_tokens - 1) must fit its slot: checked here, before the first pass
+    if (int rc = check_args(s, first, std::max(max_tokens - 1, 0))) return rc;
     std::vector<size_t> c0((size_t)n + 1, 0);      // row i's context = contexts[c0[i] .. c0[i + 1])
     for (int i = 0; i < n; i++) {
-        const int nc = n_context ? n_context[i] : 0;
-        if (nc < 0 || (nc > 0 && !contexts)) return kr_fail(KR_ERR_VALUE, "row %d: bad context (%d tokens)", i, nc);
+        const int nc = dr.n_context ? dr.n_context[i] : 0;
+        if (nc < 0 || (nc > 0 && !dr.contexts)) return kr_fail(KR_ERR_VALUE, "row %d: bad context (%d tokens)", i, nc);
         c0[(size_t)i + 1] = c0[(size_t)i] + (size_t)nc;
         for (size_t j = c0[(size_t)i]; j < c0[(size_t)i + 1]; j++)      // a context token becomes a draft token: it must be a valid id
-            if (contexts[j] < 0 || contexts[j] >= s->vocab) return kr_fail(KR_ERR_VALUE, "row %d: context token id %d out of range (vocab %d)", i, contexts[j], s->vocab);
+            if (dr.contexts[j] < 0 || dr.contexts[j] >= s->vocab) return kr_fail(KR_ERR_VALUE, "row %d: context token id %d out of range (vocab %d)", i, dr.contexts[j], s->vocab);
     }
-    if (sample) {
-        if (!top_k || !top_p || !presence_penalty || !rng_seeds) return kr_fail(KR_ERR_VALUE, "null sampler parameter array");
-        for (int i = 0; i < n; i++) if (!(temperature[i] >= 0.0f)) return kr_fail(KR_ERR_VALUE, "row %d: temperature must be >= 0", i);
+    if (smp) {      // the other four columns come after the rows: a call wrong in both names its row
+        if (!smp->top_k || !smp->top_p || !smp->presence_penalty || !smp->rng_seeds) return kr_fail(KR_ERR_VALUE, "null sampler parameter array");
+        for (int i = 0; i < n; i++) if (!(smp->temperature[i] >= 0.0f)) return kr_fail(KR_ERR_VALUE, "row %d: temperature must be >= 0", i);
     }
-    for (int i = 0; i < n; i++) { n_out[i] = 0; if (n_accepted_out) n_accepted_out[i] = 0; }
-    if (n_passes_out) *n_passes_out = 0;
-    if (max_tokens == 0 && !sample) return KR_OK;
+    for (int i = 0; i < n; i++) { out.n[i] = 0; if (out.n_accepted) out.n_accepted[i] = 0; }
+    if (out.n_passes) *out.n_passes = 0;
+    if (max_tokens == 0 && !smp) return KR_OK;
     KR_HIP(hipSetDevice(s->eng->device));
     hipStream_t st = kr_pick_stream(s->eng, stream);
     if (int rc = order_after_store(s, st)) return rc;
     std::vector<char> drafts((size_t)n, 1);
-    if (sample)
+    if (smp)
         for (int i = 0; i < n; i++) {
-            if (int rc = set_sampler(s, slots[i], first_tokens[i], temperature[i], top_k[i], top_p[i], presence_penalty[i], rng_seeds[i], st)) return rc;
-            drafts[(size_t)i] = sample_row(s, slots[i]).mode != KR_MS_LOOP;
+            if (int rc = set_sampler(s, first.slots[i], first.tokens[i], smp->temperature[i], smp->top_k[i], smp->top_p[i], smp->presence_penalty[i], smp->rng_seeds[i], st)) return rc;
+            drafts[(size_t)i] = sample_row(s, first.slots[i]).mode != KR_MS_LOOP;
         }
     if (max_tokens == 0) return KR_OK;
     // a run over positions [pos, pos + k] must stay inside the slot and the rope tables (check_args' limits)
     int limit = s->multi->max_seq;
     if (s->max_rope_seq > 0) limit = std::min(limit, s->max_rope_seq);
     for (const DLayer& L : s->layers) if (L.attn == ATTN_MLA) limit = std::min(limit, L.mla_rope_seq);
-    std::vector<LookupIndex> ix;
-    ix.reserve((size_t)n);
-    for (int i = 0; i < n; i++) {
-        ix.emplace_back(ngram_max);
-        for (size_t j = c0[(size_t)i]; j < c0[(size_t)i + 1]; j++) ix.back().push(contexts[j]);
-        ix.back().push(first_tokens[i]);
+    std::vector<LookupIndex> ix;      // one per row; none without drafting
+    if (max_draft > 0) ix.reserve((size_t)n);
+    for (int i = 0; max_draft > 0 && i < n; i++) {
+        ix.emplace_back(dr.ngram_max);
+        for (size_t j = c0[(size_t)i]; j < c0[(size_t)i + 1]; j++) ix.back().push(dr.contexts[j]);
+        ix.back().push(first.tokens[i]);
     }
     auto is_stop = [&](int t) { for (int j = 0; j < n_stop; j++) if (stop_ids[j] == t) return true; return false; };
     std::vector<int> act((size_t)n);                           // rows still generating, in caller order
-    std::vector<int32_t> tk((size_t)n), ps((size_t)n);
-    for (int i = 0; i < n; i++) { act[(size_t)i] = i; tk[(size_t)i] = first_tokens[i]; ps[(size_t)i] = start_positions[i]; }
+    std::vector<int32_t> tk(first.tokens, first.tokens + n), ps(first.positions, first.positions + n);
+    for (int i = 0; i < n; i++) act[(size_t)i] = i;
     int passes = 0;
     while (!act.empty()) {
         const int m = (int)act.size(), fit = KR_EXTEND_MAX_TOKENS / m - 1;      // m rows of 1 + fit tokens always fit a pass
-        std::vector<int32_t> sl((size_t)m), rp((size_t)m), cn((size_t)m), run, greedy, nm((size_t)m), keep((size_t)m);
-        bool any = false;
+        std::vector<int32_t> sl((size_t)m), rp((size_t)m), cn((size_t)m), run, ids, nm((size_t)m, 0), keep((size_t)m);
         for (int k = 0; k < m; k++) {
             const int i = act[(size_t)k];
             int32_t draft[KR_VERIFY_MAX];
-            int d = max_draft > 0 && drafts[(size_t)i] ? ix[(size_t)i].draft(max_draft, draft) : 0;
-            d = std::min(d, max_tokens - n_out[i] - 1);                   // the pass yields at most d + 1 tokens
-            d = std::min(d, limit - ps[(size_t)i] - 1);
-            d = std::max(std::min(d, fit), 0);
-            for (int j = 0; j < d; j++) if (is_stop(draft[j])) { d = j + 1; break; }      // nothing after a stop id can be kept
-            sl[(size_t)k] = slots[i]; rp[(size_t)k] = ps[(size_t)i]; cn[(size_t)k] = 1 + d;
+            const int d = lookup_clamp(max_draft > 0 && drafts[(size_t)i] ? ix[(size_t)i].draft(max_draft, draft) : 0, draft, max_tokens - out.n[i], limit - ps[(size_t)i], fit, is_stop);
+            sl[(size_t)k] = first.slots[i]; rp[(size_t)k] = ps[(size_t)i]; cn[(size_t)k] = 1 + d;
             run.push_back(tk[(size_t)i]);
             run.insert(run.end(), draft, draft + d);
-            any |= d > 0;
         }
+        const bool any = run.size() > (size_t)m;      // a row drafts
         passes++;
-        greedy.resize(run.size());
-        if (!any) {      // the plain loop's step
-            if (int rc = step_impl(s, m, sl.data(), run.data(), rp.data(), greedy.data(), nullptr, st, sample)) return rc;
-            std::fill(nm.begin(), nm.end(), 0);
-        } else if (int rc = verify_impl(s, m, sl.data(), cn.data(), run.data(), rp.data(), greedy.data(), nm.data(), st, sample)) return rc;
-        // greedy[0 .. n_match] of a row (sample: its sampler's draws) is what the plain loop generates next; a stop id among them ends the row there.  After emitting greedy[j] the plain
-        // loop has consumed tokens 0 .. j of the run: that many are kept
+        ids.resize(run.size());
+        const Rows rows{m, sl.data(), any ? cn.data() : nullptr, run.data(), rp.data()};
+        if (any) { if (int rc = verify_impl(s, rows, ids.data(), nm.data(), st, smp != nullptr)) return rc; }
+        else if (int rc = step_impl(s, rows, ids.data(), nullptr, st, smp != nullptr)) return rc;      // the plain loop's step
         std::vector<int> next;
         size_t g0 = 0;
         for (int k = 0; k < m; k++) {
             const int i = act[(size_t)k], mt = nm[(size_t)k];
-            int kp = mt + 1;
-            bool stop = false;
-            for (int j = 0; j <= mt; j++) {
-                const int t = greedy[g0 + (size_t)j];
-                tokens_out[(size_t)i * max_tokens + n_out[i]++] = t; ix[(size_t)i].push(t);
-                if (is_stop(t)) { kp = j + 1; stop = true; break; }
-            }
-            if (n_accepted_out) n_accepted_out[i] += std::min(mt, kp);
-            keep[(size_t)k] = kp;
-            tk[(size_t)i] = greedy[g0 + (size_t)kp - 1]; ps[(size_t)i] += kp;
+            const LookupKept kept = lookup_emit(&ids[g0], mt, out.tokens + (size_t)i * max_tokens, out.n[i], ix.empty() ? nullptr : &ix[(size_t)i], is_stop);
+            if (out.n_accepted) out.n_accepted[i] += std::min(mt, kept.keep);
+            keep[(size_t)k] = kept.keep;
+            tk[(size_t)i] = ids[g0 + (size_t)kept.keep - 1]; ps[(size_t)i] += kept.keep;
             g0 += (size_t)cn[(size_t)k];
-            if (!stop && n_out[i] < max_tokens) next.push_back(i);      // a finished row leaves the batch: its slot is not touched again
+            if (!kept.stop && out.n[i] < max_tokens) next.push_back(i);
         }
         if (any) if (int rc = commit_impl(s, keep.data())) return rc;
         act.swap(next);
     }
-    if (n_passes_out) *n_passes_out = passes;
+    if (out.n_passes) *out.n_passes = passes;
     return KR_OK;
 }
 }  // namespace
@@ -587,19 +521,20 @@ extern "C" int kr_decode_slot_load(kr_decode_store* s, int slot, int seq_len) { 
 
 extern "C" int kr_decode_step_multi(kr_decode_store* s, int n, const int32_t* slots, const int32_t* tokens, const int32_t* positions,
                                     int32_t* next_out, float* logits_out, void* stream) {
-    return step_entry(s, n, slots, nullptr, tokens, positions, next_out, logits_out, false, stream);
+    return step_entry(s, Rows{n, slots, nullptr, tokens, positions}, next_out, logits_out, false, stream);
 }
 
 extern "C" int kr_decode_generate_multi(kr_decode_store* s, int n, const int32_t* slots, const int32_t* first_tokens, const int32_t* start_positions,
                                         int max_tokens, const int* stop_ids, int n_stop, int32_t* tokens_out, int32_t* n_out, void* stream) {
-    return generate_impl(s, n, slots, first_tokens, start_positions, max_tokens, nullptr, nullptr, nullptr, nullptr, nullptr, stop_ids, n_stop, tokens_out, n_out, stream);
+    return generate_slots(s, Rows{n, slots, nullptr, first_tokens, start_positions}, max_tokens, Drafting{nullptr, nullptr, 0, 1}, nullptr, stop_ids, n_stop,
+                          GenOut{tokens_out, n_out, nullptr, nullptr}, stream);
 }
 
 // ---- per-row sampling (docs/design/14-multi-sampling.md)
 extern "C" int kr_decode_slot_sampler(kr_decode_store* s, int slot, int first_token, float temperature, int top_k, float top_p, float presence_penalty,
                                       uint64_t rng_seed) {
     if (int rc = multi_begin(s)) return rc;
-    if (slot < 0 || slot >= s->multi->n_slots) return kr_fail(KR_ERR_VALUE, "slot %d out of range [0, %d)", slot, s->multi->n_slots);
+    if (int rc = slot_in_range(s, slot)) return rc;
     if (!(temperature >= 0.0f)) return kr_fail(KR_ERR_VALUE, "temperature must be >= 0");
     KR_HIP(hipSetDevice(s->eng->device));
     return set_sampler(s, slot, first_token, temperature, top_k, top_p, presence_penalty, rng_seed, s->eng->stream);
@@ -607,22 +542,22 @@ extern "C" int kr_decode_slot_sampler(kr_decode_store* s, int slot, int first_to
 
 extern "C" int kr_decode_step_multi_sample(kr_decode_store* s, int n, const int32_t* slots, const int32_t* tokens, const int32_t* positions,
                                            int32_t* next_out, float* logits_out, void* stream) {
-    return step_entry(s, n, slots, nullptr, tokens, positions, next_out, logits_out, true, stream);
+    return step_entry(s, Rows{n, slots, nullptr, tokens, positions}, next_out, logits_out, true, stream);
 }
 
 // ---- multi-token extend of slots (docs/design/17-multi-extend.md)
 extern "C" int kr_decode_extend_multi(kr_decode_store* s, int n, const int32_t* slots, const int32_t* counts, const int32_t* tokens, const int32_t* positions,
                                       int32_t* next_out, float* logits_out, int sample, void* stream) {
     // null counts are refused with the other null arguments (to the pass they would mean one token per row)
-    return step_entry(s, n, counts ? slots : nullptr, counts, tokens, positions, next_out, logits_out, sample != 0, stream);
+    return step_entry(s, Rows{n, counts ? slots : nullptr, counts, tokens, positions}, next_out, logits_out, sample != 0, stream);
 }
 
 extern "C" int kr_decode_generate_multi_sample(kr_decode_store* s, int n, const int32_t* slots, const int32_t* first_tokens, const int32_t* start_positions,
                                                int max_tokens, const float* temperature, const int* top_k, const float* top_p, const float* presence_penalty,
                                                const uint64_t* rng_seeds, const int* stop_ids, int n_stop, int32_t* tokens_out, int32_t* n_out, void* stream) {
-    if (!temperature) return kr_fail(KR_ERR_VALUE, "null sampler parameter array");
-    return generate_impl(s, n, slots, first_tokens, start_positions, max_tokens, temperature, top_k, top_p, presence_penalty, rng_seeds, stop_ids, n_stop,
-                         tokens_out, n_out, stream);
+    const SamplerCols smp{temperature, top_k, top_p, presence_penalty, rng_seeds};
+    return generate_slots(s, Rows{n, slots, nullptr, first_tokens, start_positions}, max_tokens, Drafting{nullptr, nullptr, 0, 1}, &smp, stop_ids, n_stop,
+                          GenOut{tokens_out, n_out, nullptr, nullptr}, stream);
 }
 
 // test aid: the batched sampler on host rows, row b = "slot" b (its own seen bitmap and xorshift64 state)
@@ -656,25 +591,25 @@ extern "C" int kr_sample_rows(const float* logits, int n, int vocab, const float
 }
 
 // ---- verify and commit over slots (docs/design/18-multi-verify.md, 19-multi-verify-sample.md)
-static int verify_entry(kr_decode_store* s, int n, const int32_t* slots, const int32_t* counts, const int32_t* tokens, const int32_t* positions, int32_t* ids_out,
-                        int32_t* n_match_out, bool sample, void* stream) {
+static int verify_entry(kr_decode_store* s, Rows r, int32_t* ids_out, int32_t* n_match_out, bool sample, void* stream) {
+    if (!r.counts) r.slots = nullptr;      // null counts are refused with the other null arguments
     if (int rc = multi_begin(s)) return rc;
-    if (int rc = check_args(s, n, counts ? slots : nullptr, counts, tokens, positions, 0)) return rc;
+    if (int rc = check_args(s, r, 0)) return rc;
     if (!ids_out || !n_match_out) return kr_fail(KR_ERR_VALUE, "null %s / n_match_out", sample ? "sampled_out" : "greedy_out");
-    for (int i = 0; i < n; i++)
-        if (counts[i] > KR_VERIFY_MAX) return kr_fail(KR_ERR_VALUE, "row %d: a run of %d tokens, at most %d (KR_VERIFY_MAX) in a verify", i, counts[i], KR_VERIFY_MAX);
+    for (int i = 0; i < r.n; i++)
+        if (r.counts[i] > KR_VERIFY_MAX) return kr_fail(KR_ERR_VALUE, "row %d: a run of %d tokens, at most %d (KR_VERIFY_MAX) in a verify", i, r.counts[i], KR_VERIFY_MAX);
     KR_HIP(hipSetDevice(s->eng->device));
     hipStream_t st = kr_pick_stream(s->eng, stream);
     if (int rc = order_after_store(s, st)) return rc;
-    return verify_impl(s, n, slots, counts, tokens, positions, ids_out, n_match_out, st, sample);
+    return verify_impl(s, r, ids_out, n_match_out, st, sample);
 }
 extern "C" int kr_decode_verify_multi(kr_decode_store* s, int n, const int32_t* slots, const int32_t* counts, const int32_t* tokens, const int32_t* positions,
                                       int32_t* greedy_out, int32_t* n_match_out, void* stream) {
-    return verify_entry(s, n, slots, counts, tokens, positions, greedy_out, n_match_out, false, stream);
+    return verify_entry(s, Rows{n, slots, counts, tokens, positions}, greedy_out, n_match_out, false, stream);
 }
 extern "C" int kr_decode_verify_multi_sample(kr_decode_store* s, int n, const int32_t* slots, const int32_t* counts, const int32_t* tokens, const int32_t* positions,
                                              int32_t* sampled_out, int32_t* n_match_out, void* stream) {
-    return verify_entry(s, n, slots, counts, tokens, positions, sampled_out, n_match_out, true, stream);
+    return verify_entry(s, Rows{n, slots, counts, tokens, positions}, sampled_out, n_match_out, true, stream);
 }
 
 extern "C" int kr_decode_commit_multi(kr_decode_store* s, const int32_t* n_keep) {
@@ -687,23 +622,23 @@ extern "C" int kr_decode_generate_multi_lookup(kr_decode_store* s, int n, const 
                                                const int32_t* first_tokens, const int32_t* start_positions, int max_tokens, int max_draft, int ngram_max,
                                                const int* stop_ids, int n_stop, int32_t* tokens_out, int32_t* n_out, int* n_passes_out,
                                                int32_t* n_accepted_out, void* stream) {
-    return lookup_impl(s, n, slots, contexts, n_context, first_tokens, start_positions, max_tokens, max_draft, ngram_max, nullptr, nullptr, nullptr, nullptr, nullptr,
-                       stop_ids, n_stop, tokens_out, n_out, n_passes_out, n_accepted_out, stream);
+    return generate_slots(s, Rows{n, slots, nullptr, first_tokens, start_positions}, max_tokens, Drafting{contexts, n_context, max_draft, ngram_max}, nullptr, stop_ids,
+                          n_stop, GenOut{tokens_out, n_out, n_passes_out, n_accepted_out}, stream);
 }
 extern "C" int kr_decode_generate_multi_lookup_sample(kr_decode_store* s, int n, const int32_t* slots, const int32_t* contexts, const int32_t* n_context,
                                                       const int32_t* first_tokens, const int32_t* start_positions, int max_tokens, int max_draft, int ngram_max,
                                                       const float* temperature, const int* top_k, const float* top_p, const float* presence_penalty,
                                                       const uint64_t* rng_seeds, const int* stop_ids, int n_stop, int32_t* tokens_out, int32_t* n_out,
                                                       int* n_passes_out, int32_t* n_accepted_out, void* stream) {
-    if (!temperature) return kr_fail(KR_ERR_VALUE, "null sampler parameter array");
-    return lookup_impl(s, n, slots, contexts, n_context, first_tokens, start_positions, max_tokens, max_draft, ngram_max, temperature, top_k, top_p, presence_penalty,
-                       rng_seeds, stop_ids, n_stop, tokens_out, n_out, n_passes_out, n_accepted_out, stream);
+    const SamplerCols smp{temperature, top_k, top_p, presence_penalty, rng_seeds};
+    return generate_slots(s, Rows{n, slots, nullptr, first_tokens, start_positions}, max_tokens, Drafting{contexts, n_context, max_draft, ngram_max}, &smp, stop_ids,
+                          n_stop, GenOut{tokens_out, n_out, n_passes_out, n_accepted_out}, stream);
 }
 
 extern "C" int kr_decode_slot_sampler_get(kr_decode_store* s, int slot, uint32_t* seen_out, uint64_t* rng_out) {
     if (int rc = multi_begin(s)) return rc;
+    if (int rc = slot_in_range(s, slot)) return rc;
     kr_multi_state& M = *s->multi;
-    if (slot < 0 || slot >= M.n_slots) return kr_fail(KR_ERR_VALUE, "slot %d out of range [0, %d)", slot, M.n_slots);
     if (!seen_out || !rng_out) return kr_fail(KR_ERR_VALUE, "null seen_out / rng_out");
     const size_t words = ((size_t)s->vocab + 31) / 32;
     if (M.smp.empty()) { std::fill(seen_out, seen_out + words, 0u); *rng_out = 0; return KR_OK; }      // no sampler was ever set
@@ -736,7 +671,7 @@ extern "C" int kr_sample_runs(const float* logits, int n, const int32_t* counts,
     for (int i = 0; i < n; i++) { slots[(size_t)i] = i; per_run.push_back(mode_row(i, temperature[i], top_k[i], top_p[i], presence_penalty[i], vocab, force_loop != 0)); }
     size_t T = 0; int max_pos = 0;
     std::vector<int> row_of;
-    const std::vector<int32_t> h = lay_rows(n, slots.data(), counts, tokens, zeros.data(), T, max_pos, &row_of);
+    const std::vector<int32_t> h = lay_rows(Rows{n, slots.data(), counts, tokens, zeros.data()}, T, max_pos, &row_of);
     run_rows(n, counts, row_of, per_run, rows, at);
     const size_t V = (size_t)vocab, words = (V + 31) / 32;
     kr_multi_state M;

@@ -576,22 +576,36 @@ int kr_spec_pending_fail(kr_decode_store* s) {
     return s && s->spec_pending ? kr_fail(KR_ERR_STATE, "a kr_decode_verify is pending: kr_decode_commit must come first") : KR_OK;
 }
 
-int kr_spec_refuse(kr_decode_store* s) {
+// what no exact pass over this store runs: tolerance modes, expert parallelism, MoE layers without an engine or with native-GGUF experts, geometries the
+// verify-form kernels do not cover.  slots: the pass over device slots (multi_refuse, kr_decode_multi.cpp), whose messages start with another noun and whose
+// per-slot kernels refuse more; its clauses sit here, each in its place, because the order of the refusals is part of both contracts
+int kr_exact_refuse(kr_decode_store* s, bool slots) {
+    const char *the = slots ? "the " : "", *what = slots ? "multi-sequence step" : "speculative decoding";
     if (s->attn_fast || s->gemm_fast || s->decode_fast)
-        return kr_fail(KR_ERR_STATE, "speculative decoding is exact-mode only: the attention mode has tolerance bits set (%d)", s->attn_fast | s->gemm_fast << 1 | s->decode_fast << 2);
+        return kr_fail(KR_ERR_STATE, "%s%s is exact-mode only: the attention mode has tolerance bits set (%d)", the, what, s->attn_fast | s->gemm_fast << 1 | s->decode_fast << 2);
+    if (slots && s->opt_multi_attn_fast)
+        for (size_t i = 0; i < s->layers.size(); i++)
+            if (s->layers[i].attn == ATTN_MLA)
+                return kr_fail(KR_ERR_STATE, "the \"multi_attn_fast\" option covers GQA layers only: layer %zu is MLA (set the option to 0 for the exact step)", i);
     kr_engine* e = s->eng;
-    if (e->ep) return kr_fail(KR_ERR_STATE, "speculative decoding does not run under expert parallelism");
+    if (e->ep) return kr_fail(KR_ERR_STATE, "%s%s does not run under expert parallelism", the, what);
     for (const DLayer& L : s->layers) {
+        if (slots && L.attn == ATTN_MLA && !kr_multi_mla_ok(L.klr, L.nd, L.rd))
+            return kr_fail(KR_ERR_VALUE, "%s: MLA geometry kv_lora_rank %d nope %d rope %d not covered (kv_lora_rank 512 / 256, rope 64)", what, L.klr, L.nd, L.rd);
         if (L.mlp == MLP_MOE) {
             if (s->own_eng || L.moe_layer >= (int)e->layers.size()) return kr_fail(KR_ERR_STATE, "set_moe_store was not called (MoE layer %d has no engine)", L.moe_layer);
             if (e->layers[L.moe_layer].gguf)
-                return kr_fail(KR_ERR_STATE, "speculative decoding is exact-mode only: MoE layer %d holds native GGUF experts (their prompt pass is tolerance-only)", L.moe_layer);
+                return kr_fail(KR_ERR_STATE, "%s%s is exact-mode only: MoE layer %d holds native GGUF experts (their prompt pass is tolerance-only)", the, what, L.moe_layer);
         }
-        if (L.attn == ATTN_LA && (L.kd != 4 || (L.dk != 64 && L.dk != 128) || L.dv > 256 || L.dv % 8))
-            return kr_fail(KR_ERR_VALUE, "speculative decoding: linear-attention geometry kd %d dk %d dv %d not covered (kd 4, dk 64 / 128, dv <= 256)", L.kd, L.dk, L.dv);
+        // the slots' kernels also need whole value-head groups per key head
+        if (L.attn == ATTN_LA && (L.kd != 4 || (L.dk != 64 && L.dk != 128) || L.dv > 256 || L.dv % 8 || (slots && L.nv != L.nk * (L.nv / L.nk))))
+            return kr_fail(KR_ERR_VALUE, "%s: linear-attention geometry kd %d dk %d dv %d not covered (kd 4, dk 64 / 128, dv <= 256)", what, L.kd, L.dk, L.dv);
+        if (slots && L.attn == ATTN_GQA && ((L.hd != 64 && L.hd != 128 && L.hd != 256) || L.nkv < 1 || L.nh % L.nkv || (L.nh / L.nkv) * (L.hd + 64) > 12288))
+            return kr_fail(KR_ERR_VALUE, "%s: GQA geometry nh %d nkv %d head_dim %d not covered (head_dim 64 / 128 / 256)", what, L.nh, L.nkv, L.hd);
     }
     return KR_OK;
 }
+int kr_spec_refuse(kr_decode_store* s) { return kr_exact_refuse(s, false); }
 
 // verify buffers of every linear-attention layer (KR_VERIFY_MAX rows) + the device table the snapshot / rollback kernels walk
 static int spec_prepare(kr_decode_store* s, hipStream_t st) {

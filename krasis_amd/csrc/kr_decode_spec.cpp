@@ -58,36 +58,26 @@ extern "C" int kr_decode_generate_lookup(kr_decode_store* s, const int32_t* cont
     int tok = first_token, pos = start_pos, n = 0, passes = 0, accepted = 0;
     int32_t draft[KR_VERIFY_MAX], pass[KR_VERIFY_MAX], greedy[KR_VERIFY_MAX];
     while (n < max_tokens) {
-        int k = max_draft > 0 ? ix.draft(max_draft, draft) : 0;
-        k = std::min(k, max_tokens - n - 1);                       // the pass yields at most k + 1 tokens
-        k = pos < 0 ? 0 : std::min(k, limit - pos - 1);
-        for (int i = 0; i < k; i++) if (is_stop(draft[i])) { k = i + 1; break; }      // nothing after a stop id can be kept
+        // a negative position drafts nothing: the plain step refuses it as the plain loop does
+        const int k = pos < 0 ? 0 : lookup_clamp(max_draft > 0 ? ix.draft(max_draft, draft) : 0, draft, max_tokens - n, limit - pos, INT_MAX, is_stop);
         passes++;
-        if (k <= 0) {      // the plain loop's step (graph replay)
-            if (int rc = kr_decode_step(s, tok, pos, nullptr, stream)) { stamp(); return rc; }
-            int next = 0;
-            KR_HIP(hipMemcpyAsync(&next, s->tok.p, 4, hipMemcpyDeviceToHost, st));
-            KR_HIP(hipStreamSynchronize(st));
-            tokens_out[n++] = next; ix.push(next); tok = next; pos++;
-            if (is_stop(next)) break;
-            continue;
-        }
-        pass[0] = tok;
-        for (int i = 0; i < k; i++) pass[i + 1] = draft[i];
         int m = 0;
-        if (int rc = kr_decode_verify(s, pass, k + 1, pos, greedy, &m, stream)) { stamp(); return rc; }
-        // greedy[0..m] is what the plain loop generates next; a stop id among them ends the run there.  After emitting greedy[i] the plain loop has
-        // consumed pass[0..i] (= tok, greedy[0..i-1]): that many tokens are kept.
-        int keep = m + 1;
-        bool stop = false;
-        for (int i = 0; i <= m; i++) {
-            tokens_out[n++] = greedy[i]; ix.push(greedy[i]);
-            if (is_stop(greedy[i])) { keep = i + 1; stop = true; break; }
+        if (k == 0) {      // the plain loop's step (graph replay)
+            if (int rc = kr_decode_step(s, tok, pos, nullptr, stream)) { stamp(); return rc; }
+            KR_HIP(hipMemcpyAsync(greedy, s->tok.p, 4, hipMemcpyDeviceToHost, st));
+            KR_HIP(hipStreamSynchronize(st));
+        } else {
+            pass[0] = tok;
+            for (int i = 0; i < k; i++) pass[i + 1] = draft[i];
+            if (int rc = kr_decode_verify(s, pass, k + 1, pos, greedy, &m, stream)) { stamp(); return rc; }
         }
-        accepted += std::min(m, keep);
-        if (int rc = kr_decode_commit(s, keep)) { stamp(); return rc; }
-        tok = greedy[keep - 1]; pos += keep;
-        if (stop) break;
+        const LookupKept kept = lookup_emit(greedy, m, tokens_out, n, &ix, is_stop);
+        if (k > 0) {
+            accepted += std::min(m, kept.keep);
+            if (int rc = kr_decode_commit(s, kept.keep)) { stamp(); return rc; }
+        }
+        tok = greedy[kept.keep - 1]; pos += kept.keep;
+        if (kept.stop) break;
     }
     KR_HIP(hipStreamSynchronize(st));
     stamp();

@@ -1,5 +1,6 @@
-// kr_lookup_index.h -- the prompt-lookup drafting rule, indexed incrementally (docs/design/12-speculative.md): the one copy behind
-// kr_decode_generate_lookup (kr_decode_spec.cpp) and kr_decode_generate_multi_lookup (kr_decode_multi.cpp, one index per row)
+// kr_lookup_index.h -- the prompt-lookup drafting rule, indexed incrementally, and the rule that decides what a pass runs and keeps
+// (docs/design/12-speculative.md): the one copy behind kr_decode_generate_lookup (kr_decode_spec.cpp) and the slot generation loop
+// (generate_slots in kr_decode_multi.cpp, one index per row)
 #pragma once
 #include <stdint.h>
 
@@ -34,3 +35,26 @@ struct LookupIndex {
         return 0;
     }
 };
+
+// The two halves of the draft rule, which make speculation exact.  is_stop(id): whether the id ends a sequence.
+// lookup_clamp: how many of the d proposed draft tokens a pass runs.  want = tokens the row still wants (the pass yields at most d + 1), room = positions
+// from the pass's first one to the end of the cache and rope tables (it occupies d + 1), cap = the most one row may draft in this pass; never below 0, and
+// nothing after a stop id, which cannot be kept
+template <class Stop>
+inline int lookup_clamp(int d, const int32_t* draft, int want, int room, int cap, Stop is_stop) {
+    d = std::max(std::min(std::min(d, cap), std::min(want, room) - 1), 0);
+    for (int j = 0; j < d; j++) if (is_stop(draft[j])) return j + 1;
+    return d;
+}
+// lookup_emit: ids[0 .. n_match] of a pass are what the plain loop generates next: appended to out (n_out counts them) and to the index (ix null: no index
+// is kept), up to and with the first stop id.  After emitting ids[j] the plain loop has consumed tokens 0 .. j of the run: that many are kept
+struct LookupKept { int keep; bool stop; };
+template <class Stop>
+inline LookupKept lookup_emit(const int32_t* ids, int n_match, int32_t* out, int32_t& n_out, LookupIndex* ix, Stop is_stop) {
+    for (int j = 0; j <= n_match; j++) {
+        out[n_out++] = ids[j];
+        if (ix) ix->push(ids[j]);
+        if (is_stop(ids[j])) return {j + 1, true};
+    }
+    return {n_match + 1, false};
+}

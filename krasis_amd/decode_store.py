@@ -430,12 +430,18 @@ class CpuDecodeStore:
         (logits, id, the KV row -- or MLA latent and rope-key rows -- it appends to the slot).  Returns the greedy ids, or (ids, logits f32 [n, vocab]) with logits=True.
         After set_option("multi_attn_fast", 1), over slots of max_seq > 1024: row i is bit-identical to decode_step under set_attention_mode(True) on that
         sequence alone instead (GQA attention as split-KV flash-decode; logits within 1e-3 of the exact step relative to their largest magnitude)."""
+        return self._step_multi(self._lib.kr_decode_step_multi, slots, None, tokens, positions, logits)
+
+    def _step_multi(self, entry, slots, counts, tokens, positions, logits, *flags):
+        """step_multi / step_multi_sample / extend_multi: the rows in (counts None: the entry point takes none, one token per row), one id per row out,
+        optionally with the logits"""
         self._need()
         n = len(slots)
-        arr = lambda xs: (C.c_int32 * max(n, 1))(*xs)
+        arr = lambda xs, k=n: (C.c_int32 * max(k, 1))(*xs)      # one value per row unless told otherwise
         ids = (C.c_int32 * max(n, 1))()
         out = np.empty((n, self._vocab), np.float32) if logits else None
-        check(self._lib.kr_decode_step_multi(self._h, n, arr(slots), arr(tokens), arr(positions), ids, out.ctypes.data if logits else None, None))
+        runs = (arr(tokens),) if counts is None else (arr(counts), arr(tokens, len(tokens)))
+        check(entry(self._h, n, arr(slots), *runs, arr(positions), ids, out.ctypes.data if logits else None, *flags, None))
         return (list(ids[:n]), out) if logits else list(ids[:n])
 
     def generate_multi(self, slots: Sequence[int], first_tokens: Sequence[int], start_positions: Sequence[int], max_tokens: int,
@@ -445,21 +451,33 @@ class CpuDecodeStore:
         Any of temperature / top_k / top_p / presence_penalty / rng_seeds given (a scalar or one value per row; the others default to 0, 0, 1.0,
         0, 0): kr_decode_generate_multi_sample, row i = generate_batch(..., temperature[i], top_k[i], top_p[i], stop_ids, presence_penalty[i],
         rng_seeds[i]) on that sequence alone."""
+        sampler = (temperature, top_k, top_p, presence_penalty, rng_seeds)
+        if all(p is None for p in sampler):
+            return self._generate_multi(self._lib.kr_decode_generate_multi, slots, first_tokens, start_positions, max_tokens, stop_ids)
+        return self._generate_multi(self._lib.kr_decode_generate_multi_sample, slots, first_tokens, start_positions, max_tokens, stop_ids, sampler=sampler)
+
+    def _generate_multi(self, entry, slots, first_tokens, start_positions, max_tokens, stop_ids, lookup=None, sampler=None):
+        """the four generation entry points over slots: lookup = (contexts, max_draft, ngram_max) for the lookup forms, which also leave
+        last_multi_lookup_stats; sampler = (temperature, top_k, top_p, presence_penalty, rng_seeds) for the sampled forms, each a scalar, one value per row
+        or None for its default.  Returns the tokens of every row."""
         self._need()
         n = len(slots)
-        arr = lambda xs: (C.c_int32 * max(n, 1))(*xs)
-        out = (C.c_int32 * max(n * max_tokens, 1))(); cnt = (C.c_int32 * max(n, 1))()
-        stops = (C.c_int * max(len(stop_ids), 1))(*stop_ids)
-        params = (temperature, top_k, top_p, presence_penalty, rng_seeds)
-        if all(p is None for p in params):
-            check(self._lib.kr_decode_generate_multi(self._h, n, arr(slots), arr(first_tokens), arr(start_positions), max_tokens, stops, len(stop_ids),
-                                                     out, cnt, None))
-        else:
-            rows = lambda v, default, ctype: _per_row(v, default, ctype, n)
-            check(self._lib.kr_decode_generate_multi_sample(self._h, n, arr(slots), arr(first_tokens), arr(start_positions), max_tokens,
-                                                            rows(temperature, 0.0, C.c_float), rows(top_k, 0, C.c_int), rows(top_p, 1.0, C.c_float),
-                                                            rows(presence_penalty, 0.0, C.c_float), rows(rng_seeds, 0, C.c_uint64), stops, len(stop_ids),
-                                                            out, cnt, None))
+        arr = lambda xs, k=n: (C.c_int32 * max(k, 1))(*xs)      # one value per row unless told otherwise
+        out = (C.c_int32 * max(n * max_tokens, 1))(); cnt = (C.c_int32 * max(n, 1))(); acc = (C.c_int32 * max(n, 1))(); passes = C.c_int()
+        ctx, draft, stats = (), (), ()
+        if lookup is not None:
+            contexts, max_draft, ngram_max = lookup
+            contexts = [[] for _ in range(n)] if contexts is None else [list(c) for c in contexts]
+            if len(contexts) != n:
+                raise ValueError(f"{len(contexts)} contexts for {n} rows")
+            flat = [int(t) for c in contexts for t in c]
+            ctx, draft, stats = (arr(flat, len(flat)), arr([len(c) for c in contexts])), (max_draft, ngram_max), (C.byref(passes), acc)
+        cols = () if sampler is None else tuple(_per_row(v, default, ctype, n) for v, (default, ctype) in
+                                                zip(sampler, ((0.0, C.c_float), (0, C.c_int), (1.0, C.c_float), (0.0, C.c_float), (0, C.c_uint64))))
+        check(entry(self._h, n, arr(slots), *ctx, arr(first_tokens), arr(start_positions), max_tokens, *draft, *cols,
+                    (C.c_int * max(len(stop_ids), 1))(*stop_ids), len(stop_ids), out, cnt, *stats, None))
+        if lookup is not None:
+            self.last_multi_lookup_stats = {"passes": passes.value, "accepted": list(acc[:n])}
         return [list(out[i * max_tokens: i * max_tokens + cnt[i]]) for i in range(n)]
 
     def set_slot_sampler(self, slot: int, first_token: int, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0,
@@ -473,13 +491,7 @@ class CpuDecodeStore:
         """kr_decode_step_multi_sample: step_multi, but row i's id is drawn by slot slots[i]'s sampler (set_slot_sampler), exactly as
         generate_batch draws it for that sequence alone.  Returns the ids, or (ids, logits f32 [n, vocab]) with logits=True (the model's
         logits, before penalty and temperature)."""
-        self._need()
-        n = len(slots)
-        arr = lambda xs: (C.c_int32 * max(n, 1))(*xs)
-        ids = (C.c_int32 * max(n, 1))()
-        out = np.empty((n, self._vocab), np.float32) if logits else None
-        check(self._lib.kr_decode_step_multi_sample(self._h, n, arr(slots), arr(tokens), arr(positions), ids, out.ctypes.data if logits else None, None))
-        return (list(ids[:n]), out) if logits else list(ids[:n])
+        return self._step_multi(self._lib.kr_decode_step_multi_sample, slots, None, tokens, positions, logits)
 
     def extend_multi(self, slots: Sequence[int], token_lists: Sequence[Sequence[int]], positions: Sequence[int], logits: bool = False,
                      sample: bool = False):
@@ -488,17 +500,10 @@ class CpuDecodeStore:
         recurrent state, the last token's logits and id), however a token stream is cut into calls and whatever rows share the pass.  At most
         KR_EXTEND_MAX_TOKENS tokens per call, all rows together.  Returns one id per row -- the greedy id after its last token, or with sample=True the
         draw of the slot's sampler (set_slot_sampler) on those logits, as step_multi_sample draws it -- or (ids, logits f32 [n, vocab]) with logits=True."""
-        self._need()
-        n = len(slots)
-        if len(token_lists) != n or len(positions) != n:
-            raise ValueError(f"{n} slots, {len(token_lists)} token lists, {len(positions)} positions")
-        flat = [int(t) for run in token_lists for t in run]
-        arr = lambda xs: (C.c_int32 * max(len(xs), 1))(*xs)
-        ids = (C.c_int32 * max(n, 1))()
-        out = np.empty((n, self._vocab), np.float32) if logits else None
-        check(self._lib.kr_decode_extend_multi(self._h, n, arr(list(slots)), arr([len(run) for run in token_lists]), arr(flat), arr(list(positions)), ids,
-                                               out.ctypes.data if logits else None, 1 if sample else 0, None))
-        return (list(ids[:n]), out) if logits else list(ids[:n])
+        if len(token_lists) != len(slots) or len(positions) != len(slots):
+            raise ValueError(f"{len(slots)} slots, {len(token_lists)} token lists, {len(positions)} positions")
+        return self._step_multi(self._lib.kr_decode_extend_multi, slots, [len(run) for run in token_lists], [int(t) for run in token_lists for t in run],
+                                positions, logits, 1 if sample else 0)
 
     def verify_multi(self, slots: Sequence[int], token_lists: Sequence[Sequence[int]], positions: Sequence[int]):
         """kr_decode_verify_multi (docs/design/18-multi-verify.md): row i = slot slots[i] runs token_lists[i] = [its sampled, not yet consumed token, its
@@ -540,20 +545,8 @@ class CpuDecodeStore:
         """kr_decode_generate_multi_lookup: the tokens and slot states of generate_multi(slots, first_tokens, start_positions, max_tokens, stop_ids) in fewer
         passes where a row's text repeats its context (contexts[i], e.g. its prompt) or itself: prompt-lookup drafts per row, one verify_multi +
         commit_multi per pass.  last_multi_lookup_stats = {"passes": passes, "accepted": accepted draft tokens per row}."""
-        self._need()
-        n = len(slots)
-        contexts = [[] for _ in range(n)] if contexts is None else [list(c) for c in contexts]
-        if len(contexts) != n:
-            raise ValueError(f"{len(contexts)} contexts for {n} rows")
-        arr = lambda xs: (C.c_int32 * max(len(xs), 1))(*xs)
-        flat = [int(t) for c in contexts for t in c]
-        out = (C.c_int32 * max(n * max_tokens, 1))(); cnt = (C.c_int32 * max(n, 1))(); acc = (C.c_int32 * max(n, 1))(); passes = C.c_int()
-        stops = (C.c_int * max(len(stop_ids), 1))(*stop_ids)
-        check(self._lib.kr_decode_generate_multi_lookup(self._h, n, arr(list(slots)), arr(flat), arr([len(c) for c in contexts]), arr(list(first_tokens)),
-                                                        arr(list(start_positions)), max_tokens, max_draft, ngram_max, stops, len(stop_ids), out, cnt,
-                                                        C.byref(passes), acc, None))
-        self.last_multi_lookup_stats = {"passes": passes.value, "accepted": list(acc[:n])}
-        return [list(out[i * max_tokens: i * max_tokens + cnt[i]]) for i in range(n)]
+        return self._generate_multi(self._lib.kr_decode_generate_multi_lookup, slots, first_tokens, start_positions, max_tokens, stop_ids,
+                                    lookup=(contexts, max_draft, ngram_max))
 
     # ------------------------------------------------------------------ sampled speculation over slots (docs/design/19-multi-verify-sample.md)
     def verify_multi_sample(self, slots: Sequence[int], token_lists: Sequence[Sequence[int]], positions: Sequence[int]):
@@ -570,22 +563,8 @@ class CpuDecodeStore:
         """kr_decode_generate_multi_lookup_sample: the tokens, slot states and sampler states of generate_multi(..., temperature=, top_k=, top_p=,
         presence_penalty=, rng_seeds=) (a scalar or one value per row; defaults 0, 0, 1.0, 0, 0) in fewer passes: prompt-lookup drafts per row, one
         verify_multi_sample + commit_multi per pass.  last_multi_lookup_stats = {"passes": passes, "accepted": accepted draft tokens per row}."""
-        self._need()
-        n = len(slots)
-        contexts = [[] for _ in range(n)] if contexts is None else [list(c) for c in contexts]
-        if len(contexts) != n:
-            raise ValueError(f"{len(contexts)} contexts for {n} rows")
-        rows = lambda v, default, ctype: _per_row(v, default, ctype, n)
-        arr = lambda xs: (C.c_int32 * max(len(xs), 1))(*xs)
-        flat = [int(t) for c in contexts for t in c]
-        out = (C.c_int32 * max(n * max_tokens, 1))(); cnt = (C.c_int32 * max(n, 1))(); acc = (C.c_int32 * max(n, 1))(); passes = C.c_int()
-        stops = (C.c_int * max(len(stop_ids), 1))(*stop_ids)
-        check(self._lib.kr_decode_generate_multi_lookup_sample(
-            self._h, n, arr(list(slots)), arr(flat), arr([len(c) for c in contexts]), arr(list(first_tokens)), arr(list(start_positions)), max_tokens,
-            max_draft, ngram_max, rows(temperature, 0.0, C.c_float), rows(top_k, 0, C.c_int), rows(top_p, 1.0, C.c_float),
-            rows(presence_penalty, 0.0, C.c_float), rows(rng_seeds, 0, C.c_uint64), stops, len(stop_ids), out, cnt, C.byref(passes), acc, None))
-        self.last_multi_lookup_stats = {"passes": passes.value, "accepted": list(acc[:n])}
-        return [list(out[i * max_tokens: i * max_tokens + cnt[i]]) for i in range(n)]
+        return self._generate_multi(self._lib.kr_decode_generate_multi_lookup_sample, slots, first_tokens, start_positions, max_tokens, stop_ids,
+                                    lookup=(contexts, max_draft, ngram_max), sampler=(temperature, top_k, top_p, presence_penalty, rng_seeds))
 
     def slot_sampler_state(self, slot: int):
         """kr_decode_slot_sampler_get: (seen-token bitmap as uint32 [(vocab + 31) // 32], xorshift64 state) of the slot's sampler; zeros before any

@@ -62,7 +62,22 @@ def test_the_greedy_signatures_are_as_they_were():
 
 
 def test_the_generation_loop_has_one_copy():
-    """the greedy and the sampled lookup loop are one function: both entry points call lookup_impl, and the drafting call appears once"""
+    """the four generation entry points over slots are one function: the drafting call and the loop over the rows still generating each appear once in
+    the file, in the same internal function, and the body of every entry point returns through that function"""
     src = open(os.path.join(CSRC, "kr_decode_multi.cpp")).read()
     assert src.count(".draft(max_draft, draft)") == 1
-    assert len(re.findall(r"\breturn lookup_impl\(", src)) == 2
+    assert len(re.findall(r"\b(?:while|for)\s*\([^\n]*\bact\.(?:empty|size)\(\)", src)) == 1      # one loop walks the active rows
+    loop_at = src.index("while (!act.empty())")
+    starts = {m.start(): m.group(1) for m in re.finditer(r"^\w[\w:<>*& ]* [*&]*(\w+)\(", src, flags=re.M)}      # functions defined in column 0
+
+    def owner(at):
+        return starts[max(p for p in starts if p < at)]
+
+    loop = owner(loop_at)
+    assert owner(src.index(".draft(max_draft, draft)")) == loop
+    entries = ["kr_decode_generate_multi", "kr_decode_generate_multi_sample", "kr_decode_generate_multi_lookup", "kr_decode_generate_multi_lookup_sample"]
+    for name in entries:
+        body = re.search(r'extern "C" int %s\(.*?\)\s*\{(.*?)\n\}\n' % name, src, flags=re.S)
+        assert body, name
+        assert len(re.findall(r"\breturn %s\(" % loop, body.group(1))) == 1, name
+    assert len(re.findall(r"\b%s\(" % loop, src)) == len(entries) + 1      # its definition and those four calls
