@@ -80,6 +80,8 @@ struct kr_decode_store {
     DevBuf img_in, img_post, img_post_bf16, img_attn;   // pre-built INT16 activation images (input norm, post-attention norm f32 / bf16, attention output)
     int opt_gqa_stream = 0, opt_pfm_timing = 0, opt_norm_rows = 1, opt_la_conv_fused = 1, opt_gqa_fused = 1, opt_lm_fused = 1, opt_la_heads = 1, opt_w2_combine = 1, opt_dense_fast = 1;   // kr_decode_set_option: test / tuning hooks (no environment lookups on launch paths)
     int opt_multi_sample_loop = 0;               // kr_decode_set_option("multi_sample_loop"): every sampled row of a multi-sequence step takes the single-row sampler, one row after another (A/B and test hook; same tokens)
+    int opt_gguf_exact_pass = 0;                 // kr_decode_set_option("gguf_exact_pass"): every multi-row pass runs native-GGUF MoE layers through the exact forms (KR_PF_SET_GGUF_EXACT, docs/design/20-gguf-exact-pass.md): a row carries the bits of kr_decode_step, and the slot / speculation entry points accept such a store
+    int opt_gguf_exact_grouped = 1;              // ... 0 = through the streaming kernels for every block type (A/B and test hook; same bits)
     int opt_multi_attn_fast = 0;                 // kr_decode_set_option("multi_attn_fast"): the GQA layers of every batched multi-sequence step run split-KV flash-decode over slots longer than gqa_split_min (tolerance form, docs/design/16-multi-attn-fast.md); the mode bits stay refused
     int opt_gen_lookahead = 0;                    // kr_decode_set_option("generate_lookahead"): generate_batch feeds the sampled token back ON THE DEVICE and queues step i + 1 before the host has read token i
     int opt_ep_graph = 0;                         // kr_decode_set_option("ep_graph"): expert-parallel decode over RCCL replays a captured graph (the all-reduce is captured with the kernels)
@@ -115,7 +117,7 @@ enum { PK_EMBED = 0, PK_RMSNORM, PK_MATVEC, PK_LA_CONV, PK_LA_RECUR, PK_GATED_NO
 
 static inline KrMatDev mv(kr_decode_store* s, int wid) { return s->weights[wid]->ms.view(); }
 int kr_ensure_wsum(kr_engine* e, MatSet& ms, hipStream_t st);
-int kr_moe_prefill_prepare(kr_engine* e, int layer, int fast, int routed_only, hipStream_t st);   // kr_engine.cpp: the lazily derived data of a native-GGUF layer, built on `st` now
+int kr_moe_prefill_prepare(kr_engine* e, int layer, int fast, int routed_only, hipStream_t st, int gguf_exact = 0);   // kr_engine.cpp: the lazily derived data of a native-GGUF layer, built on `st` now
 void kr_standalone_release(kr_decode_store* s);
 int kr_exact_refuse(kr_decode_store* s, bool slots);   // kr_decode_prefill.cpp: KR_OK when an exact pass can run on this store -- speculative decoding on its own sequence, or (slots) the multi-sequence step
 int kr_spec_refuse(kr_decode_store* s);          // kr_exact_refuse(s, false)

@@ -83,6 +83,18 @@ static void pf_act(kr_decode_store* s, const float* gu, int C, int n, int gu_ld,
     else kr_launch_pf_act(gu, C, n, gu_ld, KR_ACT_SILU_MUL, 0.0f, 0.0f, B.yh, B.yl, B.ys, st);
 }
 
+// "gguf_exact_pass": native-GGUF MoE layers of every multi-row pass take the exact forms (B.xb holds bf16_rne(normed), kr_pfm_norm_kernel: the row
+// gg_prologue_f32_as_bf16 forms from the decode step's f32 hidden, so the activation images are the step's)
+static int gguf_exact_bits(const kr_decode_store* s) {
+    return s->opt_gguf_exact_pass ? KR_PF_SET_GGUF_EXACT | (s->opt_gguf_exact_grouped ? 0 : KR_PF_SET_GGUF_STREAM) : 0;
+}
+static bool has_gguf_moe(const kr_decode_store* s) {
+    const kr_engine* e = s->eng;
+    if (!e || s->own_eng) return false;
+    for (const DLayer& L : s->layers) if (L.mlp == MLP_MOE && L.moe_layer >= 0 && L.moe_layer < (int)e->layers.size() && e->layers[L.moe_layer].gguf) return true;
+    return false;
+}
+
 // everything a layer launches, for one chunk, on the chunk's stream
 static int run_layer(kr_decode_store* s, Chunk& cx, size_t li) {
     kr_engine* e = s->eng;
@@ -246,7 +258,7 @@ static int run_layer(kr_decode_store* s, Chunk& cx, size_t li) {
         // prefill_impl pads ranks that have fewer chunks with empty-shard calls.  Every chunk in flight has its own exchange-buffer set (cx.set) and stream; the
         // collectives of all chunks are ISSUED in one host order that is the same on every rank (the loop structure below depends only on the agreed chunk count).
         if (e->ep) { if (int rc = kr_moe_prefill_ep_set(e, L.moe_layer, B.xb, B.ids, B.w, B.moe, Cc, k, KR_OUT_F32, 1, cx.set, st ? (void*)st : (void*)1)) return rc; }
-        else if (int rc = kr_moe_prefill_set(e, L.moe_layer, B.xb, B.ids, B.w, B.moe, Cc, k, KR_OUT_F32, 1, cx.set | (s->gemm_fast ? KR_PF_SET_FAST : 0), st)) return rc;
+        else if (int rc = kr_moe_prefill_set(e, L.moe_layer, B.xb, B.ids, B.w, B.moe, Cc, k, KR_OUT_F32, 1, cx.set | (s->gemm_fast ? KR_PF_SET_FAST : 0) | gguf_exact_bits(s), st)) return rc;
         const bool has_shared = L.sgu_wid >= 0, has_gate = has_shared && L.sg_wid >= 0;
         if (has_shared) {   // decode-store numerics: f32 input digits, fast_silu_mul + f32::round digits (decode.rs:3356-3378)
             const int si2 = s->weights[L.sgu_wid]->rows, SI = si2 / 2;
@@ -369,7 +381,7 @@ static int pf_layout(kr_decode_store* s, size_t C, bool lm_rows, bool multi, hip
             if (int rc = kr_ensure_gate_row(e, Ly.moe_layer)) return rc;
             if (int rc = kr_ensure_wsum(e, EL.w13, st)) return rc;
             if (int rc = kr_ensure_wsum(e, EL.w2, st)) return rc;
-            if (int rc = kr_moe_prefill_prepare(e, Ly.moe_layer, s->gemm_fast ? 1 : 0, 1, st)) return rc;     // native-GGUF layers: block sums / tolerance copies, before any chunk stream runs
+            if (int rc = kr_moe_prefill_prepare(e, Ly.moe_layer, s->gemm_fast ? 1 : 0, 1, st, s->opt_gguf_exact_pass)) return rc;     // native-GGUF layers: block sums / tolerance copies, before any chunk stream runs
         } else if (Ly.mlp == MLP_DENSE) {
             sid = std::max(sid, 2 * (size_t)s->weights[Ly.down_wid]->cols); kmax = std::max(kmax, (size_t)s->weights[Ly.down_wid]->cols);
             for (int w : {Ly.gate_wid, Ly.up_wid, Ly.down_wid}) wids.push_back(w);
@@ -416,6 +428,8 @@ static int prefill_impl(kr_decode_store* s, const int32_t* tokens, int n_tokens,
     if (!verify) if (int rc = kr_spec_pending_fail(s)) return rc;
     if (!tokens || n_tokens <= 0) return kr_fail(KR_ERR_VALUE, "kr_decode_prefill: empty prompt");
     if ((int)s->layers.size() != s->n_layers) return kr_fail(KR_ERR_STATE, "finalize_decode was not called");
+    if (s->opt_gguf_exact_pass && s->gemm_fast && has_gguf_moe(s))
+        return kr_fail(KR_ERR_STATE, "the \"gguf_exact_pass\" option and KR_GEMM_FAST exclude each other on a store with native GGUF experts: the exact pass has no tolerance GEMM (clear one of them)");
     if (start_pos < 0 || (s->kv_max_seq > 0 && start_pos + n_tokens > s->kv_max_seq))
         return kr_fail(KR_ERR_VALUE, "prompt [%d, %d) does not fit kv_max_seq %d", start_pos, start_pos + n_tokens, s->kv_max_seq);
     for (int i = 0; i < n_tokens; i++) if (tokens[i] < 0 || tokens[i] >= s->vocab) return kr_fail(KR_ERR_VALUE, "token id %d out of range (vocab %d)", tokens[i], s->vocab);
@@ -576,7 +590,8 @@ int kr_spec_pending_fail(kr_decode_store* s) {
     return s && s->spec_pending ? kr_fail(KR_ERR_STATE, "a kr_decode_verify is pending: kr_decode_commit must come first") : KR_OK;
 }
 
-// what no exact pass over this store runs: tolerance modes, expert parallelism, MoE layers without an engine or with native-GGUF experts, geometries the
+// what no exact pass over this store runs: tolerance modes, expert parallelism, MoE layers without an engine or with native-GGUF experts (unless the
+// "gguf_exact_pass" option gives those an exact pass, docs/design/20-gguf-exact-pass.md), geometries the
 // verify-form kernels do not cover.  slots: the pass over device slots (multi_refuse, kr_decode_multi.cpp), whose messages start with another noun and whose
 // per-slot kernels refuse more; its clauses sit here, each in its place, because the order of the refusals is part of both contracts
 int kr_exact_refuse(kr_decode_store* s, bool slots) {
@@ -594,8 +609,9 @@ int kr_exact_refuse(kr_decode_store* s, bool slots) {
             return kr_fail(KR_ERR_VALUE, "%s: MLA geometry kv_lora_rank %d nope %d rope %d not covered (kv_lora_rank 512 / 256, rope 64)", what, L.klr, L.nd, L.rd);
         if (L.mlp == MLP_MOE) {
             if (s->own_eng || L.moe_layer >= (int)e->layers.size()) return kr_fail(KR_ERR_STATE, "set_moe_store was not called (MoE layer %d has no engine)", L.moe_layer);
-            if (e->layers[L.moe_layer].gguf)
-                return kr_fail(KR_ERR_STATE, "%s%s is exact-mode only: MoE layer %d holds native GGUF experts (their prompt pass is tolerance-only)", the, what, L.moe_layer);
+            if (e->layers[L.moe_layer].gguf && !s->opt_gguf_exact_pass)
+                return kr_fail(KR_ERR_STATE, "%s%s is exact-mode only: MoE layer %d holds native GGUF experts (their prompt pass is tolerance-only); the \"gguf_exact_pass\" option gives them an exact pass",
+                               the, what, L.moe_layer);
         }
         // the slots' kernels also need whole value-head groups per key head
         if (L.attn == ATTN_LA && (L.kd != 4 || (L.dk != 64 && L.dk != 128) || L.dv > 256 || L.dv % 8 || (slots && L.nv != L.nk * (L.nv / L.nk))))

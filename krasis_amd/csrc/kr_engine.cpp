@@ -884,9 +884,9 @@ static bool gg_fast_ok(const Layer& L, int H, bool use_shared) {
 // Everything moe_prefill_gguf / moe_prefill_gguf_fast would build lazily for one layer, built NOW on `st`.  The whole-model prompt pass calls this for every
 // MoE layer on its main stream before the start event (kr_decode_prefill.cpp prefill_impl): with several chunks in flight on several streams, a lazy build
 // queued on chunk c's stream is not ordered before chunk c + 1's GEMMs on another stream.
-int kr_moe_prefill_prepare(kr_engine* e, int layer, int fast, int routed_only, hipStream_t st) {
+int kr_moe_prefill_prepare(kr_engine* e, int layer, int fast, int routed_only, hipStream_t st, int gguf_exact) {
     Layer& L = e->layers[layer];
-    if (!L.gguf) return KR_OK;
+    if (!L.gguf || gguf_exact) return KR_OK;      // KR_PF_SET_GGUF_EXACT: the exact forms read the blocks as they are, no sums and no copies
     std::lock_guard<std::mutex> lk(e->mu);
     const bool use_shared = L.gguf_shared && !routed_only;
     if (fast && gg_fast_ok(L, e->cfg.hidden_size, use_shared)) {
@@ -1024,6 +1024,67 @@ static int moe_prefill_gguf(kr_engine* e, Layer& L, int layer, const void* x_bf1
     return KR_OK;
 }
 
+// KR_PF_SET_GGUF_EXACT (the decode store's "gguf_exact_pass"): every row with the bits of the decode step's block kernels (docs/design/20-gguf-exact-pass.md).
+// Q4_K / Q8_0 layers: rows sorted by expert, one activation image per row, the grouped kernels of kr_gguf_group.hip; any other layer (Q4_0 / Q5_0 / Q6_K, a k
+// that is no multiple of 32) or `stream`: the streaming kernels of kr_gguf.hip over the rows.  Routed experts only: the weighted sum in routing order, no rsf
+// (the caller's epilogue applies its own, as the decode step's next norm does).  Scratch is the chunk's own set: several chunks may be in flight.
+static int moe_prefill_gguf_exact(kr_engine* e, Layer& L, const void* x_bf16, const int32_t* ids, const float* wts, void* out, int M, int topk,
+                                  int out_dtype, int routed_only, int set, int stream, hipStream_t st) {
+    const int H = e->cfg.hidden_size, I = L.inter, E = e->cfg.n_routed_experts;
+    if (L.gguf_shared && !routed_only) return kr_fail(KR_ERR_VALUE, "the exact GGUF pass covers routed experts only (routed_only = 1)");
+    kr_engine::PfSet& P = e->pf[set % KR_PF_MAX_DEPTH];
+    const size_t ob = out_dtype == KR_OUT_BF16 ? 2 : 4;
+    const bool grouped = !stream && kr_ggg_type_supported(L.g_gate.type, H) && L.g_up.type == L.g_gate.type && kr_ggg_type_supported(L.g_down.type, I) &&
+                         L.g_gate.N == I && L.g_up.N == I && L.g_down.N == H;
+    if (!grouped) {      // grid z = rows: 16 384 per pass
+        const int CH = M < 16384 ? M : 16384;
+        if (P.gu.ensure((size_t)CH * topk * 2 * I * 4) || P.eo.ensure((size_t)CH * topk * H * 4)) return kr_fail(KR_ERR_HIP, "hipMalloc of prefill scratch failed");
+        for (int m0 = 0; m0 < M; m0 += CH) {
+            const int mc = M - m0 < CH ? M - m0 : CH;
+            GgMoeArgs g{};
+            g.B = mc; g.topk = topk; g.n_slots = topk; g.H = H; g.E = E; g.I_max = I; g.gu_ld = 2 * I;
+            g.act = (const uint16_t*)x_bf16 + (size_t)m0 * H; g.ids = ids + (size_t)m0 * topk;
+            g.gate = L.g_gate.view(); g.up = L.g_up.view(); g.down = L.g_down.view();
+            g.gu = (float*)P.gu.p; g.eo = (float*)P.eo.p;
+            kr_launch_gguf_moe(g, st);
+            KrMoeArgs c{};
+            c.B = mc; c.topk = topk; c.n_slots = topk; c.H = H; c.E = E; c.ids = g.ids; c.wts = wts + (size_t)m0 * topk; c.eo = g.eo;
+            c.out = (char*)out + (size_t)m0 * H * ob; c.out_bf16 = out_dtype == KR_OUT_BF16; c.rsf = 1.0f;
+            kr_launch_moe_combine(c, st);
+        }
+        KR_HIP(hipGetLastError());
+        return KR_OK;
+    }
+    const int R = kr_ggg_group_rows();
+    const int pairs = e->pf_pairs > 0 ? e->pf_pairs : KR_PF_PAIRS;
+    const int CHmax = pairs / topk > 64 ? pairs / topk : 64;
+    const int CH = M < CHmax ? M : CHmax;
+    const size_t np = (size_t)CH * topk;
+    const int max_tiles = (int)(np / R) + E + 1;
+    const size_t n_i32 = 3 * (size_t)E + 3 * (size_t)max_tiles + 4 + 2 * np;
+    if (P.i32.ensure(n_i32 * 4) || P.xh.ensure((size_t)CH * kr_ggg_image_stride(H)) || P.hh.ensure(np * kr_ggg_image_stride(I)) || P.gu.ensure(np * 2 * I * 4) || P.eo.ensure(np * H * 4))
+        return kr_fail(KR_ERR_HIP, "hipMalloc of prefill scratch failed");
+    int* ib = (int*)P.i32.p;
+    KrPfSort so{};
+    so.counts = ib; so.offsets = ib + E; so.cursor = ib + 2 * E; ib += 3 * E;
+    so.tile_expert = ib; so.tile_row0 = ib + max_tiles; so.tile_rows = ib + 2 * max_tiles; ib += 3 * max_tiles;
+    so.n_tiles = ib; ib += 4; so.row_pair = ib; so.pair_row = ib + np;
+    const GgMat gate = L.g_gate.view(), up = L.g_up.view(), down = L.g_down.view();
+    for (int m0 = 0; m0 < M; m0 += CH) {
+        const int mc = M - m0 < CH ? M - m0 : CH;
+        const uint16_t* xc = (const uint16_t*)x_bf16 + (size_t)m0 * H;
+        const int32_t* idc = ids + (size_t)m0 * topk; const float* wc = wts + (size_t)m0 * topk;
+        kr_launch_pf_sort(idc, mc, topk, E, so, st, R);
+        kr_launch_ggg_image_x(xc, mc, H, P.xh.p, st);
+        kr_launch_ggg_gemm(gate, &up, P.xh.p, &so, topk, 1, mc * topk, E, (float*)P.gu.p, 2 * I, st);
+        kr_launch_ggg_image_h((const float*)P.gu.p, mc * topk, I, 2 * I, &so, P.hh.p, st);
+        kr_launch_ggg_gemm(down, nullptr, P.hh.p, &so, topk, 0, mc * topk, E, (float*)P.eo.p, H, st);
+        kr_launch_pf_combine((const float*)P.eo.p, so.pair_row, wc, mc, topk, H, nullptr, 1.0f, (char*)out + (size_t)m0 * H * ob, out_dtype == KR_OUT_BF16, st);
+    }
+    KR_HIP(hipGetLastError());
+    return KR_OK;
+}
+
 // kr_moe_prefill in the tolerance form (kr_moe_set_gemm_mode(e, 1)): same launches, the activations travel as f16 rows and the GEMMs run on the
 // f16 matrix cores with f32 accumulation over the whole k range (kr_prefill_h.hip).  Sort, combine, routing weights and skip rules are the exact path's.
 static int moe_prefill_fast(kr_engine* e, Layer& L, const void* x_bf16, const int32_t* ids, const float* wts, void* out, int M, int topk,
@@ -1090,7 +1151,12 @@ int kr_moe_prefill_set(kr_engine* e, int layer, const void* x_bf16, const int32_
     std::lock_guard<std::mutex> lk(e->mu);
     KR_HIP(hipSetDevice(e->device));
     const bool fast = e->gemm_fast || (set & KR_PF_SET_FAST);
+    const bool gguf_exact = set & KR_PF_SET_GGUF_EXACT, gguf_stream = set & KR_PF_SET_GGUF_STREAM;
     set &= 0xFF;
+    if (L.gguf && gguf_exact) {
+        if (fast) return kr_fail(KR_ERR_STATE, "the exact GGUF pass (\"gguf_exact_pass\") does not run together with the tolerance GEMMs (KR_GEMM_FAST)");
+        return moe_prefill_gguf_exact(e, L, x_bf16, ids, wts, out, M, topk, out_dtype, routed_only, set, gguf_stream, st);
+    }
     if (L.gguf) {      // native GGUF blocks: the exact int8-MFMA form, or (tolerance mode, Q4_K layers) f16 MFMA on the re-tiled copy
         if (fast && gg_fast_ok(L, e->cfg.hidden_size, L.gguf_shared && !routed_only)) return moe_prefill_gguf_fast(e, L, x_bf16, ids, wts, out, M, topk, out_dtype, routed_only, set, st);
         return moe_prefill_gguf(e, L, layer, x_bf16, ids, wts, out, M, topk, out_dtype, routed_only, set, st);

@@ -138,6 +138,8 @@ int download_mat(kr_engine* e, MatSet& ms, int idx, void* w, uint16_t* sc);
 int kr_ensure_gate_row(kr_engine* e, int layer);   // kr_engine.cpp: uploads Layer::gate_row on first use (synchronous copy: call before enqueueing the pass)
 int kr_moe_prefill_rows(kr_engine* e, int layer, const void* rows_bf16, const int32_t* lid, void* out, int n, int out_bf16, int set, hipStream_t st);
 #define KR_PF_SET_FAST 0x100   // or-ed into `set`: this call takes the tolerance GEMMs whatever kr_moe_set_gemm_mode says (the decode store's KR_GEMM_FAST)
+#define KR_PF_SET_GGUF_EXACT 0x200    // or-ed into `set`: a native-GGUF layer takes the exact pass (kr_gguf_group.hip; the decode store's "gguf_exact_pass"): every row with the decode step's bits
+#define KR_PF_SET_GGUF_STREAM 0x400   // ... through the streaming kernels of kr_gguf.hip for every block type ("gguf_exact_grouped" 0: A/B and test hook, same bits)
 int kr_moe_prefill_set(kr_engine* e, int layer, const void* x_bf16, const int32_t* ids, const float* wts, void* out, int M, int topk,
                        int out_dtype, int routed_only, int set, hipStream_t st);
 

@@ -35,3 +35,11 @@ void kr_launch_gq_repack(const GgMat& m, int n_experts, void* q_out, size_t q_st
 // Q8_0 -> the tolerance GEMM's INT8 operand form (INT8 lane tiles + one f16 scale per 32-wide block)
 void kr_launch_gq8_repack(const GgMat& m, int n_experts, void* q_out, size_t q_stride, void* qs_out, size_t qs_stride, int tile_off, hipStream_t st);
 void kr_launch_gpf_fill_synth(void* q, size_t q_bytes, void* h, size_t h_bytes, int type, uint64_t seed, hipStream_t st);
+
+// ---- the exact grouped pass (kr_gguf_group.hip): rows sorted by expert in groups of kr_ggg_group_rows(), one activation image per row, the block kernels' chains per row ----
+bool kr_ggg_type_supported(int type, int K);        // Q4_K with K % 256 == 0, Q8_0 with K % 32 == 0
+int kr_ggg_group_rows();                            // rows per tile the sort's tile table must be built with
+size_t kr_ggg_image_stride(int K);                  // bytes of one row's image: {AH4, AL4} per sub-block and AVX lane, f32 scale and i32 sum per sub-block
+void kr_launch_ggg_image_x(const uint16_t* x_bf16, int M, int K, void* img, hipStream_t st);                                     // images of M bf16 rows
+void kr_launch_ggg_image_h(const float* gu, int pairs, int I, int gu_ld, const KrPfSort* sort, void* img, hipStream_t st);       // images of silu(gate) * up of the sorted rows
+void kr_launch_ggg_gemm(const GgMat& m0, const GgMat* m1, const void* img, const KrPfSort* sort, int topk, int gather_tokens, int pairs, int n_experts, float* out, int out_ld, hipStream_t st);

@@ -1,5 +1,6 @@
 // kr_gguf_dev.h -- device side of the native GGUF block experts, shared by kr_gguf.hip (the exact kernels: moe_forward_gguf bit for bit) and
-// kr_decode_fast.hip (KR_DECODE_FAST: the same products with the row's blocks split over two waves and the select / activation / combine folded in).
+// kr_decode_fast.hip (KR_DECODE_FAST: the same products with the row's blocks split over two waves and the select / activation / combine folded in) and
+// kr_gguf_group.hip (the exact grouped pass: an expert's blocks loaded once per group of rows, every row with the chains and the hsum tree below).
 #pragma once
 #include "kr_device.h"
 #include "kr_libm.h"
@@ -102,6 +103,30 @@ __device__ __forceinline__ void gg_scale_min_k4(int j, uint32_t s0, uint32_t s1,
     else { sc = (int)((B(j + 4) & 0xFu) | ((B(j - 4) >> 6) << 4)); mn = (int)((B(j + 4) >> 4) | ((B(j) >> 6) << 4)); }
 }
 
+// ---- the per-sub-block bodies of the int path, shared by the streaming tiles below and the grouped kernels (kr_gguf_group.hip): one weight word of one AVX
+//      lane against one activation image; `s` indexes the image's sub-blocks (the grouped kernels pass a stage-relative index into their LDS images) ----
+// Q4_K: chunk j of a super-block = sub-blocks s_lo (low nibbles) and s_lo + 1 (high nibbles), in this order (matvec_q4_k_avx2, gguf_kernels.rs:271)
+__device__ __forceinline__ void gg_pair_q4k(uint32_t w, float d, float dmin, int sc_lo, int mn_lo, int sc_hi, int mn_hi, const GgAct& A, int s_lo, int l, float& acc, float& corr) {
+    const int s_hi = s_lo + 1;
+    const u32x2 r_lo = *reinterpret_cast<const u32x2*>(A.rec + ((size_t)s_lo * 8 + l) * 2);
+    const u32x2 r_hi = *reinterpret_cast<const u32x2*>(A.rec + ((size_t)s_hi * 8 + l) * 2);
+    const uint32_t lo = w & 0x0F0F0F0Fu, hi = (w >> 4) & 0x0F0F0F0Fu;
+    const int i_lo = (__builtin_amdgcn_sdot4((int)lo, (int)r_lo.x, 0, false) << 8) + (int)__builtin_amdgcn_udot4(lo, r_lo.y, 0u, false);
+    const int i_hi = (__builtin_amdgcn_sdot4((int)hi, (int)r_hi.x, 0, false) << 8) + (int)__builtin_amdgcn_udot4(hi, r_hi.y, 0u, false);
+    const float as_lo = A.scale[s_lo], as_hi = A.scale[s_hi];
+    acc = __builtin_fmaf((float)i_lo, d * (float)sc_lo * as_lo, acc);
+    corr += dmin * (float)mn_lo * as_lo * (float)A.sum[s_lo];
+    acc = __builtin_fmaf((float)i_hi, d * (float)sc_hi * as_hi, acc);
+    corr += dmin * (float)mn_hi * as_hi * (float)A.sum[s_hi];
+}
+// Q8_0: one 32-wide block (matvec_q8_0_avx2, gguf_kernels.rs:379)
+__device__ __forceinline__ void gg_sub_q8_0(uint32_t w, float d, const GgAct& A, int s, int l, float& acc) {
+    const u32x2 r = *reinterpret_cast<const u32x2*>(A.rec + ((size_t)s * 8 + l) * 2);
+    const int iv = (__builtin_amdgcn_sdot4((int)w, (int)r.x, 0, false) << 8) + __builtin_amdgcn_sdot4((int)w, (int)(r.y ^ 0x80808080u), 0, false) +
+                   (__builtin_amdgcn_sdot4((int)w, 0x01010101, 0, false) << 7);
+    acc = __builtin_fmaf((float)iv, d * A.scale[s], acc);
+}
+
 // ---- one row tile (8 rows x 8 lanes), int path; returns the row result in every lane of the row's 8-lane group ----
 // The block records of a tile are REQUESTED IN BATCHES of GG_PF before the first one is consumed (round 4): the loop used to issue one block's two loads,
 // wait for them (one HBM / fabric round trip each), compute, and go on -- K / 256 dependent round trips per tile, the whole duration of the launch.  Indices
@@ -130,17 +155,7 @@ __device__ __forceinline__ float gg_tile_q4k(const GgMat& m, int tile, const GgA
                 for (int j = 0; j < 4; j++) {
                     int sc_lo, mn_lo, sc_hi, mn_hi;
                     gg_scale_min_k4(2 * j, hd.y, hd.z, hd.w, sc_lo, mn_lo); gg_scale_min_k4(2 * j + 1, hd.y, hd.z, hd.w, sc_hi, mn_hi);
-                    const int s_lo = b * 8 + 2 * j, s_hi = s_lo + 1;
-                    const u32x2 r_lo = *reinterpret_cast<const u32x2*>(A.rec + ((size_t)s_lo * 8 + l) * 2);
-                    const u32x2 r_hi = *reinterpret_cast<const u32x2*>(A.rec + ((size_t)s_hi * 8 + l) * 2);
-                    const uint32_t lo = wj[j] & 0x0F0F0F0Fu, hi = (wj[j] >> 4) & 0x0F0F0F0Fu;
-                    const int i_lo = (__builtin_amdgcn_sdot4((int)lo, (int)r_lo.x, 0, false) << 8) + (int)__builtin_amdgcn_udot4(lo, r_lo.y, 0u, false);
-                    const int i_hi = (__builtin_amdgcn_sdot4((int)hi, (int)r_hi.x, 0, false) << 8) + (int)__builtin_amdgcn_udot4(hi, r_hi.y, 0u, false);
-                    const float as_lo = A.scale[s_lo], as_hi = A.scale[s_hi];
-                    acc = __builtin_fmaf((float)i_lo, d * (float)sc_lo * as_lo, acc);
-                    corr += dmin * (float)mn_lo * as_lo * (float)A.sum[s_lo];
-                    acc = __builtin_fmaf((float)i_hi, d * (float)sc_hi * as_hi, acc);
-                    corr += dmin * (float)mn_hi * as_hi * (float)A.sum[s_hi];
+                    gg_pair_q4k(wj[j], d, dmin, sc_lo, mn_lo, sc_hi, mn_hi, A, b * 8 + 2 * j, l, acc, corr);
                 }
             }
         }
@@ -169,10 +184,7 @@ __device__ __forceinline__ float gg_tile_q8_0(const GgMat& m, int tile, const Gg
                 for (int u = 0; u < 4; u++) {
                     const int s = bg * 4 + u;
                     if (s < nb) {
-                        const u32x2 r = *reinterpret_cast<const u32x2*>(A.rec + ((size_t)s * 8 + l) * 2);
-                        const int iv = (__builtin_amdgcn_sdot4((int)wb[u], (int)r.x, 0, false) << 8) + __builtin_amdgcn_sdot4((int)wb[u], (int)(r.y ^ 0x80808080u), 0, false) +
-                                       (__builtin_amdgcn_sdot4((int)wb[u], 0x01010101, 0, false) << 7);
-                        acc = __builtin_fmaf((float)iv, dd[u] * A.scale[s], acc);
+                        gg_sub_q8_0(wb[u], dd[u], A, s, l, acc);
                     }
                 }
             }

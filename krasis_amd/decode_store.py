@@ -300,7 +300,12 @@ class CpuDecodeStore:
         """options by name.  Test / tuning hooks ("gqa_stream", "pfm_timing", "multi_sample_loop", ...), and "multi_attn_fast" (default 0): with 1
         the GQA layers of every batched step (step_multi, step_multi_sample, generate_multi) run split-KV flash-decode over slots of max_seq > 1024
         -- tolerance form, row i bit-identical to decode_step under set_attention_mode(True) on that sequence alone; shorter slots keep the exact
-        step; nothing else in the store changes; a store with MLA layers is then refused by the batched calls (docs/design/16-multi-attn-fast.md)"""
+        step; nothing else in the store changes; a store with MLA layers is then refused by the batched calls (docs/design/16-multi-attn-fast.md).
+        "gguf_exact_pass" (default 0): with 1 every multi-row pass (prefill, prefill_nll, verify, and the batched pass behind every slot call) runs
+        native-GGUF MoE layers through the exact grouped block kernels -- every row carries the bits of decode_step on that sequence alone -- and the
+        slot and speculation calls accept a store with such layers; slower than the default int8-MFMA form on long prompts; refused together with
+        gemm_fast; nothing changes for other weight forms (docs/design/20-gguf-exact-pass.md).  "gguf_exact_grouped" (default 1): 0 makes that pass
+        take the streaming block kernels for every type (A/B and test hook, same bits)"""
         self._need(); check(self._lib.kr_decode_set_option(self._h, name.encode(), int(value)))
 
     def finalize_decode(self) -> None:
