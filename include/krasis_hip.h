@@ -474,6 +474,26 @@ int kr_decode_generate_multi_lookup_sample(kr_decode_store* s, int n, const int3
                                   int* n_passes_out, int32_t* n_accepted_out, void* stream);
 /* one slot's sampler state read back (a zero bitmap and a zero state before any sampler was set); refused while a verify over slots is pending */
 int kr_decode_slot_sampler_get(kr_decode_store* s, int slot, uint32_t* seen_out /* (vocab + 31) / 32 words */, uint64_t* rng_out);
+/* ---- paged slots (docs/design/21-paged-slots.md).  A paged slot set behaves as a flat one of the same n_slots and max_seq through every slot entry point --
+   ids, logits, n_match, stored rows, conv / recurrent state and sampler state are the same bit for bit -- but the KV rows of every GQA layer (K and V pools
+   [n_pages][page_tokens][nkv * hd]) and the latent and rope-key rows of every MLA layer ([n_pages][page_tokens][klr] / [..][rd]) live in pages shared by all
+   slots, in the store's current KV element type; linear-attention state stays per slot.  One page table serves all layers: int32
+   [n_slots][ceil(max_seq / page_tokens)], -1 = unmapped, page id p = page p of every pool.  So capacity is bounded by the pool, not by n_slots * max_seq,
+   and rows in a page that is not mapped read as zero.
+   Mapping is host-side and all or nothing per call: after its argument checks and before anything is queued, a call maps the pages its rows still need to
+   cover [0, position + count), lowest free id first, and makes them read as zero; if the pool cannot give them it fails with KR_ERR_STATE naming the first
+   row that does not fit, and nothing is mapped or run.  kr_decode_generate_multi* reserve [0, start + max_tokens) before the first pass and on return give
+   back the pages that call mapped which lie wholly past each row's final position.  kr_decode_verify_multi* map the drafted positions and the commit leaves
+   them mapped.  kr_decode_slot_save maps what [0, seq_len) needs; kr_decode_slot_load zeroes the store's rows of pages that are not mapped.
+   With "multi_attn_fast" set every batched call on paged slots is refused (KR_ERR_STATE).
+   Replaces any earlier slots, flat or paged.  page_tokens: a power of two, at least 32; n_pages >= 1; n_slots >= 1.  *bytes_out (may be NULL) = pools +
+   linear-attention state + table. */
+int kr_decode_slots_create_paged(kr_decode_store* s, int n_slots, int max_seq, int page_tokens, int n_pages, size_t* bytes_out);
+/* every page of the slot with index >= ceil(seq_len / page_tokens) back to the pool (seq_len 0: all of them); linear-attention state and sampler untouched.
+   On flat slots a no-op that still checks its arguments (slot in range, 0 <= seq_len <= max_seq).  Refused while a verify over slots is pending. */
+int kr_decode_slot_trim(kr_decode_store* s, int slot, int seq_len);
+/* the geometry, the free pages and the mapped pages of every slot (per_slot_out [n_slots], may be NULL; so may the others).  Flat slots: page_tokens 0, n_pages 0 */
+int kr_decode_slots_pages(kr_decode_store* s, int32_t* page_tokens_out, int32_t* n_pages_out, int32_t* n_free_out, int32_t* per_slot_out);
 /* test aid beside kr_sample_rows: the verify-form sampler, the accept kernel and the sampler commit on host logits [T][vocab] in caller order (the runs
    concatenated: counts[n] in [1, KR_VERIFY_MAX], tokens[T]); run i is its own "slot" with per-run parameters, seen bitmap [n][(vocab+31)/32] and xorshift64
    state (both in / out: the state after the commit).  ids_out[T] and n_match_out[n] as kr_decode_verify_multi_sample's.  n_keep[n] in / out: the wanted

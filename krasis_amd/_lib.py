@@ -34,6 +34,7 @@ SYMBOLS = [
     "kr_decode_slot_sampler", "kr_decode_step_multi_sample", "kr_decode_generate_multi_sample", "kr_sample_rows",
     "kr_decode_extend_multi", "kr_decode_verify_multi", "kr_decode_commit_multi", "kr_decode_generate_multi_lookup",
     "kr_decode_verify_multi_sample", "kr_decode_generate_multi_lookup_sample", "kr_decode_slot_sampler_get", "kr_sample_runs",
+    "kr_decode_slots_create_paged", "kr_decode_slot_trim", "kr_decode_slots_pages",
 ]
 TOKEN_CB = C.CFUNCTYPE(C.c_int, C.c_int, C.c_int, C.c_void_p)      # kr_token_cb(token, finish_reason, user) -> continue?
 
@@ -176,6 +177,9 @@ def load_library() -> C.CDLL:
     lib.kr_decode_generate_lookup.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, vp, ci, vp, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), vp]
     lib.kr_lookup_draft.argtypes = [vp, ci, ci, ci, vp]
     lib.kr_decode_slots_create.argtypes = [vp, ci, ci, C.POINTER(C.c_size_t)]
+    lib.kr_decode_slots_create_paged.argtypes = [vp, ci, ci, ci, ci, C.POINTER(C.c_size_t)]
+    lib.kr_decode_slot_trim.argtypes = [vp, ci, ci]
+    lib.kr_decode_slots_pages.argtypes = [vp, vp, vp, vp, vp]
     lib.kr_decode_slot_save.argtypes = [vp, ci, ci]
     lib.kr_decode_slot_load.argtypes = [vp, ci, ci]
     lib.kr_decode_step_multi.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp]

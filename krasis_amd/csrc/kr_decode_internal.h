@@ -8,6 +8,7 @@
 #include "kr_decode_ops.h"
 #include "kr_engine_internal.h"
 #include "kr_multi.h"
+#include "kr_page_pool.h"
 #include "kr_spec.h"
 
 struct DWeight { MatSet ms; int rows = 0, cols = 0; };
@@ -39,6 +40,10 @@ struct kr_multi_state {
     int n_slots = 0, max_seq = 0, kv_fp8 = 0;
     std::vector<DevBuf> a, b;                  // per layer: LA conv / recurrent state, GQA K / V, MLA latent / rope-key rows
     std::vector<size_t> a_stride, b_stride;    // per layer: bytes per slot
+    // paged slots (kr_decode_slots_create_paged, docs/design/21-paged-slots.md): a / b of a GQA or MLA layer are then pools [n_pages][page_tokens][row] shared by
+    // all slots and a_stride / b_stride the bytes of one page.  pg: the free list and the page table on the host; pg_table: its device copy; pg_pools: KrPagePoolDev
+    // of every pool; pg_new: the ids of the pages a pass has to zero.  pg_pending: mappings made on the host that the device has not seen yet (pg_flush)
+    KrPagePool pg; DevBuf pg_table, pg_pools, pg_new; int pg_npools = 0; std::vector<KrPageChange> pg_pending;
     DevBuf rows, ids, logits, scores, scratch; // step: [slots | tokens | positions] (device), greedy ids, [n][vocab] logits, attention scores, the arena
     DevBuf fd_o, fd_ml; bool fd_ready = false; // "multi_attn_fast": split-KV partials [n][nkv][chunks][G][hd] and (max, sum) [n][nh][chunks][2] of one GQA layer, sized by the step's longest row; the kernels' LDS windows are raised
     // per-slot samplers (kr_decode_slot_sampler, docs/design/14-multi-sampling.md): allocated for every slot on the first call; empty = every slot greedy

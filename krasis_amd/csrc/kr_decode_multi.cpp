@@ -16,6 +16,8 @@
 // that the drafts before it were the sampler's draws; the commit applies the kept draws to the samplers.  All four generation entry points
 // (kr_decode_generate_multi, its _sample, _lookup and _lookup_sample forms) are one loop, generate_slots: steps where no row drafts (max_draft 0: always),
 // verify + commit where one does, with the draft rule of kr_lookup_index.h.
+// Paged slots (kr_decode_slots_create_paged, docs/design/21-paged-slots.md): the GQA / MLA rows live in pools of pages shared by all slots; every entry point maps
+// the pages its rows need on the host first (kr_page_pool.h), all or nothing, and the pass opens by sending the changed table entries and zeroing the new pages.
 #include <algorithm>
 #include <chrono>
 #include <climits>
@@ -58,6 +60,64 @@ int multi_begin(kr_decode_store* s) {
 int slot_in_range(kr_decode_store* s, int slot) {
     return slot < 0 || slot >= s->multi->n_slots ? kr_fail(KR_ERR_VALUE, "slot %d out of range [0, %d)", slot, s->multi->n_slots) : KR_OK;
 }
+// ---- paged slots (docs/design/21-paged-slots.md): the GQA / MLA rows live in pools of pages shared by all slots; M.pg is the allocator and the table
+// "multi_attn_fast" reads flat slots only: with the option on every batched call on paged slots is refused (an option that silently does nothing is a trap)
+int paged_refuse(kr_decode_store* s) {
+    if (s->multi->pg.paged() && s->opt_multi_attn_fast)
+        return kr_fail(KR_ERR_STATE, "\"multi_attn_fast\" does not read paged slots (kr_decode_slots_create_paged): clear the option or create flat slots");
+    return KR_OK;
+}
+// all or nothing, on the host: slot slots[i] gets the pages that cover [0, lens[i]), lowest free id first; the mappings wait in pg_pending for pg_flush and
+// are appended to log (a caller that gives some back later)
+int pg_reserve(kr_decode_store* s, int n, const int32_t* slots, const long long* lens, std::vector<KrPageChange>* log) {
+    kr_multi_state& M = *s->multi;
+    if (!M.pg.paged()) return KR_OK;
+    const size_t before = M.pg_pending.size();
+    int need = 0, have = 0;
+    const int bad = M.pg.reserve(n, slots, lens, &M.pg_pending, &need, &have);
+    if (bad >= 0)
+        return kr_fail(KR_ERR_STATE, "row %d: slot %d does not fit the page pool: positions [0, %lld) bring the call to %d more pages of %d positions, %d of %d are free",
+                       bad, slots[bad], lens[bad], need, M.pg.page_tokens, have, M.pg.n_pages);
+    if (log) log->insert(log->end(), M.pg_pending.begin() + (ptrdiff_t)before, M.pg_pending.end());
+    return KR_OK;
+}
+struct Rows;
+int pg_reserve_rows(kr_decode_store* s, const Rows& r, int extra, std::vector<KrPageChange>* log);
+// table entries [lo, hi] of a slot -> the device copy (pageable source: staged before the call returns)
+int pg_upload(kr_multi_state& M, int slot, int lo, int hi, hipStream_t st) {
+    const size_t o = (size_t)slot * M.pg.stride + (size_t)lo;
+    KR_HIP(hipMemcpyAsync((int32_t*)M.pg_table.p + o, M.pg.table.data() + o, (size_t)(hi - lo + 1) * 4, hipMemcpyHostToDevice, st));
+    return KR_OK;
+}
+// what the host mapped since the last pass -> the device, on the pass's stream ahead of the pass: the changed table entries, then ONE launch that makes the
+// new pages read as zero in every layer's pools, as a freshly created flat slot does
+int pg_flush(kr_multi_state& M, hipStream_t st) {
+    if (M.pg_pending.empty()) return KR_OK;
+    std::vector<int32_t> pages;
+    std::vector<int> lo((size_t)M.n_slots, INT_MAX), hi((size_t)M.n_slots, -1);
+    for (const KrPageChange& c : M.pg_pending) {
+        pages.push_back(c.page);
+        lo[(size_t)c.slot] = std::min(lo[(size_t)c.slot], (int)c.idx); hi[(size_t)c.slot] = std::max(hi[(size_t)c.slot], (int)c.idx);
+    }
+    M.pg_pending.clear();
+    for (int sl = 0; sl < M.n_slots; sl++) if (hi[(size_t)sl] >= 0) if (int rc = pg_upload(M, sl, lo[(size_t)sl], hi[(size_t)sl], st)) return rc;
+    KR_HIP(hipMemcpyAsync(M.pg_new.p, pages.data(), pages.size() * 4, hipMemcpyHostToDevice, st));      // pg_new holds n_pages ids, and a page is pending once
+    kr_launch_multi_zero_pages((const KrPagePoolDev*)M.pg_pools.p, M.pg_npools, (const int*)M.pg_new.p, (int)pages.size(), st);
+    KR_HIP(hipGetLastError());
+    return KR_OK;
+}
+// pages went back to the pool (freed): a mapping of them the device has not seen is dropped with them, and the slots' table rows go to the device
+int pg_released(kr_decode_store* s, const std::vector<KrPageChange>& freed) {
+    kr_multi_state& M = *s->multi;
+    if (freed.empty()) return KR_OK;
+    M.pg_pending.erase(std::remove_if(M.pg_pending.begin(), M.pg_pending.end(), [&](const KrPageChange& c) { return M.pg.row(c.slot)[c.idx] != c.page; }), M.pg_pending.end());
+    KR_HIP(hipSetDevice(s->eng->device));
+    std::vector<char> hit((size_t)M.n_slots, 0);
+    for (const KrPageChange& c : freed) hit[(size_t)c.slot] = 1;
+    for (int sl = 0; sl < M.n_slots; sl++) if (hit[(size_t)sl]) if (int rc = pg_upload(M, sl, 0, M.pg.stride - 1, s->eng->stream)) return rc;
+    KR_HIP(hipStreamSynchronize(s->eng->stream));
+    return KR_OK;
+}
 // the rows of one call, as they travel from the entry points inward: row i = slot slots[i] runs cnt(i) tokens of `tokens` (the runs in call order) at
 // positions[i] ...
 struct Rows {
@@ -96,6 +156,13 @@ int check_args(kr_decode_store* s, const Rows& r, int extra) {
         if (has_mla && last >= mla_rope) return kr_fail(KR_ERR_VALUE, "row %d: position %lld past the MLA rope table (%d)", i, last, mla_rope);
     }
     return KR_OK;
+}
+// paged slots: the pages row i still needs to cover [0, positions[i] + cnt(i) + extra)
+int pg_reserve_rows(kr_decode_store* s, const Rows& r, int extra, std::vector<KrPageChange>* log) {
+    if (!s->multi->pg.paged()) return KR_OK;
+    std::vector<long long> lens((size_t)r.n);
+    for (int i = 0; i < r.n; i++) lens[(size_t)i] = (long long)r.positions[i] + r.cnt(i) + extra;
+    return pg_reserve(s, r.n, r.slots, lens.data(), log);
 }
 // what a row with these sampler parameters does: the three paths of kr_decode_generate's loop (kr_decode.cpp generate_core)
 KrMsRow mode_row(int slot, float temperature, int top_k, float top_p, float penalty, int vocab, bool force_loop) {
@@ -195,6 +262,7 @@ struct Pass { size_t T = 0; int max_pos = 0; std::vector<KrMsRow> sr; std::vecto
 int open_pass(kr_decode_store* s, const Rows& r, bool sample, bool verify, hipStream_t st, Pass& p) {
     kr_multi_state& M = *s->multi;
     std::vector<int> row_of;
+    if (int rc = pg_flush(M, st)) return rc;      // paged slots: the table entries and zeroed pages of this pass's rows, ahead of the pass
     if (int rc = put_rows(M, r, st, p.T, p.max_pos, verify ? &row_of : nullptr)) return rc;
     std::vector<KrMsRow> per_run;
     bool greedy = true;
@@ -242,6 +310,8 @@ int step_entry(kr_decode_store* s, const Rows& r, int32_t* next_out, float* logi
     if (int rc = multi_begin(s)) return rc;
     if (int rc = check_args(s, r, 0)) return rc;
     if (!next_out) return kr_fail(KR_ERR_VALUE, "null next_out");
+    if (int rc = paged_refuse(s)) return rc;
+    if (int rc = pg_reserve_rows(s, r, 0, nullptr)) return rc;      // all or nothing, before anything is queued
     KR_HIP(hipSetDevice(s->eng->device));
     hipStream_t st = kr_pick_stream(s->eng, stream);
     if (int rc = order_after_store(s, st)) return rc;
@@ -258,11 +328,28 @@ int slot_copy(kr_decode_store* s, int slot, int seq_len, bool save) {
     for (size_t i = 0; i < s->layers.size(); i++)
         if ((s->layers[i].attn == ATTN_GQA || s->layers[i].attn == ATTN_MLA) && (!s->layers[i].kv_k.p || !s->layers[i].kv_v.p))
             return kr_fail(KR_ERR_STATE, "set_decode_state was not called (no %s cache for layer %zu)", s->layers[i].attn == ATTN_MLA ? "MLA" : "KV", i);
+    const bool paged = M.pg.paged();
+    if (paged && save) { const int32_t sl = slot; const long long len = seq_len; if (int rc = pg_reserve(s, 1, &sl, &len, nullptr)) return rc; }      // what [0, seq_len) needs
     KR_HIP(hipSetDevice(s->eng->device));
     KR_HIP(hipDeviceSynchronize());          // steps / prompt passes still in flight on any stream read or write both sides
     hipStream_t st = s->eng->stream;
+    if (int rc = pg_flush(M, st)) return rc;
     for (size_t i = 0; i < s->layers.size(); i++) {
         DLayer& L = s->layers[i];
+        if (paged && (L.attn == ATTN_GQA || L.attn == ATTN_MLA)) {      // page by page; a page that is not mapped reads as zero (load only: save has mapped them)
+            const size_t esz = M.kv_fp8 ? 1 : 2, row[2] = {(L.attn == ATTN_GQA ? (size_t)L.nkv * L.hd : (size_t)L.klr) * esz, (L.attn == ATTN_GQA ? (size_t)L.nkv * L.hd : (size_t)L.rd) * esz};
+            for (int j = 0; j < M.pg.pages_of(seq_len); j++) {
+                const int pg = M.pg.row(slot)[j];
+                const size_t r0 = (size_t)j << M.pg.shift, nr = std::min((size_t)M.pg.page_tokens, (size_t)seq_len - r0);
+                for (int h = 0; h < 2; h++) {
+                    char* own = (char*)(h ? L.kv_v.p : L.kv_k.p) + r0 * row[h];
+                    char* pool = (char*)(h ? M.b[i].p : M.a[i].p) + (size_t)std::max(pg, 0) * (h ? M.b_stride[i] : M.a_stride[i]);
+                    if (pg < 0) KR_HIP(hipMemsetAsync(own, 0, nr * row[h], st));
+                    else KR_HIP(hipMemcpyAsync(save ? pool : own, save ? own : pool, nr * row[h], hipMemcpyDeviceToDevice, st));
+                }
+            }
+            continue;
+        }
         char* a = (char*)M.a[i].p + (size_t)slot * M.a_stride[i];
         char* b = (char*)M.b[i].p + (size_t)slot * M.b_stride[i];
         void *sa, *sb; size_t na, nb;
@@ -418,6 +505,20 @@ int generate_slots(kr_decode_store* s, const Rows& first, int max_tokens, const 
         if (!smp->top_k || !smp->top_p || !smp->presence_penalty || !smp->rng_seeds) return kr_fail(KR_ERR_VALUE, "null sampler parameter array");
         for (int i = 0; i < n; i++) if (!(smp->temperature[i] >= 0.0f)) return kr_fail(KR_ERR_VALUE, "row %d: temperature must be >= 0", i);
     }
+    if (int rc = paged_refuse(s)) return rc;
+    // paged slots: [0, start + max_tokens) of every row is reserved here, before the first pass; on return, success or error, the pages THIS call mapped that lie
+    // wholly past a row's final position go back (ps: the position each row consumes next)
+    std::vector<int32_t> ps(first.positions, first.positions + n);
+    struct PageGuard {
+        kr_decode_store* s; const Rows& first; const std::vector<int32_t>& ps; std::vector<KrPageChange> log;
+        ~PageGuard() {
+            if (log.empty()) return;
+            std::vector<KrPageChange> freed;
+            for (int i = 0; i < first.n; i++) s->multi->pg.release_logged(log, first.slots[i], ps[(size_t)i], &freed);
+            (void)pg_released(s, freed);
+        }
+    } guard{s, first, ps, {}};
+    if (int rc = pg_reserve_rows(s, first, std::max(max_tokens - 1, 0), &guard.log)) return rc;
     for (int i = 0; i < n; i++) { out.n[i] = 0; if (out.n_accepted) out.n_accepted[i] = 0; }
     if (out.n_passes) *out.n_passes = 0;
     if (max_tokens == 0 && !smp) return KR_OK;
@@ -444,7 +545,7 @@ int generate_slots(kr_decode_store* s, const Rows& first, int max_tokens, const 
     }
     auto is_stop = [&](int t) { for (int j = 0; j < n_stop; j++) if (stop_ids[j] == t) return true; return false; };
     std::vector<int> act((size_t)n);                           // rows still generating, in caller order
-    std::vector<int32_t> tk(first.tokens, first.tokens + n), ps(first.positions, first.positions + n);
+    std::vector<int32_t> tk(first.tokens, first.tokens + n);
     for (int i = 0; i < n; i++) act[(size_t)i] = i;
     int passes = 0;
     while (!act.empty()) {
@@ -483,9 +584,18 @@ int generate_slots(kr_decode_store* s, const Rows& first, int max_tokens, const 
 }
 }  // namespace
 
-extern "C" int kr_decode_slots_create(kr_decode_store* s, int n_slots, int max_seq, size_t* bytes_out) {
+// flat slots (page_tokens 0), or paged ones: every GQA / MLA layer then gets pools [n_pages][page_tokens][row] instead of [n_slots][max_seq][row]
+static int slots_create(kr_decode_store* s, int n_slots, int max_seq, int page_tokens, int n_pages, size_t* bytes_out) {
     if (int rc = multi_ready(s)) return rc;
     if (n_slots < 0 || (n_slots > 0 && max_seq < 1)) return kr_fail(KR_ERR_VALUE, "bad slot geometry: %d slots of %d positions", n_slots, max_seq);
+    const bool paged = page_tokens != 0;
+    KrPagePool pool;
+    if (paged) {
+        if (n_slots < 1) return kr_fail(KR_ERR_VALUE, "bad slot geometry: %d slots of %d positions", n_slots, max_seq);
+        const int bad = pool.init(n_slots, max_seq, page_tokens, n_pages, KR_PAGE_MIN_TOKENS);
+        if (bad == 1) return kr_fail(KR_ERR_VALUE, "page_tokens %d: must be a power of two and at least %d (a stage of the MLA attention kernel)", page_tokens, KR_PAGE_MIN_TOKENS);
+        if (bad) return kr_fail(KR_ERR_VALUE, "n_pages %d: must be at least 1", n_pages);
+    }
     KR_HIP(hipSetDevice(s->eng->device));
     KR_HIP(hipDeviceSynchronize());          // a step in flight may still use the old slots
     s->multi.reset();
@@ -493,26 +603,67 @@ extern "C" int kr_decode_slots_create(kr_decode_store* s, int n_slots, int max_s
     if (n_slots == 0) return KR_OK;
     auto M = std::make_unique<kr_multi_state>();
     M->n_slots = n_slots; M->max_seq = max_seq; M->kv_fp8 = s->kv_fp8;
-    const size_t nl = s->layers.size();
+    const size_t nl = s->layers.size(), seq_rows = paged ? (size_t)page_tokens : (size_t)max_seq;      // rows per slot, or per page
+    std::vector<KrPagePoolDev> pools;
     M->a.resize(nl); M->b.resize(nl); M->a_stride.assign(nl, 0); M->b_stride.assign(nl, 0);
     size_t total = 0;
     for (size_t i = 0; i < nl; i++) {
         const DLayer& L = s->layers[i];
         if (L.attn == ATTN_LA) { M->a_stride[i] = (size_t)(2 * L.nk * L.dk + L.nv * L.dv) * L.kd * 4; M->b_stride[i] = (size_t)L.nv * L.dk * L.dv * 4; }
-        else if (L.attn == ATTN_GQA) M->a_stride[i] = M->b_stride[i] = (size_t)max_seq * L.nkv * L.hd * (s->kv_fp8 ? 1 : 2);
-        else if (L.attn == ATTN_MLA) { M->a_stride[i] = (size_t)max_seq * L.klr * (s->kv_fp8 ? 1 : 2); M->b_stride[i] = (size_t)max_seq * L.rd * (s->kv_fp8 ? 1 : 2); }
+        else if (L.attn == ATTN_GQA) M->a_stride[i] = M->b_stride[i] = seq_rows * L.nkv * L.hd * (s->kv_fp8 ? 1 : 2);
+        else if (L.attn == ATTN_MLA) { M->a_stride[i] = seq_rows * L.klr * (s->kv_fp8 ? 1 : 2); M->b_stride[i] = seq_rows * L.rd * (s->kv_fp8 ? 1 : 2); }
+        const bool pooled = paged && (L.attn == ATTN_GQA || L.attn == ATTN_MLA);
         for (int h = 0; h < 2; h++) {
             DevBuf& d = h ? M->b[i] : M->a[i];
-            const size_t bytes = (h ? M->b_stride[i] : M->a_stride[i]) * (size_t)n_slots;
+            const size_t stride = h ? M->b_stride[i] : M->a_stride[i], bytes = stride * (size_t)(pooled ? n_pages : n_slots);
             if (!bytes) continue;
+            if (pooled && stride % 16) return kr_fail(KR_ERR_VALUE, "layer %zu: a page of %zu bytes is not a multiple of 16", i, stride);
             if (d.ensure(bytes)) return kr_fail(KR_ERR_HIP, "hipMalloc of %d sequence slots (%zu MiB so far) failed", n_slots, (total + bytes) >> 20);
-            KR_HIP(hipMemsetAsync(d.p, 0, bytes, s->eng->stream));
+            if (pooled) pools.push_back(KrPagePoolDev{d.p, stride});      // a page is zeroed when it is mapped (pg_flush)
+            else KR_HIP(hipMemsetAsync(d.p, 0, bytes, s->eng->stream));
             total += bytes;
         }
+    }
+    if (paged) {      // the table (-1 everywhere), the pools' addresses and room for the ids of the pages a pass zeroes
+        const size_t tb = pool.table.size() * 4;
+        if (M->pg_table.ensure(tb) || M->pg_pools.ensure(std::max(pools.size(), (size_t)1) * sizeof(KrPagePoolDev)) || M->pg_new.ensure((size_t)n_pages * 4))
+            return kr_fail(KR_ERR_HIP, "hipMalloc of the page table (%zu KiB) failed", tb >> 10);
+        KR_HIP(hipMemsetAsync(M->pg_table.p, 0xFF, tb, s->eng->stream));
+        if (!pools.empty()) KR_HIP(hipMemcpyAsync(M->pg_pools.p, pools.data(), pools.size() * sizeof(KrPagePoolDev), hipMemcpyHostToDevice, s->eng->stream));
+        M->pg_npools = (int)pools.size(); M->pg = std::move(pool);
+        total += tb;
     }
     KR_HIP(hipStreamSynchronize(s->eng->stream));
     s->multi = std::move(M);
     if (bytes_out) *bytes_out = total;
+    return KR_OK;
+}
+
+extern "C" int kr_decode_slots_create(kr_decode_store* s, int n_slots, int max_seq, size_t* bytes_out) { return slots_create(s, n_slots, max_seq, 0, 0, bytes_out); }
+
+// ---- paged slots (docs/design/21-paged-slots.md)
+extern "C" int kr_decode_slots_create_paged(kr_decode_store* s, int n_slots, int max_seq, int page_tokens, int n_pages, size_t* bytes_out) {
+    if (page_tokens == 0) return kr_fail(KR_ERR_VALUE, "page_tokens 0: must be a power of two and at least %d (a stage of the MLA attention kernel)", KR_PAGE_MIN_TOKENS);
+    return slots_create(s, n_slots, max_seq, page_tokens, n_pages, bytes_out);
+}
+extern "C" int kr_decode_slot_trim(kr_decode_store* s, int slot, int seq_len) {
+    if (int rc = multi_begin(s)) return rc;
+    if (int rc = slot_in_range(s, slot)) return rc;
+    kr_multi_state& M = *s->multi;
+    if (seq_len < 0 || seq_len > M.max_seq) return kr_fail(KR_ERR_VALUE, "seq_len %d outside [0, %d] (slot max_seq)", seq_len, M.max_seq);
+    if (!M.pg.paged()) return KR_OK;
+    std::vector<KrPageChange> freed;
+    M.pg.trim(slot, seq_len, &freed);
+    return pg_released(s, freed);      // every slot call returns with its stream drained: nothing in flight reads the pages
+}
+extern "C" int kr_decode_slots_pages(kr_decode_store* s, int32_t* page_tokens_out, int32_t* n_pages_out, int32_t* n_free_out, int32_t* per_slot_out) {
+    if (int rc = multi_ready(s)) return rc;
+    if (int rc = need_slots(s)) return rc;
+    const kr_multi_state& M = *s->multi;
+    if (page_tokens_out) *page_tokens_out = M.pg.page_tokens;
+    if (n_pages_out) *n_pages_out = M.pg.n_pages;
+    if (n_free_out) *n_free_out = M.pg.n_free;
+    if (per_slot_out) for (int i = 0; i < M.n_slots; i++) per_slot_out[i] = M.pg.paged() ? M.pg.mapped(i) : 0;
     return KR_OK;
 }
 
@@ -598,6 +749,8 @@ static int verify_entry(kr_decode_store* s, Rows r, int32_t* ids_out, int32_t* n
     if (!ids_out || !n_match_out) return kr_fail(KR_ERR_VALUE, "null %s / n_match_out", sample ? "sampled_out" : "greedy_out");
     for (int i = 0; i < r.n; i++)
         if (r.counts[i] > KR_VERIFY_MAX) return kr_fail(KR_ERR_VALUE, "row %d: a run of %d tokens, at most %d (KR_VERIFY_MAX) in a verify", i, r.counts[i], KR_VERIFY_MAX);
+    if (int rc = paged_refuse(s)) return rc;
+    if (int rc = pg_reserve_rows(s, r, 0, nullptr)) return rc;      // the drafted positions too: the commit leaves them mapped (the caller may trim)
     KR_HIP(hipSetDevice(s->eng->device));
     hipStream_t st = kr_pick_stream(s->eng, stream);
     if (int rc = order_after_store(s, st)) return rc;

@@ -159,6 +159,7 @@ static int run_layer(kr_decode_store* s, Chunk& cx, size_t li) {
             m.rope_cos = (const float*)s->rope_cos.p; m.rope_sin = (const float*)s->rope_sin.p; m.rope_half = s->rope_half;
             m.k_cache = M.a[li].p; m.v_cache = M.b[li].p; m.slot_elems = M.a_stride[li] / (M.kv_fp8 ? 1 : 2); m.kv_fp8 = M.kv_fp8;
             m.q_out = B.q; m.gate = B.gate; m.attn_out = B.attn; m.scores = (float*)M.scores.p; m.sc_ld = cx.m_sc_ld;
+            if (M.pg.paged()) { m.page_table = (const int*)M.pg_table.p; m.page_stride = M.pg.stride; m.page_shift = M.pg.shift; }      // paged slots: a / b are pools
             m.gated = L.gated; m.nh = L.nh; m.nkv = L.nkv; m.hd = L.hd; m.eps = s->eps; m.sm_scale = L.sm_scale;
             if (cx.m_fd_chunks) { m.fd_o = (float*)M.fd_o.p; m.fd_ml = (float*)M.fd_ml.p; m.fd_chunk = cx.m_fd_chunk; m.fd_chunks = cx.m_fd_chunks; }      // "multi_attn_fast", long slots
             if (kr_launch_multi_gqa(m, Cc, st)) return kr_fail(KR_ERR_VALUE, "unsupported GQA geometry for the multi-sequence step");
@@ -217,6 +218,7 @@ static int run_layer(kr_decode_store* s, Chunk& cx, size_t li) {
             m.ckv_cache = M.a[li].p; m.kpe_cache = M.b[li].p; m.ckv_stride = M.a_stride[li]; m.kpe_stride = M.b_stride[li]; m.kv_fp8 = M.kv_fp8;
             m.q_abs = B.q; m.q_pe = B.z; m.attn_lat = B.recur; m.v_proj = B.attn; m.scores = (float*)M.scores.p; m.sc_ld = cx.m_sc_ld;
             m.nh = L.nh; m.klr = L.klr; m.nd = L.nd; m.rd = L.rd; m.vhd = L.vhd; m.eps = s->eps; m.sm_scale = L.sm_scale;
+            if (M.pg.paged()) { m.page_table = (const int*)M.pg_table.p; m.page_stride = M.pg.stride; m.page_shift = M.pg.shift; }      // paged slots: the strides are a page's bytes
             if (nkv < L.klr + L.rd) return kr_fail(KR_ERR_VALUE, "kv_a_proj rows %d < kv_lora_rank + rope dim", nkv);
             if (oc != L.nh * L.vhd) return kr_fail(KR_ERR_VALUE, "o_proj cols %d != nh*v_head_dim", oc);
             if (kr_launch_multi_mla(m, Cc, st)) return kr_fail(KR_ERR_VALUE, "unsupported MLA geometry for the multi-sequence step");

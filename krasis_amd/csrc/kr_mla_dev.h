@@ -74,7 +74,8 @@ __device__ __forceinline__ void kr_mla_rope_qpe(const float* qh, float* q_pe_h, 
 // rope (decode.rs:3098-3107, 3131-3140), both rows stored at `pos` of the caches.  sh: 640 floats of LDS (klr <= 576 values, sh[639] = rms).
 template <bool FP8>
 __device__ __forceinline__ void kr_mla_append_row(const float* kv_out, const float* kv_a_norm, const float* rope_cos, const float* rope_sin, void* ckv_cache,
-                                                  void* kpe_cache, int pos, int klr, int rd, float eps, float* sh) {
+                                                  void* kpe_cache, int pos, int klr, int rd, float eps, float* sh, int at = -1) {
+    const int wr = at < 0 ? pos : at;      // the row of the caches it lands in: `pos`, or (paged slots) the position inside the page the caches point at
     const int t = threadIdx.x, half = rd / 2;
     float* x = sh;
     for (int i = t; i < klr; i += 64) x[i] = kv_out[i];
@@ -95,12 +96,12 @@ __device__ __forceinline__ void kr_mla_append_row(const float* kv_out, const flo
     const float rms = sh[639];
     for (int i = t; i < klr; i += 64) {
         const float v = x[i] * (rms * kv_a_norm[i]);                                     // x *= rms * w (decode.rs:3030)
-        kr_mla_st<FP8>(ckv_cache, (size_t)pos * klr + i, v);
+        kr_mla_st<FP8>(ckv_cache, (size_t)wr * klr + i, v);
     }
     if (t < half) {
         const float x1 = kv_out[klr + 2 * t], x2 = kv_out[klr + 2 * t + 1];
         const float c = rope_cos[(size_t)pos * half + t], s = rope_sin[(size_t)pos * half + t];
-        kr_mla_st<FP8>(kpe_cache, (size_t)pos * rd + t, x1 * c - x2 * s);
-        kr_mla_st<FP8>(kpe_cache, (size_t)pos * rd + half + t, x2 * c + x1 * s);
+        kr_mla_st<FP8>(kpe_cache, (size_t)wr * rd + t, x1 * c - x2 * s);
+        kr_mla_st<FP8>(kpe_cache, (size_t)wr * rd + half + t, x2 * c + x1 * s);
     }
 }

@@ -53,6 +53,9 @@ struct KrMultiGqaArgs {
     // "multi_attn_fast" (kr_multi_flash.hip): split-KV partials [B][nkv][fd_chunks][G][hd] and (max, sum) [B][nh][fd_chunks][2]; fd_chunk positions per
     // chunk, fd_chunks = the longest row's chunk count.  Null: the exact per-slot kernel (scores is not read when they are set)
     float *fd_o, *fd_ml; int fd_chunk, fd_chunks;
+    // paged slots (docs/design/21-paged-slots.md): page_table [n_slots][page_stride] on the device, -1 = unmapped; k_cache / v_cache are then pools
+    // [n_pages][1 << page_shift][nkv * hd] and position s of slot b is row (page_table[b][s >> page_shift] << page_shift) | (s & mask).  Null: flat slots
+    const int* page_table; int page_stride, page_shift;
 };
 // 0: launched; 1: geometry not covered (hd 64 / 128 / 256, nh % nkv == 0)
 int kr_launch_multi_gqa(const KrMultiGqaArgs& a, int B, hipStream_t st);
@@ -74,11 +77,18 @@ struct KrMultiMlaArgs {
     float* scores; int sc_ld;                  // scratch [B][nh][sc_ld], sc_ld >= the longest row's pos + 1 rounded up to 32
     int nh, klr, nd, rd, vhd; float eps, sm_scale;
     int absorb_done;                           // set by the launch: q_abs came from the matrix-core absorption, the prep launch skips its tiles
+    // paged slots, as KrMultiGqaArgs: ckv_cache / kpe_cache are pools [n_pages][1 << page_shift][klr] / [..][rd]; a stage of KR_MM_ROWS rows lies in one page
+    const int* page_table; int page_stride, page_shift;
 };
 // the geometries the per-slot MLA kernels are specialised for (klr 512 / 256 with rd 64; nd within the prep launch's LDS row)
 int kr_multi_mla_ok(int klr, int nd, int rd);
 // 0: launched (absorption, prep, attention, w_vc projection); 1: geometry not covered
 int kr_launch_multi_mla(const KrMultiMlaArgs& a, int B, hipStream_t st);
+
+// paged slots: the pools of every layer, and the launch that makes freshly mapped pages read as zero in all of them -- grid (n_pages, n_pools), one launch per pass
+#define KR_PAGE_MIN_TOKENS 32      // = KR_MM_ROWS (kr_multi.hip): a stage of the MLA attention kernel never straddles a page
+struct KrPagePoolDev { void* base; size_t page_bytes; };
+void kr_launch_multi_zero_pages(const KrPagePoolDev* pools, int n_pools, const int* pages, int n_pages, hipStream_t st);
 
 // per row b < B of logits [B][ld]: out[b] = first-maximum argmax of the row's first V values (kr_argmax_kernel's rule)
 void kr_launch_multi_argmax(const float* logits, size_t ld, int V, int B, int* out, hipStream_t st);

@@ -237,6 +237,8 @@ int kr_launch_multi_la(const KrMultiLaArgs& a, const int* runs, int n_runs, int 
 // ---- GQA -----------------------------------------------------------------------------------------------------------------------------------------
 // decode.rs:2873-2966 per row: gated split, per-head RMS norm (scalar sequential sum), half-split RoPE at the row's position, K / V into the row's
 // slot.  grid (nh + nkv, B), 256 threads (hd <= 256).  The exact branch of kr_gqa_prep_kernel.
+// PAGED (docs/design/21-paged-slots.md): the row lands in the page of the slot's table that holds its position; the flat instantiation is the code above it
+template <bool PAGED>
 __global__ void __launch_bounds__(256) kr_multi_gqa_prep_kernel(const KrMultiGqaArgs a) {
     __shared__ float x[256]; __shared__ float rms_s;
     const int hb = blockIdx.x, row = blockIdx.y, d = threadIdx.x, hd = a.hd, pos = a.positions[row];
@@ -271,7 +273,11 @@ __global__ void __launch_bounds__(256) kr_multi_gqa_prep_kernel(const KrMultiGqa
     if (d < hd) {
         if (is_q) a.q_out[(size_t)row * a.nh * hd + (size_t)h * hd + d] = val;
         else {
-            const size_t o = (size_t)a.slots[row] * a.slot_elems + (size_t)pos * a.nkv * hd + (size_t)h * hd + d;
+            size_t o;
+            if constexpr (PAGED) {
+                const int pg = max(a.page_table[(size_t)a.slots[row] * a.page_stride + (pos >> a.page_shift)], 0);      // mapped by the host before the pass
+                o = (((size_t)pg << a.page_shift) | (size_t)(pos & ((1 << a.page_shift) - 1))) * a.nkv * hd + (size_t)h * hd + d;
+            } else o = (size_t)a.slots[row] * a.slot_elems + (size_t)pos * a.nkv * hd + (size_t)h * hd + d;
             kr_kv_store(a.k_cache, o, val, a.kv_fp8);
             kr_kv_store(a.v_cache, o, a.v_in[(size_t)row * a.ld_v + (size_t)h * hd + d], a.kv_fp8);
         }
@@ -286,7 +292,9 @@ __global__ void __launch_bounds__(256) kr_multi_gqa_prep_kernel(const KrMultiGqa
 #define KR_MG_TILE 1024      // softmax-sum tile per wave (floats)
 #define KR_MG_PT 64          // positions per P.V stage
 #define KR_MG_ACC 16         // heads per thread and pass of the P.V loop
-template <int NB, bool FP8>
+// PAGED: the slot's table slice for [0, seq) is loaded into LDS once, and position s is row (page << shift) | (s & mask) of the pools; the loops and their
+// order are the flat kernel's
+template <int NB, bool FP8, bool PAGED>
 __global__ void __launch_bounds__(256) kr_multi_gqa_attn_kernel(const KrMultiGqaArgs a) {
     constexpr int HD = NB * 8;
     extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -296,7 +304,19 @@ __global__ void __launch_bounds__(256) kr_multi_gqa_attn_kernel(const KrMultiGqa
     float* pt = tile + 4 * KR_MG_TILE;               // [G][KR_MG_PT]
     const int kvh = blockIdx.x, row = blockIdx.y, t = threadIdx.x, lane = t & 63, w = t >> 6;
     const int pos = a.positions[row], seq = pos + 1, kvs = a.nkv * HD;
-    const size_t kv0 = (size_t)a.slots[row] * a.slot_elems + (size_t)kvh * HD;      // element of (position 0, this KV head) in the slot
+    const size_t kv0 = PAGED ? (size_t)kvh * HD : (size_t)a.slots[row] * a.slot_elems + (size_t)kvh * HD;      // element of (position 0, this KV head) in the slot (paged: in a page)
+    const int* pgt = reinterpret_cast<const int*>(pt + (size_t)G * KR_MG_PT);      // PAGED: [ceil(seq / page_tokens)] page ids of the slot
+    const int psh = PAGED ? a.page_shift : 0, pmask = (1 << psh) - 1;
+    if constexpr (PAGED) {
+        const int* src = a.page_table + (size_t)a.slots[row] * a.page_stride;
+        int* dst = reinterpret_cast<int*>(pt + (size_t)G * KR_MG_PT);
+        for (int i = t; i < ((seq + pmask) >> psh); i += 256) dst[i] = max(src[i], 0);      // every page of [0, seq) was mapped by the host before the pass
+    }
+    // element of (position s, this KV head)
+    auto kvat = [&](int s) -> size_t {
+        if constexpr (PAGED) return kv0 + (((size_t)pgt[s >> psh] << psh) | (size_t)(s & pmask)) * kvs;
+        else return kv0 + (size_t)s * kvs;
+    };
     float* sc = a.scores + ((size_t)row * a.nh + (size_t)kvh * G) * a.sc_ld;        // [G][sc_ld]
     const float* q = a.q_out + (size_t)row * a.nh * HD + (size_t)kvh * G * HD;
     for (int i = t; i < G * HD; i += 256) qs[i] = q[i];
@@ -307,7 +327,7 @@ __global__ void __launch_bounds__(256) kr_multi_gqa_attn_kernel(const KrMultiGqa
         for (int s = grp; s < seq; s += 32) {
             float kr[NB];
 #pragma unroll
-            for (int e = 0; e < NB; e++) kr[e] = kr_kv_load(a.k_cache, kv0 + (size_t)s * kvs + e * 8 + l, FP8);
+            for (int e = 0; e < NB; e++) kr[e] = kr_kv_load(a.k_cache, kvat(s) + e * 8 + l, FP8);
             for (int g = 0; g < G; g++) {
                 float acc = 0.0f;
 #pragma unroll
@@ -361,7 +381,7 @@ __global__ void __launch_bounds__(256) kr_multi_gqa_attn_kernel(const KrMultiGqa
             for (int s1 = 0; s1 < n; s1 += 16) {
                 float v[16];
 #pragma unroll
-                for (int u = 0; u < 16; u++) v[u] = kr_kv_load(a.v_cache, kv0 + (size_t)(s0 + min(s1 + u, n - 1)) * kvs + d, FP8);
+                for (int u = 0; u < 16; u++) v[u] = kr_kv_load(a.v_cache, kvat(s0 + min(s1 + u, n - 1)) + d, FP8);
 #pragma unroll
                 for (int u = 0; u < 16; u++) {
 #pragma unroll
@@ -387,17 +407,25 @@ __global__ void __launch_bounds__(256) kr_multi_gqa_attn_kernel(const KrMultiGqa
 int kr_launch_multi_gqa(const KrMultiGqaArgs& a, int B, hipStream_t st) {
     if ((a.hd != 64 && a.hd != 128 && a.hd != 256) || a.nkv < 1 || a.nh % a.nkv || a.sc_ld % 32) return 1;
     const int G = a.nh / a.nkv;
-    const size_t lds = ((size_t)G * a.hd + 4 * KR_MG_TILE + (size_t)G * KR_MG_PT) * 4;
-    if (a.fd_o) {      // "multi_attn_fast": the same prep launch, then split-KV flash-decode over the slots (kr_multi_flash.hip)
+    const size_t lds = ((size_t)G * a.hd + 4 * KR_MG_TILE + (size_t)G * KR_MG_PT + (a.page_table ? (size_t)a.page_stride : 0)) * 4;
+    if (a.fd_o) {
+        if (a.page_table) return 1;      // the split-KV form reads flat slots only (refused with a message at the entry points)      // "multi_attn_fast": the same prep launch, then split-KV flash-decode over the slots (kr_multi_flash.hip)
         if (!kr_multi_fd_ok(a.nh, a.nkv, a.hd) || !a.fd_ml || a.fd_chunks < 1 || a.fd_chunks > 1024) return 1;
-        hipLaunchKernelGGL(kr_multi_gqa_prep_kernel, dim3(a.nh + a.nkv, B), dim3(256), 0, st, a);
+        hipLaunchKernelGGL(kr_multi_gqa_prep_kernel<false>, dim3(a.nh + a.nkv, B), dim3(256), 0, st, a);
         return kr_launch_multi_fd(a, B, a.fd_chunks, st);
     }
     if (lds > 64 * 1024) return 1;
-    hipLaunchKernelGGL(kr_multi_gqa_prep_kernel, dim3(a.nh + a.nkv, B), dim3(256), 0, st, a);
-#define KR_MGA(NB_, F_) hipLaunchKernelGGL((kr_multi_gqa_attn_kernel<NB_, F_>), dim3(a.nkv, B), dim3(256), lds, st, a)
-    if (a.kv_fp8) { if (a.hd == 256) KR_MGA(32, true); else if (a.hd == 128) KR_MGA(16, true); else KR_MGA(8, true); }
-    else { if (a.hd == 256) KR_MGA(32, false); else if (a.hd == 128) KR_MGA(16, false); else KR_MGA(8, false); }
+#define KR_MGA(NB_, F_, P_) hipLaunchKernelGGL((kr_multi_gqa_attn_kernel<NB_, F_, P_>), dim3(a.nkv, B), dim3(256), lds, st, a)
+#define KR_MGA_HD(F_, P_) do { if (a.hd == 256) KR_MGA(32, F_, P_); else if (a.hd == 128) KR_MGA(16, F_, P_); else KR_MGA(8, F_, P_); } while (0)
+    if (a.page_table) {
+        if (a.page_stride < 1 || a.page_shift < 5) return 1;
+        hipLaunchKernelGGL(kr_multi_gqa_prep_kernel<true>, dim3(a.nh + a.nkv, B), dim3(256), 0, st, a);
+        if (a.kv_fp8) KR_MGA_HD(true, true); else KR_MGA_HD(false, true);
+        return 0;
+    }
+    hipLaunchKernelGGL(kr_multi_gqa_prep_kernel<false>, dim3(a.nh + a.nkv, B), dim3(256), 0, st, a);
+    if (a.kv_fp8) KR_MGA_HD(true, false); else KR_MGA_HD(false, false);
+#undef KR_MGA_HD
 #undef KR_MGA
     return 0;
 }
@@ -407,7 +435,8 @@ int kr_launch_multi_gqa(const KrMultiGqaArgs& a, int B, hipStream_t st) {
 // functions of kr_mla_dev.h.  grid (nh * klr / 64 + 1, B) -- or (nh + 1, B) when the matrix-core absorption has produced q_abs -- 64 threads:
 // workgroups below the last: absorption tile (h, jt) of row b, the jt == 0 one also ropes q_pe[h] at the row's position; the last: latent RMSNorm,
 // k_pe rope, both rows stored at the row's position of the row's slot.
-template <bool FP8>
+// PAGED: kr_mla_append_row receives the base of the page that holds the position, and the position inside it
+template <bool FP8, bool PAGED>
 __global__ void __launch_bounds__(64) kr_multi_mla_prep_kernel(const KrMultiMlaArgs a) {
     __shared__ float sh[640];
     const int row = blockIdx.y, pos = a.positions[row];
@@ -420,8 +449,14 @@ __global__ void __launch_bounds__(64) kr_multi_mla_prep_kernel(const KrMultiMlaA
         return;
     }
     const size_t slot = (size_t)a.slots[row];
-    kr_mla_append_row<FP8>(a.kv_out + (size_t)row * a.ld_kv, a.kv_a_norm, a.rope_cos, a.rope_sin, (char*)a.ckv_cache + slot * a.ckv_stride,
-                           (char*)a.kpe_cache + slot * a.kpe_stride, pos, a.klr, a.rd, a.eps, sh);
+    if constexpr (PAGED) {      // ckv_stride / kpe_stride = bytes of one page; the rope tables are still read at the position itself
+        const size_t pg = (size_t)max(a.page_table[slot * a.page_stride + (pos >> a.page_shift)], 0);      // mapped by the host before the pass
+        kr_mla_append_row<FP8>(a.kv_out + (size_t)row * a.ld_kv, a.kv_a_norm, a.rope_cos, a.rope_sin, (char*)a.ckv_cache + pg * a.ckv_stride,
+                               (char*)a.kpe_cache + pg * a.kpe_stride, pos, a.klr, a.rd, a.eps, sh, pos & ((1 << a.page_shift) - 1));
+    } else {
+        kr_mla_append_row<FP8>(a.kv_out + (size_t)row * a.ld_kv, a.kv_a_norm, a.rope_cos, a.rope_sin, (char*)a.ckv_cache + slot * a.ckv_stride,
+                               (char*)a.kpe_cache + slot * a.kpe_stride, pos, a.klr, a.rd, a.eps, sh);
+    }
 }
 
 // Attention of KR_MM_HG heads of row b over the slot's rows [0, pos].  grid (ceil(nh / KR_MM_HG), B), 512 threads.  The latent + rope rows are
@@ -433,7 +468,10 @@ __global__ void __launch_bounds__(64) kr_multi_mla_prep_kernel(const KrMultiMlaA
 //   weighted sum: the rows staged again; thread t owns latent element t % klr of heads t / klr + k * (512 / klr): one fma per position, ascending
 #define KR_MM_ROWS 32
 #define KR_MM_HG 4
-template <bool FP8, int NBC>
+static_assert(KR_PAGE_MIN_TOKENS % KR_MM_ROWS == 0, "a stage of the MLA attention kernel lies in one page");
+// PAGED: a stage lies in one page (page_tokens is a multiple of KR_MM_ROWS), so each stage builds its two descriptors from that page's base with
+// num_records = the page's rows below the current length; a stage past the end or in an unmapped page gets num_records 0 and reads zeros
+template <bool FP8, int NBC, bool PAGED>
 __global__ void __launch_bounds__(512) kr_multi_mla_attn_kernel(const KrMultiMlaArgs a) {
     constexpr int klr = NBC * 8, NBR = 8, rd = NBR * 8, esz = FP8 ? 1 : 2, HG = KR_MM_HG, ROWS = KR_MM_ROWS;
     constexpr int CPR_C = klr * esz / 16, CPR_R = rd * esz / 16, pitch = (klr + rd) * esz + 16, NLC = ROWS * CPR_C / 512;
@@ -448,20 +486,44 @@ __global__ void __launch_bounds__(512) kr_multi_mla_attn_kernel(const KrMultiMla
     const int seq = a.positions[row] + 1, nst = (seq + ROWS - 1) / ROWS;
     const size_t slot = (size_t)a.slots[row];
     float* sc = a.scores + ((size_t)row * a.nh + hg0) * a.sc_ld;                  // [nhg][sc_ld]
-    const __amdgpu_buffer_rsrc_t srd_c = __builtin_amdgcn_make_buffer_rsrc((char*)a.ckv_cache + slot * a.ckv_stride, 0, seq * klr * esz, 0x00020000);
-    const __amdgpu_buffer_rsrc_t srd_r = __builtin_amdgcn_make_buffer_rsrc((char*)a.kpe_cache + slot * a.kpe_stride, 0, seq * rd * esz, 0x00020000);
+    const __amdgpu_buffer_rsrc_t srd_c = __builtin_amdgcn_make_buffer_rsrc((char*)a.ckv_cache + (PAGED ? 0 : slot * a.ckv_stride), 0, PAGED ? 0 : seq * klr * esz, 0x00020000);
+    const __amdgpu_buffer_rsrc_t srd_r = __builtin_amdgcn_make_buffer_rsrc((char*)a.kpe_cache + (PAGED ? 0 : slot * a.kpe_stride), 0, PAGED ? 0 : seq * rd * esz, 0x00020000);
+    // PAGED: the page of stage s0 (a multiple of ROWS) -> its id made wave-uniform for the descriptors (-1: none) and the rows of it that are below seq
+    const int psh = PAGED ? a.page_shift : 0, pmask = (1 << psh) - 1;
+    const int* ptab = PAGED ? a.page_table + slot * a.page_stride : nullptr;
+    auto page_of = [&](int s0, int& nrec) -> int {
+        int pg = -1;
+        if (s0 < seq) pg = ptab[s0 >> psh];
+        pg = __builtin_amdgcn_readfirstlane(pg);
+        nrec = pg >= 0 ? min(1 << psh, seq - (s0 & ~pmask)) : 0;
+        return max(pg, 0);
+    };
     // unconditional loads: rows at or past the current length are outside the descriptors and read as zero
     struct Regs { u32x4 c[NLC]; u32x4 r; };
     const int rrow = t / CPR_R, rcol = t % CPR_R;
     const bool has_r = t < ROWS * CPR_R;
     auto issue_c = [&](Regs& R, int s0) {
+        __amdgpu_buffer_rsrc_t srd = srd_c; int r0 = s0;      // the descriptor and the first row of the stage inside it
+        if constexpr (PAGED) {
+            int nrec; const int pg = page_of(s0, nrec);
+            srd = __builtin_amdgcn_make_buffer_rsrc((char*)a.ckv_cache + (size_t)pg * a.ckv_stride, 0, nrec * klr * esz, 0x00020000);
+            r0 = s0 & pmask;
+        }
 #pragma unroll
         for (int i = 0; i < NLC; i++) {
             const int c = t + 512 * i, r = c / CPR_C, col = c % CPR_C;
-            R.c[i] = __builtin_amdgcn_raw_buffer_load_b128(srd_c, (s0 + r) * klr * esz + col * 16, 0, 0);
+            R.c[i] = __builtin_amdgcn_raw_buffer_load_b128(srd, (r0 + r) * klr * esz + col * 16, 0, 0);
         }
     };
-    auto issue_r = [&](Regs& R, int s0) { R.r = __builtin_amdgcn_raw_buffer_load_b128(srd_r, has_r ? (s0 + rrow) * rd * esz + rcol * 16 : 0x7FFFFFF0, 0, 0); };
+    auto issue_r = [&](Regs& R, int s0) {
+        __amdgpu_buffer_rsrc_t srd = srd_r; int r0 = s0;
+        if constexpr (PAGED) {
+            int nrec; const int pg = page_of(s0, nrec);
+            srd = __builtin_amdgcn_make_buffer_rsrc((char*)a.kpe_cache + (size_t)pg * a.kpe_stride, 0, nrec * rd * esz, 0x00020000);
+            r0 = s0 & pmask;
+        }
+        R.r = __builtin_amdgcn_raw_buffer_load_b128(srd, has_r ? (r0 + rrow) * rd * esz + rcol * 16 : 0x7FFFFFF0, 0, 0);
+    };
     auto commit_c = [&](const Regs& R) {
 #pragma unroll
         for (int i = 0; i < NLC; i++) {
@@ -587,15 +649,17 @@ int kr_multi_mla_ok(int klr, int nd, int rd) { return (klr == 512 || klr == 256)
 int kr_launch_multi_mla(const KrMultiMlaArgs& a_in, int B, hipStream_t st) {
     KrMultiMlaArgs a = a_in;
     if (!kr_multi_mla_ok(a.klr, a.nd, a.rd) || a.nh < 1 || a.sc_ld % 32) return 1;
+    if (a.page_table && (a.page_stride < 1 || (1 << a.page_shift) < KR_MM_ROWS)) return 1;      // a stage must not straddle a page
     static_assert(kr_multi_mla_lds<false, 64>() <= 64 * 1024, "the attention kernel stays inside the default 64 KiB LDS window");
     // the w_kc absorption, row-wise: from 32 rows on the matrix cores (one fma chain per output, the prompt pass's launch), the prep launch's tiles below
     a.absorb_done = B >= 32 && kr_launch_mla_absorb_mfma(a.q_full, a.ld_q, a.nd + a.rd, a.nd, a.w_kc, a.klr, a.q_abs, B, a.nh, st) == 0;
     const dim3 pg(a.nh * (a.absorb_done ? 1 : a.klr / 64) + 1, B), ag((a.nh + KR_MM_HG - 1) / KR_MM_HG, B);
-    if (a.kv_fp8) hipLaunchKernelGGL(kr_multi_mla_prep_kernel<true>, pg, dim3(64), 0, st, a);
-    else hipLaunchKernelGGL(kr_multi_mla_prep_kernel<false>, pg, dim3(64), 0, st, a);
-#define KR_MMA(F_, NBC_) hipLaunchKernelGGL((kr_multi_mla_attn_kernel<F_, NBC_>), ag, dim3(512), (kr_multi_mla_lds<F_, NBC_>()), st, a)
-    if (a.kv_fp8) { if (a.klr == 512) KR_MMA(true, 64); else KR_MMA(true, 32); }
-    else { if (a.klr == 512) KR_MMA(false, 64); else KR_MMA(false, 32); }
+#define KR_MMA(F_, NBC_, P_) hipLaunchKernelGGL((kr_multi_mla_attn_kernel<F_, NBC_, P_>), ag, dim3(512), (kr_multi_mla_lds<F_, NBC_>()), st, a)
+#define KR_MMA_ALL(P_) do { \
+    if (a.kv_fp8) { hipLaunchKernelGGL((kr_multi_mla_prep_kernel<true, P_>), pg, dim3(64), 0, st, a); if (a.klr == 512) KR_MMA(true, 64, P_); else KR_MMA(true, 32, P_); } \
+    else { hipLaunchKernelGGL((kr_multi_mla_prep_kernel<false, P_>), pg, dim3(64), 0, st, a); if (a.klr == 512) KR_MMA(false, 64, P_); else KR_MMA(false, 32, P_); } } while (0)
+    if (a.page_table) KR_MMA_ALL(true); else KR_MMA_ALL(false);
+#undef KR_MMA_ALL
 #undef KR_MMA
     // the w_vc projection, row-wise: the prompt pass's matrix-core launch from 32 rows, the decode launch with a token dimension below
     if (B >= 32 && kr_launch_mla_wvc_mfma(a.w_vc, a.attn_lat, a.v_proj, B, a.nh, a.vhd, a.klr, st) == 0) return 0;
@@ -604,6 +668,18 @@ int kr_launch_multi_mla(const KrMultiMlaArgs& a_in, int B, hipStream_t st) {
     m.q_abs = a.q_abs; m.q_pe = a.q_pe; m.attn_lat = a.attn_lat; m.v_proj = a.v_proj; m.nh = a.nh; m.klr = a.klr; m.nd = a.nd; m.rd = a.rd; m.vhd = a.vhd;
     kr_launch_mla_wvc(m, st, B);
     return 0;
+}
+
+// ---- paged slots: freshly mapped pages read as zero in every pool (docs/design/21-paged-slots.md).  grid (n_pages, n_pools), 256 threads; page_bytes % 16 == 0
+__global__ void __launch_bounds__(256) kr_multi_zero_pages_kernel(const KrPagePoolDev* __restrict__ pools, const int* __restrict__ pages) {
+    const KrPagePoolDev P = pools[blockIdx.y];
+    uint4* dst = reinterpret_cast<uint4*>((char*)P.base + (size_t)pages[blockIdx.x] * P.page_bytes);
+    const size_t n = P.page_bytes / 16;
+    for (size_t i = threadIdx.x; i < n; i += 256) dst[i] = make_uint4(0u, 0u, 0u, 0u);
+}
+void kr_launch_multi_zero_pages(const KrPagePoolDev* pools, int n_pools, const int* pages, int n_pages, hipStream_t st) {
+    if (n_pools < 1 || n_pages < 1) return;
+    hipLaunchKernelGGL(kr_multi_zero_pages_kernel, dim3(n_pages, n_pools), dim3(256), 0, st, pools, pages);
 }
 
 // ---- per-row greedy id ---------------------------------------------------------------------------------------------------------------------------

@@ -412,14 +412,35 @@ class CpuDecodeStore:
         return list(out[: n.value])
 
     # ------------------------------------------------------------------ sequence slots (docs/design/13-multi-sequence.md)
-    def create_slots(self, n: int, max_seq: int) -> int:
+    def create_slots(self, n: int, max_seq: int, page_tokens: Optional[int] = None, n_pages: Optional[int] = None) -> int:
         """kr_decode_slots_create: n zeroed sequence slots of up to max_seq positions (replacing any earlier ones; n = 0 frees them), KV rows
-        (for an MLA layer: compressed-KV rows [kv_lora_rank] and rope-key rows [rope dim]) of the store's current element type.  Returns their device bytes."""
+        (for an MLA layer: compressed-KV rows [kv_lora_rank] and rope-key rows [rope dim]) of the store's current element type.  Returns their device bytes.
+        With page_tokens and n_pages (kr_decode_slots_create_paged, docs/design/21-paged-slots.md) the GQA / MLA rows live in a pool of n_pages pages of
+        page_tokens positions (a power of two, at least 32) shared by all slots: same results bit for bit, capacity bounded by the pool; a call that
+        needs more pages than are free fails with KR_ERR_STATE and changes nothing."""
         self._need()
+        if (page_tokens is None) != (n_pages is None):
+            raise ValueError("create_slots: page_tokens and n_pages go together")
         b = C.c_size_t()
-        check(self._lib.kr_decode_slots_create(self._h, n, max_seq, C.byref(b)))
+        if page_tokens is None:
+            check(self._lib.kr_decode_slots_create(self._h, n, max_seq, C.byref(b)))
+        else:
+            check(self._lib.kr_decode_slots_create_paged(self._h, n, max_seq, page_tokens, n_pages, C.byref(b)))
         self._multi_verify_rows = None      # a pending verify_multi goes with the slots
+        self._n_slots = n
         return b.value
+
+    def trim_slot(self, slot: int, seq_len: int) -> None:
+        """kr_decode_slot_trim: the pages of a paged slot wholly at or past position seq_len go back to the pool (0: all); a checked no-op on flat slots"""
+        self._need(); check(self._lib.kr_decode_slot_trim(self._h, slot, seq_len))
+
+    def slot_pages(self) -> dict:
+        """kr_decode_slots_pages: dict(page_tokens, n_pages, free, per_slot) -- per_slot[i] = pages mapped to slot i; flat slots: page_tokens 0, n_pages 0"""
+        self._need()
+        pt, npg, free = C.c_int32(), C.c_int32(), C.c_int32()
+        per = np.zeros(max(int(getattr(self, "_n_slots", 0)), 1), dtype=np.int32)
+        check(self._lib.kr_decode_slots_pages(self._h, C.byref(pt), C.byref(npg), C.byref(free), per.ctypes.data))
+        return dict(page_tokens=pt.value, n_pages=npg.value, free=free.value, per_slot=[int(x) for x in per[: int(getattr(self, "_n_slots", 0))]])
 
     def save_slot(self, slot: int, seq_len: int) -> None:
         """the store's own sequence -> slot: KV rows [0, seq_len) of every GQA layer, compressed-KV and rope-key rows [0, seq_len) of every MLA
