@@ -111,7 +111,7 @@ __global__ void __launch_bounds__(256, 2) kr_pfm_gqa_scores_mfma_kernel(const Kr
             for (int j = 0; j < 8; j++) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(qa[j], ka[j], acc[j], 0, 0, 0);
         }
     }
-    // hsum8 of the reference (kr_pfm_hsum8: xor 4, xor 1, xor 2), * sm_scale, causal store; the maximum of every row over this block's 32
+    // hsum8 of the reference (kr_hsum8: xor 4, xor 1, xor 2), * sm_scale, causal store; the maximum of every row over this block's 32
     // positions goes to tmax[row][32-position block] so that pass B finds the row maximum without another walk over the score scratch (the
     // scratch is the traffic of the exact attention: a 20 k-token context is 1.3 GB of scores per chunk and layer)
     const int pos = p_lo + pb + r31;

@@ -15,6 +15,7 @@
 #include "kr_lds_optin.h"
 #include "kr_device.h"
 #include "kr_libm.h"
+#include "kr_exact_dev.h"
 #include "kr_decode_ops.h"
 
 #define KR_FD_CH 256
@@ -43,9 +44,7 @@ __global__ void __launch_bounds__(256) kr_fd_partial_kernel(const KrFdArgs a, in
     for (int g = 0; g < GMAX; g++) sv[g] = (g < G && t < n) ? a.sc_g[(size_t)(kvh * G + g) * max_seq + p0 + t] : -__builtin_inff();
 #pragma unroll
     for (int g = 0; g < GMAX; g++) {
-        float m = sv[g];
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
+        const float m = kr_wave_max(sv[g]);
         if ((t & 63) == 0) red[t >> 6][g] = m;
     }
     __syncthreads();
@@ -136,9 +135,7 @@ __global__ void __launch_bounds__(1024) kr_fd_merge_kernel(const KrFdArgs a, int
     const int seq = a.step->pos + 1, nc = min((seq + KR_FD_CH - 1) / KR_FD_CH, 1024);
     const float* ml = a.fd_ml + (size_t)h * n_chunks * 2;
     const float mv = t < nc ? ml[t * 2] : -__builtin_inff(), lv = t < nc ? ml[t * 2 + 1] : 0.0f;
-    float mx = mv;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
+    float mx = kr_wave_max(mv);
     if ((t & 63) == 0) red[t >> 6] = mx;
     __syncthreads();
     mx = red[0];

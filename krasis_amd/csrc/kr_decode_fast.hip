@@ -13,6 +13,7 @@
 
 #include "kr_device.h"
 #include "kr_libm.h"
+#include "kr_exact_dev.h"
 #include "kr_matvec_dev.h"
 #include "kr_topk.h"
 
@@ -203,7 +204,7 @@ __device__ __forceinline__ void kr_f_norm_finish(const KrFNormIn& in, const KrFN
     if ((t & 63) == 0) s_red[t >> 6] = ss;
     __syncthreads();
     const float tot = (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
-    const float rms = 1.0f / sqrtf(tot / (float)in.n + in.eps);
+    const float rms = kr_rms_inv(tot, in.n, in.eps);
 #pragma unroll
     for (int u = 0; u < 2; u++)
 #pragma unroll
@@ -346,15 +347,11 @@ __global__ void __launch_bounds__(256) kr_fdm_kernel(const void* p0, const float
     if (out_lane) {
         if (kind < 0) my[col] = acc;
         else if (kind == 3) a.z_out[dst] = acc;
-        else if (kind == 4) a.beta_out[dst] = 1.0f / (1.0f + kr_expf(-acc));
-        else if (kind == 5) {
-            const float ap_dt = acc + g_dt;
-            const float softplus = ap_dt > 20.0f ? ap_dt : kr_logf(1.0f + kr_expf(ap_dt));
-            a.ge_out[dst] = kr_expf(-(kr_expf(g_al)) * softplus);
-        } else {   // decode.rs:3815-3890: depthwise conv1d (kernel 4) over the shifted state, SiLU; the state shift is this lane's alone
+        else if (kind == 4) a.beta_out[dst] = kr_la_beta(acc);
+        else if (kind == 5) a.ge_out[dst] = kr_expf(kr_la_g(acc, g_dt, g_al));
+        else {   // decode.rs:3815-3890: depthwise conv1d (kernel 4) over the shifted state, SiLU; the state shift is this lane's alone
             reinterpret_cast<float4*>(a.conv_state)[ch] = float4{cs.y, cs.z, cs.w, acc};
-            float co = cs.y * cw.x + cs.z * cw.y + cs.w * cw.z + acc * cw.w;
-            co = co * kr_sigmoid_poly5(co);
+            const float co = kr_conv4_silu(cs.y, cs.z, cs.w, acc, cw);
             if (kind == 2) a.v_out[dst] = co; else a.qk_out[dst] = co;
         }
     }
@@ -395,7 +392,7 @@ __global__ void __launch_bounds__(512) kr_fla_kernel(const float* p_qk, const fl
     float ssq = s_red[0], ssk = s_red[WQ];
 #pragma unroll
     for (int w = 1; w < WQ; w++) { ssq += s_red[w]; ssk += s_red[WQ + w]; }
-    const float inv_q = (ssq > 0.0f ? 1.0f / sqrtf(ssq) : 0.0f) * a.scale, inv_k = ssk > 0.0f ? 1.0f / sqrtf(ssk) : 0.0f;
+    const float inv_q = kr_l2_inv(ssq) * a.scale, inv_k = kr_l2_inv(ssk);
     float kk[RPS], qq[RPS];
 #pragma unroll
     for (int u = 0; u < RPS; u++) { kk[u] = s_qk[DK + slice * RPS + u] * inv_k; qq[u] = s_qk[slice * RPS + u] * inv_q; }
@@ -445,9 +442,7 @@ __global__ void __launch_bounds__(512) kr_fla_kernel(const float* p_qk, const fl
         float ss = s_red[0];
 #pragma unroll
         for (int w = 1; w < DV / 64; w++) ss += s_red[w];
-        const float rms = 1.0f / sqrtf(ss / (float)DV + a.eps);
-        const float normed = (ob * rms) * wn;
-        ov = (zz * kr_sigmoid_poly5(zz)) * normed;
+        ov = kr_gated_norm_out(ob, kr_rms_inv(ss, DV, a.eps), wn, zz);
         a.out[(size_t)vh * DV + t] = ov;
         s_vec[t] = ov;
     }
@@ -1085,8 +1080,8 @@ __global__ void __launch_bounds__(256) kr_fgqa_kernel(const KrStep* p_step, cons
     if (lane == 0) { s_red[0][wave] = sq; s_red[1][wave] = sk; }
     __syncthreads();
     float qx = qraw, kx = kraw;
-    if (a.q_norm) { const float ss = (s_red[0][0] + s_red[0][1]) + (s_red[0][2] + s_red[0][3]); qx = qraw * ((1.0f / sqrtf(ss / (float)HD + a.eps)) * qw); }
-    if (a.k_norm) { const float ss = (s_red[1][0] + s_red[1][1]) + (s_red[1][2] + s_red[1][3]); kx = kraw * ((1.0f / sqrtf(ss / (float)HD + a.eps)) * kw); }
+    if (a.q_norm) { const float ss = (s_red[0][0] + s_red[0][1]) + (s_red[0][2] + s_red[0][3]); qx = qraw * (kr_rms_inv(ss, HD, a.eps) * qw); }
+    if (a.k_norm) { const float ss = (s_red[1][0] + s_red[1][1]) + (s_red[1][2] + s_red[1][3]); kx = kraw * (kr_rms_inv(ss, HD, a.eps) * kw); }
     if (own) { s_q[t] = qx; s_k[t] = kx; }
     __syncthreads();
     float qv = qx, kv = kx;

@@ -8,6 +8,7 @@
 #include "kr_lds_optin.h"
 #include "kr_device.h"
 #include "kr_libm.h"
+#include "kr_exact_dev.h"
 #include "kr_decode_ops.h"
 #include <hip/hip_fp16.h>
 #include <cstdlib>
@@ -18,37 +19,6 @@ __device__ unsigned long long kr_dstamps[32];
 #else
 #define KR_DSTAMP(i) do { } while (0)
 #endif
-
-// hsum over 8 consecutive lanes in the order of the reference's hsum (lo+hi, movehdup, movehl)
-__device__ __forceinline__ float kr_hsum8(float v) {
-    v = v + __shfl_xor(v, 4);
-    v = v + __shfl_xor(v, 1);
-    v = v + __shfl_xor(v, 2);
-    return v;
-}
-
-// sum of squares of x[0..n) (n % 8 == 0) with 8 fma lanes; call with the first 8 lanes of a wave (others idle)
-__device__ __forceinline__ float kr_sumsq_chain8(const float* x, int n, int l) {
-    float acc = 0.0f;
-    const int nb = n / 8;
-    int b = 0;
-    for (; b + 32 <= nb; b += 32) {          // 32 LDS values in flight per lane, then the lane's fma chain
-        float v[32];
-#pragma unroll
-        for (int u = 0; u < 32; u++) v[u] = x[(b + u) * 8 + l];
-#pragma unroll
-        for (int u = 0; u < 32; u++) acc = __builtin_fmaf(v[u], v[u], acc);
-    }
-    for (; b + 8 <= nb; b += 8) {
-        float v[8];
-#pragma unroll
-        for (int u = 0; u < 8; u++) v[u] = x[(b + u) * 8 + l];
-#pragma unroll
-        for (int u = 0; u < 8; u++) acc = __builtin_fmaf(v[u], v[u], acc);
-    }
-    for (; b < nb; b++) { const float v = x[b * 8 + l]; acc = __builtin_fmaf(v, v, acc); }
-    return kr_hsum8(acc);
-}
 
 __global__ void kr_embed_kernel(const float* __restrict__ emb, const KrStep* __restrict__ st, float* __restrict__ hidden, int H) {
     const size_t base = (size_t)st->token * H;
@@ -167,10 +137,10 @@ __global__ void __launch_bounds__(KR_NORM_THREADS) kr_fused_add_rmsnorm_kernel(c
     __syncthreads();
     KR_DSTAMP(12);
     if (threadIdx.x < 8) {
-        float ss = tr ? kr_hsum8(kr_sumsq_lane_t(rt, ldt, n, threadIdx.x)) : kr_sumsq_chain8(r, n, threadIdx.x);
+        float ss = tr ? kr_hsum8(kr_sumsq_lane_t(rt, ldt, n, threadIdx.x)) : kr_sumsq8<32, 8>(r, n, threadIdx.x);
         if (threadIdx.x == 0) {
             for (int t = (n / 8) * 8; t < n; t++) ss += r[t] * r[t];
-            sm[n] = 1.0f / sqrtf(ss / (float)n + eps);
+            sm[n] = kr_rms_inv(ss, n, eps);
         }
     }
     KR_DSTAMP(13);
@@ -205,8 +175,7 @@ __global__ void __launch_bounds__(256) kr_la_conv_kernel(const KrLaArgs a) {
         const float* cw = a.conv_w + (size_t)ch * 4;
         const float s1 = cs[1], s2 = cs[2], s3 = cs[3];
         cs[0] = s1; cs[1] = s2; cs[2] = s3; cs[3] = s4;
-        float co = s1 * cw[0] + s2 * cw[1] + s3 * cw[2] + s4 * cw[3];
-        co = co * kr_sigmoid_poly5(co);  // fast_silu_avx2 (conv_dim % 8 == 0)
+        const float co = kr_conv4_silu(s1, s2, s3, s4, float4{cw[0], cw[1], cw[2], cw[3]});      // (conv_dim % 8 == 0)
         if (c < dk) qc[c] = co;
         else if (c < 2 * dk) kc[c - dk] = co;
         else a.v[(size_t)(ch - 2 * key_dim)] = co;
@@ -220,17 +189,15 @@ __global__ void __launch_bounds__(256) kr_la_conv_kernel(const KrLaArgs a) {
     if ((int)threadIdx.x < hr) {
         const int r = threadIdx.x, vh = kh * hr + r;
         const float b_raw = a.ba[kh * 2 * hr + r], a_p = a.ba[kh * 2 * hr + hr + r];
-        a.beta[vh] = 1.0f / (1.0f + kr_expf(-b_raw));
-        const float ap_dt = a_p + a.dt_bias[vh];
-        const float softplus = ap_dt > 20.0f ? ap_dt : kr_logf(1.0f + kr_expf(ap_dt));
-        a.g[vh] = -(kr_expf(a.a_log[vh])) * softplus;
+        a.beta[vh] = kr_la_beta(b_raw);
+        a.g[vh] = kr_la_g(a_p, a.dt_bias[vh], a.a_log[vh]);
     }
     __syncthreads();
     // L2 norms: lanes 0-7 -> q, lanes 8-15 -> k (decode.rs:3909-3945)
     if (threadIdx.x < 16) {
         const int which = threadIdx.x >> 3, l = threadIdx.x & 7;
-        const float ss = kr_sumsq_chain8(which ? kc : qc, dk, l);
-        if (l == 0) nrm[which] = ss > 0.0f ? 1.0f / sqrtf(ss) : 0.0f;
+        const float ss = kr_sumsq8<32, 8>(which ? kc : qc, dk, l);
+        if (l == 0) nrm[which] = kr_l2_inv(ss);
     }
     __syncthreads();
     const float inv_q = nrm[0] * a.scale, inv_k = nrm[1] * 1.0f;
@@ -281,12 +248,10 @@ __global__ void __launch_bounds__(256) kr_la_recurrent_gnorm_kernel(float* __res
     }
     r[j] = ob;
     __syncthreads();
-    if (j < 8) { const float ss = kr_sumsq_chain8(r, dv, j); if (j == 0) rms_s = 1.0f / sqrtf(ss / (float)dv + eps); }
+    if (j < 8) { const float ss = kr_sumsq8<32, 8>(r, dv, j); if (j == 0) rms_s = kr_rms_inv(ss, dv, eps); }
     __syncthreads();
     const size_t o = (size_t)h * dv + j;
-    const float normed = (ob * rms_s) * w[o];
-    const float zz = z[o];
-    const float ov = (zz * kr_sigmoid_poly5(zz)) * normed;
+    const float ov = kr_gated_norm_out(ob, rms_s, w[o], z[o]);
     out[o] = ov;
     if (img_out) {   // dv == 128: this head is exactly one quantization group of the out-projection's input
         __syncthreads();
@@ -358,13 +323,7 @@ __global__ void __launch_bounds__(256) kr_la_step_kernel(const KrLaArgs a, float
         if (t < DK) { qc[t] = pq; kc[t] = pk; }
         for (int i = t + nt; i < DK; i += nt) { qc[i] = a.q[(size_t)kh * 2 * DK + i]; kc[i] = a.q[(size_t)kh * 2 * DK + DK + i]; }      // DK > dv only
         vs[t] = pv;
-        if (t == 0) {      // gates, the arithmetic of the CONV form below
-            bt[0] = 1.0f / (1.0f + kr_expf(-pb));
-            const float ap_dt = pg + pdt;
-            const float softplus = ap_dt > 20.0f ? ap_dt : kr_logf(1.0f + kr_expf(ap_dt));
-            const float g = -(kr_expf(pal)) * softplus;
-            ge[0] = kr_expf(g);
-        }
+        if (t == 0) { float g; kr_la_gate(pb, pg, pdt, pal, bt[0], g); ge[0] = kr_expf(g); }
     }
     for (int c0 = t; CONV && c0 < nch; c0 += 2 * nt) {
         const int c1 = c0 + nt; const bool two = c1 < nch;
@@ -374,28 +333,23 @@ __global__ void __launch_bounds__(256) kr_la_step_kernel(const KrLaArgs a, float
         float4 s1 = s0, w1 = w0; float x1 = 0.0f;
         if (two) { s1 = *cs1; w1 = reinterpret_cast<const float4*>(a.conv_w)[ch1]; x1 = src[c1]; }
         *cs0 = float4{s0.y, s0.z, s0.w, x0};
-        float co = s0.y * w0.x + s0.z * w0.y + s0.w * w0.z + x0 * w0.w;
-        put(c0, co * kr_sigmoid_poly5(co));      // fast_silu_avx2 (conv_dim % 8 == 0)
+        put(c0, kr_conv4_silu(s0.y, s0.z, s0.w, x0, w0));      // (conv_dim % 8 == 0)
         if (two) {
             *cs1 = float4{s1.y, s1.z, s1.w, x1};
-            co = s1.y * w1.x + s1.z * w1.y + s1.w * w1.z + x1 * w1.w;
-            put(c1, co * kr_sigmoid_poly5(co));
+            put(c1, kr_conv4_silu(s1.y, s1.z, s1.w, x1, w1));
         }
     }
     if (CONV && t < hr) {   // gates (decode.rs:3891-3901)
         const int vg = kh * hr + t;
         const float b_raw = a.ba[kh * 2 * hr + t], a_p = a.ba[kh * 2 * hr + hr + t];
-        bt[t] = 1.0f / (1.0f + kr_expf(-b_raw));
-        const float ap_dt = a_p + a.dt_bias[vg];
-        const float softplus = ap_dt > 20.0f ? ap_dt : kr_logf(1.0f + kr_expf(ap_dt));
-        const float g = -(kr_expf(a.a_log[vg])) * softplus;
+        float g; kr_la_gate(b_raw, a_p, a.dt_bias[vg], a.a_log[vg], bt[t], g);
         ge[t] = kr_expf(g);
     }
     __syncthreads();
     if (t < 16) {   // L2 norms: lanes 0-7 -> q, lanes 8-15 -> k (decode.rs:3909-3945)
         const int which = t >> 3, l = t & 7;
-        const float ss = kr_sumsq_chain8(which ? kc : qc, DK, l);
-        if (l == 0) nrm[which] = ss > 0.0f ? 1.0f / sqrtf(ss) : 0.0f;
+        const float ss = kr_sumsq8<32, 8>(which ? kc : qc, DK, l);
+        if (l == 0) nrm[which] = kr_l2_inv(ss);
     }
     __syncthreads();
     {
@@ -459,10 +413,9 @@ __global__ void __launch_bounds__(256) kr_la_step_kernel(const KrLaArgs a, float
     }
     rr[t] = ob;
     __syncthreads();
-    if (t < 8 * hr) { const int hh = t >> 3, l = t & 7; const float ss = kr_sumsq_chain8(rr + hh * dv, dv, l); if (l == 0) rms[hh] = 1.0f / sqrtf(ss / (float)dv + eps); }
+    if (t < 8 * hr) { const int hh = t >> 3, l = t & 7; const float ss = kr_sumsq8<32, 8>(rr + hh * dv, dv, l); if (l == 0) rms[hh] = kr_rms_inv(ss, dv, eps); }
     __syncthreads();
-    const float normed = (ob * rms[r]) * wn;
-    const float ov = (zz * kr_sigmoid_poly5(zz)) * normed;
+    const float ov = kr_gated_norm_out(ob, rms[r], wn, zz);
     out[o] = ov;
     if (img_out) {   // dv == 128: each value head is exactly one quantization group of the out-projection's input
         __syncthreads();
@@ -493,13 +446,11 @@ __global__ void __launch_bounds__(256) kr_gated_rmsnorm_silu_kernel(const float*
     const int h = blockIdx.x, i = threadIdx.x;
     if (i < dv) r[i] = recur[(size_t)h * dv + i];
     __syncthreads();
-    if (i < 8) { const float ss = kr_sumsq_chain8(r, dv, i); if (i == 0) rms_s = 1.0f / sqrtf(ss / (float)dv + eps); }
+    if (i < 8) { const float ss = kr_sumsq8<32, 8>(r, dv, i); if (i == 0) rms_s = kr_rms_inv(ss, dv, eps); }
     __syncthreads();
     if (i < dv) {
         const size_t o = (size_t)h * dv + i;
-        const float normed = (r[i] * rms_s) * w[o];
-        const float zz = z[o];
-        out[o] = (zz * kr_sigmoid_poly5(zz)) * normed;
+        out[o] = kr_gated_norm_out(r[i], rms_s, w[o], z[o]);
     }
 }
 
@@ -523,7 +474,7 @@ __global__ void __launch_bounds__(256) kr_gqa_prep_kernel(const KrGqaArgs a) {
         if ((d & 63) == 0) part[d >> 6] = v;
         __syncthreads();
         const float ss = (part[0] + part[1]) + (part[2] + part[3]);
-        const float rms = 1.0f / sqrtf(ss / (float)hd + a.eps);
+        const float rms = kr_rms_inv(ss, hd, a.eps);
         const int per_head = is_q ? a.q_norm_per_head : a.k_norm_per_head;
         const float xv = d < hd ? x[d] * (rms * nw[(per_head ? h * hd : 0) + d]) : 0.0f;
         __syncthreads();
@@ -540,7 +491,7 @@ __global__ void __launch_bounds__(256) kr_gqa_prep_kernel(const KrGqaArgs a) {
                 for (int u = 0; u < 32; u++) ss += v[u];
             }
             for (; i < hd; i++) ss += x[i] * x[i];
-            rms_s = 1.0f / sqrtf(ss / (float)hd + a.eps);
+            rms_s = kr_rms_inv(ss, hd, a.eps);
         }
         __syncthreads();
         const int per_head = is_q ? a.q_norm_per_head : a.k_norm_per_head;
@@ -726,8 +677,7 @@ __global__ void __launch_bounds__(256) kr_gqa_attn_kernel(const KrGqaArgs a, int
         float* row = a.sc_g + (size_t)h * max_seq;
         float mx = -__builtin_inff();
         for (int s = t; s < seq; s += 256) mx = fmaxf(mx, row[s]);
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
+        mx = kr_wave_max(mx);
         if ((t & 63) == 0) red[t >> 6] = mx;
         __syncthreads();
         mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
@@ -836,8 +786,7 @@ __global__ void __launch_bounds__(256) kr_gqa_attn_kernel(const KrGqaArgs a, int
     __syncthreads();
     float mx = -__builtin_inff();
     for (int s = t; s < seq; s += 256) mx = fmaxf(mx, sc[s]);
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
+    mx = kr_wave_max(mx);
     if ((t & 63) == 0) red[t >> 6] = mx;
     __syncthreads();
     mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
@@ -1001,8 +950,7 @@ __global__ void __launch_bounds__(512) kr_gqa_pv_kernel(const KrGqaArgs a, int m
     float mx = -__builtin_inff();
     if (STREAM) { for (int s = t; s < seq; s += 512) mx = fmaxf(mx, row[s]); }
     else { for (int s = t; s < seq; s += 512) { const float v = row[s]; sc[s] = v; mx = fmaxf(mx, v); } }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
+    mx = kr_wave_max(mx);
     if ((t & 63) == 0) red[t >> 6] = mx;
     __syncthreads();
     mx = red[0];

@@ -5,6 +5,7 @@
 #pragma once
 #include "kr_device.h"
 #include "kr_libm.h"
+#include "kr_exact_dev.h"
 
 typedef _Float16 v8h __attribute__((ext_vector_type(8)));
 typedef float v16f __attribute__((ext_vector_type(16)));
@@ -206,11 +207,8 @@ __device__ __forceinline__ void kr_fd_merge2_body(int seq, int h, const float* f
     const int t = threadIdx.x, G = nh / nkv, kvh = h / G, g = h % G;
     const int nc = min((seq + chunk - 1) / chunk, 1024);
     const float* ml = fd_ml + (size_t)h * n_chunks * 2;
-    float mx = -__builtin_inff();
     const float mv = t < nc ? ml[t * 2] : -__builtin_inff(), lv = t < nc ? ml[t * 2 + 1] : 0.0f;      // nc <= 1024 = one chunk per thread
-    mx = mv;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
+    float mx = kr_wave_max(mv);
     if ((t & 63) == 0) red[t >> 6] = mx;
     __syncthreads();
     mx = red[0];

@@ -4,16 +4,13 @@
 #pragma once
 #include "kr_device.h"
 #include "kr_libm.h"
+#include "kr_exact_dev.h"
 #include "kr_gguf.h"
 #include <hip/hip_fp16.h>
 
 #define GG_BLOCK 256
 
 __device__ __forceinline__ float gg_f16(uint32_t bits16) { return __half2float(__ushort_as_half((uint16_t)bits16)); }
-__device__ __forceinline__ float gg_hsum8(float v) {
-    v = v + __shfl_xor(v, 4); v = v + __shfl_xor(v, 1); v = v + __shfl_xor(v, 2);
-    return v;
-}
 
 // ---- activation image: per 32-element sub-block s and AVX lane l an 8-byte record {AH4, AL4} of elements {2l,2l+1,16+2l,17+2l} ----
 struct GgAct { uint32_t* rec; float* scale; int* sum; float* f32v; };   // rec [K/32][8][2], scale/sum [K/32], f32v [K] (scalar path)
@@ -160,7 +157,7 @@ __device__ __forceinline__ float gg_tile_q4k(const GgMat& m, int tile, const GgA
             }
         }
     }
-    return gg_hsum8(acc) - corr;
+    return kr_hsum8(acc) - corr;
 }
 
 __device__ __forceinline__ float gg_tile_q8_0(const GgMat& m, int tile, const GgAct& A, int lane, int part = 0, int parts = 1) {
@@ -190,7 +187,7 @@ __device__ __forceinline__ float gg_tile_q8_0(const GgMat& m, int tile, const Gg
             }
         }
     }
-    return gg_hsum8(acc);
+    return kr_hsum8(acc);
 }
 
 __device__ __forceinline__ float gg_tile_q4_0(const GgMat& m, int tile, const GgAct& A, int lane, int part = 0, int parts = 1) {
@@ -218,7 +215,7 @@ __device__ __forceinline__ float gg_tile_q4_0(const GgMat& m, int tile, const Gg
             }
         }
     }
-    return gg_hsum8(acc) - corr;
+    return kr_hsum8(acc) - corr;
 }
 
 __device__ __forceinline__ bool gg_int_path(int t) { return t == GG_Q4_K || t == GG_Q8_0 || t == GG_Q4_0; }

@@ -6,7 +6,7 @@
 // image (the GgAct records of kr_gguf_dev.h), and a workgroup that owns one group of at most GGG_R rows of one expert and a span of 8-row output tiles.
 // A wave's lanes are 8 output rows x 8 AVX lanes as in gg_tile_*; a lane loads a block's record and header once and runs gg_pair_q4k / gg_sub_q8_0 (the
 // streaming tiles' own bodies) against each row's image staged in LDS: GGG_R independent (acc, corr) chains per lane, each with the order of blocks,
-// sub-blocks and lo / hi halves, the gg_hsum8 tree and the `- corr` of the decode step.  Rows never meet: a row's bits do not depend on its group.
+// sub-blocks and lo / hi halves, the kr_hsum8 tree and the `- corr` of the decode step.  Rows never meet: a row's bits do not depend on its group.
 //
 // Image of one row (global, stride ggg_image_stride(K)): rec [K/32][8 lanes]{AH4, AL4}, then scale f32 [K/32], then sum i32 [K/32] -- gg_carve's layout.
 // LDS stage: GGG_STAGE sub-blocks (= GG_PF Q4_K super-blocks, one request batch of the streaming tile) of GGG_R rows, 72 B per sub-block: 36 864 B.
@@ -182,7 +182,7 @@ __global__ void __launch_bounds__(GG_BLOCK) kr_ggg_kernel(const GggArgs a) {
 #pragma unroll
             for (int i = 0; i < GGG_R; i++) {
                 if (i < nr) {
-                    const float r = TYPE == GG_Q4_K ? gg_hsum8(acc[i]) - corr[i] : gg_hsum8(acc[i]);
+                    const float r = TYPE == GG_Q4_K ? kr_hsum8(acc[i]) - corr[i] : kr_hsum8(acc[i]);
                     if ((lane & 7) == 0 && orow < m.N) a.out[(size_t)(row0 + i) * a.out_ld + (second ? a.m0.N : 0) + orow] = r;
                 }
             }

@@ -25,6 +25,7 @@
 #include "kr_lds_optin.h"
 #include "kr_device.h"
 #include "kr_libm.h"
+#include "kr_exact_dev.h"
 #include "kr_prefill_ops.h"
 
 #ifdef KR_TIMING   // tools/probes/lac_timing.hip: wall-clock stamps (10 ns units) by thread 0 of workgroup (0, 0); no-op in the product build
@@ -40,14 +41,6 @@ typedef float f2 __attribute__((ext_vector_type(2)));
 // 1.1 us per 16 values on a lone wave -- more than the epilogue it sits in
 __device__ __forceinline__ float lc_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896340736f); }
 typedef __bf16 lc_b8 __attribute__((ext_vector_type(8)));
-// sum of squares of x[0..n) with 8 fma lanes (lane l owns elements 8 b + l, b ascending) folded by the reference's hsum tree: kr_pfm_sumsq8 of kr_prefill_ops.hip,
-// callable by ANY aligned group of 8 lanes (the fold uses xor shuffles inside the group)
-__device__ __forceinline__ float kr_lc_sumsq8(const float* x, int n, int l) {
-    float acc = 0.0f;
-    for (int b = 0; b < n / 8; b++) { const float v = x[b * 8 + l]; acc = __builtin_fmaf(v, v, acc); }
-    acc = acc + __shfl_xor(acc, 4); acc = acc + __shfl_xor(acc, 1); acc = acc + __shfl_xor(acc, 2);
-    return acc;
-}
 typedef uint32_t lc_u4 __attribute__((ext_vector_type(4)));
 typedef uint32_t lc_u2 __attribute__((ext_vector_type(2)));
 // x = hi + lo in bf16 (round to nearest even, v_cvt_pk_bf16_f32): the pair carries x to ~2^-17 relative
@@ -160,11 +153,8 @@ __global__ void __launch_bounds__(LC_PTH) kr_lac_prep_kernel(KrLacArgs a) {
                 const int t = 4 * tg + tt;
                 float4 co = float4{0.0f, 0.0f, 0.0f, 0.0f};
                 if (t < n) {
-                    co.x = x[tt].x * cw[0].x + x[tt + 1].x * cw[0].y + x[tt + 2].x * cw[0].z + x[tt + 3].x * cw[0].w;
-                    co.y = x[tt].y * cw[1].x + x[tt + 1].y * cw[1].y + x[tt + 2].y * cw[1].z + x[tt + 3].y * cw[1].w;
-                    co.z = x[tt].z * cw[2].x + x[tt + 1].z * cw[2].y + x[tt + 2].z * cw[2].z + x[tt + 3].z * cw[2].w;
-                    co.w = x[tt].w * cw[3].x + x[tt + 1].w * cw[3].y + x[tt + 2].w * cw[3].z + x[tt + 3].w * cw[3].w;
-                    co.x = co.x * kr_sigmoid_poly5(co.x); co.y = co.y * kr_sigmoid_poly5(co.y); co.z = co.z * kr_sigmoid_poly5(co.z); co.w = co.w * kr_sigmoid_poly5(co.w);
+                    co.x = kr_conv4_silu(x[tt].x, x[tt + 1].x, x[tt + 2].x, x[tt + 3].x, cw[0]); co.y = kr_conv4_silu(x[tt].y, x[tt + 1].y, x[tt + 2].y, x[tt + 3].y, cw[1]);
+                    co.z = kr_conv4_silu(x[tt].z, x[tt + 1].z, x[tt + 2].z, x[tt + 3].z, cw[2]); co.w = kr_conv4_silu(x[tt].w, x[tt + 1].w, x[tt + 2].w, x[tt + 3].w, cw[3]);
                 }
                 *reinterpret_cast<float4*>(T + t * LC_LD + c) = co;
             }
@@ -175,10 +165,8 @@ __global__ void __launch_bounds__(LC_PTH) kr_lac_prep_kernel(KrLacArgs a) {
             if (t < n) {
                 const float* ba = a.ba + (size_t)(c0 + t) * a.ld_ba;
                 const float b_raw = ba[kh * 2 * a.hr + rr], a_p = ba[kh * 2 * a.hr + a.hr + rr];
-                b = 1.0f / (1.0f + kr_expf(-b_raw));
-                const float ap_dt = a_p + a.dt_bias[h];
-                const float softplus = ap_dt > 20.0f ? ap_dt : kr_logf(1.0f + kr_expf(ap_dt));
-                const float ge = kr_expf(-(kr_expf(a.a_log[h])) * softplus);
+                b = kr_la_beta(b_raw);
+                const float ge = kr_expf(kr_la_g(a_p, a.dt_bias[h], a.a_log[h]));
                 g = fmaxf(logf(fmaxf(ge, 1e-37f)), -80.0f);
             }
 #pragma unroll
@@ -187,11 +175,11 @@ __global__ void __launch_bounds__(LC_PTH) kr_lac_prep_kernel(KrLacArgs a) {
             a.G[tile + t] = g;
         }
         __syncthreads();
-        // L2 norms of the 64 q rows and 64 k rows: 8 lanes per chain, the reference's order (kr_pfm_sumsq8); 128 chains on 512 threads in two rounds
+        // L2 norms of the 64 q rows and 64 k rows: 8 lanes per chain, the reference's order (kr_sumsq8, callable by any aligned group of 8 lanes); 128 chains on 512 threads in two rounds
         for (int u = tid; u < 2 * LC_T * 8; u += LC_PTH) {
             const int rowi = u >> 3, l = u & 7, t = rowi >> 1, which = rowi & 1;
-            const float ss = kr_lc_sumsq8((which ? Kt : Qt) + t * LC_LD, LC_D, l);
-            if (l == 0) nrm[t * 2 + which] = ss > 0.0f ? 1.0f / sqrtf(ss) : 0.0f;
+            const float ss = kr_sumsq8<0, 0>((which ? Kt : Qt) + t * LC_LD, LC_D, l);
+            if (l == 0) nrm[t * 2 + which] = kr_l2_inv(ss);
         }
         __syncthreads();
         for (int u = tid; u < LC_T * 32; u += LC_PTH) {

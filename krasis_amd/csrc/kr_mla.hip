@@ -77,8 +77,7 @@ __global__ void __launch_bounds__(512) kr_mla_attn_kernel(KrMlaArgs a) {
     __syncthreads();
     float mx = -__builtin_inff();
     for (int s = t; s < seq; s += 512) mx = fmaxf(mx, sc[s]);
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
+    mx = kr_wave_max(mx);
     if ((t & 63) == 0) red[t >> 6] = mx;
     __syncthreads();
     mx = red[0];
@@ -205,13 +204,14 @@ __global__ void __launch_bounds__(512) kr_mla_attn_staged_kernel(KrMlaArgs a, in
                 float acc = 0.0f;
 #pragma unroll
                 for (int u = 0; u < NQC; u++) acc = __builtin_fmaf(qc[u], kc[u], acc);
+                // (kr_mla_pair_hsum written out: the call moves this kernel's register count, docs/design/02-numerics.md)
                 float oth = __shfl_xor(acc, 8);
-                float v = kr_mla_hsum8(a2 == 0 ? acc + oth : oth + acc);
+                float v = kr_hsum8(a2 == 0 ? acc + oth : oth + acc);
                 acc = 0.0f;
 #pragma unroll
                 for (int u = 0; u < NQR; u++) acc = __builtin_fmaf(qr[u], kr[u], acc);
                 oth = __shfl_xor(acc, 8);
-                v += kr_mla_hsum8(a2 == 0 ? acc + oth : oth + acc);
+                v += kr_hsum8(a2 == 0 ? acc + oth : oth + acc);
                 v *= a.sm_scale;
                 if (c16 == 0) sc[s0 + r] = v;
             }
@@ -222,8 +222,7 @@ __global__ void __launch_bounds__(512) kr_mla_attn_staged_kernel(KrMlaArgs a, in
     KR_MSTAMP(4);
     float mx = -__builtin_inff();
     for (int s = t; s < seq; s += 512) mx = fmaxf(mx, sc[s]);
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
+    mx = kr_wave_max(mx);
     if ((t & 63) == 0) red[t >> 6] = mx;
     __syncthreads();
     mx = red[0];
@@ -316,13 +315,11 @@ __global__ void __launch_bounds__(512) kr_mla_scores_kernel(KrMlaArgs a, int max
         float acc = 0.0f;
 #pragma unroll
         for (int u = 0; u < NQC; u++) acc = __builtin_fmaf(qc[u], kc[u], acc);
-        float oth = __shfl_xor(acc, 8);
-        float v = kr_mla_hsum8(a2 == 0 ? acc + oth : oth + acc);
+        float v = kr_mla_pair_hsum(acc, a2);
         acc = 0.0f;
 #pragma unroll
         for (int u = 0; u < NQR; u++) acc = __builtin_fmaf(qr[u], kr[u], acc);
-        oth = __shfl_xor(acc, 8);
-        v += kr_mla_hsum8(a2 == 0 ? acc + oth : oth + acc);
+        v += kr_mla_pair_hsum(acc, a2);
         v *= a.sm_scale;
         if (c16 == 0) out[r] = v;
     }
@@ -384,7 +381,7 @@ __global__ void __launch_bounds__(256) kr_mla_prep_fast_kernel(KrMlaArgs a) {
     for (int o = 32; o >= 1; o >>= 1) ss += __shfl_xor(ss, o);
     if (lane == 0) sh[0][wave] = ss;
     __syncthreads();
-    const float rms = 1.0f / sqrtf(((sh[0][0] + sh[0][1]) + (sh[0][2] + sh[0][3])) / (float)a.klr + a.eps);
+    const float rms = kr_rms_inv((sh[0][0] + sh[0][1]) + (sh[0][2] + sh[0][3]), a.klr, a.eps);
     for (int i = t; i < a.klr; i += 256) {
         const float v = xs[i] * (rms * a.kv_a_norm[i]);
         if (a.kv_fp8) kr_mla_st<true>(a.ckv_cache, (size_t)pos * a.klr + i, v); else kr_mla_st<false>(a.ckv_cache, (size_t)pos * a.klr + i, v);
@@ -438,7 +435,7 @@ __global__ void __launch_bounds__(256) kr_rmsnorm_seq_kernel(float* __restrict__
             for (int u = 0; u < 8; u++) ss += v[u];
         }
         for (; i < n; i++) ss += lds[i] * lds[i];
-        lds[n] = 1.0f / sqrtf(ss / (float)n + eps);
+        lds[n] = kr_rms_inv(ss, n, eps);
     }
     __syncthreads();
     const float rms = lds[n];
@@ -524,8 +521,7 @@ __global__ void __launch_bounds__(NBC * 8 / KR_MPV_EPT + 256) kr_mla_pv_kernel(K
     // ---- softmax over the streamed score row
     float mx = -__builtin_inff();
     for (int s2 = t; s2 < seq; s2 += NT) mx = fmaxf(mx, row[s2]);
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
+    mx = kr_wave_max(mx);
     if ((t & 63) == 0) red[t >> 6] = mx;
     __syncthreads();
     mx = red[0];

@@ -3,14 +3,9 @@
 // rope of q_pe, latent RMSNorm + rope of k_pe + cache append).  One definition, so every caller carries the same operations in the same order.
 #pragma once
 #include "kr_device.h"
+#include "kr_exact_dev.h"
 #include <hip/hip_fp16.h>
 
-__device__ __forceinline__ float kr_mla_hsum8(float v) {   // lo+hi, movehdup, movehl (same tree as every hsum in decode.rs)
-    v = v + __shfl_xor(v, 4);
-    v = v + __shfl_xor(v, 1);
-    v = v + __shfl_xor(v, 2);
-    return v;
-}
 __device__ __forceinline__ float kr_h2f(uint16_t h) { return __half2float(__ushort_as_half(h)); }
 // cache element i of a row / of the whole cache: FP16 (reference CPU decode) or E4M3 (the GPU cache dtype, extended to the latent cache)
 template <bool FP8> __device__ __forceinline__ float kr_mla_ld(const void* base, size_t i) {
@@ -27,6 +22,12 @@ template <bool FP8> __device__ __forceinline__ void kr_mla_st(void* base, size_t
     else reinterpret_cast<uint16_t*>(base)[i] = __half_as_ushort(__float2half_rn(v));
 }
 
+// end of a two-accumulator dot product on 16 lanes: lane (a, l) holds AVX lane l of accumulator a; _mm256_add_ps(acc0, acc1) with acc0 as the left
+// operand on both halves, then the hsum.  Every lane of the 16 returns the result.
+__device__ __forceinline__ float kr_mla_pair_hsum(float acc, int a) {
+    const float other = __shfl_xor(acc, 8);
+    return kr_hsum8(a == 0 ? acc + other : other + acc);
+}
 // 16 cooperating lanes (c = lane & 15) evaluate mla_attn_dot_fp16_avx2 / the w_vc row dot: chain (a = c >> 3, l = c & 7) owns the
 // 8-blocks i with i % 2 == a (an odd trailing block goes to accumulator 0), ascending.  Every lane of the 16 returns the result.
 template <typename LoadB>
@@ -35,9 +36,7 @@ __device__ __forceinline__ float kr_dot2acc(const float* q, LoadB loadb, int dim
     float acc = 0.0f;
     for (int i = a; i < paired; i += 2) acc = __builtin_fmaf(q[i * 8 + l], loadb(i * 8 + l), acc);
     if ((n8 & 1) && a == 0) acc = __builtin_fmaf(q[(n8 - 1) * 8 + l], loadb((n8 - 1) * 8 + l), acc);
-    const float other = __shfl_xor(acc, 8);
-    const float s8 = a == 0 ? acc + other : other + acc;   // _mm256_add_ps(acc0, acc1)
-    return kr_mla_hsum8(s8);
+    return kr_mla_pair_hsum(acc, a);
 }
 
 // ---- the sections of the prep launch, each for a workgroup of 64 threads (t = threadIdx.x) ---------------------------------------------
@@ -90,7 +89,7 @@ __device__ __forceinline__ void kr_mla_append_row(const float* kv_out, const flo
             for (int u = 0; u < 8; u++) ss += v[u];
         }
         for (; i < klr; i++) ss += x[i] * x[i];
-        sh[639] = 1.0f / sqrtf(ss / (float)klr + eps);
+        sh[639] = kr_rms_inv(ss, klr, eps);
     }
     __syncthreads();
     const float rms = sh[639];

@@ -18,6 +18,7 @@
 #include "kr_kernels.h"
 #include "kr_matvec_dev.h"
 #include "kr_libm.h"
+#include "kr_exact_dev.h"
 #include <cstdio>
 
 #define KR_BLOCK 256
@@ -600,8 +601,7 @@ __global__ void __launch_bounds__(KR_BLOCK) kr_matvec_coop_kernel(const T* x, in
             if (LA && la_kind >= 0) {      // (tpb == 1: t == 0, this is wave 0 and `col` the row the operands above were requested for)
                 if (la_kind <= 1) {        // depthwise conv1d (kernel 4) over the shifted state, SiLU (fast_silu_avx2); the state shift is this lane's alone
                     reinterpret_cast<float4*>(la.conv_state)[la_ch] = float4{la_cs.y, la_cs.z, la_cs.w, acc};
-                    float co = la_cs.y * la_cw.x + la_cs.z * la_cw.y + la_cs.w * la_cw.z + acc * la_cw.w;
-                    co = co * kr_sigmoid_poly5(co);
+                    const float co = kr_conv4_silu(la_cs.y, la_cs.z, la_cs.w, acc, la_cw);
                     if (la_kind == 0) la.qk_out[la_dst] = co; else la.v_out[la_dst] = co;
                 } else la.z_out[la_dst] = acc;
             } else if (col < m.N) mm.y[mi][col] = acc;

@@ -4,25 +4,12 @@
 // same order, so each row's results carry the bits kr_decode_step gives on that sequence alone.
 #include "kr_device.h"
 #include "kr_libm.h"
+#include "kr_exact_dev.h"
 #include "kr_multi.h"
 #include "kr_mla_dev.h"
 #include "kr_decode_ops.h"
 #include "kr_router.h"
 #include "kr_sample_dev.h"
-
-// hsum over 8 consecutive lanes in the order of the reference's hsum (kr_decode_ops.hip kr_hsum8)
-__device__ __forceinline__ float kr_m_hsum8(float v) {
-    v = v + __shfl_xor(v, 4);
-    v = v + __shfl_xor(v, 1);
-    v = v + __shfl_xor(v, 2);
-    return v;
-}
-// sum of squares of x[0..n) (n % 8 == 0): lane l < 8 chains fma over elements b * 8 + l, ascending b, then hsum8 (kr_sumsq_chain8)
-__device__ __forceinline__ float kr_m_sumsq8(const float* x, int n, int l) {
-    float acc = 0.0f;
-    for (int b = 0; b < n / 8; b++) { const float v = x[b * 8 + l]; acc = __builtin_fmaf(v, v, acc); }
-    return kr_m_hsum8(acc);
-}
 
 // ---- linear attention ----------------------------------------------------------------------------------------------------------------------------
 // Run i of a pass is `cnt` consecutive tokens of one slot: runs[3 i] = the slot, runs[3 i + 1] = off, runs[3 i + 2] = cnt.  Its tokens sit, in order, in
@@ -52,8 +39,7 @@ __global__ void __launch_bounds__(256) kr_multi_la_conv_kernel(const KrMultiLaAr
     for (int t = 0; t < cnt; t++) {
         const int b = kr_m_run_row(i, row0, cnt, t);
         const float x = xin[(size_t)b * a.ld_qkvz];
-        const float co = s.y * w.x + s.z * w.y + s.w * w.z + x * w.w;
-        a.conv_out[(size_t)b * conv_dim + ch] = co * kr_sigmoid_poly5(co);      // fast_silu_avx2
+        a.conv_out[(size_t)b * conv_dim + ch] = kr_conv4_silu(s.y, s.z, s.w, x, w);
         if constexpr (VERIFY) a.rec_x[(size_t)b * conv_dim + ch] = x;
         s = float4{s.y, s.z, s.w, x};
     }
@@ -79,10 +65,7 @@ __global__ void __launch_bounds__(256) kr_multi_la_recur_kernel(const KrMultiLaA
     for (int t = j; t < cnt; t += dv) {      // gates (decode.rs:3891-3901)
         const float* ba = a.ba + (size_t)kr_m_run_row(ri, row0, cnt, t) * a.ld_ba;
         const float b_raw = ba[kh * 2 * hr + r], a_p = ba[kh * 2 * hr + hr + r];
-        be[t] = 1.0f / (1.0f + kr_expf(-b_raw));
-        const float ap_dt = a_p + a.dt_bias[h];
-        const float softplus = ap_dt > 20.0f ? ap_dt : kr_logf(1.0f + kr_expf(ap_dt));
-        const float g = -(kr_expf(a.a_log[h])) * softplus;
+        float g; kr_la_gate(b_raw, a_p, a.dt_bias[h], a.a_log[h], be[t], g);
         ge[t] = kr_expf(g);
     }
     const __amdgpu_buffer_rsrc_t srd = __builtin_amdgcn_make_buffer_rsrc(a.recur + (size_t)slot * a.recur_stride + (size_t)h * DK * dv, 0, DK * dv * 4, 0x00020000);
@@ -101,8 +84,8 @@ __global__ void __launch_bounds__(256) kr_multi_la_recur_kernel(const KrMultiLaA
         __syncthreads();      // (first token: also the gate rows)
         if (j < 16) {      // L2 norms: lanes 0-7 -> q, lanes 8-15 -> k (decode.rs:3909-3945)
             const int which = j >> 3, l = j & 7;
-            const float ss = kr_m_sumsq8(which ? kc : qc, DK, l);
-            if (l == 0) nrm[which] = ss > 0.0f ? 1.0f / sqrtf(ss) : 0.0f;
+            const float ss = kr_sumsq8<0, 0>(which ? kc : qc, DK, l);
+            if (l == 0) nrm[which] = kr_l2_inv(ss);
         }
         __syncthreads();
         {
@@ -150,10 +133,9 @@ __global__ void __launch_bounds__(256) kr_multi_la_recur_kernel(const KrMultiLaA
         }
         rr[j] = ob;
         __syncthreads();
-        if (j < 8) { const float ss = kr_m_sumsq8(rr, dv, j); if (j == 0) rms_s = 1.0f / sqrtf(ss / (float)dv + a.eps); }
+        if (j < 8) { const float ss = kr_sumsq8<0, 0>(rr, dv, j); if (j == 0) rms_s = kr_rms_inv(ss, dv, a.eps); }
         __syncthreads();
-        const float normed = (ob * rms_s) * wn;
-        a.out[(size_t)b * a.ld_out + (size_t)h * dv + j] = (zz * kr_sigmoid_poly5(zz)) * normed;
+        a.out[(size_t)b * a.ld_out + (size_t)h * dv + j] = kr_gated_norm_out(ob, rms_s, wn, zz);
     }
     if constexpr (!VERIFY) {
 #pragma unroll
@@ -234,6 +216,32 @@ int kr_launch_multi_la(const KrMultiLaArgs& a, const int* runs, int n_runs, int 
     return 0;
 }
 
+// ---- softmax of one score row by one wave (decode.rs:4245-4254) -----------------------------------------------------------------------------------
+// rowp[0, seq) in place: the maximum, libm exp of (score - max), the sum of the exponentials in position order -- by lane 0 over LDS tiles of
+// KR_MG_TILE floats (tw: this wave's tile; zero padding to a multiple of 32 leaves a sum of exponentials unchanged) -- and the scale by its reciprocal.
+// It contains workgroup barriers: EVERY thread of the workgroup calls it, the same number of times; a wave without a row passes on = false (and any
+// valid row pointer) and only keeps the barriers.
+#define KR_MG_TILE 1024      // softmax-sum tile per wave (floats)
+__device__ __forceinline__ void kr_m_wave_softmax(float* rowp, int seq, float* tw, bool on, int lane) {
+    const int seq32 = (seq + 31) & ~31;
+    float mx = -__builtin_inff();
+    if (on) for (int s = lane; s < seq; s += 64) mx = fmaxf(mx, rowp[s]);
+    mx = kr_wave_max(mx);
+    if (on) for (int s = lane; s < seq; s += 64) rowp[s] = kr_expf(rowp[s] - mx);
+    __syncthreads();
+    float se = 0.0f;
+    for (int s0 = 0; s0 < seq32; s0 += KR_MG_TILE) {
+        const int n = min(KR_MG_TILE, seq32 - s0);
+        if (on) for (int i = lane; i < n; i += 64) tw[i] = s0 + i < seq ? rowp[s0 + i] : 0.0f;
+        __syncthreads();
+        if (on && lane == 0) se = kr_seq_sum(tw, n, se);
+        __syncthreads();
+    }
+    se = __shfl(se, 0);
+    const float inv = 1.0f / se;
+    if (on) for (int s = lane; s < seq; s += 64) rowp[s] *= inv;
+}
+
 // ---- GQA -----------------------------------------------------------------------------------------------------------------------------------------
 // decode.rs:2873-2966 per row: gated split, per-head RMS norm (scalar sequential sum), half-split RoPE at the row's position, K / V into the row's
 // slot.  grid (nh + nkv, B), 256 threads (hd <= 256).  The exact branch of kr_gqa_prep_kernel.
@@ -256,7 +264,7 @@ __global__ void __launch_bounds__(256) kr_multi_gqa_prep_kernel(const KrMultiGqa
         if (d == 0) {
             float ss = 0.0f;
             for (int i = 0; i < hd; i++) ss += x[i] * x[i];
-            rms_s = 1.0f / sqrtf(ss / (float)hd + a.eps);
+            rms_s = kr_rms_inv(ss, hd, a.eps);
         }
         __syncthreads();
         const int per_head = is_q ? a.q_norm_per_head : a.k_norm_per_head;
@@ -286,10 +294,8 @@ __global__ void __launch_bounds__(256) kr_multi_gqa_prep_kernel(const KrMultiGqa
 
 // decode.rs:4194 per row: the G = nh / nkv query heads of KV head kvh over the slot's rows [0, pos].  grid (nkv, B), 256 threads; every K and V row
 // of the sequence is read once for the G heads.  Scores: 8 lanes per position, lane l chains fma over elements e * 8 + l (ascending e) and the
-// 8-lane hsum -- one K row in registers serves all G heads.  Softmax: one wave per head (rounds of 4 heads): max, libm exp in place, the
-// position-ordered sum over LDS tiles by one lane (zero padding to a multiple of 32 leaves a sum of exponentials unchanged), the scale by the
-// reciprocal.  P.V: thread t owns output d = t % hd of heads t / hd, t / hd + 256 / hd, ..: one fma per position, ascending.
-#define KR_MG_TILE 1024      // softmax-sum tile per wave (floats)
+// 8-lane hsum -- one K row in registers serves all G heads.  Softmax: one wave per head (rounds of 4 heads), kr_m_wave_softmax.
+// P.V: thread t owns output d = t % hd of heads t / hd, t / hd + 256 / hd, ..: one fma per position, ascending.
 #define KR_MG_PT 64          // positions per P.V stage
 #define KR_MG_ACC 16         // heads per thread and pass of the P.V loop
 // PAGED: the slot's table slice for [0, seq) is loaded into LDS once, and position s is row (page << shift) | (s & mask) of the pools; the loops and their
@@ -332,36 +338,18 @@ __global__ void __launch_bounds__(256) kr_multi_gqa_attn_kernel(const KrMultiGqa
                 float acc = 0.0f;
 #pragma unroll
                 for (int e = 0; e < NB; e++) acc = __builtin_fmaf(qs[g * HD + e * 8 + l], kr[e], acc);
-                acc = kr_m_hsum8(acc);
+                acc = kr_hsum8(acc);
                 if (l == 0) sc[(size_t)g * a.sc_ld + s] = acc * a.sm_scale;
             }
         }
     }
     __syncthreads();
     // ---- softmax, one wave per head
-    const int seq32 = (seq + 31) & ~31;
     float* tw = tile + w * KR_MG_TILE;
     for (int g0 = 0; g0 < G; g0 += 4) {
         const int g = g0 + w;
         const bool on = g < G;
-        float* rowp = sc + (size_t)(on ? g : 0) * a.sc_ld;
-        float mx = -__builtin_inff();
-        if (on) for (int s = lane; s < seq; s += 64) mx = fmaxf(mx, rowp[s]);
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
-        if (on) for (int s = lane; s < seq; s += 64) rowp[s] = kr_expf(rowp[s] - mx);
-        __syncthreads();
-        float se = 0.0f;
-        for (int s0 = 0; s0 < seq32; s0 += KR_MG_TILE) {
-            const int n = min(KR_MG_TILE, seq32 - s0);
-            if (on) for (int i = lane; i < n; i += 64) tw[i] = s0 + i < seq ? rowp[s0 + i] : 0.0f;
-            __syncthreads();
-            if (on && lane == 0) se = kr_seq_sum(tw, n, se);
-            __syncthreads();
-        }
-        se = __shfl(se, 0);
-        const float inv = 1.0f / se;
-        if (on) for (int s = lane; s < seq; s += 64) rowp[s] *= inv;
+        kr_m_wave_softmax(sc + (size_t)(on ? g : 0) * a.sc_ld, seq, tw, on, lane);
     }
     __syncthreads();
     // ---- P.V
@@ -464,7 +452,7 @@ __global__ void __launch_bounds__(64) kr_multi_mla_prep_kernel(const KrMultiMlaA
 // past it read as zero), committed to LDS while the next stage's loads are in flight, and serve all heads of the group.
 //   scores: 16 lanes per (position, head) pair -- kr_dot2acc over klr + kr_dot2acc over rd, x sm_scale (the query slice stays in registers) -- into the
 //           row's global score rows, so the form (and its bits) does not depend on the slot capacity
-//   softmax: one wave per head: max, libm exp in place, the position-ordered sum over LDS tiles by one lane, x 1 / sum (kr_multi_gqa_attn_kernel's)
+//   softmax: one wave per head (kr_m_wave_softmax)
 //   weighted sum: the rows staged again; thread t owns latent element t % klr of heads t / klr + k * (512 / klr): one fma per position, ascending
 #define KR_MM_ROWS 32
 #define KR_MM_HG 4
@@ -567,13 +555,11 @@ __global__ void __launch_bounds__(512) kr_multi_mla_attn_kernel(const KrMultiMla
                 float acc = 0.0f;
 #pragma unroll
                 for (int u = 0; u < NQC; u++) acc = __builtin_fmaf(qc[u], kc[u], acc);
-                float oth = __shfl_xor(acc, 8);
-                float v = kr_mla_hsum8(a2 == 0 ? acc + oth : oth + acc);
+                float v = kr_mla_pair_hsum(acc, a2);
                 acc = 0.0f;
 #pragma unroll
                 for (int u = 0; u < NQR; u++) acc = __builtin_fmaf(qr[u], kr[u], acc);
-                oth = __shfl_xor(acc, 8);
-                v += kr_mla_hsum8(a2 == 0 ? acc + oth : oth + acc);
+                v += kr_mla_pair_hsum(acc, a2);
                 v *= a.sm_scale;
                 if (c16 == 0) out[s0 + r] = v;
             }
@@ -583,27 +569,8 @@ __global__ void __launch_bounds__(512) kr_multi_mla_attn_kernel(const KrMultiMla
     __syncthreads();
     // ---- softmax: wave w < nhg takes head hg0 + w
     {
-        const int seq32 = (seq + 31) & ~31;
         const bool on = w < nhg;
-        float* rowp = sc + (size_t)(on ? w : 0) * a.sc_ld;
-        float* tw = tile + (w & 3) * KR_MG_TILE;
-        float mx = -__builtin_inff();
-        if (on) for (int s = lane; s < seq; s += 64) mx = fmaxf(mx, rowp[s]);
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
-        if (on) for (int s = lane; s < seq; s += 64) rowp[s] = kr_expf(rowp[s] - mx);
-        __syncthreads();
-        float se = 0.0f;
-        for (int s0 = 0; s0 < seq32; s0 += KR_MG_TILE) {
-            const int n = min(KR_MG_TILE, seq32 - s0);
-            if (on) for (int i = lane; i < n; i += 64) tw[i] = s0 + i < seq ? rowp[s0 + i] : 0.0f;      // zero padding leaves a sum of exponentials unchanged
-            __syncthreads();
-            if (on && lane == 0) se = kr_seq_sum(tw, n, se);
-            __syncthreads();
-        }
-        se = __shfl(se, 0);
-        const float inv = 1.0f / se;
-        if (on) for (int s = lane; s < seq; s += 64) rowp[s] *= inv;
+        kr_m_wave_softmax(sc + (size_t)(on ? w : 0) * a.sc_ld, seq, tile + (w & 3) * KR_MG_TILE, on, lane);
     }
     // ---- weighted sum
     constexpr int TPH = 512 / klr, KH = HG / TPH;    // threads per latent element; heads per thread: hq + k * TPH

@@ -8,26 +8,11 @@
 #include "kr_lds_optin.h"
 #include "kr_device.h"
 #include "kr_libm.h"
+#include "kr_exact_dev.h"
 #include "kr_prefill_ops.h"
 #include "kr_pfh_dev.h"
 #include <hip/hip_fp16.h>
 #include <stdlib.h>
-
-__device__ __forceinline__ float kr_pfm_hsum8(float v) { v = v + __shfl_xor(v, 4); v = v + __shfl_xor(v, 1); v = v + __shfl_xor(v, 2); return v; }
-
-// sum of squares of x[0..n) with 8 fma lanes (lane l owns elements 8b + l, b ascending), call with lanes 0..7 of a wave
-__device__ __forceinline__ float kr_pfm_sumsq8(const float* x, int n, int l) {
-    float acc = 0.0f; const int nb = n / 8; int b = 0;
-    for (; b + 8 <= nb; b += 8) {
-        float v[8];
-#pragma unroll
-        for (int u = 0; u < 8; u++) v[u] = x[(b + u) * 8 + l];
-#pragma unroll
-        for (int u = 0; u < 8; u++) acc = __builtin_fmaf(v[u], v[u], acc);
-    }
-    for (; b < nb; b++) { const float v = x[b * 8 + l]; acc = __builtin_fmaf(v, v, acc); }
-    return kr_pfm_hsum8(acc);
-}
 
 __device__ __forceinline__ void kr_pfm_store_digits(int8_t* hi, int8_t* lo, const int (&q)[8]) {
     u32x2 h, l;
@@ -64,8 +49,8 @@ __global__ void __launch_bounds__(256) kr_pfm_norm_kernel(const KrPfmNormArgs a)
     for (int i = tid; i < H; i += 256) { const float v = a.first ? add[i] : (add[i] + res[i]); r[i] = v; res[i] = v; }
     __syncthreads();
     if (tid < 8) {
-        float ss = kr_pfm_sumsq8(r, H, tid);
-        if (tid == 0) { for (int q = (H / 8) * 8; q < H; q++) ss += r[q] * r[q]; r[H] = 1.0f / sqrtf(ss / (float)H + a.eps); }
+        float ss = kr_sumsq8<8, 0>(r, H, tid);
+        if (tid == 0) { for (int q = (H / 8) * 8; q < H; q++) ss += r[q] * r[q]; r[H] = kr_rms_inv(ss, H, a.eps); }
     }
     __syncthreads();
     const float rms = r[H];
@@ -150,12 +135,8 @@ __global__ void __launch_bounds__(256) kr_pfm_la_conv_kernel(const KrPfmLaArgs a
 #pragma unroll
         for (int tt = 0; tt < PFC_TT; tt++)
             if (tt < nt) {
-                float4 co;
-                co.x = x[tt].x * cw[0].x + x[tt + 1].x * cw[0].y + x[tt + 2].x * cw[0].z + x[tt + 3].x * cw[0].w;
-                co.y = x[tt].y * cw[1].x + x[tt + 1].y * cw[1].y + x[tt + 2].y * cw[1].z + x[tt + 3].y * cw[1].w;
-                co.z = x[tt].z * cw[2].x + x[tt + 1].z * cw[2].y + x[tt + 2].z * cw[2].z + x[tt + 3].z * cw[2].w;
-                co.w = x[tt].w * cw[3].x + x[tt + 1].w * cw[3].y + x[tt + 2].w * cw[3].z + x[tt + 3].w * cw[3].w;
-                co.x = co.x * kr_sigmoid_poly5(co.x); co.y = co.y * kr_sigmoid_poly5(co.y); co.z = co.z * kr_sigmoid_poly5(co.z); co.w = co.w * kr_sigmoid_poly5(co.w);
+                const float4 co = float4{kr_conv4_silu(x[tt].x, x[tt + 1].x, x[tt + 2].x, x[tt + 3].x, cw[0]), kr_conv4_silu(x[tt].y, x[tt + 1].y, x[tt + 2].y, x[tt + 3].y, cw[1]),
+                                         kr_conv4_silu(x[tt].z, x[tt + 1].z, x[tt + 2].z, x[tt + 3].z, cw[2]), kr_conv4_silu(x[tt].w, x[tt + 1].w, x[tt + 2].w, x[tt + 3].w, cw[3])};
                 const int wt = half * PFC_TT + tt;
                 if (c < dk) *reinterpret_cast<float4*>(qc + wt * dk + c) = co;
                 else if (c < 2 * dk) *reinterpret_cast<float4*>(kc + wt * dk + (c - dk)) = co;
@@ -171,18 +152,15 @@ __global__ void __launch_bounds__(256) kr_pfm_la_conv_kernel(const KrPfmLaArgs a
         const int tt = gi / hr, r = gi % hr, vh = kh * hr + r, t = w0 + tt;
         const float* ba = a.ba + (size_t)t * a.ld_ba;
         const float b_raw = ba[kh * 2 * hr + r], a_p = ba[kh * 2 * hr + hr + r];
-        a.beta[(size_t)t * a.nv + vh] = 1.0f / (1.0f + kr_expf(-b_raw));
-        const float ap_dt = a_p + a.dt_bias[vh];
-        const float softplus = ap_dt > 20.0f ? ap_dt : kr_logf(1.0f + kr_expf(ap_dt));
-        const float g = -(kr_expf(a.a_log[vh])) * softplus;
+        float g; kr_la_gate(b_raw, a_p, a.dt_bias[vh], a.a_log[vh], a.beta[(size_t)t * a.nv + vh], g);
         a.gexp[(size_t)t * a.nv + vh] = kr_expf(g);   // decode.rs:1293 decays the state by exp(g)
     }
     __syncthreads();
     if (threadIdx.x < 16 * PFC_WT) {            // 8 lanes per (token, q | k) chain
         const int tt = threadIdx.x >> 4, which = (threadIdx.x >> 3) & 1, l = threadIdx.x & 7;
         if (tt < nw) {
-            const float ss = kr_pfm_sumsq8((which ? kc : qc) + tt * dk, dk, l);
-            if (l == 0) nrm[tt * 2 + which] = ss > 0.0f ? 1.0f / sqrtf(ss) : 0.0f;
+            const float ss = kr_sumsq8<8, 0>((which ? kc : qc) + tt * dk, dk, l);
+            if (l == 0) nrm[tt * 2 + which] = kr_l2_inv(ss);
         }
     }
     __syncthreads();
@@ -321,7 +299,7 @@ __global__ void __launch_bounds__(256) kr_pfm_la_recur_kernel(float* __restrict_
 
 // ---- gated RMSNorm + SiLU gate per (token, head) (decode.rs:3979) ----------------------------------------------------------------
 // grid (nv, ceil(C / 8)), 256 threads: a WAVE takes one (token, head) row at a time (two rows per wave: 8 tokens per workgroup), the row in a wave-private LDS slice,
-// the sum of squares as the reference's 8-lane chain + hsum (kr_pfm_sumsq8) on lanes 0..7, no workgroup barrier.  (Rounds 1-5: one workgroup of dv threads per
+// the sum of squares as the reference's 8-lane chain + hsum (kr_sumsq8) on lanes 0..7, no workgroup barrier.  (Rounds 1-5: one workgroup of dv threads per
 // (token, head) -- 262 144 workgroups of two waves for an 8192-token chunk, 140 us against ~80 us of traffic.)  z may sit inside the in-projection's output
 // (z_ld = its row stride, z_head = floats between the z blocks of consecutive value heads): the stand-alone copy of z is then never made.
 #define PFG_TT 8
@@ -342,13 +320,13 @@ __global__ void __launch_bounds__(256) kr_pfm_gated_norm_kernel(const float* __r
         float4 v = float4{0.0f, 0.0f, 0.0f, 0.0f}, zz = v;
         if (act) { v = *reinterpret_cast<const float4*>(recur + o + 4 * lane); zz = *reinterpret_cast<const float4*>(z + (size_t)t * z_ld + zoff + 4 * lane); *reinterpret_cast<float4*>(r + 4 * lane) = v; }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup"); __builtin_amdgcn_wave_barrier();
-        if (lane < 8) { const float ss = kr_pfm_sumsq8(r, dv, lane); if (lane == 0) r[256] = 1.0f / sqrtf(ss / (float)dv + eps); }
+        if (lane < 8) { const float ss = kr_sumsq8<8, 0>(r, dv, lane); if (lane == 0) r[256] = kr_rms_inv(ss, dv, eps); }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup"); __builtin_amdgcn_wave_barrier();
         const float rms = r[256];
         if (act) {
             float4 ov;
-            ov.x = (zz.x * kr_sigmoid_poly5(zz.x)) * ((v.x * rms) * wv.x); ov.y = (zz.y * kr_sigmoid_poly5(zz.y)) * ((v.y * rms) * wv.y);
-            ov.z = (zz.z * kr_sigmoid_poly5(zz.z)) * ((v.z * rms) * wv.z); ov.w = (zz.w * kr_sigmoid_poly5(zz.w)) * ((v.w * rms) * wv.w);
+            ov.x = kr_gated_norm_out(v.x, rms, wv.x, zz.x); ov.y = kr_gated_norm_out(v.y, rms, wv.y, zz.y);
+            ov.z = kr_gated_norm_out(v.z, rms, wv.z, zz.z); ov.w = kr_gated_norm_out(v.w, rms, wv.w, zz.w);
             *reinterpret_cast<float4*>(out + o + 4 * lane) = ov;
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup"); __builtin_amdgcn_wave_barrier();      // the slice is rewritten by the wave's next row
@@ -397,7 +375,7 @@ __global__ void __launch_bounds__(256) kr_pfm_gqa_prep_kernel(const KrPfmGqaArgs
                 float ss = 0.0f;
                 const float4* x4 = reinterpret_cast<const float4*>(x);
                 for (int i = 0; i < nc; i++) { const float4 v = x4[i]; ss += v.x * v.x; ss += v.y * v.y; ss += v.z * v.z; ss += v.w * v.w; }      // index order (decode.rs:2891)
-                x[hd] = 1.0f / sqrtf(ss / (float)hd + a.eps);
+                x[hd] = kr_rms_inv(ss, hd, a.eps);
             }
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup"); __builtin_amdgcn_wave_barrier();
             const float rms = x[hd];
@@ -515,7 +493,7 @@ __global__ void __launch_bounds__(256) kr_pfm_gqa_scores_kernel(const KrPfmGqaAr
 #pragma unroll
             for (int u = 0; u < 4; u++) {
                 const int r = r0 + u, tt = r / group, hh = kvh * group + r % group, qpos = a.pos0 + t0 + tt;
-                const float sv = kr_pfm_hsum8(acc[u]);
+                const float sv = kr_hsum8(acc[u]);
                 if (r < R && l == 0 && pos <= qpos) sc[((size_t)(t0 + tt) * a.nh + hh) * sc_ld + pos] = sv * a.sm_scale;
             }
         }
@@ -601,7 +579,7 @@ __global__ void __launch_bounds__(256) kr_pfm_gqa_scores_t_kernel(const KrPfmGqa
 #pragma unroll
             for (int u = 0; u < 4; u++) {
                 const int r = r0 + u, tt = r / group, hh = kvh * group + r % group, qpos = a.pos0 + t0 + tt;
-                const float sv = kr_pfm_hsum8(acc[u]);
+                const float sv = kr_hsum8(acc[u]);
                 if (r < R && l == 0 && pos <= qpos) sc[((size_t)(t0 + tt) * a.nh + hh) * sc_ld + pos] = sv * a.sm_scale;
             }
         }
@@ -622,8 +600,7 @@ __global__ void __launch_bounds__(256) kr_pfm_gqa_softmax_kernel(float* __restri
         const float* tm = tmax + (size_t)row * (sc_ld >> 5);
         for (int b = lane; b < (seq + 31) >> 5; b += 64) mx = fmaxf(mx, tm[b]);
     } else for (int p = lane; p < seq; p += 64) mx = fmaxf(mx, s[p]);
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
+    mx = kr_wave_max(mx);
     float se = 0.0f;
     for (int p0 = 0; p0 < seq; p0 += 64) {
         const int p = p0 + lane;
@@ -940,8 +917,7 @@ __global__ void __launch_bounds__(1024) kr_pfm_nll_kernel(const float* __restric
     const int t = threadIdx.x;
     float mx = -__builtin_inff();
     for (int i = t; i < V; i += 1024) mx = fmaxf(mx, x[i]);
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
+    mx = kr_wave_max(mx);
     if ((t & 63) == 0) redf[t >> 6] = mx;
     __syncthreads();
     mx = redf[0];

@@ -13,6 +13,7 @@
 //   bf16: G[e/4][c8 < H/128][(e%4)*16 + j][u < 8] = gate[e][16*(8*c8+u) + j]   (used when every value is bf16-exact)
 #include "kr_device.h"
 #include "kr_libm.h"
+#include "kr_exact_dev.h"
 #include "kr_router.h"
 #include "kr_topk.h"
 
@@ -78,11 +79,7 @@ __global__ void __launch_bounds__(256) kr_route_logits_decode_kernel(const void*
         }
     }
     // acc0 + acc1 (decode.rs:1419), then the hsum tree (:1420-1427): (l0+l4 + l1+l5) + (l2+l6 + l3+l7)
-    float v = acc;
-    v = v + __shfl_xor(v, 8);
-    v = v + __shfl_xor(v, 4);
-    v = v + __shfl_xor(v, 1);
-    v = v + __shfl_xor(v, 2);
+    float v = kr_hsum8(acc + __shfl_xor(acc, 8));
     const int e = eb * 4 + (lane >> 4);
     if (j == 0 && e < E) {
         if (bias) v += bias[e];  // decode.rs:3292-3294
@@ -340,11 +337,10 @@ __global__ void __launch_bounds__(256) kr_route_fused_decode_kernel(const KrRout
             for (int i = t; i < H; i += 256) { const float v = a.hid_in[i] + a.res_in[i]; r[i] = v; rt[(i & 7) * ldt + (i >> 3)] = v; if (blockIdx.x == 0) a.res_out[i] = v; }
         __syncthreads();
         if (t < 8) {
-            float ss = kr_sumsq_lane_t(rt, ldt, H, t);
-            ss = ss + __shfl_xor(ss, 4); ss = ss + __shfl_xor(ss, 1); ss = ss + __shfl_xor(ss, 2);
+            float ss = kr_hsum8(kr_sumsq_lane_t(rt, ldt, H, t));
             if (t == 0) {
                 for (int q = (H / 8) * 8; q < H; q++) ss += r[q] * r[q];
-                r[H] = 1.0f / sqrtf(ss / (float)H + a.eps);
+                r[H] = kr_rms_inv(ss, H, a.eps);
             }
         }
         __syncthreads();
@@ -438,11 +434,7 @@ __global__ void __launch_bounds__(256) kr_route_fused_decode_kernel(const KrRout
                 }
             }
         }
-        float v = acc;
-        v = v + __shfl_xor(v, 8);
-        v = v + __shfl_xor(v, 4);
-        v = v + __shfl_xor(v, 1);
-        v = v + __shfl_xor(v, 2);
+        float v = kr_hsum8(acc + __shfl_xor(acc, 8));
         const int e = eb * 4 + (lane >> 4);
         if (j == 0 && e < E) {
             if (a.bias) v += a.bias[e];

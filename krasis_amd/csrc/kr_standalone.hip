@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include "kr_libm.h"
+#include "kr_exact_dev.h"
 #include "kr_standalone.h"
 
 // decode.rs:473-507 rmsnorm: sum_sq += x*x in index order (mul, then add -- the build keeps contraction off), rms = 1/sqrt(sum/n + eps),
@@ -17,7 +18,7 @@ __global__ void __launch_bounds__(256) kr_op_rmsnorm_kernel(const float* __restr
     if (threadIdx.x == 0) {
         float ss = 0.0f;
         for (int i = 0; i < n; i++) ss += x[i] * x[i];
-        rms_s = 1.0f / sqrtf(ss / (float)n + eps);
+        rms_s = kr_rms_inv(ss, n, eps);
     }
     __syncthreads();
     const float rms = rms_s;
@@ -41,7 +42,7 @@ __global__ void __launch_bounds__(256) kr_op_gated_rmsnorm_silu_kernel(const flo
     if (threadIdx.x == 0) {
         float ss = 0.0f;
         for (int j = 0; j < dv; j++) ss += x[base + j] * x[base + j];
-        rms_s = 1.0f / sqrtf(ss / (float)dv + eps);
+        rms_s = kr_rms_inv(ss, dv, eps);
     }
     __syncthreads();
     const float rms = rms_s;
@@ -80,10 +81,8 @@ __global__ void __launch_bounds__(256) kr_op_la_conv1_kernel(KrOpLaConvArgs a) {
     if (ch < nv) {        // gates (decode.rs:878-885)
         const int h = ch / hr, r = ch % hr;
         const float b_raw = a.ba[h * 2 * hr + r], a_p = a.ba[h * 2 * hr + hr + r];
-        a.beta[ch] = 1.0f / (1.0f + kr_expf(-b_raw));
-        const float ap_dt = a_p + a.dt_bias[ch];
-        const float softplus = ap_dt > 20.0f ? ap_dt : kr_logf(1.0f + kr_expf(ap_dt));
-        a.g[ch] = -(kr_expf(a.a_log[ch])) * softplus;
+        a.beta[ch] = kr_la_beta(b_raw);
+        a.g[ch] = kr_la_g(a_p, a.dt_bias[ch], a.a_log[ch]);
     }
 }
 __global__ void __launch_bounds__(256) kr_op_la_conv2_kernel(KrOpLaConvArgs a) {
@@ -94,7 +93,7 @@ __global__ void __launch_bounds__(256) kr_op_la_conv2_kernel(KrOpLaConvArgs a) {
         const float* s = threadIdx.x ? ks : qs;
         float ss = 0.0f;
         for (int i = 0; i < dk; i++) { const float v = s[i]; ss += v * v; }
-        inv_s[threadIdx.x] = ss > 0.0f ? 1.0f / sqrtf(ss) : 0.0f;
+        inv_s[threadIdx.x] = kr_l2_inv(ss);
     }
     __syncthreads();
     const float iq = inv_s[0], ik = inv_s[1];
