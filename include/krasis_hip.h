@@ -494,6 +494,32 @@ int kr_decode_slots_create_paged(kr_decode_store* s, int n_slots, int max_seq, i
 int kr_decode_slot_trim(kr_decode_store* s, int slot, int seq_len);
 /* the geometry, the free pages and the mapped pages of every slot (per_slot_out [n_slots], may be NULL; so may the others).  Flat slots: page_tokens 0, n_pages 0 */
 int kr_decode_slots_pages(kr_decode_store* s, int32_t* page_tokens_out, int32_t* n_pages_out, int32_t* n_free_out, int32_t* per_slot_out);
+/* ---- slot fork with shared, copy-on-write pages (docs/design/22-slot-fork.md).  After the call every dsts[i] behaves as a fresh slot into which src's first
+   seq_len positions were prefilled: GQA rows (K, V) and MLA rows (latent, rope-key) [0, seq_len) have src's bits, rows at or past seq_len read as zero, and the
+   conv + recurrent state of every linear-attention layer is copied from src as it stands.  The library keeps no per-slot length: on a store with
+   linear-attention layers seq_len must therefore be the number of tokens src has consumed (this cannot be checked); a store of GQA / MLA layers only may
+   fork at any prefix.  Whatever a dst held is released first, as kr_decode_slot_trim(dst, 0); its sampler (parameters, seen set, RNG) is not touched --
+   n-best sampling is a fork followed by kr_decode_slot_sampler with different seeds.  src is unchanged bit for bit, and so are the store's own sequence, a
+   captured decode graph and the options.
+   Paged slots: the whole pages below seq_len are shared by reference count, not copied; if seq_len is not a multiple of page_tokens each dst gets a page of its
+   own holding src's rows of the boundary page with zeroes behind them; later pages stay unmapped.  All or nothing: the call needs one page per dst (none at a
+   page boundary) out of the free pages and those the dsts give back, else KR_ERR_STATE naming pages needed, free and the pool size, and nothing changes.
+   A write never lands in a page with more than one reference: every batched entry point (and kr_decode_slot_save) first replaces such a page, where its rows
+   will write, by a private copy, counted in its all-or-nothing reservation.  Trim and the give-back of kr_decode_generate_multi* drop a reference; a page
+   returns to the pool with its last one.  Flat slots: rows [0, seq_len) are copied, rows [seq_len, max_seq) of each dst zeroed.
+   KR_ERR_VALUE: src or a dst out of range, src among dsts, a dst named twice, n_dst outside [1, n_slots - 1], seq_len outside [0, max_seq].  KR_ERR_STATE:
+   a verify over slots is pending; the pool cannot supply the call.  Returns with its stream drained. */
+int kr_decode_slot_fork(kr_decode_store* s, int src, int n_dst, const int32_t* dsts, int seq_len);
+/* a paged slot's table row (ids_out [ceil(max_seq / page_tokens)], -1 = unmapped) and the reference count of each mapped page (refs_out, 0 for unmapped);
+   either may be NULL.  Flat slots: KR_ERR_STATE */
+int kr_decode_slot_page_ids(kr_decode_store* s, int slot, int32_t* ids_out, int32_t* refs_out);
+/* the entries of a paged slot's table row, ceil(max_seq / page_tokens): what kr_decode_slot_page_ids writes to each of its outputs.  Flat slots: 0 */
+int kr_decode_slots_page_stride(kr_decode_store* s, int32_t* stride_out);
+/* test aid: the page-copy launch of a fork / a copy-on-write on one host pool [n_pages][page_bytes] (in / out), a row being page_bytes / page_tokens bytes:
+   copy c = the first rows[c] rows of page src_pages[c] into page dst_pages[c], zeroes behind them.  No page may be a destination twice, or a source and a
+   destination.  The device copy of the pool starts base_offset bytes (in [0, 256)) past an aligned address. */
+int kr_copy_pages(void* pool, size_t page_bytes, int n_pages, int page_tokens, int n_copies, const int32_t* dst_pages, const int32_t* src_pages,
+                  const int32_t* rows, int base_offset);
 /* test aid beside kr_sample_rows: the verify-form sampler, the accept kernel and the sampler commit on host logits [T][vocab] in caller order (the runs
    concatenated: counts[n] in [1, KR_VERIFY_MAX], tokens[T]); run i is its own "slot" with per-run parameters, seen bitmap [n][(vocab+31)/32] and xorshift64
    state (both in / out: the state after the commit).  ids_out[T] and n_match_out[n] as kr_decode_verify_multi_sample's.  n_keep[n] in / out: the wanted

@@ -44,6 +44,9 @@ struct kr_multi_state {
     // all slots and a_stride / b_stride the bytes of one page.  pg: the free list and the page table on the host; pg_table: its device copy; pg_pools: KrPagePoolDev
     // of every pool; pg_new: the ids of the pages a pass has to zero.  pg_pending: mappings made on the host that the device has not seen yet (pg_flush)
     KrPagePool pg; DevBuf pg_table, pg_pools, pg_new; int pg_npools = 0; std::vector<KrPageChange> pg_pending;
+    // shared pages (kr_decode_slot_fork, docs/design/22-slot-fork.md): pg_new holds, behind the n_pages ids to zero, [dst | src | rows] of the page copies a pass
+    // opens with.  la_pools: KrPagePoolDev of every linear-attention state buffer, a "page" being a slot (flat and paged slots); fk_ids: [dst | src | rows] slots of a fork
+    DevBuf la_pools, fk_ids; int la_npools = 0;
     DevBuf rows, ids, logits, scores, scratch; // step: [slots | tokens | positions] (device), greedy ids, [n][vocab] logits, attention scores, the arena
     DevBuf fd_o, fd_ml; bool fd_ready = false; // "multi_attn_fast": split-KV partials [n][nkv][chunks][G][hd] and (max, sum) [n][nh][chunks][2] of one GQA layer, sized by the step's longest row; the kernels' LDS windows are raised
     // per-slot samplers (kr_decode_slot_sampler, docs/design/14-multi-sampling.md): allocated for every slot on the first call; empty = every slot greedy

@@ -18,6 +18,8 @@
 // verify + commit where one does, with the draft rule of kr_lookup_index.h.
 // Paged slots (kr_decode_slots_create_paged, docs/design/21-paged-slots.md): the GQA / MLA rows live in pools of pages shared by all slots; every entry point maps
 // the pages its rows need on the host first (kr_page_pool.h), all or nothing, and the pass opens by sending the changed table entries and zeroing the new pages.
+// kr_decode_slot_fork (docs/design/22-slot-fork.md): a slot's prefix into other slots without the prompt pass -- paged slots share the whole pages below the
+// fork point by reference count, and the reservation of every call that writes rows first gives a row a private copy of a page other slots hold too.
 #include <algorithm>
 #include <chrono>
 #include <climits>
@@ -68,13 +70,14 @@ int paged_refuse(kr_decode_store* s) {
     return KR_OK;
 }
 // all or nothing, on the host: slot slots[i] gets the pages that cover [0, lens[i]), lowest free id first; the mappings wait in pg_pending for pg_flush and
-// are appended to log (a caller that gives some back later)
-int pg_reserve(kr_decode_store* s, int n, const int32_t* slots, const long long* lens, std::vector<KrPageChange>* log) {
+// are appended to log (a caller that gives some back later).  from (null: the call writes no rows) = the first position each slot writes: a page there that
+// other slots hold too is replaced by a private copy, counted in the same sum (docs/design/22-slot-fork.md)
+int pg_reserve(kr_decode_store* s, int n, const int32_t* slots, const long long* lens, const long long* from, std::vector<KrPageChange>* log) {
     kr_multi_state& M = *s->multi;
     if (!M.pg.paged()) return KR_OK;
     const size_t before = M.pg_pending.size();
     int need = 0, have = 0;
-    const int bad = M.pg.reserve(n, slots, lens, &M.pg_pending, &need, &have);
+    const int bad = M.pg.reserve(n, slots, lens, &M.pg_pending, &need, &have, from);
     if (bad >= 0)
         return kr_fail(KR_ERR_STATE, "row %d: slot %d does not fit the page pool: positions [0, %lld) bring the call to %d more pages of %d positions, %d of %d are free",
                        bad, slots[bad], lens[bad], need, M.pg.page_tokens, have, M.pg.n_pages);
@@ -90,27 +93,50 @@ int pg_upload(kr_multi_state& M, int slot, int lo, int hi, hipStream_t st) {
     return KR_OK;
 }
 // what the host mapped since the last pass -> the device, on the pass's stream ahead of the pass: the changed table entries, then ONE launch that makes the
-// new pages read as zero in every layer's pools, as a freshly created flat slot does
+// new pages read as zero in every layer's pools, as a freshly created flat slot does, then ONE launch for the pages that start as a copy of another (a fork's
+// boundary page, a private copy of a shared page: written whole by that launch, so not zeroed first).  A copy that reads the page an earlier queued copy
+// writes goes into a launch of its own behind it (kr_page_copy_launches).  A copy's source is held until here; an error leaves everything queued and held
 int pg_flush(kr_multi_state& M, hipStream_t st) {
     if (M.pg_pending.empty()) return KR_OK;
-    std::vector<int32_t> pages;
+    std::vector<int32_t> pages, copies[3];      // copies: dst, src, rows
     std::vector<int> lo((size_t)M.n_slots, INT_MAX), hi((size_t)M.n_slots, -1);
     for (const KrPageChange& c : M.pg_pending) {
-        pages.push_back(c.page);
+        if (c.src < 0) pages.push_back(c.page);
+        else { copies[0].push_back(c.page); copies[1].push_back(c.src); copies[2].push_back(c.rows); }
         lo[(size_t)c.slot] = std::min(lo[(size_t)c.slot], (int)c.idx); hi[(size_t)c.slot] = std::max(hi[(size_t)c.slot], (int)c.idx);
     }
-    M.pg_pending.clear();
     for (int sl = 0; sl < M.n_slots; sl++) if (hi[(size_t)sl] >= 0) if (int rc = pg_upload(M, sl, lo[(size_t)sl], hi[(size_t)sl], st)) return rc;
-    KR_HIP(hipMemcpyAsync(M.pg_new.p, pages.data(), pages.size() * 4, hipMemcpyHostToDevice, st));      // pg_new holds n_pages ids, and a page is pending once
-    kr_launch_multi_zero_pages((const KrPagePoolDev*)M.pg_pools.p, M.pg_npools, (const int*)M.pg_new.p, (int)pages.size(), st);
+    if (!pages.empty()) {
+        KR_HIP(hipMemcpyAsync(M.pg_new.p, pages.data(), pages.size() * 4, hipMemcpyHostToDevice, st));      // pg_new holds n_pages ids, and a page is pending once
+        kr_launch_multi_zero_pages((const KrPagePoolDev*)M.pg_pools.p, M.pg_npools, (const int*)M.pg_new.p, (int)pages.size(), st);
+    }
+    if (const size_t nc = copies[0].size()) {      // behind the ids to zero: [dst | src | rows], n_pages each (a page is a destination once)
+        int32_t* ids = (int32_t*)M.pg_new.p + (size_t)M.pg.n_pages;
+        for (int k = 0; k < 3; k++) KR_HIP(hipMemcpyAsync(ids + (size_t)k * M.pg.n_pages, copies[k].data(), nc * 4, hipMemcpyHostToDevice, st));
+        size_t c0 = 0;
+        for (size_t end : kr_page_copy_launches(copies[0], copies[1])) {      // one launch, unless a copy reads what an earlier one writes
+            kr_launch_multi_copy_pages((const KrPagePoolDev*)M.pg_pools.p, M.pg_npools, ids + c0, ids + (size_t)M.pg.n_pages + c0, ids + (size_t)2 * M.pg.n_pages + c0, (int)(end - c0),
+                                       M.pg.page_tokens, st);
+            c0 = end;
+        }
+    }
     KR_HIP(hipGetLastError());
+    for (int32_t p : copies[1]) M.pg.unhold(p);      // enqueued: what follows on this stream may take the page
+    M.pg_pending.clear();
     return KR_OK;
 }
-// pages went back to the pool (freed): a mapping of them the device has not seen is dropped with them, and the slots' table rows go to the device
+// entries gave their pages back: a mapping of them the device has not seen is dropped with them, and with it the hold on the page it was to copy from
+void pg_prune(kr_multi_state& M) {
+    M.pg_pending.erase(std::remove_if(M.pg_pending.begin(), M.pg_pending.end(), [&](const KrPageChange& c) {
+        if (M.pg.row(c.slot)[c.idx] == c.page) return false;
+        if (c.src >= 0) M.pg.unhold(c.src);
+        return true; }), M.pg_pending.end());
+}
+// pages went back to the pool (freed): pending mappings of them are dropped, and the slots' table rows go to the device
 int pg_released(kr_decode_store* s, const std::vector<KrPageChange>& freed) {
     kr_multi_state& M = *s->multi;
     if (freed.empty()) return KR_OK;
-    M.pg_pending.erase(std::remove_if(M.pg_pending.begin(), M.pg_pending.end(), [&](const KrPageChange& c) { return M.pg.row(c.slot)[c.idx] != c.page; }), M.pg_pending.end());
+    pg_prune(M);
     KR_HIP(hipSetDevice(s->eng->device));
     std::vector<char> hit((size_t)M.n_slots, 0);
     for (const KrPageChange& c : freed) hit[(size_t)c.slot] = 1;
@@ -157,12 +183,12 @@ int check_args(kr_decode_store* s, const Rows& r, int extra) {
     }
     return KR_OK;
 }
-// paged slots: the pages row i still needs to cover [0, positions[i] + cnt(i) + extra)
+// paged slots: the pages row i still needs to cover [0, positions[i] + cnt(i) + extra), and a page of its own wherever it will write, from positions[i] on
 int pg_reserve_rows(kr_decode_store* s, const Rows& r, int extra, std::vector<KrPageChange>* log) {
     if (!s->multi->pg.paged()) return KR_OK;
-    std::vector<long long> lens((size_t)r.n);
-    for (int i = 0; i < r.n; i++) lens[(size_t)i] = (long long)r.positions[i] + r.cnt(i) + extra;
-    return pg_reserve(s, r.n, r.slots, lens.data(), log);
+    std::vector<long long> lens((size_t)r.n), from((size_t)r.n);
+    for (int i = 0; i < r.n; i++) { from[(size_t)i] = r.positions[i]; lens[(size_t)i] = (long long)r.positions[i] + r.cnt(i) + extra; }
+    return pg_reserve(s, r.n, r.slots, lens.data(), from.data(), log);
 }
 // what a row with these sampler parameters does: the three paths of kr_decode_generate's loop (kr_decode.cpp generate_core)
 KrMsRow mode_row(int slot, float temperature, int top_k, float top_p, float penalty, int vocab, bool force_loop) {
@@ -329,7 +355,7 @@ int slot_copy(kr_decode_store* s, int slot, int seq_len, bool save) {
         if ((s->layers[i].attn == ATTN_GQA || s->layers[i].attn == ATTN_MLA) && (!s->layers[i].kv_k.p || !s->layers[i].kv_v.p))
             return kr_fail(KR_ERR_STATE, "set_decode_state was not called (no %s cache for layer %zu)", s->layers[i].attn == ATTN_MLA ? "MLA" : "KV", i);
     const bool paged = M.pg.paged();
-    if (paged && save) { const int32_t sl = slot; const long long len = seq_len; if (int rc = pg_reserve(s, 1, &sl, &len, nullptr)) return rc; }      // what [0, seq_len) needs
+    if (paged && save) { const int32_t sl = slot; const long long len = seq_len, from = 0; if (int rc = pg_reserve(s, 1, &sl, &len, &from, nullptr)) return rc; }      // what [0, seq_len) needs; the save writes all of it
     KR_HIP(hipSetDevice(s->eng->device));
     KR_HIP(hipDeviceSynchronize());          // steps / prompt passes still in flight on any stream read or write both sides
     hipStream_t st = s->eng->stream;
@@ -604,7 +630,7 @@ static int slots_create(kr_decode_store* s, int n_slots, int max_seq, int page_t
     auto M = std::make_unique<kr_multi_state>();
     M->n_slots = n_slots; M->max_seq = max_seq; M->kv_fp8 = s->kv_fp8;
     const size_t nl = s->layers.size(), seq_rows = paged ? (size_t)page_tokens : (size_t)max_seq;      // rows per slot, or per page
-    std::vector<KrPagePoolDev> pools;
+    std::vector<KrPagePoolDev> pools, la_pools;
     M->a.resize(nl); M->b.resize(nl); M->a_stride.assign(nl, 0); M->b_stride.assign(nl, 0);
     size_t total = 0;
     for (size_t i = 0; i < nl; i++) {
@@ -621,17 +647,23 @@ static int slots_create(kr_decode_store* s, int n_slots, int max_seq, int page_t
             if (d.ensure(bytes)) return kr_fail(KR_ERR_HIP, "hipMalloc of %d sequence slots (%zu MiB so far) failed", n_slots, (total + bytes) >> 20);
             if (pooled) pools.push_back(KrPagePoolDev{d.p, stride});      // a page is zeroed when it is mapped (pg_flush)
             else KR_HIP(hipMemsetAsync(d.p, 0, bytes, s->eng->stream));
+            if (L.attn == ATTN_LA) la_pools.push_back(KrPagePoolDev{d.p, stride});      // a fork copies a slot's state as one "page" (docs/design/22-slot-fork.md)
             total += bytes;
         }
     }
     if (paged) {      // the table (-1 everywhere), the pools' addresses and room for the ids of the pages a pass zeroes
         const size_t tb = pool.table.size() * 4;
-        if (M->pg_table.ensure(tb) || M->pg_pools.ensure(std::max(pools.size(), (size_t)1) * sizeof(KrPagePoolDev)) || M->pg_new.ensure((size_t)n_pages * 4))
+        if (M->pg_table.ensure(tb) || M->pg_pools.ensure(std::max(pools.size(), (size_t)1) * sizeof(KrPagePoolDev)) || M->pg_new.ensure((size_t)n_pages * 4 * 4))      // ids to zero, then [dst | src | rows] of the copies
             return kr_fail(KR_ERR_HIP, "hipMalloc of the page table (%zu KiB) failed", tb >> 10);
         KR_HIP(hipMemsetAsync(M->pg_table.p, 0xFF, tb, s->eng->stream));
         if (!pools.empty()) KR_HIP(hipMemcpyAsync(M->pg_pools.p, pools.data(), pools.size() * sizeof(KrPagePoolDev), hipMemcpyHostToDevice, s->eng->stream));
         M->pg_npools = (int)pools.size(); M->pg = std::move(pool);
         total += tb;
+    }
+    if (!la_pools.empty()) {
+        if (M->la_pools.ensure(la_pools.size() * sizeof(KrPagePoolDev))) return kr_fail(KR_ERR_HIP, "hipMalloc of the linear-attention state table failed");
+        KR_HIP(hipMemcpyAsync(M->la_pools.p, la_pools.data(), la_pools.size() * sizeof(KrPagePoolDev), hipMemcpyHostToDevice, s->eng->stream));
+        M->la_npools = (int)la_pools.size();
     }
     KR_HIP(hipStreamSynchronize(s->eng->stream));
     s->multi = std::move(M);
@@ -664,6 +696,125 @@ extern "C" int kr_decode_slots_pages(kr_decode_store* s, int32_t* page_tokens_ou
     if (n_pages_out) *n_pages_out = M.pg.n_pages;
     if (n_free_out) *n_free_out = M.pg.n_free;
     if (per_slot_out) for (int i = 0; i < M.n_slots; i++) per_slot_out[i] = M.pg.paged() ? M.pg.mapped(i) : 0;
+    return KR_OK;
+}
+
+// ---- slot fork (docs/design/22-slot-fork.md)
+extern "C" int kr_decode_slot_page_ids(kr_decode_store* s, int slot, int32_t* ids_out, int32_t* refs_out) {
+    if (int rc = multi_ready(s)) return rc;
+    if (int rc = need_slots(s)) return rc;
+    if (int rc = slot_in_range(s, slot)) return rc;
+    const kr_multi_state& M = *s->multi;
+    if (!M.pg.paged()) return kr_fail(KR_ERR_STATE, "flat slots have no pages: create them with kr_decode_slots_create_paged");
+    for (int j = 0; j < M.pg.stride; j++) {
+        const int32_t t = M.pg.row(slot)[j];
+        if (ids_out) ids_out[j] = t;
+        if (refs_out) refs_out[j] = t >= 0 ? M.pg.refs[(size_t)t] : 0;
+    }
+    return KR_OK;
+}
+extern "C" int kr_decode_slots_page_stride(kr_decode_store* s, int32_t* stride_out) {
+    if (int rc = multi_ready(s)) return rc;
+    if (int rc = need_slots(s)) return rc;
+    if (!stride_out) return kr_fail(KR_ERR_VALUE, "null stride_out");
+    *stride_out = s->multi->pg.paged() ? s->multi->pg.stride : 0;
+    return KR_OK;
+}
+// test aid: kr_multi_copy_pages_kernel on one host pool [n_pages][page_bytes] (in / out), its device copy placed base_offset bytes past a 256-byte boundary
+extern "C" int kr_copy_pages(void* pool, size_t page_bytes, int n_pages, int page_tokens, int n_copies, const int32_t* dst_pages, const int32_t* src_pages,
+                             const int32_t* rows, int base_offset) {
+    if (!pool || !dst_pages || !src_pages || !rows) return kr_fail(KR_ERR_VALUE, "kr_copy_pages: null pointer");
+    if (page_bytes < 1 || n_pages < 1 || page_tokens < 1 || page_bytes % (size_t)page_tokens) return kr_fail(KR_ERR_VALUE, "kr_copy_pages: %d pages of %zu bytes and %d rows", n_pages, page_bytes, page_tokens);
+    if (n_copies < 1 || n_copies > n_pages) return kr_fail(KR_ERR_VALUE, "n_copies %d outside [1, %d]", n_copies, n_pages);
+    if (base_offset < 0 || base_offset >= 256) return kr_fail(KR_ERR_VALUE, "base_offset %d outside [0, 256)", base_offset);
+    std::vector<char> written((size_t)n_pages, 0);
+    for (int c = 0; c < n_copies; c++) {      // a launch's copies have no order: a destination is written once and never read
+        if (dst_pages[c] < 0 || dst_pages[c] >= n_pages || src_pages[c] < 0 || src_pages[c] >= n_pages) return kr_fail(KR_ERR_VALUE, "copy %d: page out of range [0, %d)", c, n_pages);
+        if (rows[c] < 0 || rows[c] > page_tokens) return kr_fail(KR_ERR_VALUE, "copy %d: %d rows outside [0, %d]", c, rows[c], page_tokens);
+        if (written[(size_t)dst_pages[c]]++) return kr_fail(KR_ERR_VALUE, "copy %d: page %d is a destination twice", c, dst_pages[c]);
+    }
+    for (int c = 0; c < n_copies; c++) if (written[(size_t)src_pages[c]]) return kr_fail(KR_ERR_VALUE, "copy %d: page %d is a source and a destination", c, src_pages[c]);
+    int dev_count = 0;
+    if (hipGetDeviceCount(&dev_count) != hipSuccess || dev_count == 0) return kr_fail(KR_ERR_HIP, "no HIP device");
+    const size_t bytes = page_bytes * (size_t)n_pages;
+    DevBuf buf, tab, ids;
+    if (buf.ensure(bytes + 256) || tab.ensure(sizeof(KrPagePoolDev)) || ids.ensure((size_t)3 * n_copies * 4)) return kr_fail(KR_ERR_HIP, "hipMalloc failed");
+    const KrPagePoolDev P{(char*)buf.p + base_offset, page_bytes};
+    int32_t* d = (int32_t*)ids.p;
+    KR_HIP(hipMemcpy(P.base, pool, bytes, hipMemcpyHostToDevice));
+    KR_HIP(hipMemcpy(tab.p, &P, sizeof(P), hipMemcpyHostToDevice));
+    KR_HIP(hipMemcpy(d, dst_pages, (size_t)n_copies * 4, hipMemcpyHostToDevice));
+    KR_HIP(hipMemcpy(d + n_copies, src_pages, (size_t)n_copies * 4, hipMemcpyHostToDevice));
+    KR_HIP(hipMemcpy(d + 2 * n_copies, rows, (size_t)n_copies * 4, hipMemcpyHostToDevice));
+    kr_launch_multi_copy_pages((const KrPagePoolDev*)tab.p, 1, d, d + n_copies, d + 2 * n_copies, n_copies, page_tokens, nullptr);
+    KR_HIP(hipGetLastError());
+    KR_HIP(hipDeviceSynchronize());
+    KR_HIP(hipMemcpy(pool, P.base, bytes, hipMemcpyDeviceToHost));
+    return KR_OK;
+}
+// every dsts[i] becomes a fresh slot into which src's first seq_len positions were prefilled.  Paged slots: whole pages below seq_len are shared by reference,
+// the boundary page is a copy of src's rows with zeroes behind them; flat slots: device copies.  The linear-attention state goes over as it stands
+extern "C" int kr_decode_slot_fork(kr_decode_store* s, int src, int n_dst, const int32_t* dsts, int seq_len) {
+    if (int rc = multi_begin(s)) return rc;
+    kr_multi_state& M = *s->multi;
+    if (src < 0 || src >= M.n_slots) return kr_fail(KR_ERR_VALUE, "src: slot %d out of range [0, %d)", src, M.n_slots);
+    if (n_dst < 1 || n_dst > M.n_slots - 1) return kr_fail(KR_ERR_VALUE, "n_dst %d outside [1, %d] (n_slots - 1)", n_dst, M.n_slots - 1);
+    if (!dsts) return kr_fail(KR_ERR_VALUE, "null dsts");
+    std::vector<char> seen((size_t)M.n_slots, 0);
+    for (int i = 0; i < n_dst; i++) {
+        if (dsts[i] < 0 || dsts[i] >= M.n_slots) return kr_fail(KR_ERR_VALUE, "dsts[%d]: slot %d out of range [0, %d)", i, dsts[i], M.n_slots);
+        if (dsts[i] == src) return kr_fail(KR_ERR_VALUE, "dsts[%d]: slot %d is src", i, src);
+        if (seen[(size_t)dsts[i]]++) return kr_fail(KR_ERR_VALUE, "dsts[%d]: slot %d is named twice", i, dsts[i]);
+    }
+    if (seq_len < 0 || seq_len > M.max_seq) return kr_fail(KR_ERR_VALUE, "seq_len %d outside [0, %d] (slot max_seq)", seq_len, M.max_seq);
+    const bool paged = M.pg.paged();
+    const int full = paged ? seq_len >> M.pg.shift : 0, part = paged ? seq_len & (M.pg.page_tokens - 1) : 0;      // whole pages below seq_len; rows of the boundary page
+    const int32_t edge = part ? M.pg.row(src)[full] : -1;      // src's boundary page: every dst gets a copy of its own (unmapped: it stays unmapped there too)
+    if (paged) {      // all or nothing: the boundary pages, out of the free pages and those the dsts give back
+        const int need = edge >= 0 ? n_dst : 0, gain = M.pg.would_free(n_dst, dsts);
+        if (need > M.pg.n_free + gain)
+            return kr_fail(KR_ERR_STATE, "the fork of slot %d at seq_len %d does not fit the page pool: %d more pages of %d positions, %d of %d are free (%d of them once the dsts are released)",
+                           src, seq_len, need, M.pg.page_tokens, M.pg.n_free + gain, M.pg.n_pages, gain);
+    }
+    if (M.fk_ids.ensure((size_t)3 * M.n_slots * 4)) return kr_fail(KR_ERR_HIP, "hipMalloc of the fork's slot ids failed");
+    KR_HIP(hipSetDevice(s->eng->device));
+    KR_HIP(hipDeviceSynchronize());          // steps still in flight on any stream read or write both sides
+    hipStream_t st = s->eng->stream;
+    if (paged) {
+        for (int i = 0; i < n_dst; i++) M.pg.trim(dsts[i], 0, nullptr);      // what the dsts held, as kr_decode_slot_trim(dst, 0)
+        pg_prune(M);
+        for (int i = 0; i < n_dst; i++) {
+            M.pg.share(src, dsts[i], full);
+            if (edge < 0) continue;
+            M.pg.row(dsts[i])[full] = M.pg.take();
+            M.pg.holds[(size_t)edge]++;
+            M.pg_pending.push_back(KrPageChange{dsts[i], full, M.pg.row(dsts[i])[full], edge, part});
+        }
+        if (int rc = pg_flush(M, st)) return rc;      // src's own pending pages are zeroed, or copied in an earlier launch, ahead of the boundary copies
+        for (int i = 0; i < n_dst; i++) if (int rc = pg_upload(M, dsts[i], 0, M.pg.stride - 1, st)) return rc;
+    }
+    for (size_t li = 0; li < s->layers.size() && !paged; li++) {      // flat slots: rows [0, seq_len) copied, the rest zeroed
+        const DLayer& L = s->layers[li];
+        if (L.attn != ATTN_GQA && L.attn != ATTN_MLA) continue;
+        for (int h = 0; h < 2; h++) {
+            const size_t stride = h ? M.b_stride[li] : M.a_stride[li], head = stride / (size_t)M.max_seq * (size_t)seq_len;
+            char* base = (char*)(h ? M.b[li].p : M.a[li].p);
+            for (int i = 0; i < n_dst; i++) {
+                char* d = base + (size_t)dsts[i] * stride;
+                if (head) KR_HIP(hipMemcpyAsync(d, base + (size_t)src * stride, head, hipMemcpyDeviceToDevice, st));
+                if (stride > head) KR_HIP(hipMemsetAsync(d + head, 0, stride - head, st));
+            }
+        }
+    }
+    if (M.la_npools) {      // conv and recurrent state of every linear-attention layer: one launch, a slot being the page
+        std::vector<int32_t> ids((size_t)3 * n_dst);
+        for (int i = 0; i < n_dst; i++) { ids[(size_t)i] = dsts[i]; ids[(size_t)n_dst + i] = src; ids[(size_t)2 * n_dst + i] = 1; }
+        KR_HIP(hipMemcpyAsync(M.fk_ids.p, ids.data(), ids.size() * 4, hipMemcpyHostToDevice, st));
+        const int32_t* d = (const int32_t*)M.fk_ids.p;
+        kr_launch_multi_copy_pages((const KrPagePoolDev*)M.la_pools.p, M.la_npools, d, d + n_dst, d + 2 * n_dst, n_dst, 1, st);
+        KR_HIP(hipGetLastError());
+    }
+    KR_HIP(hipStreamSynchronize(st));
     return KR_OK;
 }
 

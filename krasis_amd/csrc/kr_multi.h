@@ -89,6 +89,10 @@ int kr_launch_multi_mla(const KrMultiMlaArgs& a, int B, hipStream_t st);
 #define KR_PAGE_MIN_TOKENS 32      // = KR_MM_ROWS (kr_multi.hip): a stage of the MLA attention kernel never straddles a page
 struct KrPagePoolDev { void* base; size_t page_bytes; };
 void kr_launch_multi_zero_pages(const KrPagePoolDev* pools, int n_pools, const int* pages, int n_pages, hipStream_t st);
+// shared pages (docs/design/22-slot-fork.md): in every pool, copy c = the first rows[c] rows of page src_pages[c] into page dst_pages[c] and zeroes behind them,
+// a row being page_bytes / page_tokens bytes -- grid (n_copies, n_pools), one launch.  Also the per-slot linear-attention state of a fork: pools whose "page" is
+// a slot, page_tokens 1, rows 1
+void kr_launch_multi_copy_pages(const KrPagePoolDev* pools, int n_pools, const int* dst_pages, const int* src_pages, const int* rows, int n_copies, int page_tokens, hipStream_t st);
 
 // per row b < B of logits [B][ld]: out[b] = first-maximum argmax of the row's first V values (kr_argmax_kernel's rule)
 void kr_launch_multi_argmax(const float* logits, size_t ld, int V, int B, int* out, hipStream_t st);

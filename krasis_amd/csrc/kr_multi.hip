@@ -648,6 +648,39 @@ void kr_launch_multi_zero_pages(const KrPagePoolDev* pools, int n_pools, const i
     if (n_pools < 1 || n_pages < 1) return;
     hipLaunchKernelGGL(kr_multi_zero_pages_kernel, dim3(n_pages, n_pools), dim3(256), 0, st, pools, pages);
 }
+// ---- shared pages (docs/design/22-slot-fork.md): copy c of pool p = the first rows[c] * (page_bytes / page_tokens) bytes of page src[c] into page dst[c], the
+// rest of dst[c] zeroed -- a destination page is written whole.  grid (n_copies, n_pools), 256 threads.  The body moves 16 bytes per thread and step; the one
+// vector the split may fall inside (rope-key rows of rd E4M3 bytes) keeps the source's bytes below the split.  A pool whose pages are not 16-byte aligned
+// (a per-slot state buffer of an odd geometry) goes byte by byte.
+__device__ __forceinline__ uint32_t kr_low_bytes(uint32_t v, int keep) { return keep >= 4 ? v : keep <= 0 ? 0u : v & ((1u << (8 * keep)) - 1u); }
+__global__ void __launch_bounds__(256) kr_multi_copy_pages_kernel(const KrPagePoolDev* __restrict__ pools, const int* __restrict__ dst_pages, const int* __restrict__ src_pages,
+                                                                  const int* __restrict__ rows, int page_tokens) {
+    const KrPagePoolDev P = pools[blockIdx.y];
+    char* dst = (char*)P.base + (size_t)dst_pages[blockIdx.x] * P.page_bytes;
+    const char* src = (const char*)P.base + (size_t)src_pages[blockIdx.x] * P.page_bytes;
+    const size_t split = (size_t)min(max(rows[blockIdx.x], 0), page_tokens) * (P.page_bytes / (size_t)page_tokens);      // bytes copied; zero from there on
+    if ((P.page_bytes | (size_t)P.base) & 15) {
+        for (size_t i = threadIdx.x; i < P.page_bytes; i += 256) dst[i] = i < split ? src[i] : (char)0;
+        return;
+    }
+    const uint4* s4 = reinterpret_cast<const uint4*>(src);
+    uint4* d4 = reinterpret_cast<uint4*>(dst);
+    const size_t n = P.page_bytes / 16, whole = split / 16;
+    for (size_t i = threadIdx.x; i < n; i += 256) {
+        uint4 v = make_uint4(0u, 0u, 0u, 0u);
+        if (i < whole) v = s4[i];
+        else if (i * 16 < split) {      // i == whole and the split is inside this vector
+            const int keep = (int)(split - i * 16);
+            const uint4 t = s4[i];
+            v = make_uint4(kr_low_bytes(t.x, keep), kr_low_bytes(t.y, keep - 4), kr_low_bytes(t.z, keep - 8), kr_low_bytes(t.w, keep - 12));
+        }
+        d4[i] = v;
+    }
+}
+void kr_launch_multi_copy_pages(const KrPagePoolDev* pools, int n_pools, const int* dst_pages, const int* src_pages, const int* rows, int n_copies, int page_tokens, hipStream_t st) {
+    if (n_pools < 1 || n_copies < 1 || page_tokens < 1) return;
+    hipLaunchKernelGGL(kr_multi_copy_pages_kernel, dim3(n_copies, n_pools), dim3(256), 0, st, pools, dst_pages, src_pages, rows, page_tokens);
+}
 
 // ---- per-row greedy id ---------------------------------------------------------------------------------------------------------------------------
 // grid B, 1024 threads per row: kr_argmax_kernel's first maximum (kr_row_argmax_1024)

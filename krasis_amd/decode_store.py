@@ -442,6 +442,27 @@ class CpuDecodeStore:
         check(self._lib.kr_decode_slots_pages(self._h, C.byref(pt), C.byref(npg), C.byref(free), per.ctypes.data))
         return dict(page_tokens=pt.value, n_pages=npg.value, free=free.value, per_slot=[int(x) for x in per[: int(getattr(self, "_n_slots", 0))]])
 
+    def fork_slot(self, src: int, dsts, seq_len: int) -> None:
+        """kr_decode_slot_fork (docs/design/22-slot-fork.md): every slot of dsts (an int or a sequence) becomes a fresh slot into which src's first seq_len
+        positions were prefilled -- GQA / MLA rows [0, seq_len) with src's bits, zero from there on, the linear-attention state copied as it stands.  The
+        library keeps no per-slot length: on a store with linear-attention layers seq_len must be the number of tokens src has consumed (this cannot be
+        checked); a store of GQA / MLA layers only may fork at any prefix.  What a dst held is released first; its sampler is not touched (n-best: fork,
+        then set_slot_sampler with different seeds).  Paged slots share the whole pages below seq_len by reference and copy on write; all or nothing:
+        a pool that cannot give each dst its boundary page refuses the call (RuntimeError) and nothing changes."""
+        self._need()
+        d = np.ascontiguousarray([dsts] if isinstance(dsts, (int, np.integer)) else list(dsts), dtype=np.int32)
+        check(self._lib.kr_decode_slot_fork(self._h, src, len(d), d.ctypes.data, seq_len))
+
+    def slot_page_ids(self, slot: int):
+        """kr_decode_slot_page_ids: (ids, refs) of a paged slot -- its table row (-1 = unmapped) and the reference count of each mapped page (0 for
+        unmapped); flat slots: RuntimeError"""
+        self._need()
+        stride = C.c_int32()      # the row length comes from the library: the slots may have been made through another wrapper on this handle
+        check(self._lib.kr_decode_slots_page_stride(self._h, C.byref(stride)))
+        ids, refs = np.full(max(stride.value, 1), -1, np.int32), np.zeros(max(stride.value, 1), np.int32)
+        check(self._lib.kr_decode_slot_page_ids(self._h, slot, ids.ctypes.data, refs.ctypes.data))
+        return [int(x) for x in ids], [int(x) for x in refs]
+
     def save_slot(self, slot: int, seq_len: int) -> None:
         """the store's own sequence -> slot: KV rows [0, seq_len) of every GQA layer, compressed-KV and rope-key rows [0, seq_len) of every MLA
         layer, conv + recurrent state of every linear-attention layer"""
