@@ -486,8 +486,10 @@ int kr_decode_slot_sampler_get(kr_decode_store* s, int slot, uint32_t* seen_out 
    back the pages that call mapped which lie wholly past each row's final position.  kr_decode_verify_multi* map the drafted positions and the commit leaves
    them mapped.  kr_decode_slot_save maps what [0, seq_len) needs; kr_decode_slot_load zeroes the store's rows of pages that are not mapped.
    With "multi_attn_fast" set every batched call on paged slots is refused (KR_ERR_STATE).
-   Replaces any earlier slots, flat or paged.  page_tokens: a power of two, at least 32; n_pages >= 1; n_slots >= 1.  *bytes_out (may be NULL) = pools +
-   linear-attention state + table. */
+   Replaces any earlier slots, flat or paged.  page_tokens: a power of two, at least 32; n_pages >= 1; n_slots >= 1.  ceil(max_seq / page_tokens) table
+   entries must fit in the LDS of the GQA attention launch beside its tiles, for every GQA layer of the store (7168 entries at 16 query heads per KV head of
+   head_dim 256, more for narrower layers): otherwise KR_ERR_VALUE naming max_seq, page_tokens, the layer and the largest number of entries, and, as for
+   every bad argument, the earlier slots stay.  *bytes_out (may be NULL) = pools + linear-attention state + table. */
 int kr_decode_slots_create_paged(kr_decode_store* s, int n_slots, int max_seq, int page_tokens, int n_pages, size_t* bytes_out);
 /* every page of the slot with index >= ceil(seq_len / page_tokens) back to the pool (seq_len 0: all of them); linear-attention state and sampler untouched.
    On flat slots a no-op that still checks its arguments (slot in range, 0 <= seq_len <= max_seq).  Refused while a verify over slots is pending. */

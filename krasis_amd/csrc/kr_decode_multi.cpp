@@ -621,6 +621,18 @@ static int slots_create(kr_decode_store* s, int n_slots, int max_seq, int page_t
         const int bad = pool.init(n_slots, max_seq, page_tokens, n_pages, KR_PAGE_MIN_TOKENS);
         if (bad == 1) return kr_fail(KR_ERR_VALUE, "page_tokens %d: must be a power of two and at least %d (a stage of the MLA attention kernel)", page_tokens, KR_PAGE_MIN_TOKENS);
         if (bad) return kr_fail(KR_ERR_VALUE, "n_pages %d: must be at least 1", n_pages);
+        // the paged GQA attention kernel keeps a slot's whole table row in LDS beside its tiles: a capacity it could not launch with is refused here, not by
+        // the first pass, which has mapped pages and advanced linear-attention state by the time it reaches a GQA layer
+        for (size_t i = 0; i < s->layers.size(); i++) {
+            const DLayer& L = s->layers[i];
+            if (L.attn != ATTN_GQA || L.nkv < 1 || L.nh % L.nkv) continue;
+            const size_t tiles = kr_multi_gqa_lds_bytes(L.nh / L.nkv, L.hd, 0);
+            if (tiles > KR_MULTI_GQA_LDS_MAX) continue;      // no slots of this geometry step, flat or paged: the pass says so
+            const long long fit = (long long)((KR_MULTI_GQA_LDS_MAX - tiles) / 4);
+            if (pool.stride > fit)
+                return kr_fail(KR_ERR_VALUE, "max_seq %d at page_tokens %d is a page table of %d entries per slot: GQA layer %zu (%d query heads per KV head, head_dim %d) "
+                               "has room for at most %lld entries beside its tiles (max_seq %lld)", max_seq, page_tokens, pool.stride, i, L.nh / L.nkv, L.hd, fit, fit * page_tokens);
+        }
     }
     KR_HIP(hipSetDevice(s->eng->device));
     KR_HIP(hipDeviceSynchronize());          // a step in flight may still use the old slots

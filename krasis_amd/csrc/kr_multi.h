@@ -57,8 +57,12 @@ struct KrMultiGqaArgs {
     // [n_pages][1 << page_shift][nkv * hd] and position s of slot b is row (page_table[b][s >> page_shift] << page_shift) | (s & mask).  Null: flat slots
     const int* page_table; int page_stride, page_shift;
 };
-// 0: launched; 1: geometry not covered (hd 64 / 128 / 256, nh % nkv == 0)
+// 0: launched; 1: geometry not covered (hd 64 / 128 / 256, nh % nkv == 0), or the dynamic LDS below is over KR_MULTI_GQA_LDS_MAX
 int kr_launch_multi_gqa(const KrMultiGqaArgs& a, int B, hipStream_t st);
+// dynamic LDS of kr_multi_gqa_attn_kernel in bytes: the G = nh / nkv query rows, four softmax tiles, the P.V tile and, on paged slots, the slot's page-table
+// row of page_stride entries (0: flat).  The launcher and kr_decode_slots_create_paged both ask here, so a slot set that is created can be stepped
+#define KR_MULTI_GQA_LDS_MAX (64 * 1024)
+size_t kr_multi_gqa_lds_bytes(int G, int hd, int page_stride);
 // the flash-decode form of the attention launch (after the prep launch): geometry test, the LDS window of its kernel (once, outside the step; non-zero =
 // refused), the chunk pass + merge over n_chunks chunks (0: launched)
 int kr_multi_fd_ok(int nh, int nkv, int hd);

@@ -392,17 +392,21 @@ __global__ void __launch_bounds__(256) kr_multi_gqa_attn_kernel(const KrMultiGqa
     }
 }
 
+size_t kr_multi_gqa_lds_bytes(int G, int hd, int page_stride) {
+    return ((size_t)G * hd + 4 * KR_MG_TILE + (size_t)G * KR_MG_PT + (size_t)page_stride) * 4;
+}
+
 int kr_launch_multi_gqa(const KrMultiGqaArgs& a, int B, hipStream_t st) {
     if ((a.hd != 64 && a.hd != 128 && a.hd != 256) || a.nkv < 1 || a.nh % a.nkv || a.sc_ld % 32) return 1;
     const int G = a.nh / a.nkv;
-    const size_t lds = ((size_t)G * a.hd + 4 * KR_MG_TILE + (size_t)G * KR_MG_PT + (a.page_table ? (size_t)a.page_stride : 0)) * 4;
+    const size_t lds = kr_multi_gqa_lds_bytes(G, a.hd, a.page_table ? a.page_stride : 0);
     if (a.fd_o) {
         if (a.page_table) return 1;      // the split-KV form reads flat slots only (refused with a message at the entry points)      // "multi_attn_fast": the same prep launch, then split-KV flash-decode over the slots (kr_multi_flash.hip)
         if (!kr_multi_fd_ok(a.nh, a.nkv, a.hd) || !a.fd_ml || a.fd_chunks < 1 || a.fd_chunks > 1024) return 1;
         hipLaunchKernelGGL(kr_multi_gqa_prep_kernel<false>, dim3(a.nh + a.nkv, B), dim3(256), 0, st, a);
         return kr_launch_multi_fd(a, B, a.fd_chunks, st);
     }
-    if (lds > 64 * 1024) return 1;
+    if (lds > KR_MULTI_GQA_LDS_MAX) return 1;
 #define KR_MGA(NB_, F_, P_) hipLaunchKernelGGL((kr_multi_gqa_attn_kernel<NB_, F_, P_>), dim3(a.nkv, B), dim3(256), lds, st, a)
 #define KR_MGA_HD(F_, P_) do { if (a.hd == 256) KR_MGA(32, F_, P_); else if (a.hd == 128) KR_MGA(16, F_, P_); else KR_MGA(8, F_, P_); } while (0)
     if (a.page_table) {

@@ -1,6 +1,7 @@
 """Slot fork with shared, copy-on-write pages (docs/design/22-slot-fork.md) at the drop-in boundary, without a GPU: the header declares the two entry points
 with the contract's argument lists, the built library exports them, CpuDecodeStore carries the methods, the copy kernel sits beside the zero kernel, and the
-allocator's sharing -- host-only code -- passes its stand-alone check under AddressSanitizer and UBSan in a child process."""
+allocator's sharing -- host-only code -- passes its stand-alone checks, hand-written scenarios and seeded random calls beside a naive model, under
+AddressSanitizer and UBSan in child processes."""
 import inspect
 import os
 import re
@@ -85,3 +86,20 @@ def test_sharing_program_under_sanitizers(tmp_path):
                            "-I", CSRC, "-o", exe, os.path.join(ROOT, "tests", "page_share_check.cpp")])      # runtimes inside the program: no library order to get wrong
     run = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     assert run.returncode == 0 and "page share ok" in run.stdout, run.stdout
+
+
+def test_random_calls_against_a_naive_model_under_sanitizers(tmp_path):
+    """4000 seeded random calls per seed on KrPagePool -- reservations that append, rewind or write nothing, forks, give-backs, trims, release_logged, queued copies
+    let go in and out of order -- beside a naive model (a set of holders per page, lowest free id by linear scan): table, refs, n_free, n_shared and every log agree
+    after each call, and row, need and have on a refusal; random copy queues through kr_page_copy_launches.  tests/page_pool_random_check.cpp with its own main,
+    compiled alone with -fsanitize=address,undefined and run as a child process (nothing sanitized is loaded into Python)"""
+    cxx = shutil.which("g++") or shutil.which("c++")
+    assert cxx, "no host C++ compiler"
+    exe = str(tmp_path / "page_pool_random_check")
+    subprocess.check_call([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan",
+                           "-I", CSRC, "-o", exe, os.path.join(ROOT, "tests", "page_pool_random_check.cpp")])
+    for seed in (1, 2, 3):
+        run = subprocess.run([exe, "4000", str(seed)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+        assert run.returncode == 0 and "page pool random ok" in run.stdout, (seed, run.stdout)
+        counts = dict(zip(("reserved", "refused", "copies"), map(int, re.search(r"(\d+) reservations, (\d+) refused, (\d+) copy-on-write", run.stdout).groups())))
+        assert counts["refused"] >= 100 and counts["copies"] >= 50 and counts["refused"] < counts["reserved"] // 2, counts      # the run reached what it is about
