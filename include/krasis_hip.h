@@ -264,7 +264,8 @@ int kr_decode_set_kv_dtype(kr_decode_store* s, int kv_dtype);
 #define KR_GEMM_FAST 2   /* or-ed into the mode: every GEMM of kr_decode_prefill (projections, shared expert, routed experts, lm_head of the scoring pass) in the tolerance form of kr_moe_set_gemm_mode; decode steps are unaffected */
 #define KR_DECODE_FAST 4 /* or-ed into the mode: decode steps run the tolerance-mode kernels of kr_decode_fast.hip -- the reference's products (INT16 activation digits, exact integer group sums, its sigmoid / libm functions), but every f32 reduction as a lane / wave / workgroup TREE instead of the reference's sequential chain, the norms folded into the launches that consume them, top-k + silu*up + the expert combine inside the expert launches (6 launches per linear-attention MoE layer).  Router ids are those of the exact kernels for identical logits, with one stated exception: exact ties fall back to the reference's heap order, but with plain softmax scoring + renormalised weights the selection runs on the LOGITS, so two distinct logits among the leading k + 1 whose f32 softmax scores round to the same value (a few ulp apart) are ordered by value here and by the heap's tie rule in the exact kernel; logits agree with the exact mode to the tolerance stated in tests/test_decode_fast_gpu.py.  MLA layers: projections, absorption, latent norm and w_vc in this form, the attention launch itself in the exact order.  Native-GGUF MoE layers (Q4_K / Q8_0 / Q4_0): the routed slots of the two expert launches walk the GGUF blocks (the block kernels' products, a row's blocks split over two waves).  Geometries the kernels do not cover (the down projection of a dense MLP, GPT-OSS activation, E > 512, hidden > 4096, Q5_0 / Q6_K blocks) keep the exact kernels for that layer -- never a CPU path.  The prompt pass is unaffected. */
 int kr_decode_set_attention_mode(kr_decode_store* s, int mode);
-/* Options by name.  Test / tuning hooks: "gqa_stream", "pfm_timing", ... (see kr_decode.cpp); "multi_attn_fast": see kr_decode_step_multi.
+/* Options by name.  Test / tuning hooks: "gqa_stream", "pfm_timing", ... (see kr_decode.cpp); "multi_attn_fast": see kr_decode_step_multi;
+ * "multi_attn_fast_paged" (default 0; docs/design/23-multi-attn-fast-paged.md): "multi_attn_fast" for flat and paged slots alike, see kr_decode_step_multi.
  * "gguf_exact_pass" (default 0; docs/design/20-gguf-exact-pass.md): with 1, every multi-row pass of the store -- kr_decode_prefill, kr_decode_prefill_nll,
  * kr_decode_verify and the batched pass behind every slot entry point -- runs MoE layers that hold native GGUF blocks through the exact grouped block
  * kernels (kr_gguf_group.hip) instead of the int8-MFMA form: every row then carries the bits of kr_decode_step on that sequence alone, and the slot and
@@ -375,7 +376,12 @@ int kr_decode_slot_load(kr_decode_store* s, int slot, int seq_len);
    entry point below run split-KV flash-decode over slots of max_seq > 1024: row i then carries the bits of kr_decode_step under KR_ATTN_FAST on that
    sequence alone (logits within 1e-3 of the exact step, relative to their largest magnitude), whatever rows share the step; shorter slots keep the
    exact step.  The option changes nothing else in the store; the mode bits of kr_decode_set_attention_mode stay refused here, and with the option
-   set a store with MLA layers is refused (KR_ERR_STATE). */
+   set a store with MLA layers is refused (KR_ERR_STATE).  "multi_attn_fast" reads flat slots only: alone it is refused on paged slots.
+   kr_decode_set_option(s, "multi_attn_fast_paged", 1) (default 0; docs/design/23-multi-attn-fast-paged.md) is the same option over both kinds: on paged
+   slots of max_seq > 1024 the flash-decode reads the pools through the slots' page tables and row i carries the bits of the same call on flat slots of
+   the same n_slots and max_seq under "multi_attn_fast", for any page_tokens, any placement of the pages and pages shared by kr_decode_slot_fork; paged
+   slots of max_seq <= 1024 keep the exact paged step; on flat slots it is "multi_attn_fast"; with both set it governs.  Its refusals are those of
+   "multi_attn_fast", and the page pool behaves as without it. */
 int kr_decode_step_multi(kr_decode_store* s, int n, const int32_t* slots, const int32_t* tokens, const int32_t* positions,
                          int32_t* next_out, float* logits_out, void* stream);
 /* greedy generation of n slots together.  Row i's tokens_out[i*max_tokens ...], n_out[i] and its slot's state afterwards are exactly those of
@@ -485,7 +491,8 @@ int kr_decode_slot_sampler_get(kr_decode_store* s, int slot, uint32_t* seen_out 
    row that does not fit, and nothing is mapped or run.  kr_decode_generate_multi* reserve [0, start + max_tokens) before the first pass and on return give
    back the pages that call mapped which lie wholly past each row's final position.  kr_decode_verify_multi* map the drafted positions and the commit leaves
    them mapped.  kr_decode_slot_save maps what [0, seq_len) needs; kr_decode_slot_load zeroes the store's rows of pages that are not mapped.
-   With "multi_attn_fast" set every batched call on paged slots is refused (KR_ERR_STATE).
+   With "multi_attn_fast" set and "multi_attn_fast_paged" clear every batched call on paged slots is refused (KR_ERR_STATE); "multi_attn_fast_paged" is
+   the split-KV option that reads pages (kr_decode_step_multi).
    Replaces any earlier slots, flat or paged.  page_tokens: a power of two, at least 32; n_pages >= 1; n_slots >= 1.  ceil(max_seq / page_tokens) table
    entries must fit in the LDS of the GQA attention launch beside its tiles, for every GQA layer of the store (7168 entries at 16 query heads per KV head of
    head_dim 256, more for narrower layers): otherwise KR_ERR_VALUE naming max_seq, page_tokens, the layer and the largest number of entries, and, as for

@@ -90,6 +90,7 @@ struct kr_decode_store {
     int opt_multi_sample_loop = 0;               // kr_decode_set_option("multi_sample_loop"): every sampled row of a multi-sequence step takes the single-row sampler, one row after another (A/B and test hook; same tokens)
     int opt_gguf_exact_pass = 0;                 // kr_decode_set_option("gguf_exact_pass"): every multi-row pass runs native-GGUF MoE layers through the exact forms (KR_PF_SET_GGUF_EXACT, docs/design/20-gguf-exact-pass.md): a row carries the bits of kr_decode_step, and the slot / speculation entry points accept such a store
     int opt_gguf_exact_grouped = 1;              // ... 0 = through the streaming kernels for every block type (A/B and test hook; same bits)
+    int opt_multi_attn_fast_paged = 0;           // kr_decode_set_option("multi_attn_fast_paged"): "multi_attn_fast" over flat and paged slots alike, the split-KV kernels of paged slots read the pools through the page table (docs/design/23-multi-attn-fast-paged.md); governs when both are set
     int opt_multi_attn_fast = 0;                 // kr_decode_set_option("multi_attn_fast"): the GQA layers of every batched multi-sequence step run split-KV flash-decode over slots longer than gqa_split_min (tolerance form, docs/design/16-multi-attn-fast.md); the mode bits stay refused
     int opt_gen_lookahead = 0;                    // kr_decode_set_option("generate_lookahead"): generate_batch feeds the sampled token back ON THE DEVICE and queues step i + 1 before the host has read token i
     int opt_ep_graph = 0;                         // kr_decode_set_option("ep_graph"): expert-parallel decode over RCCL replays a captured graph (the all-reduce is captured with the kernels)

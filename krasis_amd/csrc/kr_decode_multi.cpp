@@ -63,10 +63,11 @@ int slot_in_range(kr_decode_store* s, int slot) {
     return slot < 0 || slot >= s->multi->n_slots ? kr_fail(KR_ERR_VALUE, "slot %d out of range [0, %d)", slot, s->multi->n_slots) : KR_OK;
 }
 // ---- paged slots (docs/design/21-paged-slots.md): the GQA / MLA rows live in pools of pages shared by all slots; M.pg is the allocator and the table
-// "multi_attn_fast" reads flat slots only: with the option on every batched call on paged slots is refused (an option that silently does nothing is a trap)
+// "multi_attn_fast" reads flat slots only: with that option alone every batched call on paged slots is refused (an option that silently does nothing is a
+// trap); "multi_attn_fast_paged" is the option that reads both kinds (docs/design/23-multi-attn-fast-paged.md)
 int paged_refuse(kr_decode_store* s) {
-    if (s->multi->pg.paged() && s->opt_multi_attn_fast)
-        return kr_fail(KR_ERR_STATE, "\"multi_attn_fast\" does not read paged slots (kr_decode_slots_create_paged): clear the option or create flat slots");
+    if (s->multi->pg.paged() && s->opt_multi_attn_fast && !s->opt_multi_attn_fast_paged)
+        return kr_fail(KR_ERR_STATE, "\"multi_attn_fast\" does not read paged slots (kr_decode_slots_create_paged): set \"multi_attn_fast_paged\", clear the option or create flat slots");
     return KR_OK;
 }
 // all or nothing, on the host: slot slots[i] gets the pages that cover [0, lens[i]), lowest free id first; the mappings wait in pg_pending for pg_flush and

@@ -600,10 +600,11 @@ int kr_exact_refuse(kr_decode_store* s, bool slots) {
     const char *the = slots ? "the " : "", *what = slots ? "multi-sequence step" : "speculative decoding";
     if (s->attn_fast || s->gemm_fast || s->decode_fast)
         return kr_fail(KR_ERR_STATE, "%s%s is exact-mode only: the attention mode has tolerance bits set (%d)", the, what, s->attn_fast | s->gemm_fast << 1 | s->decode_fast << 2);
-    if (slots && s->opt_multi_attn_fast)
+    if (slots && (s->opt_multi_attn_fast || s->opt_multi_attn_fast_paged))
         for (size_t i = 0; i < s->layers.size(); i++)
             if (s->layers[i].attn == ATTN_MLA)
-                return kr_fail(KR_ERR_STATE, "the \"multi_attn_fast\" option covers GQA layers only: layer %zu is MLA (set the option to 0 for the exact step)", i);
+                return kr_fail(KR_ERR_STATE, "the \"%s\" option covers GQA layers only: layer %zu is MLA (set the option to 0 for the exact step)",
+                               s->opt_multi_attn_fast_paged ? "multi_attn_fast_paged" : "multi_attn_fast", i);
     kr_engine* e = s->eng;
     if (e->ep) return kr_fail(KR_ERR_STATE, "%s%s does not run under expert parallelism", the, what);
     for (const DLayer& L : s->layers) {
@@ -738,7 +739,8 @@ int kr_multi_pass(kr_decode_store* s, int n, int n_final, const int32_t* d_rows,
     }
     // "multi_attn_fast": over slots longer than gqa_split_min (the capacity rule of the store's own KR_ATTN_FAST step) every GQA layer takes the split-KV
     // flash-decode; the partials are sized by this step's longest row, and the score rows are not needed unless another kind of layer reads them
-    const bool flash = s->opt_multi_attn_fast && has_gqa && M.max_seq > s->gqa_split_min;
+    // "multi_attn_fast_paged": the same over flat and paged slots; paged ones read through the table (docs/design/23-multi-attn-fast-paged.md)
+    const bool flash = (s->opt_multi_attn_fast || s->opt_multi_attn_fast_paged) && has_gqa && M.max_seq > s->gqa_split_min;
     int fd_chunk = 0, fd_chunks = 0;
     if (flash) {
         fd_chunk = kr_fd_flash_chunk(M.max_seq); fd_chunks = (max_pos + fd_chunk) / fd_chunk;
@@ -747,7 +749,7 @@ int kr_multi_pass(kr_decode_store* s, int n, int n_final, const int32_t* d_rows,
             for (const DLayer& L : s->layers) {
                 if (L.attn != ATTN_GQA) continue;
                 if (!kr_multi_fd_ok(L.nh, L.nkv, L.hd)) return kr_fail(KR_ERR_VALUE, "multi_attn_fast: GQA geometry nh %d nkv %d head_dim %d not covered (head_dim 64 / 128 / 256, at most 32 heads per KV head)", L.nh, L.nkv, L.hd);
-                if (kr_multi_fd_prepare(L.hd, M.kv_fp8)) return kr_fail(KR_ERR_HIP, "multi_attn_fast: LDS window of the flash-decode kernel refused (head_dim %d)", L.hd);
+                if (kr_multi_fd_prepare(L.hd, M.kv_fp8, M.pg.paged())) return kr_fail(KR_ERR_HIP, "multi_attn_fast: LDS window of the flash-decode kernel refused (head_dim %d)", L.hd);
             }
             M.fd_ready = true;
         }

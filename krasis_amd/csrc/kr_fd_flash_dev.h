@@ -29,9 +29,13 @@ __device__ __forceinline__ int fa_vslot(int pp) { return (pp & ~6) | ((pp & 2) <
 // ([position][nkv * HD], FP16 or E4M3) against the G = nh / nkv query heads of the group, q_heads [nh][HD] after QK-norm / RoPE.  256 threads, dynamic LDS
 // FA_TK * (HD * 2 + 16) + HD * (FA_TK * 2 + 16) bytes.  Writes the chunk's un-normalised O to fd_o [nkv][n_chunks][G][HD] and (max in log2 units, sum) to
 // fd_ml [nh][n_chunks][2]; leaves at once when the chunk starts past the sequence.
-template <int HD, bool FP8>
+// PAGED (docs/design/23-multi-attn-fast-paged.md): k_cache / v_cache are pools of pages of 1 << psh positions (psh >= 5) and position p of the sequence is row
+// (ptab[p >> psh] << psh) | (p & mask) of them.  A tile of FA_TK positions starts at a multiple of FA_TK, so it lies in one page, or in two at 32
+// positions per page: the two page ids are workgroup-uniform and their byte offsets stay in scalar registers; a lane adds its row's offset inside the page.
+// Only the three cache addresses differ from the flat instantiation: the order of every operation is the same.
+template <int HD, bool FP8, bool PAGED = false>
 __device__ __forceinline__ void kr_fd_flash_body(int seq, int c, int kvh, const float* q_heads, const void* k_cache, const void* v_cache, float* fd_o, float* fd_ml,
-                                                 int nh, int nkv, float sm_scale, int n_chunks, int chunk) {
+                                                 int nh, int nkv, float sm_scale, int n_chunks, int chunk, const int* ptab = nullptr, int psh = 0) {
     constexpr int KSTEPS = HD / 16, DB = HD / 32, DBW = DB >= 4 ? DB / 4 : 1, LDK = HD * 2 + 16, LDV = FA_TK * 2 + 16;
     constexpr int CPR = FP8 ? HD / 16 : HD / 8, KCH = FA_TK * CPR / 256, VUN = (FA_TK / 2) * CPR, VPT = (VUN + 255) / 256;
     extern __shared__ __attribute__((aligned(16))) char fa_smem[];
@@ -65,21 +69,42 @@ __device__ __forceinline__ void kr_fd_flash_body(int seq, int c, int kvh, const 
     const unsigned char* kc = reinterpret_cast<const unsigned char*>(k_cache) + (size_t)kvh * HD * esz;
     const unsigned char* vc = reinterpret_cast<const unsigned char*>(v_cache) + (size_t)kvh * HD * esz;
     u32x4 pk[KCH], pva[VPT], pvb[VPT];
+    // PAGED: byte offsets in the pools of the pages that hold the two halves of the tile at p0: lo = the page of p0 .. p0 + 31, hi = the page of
+    // min(p0 + 32, pend - 1), which holds every clamped position of rows 32 .. 63 (the last position itself where the tile ends before them).  Both positions
+    // lie in [pbeg, pend), so both entries were mapped by the host before the pass; -1 is never turned into an address all the same
+    const size_t rowb = (size_t)kvs * esz;
+    const int pmask = (1 << psh) - 1;
+    auto tile_pages = [&](int p0, size_t& lo, size_t& hi) {
+        const int i0 = __builtin_amdgcn_readfirstlane(max(ptab[p0 >> psh], 0)), i1 = __builtin_amdgcn_readfirstlane(max(ptab[min(p0 + 32, pend - 1) >> psh], 0));
+        lo = ((size_t)i0 << psh) * rowb; hi = ((size_t)i1 << psh) * rowb;
+    };
     auto load_k = [&](int p0) {
+        [[maybe_unused]] size_t lo = 0, hi = 0;
+        if constexpr (PAGED) tile_pages(p0, lo, hi);
 #pragma unroll
         for (int j = 0; j < KCH; j++) {
             const int cc = tid + j * 256, row = cc / CPR, dc = cc % CPR, p = min(p0 + row, pend - 1);     // clamped: rows past the end are masked below
-            pk[j] = *reinterpret_cast<const u32x4*>(kc + (size_t)p * kvs * esz + dc * 16);
+            if constexpr (PAGED) pk[j] = *reinterpret_cast<const u32x4*>(kc + (row >= 32 ? hi : lo) + (size_t)(p & pmask) * rowb + dc * 16);
+            else pk[j] = *reinterpret_cast<const u32x4*>(kc + (size_t)p * kvs * esz + dc * 16);
         }
     };
     auto load_v = [&](int p0) {
+        [[maybe_unused]] size_t lo = 0, hi = 0;
+        if constexpr (PAGED) tile_pages(p0, lo, hi);
 #pragma unroll
         for (int j = 0; j < VPT; j++) {
             const int u = tid + j * 256, pp = u & 31, dc = u >> 5, p = p0 + 2 * pp;
             pva[j] = u32x4{0, 0, 0, 0}; pvb[j] = u32x4{0, 0, 0, 0};
             if (u < VUN) {
-                const u32x4 va = *reinterpret_cast<const u32x4*>(vc + (size_t)min(p, pend - 1) * kvs * esz + dc * 16);
-                const u32x4 vb = *reinterpret_cast<const u32x4*>(vc + (size_t)min(p + 1, pend - 1) * kvs * esz + dc * 16);
+                u32x4 va, vb;
+                if constexpr (PAGED) {      // p is even: p and p + 1 share a page, and so do their clamped forms
+                    const int pa = min(p, pend - 1), pb = min(p + 1, pend - 1);
+                    const unsigned char* ra = vc + (pp >= 16 ? hi : lo) + (size_t)(pa & pmask) * rowb + dc * 16;
+                    va = *reinterpret_cast<const u32x4*>(ra); vb = *reinterpret_cast<const u32x4*>(ra + (size_t)(pb - pa) * rowb);
+                } else {
+                    va = *reinterpret_cast<const u32x4*>(vc + (size_t)min(p, pend - 1) * kvs * esz + dc * 16);
+                    vb = *reinterpret_cast<const u32x4*>(vc + (size_t)min(p + 1, pend - 1) * kvs * esz + dc * 16);
+                }
                 if (p < pend) pva[j] = va;                 // a probability of exactly 0 meets a finite value: rows past the end must not be NaN patterns
                 if (p + 1 < pend) pvb[j] = vb;
             }

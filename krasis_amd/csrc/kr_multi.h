@@ -51,7 +51,8 @@ struct KrMultiGqaArgs {
     float* scores; int sc_ld;                  // scratch [B][nh][sc_ld], sc_ld >= the longest row's pos + 1 rounded up to 32
     int gated, nh, nkv, hd; float eps, sm_scale;
     // "multi_attn_fast" (kr_multi_flash.hip): split-KV partials [B][nkv][fd_chunks][G][hd] and (max, sum) [B][nh][fd_chunks][2]; fd_chunk positions per
-    // chunk, fd_chunks = the longest row's chunk count.  Null: the exact per-slot kernel (scores is not read when they are set)
+    // chunk, fd_chunks = the longest row's chunk count.  Null: the exact per-slot kernel (scores is not read when they are set).  With page_table set
+    // ("multi_attn_fast_paged", docs/design/23-multi-attn-fast-paged.md) the chunk pass reads the pools through the table
     float *fd_o, *fd_ml; int fd_chunk, fd_chunks;
     // paged slots (docs/design/21-paged-slots.md): page_table [n_slots][page_stride] on the device, -1 = unmapped; k_cache / v_cache are then pools
     // [n_pages][1 << page_shift][nkv * hd] and position s of slot b is row (page_table[b][s >> page_shift] << page_shift) | (s & mask).  Null: flat slots
@@ -64,9 +65,9 @@ int kr_launch_multi_gqa(const KrMultiGqaArgs& a, int B, hipStream_t st);
 #define KR_MULTI_GQA_LDS_MAX (64 * 1024)
 size_t kr_multi_gqa_lds_bytes(int G, int hd, int page_stride);
 // the flash-decode form of the attention launch (after the prep launch): geometry test, the LDS window of its kernel (once, outside the step; non-zero =
-// refused), the chunk pass + merge over n_chunks chunks (0: launched)
+// refused; the paged instantiations are kernels of their own), the chunk pass + merge over n_chunks chunks (0: launched; a.page_table set: through the table)
 int kr_multi_fd_ok(int nh, int nkv, int hd);
-int kr_multi_fd_prepare(int hd, int fp8);
+int kr_multi_fd_prepare(int hd, int fp8, int paged);
 int kr_launch_multi_fd(const KrMultiGqaArgs& a, int B, int n_chunks, hipStream_t st);
 
 // MLA, one token per row: rope of q_pe, latent RMSNorm + rope of k_pe, both rows appended to the row's slot, attention over the slot's rows [0, pos]

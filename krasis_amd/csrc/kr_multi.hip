@@ -401,9 +401,12 @@ int kr_launch_multi_gqa(const KrMultiGqaArgs& a, int B, hipStream_t st) {
     const int G = a.nh / a.nkv;
     const size_t lds = kr_multi_gqa_lds_bytes(G, a.hd, a.page_table ? a.page_stride : 0);
     if (a.fd_o) {
-        if (a.page_table) return 1;      // the split-KV form reads flat slots only (refused with a message at the entry points)      // "multi_attn_fast": the same prep launch, then split-KV flash-decode over the slots (kr_multi_flash.hip)
+        // "multi_attn_fast" / "multi_attn_fast_paged": the same prep launch, then split-KV flash-decode over the slots, flat or paged (kr_multi_flash.hip)
         if (!kr_multi_fd_ok(a.nh, a.nkv, a.hd) || !a.fd_ml || a.fd_chunks < 1 || a.fd_chunks > 1024) return 1;
-        hipLaunchKernelGGL(kr_multi_gqa_prep_kernel<false>, dim3(a.nh + a.nkv, B), dim3(256), 0, st, a);
+        if (a.page_table) {
+            if (a.page_stride < 1 || a.page_shift < 5) return 1;
+            hipLaunchKernelGGL(kr_multi_gqa_prep_kernel<true>, dim3(a.nh + a.nkv, B), dim3(256), 0, st, a);
+        } else hipLaunchKernelGGL(kr_multi_gqa_prep_kernel<false>, dim3(a.nh + a.nkv, B), dim3(256), 0, st, a);
         return kr_launch_multi_fd(a, B, a.fd_chunks, st);
     }
     if (lds > KR_MULTI_GQA_LDS_MAX) return 1;
