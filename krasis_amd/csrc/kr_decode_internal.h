@@ -40,10 +40,12 @@ struct kr_multi_state {
     int n_slots = 0, max_seq = 0, kv_fp8 = 0;
     std::vector<DevBuf> a, b;                  // per layer: LA conv / recurrent state, GQA K / V, MLA latent / rope-key rows
     std::vector<size_t> a_stride, b_stride;    // per layer: bytes per slot
+    std::vector<size_t> a_row, b_row;          // per GQA / MLA layer: bytes of one cache row of a / b (one position; a slot is max_seq of them, a page page_tokens)
     // paged slots (kr_decode_slots_create_paged, docs/design/21-paged-slots.md): a / b of a GQA or MLA layer are then pools [n_pages][page_tokens][row] shared by
-    // all slots and a_stride / b_stride the bytes of one page.  pg: the free list and the page table on the host; pg_table: its device copy; pg_pools: KrPagePoolDev
-    // of every pool; pg_new: the ids of the pages a pass has to zero.  pg_pending: mappings made on the host that the device has not seen yet (pg_flush)
-    KrPagePool pg; DevBuf pg_table, pg_pools, pg_new; int pg_npools = 0; std::vector<KrPageChange> pg_pending;
+    // all slots and a_stride / b_stride the bytes of one page.  pg: the free list, the page table and the queue of mappings the device has not seen yet, all on
+    // the host: the pool owns the queue and prunes it whenever entries are given back; pg_flush only carries out its plan.  pg_table: the table's device copy;
+    // pg_pools: KrPagePoolDev of every pool; pg_new: the ids of the pages a pass has to zero
+    KrPagePool pg; DevBuf pg_table, pg_pools, pg_new; int pg_npools = 0;
     // shared pages (kr_decode_slot_fork, docs/design/22-slot-fork.md): pg_new holds, behind the n_pages ids to zero, [dst | src | rows] of the page copies a pass
     // opens with.  la_pools: KrPagePoolDev of every linear-attention state buffer, a "page" being a slot (flat and paged slots); fk_ids: [dst | src | rows] slots of a fork
     DevBuf la_pools, fk_ids; int la_npools = 0;

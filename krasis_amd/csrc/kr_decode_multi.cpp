@@ -17,12 +17,12 @@
 // (kr_decode_generate_multi, its _sample, _lookup and _lookup_sample forms) are one loop, generate_slots: steps where no row drafts (max_draft 0: always),
 // verify + commit where one does, with the draft rule of kr_lookup_index.h.
 // Paged slots (kr_decode_slots_create_paged, docs/design/21-paged-slots.md): the GQA / MLA rows live in pools of pages shared by all slots; every entry point maps
-// the pages its rows need on the host first (kr_page_pool.h), all or nothing, and the pass opens by sending the changed table entries and zeroing the new pages.
-// kr_decode_slot_fork (docs/design/22-slot-fork.md): a slot's prefix into other slots without the prompt pass -- paged slots share the whole pages below the
-// fork point by reference count, and the reservation of every call that writes rows first gives a row a private copy of a page other slots hold too.
+// the pages its rows need on the host first, all or nothing, and the pass opens by sending the changed table entries and zeroing the new pages.  The table, the
+// free list and the queue of unseen mappings are KrPagePool's (kr_page_pool.h), which prunes the queue itself; here: its members, and flush_plan() carried out (pg_flush).
+// kr_decode_slot_fork (docs/design/22-slot-fork.md): a slot's prefix into other slots without the prompt pass -- paged slots share the whole pages below the fork
+// point by reference count, and the reservation of every call that writes rows first gives a row a private copy of a page other slots hold too.
 #include <algorithm>
 #include <chrono>
-#include <climits>
 #include <cstring>
 #include <vector>
 
@@ -70,23 +70,18 @@ int paged_refuse(kr_decode_store* s) {
         return kr_fail(KR_ERR_STATE, "\"multi_attn_fast\" does not read paged slots (kr_decode_slots_create_paged): set \"multi_attn_fast_paged\", clear the option or create flat slots");
     return KR_OK;
 }
-// all or nothing, on the host: slot slots[i] gets the pages that cover [0, lens[i]), lowest free id first; the mappings wait in pg_pending for pg_flush and
-// are appended to log (a caller that gives some back later).  from (null: the call writes no rows) = the first position each slot writes: a page there that
-// other slots hold too is replaced by a private copy, counted in the same sum (docs/design/22-slot-fork.md)
+// all or nothing, on the host: slot slots[i] gets the pages that cover [0, lens[i]), lowest free id first; the mappings wait in the pool's queue for pg_flush
+// and are appended to log (a caller that gives some back later).  from (null: the call writes no rows) = the first position each slot writes: a page there
+// that other slots hold too is replaced by a private copy, counted in the same sum (docs/design/22-slot-fork.md)
 int pg_reserve(kr_decode_store* s, int n, const int32_t* slots, const long long* lens, const long long* from, std::vector<KrPageChange>* log) {
     kr_multi_state& M = *s->multi;
     if (!M.pg.paged()) return KR_OK;
-    const size_t before = M.pg_pending.size();
     int need = 0, have = 0;
-    const int bad = M.pg.reserve(n, slots, lens, &M.pg_pending, &need, &have, from);
-    if (bad >= 0)
-        return kr_fail(KR_ERR_STATE, "row %d: slot %d does not fit the page pool: positions [0, %lld) bring the call to %d more pages of %d positions, %d of %d are free",
-                       bad, slots[bad], lens[bad], need, M.pg.page_tokens, have, M.pg.n_pages);
-    if (log) log->insert(log->end(), M.pg_pending.begin() + (ptrdiff_t)before, M.pg_pending.end());
-    return KR_OK;
+    const int bad = M.pg.reserve(n, slots, lens, log, &need, &have, from);
+    if (bad < 0) return KR_OK;
+    return kr_fail(KR_ERR_STATE, "row %d: slot %d does not fit the page pool: positions [0, %lld) bring the call to %d more pages of %d positions, %d of %d are free",
+                   bad, slots[bad], lens[bad], need, M.pg.page_tokens, have, M.pg.n_pages);
 }
-struct Rows;
-int pg_reserve_rows(kr_decode_store* s, const Rows& r, int extra, std::vector<KrPageChange>* log);
 // table entries [lo, hi] of a slot -> the device copy (pageable source: staged before the call returns)
 int pg_upload(kr_multi_state& M, int slot, int lo, int hi, hipStream_t st) {
     const size_t o = (size_t)slot * M.pg.stride + (size_t)lo;
@@ -96,48 +91,33 @@ int pg_upload(kr_multi_state& M, int slot, int lo, int hi, hipStream_t st) {
 // what the host mapped since the last pass -> the device, on the pass's stream ahead of the pass: the changed table entries, then ONE launch that makes the
 // new pages read as zero in every layer's pools, as a freshly created flat slot does, then ONE launch for the pages that start as a copy of another (a fork's
 // boundary page, a private copy of a shared page: written whole by that launch, so not zeroed first).  A copy that reads the page an earlier queued copy
-// writes goes into a launch of its own behind it (kr_page_copy_launches).  A copy's source is held until here; an error leaves everything queued and held
+// writes goes into a launch of its own behind it.  What to send is the pool's plan (flush_plan); sources are held until flushed(): an error leaves all queued and held
 int pg_flush(kr_multi_state& M, hipStream_t st) {
-    if (M.pg_pending.empty()) return KR_OK;
-    std::vector<int32_t> pages, copies[3];      // copies: dst, src, rows
-    std::vector<int> lo((size_t)M.n_slots, INT_MAX), hi((size_t)M.n_slots, -1);
-    for (const KrPageChange& c : M.pg_pending) {
-        if (c.src < 0) pages.push_back(c.page);
-        else { copies[0].push_back(c.page); copies[1].push_back(c.src); copies[2].push_back(c.rows); }
-        lo[(size_t)c.slot] = std::min(lo[(size_t)c.slot], (int)c.idx); hi[(size_t)c.slot] = std::max(hi[(size_t)c.slot], (int)c.idx);
+    if (M.pg.pending.empty()) return KR_OK;
+    const KrPageFlush f = M.pg.flush_plan();
+    for (const KrPageFlush::Range& r : f.ranges) if (int rc = pg_upload(M, r.slot, r.lo, r.hi, st)) return rc;
+    if (!f.zero.empty()) {
+        KR_HIP(hipMemcpyAsync(M.pg_new.p, f.zero.data(), f.zero.size() * 4, hipMemcpyHostToDevice, st));      // pg_new holds n_pages ids, and a page is pending once
+        kr_launch_multi_zero_pages((const KrPagePoolDev*)M.pg_pools.p, M.pg_npools, (const int*)M.pg_new.p, (int)f.zero.size(), st);
     }
-    for (int sl = 0; sl < M.n_slots; sl++) if (hi[(size_t)sl] >= 0) if (int rc = pg_upload(M, sl, lo[(size_t)sl], hi[(size_t)sl], st)) return rc;
-    if (!pages.empty()) {
-        KR_HIP(hipMemcpyAsync(M.pg_new.p, pages.data(), pages.size() * 4, hipMemcpyHostToDevice, st));      // pg_new holds n_pages ids, and a page is pending once
-        kr_launch_multi_zero_pages((const KrPagePoolDev*)M.pg_pools.p, M.pg_npools, (const int*)M.pg_new.p, (int)pages.size(), st);
-    }
-    if (const size_t nc = copies[0].size()) {      // behind the ids to zero: [dst | src | rows], n_pages each (a page is a destination once)
+    if (const size_t nc = f.copies[0].size()) {      // behind the ids to zero: [dst | src | rows], n_pages each (a page is a destination once)
         int32_t* ids = (int32_t*)M.pg_new.p + (size_t)M.pg.n_pages;
-        for (int k = 0; k < 3; k++) KR_HIP(hipMemcpyAsync(ids + (size_t)k * M.pg.n_pages, copies[k].data(), nc * 4, hipMemcpyHostToDevice, st));
+        for (int k = 0; k < 3; k++) KR_HIP(hipMemcpyAsync(ids + (size_t)k * M.pg.n_pages, f.copies[k].data(), nc * 4, hipMemcpyHostToDevice, st));
         size_t c0 = 0;
-        for (size_t end : kr_page_copy_launches(copies[0], copies[1])) {      // one launch, unless a copy reads what an earlier one writes
+        for (size_t end : f.ends) {      // one launch, unless a copy reads what an earlier one writes
             kr_launch_multi_copy_pages((const KrPagePoolDev*)M.pg_pools.p, M.pg_npools, ids + c0, ids + (size_t)M.pg.n_pages + c0, ids + (size_t)2 * M.pg.n_pages + c0, (int)(end - c0),
                                        M.pg.page_tokens, st);
             c0 = end;
         }
     }
     KR_HIP(hipGetLastError());
-    for (int32_t p : copies[1]) M.pg.unhold(p);      // enqueued: what follows on this stream may take the page
-    M.pg_pending.clear();
+    M.pg.flushed();      // enqueued: what follows on this stream may take the copies' sources
     return KR_OK;
 }
-// entries gave their pages back: a mapping of them the device has not seen is dropped with them, and with it the hold on the page it was to copy from
-void pg_prune(kr_multi_state& M) {
-    M.pg_pending.erase(std::remove_if(M.pg_pending.begin(), M.pg_pending.end(), [&](const KrPageChange& c) {
-        if (M.pg.row(c.slot)[c.idx] == c.page) return false;
-        if (c.src >= 0) M.pg.unhold(c.src);
-        return true; }), M.pg_pending.end());
-}
-// pages went back to the pool (freed): pending mappings of them are dropped, and the slots' table rows go to the device
+// pages went back to the pool (freed; the pool has dropped the queued mappings of them): the slots' whole table rows go to the device
 int pg_released(kr_decode_store* s, const std::vector<KrPageChange>& freed) {
     kr_multi_state& M = *s->multi;
     if (freed.empty()) return KR_OK;
-    pg_prune(M);
     KR_HIP(hipSetDevice(s->eng->device));
     std::vector<char> hit((size_t)M.n_slots, 0);
     for (const KrPageChange& c : freed) hit[(size_t)c.slot] = 1;
@@ -364,7 +344,7 @@ int slot_copy(kr_decode_store* s, int slot, int seq_len, bool save) {
     for (size_t i = 0; i < s->layers.size(); i++) {
         DLayer& L = s->layers[i];
         if (paged && (L.attn == ATTN_GQA || L.attn == ATTN_MLA)) {      // page by page; a page that is not mapped reads as zero (load only: save has mapped them)
-            const size_t esz = M.kv_fp8 ? 1 : 2, row[2] = {(L.attn == ATTN_GQA ? (size_t)L.nkv * L.hd : (size_t)L.klr) * esz, (L.attn == ATTN_GQA ? (size_t)L.nkv * L.hd : (size_t)L.rd) * esz};
+            const size_t row[2] = {M.a_row[i], M.b_row[i]};
             for (int j = 0; j < M.pg.pages_of(seq_len); j++) {
                 const int pg = M.pg.row(slot)[j];
                 const size_t r0 = (size_t)j << M.pg.shift, nr = std::min((size_t)M.pg.page_tokens, (size_t)seq_len - r0);
@@ -381,8 +361,7 @@ int slot_copy(kr_decode_store* s, int slot, int seq_len, bool save) {
         char* b = (char*)M.b[i].p + (size_t)slot * M.b_stride[i];
         void *sa, *sb; size_t na, nb;
         if (L.attn == ATTN_LA) { sa = L.conv_state.p; sb = L.recur_state.p; na = M.a_stride[i]; nb = M.b_stride[i]; }
-        else if (L.attn == ATTN_GQA) { sa = L.kv_k.p; sb = L.kv_v.p; na = nb = (size_t)seq_len * L.nkv * L.hd * (M.kv_fp8 ? 1 : 2); }
-        else if (L.attn == ATTN_MLA) { sa = L.kv_k.p; sb = L.kv_v.p; na = (size_t)seq_len * L.klr * (M.kv_fp8 ? 1 : 2); nb = (size_t)seq_len * L.rd * (M.kv_fp8 ? 1 : 2); }
+        else if (L.attn == ATTN_GQA || L.attn == ATTN_MLA) { sa = L.kv_k.p; sb = L.kv_v.p; na = (size_t)seq_len * M.a_row[i]; nb = (size_t)seq_len * M.b_row[i]; }
         else continue;
         if (na) KR_HIP(hipMemcpyAsync(save ? (void*)a : sa, save ? sa : (void*)a, na, hipMemcpyDeviceToDevice, st));
         if (nb) KR_HIP(hipMemcpyAsync(save ? (void*)b : sb, save ? sb : (void*)b, nb, hipMemcpyDeviceToDevice, st));
@@ -644,13 +623,14 @@ static int slots_create(kr_decode_store* s, int n_slots, int max_seq, int page_t
     M->n_slots = n_slots; M->max_seq = max_seq; M->kv_fp8 = s->kv_fp8;
     const size_t nl = s->layers.size(), seq_rows = paged ? (size_t)page_tokens : (size_t)max_seq;      // rows per slot, or per page
     std::vector<KrPagePoolDev> pools, la_pools;
-    M->a.resize(nl); M->b.resize(nl); M->a_stride.assign(nl, 0); M->b_stride.assign(nl, 0);
+    M->a.resize(nl); M->b.resize(nl); M->a_stride.assign(nl, 0); M->b_stride.assign(nl, 0); M->a_row.assign(nl, 0); M->b_row.assign(nl, 0);
     size_t total = 0;
     for (size_t i = 0; i < nl; i++) {
         const DLayer& L = s->layers[i];
         if (L.attn == ATTN_LA) { M->a_stride[i] = (size_t)(2 * L.nk * L.dk + L.nv * L.dv) * L.kd * 4; M->b_stride[i] = (size_t)L.nv * L.dk * L.dv * 4; }
-        else if (L.attn == ATTN_GQA) M->a_stride[i] = M->b_stride[i] = seq_rows * L.nkv * L.hd * (s->kv_fp8 ? 1 : 2);
-        else if (L.attn == ATTN_MLA) { M->a_stride[i] = seq_rows * L.klr * (s->kv_fp8 ? 1 : 2); M->b_stride[i] = seq_rows * L.rd * (s->kv_fp8 ? 1 : 2); }
+        else if (L.attn == ATTN_GQA) M->a_row[i] = M->b_row[i] = (size_t)L.nkv * L.hd * (s->kv_fp8 ? 1 : 2);
+        else if (L.attn == ATTN_MLA) { M->a_row[i] = (size_t)L.klr * (s->kv_fp8 ? 1 : 2); M->b_row[i] = (size_t)L.rd * (s->kv_fp8 ? 1 : 2); }
+        if (L.attn == ATTN_GQA || L.attn == ATTN_MLA) { M->a_stride[i] = seq_rows * M->a_row[i]; M->b_stride[i] = seq_rows * M->b_row[i]; }
         const bool pooled = paged && (L.attn == ATTN_GQA || L.attn == ATTN_MLA);
         for (int h = 0; h < 2; h++) {
             DevBuf& d = h ? M->b[i] : M->a[i];
@@ -781,28 +761,18 @@ extern "C" int kr_decode_slot_fork(kr_decode_store* s, int src, int n_dst, const
     }
     if (seq_len < 0 || seq_len > M.max_seq) return kr_fail(KR_ERR_VALUE, "seq_len %d outside [0, %d] (slot max_seq)", seq_len, M.max_seq);
     const bool paged = M.pg.paged();
-    const int full = paged ? seq_len >> M.pg.shift : 0, part = paged ? seq_len & (M.pg.page_tokens - 1) : 0;      // whole pages below seq_len; rows of the boundary page
-    const int32_t edge = part ? M.pg.row(src)[full] : -1;      // src's boundary page: every dst gets a copy of its own (unmapped: it stays unmapped there too)
     if (paged) {      // all or nothing: the boundary pages, out of the free pages and those the dsts give back
-        const int need = edge >= 0 ? n_dst : 0, gain = M.pg.would_free(n_dst, dsts);
-        if (need > M.pg.n_free + gain)
+        const KrPageFork fit = M.pg.fork_fit(src, n_dst, dsts, seq_len);
+        if (!fit.fits())
             return kr_fail(KR_ERR_STATE, "the fork of slot %d at seq_len %d does not fit the page pool: %d more pages of %d positions, %d of %d are free (%d of them once the dsts are released)",
-                           src, seq_len, need, M.pg.page_tokens, M.pg.n_free + gain, M.pg.n_pages, gain);
+                           src, seq_len, fit.need, M.pg.page_tokens, fit.free + fit.gain, M.pg.n_pages, fit.gain);
     }
     if (M.fk_ids.ensure((size_t)3 * M.n_slots * 4)) return kr_fail(KR_ERR_HIP, "hipMalloc of the fork's slot ids failed");
     KR_HIP(hipSetDevice(s->eng->device));
     KR_HIP(hipDeviceSynchronize());          // steps still in flight on any stream read or write both sides
     hipStream_t st = s->eng->stream;
     if (paged) {
-        for (int i = 0; i < n_dst; i++) M.pg.trim(dsts[i], 0, nullptr);      // what the dsts held, as kr_decode_slot_trim(dst, 0)
-        pg_prune(M);
-        for (int i = 0; i < n_dst; i++) {
-            M.pg.share(src, dsts[i], full);
-            if (edge < 0) continue;
-            M.pg.row(dsts[i])[full] = M.pg.take();
-            M.pg.holds[(size_t)edge]++;
-            M.pg_pending.push_back(KrPageChange{dsts[i], full, M.pg.row(dsts[i])[full], edge, part});
-        }
+        (void)M.pg.fork(src, n_dst, dsts, seq_len);      // the count above again, on the same state: it fits.  The dsts release what they held (as kr_decode_slot_trim(dst, 0)), share, queue their copies
         if (int rc = pg_flush(M, st)) return rc;      // src's own pending pages are zeroed, or copied in an earlier launch, ahead of the boundary copies
         for (int i = 0; i < n_dst; i++) if (int rc = pg_upload(M, dsts[i], 0, M.pg.stride - 1, st)) return rc;
     }
@@ -810,7 +780,7 @@ extern "C" int kr_decode_slot_fork(kr_decode_store* s, int src, int n_dst, const
         const DLayer& L = s->layers[li];
         if (L.attn != ATTN_GQA && L.attn != ATTN_MLA) continue;
         for (int h = 0; h < 2; h++) {
-            const size_t stride = h ? M.b_stride[li] : M.a_stride[li], head = stride / (size_t)M.max_seq * (size_t)seq_len;
+            const size_t stride = h ? M.b_stride[li] : M.a_stride[li], head = (h ? M.b_row[li] : M.a_row[li]) * (size_t)seq_len;
             char* base = (char*)(h ? M.b[li].p : M.a[li].p);
             for (int i = 0; i < n_dst; i++) {
                 char* d = base + (size_t)dsts[i] * stride;

@@ -157,7 +157,7 @@ static int run_layer(kr_decode_store* s, Chunk& cx, size_t li) {
             m.q_norm = L.q_norm_len ? (const float*)L.q_norm.p : nullptr; m.k_norm = L.k_norm_len ? (const float*)L.k_norm.p : nullptr;
             m.q_norm_per_head = L.q_norm_len == L.nh * L.hd; m.k_norm_per_head = L.k_norm_len == L.nkv * L.hd;
             m.rope_cos = (const float*)s->rope_cos.p; m.rope_sin = (const float*)s->rope_sin.p; m.rope_half = s->rope_half;
-            m.k_cache = M.a[li].p; m.v_cache = M.b[li].p; m.slot_elems = M.a_stride[li] / (M.kv_fp8 ? 1 : 2); m.kv_fp8 = M.kv_fp8;
+            m.k_cache = M.a[li].p; m.v_cache = M.b[li].p; m.slot_elems = M.a_row[li] ? M.a_stride[li] / M.a_row[li] * L.nkv * L.hd : 0; m.kv_fp8 = M.kv_fp8;
             m.q_out = B.q; m.gate = B.gate; m.attn_out = B.attn; m.scores = (float*)M.scores.p; m.sc_ld = cx.m_sc_ld;
             if (M.pg.paged()) { m.page_table = (const int*)M.pg_table.p; m.page_stride = M.pg.stride; m.page_shift = M.pg.shift; }      // paged slots: a / b are pools
             m.gated = L.gated; m.nh = L.nh; m.nkv = L.nkv; m.hd = L.hd; m.eps = s->eps; m.sm_scale = L.sm_scale;

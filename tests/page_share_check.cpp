@@ -56,7 +56,7 @@ int main() {
     CHECK(reserve1(p, 3, 40, 50, &log) == -1);
     CHECK((ids(p, 3) == std::vector<int>{0, 5, 4, -1, -1}) && log.size() == 1 && log[0].slot == 3 && log[0].idx == 1 && log[0].page == 5 && log[0].src == 1 && log[0].rows == 32);
     CHECK(p.refs[1] == 2 && p.holds[1] == 1 && p.refs[5] == 1 && p.n_free == 0 && consistent(p));
-    p.unhold(1);      // the copy was enqueued
+    p.flushed();      // the copy was enqueued
     CHECK(p.holds[1] == 0 && p.used[1] && p.n_free == 0 && consistent(p));
 
     // copy-on-write counted in all or nothing: no page is free, slot 0 writing at 10 needs one -> refused, table and counts untouched
@@ -88,7 +88,7 @@ int main() {
     CHECK(reserve1(p, 1, 0, 1, &log) == -1 && p.row(1)[0] == 2 && p.n_free == 1);
     CHECK(reserve1(p, 1, 32, 33, &log) == -1 && p.row(1)[1] == 5 && p.n_free == 0);      // page 1 is passed over
     CHECK(reserve1(p, 1, 64, 65, &log, &need, &have) == 0 && need == 1 && have == 0);
-    p.unhold(1);
+    p.flushed();
     CHECK(!p.used[1] && p.n_free == 1 && consistent(p));
     CHECK(reserve1(p, 1, 64, 65, &log) == -1 && p.row(1)[2] == 1);      // lowest free id first order unchanged
 
@@ -100,7 +100,7 @@ int main() {
     freed.clear();
     p.release_logged(log, 0, 0, &freed);
     CHECK(freed.size() == 2 && p.mapped(0) == 0 && p.refs[0] == 1 && p.row(2)[0] == 0);
-    p.unhold(0);      // the dropped mapping's hold goes with it (pg_prune)
+    CHECK(p.holds[0] == 0 && p.pending.empty());      // the dropped mapping left the queue, and its hold went with it (release_logged prunes)
     CHECK(p.n_free == 5 && consistent(p));
 
     // would_free: the pages a fork may count on when its dsts are released -- a page shared among the dsts alone counts once, one shared with another slot not at all
@@ -133,14 +133,14 @@ int main() {
     {
         KrPagePool q;
         CHECK(q.init(3, 64, 32, 4, 32) == 0);
-        std::vector<KrPageChange> pend;
-        CHECK(reserve1(q, 2, 0, 20, &pend) == -1);
+        const std::vector<KrPageChange>& pend = q.pending;
+        CHECK(reserve1(q, 2, 0, 20, nullptr) == -1);
         q.share(2, 1, 1);
-        CHECK(reserve1(q, 1, 10, 11, &pend) == -1 && pend.size() == 2 && pend[1].src == 0 && pend[1].page == 1);
-        pend.push_back(KrPageChange{0, 0, q.take(), q.row(1)[0], 8}); q.holds[(size_t)q.row(1)[0]]++;      // what a fork of slot 1 queues
-        std::vector<int32_t> dst, src;
-        for (const KrPageChange& c : pend) if (c.src >= 0) { dst.push_back(c.page); src.push_back(c.src); }
-        CHECK((kr_page_copy_launches(dst, src) == std::vector<size_t>{1, 2}));
+        CHECK(reserve1(q, 1, 10, 11, nullptr) == -1 && pend.size() == 2 && pend[1].src == 0 && pend[1].page == 1);
+        const int32_t dsts[1] = {0};
+        CHECK(q.fork(1, 1, dsts, 8).fits() && pend.size() == 3 && pend[2].page == 2 && pend[2].src == 1 && pend[2].rows == 8 && q.holds[1] == 1);      // a fork of slot 1 inside the page
+        const KrPageFlush f = q.flush_plan();
+        CHECK((f.copies[0] == std::vector<int32_t>{1, 2}) && (f.copies[1] == std::vector<int32_t>{0, 1}) && (f.ends == std::vector<size_t>{1, 2}));
     }
 
     // the last holder frees

@@ -65,7 +65,7 @@ def test_the_copy_kernel_sits_beside_the_zero_kernel():
     assert "kr_launch_multi_copy_pages" in open(os.path.join(CSRC, "kr_multi.h")).read()
     # the pass opens with table entries, the zero launch, the copy launch -- in that order
     multi = open(os.path.join(CSRC, "kr_decode_multi.cpp")).read()
-    flush = multi[multi.index("int pg_flush("):multi.index("void pg_prune(")]
+    flush = multi[multi.index("int pg_flush("):multi.index("int pg_released(")]      # to the next function
     assert flush.index("pg_upload(") < flush.index("kr_launch_multi_zero_pages(") < flush.index("kr_launch_multi_copy_pages(")
 
 
@@ -73,6 +73,10 @@ def test_the_allocator_is_still_host_only():
     code = re.sub(r"//.*", "", open(os.path.join(CSRC, "kr_page_pool.h")).read())
     assert "hip" not in code.lower()
     assert "std::vector<int32_t> refs" in code and "void share(int src, int dst, int n_entries)" in code
+    # and it alone keeps the holds, the free list and the queue of mappings the device has not seen: the library calls its members
+    multi = re.sub(r"//.*", "", open(os.path.join(CSRC, "kr_decode_multi.cpp")).read())
+    for word in (".holds[", "pg.take(", "pg_pending"):
+        assert word not in multi, word
 
 
 def test_sharing_program_under_sanitizers(tmp_path):
@@ -89,9 +93,10 @@ def test_sharing_program_under_sanitizers(tmp_path):
 
 
 def test_random_calls_against_a_naive_model_under_sanitizers(tmp_path):
-    """4000 seeded random calls per seed on KrPagePool -- reservations that append, rewind or write nothing, forks, give-backs, trims, release_logged, queued copies
-    let go in and out of order -- beside a naive model (a set of holders per page, lowest free id by linear scan): table, refs, n_free, n_shared and every log agree
-    after each call, and row, need and have on a refusal; random copy queues through kr_page_copy_launches.  tests/page_pool_random_check.cpp with its own main,
+    """4000 seeded random calls per seed on the members of KrPagePool the library calls -- reservations that append, rewind or write nothing, fork, give-backs, trims,
+    release_logged, flush_plan + flushed, give-backs of entries whose copy is still queued -- beside a naive model (a set of holders per page, lowest free id by linear
+    scan, a queue pruned by its own scan): table, refs, holds, n_free, n_shared, the whole queue and every log agree after each call, and row, need and have on a refusal;
+    every flush plan against the model's queue; random copy queues through kr_page_copy_launches.  tests/page_pool_random_check.cpp with its own main,
     compiled alone with -fsanitize=address,undefined and run as a child process (nothing sanitized is loaded into Python)"""
     cxx = shutil.which("g++") or shutil.which("c++")
     assert cxx, "no host C++ compiler"
@@ -101,5 +106,7 @@ def test_random_calls_against_a_naive_model_under_sanitizers(tmp_path):
     for seed in (1, 2, 3):
         run = subprocess.run([exe, "4000", str(seed)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
         assert run.returncode == 0 and "page pool random ok" in run.stdout, (seed, run.stdout)
-        counts = dict(zip(("reserved", "refused", "copies"), map(int, re.search(r"(\d+) reservations, (\d+) refused, (\d+) copy-on-write", run.stdout).groups())))
+        counts = dict(zip(("reserved", "refused", "copies", "forks", "forks_refused", "pruned"), map(int, re.search(
+            r"(\d+) reservations, (\d+) refused, (\d+) copy-on-write copies, (\d+) forks, (\d+) refused, (\d+) queue entries pruned", run.stdout).groups())))
         assert counts["refused"] >= 100 and counts["copies"] >= 50 and counts["refused"] < counts["reserved"] // 2, counts      # the run reached what it is about
+        assert counts["forks"] >= 300 and counts["forks_refused"] >= 1 and counts["pruned"] >= 20, counts
