@@ -266,6 +266,9 @@ int kr_decode_set_kv_dtype(kr_decode_store* s, int kv_dtype);
 int kr_decode_set_attention_mode(kr_decode_store* s, int mode);
 /* Options by name.  Test / tuning hooks: "gqa_stream", "pfm_timing", ... (see kr_decode.cpp); "multi_attn_fast": see kr_decode_step_multi;
  * "multi_attn_fast_paged" (default 0; docs/design/23-multi-attn-fast-paged.md): "multi_attn_fast" for flat and paged slots alike, see kr_decode_step_multi.
+ * "multi_mla_fast" (default 0; docs/design/24-multi-mla-fast.md): the MLA layers of every batched entry point run split-KV flash-decode over slots of
+ * max_seq > 512, flat or paged: row i carries the bits of kr_decode_step under KR_ATTN_FAST on that sequence alone; shorter slots keep the exact step.
+ * Refused on a store without MLA layers (KR_ERR_STATE) and on MLA layers of more than 64 heads (KR_ERR_VALUE); see kr_decode_step_multi.
  * "gguf_exact_pass" (default 0; docs/design/20-gguf-exact-pass.md): with 1, every multi-row pass of the store -- kr_decode_prefill, kr_decode_prefill_nll,
  * kr_decode_verify and the batched pass behind every slot entry point -- runs MoE layers that hold native GGUF blocks through the exact grouped block
  * kernels (kr_gguf_group.hip) instead of the int8-MFMA form: every row then carries the bits of kr_decode_step on that sequence alone, and the slot and
@@ -381,7 +384,15 @@ int kr_decode_slot_load(kr_decode_store* s, int slot, int seq_len);
    slots of max_seq > 1024 the flash-decode reads the pools through the slots' page tables and row i carries the bits of the same call on flat slots of
    the same n_slots and max_seq under "multi_attn_fast", for any page_tokens, any placement of the pages and pages shared by kr_decode_slot_fork; paged
    slots of max_seq <= 1024 keep the exact paged step; on flat slots it is "multi_attn_fast"; with both set it governs.  Its refusals are those of
-   "multi_attn_fast", and the page pool behaves as without it. */
+   "multi_attn_fast", and the page pool behaves as without it.
+   kr_decode_set_option(s, "multi_mla_fast", 1) (default 0; docs/design/24-multi-mla-fast.md) is the counterpart for MLA layers, one option for flat and
+   paged slots: over slots of max_seq > 512 the MLA layers of every batched entry point run split-KV flash-decode on the f16 matrix cores (through the
+   page tables on paged slots, pages shared by kr_decode_slot_fork included) and row i carries the bits of kr_decode_step under KR_ATTN_FAST on that
+   sequence alone -- logits, id, the appended latent and rope-key rows, sampler state -- provided the store's kv_max_seq and the slots' max_seq are on the
+   same side of 16 384 positions (64-position chunks up to there, 128 above); logits within 3e-3 (FP16 caches) / 5e-3 (E4M3) of the exact step,
+   relative to their largest magnitude.  Slots of max_seq <= 512 keep the exact step, and GQA and linear-attention layers are not touched.  Refused,
+   naming "multi_mla_fast": a store without an MLA layer (KR_ERR_STATE); an MLA layer of more than 64 heads or outside kv_lora_rank 512 / 256 with
+   rope 64, and a position that needs more than 1024 chunks (KR_ERR_VALUE).  Everything the step refuses without the option stays refused first. */
 int kr_decode_step_multi(kr_decode_store* s, int n, const int32_t* slots, const int32_t* tokens, const int32_t* positions,
                          int32_t* next_out, float* logits_out, void* stream);
 /* greedy generation of n slots together.  Row i's tokens_out[i*max_tokens ...], n_out[i] and its slot's state afterwards are exactly those of

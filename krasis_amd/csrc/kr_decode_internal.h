@@ -51,6 +51,7 @@ struct kr_multi_state {
     DevBuf la_pools, fk_ids; int la_npools = 0;
     DevBuf rows, ids, logits, scores, scratch; // step: [slots | tokens | positions] (device), greedy ids, [n][vocab] logits, attention scores, the arena
     DevBuf fd_o, fd_ml; bool fd_ready = false; // "multi_attn_fast": split-KV partials [n][nkv][chunks][G][hd] and (max, sum) [n][nh][chunks][2] of one GQA layer, sized by the step's longest row; the kernels' LDS windows are raised
+    bool mla_fd_ready = false;                 // "multi_mla_fast": the partials of one MLA layer, [n][chunks][nh][klr] and [n][nh][chunks][2], share fd_o / fd_ml (sized for the larger need); the kernels' LDS windows are raised
     // per-slot samplers (kr_decode_slot_sampler, docs/design/14-multi-sampling.md): allocated for every slot on the first call; empty = every slot greedy
     struct Sampler { float temperature = 0.0f, top_p = 1.0f, penalty = 0.0f; int top_k = 0; };
     std::vector<Sampler> smp; size_t smp_words = 0;   // host: parameters per slot; seen-bitmap words per slot
@@ -94,6 +95,7 @@ struct kr_decode_store {
     int opt_gguf_exact_grouped = 1;              // ... 0 = through the streaming kernels for every block type (A/B and test hook; same bits)
     int opt_multi_attn_fast_paged = 0;           // kr_decode_set_option("multi_attn_fast_paged"): "multi_attn_fast" over flat and paged slots alike, the split-KV kernels of paged slots read the pools through the page table (docs/design/23-multi-attn-fast-paged.md); governs when both are set
     int opt_multi_attn_fast = 0;                 // kr_decode_set_option("multi_attn_fast"): the GQA layers of every batched multi-sequence step run split-KV flash-decode over slots longer than gqa_split_min (tolerance form, docs/design/16-multi-attn-fast.md); the mode bits stay refused
+    int opt_multi_mla_fast = 0;                  // kr_decode_set_option("multi_mla_fast"): the MLA layers of every batched multi-sequence step run split-KV flash-decode over slots longer than mla_split_min, flat or paged (tolerance form, docs/design/24-multi-mla-fast.md); the mode bits stay refused
     int opt_gen_lookahead = 0;                    // kr_decode_set_option("generate_lookahead"): generate_batch feeds the sampled token back ON THE DEVICE and queues step i + 1 before the host has read token i
     int opt_ep_graph = 0;                         // kr_decode_set_option("ep_graph"): expert-parallel decode over RCCL replays a captured graph (the all-reduce is captured with the kernels)
     uint64_t ep_generation_seen = 0;               // kr_engine::ep_generation at the last step: a new / destroyed communicator invalidates the graph and restarts the warm-up

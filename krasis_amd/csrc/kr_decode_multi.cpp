@@ -140,6 +140,8 @@ int check_args(kr_decode_store* s, const Rows& r, int extra) {
     std::vector<char> seen((size_t)M.n_slots, 0);
     int mla_rope = 0; bool has_mla = false;
     for (const DLayer& L : s->layers) if (L.attn == ATTN_MLA) { mla_rope = has_mla ? std::min(mla_rope, L.mla_rope_seq) : L.mla_rope_seq; has_mla = true; }
+    // "multi_mla_fast" over long slots: the merge has one thread per chunk (kr_multi_pass takes the same chunk size)
+    const int mla_chunk = s->opt_multi_mla_fast && has_mla && M.max_seq > s->mla_split_min ? kr_mla_flash_decode_chunk(M.max_seq) : 0;
     int total = 0;
     for (int i = 0; i < r.n; i++) {      // the runs first: everything below indexes tokens by them
         if (r.cnt(i) < 1) return kr_fail(KR_ERR_VALUE, "row %d: a run of %d tokens, must be at least 1", i, r.cnt(i));
@@ -161,6 +163,8 @@ int check_args(kr_decode_store* s, const Rows& r, int extra) {
         if (pos < 0 || last >= M.max_seq) return kr_fail(KR_ERR_VALUE, "row %d: positions [%d, %lld] outside the slot's [0, %d)", i, pos, last, M.max_seq);
         if (s->max_rope_seq > 0 && last >= s->max_rope_seq) return kr_fail(KR_ERR_VALUE, "row %d: position %lld past the rope table (%d)", i, last, s->max_rope_seq);
         if (has_mla && last >= mla_rope) return kr_fail(KR_ERR_VALUE, "row %d: position %lld past the MLA rope table (%d)", i, last, mla_rope);
+        if (mla_chunk && last / mla_chunk >= 1024)
+            return kr_fail(KR_ERR_VALUE, "row %d: multi_mla_fast: position %lld needs %lld chunks of %d positions (at most 1024)", i, last, last / mla_chunk + 1, mla_chunk);
     }
     return KR_OK;
 }

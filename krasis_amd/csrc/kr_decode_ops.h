@@ -60,6 +60,7 @@ struct KrMlaArgs {   // decode.rs:2993-3252
 void kr_launch_mla(const KrMlaArgs& a, int max_seq, hipStream_t s, int n_tok = 1);
 void kr_launch_mla_wvc(const KrMlaArgs& a, hipStream_t s, int n_tok);   // launch 3 alone, token dimension (a.step == nullptr): the multi-sequence step below 32 rows
 size_t kr_mla_flash_decode_chunks(int max_seq);   // chunks of the FAST split-KV decode (sizes the partial buffers)
+int kr_mla_flash_decode_chunk(int max_seq);       // ... and the positions of one: 64 up to 16 384 positions, 128 above
 void kr_mla_attn_prepare(const KrMlaArgs& a, int max_seq);   // outside graph capture: LDS window of the staged attention kernel
 void kr_launch_rmsnorm_seq(float* x, const float* w, int n, float eps, hipStream_t s, int rows = 1, int ld = 0);
 

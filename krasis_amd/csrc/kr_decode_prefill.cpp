@@ -42,6 +42,7 @@ struct Chunk {      // one chunk of the prompt in flight: its arena, stream and 
     KrPfSync sy;      // this (chunk, layer)'s hand-overs with the previous / next chunk (set by the scheduler before every run_layer)
     bool verify = false;      // kr_decode_verify's pass: linear-attention layers write their recurrence inputs into the store's verify buffers (kr_spec.h)
     const int32_t* m_slots = nullptr; const int32_t* m_pos = nullptr; int m_sc_ld = 0; int m_fd_chunk = 0, m_fd_chunks = 0;   // the multi-sequence step: row b = slot m_slots[b] at m_pos[b] (device)
+    int m_mla_chunk = 0, m_mla_chunks = 0;      // ... "multi_mla_fast", long slots: positions per chunk of the MLA flash-decode and the longest row's chunk count (0: the exact kernel)
     const int32_t* m_runs = nullptr; int m_nruns = 0;      // ... and m_nruns x [slot, off, cnt] (device), the runs of token rows per slot (kr_multi.h); set whenever m_slots is
     bool m_verify = false;      // kr_decode_verify_multi's pass: linear-attention layers record instead of storing state (docs/design/18-multi-verify.md)
 };
@@ -219,6 +220,7 @@ static int run_layer(kr_decode_store* s, Chunk& cx, size_t li) {
             m.q_abs = B.q; m.q_pe = B.z; m.attn_lat = B.recur; m.v_proj = B.attn; m.scores = (float*)M.scores.p; m.sc_ld = cx.m_sc_ld;
             m.nh = L.nh; m.klr = L.klr; m.nd = L.nd; m.rd = L.rd; m.vhd = L.vhd; m.eps = s->eps; m.sm_scale = L.sm_scale;
             if (M.pg.paged()) { m.page_table = (const int*)M.pg_table.p; m.page_stride = M.pg.stride; m.page_shift = M.pg.shift; }      // paged slots: the strides are a page's bytes
+            if (cx.m_mla_chunks) { m.fd_o = (float*)M.fd_o.p; m.fd_ml = (float*)M.fd_ml.p; m.fd_chunk = cx.m_mla_chunk; m.fd_chunks = cx.m_mla_chunks; }      // "multi_mla_fast", long slots
             if (nkv < L.klr + L.rd) return kr_fail(KR_ERR_VALUE, "kv_a_proj rows %d < kv_lora_rank + rope dim", nkv);
             if (oc != L.nh * L.vhd) return kr_fail(KR_ERR_VALUE, "o_proj cols %d != nh*v_head_dim", oc);
             if (kr_launch_multi_mla(m, Cc, st)) return kr_fail(KR_ERR_VALUE, "unsupported MLA geometry for the multi-sequence step");
@@ -622,6 +624,19 @@ int kr_exact_refuse(kr_decode_store* s, bool slots) {
         if (slots && L.attn == ATTN_GQA && ((L.hd != 64 && L.hd != 128 && L.hd != 256) || L.nkv < 1 || L.nh % L.nkv || (L.nh / L.nkv) * (L.hd + 64) > 12288))
             return kr_fail(KR_ERR_VALUE, "%s: GQA geometry nh %d nkv %d head_dim %d not covered (head_dim 64 / 128 / 256)", what, L.nh, L.nkv, L.hd);
     }
+    // "multi_mla_fast", behind everything the step refused before the option existed.  A store without an MLA layer: an option that silently does nothing is a
+    // trap.  More than 64 heads, or a geometry outside the flash kernel's: the single-sequence launcher falls back to the exact kernels there
+    // (kr_launch_mla_flash_decode), so there would be no fast step to be identical to
+    if (slots && s->opt_multi_mla_fast) {
+        bool mla = false;
+        for (const DLayer& L : s->layers) {
+            if (L.attn != ATTN_MLA) continue;
+            mla = true;
+            if (!kr_multi_mla_fd_ok(L.nh, L.klr, L.rd))
+                return kr_fail(KR_ERR_VALUE, "multi_mla_fast: MLA geometry heads %d kv_lora_rank %d rope %d not covered (at most 64 heads, kv_lora_rank 512 / 256, rope 64)", L.nh, L.klr, L.rd);
+        }
+        if (!mla) return kr_fail(KR_ERR_STATE, "the \"multi_mla_fast\" option covers MLA layers only: this store has none (set the option to 0 for the exact step)");
+    }
     return KR_OK;
 }
 int kr_spec_refuse(kr_decode_store* s) { return kr_exact_refuse(s, false); }
@@ -731,17 +746,22 @@ int kr_multi_pass(kr_decode_store* s, int n, int n_final, const int32_t* d_rows,
     kr_multi_state& M = *s->multi;
     PfLayout Lo;
     if (int rc = pf_layout(s, (size_t)n, true, true, st, Lo)) return rc;
-    int nh_max = 1; size_t gqa_row = 0; bool has_gqa = false, has_mla = false;
+    int nh_max = 1; size_t gqa_row = 0, mla_row = 0; bool has_gqa = false, has_mla = false;
     for (const DLayer& L : s->layers) {
         if (L.attn == ATTN_GQA || L.attn == ATTN_MLA) nh_max = std::max(nh_max, L.nh);      // a score row per query head of either kind
         if (L.attn == ATTN_GQA) { has_gqa = true; gqa_row = std::max(gqa_row, (size_t)L.nh * L.hd); }
-        has_mla |= L.attn == ATTN_MLA;
+        if (L.attn == ATTN_MLA) { has_mla = true; mla_row = std::max(mla_row, (size_t)L.nh * L.klr); }
     }
     // "multi_attn_fast": over slots longer than gqa_split_min (the capacity rule of the store's own KR_ATTN_FAST step) every GQA layer takes the split-KV
     // flash-decode; the partials are sized by this step's longest row, and the score rows are not needed unless another kind of layer reads them
     // "multi_attn_fast_paged": the same over flat and paged slots; paged ones read through the table (docs/design/23-multi-attn-fast-paged.md)
     const bool flash = (s->opt_multi_attn_fast || s->opt_multi_attn_fast_paged) && has_gqa && M.max_seq > s->gqa_split_min;
-    int fd_chunk = 0, fd_chunks = 0;
+    // "multi_mla_fast": the same for every MLA layer over slots longer than mla_split_min, flat or paged (docs/design/24-multi-mla-fast.md).  Its chunks are
+    // kr_mla_flash_decode_chunk's (64 / 128 positions against the GQA kernels' 128 / 256), so both counts travel with the pass; the partials of the two kinds
+    // of layer share M.fd_o / M.fd_ml, sized for the larger need
+    const bool mla_flash = s->opt_multi_mla_fast && has_mla && M.max_seq > s->mla_split_min;
+    int fd_chunk = 0, fd_chunks = 0, mla_chunk = 0, mla_chunks = 0;
+    size_t fd_o_bytes = 0, fd_ml_bytes = 0;
     if (flash) {
         fd_chunk = kr_fd_flash_chunk(M.max_seq); fd_chunks = (max_pos + fd_chunk) / fd_chunk;
         if (fd_chunks > 1024) return kr_fail(KR_ERR_VALUE, "multi_attn_fast: position %d needs %d chunks of %d positions (at most 1024)", max_pos, fd_chunks, fd_chunk);
@@ -753,10 +773,22 @@ int kr_multi_pass(kr_decode_store* s, int n, int n_final, const int32_t* d_rows,
             }
             M.fd_ready = true;
         }
-        if (M.fd_o.ensure((size_t)n * fd_chunks * gqa_row * 4) || M.fd_ml.ensure((size_t)n * nh_max * fd_chunks * 8))
-            return kr_fail(KR_ERR_HIP, "hipMalloc of the multi-sequence step's split-KV partials (%zu MiB) failed", ((size_t)n * fd_chunks * (gqa_row * 4 + nh_max * 8)) >> 20);
+        fd_o_bytes = (size_t)n * fd_chunks * gqa_row * 4; fd_ml_bytes = (size_t)n * nh_max * fd_chunks * 8;
     }
-    const bool need_scores = (has_gqa && !flash) || has_mla;
+    if (mla_flash) {
+        mla_chunk = kr_mla_flash_decode_chunk(M.max_seq); mla_chunks = (max_pos + mla_chunk) / mla_chunk;
+        if (mla_chunks > 1024) return kr_fail(KR_ERR_VALUE, "multi_mla_fast: position %d needs %d chunks of %d positions (at most 1024)", max_pos, mla_chunks, mla_chunk);
+        if (!M.mla_fd_ready) {
+            for (const DLayer& L : s->layers)
+                if (L.attn == ATTN_MLA && kr_multi_mla_fd_prepare(L.klr, M.kv_fp8, M.pg.paged()))
+                    return kr_fail(KR_ERR_HIP, "multi_mla_fast: LDS window of the flash-decode kernel refused (kv_lora_rank %d)", L.klr);
+            M.mla_fd_ready = true;
+        }
+        fd_o_bytes = std::max(fd_o_bytes, (size_t)n * mla_chunks * mla_row * 4); fd_ml_bytes = std::max(fd_ml_bytes, (size_t)n * nh_max * mla_chunks * 8);
+    }
+    if ((flash || mla_flash) && (M.fd_o.ensure(fd_o_bytes) || M.fd_ml.ensure(fd_ml_bytes)))
+        return kr_fail(KR_ERR_HIP, "hipMalloc of the multi-sequence step's split-KV partials (%zu MiB) failed", (fd_o_bytes + fd_ml_bytes) >> 20);
+    const bool need_scores = (has_gqa && !flash) || (has_mla && !mla_flash);
     const int sc_ld = (max_pos + 1 + 31) & ~31;
     const int n_logits = verify ? n : n_final;      // a verify pass: the lm_head over every token row (what Chunk::verify is to the store's own pass)
     if (M.scratch.ensure(Lo.total) || (need_scores && M.scores.ensure((size_t)n * nh_max * sc_ld * 4)) || M.logits.ensure((size_t)n_logits * s->vocab * 4))
@@ -765,6 +797,7 @@ int kr_multi_pass(kr_decode_store* s, int n, int n_final, const int32_t* d_rows,
     cx.B = pf_carve(Lo, (char*)M.scratch.p); cx.scores = nullptr; cx.tok = d_rows + n; cx.Cc = n; cx.pos0 = 0; cx.set = KR_PF_MAX_DEPTH - 1;
     cx.first = true; cx.add_is_emb = true; cx.st = st;
     cx.m_slots = d_rows; cx.m_pos = d_rows + 2 * n; cx.m_sc_ld = sc_ld; cx.m_fd_chunk = fd_chunk; cx.m_fd_chunks = fd_chunks;
+    cx.m_mla_chunk = mla_chunk; cx.m_mla_chunks = mla_chunks;
     cx.m_runs = d_runs; cx.m_nruns = n_final; cx.m_verify = verify;
     for (size_t l = 0; l < s->layers.size(); l++)
         if (int rc = run_layer(s, cx, l)) return rc;

@@ -84,11 +84,21 @@ struct KrMultiMlaArgs {
     int absorb_done;                           // set by the launch: q_abs came from the matrix-core absorption, the prep launch skips its tiles
     // paged slots, as KrMultiGqaArgs: ckv_cache / kpe_cache are pools [n_pages][1 << page_shift][klr] / [..][rd]; a stage of KR_MM_ROWS rows lies in one page
     const int* page_table; int page_stride, page_shift;
+    // "multi_mla_fast" (kr_multi_mla_flash.hip, docs/design/24-multi-mla-fast.md): split-KV partials [B][fd_chunks][nh][klr] and (max, sum) [B][nh][fd_chunks][2];
+    // fd_chunk positions per chunk, fd_chunks = the longest row's chunk count.  Null: the exact per-slot kernel (scores is not read when they are set).  With
+    // page_table set the chunk pass reads the pools through the table
+    float *fd_o, *fd_ml; int fd_chunk, fd_chunks;
 };
 // the geometries the per-slot MLA kernels are specialised for (klr 512 / 256 with rd 64; nd within the prep launch's LDS row)
 int kr_multi_mla_ok(int klr, int nd, int rd);
-// 0: launched (absorption, prep, attention, w_vc projection); 1: geometry not covered
+// 0: launched (absorption, prep, attention -- the flash-decode pair when a.fd_o is set --, w_vc projection); 1: geometry not covered
 int kr_launch_multi_mla(const KrMultiMlaArgs& a, int B, hipStream_t st);
+// the flash-decode form of the attention launch (after the prep launch): geometry test (at most 64 heads = one query tile), the LDS window of its kernel
+// (once per slot set, outside the pass; non-zero = refused; every instantiation is a kernel of its own), the chunk pass + merge over a.fd_chunks chunks
+// (0: launched; a.page_table set: through the table)
+int kr_multi_mla_fd_ok(int nh, int klr, int rd);
+int kr_multi_mla_fd_prepare(int klr, int fp8, int paged);
+int kr_launch_multi_mla_fd(const KrMultiMlaArgs& a, int B, hipStream_t st);
 
 // paged slots: the pools of every layer, and the launch that makes freshly mapped pages read as zero in all of them -- grid (n_pages, n_pools), one launch per pass
 #define KR_PAGE_MIN_TOKENS 32      // = KR_MM_ROWS (kr_multi.hip): a stage of the MLA attention kernel never straddles a page

@@ -625,16 +625,22 @@ int kr_launch_multi_mla(const KrMultiMlaArgs& a_in, int B, hipStream_t st) {
     if (!kr_multi_mla_ok(a.klr, a.nd, a.rd) || a.nh < 1 || a.sc_ld % 32) return 1;
     if (a.page_table && (a.page_stride < 1 || (1 << a.page_shift) < KR_MM_ROWS)) return 1;      // a stage must not straddle a page
     static_assert(kr_multi_mla_lds<false, 64>() <= 64 * 1024, "the attention kernel stays inside the default 64 KiB LDS window");
+    // "multi_mla_fast" (a.fd_o set): the same absorption and prep launch, then split-KV flash-decode over the slots, flat or paged
+    // (kr_multi_mla_flash.hip) in place of the attention kernel; checked before anything is launched
+    if (a.fd_o && (!kr_multi_mla_fd_ok(a.nh, a.klr, a.rd) || !a.fd_ml || a.fd_chunk < 32 || a.fd_chunk % 32 || a.fd_chunks < 1 || a.fd_chunks > 1024)) return 1;
     // the w_kc absorption, row-wise: from 32 rows on the matrix cores (one fma chain per output, the prompt pass's launch), the prep launch's tiles below
     a.absorb_done = B >= 32 && kr_launch_mla_absorb_mfma(a.q_full, a.ld_q, a.nd + a.rd, a.nd, a.w_kc, a.klr, a.q_abs, B, a.nh, st) == 0;
     const dim3 pg(a.nh * (a.absorb_done ? 1 : a.klr / 64) + 1, B), ag((a.nh + KR_MM_HG - 1) / KR_MM_HG, B);
+#define KR_MMP(F_, P_) hipLaunchKernelGGL((kr_multi_mla_prep_kernel<F_, P_>), pg, dim3(64), 0, st, a)
 #define KR_MMA(F_, NBC_, P_) hipLaunchKernelGGL((kr_multi_mla_attn_kernel<F_, NBC_, P_>), ag, dim3(512), (kr_multi_mla_lds<F_, NBC_>()), st, a)
 #define KR_MMA_ALL(P_) do { \
-    if (a.kv_fp8) { hipLaunchKernelGGL((kr_multi_mla_prep_kernel<true, P_>), pg, dim3(64), 0, st, a); if (a.klr == 512) KR_MMA(true, 64, P_); else KR_MMA(true, 32, P_); } \
-    else { hipLaunchKernelGGL((kr_multi_mla_prep_kernel<false, P_>), pg, dim3(64), 0, st, a); if (a.klr == 512) KR_MMA(false, 64, P_); else KR_MMA(false, 32, P_); } } while (0)
+    if (a.kv_fp8) { KR_MMP(true, P_); if (a.fd_o) break; if (a.klr == 512) KR_MMA(true, 64, P_); else KR_MMA(true, 32, P_); } \
+    else { KR_MMP(false, P_); if (a.fd_o) break; if (a.klr == 512) KR_MMA(false, 64, P_); else KR_MMA(false, 32, P_); } } while (0)
     if (a.page_table) KR_MMA_ALL(true); else KR_MMA_ALL(false);
 #undef KR_MMA_ALL
 #undef KR_MMA
+#undef KR_MMP
+    if (a.fd_o && kr_launch_multi_mla_fd(a, B, st)) return 1;
     // the w_vc projection, row-wise: the prompt pass's matrix-core launch from 32 rows, the decode launch with a token dimension below
     if (B >= 32 && kr_launch_mla_wvc_mfma(a.w_vc, a.attn_lat, a.v_proj, B, a.nh, a.vhd, a.klr, st) == 0) return 0;
     KrMlaArgs m{};

@@ -304,6 +304,10 @@ class CpuDecodeStore:
         "multi_attn_fast" alone reads flat slots only and is refused on paged ones; "multi_attn_fast_paged" (default 0) is the same option for both
         kinds: on paged slots the flash-decode reads the page pool through the slots' tables, row i bit-identical to the same call on flat slots
         under "multi_attn_fast"; on flat slots it is "multi_attn_fast"; with both set it governs (docs/design/23-multi-attn-fast-paged.md).
+        "multi_mla_fast" (default 0): the counterpart for MLA layers, one option for flat and paged slots -- with 1 the MLA layers of every batched call
+        run split-KV flash-decode over slots of max_seq > 512, row i bit-identical to decode_step under set_attention_mode(True) on that sequence alone;
+        shorter slots keep the exact step; GQA and linear-attention layers are untouched; a store without MLA layers, or an MLA layer of more than 64
+        heads, is then refused by the batched calls (docs/design/24-multi-mla-fast.md).
         "gguf_exact_pass" (default 0): with 1 every multi-row pass (prefill, prefill_nll, verify, and the batched pass behind every slot call) runs
         native-GGUF MoE layers through the exact grouped block kernels -- every row carries the bits of decode_step on that sequence alone -- and the
         slot and speculation calls accept a store with such layers; slower than the default int8-MFMA form on long prompts; refused together with
@@ -421,7 +425,8 @@ class CpuDecodeStore:
         With page_tokens and n_pages (kr_decode_slots_create_paged, docs/design/21-paged-slots.md) the GQA / MLA rows live in a pool of n_pages pages of
         page_tokens positions (a power of two, at least 32) shared by all slots: same results bit for bit, capacity bounded by the pool; a call that
         needs more pages than are free fails with KR_ERR_STATE and changes nothing.  Of the two split-KV options, paged slots take
-        "multi_attn_fast_paged"; "multi_attn_fast" alone is refused on them (set_option)."""
+        "multi_attn_fast_paged"; "multi_attn_fast" alone is refused on them (set_option).  "multi_mla_fast", the split-KV option of MLA layers, reads flat
+        and paged slots alike (over slots of max_seq > 512)."""
         self._need()
         if (page_tokens is None) != (n_pages is None):
             raise ValueError("create_slots: page_tokens and n_pages go together")
@@ -481,7 +486,10 @@ class CpuDecodeStore:
         (logits, id, the KV row -- or MLA latent and rope-key rows -- it appends to the slot).  Returns the greedy ids, or (ids, logits f32 [n, vocab]) with logits=True.
         After set_option("multi_attn_fast", 1), over slots of max_seq > 1024: row i is bit-identical to decode_step under set_attention_mode(True) on that
         sequence alone instead (GQA attention as split-KV flash-decode; logits within 1e-3 of the exact step relative to their largest magnitude).
-        On paged slots that takes set_option("multi_attn_fast_paged", 1), which gives the same bits through the page table."""
+        On paged slots that takes set_option("multi_attn_fast_paged", 1), which gives the same bits through the page table.
+        After set_option("multi_mla_fast", 1), over flat or paged slots of max_seq > 512, the same holds for MLA layers: their attention runs as split-KV
+        flash-decode and row i is bit-identical to decode_step under set_attention_mode(True) on that sequence alone (logits within 3e-3 of the exact
+        step with FP16 caches, 5e-3 with E4M3, relative to their largest magnitude)."""
         return self._step_multi(self._lib.kr_decode_step_multi, slots, None, tokens, positions, logits)
 
     def _step_multi(self, entry, slots, counts, tokens, positions, logits, *flags):
