@@ -269,6 +269,16 @@ int kr_decode_set_attention_mode(kr_decode_store* s, int mode);
  * "multi_mla_fast" (default 0; docs/design/24-multi-mla-fast.md): the MLA layers of every batched entry point run split-KV flash-decode over slots of
  * max_seq > 512, flat or paged: row i carries the bits of kr_decode_step under KR_ATTN_FAST on that sequence alone; shorter slots keep the exact step.
  * Refused on a store without MLA layers (KR_ERR_STATE) and on MLA layers of more than 64 heads (KR_ERR_VALUE); see kr_decode_step_multi.
+ * "multi_extend_flash" (default 0; docs/design/25-multi-extend-flash.md): in a non-verify batched pass (kr_decode_extend_multi) the GQA layers give every run of
+ * counts[i] >= 2 tokens causal flash attention over its slot, flat or paged, on the f16 matrix cores: run i carries the bits of kr_decode_prefill(tokens,
+ * positions[i]) under KR_ATTN_FAST on a store whose attention layers are all GQA and whose own sequence holds the same prefix -- the last token's logits and id
+ * and every K / V row the run appends -- whatever other rows share the pass; the slot's cache is streamed once per query tile of 128 / (heads per KV head)
+ * tokens instead of once per token, and no score scratch is needed for those rows.  Runs of one token (kr_decode_step_multi*, kr_decode_generate_multi*, decode
+ * rows of a mixed pass) keep exactly what they had, verify passes are untouched, linear-attention layers stay exact (a hybrid store: within 3e-3 of the exact
+ * run, docs/design/02-numerics.md 2b).  Consequence: under the option a token's bits depend on whether it entered in a run of >= 2 tokens or alone -- as the
+ * store's KR_ATTN_FAST prompt pass differs from its decode step; among cuts of >= 2 tokens each the result does not depend on the cut.  Refused by every batched
+ * entry point, behind everything they refused before, each message naming the option: a store with an MLA layer or without a GQA layer (KR_ERR_STATE), a GQA
+ * layer outside the prompt pass's flash kernels -- heads per KV head must divide 128, head_dim 64 / 128 / 256 -- (KR_ERR_VALUE), an LDS window refusal (KR_ERR_HIP).
  * "gguf_exact_pass" (default 0; docs/design/20-gguf-exact-pass.md): with 1, every multi-row pass of the store -- kr_decode_prefill, kr_decode_prefill_nll,
  * kr_decode_verify and the batched pass behind every slot entry point -- runs MoE layers that hold native GGUF blocks through the exact grouped block
  * kernels (kr_gguf_group.hip) instead of the int8-MFMA form: every row then carries the bits of kr_decode_step on that sequence alone, and the slot and

@@ -296,7 +296,7 @@ int step_impl(kr_decode_store* s, const Rows& r, int32_t* next_out, float* logit
     if (int rc = open_pass(s, r, sample, false, st, p)) return rc;
     const bool greedy = p.sr.empty();
     if (!greedy) KR_HIP(hipMemcpyAsync(M.smp_rows.p, p.sr.data(), p.sr.size() * sizeof(KrMsRow), hipMemcpyHostToDevice, st));
-    if (int rc = kr_multi_pass(s, (int)p.T, n, (const int32_t*)M.rows.p, (const int32_t*)M.rows.p + 3 * p.T, p.max_pos, st)) return fail_pass(st, rc);
+    if (int rc = kr_multi_pass(s, (int)p.T, n, (const int32_t*)M.rows.p, (const int32_t*)M.rows.p + 3 * p.T, p.max_pos, st, false, r.counts, r.positions)) return fail_pass(st, rc);
     const size_t V = (size_t)s->vocab;
     if (greedy) kr_launch_multi_argmax((const float*)M.logits.p, V, (int)V, n, (int*)M.ids.p, st);
     else if (kr_launch_multi_sample(sampler_args(M, (const float*)M.logits.p, s->vocab, n, p.sr, (uint32_t*)M.smp_seen.p, M.smp_words, (uint64_t*)M.smp_rng.p, (int*)M.ids.p), st))

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/krasis_hip.h"
+#include "kr_pf_tiles.h"
 #include "kr_decode_internal.h"
 #include "kr_prefill.h"
 #include "kr_prefill_ops.h"
@@ -44,9 +45,13 @@ struct Chunk {      // one chunk of the prompt in flight: its arena, stream and 
     const int32_t* m_slots = nullptr; const int32_t* m_pos = nullptr; int m_sc_ld = 0; int m_fd_chunk = 0, m_fd_chunks = 0;   // the multi-sequence step: row b = slot m_slots[b] at m_pos[b] (device)
     int m_mla_chunk = 0, m_mla_chunks = 0;      // ... "multi_mla_fast", long slots: positions per chunk of the MLA flash-decode and the longest row's chunk count (0: the exact kernel)
     const int32_t* m_runs = nullptr; int m_nruns = 0;      // ... and m_nruns x [slot, off, cnt] (device), the runs of token rows per slot (kr_multi.h); set whenever m_slots is
+    // ... "multi_extend_flash", a pass with a run of >= 2 tokens: the query tiles [run, t0] of its runs (device), one table per tile width 1 << w tokens at
+    // entry m_pf_off[w] with m_pf_n[w] tiles (kr_pf_tiles.h); m_pf_units = its runs of one token.  Null: every row takes the per-row attention kernels
+    const int32_t* m_pf_tiles = nullptr; int m_pf_off[8] = {0, 0, 0, 0, 0, 0, 0, 0}, m_pf_n[8] = {0, 0, 0, 0, 0, 0, 0, 0}, m_pf_units = 0;
     bool m_verify = false;      // kr_decode_verify_multi's pass: linear-attention layers record instead of storing state (docs/design/18-multi-verify.md)
 };
 size_t al(size_t n) { return (n + 255) & ~(size_t)255; }
+int pf_log2(int tq) { int w = 0; while ((1 << w) < tq) w++; return w; }      // tile widths are powers of two up to 128
 }  // namespace
 
 static int pf_gemm(kr_decode_store* s, int wid, const Act& A, int C, float* out, int ld, hipStream_t st) {
@@ -163,6 +168,10 @@ static int run_layer(kr_decode_store* s, Chunk& cx, size_t li) {
             if (M.pg.paged()) { m.page_table = (const int*)M.pg_table.p; m.page_stride = M.pg.stride; m.page_shift = M.pg.shift; }      // paged slots: a / b are pools
             m.gated = L.gated; m.nh = L.nh; m.nkv = L.nkv; m.hd = L.hd; m.eps = s->eps; m.sm_scale = L.sm_scale;
             if (cx.m_fd_chunks) { m.fd_o = (float*)M.fd_o.p; m.fd_ml = (float*)M.fd_ml.p; m.fd_chunk = cx.m_fd_chunk; m.fd_chunks = cx.m_fd_chunks; }      // "multi_attn_fast", long slots
+            if (cx.m_pf_tiles) {      // "multi_extend_flash": the runs of >= 2 tokens take the run kernels, the per-row kernels the first m_nruns rows
+                const int w = pf_log2(kr_pf_tile_tokens(L.nh, L.nkv));
+                m.pf_runs = cx.m_runs; m.pf_nruns = cx.m_nruns; m.pf_tiles = cx.m_pf_tiles + 2 * (size_t)cx.m_pf_off[w]; m.pf_ntiles = cx.m_pf_n[w]; m.pf_units = cx.m_pf_units;
+            }
             if (kr_launch_multi_gqa(m, Cc, st)) return kr_fail(KR_ERR_VALUE, "unsupported GQA geometry for the multi-sequence step");
         } else {
             KrPfmGqaArgs a{};
@@ -637,6 +646,30 @@ int kr_exact_refuse(kr_decode_store* s, bool slots) {
         }
         if (!mla) return kr_fail(KR_ERR_STATE, "the \"multi_mla_fast\" option covers MLA layers only: this store has none (set the option to 0 for the exact step)");
     }
+    // "multi_extend_flash", behind everything refused before the option existed.  An MLA layer: its runs would stay exact beside flash GQA runs, and no
+    // single-sequence pass is like that.  No GQA layer: an option that silently does nothing is a trap.  A geometry outside the prompt pass's flash kernels is an
+    // error, not a fall-back.  The LDS windows of the run kernels are raised here, once per slot set: a refusal leaves nothing reserved or advanced
+    // (paged slots under "multi_attn_fast" alone: the entry point refuses the call a few lines on with the words it always had, paged_refuse in kr_decode_multi.cpp,
+    // unless its argument check does first; this clause stands back so that refusal stays ahead of it)
+    const bool paged_refused = slots && s->multi && s->multi->pg.paged() && s->opt_multi_attn_fast && !s->opt_multi_attn_fast_paged;
+    if (slots && s->opt_multi_extend_flash && !paged_refused) {
+        bool gqa = false;
+        for (size_t i = 0; i < s->layers.size(); i++)
+            if (s->layers[i].attn == ATTN_MLA)
+                return kr_fail(KR_ERR_STATE, "the \"multi_extend_flash\" option covers GQA layers only: layer %zu is MLA (set the option to 0 for the exact pass)", i);
+        for (const DLayer& L : s->layers) gqa |= L.attn == ATTN_GQA;
+        if (!gqa) return kr_fail(KR_ERR_STATE, "the \"multi_extend_flash\" option covers GQA layers only: this store has none (set the option to 0 for the exact pass)");
+        for (const DLayer& L : s->layers)
+            if (L.attn == ATTN_GQA && !kr_pfm_gqa_flash_ok(L.nh, L.nkv, L.hd))
+                return kr_fail(KR_ERR_VALUE, "multi_extend_flash: GQA geometry nh %d nkv %d head_dim %d not covered (heads per KV head must divide 128, head_dim 64 / 128 / 256)", L.nh, L.nkv, L.hd);
+        if (s->multi && !s->multi->pf_ready) {
+            KR_HIP(hipSetDevice(e->device));
+            for (const DLayer& L : s->layers)
+                if (L.attn == ATTN_GQA && kr_multi_pf_prepare(L.hd, s->multi->kv_fp8, s->multi->pg.paged()))
+                    return kr_fail(KR_ERR_HIP, "multi_extend_flash: LDS window of the run kernel refused (head_dim %d)", L.hd);
+            s->multi->pf_ready = true;
+        }
+    }
     return KR_OK;
 }
 int kr_spec_refuse(kr_decode_store* s) { return kr_exact_refuse(s, false); }
@@ -742,7 +775,8 @@ extern "C" int kr_decode_commit(kr_decode_store* s, int n_keep) {
 // sections leave records instead of state, docs/design/18-multi-verify.md).  Engine buffer set KR_PF_MAX_DEPTH - 1; the
 // caller has ordered this pass after everything the store queued.
 // ------------------------------------------------------------------------------------------------
-int kr_multi_pass(kr_decode_store* s, int n, int n_final, const int32_t* d_rows, const int32_t* d_runs, int max_pos, hipStream_t st, bool verify) {
+int kr_multi_pass(kr_decode_store* s, int n, int n_final, const int32_t* d_rows, const int32_t* d_runs, int max_pos, hipStream_t st, bool verify,
+                  const int32_t* h_counts, const int32_t* h_positions) {
     kr_multi_state& M = *s->multi;
     PfLayout Lo;
     if (int rc = pf_layout(s, (size_t)n, true, true, st, Lo)) return rc;
@@ -760,11 +794,21 @@ int kr_multi_pass(kr_decode_store* s, int n, int n_final, const int32_t* d_rows,
     // kr_mla_flash_decode_chunk's (64 / 128 positions against the GQA kernels' 128 / 256), so both counts travel with the pass; the partials of the two kinds
     // of layer share M.fd_o / M.fd_ml, sized for the larger need
     const bool mla_flash = s->opt_multi_mla_fast && has_mla && M.max_seq > s->mla_split_min;
+    // "multi_extend_flash": a non-verify pass with a run of >= 2 tokens gives those runs the run kernels (docs/design/25-multi-extend-flash.md).  The per-row
+    // kernels then see the unit rows only, which lie among the first n_final rows: their score rows and split-KV partials are sized by n_final rows and the
+    // unit rows' longest position, not by every token row at the pass's longest.  Off, or every run of one token: attn_rows = n, attn_pos = max_pos, as ever
+    bool pf = false; int n_unit = 0, attn_rows = n, attn_pos = max_pos;
+    if (s->opt_multi_extend_flash && !verify && has_gqa && h_counts && h_positions) {
+        int unit_pos = -1;
+        for (int i = 0; i < n_final; i++) { if (h_counts[i] >= 2) pf = true; else { n_unit++; unit_pos = std::max(unit_pos, h_positions[i]); } }
+        if (pf) { attn_rows = n_final; attn_pos = unit_pos; }
+    }
+    const bool row_attn = !pf || n_unit > 0;      // some row takes the per-row attention kernels
     int fd_chunk = 0, fd_chunks = 0, mla_chunk = 0, mla_chunks = 0;
     size_t fd_o_bytes = 0, fd_ml_bytes = 0;
-    if (flash) {
-        fd_chunk = kr_fd_flash_chunk(M.max_seq); fd_chunks = (max_pos + fd_chunk) / fd_chunk;
-        if (fd_chunks > 1024) return kr_fail(KR_ERR_VALUE, "multi_attn_fast: position %d needs %d chunks of %d positions (at most 1024)", max_pos, fd_chunks, fd_chunk);
+    if (flash && row_attn) {
+        fd_chunk = kr_fd_flash_chunk(M.max_seq); fd_chunks = (attn_pos + fd_chunk) / fd_chunk;
+        if (fd_chunks > 1024) return kr_fail(KR_ERR_VALUE, "multi_attn_fast: position %d needs %d chunks of %d positions (at most 1024)", attn_pos, fd_chunks, fd_chunk);
         if (!M.fd_ready) {
             for (const DLayer& L : s->layers) {
                 if (L.attn != ATTN_GQA) continue;
@@ -773,7 +817,7 @@ int kr_multi_pass(kr_decode_store* s, int n, int n_final, const int32_t* d_rows,
             }
             M.fd_ready = true;
         }
-        fd_o_bytes = (size_t)n * fd_chunks * gqa_row * 4; fd_ml_bytes = (size_t)n * nh_max * fd_chunks * 8;
+        fd_o_bytes = (size_t)attn_rows * fd_chunks * gqa_row * 4; fd_ml_bytes = (size_t)attn_rows * nh_max * fd_chunks * 8;
     }
     if (mla_flash) {
         mla_chunk = kr_mla_flash_decode_chunk(M.max_seq); mla_chunks = (max_pos + mla_chunk) / mla_chunk;
@@ -786,19 +830,34 @@ int kr_multi_pass(kr_decode_store* s, int n, int n_final, const int32_t* d_rows,
         }
         fd_o_bytes = std::max(fd_o_bytes, (size_t)n * mla_chunks * mla_row * 4); fd_ml_bytes = std::max(fd_ml_bytes, (size_t)n * nh_max * mla_chunks * 8);
     }
-    if ((flash || mla_flash) && (M.fd_o.ensure(fd_o_bytes) || M.fd_ml.ensure(fd_ml_bytes)))
+    if (((flash && row_attn) || mla_flash) && (M.fd_o.ensure(fd_o_bytes) || M.fd_ml.ensure(fd_ml_bytes)))
         return kr_fail(KR_ERR_HIP, "hipMalloc of the multi-sequence step's split-KV partials (%zu MiB) failed", (fd_o_bytes + fd_ml_bytes) >> 20);
-    const bool need_scores = (has_gqa && !flash) || (has_mla && !mla_flash);
-    const int sc_ld = (max_pos + 1 + 31) & ~31;
+    const bool need_scores = (has_gqa && !flash && row_attn) || (has_mla && !mla_flash);
+    const int sc_ld = (attn_pos + 1 + 31) & ~31;
     const int n_logits = verify ? n : n_final;      // a verify pass: the lm_head over every token row (what Chunk::verify is to the store's own pass)
-    if (M.scratch.ensure(Lo.total) || (need_scores && M.scores.ensure((size_t)n * nh_max * sc_ld * 4)) || M.logits.ensure((size_t)n_logits * s->vocab * 4))
-        return kr_fail(KR_ERR_HIP, "hipMalloc of the multi-sequence step's scratch (%zu MiB) failed", (Lo.total + ((size_t)n * nh_max * sc_ld + (size_t)n_logits * s->vocab) * 4) >> 20);
+    if (M.scratch.ensure(Lo.total) || (need_scores && M.scores.ensure((size_t)attn_rows * nh_max * sc_ld * 4)) || M.logits.ensure((size_t)n_logits * s->vocab * 4))
+        return kr_fail(KR_ERR_HIP, "hipMalloc of the multi-sequence step's scratch (%zu MiB) failed", (Lo.total + ((size_t)attn_rows * nh_max * sc_ld + (size_t)n_logits * s->vocab) * 4) >> 20);
     Chunk cx{};
     cx.B = pf_carve(Lo, (char*)M.scratch.p); cx.scores = nullptr; cx.tok = d_rows + n; cx.Cc = n; cx.pos0 = 0; cx.set = KR_PF_MAX_DEPTH - 1;
     cx.first = true; cx.add_is_emb = true; cx.st = st;
     cx.m_slots = d_rows; cx.m_pos = d_rows + 2 * n; cx.m_sc_ld = sc_ld; cx.m_fd_chunk = fd_chunk; cx.m_fd_chunks = fd_chunks;
     cx.m_mla_chunk = mla_chunk; cx.m_mla_chunks = mla_chunks;
     cx.m_runs = d_runs; cx.m_nruns = n_final; cx.m_verify = verify;
+    if (pf) {      // the query tiles of the runs, one table per tile width among the GQA layers (128 / G tokens), behind one another in M.pf_tiles
+        std::vector<int32_t> all, one;
+        bool have[8] = {false, false, false, false, false, false, false, false};
+        for (const DLayer& L : s->layers) {
+            if (L.attn != ATTN_GQA) continue;
+            const int tq = kr_pf_tile_tokens(L.nh, L.nkv), w = pf_log2(tq);      // kr_exact_refuse: G divides 128
+            if (have[w]) continue;
+            have[w] = true;
+            cx.m_pf_off[w] = (int)(all.size() / 2); cx.m_pf_n[w] = kr_pf_build_tiles(n_final, h_counts, tq, one).n_tiles;
+            all.insert(all.end(), one.begin(), one.end());
+        }
+        if (M.pf_tiles.ensure(std::max(all.size() * 4, (size_t)65536))) return kr_fail(KR_ERR_HIP, "hipMalloc of the multi-sequence pass's query tiles failed");
+        KR_HIP(hipMemcpyAsync(M.pf_tiles.p, all.data(), all.size() * 4, hipMemcpyHostToDevice, st));      // pageable source: staged before the call returns
+        cx.m_pf_tiles = (const int32_t*)M.pf_tiles.p; cx.m_pf_units = n_unit;
+    }
     for (size_t l = 0; l < s->layers.size(); l++)
         if (int rc = run_layer(s, cx, l)) return rc;
     cx.Cc = n_logits;

@@ -57,9 +57,22 @@ struct KrMultiGqaArgs {
     // paged slots (docs/design/21-paged-slots.md): page_table [n_slots][page_stride] on the device, -1 = unmapped; k_cache / v_cache are then pools
     // [n_pages][1 << page_shift][nkv * hd] and position s of slot b is row (page_table[b][s >> page_shift] << page_shift) | (s & mask).  Null: flat slots
     const int* page_table; int page_stride, page_shift;
+    // "multi_extend_flash" (kr_multi_pf_flash.hip, docs/design/25-multi-extend-flash.md), a pass with a run of >= 2 tokens: pf_runs = the pass's run table,
+    // pf_nruns x [slot, off, cnt] (above); pf_tiles = pf_ntiles x [run, t0], the query tiles of the runs of >= 2 tokens (kr_pf_tiles.h); pf_units = the number
+    // of runs of one token.  The prep launch covers all B rows; the per-row attention kernels above run over the first pf_nruns rows and leave those of a run
+    // of >= 2 at once (scores / fd_o / fd_ml are then sized by pf_nruns rows); the runs take causal flash attention over their slots.  Null (the option is
+    // off, or every run has one token): none of this, B rows through the per-row kernels
+    const int* pf_runs; const int* pf_tiles; int pf_nruns, pf_ntiles, pf_units;
 };
+// row b < pf_nruns is the last token of a run of >= 2 tokens: not a row of the per-row attention kernels (workgroup-uniform; false whenever pf_runs is null)
+__device__ __forceinline__ bool kr_m_row_in_run(const KrMultiGqaArgs& a, int b) { return a.pf_runs && a.pf_runs[3 * b + 2] >= 2; }
 // 0: launched; 1: geometry not covered (hd 64 / 128 / 256, nh % nkv == 0), or the dynamic LDS below is over KR_MULTI_GQA_LDS_MAX
 int kr_launch_multi_gqa(const KrMultiGqaArgs& a, int B, hipStream_t st);
+// the run kernels of "multi_extend_flash" (after the prep launch): the geometry test is kr_pfm_gqa_flash_ok's (kr_prefill_ops.h); the LDS window of the kernel a
+// layer takes (once per slot set, outside the pass; non-zero = refused; every instantiation is a kernel of its own); grid (a.pf_ntiles, nkv)
+int kr_multi_pf_args_ok(const KrMultiGqaArgs& a);      // what kr_launch_multi_pf_flash checks: asked before anything of the layer is queued
+int kr_multi_pf_prepare(int hd, int fp8, int paged);
+int kr_launch_multi_pf_flash(const KrMultiGqaArgs& a, hipStream_t st);
 // dynamic LDS of kr_multi_gqa_attn_kernel in bytes: the G = nh / nkv query rows, four softmax tiles, the P.V tile and, on paged slots, the slot's page-table
 // row of page_stride entries (0: flat).  The launcher and kr_decode_slots_create_paged both ask here, so a slot set that is created can be stepped
 #define KR_MULTI_GQA_LDS_MAX (64 * 1024)

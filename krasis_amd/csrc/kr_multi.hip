@@ -309,6 +309,7 @@ __global__ void __launch_bounds__(256) kr_multi_gqa_attn_kernel(const KrMultiGqa
     float* tile = qs + (size_t)G * HD;               // [4][KR_MG_TILE]
     float* pt = tile + 4 * KR_MG_TILE;               // [G][KR_MG_PT]
     const int kvh = blockIdx.x, row = blockIdx.y, t = threadIdx.x, lane = t & 63, w = t >> 6;
+    if (kr_m_row_in_run(a, row)) return;      // "multi_extend_flash": the last token of a run of >= 2, attended to by the run kernels (workgroup-uniform, ahead of every barrier)
     const int pos = a.positions[row], seq = pos + 1, kvs = a.nkv * HD;
     const size_t kv0 = PAGED ? (size_t)kvh * HD : (size_t)a.slots[row] * a.slot_elems + (size_t)kvh * HD;      // element of (position 0, this KV head) in the slot (paged: in a page)
     const int* pgt = reinterpret_cast<const int*>(pt + (size_t)G * KR_MG_PT);      // PAGED: [ceil(seq / page_tokens)] page ids of the slot
@@ -396,10 +397,12 @@ size_t kr_multi_gqa_lds_bytes(int G, int hd, int page_stride) {
     return ((size_t)G * hd + 4 * KR_MG_TILE + (size_t)G * KR_MG_PT + (size_t)page_stride) * 4;
 }
 
+static int multi_gqa_runs(const KrMultiGqaArgs& a, int B, size_t lds, hipStream_t st);      // below
 int kr_launch_multi_gqa(const KrMultiGqaArgs& a, int B, hipStream_t st) {
     if ((a.hd != 64 && a.hd != 128 && a.hd != 256) || a.nkv < 1 || a.nh % a.nkv || a.sc_ld % 32) return 1;
     const int G = a.nh / a.nkv;
     const size_t lds = kr_multi_gqa_lds_bytes(G, a.hd, a.page_table ? a.page_stride : 0);
+    if (a.pf_tiles) return multi_gqa_runs(a, B, lds, st);
     if (a.fd_o) {
         // "multi_attn_fast" / "multi_attn_fast_paged": the same prep launch, then split-KV flash-decode over the slots, flat or paged (kr_multi_flash.hip)
         if (!kr_multi_fd_ok(a.nh, a.nkv, a.hd) || !a.fd_ml || a.fd_chunks < 1 || a.fd_chunks > 1024) return 1;
@@ -423,6 +426,32 @@ int kr_launch_multi_gqa(const KrMultiGqaArgs& a, int B, hipStream_t st) {
 #undef KR_MGA_HD
 #undef KR_MGA
     return 0;
+}
+
+// "multi_extend_flash", a pass with a run of >= 2 tokens (docs/design/25-multi-extend-flash.md): the prep launch over all B rows as ever; the per-row attention
+// kernels -- the exact one, or the flash-decode pair when a.fd_o is set -- over the first pf_nruns rows, where every unit row lies (the rows of longer runs
+// leave at once), and not at all without a unit row; then the run kernels over the query tiles
+static int multi_gqa_runs(const KrMultiGqaArgs& a, int B, size_t lds, hipStream_t st) {
+    // every check first: the prep launch appends rows to the slots, and a layer fails whole
+    if (a.pf_nruns < 1 || a.pf_nruns > B || a.pf_units < 0 || a.pf_units >= a.pf_nruns || !kr_multi_pf_args_ok(a)) return 1;
+    if (a.page_table && (a.page_stride < 1 || a.page_shift < 5)) return 1;
+    if (a.pf_units && a.fd_o && (!kr_multi_fd_ok(a.nh, a.nkv, a.hd) || !a.fd_ml || a.fd_chunk < 64 || a.fd_chunks < 1 || a.fd_chunks > 1024)) return 1;
+    if (a.pf_units && !a.fd_o && lds > KR_MULTI_GQA_LDS_MAX) return 1;
+    if (a.page_table) hipLaunchKernelGGL(kr_multi_gqa_prep_kernel<true>, dim3(a.nh + a.nkv, B), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(kr_multi_gqa_prep_kernel<false>, dim3(a.nh + a.nkv, B), dim3(256), 0, st, a);
+    if (a.pf_units) {
+        if (a.fd_o) {
+            if (kr_launch_multi_fd(a, a.pf_nruns, a.fd_chunks, st)) return 1;
+        } else {
+#define KR_MGR(NB_, F_, P_) hipLaunchKernelGGL((kr_multi_gqa_attn_kernel<NB_, F_, P_>), dim3(a.nkv, a.pf_nruns), dim3(256), lds, st, a)
+#define KR_MGR_HD(F_, P_) do { if (a.hd == 256) KR_MGR(32, F_, P_); else if (a.hd == 128) KR_MGR(16, F_, P_); else KR_MGR(8, F_, P_); } while (0)
+            if (a.page_table) { if (a.kv_fp8) KR_MGR_HD(true, true); else KR_MGR_HD(false, true); }
+            else { if (a.kv_fp8) KR_MGR_HD(true, false); else KR_MGR_HD(false, false); }
+#undef KR_MGR_HD
+#undef KR_MGR
+        }
+    }
+    return kr_launch_multi_pf_flash(a, st);
 }
 
 // ---- MLA (docs/design/15-multi-mla.md) -----------------------------------------------------------------------------------------------------------

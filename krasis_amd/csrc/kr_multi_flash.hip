@@ -14,7 +14,9 @@
 // table; the flat instantiation is the code it was
 template <int HD, bool FP8, bool PAGED = false>
 __global__ void __launch_bounds__(256) kr_multi_fd_flash_kernel(const KrMultiGqaArgs a, int n_chunks, int chunk) {
-    const int b = blockIdx.z, seq = a.positions[b] + 1;
+    const int b = blockIdx.z;
+    if (kr_m_row_in_run(a, b)) return;      // "multi_extend_flash": the run kernels' row (workgroup-uniform, ahead of every barrier)
+    const int seq = a.positions[b] + 1;
     if constexpr (PAGED) {
         kr_fd_flash_body<HD, FP8, true>(seq, blockIdx.x, blockIdx.y, a.q_out + (size_t)b * a.nh * HD, a.k_cache, a.v_cache, a.fd_o + (size_t)b * a.nh * n_chunks * HD,
                                         a.fd_ml + (size_t)b * a.nh * n_chunks * 2, a.nh, a.nkv, a.sm_scale, n_chunks, chunk,
@@ -31,6 +33,7 @@ __global__ void __launch_bounds__(256) kr_multi_fd_flash_kernel(const KrMultiGqa
 template <int HD>
 __global__ void __launch_bounds__(1024) kr_multi_fd_merge_kernel(const KrMultiGqaArgs a, int n_chunks, int chunk) {
     const int b = blockIdx.y;
+    if (kr_m_row_in_run(a, b)) return;      // ... which left no partials
     kr_fd_merge2_body<HD>(a.positions[b] + 1, blockIdx.x, a.fd_o + (size_t)b * a.nh * n_chunks * HD, a.fd_ml + (size_t)b * a.nh * n_chunks * 2, a.nh, a.nkv,
                           a.gate + (size_t)b * a.nh * HD, a.gated, a.attn_out + (size_t)b * a.nh * HD, nullptr, n_chunks, chunk);
 }

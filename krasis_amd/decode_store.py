@@ -308,6 +308,12 @@ class CpuDecodeStore:
         run split-KV flash-decode over slots of max_seq > 512, row i bit-identical to decode_step under set_attention_mode(True) on that sequence alone;
         shorter slots keep the exact step; GQA and linear-attention layers are untouched; a store without MLA layers, or an MLA layer of more than 64
         heads, is then refused by the batched calls (docs/design/24-multi-mla-fast.md).
+        "multi_extend_flash" (default 0): with 1 a run of two or more tokens entering a slot (extend_multi, prefill_slot) takes causal flash attention
+        over the slot in its GQA layers, flat or paged -- tolerance form, the run bit-identical to prefill(run, position) under
+        set_attention_mode(True) on a store of GQA layers whose own sequence holds the same prefix; runs of one token (step_multi, generate_multi,
+        decode rows beside a chunk) and verify passes keep what they had; linear-attention layers stay exact (there: within 3e-3 of the exact run).
+        A token's bits then depend on whether it entered in a run of >= 2 or alone.  A store with an MLA layer or without a GQA layer, or a GQA
+        layer whose heads per KV head do not divide 128, is then refused by the batched calls (docs/design/25-multi-extend-flash.md).
         "gguf_exact_pass" (default 0): with 1 every multi-row pass (prefill, prefill_nll, verify, and the batched pass behind every slot call) runs
         native-GGUF MoE layers through the exact grouped block kernels -- every row carries the bits of decode_step on that sequence alone -- and the
         slot and speculation calls accept a store with such layers; slower than the default int8-MFMA form on long prompts; refused together with
@@ -559,7 +565,10 @@ class CpuDecodeStore:
         bit-identical to that many decode_step calls on that sequence alone (every KV row -- or MLA latent and rope-key row -- they append, conv and
         recurrent state, the last token's logits and id), however a token stream is cut into calls and whatever rows share the pass.  At most
         KR_EXTEND_MAX_TOKENS tokens per call, all rows together.  Returns one id per row -- the greedy id after its last token, or with sample=True the
-        draw of the slot's sampler (set_slot_sampler) on those logits, as step_multi_sample draws it -- or (ids, logits f32 [n, vocab]) with logits=True."""
+        draw of the slot's sampler (set_slot_sampler) on those logits, as step_multi_sample draws it -- or (ids, logits f32 [n, vocab]) with logits=True.
+        After set_option("multi_extend_flash", 1) a run of two or more tokens takes the prompt pass's flash attention in its GQA layers instead
+        (tolerance form, docs/design/25-multi-extend-flash.md): it then equals prefill(run, position) under set_attention_mode(True), not decode_step,
+        and a token's bits depend on whether it entered in a run of >= 2 or alone (among cuts of >= 2 tokens each the cut does not matter)."""
         if len(token_lists) != len(slots) or len(positions) != len(slots):
             raise ValueError(f"{len(slots)} slots, {len(token_lists)} token lists, {len(positions)} positions")
         return self._step_multi(self._lib.kr_decode_extend_multi, slots, [len(run) for run in token_lists], [int(t) for run in token_lists for t in run],
@@ -638,7 +647,9 @@ class CpuDecodeStore:
     def prefill_slot(self, slot: int, tokens: Sequence[int], start_pos: int = 0, chunk: Optional[int] = None) -> int:
         """A prompt straight into a slot: extend_multi over chunks of `chunk` tokens (default KR_EXTEND_MAX_TOKENS).  The slot afterwards equals
         prefill(tokens, start_pos) + save_slot bit for bit, and the store's own sequence, logits and last token are never touched.  Returns the greedy id
-        after the last token."""
+        after the last token.  After set_option("multi_extend_flash", 1) every chunk of two or more tokens takes the prompt pass's flash attention in
+        its GQA layers (see extend_multi): the slot then equals prefill under set_attention_mode(True) on a store of GQA layers, and a last chunk
+        of one token is an exact step."""
         from ._lib import KR_EXTEND_MAX_TOKENS
         chunk = KR_EXTEND_MAX_TOKENS if chunk is None else int(chunk)
         if not 1 <= chunk <= KR_EXTEND_MAX_TOKENS:

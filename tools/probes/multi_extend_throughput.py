@@ -9,6 +9,14 @@ rows.  Median wall time of the timed repeats after warm-up; every call returns a
 extend_multi passes (for a rocprofv3 --kernel-trace --stats run of its own).
 
     python tools/probes/multi_extend_throughput.py [out.txt] [--profile]
+
+--flash: the "multi_extend_flash" option (docs/design/25-multi-extend-flash.md) against the exact run kernels instead.  Admission of a 512- and a 4096-token
+prompt with prefill_slot and the mixed pass, on flat slots and on pages of 64 positions; option off and option on alternate call by call inside this process;
+the median of the timed calls after warm-up per leg; three rounds, every round's medians and their spread are reported.  --flash --off-only: the off leg alone
+and no option call (a library built from another commit, loaded through KRASIS_HIP_LIB: has option off moved?).  --flash --profile: six mixed passes on flat
+slots and nothing else, option on (with --off-only: off; with --admission: one 4096-token admission instead), for a rocprofv3 --kernel-trace --stats run.
+
+    python tools/probes/multi_extend_throughput.py [out.txt] --flash [--off-only] [--profile [--admission]]
 """
 import os
 import statistics
@@ -30,10 +38,76 @@ def timed(fn, warm, reps):
     return statistics.median(ts[warm:])
 
 
+def flash_legs(out_path, off_only, profile):
+    """option off / on, alternating call by call: admission (prefill_slot) and the mixed pass, flat and paged"""
+    kv = 4096 + 160
+    eng, st, keep = bench.build_qcn(0, 0, 48, rope_len=kv, kv_fp8=True)
+    lines = []
+
+    def log(s):
+        print(s, flush=True); lines.append(s)
+        if out_path:
+            with open(out_path, "w") as f:
+                f.write("\n".join(lines) + "\n")
+
+    toks = lambda n, i=0: [(i * 131 + j * 7) % 1000 for j in range(n)]
+    nslots, adm, chunk_slot = N_DECODE + 2, N_DECODE, N_DECODE + 1
+    rows = list(range(N_DECODE))
+    legs = (0,) if off_only else (0, 1)
+
+    def option(v):
+        if not off_only:
+            st.set_option("multi_extend_flash", v)
+
+    def alternate(fn, warm, reps):
+        """fn(i) under option off and on in turn -> the median seconds of each leg's timed calls"""
+        ts = {v: [] for v in legs}
+        for i in range(warm + reps):
+            for v in legs:
+                option(v)
+                t0 = time.perf_counter(); fn(i); dt = time.perf_counter() - t0
+                if i >= warm:
+                    ts[v].append(dt)
+        option(0)
+        return {v: statistics.median(t) for v, t in ts.items()}
+
+    for paged in (False, True):
+        kind = "pages of 64" if paged else "flat"
+        pages = dict(page_tokens=64, n_pages=N_DECODE * ((P_DECODE + 64) // 64 + 1) + 2 * ((kv + 63) // 64)) if paged else {}
+        log(f"slots ({kind}): {nslots} x {kv} positions, {st.create_slots(nslots, kv, **pages) / 2**30:.1f} GiB")
+        st.fill_state_synthetic(kv, seed=99)
+        for s in range(N_DECODE):
+            st.save_slot(s, P_DECODE)
+
+        def mixed(i):
+            st.extend_multi(rows + [chunk_slot], [[(i * 7 + b) % 1000] for b in rows] + [toks(CHUNK, i)], [P_DECODE] * N_DECODE + [0])
+
+        if profile:      # flat slots only: six mixed passes (--admission: one 4096-token admission instead), option on, or off with --off-only
+            option(1)
+            if "--admission" in sys.argv:
+                st.prefill_slot(adm, toks(4096, 1))
+            else:
+                for i in range(6):
+                    mixed(i)
+            option(0)
+            return
+        cases = [("prompt 512 -> slot", lambda i: st.prefill_slot(adm, toks(512, i)), 1, 4), ("prompt 4096 -> slot", lambda i: st.prefill_slot(adm, toks(4096, i)), 1, 2),
+                 (f"mixed: {N_DECODE} rows at {P_DECODE} + a {CHUNK}-token chunk", mixed, 2, 6)]
+        for name, fn, warm, reps in cases:
+            rounds = [alternate(fn, warm, reps) for _ in range(3)]
+            for v in legs:
+                ms = [r[v] * 1e3 for r in rounds]
+                log(f"{kind:<12} {name:<44} option {v}: rounds {ms[0]:9.2f} {ms[1]:9.2f} {ms[2]:9.2f} ms   median {statistics.median(ms):9.2f}   spread {(max(ms) - min(ms)) / statistics.median(ms) * 100:5.1f} %")
+            if len(legs) == 2:
+                log(f"{kind:<12} {name:<44} on / off = {statistics.median([r[1] for r in rounds]) / statistics.median([r[0] for r in rounds]):.3f}")
+
+
 def main():
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
     out_path = args[0] if args else None
     profile = "--profile" in sys.argv
+    if "--flash" in sys.argv:
+        return flash_legs(out_path, "--off-only" in sys.argv, profile)
     kv = 4096 + 160
     eng, st, keep = bench.build_qcn(0, 0, 48, rope_len=kv, kv_fp8=True)
     lines = []
