@@ -279,6 +279,18 @@ int kr_decode_set_attention_mode(kr_decode_store* s, int mode);
  * store's KR_ATTN_FAST prompt pass differs from its decode step; among cuts of >= 2 tokens each the result does not depend on the cut.  Refused by every batched
  * entry point, behind everything they refused before, each message naming the option: a store with an MLA layer or without a GQA layer (KR_ERR_STATE), a GQA
  * layer outside the prompt pass's flash kernels -- heads per KV head must divide 128, head_dim 64 / 128 / 256 -- (KR_ERR_VALUE), an LDS window refusal (KR_ERR_HIP).
+ * "multi_extend_la_chunk" (default 0; docs/design/26-multi-extend-la-chunk.md): in a non-verify batched pass (kr_decode_extend_multi) the linear-attention
+ * layers give every run of counts[i] >= 64 tokens the chunked gated delta rule of the KR_ATTN_FAST prompt pass (closed form over sub-chunks of 64 tokens on
+ * the bf16 matrix cores, fused form) instead of the walk token by token: run i carries the bits of kr_decode_prefill(tokens, positions[i]) under KR_ATTN_FAST
+ * on a store whose own sequence holds the same prefix, as long as that pass takes the run as one chunk (any run of at most 1024 tokens by default) and
+ * "la_conv_fused" is 1 -- the last token's logits and id, the conv and recurrent state left in the slot, the K / V rows appended -- on a store whose
+ * attention layers are all linear attention, and on a hybrid store (linear attention + GQA) with "multi_extend_flash" set as well; whatever other rows share
+ * the pass, flat and paged slots.  A hybrid store under this option alone has no single-sequence equal: within 3e-3 of the exact run
+ * (docs/design/02-numerics.md 2b).  Runs of fewer than 64 tokens, one token included, keep the exact run kernels and their bits; verify passes are untouched.
+ * Consequence: under the option a token's bits depend on whether its run had >= 64 tokens and on where the 64-token sub-chunks fall; a stream cut into calls
+ * whose lengths are multiples of 64, the last one any length >= 64, gives the bits of one call.  Refused by every batched entry point, behind everything they
+ * refused before, each message naming the option: a store without a linear-attention layer or with an MLA layer (KR_ERR_STATE), a linear-attention layer
+ * outside dk = dv = 128 with nv = nk * hr (KR_ERR_VALUE), an LDS window refusal (KR_ERR_HIP).
  * "gguf_exact_pass" (default 0; docs/design/20-gguf-exact-pass.md): with 1, every multi-row pass of the store -- kr_decode_prefill, kr_decode_prefill_nll,
  * kr_decode_verify and the batched pass behind every slot entry point -- runs MoE layers that hold native GGUF blocks through the exact grouped block
  * kernels (kr_gguf_group.hip) instead of the int8-MFMA form: every row then carries the bits of kr_decode_step on that sequence alone, and the slot and

@@ -52,6 +52,9 @@ struct kr_multi_state {
     DevBuf rows, ids, logits, scores, scratch; // step: [slots | tokens | positions] (device), greedy ids, [n][vocab] logits, attention scores, the arena
     DevBuf fd_o, fd_ml; bool fd_ready = false; // "multi_attn_fast": split-KV partials [n][nkv][chunks][G][hd] and (max, sum) [n][nh][chunks][2] of one GQA layer, sized by the step's longest row; the kernels' LDS windows are raised
     bool pf_ready = false; DevBuf pf_tiles;    // "multi_extend_flash": the LDS windows of the run kernels are raised (kr_exact_refuse, once per slot set); the pass's query tiles [run, t0] per tile width (kr_pf_tiles.h)
+    // "multi_extend_la_chunk": the LDS windows of the chunked delta rule's two kernels are raised (kr_exact_refuse, once per slot set); the pass's chunked runs
+    // [run, first tile] and behind them their sub-chunks [run, sub] (kr_lc_tiles.h); the rule's scratch of one layer, sized by the pass's sub-chunks
+    bool lc_ready = false; DevBuf lc_tiles, lc_scratch;
     bool mla_fd_ready = false;                 // "multi_mla_fast": the partials of one MLA layer, [n][chunks][nh][klr] and [n][nh][chunks][2], share fd_o / fd_ml (sized for the larger need); the kernels' LDS windows are raised
     // per-slot samplers (kr_decode_slot_sampler, docs/design/14-multi-sampling.md): allocated for every slot on the first call; empty = every slot greedy
     struct Sampler { float temperature = 0.0f, top_p = 1.0f, penalty = 0.0f; int top_k = 0; };
@@ -98,6 +101,7 @@ struct kr_decode_store {
     int opt_multi_attn_fast = 0;                 // kr_decode_set_option("multi_attn_fast"): the GQA layers of every batched multi-sequence step run split-KV flash-decode over slots longer than gqa_split_min (tolerance form, docs/design/16-multi-attn-fast.md); the mode bits stay refused
     int opt_multi_mla_fast = 0;                  // kr_decode_set_option("multi_mla_fast"): the MLA layers of every batched multi-sequence step run split-KV flash-decode over slots longer than mla_split_min, flat or paged (tolerance form, docs/design/24-multi-mla-fast.md); the mode bits stay refused
     int opt_multi_extend_flash = 0;              // kr_decode_set_option("multi_extend_flash"): in a non-verify batched pass the GQA layers give every run of >= 2 tokens causal flash attention over its slot, flat or paged -- the bits of the KR_ATTN_FAST prompt pass (tolerance form, docs/design/25-multi-extend-flash.md); runs of one token keep what they had; the mode bits stay refused
+    int opt_multi_extend_la_chunk = 0;           // kr_decode_set_option("multi_extend_la_chunk"): in a non-verify batched pass the linear-attention layers give every run of >= 64 tokens the chunked delta rule of the KR_ATTN_FAST prompt pass, fused form -- its bits (tolerance form, docs/design/26-multi-extend-la-chunk.md); shorter runs keep the exact run kernels; the mode bits stay refused
     int opt_gen_lookahead = 0;                    // kr_decode_set_option("generate_lookahead"): generate_batch feeds the sampled token back ON THE DEVICE and queues step i + 1 before the host has read token i
     int opt_ep_graph = 0;                         // kr_decode_set_option("ep_graph"): expert-parallel decode over RCCL replays a captured graph (the all-reduce is captured with the kernels)
     uint64_t ep_generation_seen = 0;               // kr_engine::ep_generation at the last step: a new / destroyed communicator invalidates the graph and restarts the warm-up
@@ -143,7 +147,7 @@ int kr_standalone_cancelled(kr_decode_store* s);
 // d_runs = n_runs x [slot, off, cnt] (kr_multi.h); logits of the first n_runs rows -> s->multi->logits [n_runs][vocab].  verify: the linear-attention layers
 // take the verify form (no state stored; records into the layers of s->multi->v_host), and the logits of all n_rows rows -> s->multi->logits [n_rows][vocab]
 // h_counts / h_positions (host, optional): the n_runs run lengths and first positions as the caller gave them -- what "multi_extend_flash" builds its query tiles
-// from and sizes the per-row kernels' scratch by; null counts: every run has one token
+// from and sizes the per-row kernels' scratch by, and "multi_extend_la_chunk" its table of chunked runs; null counts: every run has one token
 int kr_multi_pass(kr_decode_store* s, int n_rows, int n_runs, const int32_t* d_rows, const int32_t* d_runs, int max_pos, hipStream_t st, bool verify = false,
                   const int32_t* h_counts = nullptr, const int32_t* h_positions = nullptr);
 void kr_standalone_set_elapsed(kr_decode_store* s, double sec);   // kr_engine.cpp: per (group, column) nibble sums for the int8-MFMA GEMM

@@ -18,6 +18,7 @@
 
 #include "../../include/krasis_hip.h"
 #include "kr_pf_tiles.h"
+#include "kr_lc_tiles.h"
 #include "kr_decode_internal.h"
 #include "kr_prefill.h"
 #include "kr_prefill_ops.h"
@@ -48,6 +49,9 @@ struct Chunk {      // one chunk of the prompt in flight: its arena, stream and 
     // ... "multi_extend_flash", a pass with a run of >= 2 tokens: the query tiles [run, t0] of its runs (device), one table per tile width 1 << w tokens at
     // entry m_pf_off[w] with m_pf_n[w] tiles (kr_pf_tiles.h); m_pf_units = its runs of one token.  Null: every row takes the per-row attention kernels
     const int32_t* m_pf_tiles = nullptr; int m_pf_off[8] = {0, 0, 0, 0, 0, 0, 0, 0}, m_pf_n[8] = {0, 0, 0, 0, 0, 0, 0, 0}, m_pf_units = 0;
+    // ... "multi_extend_la_chunk", a pass with a run of >= 64 tokens: its chunked runs [run, first tile] and their sub-chunks [run, sub] (device, kr_lc_tiles.h),
+    // the number of shorter runs and the chunked rule's scratch of one layer.  Null: every run takes the exact run kernels
+    const int32_t* m_lc_runs = nullptr; const int32_t* m_lc_tiles = nullptr; int m_lc_nruns = 0, m_lc_ntiles = 0, m_lc_short = 0; float* m_lc_scratch = nullptr;
     bool m_verify = false;      // kr_decode_verify_multi's pass: linear-attention layers record instead of storing state (docs/design/18-multi-verify.md)
 };
 size_t al(size_t n) { return (n + 255) & ~(size_t)255; }
@@ -135,6 +139,10 @@ static int run_layer(kr_decode_store* s, Chunk& cx, size_t li) {
             if (cx.m_verify) {
                 const KrMultiLaCommit& R = M.v_host[(size_t)M.v_la_of[li]];
                 m.rec_x = (float*)R.rec_x; m.rec_k = (float*)R.rec_k; m.rec_v = (float*)R.rec_v; m.rec_ge = (float*)R.rec_ge; m.rec_be = (float*)R.rec_be;
+            }
+            if (cx.m_lc_runs) {      // "multi_extend_la_chunk": the runs of >= 64 tokens take the chunked rule, its output rows in B.recur ahead of the gated norm
+                m.lc_runs = cx.m_lc_runs; m.lc_tiles = cx.m_lc_tiles; m.lc_nruns = cx.m_lc_nruns; m.lc_ntiles = cx.m_lc_ntiles; m.lc_short = cx.m_lc_short;
+                m.lc_scratch = cx.m_lc_scratch; m.lc_o = B.recur;
             }
             if (kr_launch_multi_la(m, cx.m_runs, cx.m_nruns, Cc, st)) return kr_fail(KR_ERR_VALUE, "unsupported linear-attention geometry for the multi-sequence step");
         } else {
@@ -670,6 +678,26 @@ int kr_exact_refuse(kr_decode_store* s, bool slots) {
             s->multi->pf_ready = true;
         }
     }
+    // "multi_extend_la_chunk", behind everything refused before the option existed, and standing back like the clause above.  No linear-attention layer: an option
+    // that silently does nothing is a trap.  An MLA layer: its runs would stay exact beside chunked linear-attention runs, and no single-sequence pass is like
+    // that.  A layer outside the chunked rule's geometry is an error, not a fall-back to the run kernels.  The LDS windows of the two kernels are raised here, once
+    // per slot set: a refusal leaves nothing advanced
+    if (slots && s->opt_multi_extend_la_chunk && !paged_refused) {
+        bool la = false;
+        for (const DLayer& L : s->layers) la |= L.attn == ATTN_LA;
+        if (!la) return kr_fail(KR_ERR_STATE, "the \"multi_extend_la_chunk\" option covers linear-attention layers only: this store has none (set the option to 0 for the exact pass)");
+        for (size_t i = 0; i < s->layers.size(); i++)
+            if (s->layers[i].attn == ATTN_MLA)
+                return kr_fail(KR_ERR_STATE, "the \"multi_extend_la_chunk\" option covers linear-attention layers only: layer %zu is MLA (set the option to 0 for the exact pass)", i);
+        for (const DLayer& L : s->layers)
+            if (L.attn == ATTN_LA && !kr_multi_lc_ok(L.dk, L.dv, L.nk, L.nv, s->weights[L.qkvz_wid]->rows))
+                return kr_fail(KR_ERR_VALUE, "multi_extend_la_chunk: linear-attention geometry nk %d nv %d dk %d dv %d not covered (dk = dv = 128, whole value-head groups per key head)", L.nk, L.nv, L.dk, L.dv);
+        if (s->multi && !s->multi->lc_ready) {
+            KR_HIP(hipSetDevice(e->device));
+            if (kr_multi_lc_prepare()) return kr_fail(KR_ERR_HIP, "multi_extend_la_chunk: LDS window of the chunked delta rule's kernels refused");
+            s->multi->lc_ready = true;
+        }
+    }
     return KR_OK;
 }
 int kr_spec_refuse(kr_decode_store* s) { return kr_exact_refuse(s, false); }
@@ -857,6 +885,23 @@ int kr_multi_pass(kr_decode_store* s, int n, int n_final, const int32_t* d_rows,
         if (M.pf_tiles.ensure(std::max(all.size() * 4, (size_t)65536))) return kr_fail(KR_ERR_HIP, "hipMalloc of the multi-sequence pass's query tiles failed");
         KR_HIP(hipMemcpyAsync(M.pf_tiles.p, all.data(), all.size() * 4, hipMemcpyHostToDevice, st));      // pageable source: staged before the call returns
         cx.m_pf_tiles = (const int32_t*)M.pf_tiles.p; cx.m_pf_units = n_unit;
+    }
+    // "multi_extend_la_chunk": a non-verify pass with a run of >= 64 tokens gives those runs the chunked delta rule (docs/design/26-multi-extend-la-chunk.md).
+    // One table for every linear-attention layer -- the chunked runs, then their sub-chunks -- and one scratch, sized by the widest layer.  Off, a verify pass or
+    // every run shorter: the pointers stay null and every layer launches what it always did
+    if (s->opt_multi_extend_la_chunk && !verify && h_counts) {
+        std::vector<int32_t> lr, lt;
+        const KrLcStats ls = kr_lc_build(n_final, h_counts, lr, lt);
+        int nv_max = 0;
+        for (const DLayer& L : s->layers) if (L.attn == ATTN_LA) nv_max = std::max(nv_max, L.nv);
+        if (ls.n_runs && nv_max) {
+            lr.insert(lr.end(), lt.begin(), lt.end());
+            if (M.lc_tiles.ensure(std::max(lr.size() * 4, (size_t)65536)) || M.lc_scratch.ensure(kr_lc_scratch_floats(ls.n_tiles, nv_max) * 4))
+                return kr_fail(KR_ERR_HIP, "hipMalloc of the multi-sequence pass's chunked delta-rule scratch (%zu MiB) failed", kr_lc_scratch_floats(ls.n_tiles, nv_max) * 4 >> 20);
+            KR_HIP(hipMemcpyAsync(M.lc_tiles.p, lr.data(), lr.size() * 4, hipMemcpyHostToDevice, st));      // pageable source: staged before the call returns
+            cx.m_lc_runs = (const int32_t*)M.lc_tiles.p; cx.m_lc_tiles = cx.m_lc_runs + 2 * (size_t)ls.n_runs;
+            cx.m_lc_nruns = ls.n_runs; cx.m_lc_ntiles = ls.n_tiles; cx.m_lc_short = ls.n_short; cx.m_lc_scratch = (float*)M.lc_scratch.p;
+        }
     }
     for (size_t l = 0; l < s->layers.size(); l++)
         if (int rc = run_layer(s, cx, l)) return rc;

@@ -18,7 +18,16 @@ struct KrMultiLaArgs {
     // recorded instead: rec_x [rows][conv_dim] the pre-conv channel inputs, rec_k [rows][nk * dk] the normalised keys (once per key head), rec_v
     // [rows][nv * dv], rec_ge / rec_be [rows][nv] e^g and beta.  Null: the run form above
     float *rec_x, *rec_k, *rec_v, *rec_ge, *rec_be;
+    // "multi_extend_la_chunk" (kr_multi_la_chunk.hip, docs/design/26-multi-extend-la-chunk.md), a non-verify pass with a run of >= KR_M_LC_MIN tokens: lc_runs =
+    // lc_nruns x [run, first scratch tile], those runs in call order; lc_tiles = lc_ntiles x [run, sub], their sub-chunks of 64 tokens (kr_lc_tiles.h; scratch tile
+    // x is tile x); lc_short = the number of shorter runs; lc_scratch = kr_pfm_la_chunk_scratch_floats(64 lc_ntiles, nv) floats; lc_o [rows][nv * dv] = the delta
+    // rule's output rows ahead of the gated norm.  The two run kernels leave such a run at once and are not launched when lc_short is 0; the run takes the chunked
+    // rule of the KR_ATTN_FAST prompt pass.  Null / 0 (the option is off, a verify pass, or every run is shorter): none of this
+    const int* lc_runs; const int* lc_tiles; int lc_nruns, lc_ntiles, lc_short; float* lc_scratch; float* lc_o;
 };
+#define KR_M_LC_MIN 64      // = LC_T (kr_lac_dev.h) = KR_LC_TOKENS (kr_lc_tiles.h): kr_pfm_la_chunk_ok's rule, C >= LC_T
+// a run of cnt tokens takes the chunked rule: not a run of the exact run kernels (workgroup-uniform; false whenever lc_runs is null)
+__device__ __forceinline__ bool kr_m_run_chunked(const KrMultiLaArgs& a, int cnt) { return a.lc_runs && cnt >= KR_M_LC_MIN; }
 // runs (device) = n_runs x [slot, off, cnt]: run i's tokens are, in order, rows off .. off + cnt - 2 and then row i of qkvz / ba / conv_out / out (cnt 1:
 // row i alone).  The slot's conv and recurrent state are loaded once, carried in registers through the run and stored once.  Slots distinct across runs;
 // max_cnt = a bound on every cnt, at most 1024 (the gate rows the recurrence kernel keeps in LDS).
@@ -26,6 +35,12 @@ struct KrMultiLaArgs {
 int kr_launch_multi_la(const KrMultiLaArgs& a, const int* runs, int n_runs, int max_cnt, hipStream_t st);
 // the pass row of token t < cnt of run i (kernels of kr_multi.hip and kr_multi_sample.hip)
 __device__ __forceinline__ int kr_m_run_row(int i, int off, int cnt, int t) { return t == cnt - 1 ? i : off + t; }
+// the chunked rule of "multi_extend_la_chunk" (after the exact run kernels, which kr_launch_multi_la skips or lets leave those runs): the geometry test
+// (dk = dv = 128, nv = nk hr, 16-byte in-projection rows; the tables present); the LDS windows of the two kernels (once per slot set, outside the pass; non-zero =
+// refused); prep over (lc_ntiles, nv), the carried conv inputs of every chunked run, scan over (4 nv, lc_nruns), gated norm over the chunked runs' rows
+int kr_multi_lc_ok(int dk, int dv, int nk, int nv, int ld_qkvz);
+int kr_multi_lc_prepare();
+int kr_launch_multi_la_chunk(const KrMultiLaArgs& a, const int* runs, hipStream_t st);
 
 // commit of a verify pass (docs/design/18-multi-verify.md): one linear-attention layer's slot states and the records its verify-form launch left.  A table
 // of these lives on the device (kr_multi_state::v_tab)

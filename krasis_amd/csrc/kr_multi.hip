@@ -32,6 +32,7 @@ __global__ void __launch_bounds__(256) kr_multi_la_conv_kernel(const KrMultiLaAr
     else if (ch < 2 * key_dim) { kh = (ch - key_dim) / dk; off = dk + (ch - key_dim) % dk; }
     else { const int vh = (ch - 2 * key_dim) / dv, e = (ch - 2 * key_dim) % dv; kh = vh / hr; off = 2 * dk + (vh % hr) * dv + e; }
     const int slot = runs[3 * i], row0 = runs[3 * i + 1], cnt = runs[3 * i + 2];
+    if constexpr (!VERIFY) if (kr_m_run_chunked(a, cnt)) return;      // "multi_extend_la_chunk": the chunked rule's run (workgroup-uniform; this kernel has no barrier; never in a verify pass)
     const float* xin = a.qkvz + (size_t)kh * group_dim + off;
     float4* cs = reinterpret_cast<float4*>(a.conv_state + (size_t)slot * a.conv_stride) + ch;
     float4 s = *cs;
@@ -62,6 +63,7 @@ __global__ void __launch_bounds__(256) kr_multi_la_recur_kernel(const KrMultiLaA
     const int h = blockIdx.x, ri = blockIdx.y, j = threadIdx.x, dv = a.dv, hr = a.hr, kh = h / hr, r = h - kh * hr;
     const int key_dim = a.nk * DK, conv_dim = 2 * key_dim + a.nv * dv, group_dim = 2 * DK + 2 * dv * hr;
     const int slot = runs[3 * ri], row0 = runs[3 * ri + 1], cnt = runs[3 * ri + 2];
+    if constexpr (!VERIFY) if (kr_m_run_chunked(a, cnt)) return;      // "multi_extend_la_chunk": the chunked rule's run (workgroup-uniform, ahead of every barrier; never in a verify pass)
     for (int t = j; t < cnt; t += dv) {      // gates (decode.rs:3891-3901)
         const float* ba = a.ba + (size_t)kr_m_run_row(ri, row0, cnt, t) * a.ld_ba;
         const float b_raw = ba[kh * 2 * hr + r], a_p = ba[kh * 2 * hr + hr + r];
@@ -210,9 +212,15 @@ int kr_launch_multi_la(const KrMultiLaArgs& a, const int* runs, int n_runs, int 
         else hipLaunchKernelGGL((kr_multi_la_recur_kernel<64, true>), rg, dim3(a.dv), 0, st, a, runs);
         return 0;
     }
-    hipLaunchKernelGGL(kr_multi_la_conv_kernel<false>, cg, dim3(256), 0, st, a, runs);
-    if (a.dk == 128) hipLaunchKernelGGL((kr_multi_la_recur_kernel<128, false>), rg, dim3(a.dv), 0, st, a, runs);
-    else hipLaunchKernelGGL((kr_multi_la_recur_kernel<64, false>), rg, dim3(a.dv), 0, st, a, runs);
+    // "multi_extend_la_chunk", a pass with a run of >= 64 tokens: the run kernels over the shorter runs (none: not launched), then the chunked rule over the
+    // others.  Every check that can refuse the layer stands ahead of the first launch, which advances slot state: a layer fails whole
+    if (a.lc_runs && (!kr_multi_lc_ok(a.dk, a.dv, a.nk, a.nv, a.ld_qkvz) || !a.lc_tiles || !a.lc_scratch || !a.lc_o || a.lc_nruns < 1 || a.lc_ntiles < a.lc_nruns)) return 1;
+    if (!a.lc_runs || a.lc_short > 0) {
+        hipLaunchKernelGGL(kr_multi_la_conv_kernel<false>, cg, dim3(256), 0, st, a, runs);
+        if (a.dk == 128) hipLaunchKernelGGL((kr_multi_la_recur_kernel<128, false>), rg, dim3(a.dv), 0, st, a, runs);
+        else hipLaunchKernelGGL((kr_multi_la_recur_kernel<64, false>), rg, dim3(a.dv), 0, st, a, runs);
+    }
+    if (a.lc_runs) return kr_launch_multi_la_chunk(a, runs, st);
     return 0;
 }
 

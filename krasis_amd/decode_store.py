@@ -314,6 +314,14 @@ class CpuDecodeStore:
         decode rows beside a chunk) and verify passes keep what they had; linear-attention layers stay exact (there: within 3e-3 of the exact run).
         A token's bits then depend on whether it entered in a run of >= 2 or alone.  A store with an MLA layer or without a GQA layer, or a GQA
         layer whose heads per KV head do not divide 128, is then refused by the batched calls (docs/design/25-multi-extend-flash.md).
+        "multi_extend_la_chunk" (default 0): with 1 a run of 64 or more tokens entering a slot (extend_multi, prefill_slot) takes the prompt pass's
+        chunked delta rule in its linear-attention layers (closed form over sub-chunks of 64 tokens on the matrix cores) -- tolerance form, the run
+        bit-identical to prefill(run, position) under set_attention_mode(True) on a store whose own sequence holds the same prefix: on a store of
+        linear-attention layers, and on a hybrid store with "multi_extend_flash" set as well (this option alone there: within 3e-3 of the exact run).
+        Runs of fewer than 64 tokens and verify passes keep what they had.  A token's bits then depend on whether its run had >= 64 tokens and on
+        where the 64-token sub-chunk edges fall: calls cut at multiples of 64 (the last one any length >= 64) give the bits of one call.  A store
+        without a linear-attention layer or with an MLA layer, or a linear-attention layer outside dk = dv = 128, is then refused by the batched
+        calls (docs/design/26-multi-extend-la-chunk.md).
         "gguf_exact_pass" (default 0): with 1 every multi-row pass (prefill, prefill_nll, verify, and the batched pass behind every slot call) runs
         native-GGUF MoE layers through the exact grouped block kernels -- every row carries the bits of decode_step on that sequence alone -- and the
         slot and speculation calls accept a store with such layers; slower than the default int8-MFMA form on long prompts; refused together with
@@ -568,7 +576,11 @@ class CpuDecodeStore:
         draw of the slot's sampler (set_slot_sampler) on those logits, as step_multi_sample draws it -- or (ids, logits f32 [n, vocab]) with logits=True.
         After set_option("multi_extend_flash", 1) a run of two or more tokens takes the prompt pass's flash attention in its GQA layers instead
         (tolerance form, docs/design/25-multi-extend-flash.md): it then equals prefill(run, position) under set_attention_mode(True), not decode_step,
-        and a token's bits depend on whether it entered in a run of >= 2 or alone (among cuts of >= 2 tokens each the cut does not matter)."""
+        and a token's bits depend on whether it entered in a run of >= 2 or alone (among cuts of >= 2 tokens each the cut does not matter).
+        After set_option("multi_extend_la_chunk", 1) a run of >= 64 tokens takes the prompt pass's chunked delta rule in its linear-attention
+        layers (tolerance form, docs/design/26-multi-extend-la-chunk.md): with both options a run of 2 .. 1024 tokens on a hybrid store equals
+        prefill(run, position) under set_attention_mode(True).  A token's bits then also depend on whether its run had >= 64 tokens and on where
+        the 64-token sub-chunk edges fall: cuts at multiples of 64 tokens (the last call any length >= 64) give the bits of one call."""
         if len(token_lists) != len(slots) or len(positions) != len(slots):
             raise ValueError(f"{len(slots)} slots, {len(token_lists)} token lists, {len(positions)} positions")
         return self._step_multi(self._lib.kr_decode_extend_multi, slots, [len(run) for run in token_lists], [int(t) for run in token_lists for t in run],
@@ -649,7 +661,9 @@ class CpuDecodeStore:
         prefill(tokens, start_pos) + save_slot bit for bit, and the store's own sequence, logits and last token are never touched.  Returns the greedy id
         after the last token.  After set_option("multi_extend_flash", 1) every chunk of two or more tokens takes the prompt pass's flash attention in
         its GQA layers (see extend_multi): the slot then equals prefill under set_attention_mode(True) on a store of GQA layers, and a last chunk
-        of one token is an exact step."""
+        of one token is an exact step.  After set_option("multi_extend_la_chunk", 1) every chunk of 64 or more tokens takes the prompt pass's chunked
+        delta rule in its linear-attention layers (see extend_multi); a last chunk of fewer than 64 tokens takes the exact run kernels, as the
+        store's own fast prompt pass does."""
         from ._lib import KR_EXTEND_MAX_TOKENS
         chunk = KR_EXTEND_MAX_TOKENS if chunk is None else int(chunk)
         if not 1 <= chunk <= KR_EXTEND_MAX_TOKENS:

@@ -32,8 +32,8 @@ int main(int argc, char** argv) {
     a.Wh = pl; a.Wl = a.Wh + tiles * 128; a.Qh = a.Wl + tiles * 128; a.Ql = a.Qh + tiles * 128; a.Kh = a.Ql + tiles * 128; a.Kl = a.Kh + tiles * 128;
     // correctness first: one run from a zero state against the per-token recurrence (decode.rs:1293) in double on the host, a few heads
     {
-        hipLaunchKernelGGL(kr_lac_prep_kernel, dim3(a.n_sub, nv), dim3(LC_PTH), LC_PREP_LDS, st, a);
-        hipLaunchKernelGGL(kr_lac_scan_kernel, dim3(nv * 4), dim3(256), LC_SCAN_LDS, st, a);
+        hipLaunchKernelGGL(kr_lac_prep_kernel<KrLacChunk>, dim3(a.n_sub, nv), dim3(LC_PTH), LC_PREP_LDS, st, a);
+        hipLaunchKernelGGL(kr_lac_scan_kernel<KrLacChunk>, dim3(nv * 4), dim3(256), LC_SCAN_LDS, st, a);
         CK(hipStreamSynchronize(st));
         std::vector<float> ho(nq), hs((size_t)nv * 128 * 128), hg((size_t)C * nv), hb((size_t)C * nv);
         CK(hipMemcpy(ho.data(), out, nq * 4, hipMemcpyDeviceToHost)); CK(hipMemcpy(hs.data(), state, hs.size() * 4, hipMemcpyDeviceToHost));
@@ -63,9 +63,9 @@ int main(int argc, char** argv) {
     }
     for (int rep = 0; rep < 4; rep++) {
         CK(hipEventRecord(e0, st));
-        hipLaunchKernelGGL(kr_lac_prep_kernel, dim3(a.n_sub, nv), dim3(LC_PTH), LC_PREP_LDS, st, a);
+        hipLaunchKernelGGL(kr_lac_prep_kernel<KrLacChunk>, dim3(a.n_sub, nv), dim3(LC_PTH), LC_PREP_LDS, st, a);
         CK(hipEventRecord(e1, st));
-        hipLaunchKernelGGL(kr_lac_scan_kernel, dim3(nv * 4), dim3(256), LC_SCAN_LDS, st, a);
+        hipLaunchKernelGGL(kr_lac_scan_kernel<KrLacChunk>, dim3(nv * 4), dim3(256), LC_SCAN_LDS, st, a);
         CK(hipEventRecord(e2, st)); CK(hipStreamSynchronize(st));
         float m0, m1; CK(hipEventElapsedTime(&m0, e0, e1)); CK(hipEventElapsedTime(&m1, e1, e2));
         unsigned long long s[64]; CK(hipMemcpyFromSymbol(s, HIP_SYMBOL(kr_lstamps), sizeof(s)));

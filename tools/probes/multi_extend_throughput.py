@@ -17,6 +17,12 @@ and no option call (a library built from another commit, loaded through KRASIS_H
 slots and nothing else, option on (with --off-only: off; with --admission: one 4096-token admission instead), for a rocprofv3 --kernel-trace --stats run.
 
     python tools/probes/multi_extend_throughput.py [out.txt] --flash [--off-only] [--profile [--admission]]
+
+--la-chunk: the same legs for the "multi_extend_la_chunk" option (docs/design/26-multi-extend-la-chunk.md): "multi_extend_flash" stays on throughout and the
+new option alternates off and on call by call.  --off-only, --profile and --admission as under --flash (--off-only never names the new option, so it also runs
+against a library built from the commit before it).
+
+    python tools/probes/multi_extend_throughput.py [out.txt] --la-chunk [--off-only] [--profile [--admission]]
 """
 import os
 import statistics
@@ -38,8 +44,8 @@ def timed(fn, warm, reps):
     return statistics.median(ts[warm:])
 
 
-def flash_legs(out_path, off_only, profile):
-    """option off / on, alternating call by call: admission (prefill_slot) and the mixed pass, flat and paged"""
+def flash_legs(out_path, off_only, profile, opt="multi_extend_flash", fixed=()):
+    """option `opt` off / on, alternating call by call: admission (prefill_slot) and the mixed pass, flat and paged; the options of `fixed` stay on"""
     kv = 4096 + 160
     eng, st, keep = bench.build_qcn(0, 0, 48, rope_len=kv, kv_fp8=True)
     lines = []
@@ -54,10 +60,12 @@ def flash_legs(out_path, off_only, profile):
     nslots, adm, chunk_slot = N_DECODE + 2, N_DECODE, N_DECODE + 1
     rows = list(range(N_DECODE))
     legs = (0,) if off_only else (0, 1)
+    for f in fixed:
+        st.set_option(f, 1)
 
     def option(v):
         if not off_only:
-            st.set_option("multi_extend_flash", v)
+            st.set_option(opt, v)
 
     def alternate(fn, warm, reps):
         """fn(i) under option off and on in turn -> the median seconds of each leg's timed calls"""
@@ -106,6 +114,8 @@ def main():
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
     out_path = args[0] if args else None
     profile = "--profile" in sys.argv
+    if "--la-chunk" in sys.argv:
+        return flash_legs(out_path, "--off-only" in sys.argv, profile, "multi_extend_la_chunk", ("multi_extend_flash",))
     if "--flash" in sys.argv:
         return flash_legs(out_path, "--off-only" in sys.argv, profile)
     kv = 4096 + 160
