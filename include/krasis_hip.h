@@ -291,6 +291,17 @@ int kr_decode_set_attention_mode(kr_decode_store* s, int mode);
  * whose lengths are multiples of 64, the last one any length >= 64, gives the bits of one call.  Refused by every batched entry point, behind everything they
  * refused before, each message naming the option: a store without a linear-attention layer or with an MLA layer (KR_ERR_STATE), a linear-attention layer
  * outside dk = dv = 128 with nv = nk * hr (KR_ERR_VALUE), an LDS window refusal (KR_ERR_HIP).
+ * "multi_extend_mla_flash" (default 0; docs/design/27-multi-extend-mla-flash.md): in a non-verify batched pass (kr_decode_extend_multi) the MLA layers give every
+ * run of counts[i] >= 2 tokens causal flash attention over its slot's latent and rope-key rows, flat or paged, on the f16 matrix cores, 64 (token, head) query
+ * rows per workgroup: run i carries the bits of kr_decode_prefill(tokens, positions[i]) under KR_ATTN_FAST on the store's own sequence holding the same prefix
+ * -- the last token's logits and id and every latent / rope-key row the run appends -- whatever other rows share the pass; the slot's cache is streamed once per
+ * 64 query rows instead of once per (token, 4 heads), and no score scratch is needed for those rows.  Runs of one token (kr_decode_step_multi*,
+ * kr_decode_generate_multi*, decode rows of a mixed pass) keep exactly what they had -- the exact kernel, or the flash-decode of "multi_mla_fast", which
+ * composes with this option --, verify passes are untouched; within 3e-3 (FP16 caches) / 2e-2 (E4M3) of the exact run (docs/design/02-numerics.md 2b).
+ * Consequence: under the option a token's bits depend on whether it entered in a run of >= 2 tokens or alone -- as the store's KR_ATTN_FAST prompt pass differs
+ * from its decode step; among cuts of >= 2 tokens each the result does not depend on the cut.  Refused by every batched entry point, behind everything they
+ * refused before, each message naming the option: a store without an MLA layer (KR_ERR_STATE), an LDS window refusal (KR_ERR_HIP).  "multi_extend_flash" and
+ * "multi_extend_la_chunk" keep refusing a store with an MLA layer.
  * "gguf_exact_pass" (default 0; docs/design/20-gguf-exact-pass.md): with 1, every multi-row pass of the store -- kr_decode_prefill, kr_decode_prefill_nll,
  * kr_decode_verify and the batched pass behind every slot entry point -- runs MoE layers that hold native GGUF blocks through the exact grouped block
  * kernels (kr_gguf_group.hip) instead of the int8-MFMA form: every row then carries the bits of kr_decode_step on that sequence alone, and the slot and
@@ -453,7 +464,9 @@ int kr_decode_generate_multi_sample(kr_decode_store* s, int n, const int32_t* sl
    decode rows (counts 1) of other slots; the store's own sequence is never touched.  Distinct slots, 1 <= n <= KR_MULTI_MAX.  Refused as
    kr_decode_step_multi refuses (same codes), and as KR_ERR_VALUE naming the row: a count < 1, T > KR_EXTEND_MAX_TOKENS, a token of a run outside the
    vocabulary, a run that ends outside the slot or past a rope table; a refused call changes nothing.  Under "multi_attn_fast" over slots of
-   max_seq > 1024 every token carries the bits kr_decode_step_multi gives it under the option. */
+   max_seq > 1024 every token carries the bits kr_decode_step_multi gives it under the option.  Under "multi_extend_mla_flash" a run of counts[i] >= 2 tokens
+   takes the KR_ATTN_FAST prompt pass's MLA flash attention over its slot instead and carries the bits of kr_decode_prefill under KR_ATTN_FAST, not of
+   kr_decode_step (a tolerance form: see kr_decode_set_option); rows of one token keep the bits stated here. */
 #define KR_EXTEND_MAX_TOKENS 1024      /* = the exact prompt pass's chunk */
 int kr_decode_extend_multi(kr_decode_store* s, int n, const int32_t* slots, const int32_t* counts, const int32_t* tokens, const int32_t* positions,
                            int32_t* next_out, float* logits_out, int sample, void* stream);

@@ -55,7 +55,8 @@ struct kr_multi_state {
     // "multi_extend_la_chunk": the LDS windows of the chunked delta rule's two kernels are raised (kr_exact_refuse, once per slot set); the pass's chunked runs
     // [run, first tile] and behind them their sub-chunks [run, sub] (kr_lc_tiles.h); the rule's scratch of one layer, sized by the pass's sub-chunks
     bool lc_ready = false; DevBuf lc_tiles, lc_scratch;
-    bool mla_fd_ready = false;                 // "multi_mla_fast": the partials of one MLA layer, [n][chunks][nh][klr] and [n][nh][chunks][2], share fd_o / fd_ml (sized for the larger need); the kernels' LDS windows are raised
+    bool mf_ready = false; DevBuf mf_tiles;    // "multi_extend_mla_flash": the LDS windows of the run kernel are raised (kr_exact_refuse, once per slot set); the pass's query-row tiles [run, tile_row] per head count (kr_mf_tiles.h)
+    bool mla_fd_ready = false;               // "multi_mla_fast": the partials of one MLA layer, [n][chunks][nh][klr] and [n][nh][chunks][2], share fd_o / fd_ml (sized for the larger need); the kernels' LDS windows are raised
     // per-slot samplers (kr_decode_slot_sampler, docs/design/14-multi-sampling.md): allocated for every slot on the first call; empty = every slot greedy
     struct Sampler { float temperature = 0.0f, top_p = 1.0f, penalty = 0.0f; int top_k = 0; };
     std::vector<Sampler> smp; size_t smp_words = 0;   // host: parameters per slot; seen-bitmap words per slot
@@ -102,7 +103,8 @@ struct kr_decode_store {
     int opt_multi_mla_fast = 0;                  // kr_decode_set_option("multi_mla_fast"): the MLA layers of every batched multi-sequence step run split-KV flash-decode over slots longer than mla_split_min, flat or paged (tolerance form, docs/design/24-multi-mla-fast.md); the mode bits stay refused
     int opt_multi_extend_flash = 0;              // kr_decode_set_option("multi_extend_flash"): in a non-verify batched pass the GQA layers give every run of >= 2 tokens causal flash attention over its slot, flat or paged -- the bits of the KR_ATTN_FAST prompt pass (tolerance form, docs/design/25-multi-extend-flash.md); runs of one token keep what they had; the mode bits stay refused
     int opt_multi_extend_la_chunk = 0;           // kr_decode_set_option("multi_extend_la_chunk"): in a non-verify batched pass the linear-attention layers give every run of >= 64 tokens the chunked delta rule of the KR_ATTN_FAST prompt pass, fused form -- its bits (tolerance form, docs/design/26-multi-extend-la-chunk.md); shorter runs keep the exact run kernels; the mode bits stay refused
-    int opt_gen_lookahead = 0;                    // kr_decode_set_option("generate_lookahead"): generate_batch feeds the sampled token back ON THE DEVICE and queues step i + 1 before the host has read token i
+    int opt_multi_extend_mla_flash = 0;          // kr_decode_set_option("multi_extend_mla_flash"): in a non-verify batched pass the MLA layers give every run of >= 2 tokens causal flash attention over its slot's latent rows, flat or paged -- the bits of the KR_ATTN_FAST prompt pass (tolerance form, docs/design/27-multi-extend-mla-flash.md); runs of one token keep what they had; the mode bits stay refused
+    int opt_gen_lookahead = 0;                   // kr_decode_set_option("generate_lookahead"): generate_batch feeds the sampled token back ON THE DEVICE and queues step i + 1 before the host has read token i
     int opt_ep_graph = 0;                         // kr_decode_set_option("ep_graph"): expert-parallel decode over RCCL replays a captured graph (the all-reduce is captured with the kernels)
     uint64_t ep_generation_seen = 0;               // kr_engine::ep_generation at the last step: a new / destroyed communicator invalidates the graph and restarts the warm-up
     int ep_eager_steps = 0;                        // expert-parallel decode: steps enqueued eagerly so far (RCCL warms up outside any capture)

@@ -19,6 +19,7 @@
 #include "../../include/krasis_hip.h"
 #include "kr_pf_tiles.h"
 #include "kr_lc_tiles.h"
+#include "kr_mf_tiles.h"
 #include "kr_decode_internal.h"
 #include "kr_prefill.h"
 #include "kr_prefill_ops.h"
@@ -52,6 +53,10 @@ struct Chunk {      // one chunk of the prompt in flight: its arena, stream and 
     // ... "multi_extend_la_chunk", a pass with a run of >= 64 tokens: its chunked runs [run, first tile] and their sub-chunks [run, sub] (device, kr_lc_tiles.h),
     // the number of shorter runs and the chunked rule's scratch of one layer.  Null: every run takes the exact run kernels
     const int32_t* m_lc_runs = nullptr; const int32_t* m_lc_tiles = nullptr; int m_lc_nruns = 0, m_lc_ntiles = 0, m_lc_short = 0; float* m_lc_scratch = nullptr;
+    // ... "multi_extend_mla_flash", a pass with a run of >= 2 tokens: the query-row tiles [run, tile_row] of its runs (device), one table per head count among
+    // the MLA layers: m_mf[k] = {nh, first tile, tiles} (kr_mf_tiles.h); m_mf_units = its runs of one token.  Null: every row takes the per-row MLA kernels
+    struct MfTab { int nh, off, n; };
+    const int32_t* m_mf_tiles = nullptr; std::vector<MfTab> m_mf; int m_mf_units = 0;
     bool m_verify = false;      // kr_decode_verify_multi's pass: linear-attention layers record instead of storing state (docs/design/18-multi-verify.md)
 };
 size_t al(size_t n) { return (n + 255) & ~(size_t)255; }
@@ -238,6 +243,12 @@ static int run_layer(kr_decode_store* s, Chunk& cx, size_t li) {
             m.nh = L.nh; m.klr = L.klr; m.nd = L.nd; m.rd = L.rd; m.vhd = L.vhd; m.eps = s->eps; m.sm_scale = L.sm_scale;
             if (M.pg.paged()) { m.page_table = (const int*)M.pg_table.p; m.page_stride = M.pg.stride; m.page_shift = M.pg.shift; }      // paged slots: the strides are a page's bytes
             if (cx.m_mla_chunks) { m.fd_o = (float*)M.fd_o.p; m.fd_ml = (float*)M.fd_ml.p; m.fd_chunk = cx.m_mla_chunk; m.fd_chunks = cx.m_mla_chunks; }      // "multi_mla_fast", long slots
+            if (cx.m_mf_tiles) {      // "multi_extend_mla_flash": the runs of >= 2 tokens take the run kernel, the per-row kernels the first m_nruns rows
+                for (const Chunk::MfTab& t : cx.m_mf)
+                    if (t.nh == L.nh) { m.mf_tiles = cx.m_mf_tiles + 2 * (size_t)t.off; m.mf_ntiles = t.n; }
+                m.mf_runs = cx.m_runs; m.mf_nruns = cx.m_nruns; m.mf_units = cx.m_mf_units;
+                if (!m.mf_tiles || !kr_multi_mla_pf_args_ok(m)) return kr_fail(KR_ERR_VALUE, "multi_extend_mla_flash: MLA geometry of layer %zu not covered by the run kernel", li);
+            }
             if (nkv < L.klr + L.rd) return kr_fail(KR_ERR_VALUE, "kv_a_proj rows %d < kv_lora_rank + rope dim", nkv);
             if (oc != L.nh * L.vhd) return kr_fail(KR_ERR_VALUE, "o_proj cols %d != nh*v_head_dim", oc);
             if (kr_launch_multi_mla(m, Cc, st)) return kr_fail(KR_ERR_VALUE, "unsupported MLA geometry for the multi-sequence step");
@@ -654,12 +665,29 @@ int kr_exact_refuse(kr_decode_store* s, bool slots) {
         }
         if (!mla) return kr_fail(KR_ERR_STATE, "the \"multi_mla_fast\" option covers MLA layers only: this store has none (set the option to 0 for the exact step)");
     }
+    // paged slots under "multi_attn_fast" alone: the entry point refuses the call a few lines on with the words it always had (paged_refuse in kr_decode_multi.cpp),
+    // unless its argument check does first; the clauses of the run options below stand back so that refusal stays ahead of theirs
+    const bool paged_refused = slots && s->multi && s->multi->pg.paged() && s->opt_multi_attn_fast && !s->opt_multi_attn_fast_paged;
+    // "multi_extend_mla_flash", behind everything refused before the option existed.  A store without an MLA layer: an option that silently does nothing is a trap.
+    // The run kernel's geometry rule (kr_launch_mla_flash's: kv_lora_rank 512 / 256, rope 64, any head count) is kr_multi_mla_ok's, which the loop above has asked
+    // of every MLA layer.  The LDS windows of the run kernel's instantiations are raised here, once per slot set: a refusal leaves nothing reserved or advanced
+    if (slots && s->opt_multi_extend_mla_flash && !paged_refused) {
+        bool mla = false;
+        for (const DLayer& L : s->layers) mla |= L.attn == ATTN_MLA;
+        if (!mla) return kr_fail(KR_ERR_STATE, "the \"multi_extend_mla_flash\" option covers MLA layers only: this store has none (set the option to 0 for the exact pass)");
+        if (s->multi && !s->multi->mf_ready) {
+            KR_HIP(hipSetDevice(e->device));
+            for (const DLayer& L : s->layers)
+                if (L.attn == ATTN_MLA && kr_multi_mla_pf_prepare(L.klr, s->multi->kv_fp8, s->multi->pg.paged()))
+                    return kr_fail(KR_ERR_HIP, "multi_extend_mla_flash: LDS window of the run kernel refused (kv_lora_rank %d)", L.klr);
+            s->multi->mf_ready = true;
+        }
+    }
     // "multi_extend_flash", behind everything refused before the option existed.  An MLA layer: its runs would stay exact beside flash GQA runs, and no
     // single-sequence pass is like that.  No GQA layer: an option that silently does nothing is a trap.  A geometry outside the prompt pass's flash kernels is an
     // error, not a fall-back.  The LDS windows of the run kernels are raised here, once per slot set: a refusal leaves nothing reserved or advanced
     // (paged slots under "multi_attn_fast" alone: the entry point refuses the call a few lines on with the words it always had, paged_refuse in kr_decode_multi.cpp,
     // unless its argument check does first; this clause stands back so that refusal stays ahead of it)
-    const bool paged_refused = slots && s->multi && s->multi->pg.paged() && s->opt_multi_attn_fast && !s->opt_multi_attn_fast_paged;
     if (slots && s->opt_multi_extend_flash && !paged_refused) {
         bool gqa = false;
         for (size_t i = 0; i < s->layers.size(); i++)
@@ -832,6 +860,18 @@ int kr_multi_pass(kr_decode_store* s, int n, int n_final, const int32_t* d_rows,
         if (pf) { attn_rows = n_final; attn_pos = unit_pos; }
     }
     const bool row_attn = !pf || n_unit > 0;      // some row takes the per-row attention kernels
+    // "multi_extend_mla_flash": the same for the MLA layers (docs/design/27-multi-extend-mla-flash.md): a non-verify pass with a run of >= 2 tokens gives those
+    // runs the run kernel, and the per-row MLA kernels see the unit rows only.  The option and "multi_extend_flash" never meet in a pass (that one refuses a store
+    // with an MLA layer), so on a store of MLA layers alone the score rows and the "multi_mla_fast" partials are sized by n_final rows and the unit rows' longest
+    // position; a store that also has GQA layers keeps their rows (n at max_pos), which hold the MLA unit rows too.  Off, or every run of one token: as ever
+    bool mf = false; int mf_unit = 0, mla_rows = n, mla_pos = max_pos;
+    if (s->opt_multi_extend_mla_flash && !verify && has_mla && h_counts && h_positions) {
+        int unit_pos = -1;
+        for (int i = 0; i < n_final; i++) { if (h_counts[i] >= 2) mf = true; else { mf_unit++; unit_pos = std::max(unit_pos, h_positions[i]); } }
+        if (mf) { mla_rows = n_final; mla_pos = unit_pos; }
+        if (mf && !has_gqa) { attn_rows = n_final; attn_pos = unit_pos; }
+    }
+    const bool mla_row_attn = !mf || mf_unit > 0;      // some row takes the per-row MLA kernels
     int fd_chunk = 0, fd_chunks = 0, mla_chunk = 0, mla_chunks = 0;
     size_t fd_o_bytes = 0, fd_ml_bytes = 0;
     if (flash && row_attn) {
@@ -847,20 +887,20 @@ int kr_multi_pass(kr_decode_store* s, int n, int n_final, const int32_t* d_rows,
         }
         fd_o_bytes = (size_t)attn_rows * fd_chunks * gqa_row * 4; fd_ml_bytes = (size_t)attn_rows * nh_max * fd_chunks * 8;
     }
-    if (mla_flash) {
-        mla_chunk = kr_mla_flash_decode_chunk(M.max_seq); mla_chunks = (max_pos + mla_chunk) / mla_chunk;
-        if (mla_chunks > 1024) return kr_fail(KR_ERR_VALUE, "multi_mla_fast: position %d needs %d chunks of %d positions (at most 1024)", max_pos, mla_chunks, mla_chunk);
+    if (mla_flash && mla_row_attn) {
+        mla_chunk = kr_mla_flash_decode_chunk(M.max_seq); mla_chunks = (mla_pos + mla_chunk) / mla_chunk;
+        if (mla_chunks > 1024) return kr_fail(KR_ERR_VALUE, "multi_mla_fast: position %d needs %d chunks of %d positions (at most 1024)", mla_pos, mla_chunks, mla_chunk);
         if (!M.mla_fd_ready) {
             for (const DLayer& L : s->layers)
                 if (L.attn == ATTN_MLA && kr_multi_mla_fd_prepare(L.klr, M.kv_fp8, M.pg.paged()))
                     return kr_fail(KR_ERR_HIP, "multi_mla_fast: LDS window of the flash-decode kernel refused (kv_lora_rank %d)", L.klr);
             M.mla_fd_ready = true;
         }
-        fd_o_bytes = std::max(fd_o_bytes, (size_t)n * mla_chunks * mla_row * 4); fd_ml_bytes = std::max(fd_ml_bytes, (size_t)n * nh_max * mla_chunks * 8);
+        fd_o_bytes = std::max(fd_o_bytes, (size_t)mla_rows * mla_chunks * mla_row * 4); fd_ml_bytes = std::max(fd_ml_bytes, (size_t)mla_rows * nh_max * mla_chunks * 8);
     }
-    if (((flash && row_attn) || mla_flash) && (M.fd_o.ensure(fd_o_bytes) || M.fd_ml.ensure(fd_ml_bytes)))
+    if (((flash && row_attn) || (mla_flash && mla_row_attn)) && (M.fd_o.ensure(fd_o_bytes) || M.fd_ml.ensure(fd_ml_bytes)))
         return kr_fail(KR_ERR_HIP, "hipMalloc of the multi-sequence step's split-KV partials (%zu MiB) failed", (fd_o_bytes + fd_ml_bytes) >> 20);
-    const bool need_scores = (has_gqa && !flash && row_attn) || (has_mla && !mla_flash);
+    const bool need_scores = (has_gqa && !flash && row_attn) || ((has_mla && !mla_flash) && mla_row_attn);
     const int sc_ld = (attn_pos + 1 + 31) & ~31;
     const int n_logits = verify ? n : n_final;      // a verify pass: the lm_head over every token row (what Chunk::verify is to the store's own pass)
     if (M.scratch.ensure(Lo.total) || (need_scores && M.scores.ensure((size_t)attn_rows * nh_max * sc_ld * 4)) || M.logits.ensure((size_t)n_logits * s->vocab * 4))
@@ -885,6 +925,20 @@ int kr_multi_pass(kr_decode_store* s, int n, int n_final, const int32_t* d_rows,
         if (M.pf_tiles.ensure(std::max(all.size() * 4, (size_t)65536))) return kr_fail(KR_ERR_HIP, "hipMalloc of the multi-sequence pass's query tiles failed");
         KR_HIP(hipMemcpyAsync(M.pf_tiles.p, all.data(), all.size() * 4, hipMemcpyHostToDevice, st));      // pageable source: staged before the call returns
         cx.m_pf_tiles = (const int32_t*)M.pf_tiles.p; cx.m_pf_units = n_unit;
+    }
+    if (mf) {      // the query-row tiles of the runs, one table per head count among the MLA layers (64 (token, head) rows each), behind one another in M.mf_tiles
+        std::vector<int32_t> all, one;
+        for (const DLayer& L : s->layers) {
+            if (L.attn != ATTN_MLA) continue;
+            bool have = false;
+            for (const Chunk::MfTab& t : cx.m_mf) have |= t.nh == L.nh;
+            if (have) continue;
+            cx.m_mf.push_back(Chunk::MfTab{L.nh, (int)(all.size() / 2), kr_mf_build_tiles(n_final, h_counts, L.nh, one).n_tiles});
+            all.insert(all.end(), one.begin(), one.end());
+        }
+        if (M.mf_tiles.ensure(std::max(all.size() * 4, (size_t)65536))) return kr_fail(KR_ERR_HIP, "hipMalloc of the multi-sequence pass's MLA query tiles failed");
+        KR_HIP(hipMemcpyAsync(M.mf_tiles.p, all.data(), all.size() * 4, hipMemcpyHostToDevice, st));      // pageable source: staged before the call returns
+        cx.m_mf_tiles = (const int32_t*)M.mf_tiles.p; cx.m_mf_units = mf_unit;
     }
     // "multi_extend_la_chunk": a non-verify pass with a run of >= 64 tokens gives those runs the chunked delta rule (docs/design/26-multi-extend-la-chunk.md).
     // One table for every linear-attention layer -- the chunked runs, then their sub-chunks -- and one scratch, sized by the widest layer.  Off, a verify pass or

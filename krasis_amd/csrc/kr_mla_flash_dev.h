@@ -1,7 +1,8 @@
 // kr_mla_flash_dev.h -- MLA flash attention on the f16 matrix cores as a device function.  kr_mla_flash_kernel (kr_mla_flash.hip: the prompt pass and, in its
 // SPLIT form, the store's own KR_ATTN_FAST decode step) and kr_multi_mla_flash_kernel (kr_multi_mla_flash.hip, the batched step under "multi_mla_fast") call
-// the same body, so a row of a batched step carries the bits of the single-sequence fast step (docs/design/24-multi-mla-fast.md).  The callers differ only in
-// where the position, the query rows, the cache rows and the partials come from.
+// the same body, so a row of a batched step carries the bits of the single-sequence fast step (docs/design/24-multi-mla-fast.md); so does
+// kr_multi_mla_pf_flash_kernel (kr_multi_mla_pf_flash.hip, a run of tokens entering a slot under "multi_extend_mla_flash"), whose runs carry the bits of the
+// prompt pass (docs/design/27-multi-extend-mla-flash.md).  The callers differ only in where the position, the query rows, the cache rows and the partials come from.
 //
 // In the absorbed form (decode.rs:2993-3252; the reference's GPU side: flashinfer MLA, attention.py:300-349) ALL heads of ALL tokens of a tile
 // attend over the SAME rows:   s[h][p] = (q_abs[h] . ckv[p] + q_pe[h] . kpe[p]) * sm_scale,   out[h] = sum_p softmax(s)[p] * ckv[p]
@@ -42,10 +43,17 @@ __device__ __forceinline__ uint32_t mf_f2h2(float a, float b) { return __builtin
 // (ptab[p >> psh] << psh) | (p & mask) of both.  A tile of MF_TK positions starts at a multiple of MF_TK, so it lies in ONE page: the page id is
 // workgroup-uniform and the page's byte offsets in the two pools stay in scalar registers; a lane adds its row's offset inside the page.  Only the cache
 // addresses differ from the flat instantiation: the order of every operation is the same.
-template <int KLR, bool FP8, bool SPLIT, bool PAGED = false>
+// RowMap (docs/design/27-multi-extend-mla-flash.md): the rows above are the caller's own count from 0; rmap(row) is where that row lies in q_abs / q_pe / attn_lat.
+// The identity for a chunk of a prompt and for a decode row; a run of a batched pass maps its (token, head) rows to pass rows (kr_multi_mla_pf_flash.hip).  It
+// is asked for rows below C * nh only, where the query tile is loaded and where the non-SPLIT form writes attn_lat; positions, masks and kv_end stay in the
+// caller's rows
+struct KrMfRowsIdentity {
+    __device__ __forceinline__ int operator()(int row) const { return row; }
+};
+template <int KLR, bool FP8, bool SPLIT, bool PAGED = false, class RowMap = KrMfRowsIdentity>
 __device__ __forceinline__ void kr_mla_flash_body(const float* q_abs, const float* q_pe, const void* ckv_cache, const void* kpe_cache, int pos0, int C, int nh, float sm_scale,
                                                   float* attn_lat, float* fd_o, float* fd_ml, int tile_row, int chunk, int n_chunks, int chunk_tiles,
-                                                  const int* ptab = nullptr, int psh = 0) {
+                                                  const int* ptab = nullptr, int psh = 0, RowMap rmap = {}) {
     constexpr int RD = 64, DK = KLR + RD, KSTEPS = DK / 16, LDK = DK * 2 + 16, LDV = MF_TK * 2 + 16;
     constexpr int DBW = KLR / 64;                               // 32-dim output blocks per d-wave (two d-waves)
     constexpr int CB = FP8 ? 16 : 8;                            // dims per 16-byte global chunk
@@ -73,7 +81,8 @@ __device__ __forceinline__ void kr_mla_flash_body(const float* q_abs, const floa
             const int r = i / (DK / 8), c8 = i % (DK / 8), gr = row0 + r;
             u32x4 o = {0, 0, 0, 0};
             if (gr < nrows) {
-                const float* src = c8 < KLR / 8 ? q_abs + (size_t)gr * KLR + c8 * 8 : q_pe + (size_t)gr * RD + (c8 - KLR / 8) * 8;
+                const size_t qr = (size_t)rmap(gr);
+                const float* src = c8 < KLR / 8 ? q_abs + qr * KLR + c8 * 8 : q_pe + qr * RD + (c8 - KLR / 8) * 8;
                 const float4 x0 = *reinterpret_cast<const float4*>(src), x1 = *reinterpret_cast<const float4*>(src + 4);
                 o = u32x4{mf_f2h2(x0.x * sc, x0.y * sc), mf_f2h2(x0.z * sc, x0.w * sc), mf_f2h2(x1.x * sc, x1.y * sc), mf_f2h2(x1.z * sc, x1.w * sc)};
             }
@@ -223,7 +232,7 @@ __device__ __forceinline__ void kr_mla_flash_body(const float* q_abs, const floa
     }
     if (row_ok) {
         const float inv = l_run > 0.0f ? 1.0f / l_run : 0.0f;
-        float* out = attn_lat + (size_t)myrow * KLR + wd * (KLR / 2);
+        float* out = attn_lat + (size_t)rmap(myrow) * KLR + wd * (KLR / 2);
 #pragma unroll
         for (int db = 0; db < DBW; db++)
 #pragma unroll

@@ -116,7 +116,16 @@ struct KrMultiMlaArgs {
     // fd_chunk positions per chunk, fd_chunks = the longest row's chunk count.  Null: the exact per-slot kernel (scores is not read when they are set).  With
     // page_table set the chunk pass reads the pools through the table
     float *fd_o, *fd_ml; int fd_chunk, fd_chunks;
+    // "multi_extend_mla_flash" (kr_multi_mla_pf_flash.hip, docs/design/27-multi-extend-mla-flash.md), a non-verify pass with a run of >= 2 tokens: mf_runs = the
+    // pass's run table, mf_nruns x [slot, off, cnt] (above); mf_tiles = mf_ntiles x [run, tile_row], the tiles of 64 (token, head) query rows of the runs of >= 2
+    // tokens for this layer's head count (kr_mf_tiles.h); mf_units = the number of runs of one token.  The absorption, the prep launch and the w_vc projection
+    // cover all B rows; the per-row attention kernels run over the first mf_nruns rows and leave those of a run of >= 2 at once (scores / fd_o / fd_ml are then
+    // sized by mf_nruns rows), and are not launched when mf_units is 0; the runs take causal flash attention over their slots.  Null / 0 (the option is off, a
+    // verify pass, or every run has one token): none of this, B rows through the per-row kernels
+    const int* mf_runs; const int* mf_tiles; int mf_nruns, mf_ntiles, mf_units;
 };
+// row b < mf_nruns is the last token of a run of >= 2 tokens: not a row of the per-row MLA attention kernels (workgroup-uniform; false whenever mf_runs is null)
+__device__ __forceinline__ bool kr_m_row_in_run(const KrMultiMlaArgs& a, int b) { return a.mf_runs && a.mf_runs[3 * b + 2] >= 2; }
 // the geometries the per-slot MLA kernels are specialised for (klr 512 / 256 with rd 64; nd within the prep launch's LDS row)
 int kr_multi_mla_ok(int klr, int nd, int rd);
 // 0: launched (absorption, prep, attention -- the flash-decode pair when a.fd_o is set --, w_vc projection); 1: geometry not covered
@@ -127,6 +136,12 @@ int kr_launch_multi_mla(const KrMultiMlaArgs& a, int B, hipStream_t st);
 int kr_multi_mla_fd_ok(int nh, int klr, int rd);
 int kr_multi_mla_fd_prepare(int klr, int fp8, int paged);
 int kr_launch_multi_mla_fd(const KrMultiMlaArgs& a, int B, hipStream_t st);
+// the run kernel of "multi_extend_mla_flash" (after the prep launch): the geometry test is kr_launch_mla_flash's (kv_lora_rank 512 / 256, rope 64, any head
+// count); the LDS window of the kernel a layer takes (once per slot set, outside the pass; non-zero = refused; every instantiation is a kernel of its own);
+// grid (a.mf_ntiles)
+int kr_multi_mla_pf_args_ok(const KrMultiMlaArgs& a);      // what kr_launch_multi_mla_pf_flash checks: asked before anything of the layer is queued
+int kr_multi_mla_pf_prepare(int klr, int fp8, int paged);
+int kr_launch_multi_mla_pf_flash(const KrMultiMlaArgs& a, hipStream_t st);
 
 // paged slots: the pools of every layer, and the launch that makes freshly mapped pages read as zero in all of them -- grid (n_pages, n_pools), one launch per pass
 #define KR_PAGE_MIN_TOKENS 32      // = KR_MM_ROWS (kr_multi.hip): a stage of the MLA attention kernel never straddles a page

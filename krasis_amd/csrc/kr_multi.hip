@@ -515,6 +515,7 @@ __global__ void __launch_bounds__(512) kr_multi_mla_attn_kernel(const KrMultiMla
     float* pt = tile + 4 * KR_MG_TILE;               // [ROWS][HG]
     unsigned char* stage = reinterpret_cast<unsigned char*>(pt + ROWS * HG);      // [ROWS][pitch]
     const int row = blockIdx.y, hg0 = blockIdx.x * HG, nhg = min(HG, a.nh - hg0), t = threadIdx.x, lane = t & 63, w = t >> 6;
+    if (kr_m_row_in_run(a, row)) return;      // "multi_extend_mla_flash": the last token of a run of >= 2, attended to by the run kernel (workgroup-uniform, ahead of every barrier)
     const int seq = a.positions[row] + 1, nst = (seq + ROWS - 1) / ROWS;
     const size_t slot = (size_t)a.slots[row];
     float* sc = a.scores + ((size_t)row * a.nh + hg0) * a.sc_ld;                  // [nhg][sc_ld]
@@ -657,6 +658,36 @@ template <bool FP8, int NBC> static constexpr size_t kr_multi_mla_lds() {
 
 int kr_multi_mla_ok(int klr, int nd, int rd) { return (klr == 512 || klr == 256) && rd == 64 && nd >= 1 && nd <= 640; }
 
+// "multi_extend_mla_flash", a pass with a run of >= 2 tokens (docs/design/27-multi-extend-mla-flash.md): the absorption, the prep launch and the w_vc projection
+// over all B rows as ever; the per-row attention kernels -- the exact one, or the flash-decode pair when a.fd_o is set -- over the first mf_nruns rows, where
+// every unit row lies (the rows of longer runs leave at once), and not at all without a unit row; the run kernel over the query tiles
+static int multi_mla_runs(KrMultiMlaArgs& a, int B, hipStream_t st) {
+    // every check first: the prep launch appends rows to the slots, and a layer fails whole
+    if (a.mf_nruns < 1 || a.mf_nruns > B || a.mf_units < 0 || a.mf_units >= a.mf_nruns || !kr_multi_mla_pf_args_ok(a)) return 1;
+    if (a.mf_units && a.fd_o && (!kr_multi_mla_fd_ok(a.nh, a.klr, a.rd) || !a.fd_ml || a.fd_chunk < 32 || a.fd_chunk % 32 || a.fd_chunks < 1 || a.fd_chunks > 1024)) return 1;
+    if (a.mf_units && !a.fd_o && (!a.scores || a.sc_ld < 32)) return 1;
+    a.absorb_done = B >= 32 && kr_launch_mla_absorb_mfma(a.q_full, a.ld_q, a.nd + a.rd, a.nd, a.w_kc, a.klr, a.q_abs, B, a.nh, st) == 0;
+    const dim3 pg(a.nh * (a.absorb_done ? 1 : a.klr / 64) + 1, B), ag((a.nh + KR_MM_HG - 1) / KR_MM_HG, a.mf_nruns);
+    const bool rows = a.mf_units && !a.fd_o;      // the exact per-row kernel has a row to take
+#define KR_MRP(F_, P_) hipLaunchKernelGGL((kr_multi_mla_prep_kernel<F_, P_>), pg, dim3(64), 0, st, a)
+#define KR_MRA(F_, NBC_, P_) hipLaunchKernelGGL((kr_multi_mla_attn_kernel<F_, NBC_, P_>), ag, dim3(512), (kr_multi_mla_lds<F_, NBC_>()), st, a)
+#define KR_MRA_ALL(P_) do { \
+    if (a.kv_fp8) { KR_MRP(true, P_); if (!rows) break; if (a.klr == 512) KR_MRA(true, 64, P_); else KR_MRA(true, 32, P_); } \
+    else { KR_MRP(false, P_); if (!rows) break; if (a.klr == 512) KR_MRA(false, 64, P_); else KR_MRA(false, 32, P_); } } while (0)
+    if (a.page_table) KR_MRA_ALL(true); else KR_MRA_ALL(false);
+#undef KR_MRA_ALL
+#undef KR_MRA
+#undef KR_MRP
+    if (a.mf_units && a.fd_o && kr_launch_multi_mla_fd(a, a.mf_nruns, st)) return 1;
+    if (kr_launch_multi_mla_pf_flash(a, st)) return 1;
+    if (B >= 32 && kr_launch_mla_wvc_mfma(a.w_vc, a.attn_lat, a.v_proj, B, a.nh, a.vhd, a.klr, st) == 0) return 0;
+    KrMlaArgs m{};
+    m.step = nullptr; m.pos0 = 0; m.kv_out = a.kv_out; m.ld_kv = a.ld_kv; m.q_full = a.q_full; m.ld_q = a.ld_q; m.w_vc = a.w_vc;
+    m.q_abs = a.q_abs; m.q_pe = a.q_pe; m.attn_lat = a.attn_lat; m.v_proj = a.v_proj; m.nh = a.nh; m.klr = a.klr; m.nd = a.nd; m.rd = a.rd; m.vhd = a.vhd;
+    kr_launch_mla_wvc(m, st, B);
+    return 0;
+}
+
 int kr_launch_multi_mla(const KrMultiMlaArgs& a_in, int B, hipStream_t st) {
     KrMultiMlaArgs a = a_in;
     if (!kr_multi_mla_ok(a.klr, a.nd, a.rd) || a.nh < 1 || a.sc_ld % 32) return 1;
@@ -665,6 +696,7 @@ int kr_launch_multi_mla(const KrMultiMlaArgs& a_in, int B, hipStream_t st) {
     // "multi_mla_fast" (a.fd_o set): the same absorption and prep launch, then split-KV flash-decode over the slots, flat or paged
     // (kr_multi_mla_flash.hip) in place of the attention kernel; checked before anything is launched
     if (a.fd_o && (!kr_multi_mla_fd_ok(a.nh, a.klr, a.rd) || !a.fd_ml || a.fd_chunk < 32 || a.fd_chunk % 32 || a.fd_chunks < 1 || a.fd_chunks > 1024)) return 1;
+    if (a.mf_tiles) return multi_mla_runs(a, B, st);      // "multi_extend_mla_flash", a pass with a run of >= 2 tokens
     // the w_kc absorption, row-wise: from 32 rows on the matrix cores (one fma chain per output, the prompt pass's launch), the prep launch's tiles below
     a.absorb_done = B >= 32 && kr_launch_mla_absorb_mfma(a.q_full, a.ld_q, a.nd + a.rd, a.nd, a.w_kc, a.klr, a.q_abs, B, a.nh, st) == 0;
     const dim3 pg(a.nh * (a.absorb_done ? 1 : a.klr / 64) + 1, B), ag((a.nh + KR_MM_HG - 1) / KR_MM_HG, B);

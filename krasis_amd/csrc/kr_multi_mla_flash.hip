@@ -15,7 +15,9 @@
 // PAGED: ckv_cache / kpe_cache are the pools and the body walks the slot's row of the page table; the flat instantiation names no table
 template <int KLR, bool FP8, bool PAGED>
 __global__ void __launch_bounds__(256) kr_multi_mla_flash_kernel(const KrMultiMlaArgs a, int n_chunks, int chunk_tiles) {
-    const int c = blockIdx.x, b = blockIdx.y, pos = a.positions[b];
+    const int c = blockIdx.x, b = blockIdx.y;
+    if (kr_m_row_in_run(a, b)) return;      // "multi_extend_mla_flash": the last token of a run of >= 2, attended to by the run kernel (workgroup-uniform, ahead of every barrier)
+    const int pos = a.positions[b];
     const float* q_abs = a.q_abs + (size_t)b * a.nh * KLR;
     const float* q_pe = a.q_pe + (size_t)b * a.nh * 64;
     float* fd_o = a.fd_o + (size_t)b * n_chunks * a.nh * KLR;
@@ -35,6 +37,7 @@ __global__ void __launch_bounds__(256) kr_multi_mla_flash_kernel(const KrMultiMl
 template <int KLR>
 __global__ void __launch_bounds__(1024) kr_multi_mla_merge_kernel(const KrMultiMlaArgs a, int n_chunks, int chunk) {
     const int b = blockIdx.y;
+    if (kr_m_row_in_run(a, b)) return;      // its chunk pass left no partials
     kr_fd_merge2_body<KLR>(a.positions[b] + 1, blockIdx.x, a.fd_o + (size_t)b * n_chunks * a.nh * KLR, a.fd_ml + (size_t)b * a.nh * n_chunks * 2, a.nh, 1, nullptr, 0,
                            a.attn_lat + (size_t)b * a.nh * KLR, nullptr, n_chunks, chunk);
 }

@@ -322,6 +322,12 @@ class CpuDecodeStore:
         where the 64-token sub-chunk edges fall: calls cut at multiples of 64 (the last one any length >= 64) give the bits of one call.  A store
         without a linear-attention layer or with an MLA layer, or a linear-attention layer outside dk = dv = 128, is then refused by the batched
         calls (docs/design/26-multi-extend-la-chunk.md).
+        "multi_extend_mla_flash" (default 0): with 1 a run of two or more tokens entering a slot (extend_multi, prefill_slot) takes the prompt pass's
+        causal flash attention over the slot's latent and rope-key rows in its MLA layers, flat or paged -- tolerance form, the run bit-identical to
+        prefill(run, position) under set_attention_mode(True) on the store's own sequence holding the same prefix; runs of one token (step_multi,
+        generate_multi, decode rows beside a chunk) keep what they had, "multi_mla_fast" included, and verify passes are untouched.  A token's bits
+        then depend on whether it entered in a run of >= 2 or alone.  Within 3e-3 (FP16 caches) / 2e-2 (E4M3) of the exact run.  A store without an
+        MLA layer is then refused by the batched calls (docs/design/27-multi-extend-mla-flash.md).
         "gguf_exact_pass" (default 0): with 1 every multi-row pass (prefill, prefill_nll, verify, and the batched pass behind every slot call) runs
         native-GGUF MoE layers through the exact grouped block kernels -- every row carries the bits of decode_step on that sequence alone -- and the
         slot and speculation calls accept a store with such layers; slower than the default int8-MFMA form on long prompts; refused together with
@@ -580,7 +586,11 @@ class CpuDecodeStore:
         After set_option("multi_extend_la_chunk", 1) a run of >= 64 tokens takes the prompt pass's chunked delta rule in its linear-attention
         layers (tolerance form, docs/design/26-multi-extend-la-chunk.md): with both options a run of 2 .. 1024 tokens on a hybrid store equals
         prefill(run, position) under set_attention_mode(True).  A token's bits then also depend on whether its run had >= 64 tokens and on where
-        the 64-token sub-chunk edges fall: cuts at multiples of 64 tokens (the last call any length >= 64) give the bits of one call."""
+        the 64-token sub-chunk edges fall: cuts at multiples of 64 tokens (the last call any length >= 64) give the bits of one call.
+        After set_option("multi_extend_mla_flash", 1) a run of two or more tokens takes the prompt pass's flash attention in its MLA layers
+        (tolerance form, docs/design/27-multi-extend-mla-flash.md): it then equals prefill(run, position) under set_attention_mode(True), not
+        decode_step, and a token's bits depend on whether it entered in a run of >= 2 or alone (among cuts of >= 2 tokens each the cut does not
+        matter)."""
         if len(token_lists) != len(slots) or len(positions) != len(slots):
             raise ValueError(f"{len(slots)} slots, {len(token_lists)} token lists, {len(positions)} positions")
         return self._step_multi(self._lib.kr_decode_extend_multi, slots, [len(run) for run in token_lists], [int(t) for run in token_lists for t in run],
@@ -663,7 +673,9 @@ class CpuDecodeStore:
         its GQA layers (see extend_multi): the slot then equals prefill under set_attention_mode(True) on a store of GQA layers, and a last chunk
         of one token is an exact step.  After set_option("multi_extend_la_chunk", 1) every chunk of 64 or more tokens takes the prompt pass's chunked
         delta rule in its linear-attention layers (see extend_multi); a last chunk of fewer than 64 tokens takes the exact run kernels, as the
-        store's own fast prompt pass does."""
+        store's own fast prompt pass does.  After set_option("multi_extend_mla_flash", 1) every chunk of two or more tokens takes the prompt pass's
+        flash attention in its MLA layers (see extend_multi): the slot then equals prefill under set_attention_mode(True), and a last chunk of one
+        token is an exact step."""
         from ._lib import KR_EXTEND_MAX_TOKENS
         chunk = KR_EXTEND_MAX_TOKENS if chunk is None else int(chunk)
         if not 1 <= chunk <= KR_EXTEND_MAX_TOKENS:

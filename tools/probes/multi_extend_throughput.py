@@ -23,6 +23,11 @@ new option alternates off and on call by call.  --off-only, --profile and --admi
 against a library built from the commit before it).
 
     python tools/probes/multi_extend_throughput.py [out.txt] --la-chunk [--off-only] [--profile [--admission]]
+
+--mla-flash: the same legs for the "multi_extend_mla_flash" option (docs/design/27-multi-extend-mla-flash.md) on the 27-layer V2-Lite synthetic
+(bench.build_v2lite, MLA layers, E4M3 latent caches): the option alternates off and on call by call.  --off-only, --profile and --admission as under --flash.
+
+    python tools/probes/multi_extend_throughput.py [out.txt] --mla-flash [--off-only] [--profile [--admission]]
 """
 import os
 import statistics
@@ -44,10 +49,10 @@ def timed(fn, warm, reps):
     return statistics.median(ts[warm:])
 
 
-def flash_legs(out_path, off_only, profile, opt="multi_extend_flash", fixed=()):
+def flash_legs(out_path, off_only, profile, opt="multi_extend_flash", fixed=(), v2lite=False):
     """option `opt` off / on, alternating call by call: admission (prefill_slot) and the mixed pass, flat and paged; the options of `fixed` stay on"""
     kv = 4096 + 160
-    eng, st, keep = bench.build_qcn(0, 0, 48, rope_len=kv, kv_fp8=True)
+    eng, st, keep = bench.build_v2lite(0, 0, 27, rope_len=kv, kv_fp8=True) if v2lite else bench.build_qcn(0, 0, 48, rope_len=kv, kv_fp8=True)
     lines = []
 
     def log(s):
@@ -114,6 +119,8 @@ def main():
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
     out_path = args[0] if args else None
     profile = "--profile" in sys.argv
+    if "--mla-flash" in sys.argv:
+        return flash_legs(out_path, "--off-only" in sys.argv, profile, "multi_extend_mla_flash", v2lite=True)
     if "--la-chunk" in sys.argv:
         return flash_legs(out_path, "--off-only" in sys.argv, profile, "multi_extend_la_chunk", ("multi_extend_flash",))
     if "--flash" in sys.argv:
