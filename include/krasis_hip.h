@@ -302,6 +302,18 @@ int kr_decode_set_attention_mode(kr_decode_store* s, int mode);
  * from its decode step; among cuts of >= 2 tokens each the result does not depend on the cut.  Refused by every batched entry point, behind everything they
  * refused before, each message naming the option: a store without an MLA layer (KR_ERR_STATE), an LDS window refusal (KR_ERR_HIP).  "multi_extend_flash" and
  * "multi_extend_la_chunk" keep refusing a store with an MLA layer.
+ * "multi_extend_exact_mfma" (default 0; docs/design/28-multi-extend-exact-mfma.md): in a non-verify batched pass (kr_decode_extend_multi) the GQA layers give every
+ * run of counts[i] >= 2 tokens the three attention passes of the exact prompt pass over its slot, flat or paged: scores on the f32 matrix cores (8 fma lanes per
+ * (query, position), the reference's add tree, * sm_scale), the exact softmax (max, libm exp, sum in position order, 1 / sum), P.V on the f32 matrix cores (one fma
+ * chain per output over ascending positions with p = e * inv, then the sigmoid gate) -- value for value the arithmetic of the per-slot kernel, so every call
+ * gives, bit for bit, what it gives with the option off: ids, logits, every K / V row, every conv and recurrent state, on flat, paged and forked slots, FP16 and
+ * E4M3 caches, whatever other rows share the pass and however the stream is cut.  The slot's K rows are staged once per 64 / G query tokens and its V rows once
+ * per 32 / G (G = heads per KV head) instead of once per token; the score rows stay.  Runs of one token keep their kernel -- the exact per-slot kernel, or the
+ * split-KV flash-decode under "multi_attn_fast" / "multi_attn_fast_paged": a mixed pass then gives its unit rows that option's bits and its runs of >= 2 the
+ * exact bits --, verify passes, linear-attention and MLA layers are untouched, "multi_extend_la_chunk" composes with the option and keeps its own bits.  Refused
+ * by every batched entry point, behind everything they refused before, each message naming the option: together with "multi_extend_flash" (KR_ERR_STATE: two
+ * options claim the same runs), a store without a GQA layer (KR_ERR_STATE), a GQA layer whose heads per KV head do not divide 32 (KR_ERR_VALUE: an error, not a
+ * fall-back to the per-slot kernel).
  * "gguf_exact_pass" (default 0; docs/design/20-gguf-exact-pass.md): with 1, every multi-row pass of the store -- kr_decode_prefill, kr_decode_prefill_nll,
  * kr_decode_verify and the batched pass behind every slot entry point -- runs MoE layers that hold native GGUF blocks through the exact grouped block
  * kernels (kr_gguf_group.hip) instead of the int8-MFMA form: every row then carries the bits of kr_decode_step on that sequence alone, and the slot and

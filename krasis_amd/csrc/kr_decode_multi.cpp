@@ -43,7 +43,8 @@ int multi_ready(kr_decode_store* s) {
 // slots -- the clauses of every exact pass and, among them, those of the per-slot kernels
 int multi_refuse(kr_decode_store* s) {
     if (int rc = kr_spec_pending_fail(s)) return rc;
-    return kr_exact_refuse(s, true);
+    if (int rc = kr_exact_refuse(s, true)) return rc;
+    return kr_xm_refuse(s);      // "multi_extend_exact_mfma": a check of its own, behind every earlier clause (kr_decode_prefill.cpp)
 }
 int need_slots(kr_decode_store* s) {
     if (!s->multi || s->multi->n_slots == 0) return kr_fail(KR_ERR_STATE, "no sequence slots: call kr_decode_slots_create first");

@@ -18,6 +18,7 @@
 
 #include "../../include/krasis_hip.h"
 #include "kr_pf_tiles.h"
+#include "kr_xm_tiles.h"
 #include "kr_lc_tiles.h"
 #include "kr_mf_tiles.h"
 #include "kr_decode_internal.h"
@@ -57,6 +58,11 @@ struct Chunk {      // one chunk of the prompt in flight: its arena, stream and 
     // the MLA layers: m_mf[k] = {nh, first tile, tiles} (kr_mf_tiles.h); m_mf_units = its runs of one token.  Null: every row takes the per-row MLA kernels
     struct MfTab { int nh, off, n; };
     const int32_t* m_mf_tiles = nullptr; std::vector<MfTab> m_mf; int m_mf_units = 0;
+    // ... "multi_extend_exact_mfma", a pass with a run of >= 2 tokens: the query tiles [run, t0] of its runs (device) for the scores pass (64 / G tokens, m_xa_*) and
+    // the P.V pass (32 / G tokens, m_xc_*), one table per tile width 1 << w as above (kr_xm_tiles.h); its runs of one token; 1 / sum and the row maxima per 32
+    // positions of every score row; one past the largest position a run reads.  Null: every row takes the per-row attention kernels
+    const int32_t* m_xm_tiles = nullptr; int m_xa_off[8] = {0, 0, 0, 0, 0, 0, 0, 0}, m_xa_n[8] = {0, 0, 0, 0, 0, 0, 0, 0}, m_xc_off[8] = {0, 0, 0, 0, 0, 0, 0, 0}, m_xc_n[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int m_xm_units = 0, m_xm_kv_end = 0; float *m_xm_inv = nullptr, *m_xm_tmax = nullptr;
     bool m_verify = false;      // kr_decode_verify_multi's pass: linear-attention layers record instead of storing state (docs/design/18-multi-verify.md)
 };
 size_t al(size_t n) { return (n + 255) & ~(size_t)255; }
@@ -185,7 +191,12 @@ static int run_layer(kr_decode_store* s, Chunk& cx, size_t li) {
                 const int w = pf_log2(kr_pf_tile_tokens(L.nh, L.nkv));
                 m.pf_runs = cx.m_runs; m.pf_nruns = cx.m_nruns; m.pf_tiles = cx.m_pf_tiles + 2 * (size_t)cx.m_pf_off[w]; m.pf_ntiles = cx.m_pf_n[w]; m.pf_units = cx.m_pf_units;
             }
-            if (kr_launch_multi_gqa(m, Cc, st)) return kr_fail(KR_ERR_VALUE, "unsupported GQA geometry for the multi-sequence step");
+            if (cx.m_xm_tiles) {      // "multi_extend_exact_mfma": the runs of >= 2 tokens take the three exact matrix-core passes, the per-row kernels the first m_nruns rows
+                const int wa = pf_log2(kr_xm_tile_tokens_a(L.nh, L.nkv)), wc = pf_log2(kr_xm_tile_tokens_c(L.nh, L.nkv));
+                KrMultiXmArgs x{cx.m_xm_tiles + 2 * (size_t)cx.m_xa_off[wa], cx.m_xm_tiles + 2 * (size_t)cx.m_xc_off[wc], cx.m_xa_n[wa], cx.m_xc_n[wc], cx.m_xm_inv, cx.m_xm_tmax, cx.m_xm_kv_end};
+                if (kr_launch_multi_gqa_xm(m, x, cx.m_runs, cx.m_nruns, cx.m_xm_units, Cc, st))
+                    return kr_fail(KR_ERR_VALUE, "multi_extend_exact_mfma: unsupported GQA geometry for the multi-sequence step (nh %d nkv %d head_dim %d)", L.nh, L.nkv, L.hd);
+            } else if (kr_launch_multi_gqa(m, Cc, st)) return kr_fail(KR_ERR_VALUE, "unsupported GQA geometry for the multi-sequence step");
         } else {
             KrPfmGqaArgs a{};
             a.q_in = B.pa; a.k_in = B.pb; a.v_in = B.pc; a.ld_q = nq; a.ld_k = nk_; a.ld_v = nv_;
@@ -730,6 +741,29 @@ int kr_exact_refuse(kr_decode_store* s, bool slots) {
 }
 int kr_spec_refuse(kr_decode_store* s) { return kr_exact_refuse(s, false); }
 
+// "multi_extend_exact_mfma" (docs/design/28-multi-extend-exact-mfma.md): what multi_refuse (kr_decode_multi.cpp) asks directly behind kr_exact_refuse(s, true), so
+// everything refused before the option existed is refused first and with the same words.  With "multi_extend_flash": two options claim the runs of >= 2 tokens.
+// No GQA layer: an option that silently does nothing is a trap.  A GQA layer outside the matrix-core passes' geometry is an error, not a fall-back to the per-row
+// kernel.  Nothing to prepare: the kernels' static LDS is below the default window.  (Paged slots under "multi_attn_fast" alone: the entry point refuses the call a
+// few lines on with the words it always had, paged_refuse in kr_decode_multi.cpp, unless its argument check does first; this check stands back like its siblings)
+int kr_xm_refuse(kr_decode_store* s) {
+    if (!s->opt_multi_extend_exact_mfma) return KR_OK;
+    if (s->multi && s->multi->pg.paged() && s->opt_multi_attn_fast && !s->opt_multi_attn_fast_paged) return KR_OK;      // paged_refused
+    if (s->opt_multi_extend_flash)
+        return kr_fail(KR_ERR_STATE, "the \"multi_extend_exact_mfma\" and \"multi_extend_flash\" options both claim the runs of >= 2 tokens of the GQA layers: set one of them to 0");
+    bool gqa = false;
+    for (const DLayer& L : s->layers) gqa |= L.attn == ATTN_GQA;
+    if (!gqa) return kr_fail(KR_ERR_STATE, "the \"multi_extend_exact_mfma\" option covers GQA layers only: this store has none (set the option to 0)");
+    for (const DLayer& L : s->layers) {
+        if (L.attn != ATTN_GQA) continue;
+        KrPfmGqaArgs g{};
+        g.nh = L.nh; g.nkv = L.nkv; g.hd = L.hd;
+        if (!kr_pfm_gqa_exact_mfma_ok(g))
+            return kr_fail(KR_ERR_VALUE, "multi_extend_exact_mfma: GQA geometry nh %d nkv %d head_dim %d not covered (heads per KV head must divide 32, head_dim 64 / 128 / 256; set the option to 0 for the per-row kernel)", L.nh, L.nkv, L.hd);
+    }
+    return KR_OK;
+}
+
 // verify buffers of every linear-attention layer (KR_VERIFY_MAX rows) + the device table the snapshot / rollback kernels walk
 static int spec_prepare(kr_decode_store* s, hipStream_t st) {
     s->spec_la.clear(); s->spec_la_of.assign(s->layers.size(), -1);
@@ -871,6 +905,13 @@ int kr_multi_pass(kr_decode_store* s, int n, int n_final, const int32_t* d_rows,
         if (mf) { mla_rows = n_final; mla_pos = unit_pos; }
         if (mf && !has_gqa) { attn_rows = n_final; attn_pos = unit_pos; }
     }
+    // "multi_extend_exact_mfma": a non-verify pass with a run of >= 2 tokens gives those runs the exact matrix-core passes (docs/design/28-multi-extend-exact-mfma.md).
+    // They keep their score rows -- the scratch stays n rows at the pass's longest position, as with the option off -- and need them under "multi_attn_fast" too.  The
+    // row stride is a multiple of 64 then (the P.V pass reads stages of 64 columns, the row maxima are per 32): no bit depends on it.  The option and
+    // "multi_extend_flash" never meet in a pass (kr_xm_refuse).  Off, a verify pass, or every run of one token: nothing of this
+    bool xm = false; int xm_unit = 0;
+    if (s->opt_multi_extend_exact_mfma && !verify && has_gqa && h_counts && h_positions)
+        for (int i = 0; i < n_final; i++) { if (h_counts[i] >= 2) xm = true; else xm_unit++; }
     const bool mla_row_attn = !mf || mf_unit > 0;      // some row takes the per-row MLA kernels
     int fd_chunk = 0, fd_chunks = 0, mla_chunk = 0, mla_chunks = 0;
     size_t fd_o_bytes = 0, fd_ml_bytes = 0;
@@ -900,8 +941,8 @@ int kr_multi_pass(kr_decode_store* s, int n, int n_final, const int32_t* d_rows,
     }
     if (((flash && row_attn) || (mla_flash && mla_row_attn)) && (M.fd_o.ensure(fd_o_bytes) || M.fd_ml.ensure(fd_ml_bytes)))
         return kr_fail(KR_ERR_HIP, "hipMalloc of the multi-sequence step's split-KV partials (%zu MiB) failed", (fd_o_bytes + fd_ml_bytes) >> 20);
-    const bool need_scores = (has_gqa && !flash && row_attn) || ((has_mla && !mla_flash) && mla_row_attn);
-    const int sc_ld = (attn_pos + 1 + 31) & ~31;
+    const bool need_scores = (has_gqa && !flash && row_attn) || ((has_mla && !mla_flash) && mla_row_attn) || xm;
+    const int sc_ld = xm ? (attn_pos + 1 + 63) & ~63 : (attn_pos + 1 + 31) & ~31;
     const int n_logits = verify ? n : n_final;      // a verify pass: the lm_head over every token row (what Chunk::verify is to the store's own pass)
     if (M.scratch.ensure(Lo.total) || (need_scores && M.scores.ensure((size_t)attn_rows * nh_max * sc_ld * 4)) || M.logits.ensure((size_t)n_logits * s->vocab * 4))
         return kr_fail(KR_ERR_HIP, "hipMalloc of the multi-sequence step's scratch (%zu MiB) failed", (Lo.total + ((size_t)attn_rows * nh_max * sc_ld + (size_t)n_logits * s->vocab) * 4) >> 20);
@@ -925,6 +966,30 @@ int kr_multi_pass(kr_decode_store* s, int n, int n_final, const int32_t* d_rows,
         if (M.pf_tiles.ensure(std::max(all.size() * 4, (size_t)65536))) return kr_fail(KR_ERR_HIP, "hipMalloc of the multi-sequence pass's query tiles failed");
         KR_HIP(hipMemcpyAsync(M.pf_tiles.p, all.data(), all.size() * 4, hipMemcpyHostToDevice, st));      // pageable source: staged before the call returns
         cx.m_pf_tiles = (const int32_t*)M.pf_tiles.p; cx.m_pf_units = n_unit;
+    }
+    if (xm) {      // the query tiles of the runs for the scores pass (64 / G tokens) and the P.V pass (32 / G), one table per width among the GQA layers, behind one another in M.xm_tiles
+        std::vector<int32_t> all, one;
+        bool have_a[8] = {false, false, false, false, false, false, false, false}, have_c[8] = {false, false, false, false, false, false, false, false};
+        for (const DLayer& L : s->layers) {
+            if (L.attn != ATTN_GQA) continue;
+            const int ta = kr_xm_tile_tokens_a(L.nh, L.nkv), tc = kr_xm_tile_tokens_c(L.nh, L.nkv), wa = pf_log2(ta), wc = pf_log2(tc);      // kr_xm_refuse: G divides 32
+            if (!have_a[wa]) {
+                have_a[wa] = true;
+                cx.m_xa_off[wa] = (int)(all.size() / 2); cx.m_xa_n[wa] = kr_pf_build_tiles(n_final, h_counts, ta, one).n_tiles;
+                all.insert(all.end(), one.begin(), one.end());
+            }
+            if (!have_c[wc]) {
+                have_c[wc] = true;
+                cx.m_xc_off[wc] = (int)(all.size() / 2); cx.m_xc_n[wc] = kr_pf_build_tiles(n_final, h_counts, tc, one).n_tiles;
+                all.insert(all.end(), one.begin(), one.end());
+            }
+        }
+        const size_t sc_rows = (size_t)n * nh_max, inv_bytes = al(sc_rows * 4);
+        if (M.xm_tiles.ensure(std::max(all.size() * 4, (size_t)65536)) || M.xm_rows.ensure(inv_bytes + sc_rows * (size_t)(sc_ld / 32) * 4))
+            return kr_fail(KR_ERR_HIP, "hipMalloc of the multi-sequence pass's exact matrix-core attention tables failed");
+        KR_HIP(hipMemcpyAsync(M.xm_tiles.p, all.data(), all.size() * 4, hipMemcpyHostToDevice, st));      // pageable source: staged before the call returns
+        cx.m_xm_tiles = (const int32_t*)M.xm_tiles.p; cx.m_xm_units = xm_unit; cx.m_xm_kv_end = kr_xm_kv_end_max(n_final, h_counts, h_positions);
+        cx.m_xm_inv = (float*)M.xm_rows.p; cx.m_xm_tmax = (float*)((char*)M.xm_rows.p + inv_bytes);
     }
     if (mf) {      // the query-row tiles of the runs, one table per head count among the MLA layers (64 (token, head) rows each), behind one another in M.mf_tiles
         std::vector<int32_t> all, one;

@@ -88,6 +88,19 @@ int kr_launch_multi_gqa(const KrMultiGqaArgs& a, int B, hipStream_t st);
 int kr_multi_pf_args_ok(const KrMultiGqaArgs& a);      // what kr_launch_multi_pf_flash checks: asked before anything of the layer is queued
 int kr_multi_pf_prepare(int hd, int fp8, int paged);
 int kr_launch_multi_pf_flash(const KrMultiGqaArgs& a, hipStream_t st);
+// "multi_extend_exact_mfma" (kr_multi_xm.hip, docs/design/28-multi-extend-exact-mfma.md), a non-verify pass with a run of >= 2 tokens: those runs take the three
+// exact passes of the single-sequence prompt pass over their slots -- scores and P.V on the f32 matrix cores, the exact softmax between them --, bit for bit what
+// the per-row kernel gives every token.  What the passes need beside KrMultiGqaArgs travels here (that struct does not grow): tiles_a = n_a x [run, t0], the query
+// tiles of 64 / G tokens of the runs of >= 2 (pass A), tiles_c = n_c x [run, t0], those of 32 / G tokens (pass C; kr_pf_tiles.h builds both); inv [B * nh] and tmax
+// [B * nh][sc_ld / 32], the softmax's 1 / sum and pass A's row maxima per 32 positions; kv_end = one past the largest position a run of >= 2 reads
+struct KrMultiXmArgs { const int* tiles_a; const int* tiles_c; int n_a, n_c; float* inv; float* tmax; int kv_end; };
+// the whole GQA section of such a pass: every check, the prep launch over all B rows, the per-row kernels -- the exact one, or the flash-decode pair when a.fd_o is
+// set -- over the first n_runs rows when units > 0 (the rows of longer runs leave at once), then passes A, B and C.  runs = the pass's run table, n_runs x [slot,
+// off, cnt]; units = its runs of one token; a.pf_* as the caller left them (null / 0): the launcher sets them on its copy.  a.scores covers all B rows at a.sc_ld, a
+// multiple of 64 above the pass's largest position.  0: launched; 1: something not covered, nothing queued
+int kr_launch_multi_gqa_xm(const KrMultiGqaArgs& a, const KrMultiXmArgs& x, const int* runs, int n_runs, int units, int B, hipStream_t st);
+int kr_multi_xm_args_ok(const KrMultiGqaArgs& a, const KrMultiXmArgs& x);      // what kr_launch_multi_xm checks (a.pf_runs set, a.pf_tiles null)
+int kr_launch_multi_xm(const KrMultiGqaArgs& a, const KrMultiXmArgs& x, int B, hipStream_t st);      // passes A, B, C alone (after the prep launch)
 // dynamic LDS of kr_multi_gqa_attn_kernel in bytes: the G = nh / nkv query rows, four softmax tiles, the P.V tile and, on paged slots, the slot's page-table
 // row of page_stride entries (0: flat).  The launcher and kr_decode_slots_create_paged both ask here, so a slot set that is created can be stepped
 #define KR_MULTI_GQA_LDS_MAX (64 * 1024)

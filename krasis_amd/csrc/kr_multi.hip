@@ -462,6 +462,35 @@ static int multi_gqa_runs(const KrMultiGqaArgs& a, int B, size_t lds, hipStream_
     return kr_launch_multi_pf_flash(a, st);
 }
 
+// "multi_extend_exact_mfma", a non-verify pass with a run of >= 2 tokens (docs/design/28-multi-extend-exact-mfma.md): the prep launch over all B rows as ever; the
+// per-row attention kernels over the first n_runs rows, where every unit row lies (kr_m_row_in_run: the rows of longer runs leave at once), and not at all without
+// a unit row; then the three exact passes over the runs' query tiles (kr_multi_xm.hip).  pf_tiles stays null: kr_launch_multi_gqa never comes here by itself
+int kr_launch_multi_gqa_xm(const KrMultiGqaArgs& a0, const KrMultiXmArgs& x, const int* runs, int n_runs, int units, int B, hipStream_t st) {
+    KrMultiGqaArgs a = a0;
+    a.pf_runs = runs; a.pf_nruns = n_runs; a.pf_units = units; a.pf_tiles = nullptr; a.pf_ntiles = 0;
+    // every check first: the prep launch appends rows to the slots, and a layer fails whole
+    if ((a.hd != 64 && a.hd != 128 && a.hd != 256) || a.nkv < 1 || a.nh % a.nkv || a.sc_ld % 32) return 1;
+    const size_t lds = kr_multi_gqa_lds_bytes(a.nh / a.nkv, a.hd, a.page_table ? a.page_stride : 0);
+    if (n_runs < 1 || n_runs > B || units < 0 || units >= n_runs || !kr_multi_xm_args_ok(a, x)) return 1;
+    if (units && a.fd_o && (!kr_multi_fd_ok(a.nh, a.nkv, a.hd) || !a.fd_ml || a.fd_chunk < 64 || a.fd_chunks < 1 || a.fd_chunks > 1024)) return 1;
+    if (units && !a.fd_o && lds > KR_MULTI_GQA_LDS_MAX) return 1;
+    if (a.page_table) hipLaunchKernelGGL(kr_multi_gqa_prep_kernel<true>, dim3(a.nh + a.nkv, B), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(kr_multi_gqa_prep_kernel<false>, dim3(a.nh + a.nkv, B), dim3(256), 0, st, a);
+    if (units) {
+        if (a.fd_o) {
+            if (kr_launch_multi_fd(a, n_runs, a.fd_chunks, st)) return 1;
+        } else {
+#define KR_MGX(NB_, F_, P_) hipLaunchKernelGGL((kr_multi_gqa_attn_kernel<NB_, F_, P_>), dim3(a.nkv, n_runs), dim3(256), lds, st, a)
+#define KR_MGX_HD(F_, P_) do { if (a.hd == 256) KR_MGX(32, F_, P_); else if (a.hd == 128) KR_MGX(16, F_, P_); else KR_MGX(8, F_, P_); } while (0)
+            if (a.page_table) { if (a.kv_fp8) KR_MGX_HD(true, true); else KR_MGX_HD(false, true); }
+            else { if (a.kv_fp8) KR_MGX_HD(true, false); else KR_MGX_HD(false, false); }
+#undef KR_MGX_HD
+#undef KR_MGX
+        }
+    }
+    return kr_launch_multi_xm(a, x, B, st);
+}
+
 // ---- MLA (docs/design/15-multi-mla.md) -----------------------------------------------------------------------------------------------------------
 // The arithmetic specification is kr_mla_prep_kernel / kr_mla_attn_kernel (kr_mla.hip); the sections of the prep launch are the shared device
 // functions of kr_mla_dev.h.  grid (nh * klr / 64 + 1, B) -- or (nh + 1, B) when the matrix-core absorption has produced q_abs -- 64 threads:

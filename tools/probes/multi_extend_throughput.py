@@ -28,6 +28,12 @@ against a library built from the commit before it).
 (bench.build_v2lite, MLA layers, E4M3 latent caches): the option alternates off and on call by call.  --off-only, --profile and --admission as under --flash.
 
     python tools/probes/multi_extend_throughput.py [out.txt] --mla-flash [--off-only] [--profile [--admission]]
+
+--exact-mfma: the same legs for the "multi_extend_exact_mfma" option (docs/design/28-multi-extend-exact-mfma.md), which changes no bit: the option alternates
+off and on call by call.  Two more legs, where the query tiles are mostly empty: the 63 decode slots each take a run of 2, and of 8, tokens at position 512.
+--off-only, --profile and --admission as under --flash.
+
+    python tools/probes/multi_extend_throughput.py [out.txt] --exact-mfma [--off-only] [--profile [--admission]]
 """
 import os
 import statistics
@@ -49,7 +55,7 @@ def timed(fn, warm, reps):
     return statistics.median(ts[warm:])
 
 
-def flash_legs(out_path, off_only, profile, opt="multi_extend_flash", fixed=(), v2lite=False):
+def flash_legs(out_path, off_only, profile, opt="multi_extend_flash", fixed=(), v2lite=False, short_runs=()):
     """option `opt` off / on, alternating call by call: admission (prefill_slot) and the mixed pass, flat and paged; the options of `fixed` stay on"""
     kv = 4096 + 160
     eng, st, keep = bench.build_v2lite(0, 0, 27, rope_len=kv, kv_fp8=True) if v2lite else bench.build_qcn(0, 0, 48, rope_len=kv, kv_fp8=True)
@@ -106,6 +112,8 @@ def flash_legs(out_path, off_only, profile, opt="multi_extend_flash", fixed=(), 
             return
         cases = [("prompt 512 -> slot", lambda i: st.prefill_slot(adm, toks(512, i)), 1, 4), ("prompt 4096 -> slot", lambda i: st.prefill_slot(adm, toks(4096, i)), 1, 2),
                  (f"mixed: {N_DECODE} rows at {P_DECODE} + a {CHUNK}-token chunk", mixed, 2, 6)]
+        for k in short_runs:      # every decode slot takes a run of k tokens at its position: query tiles that are mostly empty
+            cases.append((f"{N_DECODE} runs of {k} tokens at {P_DECODE}", lambda i, k=k: st.extend_multi(rows, [toks(k, i + b) for b in rows], [P_DECODE] * N_DECODE), 2, 6))
         for name, fn, warm, reps in cases:
             rounds = [alternate(fn, warm, reps) for _ in range(3)]
             for v in legs:
@@ -121,6 +129,8 @@ def main():
     profile = "--profile" in sys.argv
     if "--mla-flash" in sys.argv:
         return flash_legs(out_path, "--off-only" in sys.argv, profile, "multi_extend_mla_flash", v2lite=True)
+    if "--exact-mfma" in sys.argv:
+        return flash_legs(out_path, "--off-only" in sys.argv, profile, "multi_extend_exact_mfma", short_runs=(2, 8))
     if "--la-chunk" in sys.argv:
         return flash_legs(out_path, "--off-only" in sys.argv, profile, "multi_extend_la_chunk", ("multi_extend_flash",))
     if "--flash" in sys.argv:
