@@ -314,6 +314,17 @@ int kr_decode_set_attention_mode(kr_decode_store* s, int mode);
  * by every batched entry point, behind everything they refused before, each message naming the option: together with "multi_extend_flash" (KR_ERR_STATE: two
  * options claim the same runs), a store without a GQA layer (KR_ERR_STATE), a GQA layer whose heads per KV head do not divide 32 (KR_ERR_VALUE: an error, not a
  * fall-back to the per-slot kernel).
+ * "multi_extend_mla_exact_mfma" (default 0; docs/design/29-multi-extend-mla-exact-mfma.md): the same for the MLA layers.  In a non-verify batched pass they give every
+ * run of counts[i] >= 2 tokens the three attention passes of the exact MLA prompt pass over its slot, flat or paged: scores on the f32 matrix cores in two launches
+ * (16 fma chains per dot folded by the AVX2 tree: the rope dot, then (the latent dot + that) * sm_scale), the exact softmax (max, libm exp, sum in position order,
+ * 1 / sum), P.V over the latent rows on the f32 matrix cores (one fma chain per output over ascending positions with p = e * inv) -- value for value the arithmetic
+ * of the per-slot kernel, so every call gives, bit for bit, what it gives with the option off: ids, logits, every latent and rope-key row, on flat, paged and
+ * forked slots, FP16 and E4M3 caches, kv_lora_rank 512 / 256, whatever other rows share the pass and however the stream is cut.  The slot's rows are staged once
+ * per 64 / nh query tokens (scores) and 32 / nh (P.V) instead of once per (token, 4 heads).  Runs of one token keep their kernel -- the exact per-slot kernel, or
+ * the split-KV flash-decode under "multi_mla_fast": a mixed pass then gives its unit rows that option's bits and its runs of >= 2 the exact bits --, verify passes
+ * and the other layer kinds are untouched; independent of "multi_extend_exact_mfma" and "multi_extend_la_chunk".  Refused by every batched entry point, behind
+ * everything they refused before, each message naming the option: together with "multi_extend_mla_flash" (KR_ERR_STATE: two options claim the same runs), a store
+ * without an MLA layer (KR_ERR_STATE), an MLA layer whose head count does not divide 32 (KR_ERR_VALUE: an error, not a fall-back to the per-slot kernel).
  * "gguf_exact_pass" (default 0; docs/design/20-gguf-exact-pass.md): with 1, every multi-row pass of the store -- kr_decode_prefill, kr_decode_prefill_nll,
  * kr_decode_verify and the batched pass behind every slot entry point -- runs MoE layers that hold native GGUF blocks through the exact grouped block
  * kernels (kr_gguf_group.hip) instead of the int8-MFMA form: every row then carries the bits of kr_decode_step on that sequence alone, and the slot and

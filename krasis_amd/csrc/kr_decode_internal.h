@@ -55,7 +55,7 @@ struct kr_multi_state {
     // "multi_extend_la_chunk": the LDS windows of the chunked delta rule's two kernels are raised (kr_exact_refuse, once per slot set); the pass's chunked runs
     // [run, first tile] and behind them their sub-chunks [run, sub] (kr_lc_tiles.h); the rule's scratch of one layer, sized by the pass's sub-chunks
     bool lc_ready = false; DevBuf lc_tiles, lc_scratch;
-    DevBuf xm_tiles, xm_rows;                  // "multi_extend_exact_mfma": the pass's query tiles [run, t0] per tile width of the scores and the P.V pass (kr_xm_tiles.h); 1 / sum [n * nh] and the row maxima per 32 positions [n * nh][sc_ld / 32] of the pass's score rows
+    DevBuf xm_tiles, xm_rows;                  // "multi_extend_exact_mfma" / "multi_extend_mla_exact_mfma": the pass's query tiles [run, t0] per tile width of the scores and the P.V pass (kr_xm_tiles.h); 1 / sum [n * nh] and the row maxima per 32 positions [n * nh][sc_ld / 32] of the pass's score rows
     bool mf_ready = false; DevBuf mf_tiles;    // "multi_extend_mla_flash": the LDS windows of the run kernel are raised (kr_exact_refuse, once per slot set); the pass's query-row tiles [run, tile_row] per head count (kr_mf_tiles.h)
     bool mla_fd_ready = false;               // "multi_mla_fast": the partials of one MLA layer, [n][chunks][nh][klr] and [n][nh][chunks][2], share fd_o / fd_ml (sized for the larger need); the kernels' LDS windows are raised
     // per-slot samplers (kr_decode_slot_sampler, docs/design/14-multi-sampling.md): allocated for every slot on the first call; empty = every slot greedy
@@ -105,6 +105,7 @@ struct kr_decode_store {
     int opt_multi_extend_flash = 0;              // kr_decode_set_option("multi_extend_flash"): in a non-verify batched pass the GQA layers give every run of >= 2 tokens causal flash attention over its slot, flat or paged -- the bits of the KR_ATTN_FAST prompt pass (tolerance form, docs/design/25-multi-extend-flash.md); runs of one token keep what they had; the mode bits stay refused
     int opt_multi_extend_la_chunk = 0;           // kr_decode_set_option("multi_extend_la_chunk"): in a non-verify batched pass the linear-attention layers give every run of >= 64 tokens the chunked delta rule of the KR_ATTN_FAST prompt pass, fused form -- its bits (tolerance form, docs/design/26-multi-extend-la-chunk.md); shorter runs keep the exact run kernels; the mode bits stay refused
     int opt_multi_extend_exact_mfma = 0;         // kr_decode_set_option("multi_extend_exact_mfma"): in a non-verify batched pass the GQA layers give every run of >= 2 tokens the exact prompt pass's three passes over its slot, flat or paged -- scores and P.V on the f32 matrix cores, bit for bit the per-row kernel's result (docs/design/28-multi-extend-exact-mfma.md); runs of one token keep what they had; refused together with "multi_extend_flash"
+    int opt_multi_extend_mla_exact_mfma = 0;     // kr_decode_set_option("multi_extend_mla_exact_mfma"): in a non-verify batched pass the MLA layers give every run of >= 2 tokens the exact MLA prompt pass's three passes over its slot, flat or paged -- scores and P.V on the f32 matrix cores, bit for bit the per-row kernel's result (docs/design/29-multi-extend-mla-exact-mfma.md); runs of one token keep what they had; refused together with "multi_extend_mla_flash"
     int opt_multi_extend_mla_flash = 0;          // kr_decode_set_option("multi_extend_mla_flash"): in a non-verify batched pass the MLA layers give every run of >= 2 tokens causal flash attention over its slot's latent rows, flat or paged -- the bits of the KR_ATTN_FAST prompt pass (tolerance form, docs/design/27-multi-extend-mla-flash.md); runs of one token keep what they had; the mode bits stay refused
     int opt_gen_lookahead = 0;                   // kr_decode_set_option("generate_lookahead"): generate_batch feeds the sampled token back ON THE DEVICE and queues step i + 1 before the host has read token i
     int opt_ep_graph = 0;                         // kr_decode_set_option("ep_graph"): expert-parallel decode over RCCL replays a captured graph (the all-reduce is captured with the kernels)
@@ -145,6 +146,7 @@ void kr_standalone_release(kr_decode_store* s);
 int kr_exact_refuse(kr_decode_store* s, bool slots);   // kr_decode_prefill.cpp: KR_OK when an exact pass can run on this store -- speculative decoding on its own sequence, or (slots) the multi-sequence step
 int kr_spec_refuse(kr_decode_store* s);          // kr_exact_refuse(s, false)
 int kr_xm_refuse(kr_decode_store* s);            // kr_decode_prefill.cpp: the "multi_extend_exact_mfma" option's refusals, asked by multi_refuse behind kr_exact_refuse(s, true)
+int kr_mla_xm_refuse(kr_decode_store* s);        // kr_decode_prefill.cpp: the "multi_extend_mla_exact_mfma" option's refusals, asked by multi_refuse behind kr_xm_refuse(s)
 int kr_spec_pending_fail(kr_decode_store* s);    // KR_ERR_STATE while a verify waits for its commit
 int kr_standalone_cancelled(kr_decode_store* s);
 // kr_decode_prefill.cpp: the layers + final norm + lm_head GEMM of the multi-sequence pass on `st` in s->multi's arena: n_rows token rows in n_runs runs of

@@ -63,6 +63,9 @@ struct Chunk {      // one chunk of the prompt in flight: its arena, stream and 
     // positions of every score row; one past the largest position a run reads.  Null: every row takes the per-row attention kernels
     const int32_t* m_xm_tiles = nullptr; int m_xa_off[8] = {0, 0, 0, 0, 0, 0, 0, 0}, m_xa_n[8] = {0, 0, 0, 0, 0, 0, 0, 0}, m_xc_off[8] = {0, 0, 0, 0, 0, 0, 0, 0}, m_xc_n[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     int m_xm_units = 0, m_xm_kv_end = 0; float *m_xm_inv = nullptr, *m_xm_tmax = nullptr;
+    // ... "multi_extend_mla_exact_mfma": the same for the MLA layers, at the tile widths 64 / nh and 32 / nh -- the tables above (a width both options ask for is
+    // built once), the same units, rows and kv_end.  m_xl_tiles = the tables' base; null: every row takes the per-row MLA kernels
+    const int32_t* m_xl_tiles = nullptr;
     bool m_verify = false;      // kr_decode_verify_multi's pass: linear-attention layers record instead of storing state (docs/design/18-multi-verify.md)
 };
 size_t al(size_t n) { return (n + 255) & ~(size_t)255; }
@@ -262,7 +265,12 @@ static int run_layer(kr_decode_store* s, Chunk& cx, size_t li) {
             }
             if (nkv < L.klr + L.rd) return kr_fail(KR_ERR_VALUE, "kv_a_proj rows %d < kv_lora_rank + rope dim", nkv);
             if (oc != L.nh * L.vhd) return kr_fail(KR_ERR_VALUE, "o_proj cols %d != nh*v_head_dim", oc);
-            if (kr_launch_multi_mla(m, Cc, st)) return kr_fail(KR_ERR_VALUE, "unsupported MLA geometry for the multi-sequence step");
+            if (cx.m_xl_tiles) {      // "multi_extend_mla_exact_mfma": the runs of >= 2 tokens take the three exact matrix-core passes, the per-row kernels the first m_nruns rows
+                const int wa = pf_log2(kr_xm_tile_tokens_a(L.nh, 1)), wc = pf_log2(kr_xm_tile_tokens_c(L.nh, 1));
+                KrMultiXmArgs x{cx.m_xl_tiles + 2 * (size_t)cx.m_xa_off[wa], cx.m_xl_tiles + 2 * (size_t)cx.m_xc_off[wc], cx.m_xa_n[wa], cx.m_xc_n[wc], cx.m_xm_inv, cx.m_xm_tmax, cx.m_xm_kv_end};
+                if (kr_launch_multi_mla_xm(m, x, cx.m_runs, cx.m_nruns, cx.m_xm_units, Cc, st))
+                    return kr_fail(KR_ERR_VALUE, "multi_extend_mla_exact_mfma: unsupported MLA geometry for the multi-sequence step (heads %d kv_lora_rank %d rope %d)", L.nh, L.klr, L.rd);
+            } else if (kr_launch_multi_mla(m, Cc, st)) return kr_fail(KR_ERR_VALUE, "unsupported MLA geometry for the multi-sequence step");
         } else {
             KrMlaArgs a{};
             a.step = nullptr; a.pos0 = pos0; a.kv_out = B.pb; a.ld_kv = nkv; a.q_full = B.pa; a.ld_q = nq;
@@ -764,6 +772,25 @@ int kr_xm_refuse(kr_decode_store* s) {
     return KR_OK;
 }
 
+// "multi_extend_mla_exact_mfma" (docs/design/29-multi-extend-mla-exact-mfma.md): what multi_refuse asks behind kr_xm_refuse, so everything refused before the option
+// existed is refused first and with the same words.  With "multi_extend_mla_flash": two options claim the runs of >= 2 tokens of the MLA layers.  No MLA layer: an
+// option that silently does nothing is a trap.  An MLA layer outside the matrix-core passes' geometry (kr_mla_exact_mfma_ok, the prompt pass's own rule) is an
+// error, not a fall-back to the per-row kernel.  Nothing to prepare: the kernels' static LDS is below the default window.  It stands back where the entry point's
+// paged refusal applies, like kr_xm_refuse
+int kr_mla_xm_refuse(kr_decode_store* s) {
+    if (!s->opt_multi_extend_mla_exact_mfma) return KR_OK;
+    if (s->multi && s->multi->pg.paged() && s->opt_multi_attn_fast && !s->opt_multi_attn_fast_paged) return KR_OK;      // paged_refused
+    if (s->opt_multi_extend_mla_flash)
+        return kr_fail(KR_ERR_STATE, "the \"multi_extend_mla_exact_mfma\" and \"multi_extend_mla_flash\" options both claim the runs of >= 2 tokens of the MLA layers: set one of them to 0");
+    bool mla = false;
+    for (const DLayer& L : s->layers) mla |= L.attn == ATTN_MLA;
+    if (!mla) return kr_fail(KR_ERR_STATE, "the \"multi_extend_mla_exact_mfma\" option covers MLA layers only: this store has none (set the option to 0)");
+    for (const DLayer& L : s->layers)
+        if (L.attn == ATTN_MLA && !kr_mla_exact_mfma_ok(L.nh, L.klr, L.rd))
+            return kr_fail(KR_ERR_VALUE, "multi_extend_mla_exact_mfma: MLA geometry heads %d kv_lora_rank %d rope %d not covered (the head count must divide 32, kv_lora_rank 512 / 256, rope 64; set the option to 0 for the per-row kernel)", L.nh, L.klr, L.rd);
+    return KR_OK;
+}
+
 // verify buffers of every linear-attention layer (KR_VERIFY_MAX rows) + the device table the snapshot / rollback kernels walk
 static int spec_prepare(kr_decode_store* s, hipStream_t st) {
     s->spec_la.clear(); s->spec_la_of.assign(s->layers.size(), -1);
@@ -912,6 +939,12 @@ int kr_multi_pass(kr_decode_store* s, int n, int n_final, const int32_t* d_rows,
     bool xm = false; int xm_unit = 0;
     if (s->opt_multi_extend_exact_mfma && !verify && has_gqa && h_counts && h_positions)
         for (int i = 0; i < n_final; i++) { if (h_counts[i] >= 2) xm = true; else xm_unit++; }
+    // "multi_extend_mla_exact_mfma": the same for the MLA layers (xl: the exact passes over latent rows, docs/design/29-multi-extend-mla-exact-mfma.md).  The score rows stay n rows at the pass's longest
+    // position and are needed under "multi_mla_fast" too; the option and "multi_extend_mla_flash" never meet in a pass (kr_mla_xm_refuse), and "multi_extend_flash"
+    // refuses a store with an MLA layer, so attn_rows = n and attn_pos = max_pos here
+    bool xl = false; int xl_unit = 0;
+    if (s->opt_multi_extend_mla_exact_mfma && !verify && has_mla && h_counts && h_positions)
+        for (int i = 0; i < n_final; i++) { if (h_counts[i] >= 2) xl = true; else xl_unit++; }
     const bool mla_row_attn = !mf || mf_unit > 0;      // some row takes the per-row MLA kernels
     int fd_chunk = 0, fd_chunks = 0, mla_chunk = 0, mla_chunks = 0;
     size_t fd_o_bytes = 0, fd_ml_bytes = 0;
@@ -941,8 +974,9 @@ int kr_multi_pass(kr_decode_store* s, int n, int n_final, const int32_t* d_rows,
     }
     if (((flash && row_attn) || (mla_flash && mla_row_attn)) && (M.fd_o.ensure(fd_o_bytes) || M.fd_ml.ensure(fd_ml_bytes)))
         return kr_fail(KR_ERR_HIP, "hipMalloc of the multi-sequence step's split-KV partials (%zu MiB) failed", (fd_o_bytes + fd_ml_bytes) >> 20);
-    const bool need_scores = (has_gqa && !flash && row_attn) || ((has_mla && !mla_flash) && mla_row_attn) || xm;
-    const int sc_ld = xm ? (attn_pos + 1 + 63) & ~63 : (attn_pos + 1 + 31) & ~31;
+    const bool need_scores = (has_gqa && !flash && row_attn) || ((has_mla && !mla_flash) && mla_row_attn) || xm || xl;
+    int sc_ld = xm ? (attn_pos + 1 + 63) & ~63 : (attn_pos + 1 + 31) & ~31;
+    if (xl) sc_ld = (sc_ld + 63) & ~63;      // the MLA runs ask the same of the row stride
     const int n_logits = verify ? n : n_final;      // a verify pass: the lm_head over every token row (what Chunk::verify is to the store's own pass)
     if (M.scratch.ensure(Lo.total) || (need_scores && M.scores.ensure((size_t)attn_rows * nh_max * sc_ld * 4)) || M.logits.ensure((size_t)n_logits * s->vocab * 4))
         return kr_fail(KR_ERR_HIP, "hipMalloc of the multi-sequence step's scratch (%zu MiB) failed", (Lo.total + ((size_t)attn_rows * nh_max * sc_ld + (size_t)n_logits * s->vocab) * 4) >> 20);
@@ -967,12 +1001,13 @@ int kr_multi_pass(kr_decode_store* s, int n, int n_final, const int32_t* d_rows,
         KR_HIP(hipMemcpyAsync(M.pf_tiles.p, all.data(), all.size() * 4, hipMemcpyHostToDevice, st));      // pageable source: staged before the call returns
         cx.m_pf_tiles = (const int32_t*)M.pf_tiles.p; cx.m_pf_units = n_unit;
     }
-    if (xm) {      // the query tiles of the runs for the scores pass (64 / G tokens) and the P.V pass (32 / G), one table per width among the GQA layers, behind one another in M.xm_tiles
+    if (xm || xl) {      // the query tiles of the runs for the scores pass (64 / G tokens) and the P.V pass (32 / G), one table per width among the GQA layers (xm) and the MLA layers (xl: G = nh), behind one another in M.xm_tiles
         std::vector<int32_t> all, one;
         bool have_a[8] = {false, false, false, false, false, false, false, false}, have_c[8] = {false, false, false, false, false, false, false, false};
         for (const DLayer& L : s->layers) {
-            if (L.attn != ATTN_GQA) continue;
-            const int ta = kr_xm_tile_tokens_a(L.nh, L.nkv), tc = kr_xm_tile_tokens_c(L.nh, L.nkv), wa = pf_log2(ta), wc = pf_log2(tc);      // kr_xm_refuse: G divides 32
+            if (!(xm && L.attn == ATTN_GQA) && !(xl && L.attn == ATTN_MLA)) continue;
+            const int nkv = L.attn == ATTN_MLA ? 1 : L.nkv;      // MLA: one latent row serves every head
+            const int ta = kr_xm_tile_tokens_a(L.nh, nkv), tc = kr_xm_tile_tokens_c(L.nh, nkv), wa = pf_log2(ta), wc = pf_log2(tc);      // kr_xm_refuse / kr_mla_xm_refuse: G divides 32
             if (!have_a[wa]) {
                 have_a[wa] = true;
                 cx.m_xa_off[wa] = (int)(all.size() / 2); cx.m_xa_n[wa] = kr_pf_build_tiles(n_final, h_counts, ta, one).n_tiles;
@@ -988,7 +1023,9 @@ int kr_multi_pass(kr_decode_store* s, int n, int n_final, const int32_t* d_rows,
         if (M.xm_tiles.ensure(std::max(all.size() * 4, (size_t)65536)) || M.xm_rows.ensure(inv_bytes + sc_rows * (size_t)(sc_ld / 32) * 4))
             return kr_fail(KR_ERR_HIP, "hipMalloc of the multi-sequence pass's exact matrix-core attention tables failed");
         KR_HIP(hipMemcpyAsync(M.xm_tiles.p, all.data(), all.size() * 4, hipMemcpyHostToDevice, st));      // pageable source: staged before the call returns
-        cx.m_xm_tiles = (const int32_t*)M.xm_tiles.p; cx.m_xm_units = xm_unit; cx.m_xm_kv_end = kr_xm_kv_end_max(n_final, h_counts, h_positions);
+        if (xm) cx.m_xm_tiles = (const int32_t*)M.xm_tiles.p;
+        if (xl) cx.m_xl_tiles = (const int32_t*)M.xm_tiles.p;
+        cx.m_xm_units = xm ? xm_unit : xl_unit; cx.m_xm_kv_end = kr_xm_kv_end_max(n_final, h_counts, h_positions);
         cx.m_xm_inv = (float*)M.xm_rows.p; cx.m_xm_tmax = (float*)((char*)M.xm_rows.p + inv_bytes);
     }
     if (mf) {      // the query-row tiles of the runs, one table per head count among the MLA layers (64 (token, head) rows each), behind one another in M.mf_tiles

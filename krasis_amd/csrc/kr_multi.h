@@ -101,6 +101,8 @@ struct KrMultiXmArgs { const int* tiles_a; const int* tiles_c; int n_a, n_c; flo
 int kr_launch_multi_gqa_xm(const KrMultiGqaArgs& a, const KrMultiXmArgs& x, const int* runs, int n_runs, int units, int B, hipStream_t st);
 int kr_multi_xm_args_ok(const KrMultiGqaArgs& a, const KrMultiXmArgs& x);      // what kr_launch_multi_xm checks (a.pf_runs set, a.pf_tiles null)
 int kr_launch_multi_xm(const KrMultiGqaArgs& a, const KrMultiXmArgs& x, int B, hipStream_t st);      // passes A, B, C alone (after the prep launch)
+void kr_launch_multi_xm_softmax(const KrMultiGqaArgs& a, const KrMultiXmArgs& x, int B, hipStream_t st);      // pass B alone: what kr_launch_multi_xm launches second
+void kr_launch_multi_xm_pv(const KrMultiGqaArgs& a, const KrMultiXmArgs& x, hipStream_t st);                  // pass C alone (hd 64 / 128 / 256): what it launches third
 // dynamic LDS of kr_multi_gqa_attn_kernel in bytes: the G = nh / nkv query rows, four softmax tiles, the P.V tile and, on paged slots, the slot's page-table
 // row of page_stride entries (0: flat).  The launcher and kr_decode_slots_create_paged both ask here, so a slot set that is created can be stepped
 #define KR_MULTI_GQA_LDS_MAX (64 * 1024)
@@ -155,6 +157,18 @@ int kr_launch_multi_mla_fd(const KrMultiMlaArgs& a, int B, hipStream_t st);
 int kr_multi_mla_pf_args_ok(const KrMultiMlaArgs& a);      // what kr_launch_multi_mla_pf_flash checks: asked before anything of the layer is queued
 int kr_multi_mla_pf_prepare(int klr, int fp8, int paged);
 int kr_launch_multi_mla_pf_flash(const KrMultiMlaArgs& a, hipStream_t st);
+// "multi_extend_mla_exact_mfma" (kr_multi_mla_xm.hip, docs/design/29-multi-extend-mla-exact-mfma.md), a non-verify pass with a run of >= 2 tokens: those runs take
+// the three exact passes of the single-sequence MLA prompt pass over their slots -- scores (rope dot, then latent dot) and P.V on the f32 matrix cores, the exact
+// softmax between them --, bit for bit what the per-row kernel gives every token.  KrMultiXmArgs as above, at the tile widths 64 / nh (tiles_a) and 32 / nh
+// (tiles_c); neither struct grows.
+// The whole MLA section of such a pass: every check, the absorption, the prep launch over all B rows, the per-row kernels -- the exact one, or the flash-decode
+// pair when a.fd_o is set -- over the first n_runs rows when units > 0 (the rows of longer runs leave at once), passes A (two launches), B and C, the w_vc
+// projection over all B rows.  runs = the pass's run table, n_runs x [slot, off, cnt]; units = its runs of one token; a.mf_* as the caller left them (null / 0):
+// the launcher sets mf_runs / mf_nruns / mf_units on its copy, mf_tiles stays null.  a.scores covers all B rows at a.sc_ld, a multiple of 64 above the pass's
+// largest position.  0: launched; 1: something not covered, nothing queued
+int kr_launch_multi_mla_xm(const KrMultiMlaArgs& a, const KrMultiXmArgs& x, const int* runs, int n_runs, int units, int B, hipStream_t st);
+int kr_multi_mla_xm_args_ok(const KrMultiMlaArgs& a, const KrMultiXmArgs& x);      // what kr_launch_multi_mla_xm_attn checks (a.mf_runs set, a.mf_tiles null)
+int kr_launch_multi_mla_xm_attn(const KrMultiMlaArgs& a, const KrMultiXmArgs& x, int B, hipStream_t st);      // passes A, B, C alone (after the prep launch)
 
 // paged slots: the pools of every layer, and the launch that makes freshly mapped pages read as zero in all of them -- grid (n_pages, n_pools), one launch per pass
 #define KR_PAGE_MIN_TOKENS 32      // = KR_MM_ROWS (kr_multi.hip): a stage of the MLA attention kernel never straddles a page

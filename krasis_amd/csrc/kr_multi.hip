@@ -748,6 +748,40 @@ int kr_launch_multi_mla(const KrMultiMlaArgs& a_in, int B, hipStream_t st) {
     return 0;
 }
 
+// "multi_extend_mla_exact_mfma", a non-verify pass with a run of >= 2 tokens (docs/design/29-multi-extend-mla-exact-mfma.md): the absorption, the prep launch and the
+// w_vc projection over all B rows as ever; the per-row attention kernels over the first n_runs rows, where every unit row lies (kr_m_row_in_run: the rows of
+// longer runs leave at once), and not at all without a unit row; the three exact passes over the runs' query tiles (kr_multi_mla_xm.hip).  mf_tiles stays null:
+// kr_launch_multi_mla never goes to multi_mla_runs by itself
+int kr_launch_multi_mla_xm(const KrMultiMlaArgs& a0, const KrMultiXmArgs& x, const int* runs, int n_runs, int units, int B, hipStream_t st) {
+    KrMultiMlaArgs a = a0;
+    a.mf_runs = runs; a.mf_nruns = n_runs; a.mf_units = units; a.mf_tiles = nullptr; a.mf_ntiles = 0;
+    // every check first: the prep launch appends rows to the slots, and a layer fails whole
+    if (!kr_multi_mla_ok(a.klr, a.nd, a.rd) || a.nh < 1 || a.sc_ld % 32) return 1;
+    if (a.page_table && (a.page_stride < 1 || (1 << a.page_shift) < KR_MM_ROWS)) return 1;      // a stage of the per-row kernel must not straddle a page
+    if (n_runs < 1 || n_runs > B || units < 0 || units >= n_runs || !kr_multi_mla_xm_args_ok(a, x)) return 1;
+    if (units && a.fd_o && (!kr_multi_mla_fd_ok(a.nh, a.klr, a.rd) || !a.fd_ml || a.fd_chunk < 32 || a.fd_chunk % 32 || a.fd_chunks < 1 || a.fd_chunks > 1024)) return 1;
+    a.absorb_done = B >= 32 && kr_launch_mla_absorb_mfma(a.q_full, a.ld_q, a.nd + a.rd, a.nd, a.w_kc, a.klr, a.q_abs, B, a.nh, st) == 0;
+    const dim3 pg(a.nh * (a.absorb_done ? 1 : a.klr / 64) + 1, B), ag((a.nh + KR_MM_HG - 1) / KR_MM_HG, n_runs);
+    const bool rows = units && !a.fd_o;      // the exact per-row kernel has a row to take
+#define KR_MXP(F_, P_) hipLaunchKernelGGL((kr_multi_mla_prep_kernel<F_, P_>), pg, dim3(64), 0, st, a)
+#define KR_MXR(F_, NBC_, P_) hipLaunchKernelGGL((kr_multi_mla_attn_kernel<F_, NBC_, P_>), ag, dim3(512), (kr_multi_mla_lds<F_, NBC_>()), st, a)
+#define KR_MXR_ALL(P_) do { \
+    if (a.kv_fp8) { KR_MXP(true, P_); if (!rows) break; if (a.klr == 512) KR_MXR(true, 64, P_); else KR_MXR(true, 32, P_); } \
+    else { KR_MXP(false, P_); if (!rows) break; if (a.klr == 512) KR_MXR(false, 64, P_); else KR_MXR(false, 32, P_); } } while (0)
+    if (a.page_table) KR_MXR_ALL(true); else KR_MXR_ALL(false);
+#undef KR_MXR_ALL
+#undef KR_MXR
+#undef KR_MXP
+    if (units && a.fd_o && kr_launch_multi_mla_fd(a, n_runs, st)) return 1;
+    if (kr_launch_multi_mla_xm_attn(a, x, B, st)) return 1;
+    if (B >= 32 && kr_launch_mla_wvc_mfma(a.w_vc, a.attn_lat, a.v_proj, B, a.nh, a.vhd, a.klr, st) == 0) return 0;
+    KrMlaArgs m{};
+    m.step = nullptr; m.pos0 = 0; m.kv_out = a.kv_out; m.ld_kv = a.ld_kv; m.q_full = a.q_full; m.ld_q = a.ld_q; m.w_vc = a.w_vc;
+    m.q_abs = a.q_abs; m.q_pe = a.q_pe; m.attn_lat = a.attn_lat; m.v_proj = a.v_proj; m.nh = a.nh; m.klr = a.klr; m.nd = a.nd; m.rd = a.rd; m.vhd = a.vhd;
+    kr_launch_mla_wvc(m, st, B);
+    return 0;
+}
+
 // ---- paged slots: freshly mapped pages read as zero in every pool (docs/design/21-paged-slots.md).  grid (n_pages, n_pools), 256 threads; page_bytes % 16 == 0
 __global__ void __launch_bounds__(256) kr_multi_zero_pages_kernel(const KrPagePoolDev* __restrict__ pools, const int* __restrict__ pages) {
     const KrPagePoolDev P = pools[blockIdx.y];

@@ -107,20 +107,29 @@ int kr_multi_xm_args_ok(const KrMultiGqaArgs& a, const KrMultiXmArgs& x) {
     if (!x.tiles_a || !x.tiles_c || x.n_a < 1 || x.n_c < 1 || x.n_a > 65535 || !x.inv || !x.tmax || x.kv_end < 2 || x.kv_end > a.sc_ld) return 0;
     return !(a.page_table && (a.page_stride < 1 || a.page_shift < 5));
 }
-int kr_launch_multi_xm(const KrMultiGqaArgs& a, const KrMultiXmArgs& x, int B, hipStream_t st) {
-    if (!kr_multi_xm_args_ok(a, x) || B < 1) return 1;
-    const dim3 ga((x.kv_end + 63) / 64, x.n_a, a.nkv), gc(x.n_c, a.nkv);
+// passes B and C on their own: the MLA runs of "multi_extend_mla_exact_mfma" take them behind a scores pass of their own (kr_multi_mla_xm.hip) through a view of
+// the layer with nkv = 1, hd = kv_lora_rank 256.  The caller has checked what kr_multi_xm_args_ok checks
+void kr_launch_multi_xm_softmax(const KrMultiGqaArgs& a, const KrMultiXmArgs& x, int B, hipStream_t st) {
     const int rows = B * a.nh;
-#define KR_XA(F_, P_) hipLaunchKernelGGL((kr_multi_xm_scores_kernel<F_, P_>), ga, dim3(256), 0, st, a, x)
-    if (a.page_table) { if (a.kv_fp8) KR_XA(true, true); else KR_XA(false, true); }
-    else { if (a.kv_fp8) KR_XA(true, false); else KR_XA(false, false); }
-#undef KR_XA
     hipLaunchKernelGGL(kr_multi_xm_softmax_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, a, x, rows);
+}
+void kr_launch_multi_xm_pv(const KrMultiGqaArgs& a, const KrMultiXmArgs& x, hipStream_t st) {
+    const dim3 gc(x.n_c, a.nkv);
 #define KR_XC(F_, H_) do { if (a.page_table) hipLaunchKernelGGL((kr_multi_xm_pv_kernel<F_, H_, true>), gc, dim3(256), 0, st, a, x); \
                            else hipLaunchKernelGGL((kr_multi_xm_pv_kernel<F_, H_, false>), gc, dim3(256), 0, st, a, x); } while (0)
     if (a.hd == 256) { if (a.kv_fp8) KR_XC(true, 256); else KR_XC(false, 256); }
     else if (a.hd == 128) { if (a.kv_fp8) KR_XC(true, 128); else KR_XC(false, 128); }
     else { if (a.kv_fp8) KR_XC(true, 64); else KR_XC(false, 64); }
 #undef KR_XC
+}
+int kr_launch_multi_xm(const KrMultiGqaArgs& a, const KrMultiXmArgs& x, int B, hipStream_t st) {
+    if (!kr_multi_xm_args_ok(a, x) || B < 1) return 1;
+    const dim3 ga((x.kv_end + 63) / 64, x.n_a, a.nkv);
+#define KR_XA(F_, P_) hipLaunchKernelGGL((kr_multi_xm_scores_kernel<F_, P_>), ga, dim3(256), 0, st, a, x)
+    if (a.page_table) { if (a.kv_fp8) KR_XA(true, true); else KR_XA(false, true); }
+    else { if (a.kv_fp8) KR_XA(true, false); else KR_XA(false, false); }
+#undef KR_XA
+    kr_launch_multi_xm_softmax(a, x, B, st);
+    kr_launch_multi_xm_pv(a, x, st);
     return 0;
 }

@@ -337,6 +337,15 @@ class CpuDecodeStore:
         "multi_extend_la_chunk" composes with it and keeps its own bits.  Refused by the batched calls together with "multi_extend_flash" (both
         claim the same runs), on a store without a GQA layer, and on a GQA layer whose heads per KV head do not divide 32
         (docs/design/28-multi-extend-exact-mfma.md).
+        "multi_extend_mla_exact_mfma" (default 0): the same for the MLA layers.  With 1 a run of two or more tokens entering a slot (extend_multi,
+        prefill_slot) takes the exact MLA prompt pass's three attention passes over the slot's latent and rope-key rows, flat or paged -- the two
+        score dots and P.V on the f32 matrix cores, the exact softmax between them -- and every call gives, bit for bit, what it gives with the
+        option off: ids, logits, every latent and rope-key row, however the stream is cut.  Only the speed of the admission changes.  Runs of one
+        token keep their kernel (the exact per-slot kernel, or the split-KV flash-decode under "multi_mla_fast": a mixed pass then gives its unit
+        rows that option's bits and its runs of >= 2 the exact bits); verify passes and the other layer kinds are untouched, and the option is
+        independent of "multi_extend_exact_mfma" and "multi_extend_la_chunk".  Refused by the batched calls together with
+        "multi_extend_mla_flash" (both claim the same runs), on a store without an MLA layer, and on an MLA layer whose head count does not divide
+        32 (docs/design/29-multi-extend-mla-exact-mfma.md).
         "gguf_exact_pass" (default 0): with 1 every multi-row pass (prefill, prefill_nll, verify, and the batched pass behind every slot call) runs
         native-GGUF MoE layers through the exact grouped block kernels -- every row carries the bits of decode_step on that sequence alone -- and the
         slot and speculation calls accept a store with such layers; slower than the default int8-MFMA form on long prompts; refused together with
@@ -603,7 +612,11 @@ class CpuDecodeStore:
         After set_option("multi_extend_exact_mfma", 1) a run of two or more tokens takes the exact prompt pass's matrix-core scores, softmax and
         P.V over its slot in the GQA layers (docs/design/28-multi-extend-exact-mfma.md): no bit changes -- the call still equals that many
         decode_step calls, whatever the cut.  Runs of one token keep their kernel: with "multi_attn_fast" / "multi_attn_fast_paged" also set a
-        mixed pass gives its unit rows that option's bits and its runs of >= 2 the exact bits."""
+        mixed pass gives its unit rows that option's bits and its runs of >= 2 the exact bits.
+        After set_option("multi_extend_mla_exact_mfma", 1) a run of two or more tokens takes the exact MLA prompt pass's matrix-core scores,
+        softmax and P.V over its slot in the MLA layers (docs/design/29-multi-extend-mla-exact-mfma.md): again no bit changes, whatever the cut.
+        Runs of one token keep their kernel: with "multi_mla_fast" also set a mixed pass gives its unit rows that option's bits and its runs of
+        >= 2 the exact bits."""
         if len(token_lists) != len(slots) or len(positions) != len(slots):
             raise ValueError(f"{len(slots)} slots, {len(token_lists)} token lists, {len(positions)} positions")
         return self._step_multi(self._lib.kr_decode_extend_multi, slots, [len(run) for run in token_lists], [int(t) for run in token_lists for t in run],
@@ -690,7 +703,10 @@ class CpuDecodeStore:
         flash attention in its MLA layers (see extend_multi): the slot then equals prefill under set_attention_mode(True), and a last chunk of one
         token is an exact step.  After set_option("multi_extend_exact_mfma", 1) every chunk of two or more tokens takes the exact matrix-core
         attention passes in its GQA layers (see extend_multi): the slot is bit for bit what it is with the option off, only sooner; a last
-        chunk of one token keeps its kernel (with "multi_attn_fast" set: that option's bits for that token)."""
+        chunk of one token keeps its kernel (with "multi_attn_fast" set: that option's bits for that token).  After
+        set_option("multi_extend_mla_exact_mfma", 1) the same holds for the MLA layers (see extend_multi): the slot is bit for bit what it is with
+        the option off; a last chunk of one token keeps its kernel (with "multi_mla_fast" set: that option's bits for that token, a unit row,
+        while the chunks of two or more tokens carry the exact bits)."""
         from ._lib import KR_EXTEND_MAX_TOKENS
         chunk = KR_EXTEND_MAX_TOKENS if chunk is None else int(chunk)
         if not 1 <= chunk <= KR_EXTEND_MAX_TOKENS:

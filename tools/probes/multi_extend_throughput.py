@@ -34,6 +34,12 @@ off and on call by call.  Two more legs, where the query tiles are mostly empty:
 --off-only, --profile and --admission as under --flash.
 
     python tools/probes/multi_extend_throughput.py [out.txt] --exact-mfma [--off-only] [--profile [--admission]]
+
+--mla-exact-mfma: the legs of --exact-mfma, the two short-run legs included, for the "multi_extend_mla_exact_mfma" option
+(docs/design/29-multi-extend-mla-exact-mfma.md) on the 27-layer V2-Lite synthetic (bench.build_v2lite, MLA layers, E4M3 latent caches): no bit changes, the
+option alternates off and on call by call.  --off-only, --profile and --admission as under --flash.
+
+    python tools/probes/multi_extend_throughput.py [out.txt] --mla-exact-mfma [--off-only] [--profile [--admission]]
 """
 import os
 import statistics
@@ -129,6 +135,8 @@ def main():
     profile = "--profile" in sys.argv
     if "--mla-flash" in sys.argv:
         return flash_legs(out_path, "--off-only" in sys.argv, profile, "multi_extend_mla_flash", v2lite=True)
+    if "--mla-exact-mfma" in sys.argv:
+        return flash_legs(out_path, "--off-only" in sys.argv, profile, "multi_extend_mla_exact_mfma", v2lite=True, short_runs=(2, 8))
     if "--exact-mfma" in sys.argv:
         return flash_legs(out_path, "--off-only" in sys.argv, profile, "multi_extend_exact_mfma", short_runs=(2, 8))
     if "--la-chunk" in sys.argv:
