@@ -1059,6 +1059,11 @@ extern "C" int kr_decode_set_option(kr_decode_store* s, const char* name, int va
     if (!strcmp(name, "multi_extend_la_chunk")) { s->opt_multi_extend_la_chunk = value != 0; return KR_OK; }    // a run of >= 64 tokens entering a slot (extend_multi / prefill_slot) takes the prompt pass's chunked delta rule in its linear-attention layers (docs/design/26-multi-extend-la-chunk.md)
     if (!strcmp(name, "multi_extend_exact_mfma")) { s->opt_multi_extend_exact_mfma = value != 0; return KR_OK; }     // a run of >= 2 tokens entering a slot (extend_multi / prefill_slot) takes the exact prompt pass's matrix-core scores, softmax and P.V over the slot, flat or paged: same bits as the per-row kernel (docs/design/28-multi-extend-exact-mfma.md)
     if (!strcmp(name, "multi_extend_mla_exact_mfma")) { s->opt_multi_extend_mla_exact_mfma = value != 0; return KR_OK; }     // a run of >= 2 tokens entering a slot (extend_multi / prefill_slot) takes the exact MLA prompt pass's matrix-core scores, softmax and P.V over the slot's latent rows, flat or paged: same bits as the per-row kernel (docs/design/29-multi-extend-mla-exact-mfma.md)
+    if (!strcmp(name, "multi_attn_exact_split")) { s->opt_multi_attn_exact_split = value != 0; return KR_OK; }      // the exact per-slot GQA attention of every batched pass (steps, verify passes, the unit rows of extends) as scores / softmax / P.V launches spread over positions, heads and head-dim slices: same bits as the one kernel (docs/design/30-multi-attn-exact-split.md)
+    if (!strcmp(name, "multi_attn_exact_split_min")) {      // the smallest number of positions (the pass's longest per-row attention) from which "multi_attn_exact_split" applies; both forms give the same bits
+        if (value < 1) return kr_fail(KR_ERR_VALUE, "multi_attn_exact_split_min %d: at least 1", value);
+        s->opt_multi_attn_exact_split_min = value; return KR_OK;
+    }
     if (!strcmp(name, "multi_extend_flash")) { s->opt_multi_extend_flash = value != 0; return KR_OK; }          // a run of >= 2 tokens entering a slot (extend_multi / prefill_slot) takes the prompt pass's causal flash attention over the slot, flat or paged (docs/design/25-multi-extend-flash.md)
     if (!strcmp(name, "multi_extend_mla_flash")) { s->opt_multi_extend_mla_flash = value != 0; return KR_OK; }  // a run of >= 2 tokens entering a slot (extend_multi / prefill_slot) takes the prompt pass's causal MLA flash attention over the slot's latent rows, flat or paged (docs/design/27-multi-extend-mla-flash.md)
     if (!strcmp(name, "gguf_exact_pass")) { s->opt_gguf_exact_pass = value != 0; return KR_OK; }              // native-GGUF MoE layers of every multi-row pass in the exact forms; lifts the GGUF refusal of the slot and speculation entry points (docs/design/20-gguf-exact-pass.md)

@@ -62,6 +62,7 @@ struct Chunk {      // one chunk of the prompt in flight: its arena, stream and 
     // the P.V pass (32 / G tokens, m_xc_*), one table per tile width 1 << w as above (kr_xm_tiles.h); its runs of one token; 1 / sum and the row maxima per 32
     // positions of every score row; one past the largest position a run reads.  Null: every row takes the per-row attention kernels
     const int32_t* m_xm_tiles = nullptr; int m_xa_off[8] = {0, 0, 0, 0, 0, 0, 0, 0}, m_xa_n[8] = {0, 0, 0, 0, 0, 0, 0, 0}, m_xc_off[8] = {0, 0, 0, 0, 0, 0, 0, 0}, m_xc_n[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int m_xs_split = 0;      // "multi_attn_exact_split": this pass's GQA layers launch the exact per-slot attention as scores / softmax / P.V kernels (kr_multi_split.hip)
     int m_xm_units = 0, m_xm_kv_end = 0; float *m_xm_inv = nullptr, *m_xm_tmax = nullptr;
     // ... "multi_extend_mla_exact_mfma": the same for the MLA layers, at the tile widths 64 / nh and 32 / nh -- the tables above (a width both options ask for is
     // built once), the same units, rows and kv_end.  m_xl_tiles = the tables' base; null: every row takes the per-row MLA kernels
@@ -189,6 +190,7 @@ static int run_layer(kr_decode_store* s, Chunk& cx, size_t li) {
             m.q_out = B.q; m.gate = B.gate; m.attn_out = B.attn; m.scores = (float*)M.scores.p; m.sc_ld = cx.m_sc_ld;
             if (M.pg.paged()) { m.page_table = (const int*)M.pg_table.p; m.page_stride = M.pg.stride; m.page_shift = M.pg.shift; }      // paged slots: a / b are pools
             m.gated = L.gated; m.nh = L.nh; m.nkv = L.nkv; m.hd = L.hd; m.eps = s->eps; m.sm_scale = L.sm_scale;
+            m.xs_split = cx.m_xs_split;      // "multi_attn_exact_split": the exact per-slot attention as three launches
             if (cx.m_fd_chunks) { m.fd_o = (float*)M.fd_o.p; m.fd_ml = (float*)M.fd_ml.p; m.fd_chunk = cx.m_fd_chunk; m.fd_chunks = cx.m_fd_chunks; }      // "multi_attn_fast", long slots
             if (cx.m_pf_tiles) {      // "multi_extend_flash": the runs of >= 2 tokens take the run kernels, the per-row kernels the first m_nruns rows
                 const int w = pf_log2(kr_pf_tile_tokens(L.nh, L.nkv));
@@ -791,6 +793,18 @@ int kr_mla_xm_refuse(kr_decode_store* s) {
     return KR_OK;
 }
 
+// "multi_attn_exact_split" (docs/design/30-multi-attn-exact-split.md): what multi_refuse asks behind kr_mla_xm_refuse, so everything refused before the option existed
+// is refused first and with the same words.  No GQA layer: an option that silently does nothing is a trap.  Nothing else: the three launches cover every geometry
+// the one kernel covers, and the pass makes that kernel's checks either way.  It stands back where the entry point's paged refusal applies, like its siblings
+int kr_xs_refuse(kr_decode_store* s) {
+    if (!s->opt_multi_attn_exact_split) return KR_OK;
+    if (s->multi && s->multi->pg.paged() && s->opt_multi_attn_fast && !s->opt_multi_attn_fast_paged) return KR_OK;      // paged_refused
+    bool gqa = false;
+    for (const DLayer& L : s->layers) gqa |= L.attn == ATTN_GQA;
+    if (!gqa) return kr_fail(KR_ERR_STATE, "the \"multi_attn_exact_split\" option covers GQA layers only: this store has none (set the option to 0)");
+    return KR_OK;
+}
+
 // verify buffers of every linear-attention layer (KR_VERIFY_MAX rows) + the device table the snapshot / rollback kernels walk
 static int spec_prepare(kr_decode_store* s, hipStream_t st) {
     s->spec_la.clear(); s->spec_la_of.assign(s->layers.size(), -1);
@@ -986,6 +1000,9 @@ int kr_multi_pass(kr_decode_store* s, int n, int n_final, const int32_t* d_rows,
     cx.m_slots = d_rows; cx.m_pos = d_rows + 2 * n; cx.m_sc_ld = sc_ld; cx.m_fd_chunk = fd_chunk; cx.m_fd_chunks = fd_chunks;
     cx.m_mla_chunk = mla_chunk; cx.m_mla_chunks = mla_chunks;
     cx.m_runs = d_runs; cx.m_nruns = n_final; cx.m_verify = verify;
+    // "multi_attn_exact_split": a pass-level choice by the longest per-row attention of the pass; both forms give the same bits.  (Under flash the per-row rows take
+    // the flash-decode pair and the flag is not read)
+    cx.m_xs_split = s->opt_multi_attn_exact_split && has_gqa && attn_pos + 1 >= s->opt_multi_attn_exact_split_min;
     if (pf) {      // the query tiles of the runs, one table per tile width among the GQA layers (128 / G tokens), behind one another in M.pf_tiles
         std::vector<int32_t> all, one;
         bool have[8] = {false, false, false, false, false, false, false, false};

@@ -64,6 +64,10 @@ struct KrMultiGqaArgs {
     void *k_cache, *v_cache; size_t slot_elems; int kv_fp8;   // slot s: cache + s * slot_elems elements, [max_seq][nkv * hd]
     float *q_out, *gate, *attn_out;            // [B][nh * hd]
     float* scores; int sc_ld;                  // scratch [B][nh][sc_ld], sc_ld >= the longest row's pos + 1 rounded up to 32
+    // "multi_attn_exact_split" (kr_multi_split.hip, docs/design/30-multi-attn-exact-split.md): non-zero = wherever a launcher below would launch the exact per-slot
+    // attention kernel it launches the scores / softmax / P.V kernels of kr_launch_multi_gqa_split over the same rows instead -- the same bits, the same checks
+    // first.  0 (the option is off, or the pass is below "multi_attn_exact_split_min"): the one kernel, as ever
+    int xs_split;
     int gated, nh, nkv, hd; float eps, sm_scale;
     // "multi_attn_fast" (kr_multi_flash.hip): split-KV partials [B][nkv][fd_chunks][G][hd] and (max, sum) [B][nh][fd_chunks][2]; fd_chunk positions per
     // chunk, fd_chunks = the longest row's chunk count.  Null: the exact per-slot kernel (scores is not read when they are set).  With page_table set
@@ -83,6 +87,9 @@ struct KrMultiGqaArgs {
 __device__ __forceinline__ bool kr_m_row_in_run(const KrMultiGqaArgs& a, int b) { return a.pf_runs && a.pf_runs[3 * b + 2] >= 2; }
 // 0: launched; 1: geometry not covered (hd 64 / 128 / 256, nh % nkv == 0), or the dynamic LDS below is over KR_MULTI_GQA_LDS_MAX
 int kr_launch_multi_gqa(const KrMultiGqaArgs& a, int B, hipStream_t st);
+// "multi_attn_exact_split": the three launches over the first `rows` rows of the pass (after the prep launch), in place of the exact per-slot attention kernel over
+// those rows; the rows of runs of >= 2 tokens leave at once as they do there.  0: launched; 1: geometry not covered (what kr_launch_multi_gqa checks)
+int kr_launch_multi_gqa_split(const KrMultiGqaArgs& a, int rows, hipStream_t st);
 // the run kernels of "multi_extend_flash" (after the prep launch): the geometry test is kr_pfm_gqa_flash_ok's (kr_prefill_ops.h); the LDS window of the kernel a
 // layer takes (once per slot set, outside the pass; non-zero = refused; every instantiation is a kernel of its own); grid (a.pf_ntiles, nkv)
 int kr_multi_pf_args_ok(const KrMultiGqaArgs& a);      // what kr_launch_multi_pf_flash checks: asked before anything of the layer is queued

@@ -6,6 +6,7 @@
 #include "kr_libm.h"
 #include "kr_exact_dev.h"
 #include "kr_multi.h"
+#include "kr_multi_softmax_dev.h"      // kr_m_wave_softmax, KR_MG_TILE
 #include "kr_mla_dev.h"
 #include "kr_decode_ops.h"
 #include "kr_router.h"
@@ -224,31 +225,7 @@ int kr_launch_multi_la(const KrMultiLaArgs& a, const int* runs, int n_runs, int 
     return 0;
 }
 
-// ---- softmax of one score row by one wave (decode.rs:4245-4254) -----------------------------------------------------------------------------------
-// rowp[0, seq) in place: the maximum, libm exp of (score - max), the sum of the exponentials in position order -- by lane 0 over LDS tiles of
-// KR_MG_TILE floats (tw: this wave's tile; zero padding to a multiple of 32 leaves a sum of exponentials unchanged) -- and the scale by its reciprocal.
-// It contains workgroup barriers: EVERY thread of the workgroup calls it, the same number of times; a wave without a row passes on = false (and any
-// valid row pointer) and only keeps the barriers.
-#define KR_MG_TILE 1024      // softmax-sum tile per wave (floats)
-__device__ __forceinline__ void kr_m_wave_softmax(float* rowp, int seq, float* tw, bool on, int lane) {
-    const int seq32 = (seq + 31) & ~31;
-    float mx = -__builtin_inff();
-    if (on) for (int s = lane; s < seq; s += 64) mx = fmaxf(mx, rowp[s]);
-    mx = kr_wave_max(mx);
-    if (on) for (int s = lane; s < seq; s += 64) rowp[s] = kr_expf(rowp[s] - mx);
-    __syncthreads();
-    float se = 0.0f;
-    for (int s0 = 0; s0 < seq32; s0 += KR_MG_TILE) {
-        const int n = min(KR_MG_TILE, seq32 - s0);
-        if (on) for (int i = lane; i < n; i += 64) tw[i] = s0 + i < seq ? rowp[s0 + i] : 0.0f;
-        __syncthreads();
-        if (on && lane == 0) se = kr_seq_sum(tw, n, se);
-        __syncthreads();
-    }
-    se = __shfl(se, 0);
-    const float inv = 1.0f / se;
-    if (on) for (int s = lane; s < seq; s += 64) rowp[s] *= inv;
-}
+// ---- softmax of one score row by one wave: kr_m_wave_softmax and KR_MG_TILE, in kr_multi_softmax_dev.h (shared with kr_multi_split.hip) ----------------------------
 
 // ---- GQA -----------------------------------------------------------------------------------------------------------------------------------------
 // decode.rs:2873-2966 per row: gated split, per-head RMS norm (scalar sequential sum), half-split RoPE at the row's position, K / V into the row's
@@ -426,10 +403,12 @@ int kr_launch_multi_gqa(const KrMultiGqaArgs& a, int B, hipStream_t st) {
     if (a.page_table) {
         if (a.page_stride < 1 || a.page_shift < 5) return 1;
         hipLaunchKernelGGL(kr_multi_gqa_prep_kernel<true>, dim3(a.nh + a.nkv, B), dim3(256), 0, st, a);
+        if (a.xs_split) return kr_launch_multi_gqa_split(a, B, st);      // "multi_attn_exact_split": the same bits from three launches (kr_multi_split.hip)
         if (a.kv_fp8) KR_MGA_HD(true, true); else KR_MGA_HD(false, true);
         return 0;
     }
     hipLaunchKernelGGL(kr_multi_gqa_prep_kernel<false>, dim3(a.nh + a.nkv, B), dim3(256), 0, st, a);
+    if (a.xs_split) return kr_launch_multi_gqa_split(a, B, st);
     if (a.kv_fp8) KR_MGA_HD(true, false); else KR_MGA_HD(false, false);
 #undef KR_MGA_HD
 #undef KR_MGA
@@ -450,6 +429,8 @@ static int multi_gqa_runs(const KrMultiGqaArgs& a, int B, size_t lds, hipStream_
     if (a.pf_units) {
         if (a.fd_o) {
             if (kr_launch_multi_fd(a, a.pf_nruns, a.fd_chunks, st)) return 1;
+        } else if (a.xs_split) {      // "multi_attn_exact_split": the unit rows' attention as three launches
+            if (kr_launch_multi_gqa_split(a, a.pf_nruns, st)) return 1;
         } else {
 #define KR_MGR(NB_, F_, P_) hipLaunchKernelGGL((kr_multi_gqa_attn_kernel<NB_, F_, P_>), dim3(a.nkv, a.pf_nruns), dim3(256), lds, st, a)
 #define KR_MGR_HD(F_, P_) do { if (a.hd == 256) KR_MGR(32, F_, P_); else if (a.hd == 128) KR_MGR(16, F_, P_); else KR_MGR(8, F_, P_); } while (0)
@@ -479,6 +460,8 @@ int kr_launch_multi_gqa_xm(const KrMultiGqaArgs& a0, const KrMultiXmArgs& x, con
     if (units) {
         if (a.fd_o) {
             if (kr_launch_multi_fd(a, n_runs, a.fd_chunks, st)) return 1;
+        } else if (a.xs_split) {      // "multi_attn_exact_split": the unit rows' attention as three launches
+            if (kr_launch_multi_gqa_split(a, n_runs, st)) return 1;
         } else {
 #define KR_MGX(NB_, F_, P_) hipLaunchKernelGGL((kr_multi_gqa_attn_kernel<NB_, F_, P_>), dim3(a.nkv, n_runs), dim3(256), lds, st, a)
 #define KR_MGX_HD(F_, P_) do { if (a.hd == 256) KR_MGX(32, F_, P_); else if (a.hd == 128) KR_MGX(16, F_, P_); else KR_MGX(8, F_, P_); } while (0)

@@ -346,6 +346,16 @@ class CpuDecodeStore:
         independent of "multi_extend_exact_mfma" and "multi_extend_la_chunk".  Refused by the batched calls together with
         "multi_extend_mla_flash" (both claim the same runs), on a store without an MLA layer, and on an MLA layer whose head count does not divide
         32 (docs/design/29-multi-extend-mla-exact-mfma.md).
+        "multi_attn_exact_split" (default 0): with 1 every batched pass over slots (step_multi, the unit rows of extend_multi / prefill_slot, all token
+        rows of verify_multi / verify_multi_sample, every pass of the generate_multi* loops) launches the exact per-slot GQA attention as three
+        kernels -- scores spread over tiles of 256 positions, the softmax one wave per (row, head), P.V spread over heads and slices of 32 outputs
+        -- where it launched one workgroup per (row, KV head).  Every call gives, bit for bit, what it gives with the option off: ids, logits,
+        every K / V row and state; only the time changes.  Over slots longer than gqa_split_min "multi_attn_fast" / "multi_attn_fast_paged" still
+        take the rows for the flash-decode, and the runs of "multi_extend_flash" / "multi_extend_exact_mfma" keep their run kernels; MLA and
+        linear-attention layers are untouched.  Refused by the batched calls on a store without a GQA layer
+        (docs/design/30-multi-attn-exact-split.md).
+        "multi_attn_exact_split_min" (default 512, at least 1 -- below: ValueError): a pass takes the split when the longest attention of its
+        per-row kernels, position + 1, is at least this; both forms give the same bits, the value is a measured one.
         "gguf_exact_pass" (default 0): with 1 every multi-row pass (prefill, prefill_nll, verify, and the batched pass behind every slot call) runs
         native-GGUF MoE layers through the exact grouped block kernels -- every row carries the bits of decode_step on that sequence alone -- and the
         slot and speculation calls accept a store with such layers; slower than the default int8-MFMA form on long prompts; refused together with

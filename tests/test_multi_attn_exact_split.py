@@ -1,0 +1,83 @@
+"""The "multi_attn_exact_split" option (docs/design/30-multi-attn-exact-split.md) without a GPU: both options are known in every layer, the refusal is a function
+of its own behind its siblings, the three kernels stand in every launcher that launches the one kernel, the softmax both forms call is one copy, no C-ABI symbol
+was added, and every instantiation of the new kernels is in the library."""
+import os
+import re
+import subprocess
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "krasis_amd", "csrc")
+OPT, MIN = "multi_attn_exact_split", "multi_attn_exact_split_min"
+DOC = "30-multi-attn-exact-split.md"
+
+
+def _src(name):
+    return open(os.path.join(CSRC, name)).read()
+
+
+def _lib():
+    from krasis_amd import _lib
+    if not os.path.exists(_lib.lib_path()):
+        subprocess.check_call(["make", "-C", CSRC])
+    return _lib
+
+
+def test_the_options_are_known_everywhere():
+    dec = _src("kr_decode.cpp")
+    for o in (OPT, MIN):
+        assert '!strcmp(name, "%s")' % o in dec and "opt_%s" % o in _src("kr_decode_internal.h")
+    assert "if (value < 1) return kr_fail(KR_ERR_VALUE" in dec[dec.index('"%s"))' % MIN):][:300]
+    from krasis_amd.decode_store import CpuDecodeStore
+    assert OPT in CpuDecodeStore.set_option.__doc__ and MIN in CpuDecodeStore.set_option.__doc__
+    doc = open(os.path.join(ROOT, "docs", "design", DOC)).read()
+    for word in (OPT, MIN, "kr_multi_mla_attn_kernel", "Not measured", "barrier", "kernel-resource-usage"):
+        assert word in doc, word
+    assert OPT in open(os.path.join(ROOT, "README.md")).read()
+    assert "kr_multi_split.hip" in _src("Makefile") and "kr_multi_softmax_dev.h" in _src("Makefile")
+    assert os.path.exists(os.path.join(ROOT, "profiles", "multi_attn_exact_split.txt"))
+
+
+def test_the_refusal_stands_behind_its_siblings():
+    multi = _src("kr_decode_multi.cpp")
+    body = multi[multi.index("int multi_refuse(kr_decode_store* s) {"):]
+    body = body[:body.index("\n}\n")]
+    assert body.index("kr_exact_refuse(s, true)") < body.index("kr_xm_refuse(s)") < body.index("kr_mla_xm_refuse(s)") < body.index("kr_xs_refuse(s)")
+    pre = _src("kr_decode_prefill.cpp")
+    mine = pre[pre.index("int kr_xs_refuse(kr_decode_store* s) {"):]
+    mine = mine[:mine.index("\n}\n")]
+    assert "KR_ERR_STATE" in mine and "covers GQA layers only: this store has none" in mine and "graph_ok" not in mine
+    assert "attn_pos + 1 >= s->opt_multi_attn_exact_split_min" in pre      # the pass-level choice, by the longest attention of the per-row kernels
+
+
+def test_every_launcher_of_the_one_kernel_takes_the_split_and_the_softmax_is_one_copy():
+    multi = _src("kr_multi.hip")
+    assert multi.count("kr_launch_multi_gqa_split(") == 4      # flat and paged in kr_launch_multi_gqa, multi_gqa_runs, kr_launch_multi_gqa_xm
+    for site in ("kr_launch_multi_gqa_split(a, B, st)", "kr_launch_multi_gqa_split(a, a.pf_nruns, st)", "kr_launch_multi_gqa_split(a, n_runs, st)"):
+        assert site in multi, site
+    for fn in ("int kr_launch_multi_gqa(", "static int multi_gqa_runs(const KrMultiGqaArgs& a, int B, size_t lds, hipStream_t st) {", "int kr_launch_multi_gqa_xm("):
+        body = multi[multi.index(fn):]
+        body = body[:body.index("\n}\n")]
+        assert body.index("lds > KR_MULTI_GQA_LDS_MAX") < body.index("kr_launch_multi_gqa_split("), fn      # what the one kernel refuses is refused first
+    split = _src("kr_multi_split.hip")
+    code = re.sub(r"//.*", "", split)
+    assert '#include "kr_multi_softmax_dev.h"' in split and '#include "kr_multi_softmax_dev.h"' in multi
+    assert "void kr_m_wave_softmax(" not in multi and "void kr_m_wave_softmax(" not in split and _src("kr_multi_softmax_dev.h").count("void kr_m_wave_softmax(") == 1
+    assert code.count("kr_m_wave_softmax(") == 1 and "asm" not in code
+    assert code.count("if (kr_m_row_in_run(a, row)) return;") == 3      # all three leave the run kernels' rows
+    for k in ("scores", "softmax", "pv"):      # ... ahead of the kernel's first barrier
+        body = code[code.index("kr_multi_split_%s_kernel(const KrMultiGqaArgs a) {" % k):]
+        assert body.index("if (kr_m_row_in_run(a, row)) return;") < body.index("kr_m_wave_softmax(" if k == "softmax" else "__syncthreads()"), k
+
+
+def test_library_exports_no_new_symbol_and_holds_the_new_kernels():
+    _lib_mod = _lib()
+    out = subprocess.run(["nm", "-D", "--defined-only", _lib_mod.lib_path()], stdout=subprocess.PIPE, text=True, check=True).stdout
+    exported = {line.split()[-1] for line in out.splitlines() if re.search(r" T kr_\w+$", line)}
+    assert not [n for n in exported if "split" in n and "multi" in n], exported
+    names = subprocess.run(["nm", "-C", _lib_mod.lib_path()], stdout=subprocess.PIPE, text=True, check=True).stdout
+    assert "kr_multi_split_softmax_kernel" in names
+    for nb in (8, 16, 32):
+        for fp8 in ("true", "false"):
+            for paged in ("true", "false"):
+                for k in ("scores", "pv"):
+                    assert "kr_multi_split_%s_kernel<%d, %s, %s>" % (k, nb, fp8, paged) in names, (k, nb, fp8, paged)
