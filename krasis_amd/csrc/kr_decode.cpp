@@ -1064,6 +1064,11 @@ extern "C" int kr_decode_set_option(kr_decode_store* s, const char* name, int va
         if (value < 1) return kr_fail(KR_ERR_VALUE, "multi_attn_exact_split_min %d: at least 1", value);
         s->opt_multi_attn_exact_split_min = value; return KR_OK;
     }
+    if (!strcmp(name, "multi_mla_exact_split")) { s->opt_multi_mla_exact_split = value != 0; return KR_OK; }      // the exact per-slot MLA attention of every batched pass (steps, verify passes, the unit rows of extends) as scores / softmax / weighted-sum launches spread over positions, heads and latent slices: same bits as the one kernel (docs/design/31-multi-mla-exact-split.md)
+    if (!strcmp(name, "multi_mla_exact_split_min")) {      // the smallest number of positions (the pass's longest per-row MLA attention) from which "multi_mla_exact_split" applies; both forms give the same bits
+        if (value < 1) return kr_fail(KR_ERR_VALUE, "multi_mla_exact_split_min %d: at least 1", value);
+        s->opt_multi_mla_exact_split_min = value; return KR_OK;
+    }
     if (!strcmp(name, "multi_extend_flash")) { s->opt_multi_extend_flash = value != 0; return KR_OK; }          // a run of >= 2 tokens entering a slot (extend_multi / prefill_slot) takes the prompt pass's causal flash attention over the slot, flat or paged (docs/design/25-multi-extend-flash.md)
     if (!strcmp(name, "multi_extend_mla_flash")) { s->opt_multi_extend_mla_flash = value != 0; return KR_OK; }  // a run of >= 2 tokens entering a slot (extend_multi / prefill_slot) takes the prompt pass's causal MLA flash attention over the slot's latent rows, flat or paged (docs/design/27-multi-extend-mla-flash.md)
     if (!strcmp(name, "gguf_exact_pass")) { s->opt_gguf_exact_pass = value != 0; return KR_OK; }              // native-GGUF MoE layers of every multi-row pass in the exact forms; lifts the GGUF refusal of the slot and speculation entry points (docs/design/20-gguf-exact-pass.md)

@@ -46,7 +46,8 @@ int multi_refuse(kr_decode_store* s) {
     if (int rc = kr_exact_refuse(s, true)) return rc;
     if (int rc = kr_xm_refuse(s)) return rc;      // "multi_extend_exact_mfma": a check of its own, behind every earlier clause (kr_decode_prefill.cpp)
     if (int rc = kr_mla_xm_refuse(s)) return rc;  // "multi_extend_mla_exact_mfma": the same, behind that one
-    return kr_xs_refuse(s);                       // "multi_attn_exact_split": the same, behind that one
+    if (int rc = kr_xs_refuse(s)) return rc;      // "multi_attn_exact_split": the same, behind that one
+    return kr_mla_xs_refuse(s);                   // "multi_mla_exact_split": the same, behind that one
 }
 int need_slots(kr_decode_store* s) {
     if (!s->multi || s->multi->n_slots == 0) return kr_fail(KR_ERR_STATE, "no sequence slots: call kr_decode_slots_create first");

@@ -63,6 +63,7 @@ struct Chunk {      // one chunk of the prompt in flight: its arena, stream and 
     // positions of every score row; one past the largest position a run reads.  Null: every row takes the per-row attention kernels
     const int32_t* m_xm_tiles = nullptr; int m_xa_off[8] = {0, 0, 0, 0, 0, 0, 0, 0}, m_xa_n[8] = {0, 0, 0, 0, 0, 0, 0, 0}, m_xc_off[8] = {0, 0, 0, 0, 0, 0, 0, 0}, m_xc_n[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     int m_xs_split = 0;      // "multi_attn_exact_split": this pass's GQA layers launch the exact per-slot attention as scores / softmax / P.V kernels (kr_multi_split.hip)
+    int m_mla_xs_split = 0;  // "multi_mla_exact_split": this pass's MLA layers launch the exact per-slot attention as scores / softmax / weighted-sum kernels (kr_multi_mla_split.hip)
     int m_xm_units = 0, m_xm_kv_end = 0; float *m_xm_inv = nullptr, *m_xm_tmax = nullptr;
     // ... "multi_extend_mla_exact_mfma": the same for the MLA layers, at the tile widths 64 / nh and 32 / nh -- the tables above (a width both options ask for is
     // built once), the same units, rows and kv_end.  m_xl_tiles = the tables' base; null: every row takes the per-row MLA kernels
@@ -258,6 +259,7 @@ static int run_layer(kr_decode_store* s, Chunk& cx, size_t li) {
             m.q_abs = B.q; m.q_pe = B.z; m.attn_lat = B.recur; m.v_proj = B.attn; m.scores = (float*)M.scores.p; m.sc_ld = cx.m_sc_ld;
             m.nh = L.nh; m.klr = L.klr; m.nd = L.nd; m.rd = L.rd; m.vhd = L.vhd; m.eps = s->eps; m.sm_scale = L.sm_scale;
             if (M.pg.paged()) { m.page_table = (const int*)M.pg_table.p; m.page_stride = M.pg.stride; m.page_shift = M.pg.shift; }      // paged slots: the strides are a page's bytes
+            m.xs_split = cx.m_mla_xs_split;      // "multi_mla_exact_split": the exact per-slot attention as three launches
             if (cx.m_mla_chunks) { m.fd_o = (float*)M.fd_o.p; m.fd_ml = (float*)M.fd_ml.p; m.fd_chunk = cx.m_mla_chunk; m.fd_chunks = cx.m_mla_chunks; }      // "multi_mla_fast", long slots
             if (cx.m_mf_tiles) {      // "multi_extend_mla_flash": the runs of >= 2 tokens take the run kernel, the per-row kernels the first m_nruns rows
                 for (const Chunk::MfTab& t : cx.m_mf)
@@ -805,6 +807,18 @@ int kr_xs_refuse(kr_decode_store* s) {
     return KR_OK;
 }
 
+// "multi_mla_exact_split" (docs/design/31-multi-mla-exact-split.md): what multi_refuse asks last, behind kr_xs_refuse, so everything refused before the option existed
+// is refused first and with the same words.  No MLA layer: an option that silently does nothing is a trap.  Nothing else: the three launches cover every geometry
+// the one kernel covers, and the pass makes that kernel's checks either way.  It stands back where the entry point's paged refusal applies, like its siblings
+int kr_mla_xs_refuse(kr_decode_store* s) {
+    if (!s->opt_multi_mla_exact_split) return KR_OK;
+    if (s->multi && s->multi->pg.paged() && s->opt_multi_attn_fast && !s->opt_multi_attn_fast_paged) return KR_OK;      // paged_refused
+    bool mla = false;
+    for (const DLayer& L : s->layers) mla |= L.attn == ATTN_MLA;
+    if (!mla) return kr_fail(KR_ERR_STATE, "the \"multi_mla_exact_split\" option covers MLA layers only: this store has none (set the option to 0)");
+    return KR_OK;
+}
+
 // verify buffers of every linear-attention layer (KR_VERIFY_MAX rows) + the device table the snapshot / rollback kernels walk
 static int spec_prepare(kr_decode_store* s, hipStream_t st) {
     s->spec_la.clear(); s->spec_la_of.assign(s->layers.size(), -1);
@@ -1003,6 +1017,8 @@ int kr_multi_pass(kr_decode_store* s, int n, int n_final, const int32_t* d_rows,
     // "multi_attn_exact_split": a pass-level choice by the longest per-row attention of the pass; both forms give the same bits.  (Under flash the per-row rows take
     // the flash-decode pair and the flag is not read)
     cx.m_xs_split = s->opt_multi_attn_exact_split && has_gqa && attn_pos + 1 >= s->opt_multi_attn_exact_split_min;
+    // "multi_mla_exact_split": the same for the MLA layers, by the longest attention of the pass's per-row MLA kernels (mla_pos = -1: no unit row, nothing launched)
+    cx.m_mla_xs_split = s->opt_multi_mla_exact_split && has_mla && mla_pos + 1 >= s->opt_multi_mla_exact_split_min;
     if (pf) {      // the query tiles of the runs, one table per tile width among the GQA layers (128 / G tokens), behind one another in M.pf_tiles
         std::vector<int32_t> all, one;
         bool have[8] = {false, false, false, false, false, false, false, false};

@@ -132,6 +132,10 @@ struct KrMultiMlaArgs {
     float* scores; int sc_ld;                  // scratch [B][nh][sc_ld], sc_ld >= the longest row's pos + 1 rounded up to 32
     int nh, klr, nd, rd, vhd; float eps, sm_scale;
     int absorb_done;                           // set by the launch: q_abs came from the matrix-core absorption, the prep launch skips its tiles
+    // "multi_mla_exact_split" (kr_multi_mla_split.hip, docs/design/31-multi-mla-exact-split.md): non-zero = wherever a launcher below would launch the exact per-slot
+    // attention kernel it launches the scores / softmax / weighted-sum kernels of kr_launch_multi_mla_split over the same rows instead -- the same bits, the same
+    // checks first.  0 (the option is off, or the pass is below "multi_mla_exact_split_min"): the one kernel, as ever
+    int xs_split;
     // paged slots, as KrMultiGqaArgs: ckv_cache / kpe_cache are pools [n_pages][1 << page_shift][klr] / [..][rd]; a stage of KR_MM_ROWS rows lies in one page
     const int* page_table; int page_stride, page_shift;
     // "multi_mla_fast" (kr_multi_mla_flash.hip, docs/design/24-multi-mla-fast.md): split-KV partials [B][fd_chunks][nh][klr] and (max, sum) [B][nh][fd_chunks][2];
@@ -152,6 +156,10 @@ __device__ __forceinline__ bool kr_m_row_in_run(const KrMultiMlaArgs& a, int b) 
 int kr_multi_mla_ok(int klr, int nd, int rd);
 // 0: launched (absorption, prep, attention -- the flash-decode pair when a.fd_o is set --, w_vc projection); 1: geometry not covered
 int kr_launch_multi_mla(const KrMultiMlaArgs& a, int B, hipStream_t st);
+// "multi_mla_exact_split": the three launches over the first `rows` rows of the pass (after the prep launch, ahead of the w_vc projection), in place of the exact
+// per-slot attention kernel over those rows; the rows of runs of >= 2 tokens leave at once as they do there.  0: launched; 1: geometry not covered (what
+// kr_launch_multi_mla checks)
+int kr_launch_multi_mla_split(const KrMultiMlaArgs& a, int rows, hipStream_t st);
 // the flash-decode form of the attention launch (after the prep launch): geometry test (at most 64 heads = one query tile), the LDS window of its kernel
 // (once per slot set, outside the pass; non-zero = refused; every instantiation is a kernel of its own), the chunk pass + merge over a.fd_chunks chunks
 // (0: launched; a.page_table set: through the table)

@@ -680,7 +680,7 @@ static int multi_mla_runs(KrMultiMlaArgs& a, int B, hipStream_t st) {
     if (a.mf_units && !a.fd_o && (!a.scores || a.sc_ld < 32)) return 1;
     a.absorb_done = B >= 32 && kr_launch_mla_absorb_mfma(a.q_full, a.ld_q, a.nd + a.rd, a.nd, a.w_kc, a.klr, a.q_abs, B, a.nh, st) == 0;
     const dim3 pg(a.nh * (a.absorb_done ? 1 : a.klr / 64) + 1, B), ag((a.nh + KR_MM_HG - 1) / KR_MM_HG, a.mf_nruns);
-    const bool rows = a.mf_units && !a.fd_o;      // the exact per-row kernel has a row to take
+    const bool rows = a.mf_units && !a.fd_o && !a.xs_split;      // the exact per-row kernel has a row to take ("multi_mla_exact_split": the three launches below)
 #define KR_MRP(F_, P_) hipLaunchKernelGGL((kr_multi_mla_prep_kernel<F_, P_>), pg, dim3(64), 0, st, a)
 #define KR_MRA(F_, NBC_, P_) hipLaunchKernelGGL((kr_multi_mla_attn_kernel<F_, NBC_, P_>), ag, dim3(512), (kr_multi_mla_lds<F_, NBC_>()), st, a)
 #define KR_MRA_ALL(P_) do { \
@@ -691,6 +691,7 @@ static int multi_mla_runs(KrMultiMlaArgs& a, int B, hipStream_t st) {
 #undef KR_MRA
 #undef KR_MRP
     if (a.mf_units && a.fd_o && kr_launch_multi_mla_fd(a, a.mf_nruns, st)) return 1;
+    if (a.mf_units && !a.fd_o && a.xs_split && kr_launch_multi_mla_split(a, a.mf_nruns, st)) return 1;      // "multi_mla_exact_split": the unit rows' attention as three launches
     if (kr_launch_multi_mla_pf_flash(a, st)) return 1;
     if (B >= 32 && kr_launch_mla_wvc_mfma(a.w_vc, a.attn_lat, a.v_proj, B, a.nh, a.vhd, a.klr, st) == 0) return 0;
     KrMlaArgs m{};
@@ -715,13 +716,14 @@ int kr_launch_multi_mla(const KrMultiMlaArgs& a_in, int B, hipStream_t st) {
 #define KR_MMP(F_, P_) hipLaunchKernelGGL((kr_multi_mla_prep_kernel<F_, P_>), pg, dim3(64), 0, st, a)
 #define KR_MMA(F_, NBC_, P_) hipLaunchKernelGGL((kr_multi_mla_attn_kernel<F_, NBC_, P_>), ag, dim3(512), (kr_multi_mla_lds<F_, NBC_>()), st, a)
 #define KR_MMA_ALL(P_) do { \
-    if (a.kv_fp8) { KR_MMP(true, P_); if (a.fd_o) break; if (a.klr == 512) KR_MMA(true, 64, P_); else KR_MMA(true, 32, P_); } \
-    else { KR_MMP(false, P_); if (a.fd_o) break; if (a.klr == 512) KR_MMA(false, 64, P_); else KR_MMA(false, 32, P_); } } while (0)
+    if (a.kv_fp8) { KR_MMP(true, P_); if (a.fd_o) break; if (a.xs_split) break; if (a.klr == 512) KR_MMA(true, 64, P_); else KR_MMA(true, 32, P_); } \
+    else { KR_MMP(false, P_); if (a.fd_o) break; if (a.xs_split) break; if (a.klr == 512) KR_MMA(false, 64, P_); else KR_MMA(false, 32, P_); } } while (0)
     if (a.page_table) KR_MMA_ALL(true); else KR_MMA_ALL(false);
 #undef KR_MMA_ALL
 #undef KR_MMA
 #undef KR_MMP
     if (a.fd_o && kr_launch_multi_mla_fd(a, B, st)) return 1;
+    if (!a.fd_o && a.xs_split && kr_launch_multi_mla_split(a, B, st)) return 1;      // "multi_mla_exact_split": the attention as three launches, flat or paged
     // the w_vc projection, row-wise: the prompt pass's matrix-core launch from 32 rows, the decode launch with a token dimension below
     if (B >= 32 && kr_launch_mla_wvc_mfma(a.w_vc, a.attn_lat, a.v_proj, B, a.nh, a.vhd, a.klr, st) == 0) return 0;
     KrMlaArgs m{};
@@ -745,7 +747,7 @@ int kr_launch_multi_mla_xm(const KrMultiMlaArgs& a0, const KrMultiXmArgs& x, con
     if (units && a.fd_o && (!kr_multi_mla_fd_ok(a.nh, a.klr, a.rd) || !a.fd_ml || a.fd_chunk < 32 || a.fd_chunk % 32 || a.fd_chunks < 1 || a.fd_chunks > 1024)) return 1;
     a.absorb_done = B >= 32 && kr_launch_mla_absorb_mfma(a.q_full, a.ld_q, a.nd + a.rd, a.nd, a.w_kc, a.klr, a.q_abs, B, a.nh, st) == 0;
     const dim3 pg(a.nh * (a.absorb_done ? 1 : a.klr / 64) + 1, B), ag((a.nh + KR_MM_HG - 1) / KR_MM_HG, n_runs);
-    const bool rows = units && !a.fd_o;      // the exact per-row kernel has a row to take
+    const bool rows = units && !a.fd_o && !a.xs_split;      // the exact per-row kernel has a row to take ("multi_mla_exact_split": the three launches below)
 #define KR_MXP(F_, P_) hipLaunchKernelGGL((kr_multi_mla_prep_kernel<F_, P_>), pg, dim3(64), 0, st, a)
 #define KR_MXR(F_, NBC_, P_) hipLaunchKernelGGL((kr_multi_mla_attn_kernel<F_, NBC_, P_>), ag, dim3(512), (kr_multi_mla_lds<F_, NBC_>()), st, a)
 #define KR_MXR_ALL(P_) do { \
@@ -756,6 +758,7 @@ int kr_launch_multi_mla_xm(const KrMultiMlaArgs& a0, const KrMultiXmArgs& x, con
 #undef KR_MXR
 #undef KR_MXP
     if (units && a.fd_o && kr_launch_multi_mla_fd(a, n_runs, st)) return 1;
+    if (units && !a.fd_o && a.xs_split && kr_launch_multi_mla_split(a, n_runs, st)) return 1;      // "multi_mla_exact_split": the unit rows' attention as three launches
     if (kr_launch_multi_mla_xm_attn(a, x, B, st)) return 1;
     if (B >= 32 && kr_launch_mla_wvc_mfma(a.w_vc, a.attn_lat, a.v_proj, B, a.nh, a.vhd, a.klr, st) == 0) return 0;
     KrMlaArgs m{};

@@ -356,6 +356,17 @@ class CpuDecodeStore:
         (docs/design/30-multi-attn-exact-split.md).
         "multi_attn_exact_split_min" (default 512, at least 1 -- below: ValueError): a pass takes the split when the longest attention of its
         per-row kernels, position + 1, is at least this; both forms give the same bits, the value is a measured one.
+        "multi_mla_exact_split" (default 0): the same for MLA layers -- with 1 every batched pass over slots (step_multi, the unit rows of
+        extend_multi / prefill_slot, all token rows of verify_multi / verify_multi_sample, every pass of the generate_multi* loops) launches the
+        exact per-slot MLA attention as three kernels -- scores spread over tiles of 64 positions and groups of 4 heads, the softmax one wave per
+        (row, head), the weighted sum spread over heads and slices of 32 latent elements -- where it launched one workgroup per (row, 4 heads).
+        Every call gives, bit for bit, what it gives with the option off: ids, logits, every latent and rope-key row and sampler state; only the
+        time changes.  Over slots longer than mla_split_min "multi_mla_fast" still takes the rows for the flash-decode, and the runs of
+        "multi_extend_mla_flash" / "multi_extend_mla_exact_mfma" keep their run kernels; GQA and linear-attention layers are untouched, and the
+        option is independent of "multi_attn_exact_split".  Refused by the batched calls on a store without an MLA layer
+        (docs/design/31-multi-mla-exact-split.md).
+        "multi_mla_exact_split_min" (default 512, at least 1 -- below: ValueError): a pass takes the split when the longest attention of its
+        per-row MLA kernels, position + 1, is at least this; both forms give the same bits, the value is a measured one.
         "gguf_exact_pass" (default 0): with 1 every multi-row pass (prefill, prefill_nll, verify, and the batched pass behind every slot call) runs
         native-GGUF MoE layers through the exact grouped block kernels -- every row carries the bits of decode_step on that sequence alone -- and the
         slot and speculation calls accept a store with such layers; slower than the default int8-MFMA form on long prompts; refused together with
