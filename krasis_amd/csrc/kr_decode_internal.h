@@ -51,12 +51,10 @@ struct kr_multi_state {
     DevBuf la_pools, fk_ids; int la_npools = 0;
     DevBuf rows, ids, logits, scores, scratch; // step: [slots | tokens | positions] (device), greedy ids, [n][vocab] logits, attention scores, the arena
     DevBuf fd_o, fd_ml; bool fd_ready = false; // "multi_attn_fast": split-KV partials [n][nkv][chunks][G][hd] and (max, sum) [n][nh][chunks][2] of one GQA layer, sized by the step's longest row; the kernels' LDS windows are raised
-    bool pf_ready = false; DevBuf pf_tiles;    // "multi_extend_flash": the LDS windows of the run kernels are raised (kr_exact_refuse, once per slot set); the pass's query tiles [run, t0] per tile width (kr_pf_tiles.h)
-    // "multi_extend_la_chunk": the LDS windows of the chunked delta rule's two kernels are raised (kr_exact_refuse, once per slot set); the pass's chunked runs
-    // [run, first tile] and behind them their sub-chunks [run, sub] (kr_lc_tiles.h); the rule's scratch of one layer, sized by the pass's sub-chunks
-    bool lc_ready = false; DevBuf lc_tiles, lc_scratch;
-    DevBuf xm_tiles, xm_rows;                  // "multi_extend_exact_mfma" / "multi_extend_mla_exact_mfma": the pass's query tiles [run, t0] per tile width of the scores and the P.V pass (kr_xm_tiles.h); 1 / sum [n * nh] and the row maxima per 32 positions [n * nh][sc_ld / 32] of the pass's score rows
-    bool mf_ready = false; DevBuf mf_tiles;    // "multi_extend_mla_flash": the LDS windows of the run kernel are raised (kr_exact_refuse, once per slot set); the pass's query-row tiles [run, tile_row] per head count (kr_mf_tiles.h)
+    DevBuf tiles;                              // every tile table of a pass, one upload (kr_multi_plan.h: the plan's vector; its spans are relative to this buffer)
+    bool pf_ready = false, mf_ready = false, lc_ready = false;   // "multi_extend_flash" / "multi_extend_mla_flash" / "multi_extend_la_chunk": the LDS windows of the run kernels are raised (kr_exact_refuse, once per slot set)
+    DevBuf lc_scratch;                         // "multi_extend_la_chunk": the rule's scratch of one layer, sized by the pass's sub-chunks
+    DevBuf xm_rows;                            // "multi_extend_exact_mfma" / "multi_extend_mla_exact_mfma": 1 / sum [n * nh] and the row maxima per 32 positions [n * nh][sc_ld / 32] of the pass's score rows
     bool mla_fd_ready = false;               // "multi_mla_fast": the partials of one MLA layer, [n][chunks][nh][klr] and [n][nh][chunks][2], share fd_o / fd_ml (sized for the larger need); the kernels' LDS windows are raised
     // per-slot samplers (kr_decode_slot_sampler, docs/design/14-multi-sampling.md): allocated for every slot on the first call; empty = every slot greedy
     struct Sampler { float temperature = 0.0f, top_p = 1.0f, penalty = 0.0f; int top_k = 0; };
@@ -149,6 +147,8 @@ int kr_moe_prefill_prepare(kr_engine* e, int layer, int fast, int routed_only, h
 void kr_standalone_release(kr_decode_store* s);
 int kr_exact_refuse(kr_decode_store* s, bool slots);   // kr_decode_prefill.cpp: KR_OK when an exact pass can run on this store -- speculative decoding on its own sequence, or (slots) the multi-sequence step
 int kr_spec_refuse(kr_decode_store* s);          // kr_exact_refuse(s, false)
+bool paged_refused(const kr_decode_store* s);    // kr_decode_prefill.cpp: paged slots under "multi_attn_fast" alone -- what paged_refuse (kr_decode_multi.cpp) refuses and the options' refusals below stand back for
+bool has_attn(const kr_decode_store* s, int kind);   // kr_decode_prefill.cpp: the store has a layer of this attention kind (ATTN_*)
 int kr_xm_refuse(kr_decode_store* s);            // kr_decode_prefill.cpp: the "multi_extend_exact_mfma" option's refusals, asked by multi_refuse behind kr_exact_refuse(s, true)
 int kr_xs_refuse(kr_decode_store* s);            // kr_decode_prefill.cpp: the "multi_attn_exact_split" option's refusal, asked by multi_refuse behind kr_mla_xm_refuse(s)
 int kr_mla_xm_refuse(kr_decode_store* s);        // kr_decode_prefill.cpp: the "multi_extend_mla_exact_mfma" option's refusals, asked by multi_refuse behind kr_xm_refuse(s)
@@ -159,8 +159,8 @@ int kr_standalone_cancelled(kr_decode_store* s);
 // consecutive tokens per slot (a step: runs of one).  d_rows = [slots | tokens | positions] of n_rows each on the device, the last token of run i in row i;
 // d_runs = n_runs x [slot, off, cnt] (kr_multi.h); logits of the first n_runs rows -> s->multi->logits [n_runs][vocab].  verify: the linear-attention layers
 // take the verify form (no state stored; records into the layers of s->multi->v_host), and the logits of all n_rows rows -> s->multi->logits [n_rows][vocab]
-// h_counts / h_positions (host, optional): the n_runs run lengths and first positions as the caller gave them -- what "multi_extend_flash" builds its query tiles
-// from and sizes the per-row kernels' scratch by, and "multi_extend_la_chunk" its table of chunked runs; null counts: every run has one token
+// h_counts / h_positions (host, optional): the n_runs run lengths and first positions as the caller gave them -- what the plan (kr_multi_plan.h) builds the
+// tables of the run options from and sizes the per-row kernels' scratch by; null counts: every run has one token
 int kr_multi_pass(kr_decode_store* s, int n_rows, int n_runs, const int32_t* d_rows, const int32_t* d_runs, int max_pos, hipStream_t st, bool verify = false,
                   const int32_t* h_counts = nullptr, const int32_t* h_positions = nullptr);
 void kr_standalone_set_elapsed(kr_decode_store* s, double sec);   // kr_engine.cpp: per (group, column) nibble sums for the int8-MFMA GEMM

@@ -70,7 +70,7 @@ int slot_in_range(kr_decode_store* s, int slot) {
 // "multi_attn_fast" reads flat slots only: with that option alone every batched call on paged slots is refused (an option that silently does nothing is a
 // trap); "multi_attn_fast_paged" is the option that reads both kinds (docs/design/23-multi-attn-fast-paged.md)
 int paged_refuse(kr_decode_store* s) {
-    if (s->multi->pg.paged() && s->opt_multi_attn_fast && !s->opt_multi_attn_fast_paged)
+    if (paged_refused(s))
         return kr_fail(KR_ERR_STATE, "\"multi_attn_fast\" does not read paged slots (kr_decode_slots_create_paged): set \"multi_attn_fast_paged\", clear the option or create flat slots");
     return KR_OK;
 }

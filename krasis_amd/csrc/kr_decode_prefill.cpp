@@ -17,10 +17,7 @@
 #include <vector>
 
 #include "../../include/krasis_hip.h"
-#include "kr_pf_tiles.h"
-#include "kr_xm_tiles.h"
-#include "kr_lc_tiles.h"
-#include "kr_mf_tiles.h"
+#include "kr_multi_plan.h"
 #include "kr_decode_internal.h"
 #include "kr_prefill.h"
 #include "kr_prefill_ops.h"
@@ -41,37 +38,20 @@ struct Scratch {   // carved from one allocation per arena (grown on demand)
 struct Act { const int8_t* h; const int8_t* l; const float* s; const uint16_t* f; const float* fm; };   // one GEMM input: INT16 digits or f16 rows
 Act X(const Scratch& B) { return Act{B.xh, B.xl, B.xs, B.xf, B.xfm}; }
 Act Y(const Scratch& B) { return Act{B.yh, B.yl, B.ys, B.yf, B.yfm}; }
+struct MultiPass {      // the batched pass over device slots: row b = slot slots[b] at pos[b]; nruns x [slot, off, cnt], the runs of token rows per slot (kr_multi.h)
+    const KrMultiPlan& plan;      // what the pass decided (kr_multi_plan.h); its spans are relative to `tables`
+    const int32_t* tables; float* lc_scratch; float *xm_inv, *xm_tmax;      // device
+    const int32_t *slots, *pos, *runs; int nruns;                           // device
+    bool verify;      // kr_decode_verify_multi's pass: linear-attention layers record instead of storing state (docs/design/18-multi-verify.md)
+    const int32_t* table(KrMpSpan sp) const { return sp.off < 0 ? nullptr : tables + sp.off; }
+};
 struct Chunk {      // one chunk of the prompt in flight: its arena, stream and running flags
     Scratch B; float* scores; const int* tok; int Cc, pos0, set; bool first, add_is_emb; hipStream_t st;
     KrPfSync sy;      // this (chunk, layer)'s hand-overs with the previous / next chunk (set by the scheduler before every run_layer)
     bool verify = false;      // kr_decode_verify's pass: linear-attention layers write their recurrence inputs into the store's verify buffers (kr_spec.h)
-    const int32_t* m_slots = nullptr; const int32_t* m_pos = nullptr; int m_sc_ld = 0; int m_fd_chunk = 0, m_fd_chunks = 0;   // the multi-sequence step: row b = slot m_slots[b] at m_pos[b] (device)
-    int m_mla_chunk = 0, m_mla_chunks = 0;      // ... "multi_mla_fast", long slots: positions per chunk of the MLA flash-decode and the longest row's chunk count (0: the exact kernel)
-    const int32_t* m_runs = nullptr; int m_nruns = 0;      // ... and m_nruns x [slot, off, cnt] (device), the runs of token rows per slot (kr_multi.h); set whenever m_slots is
-    // ... "multi_extend_flash", a pass with a run of >= 2 tokens: the query tiles [run, t0] of its runs (device), one table per tile width 1 << w tokens at
-    // entry m_pf_off[w] with m_pf_n[w] tiles (kr_pf_tiles.h); m_pf_units = its runs of one token.  Null: every row takes the per-row attention kernels
-    const int32_t* m_pf_tiles = nullptr; int m_pf_off[8] = {0, 0, 0, 0, 0, 0, 0, 0}, m_pf_n[8] = {0, 0, 0, 0, 0, 0, 0, 0}, m_pf_units = 0;
-    // ... "multi_extend_la_chunk", a pass with a run of >= 64 tokens: its chunked runs [run, first tile] and their sub-chunks [run, sub] (device, kr_lc_tiles.h),
-    // the number of shorter runs and the chunked rule's scratch of one layer.  Null: every run takes the exact run kernels
-    const int32_t* m_lc_runs = nullptr; const int32_t* m_lc_tiles = nullptr; int m_lc_nruns = 0, m_lc_ntiles = 0, m_lc_short = 0; float* m_lc_scratch = nullptr;
-    // ... "multi_extend_mla_flash", a pass with a run of >= 2 tokens: the query-row tiles [run, tile_row] of its runs (device), one table per head count among
-    // the MLA layers: m_mf[k] = {nh, first tile, tiles} (kr_mf_tiles.h); m_mf_units = its runs of one token.  Null: every row takes the per-row MLA kernels
-    struct MfTab { int nh, off, n; };
-    const int32_t* m_mf_tiles = nullptr; std::vector<MfTab> m_mf; int m_mf_units = 0;
-    // ... "multi_extend_exact_mfma", a pass with a run of >= 2 tokens: the query tiles [run, t0] of its runs (device) for the scores pass (64 / G tokens, m_xa_*) and
-    // the P.V pass (32 / G tokens, m_xc_*), one table per tile width 1 << w as above (kr_xm_tiles.h); its runs of one token; 1 / sum and the row maxima per 32
-    // positions of every score row; one past the largest position a run reads.  Null: every row takes the per-row attention kernels
-    const int32_t* m_xm_tiles = nullptr; int m_xa_off[8] = {0, 0, 0, 0, 0, 0, 0, 0}, m_xa_n[8] = {0, 0, 0, 0, 0, 0, 0, 0}, m_xc_off[8] = {0, 0, 0, 0, 0, 0, 0, 0}, m_xc_n[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    int m_xs_split = 0;      // "multi_attn_exact_split": this pass's GQA layers launch the exact per-slot attention as scores / softmax / P.V kernels (kr_multi_split.hip)
-    int m_mla_xs_split = 0;  // "multi_mla_exact_split": this pass's MLA layers launch the exact per-slot attention as scores / softmax / weighted-sum kernels (kr_multi_mla_split.hip)
-    int m_xm_units = 0, m_xm_kv_end = 0; float *m_xm_inv = nullptr, *m_xm_tmax = nullptr;
-    // ... "multi_extend_mla_exact_mfma": the same for the MLA layers, at the tile widths 64 / nh and 32 / nh -- the tables above (a width both options ask for is
-    // built once), the same units, rows and kv_end.  m_xl_tiles = the tables' base; null: every row takes the per-row MLA kernels
-    const int32_t* m_xl_tiles = nullptr;
-    bool m_verify = false;      // kr_decode_verify_multi's pass: linear-attention layers record instead of storing state (docs/design/18-multi-verify.md)
+    const MultiPass* mp = nullptr;      // the batched pass over device slots (kr_multi_pass): what its per-slot sections read; null: a prompt pass
 };
 size_t al(size_t n) { return (n + 255) & ~(size_t)255; }
-int pf_log2(int tq) { int w = 0; while ((1 << w) < tq) w++; return w; }      // tile widths are powers of two up to 128
 }  // namespace
 
 static int pf_gemm(kr_decode_store* s, int wid, const Act& A, int C, float* out, int ld, hipStream_t st) {
@@ -121,6 +101,68 @@ static bool has_gguf_moe(const kr_decode_store* s) {
     return false;
 }
 
+// ---- the batched pass over device slots: a layer's arguments for the per-slot kernels (kr_multi.hip), from the layer, the chunk's arena and the pass
+static KrMultiLaArgs multi_la_args(kr_decode_store* s, size_t li, const Scratch& B, const MultiPass& P, float* qkvz) {
+    const kr_multi_state& M = *s->multi; const DLayer& L = s->layers[li]; const KrMultiPlan& pl = P.plan;
+    KrMultiLaArgs m{};
+    m.qkvz = qkvz; m.ld_qkvz = s->weights[L.qkvz_wid]->rows; m.ba = B.pb; m.ld_ba = s->weights[L.ba_wid]->rows;
+    m.conv_w = (const float*)L.conv_w.p; m.a_log = (const float*)L.a_log.p; m.dt_bias = (const float*)L.dt_bias.p; m.norm_w = (const float*)L.la_norm_w.p;
+    m.conv_state = (float*)M.a[li].p; m.conv_stride = M.a_stride[li] / 4; m.recur = (float*)M.b[li].p; m.recur_stride = M.b_stride[li] / 4;
+    m.conv_out = B.cv; m.out = B.attn; m.ld_out = s->weights[L.out_wid]->cols; m.nk = L.nk; m.nv = L.nv; m.dk = L.dk; m.dv = L.dv; m.hr = L.nv / L.nk; m.scale = L.la_scale; m.eps = s->eps;
+    if (P.verify) {
+        const KrMultiLaCommit& R = M.v_host[(size_t)M.v_la_of[li]];
+        m.rec_x = (float*)R.rec_x; m.rec_k = (float*)R.rec_k; m.rec_v = (float*)R.rec_v; m.rec_ge = (float*)R.rec_ge; m.rec_be = (float*)R.rec_be;
+    }
+    if (pl.lc_nruns) {      // "multi_extend_la_chunk": the runs of >= 64 tokens take the chunked rule, its output rows in B.recur ahead of the gated norm
+        m.lc_runs = P.table(pl.lc_runs); m.lc_tiles = P.table(pl.lc_tiles); m.lc_nruns = pl.lc_nruns; m.lc_ntiles = pl.lc_ntiles; m.lc_short = pl.lc_short;
+        m.lc_scratch = P.lc_scratch; m.lc_o = B.recur;
+    }
+    return m;
+}
+static KrMultiGqaArgs multi_gqa_args(kr_decode_store* s, size_t li, const Scratch& B, const MultiPass& P) {
+    const kr_multi_state& M = *s->multi; const DLayer& L = s->layers[li]; const KrMultiPlan& pl = P.plan;
+    KrMultiGqaArgs m{};
+    m.slots = P.slots; m.positions = P.pos; m.q_in = B.pa; m.k_in = B.pb; m.v_in = B.pc;
+    m.ld_q = s->weights[L.q_wid]->rows; m.ld_k = s->weights[L.k_wid]->rows; m.ld_v = s->weights[L.v_wid]->rows;
+    m.q_norm = L.q_norm_len ? (const float*)L.q_norm.p : nullptr; m.k_norm = L.k_norm_len ? (const float*)L.k_norm.p : nullptr;
+    m.q_norm_per_head = L.q_norm_len == L.nh * L.hd; m.k_norm_per_head = L.k_norm_len == L.nkv * L.hd;
+    m.rope_cos = (const float*)s->rope_cos.p; m.rope_sin = (const float*)s->rope_sin.p; m.rope_half = s->rope_half;
+    m.k_cache = M.a[li].p; m.v_cache = M.b[li].p; m.slot_elems = M.a_row[li] ? M.a_stride[li] / M.a_row[li] * L.nkv * L.hd : 0; m.kv_fp8 = M.kv_fp8;
+    m.q_out = B.q; m.gate = B.gate; m.attn_out = B.attn; m.scores = (float*)M.scores.p; m.sc_ld = pl.sc_ld;
+    if (M.pg.paged()) { m.page_table = (const int*)M.pg_table.p; m.page_stride = M.pg.stride; m.page_shift = M.pg.shift; }      // paged slots: a / b are pools
+    m.gated = L.gated; m.nh = L.nh; m.nkv = L.nkv; m.hd = L.hd; m.eps = s->eps; m.sm_scale = L.sm_scale;
+    m.xs_split = pl.xs_split;      // "multi_attn_exact_split": the exact per-slot attention as three launches
+    if (pl.fd_chunks) { m.fd_o = (float*)M.fd_o.p; m.fd_ml = (float*)M.fd_ml.p; m.fd_chunk = pl.fd_chunk; m.fd_chunks = pl.fd_chunks; }      // "multi_attn_fast", long slots
+    if (pl.gqa_runs == KR_MP_RUNS_FLASH) {      // "multi_extend_flash": the runs of >= 2 tokens take the run kernels, the per-row kernels the first nruns rows
+        const KrMpSpan t = kr_mp_pf(pl, L.nh, L.nkv);
+        m.pf_runs = P.runs; m.pf_nruns = P.nruns; m.pf_tiles = P.table(t); m.pf_ntiles = t.n; m.pf_units = pl.n_unit;
+    }
+    return m;
+}
+static KrMultiMlaArgs multi_mla_args(kr_decode_store* s, size_t li, const Scratch& B, const MultiPass& P) {
+    const kr_multi_state& M = *s->multi; const DLayer& L = s->layers[li]; const KrMultiPlan& pl = P.plan;
+    KrMultiMlaArgs m{};
+    m.slots = P.slots; m.positions = P.pos; m.kv_out = B.pb; m.ld_kv = s->weights[L.kva_wid]->rows; m.q_full = B.pa; m.ld_q = L.nh * (L.nd + L.rd);
+    m.kv_a_norm = (const float*)L.kv_a_norm.p; m.w_kc = (const float*)L.w_kc.p; m.w_vc = (const float*)L.w_vc.p;
+    m.rope_cos = (const float*)L.mla_cos.p; m.rope_sin = (const float*)L.mla_sin.p;
+    m.ckv_cache = M.a[li].p; m.kpe_cache = M.b[li].p; m.ckv_stride = M.a_stride[li]; m.kpe_stride = M.b_stride[li]; m.kv_fp8 = M.kv_fp8;
+    m.q_abs = B.q; m.q_pe = B.z; m.attn_lat = B.recur; m.v_proj = B.attn; m.scores = (float*)M.scores.p; m.sc_ld = pl.sc_ld;
+    m.nh = L.nh; m.klr = L.klr; m.nd = L.nd; m.rd = L.rd; m.vhd = L.vhd; m.eps = s->eps; m.sm_scale = L.sm_scale;
+    if (M.pg.paged()) { m.page_table = (const int*)M.pg_table.p; m.page_stride = M.pg.stride; m.page_shift = M.pg.shift; }      // paged slots: the strides are a page's bytes
+    m.xs_split = pl.mla_xs_split;      // "multi_mla_exact_split": the exact per-slot attention as three launches
+    if (pl.mla_chunks) { m.fd_o = (float*)M.fd_o.p; m.fd_ml = (float*)M.fd_ml.p; m.fd_chunk = pl.mla_chunk; m.fd_chunks = pl.mla_chunks; }      // "multi_mla_fast", long slots
+    if (pl.mla_runs == KR_MP_RUNS_FLASH) {      // "multi_extend_mla_flash": the runs of >= 2 tokens take the run kernel, the per-row kernels the first nruns rows
+        const KrMpSpan t = kr_mp_mf(pl, L.nh);
+        m.mf_runs = P.runs; m.mf_nruns = P.nruns; m.mf_tiles = P.table(t); m.mf_ntiles = t.n; m.mf_units = pl.n_unit;
+    }
+    return m;
+}
+// the matrix-core passes' tables of a layer of nh heads over nkv rows (MLA: 1), the score rows' 1 / sum and maxima, one past the largest position a run reads
+static KrMultiXmArgs multi_xm_args(const MultiPass& P, int nh, int nkv) {
+    const KrMpSpan a = kr_mp_xa(P.plan, nh, nkv), c = kr_mp_xc(P.plan, nh, nkv);
+    return KrMultiXmArgs{P.table(a), P.table(c), a.n, c.n, P.xm_inv, P.xm_tmax, P.plan.kv_end};
+}
+
 // everything a layer launches, for one chunk, on the chunk's stream
 static int run_layer(kr_decode_store* s, Chunk& cx, size_t li) {
     kr_engine* e = s->eng;
@@ -144,23 +186,10 @@ static int run_layer(kr_decode_store* s, Chunk& cx, size_t li) {
         float* qkvz = vc ? (float*)vc->qkvz : B.pa;
         { const int wids[2] = {L.qkvz_wid, L.ba_wid}; float* outs[2] = {qkvz, B.pb}; const int lds[2] = {nq, nb};
           if (int rc = pf_gemm_multi(s, wids, outs, lds, 2, X(B), Cc, st)) return rc; }
-        if (cx.m_slots) {      // multi-sequence step: every row advances its own slot's conv / recurrent state (kr_multi.hip)
-            kr_multi_state& M = *s->multi;
-            KrMultiLaArgs m{};
-            m.qkvz = qkvz; m.ld_qkvz = nq; m.ba = B.pb; m.ld_ba = nb;
-            m.conv_w = (const float*)L.conv_w.p; m.a_log = (const float*)L.a_log.p; m.dt_bias = (const float*)L.dt_bias.p; m.norm_w = (const float*)L.la_norm_w.p;
-            m.conv_state = (float*)M.a[li].p; m.conv_stride = M.a_stride[li] / 4; m.recur = (float*)M.b[li].p; m.recur_stride = M.b_stride[li] / 4;
-            m.conv_out = B.cv; m.out = B.attn; m.ld_out = oc; m.nk = L.nk; m.nv = L.nv; m.dk = L.dk; m.dv = L.dv; m.hr = L.nv / L.nk; m.scale = L.la_scale; m.eps = s->eps;
+        if (cx.mp) {      // multi-sequence step: every row advances its own slot's conv / recurrent state (kr_multi.hip)
             if (oc != L.nv * L.dv) return kr_fail(KR_ERR_VALUE, "out_proj cols %d != nv*dv", oc);
-            if (cx.m_verify) {
-                const KrMultiLaCommit& R = M.v_host[(size_t)M.v_la_of[li]];
-                m.rec_x = (float*)R.rec_x; m.rec_k = (float*)R.rec_k; m.rec_v = (float*)R.rec_v; m.rec_ge = (float*)R.rec_ge; m.rec_be = (float*)R.rec_be;
-            }
-            if (cx.m_lc_runs) {      // "multi_extend_la_chunk": the runs of >= 64 tokens take the chunked rule, its output rows in B.recur ahead of the gated norm
-                m.lc_runs = cx.m_lc_runs; m.lc_tiles = cx.m_lc_tiles; m.lc_nruns = cx.m_lc_nruns; m.lc_ntiles = cx.m_lc_ntiles; m.lc_short = cx.m_lc_short;
-                m.lc_scratch = cx.m_lc_scratch; m.lc_o = B.recur;
-            }
-            if (kr_launch_multi_la(m, cx.m_runs, cx.m_nruns, Cc, st)) return kr_fail(KR_ERR_VALUE, "unsupported linear-attention geometry for the multi-sequence step");
+            const KrMultiLaArgs m = multi_la_args(s, li, B, *cx.mp, qkvz);
+            if (kr_launch_multi_la(m, cx.mp->runs, cx.mp->nruns, Cc, st)) return kr_fail(KR_ERR_VALUE, "unsupported linear-attention geometry for the multi-sequence step");
         } else {
             KrPfmLaArgs a{};
             a.qkvz = qkvz; a.ld_qkvz = nq; a.ba = B.pb; a.ld_ba = nb; a.conv_state = (float*)L.conv_state.p; a.conv_w = (const float*)L.conv_w.p;
@@ -175,32 +204,16 @@ static int run_layer(kr_decode_store* s, Chunk& cx, size_t li) {
         pf_rows(s, B.attn, Cc, oc, oc, B, true, st);
         if (int rc = pf_gemm(s, L.out_wid, Y(B), Cc, B.hid, H, st)) return rc;
     } else if (L.attn == ATTN_GQA) {
-        if (!L.kv_k.p && !cx.m_slots) return kr_fail(KR_ERR_STATE, "set_decode_state was not called (no KV cache for layer %zu)", li);
+        if (!L.kv_k.p && !cx.mp) return kr_fail(KR_ERR_STATE, "set_decode_state was not called (no KV cache for layer %zu)", li);
         const int nq = s->weights[L.q_wid]->rows, nk_ = s->weights[L.k_wid]->rows, nv_ = s->weights[L.v_wid]->rows, oc = s->weights[L.o_wid]->cols;
         { const int wids[3] = {L.q_wid, L.k_wid, L.v_wid}; float* outs[3] = {B.pa, B.pb, B.pc}; const int lds[3] = {nq, nk_, nv_};
           if (int rc = pf_gemm_multi(s, wids, outs, lds, 3, X(B), Cc, st)) return rc; }
-        if (cx.m_slots) {      // multi-sequence step: each row appends to and attends over its own slot at its own position (kr_multi.hip)
-            kr_multi_state& M = *s->multi;
+        if (cx.mp) {      // multi-sequence step: each row appends to and attends over its own slot at its own position (kr_multi.hip)
+            const MultiPass& P = *cx.mp;
             if (oc != L.nh * L.hd) return kr_fail(KR_ERR_VALUE, "o_proj cols %d != nh*hd", oc);
-            KrMultiGqaArgs m{};
-            m.slots = cx.m_slots; m.positions = cx.m_pos; m.q_in = B.pa; m.k_in = B.pb; m.v_in = B.pc; m.ld_q = nq; m.ld_k = nk_; m.ld_v = nv_;
-            m.q_norm = L.q_norm_len ? (const float*)L.q_norm.p : nullptr; m.k_norm = L.k_norm_len ? (const float*)L.k_norm.p : nullptr;
-            m.q_norm_per_head = L.q_norm_len == L.nh * L.hd; m.k_norm_per_head = L.k_norm_len == L.nkv * L.hd;
-            m.rope_cos = (const float*)s->rope_cos.p; m.rope_sin = (const float*)s->rope_sin.p; m.rope_half = s->rope_half;
-            m.k_cache = M.a[li].p; m.v_cache = M.b[li].p; m.slot_elems = M.a_row[li] ? M.a_stride[li] / M.a_row[li] * L.nkv * L.hd : 0; m.kv_fp8 = M.kv_fp8;
-            m.q_out = B.q; m.gate = B.gate; m.attn_out = B.attn; m.scores = (float*)M.scores.p; m.sc_ld = cx.m_sc_ld;
-            if (M.pg.paged()) { m.page_table = (const int*)M.pg_table.p; m.page_stride = M.pg.stride; m.page_shift = M.pg.shift; }      // paged slots: a / b are pools
-            m.gated = L.gated; m.nh = L.nh; m.nkv = L.nkv; m.hd = L.hd; m.eps = s->eps; m.sm_scale = L.sm_scale;
-            m.xs_split = cx.m_xs_split;      // "multi_attn_exact_split": the exact per-slot attention as three launches
-            if (cx.m_fd_chunks) { m.fd_o = (float*)M.fd_o.p; m.fd_ml = (float*)M.fd_ml.p; m.fd_chunk = cx.m_fd_chunk; m.fd_chunks = cx.m_fd_chunks; }      // "multi_attn_fast", long slots
-            if (cx.m_pf_tiles) {      // "multi_extend_flash": the runs of >= 2 tokens take the run kernels, the per-row kernels the first m_nruns rows
-                const int w = pf_log2(kr_pf_tile_tokens(L.nh, L.nkv));
-                m.pf_runs = cx.m_runs; m.pf_nruns = cx.m_nruns; m.pf_tiles = cx.m_pf_tiles + 2 * (size_t)cx.m_pf_off[w]; m.pf_ntiles = cx.m_pf_n[w]; m.pf_units = cx.m_pf_units;
-            }
-            if (cx.m_xm_tiles) {      // "multi_extend_exact_mfma": the runs of >= 2 tokens take the three exact matrix-core passes, the per-row kernels the first m_nruns rows
-                const int wa = pf_log2(kr_xm_tile_tokens_a(L.nh, L.nkv)), wc = pf_log2(kr_xm_tile_tokens_c(L.nh, L.nkv));
-                KrMultiXmArgs x{cx.m_xm_tiles + 2 * (size_t)cx.m_xa_off[wa], cx.m_xm_tiles + 2 * (size_t)cx.m_xc_off[wc], cx.m_xa_n[wa], cx.m_xc_n[wc], cx.m_xm_inv, cx.m_xm_tmax, cx.m_xm_kv_end};
-                if (kr_launch_multi_gqa_xm(m, x, cx.m_runs, cx.m_nruns, cx.m_xm_units, Cc, st))
+            const KrMultiGqaArgs m = multi_gqa_args(s, li, B, P);
+            if (P.plan.gqa_runs == KR_MP_RUNS_XM) {      // "multi_extend_exact_mfma": the runs of >= 2 tokens take the three exact matrix-core passes, the per-row kernels the first nruns rows
+                if (kr_launch_multi_gqa_xm(m, multi_xm_args(P, L.nh, L.nkv), P.runs, P.nruns, P.plan.n_unit, Cc, st))
                     return kr_fail(KR_ERR_VALUE, "multi_extend_exact_mfma: unsupported GQA geometry for the multi-sequence step (nh %d nkv %d head_dim %d)", L.nh, L.nkv, L.hd);
             } else if (kr_launch_multi_gqa(m, Cc, st)) return kr_fail(KR_ERR_VALUE, "unsupported GQA geometry for the multi-sequence step");
         } else {
@@ -234,8 +247,8 @@ static int run_layer(kr_decode_store* s, Chunk& cx, size_t li) {
         // MLA (decode.rs:2993-3252): batched projections on the GEMM, then the three decode launches with a token dimension.  The
         // prep launch appends every token's latent / rope rows before the attention launch reads them, so token t of the chunk
         // sees exactly the cache decode_step would have built.
-        if (!L.kv_k.p && !cx.m_slots) return kr_fail(KR_ERR_STATE, "set_decode_state was not called (no MLA cache for layer %zu)", li);
-        if (!cx.m_slots && L.mla_rope_seq < pos0 + Cc) return kr_fail(KR_ERR_VALUE, "prompt exceeds the MLA rope table (%d)", L.mla_rope_seq);
+        if (!L.kv_k.p && !cx.mp) return kr_fail(KR_ERR_STATE, "set_decode_state was not called (no MLA cache for layer %zu)", li);
+        if (!cx.mp && L.mla_rope_seq < pos0 + Cc) return kr_fail(KR_ERR_VALUE, "prompt exceeds the MLA rope table (%d)", L.mla_rope_seq);
         const int nkv = s->weights[L.kva_wid]->rows, nq = L.nh * (L.nd + L.rd), oc = s->weights[L.o_wid]->cols;
         if (int rc = pf_gemm(s, L.kva_wid, X(B), Cc, B.pb, nkv, st)) return rc;
         if (L.mq_wid >= 0) {
@@ -248,31 +261,16 @@ static int run_layer(kr_decode_store* s, Chunk& cx, size_t li) {
             pf_rows(s, B.pc, Cc, qlr, qlr, B, true, st);
             if (int rc = pf_gemm(s, L.mqb_wid, Y(B), Cc, B.pa, nq, st)) return rc;
         }
-        if (cx.m_slots) {      // multi-sequence step: each row appends to and attends over its own slot at its own position (kr_multi.hip); row positions
-                               // were bounded by the shortest MLA rope table before the pass (check_args, kr_decode_multi.cpp)
-            kr_multi_state& M = *s->multi;
-            KrMultiMlaArgs m{};
-            m.slots = cx.m_slots; m.positions = cx.m_pos; m.kv_out = B.pb; m.ld_kv = nkv; m.q_full = B.pa; m.ld_q = nq;
-            m.kv_a_norm = (const float*)L.kv_a_norm.p; m.w_kc = (const float*)L.w_kc.p; m.w_vc = (const float*)L.w_vc.p;
-            m.rope_cos = (const float*)L.mla_cos.p; m.rope_sin = (const float*)L.mla_sin.p;
-            m.ckv_cache = M.a[li].p; m.kpe_cache = M.b[li].p; m.ckv_stride = M.a_stride[li]; m.kpe_stride = M.b_stride[li]; m.kv_fp8 = M.kv_fp8;
-            m.q_abs = B.q; m.q_pe = B.z; m.attn_lat = B.recur; m.v_proj = B.attn; m.scores = (float*)M.scores.p; m.sc_ld = cx.m_sc_ld;
-            m.nh = L.nh; m.klr = L.klr; m.nd = L.nd; m.rd = L.rd; m.vhd = L.vhd; m.eps = s->eps; m.sm_scale = L.sm_scale;
-            if (M.pg.paged()) { m.page_table = (const int*)M.pg_table.p; m.page_stride = M.pg.stride; m.page_shift = M.pg.shift; }      // paged slots: the strides are a page's bytes
-            m.xs_split = cx.m_mla_xs_split;      // "multi_mla_exact_split": the exact per-slot attention as three launches
-            if (cx.m_mla_chunks) { m.fd_o = (float*)M.fd_o.p; m.fd_ml = (float*)M.fd_ml.p; m.fd_chunk = cx.m_mla_chunk; m.fd_chunks = cx.m_mla_chunks; }      // "multi_mla_fast", long slots
-            if (cx.m_mf_tiles) {      // "multi_extend_mla_flash": the runs of >= 2 tokens take the run kernel, the per-row kernels the first m_nruns rows
-                for (const Chunk::MfTab& t : cx.m_mf)
-                    if (t.nh == L.nh) { m.mf_tiles = cx.m_mf_tiles + 2 * (size_t)t.off; m.mf_ntiles = t.n; }
-                m.mf_runs = cx.m_runs; m.mf_nruns = cx.m_nruns; m.mf_units = cx.m_mf_units;
-                if (!m.mf_tiles || !kr_multi_mla_pf_args_ok(m)) return kr_fail(KR_ERR_VALUE, "multi_extend_mla_flash: MLA geometry of layer %zu not covered by the run kernel", li);
-            }
+        if (cx.mp) {      // multi-sequence step: each row appends to and attends over its own slot at its own position (kr_multi.hip); row positions
+                          // were bounded by the shortest MLA rope table before the pass (check_args, kr_decode_multi.cpp)
+            const MultiPass& P = *cx.mp;
+            const KrMultiMlaArgs m = multi_mla_args(s, li, B, P);
+            if (P.plan.mla_runs == KR_MP_RUNS_FLASH && (!m.mf_tiles || !kr_multi_mla_pf_args_ok(m)))
+                return kr_fail(KR_ERR_VALUE, "multi_extend_mla_flash: MLA geometry of layer %zu not covered by the run kernel", li);
             if (nkv < L.klr + L.rd) return kr_fail(KR_ERR_VALUE, "kv_a_proj rows %d < kv_lora_rank + rope dim", nkv);
             if (oc != L.nh * L.vhd) return kr_fail(KR_ERR_VALUE, "o_proj cols %d != nh*v_head_dim", oc);
-            if (cx.m_xl_tiles) {      // "multi_extend_mla_exact_mfma": the runs of >= 2 tokens take the three exact matrix-core passes, the per-row kernels the first m_nruns rows
-                const int wa = pf_log2(kr_xm_tile_tokens_a(L.nh, 1)), wc = pf_log2(kr_xm_tile_tokens_c(L.nh, 1));
-                KrMultiXmArgs x{cx.m_xl_tiles + 2 * (size_t)cx.m_xa_off[wa], cx.m_xl_tiles + 2 * (size_t)cx.m_xc_off[wc], cx.m_xa_n[wa], cx.m_xc_n[wc], cx.m_xm_inv, cx.m_xm_tmax, cx.m_xm_kv_end};
-                if (kr_launch_multi_mla_xm(m, x, cx.m_runs, cx.m_nruns, cx.m_xm_units, Cc, st))
+            if (P.plan.mla_runs == KR_MP_RUNS_XM) {      // "multi_extend_mla_exact_mfma": the runs of >= 2 tokens take the three exact matrix-core passes, the per-row kernels the first nruns rows
+                if (kr_launch_multi_mla_xm(m, multi_xm_args(P, L.nh, 1), P.runs, P.nruns, P.plan.n_unit, Cc, st))
                     return kr_fail(KR_ERR_VALUE, "multi_extend_mla_exact_mfma: unsupported MLA geometry for the multi-sequence step (heads %d kv_lora_rank %d rope %d)", L.nh, L.klr, L.rd);
             } else if (kr_launch_multi_mla(m, Cc, st)) return kr_fail(KR_ERR_VALUE, "unsupported MLA geometry for the multi-sequence step");
         } else {
@@ -645,6 +643,15 @@ int kr_spec_pending_fail(kr_decode_store* s) {
     return s && s->spec_pending ? kr_fail(KR_ERR_STATE, "a kr_decode_verify is pending: kr_decode_commit must come first") : KR_OK;
 }
 
+// paged slots under "multi_attn_fast" alone: the entry point refuses the call with the words it always had (paged_refuse, kr_decode_multi.cpp), unless its
+// argument check does first; every refusal of a later option stands back there, so that one stays ahead of theirs
+bool paged_refused(const kr_decode_store* s) { return s->multi && s->multi->pg.paged() && s->opt_multi_attn_fast && !s->opt_multi_attn_fast_paged; }
+// the store has a layer of this attention kind (ATTN_*)
+bool has_attn(const kr_decode_store* s, int kind) {
+    for (const DLayer& L : s->layers) if (L.attn == kind) return true;
+    return false;
+}
+
 // what no exact pass over this store runs: tolerance modes, expert parallelism, MoE layers without an engine or with native-GGUF experts (unless the
 // "gguf_exact_pass" option gives those an exact pass, docs/design/20-gguf-exact-pass.md), geometries the
 // verify-form kernels do not cover.  slots: the pass over device slots (multi_refuse, kr_decode_multi.cpp), whose messages start with another noun and whose
@@ -679,25 +686,16 @@ int kr_exact_refuse(kr_decode_store* s, bool slots) {
     // trap.  More than 64 heads, or a geometry outside the flash kernel's: the single-sequence launcher falls back to the exact kernels there
     // (kr_launch_mla_flash_decode), so there would be no fast step to be identical to
     if (slots && s->opt_multi_mla_fast) {
-        bool mla = false;
-        for (const DLayer& L : s->layers) {
-            if (L.attn != ATTN_MLA) continue;
-            mla = true;
-            if (!kr_multi_mla_fd_ok(L.nh, L.klr, L.rd))
+        for (const DLayer& L : s->layers)
+            if (L.attn == ATTN_MLA && !kr_multi_mla_fd_ok(L.nh, L.klr, L.rd))
                 return kr_fail(KR_ERR_VALUE, "multi_mla_fast: MLA geometry heads %d kv_lora_rank %d rope %d not covered (at most 64 heads, kv_lora_rank 512 / 256, rope 64)", L.nh, L.klr, L.rd);
-        }
-        if (!mla) return kr_fail(KR_ERR_STATE, "the \"multi_mla_fast\" option covers MLA layers only: this store has none (set the option to 0 for the exact step)");
+        if (!has_attn(s, ATTN_MLA)) return kr_fail(KR_ERR_STATE, "the \"multi_mla_fast\" option covers MLA layers only: this store has none (set the option to 0 for the exact step)");
     }
-    // paged slots under "multi_attn_fast" alone: the entry point refuses the call a few lines on with the words it always had (paged_refuse in kr_decode_multi.cpp),
-    // unless its argument check does first; the clauses of the run options below stand back so that refusal stays ahead of theirs
-    const bool paged_refused = slots && s->multi && s->multi->pg.paged() && s->opt_multi_attn_fast && !s->opt_multi_attn_fast_paged;
     // "multi_extend_mla_flash", behind everything refused before the option existed.  A store without an MLA layer: an option that silently does nothing is a trap.
     // The run kernel's geometry rule (kr_launch_mla_flash's: kv_lora_rank 512 / 256, rope 64, any head count) is kr_multi_mla_ok's, which the loop above has asked
     // of every MLA layer.  The LDS windows of the run kernel's instantiations are raised here, once per slot set: a refusal leaves nothing reserved or advanced
-    if (slots && s->opt_multi_extend_mla_flash && !paged_refused) {
-        bool mla = false;
-        for (const DLayer& L : s->layers) mla |= L.attn == ATTN_MLA;
-        if (!mla) return kr_fail(KR_ERR_STATE, "the \"multi_extend_mla_flash\" option covers MLA layers only: this store has none (set the option to 0 for the exact pass)");
+    if (slots && s->opt_multi_extend_mla_flash && !paged_refused(s)) {
+        if (!has_attn(s, ATTN_MLA)) return kr_fail(KR_ERR_STATE, "the \"multi_extend_mla_flash\" option covers MLA layers only: this store has none (set the option to 0 for the exact pass)");
         if (s->multi && !s->multi->mf_ready) {
             KR_HIP(hipSetDevice(e->device));
             for (const DLayer& L : s->layers)
@@ -709,15 +707,12 @@ int kr_exact_refuse(kr_decode_store* s, bool slots) {
     // "multi_extend_flash", behind everything refused before the option existed.  An MLA layer: its runs would stay exact beside flash GQA runs, and no
     // single-sequence pass is like that.  No GQA layer: an option that silently does nothing is a trap.  A geometry outside the prompt pass's flash kernels is an
     // error, not a fall-back.  The LDS windows of the run kernels are raised here, once per slot set: a refusal leaves nothing reserved or advanced
-    // (paged slots under "multi_attn_fast" alone: the entry point refuses the call a few lines on with the words it always had, paged_refuse in kr_decode_multi.cpp,
-    // unless its argument check does first; this clause stands back so that refusal stays ahead of it)
-    if (slots && s->opt_multi_extend_flash && !paged_refused) {
-        bool gqa = false;
+    // (it stands back where paged_refused holds, like the clause above and the one below)
+    if (slots && s->opt_multi_extend_flash && !paged_refused(s)) {
         for (size_t i = 0; i < s->layers.size(); i++)
             if (s->layers[i].attn == ATTN_MLA)
                 return kr_fail(KR_ERR_STATE, "the \"multi_extend_flash\" option covers GQA layers only: layer %zu is MLA (set the option to 0 for the exact pass)", i);
-        for (const DLayer& L : s->layers) gqa |= L.attn == ATTN_GQA;
-        if (!gqa) return kr_fail(KR_ERR_STATE, "the \"multi_extend_flash\" option covers GQA layers only: this store has none (set the option to 0 for the exact pass)");
+        if (!has_attn(s, ATTN_GQA)) return kr_fail(KR_ERR_STATE, "the \"multi_extend_flash\" option covers GQA layers only: this store has none (set the option to 0 for the exact pass)");
         for (const DLayer& L : s->layers)
             if (L.attn == ATTN_GQA && !kr_pfm_gqa_flash_ok(L.nh, L.nkv, L.hd))
                 return kr_fail(KR_ERR_VALUE, "multi_extend_flash: GQA geometry nh %d nkv %d head_dim %d not covered (heads per KV head must divide 128, head_dim 64 / 128 / 256)", L.nh, L.nkv, L.hd);
@@ -733,10 +728,8 @@ int kr_exact_refuse(kr_decode_store* s, bool slots) {
     // that silently does nothing is a trap.  An MLA layer: its runs would stay exact beside chunked linear-attention runs, and no single-sequence pass is like
     // that.  A layer outside the chunked rule's geometry is an error, not a fall-back to the run kernels.  The LDS windows of the two kernels are raised here, once
     // per slot set: a refusal leaves nothing advanced
-    if (slots && s->opt_multi_extend_la_chunk && !paged_refused) {
-        bool la = false;
-        for (const DLayer& L : s->layers) la |= L.attn == ATTN_LA;
-        if (!la) return kr_fail(KR_ERR_STATE, "the \"multi_extend_la_chunk\" option covers linear-attention layers only: this store has none (set the option to 0 for the exact pass)");
+    if (slots && s->opt_multi_extend_la_chunk && !paged_refused(s)) {
+        if (!has_attn(s, ATTN_LA)) return kr_fail(KR_ERR_STATE, "the \"multi_extend_la_chunk\" option covers linear-attention layers only: this store has none (set the option to 0 for the exact pass)");
         for (size_t i = 0; i < s->layers.size(); i++)
             if (s->layers[i].attn == ATTN_MLA)
                 return kr_fail(KR_ERR_STATE, "the \"multi_extend_la_chunk\" option covers linear-attention layers only: layer %zu is MLA (set the option to 0 for the exact pass)", i);
@@ -756,16 +749,12 @@ int kr_spec_refuse(kr_decode_store* s) { return kr_exact_refuse(s, false); }
 // "multi_extend_exact_mfma" (docs/design/28-multi-extend-exact-mfma.md): what multi_refuse (kr_decode_multi.cpp) asks directly behind kr_exact_refuse(s, true), so
 // everything refused before the option existed is refused first and with the same words.  With "multi_extend_flash": two options claim the runs of >= 2 tokens.
 // No GQA layer: an option that silently does nothing is a trap.  A GQA layer outside the matrix-core passes' geometry is an error, not a fall-back to the per-row
-// kernel.  Nothing to prepare: the kernels' static LDS is below the default window.  (Paged slots under "multi_attn_fast" alone: the entry point refuses the call a
-// few lines on with the words it always had, paged_refuse in kr_decode_multi.cpp, unless its argument check does first; this check stands back like its siblings)
+// kernel.  Nothing to prepare: the kernels' static LDS is below the default window.  It stands back where paged_refused holds, like its siblings
 int kr_xm_refuse(kr_decode_store* s) {
-    if (!s->opt_multi_extend_exact_mfma) return KR_OK;
-    if (s->multi && s->multi->pg.paged() && s->opt_multi_attn_fast && !s->opt_multi_attn_fast_paged) return KR_OK;      // paged_refused
+    if (!s->opt_multi_extend_exact_mfma || paged_refused(s)) return KR_OK;
     if (s->opt_multi_extend_flash)
         return kr_fail(KR_ERR_STATE, "the \"multi_extend_exact_mfma\" and \"multi_extend_flash\" options both claim the runs of >= 2 tokens of the GQA layers: set one of them to 0");
-    bool gqa = false;
-    for (const DLayer& L : s->layers) gqa |= L.attn == ATTN_GQA;
-    if (!gqa) return kr_fail(KR_ERR_STATE, "the \"multi_extend_exact_mfma\" option covers GQA layers only: this store has none (set the option to 0)");
+    if (!has_attn(s, ATTN_GQA)) return kr_fail(KR_ERR_STATE, "the \"multi_extend_exact_mfma\" option covers GQA layers only: this store has none (set the option to 0)");
     for (const DLayer& L : s->layers) {
         if (L.attn != ATTN_GQA) continue;
         KrPfmGqaArgs g{};
@@ -782,13 +771,10 @@ int kr_xm_refuse(kr_decode_store* s) {
 // error, not a fall-back to the per-row kernel.  Nothing to prepare: the kernels' static LDS is below the default window.  It stands back where the entry point's
 // paged refusal applies, like kr_xm_refuse
 int kr_mla_xm_refuse(kr_decode_store* s) {
-    if (!s->opt_multi_extend_mla_exact_mfma) return KR_OK;
-    if (s->multi && s->multi->pg.paged() && s->opt_multi_attn_fast && !s->opt_multi_attn_fast_paged) return KR_OK;      // paged_refused
+    if (!s->opt_multi_extend_mla_exact_mfma || paged_refused(s)) return KR_OK;
     if (s->opt_multi_extend_mla_flash)
         return kr_fail(KR_ERR_STATE, "the \"multi_extend_mla_exact_mfma\" and \"multi_extend_mla_flash\" options both claim the runs of >= 2 tokens of the MLA layers: set one of them to 0");
-    bool mla = false;
-    for (const DLayer& L : s->layers) mla |= L.attn == ATTN_MLA;
-    if (!mla) return kr_fail(KR_ERR_STATE, "the \"multi_extend_mla_exact_mfma\" option covers MLA layers only: this store has none (set the option to 0)");
+    if (!has_attn(s, ATTN_MLA)) return kr_fail(KR_ERR_STATE, "the \"multi_extend_mla_exact_mfma\" option covers MLA layers only: this store has none (set the option to 0)");
     for (const DLayer& L : s->layers)
         if (L.attn == ATTN_MLA && !kr_mla_exact_mfma_ok(L.nh, L.klr, L.rd))
             return kr_fail(KR_ERR_VALUE, "multi_extend_mla_exact_mfma: MLA geometry heads %d kv_lora_rank %d rope %d not covered (the head count must divide 32, kv_lora_rank 512 / 256, rope 64; set the option to 0 for the per-row kernel)", L.nh, L.klr, L.rd);
@@ -799,11 +785,8 @@ int kr_mla_xm_refuse(kr_decode_store* s) {
 // is refused first and with the same words.  No GQA layer: an option that silently does nothing is a trap.  Nothing else: the three launches cover every geometry
 // the one kernel covers, and the pass makes that kernel's checks either way.  It stands back where the entry point's paged refusal applies, like its siblings
 int kr_xs_refuse(kr_decode_store* s) {
-    if (!s->opt_multi_attn_exact_split) return KR_OK;
-    if (s->multi && s->multi->pg.paged() && s->opt_multi_attn_fast && !s->opt_multi_attn_fast_paged) return KR_OK;      // paged_refused
-    bool gqa = false;
-    for (const DLayer& L : s->layers) gqa |= L.attn == ATTN_GQA;
-    if (!gqa) return kr_fail(KR_ERR_STATE, "the \"multi_attn_exact_split\" option covers GQA layers only: this store has none (set the option to 0)");
+    if (!s->opt_multi_attn_exact_split || paged_refused(s)) return KR_OK;
+    if (!has_attn(s, ATTN_GQA)) return kr_fail(KR_ERR_STATE, "the \"multi_attn_exact_split\" option covers GQA layers only: this store has none (set the option to 0)");
     return KR_OK;
 }
 
@@ -811,11 +794,8 @@ int kr_xs_refuse(kr_decode_store* s) {
 // is refused first and with the same words.  No MLA layer: an option that silently does nothing is a trap.  Nothing else: the three launches cover every geometry
 // the one kernel covers, and the pass makes that kernel's checks either way.  It stands back where the entry point's paged refusal applies, like its siblings
 int kr_mla_xs_refuse(kr_decode_store* s) {
-    if (!s->opt_multi_mla_exact_split) return KR_OK;
-    if (s->multi && s->multi->pg.paged() && s->opt_multi_attn_fast && !s->opt_multi_attn_fast_paged) return KR_OK;      // paged_refused
-    bool mla = false;
-    for (const DLayer& L : s->layers) mla |= L.attn == ATTN_MLA;
-    if (!mla) return kr_fail(KR_ERR_STATE, "the \"multi_mla_exact_split\" option covers MLA layers only: this store has none (set the option to 0)");
+    if (!s->opt_multi_mla_exact_split || paged_refused(s)) return KR_OK;
+    if (!has_attn(s, ATTN_MLA)) return kr_fail(KR_ERR_STATE, "the \"multi_mla_exact_split\" option covers MLA layers only: this store has none (set the option to 0)");
     return KR_OK;
 }
 
@@ -925,175 +905,57 @@ int kr_multi_pass(kr_decode_store* s, int n, int n_final, const int32_t* d_rows,
     kr_multi_state& M = *s->multi;
     PfLayout Lo;
     if (int rc = pf_layout(s, (size_t)n, true, true, st, Lo)) return rc;
-    int nh_max = 1; size_t gqa_row = 0, mla_row = 0; bool has_gqa = false, has_mla = false;
-    for (const DLayer& L : s->layers) {
-        if (L.attn == ATTN_GQA || L.attn == ATTN_MLA) nh_max = std::max(nh_max, L.nh);      // a score row per query head of either kind
-        if (L.attn == ATTN_GQA) { has_gqa = true; gqa_row = std::max(gqa_row, (size_t)L.nh * L.hd); }
-        if (L.attn == ATTN_MLA) { has_mla = true; mla_row = std::max(mla_row, (size_t)L.nh * L.klr); }
+    // everything the pass decides, from plain values (kr_multi_plan.h, docs/design/32-multi-pass-plan.md); here: allocation, upload and launch
+    KrMultiPlanOpts o{};
+    o.attn_fast = s->opt_multi_attn_fast || s->opt_multi_attn_fast_paged; o.mla_fast = s->opt_multi_mla_fast;
+    o.extend_flash = s->opt_multi_extend_flash; o.extend_mla_flash = s->opt_multi_extend_mla_flash; o.extend_la_chunk = s->opt_multi_extend_la_chunk;
+    o.extend_exact_mfma = s->opt_multi_extend_exact_mfma; o.extend_mla_exact_mfma = s->opt_multi_extend_mla_exact_mfma;
+    o.attn_exact_split = s->opt_multi_attn_exact_split; o.attn_exact_split_min = s->opt_multi_attn_exact_split_min;
+    o.mla_exact_split = s->opt_multi_mla_exact_split; o.mla_exact_split_min = s->opt_multi_mla_exact_split_min;
+    o.gqa_split_min = s->gqa_split_min; o.mla_split_min = s->mla_split_min;
+    o.max_seq = M.max_seq; o.fd_chunk = kr_fd_flash_chunk(M.max_seq); o.mla_chunk = kr_mla_flash_decode_chunk(M.max_seq);
+    std::vector<KrMultiPlanLayer> pl_layers;
+    for (const DLayer& L : s->layers) pl_layers.push_back(KrMultiPlanLayer{L.attn, L.nh, L.nkv, L.hd, L.klr, L.nv});      // ATTN_* are KR_MP_*
+    static_assert(ATTN_NONE == KR_MP_OTHER && ATTN_LA == KR_MP_LA && ATTN_GQA == KR_MP_GQA && ATTN_MLA == KR_MP_MLA, "the plan's layer kinds are the store's");
+    KrMultiPlan plan;
+    switch (kr_multi_plan(o, pl_layers.data(), (int)pl_layers.size(), KrMultiPlanRows{n, n_final, max_pos, verify, h_counts, h_positions}, plan)) {
+    case KR_MP_GQA_CHUNKS: return kr_fail(KR_ERR_VALUE, "multi_attn_fast: position %d needs %d chunks of %d positions (at most 1024)", plan.attn_pos, plan.fd_chunks, plan.fd_chunk);
+    case KR_MP_MLA_CHUNKS: return kr_fail(KR_ERR_VALUE, "multi_mla_fast: position %d needs %d chunks of %d positions (at most 1024)", plan.mla_pos, plan.mla_chunks, plan.mla_chunk);
     }
-    // "multi_attn_fast": over slots longer than gqa_split_min (the capacity rule of the store's own KR_ATTN_FAST step) every GQA layer takes the split-KV
-    // flash-decode; the partials are sized by this step's longest row, and the score rows are not needed unless another kind of layer reads them
-    // "multi_attn_fast_paged": the same over flat and paged slots; paged ones read through the table (docs/design/23-multi-attn-fast-paged.md)
-    const bool flash = (s->opt_multi_attn_fast || s->opt_multi_attn_fast_paged) && has_gqa && M.max_seq > s->gqa_split_min;
-    // "multi_mla_fast": the same for every MLA layer over slots longer than mla_split_min, flat or paged (docs/design/24-multi-mla-fast.md).  Its chunks are
-    // kr_mla_flash_decode_chunk's (64 / 128 positions against the GQA kernels' 128 / 256), so both counts travel with the pass; the partials of the two kinds
-    // of layer share M.fd_o / M.fd_ml, sized for the larger need
-    const bool mla_flash = s->opt_multi_mla_fast && has_mla && M.max_seq > s->mla_split_min;
-    // "multi_extend_flash": a non-verify pass with a run of >= 2 tokens gives those runs the run kernels (docs/design/25-multi-extend-flash.md).  The per-row
-    // kernels then see the unit rows only, which lie among the first n_final rows: their score rows and split-KV partials are sized by n_final rows and the
-    // unit rows' longest position, not by every token row at the pass's longest.  Off, or every run of one token: attn_rows = n, attn_pos = max_pos, as ever
-    bool pf = false; int n_unit = 0, attn_rows = n, attn_pos = max_pos;
-    if (s->opt_multi_extend_flash && !verify && has_gqa && h_counts && h_positions) {
-        int unit_pos = -1;
-        for (int i = 0; i < n_final; i++) { if (h_counts[i] >= 2) pf = true; else { n_unit++; unit_pos = std::max(unit_pos, h_positions[i]); } }
-        if (pf) { attn_rows = n_final; attn_pos = unit_pos; }
-    }
-    const bool row_attn = !pf || n_unit > 0;      // some row takes the per-row attention kernels
-    // "multi_extend_mla_flash": the same for the MLA layers (docs/design/27-multi-extend-mla-flash.md): a non-verify pass with a run of >= 2 tokens gives those
-    // runs the run kernel, and the per-row MLA kernels see the unit rows only.  The option and "multi_extend_flash" never meet in a pass (that one refuses a store
-    // with an MLA layer), so on a store of MLA layers alone the score rows and the "multi_mla_fast" partials are sized by n_final rows and the unit rows' longest
-    // position; a store that also has GQA layers keeps their rows (n at max_pos), which hold the MLA unit rows too.  Off, or every run of one token: as ever
-    bool mf = false; int mf_unit = 0, mla_rows = n, mla_pos = max_pos;
-    if (s->opt_multi_extend_mla_flash && !verify && has_mla && h_counts && h_positions) {
-        int unit_pos = -1;
-        for (int i = 0; i < n_final; i++) { if (h_counts[i] >= 2) mf = true; else { mf_unit++; unit_pos = std::max(unit_pos, h_positions[i]); } }
-        if (mf) { mla_rows = n_final; mla_pos = unit_pos; }
-        if (mf && !has_gqa) { attn_rows = n_final; attn_pos = unit_pos; }
-    }
-    // "multi_extend_exact_mfma": a non-verify pass with a run of >= 2 tokens gives those runs the exact matrix-core passes (docs/design/28-multi-extend-exact-mfma.md).
-    // They keep their score rows -- the scratch stays n rows at the pass's longest position, as with the option off -- and need them under "multi_attn_fast" too.  The
-    // row stride is a multiple of 64 then (the P.V pass reads stages of 64 columns, the row maxima are per 32): no bit depends on it.  The option and
-    // "multi_extend_flash" never meet in a pass (kr_xm_refuse).  Off, a verify pass, or every run of one token: nothing of this
-    bool xm = false; int xm_unit = 0;
-    if (s->opt_multi_extend_exact_mfma && !verify && has_gqa && h_counts && h_positions)
-        for (int i = 0; i < n_final; i++) { if (h_counts[i] >= 2) xm = true; else xm_unit++; }
-    // "multi_extend_mla_exact_mfma": the same for the MLA layers (xl: the exact passes over latent rows, docs/design/29-multi-extend-mla-exact-mfma.md).  The score rows stay n rows at the pass's longest
-    // position and are needed under "multi_mla_fast" too; the option and "multi_extend_mla_flash" never meet in a pass (kr_mla_xm_refuse), and "multi_extend_flash"
-    // refuses a store with an MLA layer, so attn_rows = n and attn_pos = max_pos here
-    bool xl = false; int xl_unit = 0;
-    if (s->opt_multi_extend_mla_exact_mfma && !verify && has_mla && h_counts && h_positions)
-        for (int i = 0; i < n_final; i++) { if (h_counts[i] >= 2) xl = true; else xl_unit++; }
-    const bool mla_row_attn = !mf || mf_unit > 0;      // some row takes the per-row MLA kernels
-    int fd_chunk = 0, fd_chunks = 0, mla_chunk = 0, mla_chunks = 0;
-    size_t fd_o_bytes = 0, fd_ml_bytes = 0;
-    if (flash && row_attn) {
-        fd_chunk = kr_fd_flash_chunk(M.max_seq); fd_chunks = (attn_pos + fd_chunk) / fd_chunk;
-        if (fd_chunks > 1024) return kr_fail(KR_ERR_VALUE, "multi_attn_fast: position %d needs %d chunks of %d positions (at most 1024)", attn_pos, fd_chunks, fd_chunk);
-        if (!M.fd_ready) {
-            for (const DLayer& L : s->layers) {
-                if (L.attn != ATTN_GQA) continue;
-                if (!kr_multi_fd_ok(L.nh, L.nkv, L.hd)) return kr_fail(KR_ERR_VALUE, "multi_attn_fast: GQA geometry nh %d nkv %d head_dim %d not covered (head_dim 64 / 128 / 256, at most 32 heads per KV head)", L.nh, L.nkv, L.hd);
-                if (kr_multi_fd_prepare(L.hd, M.kv_fp8, M.pg.paged())) return kr_fail(KR_ERR_HIP, "multi_attn_fast: LDS window of the flash-decode kernel refused (head_dim %d)", L.hd);
-            }
-            M.fd_ready = true;
-        }
-        fd_o_bytes = (size_t)attn_rows * fd_chunks * gqa_row * 4; fd_ml_bytes = (size_t)attn_rows * nh_max * fd_chunks * 8;
-    }
-    if (mla_flash && mla_row_attn) {
-        mla_chunk = kr_mla_flash_decode_chunk(M.max_seq); mla_chunks = (mla_pos + mla_chunk) / mla_chunk;
-        if (mla_chunks > 1024) return kr_fail(KR_ERR_VALUE, "multi_mla_fast: position %d needs %d chunks of %d positions (at most 1024)", mla_pos, mla_chunks, mla_chunk);
-        if (!M.mla_fd_ready) {
-            for (const DLayer& L : s->layers)
-                if (L.attn == ATTN_MLA && kr_multi_mla_fd_prepare(L.klr, M.kv_fp8, M.pg.paged()))
-                    return kr_fail(KR_ERR_HIP, "multi_mla_fast: LDS window of the flash-decode kernel refused (kv_lora_rank %d)", L.klr);
-            M.mla_fd_ready = true;
-        }
-        fd_o_bytes = std::max(fd_o_bytes, (size_t)mla_rows * mla_chunks * mla_row * 4); fd_ml_bytes = std::max(fd_ml_bytes, (size_t)mla_rows * nh_max * mla_chunks * 8);
-    }
-    if (((flash && row_attn) || (mla_flash && mla_row_attn)) && (M.fd_o.ensure(fd_o_bytes) || M.fd_ml.ensure(fd_ml_bytes)))
-        return kr_fail(KR_ERR_HIP, "hipMalloc of the multi-sequence step's split-KV partials (%zu MiB) failed", (fd_o_bytes + fd_ml_bytes) >> 20);
-    const bool need_scores = (has_gqa && !flash && row_attn) || ((has_mla && !mla_flash) && mla_row_attn) || xm || xl;
-    int sc_ld = xm ? (attn_pos + 1 + 63) & ~63 : (attn_pos + 1 + 31) & ~31;
-    if (xl) sc_ld = (sc_ld + 63) & ~63;      // the MLA runs ask the same of the row stride
-    const int n_logits = verify ? n : n_final;      // a verify pass: the lm_head over every token row (what Chunk::verify is to the store's own pass)
-    if (M.scratch.ensure(Lo.total) || (need_scores && M.scores.ensure((size_t)attn_rows * nh_max * sc_ld * 4)) || M.logits.ensure((size_t)n_logits * s->vocab * 4))
-        return kr_fail(KR_ERR_HIP, "hipMalloc of the multi-sequence step's scratch (%zu MiB) failed", (Lo.total + ((size_t)attn_rows * nh_max * sc_ld + (size_t)n_logits * s->vocab) * 4) >> 20);
-    Chunk cx{};
-    cx.B = pf_carve(Lo, (char*)M.scratch.p); cx.scores = nullptr; cx.tok = d_rows + n; cx.Cc = n; cx.pos0 = 0; cx.set = KR_PF_MAX_DEPTH - 1;
-    cx.first = true; cx.add_is_emb = true; cx.st = st;
-    cx.m_slots = d_rows; cx.m_pos = d_rows + 2 * n; cx.m_sc_ld = sc_ld; cx.m_fd_chunk = fd_chunk; cx.m_fd_chunks = fd_chunks;
-    cx.m_mla_chunk = mla_chunk; cx.m_mla_chunks = mla_chunks;
-    cx.m_runs = d_runs; cx.m_nruns = n_final; cx.m_verify = verify;
-    // "multi_attn_exact_split": a pass-level choice by the longest per-row attention of the pass; both forms give the same bits.  (Under flash the per-row rows take
-    // the flash-decode pair and the flag is not read)
-    cx.m_xs_split = s->opt_multi_attn_exact_split && has_gqa && attn_pos + 1 >= s->opt_multi_attn_exact_split_min;
-    // "multi_mla_exact_split": the same for the MLA layers, by the longest attention of the pass's per-row MLA kernels (mla_pos = -1: no unit row, nothing launched)
-    cx.m_mla_xs_split = s->opt_multi_mla_exact_split && has_mla && mla_pos + 1 >= s->opt_multi_mla_exact_split_min;
-    if (pf) {      // the query tiles of the runs, one table per tile width among the GQA layers (128 / G tokens), behind one another in M.pf_tiles
-        std::vector<int32_t> all, one;
-        bool have[8] = {false, false, false, false, false, false, false, false};
+    // the LDS windows of the flash-decode kernels, on the first pass that needs them
+    if (plan.fd_chunks && !M.fd_ready) {
         for (const DLayer& L : s->layers) {
             if (L.attn != ATTN_GQA) continue;
-            const int tq = kr_pf_tile_tokens(L.nh, L.nkv), w = pf_log2(tq);      // kr_exact_refuse: G divides 128
-            if (have[w]) continue;
-            have[w] = true;
-            cx.m_pf_off[w] = (int)(all.size() / 2); cx.m_pf_n[w] = kr_pf_build_tiles(n_final, h_counts, tq, one).n_tiles;
-            all.insert(all.end(), one.begin(), one.end());
+            if (!kr_multi_fd_ok(L.nh, L.nkv, L.hd)) return kr_fail(KR_ERR_VALUE, "multi_attn_fast: GQA geometry nh %d nkv %d head_dim %d not covered (head_dim 64 / 128 / 256, at most 32 heads per KV head)", L.nh, L.nkv, L.hd);
+            if (kr_multi_fd_prepare(L.hd, M.kv_fp8, M.pg.paged())) return kr_fail(KR_ERR_HIP, "multi_attn_fast: LDS window of the flash-decode kernel refused (head_dim %d)", L.hd);
         }
-        if (M.pf_tiles.ensure(std::max(all.size() * 4, (size_t)65536))) return kr_fail(KR_ERR_HIP, "hipMalloc of the multi-sequence pass's query tiles failed");
-        KR_HIP(hipMemcpyAsync(M.pf_tiles.p, all.data(), all.size() * 4, hipMemcpyHostToDevice, st));      // pageable source: staged before the call returns
-        cx.m_pf_tiles = (const int32_t*)M.pf_tiles.p; cx.m_pf_units = n_unit;
+        M.fd_ready = true;
     }
-    if (xm || xl) {      // the query tiles of the runs for the scores pass (64 / G tokens) and the P.V pass (32 / G), one table per width among the GQA layers (xm) and the MLA layers (xl: G = nh), behind one another in M.xm_tiles
-        std::vector<int32_t> all, one;
-        bool have_a[8] = {false, false, false, false, false, false, false, false}, have_c[8] = {false, false, false, false, false, false, false, false};
-        for (const DLayer& L : s->layers) {
-            if (!(xm && L.attn == ATTN_GQA) && !(xl && L.attn == ATTN_MLA)) continue;
-            const int nkv = L.attn == ATTN_MLA ? 1 : L.nkv;      // MLA: one latent row serves every head
-            const int ta = kr_xm_tile_tokens_a(L.nh, nkv), tc = kr_xm_tile_tokens_c(L.nh, nkv), wa = pf_log2(ta), wc = pf_log2(tc);      // kr_xm_refuse / kr_mla_xm_refuse: G divides 32
-            if (!have_a[wa]) {
-                have_a[wa] = true;
-                cx.m_xa_off[wa] = (int)(all.size() / 2); cx.m_xa_n[wa] = kr_pf_build_tiles(n_final, h_counts, ta, one).n_tiles;
-                all.insert(all.end(), one.begin(), one.end());
-            }
-            if (!have_c[wc]) {
-                have_c[wc] = true;
-                cx.m_xc_off[wc] = (int)(all.size() / 2); cx.m_xc_n[wc] = kr_pf_build_tiles(n_final, h_counts, tc, one).n_tiles;
-                all.insert(all.end(), one.begin(), one.end());
-            }
-        }
-        const size_t sc_rows = (size_t)n * nh_max, inv_bytes = al(sc_rows * 4);
-        if (M.xm_tiles.ensure(std::max(all.size() * 4, (size_t)65536)) || M.xm_rows.ensure(inv_bytes + sc_rows * (size_t)(sc_ld / 32) * 4))
-            return kr_fail(KR_ERR_HIP, "hipMalloc of the multi-sequence pass's exact matrix-core attention tables failed");
-        KR_HIP(hipMemcpyAsync(M.xm_tiles.p, all.data(), all.size() * 4, hipMemcpyHostToDevice, st));      // pageable source: staged before the call returns
-        if (xm) cx.m_xm_tiles = (const int32_t*)M.xm_tiles.p;
-        if (xl) cx.m_xl_tiles = (const int32_t*)M.xm_tiles.p;
-        cx.m_xm_units = xm ? xm_unit : xl_unit; cx.m_xm_kv_end = kr_xm_kv_end_max(n_final, h_counts, h_positions);
-        cx.m_xm_inv = (float*)M.xm_rows.p; cx.m_xm_tmax = (float*)((char*)M.xm_rows.p + inv_bytes);
+    if (plan.mla_chunks && !M.mla_fd_ready) {
+        for (const DLayer& L : s->layers)
+            if (L.attn == ATTN_MLA && kr_multi_mla_fd_prepare(L.klr, M.kv_fp8, M.pg.paged()))
+                return kr_fail(KR_ERR_HIP, "multi_mla_fast: LDS window of the flash-decode kernel refused (kv_lora_rank %d)", L.klr);
+        M.mla_fd_ready = true;
     }
-    if (mf) {      // the query-row tiles of the runs, one table per head count among the MLA layers (64 (token, head) rows each), behind one another in M.mf_tiles
-        std::vector<int32_t> all, one;
-        for (const DLayer& L : s->layers) {
-            if (L.attn != ATTN_MLA) continue;
-            bool have = false;
-            for (const Chunk::MfTab& t : cx.m_mf) have |= t.nh == L.nh;
-            if (have) continue;
-            cx.m_mf.push_back(Chunk::MfTab{L.nh, (int)(all.size() / 2), kr_mf_build_tiles(n_final, h_counts, L.nh, one).n_tiles});
-            all.insert(all.end(), one.begin(), one.end());
-        }
-        if (M.mf_tiles.ensure(std::max(all.size() * 4, (size_t)65536))) return kr_fail(KR_ERR_HIP, "hipMalloc of the multi-sequence pass's MLA query tiles failed");
-        KR_HIP(hipMemcpyAsync(M.mf_tiles.p, all.data(), all.size() * 4, hipMemcpyHostToDevice, st));      // pageable source: staged before the call returns
-        cx.m_mf_tiles = (const int32_t*)M.mf_tiles.p; cx.m_mf_units = mf_unit;
+    if ((plan.fd_chunks || plan.mla_chunks) && (M.fd_o.ensure(plan.fd_o_bytes) || M.fd_ml.ensure(plan.fd_ml_bytes)))
+        return kr_fail(KR_ERR_HIP, "hipMalloc of the multi-sequence step's split-KV partials (%zu MiB) failed", (plan.fd_o_bytes + plan.fd_ml_bytes) >> 20);
+    if (M.scratch.ensure(Lo.total) || (plan.need_scores && M.scores.ensure(plan.score_bytes)) || M.logits.ensure((size_t)plan.n_logits * s->vocab * 4))
+        return kr_fail(KR_ERR_HIP, "hipMalloc of the multi-sequence step's scratch (%zu MiB) failed", (Lo.total + plan.score_bytes + (size_t)plan.n_logits * s->vocab * 4) >> 20);
+    if (plan.xm_inv_bytes && M.xm_rows.ensure(plan.xm_inv_bytes + plan.xm_tmax_bytes))
+        return kr_fail(KR_ERR_HIP, "hipMalloc of the multi-sequence pass's exact matrix-core attention tables failed");
+    if (plan.lc_nruns && M.lc_scratch.ensure(plan.lc_scratch_floats * 4))
+        return kr_fail(KR_ERR_HIP, "hipMalloc of the multi-sequence pass's chunked delta-rule scratch (%zu MiB) failed", plan.lc_scratch_floats * 4 >> 20);
+    if (!plan.tables.empty()) {      // every table of the pass in one upload
+        if (M.tiles.ensure(std::max(plan.tables.size() * 4, (size_t)65536))) return kr_fail(KR_ERR_HIP, "hipMalloc of the multi-sequence pass's query tiles failed");
+        KR_HIP(hipMemcpyAsync(M.tiles.p, plan.tables.data(), plan.tables.size() * 4, hipMemcpyHostToDevice, st));      // pageable source: staged before the call returns
     }
-    // "multi_extend_la_chunk": a non-verify pass with a run of >= 64 tokens gives those runs the chunked delta rule (docs/design/26-multi-extend-la-chunk.md).
-    // One table for every linear-attention layer -- the chunked runs, then their sub-chunks -- and one scratch, sized by the widest layer.  Off, a verify pass or
-    // every run shorter: the pointers stay null and every layer launches what it always did
-    if (s->opt_multi_extend_la_chunk && !verify && h_counts) {
-        std::vector<int32_t> lr, lt;
-        const KrLcStats ls = kr_lc_build(n_final, h_counts, lr, lt);
-        int nv_max = 0;
-        for (const DLayer& L : s->layers) if (L.attn == ATTN_LA) nv_max = std::max(nv_max, L.nv);
-        if (ls.n_runs && nv_max) {
-            lr.insert(lr.end(), lt.begin(), lt.end());
-            if (M.lc_tiles.ensure(std::max(lr.size() * 4, (size_t)65536)) || M.lc_scratch.ensure(kr_lc_scratch_floats(ls.n_tiles, nv_max) * 4))
-                return kr_fail(KR_ERR_HIP, "hipMalloc of the multi-sequence pass's chunked delta-rule scratch (%zu MiB) failed", kr_lc_scratch_floats(ls.n_tiles, nv_max) * 4 >> 20);
-            KR_HIP(hipMemcpyAsync(M.lc_tiles.p, lr.data(), lr.size() * 4, hipMemcpyHostToDevice, st));      // pageable source: staged before the call returns
-            cx.m_lc_runs = (const int32_t*)M.lc_tiles.p; cx.m_lc_tiles = cx.m_lc_runs + 2 * (size_t)ls.n_runs;
-            cx.m_lc_nruns = ls.n_runs; cx.m_lc_ntiles = ls.n_tiles; cx.m_lc_short = ls.n_short; cx.m_lc_scratch = (float*)M.lc_scratch.p;
-        }
-    }
+    const MultiPass mp{plan, (const int32_t*)M.tiles.p, (float*)M.lc_scratch.p, (float*)M.xm_rows.p, (float*)((char*)M.xm_rows.p + plan.xm_inv_bytes),
+                       d_rows, d_rows + 2 * n, d_runs, n_final, verify};
+    Chunk cx{};
+    cx.B = pf_carve(Lo, (char*)M.scratch.p); cx.scores = nullptr; cx.tok = d_rows + n; cx.Cc = n; cx.pos0 = 0; cx.set = KR_PF_MAX_DEPTH - 1;
+    cx.first = true; cx.add_is_emb = true; cx.st = st; cx.mp = &mp;
     for (size_t l = 0; l < s->layers.size(); l++)
         if (int rc = run_layer(s, cx, l)) return rc;
-    cx.Cc = n_logits;
+    cx.Cc = plan.n_logits;
     return final_rows(s, cx, (float*)M.logits.p);
 }

@@ -5,6 +5,8 @@ import os
 import re
 import subprocess
 
+from tests.test_multi_pass_plan import case_passed
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "krasis_amd", "csrc")
 OPT, MIN = "multi_attn_exact_split", "multi_attn_exact_split_min"
@@ -46,7 +48,10 @@ def test_the_refusal_stands_behind_its_siblings():
     mine = pre[pre.index("int kr_xs_refuse(kr_decode_store* s) {"):]
     mine = mine[:mine.index("\n}\n")]
     assert "KR_ERR_STATE" in mine and "covers GQA layers only: this store has none" in mine and "graph_ok" not in mine
-    assert "attn_pos + 1 >= s->opt_multi_attn_exact_split_min" in pre      # the pass-level choice, by the longest attention of the per-row kernels
+    assert "|| paged_refused(s)) return KR_OK;" in mine
+    # the pass-level choice, by the longest attention of the per-row kernels: the plan's (docs/design/32-multi-pass-plan.md)
+    assert "o.attn_exact_split_min = s->opt_multi_attn_exact_split_min;" in pre and "p.attn_pos + 1 >= o.attn_exact_split_min" in _src("kr_multi_plan.h")
+    assert case_passed("H") and case_passed("B") and "m.xs_split = pl.xs_split;" in pre
 
 
 def test_every_launcher_of_the_one_kernel_takes_the_split_and_the_softmax_is_one_copy():

@@ -5,6 +5,8 @@ import os
 import re
 import subprocess
 
+from tests.test_multi_pass_plan import case_passed
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "krasis_amd", "csrc")
 OPT = "multi_attn_fast_paged"
@@ -50,10 +52,12 @@ def test_the_option_is_known_everywhere():
     assert '!strcmp(name, "%s")' % OPT in _src("kr_decode.cpp")
     assert "opt_%s" % OPT in _src("kr_decode_internal.h")
     pre = _src("kr_decode_prefill.cpp")
-    assert "(s->opt_multi_attn_fast || s->opt_multi_attn_fast_paged) && has_gqa && M.max_seq > s->gqa_split_min" in pre
+    assert "o.attn_fast = s->opt_multi_attn_fast || s->opt_multi_attn_fast_paged;" in pre      # either option: one flag of the plan (docs/design/32-multi-pass-plan.md)
+    assert "o.attn_fast && has_gqa && o.max_seq > o.gqa_split_min" in _src("kr_multi_plan.h") and case_passed("A") and case_passed("I")
     assert "slots && (s->opt_multi_attn_fast || s->opt_multi_attn_fast_paged)" in pre      # the MLA refusal covers either option
     refuse = re.search(r"int paged_refuse\(kr_decode_store\* s\) \{(.*?)\n\}", _src("kr_decode_multi.cpp"), re.S).group(1)
-    assert "s->opt_multi_attn_fast && !s->opt_multi_attn_fast_paged" in refuse and "paged slots" in refuse
+    assert "if (paged_refused(s))" in refuse and "paged slots" in refuse
+    assert "bool paged_refused(const kr_decode_store* s) { return s->multi && s->multi->pg.paged() && s->opt_multi_attn_fast && !s->opt_multi_attn_fast_paged; }" in pre
     header = open(os.path.join(ROOT, "include", "krasis_hip.h")).read()
     assert header.count('"%s"' % OPT) >= 3
     from krasis_amd.decode_store import CpuDecodeStore

@@ -6,6 +6,8 @@ import re
 import shutil
 import subprocess
 
+from tests.test_multi_pass_plan import case_passed
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "krasis_amd", "csrc")
 OPT = "multi_extend_exact_mfma"
@@ -49,7 +51,7 @@ def test_the_refusal_is_a_function_of_its_own_behind_every_earlier_clause():
     assert re.search(r'KR_ERR_STATE[^;]*multi_extend_exact_mfma[^;]*multi_extend_flash', mine)      # both run options: the message names both
     assert re.search(r"KR_ERR_STATE[^;]*has none", mine) and re.search(r"KR_ERR_VALUE[^;]*not covered", mine)
     assert mine.count(OPT) >= 4 and "kr_pfm_gqa_exact_mfma_ok(g)" in mine     # every message names the option; the prompt pass's own geometry rule
-    assert "s->multi->pg.paged() && s->opt_multi_attn_fast && !s->opt_multi_attn_fast_paged" in mine      # stands back where the entry point's paged refusal applies
+    assert "|| paged_refused(s)) return KR_OK;" in mine and _src("kr_decode_prefill.cpp").count("pg.paged() && s->opt_multi_attn_fast && !s->opt_multi_attn_fast_paged") == 1      # stands back where the entry point's paged refusal applies
     multi = _src("kr_decode_multi.cpp")
     body = multi[multi.index("int multi_refuse("):]
     body = body[:body.index("\n}\n")]
@@ -94,9 +96,10 @@ def test_the_launcher_and_the_pass():
     assert "dim3(a.nh + a.nkv, B)" in mine and "dim3(a.nkv, n_runs)" in mine and "kr_launch_multi_fd(a, n_runs, a.fd_chunks, st)" in mine
     assert mine.rstrip().endswith("return kr_launch_multi_xm(a, x, B, st);")
     pre = _src("kr_decode_prefill.cpp")
-    assert "s->opt_multi_extend_exact_mfma && !verify && has_gqa && h_counts && h_positions" in pre      # never in a verify pass
-    assert "M.scores.ensure((size_t)attn_rows * nh_max * sc_ld * 4)" in pre and "if (pf) { attn_rows = n_final; attn_pos = unit_pos; }" in pre and "(has_mla && !mla_flash)" in pre
-    assert "xm ? (attn_pos + 1 + 63) & ~63 : (attn_pos + 1 + 31) & ~31" in pre
+    plan = _src("kr_multi_plan.h")      # the pass's decisions are the plan's (docs/design/32-multi-pass-plan.md): its check program's cases stand for the lines once pinned here
+    assert "o.extend_exact_mfma = s->opt_multi_extend_exact_mfma;" in pre and case_passed("F")      # never in a verify pass
+    assert "plan.need_scores && M.scores.ensure(plan.score_bytes)" in pre and case_passed("A") and "(has_mla && !mla_flash && p.mla_row_attn)" in plan and case_passed("D")
+    assert case_passed("E") and case_passed("K")                              # the row stride: a multiple of 64 under the option, of 32 otherwise
     tiles = re.sub(r"//.*", "", _src("kr_xm_tiles.h"))
     assert "hip" not in tiles.lower() and "__device__" not in tiles
 

@@ -6,6 +6,8 @@ import re
 import shutil
 import subprocess
 
+from tests.test_multi_pass_plan import case_passed
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "krasis_amd", "csrc")
 OPT = "multi_extend_flash"
@@ -44,7 +46,7 @@ def test_refusals_sit_behind_every_earlier_clause_and_name_the_option():
     assert "kr_pfm_gqa_flash_ok(L.nh, L.nkv, L.hd)" in tail                   # the prompt pass's own geometry rule
     assert "kr_multi_pf_prepare(L.hd, s->multi->kv_fp8, s->multi->pg.paged())" in tail and "pf_ready" in tail      # windows once per slot set, outside the pass
     # paged slots under "multi_attn_fast" alone are still refused by the entry points
-    assert "s->multi->pg.paged() && s->opt_multi_attn_fast && !s->opt_multi_attn_fast_paged" in _src("kr_decode_multi.cpp")
+    assert "if (paged_refused(s))" in _src("kr_decode_multi.cpp") and _src("kr_decode_prefill.cpp").count("pg.paged() && s->opt_multi_attn_fast && !s->opt_multi_attn_fast_paged") == 1      # the entry points' refusal and its siblings' standing back: one predicate
 
 
 def test_one_body_two_callers():
@@ -110,17 +112,18 @@ def test_the_batched_launcher_keeps_its_lines_and_gains_the_run_path():
     assert body.rstrip().endswith("const int* pf_runs; const int* pf_tiles; int pf_nruns, pf_ntiles, pf_units;")      # new fields at the end
     assert "return a.pf_runs && a.pf_runs[3 * b + 2] >= 2;" in hdr          # null pointer: no row is skipped
     pre = _src("kr_decode_prefill.cpp")
-    assert "(s->opt_multi_attn_fast || s->opt_multi_attn_fast_paged) && has_gqa && M.max_seq > s->gqa_split_min" in pre
-    assert "s->opt_multi_extend_flash && !verify && has_gqa && h_counts && h_positions" in pre      # never in a verify pass
-    assert "if (pf) { attn_rows = n_final; attn_pos = unit_pos; }" in pre    # scratch of the per-row kernels sized by the unit rows
-    assert "M.scores.ensure((size_t)attn_rows * nh_max * sc_ld * 4)" in pre
+    plan = _src("kr_multi_plan.h")      # the pass's decisions are the plan's (docs/design/32-multi-pass-plan.md): its check program's cases stand for the lines once pinned here
+    assert "o.attn_fast = s->opt_multi_attn_fast || s->opt_multi_attn_fast_paged;" in pre and "o.attn_fast && has_gqa && o.max_seq > o.gqa_split_min" in plan
+    assert "o.extend_flash = s->opt_multi_extend_flash;" in pre and case_passed("F")      # never in a verify pass
+    assert case_passed("A") and case_passed("B")                             # scratch of the per-row kernels sized by the unit rows
+    assert "plan.need_scores && M.scores.ensure(plan.score_bytes)" in pre and "p.score_bytes = (size_t)p.attn_rows * nh_max * p.sc_ld * 4;" in plan and case_passed("K")
 
 
 def test_the_tile_builder_is_host_only():
     src = _src("kr_pf_tiles.h")
     code = re.sub(r"//.*", "", src)
     assert "hip" not in code.lower() and "__device__" not in code
-    assert '#include "kr_pf_tiles.h"' in _src("kr_decode_prefill.cpp")
+    assert '#include "kr_pf_tiles.h"' in _src("kr_multi_plan.h") and '#include "kr_multi_plan.h"' in _src("kr_decode_prefill.cpp")
 
 
 def test_library_exports_exactly_the_declared_symbols():

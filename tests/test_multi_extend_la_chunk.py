@@ -7,6 +7,8 @@ import re
 import shutil
 import subprocess
 
+from tests.test_multi_pass_plan import case_passed
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "krasis_amd", "csrc")
 OPT = "multi_extend_la_chunk"
@@ -92,9 +94,10 @@ def test_refusal_clause_is_last_and_names_the_option():
     assert "kr_multi_lc_ok(L.dk, L.dv, L.nk, L.nv," in tail
     assert "return dk == LC_D && dv == LC_D" in _src("kr_multi_la_chunk.hip")
     # the pass: never in a verify pass, the table with the other tables of the pass, the scratch ahead of the layer loop
-    assert "s->opt_%s && !verify && h_counts" % OPT in pre
+    assert "o.extend_la_chunk = s->opt_%s;" % OPT in pre and "o.extend_la_chunk && !r.verify && r.counts" in _src("kr_multi_plan.h")
+    assert case_passed("F") and case_passed("G") and case_passed("K")      # a plain step and a verify pass have no table (docs/design/32-multi-pass-plan.md)
     p = pre[pre.index("int kr_multi_pass("):]
-    assert p.index("kr_lc_build(n_final, h_counts") < p.index("M.lc_scratch.ensure(") < p.index("run_layer(s, cx, l)")
+    assert p.index("kr_multi_plan(o, ") < p.index("M.lc_scratch.ensure(") < p.index("run_layer(s, cx, l)")
 
 
 def test_new_fields_stand_at_the_end_and_the_run_kernels_leave_chunked_runs():
@@ -119,7 +122,7 @@ def test_new_fields_stand_at_the_end_and_the_run_kernels_leave_chunked_runs():
 def test_the_table_builder_is_host_only():
     code = _code(_src("kr_lc_tiles.h"))
     assert "hip" not in code.lower() and "__device__" not in code
-    assert '#include "kr_lc_tiles.h"' in _src("kr_decode_prefill.cpp")
+    assert '#include "kr_lc_tiles.h"' in _src("kr_multi_plan.h") and '#include "kr_multi_plan.h"' in _src("kr_decode_prefill.cpp")
 
 
 def test_library_exports_no_new_symbol():

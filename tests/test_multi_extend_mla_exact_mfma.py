@@ -6,6 +6,8 @@ import os
 import re
 import subprocess
 
+from tests.test_multi_pass_plan import case_passed
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "krasis_amd", "csrc")
 OPT = "multi_extend_mla_exact_mfma"
@@ -58,7 +60,7 @@ def test_the_refusal_is_a_function_of_its_own_behind_every_earlier_clause():
     assert re.search(r'KR_ERR_STATE[^;]*multi_extend_mla_exact_mfma[^;]*multi_extend_mla_flash', mine)      # both run options: the message names both
     assert re.search(r"KR_ERR_STATE[^;]*has none", mine) and re.search(r"KR_ERR_VALUE[^;]*divide 32", mine)
     assert mine.count(OPT) >= 4 and "kr_mla_exact_mfma_ok(L.nh, L.klr, L.rd)" in mine      # every message names the option; the prompt pass's own geometry rule
-    assert "s->multi->pg.paged() && s->opt_multi_attn_fast && !s->opt_multi_attn_fast_paged" in mine      # stands back where the entry point's paged refusal applies
+    assert "|| paged_refused(s)) return KR_OK;" in mine and _src("kr_decode_prefill.cpp").count("pg.paged() && s->opt_multi_attn_fast && !s->opt_multi_attn_fast_paged") == 1      # stands back where the entry point's paged refusal applies
     body = _body(_src("kr_decode_multi.cpp"), "int multi_refuse(")
     assert body.index("kr_spec_pending_fail(s)") < body.index("kr_exact_refuse(s, true)") < body.index("kr_xm_refuse(s)") < body.index("kr_mla_xm_refuse(s)")
 
@@ -94,8 +96,9 @@ def test_the_launcher_and_the_pass():
     assert "(a.nh + KR_MM_HG - 1) / KR_MM_HG, n_runs)" in mine                # the per-row kernel over the first n_runs rows
     assert mine.rstrip().endswith("kr_launch_mla_wvc(m, st, B);\n    return 0;")      # ends with the w_vc projection over all rows
     pre = _src("kr_decode_prefill.cpp")
-    assert "s->opt_multi_extend_mla_exact_mfma && !verify && has_mla && h_counts && h_positions" in pre      # never in a verify pass
-    assert "kr_launch_multi_mla_xm(m, x, cx.m_runs, cx.m_nruns, cx.m_xm_units, Cc, st)" in pre
+    assert "o.extend_mla_exact_mfma = s->opt_multi_extend_mla_exact_mfma;" in pre and case_passed("F") and case_passed("K")      # never in a verify pass (docs/design/32-multi-pass-plan.md)
+    assert case_passed("J")                                                   # the tables at 64 / nh and 32 / nh, shared with a GQA layer of the same group size
+    assert "kr_launch_multi_mla_xm(m, multi_xm_args(P, L.nh, 1), P.runs, P.nruns, P.plan.n_unit, Cc, st)" in pre
 
 
 def test_library_exports_exactly_the_declared_symbols_and_holds_the_new_kernels():

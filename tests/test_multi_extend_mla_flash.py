@@ -8,6 +8,8 @@ import re
 import shutil
 import subprocess
 
+from tests.test_multi_pass_plan import case_passed
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "krasis_amd", "csrc")
 OPT = "multi_extend_mla_flash"
@@ -86,8 +88,9 @@ def test_refusal_clause_stands_between_its_neighbours_and_names_the_option():
     refuse = pre[pre.index("int kr_exact_refuse("):pre.index("int kr_spec_refuse(")]
     mine = refuse.index("slots && s->opt_%s && !paged_refused" % OPT)        # stands back where the entry point's paged refusal applies
     for earlier in ("is exact-mode only: the attention mode has tolerance bits set", "slots && (s->opt_multi_attn_fast || s->opt_multi_attn_fast_paged)",
-                    "does not run under expert parallelism", "slots && s->opt_multi_mla_fast", "multi_mla_fast: MLA geometry heads", "const bool paged_refused = "):
+                    "does not run under expert parallelism", "slots && s->opt_multi_mla_fast", "multi_mla_fast: MLA geometry heads"):
         assert refuse.index(earlier) < mine, earlier
+    assert pre.index("bool paged_refused(const kr_decode_store* s) {") < pre.index("int kr_exact_refuse(")      # the predicate, stated once ahead of its users
     nxt = refuse.index("slots && s->opt_multi_extend_flash && !paged_refused")
     assert mine < nxt < refuse.index("slots && s->opt_multi_extend_la_chunk && !paged_refused")
     clause = refuse[mine:nxt]
@@ -97,7 +100,7 @@ def test_refusal_clause_stands_between_its_neighbours_and_names_the_option():
     assert re.search(r"KR_ERR_STATE[^;]*has none", clause) and re.search(r"KR_ERR_HIP[^;]*LDS window", clause)
     assert "kr_multi_mla_pf_prepare(L.klr, s->multi->kv_fp8, s->multi->pg.paged())" in clause and "mf_ready" in clause      # windows once per slot set, outside the pass
     assert "mf_ready" not in pre[pre.index("int kr_multi_pass("):]           # never inside the pass
-    assert "s->multi->pg.paged() && s->opt_multi_attn_fast && !s->opt_multi_attn_fast_paged" in _src("kr_decode_multi.cpp")
+    assert "if (paged_refused(s))" in _src("kr_decode_multi.cpp") and _src("kr_decode_prefill.cpp").count("pg.paged() && s->opt_multi_attn_fast && !s->opt_multi_attn_fast_paged") == 1      # the entry points' refusal and its siblings' standing back: one predicate
 
 
 def test_new_fields_at_the_end_and_per_row_kernels_leave_longer_runs():
@@ -124,15 +127,15 @@ def test_new_fields_at_the_end_and_per_row_kernels_leave_longer_runs():
     assert "a.mf_nruns);" in runs and "kr_launch_multi_mla_fd(a, a.mf_nruns, st)" in runs and "kr_launch_multi_mla_pf_flash(a, st)" in runs
     assert runs.index("kr_launch_multi_mla_pf_flash(a, st)") < runs.index("kr_launch_mla_wvc_mfma(")
     pre = _src("kr_decode_prefill.cpp")
-    assert "s->opt_multi_extend_mla_flash && !verify && has_mla && h_counts && h_positions" in pre      # never in a verify pass
-    assert "if (mf) { mla_rows = n_final; mla_pos = unit_pos; }" in pre
+    assert "o.extend_mla_flash = s->opt_multi_extend_mla_flash;" in pre and case_passed("F") and case_passed("K")      # never in a verify pass (docs/design/32-multi-pass-plan.md)
+    assert case_passed("C") and case_passed("D")                             # the per-row MLA kernels see the unit rows only; a mixed store keeps the score rows
 
 
 def test_the_tile_builder_is_host_only():
     src = _src("kr_mf_tiles.h")
     code = _code(src)
     assert "hip" not in code.lower() and "__device__" not in code
-    assert '#include "kr_mf_tiles.h"' in _src("kr_decode_prefill.cpp")
+    assert '#include "kr_mf_tiles.h"' in _src("kr_multi_plan.h") and '#include "kr_multi_plan.h"' in _src("kr_decode_prefill.cpp")
 
 
 def test_library_exports_exactly_the_declared_symbols():

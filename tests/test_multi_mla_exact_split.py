@@ -5,6 +5,8 @@ import os
 import re
 import subprocess
 
+from tests.test_multi_pass_plan import case_passed
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "krasis_amd", "csrc")
 OPT, MIN = "multi_mla_exact_split", "multi_mla_exact_split_min"
@@ -55,9 +57,10 @@ def test_the_refusal_is_asked_last():
     pre = _src("kr_decode_prefill.cpp")
     mine = _body(pre, "int kr_mla_xs_refuse(kr_decode_store* s) {")
     assert "KR_ERR_STATE" in mine and "covers MLA layers only: this store has none" in mine and "graph_ok" not in mine
-    assert "s->multi->pg.paged() && s->opt_multi_attn_fast && !s->opt_multi_attn_fast_paged" in mine      # stands back where the entry point's paged refusal applies
-    assert "s->opt_multi_mla_exact_split && has_mla && mla_pos + 1 >= s->opt_multi_mla_exact_split_min" in pre      # the pass-level choice
-    assert "m.xs_split = cx.m_mla_xs_split;" in pre
+    assert "|| paged_refused(s)) return KR_OK;" in mine and pre.count("pg.paged() && s->opt_multi_attn_fast && !s->opt_multi_attn_fast_paged") == 1      # stands back where the entry point's paged refusal applies
+    # the pass-level choice: the plan's (docs/design/32-multi-pass-plan.md)
+    assert "o.mla_exact_split_min = s->opt_multi_mla_exact_split_min;" in pre and "o.mla_exact_split && has_mla && p.mla_pos + 1 >= o.mla_exact_split_min" in _src("kr_multi_plan.h")
+    assert case_passed("H") and "m.xs_split = pl.mla_xs_split;" in pre
     assert "int kr_mla_xs_refuse(kr_decode_store* s);" in _src("kr_decode_internal.h")
 
 

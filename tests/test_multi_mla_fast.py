@@ -6,6 +6,8 @@ import os
 import re
 import subprocess
 
+from tests.test_multi_pass_plan import case_passed
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "krasis_amd", "csrc")
 OPT = "multi_mla_fast"
@@ -56,7 +58,8 @@ def test_launcher_dispatches_and_prepares_the_paged_instantiations():
     pre = _src("kr_decode_prefill.cpp")
     assert "kr_multi_mla_fd_prepare(L.klr, M.kv_fp8, M.pg.paged())" in pre and "M.mla_fd_ready" in pre
     assert "kr_mla_flash_decode_chunk(M.max_seq)" in pre
-    assert "(has_mla && !mla_flash)" in pre                                 # no score rows when no layer reads them
+    assert "(has_mla && !mla_flash && p.mla_row_attn)" in _src("kr_multi_plan.h") and case_passed("D")      # no score rows when no layer reads them: the plan's (docs/design/32-multi-pass-plan.md)
+    assert "o.mla_chunk = kr_mla_flash_decode_chunk(M.max_seq);" in pre and case_passed("I")
     assert "kr_multi_mla_flash.hip" in _src("Makefile") and "kr_mla_flash_dev.h" in _src("Makefile")
 
 
@@ -64,9 +67,11 @@ def test_the_option_is_known_everywhere():
     assert '!strcmp(name, "%s")' % OPT in _src("kr_decode.cpp")
     assert "opt_%s" % OPT in _src("kr_decode_internal.h")
     pre = _src("kr_decode_prefill.cpp")
-    assert "s->opt_multi_mla_fast && has_mla && M.max_seq > s->mla_split_min" in pre
+    plan = _src("kr_multi_plan.h")
+    assert "o.mla_fast = s->opt_multi_mla_fast;" in pre and "o.mla_fast && has_mla && o.max_seq > o.mla_split_min" in plan
     # the two GQA options keep their clauses, ahead of the new option's
-    assert "(s->opt_multi_attn_fast || s->opt_multi_attn_fast_paged) && has_gqa && M.max_seq > s->gqa_split_min" in pre
+    assert "o.attn_fast = s->opt_multi_attn_fast || s->opt_multi_attn_fast_paged;" in pre
+    assert plan.index("o.attn_fast && has_gqa && o.max_seq > o.gqa_split_min") < plan.index("o.mla_fast && has_mla && o.max_seq > o.mla_split_min")
     refuse = pre[pre.index("int kr_exact_refuse("):pre.index("int kr_spec_refuse(")]
     assert refuse.index("slots && (s->opt_multi_attn_fast || s->opt_multi_attn_fast_paged)") < refuse.index("slots && s->opt_multi_mla_fast")
     assert refuse.index("does not run under expert parallelism") < refuse.index("slots && s->opt_multi_mla_fast")
