@@ -330,7 +330,11 @@ int kr_decode_set_attention_mode(kr_decode_store* s, int mode);
  * kernels (kr_gguf_group.hip) instead of the int8-MFMA form: every row then carries the bits of kr_decode_step on that sequence alone, and the slot and
  * speculation entry points, which otherwise refuse a store with such layers, accept it.  Slower than the default form on long prompts.  A prompt pass
  * with the option and KR_GEMM_FAST both set is refused (KR_ERR_STATE).  Stores without native GGUF layers are unaffected.
- * "gguf_exact_grouped" (default 1): 0 = that pass through the streaming block kernels for every block type (A/B and test hook; same bits). */
+ * "gguf_exact_grouped" (default 1): 0 = that pass through the streaming block kernels for every block type (A/B and test hook; same bits).
+ * "slot_select" (default 1; docs/design/33-slot-select.md): KR_DECODE_FAST, MoE layers under the lean routing rule (softmax scoring, no score
+ * correction, renormalised weights; E <= 512): with 1 every routed workgroup of the gate|up launch selects the expert id of its own rank only and one
+ * extra grid row publishes ids and weights for the down launch; with 0 every workgroup runs the full top-k select and workgroup (0, 0) publishes.  Same
+ * bits either way (tests/test_decode_fast_slot_select_gpu.py); every other routing rule keeps the 0 form whatever the value.  A/B and test hook. */
 int kr_decode_set_option(kr_decode_store* s, const char* name, int value);                                                                        /* decode.rs:2471 */
 /* Whole-model prompt pass.  Replaces the reference's GPU prefill (python/krasis/model.py forward_prefill_layer_grouped / server_prefill,
  * layer.py:242-461, attention.py:496-687, linear_attention.py:695-845 -- third-party kernels) AND the GPU->CPU state hand-off

@@ -11,6 +11,7 @@
 //   kr_launch_frt     post-attention add+RMSNorm + router gate GEMV (decode.rs:1385), expert images for the expert launches
 //   kr_launch_fw13    scoring + top-k (decode.rs:4088, wave-parallel; ids identical to the exact kernel for identical logits unless two leaders
 //                     tie, then the reference's heap order is emulated) in the prologue of the gate|up matvec; silu(g) * u in its epilogue
+//                     (lean routing rule: a routed workgroup selects the id of its own rank only, an extra grid row publishes ids / weights: KrFmoeArgs::slot_select)
 //   kr_launch_fw2     INT16 quantisation of the expert hidden, down matvec of all k (+ shared) experts of one column tile in ONE workgroup
 //                     and the weighted combine (moe.rs:661-667, decode.rs:3343-3402) -- the MoE output lands in the hidden buffer
 #pragma once
@@ -58,6 +59,8 @@ struct KrFmoeArgs {
     const float* act_f32;     // block kernels' products (kr_gguf_dev.h) with a row's blocks split over two waves, libm SiLU (gguf_kernels.rs:733-737)
     int shared_skip;          // expert-parallel decode (m.e_hi > 0): the shared expert of this layer is evaluated by another rank; this rank's hid_out is then its PARTIAL
                               // rsf * sum over its own slots (+ the shared term on the one rank that evaluates it) and the ranks' partials are summed by one all-reduce of [H]
+    int slot_select;          // w13 launch, lean rule (softmax scoring, no score correction, renormalised weights): every routed workgroup selects the id of its own rank only and an
+                              // extra grid row publishes ids / wts (docs/design/33-slot-select.md); 0 = every workgroup runs the full select, workgroup (0, 0) publishes
 };
 int kr_fmoe_check(const KrFmoeArgs& a);      // 0 when both launches below cover the geometry
 int kr_launch_fw13(const KrFmoeArgs& a, hipStream_t st);

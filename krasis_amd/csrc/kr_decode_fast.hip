@@ -23,6 +23,7 @@ extern __shared__ __attribute__((aligned(16))) u32x4 kr_fsm[];
 #ifdef KR_FTIMING   // libkrasis_hip_timing.so (make timing): wall-clock stamps (10 ns units) of wave 0 of the middle workgroup, read back by tools/probes/decode_fast_stamps.py
 __device__ unsigned long long kr_fstamps[8][16];
 #define KR_FSTAMP(k, i) do { if (blockIdx.x == gridDim.x / 2 && blockIdx.y == 0 && threadIdx.x == 0) kr_fstamps[k][i] = wall_clock64(); } while (0)
+#define KR_FSTAMPY(k, i, row_) do { if (blockIdx.x == gridDim.x / 2 && (int)blockIdx.y == (row_) && threadIdx.x == 0) kr_fstamps[k][i] = wall_clock64(); } while (0)      // the same workgroup column, grid row y
 extern "C" int kr_debug_fstamps(unsigned long long* out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(kr_fstamps), sizeof(kr_fstamps)); }
 // entry / exit time and hardware id of EVERY workgroup of a launch (wave 0), for the launches of the last layer of a step: where a launch's tail comes from
 __device__ unsigned long long kr_fwg[6][1024][3];
@@ -31,6 +32,7 @@ __device__ unsigned long long kr_fwg[6][1024][3];
 extern "C" int kr_debug_fwg(unsigned long long* out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(kr_fwg), sizeof(kr_fwg)); }
 #else
 #define KR_FSTAMP(k, i) do { } while (0)
+#define KR_FSTAMPY(k, i, y) do { } while (0)
 #define KR_FWG(k, i) do { } while (0)
 #endif
 
@@ -735,12 +737,100 @@ __device__ __forceinline__ void kr_f_select(const float* logits, const float* es
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
+// The `lean` rule for ONE rank: a routed workgroup of the gate|up launch at grid row `slot` needs the expert id at rank `slot` and nothing else -- the other k - 1 ids
+// and the k weights are read by the down + combine launch only, from what the publisher workgroup of kr_fw13_kernel writes.  The lane sorts its NV keys descending in
+// registers (a fixed compare-exchange network on values, no index carried), then slot + 2 rounds (never past the np of the full select) of: wave maximum of the lane
+// heads, ballot of the lanes that hold it, the first of them pops its head.  Round r yields the r-th largest VALUE whichever of several equal holders pops.  The index
+// is recovered once, after the rounds: the lane that won round `slot` looks the value up among its NV unsorted keys.
+// WHY THE ID IS THAT OF kr_f_select_lean: that function orders the leading np elements by (value desc, index asc) and hands the ids to the reference's heap order only
+// when two of the leading k + 1 values are equal; the heap order permutes EQUAL values only.  A rank whose value differs from both neighbours' (ranks slot - 1 and
+// slot + 1) is therefore held by one element, and that element has rank `slot` under either order.  Any rank that ties a neighbour returns false here -- more than one
+// lane in the ballot of round `slot`, the winner's next key equal to the popped one, or the values of rounds slot - 1, slot, slot + 1 not strictly decreasing -- and
+// the caller runs the full select, unchanged, for this workgroup.  Writes *s_id only: no weights, no other id, no candidate list in LDS.
+// ---------------------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t kr_umin(uint32_t a, uint32_t b) { return a < b ? a : b; }
+#define KR_F_CEX(a_, b_) do { const uint32_t hi_ = kr_umax(s[a_], s[b_]), lo_ = kr_umin(s[a_], s[b_]); s[a_] = hi_; s[b_] = lo_; } while (0)
+template <int NV>
+__device__ __forceinline__ void kr_f_sort_desc(uint32_t (&s)[NV]) {
+    static_assert(NV == 1 || NV == 2 || NV == 4 || NV == 8, "networks for 1, 2, 4 and 8 keys");
+    if constexpr (NV == 2) { KR_F_CEX(0, 1); }
+    if constexpr (NV == 4) { KR_F_CEX(0, 2); KR_F_CEX(1, 3); KR_F_CEX(0, 1); KR_F_CEX(2, 3); KR_F_CEX(1, 2); }
+    if constexpr (NV == 8) {      // 19 exchanges, depth 6
+        KR_F_CEX(0, 2); KR_F_CEX(1, 3); KR_F_CEX(4, 6); KR_F_CEX(5, 7);
+        KR_F_CEX(0, 4); KR_F_CEX(1, 5); KR_F_CEX(2, 6); KR_F_CEX(3, 7);
+        KR_F_CEX(0, 1); KR_F_CEX(2, 3); KR_F_CEX(4, 5); KR_F_CEX(6, 7);
+        KR_F_CEX(2, 4); KR_F_CEX(3, 5);
+        KR_F_CEX(1, 4); KR_F_CEX(3, 6);
+        KR_F_CEX(1, 2); KR_F_CEX(3, 4); KR_F_CEX(5, 6);
+    }
+}
+#undef KR_F_CEX
+#define KR_FSEL(i) do { if (slot == 0) KR_FSTAMPY(7, (i), 0); else if (slot == k - 1) KR_FSTAMPY(7, 8 + (i), slot); } while (0)      // timing build: row 7 = the per-slot select of slot 0 ([0..4]) and of slot k - 1 ([8..12])
+template <int NV>
+__device__ __forceinline__ bool kr_f_slot_select(const float* logits, int E, int k, int slot, int* s_id) {
+    const int lane = threadIdx.x & 63;
+    KR_FSEL(0);
+    float lg[NV];
+    if (NV % 4 == 0 && E % 4 == 0) {
+#pragma unroll
+        for (int i = 0; i + 3 < NV; i += 4) {
+            const int e = lane * NV + i;
+            const float4 v = *reinterpret_cast<const float4*>(logits + (e < E ? e : 0));
+            lg[i] = v.x; lg[i + 1] = v.y; lg[i + 2] = v.z; lg[i + 3] = v.w;
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < NV; i++) { const int e = lane * NV + i; lg[i] = logits[e < E ? e : 0]; }
+    }
+#ifdef KR_FTIMING
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#endif
+    KR_FSEL(1);
+    uint32_t key[NV], s[NV];
+#pragma unroll
+    for (int i = 0; i < NV; i++) { const int e = lane * NV + i; key[i] = e < E ? kr_make_key(lg[i]) : 0u; s[i] = key[i]; }      // (elements e >= E carry the lowest key: never reached, the rounds stop at E)
+    kr_f_sort_desc<NV>(s);
+    KR_FSEL(2);
+    const int np = k + 1 <= E ? k + 1 : k;
+    const int rounds = slot + 2 < np ? slot + 2 : np;      // slot <= k - 1 <= np - 1: round `slot` always runs
+    uint32_t prev = 0u, vs = 0u;
+    int win_s = 0;
+    bool tie = false;
+    for (int r = 0; r < rounds; r++) {
+        const uint32_t w = kr_wave_umax(s[0]);
+        const uint64_t mask = __ballot(s[0] == w);
+        const int win = __builtin_ctzll(mask);
+        if (r == slot) {
+            vs = w; win_s = win;
+            tie = (mask & (mask - 1ull)) != 0ull || (r > 0 && prev == w);
+            if constexpr (NV > 1) tie = tie || (uint32_t)__builtin_amdgcn_readlane((int)s[1], win) == w;
+        } else if (r > slot) tie = tie || w == vs;
+        if (lane == win) {
+#pragma unroll
+            for (int i = 0; i + 1 < NV; i++) s[i] = s[i + 1];
+            s[NV - 1] = 0u;
+        }
+        prev = w;
+    }
+    KR_FSEL(3);
+    if (tie || vs == 0u) return false;      // (key 0 is no element's unless a logit is the all-ones NaN: the full select decides there as it always did)
+    if (lane == win_s) {
+        int idx = 0;
+#pragma unroll
+        for (int i = NV - 1; i >= 0; i--) if (key[i] == vs) idx = i;
+        *s_id = lane * NV + idx;
+    }
+    KR_FSEL(4);
+    return true;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
 // K5: gate | up of the k routed experts + the shared expert (+ its sigmoid-gate row).  grid (units, n_slots); 2 tile PAIRS per workgroup
 // (gate tile t and up tile t + I / 8 of the same hidden column), 2 waves split K; epilogue h = silu(g) * u (avx2.rs:2331-2333, decode.rs:1731-1733).
 // ---------------------------------------------------------------------------------------------------------------------------------
 // (leading scalars = what the select wave and the image copy need for their first requests, preloaded into SGPRs: see kr_fdm_kernel)
 template <int BITS, int NU>
-__global__ void __launch_bounds__(256) kr_fw13_kernel(const float* p_logits, const float* p_esc, const void* p_img_bf16, int p_E, int p_topk, int p_scoring, int p_norm, int p_H, int p_I, int p_gguf,
+__global__ void __launch_bounds__(256) kr_fw13_kernel(const float* p_logits, const float* p_esc, const void* p_img_bf16, int p_E, int p_topk, int p_scoring, int p_norm, int p_H, int p_I, int p_gguf, int p_pub,
                                                       const KrFmoeArgs fa) {
     const KrMoeArgs& a = fa.m;
     constexpr int KS = 2, TW = 2;
@@ -748,17 +838,22 @@ __global__ void __launch_bounds__(256) kr_fw13_kernel(const float* p_logits, con
     __shared__ float s_w[32];
     __shared__ float s_x[TW][KS][2][8];
     const int slot = blockIdx.y;
-    const bool shared = slot >= p_topk;
+    // p_pub != 0 ("slot_select", lean rule only: kr_launch_fw13): grid row p_pub = n_slots is the PUBLISHER row.  Wave 0 of its first workgroup runs the full select
+    // and writes the routing for the w2 launch -- it owns no tile, so it is on no one's path --, every other wave of the row leaves here; a routed workgroup then
+    // selects the id of its own rank only (kr_f_slot_select).  p_pub == 0: every routed workgroup runs the full select and workgroup (0, 0) publishes.
+    const bool pub = p_pub != 0 && slot == p_pub;
+    if (pub && (blockIdx.x != 0 || threadIdx.x >= 64)) return;
+    const bool shared = slot >= p_topk && !pub;
     // the grid's x extent follows the widest slot (a shared expert may be wider than the routed ones): a routed workgroup past its expert's last tile pair leaves
     // before the select and the image copy, not after them (DeepSeek-V2-Lite: half of the launch's workgroups)
-    if (!shared && (int)blockIdx.x * 2 /* TW */ >= p_I / 8) return;      // (workgroup (0, 0), which publishes the routing, always has a tile pair)
+    if (slot < p_topk && (int)blockIdx.x * 2 /* TW */ >= p_I / 8) return;      // (workgroup (0, 0), which publishes the routing when p_pub == 0, always has a tile pair)
     const int t = threadIdx.x, wave = t >> 6, lane = t & 63, l8 = lane & 7, cl = lane >> 3;
     const int tw = wave >> 1, ks = wave & 1;
     const KrActLds L = kr_carve_lds(kr_fsm, p_H, BITS == 8);
     const bool gg = p_gguf && !shared;                  // routed slot on native GGUF blocks: per-32 activation image instead of the per-128 one
     const GgAct GA = gg_carve(reinterpret_cast<char*>(kr_fsm), p_H);
     const size_t img_bytes = p_gguf ? (kr_lds_bytes(p_H, BITS == 8) > gg_lds_bytes(p_H, false) ? kr_lds_bytes(p_H, BITS == 8) : gg_lds_bytes(p_H, false)) : kr_lds_bytes(p_H, BITS == 8);
-    KR_FSTAMP(4, 0); KR_FWG(4, 0);
+    KR_FSTAMP(4, 0); KR_FWG(4, 0); KR_FSTAMPY(7, 13, p_topk - 1);
     if (shared) kr_f_image_copy<BITS>(a.act_img, p_H, kr_fsm, L, t, 256);
     else if (wave > 0) {
         if (gg) {      // quantize_bf16_to_int16 of bf16(hidden) (gguf_kernels.rs:110, decode.rs:3307-3309), 8 values per thread, 4 consecutive lanes per sub-block
@@ -773,14 +868,24 @@ __global__ void __launch_bounds__(256) kr_fw13_kernel(const float* p_logits, con
     } else {
         float* selsm = reinterpret_cast<float*>(reinterpret_cast<char*>(kr_fsm) + img_bytes);
         const int nv = (p_E + 63) / 64;
-        if (nv <= 1) kr_f_select<1>(p_logits, p_esc, p_E, p_topk, p_scoring, p_norm, selsm, s_ids, s_w);
-        else if (nv <= 2) kr_f_select<2>(p_logits, p_esc, p_E, p_topk, p_scoring, p_norm, selsm, s_ids, s_w);
-        else if (nv <= 4) kr_f_select<4>(p_logits, p_esc, p_E, p_topk, p_scoring, p_norm, selsm, s_ids, s_w);
-        else kr_f_select<8>(p_logits, p_esc, p_E, p_topk, p_scoring, p_norm, selsm, s_ids, s_w);
-        if (blockIdx.x == 0 && slot == 0 && lane < p_topk) {   // the routing of this token, for the w2 launch (and anyone who asks)
-            const_cast<int32_t*>(a.ids)[lane] = s_ids[lane]; const_cast<float*>(a.wts)[lane] = s_w[lane];
+        bool full = true;      // the full select: always with p_pub == 0; with p_pub != 0 the publisher, and a routed workgroup whose rank ties a neighbour
+        if (p_pub != 0 && !pub) {
+            if (nv <= 1) full = !kr_f_slot_select<1>(p_logits, p_E, p_topk, slot, &s_ids[slot]);
+            else if (nv <= 2) full = !kr_f_slot_select<2>(p_logits, p_E, p_topk, slot, &s_ids[slot]);
+            else if (nv <= 4) full = !kr_f_slot_select<4>(p_logits, p_E, p_topk, slot, &s_ids[slot]);
+            else full = !kr_f_slot_select<8>(p_logits, p_E, p_topk, slot, &s_ids[slot]);
+        }
+        if (full) {
+            if (nv <= 1) kr_f_select<1>(p_logits, p_esc, p_E, p_topk, p_scoring, p_norm, selsm, s_ids, s_w);
+            else if (nv <= 2) kr_f_select<2>(p_logits, p_esc, p_E, p_topk, p_scoring, p_norm, selsm, s_ids, s_w);
+            else if (nv <= 4) kr_f_select<4>(p_logits, p_esc, p_E, p_topk, p_scoring, p_norm, selsm, s_ids, s_w);
+            else kr_f_select<8>(p_logits, p_esc, p_E, p_topk, p_scoring, p_norm, selsm, s_ids, s_w);
+            if ((p_pub != 0 ? pub : (blockIdx.x == 0 && slot == 0)) && lane < p_topk) {   // the routing of this token, for the w2 launch (and anyone who asks)
+                const_cast<int32_t*>(a.ids)[lane] = s_ids[lane]; const_cast<float*>(a.wts)[lane] = s_w[lane];
+            }
         }
     }
+    if (pub) return;      // (its other waves left at the top: no barrier is left behind it)
     KR_FSTAMP(4, 1);
     __syncthreads();
     KR_FSTAMP(4, 2);
@@ -830,7 +935,7 @@ __global__ void __launch_bounds__(256) kr_fw13_kernel(const float* p_logits, con
     if (pair) {
         kr_f_fetch<BITS, NU, 8>(Wg, m, qb, sb, unit, lane, u0, u1);
         kr_f_fetch<BITS, NU, 8>(Wu, m, qb, sb, unit + ntp, lane, u0, u1);
-        KR_FSTAMP(4, 3);
+        KR_FSTAMP(4, 3); KR_FSTAMPY(7, 14, p_topk - 1);
         ag = kr_f_tile<BITS, NU, 8>(Wg, m, qb, sb, unit, lane, u0, u1, L);
         au = kr_f_tile<BITS, NU, 8>(Wu, m, qb, sb, unit + ntp, lane, u0, u1, L);
     } else if (gate_row) {
@@ -1441,7 +1546,11 @@ int kr_launch_fw13(const KrFmoeArgs& fa, hipStream_t st) {
     const bool has_shared = a.n_slots > a.topk;
     int ntp = a.I / 8;
     if (has_shared && a.I_shared / 8 + (a.sgate.q ? 1 : 0) > ntp) ntp = a.I_shared / 8 + (a.sgate.q ? 1 : 0);
-    dim3 grid((ntp + 1) / 2, a.n_slots);
+    // fa.slot_select (kr_decode_set_option "slot_select"): under the lean rule -- softmax scoring, no score correction, renormalised weights -- a routed workgroup selects its own
+    // rank only and one extra grid row, row n_slots, publishes the routing; every other rule keeps today's launch, grid and prologue
+    const bool per_slot = fa.slot_select != 0 && fa.scoring == 1 && fa.esc == nullptr && fa.norm_topk != 0 && a.E <= 512 && a.topk + 1 <= 64;
+    const int pub = per_slot ? a.n_slots : 0;
+    dim3 grid((ntp + 1) / 2, a.n_slots + (per_slot ? 1 : 0));
     const KrMatDev& wm = fa.gguf ? a.sw13 : a.w13;      // GGUF routed experts: the template follows the (transposed) shared expert; INT4 form when there is none
     const int wbits = fa.gguf && !has_shared ? 4 : wm.bits;
     size_t img = kr_lds_bytes(a.H, wbits == 8);
@@ -1450,7 +1559,7 @@ int kr_launch_fw13(const KrFmoeArgs& fa, hipStream_t st) {
     const int units = fa.gguf && !has_shared ? 0 : (wbits == 4 ? wm.ngp : wm.ng);
     const bool even = !fa.gguf && (a.w13.bits == 8 || (a.w13.ng % 2) == 0) && units % 2 == 0;
     const int nu = even ? units / 2 : 0;
-#define KR_FW13(B_, N_) hipLaunchKernelGGL((kr_fw13_kernel<B_, N_>), grid, dim3(256), lds, st, fa.logits, fa.esc, a.act_img_bf16, a.E, a.topk, fa.scoring, fa.norm_topk, a.H, a.I, fa.gguf, fa)
+#define KR_FW13(B_, N_) hipLaunchKernelGGL((kr_fw13_kernel<B_, N_>), grid, dim3(256), lds, st, fa.logits, fa.esc, a.act_img_bf16, a.E, a.topk, fa.scoring, fa.norm_topk, a.H, a.I, fa.gguf, pub, fa)
     if (wbits == 4) { if (nu == 4) KR_FW13(4, 4); else if (nu == 8) KR_FW13(4, 8); else KR_FW13(4, 0); }
     else { if (nu == 8) KR_FW13(8, 8); else KR_FW13(8, 0); }
 #undef KR_FW13

@@ -27,9 +27,11 @@ def main():
     eng, st, keep = bench.build_qcn(0, 0, int(os.environ.get("LAYERS", "48")), 0, 4, kv_fp8=True, gguf=os.environ.get("GGUF", "0") == "1")
     st.set_attention_mode(False, decode_fast=True)
     st.set_option("lm_fused", 0)      # the one-launch final norm + vocabulary projection is a kr_fdm launch too: it would overwrite the in-projection's stamps
+    if os.environ.get("SLOT_SELECT", "") != "":      # A/B of the gate|up launch's per-slot select (a library from before the option: leave unset)
+        st.set_option("slot_select", int(os.environ["SLOT_SELECT"]))
     lib = st._lib
     buf = (C.c_ulonglong * (8 * 16))()
-    acc = {}; raws = []; raw_last = None; acc6 = []
+    acc = {}; raws = []; raw_last = None; acc6 = []; acc7 = []
     reps = 20
     for i in range(reps + 3):
         st.decode_step(0, 10 + i)
@@ -43,6 +45,7 @@ def main():
             acc.setdefault(k, []).append(d)
         raws.append(a.copy()); raw_last = a
         acc6.append(np.diff(a[6, :7]) * 0.01)
+        acc7.append(a[7].copy())
     lines = []
     # the select prologue of kr_fw13 in finer steps (row 6) and the data-path gap between consecutive launches: last stamp of launch i -> first stamp of launch i + 1
     # (s_memrealtime is one constant-rate counter for the whole device, 10 ns)
@@ -50,6 +53,18 @@ def main():
     if raw_last is not None and raw_last[6, 0] > 0:
         d6 = np.mean(acc6, axis=0)
         lines.append("%-45s in-select %.2f us : " % ("kr_fw13 select prologue, finer", d6.sum()) + "  ".join("%s %.2f" % (p, v) for p, v in zip(sel, d6)))
+    # the per-slot select of kr_fw13 (row 7; "slot_select" 1, lean rule): wave 0 of the middle workgroup of grid row 0 ([0..4]) and of grid row k - 1 ([8..12]),
+    # and that last routed row's kernel entry [13] and "weight fetch issued" [14].  Under "slot_select" 0 the row stays empty but for [13], [14].
+    ssel = ["load", "sort", "rounds", "index"]
+    if raw_last is not None and raw_last[7, 0] > 0:
+        a7 = np.array(acc7)
+        for nm, b in (("slot 0", 0), ("slot k - 1", 8)):
+            if np.all(a7[:, b] > 0):
+                d7 = np.mean(np.diff(a7[:, b:b + 5], axis=1), axis=0) * 0.01
+                lines.append("%-45s in-select %.2f us : " % ("kr_fw13 per-slot select, " + nm, d7.sum()) + "  ".join("%s %.2f" % (p, v) for p, v in zip(ssel, d7)))
+    if raw_last is not None and raw_last[7, 13] > 0 and raw_last[7, 14] > 0:
+        a7 = np.array(acc7)
+        lines.append("%-45s entry -> weight fetch issued %.2f us" % ("kr_fw13, grid row k - 1", float(np.mean(a7[:, 14] - a7[:, 13])) * 0.01))
     chain = [(0, 1), (1, 2), (2, 3), (3, 4), (4, 5)]
     gl = []
     for (a_, b_) in chain:
