@@ -334,7 +334,17 @@ int kr_decode_set_attention_mode(kr_decode_store* s, int mode);
  * "slot_select" (default 1; docs/design/33-slot-select.md): KR_DECODE_FAST, MoE layers under the lean routing rule (softmax scoring, no score
  * correction, renormalised weights; E <= 512): with 1 every routed workgroup of the gate|up launch selects the expert id of its own rank only and one
  * extra grid row publishes ids and weights for the down launch; with 0 every workgroup runs the full top-k select and workgroup (0, 0) publishes.  Same
- * bits either way (tests/test_decode_fast_slot_select_gpu.py); every other routing rule keeps the 0 form whatever the value.  A/B and test hook. */
+ * bits either way (tests/test_decode_fast_slot_select_gpu.py); every other routing rule keeps the 0 form whatever the value.  A/B and test hook.
+ * "pass_few_rows" (default 0; docs/design/34-pass-few-rows.md): with 1, a multi-row pass of T <= "pass_few_rows_max" token rows -- T = n_tokens for
+ * kr_decode_prefill / kr_decode_prefill_nll / kr_decode_verify, the sum of the counts for the slot entry points; decided per pass, never per chunk -- runs every
+ * projection (q|k|v, qkvz|ba, out / o, the MLA kv_a / q / q_a / q_b, the shared expert, the dense MLP, the all-row lm_head) on the few-row streaming matvec
+ * (kr_rows_matvec.hip: the decode step's tile, one weight record applied to all rows of a row group) and the routed experts of INT4 / INT8-g128 layers as the
+ * decode step's three launches over the rows.  Every output keeps the bits it has without the option (tests/test_pass_few_rows_gpu.py).  Passes under
+ * KR_GEMM_FAST, larger passes, native-GGUF routed experts and expert-parallel engines' routed experts keep what they run now.  The option refuses nothing:
+ * a call refused without it is refused with the same code and words.
+ * "pass_few_rows_max" (1 .. 16, else KR_ERR_VALUE; default 16, a measured value: profiles/pass_few_rows.txt): the most token rows of a pass that takes those kernels.
+ * "pass_few_rows_group" (0 .. 16, else KR_ERR_VALUE; default 0 = chosen per launch): the most rows one workgroup of the few-row matvec holds (A/B and test
+ * hook; same bits).  kr_decode_matmul_rows reads it too. */
 int kr_decode_set_option(kr_decode_store* s, const char* name, int value);                                                                        /* decode.rs:2471 */
 /* Whole-model prompt pass.  Replaces the reference's GPU prefill (python/krasis/model.py forward_prefill_layer_grouped / server_prefill,
  * layer.py:242-461, attention.py:496-687, linear_attention.py:695-845 -- third-party kernels) AND the GPU->CPU state hand-off
@@ -620,6 +630,9 @@ int kr_sample_rows(const float* logits, int n, int vocab, const float* temperatu
  * kro_op_* restatements); several differ from the decode graph's arithmetic exactly as they do in the reference (scalar loops, libm exp). */
 int kr_decode_matmul(kr_decode_store* s, int weight_id, const float* input, float* output);                                   /* decode.rs:328 */
 int kr_decode_matmul_batch(kr_decode_store* s, const int* weight_ids, int n, const float* input, float* const* outputs);      /* decode.rs:364 */
+/* kr_decode_matmul over n_rows input rows (no reference counterpart; docs/design/34-pass-few-rows.md): input [n_rows][cols], output [n_rows][rows]; output row r
+   holds the bits of kr_decode_matmul on input row r.  1 <= n_rows <= 16 and cols a multiple of 128, else KR_ERR_VALUE.  The weights are read once per row group. */
+int kr_decode_matmul_rows(kr_decode_store* s, int weight_id, const float* input, int n_rows, float* output);
 /* fused_add_rmsnorm (weight != NULL, decode.rs:406) / fused_add_rmsnorm_id (weight == NULL, stored norm `norm_id`, decode.rs:447) */
 int kr_decode_fused_add_rmsnorm(kr_decode_store* s, float* hidden, float* residual, const float* weight, int norm_id, float eps, int size, int first_call);
 int kr_decode_rmsnorm(kr_decode_store* s, const float* input, const float* weight, float eps, float* output, int size);      /* decode.rs:473 */

@@ -26,7 +26,7 @@ SYMBOLS = [
     "kr_decode_add_gqa_layer", "kr_decode_add_mla_layer", "kr_decode_prefill", "kr_decode_prefill_nll", "kr_decode_reset_state", "kr_decode_generate", "kr_decode_sample", "kr_sample_order", "kr_decode_set_prefill_chunk", "kr_decode_set_prefill_depth", "kr_decode_set_layer_moe", "kr_decode_set_layer_dense", "kr_decode_set_rope", "kr_decode_finalize", "kr_decode_set_kv_dtype", "kr_decode_set_attention_mode", "kr_decode_set_option", "kr_decode_create_on",
     "kr_decode_set_state", "kr_decode_fill_state_synthetic", "kr_decode_get_state", "kr_decode_step", "kr_decode_generate_greedy",
     "kr_decode_last_token", "kr_decode_set_use_graph", "kr_decode_read_buffer", "kr_decode_device_bytes", "kr_decode_profile_step",
-    "kr_decode_generate_stream", "kr_decode_cancel", "kr_decode_reset_cancel", "kr_decode_last_elapsed_s", "kr_decode_matmul", "kr_decode_matmul_batch",
+    "kr_decode_generate_stream", "kr_decode_cancel", "kr_decode_reset_cancel", "kr_decode_last_elapsed_s", "kr_decode_matmul", "kr_decode_matmul_batch", "kr_decode_matmul_rows",
     "kr_decode_fused_add_rmsnorm", "kr_decode_rmsnorm", "kr_decode_silu_mul", "kr_decode_fused_shared_expert", "kr_decode_linear_attention_recurrent",
     "kr_decode_gated_rmsnorm_silu", "kr_decode_linear_attention_conv", "kr_decode_store_route_weight", "kr_decode_moe_route", "kr_decode_num_route_weights",
     "kr_decode_weight_bytes", "kr_decode_verify", "kr_decode_commit", "kr_decode_generate_lookup", "kr_lookup_draft",
@@ -162,6 +162,7 @@ def load_library() -> C.CDLL:
     lib.kr_decode_last_elapsed_s.argtypes = [vp]; lib.kr_decode_last_elapsed_s.restype = C.c_double
     lib.kr_decode_matmul.argtypes = [vp, ci, vp, vp]
     lib.kr_decode_matmul_batch.argtypes = [vp, vp, ci, vp, vp]
+    lib.kr_decode_matmul_rows.argtypes = [vp, ci, vp, ci, vp]
     lib.kr_decode_fused_add_rmsnorm.argtypes = [vp, vp, vp, vp, ci, cf, ci, ci]
     lib.kr_decode_rmsnorm.argtypes = [vp, vp, vp, cf, vp, ci]
     lib.kr_decode_silu_mul.argtypes = [vp, vp, vp, vp, ci]

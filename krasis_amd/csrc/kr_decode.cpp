@@ -1074,6 +1074,15 @@ extern "C" int kr_decode_set_option(kr_decode_store* s, const char* name, int va
     if (!strcmp(name, "multi_extend_mla_flash")) { s->opt_multi_extend_mla_flash = value != 0; return KR_OK; }  // a run of >= 2 tokens entering a slot (extend_multi / prefill_slot) takes the prompt pass's causal MLA flash attention over the slot's latent rows, flat or paged (docs/design/27-multi-extend-mla-flash.md)
     if (!strcmp(name, "gguf_exact_pass")) { s->opt_gguf_exact_pass = value != 0; return KR_OK; }              // native-GGUF MoE layers of every multi-row pass in the exact forms; lifts the GGUF refusal of the slot and speculation entry points (docs/design/20-gguf-exact-pass.md)
     if (!strcmp(name, "gguf_exact_grouped")) { s->opt_gguf_exact_grouped = value != 0; return KR_OK; }        // "gguf_exact_pass": 0 = the streaming kernels for every block type (A/B and test hook; same bits)
+    if (!strcmp(name, "pass_few_rows")) { s->opt_pass_few_rows = value != 0; return KR_OK; }                  // a multi-row pass of at most "pass_few_rows_max" token rows takes the few-row streaming matvec and the decode step's expert launches: same bits (docs/design/34-pass-few-rows.md)
+    if (!strcmp(name, "pass_few_rows_max")) {      // the most token rows of a pass (n_tokens; the sum of a slot call's counts) that takes the few-row kernels; both forms give the same bits
+        if (value < 1 || value > 16) return kr_fail(KR_ERR_VALUE, "pass_few_rows_max %d: 1 .. 16", value);
+        s->opt_pass_few_rows_max = value; return KR_OK;
+    }
+    if (!strcmp(name, "pass_few_rows_group")) {      // the most rows per workgroup of the few-row matvec, 0 = chosen per launch (A/B and test hook; same bits)
+        if (value < 0 || value > 16) return kr_fail(KR_ERR_VALUE, "pass_few_rows_group %d: 0 .. 16", value);
+        s->opt_pass_few_rows_group = value; return KR_OK;
+    }
     if (!strcmp(name, "ep_graph")) { s->opt_ep_graph = value != 0; s->graph_ok = false; return KR_OK; }
     return kr_fail(KR_ERR_VALUE, "unknown option '%s'", name);
 }

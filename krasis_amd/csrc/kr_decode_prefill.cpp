@@ -18,6 +18,7 @@
 
 #include "../../include/krasis_hip.h"
 #include "kr_multi_plan.h"
+#include "kr_rows_plan.h"
 #include "kr_decode_internal.h"
 #include "kr_prefill.h"
 #include "kr_prefill_ops.h"
@@ -34,10 +35,16 @@ struct Scratch {   // carved from one allocation per arena (grown on demand)
     uint16_t *xf, *yf; float *xfm, *yfm;     // KR_GEMM_FAST: the same two activation slots as f16 rows + row multipliers (kr_prefill_h.hip)
     uint16_t* xb; int32_t* ids; float* w;
     float* cv;                               // multi-sequence step: conv + SiLU outputs [rows][conv_dim] of a linear-attention layer
+    // "pass_few_rows" (set per pass, kr_rows_plan.h): the projections read their f32 source rows themselves (kr_rows_matvec.hip) -- slot x is B.normed [rows][H],
+    // slot y what pf_rows / pf_act were last given (they launch nothing then)
+    bool few; int few_group, H; const float* ysrc; int yld, yact;
 };
-struct Act { const int8_t* h; const int8_t* l; const float* s; const uint16_t* f; const float* fm; };   // one GEMM input: INT16 digits or f16 rows
-Act X(const Scratch& B) { return Act{B.xh, B.xl, B.xs, B.xf, B.xfm}; }
-Act Y(const Scratch& B) { return Act{B.yh, B.yl, B.ys, B.yf, B.yfm}; }
+struct Act {      // one GEMM input: INT16 digits or f16 rows; few: its f32 source rows (ld floats apart; act >= 0: rows of [gate | up], that activation first)
+    const int8_t* h; const int8_t* l; const float* s; const uint16_t* f; const float* fm;
+    bool few; int few_group; const float* x; int ld, act;
+};
+Act X(const Scratch& B) { return Act{B.xh, B.xl, B.xs, B.xf, B.xfm, B.few, B.few_group, B.normed, B.H, -1}; }
+Act Y(const Scratch& B) { return Act{B.yh, B.yl, B.ys, B.yf, B.yfm, B.few, B.few_group, B.ysrc, B.yld, B.yact}; }
 struct MultiPass {      // the batched pass over device slots: row b = slot slots[b] at pos[b]; nruns x [slot, off, cnt], the runs of token rows per slot (kr_multi.h)
     const KrMultiPlan& plan;      // what the pass decided (kr_multi_plan.h); its spans are relative to `tables`
     const int32_t* tables; float* lc_scratch; float *xm_inv, *xm_tmax;      // device
@@ -54,8 +61,14 @@ struct Chunk {      // one chunk of the prompt in flight: its arena, stream and 
 size_t al(size_t n) { return (n + 255) & ~(size_t)255; }
 }  // namespace
 
+// "pass_few_rows": the projections of a pass of at most 16 token rows on the few-row streaming matvec, every row with the decode step's bits
+static int pf_few(const KrMatDev* mats, float* const* outs, const int* lds, int n, const Act& A, int C, hipStream_t st) {
+    if (kr_launch_rows_matvec(mats, outs, lds, n, A.x, A.ld, C, A.act, A.few_group, st)) return kr_fail(KR_ERR_HIP, "pass_few_rows: the few-row matvec launch was refused (%d rows, K %d)", C, mats[0].K);
+    return KR_OK;
+}
 static int pf_gemm(kr_decode_store* s, int wid, const Act& A, int C, float* out, int ld, hipStream_t st) {
     DWeight& W = *s->weights[wid];
+    if (A.few) { const KrMatDev m = W.ms.view(); return pf_few(&m, &out, &ld, 1, A, C, st); }
     if (s->gemm_fast) { kr_launch_pfh_gemm(W.ms.view(), A.f, A.fm, nullptr, 1, 0, 0, C, out, ld, st); return KR_OK; }
     if (!W.ms.wsum.p) return kr_fail(KR_ERR_STATE, "internal: nibble sums of weight %d were not prepared", wid);
     kr_launch_pf_gemm(W.ms.view(), (const uint32_t*)W.ms.wsum.p, A.h, A.l, A.s, nullptr, 1, 0, 0, C, out, ld, st);
@@ -65,6 +78,10 @@ static int pf_gemm(kr_decode_store* s, int wid, const Act& A, int C, float* out,
 // when the weight widths or K differ
 static int pf_gemm_multi(kr_decode_store* s, const int* wids, float* const* outs, const int* lds, int n, const Act& A, int C, hipStream_t st) {
     KrMatDev mats[3]; const uint32_t* ws[3];
+    if (A.few && n <= 3) {      // one launch for matrices of one width and K, one each otherwise (the launcher's rule)
+        for (int i = 0; i < n; i++) mats[i] = s->weights[wids[i]]->ms.view();
+        return pf_few(mats, outs, lds, n, A, C, st);
+    }
     bool same = n <= 3;
     for (int i = 0; i < n; i++) {
         DWeight& W = *s->weights[wids[i]];
@@ -81,16 +98,22 @@ static int pf_gemm_multi(kr_decode_store* s, const int* wids, float* const* outs
 }
 // the producers of a GEMM input: INT16 digits (exact) or f16 rows (KR_GEMM_FAST)
 static void pf_rows(kr_decode_store* s, const float* x, int C, int ld, int K, Scratch& B, bool slot_y, hipStream_t st) {
+    if (B.few && slot_y) { B.ysrc = x; B.yld = ld; B.yact = -1; return; }      // the few-row kernel quantises the rows in its prologue
     if (s->gemm_fast) kr_launch_pfh_rows_f32(x, C, ld, K, slot_y ? B.yf : B.xf, slot_y ? B.yfm : B.xfm, st);
     else kr_launch_pfm_quant_f32(x, C, ld, K, slot_y ? B.yh : B.xh, slot_y ? B.yl : B.xl, slot_y ? B.ys : B.xs, st);
 }
 static void pf_act(kr_decode_store* s, const float* gu, int C, int n, int gu_ld, Scratch& B, hipStream_t st) {
+    if (B.few) { B.ysrc = gu; B.yld = gu_ld; B.yact = KR_ACT_SILU_MUL; return; }      // ... and applies the activation there
     if (s->gemm_fast) kr_launch_pfh_act(gu, C, n, gu_ld, KR_ACT_SILU_MUL, 0.0f, 0.0f, B.yf, B.yfm, st);
     else kr_launch_pf_act(gu, C, n, gu_ld, KR_ACT_SILU_MUL, 0.0f, 0.0f, B.yh, B.yl, B.ys, st);
 }
 
 // "gguf_exact_pass": native-GGUF MoE layers of every multi-row pass take the exact forms (B.xb holds bf16_rne(normed), kr_pfm_norm_kernel: the row
 // gg_prologue_f32_as_bf16 forms from the decode step's f32 hidden, so the activation images are the step's)
+// "pass_few_rows": a pass of T token rows (n_tokens of prefill / verify, the sum of the counts of a slot entry point) takes the few-row kernels (kr_rows_plan.h)
+static bool pass_few_rows(const kr_decode_store* s, int T) {
+    return kr_rows_use(s->opt_pass_few_rows, s->opt_pass_few_rows_max, T, s->gemm_fast ? KR_ROWS_MODE_GEMM_FAST : 0);
+}
 static int gguf_exact_bits(const kr_decode_store* s) {
     return s->opt_gguf_exact_pass ? KR_PF_SET_GGUF_EXACT | (s->opt_gguf_exact_grouped ? 0 : KR_PF_SET_GGUF_STREAM) : 0;
 }
@@ -174,7 +197,7 @@ static int run_layer(kr_decode_store* s, Chunk& cx, size_t li) {
     na.mode = cx.add_is_emb ? 1 : 0; na.add_in = B.hid; na.emb = (const float*)s->embedding.p; na.tokens = cx.tok; na.res = B.res;
     na.w = (const float*)s->norms[L.input_norm]->p; na.out = B.normed; na.xh = B.xh; na.xl = B.xl; na.xs = B.xs; na.H = H; na.first = cx.first ? 1 : 0;
     na.bias_one = s->norm_bias_one; na.eps = s->eps;
-    if (s->gemm_fast) { na.xh = nullptr; na.xl = nullptr; na.xs = nullptr; }      // tolerance GEMMs take f16 rows of the normalised value instead of the digits
+    if (s->gemm_fast || B.few) { na.xh = nullptr; na.xl = nullptr; na.xs = nullptr; }      // tolerance GEMMs take f16 rows of the normalised value instead of the digits; the few-row kernels the f32 rows
     if (s->gemm_fast && s->opt_norm_rows) { na.xf = B.xf; na.xfm = B.xfm; }      // ... and the norm launch writes that row image itself (round 6: one launch per norm less)
     kr_launch_pfm_norm(na, Cc, st);
     if (s->gemm_fast && !s->opt_norm_rows) kr_launch_pfh_rows_f32(B.normed, Cc, H, H, B.xf, B.xfm, st);
@@ -311,7 +334,7 @@ static int run_layer(kr_decode_store* s, Chunk& cx, size_t li) {
         // prefill_impl pads ranks that have fewer chunks with empty-shard calls.  Every chunk in flight has its own exchange-buffer set (cx.set) and stream; the
         // collectives of all chunks are ISSUED in one host order that is the same on every rank (the loop structure below depends only on the agreed chunk count).
         if (e->ep) { if (int rc = kr_moe_prefill_ep_set(e, L.moe_layer, B.xb, B.ids, B.w, B.moe, Cc, k, KR_OUT_F32, 1, cx.set, st ? (void*)st : (void*)1)) return rc; }
-        else if (int rc = kr_moe_prefill_set(e, L.moe_layer, B.xb, B.ids, B.w, B.moe, Cc, k, KR_OUT_F32, 1, cx.set | (s->gemm_fast ? KR_PF_SET_FAST : 0) | gguf_exact_bits(s), st)) return rc;
+        else if (int rc = kr_moe_prefill_set(e, L.moe_layer, B.xb, B.ids, B.w, B.moe, Cc, k, KR_OUT_F32, 1, cx.set | (s->gemm_fast ? KR_PF_SET_FAST : 0) | gguf_exact_bits(s) | (B.few ? KR_PF_SET_ROWS : 0), st)) return rc;
         const bool has_shared = L.sgu_wid >= 0, has_gate = has_shared && L.sg_wid >= 0;
         if (has_shared) {   // decode-store numerics: f32 input digits, fast_silu_mul + f32::round digits (decode.rs:3356-3378)
             const int si2 = s->weights[L.sgu_wid]->rows, SI = si2 / 2;
@@ -360,7 +383,7 @@ static int final_rows(kr_decode_store* s, Chunk& cx, float* vlogits) {
     na.mode = cx.add_is_emb ? 1 : 0; na.add_in = B.hid; na.emb = (const float*)s->embedding.p; na.tokens = cx.tok; na.res = B.res;
     na.w = (const float*)s->norms[s->final_norm]->p; na.out = B.normed; na.xh = B.xh; na.xl = B.xl; na.xs = B.xs; na.H = H; na.first = cx.first ? 1 : 0;
     na.bias_one = s->norm_bias_one; na.eps = s->eps;
-    if (s->gemm_fast) { na.xh = nullptr; na.xl = nullptr; na.xs = nullptr; }
+    if (s->gemm_fast || B.few) { na.xh = nullptr; na.xl = nullptr; na.xs = nullptr; }
     if (s->gemm_fast && s->opt_norm_rows) { na.xf = B.xf; na.xfm = B.xfm; }
     kr_launch_pfm_norm(na, cx.Cc, cx.st);
     if (s->gemm_fast && !s->opt_norm_rows) kr_launch_pfh_rows_f32(B.normed, cx.Cc, H, H, B.xf, B.xfm, cx.st);
@@ -544,10 +567,11 @@ static int prefill_impl(kr_decode_store* s, const int32_t* tokens, int n_tokens,
         for (int i = 1; i < D; i++) KR_HIP(hipStreamWaitEvent(streams[i], s->pf_events[ev_start], 0));
     }
     const auto t_enqueue = std::chrono::steady_clock::now();
+    const bool few = pass_few_rows(s, n_tokens);      // decided for the pass, never per chunk
     std::vector<Chunk> chunks(n_chunks);
     for (int c = 0; c < n_chunks; c++) {
         Chunk& cx = chunks[c];
-        cx.set = c % D; cx.B = carve(cx.set); cx.scores = sc_rows ? (float*)((char*)s->pf_scores.p + (size_t)cx.set * sc_bytes) : nullptr;
+        cx.set = c % D; cx.B = carve(cx.set); cx.B.H = H; cx.B.few = few; cx.B.few_group = s->opt_pass_few_rows_group; cx.scores = sc_rows ? (float*)((char*)s->pf_scores.p + (size_t)cx.set * sc_bytes) : nullptr;
         cx.Cc = std::min(CH, n_tokens - c * CH); cx.pos0 = start_pos + c * CH; cx.tok = (const int*)s->pf_tokens.p + (size_t)c * CH;
         cx.first = true; cx.add_is_emb = true; cx.st = streams[cx.set]; cx.verify = verify;
     }
@@ -952,7 +976,7 @@ int kr_multi_pass(kr_decode_store* s, int n, int n_final, const int32_t* d_rows,
     const MultiPass mp{plan, (const int32_t*)M.tiles.p, (float*)M.lc_scratch.p, (float*)M.xm_rows.p, (float*)((char*)M.xm_rows.p + plan.xm_inv_bytes),
                        d_rows, d_rows + 2 * n, d_runs, n_final, verify};
     Chunk cx{};
-    cx.B = pf_carve(Lo, (char*)M.scratch.p); cx.scores = nullptr; cx.tok = d_rows + n; cx.Cc = n; cx.pos0 = 0; cx.set = KR_PF_MAX_DEPTH - 1;
+    cx.B = pf_carve(Lo, (char*)M.scratch.p); cx.B.H = s->hidden; cx.B.few = pass_few_rows(s, n); cx.B.few_group = s->opt_pass_few_rows_group; cx.scores = nullptr; cx.tok = d_rows + n; cx.Cc = n; cx.pos0 = 0; cx.set = KR_PF_MAX_DEPTH - 1;
     cx.first = true; cx.add_is_emb = true; cx.st = st; cx.mp = &mp;
     for (size_t l = 0; l < s->layers.size(); l++)
         if (int rc = run_layer(s, cx, l)) return rc;

@@ -96,6 +96,25 @@ extern "C" int kr_decode_matmul(kr_decode_store* s, int weight_id, const float* 
     return g.finish();
 }
 
+// ---- matmul over 1 .. 16 input rows: output row r = kr_decode_matmul on input row r, bit for bit, the weights read once per row group (kr_rows_matvec.hip)
+extern "C" int kr_decode_matmul_rows(kr_decode_store* s, int weight_id, const float* input, int n_rows, float* output) {
+    if (int rc = chk(s)) return rc;
+    if (int rc = chk_w(s, weight_id)) return rc;
+    if (!input || !output) return kr_fail(KR_ERR_VALUE, "null pointer argument");
+    if (n_rows < 1 || n_rows > 16) return kr_fail(KR_ERR_VALUE, "kr_decode_matmul_rows: n_rows %d out of range (1 .. 16)", n_rows);
+    std::lock_guard<std::mutex> lk(sa(s)->mu);
+    DWeight& W = *s->weights[weight_id];
+    if (W.cols % 128) return kr_fail(KR_ERR_VALUE, "kr_decode_matmul_rows: weight %d has %d columns, not a multiple of 128", weight_id, W.cols);
+    Stage g(s);
+    const float* x = (const float*)g.in(input, (size_t)n_rows * W.cols * 4); float* y = (float*)g.out(output, (size_t)n_rows * W.rows * 4);
+    if (!g.failed) {
+        const KrMatDev m = mv(s, weight_id); const int ld = W.rows;
+        if (kr_launch_rows_matvec(&m, &y, &ld, 1, x, W.cols, n_rows, -1, s->opt_pass_few_rows_group, g.st))
+            return kr_fail(KR_ERR_HIP, "kr_decode_matmul_rows: the few-row matvec launch was refused (%d rows, K %d)", n_rows, W.cols);
+    }
+    return g.finish();
+}
+
 extern "C" int kr_decode_matmul_batch(kr_decode_store* s, const int* weight_ids, int n, const float* input, float* const* outputs) {
     if (int rc = chk(s)) return rc;
     if (n < 0 || (n > 0 && (!weight_ids || !outputs || !input))) return kr_fail(KR_ERR_VALUE, "null pointer argument");

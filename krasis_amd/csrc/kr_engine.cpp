@@ -1151,7 +1151,7 @@ int kr_moe_prefill_set(kr_engine* e, int layer, const void* x_bf16, const int32_
     std::lock_guard<std::mutex> lk(e->mu);
     KR_HIP(hipSetDevice(e->device));
     const bool fast = e->gemm_fast || (set & KR_PF_SET_FAST);
-    const bool gguf_exact = set & KR_PF_SET_GGUF_EXACT, gguf_stream = set & KR_PF_SET_GGUF_STREAM;
+    const bool gguf_exact = set & KR_PF_SET_GGUF_EXACT, gguf_stream = set & KR_PF_SET_GGUF_STREAM, few_rows = set & KR_PF_SET_ROWS;
     set &= 0xFF;
     if (L.gguf && gguf_exact) {
         if (fast) return kr_fail(KR_ERR_STATE, "the exact GGUF pass (\"gguf_exact_pass\") does not run together with the tolerance GEMMs (KR_GEMM_FAST)");
@@ -1168,6 +1168,21 @@ int kr_moe_prefill_set(kr_engine* e, int layer, const void* x_bf16, const int32_
     const int H = e->cfg.hidden_size, I = L.inter, E = e->cfg.n_routed_experts;
     const bool use_shared = L.shared_present && !routed_only;
     const int SI = L.shared_inter;
+    if (few_rows && M <= 16 && !use_shared) {
+        // KR_PF_SET_ROWS: the decode step's launches with B = M rows on blockIdx.z -- per (row, slot) the streaming matvec over the row's bf16 image, the activation in
+        // the down launch's prologue, the routing-order sum (bit-identical to the grouped GEMM below: header comment of kr_prefill.hip).  No sort, no row quantiser.
+        KrMoeArgs a{};
+        a.B = M; a.topk = topk; a.n_slots = topk; a.E = E; a.H = H; a.I = I; a.I_shared = SI;
+        a.w13 = L.w13.view(); a.w2 = L.w2.view(); a.gu_ld = 2 * I;
+        if (P.gu.ensure((size_t)M * topk * a.gu_ld * 4) || P.eo.ensure((size_t)M * topk * H * 4)) return kr_fail(KR_ERR_HIP, "hipMalloc of prefill scratch failed");
+        a.gu = (float*)P.gu.p; a.eo = (float*)P.eo.p;
+        a.act = (const uint16_t*)x_bf16; a.ids = ids; a.wts = wts; a.out = out; a.out_bf16 = out_dtype == KR_OUT_BF16;
+        a.rsf = e->cfg.routed_scaling_factor; a.swiglu_limit = e->cfg.swiglu_limit; a.alpha = e->cfg.activation_alpha;
+        a.act_mode = e->cfg.swiglu_limit > 0.0f ? KR_ACT_GPTOSS : KR_ACT_SILU_FUSED;
+        kr_launch_moe_decode(a, st);
+        KR_HIP(hipGetLastError());
+        return KR_OK;
+    }
     if (int rc = kr_ensure_wsum(e, L.w13, st)) return rc;
     if (int rc = kr_ensure_wsum(e, L.w2, st)) return rc;
     if (use_shared) { if (int rc = kr_ensure_wsum(e, L.sw13, st)) return rc; if (int rc = kr_ensure_wsum(e, L.sw2, st)) return rc; }

@@ -140,6 +140,7 @@ int kr_moe_prefill_rows(kr_engine* e, int layer, const void* rows_bf16, const in
 #define KR_PF_SET_FAST 0x100   // or-ed into `set`: this call takes the tolerance GEMMs whatever kr_moe_set_gemm_mode says (the decode store's KR_GEMM_FAST)
 #define KR_PF_SET_GGUF_EXACT 0x200    // or-ed into `set`: a native-GGUF layer takes the exact pass (kr_gguf_group.hip; the decode store's "gguf_exact_pass"): every row with the decode step's bits
 #define KR_PF_SET_GGUF_STREAM 0x400   // ... through the streaming kernels of kr_gguf.hip for every block type ("gguf_exact_grouped" 0: A/B and test hook, same bits)
+#define KR_PF_SET_ROWS 0x800          // or-ed into `set`: an INT4 / INT8-g128 layer with M <= 16 and no shared expert in the call runs as the decode step's three launches over the bf16 rows (kr_launch_moe_w13 / _w2 / _combine, B = M; the decode store's "pass_few_rows"): the same bits, 3 launches instead of 8
 int kr_moe_prefill_set(kr_engine* e, int layer, const void* x_bf16, const int32_t* ids, const float* wts, void* out, int M, int topk,
                        int out_dtype, int routed_only, int set, hipStream_t st);
 

@@ -89,6 +89,10 @@ struct KrCoLa {
     int nk, dk, hr, dv, conv_mi;
 };
 int kr_launch_multi_matvec_la(const KrMatDev* mats, float* const* ys, int n, const void* x_img, const KrCoLa& la, hipStream_t st);
+// the same matvec over R <= 16 f32 rows (kr_rows_matvec.hip): ys[i][r * lds[i] + c] = (W_i . quant(x[r * ld_x ..]))[c], every row with kr_launch_multi_matvec's bits;
+// the lane's weight records are loaded once per row group.  act_mode < 0: rows of K values; KR_ACT_SILU_MUL: rows of [gate(K) | up(K)].  Matrices of unlike width or
+// K go one launch each.  group: 0 = auto, else the most rows per workgroup.  Non-zero: R out of range, or the LDS window was refused.
+int kr_launch_rows_matvec(const KrMatDev* mats, float* const* ys, const int* lds, int n, const float* x, int ld_x, int R, int act_mode, int group, hipStream_t st);
 
 void kr_launch_fill_synth(void* q, size_t q_bytes, uint32_t* s, size_t s_words, uint64_t seed, hipStream_t st);
 void kr_launch_fill_uniform_f32(float* x, size_t n, float amp, uint64_t seed, hipStream_t st);

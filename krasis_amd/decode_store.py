@@ -175,6 +175,11 @@ class CpuDecodeStore:
     def matmul(self, weight_id: int, input_ptr: int, output_ptr: int) -> None:
         check(self._lib.kr_decode_matmul(self._h, weight_id, input_ptr, output_ptr))
 
+    def matmul_rows(self, weight_id: int, input_ptr: int, n_rows: int, output_ptr: int) -> None:
+        """matmul over 1 .. 16 input rows (no reference counterpart): input [n_rows][cols], output [n_rows][rows]; row r carries the bits of matmul on row r,
+        the weights are read once per row group (docs/design/34-pass-few-rows.md)"""
+        check(self._lib.kr_decode_matmul_rows(self._h, weight_id, input_ptr, int(n_rows), output_ptr))
+
     def matmul_batch(self, weight_ids: Sequence[int], input_ptr: int, output_ptrs: Sequence[int]) -> None:
         if len(weight_ids) != len(output_ptrs):
             raise ValueError("weight_ids and output_ptrs must have same length")          # decode.rs:370
@@ -371,7 +376,14 @@ class CpuDecodeStore:
         native-GGUF MoE layers through the exact grouped block kernels -- every row carries the bits of decode_step on that sequence alone -- and the
         slot and speculation calls accept a store with such layers; slower than the default int8-MFMA form on long prompts; refused together with
         gemm_fast; nothing changes for other weight forms (docs/design/20-gguf-exact-pass.md).  "gguf_exact_grouped" (default 1): 0 makes that pass
-        take the streaming block kernels for every type (A/B and test hook, same bits)"""
+        take the streaming block kernels for every type (A/B and test hook, same bits).
+        "pass_few_rows" (default 0): with 1 a multi-row pass of at most "pass_few_rows_max" token rows (prefill / prefill_nll / verify: the number of
+        tokens; the slot calls: the sum of their counts) runs every projection on a few-row form of the decode step's streaming matvec and the INT4 /
+        INT8 routed experts as the step's three launches.  Every call gives, bit for bit, what it gives with the option off; passes under gemm_fast,
+        larger passes, native-GGUF and expert-parallel routed experts keep what they run; nothing is refused that was not refused before
+        (docs/design/34-pass-few-rows.md).  "pass_few_rows_max" (1 .. 16 -- outside: ValueError; default 16, a measured value).
+        "pass_few_rows_group" (0 .. 16, default 0 = chosen per launch): the most rows one workgroup of that matvec holds (A/B and test hook, same
+        bits; matmul_rows reads it too)"""
         self._need(); check(self._lib.kr_decode_set_option(self._h, name.encode(), int(value)))
 
     def finalize_decode(self) -> None:
