@@ -335,6 +335,10 @@ int kr_decode_set_attention_mode(kr_decode_store* s, int mode);
  * correction, renormalised weights; E <= 512): with 1 every routed workgroup of the gate|up launch selects the expert id of its own rank only and one
  * extra grid row publishes ids and weights for the down launch; with 0 every workgroup runs the full top-k select and workgroup (0, 0) publishes.  Same
  * bits either way (tests/test_decode_fast_slot_select_gpu.py); every other routing rule keeps the 0 form whatever the value.  A/B and test hook.
+ * "slot_rows_late_first" (default 1; docs/design/35-launch-stragglers.md): KR_DECODE_FAST, the gate|up launch under the per-slot select serves slot
+ * topk - 1 - y in routed grid row y, so that the slots with the longest select are handed out first; with 0 row y serves slot y; without the per-slot select
+ * the value changes nothing.  Scheduling only, no workgroup reads another's output inside the launch; same bits either way
+ * (tests/test_decode_fast_stragglers_gpu.py).  A/B and test hook.
  * "pass_few_rows" (default 0; docs/design/34-pass-few-rows.md): with 1, a multi-row pass of T <= "pass_few_rows_max" token rows -- T = n_tokens for
  * kr_decode_prefill / kr_decode_prefill_nll / kr_decode_verify, the sum of the counts for the slot entry points; decided per pass, never per chunk -- runs every
  * projection (q|k|v, qkvz|ba, out / o, the MLA kv_a / q / q_a / q_b, the shared expert, the dense MLP, the all-row lm_head) on the few-row streaming matvec

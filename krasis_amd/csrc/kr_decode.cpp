@@ -752,7 +752,7 @@ static int fast_moe(StepCtx& cx, DLayer& L, Layer& EL, size_t li, bool* done) {
         else ok = false;
     }
     fa.logits = (const float*)s->r_logits.p; fa.esc = route_esc(EL); fa.scoring = s->scoring; fa.norm_topk = s->norm_topk;
-    fa.hid_out = cx.hid; fa.slot_select = s->opt_slot_select;
+    fa.hid_out = cx.hid; fa.slot_select = s->opt_slot_select; fa.slot_rows_late_first = s->opt_slot_rows_late_first;
     if (cx.ep_dec) {
         kr_ep_slice(e, &a.e_lo, &a.e_hi, &a.e_sub);
         fa.shared_skip = m.has_shared && kr_ep_rank(e) != (int)(li % (size_t)kr_ep_world(e)) ? 1 : 0;
@@ -1050,6 +1050,7 @@ extern "C" int kr_decode_set_option(kr_decode_store* s, const char* name, int va
     if (!strcmp(name, "la_conv_fused")) { s->opt_la_conv_fused = value != 0; return KR_OK; }                // KR_ATTN_FAST prompt pass: 0 = the stand-alone conv launch in front of the delta-rule prep (A/B and test hook; same bits)
     if (!strcmp(name, "dense_fast")) { s->opt_dense_fast = value != 0; s->graph_ok = false; return KR_OK; }       // KR_DECODE_FAST: 0 = a dense MLP layer keeps the exact norm + gate | up launches (A/B and test hook)
     if (!strcmp(name, "slot_select")) { s->opt_slot_select = value != 0; s->graph_ok = false; return KR_OK; }     // KR_DECODE_FAST, lean routing rule: 0 = every workgroup of the gate|up launch runs the full top-k select and workgroup (0, 0) publishes the routing (A/B and test hook; same bits; docs/design/33-slot-select.md)
+    if (!strcmp(name, "slot_rows_late_first")) { s->opt_slot_rows_late_first = value != 0; s->graph_ok = false; return KR_OK; }     // KR_DECODE_FAST, gate|up launch under "slot_select": 0 = routed grid row y serves slot y instead of slot topk - 1 - y (A/B and test hook; scheduling only, same bits; docs/design/35-launch-stragglers.md)
     if (!strcmp(name, "norm_rows")) { s->opt_norm_rows = value != 0; return KR_OK; }                        // KR_GEMM_FAST prompt pass: 0 = the f16 row image of a norm's output by its own launch (A/B and test hook; same bits)
     if (!strcmp(name, "pfm_timing")) { s->opt_pfm_timing = value != 0; return KR_OK; }
     if (!strcmp(name, "generate_lookahead")) { s->opt_gen_lookahead = value != 0; return KR_OK; }

@@ -61,6 +61,8 @@ struct KrFmoeArgs {
                               // rsf * sum over its own slots (+ the shared term on the one rank that evaluates it) and the ranks' partials are summed by one all-reduce of [H]
     int slot_select;          // w13 launch, lean rule (softmax scoring, no score correction, renormalised weights): every routed workgroup selects the id of its own rank only and an
                               // extra grid row publishes ids / wts (docs/design/33-slot-select.md); 0 = every workgroup runs the full select, workgroup (0, 0) publishes
+    int slot_rows_late_first; // w13 launch under the per-slot select: routed grid row y serves slot topk - 1 - y, so that the slots with the longest select start first
+                              // (docs/design/35-launch-stragglers.md); 0 = row y serves slot y.  Scheduling only: same bits
 };
 int kr_fmoe_check(const KrFmoeArgs& a);      // 0 when both launches below cover the geometry
 int kr_launch_fw13(const KrFmoeArgs& a, hipStream_t st);

@@ -765,7 +765,7 @@ __device__ __forceinline__ void kr_f_sort_desc(uint32_t (&s)[NV]) {
     }
 }
 #undef KR_F_CEX
-#define KR_FSEL(i) do { if (slot == 0) KR_FSTAMPY(7, (i), 0); else if (slot == k - 1) KR_FSTAMPY(7, 8 + (i), slot); } while (0)      // timing build: row 7 = the per-slot select of slot 0 ([0..4]) and of slot k - 1 ([8..12])
+#define KR_FSEL(i) do { if (slot == 0) KR_FSTAMPY(7, (i), (int)blockIdx.y); else if (slot == k - 1) KR_FSTAMPY(7, 8 + (i), (int)blockIdx.y); } while (0)      // timing build: row 7 = the per-slot select of slot 0 ([0..4]) and of slot k - 1 ([8..12]), whichever grid rows serve them
 template <int NV>
 __device__ __forceinline__ bool kr_f_slot_select(const float* logits, int E, int k, int slot, int* s_id) {
     const int lane = threadIdx.x & 63;
@@ -837,11 +837,17 @@ __global__ void __launch_bounds__(256) kr_fw13_kernel(const float* p_logits, con
     __shared__ int s_ids[32];
     __shared__ float s_w[32];
     __shared__ float s_x[TW][KS][2][8];
-    const int slot = blockIdx.y;
-    // p_pub != 0 ("slot_select", lean rule only: kr_launch_fw13): grid row p_pub = n_slots is the PUBLISHER row.  Wave 0 of its first workgroup runs the full select
+    // p_pub != 0 ("slot_select", lean rule only: kr_launch_fw13): grid row |p_pub| = n_slots is the PUBLISHER row.  Wave 0 of its first workgroup runs the full select
     // and writes the routing for the w2 launch -- it owns no tile, so it is on no one's path --, every other wave of the row leaves here; a routed workgroup then
     // selects the id of its own rank only (kr_f_slot_select).  p_pub == 0: every routed workgroup runs the full select and workgroup (0, 0) publishes.
-    const bool pub = p_pub != 0 && slot == p_pub;
+    // p_pub < 0 ("slot_rows_late_first"): routed grid row y serves slot topk - 1 - y.  The per-slot select of slot s walks s + 2 serial rounds before the workgroup can
+    // ask for its weights, and grid rows have been observed to start in row order, the last ones on CUs that already hold a workgroup: the longest prologues get the
+    // head start and the empty CUs.  Scheduling for speed only -- dispatch order and placement are no contract and nothing here depends on them: every row computes
+    // what it computes under the identity mapping, everything below goes by `slot`, and the shared and publisher rows keep their places.
+    const int prow = p_pub < 0 ? -p_pub : p_pub;
+    const int slot = p_pub < 0 && (int)blockIdx.y < p_topk ? p_topk - 1 - (int)blockIdx.y : (int)blockIdx.y;
+    [[maybe_unused]] const int ylast = p_pub < 0 ? 0 : p_topk - 1;      // timing build: the grid row of slot topk - 1
+    const bool pub = p_pub != 0 && slot == prow;
     if (pub && (blockIdx.x != 0 || threadIdx.x >= 64)) return;
     const bool shared = slot >= p_topk && !pub;
     // the grid's x extent follows the widest slot (a shared expert may be wider than the routed ones): a routed workgroup past its expert's last tile pair leaves
@@ -853,7 +859,7 @@ __global__ void __launch_bounds__(256) kr_fw13_kernel(const float* p_logits, con
     const bool gg = p_gguf && !shared;                  // routed slot on native GGUF blocks: per-32 activation image instead of the per-128 one
     const GgAct GA = gg_carve(reinterpret_cast<char*>(kr_fsm), p_H);
     const size_t img_bytes = p_gguf ? (kr_lds_bytes(p_H, BITS == 8) > gg_lds_bytes(p_H, false) ? kr_lds_bytes(p_H, BITS == 8) : gg_lds_bytes(p_H, false)) : kr_lds_bytes(p_H, BITS == 8);
-    KR_FSTAMP(4, 0); KR_FWG(4, 0); KR_FSTAMPY(7, 13, p_topk - 1);
+    KR_FSTAMP(4, 0); KR_FWG(4, 0); KR_FSTAMPY(7, 13, ylast);
     if (shared) kr_f_image_copy<BITS>(a.act_img, p_H, kr_fsm, L, t, 256);
     else if (wave > 0) {
         if (gg) {      // quantize_bf16_to_int16 of bf16(hidden) (gguf_kernels.rs:110, decode.rs:3307-3309), 8 values per thread, 4 consecutive lanes per sub-block
@@ -935,7 +941,7 @@ __global__ void __launch_bounds__(256) kr_fw13_kernel(const float* p_logits, con
     if (pair) {
         kr_f_fetch<BITS, NU, 8>(Wg, m, qb, sb, unit, lane, u0, u1);
         kr_f_fetch<BITS, NU, 8>(Wu, m, qb, sb, unit + ntp, lane, u0, u1);
-        KR_FSTAMP(4, 3); KR_FSTAMPY(7, 14, p_topk - 1);
+        KR_FSTAMP(4, 3); KR_FSTAMPY(7, 14, ylast);
         ag = kr_f_tile<BITS, NU, 8>(Wg, m, qb, sb, unit, lane, u0, u1, L);
         au = kr_f_tile<BITS, NU, 8>(Wu, m, qb, sb, unit + ntp, lane, u0, u1, L);
     } else if (gate_row) {
@@ -1549,7 +1555,8 @@ int kr_launch_fw13(const KrFmoeArgs& fa, hipStream_t st) {
     // fa.slot_select (kr_decode_set_option "slot_select"): under the lean rule -- softmax scoring, no score correction, renormalised weights -- a routed workgroup selects its own
     // rank only and one extra grid row, row n_slots, publishes the routing; every other rule keeps today's launch, grid and prologue
     const bool per_slot = fa.slot_select != 0 && fa.scoring == 1 && fa.esc == nullptr && fa.norm_topk != 0 && a.E <= 512 && a.topk + 1 <= 64;
-    const int pub = per_slot ? a.n_slots : 0;
+    // fa.slot_rows_late_first ("slot_rows_late_first"; per-slot select only): the sign of the publisher row tells the kernel that routed grid row y serves slot topk - 1 - y
+    const int pub = per_slot ? (fa.slot_rows_late_first ? -a.n_slots : a.n_slots) : 0;
     dim3 grid((ntp + 1) / 2, a.n_slots + (per_slot ? 1 : 0));
     const KrMatDev& wm = fa.gguf ? a.sw13 : a.w13;      // GGUF routed experts: the template follows the (transposed) shared expert; INT4 form when there is none
     const int wbits = fa.gguf && !has_shared ? 4 : wm.bits;

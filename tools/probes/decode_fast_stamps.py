@@ -29,6 +29,8 @@ def main():
     st.set_option("lm_fused", 0)      # the one-launch final norm + vocabulary projection is a kr_fdm launch too: it would overwrite the in-projection's stamps
     if os.environ.get("SLOT_SELECT", "") != "":      # A/B of the gate|up launch's per-slot select (a library from before the option: leave unset)
         st.set_option("slot_select", int(os.environ["SLOT_SELECT"]))
+    if os.environ.get("SLOT_ROWS_LATE_FIRST", "") != "":      # A/B of docs/design/35-launch-stragglers.md (a library from before the option: leave unset)
+        st.set_option("slot_rows_late_first", int(os.environ["SLOT_ROWS_LATE_FIRST"]))
     lib = st._lib
     buf = (C.c_ulonglong * (8 * 16))()
     acc = {}; raws = []; raw_last = None; acc6 = []; acc7 = []
@@ -55,6 +57,7 @@ def main():
         lines.append("%-45s in-select %.2f us : " % ("kr_fw13 select prologue, finer", d6.sum()) + "  ".join("%s %.2f" % (p, v) for p, v in zip(sel, d6)))
     # the per-slot select of kr_fw13 (row 7; "slot_select" 1, lean rule): wave 0 of the middle workgroup of grid row 0 ([0..4]) and of grid row k - 1 ([8..12]),
     # and that last routed row's kernel entry [13] and "weight fetch issued" [14].  Under "slot_select" 0 the row stays empty but for [13], [14].
+    # Under "slot_rows_late_first" 1 the stamps follow the SLOTS (slot 0 sits in grid row k - 1, slot k - 1 in grid row 0); the kr_fw13 phase line below stays grid row 0.
     ssel = ["load", "sort", "rounds", "index"]
     if raw_last is not None and raw_last[7, 0] > 0:
         a7 = np.array(acc7)

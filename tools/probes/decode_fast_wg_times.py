@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Where the tail of a KR_DECODE_FAST launch comes from: entry / exit wall-clock time (s_memrealtime, 10 ns) and hardware id (XCC, SE, CU) of EVERY workgroup of
 the six launches of the last layer of a step (timing build: make -C krasis_amd/csrc timing).
-    KRASIS_HIP_LIB=krasis_amd/libkrasis_hip_timing.so LAYERS=47 python tools/probes/decode_fast_wg_times.py"""
+    KRASIS_HIP_LIB=krasis_amd/libkrasis_hip_timing.so LAYERS=47 [SLOT_SELECT=0|1] [SLOT_ROWS_LATE_FIRST=0|1] python tools/probes/decode_fast_wg_times.py"""
 import ctypes as C
 import os
 import sys
@@ -21,6 +21,9 @@ def main():
     eng, st, keep = bench.build_qcn(0, 0, int(os.environ.get("LAYERS", "47")), 0, 4, kv_fp8=True)
     st.set_attention_mode(False, decode_fast=True)
     st.set_option("lm_fused", 0)      # the one-launch final norm + vocabulary projection is a kr_fdm launch too: it would overwrite the in-projection's stamps
+    for env, name in (("SLOT_SELECT", "slot_select"), ("SLOT_ROWS_LATE_FIRST", "slot_rows_late_first")):      # A/B hooks (a library from before an option: leave it unset)
+        if os.environ.get(env, "") != "":
+            st.set_option(name, int(os.environ[env]))
     buf = (C.c_ulonglong * (6 * 1024 * 3))()
     lines = ["# QCN decode step, KR_DECODE_FAST, launches of the last (linear-attention) layer: per workgroup entry / exit (us, relative to the launch's first entry)"]
     acc = {}
