@@ -325,6 +325,18 @@ int kr_decode_set_attention_mode(kr_decode_store* s, int mode);
  * and the other layer kinds are untouched; independent of "multi_extend_exact_mfma" and "multi_extend_la_chunk".  Refused by every batched entry point, behind
  * everything they refused before, each message naming the option: together with "multi_extend_mla_flash" (KR_ERR_STATE: two options claim the same runs), a store
  * without an MLA layer (KR_ERR_STATE), an MLA layer whose head count does not divide 32 (KR_ERR_VALUE: an error, not a fall-back to the per-slot kernel).
+ * "multi_extend_la_exact" (default 0; docs/design/36-multi-extend-la-exact.md): in a non-verify batched pass (kr_decode_extend_multi and the steps that go
+ * through the same pass) the linear-attention layers give every run of counts[i] >= "multi_extend_la_exact_min" tokens the staged form of the store's own exact
+ * prompt pass: conv + SiLU + gates + L2 norms parallel over (key head, 16 tokens), the carried conv inputs, the delta rule alone in the serial loop (the output
+ * chain of token t and the kv chain of token t + 1 interleaved, one barrier per token), the gated RMSNorm parallel over tokens -- the same kernel templates under
+ * another placement (kr_pfm_la_dev.h), value for value the arithmetic of the run kernels, so every call gives, bit for bit, what it gives with the option off:
+ * ids, logits, every conv input and recurrent state, every K / V or latent row, on flat, paged and forked slots, whatever other rows share the pass and however
+ * the stream is cut.  Shorter runs and unit rows keep the run kernels; verify passes and the other layer kinds are untouched; it composes with
+ * "multi_extend_exact_mfma", "multi_extend_mla_exact_mfma", "multi_attn_exact_split", "multi_mla_exact_split", "pass_few_rows" and the flash run options.
+ * Refused by every batched entry point, behind everything they refused before, each message naming the option: together with "multi_extend_la_chunk"
+ * (KR_ERR_STATE: two options claim the long runs), a store without a linear-attention layer (KR_ERR_STATE), a linear-attention layer outside dk 64 / 128,
+ * dk <= dv <= 256, dv % 8 == 0, 16-byte in-projection rows, nv = nk hr (KR_ERR_VALUE: an error, not a fall-back to the run kernels).
+ * "multi_extend_la_exact_min" (default 8, 2 .. 1024 -- outside: KR_ERR_VALUE): the shortest run that is staged; same bits either way, the value is a measured one.
  * "gguf_exact_pass" (default 0; docs/design/20-gguf-exact-pass.md): with 1, every multi-row pass of the store -- kr_decode_prefill, kr_decode_prefill_nll,
  * kr_decode_verify and the batched pass behind every slot entry point -- runs MoE layers that hold native GGUF blocks through the exact grouped block
  * kernels (kr_gguf_group.hip) instead of the int8-MFMA form: every row then carries the bits of kr_decode_step on that sequence alone, and the slot and

@@ -1067,6 +1067,11 @@ extern "C" int kr_decode_set_option(kr_decode_store* s, const char* name, int va
         s->opt_multi_attn_exact_split_min = value; return KR_OK;
     }
     if (!strcmp(name, "multi_mla_exact_split")) { s->opt_multi_mla_exact_split = value != 0; return KR_OK; }      // the exact per-slot MLA attention of every batched pass (steps, verify passes, the unit rows of extends) as scores / softmax / weighted-sum launches spread over positions, heads and latent slices: same bits as the one kernel (docs/design/31-multi-mla-exact-split.md)
+    if (!strcmp(name, "multi_extend_la_exact")) { s->opt_multi_extend_la_exact = value != 0; return KR_OK; }      // a run of >= "multi_extend_la_exact_min" tokens entering a slot (extend_multi / prefill_slot) takes the staged exact form of the prompt pass in its linear-attention layers: same bits as the run kernels (docs/design/36-multi-extend-la-exact.md)
+    if (!strcmp(name, "multi_extend_la_exact_min")) {      // the shortest run that is staged; both forms give the same bits
+        if (value < 2 || value > 1024) return kr_fail(KR_ERR_VALUE, "multi_extend_la_exact_min %d: must be in [2, 1024]", value);
+        s->opt_multi_extend_la_exact_min = value; return KR_OK;
+    }
     if (!strcmp(name, "multi_mla_exact_split_min")) {      // the smallest number of positions (the pass's longest per-row MLA attention) from which "multi_mla_exact_split" applies; both forms give the same bits
         if (value < 1) return kr_fail(KR_ERR_VALUE, "multi_mla_exact_split_min %d: at least 1", value);
         s->opt_multi_mla_exact_split_min = value; return KR_OK;

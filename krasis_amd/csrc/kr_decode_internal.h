@@ -104,6 +104,8 @@ struct kr_decode_store {
     int opt_multi_extend_la_chunk = 0;           // kr_decode_set_option("multi_extend_la_chunk"): in a non-verify batched pass the linear-attention layers give every run of >= 64 tokens the chunked delta rule of the KR_ATTN_FAST prompt pass, fused form -- its bits (tolerance form, docs/design/26-multi-extend-la-chunk.md); shorter runs keep the exact run kernels; the mode bits stay refused
     int opt_multi_attn_exact_split = 0;          // kr_decode_set_option("multi_attn_exact_split"): a batched pass whose per-row GQA kernels attend over at least opt_multi_attn_exact_split_min positions launches the exact per-slot attention as scores / softmax / P.V kernels spread over positions, heads and head-dim slices (kr_multi_split.hip) -- bit for bit the one kernel's result (docs/design/30-multi-attn-exact-split.md)
     int opt_multi_attn_exact_split_min = 512;    // kr_decode_set_option("multi_attn_exact_split_min"), >= 1: the smallest attn_pos + 1 of a pass that takes the split (a measured default: profiles/multi_attn_exact_split.txt)
+    int opt_multi_extend_la_exact = 0;           // kr_decode_set_option("multi_extend_la_exact"): in a non-verify batched pass the linear-attention layers give every run of >= opt_multi_extend_la_exact_min tokens the staged exact form of the store's own prompt pass (kr_multi_la_exact.hip) -- bit for bit the run kernels' result (docs/design/36-multi-extend-la-exact.md); shorter runs and unit rows keep the run kernels
+    int opt_multi_extend_la_exact_min = 8;       // kr_decode_set_option("multi_extend_la_exact_min"), 2 .. 1024: the shortest run that is staged (a measured default: profiles/multi_extend_la_exact.txt)
     int opt_multi_mla_exact_split = 0;           // kr_decode_set_option("multi_mla_exact_split"): a batched pass whose per-row MLA kernels attend over at least opt_multi_mla_exact_split_min positions launches the exact per-slot MLA attention as scores / softmax / weighted-sum kernels spread over positions, heads and latent slices (kr_multi_mla_split.hip) -- bit for bit the one kernel's result (docs/design/31-multi-mla-exact-split.md)
     int opt_multi_mla_exact_split_min = 512;     // kr_decode_set_option("multi_mla_exact_split_min"), >= 1: the smallest mla_pos + 1 of a pass that takes the split (a measured default: profiles/multi_mla_exact_split.txt)
     int opt_multi_extend_exact_mfma = 0;         // kr_decode_set_option("multi_extend_exact_mfma"): in a non-verify batched pass the GQA layers give every run of >= 2 tokens the exact prompt pass's three passes over its slot, flat or paged -- scores and P.V on the f32 matrix cores, bit for bit the per-row kernel's result (docs/design/28-multi-extend-exact-mfma.md); runs of one token keep what they had; refused together with "multi_extend_flash"
@@ -155,6 +157,7 @@ bool has_attn(const kr_decode_store* s, int kind);   // kr_decode_prefill.cpp: t
 int kr_xm_refuse(kr_decode_store* s);            // kr_decode_prefill.cpp: the "multi_extend_exact_mfma" option's refusals, asked by multi_refuse behind kr_exact_refuse(s, true)
 int kr_xs_refuse(kr_decode_store* s);            // kr_decode_prefill.cpp: the "multi_attn_exact_split" option's refusal, asked by multi_refuse behind kr_mla_xm_refuse(s)
 int kr_mla_xm_refuse(kr_decode_store* s);        // kr_decode_prefill.cpp: the "multi_extend_mla_exact_mfma" option's refusals, asked by multi_refuse behind kr_xm_refuse(s)
+int kr_la_exact_refuse(kr_decode_store* s);      // kr_decode_prefill.cpp: the "multi_extend_la_exact" option's refusal, asked by multi_refuse behind kr_mla_xs_refuse(s)
 int kr_mla_xs_refuse(kr_decode_store* s);        // kr_decode_prefill.cpp: the "multi_mla_exact_split" option's refusal, asked by multi_refuse last, behind kr_xs_refuse(s)
 int kr_spec_pending_fail(kr_decode_store* s);    // KR_ERR_STATE while a verify waits for its commit
 int kr_standalone_cancelled(kr_decode_store* s);

@@ -47,6 +47,7 @@ int multi_refuse(kr_decode_store* s) {
     if (int rc = kr_xm_refuse(s)) return rc;      // "multi_extend_exact_mfma": a check of its own, behind every earlier clause (kr_decode_prefill.cpp)
     if (int rc = kr_mla_xm_refuse(s)) return rc;  // "multi_extend_mla_exact_mfma": the same, behind that one
     if (int rc = kr_xs_refuse(s)) return rc;      // "multi_attn_exact_split": the same, behind that one
+    if (s->opt_multi_extend_la_exact) { if (int rc = kr_mla_xs_refuse(s)) return rc; return kr_la_exact_refuse(s); }      // "multi_extend_la_exact": the same, behind the last one; with the option off the chain ends where it always did
     return kr_mla_xs_refuse(s);                   // "multi_mla_exact_split": the same, behind that one
 }
 int need_slots(kr_decode_store* s) {

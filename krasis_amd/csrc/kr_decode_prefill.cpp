@@ -136,11 +136,17 @@ static KrMultiLaArgs multi_la_args(kr_decode_store* s, size_t li, const Scratch&
         const KrMultiLaCommit& R = M.v_host[(size_t)M.v_la_of[li]];
         m.rec_x = (float*)R.rec_x; m.rec_k = (float*)R.rec_k; m.rec_v = (float*)R.rec_v; m.rec_ge = (float*)R.rec_ge; m.rec_be = (float*)R.rec_be;
     }
+    if (pl.lx_nruns) m.lx_min = s->opt_multi_extend_la_exact_min;      // "multi_extend_la_exact": the run kernels leave the staged runs (multi_lx_args)
     if (pl.lc_nruns) {      // "multi_extend_la_chunk": the runs of >= 64 tokens take the chunked rule, its output rows in B.recur ahead of the gated norm
         m.lc_runs = P.table(pl.lc_runs); m.lc_tiles = P.table(pl.lc_tiles); m.lc_nruns = pl.lc_nruns; m.lc_ntiles = pl.lc_ntiles; m.lc_short = pl.lc_short;
         m.lc_scratch = P.lc_scratch; m.lc_o = B.recur;
     }
     return m;
+}
+// "multi_extend_la_exact": the staged runs' tables and the arena rows their four launches write and read (the same for every linear-attention layer)
+static KrMultiLxArgs multi_lx_args(const Scratch& B, const MultiPass& P) {
+    const KrMultiPlan& pl = P.plan;
+    return KrMultiLxArgs{P.table(pl.lx_runs), P.table(pl.lx_t16), P.table(pl.lx_t8), pl.lx_nruns, pl.lx_t16.n, pl.lx_t8.n, pl.lx_short, B.q, B.k, B.v, B.z, B.gexp, B.beta, B.recur};
 }
 static KrMultiGqaArgs multi_gqa_args(kr_decode_store* s, size_t li, const Scratch& B, const MultiPass& P) {
     const kr_multi_state& M = *s->multi; const DLayer& L = s->layers[li]; const KrMultiPlan& pl = P.plan;
@@ -212,7 +218,8 @@ static int run_layer(kr_decode_store* s, Chunk& cx, size_t li) {
         if (cx.mp) {      // multi-sequence step: every row advances its own slot's conv / recurrent state (kr_multi.hip)
             if (oc != L.nv * L.dv) return kr_fail(KR_ERR_VALUE, "out_proj cols %d != nv*dv", oc);
             const KrMultiLaArgs m = multi_la_args(s, li, B, *cx.mp, qkvz);
-            if (kr_launch_multi_la(m, cx.mp->runs, cx.mp->nruns, Cc, st)) return kr_fail(KR_ERR_VALUE, "unsupported linear-attention geometry for the multi-sequence step");
+            const KrMultiLxArgs x = multi_lx_args(B, *cx.mp);
+            if (kr_launch_multi_la(m, cx.mp->runs, cx.mp->nruns, Cc, st, cx.mp->plan.lx_nruns ? &x : nullptr)) return kr_fail(KR_ERR_VALUE, "unsupported linear-attention geometry for the multi-sequence step");
         } else {
             KrPfmLaArgs a{};
             a.qkvz = qkvz; a.ld_qkvz = nq; a.ba = B.pb; a.ld_ba = nb; a.conv_state = (float*)L.conv_state.p; a.conv_w = (const float*)L.conv_w.p;
@@ -823,6 +830,21 @@ int kr_mla_xs_refuse(kr_decode_store* s) {
     return KR_OK;
 }
 
+// "multi_extend_la_exact" (docs/design/36-multi-extend-la-exact.md): what multi_refuse asks behind kr_mla_xs_refuse, so everything refused before the option existed
+// is refused first and with the same words.  With "multi_extend_la_chunk": two options claim the long runs of the linear-attention layers.  No such layer: an
+// option that silently does nothing is a trap.  A layer outside the staged kernels' geometry (kr_launch_pfm_la's own rule) is an error, not a fall-back to the run
+// kernels.  Nothing to prepare: the kernels' LDS is below the default window.  It stands back where the entry point's paged refusal applies, like its siblings
+int kr_la_exact_refuse(kr_decode_store* s) {
+    if (!s->opt_multi_extend_la_exact || paged_refused(s)) return KR_OK;
+    if (s->opt_multi_extend_la_chunk)
+        return kr_fail(KR_ERR_STATE, "the \"multi_extend_la_exact\" and \"multi_extend_la_chunk\" options both claim the long runs of the linear-attention layers: set one of them to 0");
+    if (!has_attn(s, ATTN_LA)) return kr_fail(KR_ERR_STATE, "the \"multi_extend_la_exact\" option covers linear-attention layers only: this store has none (set the option to 0)");
+    for (const DLayer& L : s->layers)
+        if (L.attn == ATTN_LA && !kr_multi_lx_ok(L.dk, L.dv, L.nk, L.nv, s->weights[L.qkvz_wid]->rows))
+            return kr_fail(KR_ERR_VALUE, "multi_extend_la_exact: linear-attention geometry nk %d nv %d dk %d dv %d not covered (dk 64 / 128, dk <= dv <= 256, dv a multiple of 8, 16-byte in-projection rows, whole value-head groups per key head; set the option to 0 for the run kernels)", L.nk, L.nv, L.dk, L.dv);
+    return KR_OK;
+}
+
 // verify buffers of every linear-attention layer (KR_VERIFY_MAX rows) + the device table the snapshot / rollback kernels walk
 static int spec_prepare(kr_decode_store* s, hipStream_t st) {
     s->spec_la.clear(); s->spec_la_of.assign(s->layers.size(), -1);
@@ -937,6 +959,7 @@ int kr_multi_pass(kr_decode_store* s, int n, int n_final, const int32_t* d_rows,
     o.attn_exact_split = s->opt_multi_attn_exact_split; o.attn_exact_split_min = s->opt_multi_attn_exact_split_min;
     o.mla_exact_split = s->opt_multi_mla_exact_split; o.mla_exact_split_min = s->opt_multi_mla_exact_split_min;
     o.gqa_split_min = s->gqa_split_min; o.mla_split_min = s->mla_split_min;
+    o.extend_la_exact = s->opt_multi_extend_la_exact; o.la_exact_min = s->opt_multi_extend_la_exact_min;
     o.max_seq = M.max_seq; o.fd_chunk = kr_fd_flash_chunk(M.max_seq); o.mla_chunk = kr_mla_flash_decode_chunk(M.max_seq);
     std::vector<KrMultiPlanLayer> pl_layers;
     for (const DLayer& L : s->layers) pl_layers.push_back(KrMultiPlanLayer{L.attn, L.nh, L.nkv, L.hd, L.klr, L.nv});      // ATTN_* are KR_MP_*

@@ -18,6 +18,9 @@ struct KrMultiLaArgs {
     // recorded instead: rec_x [rows][conv_dim] the pre-conv channel inputs, rec_k [rows][nk * dk] the normalised keys (once per key head), rec_v
     // [rows][nv * dv], rec_ge / rec_be [rows][nv] e^g and beta.  Null: the run form above
     float *rec_x, *rec_k, *rec_v, *rec_ge, *rec_be;
+    // "multi_extend_la_exact" (kr_multi_la_exact.hip, docs/design/36-multi-extend-la-exact.md), a non-verify pass with a run of >= lx_min tokens: the two run
+    // kernels leave such a run at once; it takes the staged exact form (KrMultiLxArgs below).  0 (the option is off, a verify pass, or every run is shorter): none
+    int lx_min;
     // "multi_extend_la_chunk" (kr_multi_la_chunk.hip, docs/design/26-multi-extend-la-chunk.md), a non-verify pass with a run of >= KR_M_LC_MIN tokens: lc_runs =
     // lc_nruns x [run, first scratch tile], those runs in call order; lc_tiles = lc_ntiles x [run, sub], their sub-chunks of 64 tokens (kr_lc_tiles.h; scratch tile
     // x is tile x); lc_short = the number of shorter runs; lc_scratch = kr_pfm_la_chunk_scratch_floats(64 lc_ntiles, nv) floats; lc_o [rows][nv * dv] = the delta
@@ -28,11 +31,19 @@ struct KrMultiLaArgs {
 #define KR_M_LC_MIN 64      // = LC_T (kr_lac_dev.h) = KR_LC_TOKENS (kr_lc_tiles.h): kr_pfm_la_chunk_ok's rule, C >= LC_T
 // a run of cnt tokens takes the chunked rule: not a run of the exact run kernels (workgroup-uniform; false whenever lc_runs is null)
 __device__ __forceinline__ bool kr_m_run_chunked(const KrMultiLaArgs& a, int cnt) { return a.lc_runs && cnt >= KR_M_LC_MIN; }
+// a run of cnt tokens takes the staged exact form: not a run of the run kernels (workgroup-uniform; false whenever lx_min is 0)
+__device__ __forceinline__ bool kr_m_run_staged(const KrMultiLaArgs& a, int cnt) { return a.lx_min && cnt >= a.lx_min; }
+// "multi_extend_la_exact": what the staged form needs beside KrMultiLaArgs.  runs = n_runs x [run, first 16-token tile], the runs of >= lx_min tokens in call
+// order; t16 = n16 x [run, t0], their tiles of 16 tokens (conv launch); t8 = n8 x [run, t0], those of 8 tokens (gated norm) -- kr_lc_tiles.h builds all three;
+// n_short = the other runs of the pass (0: the run kernels are not launched); q / k [rows][nv * dk], v / z / o [rows][nv * dv], gexp / beta [rows][nv]: rows of
+// the pass's arena, written and read at the staged runs' rows only (o = the delta rule's output ahead of the gated norm)
+struct KrMultiLxArgs { const int* runs; const int* t16; const int* t8; int n_runs, n16, n8, n_short; float *q, *k, *v, *z, *gexp, *beta, *o; };
 // runs (device) = n_runs x [slot, off, cnt]: run i's tokens are, in order, rows off .. off + cnt - 2 and then row i of qkvz / ba / conv_out / out (cnt 1:
 // row i alone).  The slot's conv and recurrent state are loaded once, carried in registers through the run and stored once.  Slots distinct across runs;
 // max_cnt = a bound on every cnt, at most 1024 (the gate rows the recurrence kernel keeps in LDS).
 // 0: launched; 1: max_cnt out of range or geometry not covered (kd 4 is the caller's check; dk 64 / 128, dv <= 256, dv % 8 == 0)
-int kr_launch_multi_la(const KrMultiLaArgs& a, const int* runs, int n_runs, int max_cnt, hipStream_t st);
+// x set ("multi_extend_la_exact", a.lx_min its threshold): the run kernels over the shorter runs (none: not launched), the staged form over the others
+int kr_launch_multi_la(const KrMultiLaArgs& a, const int* runs, int n_runs, int max_cnt, hipStream_t st, const KrMultiLxArgs* x = nullptr);
 // the pass row of token t < cnt of run i (kernels of kr_multi.hip and kr_multi_sample.hip)
 __device__ __forceinline__ int kr_m_run_row(int i, int off, int cnt, int t) { return t == cnt - 1 ? i : off + t; }
 // the chunked rule of "multi_extend_la_chunk" (after the exact run kernels, which kr_launch_multi_la skips or lets leave those runs): the geometry test
@@ -41,6 +52,12 @@ __device__ __forceinline__ int kr_m_run_row(int i, int off, int cnt, int t) { re
 int kr_multi_lc_ok(int dk, int dv, int nk, int nv, int ld_qkvz);
 int kr_multi_lc_prepare();
 int kr_launch_multi_la_chunk(const KrMultiLaArgs& a, const int* runs, hipStream_t st);
+// the staged exact form of "multi_extend_la_exact" (kr_multi_la_exact.hip): the geometry test (kr_launch_pfm_la's: dk 64 / 128, dk <= dv <= 256, dv % 8 == 0,
+// 16-byte in-projection rows, nv = nk hr); what the launcher checks of its arguments, asked before anything of the layer is queued; conv over (nk, n16), the
+// carried conv inputs over (channels, n_runs), the delta rule over (nv, n_runs), the gated norm over (nv, n8).  0: launched; 1: something not covered
+int kr_multi_lx_ok(int dk, int dv, int nk, int nv, int ld_qkvz);
+int kr_multi_lx_args_ok(const KrMultiLaArgs& a, const KrMultiLxArgs& x);
+int kr_launch_multi_la_exact(const KrMultiLaArgs& a, const KrMultiLxArgs& x, const int* runs, hipStream_t st);
 
 // commit of a verify pass (docs/design/18-multi-verify.md): one linear-attention layer's slot states and the records its verify-form launch left.  A table
 // of these lives on the device (kr_multi_state::v_tab)

@@ -34,6 +34,7 @@ __global__ void __launch_bounds__(256) kr_multi_la_conv_kernel(const KrMultiLaAr
     else { const int vh = (ch - 2 * key_dim) / dv, e = (ch - 2 * key_dim) % dv; kh = vh / hr; off = 2 * dk + (vh % hr) * dv + e; }
     const int slot = runs[3 * i], row0 = runs[3 * i + 1], cnt = runs[3 * i + 2];
     if constexpr (!VERIFY) if (kr_m_run_chunked(a, cnt)) return;      // "multi_extend_la_chunk": the chunked rule's run (workgroup-uniform; this kernel has no barrier; never in a verify pass)
+    if constexpr (!VERIFY) if (kr_m_run_staged(a, cnt)) return;       // "multi_extend_la_exact": the staged form's run (the same)
     const float* xin = a.qkvz + (size_t)kh * group_dim + off;
     float4* cs = reinterpret_cast<float4*>(a.conv_state + (size_t)slot * a.conv_stride) + ch;
     float4 s = *cs;
@@ -65,6 +66,7 @@ __global__ void __launch_bounds__(256) kr_multi_la_recur_kernel(const KrMultiLaA
     const int key_dim = a.nk * DK, conv_dim = 2 * key_dim + a.nv * dv, group_dim = 2 * DK + 2 * dv * hr;
     const int slot = runs[3 * ri], row0 = runs[3 * ri + 1], cnt = runs[3 * ri + 2];
     if constexpr (!VERIFY) if (kr_m_run_chunked(a, cnt)) return;      // "multi_extend_la_chunk": the chunked rule's run (workgroup-uniform, ahead of every barrier; never in a verify pass)
+    if constexpr (!VERIFY) if (kr_m_run_staged(a, cnt)) return;       // "multi_extend_la_exact": the staged form's run (the same)
     for (int t = j; t < cnt; t += dv) {      // gates (decode.rs:3891-3901)
         const float* ba = a.ba + (size_t)kr_m_run_row(ri, row0, cnt, t) * a.ld_ba;
         const float b_raw = ba[kh * 2 * hr + r], a_p = ba[kh * 2 * hr + hr + r];
@@ -201,7 +203,7 @@ void kr_launch_multi_la_commit(const KrMultiLaCommit* tab, int n_la, bool has64,
     if (has64) hipLaunchKernelGGL(kr_multi_la_commit_kernel<64>, dim3(nv_max, n_runs, n_la), dim3(dv_max), 0, st, tab, runs, n_keep);
 }
 
-int kr_launch_multi_la(const KrMultiLaArgs& a, const int* runs, int n_runs, int max_cnt, hipStream_t st) {
+int kr_launch_multi_la(const KrMultiLaArgs& a, const int* runs, int n_runs, int max_cnt, hipStream_t st, const KrMultiLxArgs* x) {
     if (max_cnt < 1 || max_cnt > KR_M_RUN_MAX) return 1;
     if ((a.dk != 64 && a.dk != 128) || a.dv < 8 || a.dv > 256 || a.dv % 8 || a.nv != a.nk * a.hr) return 1;
     const int conv_dim = 2 * a.nk * a.dk + a.nv * a.dv;
@@ -216,12 +218,16 @@ int kr_launch_multi_la(const KrMultiLaArgs& a, const int* runs, int n_runs, int 
     // "multi_extend_la_chunk", a pass with a run of >= 64 tokens: the run kernels over the shorter runs (none: not launched), then the chunked rule over the
     // others.  Every check that can refuse the layer stands ahead of the first launch, which advances slot state: a layer fails whole
     if (a.lc_runs && (!kr_multi_lc_ok(a.dk, a.dv, a.nk, a.nv, a.ld_qkvz) || !a.lc_tiles || !a.lc_scratch || !a.lc_o || a.lc_nruns < 1 || a.lc_ntiles < a.lc_nruns)) return 1;
+    // "multi_extend_la_exact", a pass with a run of >= a.lx_min tokens: the same shape -- the run kernels over the shorter runs, the staged form over the others
+    if ((x != nullptr) != (a.lx_min != 0) || (x && (a.lc_runs || !kr_multi_lx_args_ok(a, *x)))) return 1;
+    if (x && x->n_short == 0) return kr_launch_multi_la_exact(a, *x, runs, st);      // every run is staged: the run kernels are not launched
     if (!a.lc_runs || a.lc_short > 0) {
         hipLaunchKernelGGL(kr_multi_la_conv_kernel<false>, cg, dim3(256), 0, st, a, runs);
         if (a.dk == 128) hipLaunchKernelGGL((kr_multi_la_recur_kernel<128, false>), rg, dim3(a.dv), 0, st, a, runs);
         else hipLaunchKernelGGL((kr_multi_la_recur_kernel<64, false>), rg, dim3(a.dv), 0, st, a, runs);
     }
     if (a.lc_runs) return kr_launch_multi_la_chunk(a, runs, st);
+    if (x) return kr_launch_multi_la_exact(a, *x, runs, st);
     return 0;
 }
 

@@ -24,6 +24,7 @@ struct KrMultiPlanOpts {
     bool mla_fast, extend_flash, extend_mla_flash, extend_la_chunk, extend_exact_mfma, extend_mla_exact_mfma, attn_exact_split, mla_exact_split;
     int attn_exact_split_min, mla_exact_split_min, gqa_split_min, mla_split_min;
     int max_seq, fd_chunk, mla_chunk;      // the slots' capacity; kr_fd_flash_chunk(max_seq) and kr_mla_flash_decode_chunk(max_seq): the rules stay beside their kernels
+    bool extend_la_exact; int la_exact_min;      // "multi_extend_la_exact" and its threshold "multi_extend_la_exact_min" (docs/design/36-multi-extend-la-exact.md)
 };
 struct KrMultiPlanLayer { int kind, nh, nkv, hd, klr, nv; };
 struct KrMultiPlanRows { int n, n_final, max_pos; bool verify; const int32_t* counts; const int32_t* positions; };      // counts / positions: host, may be null (a plain step)
@@ -40,11 +41,13 @@ struct KrMultiPlan {
     int n_unit = 0;                                                  // runs of one token
     int kv_end = 0; size_t xm_inv_bytes = 0, xm_tmax_bytes = 0;      // matrix-core passes: one past the largest position a run reads; 1 / sum and row maxima per 32 positions
     int lc_nruns = 0, lc_ntiles = 0, lc_short = 0; size_t lc_scratch_floats = 0;      // chunked delta rule: runs of >= 64 tokens, their sub-chunks, the other runs
+    int lx_nruns = 0, lx_short = 0;                                  // exact staged linear attention: runs of >= la_exact_min tokens, the runs left to the run kernels
     std::vector<int32_t> tables;                                     // every table of the pass, each at a multiple of four ints
     KrMpSpan pf[8], xa[8], xc[8];                                    // per tile width 1 << w tokens: flash query tiles; matrix-core scores and P.V tiles (GQA and MLA layers alike)
     struct Mf { int nh; KrMpSpan t; };
     std::vector<Mf> mf;                                              // per head count among the MLA layers: flash query-row tiles
     KrMpSpan lc_runs, lc_tiles;                                      // chunked runs [run, first tile] and their sub-chunks [run, sub]
+    KrMpSpan lx_runs, lx_t16, lx_t8;                                 // staged runs [run, first 16-token tile], their tiles of 16 and of 8 tokens [run, t0]
 };
 
 inline int kr_mp_log2(int t) { int w = 0; while ((1 << w) < t) w++; return w; }      // tile widths are powers of two up to 128
@@ -151,6 +154,15 @@ inline int kr_multi_plan(const KrMultiPlanOpts& o, const KrMultiPlanLayer* layer
         if (ls.n_runs) {
             p.lc_runs = kr_mp_append(p.tables, lr); p.lc_tiles = kr_mp_append(p.tables, lt);
             p.lc_nruns = ls.n_runs; p.lc_ntiles = ls.n_tiles; p.lc_short = ls.n_short; p.lc_scratch_floats = kr_lc_scratch_floats(ls.n_tiles, nv_max);
+        }
+    }
+    // exact staged linear attention (36): one set of tables for every linear-attention layer -- the staged runs, their conv tiles, their gated-norm tiles
+    if (o.extend_la_exact && !r.verify && r.counts && nv_max) {
+        std::vector<int32_t> xr, x16, x8;
+        const KrLxStats xs = kr_lx_build(r.n_final, r.counts, o.la_exact_min, xr, x16, x8);
+        if (xs.n_runs) {
+            p.lx_runs = kr_mp_append(p.tables, xr); p.lx_t16 = kr_mp_append(p.tables, x16); p.lx_t8 = kr_mp_append(p.tables, x8);
+            p.lx_nruns = xs.n_runs; p.lx_short = xs.n_short;
         }
     }
     return p.rc;

@@ -351,6 +351,17 @@ class CpuDecodeStore:
         independent of "multi_extend_exact_mfma" and "multi_extend_la_chunk".  Refused by the batched calls together with
         "multi_extend_mla_flash" (both claim the same runs), on a store without an MLA layer, and on an MLA layer whose head count does not divide
         32 (docs/design/29-multi-extend-mla-exact-mfma.md).
+        "multi_extend_la_exact" (default 0): with 1 a run of "multi_extend_la_exact_min" or more tokens entering a slot (extend_multi, prefill_slot)
+        takes the staged form of the exact prompt pass in its linear-attention layers -- conv, gates and L2 norms parallel over tokens, the delta
+        rule alone in the serial loop with its two chains interleaved, the gated RMSNorm parallel over tokens -- where the run kernels walk the run
+        with five barriers per token.  Every call gives, bit for bit, what it gives with the option off: ids, logits, every conv input and
+        recurrent state, every K / V or latent row, however the stream is cut and whatever rows share the pass, on flat, paged and forked slots.
+        Only the speed of the admission changes.  Shorter runs and unit rows keep the run kernels; verify passes, GQA and MLA layers are
+        untouched, and the option composes with the attention options of the other layer kinds.  Refused by the batched calls together with
+        "multi_extend_la_chunk" (both claim the long runs), on a store without a linear-attention layer, and on a linear-attention layer outside
+        dk 64 / 128, dk <= dv <= 256 (docs/design/36-multi-extend-la-exact.md).
+        "multi_extend_la_exact_min" (default 8, 2 .. 1024 -- outside: ValueError): the shortest run that is staged; both forms give the same
+        bits, the value is a measured one.
         "multi_attn_exact_split" (default 0): with 1 every batched pass over slots (step_multi, the unit rows of extend_multi / prefill_slot, all token
         rows of verify_multi / verify_multi_sample, every pass of the generate_multi* loops) launches the exact per-slot GQA attention as three
         kernels -- scores spread over tiles of 256 positions, the softmax one wave per (row, head), P.V spread over heads and slices of 32 outputs
@@ -649,7 +660,10 @@ class CpuDecodeStore:
         After set_option("multi_extend_mla_exact_mfma", 1) a run of two or more tokens takes the exact MLA prompt pass's matrix-core scores,
         softmax and P.V over its slot in the MLA layers (docs/design/29-multi-extend-mla-exact-mfma.md): again no bit changes, whatever the cut.
         Runs of one token keep their kernel: with "multi_mla_fast" also set a mixed pass gives its unit rows that option's bits and its runs of
-        >= 2 the exact bits."""
+        >= 2 the exact bits.
+        After set_option("multi_extend_la_exact", 1) a run of "multi_extend_la_exact_min" or more tokens takes the staged form of the exact
+        prompt pass in its linear-attention layers (docs/design/36-multi-extend-la-exact.md): no bit changes -- the call still equals that many
+        decode_step calls, whatever the cut; shorter runs and unit rows keep the run kernels."""
         if len(token_lists) != len(slots) or len(positions) != len(slots):
             raise ValueError(f"{len(slots)} slots, {len(token_lists)} token lists, {len(positions)} positions")
         return self._step_multi(self._lib.kr_decode_extend_multi, slots, [len(run) for run in token_lists], [int(t) for run in token_lists for t in run],
@@ -739,7 +753,9 @@ class CpuDecodeStore:
         chunk of one token keeps its kernel (with "multi_attn_fast" set: that option's bits for that token).  After
         set_option("multi_extend_mla_exact_mfma", 1) the same holds for the MLA layers (see extend_multi): the slot is bit for bit what it is with
         the option off; a last chunk of one token keeps its kernel (with "multi_mla_fast" set: that option's bits for that token, a unit row,
-        while the chunks of two or more tokens carry the exact bits)."""
+        while the chunks of two or more tokens carry the exact bits).  After set_option("multi_extend_la_exact", 1) every chunk of
+        "multi_extend_la_exact_min" or more tokens takes the staged exact form in its linear-attention layers (see extend_multi): the slot is bit
+        for bit what it is with the option off; a shorter last chunk keeps the run kernels."""
         from ._lib import KR_EXTEND_MAX_TOKENS
         chunk = KR_EXTEND_MAX_TOKENS if chunk is None else int(chunk)
         if not 1 <= chunk <= KR_EXTEND_MAX_TOKENS:

@@ -40,6 +40,14 @@ off and on call by call.  Two more legs, where the query tiles are mostly empty:
 option alternates off and on call by call.  --off-only, --profile and --admission as under --flash.
 
     python tools/probes/multi_extend_throughput.py [out.txt] --mla-exact-mfma [--off-only] [--profile [--admission]]
+
+--la-exact: the legs of --exact-mfma for the "multi_extend_la_exact" option (docs/design/36-multi-extend-la-exact.md), which changes no bit:
+"multi_extend_exact_mfma" stays on throughout, "multi_extend_la_exact_min" is 2 so that every run of the short-run legs is staged, and the new option
+alternates off and on call by call.  The short-run legs: the 63 decode slots each take a run of 2, 8 and 16 tokens at position 512, and one slot alone takes a
+run of 2, 8, 16 and 64 tokens there -- what the default of the threshold is read from.  --off-only, --profile and --admission as under --flash (--off-only
+never names the new options, so it also runs against a library built from the commit before them).
+
+    python tools/probes/multi_extend_throughput.py [out.txt] --la-exact [--off-only] [--profile [--admission]]
 """
 import os
 import statistics
@@ -61,7 +69,7 @@ def timed(fn, warm, reps):
     return statistics.median(ts[warm:])
 
 
-def flash_legs(out_path, off_only, profile, opt="multi_extend_flash", fixed=(), v2lite=False, short_runs=()):
+def flash_legs(out_path, off_only, profile, opt="multi_extend_flash", fixed=(), v2lite=False, short_runs=(), single_runs=(), opt_values=()):
     """option `opt` off / on, alternating call by call: admission (prefill_slot) and the mixed pass, flat and paged; the options of `fixed` stay on"""
     kv = 4096 + 160
     eng, st, keep = bench.build_v2lite(0, 0, 27, rope_len=kv, kv_fp8=True) if v2lite else bench.build_qcn(0, 0, 48, rope_len=kv, kv_fp8=True)
@@ -79,6 +87,9 @@ def flash_legs(out_path, off_only, profile, opt="multi_extend_flash", fixed=(), 
     legs = (0,) if off_only else (0, 1)
     for f in fixed:
         st.set_option(f, 1)
+    if not off_only:
+        for name, value in opt_values:
+            st.set_option(name, value)
 
     def option(v):
         if not off_only:
@@ -120,6 +131,8 @@ def flash_legs(out_path, off_only, profile, opt="multi_extend_flash", fixed=(), 
                  (f"mixed: {N_DECODE} rows at {P_DECODE} + a {CHUNK}-token chunk", mixed, 2, 6)]
         for k in short_runs:      # every decode slot takes a run of k tokens at its position: query tiles that are mostly empty
             cases.append((f"{N_DECODE} runs of {k} tokens at {P_DECODE}", lambda i, k=k: st.extend_multi(rows, [toks(k, i + b) for b in rows], [P_DECODE] * N_DECODE), 2, 6))
+        for k in single_runs:     # one decode slot alone takes a run of k tokens at its position
+            cases.append((f"1 run of {k} tokens at {P_DECODE}", lambda i, k=k: st.extend_multi(rows[:1], [toks(k, i)], [P_DECODE]), 2, 6))
         for name, fn, warm, reps in cases:
             rounds = [alternate(fn, warm, reps) for _ in range(3)]
             for v in legs:
@@ -139,6 +152,9 @@ def main():
         return flash_legs(out_path, "--off-only" in sys.argv, profile, "multi_extend_mla_exact_mfma", v2lite=True, short_runs=(2, 8))
     if "--exact-mfma" in sys.argv:
         return flash_legs(out_path, "--off-only" in sys.argv, profile, "multi_extend_exact_mfma", short_runs=(2, 8))
+    if "--la-exact" in sys.argv:
+        return flash_legs(out_path, "--off-only" in sys.argv, profile, "multi_extend_la_exact", ("multi_extend_exact_mfma",), short_runs=(2, 8, 16), single_runs=(2, 8, 16, 64),
+                          opt_values=(("multi_extend_la_exact_min", 2),))
     if "--la-chunk" in sys.argv:
         return flash_legs(out_path, "--off-only" in sys.argv, profile, "multi_extend_la_chunk", ("multi_extend_flash",))
     if "--flash" in sys.argv:
