@@ -640,6 +640,39 @@ int kr_sample_runs(const float* logits, int n, const int32_t* counts, const int3
    (the "multi_sample_loop" form). */
 int kr_sample_rows(const float* logits, int n, int vocab, const float* temperature, const int* top_k, const float* top_p,
                    const float* presence_penalty, const uint32_t* seen, uint64_t* rng_state, int32_t* tokens_out, int force_loop);
+/* test aid (no reference counterpart; docs/design/32-multi-pass-plan.md): which forms the multi-row passes of this store took.  Host-side counters held in the
+   store: no device work, no launch reads them, nothing on the path of kr_decode_step touches them.  The batched pass over device slots counts once per pass
+   that was queued without an error, from the pass's plan (kr_multi_plan.h), its few-row flag and the store's options -- exactly the values the sections of the
+   layer loop branch on, so a counter that moved means the section took that branch; a pass that failed counts nothing.  The two position-split counters
+   count a pass only where the three launches exist: not for flash-decode rows, and under a flash or matrix-core run form only if the pass holds a unit row,
+   since the runs then leave the per-row kernels (a pass of runs alone launches no split whatever the plan's flag says).  The store's own prompt / verify
+   passes count where the few-row form is decided for the pass.  Writes the first n counters to out (0 <= n <= KR_MPC_COUNT; out may be NULL with n 0), then
+   clears all of them if reset != 0.  KR_ERR_VALUE: a null store, a null out with n > 0, n out of range -- a caller that names more counters than the library
+   has learns it here. */
+enum {
+    KR_MPC_PASSES = 0,      /* batched passes over slots (every slot entry point; a generation loop counts each of its passes) */
+    KR_MPC_VERIFY,          /* ... that were verify passes */
+    KR_MPC_FEW,             /* ... that took the few-row kernels ("pass_few_rows") */
+    KR_MPC_XS_SPLIT,        /* ... whose per-row GQA attention was the three position-split launches ("multi_attn_exact_split") */
+    KR_MPC_MLA_XS_SPLIT,    /* ... the same for MLA ("multi_mla_exact_split") */
+    KR_MPC_GQA_XM,          /* ... whose runs of >= 2 tokens took the exact matrix-core passes in the GQA layers ("multi_extend_exact_mfma") */
+    KR_MPC_MLA_XM,          /* ... in the MLA layers ("multi_extend_mla_exact_mfma") */
+    KR_MPC_LX,              /* ... with at least one staged linear-attention run ("multi_extend_la_exact") */
+    KR_MPC_LX_RUNS,         /* the staged runs of those passes, summed */
+    KR_MPC_LX_SHORT,        /* the runs those passes left to the run kernels, summed */
+    KR_MPC_FD,              /* passes whose unit rows took split-KV flash-decode in the GQA layers ("multi_attn_fast*") */
+    KR_MPC_MLA_FD,          /* ... in the MLA layers ("multi_mla_fast") */
+    KR_MPC_GQA_FLASH,       /* passes whose runs took the flash run kernels in the GQA layers ("multi_extend_flash") */
+    KR_MPC_MLA_FLASH,       /* ... in the MLA layers ("multi_extend_mla_flash") */
+    KR_MPC_LC,              /* passes with at least one chunked delta-rule run ("multi_extend_la_chunk") */
+    KR_MPC_RUNS,            /* non-verify passes with a run of >= 2 tokens (the plan's any_run): the passes a run option can apply to */
+    KR_MPC_GGUF_EXACT,      /* passes over a store with native-GGUF experts under "gguf_exact_pass" */
+    KR_MPC_GGUF_GROUPED,    /* ... that took the grouped form ("gguf_exact_grouped" 1), not the streaming kernels */
+    KR_MPC_SEQ_PASSES,      /* prompt / verify passes of the store's own sequence (kr_decode_prefill*, kr_decode_verify) */
+    KR_MPC_SEQ_FEW,         /* ... that took the few-row kernels */
+    KR_MPC_COUNT
+};
+int kr_decode_multi_path_counts(kr_decode_store* s, int64_t* out, int n, int reset);
 
 /* ---- stand-alone CpuDecodeStore operators (decode.rs:328-1086).  Every pointer may be a host or a device pointer; host buffers are staged and
  * the call returns after the results are back.  Bit-identical to the reference methods (tests/test_standalone_ops_gpu.py against the oracle's

@@ -35,7 +35,7 @@ SYMBOLS = [
     "kr_decode_extend_multi", "kr_decode_verify_multi", "kr_decode_commit_multi", "kr_decode_generate_multi_lookup",
     "kr_decode_verify_multi_sample", "kr_decode_generate_multi_lookup_sample", "kr_decode_slot_sampler_get", "kr_sample_runs",
     "kr_decode_slots_create_paged", "kr_decode_slot_trim", "kr_decode_slots_pages",
-    "kr_decode_slot_fork", "kr_decode_slot_page_ids", "kr_decode_slots_page_stride", "kr_copy_pages",
+    "kr_decode_slot_fork", "kr_decode_slot_page_ids", "kr_decode_slots_page_stride", "kr_copy_pages", "kr_decode_multi_path_counts",
 ]
 TOKEN_CB = C.CFUNCTYPE(C.c_int, C.c_int, C.c_int, C.c_void_p)      # kr_token_cb(token, finish_reason, user) -> continue?
 
@@ -185,6 +185,7 @@ def load_library() -> C.CDLL:
     lib.kr_decode_slot_fork.argtypes = [vp, ci, ci, vp, ci]
     lib.kr_decode_slot_page_ids.argtypes = [vp, ci, vp, vp]
     lib.kr_decode_slots_page_stride.argtypes = [vp, vp]
+    lib.kr_decode_multi_path_counts.argtypes = [vp, vp, ci, ci]
     lib.kr_copy_pages.argtypes = [vp, C.c_size_t, ci, ci, ci, vp, vp, vp, ci]
     lib.kr_decode_slot_save.argtypes = [vp, ci, ci]
     lib.kr_decode_slot_load.argtypes = [vp, ci, ci]

@@ -114,6 +114,7 @@ struct kr_decode_store {
     int opt_pass_few_rows = 0;                   // kr_decode_set_option("pass_few_rows"): a multi-row pass of at most opt_pass_few_rows_max token rows (prefill / verify: n_tokens; slot entry points: the sum of the counts) runs its projections on the few-row streaming matvec (kr_rows_matvec.hip) and its INT4 / INT8 routed experts as the decode step's three launches -- bit for bit what it gives without the option (docs/design/34-pass-few-rows.md); KR_GEMM_FAST passes and larger passes keep their GEMMs
     int opt_pass_few_rows_max = 16;              // kr_decode_set_option("pass_few_rows_max"), 1 .. 16: the most token rows of a pass that takes the few-row kernels (a measured default: profiles/pass_few_rows.txt)
     int opt_pass_few_rows_group = 0;             // kr_decode_set_option("pass_few_rows_group"), 0 .. 16: the most rows a workgroup of the few-row matvec holds, 0 = chosen per launch (kr_rows_plan.h; A/B and test hook, same bits)
+    int64_t path_counts[KR_MPC_COUNT] = {};     // kr_decode_multi_path_counts: which forms the multi-row passes took (host-side test aid; written where a pass has been queued, read by nothing)
     int opt_gen_lookahead = 0;                  // kr_decode_set_option("generate_lookahead"): generate_batch feeds the sampled token back ON THE DEVICE and queues step i + 1 before the host has read token i
     int opt_ep_graph = 0;                         // kr_decode_set_option("ep_graph"): expert-parallel decode over RCCL replays a captured graph (the all-reduce is captured with the kernels)
     uint64_t ep_generation_seen = 0;               // kr_engine::ep_generation at the last step: a new / destroyed communicator invalidates the graph and restarts the warm-up

@@ -575,6 +575,7 @@ static int prefill_impl(kr_decode_store* s, const int32_t* tokens, int n_tokens,
     }
     const auto t_enqueue = std::chrono::steady_clock::now();
     const bool few = pass_few_rows(s, n_tokens);      // decided for the pass, never per chunk
+    s->path_counts[KR_MPC_SEQ_PASSES]++; s->path_counts[KR_MPC_SEQ_FEW] += few;      // kr_decode_multi_path_counts (host-side test aid)
     std::vector<Chunk> chunks(n_chunks);
     for (int c = 0; c < n_chunks; c++) {
         Chunk& cx = chunks[c];
@@ -946,6 +947,28 @@ extern "C" int kr_decode_commit(kr_decode_store* s, int n_keep) {
 // sections leave records instead of state, docs/design/18-multi-verify.md).  Engine buffer set KR_PF_MAX_DEPTH - 1; the
 // caller has ordered this pass after everything the store queued.
 // ------------------------------------------------------------------------------------------------
+// kr_decode_multi_path_counts: one batched pass that was queued, by the values the sections of run_layer branch on -- the plan, the pass's few-row flag, the
+// GGUF bits of the store.  The position split is counted where its three launches exist: the launchers (kr_multi.hip) give flash-decode rows the flash-decode
+// kernels whatever the flag says, and under the flash or matrix-core run forms they launch the per-row attention for the unit rows only.  Host only
+static void multi_path_count(kr_decode_store* s, const KrMultiPlan& pl, bool verify, bool few) {
+    int64_t* c = s->path_counts;
+    c[KR_MPC_PASSES]++; c[KR_MPC_VERIFY] += verify; c[KR_MPC_FEW] += few;
+    c[KR_MPC_XS_SPLIT] += pl.xs_split && !pl.fd_chunks && (pl.gqa_runs == KR_MP_RUNS_ROWS || pl.n_unit > 0);
+    c[KR_MPC_MLA_XS_SPLIT] += pl.mla_xs_split && !pl.mla_chunks && (pl.mla_runs == KR_MP_RUNS_ROWS || pl.n_unit > 0);
+    c[KR_MPC_GQA_XM] += pl.gqa_runs == KR_MP_RUNS_XM; c[KR_MPC_MLA_XM] += pl.mla_runs == KR_MP_RUNS_XM;
+    c[KR_MPC_LX] += pl.lx_nruns > 0; c[KR_MPC_LX_RUNS] += pl.lx_nruns; c[KR_MPC_LX_SHORT] += pl.lx_short;
+    c[KR_MPC_FD] += pl.fd_chunks > 0; c[KR_MPC_MLA_FD] += pl.mla_chunks > 0;
+    c[KR_MPC_GQA_FLASH] += pl.gqa_runs == KR_MP_RUNS_FLASH; c[KR_MPC_MLA_FLASH] += pl.mla_runs == KR_MP_RUNS_FLASH; c[KR_MPC_LC] += pl.lc_nruns > 0;
+    c[KR_MPC_RUNS] += pl.any_run;
+    if (has_gguf_moe(s) && (gguf_exact_bits(s) & KR_PF_SET_GGUF_EXACT)) { c[KR_MPC_GGUF_EXACT]++; c[KR_MPC_GGUF_GROUPED] += !(gguf_exact_bits(s) & KR_PF_SET_GGUF_STREAM); }
+}
+extern "C" int kr_decode_multi_path_counts(kr_decode_store* s, int64_t* out, int n, int reset) {
+    if (!s || n < 0 || n > KR_MPC_COUNT || (n > 0 && !out)) return kr_fail(KR_ERR_VALUE, "kr_decode_multi_path_counts: null store, null out or n %d outside [0, %d]", n, (int)KR_MPC_COUNT);
+    for (int i = 0; i < n; i++) out[i] = s->path_counts[i];
+    if (reset) for (int64_t& c : s->path_counts) c = 0;
+    return KR_OK;
+}
+
 int kr_multi_pass(kr_decode_store* s, int n, int n_final, const int32_t* d_rows, const int32_t* d_runs, int max_pos, hipStream_t st, bool verify,
                   const int32_t* h_counts, const int32_t* h_positions) {
     kr_multi_state& M = *s->multi;
@@ -999,10 +1022,13 @@ int kr_multi_pass(kr_decode_store* s, int n, int n_final, const int32_t* d_rows,
     const MultiPass mp{plan, (const int32_t*)M.tiles.p, (float*)M.lc_scratch.p, (float*)M.xm_rows.p, (float*)((char*)M.xm_rows.p + plan.xm_inv_bytes),
                        d_rows, d_rows + 2 * n, d_runs, n_final, verify};
     Chunk cx{};
-    cx.B = pf_carve(Lo, (char*)M.scratch.p); cx.B.H = s->hidden; cx.B.few = pass_few_rows(s, n); cx.B.few_group = s->opt_pass_few_rows_group; cx.scores = nullptr; cx.tok = d_rows + n; cx.Cc = n; cx.pos0 = 0; cx.set = KR_PF_MAX_DEPTH - 1;
+    const bool few = pass_few_rows(s, n);
+    cx.B = pf_carve(Lo, (char*)M.scratch.p); cx.B.H = s->hidden; cx.B.few = few; cx.B.few_group = s->opt_pass_few_rows_group; cx.scores = nullptr; cx.tok = d_rows + n; cx.Cc = n; cx.pos0 = 0; cx.set = KR_PF_MAX_DEPTH - 1;
     cx.first = true; cx.add_is_emb = true; cx.st = st; cx.mp = &mp;
     for (size_t l = 0; l < s->layers.size(); l++)
         if (int rc = run_layer(s, cx, l)) return rc;
     cx.Cc = plan.n_logits;
-    return final_rows(s, cx, (float*)M.logits.p);
+    if (int rc = final_rows(s, cx, (float*)M.logits.p)) return rc;
+    multi_path_count(s, plan, mp.verify, few);
+    return KR_OK;
 }

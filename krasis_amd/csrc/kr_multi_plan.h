@@ -39,6 +39,7 @@ struct KrMultiPlan {
     bool xs_split = false, mla_xs_split = false;
     int gqa_runs = KR_MP_RUNS_ROWS, mla_runs = KR_MP_RUNS_ROWS;
     int n_unit = 0;                                                  // runs of one token
+    bool any_run = false;                                            // a non-verify pass with counts and positions holds a run of >= 2 tokens: what the run options apply to
     int kv_end = 0; size_t xm_inv_bytes = 0, xm_tmax_bytes = 0;      // matrix-core passes: one past the largest position a run reads; 1 / sum and row maxima per 32 positions
     int lc_nruns = 0, lc_ntiles = 0, lc_short = 0; size_t lc_scratch_floats = 0;      // chunked delta rule: runs of >= 64 tokens, their sub-chunks, the other runs
     int lx_nruns = 0, lx_short = 0;                                  // exact staged linear attention: runs of >= la_exact_min tokens, the runs left to the run kernels
@@ -85,7 +86,7 @@ inline int kr_multi_plan(const KrMultiPlanOpts& o, const KrMultiPlanLayer* layer
     }
     // the one scan of the runs: is there a run of >= 2 tokens, how many have one, and the longest position among those.  A verify pass, or a caller that gave
     // no counts / positions (a plain step): no run option applies
-    bool any_run = false; int unit_pos = -1;
+    bool& any_run = p.any_run; int unit_pos = -1;
     p.n_unit = r.n_final;
     if (!r.verify && r.counts && r.positions) {
         p.n_unit = 0;

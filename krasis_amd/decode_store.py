@@ -739,6 +739,18 @@ class CpuDecodeStore:
         check(self._lib.kr_decode_slot_sampler_get(self._h, slot, seen.ctypes.data, C.byref(rng)))
         return seen, rng.value
 
+    MULTI_PATH_COUNTS = ("passes", "verify", "few", "xs_split", "mla_xs_split", "gqa_xm", "mla_xm", "lx", "lx_runs", "lx_short", "fd", "mla_fd",
+                         "gqa_flash", "mla_flash", "lc", "runs", "gguf_exact", "gguf_grouped", "seq_passes", "seq_few")      # KR_MPC_* of krasis_hip.h, in order
+
+    def multi_path_counts(self, reset: bool = False) -> dict:
+        """kr_decode_multi_path_counts (test aid): which forms the multi-row passes of this store took so far -- host-side counters, one count per batched
+        pass over slots that was queued without an error, read from the pass's plan, its few-row flag and the GGUF option bits (the values the layer loop
+        branches on); "seq_passes" / "seq_few" count the store's own prompt / verify passes.  reset=True clears them after the read."""
+        self._need()
+        out = (C.c_int64 * len(self.MULTI_PATH_COUNTS))()
+        check(self._lib.kr_decode_multi_path_counts(self._h, out, len(out), 1 if reset else 0))
+        return dict(zip(self.MULTI_PATH_COUNTS, (int(x) for x in out)))
+
     def prefill_slot(self, slot: int, tokens: Sequence[int], start_pos: int = 0, chunk: Optional[int] = None) -> int:
         """A prompt straight into a slot: extend_multi over chunks of `chunk` tokens (default KR_EXTEND_MAX_TOKENS).  The slot afterwards equals
         prefill(tokens, start_pos) + save_slot bit for bit, and the store's own sequence, logits and last token are never touched.  Returns the greedy id

@@ -111,9 +111,12 @@ def test_each_run_alone_equals_the_exact_prompt_pass(model):
     st.create_slots(len(CASES), KV_MAX)
     for s, ref in enumerate(refs):
         _fill(st, d, ref["prefix"], [s])
+    assert st.multi_path_counts(reset=True)["lx"] == 0      # not vacuous: nothing was staged while the option was off, every call below is (multi_path_counts)
     _on(st)
     out = [st.extend_multi([s], [ref["run"]], [ref["pos0"]], logits=True) for s, ref in enumerate(refs)]
+    took = st.multi_path_counts()
     _off(st)
+    assert (took["lx"], took["lx_runs"], took["lx_short"]) == (len(CASES), len(CASES), 0), took
     for s, (ref, (ids, lg)) in enumerate(zip(refs, out)):
         _assert_run(st, d, ref, s, ids[0], lg[0], ("case", CASES[s]))
 

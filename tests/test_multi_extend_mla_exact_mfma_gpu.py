@@ -124,7 +124,16 @@ def test_runs_equal_option_off_and_single_sequence_prefill(key, slot_seq):
         ids, lg = st.extend_multi(SLOTS, [r["run"] for r in refs], [r["pos0"] for r in refs], logits=True)
         return ids, lg, [_state(st, d, s, r["end"]) for r, s in zip(refs, SLOTS)]
 
-    off, on = _off_on(st, scenario)
+    took = []      # not vacuous: the pass took the option's form in the on-leg and not in the off-leg (multi_path_counts)
+
+    def counted(st):
+        st.multi_path_counts(reset=True)
+        out = scenario(st)
+        took.append(st.multi_path_counts()["mla_xm"])
+        return out
+
+    off, on = _off_on(st, counted)
+    assert took == [0, 1], ("mla_xm", took)
     _equal(on, off)
     for i, ref in enumerate(refs):
         assert np.array_equal(_bits(on[1][i]), ref["lg"]) and on[0][i] == ref["tok"], ("single-sequence prefill", i)

@@ -166,7 +166,16 @@ def test_step_multi_equals_option_off_and_decode_step(key, kv_max):
     st, _, d = _model(*key, kv_max)
     seq, (single, snap) = _seq(*key, kv_max), _single(*key, kv_max)
     pos = POS if kv_max == KV_MAX else POS_LONG
-    off, on = _off_on(st, lambda st: _steps(st, d, seq, pos, kv_max=kv_max))
+    took = []      # not vacuous: the pass took the option's form in the on-leg and not in the off-leg (multi_path_counts)
+
+    def counted(st):
+        st.multi_path_counts(reset=True)
+        out = _steps(st, d, seq, pos, kv_max=kv_max)
+        took.append(st.multi_path_counts()["mla_xs_split"])
+        return out
+
+    off, on = _off_on(st, counted)
+    assert took == [0, 1], ("mla_xs_split", took)
     _equal(on, off)
     for i, p in enumerate(pos):
         assert np.array_equal(_bits(on[1][i]), single[p][0]) and int(on[0][i]) == single[p][1], ("decode_step", p)

@@ -20,33 +20,37 @@ WEIGHTS = np.array([0.14, 0.28, 0.10, 0.20, 0.08, 0.10, 0.10])
 
 
 class Driver:
-    """draws the operations and runs them on paged slots of `st`; log = the successful ones with their arguments, out = what they returned"""
+    """draws the operations and runs them on paged slots of `st`; log = the successful ones with their arguments, out = what they returned.  The sizes are
+    instance attributes and the operation table a class attribute, so that a subclass can drive other sizes and further operations
+    (tests/test_multi_options_random_gpu.py)"""
+    OPS, WEIGHTS = OPS, WEIGHTS
 
-    def __init__(self, K, st, d, seed, rewind, check=True):
+    def __init__(self, K, st, d, seed, rewind, check=True, n_slots=N_SLOTS, max_seq=MAX_SEQ, pt=PT, n_pages=N_PAGES, n_ops=N_OPS, check_every=CHECK_EVERY):
         self.K, self.st, self.d, self.rewind, self.check = K, st, d, rewind, check
+        self.n_slots, self.max_seq, self.pt, self.n_pages, self.n_ops, self.check_every = n_slots, max_seq, pt, n_pages, n_ops, check_every
         self.rng = np.random.default_rng(seed)
-        self.hist = [[] for _ in range(N_SLOTS)]
+        self.hist = [[] for _ in range(n_slots)]
         self.log, self.out, self.names = [], [], []
         self.refused = self.copies = self.checkpoints = 0
 
     # ---- the page tables against the histories
     def tables(self):
-        return [self.st.slot_page_ids(s) for s in range(N_SLOTS)], self.st.slot_pages()
+        return [self.st.slot_page_ids(s) for s in range(self.n_slots)], self.st.slot_pages()
 
     def shadow(self):
         rows, pages = self.tables()
         named = {}
         for s, (ids, refs) in enumerate(rows):
-            need = (len(self.hist[s]) + PT - 1) // PT
+            need = (len(self.hist[s]) + self.pt - 1) // self.pt
             assert all(i >= 0 for i in ids[:need]), ("positions [0, len) are mapped", s, len(self.hist[s]), ids)
             assert pages["per_slot"][s] == sum(i >= 0 for i in ids), ("per_slot", s)
             for i in ids:
                 if i >= 0:
-                    assert i < N_PAGES
+                    assert i < self.n_pages
                     named[i] = named.get(i, 0) + 1
         for s, (ids, refs) in enumerate(rows):
             assert refs == [named.get(i, 0) if i >= 0 else 0 for i in ids], ("refs = the table entries naming the page", s, ids, refs)
-        assert pages["free"] == N_PAGES - len(named), ("free = n_pages - the distinct pages named", pages["free"], sorted(named))
+        assert pages["free"] == self.n_pages - len(named), ("free = n_pages - the distinct pages named", pages["free"], sorted(named))
         return rows
 
     def count_copies(self, before, after):
@@ -64,34 +68,42 @@ class Driver:
         n = int(self.rng.integers(1, min(hi, len(pool)) + 1))
         return [int(x) for x in self.rng.permutation(pool)[:n]]
 
+    def run_len(self, p):
+        """the tokens of a run that enters at position p"""
+        return int(self.rng.integers(1, min(70, self.max_seq - p) + 1))
+
     def draw(self):
         r, h = self.rng, self.hist
-        room = [s for s in range(N_SLOTS) if len(h[s]) < MAX_SEQ - 8]
-        live = [s for s in range(N_SLOTS) if h[s]]
-        name = OPS[int(r.choice(len(OPS), p=WEIGHTS))]
+        room = [s for s in range(self.n_slots) if len(h[s]) < self.max_seq - 8]
+        live = [s for s in range(self.n_slots) if h[s]]
+        name = self.OPS[int(r.choice(len(self.OPS), p=self.WEIGHTS))]
         if name == "step" and room:
             sl = self.subset(room, 5)
             return ("step", sl, self.toks(len(sl)), [len(h[s]) for s in sl])
         if name == "extend" and room:
             sl = self.subset(room, 3)
             pos = [int(r.integers(0, len(h[s]) + 1)) if self.rewind and h[s] and r.random() < 0.4 else len(h[s]) for s in sl]
-            return ("extend", sl, [self.toks(int(r.integers(1, min(70, MAX_SEQ - p) + 1))) for p in pos], pos)
+            return ("extend", sl, [self.toks(self.run_len(p)) for p in pos], pos)
         if name == "verify" and room:
             sl = self.subset(room, 3)
             return ("verify", sl, [self.toks(int(r.integers(2, 9))) for _ in sl], [len(h[s]) for s in sl], [float(r.random()) for _ in sl])
         if name == "fork" and live:
             src = int(r.choice(live))
-            dsts = self.subset([s for s in range(N_SLOTS) if s != src], 3)
+            dsts = self.subset([s for s in range(self.n_slots) if s != src], 3)
             return ("fork", src, dsts, int(r.integers(0, len(h[src]) + 1)) if self.rewind and r.random() < 0.5 else len(h[src]))
         if name == "trim" and live:
             s = int(r.choice(live))      # with linear attention only what lies past the slot's length may go: the layers' state cannot be cut back
             return ("trim", s, int(r.integers(0, len(h[s]) + 1)) if self.rewind else len(h[s]))
         if name == "save" and live:
             s = int(r.choice(live))
-            return ("save", s, s if r.random() < 0.5 else int(r.integers(0, N_SLOTS)), len(h[s]))      # onto itself: every page it shares is written, so copied
+            return ("save", s, s if r.random() < 0.5 else int(r.integers(0, self.n_slots)), len(h[s]))      # onto itself: every page it shares is written, so copied
         if name == "generate" and room:
             sl = self.subset(room, 3)
             return ("generate", sl, self.toks(len(sl)), [len(h[s]) for s in sl], int(r.integers(2, 7)))
+        return self.draw_more(name, room, live)
+
+    def draw_more(self, name, room, live):
+        """an operation of a subclass's table (or one that cannot be drawn now: None, the driver draws again)"""
         return None
 
     # ---- running one operation on whatever slots `st` has now: -> what it returned, and the histories afterwards
@@ -163,12 +175,12 @@ class Driver:
     def checkpoint(self):
         """one step over all live slots against the single-sequence path, row by row (unless the pool refuses it), then every live slot's stored state"""
         K, st, d = self.K, self.st, self.d
-        sl = [s for s in range(N_SLOTS) if 0 < len(self.hist[s]) < MAX_SEQ - 8]
+        sl = [s for s in range(self.n_slots) if 0 < len(self.hist[s]) < self.max_seq - 8]
         stepped = bool(sl) and self.step(("step", sl, self.toks(len(sl)), [len(self.hist[s]) for s in sl]))
         if not self.check:
             return
         self.checkpoints += 1
-        for s in range(N_SLOTS):
+        for s in range(self.n_slots):
             n = len(self.hist[s])
             if not n:
                 continue
@@ -182,13 +194,13 @@ class Driver:
 
     def drive(self):
         done = 0
-        while done < N_OPS:
+        while done < self.n_ops:
             op = self.draw()
             if op is None:
                 continue
             self.step(op)
             done += 1
-            if done % CHECK_EVERY == 0:
+            if done % self.check_every == 0:
                 self.checkpoint()
 
 

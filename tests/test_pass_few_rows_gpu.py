@@ -260,17 +260,21 @@ def _positions(B):
 def test_step_multi(B, var):
     st, _, d, seq = _model(var.get("fp8", False))
     pos, slots = _positions(B), SLOTS[:B]
+    took = []      # not vacuous: both passes took the few-row form in the on-leg, none in the off-leg (multi_path_counts)
 
     def scenario(arm):
         _create(st, 17, **var)
         _fill(st, d, seq, list(zip(slots, pos)))
         arm()
+        st.multi_path_counts(reset=True)
         ids, lg = st.step_multi(slots, [seq[p] for p in pos], pos, logits=True)
         ids2, lg2 = st.step_multi(slots, list(ids), [p + 1 for p in pos], logits=True)      # a second step over what the first appended
+        took.append(st.multi_path_counts()["few"])
         st.set_option(OPT, 0)
         return list(ids) + list(ids2), np.concatenate([lg, lg2]), [_slot_state(st, d, s, p + 2) for s, p in zip(slots, pos)], []
 
     off, on = _off_on(st, scenario, **var)
+    assert took == [0, 2], ("few", took)
     _equal(on, off, ("step_multi", B, var))
 
 
