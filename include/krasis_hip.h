@@ -623,6 +623,43 @@ int kr_decode_slot_fork(kr_decode_store* s, int src, int n_dst, const int32_t* d
 int kr_decode_slot_page_ids(kr_decode_store* s, int slot, int32_t* ids_out, int32_t* refs_out);
 /* the entries of a paged slot's table row, ceil(max_seq / page_tokens): what kr_decode_slot_page_ids writes to each of its outputs.  Flat slots: 0 */
 int kr_decode_slots_page_stride(kr_decode_store* s, int32_t* stride_out);
+/* ---- slot export and import (docs/design/38-slot-swap.md): a slot's complete state out to host memory as one self-describing image and back into any slot of
+   any compatible slot set, bit for bit -- what a scheduler needs to preempt a sequence when the page pool is full without prefilling its history again.
+   An image is a 64-byte header (magic, format version, KV element type, seq_len, store layers, hidden size, vocab, whether a sampler is present, a 64-bit
+   digest of the per-layer geometry, total bytes, section count, table offset), a table of {uint64 offset, uint64 bytes} per section, then the sections, each
+   at a multiple of 16 bytes: two per store layer in layer order -- GQA: K rows [seq_len][row], V rows; MLA: latent rows, rope-key rows; linear attention: conv
+   state, recurrent state; a layer without attention: two empty sections -- and last, if present, the slot's sampler: temperature, top_k, top_p, presence
+   penalty (4 bytes each), the xorshift64 state (8 bytes), 8 zero bytes, the seen bitmap.  Little-endian throughout.  The image is canonical: position-major, nothing
+   at or past seq_len, nothing that depends on n_slots, max_seq, flat or paged, page_tokens or page ids, so the same sequence state exports to the same bytes
+   from any slot set; a page inside [0, seq_len) that is not mapped exports as zeros.  There is no payload checksum: an image is the caller's memory and is
+   trusted beyond the header checks.
+   As for kr_decode_slot_fork the library keeps no per-slot length: on a store with linear-attention layers seq_len must therefore be the number of tokens the
+   slot has consumed (this cannot be checked); a store of GQA / MLA layers only may export any prefix.
+   Both calls run on the store's stream through a staging buffer of two halves of "slot_swap_chunk_bytes" (kr_decode_set_option: a multiple of 16, at least 1024,
+   else KR_ERR_VALUE; every value gives the same bytes), allocated on first use and freed with the slots, and return with their streams drained; neither touches the
+   store's own sequence, and neither synchronises the whole device except where it has to (re)allocate: the first call, the first after a change of the option,
+   and a call with more pieces than any earlier one, whose piece buffer grows (freeing device or pinned memory waits for the device).
+   kr_decode_slot_image_bytes: the bytes of the image of seq_len positions (0 <= seq_len <= max_seq) of the current slots, with_sampler != 0 with the sampler
+   section, with_sampler < 0 as kr_decode_slots_export would write it now.
+   kr_decode_slots_export: slots[n] distinct, 1 <= n <= n_slots, 0 <= seq_lens[i] <= max_seq; image_bytes[i] must be what kr_decode_slot_image_bytes gives,
+   with the sampler section if and only if the set's samplers are allocated (a kr_decode_slot_sampler or sampled generation call has been made since the slots
+   were created).  The slots, their table rows, reference counts and shared pages are unchanged bit for bit: an export takes no copy-on-write.  release != 0:
+   once every image is complete each exported slot gives all its pages back, as kr_decode_slot_trim(slot, 0) (flat slots: nothing to give).
+   kr_decode_slots_import: afterwards slots[i] behaves as a fresh slot into which the image's sequence was prefilled: rows [0, seq_len) have the image's bits,
+   rows at or past seq_len read as zero, linear-attention state and sampler come from the image; seq_lens_out[i] = the image's seq_len.  An image without a
+   sampler leaves the slot sampling greedily with a zero seen set and a zero state, like a fresh slot; an image with one, entering a set without samplers,
+   allocates them for every slot as the first kr_decode_slot_sampler call does.  Paged slots, all or nothing across the whole call: whatever the named slots
+   held is released first, as kr_decode_slot_trim(slot, 0), then the pages [0, seq_len) of every image are mapped, each with one reference (an import never
+   shares pages); the count is taken beforehand out of the free pages plus those the named slots give back, else KR_ERR_STATE naming pages needed, free pages
+   and pool size, and nothing changes.
+   KR_ERR_VALUE, naming the row: a null pointer, a slot out of range or named twice, a wrong byte count, a bad magic or version, a KV element type or geometry
+   digest other than the store's, an image seq_len above max_seq, an image sampler whose temperature is not >= 0.  KR_ERR_STATE: what kr_decode_slot_fork refuses of the store, a pending verify over slots
+   included.  A refused call changes nothing.
+   kr_decode_slot_image_info: host only, no store: the header checks of an image and what it says; every output may be NULL. */
+int kr_decode_slot_image_bytes(kr_decode_store* s, int seq_len, int with_sampler, size_t* bytes_out);
+int kr_decode_slots_export(kr_decode_store* s, int n, const int32_t* slots, const int32_t* seq_lens, void* const* images, const size_t* image_bytes, int release);
+int kr_decode_slots_import(kr_decode_store* s, int n, const int32_t* slots, const void* const* images, const size_t* image_bytes, int32_t* seq_lens_out);
+int kr_decode_slot_image_info(const void* image, size_t bytes, int32_t* seq_len_out, int32_t* kv_fp8_out, int32_t* has_sampler_out, uint64_t* geometry_out);
 /* test aid: the page-copy launch of a fork / a copy-on-write on one host pool [n_pages][page_bytes] (in / out), a row being page_bytes / page_tokens bytes:
    copy c = the first rows[c] rows of page src_pages[c] into page dst_pages[c], zeroes behind them.  No page may be a destination twice, or a source and a
    destination.  The device copy of the pool starts base_offset bytes (in [0, 256)) past an aligned address. */

@@ -36,6 +36,7 @@ SYMBOLS = [
     "kr_decode_verify_multi_sample", "kr_decode_generate_multi_lookup_sample", "kr_decode_slot_sampler_get", "kr_sample_runs",
     "kr_decode_slots_create_paged", "kr_decode_slot_trim", "kr_decode_slots_pages",
     "kr_decode_slot_fork", "kr_decode_slot_page_ids", "kr_decode_slots_page_stride", "kr_copy_pages", "kr_decode_multi_path_counts",
+    "kr_decode_slot_image_bytes", "kr_decode_slots_export", "kr_decode_slots_import", "kr_decode_slot_image_info",
 ]
 TOKEN_CB = C.CFUNCTYPE(C.c_int, C.c_int, C.c_int, C.c_void_p)      # kr_token_cb(token, finish_reason, user) -> continue?
 
@@ -203,6 +204,10 @@ def load_library() -> C.CDLL:
     lib.kr_decode_generate_multi_lookup_sample.argtypes = [vp, ci, vp, vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, ci, vp, vp, C.POINTER(ci), vp, vp]
     lib.kr_decode_slot_sampler_get.argtypes = [vp, ci, vp, vp]
     lib.kr_sample_runs.argtypes = [vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci]
+    lib.kr_decode_slot_image_bytes.argtypes = [vp, ci, ci, C.POINTER(C.c_size_t)]
+    lib.kr_decode_slots_export.argtypes = [vp, ci, vp, vp, vp, vp, ci]
+    lib.kr_decode_slots_import.argtypes = [vp, ci, vp, vp, vp, vp]
+    lib.kr_decode_slot_image_info.argtypes = [vp, C.c_size_t, vp, vp, vp, vp]
     _lib = lib
     return lib
 

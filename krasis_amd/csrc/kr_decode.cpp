@@ -1090,6 +1090,10 @@ extern "C" int kr_decode_set_option(kr_decode_store* s, const char* name, int va
         s->opt_pass_few_rows_group = value; return KR_OK;
     }
     if (!strcmp(name, "ep_graph")) { s->opt_ep_graph = value != 0; s->graph_ok = false; return KR_OK; }
+    if (!strcmp(name, "slot_swap_chunk_bytes")) {      // the bytes of one staging half of kr_decode_slots_export / _import; every value gives the same images and slots (docs/design/38-slot-swap.md)
+        if (value < KR_SLOT_CHUNK_MIN || value % 16) return kr_fail(KR_ERR_VALUE, "slot_swap_chunk_bytes %d: a multiple of 16, at least %d", value, KR_SLOT_CHUNK_MIN);
+        s->opt_slot_swap_chunk_bytes = value; return KR_OK;
+    }
     return kr_fail(KR_ERR_VALUE, "unknown option '%s'", name);
 }
 

@@ -70,7 +70,17 @@ struct kr_multi_state {
     bool v_pending = false, v_sampled = false, v_has64 = false, v_has128 = false; int v_nv_max = 0, v_dv_max = 0; size_t v_rows = 0;
     std::vector<int32_t> v_match; hipStream_t v_st = nullptr;
     hipEvent_t ev = nullptr;
-    ~kr_multi_state() { if (ev) (void)hipEventDestroy(ev); }
+    // slot export / import (kr_decode_slots_export / _import, docs/design/38-slot-swap.md), allocated on the first call: sw_stage = the device staging buffer and
+    // sw_pinned the pinned host buffer, two halves of sw_half bytes each; sw_stream carries the copies between them while the call's stream packs or unpacks the
+    // other half; sw_ev[h] = half h has been packed / unpacked, sw_ev[2 + h] = half h has been copied; sw_pools = KrPagePoolDev of every buffer a piece names
+    // (kr_slot_image.h: 2 per store layer, then the samplers' states and seen bitmaps), sw_pieces = the pieces of one call
+    DevBuf sw_stage, sw_pools, sw_pieces; void* sw_pinned = nullptr; size_t sw_half = 0; hipStream_t sw_stream = nullptr; hipEvent_t sw_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    ~kr_multi_state() {
+        if (ev) (void)hipEventDestroy(ev);
+        for (hipEvent_t e : sw_ev) if (e) (void)hipEventDestroy(e);
+        if (sw_stream) (void)hipStreamDestroy(sw_stream);
+        if (sw_pinned) (void)hipHostFree(sw_pinned);
+    }
 };
 
 struct kr_standalone_state;   // kr_decode_standalone.cpp: staging buffers, stand-alone router gates, cancel flag, elapsed time
@@ -114,6 +124,7 @@ struct kr_decode_store {
     int opt_pass_few_rows = 0;                   // kr_decode_set_option("pass_few_rows"): a multi-row pass of at most opt_pass_few_rows_max token rows (prefill / verify: n_tokens; slot entry points: the sum of the counts) runs its projections on the few-row streaming matvec (kr_rows_matvec.hip) and its INT4 / INT8 routed experts as the decode step's three launches -- bit for bit what it gives without the option (docs/design/34-pass-few-rows.md); KR_GEMM_FAST passes and larger passes keep their GEMMs
     int opt_pass_few_rows_max = 16;              // kr_decode_set_option("pass_few_rows_max"), 1 .. 16: the most token rows of a pass that takes the few-row kernels (a measured default: profiles/pass_few_rows.txt)
     int opt_pass_few_rows_group = 0;             // kr_decode_set_option("pass_few_rows_group"), 0 .. 16: the most rows a workgroup of the few-row matvec holds, 0 = chosen per launch (kr_rows_plan.h; A/B and test hook, same bits)
+    int opt_slot_swap_chunk_bytes = KR_SLOT_CHUNK_DEFAULT;   // kr_decode_set_option("slot_swap_chunk_bytes"), a multiple of 16 and at least 1024: the bytes of one staging half of slot export / import (docs/design/38-slot-swap.md; a measured default: profiles/slot_swap.txt)
     int64_t path_counts[KR_MPC_COUNT] = {};     // kr_decode_multi_path_counts: which forms the multi-row passes took (host-side test aid; written where a pass has been queued, read by nothing)
     int opt_gen_lookahead = 0;                  // kr_decode_set_option("generate_lookahead"): generate_batch feeds the sampled token back ON THE DEVICE and queues step i + 1 before the host has read token i
     int opt_ep_graph = 0;                         // kr_decode_set_option("ep_graph"): expert-parallel decode over RCCL replays a captured graph (the all-reduce is captured with the kernels)

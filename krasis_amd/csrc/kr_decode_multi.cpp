@@ -21,6 +21,8 @@
 // free list and the queue of unseen mappings are KrPagePool's (kr_page_pool.h), which prunes the queue itself; here: its members, and flush_plan() carried out (pg_flush).
 // kr_decode_slot_fork (docs/design/22-slot-fork.md): a slot's prefix into other slots without the prompt pass -- paged slots share the whole pages below the fork
 // point by reference count, and the reservation of every call that writes rows first gives a row a private copy of a page other slots hold too.
+// kr_decode_slots_export / kr_decode_slots_import (docs/design/38-slot-swap.md): a slot's whole state out to one self-describing host image (kr_slot_image.h) and back
+// into any slot of any compatible slot set, through a staging buffer of two halves and the two kernels of kr_multi_swap.hip.
 #include <algorithm>
 #include <chrono>
 #include <cstring>
@@ -382,7 +384,7 @@ int slot_copy(kr_decode_store* s, int slot, int seq_len, bool save) {
 // distinct per slot), parameters kept.  Arguments checked; allocates every slot's sampler state on the first call.
 int set_sampler(kr_decode_store* s, int slot, int first_token, float temperature, int top_k, float top_p, float presence_penalty, uint64_t rng_seed, hipStream_t st) {
     kr_multi_state& M = *s->multi;
-    if (M.smp.empty()) {
+    if (M.smp.empty()) {      // swap_samplers (slot import) allocates the same way: keep the two alike
         const size_t words = ((size_t)s->vocab + 31) / 32;
         if (M.smp_seen.ensure((size_t)M.n_slots * words * 4) || M.smp_rng.ensure((size_t)M.n_slots * 8)) return kr_fail(KR_ERR_HIP, "hipMalloc of the slot samplers failed");
         KR_HIP(hipMemsetAsync(M.smp_seen.p, 0, M.smp_seen.bytes, st));
@@ -807,6 +809,289 @@ extern "C" int kr_decode_slot_fork(kr_decode_store* s, int src, int n_dst, const
         KR_HIP(hipGetLastError());
     }
     KR_HIP(hipStreamSynchronize(st));
+    return KR_OK;
+}
+
+// ---- slot export / import (docs/design/38-slot-swap.md): a slot's whole state <-> one self-describing host image (kr_slot_image.h), in staged ranges of
+// "slot_swap_chunk_bytes": the call's stream packs / unpacks one half of the staging buffer (kr_multi_swap.hip) while the second stream copies the other between
+// device and pinned host memory and the host memcpy's between that and the caller's image.  No device-wide synchronisation: every slot entry point returns with its
+// pass finished (step_impl, verify_impl, commit_impl and the others end in a stream synchronise) and a pending verify is refused, so it suffices to order after the
+// store's last stream, to flush the page queue, and to wait for the call's own two streams
+namespace {
+KrSlotGeo swap_geo(const kr_decode_store* s) {
+    const kr_multi_state& M = *s->multi;
+    KrSlotGeo g;
+    g.kv_fp8 = M.kv_fp8; g.hidden = s->hidden; g.vocab = s->vocab;
+    for (size_t i = 0; i < s->layers.size(); i++) {
+        const int attn = s->layers[i].attn;
+        KrSlotLayerGeo x{KR_SLOT_NONE, 0, 0, 0, 0};
+        if (attn == ATTN_LA) x = KrSlotLayerGeo{KR_SLOT_LA, 0, 0, M.a_stride[i], M.b_stride[i]};
+        else if (attn == ATTN_GQA || attn == ATTN_MLA) x = KrSlotLayerGeo{attn == ATTN_GQA ? KR_SLOT_GQA : KR_SLOT_MLA, M.a_row[i], M.b_row[i], 0, 0};
+        g.layers.push_back(x);
+    }
+    return g;
+}
+// distinct slots in range, 1 <= n <= n_slots
+int swap_slots_ok(const kr_multi_state& M, int n, const int32_t* slots) {
+    if (n < 1 || n > M.n_slots) return kr_fail(KR_ERR_VALUE, "%d slots, must be in [1, %d] (n_slots)", n, M.n_slots);
+    if (!slots) return kr_fail(KR_ERR_VALUE, "null slots");
+    std::vector<char> seen((size_t)M.n_slots, 0);
+    for (int i = 0; i < n; i++) {
+        if (slots[i] < 0 || slots[i] >= M.n_slots) return kr_fail(KR_ERR_VALUE, "row %d: slot %d out of range [0, %d)", i, slots[i], M.n_slots);
+        if (seen[(size_t)slots[i]]++) return kr_fail(KR_ERR_VALUE, "row %d: slot %d is named twice", i, slots[i]);
+    }
+    return KR_OK;
+}
+// the staging buffers, the second stream and the events, on first use and whenever the half size changes (nothing is in flight: every call drains its streams)
+int swap_ensure(kr_decode_store* s) {
+    kr_multi_state& M = *s->multi;
+    const size_t half = (size_t)s->opt_slot_swap_chunk_bytes;
+    if (!M.sw_stream) KR_HIP(hipStreamCreateWithFlags(&M.sw_stream, hipStreamNonBlocking));
+    for (hipEvent_t& e : M.sw_ev) if (!e) KR_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    if (M.sw_half != half) {
+        if (M.sw_pinned) { (void)hipHostFree(M.sw_pinned); M.sw_pinned = nullptr; }
+        M.sw_half = 0;
+        if (M.sw_stage.ensure(2 * half)) return kr_fail(KR_ERR_HIP, "hipMalloc of the slot swap staging buffer (2 x %zu bytes) failed", half);
+        KR_HIP(hipHostMalloc(&M.sw_pinned, 2 * half, hipHostMallocDefault));
+        M.sw_half = half;
+    }
+    return KR_OK;
+}
+// the samplers of every slot, as the first kr_decode_slot_sampler call allocates them: zero seen sets, zero states, greedy parameters.  The twin of the allocation
+// block at the head of set_sampler (which this change leaves as it was): a new sampler buffer or another seen-set layout goes into both
+int swap_samplers(kr_decode_store* s, hipStream_t st) {
+    kr_multi_state& M = *s->multi;
+    if (!M.smp.empty()) return KR_OK;
+    const size_t words = ((size_t)s->vocab + 31) / 32;
+    if (M.smp_seen.ensure((size_t)M.n_slots * words * 4) || M.smp_rng.ensure((size_t)M.n_slots * 8)) return kr_fail(KR_ERR_HIP, "hipMalloc of the slot samplers failed");
+    KR_HIP(hipMemsetAsync(M.smp_seen.p, 0, M.smp_seen.bytes, st));
+    KR_HIP(hipMemsetAsync(M.smp_rng.p, 0, M.smp_rng.bytes, st));
+    M.smp_words = words;
+    M.smp.assign((size_t)M.n_slots, kr_multi_state::Sampler());
+    return KR_OK;
+}
+// one staged range: bytes [r0, r1) of row `row`'s image, its pieces [p0, p1) of the call's list
+struct SwapRange { int row; uint64_t r0, r1; size_t p0, p1; };
+// the pools and the pieces of a call -> the device, and the ranges: every image's payload in chunks of the half size
+int swap_plan(kr_decode_store* s, int n, const int32_t* slots, const std::vector<KrSlotLayout>& lay, hipStream_t st, std::vector<SwapRange>& ranges) {
+    kr_multi_state& M = *s->multi;
+    const size_t nl = s->layers.size();
+    std::vector<KrPagePoolDev> pools(2 * nl + 2, KrPagePoolDev{nullptr, 0});
+    for (size_t i = 0; i < nl; i++) { pools[2 * i] = KrPagePoolDev{M.a[i].p, M.a_stride[i]}; pools[2 * i + 1] = KrPagePoolDev{M.b[i].p, M.b_stride[i]}; }
+    pools[2 * nl] = KrPagePoolDev{M.smp_rng.p, 8}; pools[2 * nl + 1] = KrPagePoolDev{M.smp_seen.p, M.smp_words * 4};
+    std::vector<KrSlotPiece> pieces;
+    for (int i = 0; i < n; i++) {
+        const KrSlotPlace place{slots[i], M.pg.page_tokens, M.pg.paged() ? M.pg.row(slots[i]) : nullptr};
+        for (uint64_t r0 = lay[(size_t)i].payload; r0 < lay[(size_t)i].total; r0 += M.sw_half) {
+            SwapRange r{i, r0, std::min<uint64_t>(r0 + M.sw_half, lay[(size_t)i].total), pieces.size(), 0};
+            kr_slot_pieces(lay[(size_t)i], place, r.r0, r.r1, &pieces);
+            r.p1 = pieces.size();
+            ranges.push_back(r);
+        }
+    }
+    if (M.sw_pools.ensure(pools.size() * sizeof(KrPagePoolDev)) || M.sw_pieces.ensure(std::max(pieces.size(), (size_t)1) * sizeof(KrSlotPiece)))
+        return kr_fail(KR_ERR_HIP, "hipMalloc of the slot swap piece list (%zu pieces) failed", pieces.size());
+    KR_HIP(hipMemcpyAsync(M.sw_pools.p, pools.data(), pools.size() * sizeof(KrPagePoolDev), hipMemcpyHostToDevice, st));      // pageable sources: staged before the call returns
+    if (!pieces.empty()) KR_HIP(hipMemcpyAsync(M.sw_pieces.p, pieces.data(), pieces.size() * sizeof(KrSlotPiece), hipMemcpyHostToDevice, st));
+    KR_HIP(hipStreamSynchronize(st));      // the lists are the device's before the host's vectors go; what the store had queued ahead has finished with it
+    return KR_OK;
+}
+// whatever happens, the call leaves nothing in flight on its two streams
+struct SwapDrain { hipStream_t a, b; ~SwapDrain() { (void)hipStreamSynchronize(b); (void)hipStreamSynchronize(a); } };
+// export: range k is packed into half k & 1 on st and copied to the pinned half on the second stream, while the host takes range k - 1 out of the other half
+int swap_out(kr_multi_state& M, const std::vector<SwapRange>& ranges, void* const* images, hipStream_t st) {
+    const KrSlotPiece* pieces = (const KrSlotPiece*)M.sw_pieces.p;
+    auto issue = [&](size_t k) -> int {
+        const SwapRange& r = ranges[k];
+        const int h = (int)(k & 1);
+        char* dev = (char*)M.sw_stage.p + (size_t)h * M.sw_half;
+        if (k >= 2) KR_HIP(hipStreamWaitEvent(st, M.sw_ev[2 + h], 0));      // the copy of range k - 2 has left this half
+        kr_launch_multi_pack((const KrPagePoolDev*)M.sw_pools.p, pieces + r.p0, (int)(r.p1 - r.p0), dev, st);
+        KR_HIP(hipGetLastError());
+        KR_HIP(hipEventRecord(M.sw_ev[h], st));
+        KR_HIP(hipStreamWaitEvent(M.sw_stream, M.sw_ev[h], 0));
+        KR_HIP(hipMemcpyAsync((char*)M.sw_pinned + (size_t)h * M.sw_half, dev, (size_t)(r.r1 - r.r0), hipMemcpyDeviceToHost, M.sw_stream));
+        KR_HIP(hipEventRecord(M.sw_ev[2 + h], M.sw_stream));
+        return KR_OK;
+    };
+    if (!ranges.empty()) if (int rc = issue(0)) return rc;
+    for (size_t k = 0; k < ranges.size(); k++) {
+        if (k + 1 < ranges.size()) if (int rc = issue(k + 1)) return rc;      // its pinned half was emptied by the host one turn ago
+        const SwapRange& r = ranges[k];
+        KR_HIP(hipEventSynchronize(M.sw_ev[2 + (k & 1)]));
+        memcpy((char*)images[r.row] + r.r0, (const char*)M.sw_pinned + (k & 1) * M.sw_half, (size_t)(r.r1 - r.r0));
+    }
+    return KR_OK;
+}
+// import, the mirror image: the host fills pinned half k & 1 while range k - 1 travels; the copy waits for the unpack of range k - 2 to have left the device half
+int swap_in(kr_multi_state& M, const std::vector<SwapRange>& ranges, const void* const* images, hipStream_t st) {
+    const KrSlotPiece* pieces = (const KrSlotPiece*)M.sw_pieces.p;
+    for (size_t k = 0; k < ranges.size(); k++) {
+        const SwapRange& r = ranges[k];
+        const int h = (int)(k & 1);
+        char* dev = (char*)M.sw_stage.p + (size_t)h * M.sw_half;
+        char* pin = (char*)M.sw_pinned + (size_t)h * M.sw_half;
+        if (k >= 2) KR_HIP(hipEventSynchronize(M.sw_ev[2 + h]));      // the copy of range k - 2 has read this pinned half
+        memcpy(pin, (const char*)images[r.row] + r.r0, (size_t)(r.r1 - r.r0));
+        if (k >= 2) KR_HIP(hipStreamWaitEvent(M.sw_stream, M.sw_ev[h], 0));
+        KR_HIP(hipMemcpyAsync(dev, pin, (size_t)(r.r1 - r.r0), hipMemcpyHostToDevice, M.sw_stream));
+        KR_HIP(hipEventRecord(M.sw_ev[2 + h], M.sw_stream));
+        KR_HIP(hipStreamWaitEvent(st, M.sw_ev[2 + h], 0));
+        kr_launch_multi_unpack((const KrPagePoolDev*)M.sw_pools.p, pieces + r.p0, (int)(r.p1 - r.p0), dev, st);
+        KR_HIP(hipGetLastError());
+        KR_HIP(hipEventRecord(M.sw_ev[h], st));
+    }
+    return KR_OK;
+}
+const char* swap_image_fault(int code) {
+    switch (code) {
+        case 1: return "shorter than an image header";
+        case 2: return "bad magic: not a slot image";
+        case 3: return "an image format version this library does not read";
+        case 4: return "image_bytes is not the header's total_bytes";
+        case 6: return "its KV element type is not the slots'";
+        case 7: return "its geometry (layers, hidden size, vocabulary or the per-layer digest) is not the store's";
+        case 8: return "its seq_len is above the slots' max_seq";
+        default: return "a malformed header or section table";
+    }
+}
+}  // namespace
+
+extern "C" int kr_decode_slot_image_bytes(kr_decode_store* s, int seq_len, int with_sampler, size_t* bytes_out) {
+    if (int rc = multi_ready(s)) return rc;
+    if (int rc = need_slots(s)) return rc;
+    const kr_multi_state& M = *s->multi;
+    if (!bytes_out) return kr_fail(KR_ERR_VALUE, "null bytes_out");
+    if (seq_len < 0 || seq_len > M.max_seq) return kr_fail(KR_ERR_VALUE, "seq_len %d outside [0, %d] (slot max_seq)", seq_len, M.max_seq);
+    *bytes_out = (size_t)kr_slot_image_layout(swap_geo(s), seq_len, with_sampler < 0 ? !M.smp.empty() : with_sampler != 0).total;
+    return KR_OK;
+}
+extern "C" int kr_decode_slot_image_info(const void* image, size_t bytes, int32_t* seq_len_out, int32_t* kv_fp8_out, int32_t* has_sampler_out, uint64_t* geometry_out) {
+    if (!image) return kr_fail(KR_ERR_VALUE, "null image");
+    KrSlotImageHeader h;
+    if (const int bad = kr_slot_image_check(image, bytes, &h)) return kr_fail(KR_ERR_VALUE, "slot image: %s", swap_image_fault(bad));
+    if (seq_len_out) *seq_len_out = (int32_t)h.seq_len;
+    if (kv_fp8_out) *kv_fp8_out = (int32_t)h.kv_fp8;
+    if (has_sampler_out) *has_sampler_out = (int32_t)h.has_sampler;
+    if (geometry_out) *geometry_out = h.geometry;
+    return KR_OK;
+}
+extern "C" int kr_decode_slots_export(kr_decode_store* s, int n, const int32_t* slots, const int32_t* seq_lens, void* const* images, const size_t* image_bytes,
+                                      int release) {
+    if (int rc = multi_begin(s)) return rc;
+    kr_multi_state& M = *s->multi;
+    if (int rc = swap_slots_ok(M, n, slots)) return rc;
+    if (!seq_lens || !images || !image_bytes) return kr_fail(KR_ERR_VALUE, "null seq_lens / images / image_bytes");
+    const KrSlotGeo geo = swap_geo(s);
+    const bool smp = !M.smp.empty();
+    std::vector<KrSlotLayout> lay;
+    for (int i = 0; i < n; i++) {
+        if (seq_lens[i] < 0 || seq_lens[i] > M.max_seq) return kr_fail(KR_ERR_VALUE, "row %d: seq_len %d outside [0, %d] (slot max_seq)", i, seq_lens[i], M.max_seq);
+        if (!images[i]) return kr_fail(KR_ERR_VALUE, "row %d: null image", i);
+        lay.push_back(kr_slot_image_layout(geo, seq_lens[i], smp));
+        if (image_bytes[i] != (size_t)lay.back().total)
+            return kr_fail(KR_ERR_VALUE, "row %d: image_bytes %zu, but the image of %d positions %s a sampler has %zu (kr_decode_slot_image_bytes)", i, image_bytes[i], seq_lens[i],
+                           smp ? "with" : "without", (size_t)lay.back().total);
+    }
+    KR_HIP(hipSetDevice(s->eng->device));
+    hipStream_t st = s->eng->stream;
+    if (int rc = swap_ensure(s)) return rc;
+    if (int rc = order_after_store(s, st)) return rc;
+    SwapDrain drain{st, M.sw_stream};
+    if (int rc = pg_flush(M, st)) return rc;      // a fork's queued boundary copies and the zeroes of freshly mapped pages land ahead of the pack launches
+    std::vector<SwapRange> ranges;
+    if (int rc = swap_plan(s, n, slots, lay, st, ranges)) return rc;
+    if (int rc = swap_out(M, ranges, images, st)) return rc;
+    for (int i = 0; i < n; i++) {      // the host's part of every image: header, table, zero gaps, the sampler's parameters
+        kr_slot_image_frame(lay[(size_t)i], images[i]);
+        if (!smp) continue;
+        const kr_multi_state::Sampler& p = M.smp[(size_t)slots[i]];
+        const int32_t top_k = p.top_k;
+        char* at = (char*)images[i] + lay[(size_t)i].sampler;
+        memcpy(at, &p.temperature, 4); memcpy(at + 4, &top_k, 4); memcpy(at + 8, &p.top_p, 4); memcpy(at + 12, &p.penalty, 4);
+    }
+    KR_HIP(hipStreamSynchronize(M.sw_stream));
+    KR_HIP(hipStreamSynchronize(st));
+    if (release && M.pg.paged()) {      // only now, with every image complete: each slot's pages back, as kr_decode_slot_trim(slot, 0)
+        std::vector<KrPageChange> freed;
+        for (int i = 0; i < n; i++) M.pg.trim(slots[i], 0, &freed);
+        return pg_released(s, freed);
+    }
+    return KR_OK;
+}
+extern "C" int kr_decode_slots_import(kr_decode_store* s, int n, const int32_t* slots, const void* const* images, const size_t* image_bytes, int32_t* seq_lens_out) {
+    if (int rc = multi_begin(s)) return rc;
+    kr_multi_state& M = *s->multi;
+    if (int rc = swap_slots_ok(M, n, slots)) return rc;
+    if (!images || !image_bytes || !seq_lens_out) return kr_fail(KR_ERR_VALUE, "null images / image_bytes / seq_lens_out");
+    const KrSlotGeo geo = swap_geo(s);
+    std::vector<KrSlotLayout> lay;
+    std::vector<long long> lens((size_t)n);
+    bool any_sampler = false;
+    for (int i = 0; i < n; i++) {
+        if (!images[i]) return kr_fail(KR_ERR_VALUE, "row %d: null image", i);
+        KrSlotImageHeader h;
+        int bad = kr_slot_image_check(images[i], image_bytes[i], &h);
+        if (!bad) bad = kr_slot_image_match(images[i], h, geo, M.max_seq);
+        if (bad) return kr_fail(KR_ERR_VALUE, "row %d: slot image of %zu bytes: %s", i, image_bytes[i], swap_image_fault(bad));
+        lay.push_back(kr_slot_image_layout(geo, (int)h.seq_len, h.has_sampler != 0));
+        lens[(size_t)i] = h.seq_len; any_sampler |= h.has_sampler != 0;
+        if (h.has_sampler) {      // what kr_decode_slot_sampler refuses of its own argument: the image may not bring a sampler the setter would never leave
+            float t; memcpy(&t, (const char*)images[i] + lay.back().sampler, 4);
+            if (!(t >= 0.0f)) return kr_fail(KR_ERR_VALUE, "row %d: slot image: its sampler's temperature must be >= 0", i);
+        }
+    }
+    const bool paged = M.pg.paged();
+    if (paged) {      // all or nothing: the pages [0, seq_len) of every image, out of the free pages and those the named slots give back (as fork_fit counts)
+        long long need = 0;
+        for (int i = 0; i < n; i++) need += M.pg.pages_of(lens[(size_t)i]);
+        const int gain = M.pg.would_free(n, slots);
+        if (need > (long long)M.pg.n_free + gain)
+            return kr_fail(KR_ERR_STATE, "the import of %d slot images does not fit the page pool: %lld pages of %d positions, %d of %d are free (%d of them once the named slots are released)",
+                           n, need, M.pg.page_tokens, M.pg.n_free + gain, M.pg.n_pages, gain);
+    }
+    KR_HIP(hipSetDevice(s->eng->device));
+    hipStream_t st = s->eng->stream;
+    if (int rc = swap_ensure(s)) return rc;
+    if (int rc = order_after_store(s, st)) return rc;
+    SwapDrain drain{st, M.sw_stream};
+    if (any_sampler) if (int rc = swap_samplers(s, st)) return rc;
+    if (paged) {      // the named slots release what they held (as kr_decode_slot_trim(slot, 0)), then map fresh pages, one reference each: an import never shares
+        for (int i = 0; i < n; i++) for (int j = 0; j < M.pg.stride; j++) M.pg.drop(slots[i], j, nullptr);
+        M.pg.prune();
+        int need = 0, have = 0;
+        if (M.pg.reserve(n, slots, lens.data(), nullptr, &need, &have) >= 0) return kr_fail(KR_ERR_STATE, "slot import: the page count above no longer holds (%d needed, %d free)", need, have);
+        if (int rc = pg_flush(M, st)) return rc;      // the new pages read as zero: the tail of a boundary page comes from here
+        for (int i = 0; i < n; i++) if (int rc = pg_upload(M, slots[i], 0, M.pg.stride - 1, st)) return rc;
+    }
+    for (int i = 0; i < n; i++) {
+        const size_t slot = (size_t)slots[i];
+        for (size_t li = 0; li < s->layers.size() && !paged; li++) {      // flat slots: rows [seq_len, max_seq) zeroed, as fork does
+            if (s->layers[li].attn != ATTN_GQA && s->layers[li].attn != ATTN_MLA) continue;
+            for (int hb = 0; hb < 2; hb++) {
+                const size_t stride = hb ? M.b_stride[li] : M.a_stride[li], head = (hb ? M.b_row[li] : M.a_row[li]) * (size_t)lens[(size_t)i];
+                if (stride > head) KR_HIP(hipMemsetAsync((char*)(hb ? M.b[li].p : M.a[li].p) + slot * stride + head, 0, stride - head, st));
+            }
+        }
+        if (M.smp.empty()) continue;
+        kr_multi_state::Sampler p;
+        if (lay[(size_t)i].sampler) {
+            int32_t top_k = 0;
+            const char* at = (const char*)images[i] + lay[(size_t)i].sampler;
+            memcpy(&p.temperature, at, 4); memcpy(&top_k, at + 4, 4); memcpy(&p.top_p, at + 8, 4); memcpy(&p.penalty, at + 12, 4);
+            p.top_k = top_k;
+        } else {      // an image without a sampler: greedy, a zero seen set and a zero state, like a fresh slot
+            KR_HIP(hipMemsetAsync((uint32_t*)M.smp_seen.p + slot * M.smp_words, 0, M.smp_words * 4, st));
+            KR_HIP(hipMemsetAsync((uint64_t*)M.smp_rng.p + slot, 0, 8, st));
+        }
+        M.smp[slot] = p;
+    }
+    std::vector<SwapRange> ranges;
+    if (int rc = swap_plan(s, n, slots, lay, st, ranges)) return rc;
+    if (int rc = swap_in(M, ranges, images, st)) return rc;
+    KR_HIP(hipStreamSynchronize(M.sw_stream));
+    KR_HIP(hipStreamSynchronize(st));
+    for (int i = 0; i < n; i++) seq_lens_out[i] = (int32_t)lens[(size_t)i];
     return KR_OK;
 }
 

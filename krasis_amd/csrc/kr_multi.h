@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "kr_slot_image.h"
+
 // linear attention over runs of consecutive tokens per slot (the decode step's kr_la_step_kernel arithmetic per token); a step is runs of one token
 struct KrMultiLaArgs {
     const float* qkvz; int ld_qkvz; // in-projection rows [rows][ld_qkvz]
@@ -210,6 +212,12 @@ void kr_launch_multi_zero_pages(const KrPagePoolDev* pools, int n_pools, const i
 // a row being page_bytes / page_tokens bytes -- grid (n_copies, n_pools), one launch.  Also the per-slot linear-attention state of a fork: pools whose "page" is
 // a slot, page_tokens 1, rows 1
 void kr_launch_multi_copy_pages(const KrPagePoolDev* pools, int n_pools, const int* dst_pages, const int* src_pages, const int* rows, int n_copies, int page_tokens, hipStream_t st);
+// slot export / import (kr_multi_swap.hip, docs/design/38-slot-swap.md): one staged byte range of slot images <-> the slots' buffers, one workgroup per piece
+// (kr_slot_image.h builds the pieces: pool = an entry of `pools`, whose "page" is a page of a paged GQA / MLA pool and a slot of every other buffer).  pack: the
+// pieces' bytes -> stage + range_off, a piece of page -1 as zeroes; unpack: stage + range_off -> the pieces' bytes, nothing else written.  pools, pieces and
+// stage on the device; the host keeps every piece inside its page and the staged range
+void kr_launch_multi_pack(const KrPagePoolDev* pools, const KrSlotPiece* pieces, int n_pieces, void* stage, hipStream_t st);
+void kr_launch_multi_unpack(const KrPagePoolDev* pools, const KrSlotPiece* pieces, int n_pieces, const void* stage, hipStream_t st);
 
 // per row b < B of logits [B][ld]: out[b] = first-maximum argmax of the row's first V values (kr_argmax_kernel's rule)
 void kr_launch_multi_argmax(const float* logits, size_t ld, int V, int B, int* out, hipStream_t st);

@@ -40,6 +40,23 @@ def lookup_draft(history: Sequence[int], ngram_max: int, max_draft: int) -> List
     return list(out[:n])
 
 
+def _image_bytes(image) -> np.ndarray:
+    """a slot image as a contiguous uint8 array over the same bytes: bytes-like objects and arrays of any dtype are reinterpreted, never converted"""
+    if isinstance(image, np.ndarray):
+        return np.ascontiguousarray(image).reshape(-1).view(np.uint8)
+    return np.frombuffer(image, np.uint8)
+
+
+def slot_image_info(image) -> dict:
+    """kr_decode_slot_image_info (host only, no store): the header checks of a slot image (export_slots) and what it says --
+    dict(seq_len, kv_fp8, has_sampler, geometry); ValueError for anything that is not a whole image of this format version"""
+    lib = load_library()
+    a = _image_bytes(image)
+    seq, fp8, smp, geo = C.c_int32(), C.c_int32(), C.c_int32(), C.c_uint64()
+    check(lib.kr_decode_slot_image_info(a.ctypes.data, a.size, C.byref(seq), C.byref(fp8), C.byref(smp), C.byref(geo)))
+    return dict(seq_len=seq.value, kv_fp8=bool(fp8.value), has_sampler=bool(smp.value), geometry=geo.value)
+
+
 class CpuDecodeStore:
     def __init__(self, group_size: int = 128, parallel: bool = True, norm_bias_one: bool = False, device: Optional[int] = None):
         # Like the reference (decode.rs:229) the store exists BEFORE an engine is bound: weights, norms and router gates can be stored first and
@@ -553,6 +570,63 @@ class CpuDecodeStore:
         ids, refs = np.full(max(stride.value, 1), -1, np.int32), np.zeros(max(stride.value, 1), np.int32)
         check(self._lib.kr_decode_slot_page_ids(self._h, slot, ids.ctypes.data, refs.ctypes.data))
         return [int(x) for x in ids], [int(x) for x in refs]
+
+    # ------------------------------------------------------------------ slot export / import (docs/design/38-slot-swap.md)
+    def slot_image_bytes(self, seq_len: int) -> int:
+        """kr_decode_slot_image_bytes: the bytes of the image export_slot(slot, seq_len) would write now -- with the sampler section if and only if the
+        set's samplers are allocated"""
+        self._need()
+        b = C.c_size_t()
+        check(self._lib.kr_decode_slot_image_bytes(self._h, seq_len, -1, C.byref(b)))
+        return b.value
+
+    def export_slots(self, slots: Sequence[int], seq_lens: Sequence[int], release: bool = False) -> List[np.ndarray]:
+        """kr_decode_slots_export: the complete state of every slots[i] at seq_lens[i] positions as one self-describing host image each (uint8 arrays):
+        GQA / MLA rows [0, seq_len), the linear-attention state as it stands, the slot's sampler if the set has samplers.  The image is canonical -- the
+        same sequence state gives the same bytes from flat or paged slots, any page size and placement -- and import_slots brings it back into any slot
+        of any compatible slot set, bit for bit.  The slots, their pages and reference counts are unchanged (no copy-on-write); release=True then gives
+        every exported slot's pages back, as trim_slot(slot, 0).  The library keeps no per-slot length: on a store with linear-attention layers
+        seq_len must be the number of tokens the slot has consumed (this cannot be checked).  Refused while a verify over slots is pending."""
+        self._need()
+        slots, seq_lens = [int(x) for x in slots], [int(x) for x in seq_lens]
+        if len(slots) != len(seq_lens):
+            raise ValueError(f"{len(slots)} slots but {len(seq_lens)} seq_lens")
+        n = len(slots)
+        images = []
+        for q in seq_lens:
+            b = C.c_size_t()
+            check(self._lib.kr_decode_slot_image_bytes(self._h, q, -1, C.byref(b)))
+            images.append(np.empty(b.value, np.uint8))
+        ptrs = (C.c_void_p * max(n, 1))(*[im.ctypes.data for im in images])
+        sizes = (C.c_size_t * max(n, 1))(*[im.size for im in images])
+        check(self._lib.kr_decode_slots_export(self._h, n, (C.c_int32 * max(n, 1))(*slots), (C.c_int32 * max(n, 1))(*seq_lens), ptrs, sizes, int(bool(release))))
+        return images
+
+    def import_slots(self, slots: Sequence[int], images) -> List[int]:
+        """kr_decode_slots_import: every slots[i] becomes a fresh slot into which the sequence of images[i] (uint8 arrays or bytes, from export_slots of
+        any slot set of the same model and KV element type) was prefilled -- rows, linear-attention state and sampler from the image, zero rows behind
+        them; an image without a sampler leaves the slot greedy.  Returns the images' seq_lens.  What the slots held is released first.  Paged slots:
+        all or nothing, every page mapped with one reference; a pool that cannot hold the images, counting the pages the named slots give back,
+        refuses the call (RuntimeError) and nothing changes.  A bad image (size, magic, version, KV type, geometry, seq_len above max_seq) is a ValueError."""
+        self._need()
+        slots = [int(x) for x in slots]
+        if len(slots) != len(images):
+            raise ValueError(f"{len(slots)} slots but {len(images)} images")
+        n = len(slots)
+        arrs = [_image_bytes(im) for im in images]
+        ptrs = (C.c_void_p * max(n, 1))(*[a.ctypes.data for a in arrs])
+        sizes = (C.c_size_t * max(n, 1))(*[a.size for a in arrs])
+        out = (C.c_int32 * max(n, 1))()
+        check(self._lib.kr_decode_slots_import(self._h, n, (C.c_int32 * max(n, 1))(*slots), ptrs, sizes, out))
+        return list(out[:n])
+
+    def export_slot(self, slot: int, seq_len: int, release: bool = False) -> np.ndarray:
+        """export_slots for one slot"""
+        return self.export_slots([slot], [seq_len], release)[0]
+
+    def import_slot(self, slot: int, image) -> int:
+        """import_slots for one slot -> the image's seq_len"""
+        return self.import_slots([slot], [image])[0]
 
     def save_slot(self, slot: int, seq_len: int) -> None:
         """the store's own sequence -> slot: KV rows [0, seq_len) of every GQA layer, compressed-KV and rope-key rows [0, seq_len) of every MLA
