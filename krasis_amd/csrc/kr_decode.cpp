@@ -1055,29 +1055,29 @@ extern "C" int kr_decode_set_option(kr_decode_store* s, const char* name, int va
     if (!strcmp(name, "pfm_timing")) { s->opt_pfm_timing = value != 0; return KR_OK; }
     if (!strcmp(name, "generate_lookahead")) { s->opt_gen_lookahead = value != 0; return KR_OK; }
     if (!strcmp(name, "multi_sample_loop")) { s->opt_multi_sample_loop = value != 0; return KR_OK; }
-    if (!strcmp(name, "multi_attn_fast")) { s->opt_multi_attn_fast = value != 0; return KR_OK; }
-    if (!strcmp(name, "multi_attn_fast_paged")) { s->opt_multi_attn_fast_paged = value != 0; return KR_OK; }    // "multi_attn_fast" that also reads paged slots, through the page table (docs/design/23-multi-attn-fast-paged.md); on flat slots the same thing
-    if (!strcmp(name, "multi_mla_fast")) { s->opt_multi_mla_fast = value != 0; return KR_OK; }                  // the MLA layers of every batched step run split-KV flash-decode over slots longer than mla_split_min, flat or paged (docs/design/24-multi-mla-fast.md)
-    if (!strcmp(name, "multi_extend_la_chunk")) { s->opt_multi_extend_la_chunk = value != 0; return KR_OK; }    // a run of >= 64 tokens entering a slot (extend_multi / prefill_slot) takes the prompt pass's chunked delta rule in its linear-attention layers (docs/design/26-multi-extend-la-chunk.md)
-    if (!strcmp(name, "multi_extend_exact_mfma")) { s->opt_multi_extend_exact_mfma = value != 0; return KR_OK; }     // a run of >= 2 tokens entering a slot (extend_multi / prefill_slot) takes the exact prompt pass's matrix-core scores, softmax and P.V over the slot, flat or paged: same bits as the per-row kernel (docs/design/28-multi-extend-exact-mfma.md)
-    if (!strcmp(name, "multi_extend_mla_exact_mfma")) { s->opt_multi_extend_mla_exact_mfma = value != 0; return KR_OK; }     // a run of >= 2 tokens entering a slot (extend_multi / prefill_slot) takes the exact MLA prompt pass's matrix-core scores, softmax and P.V over the slot's latent rows, flat or paged: same bits as the per-row kernel (docs/design/29-multi-extend-mla-exact-mfma.md)
-    if (!strcmp(name, "multi_attn_exact_split")) { s->opt_multi_attn_exact_split = value != 0; return KR_OK; }      // the exact per-slot GQA attention of every batched pass (steps, verify passes, the unit rows of extends) as scores / softmax / P.V launches spread over positions, heads and head-dim slices: same bits as the one kernel (docs/design/30-multi-attn-exact-split.md)
+    if (!strcmp(name, "multi_attn_fast")) { s->mopt.attn_fast = value != 0; return KR_OK; }
+    if (!strcmp(name, "multi_attn_fast_paged")) { s->mopt.attn_fast_paged = value != 0; return KR_OK; }    // "multi_attn_fast" that also reads paged slots, through the page table (docs/design/23-multi-attn-fast-paged.md); on flat slots the same thing
+    if (!strcmp(name, "multi_mla_fast")) { s->mopt.mla_fast = value != 0; return KR_OK; }                  // the MLA layers of every batched step run split-KV flash-decode over slots longer than mla_split_min, flat or paged (docs/design/24-multi-mla-fast.md)
+    if (!strcmp(name, "multi_extend_la_chunk")) { s->mopt.extend_la_chunk = value != 0; return KR_OK; }    // a run of >= 64 tokens entering a slot (extend_multi / prefill_slot) takes the prompt pass's chunked delta rule in its linear-attention layers (docs/design/26-multi-extend-la-chunk.md)
+    if (!strcmp(name, "multi_extend_exact_mfma")) { s->mopt.extend_exact_mfma = value != 0; return KR_OK; }     // a run of >= 2 tokens entering a slot (extend_multi / prefill_slot) takes the exact prompt pass's matrix-core scores, softmax and P.V over the slot, flat or paged: same bits as the per-row kernel (docs/design/28-multi-extend-exact-mfma.md)
+    if (!strcmp(name, "multi_extend_mla_exact_mfma")) { s->mopt.extend_mla_exact_mfma = value != 0; return KR_OK; }     // a run of >= 2 tokens entering a slot (extend_multi / prefill_slot) takes the exact MLA prompt pass's matrix-core scores, softmax and P.V over the slot's latent rows, flat or paged: same bits as the per-row kernel (docs/design/29-multi-extend-mla-exact-mfma.md)
+    if (!strcmp(name, "multi_attn_exact_split")) { s->mopt.attn_exact_split = value != 0; return KR_OK; }      // the exact per-slot GQA attention of every batched pass (steps, verify passes, the unit rows of extends) as scores / softmax / P.V launches spread over positions, heads and head-dim slices: same bits as the one kernel (docs/design/30-multi-attn-exact-split.md)
     if (!strcmp(name, "multi_attn_exact_split_min")) {      // the smallest number of positions (the pass's longest per-row attention) from which "multi_attn_exact_split" applies; both forms give the same bits
         if (value < 1) return kr_fail(KR_ERR_VALUE, "multi_attn_exact_split_min %d: at least 1", value);
-        s->opt_multi_attn_exact_split_min = value; return KR_OK;
+        s->mopt.attn_exact_split_min = value; return KR_OK;
     }
-    if (!strcmp(name, "multi_mla_exact_split")) { s->opt_multi_mla_exact_split = value != 0; return KR_OK; }      // the exact per-slot MLA attention of every batched pass (steps, verify passes, the unit rows of extends) as scores / softmax / weighted-sum launches spread over positions, heads and latent slices: same bits as the one kernel (docs/design/31-multi-mla-exact-split.md)
-    if (!strcmp(name, "multi_extend_la_exact")) { s->opt_multi_extend_la_exact = value != 0; return KR_OK; }      // a run of >= "multi_extend_la_exact_min" tokens entering a slot (extend_multi / prefill_slot) takes the staged exact form of the prompt pass in its linear-attention layers: same bits as the run kernels (docs/design/36-multi-extend-la-exact.md)
+    if (!strcmp(name, "multi_mla_exact_split")) { s->mopt.mla_exact_split = value != 0; return KR_OK; }      // the exact per-slot MLA attention of every batched pass (steps, verify passes, the unit rows of extends) as scores / softmax / weighted-sum launches spread over positions, heads and latent slices: same bits as the one kernel (docs/design/31-multi-mla-exact-split.md)
+    if (!strcmp(name, "multi_extend_la_exact")) { s->mopt.extend_la_exact = value != 0; return KR_OK; }      // a run of >= "multi_extend_la_exact_min" tokens entering a slot (extend_multi / prefill_slot) takes the staged exact form of the prompt pass in its linear-attention layers: same bits as the run kernels (docs/design/36-multi-extend-la-exact.md)
     if (!strcmp(name, "multi_extend_la_exact_min")) {      // the shortest run that is staged; both forms give the same bits
         if (value < 2 || value > 1024) return kr_fail(KR_ERR_VALUE, "multi_extend_la_exact_min %d: must be in [2, 1024]", value);
-        s->opt_multi_extend_la_exact_min = value; return KR_OK;
+        s->mopt.extend_la_exact_min = value; return KR_OK;
     }
     if (!strcmp(name, "multi_mla_exact_split_min")) {      // the smallest number of positions (the pass's longest per-row MLA attention) from which "multi_mla_exact_split" applies; both forms give the same bits
         if (value < 1) return kr_fail(KR_ERR_VALUE, "multi_mla_exact_split_min %d: at least 1", value);
-        s->opt_multi_mla_exact_split_min = value; return KR_OK;
+        s->mopt.mla_exact_split_min = value; return KR_OK;
     }
-    if (!strcmp(name, "multi_extend_flash")) { s->opt_multi_extend_flash = value != 0; return KR_OK; }          // a run of >= 2 tokens entering a slot (extend_multi / prefill_slot) takes the prompt pass's causal flash attention over the slot, flat or paged (docs/design/25-multi-extend-flash.md)
-    if (!strcmp(name, "multi_extend_mla_flash")) { s->opt_multi_extend_mla_flash = value != 0; return KR_OK; }  // a run of >= 2 tokens entering a slot (extend_multi / prefill_slot) takes the prompt pass's causal MLA flash attention over the slot's latent rows, flat or paged (docs/design/27-multi-extend-mla-flash.md)
+    if (!strcmp(name, "multi_extend_flash")) { s->mopt.extend_flash = value != 0; return KR_OK; }          // a run of >= 2 tokens entering a slot (extend_multi / prefill_slot) takes the prompt pass's causal flash attention over the slot, flat or paged (docs/design/25-multi-extend-flash.md)
+    if (!strcmp(name, "multi_extend_mla_flash")) { s->mopt.extend_mla_flash = value != 0; return KR_OK; }  // a run of >= 2 tokens entering a slot (extend_multi / prefill_slot) takes the prompt pass's causal MLA flash attention over the slot's latent rows, flat or paged (docs/design/27-multi-extend-mla-flash.md)
     if (!strcmp(name, "gguf_exact_pass")) { s->opt_gguf_exact_pass = value != 0; return KR_OK; }              // native-GGUF MoE layers of every multi-row pass in the exact forms; lifts the GGUF refusal of the slot and speculation entry points (docs/design/20-gguf-exact-pass.md)
     if (!strcmp(name, "gguf_exact_grouped")) { s->opt_gguf_exact_grouped = value != 0; return KR_OK; }        // "gguf_exact_pass": 0 = the streaming kernels for every block type (A/B and test hook; same bits)
     if (!strcmp(name, "pass_few_rows")) { s->opt_pass_few_rows = value != 0; return KR_OK; }                  // a multi-row pass of at most "pass_few_rows_max" token rows takes the few-row streaming matvec and the decode step's expert launches: same bits (docs/design/34-pass-few-rows.md)

@@ -8,6 +8,7 @@
 #include "kr_decode_ops.h"
 #include "kr_engine_internal.h"
 #include "kr_multi.h"
+#include "kr_multi_opts.h"
 #include "kr_page_pool.h"
 #include "kr_spec.h"
 
@@ -52,7 +53,7 @@ struct kr_multi_state {
     DevBuf rows, ids, logits, scores, scratch; // step: [slots | tokens | positions] (device), greedy ids, [n][vocab] logits, attention scores, the arena
     DevBuf fd_o, fd_ml; bool fd_ready = false; // "multi_attn_fast": split-KV partials [n][nkv][chunks][G][hd] and (max, sum) [n][nh][chunks][2] of one GQA layer, sized by the step's longest row; the kernels' LDS windows are raised
     DevBuf tiles;                              // every tile table of a pass, one upload (kr_multi_plan.h: the plan's vector; its spans are relative to this buffer)
-    bool pf_ready = false, mf_ready = false, lc_ready = false;   // "multi_extend_flash" / "multi_extend_mla_flash" / "multi_extend_la_chunk": the LDS windows of the run kernels are raised (kr_exact_refuse, once per slot set)
+    bool pf_ready = false, mf_ready = false, lc_ready = false;   // "multi_extend_flash" / "multi_extend_mla_flash" / "multi_extend_la_chunk": the LDS windows of the run kernels are raised (kr_option_rules, once per slot set)
     DevBuf lc_scratch;                         // "multi_extend_la_chunk": the rule's scratch of one layer, sized by the pass's sub-chunks
     DevBuf xm_rows;                            // "multi_extend_exact_mfma" / "multi_extend_mla_exact_mfma": 1 / sum [n * nh] and the row maxima per 32 positions [n * nh][sc_ld / 32] of the pass's score rows
     bool mla_fd_ready = false;               // "multi_mla_fast": the partials of one MLA layer, [n][chunks][nh][klr] and [n][nh][chunks][2], share fd_o / fd_ml (sized for the larger need); the kernels' LDS windows are raised
@@ -107,20 +108,7 @@ struct kr_decode_store {
     int opt_multi_sample_loop = 0;               // kr_decode_set_option("multi_sample_loop"): every sampled row of a multi-sequence step takes the single-row sampler, one row after another (A/B and test hook; same tokens)
     int opt_gguf_exact_pass = 0;                 // kr_decode_set_option("gguf_exact_pass"): every multi-row pass runs native-GGUF MoE layers through the exact forms (KR_PF_SET_GGUF_EXACT, docs/design/20-gguf-exact-pass.md): a row carries the bits of kr_decode_step, and the slot / speculation entry points accept such a store
     int opt_gguf_exact_grouped = 1;              // ... 0 = through the streaming kernels for every block type (A/B and test hook; same bits)
-    int opt_multi_attn_fast_paged = 0;           // kr_decode_set_option("multi_attn_fast_paged"): "multi_attn_fast" over flat and paged slots alike, the split-KV kernels of paged slots read the pools through the page table (docs/design/23-multi-attn-fast-paged.md); governs when both are set
-    int opt_multi_attn_fast = 0;                 // kr_decode_set_option("multi_attn_fast"): the GQA layers of every batched multi-sequence step run split-KV flash-decode over slots longer than gqa_split_min (tolerance form, docs/design/16-multi-attn-fast.md); the mode bits stay refused
-    int opt_multi_mla_fast = 0;                  // kr_decode_set_option("multi_mla_fast"): the MLA layers of every batched multi-sequence step run split-KV flash-decode over slots longer than mla_split_min, flat or paged (tolerance form, docs/design/24-multi-mla-fast.md); the mode bits stay refused
-    int opt_multi_extend_flash = 0;              // kr_decode_set_option("multi_extend_flash"): in a non-verify batched pass the GQA layers give every run of >= 2 tokens causal flash attention over its slot, flat or paged -- the bits of the KR_ATTN_FAST prompt pass (tolerance form, docs/design/25-multi-extend-flash.md); runs of one token keep what they had; the mode bits stay refused
-    int opt_multi_extend_la_chunk = 0;           // kr_decode_set_option("multi_extend_la_chunk"): in a non-verify batched pass the linear-attention layers give every run of >= 64 tokens the chunked delta rule of the KR_ATTN_FAST prompt pass, fused form -- its bits (tolerance form, docs/design/26-multi-extend-la-chunk.md); shorter runs keep the exact run kernels; the mode bits stay refused
-    int opt_multi_attn_exact_split = 0;          // kr_decode_set_option("multi_attn_exact_split"): a batched pass whose per-row GQA kernels attend over at least opt_multi_attn_exact_split_min positions launches the exact per-slot attention as scores / softmax / P.V kernels spread over positions, heads and head-dim slices (kr_multi_split.hip) -- bit for bit the one kernel's result (docs/design/30-multi-attn-exact-split.md)
-    int opt_multi_attn_exact_split_min = 512;    // kr_decode_set_option("multi_attn_exact_split_min"), >= 1: the smallest attn_pos + 1 of a pass that takes the split (a measured default: profiles/multi_attn_exact_split.txt)
-    int opt_multi_extend_la_exact = 0;           // kr_decode_set_option("multi_extend_la_exact"): in a non-verify batched pass the linear-attention layers give every run of >= opt_multi_extend_la_exact_min tokens the staged exact form of the store's own prompt pass (kr_multi_la_exact.hip) -- bit for bit the run kernels' result (docs/design/36-multi-extend-la-exact.md); shorter runs and unit rows keep the run kernels
-    int opt_multi_extend_la_exact_min = 8;       // kr_decode_set_option("multi_extend_la_exact_min"), 2 .. 1024: the shortest run that is staged (a measured default: profiles/multi_extend_la_exact.txt)
-    int opt_multi_mla_exact_split = 0;           // kr_decode_set_option("multi_mla_exact_split"): a batched pass whose per-row MLA kernels attend over at least opt_multi_mla_exact_split_min positions launches the exact per-slot MLA attention as scores / softmax / weighted-sum kernels spread over positions, heads and latent slices (kr_multi_mla_split.hip) -- bit for bit the one kernel's result (docs/design/31-multi-mla-exact-split.md)
-    int opt_multi_mla_exact_split_min = 512;     // kr_decode_set_option("multi_mla_exact_split_min"), >= 1: the smallest mla_pos + 1 of a pass that takes the split (a measured default: profiles/multi_mla_exact_split.txt)
-    int opt_multi_extend_exact_mfma = 0;         // kr_decode_set_option("multi_extend_exact_mfma"): in a non-verify batched pass the GQA layers give every run of >= 2 tokens the exact prompt pass's three passes over its slot, flat or paged -- scores and P.V on the f32 matrix cores, bit for bit the per-row kernel's result (docs/design/28-multi-extend-exact-mfma.md); runs of one token keep what they had; refused together with "multi_extend_flash"
-    int opt_multi_extend_mla_exact_mfma = 0;     // kr_decode_set_option("multi_extend_mla_exact_mfma"): in a non-verify batched pass the MLA layers give every run of >= 2 tokens the exact MLA prompt pass's three passes over its slot, flat or paged -- scores and P.V on the f32 matrix cores, bit for bit the per-row kernel's result (docs/design/29-multi-extend-mla-exact-mfma.md); runs of one token keep what they had; refused together with "multi_extend_mla_flash"
-    int opt_multi_extend_mla_flash = 0;          // kr_decode_set_option("multi_extend_mla_flash"): in a non-verify batched pass the MLA layers give every run of >= 2 tokens causal flash attention over its slot's latent rows, flat or paged -- the bits of the KR_ATTN_FAST prompt pass (tolerance form, docs/design/27-multi-extend-mla-flash.md); runs of one token keep what they had; the mode bits stay refused
+    KrMultiOpts mopt;                            // kr_decode_set_option("multi_..."): the opt-in forms of the batched pass over device slots, each described on its field (kr_multi_opts.h)
     int opt_pass_few_rows = 0;                   // kr_decode_set_option("pass_few_rows"): a multi-row pass of at most opt_pass_few_rows_max token rows (prefill / verify: n_tokens; slot entry points: the sum of the counts) runs its projections on the few-row streaming matvec (kr_rows_matvec.hip) and its INT4 / INT8 routed experts as the decode step's three launches -- bit for bit what it gives without the option (docs/design/34-pass-few-rows.md); KR_GEMM_FAST passes and larger passes keep their GEMMs
     int opt_pass_few_rows_max = 16;              // kr_decode_set_option("pass_few_rows_max"), 1 .. 16: the most token rows of a pass that takes the few-row kernels (a measured default: profiles/pass_few_rows.txt)
     int opt_pass_few_rows_group = 0;             // kr_decode_set_option("pass_few_rows_group"), 0 .. 16: the most rows a workgroup of the few-row matvec holds, 0 = chosen per launch (kr_rows_plan.h; A/B and test hook, same bits)
@@ -164,13 +152,9 @@ int kr_moe_prefill_prepare(kr_engine* e, int layer, int fast, int routed_only, h
 void kr_standalone_release(kr_decode_store* s);
 int kr_exact_refuse(kr_decode_store* s, bool slots);   // kr_decode_prefill.cpp: KR_OK when an exact pass can run on this store -- speculative decoding on its own sequence, or (slots) the multi-sequence step
 int kr_spec_refuse(kr_decode_store* s);          // kr_exact_refuse(s, false)
-bool paged_refused(const kr_decode_store* s);    // kr_decode_prefill.cpp: paged slots under "multi_attn_fast" alone -- what paged_refuse (kr_decode_multi.cpp) refuses and the options' refusals below stand back for
+bool paged_refused(const kr_decode_store* s);    // kr_decode_prefill.cpp: paged slots under "multi_attn_fast" alone -- what paged_refuse (kr_decode_multi.cpp) refuses and the rules of kr_option_rules stand back for
+int kr_option_rules(kr_decode_store* s, bool prepare);   // kr_decode_prefill.cpp: the one walk of the slot options' ordered rule list, behind kr_exact_refuse(s, true) -- its refusals, or (prepare, once they have all passed) the LDS windows of the options that are set
 bool has_attn(const kr_decode_store* s, int kind);   // kr_decode_prefill.cpp: the store has a layer of this attention kind (ATTN_*)
-int kr_xm_refuse(kr_decode_store* s);            // kr_decode_prefill.cpp: the "multi_extend_exact_mfma" option's refusals, asked by multi_refuse behind kr_exact_refuse(s, true)
-int kr_xs_refuse(kr_decode_store* s);            // kr_decode_prefill.cpp: the "multi_attn_exact_split" option's refusal, asked by multi_refuse behind kr_mla_xm_refuse(s)
-int kr_mla_xm_refuse(kr_decode_store* s);        // kr_decode_prefill.cpp: the "multi_extend_mla_exact_mfma" option's refusals, asked by multi_refuse behind kr_xm_refuse(s)
-int kr_la_exact_refuse(kr_decode_store* s);      // kr_decode_prefill.cpp: the "multi_extend_la_exact" option's refusal, asked by multi_refuse behind kr_mla_xs_refuse(s)
-int kr_mla_xs_refuse(kr_decode_store* s);        // kr_decode_prefill.cpp: the "multi_mla_exact_split" option's refusal, asked by multi_refuse last, behind kr_xs_refuse(s)
 int kr_spec_pending_fail(kr_decode_store* s);    // KR_ERR_STATE while a verify waits for its commit
 int kr_standalone_cancelled(kr_decode_store* s);
 // kr_decode_prefill.cpp: the layers + final norm + lm_head GEMM of the multi-sequence pass on `st` in s->multi's arena: n_rows token rows in n_runs runs of

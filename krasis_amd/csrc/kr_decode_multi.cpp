@@ -42,15 +42,11 @@ int multi_ready(kr_decode_store* s) {
     return KR_OK;
 }
 // what the multi-sequence step does not run: a pending verify of the store's own sequence, then what kr_exact_refuse (kr_decode_prefill.cpp) lists for the
-// slots -- the clauses of every exact pass and, among them, those of the per-slot kernels
+// slots -- the base clauses of every exact pass and, among them, those of the per-slot kernels -- then the slot options' ordered rule list (kr_option_rules)
 int multi_refuse(kr_decode_store* s) {
     if (int rc = kr_spec_pending_fail(s)) return rc;
     if (int rc = kr_exact_refuse(s, true)) return rc;
-    if (int rc = kr_xm_refuse(s)) return rc;      // "multi_extend_exact_mfma": a check of its own, behind every earlier clause (kr_decode_prefill.cpp)
-    if (int rc = kr_mla_xm_refuse(s)) return rc;  // "multi_extend_mla_exact_mfma": the same, behind that one
-    if (int rc = kr_xs_refuse(s)) return rc;      // "multi_attn_exact_split": the same, behind that one
-    if (s->opt_multi_extend_la_exact) { if (int rc = kr_mla_xs_refuse(s)) return rc; return kr_la_exact_refuse(s); }      // "multi_extend_la_exact": the same, behind the last one; with the option off the chain ends where it always did
-    return kr_mla_xs_refuse(s);                   // "multi_mla_exact_split": the same, behind that one
+    return kr_option_rules(s, false);
 }
 int need_slots(kr_decode_store* s) {
     if (!s->multi || s->multi->n_slots == 0) return kr_fail(KR_ERR_STATE, "no sequence slots: call kr_decode_slots_create first");
@@ -64,7 +60,8 @@ int multi_begin(kr_decode_store* s) {
     if (int rc = multi_ready(s)) return rc;
     if (int rc = need_slots(s)) return rc;
     if (s->multi->v_pending) return kr_fail(KR_ERR_STATE, "a verify over slots is pending: call kr_decode_commit_multi first");
-    return multi_refuse(s);
+    if (int rc = multi_refuse(s)) return rc;
+    return kr_option_rules(s, true);      // preparing is not refusing: the options' LDS windows, once every refusal has passed
 }
 int slot_in_range(kr_decode_store* s, int slot) {
     return slot < 0 || slot >= s->multi->n_slots ? kr_fail(KR_ERR_VALUE, "slot %d out of range [0, %d)", slot, s->multi->n_slots) : KR_OK;
@@ -148,7 +145,7 @@ int check_args(kr_decode_store* s, const Rows& r, int extra) {
     int mla_rope = 0; bool has_mla = false;
     for (const DLayer& L : s->layers) if (L.attn == ATTN_MLA) { mla_rope = has_mla ? std::min(mla_rope, L.mla_rope_seq) : L.mla_rope_seq; has_mla = true; }
     // "multi_mla_fast" over long slots: the merge has one thread per chunk (kr_multi_pass takes the same chunk size)
-    const int mla_chunk = s->opt_multi_mla_fast && has_mla && M.max_seq > s->mla_split_min ? kr_mla_flash_decode_chunk(M.max_seq) : 0;
+    const int mla_chunk = s->mopt.mla_fast && has_mla && M.max_seq > s->mla_split_min ? kr_mla_flash_decode_chunk(M.max_seq) : 0;
     int total = 0;
     for (int i = 0; i < r.n; i++) {      // the runs first: everything below indexes tokens by them
         if (r.cnt(i) < 1) return kr_fail(KR_ERR_VALUE, "row %d: a run of %d tokens, must be at least 1", i, r.cnt(i));

@@ -136,7 +136,7 @@ static KrMultiLaArgs multi_la_args(kr_decode_store* s, size_t li, const Scratch&
         const KrMultiLaCommit& R = M.v_host[(size_t)M.v_la_of[li]];
         m.rec_x = (float*)R.rec_x; m.rec_k = (float*)R.rec_k; m.rec_v = (float*)R.rec_v; m.rec_ge = (float*)R.rec_ge; m.rec_be = (float*)R.rec_be;
     }
-    if (pl.lx_nruns) m.lx_min = s->opt_multi_extend_la_exact_min;      // "multi_extend_la_exact": the run kernels leave the staged runs (multi_lx_args)
+    if (pl.lx_nruns) m.lx_min = s->mopt.extend_la_exact_min;      // "multi_extend_la_exact": the run kernels leave the staged runs (multi_lx_args)
     if (pl.lc_nruns) {      // "multi_extend_la_chunk": the runs of >= 64 tokens take the chunked rule, its output rows in B.recur ahead of the gated norm
         m.lc_runs = P.table(pl.lc_runs); m.lc_tiles = P.table(pl.lc_tiles); m.lc_nruns = pl.lc_nruns; m.lc_ntiles = pl.lc_ntiles; m.lc_short = pl.lc_short;
         m.lc_scratch = P.lc_scratch; m.lc_o = B.recur;
@@ -677,7 +677,7 @@ int kr_spec_pending_fail(kr_decode_store* s) {
 
 // paged slots under "multi_attn_fast" alone: the entry point refuses the call with the words it always had (paged_refuse, kr_decode_multi.cpp), unless its
 // argument check does first; every refusal of a later option stands back there, so that one stays ahead of theirs
-bool paged_refused(const kr_decode_store* s) { return s->multi && s->multi->pg.paged() && s->opt_multi_attn_fast && !s->opt_multi_attn_fast_paged; }
+bool paged_refused(const kr_decode_store* s) { return s->multi && s->multi->pg.paged() && s->mopt.attn_fast && !s->mopt.attn_fast_paged; }
 // the store has a layer of this attention kind (ATTN_*)
 bool has_attn(const kr_decode_store* s, int kind) {
     for (const DLayer& L : s->layers) if (L.attn == kind) return true;
@@ -687,16 +687,17 @@ bool has_attn(const kr_decode_store* s, int kind) {
 // what no exact pass over this store runs: tolerance modes, expert parallelism, MoE layers without an engine or with native-GGUF experts (unless the
 // "gguf_exact_pass" option gives those an exact pass, docs/design/20-gguf-exact-pass.md), geometries the
 // verify-form kernels do not cover.  slots: the pass over device slots (multi_refuse, kr_decode_multi.cpp), whose messages start with another noun and whose
-// per-slot kernels refuse more; its clauses sit here, each in its place, because the order of the refusals is part of both contracts
+// per-slot kernels refuse more; its base clauses sit here, each in its place, because the order of the refusals is part of both contracts; the slot options' own
+// rules follow in kr_option_rules below (the "multi_attn_fast" MLA clause apart: its place ahead of the expert-parallelism clause can be seen)
 int kr_exact_refuse(kr_decode_store* s, bool slots) {
     const char *the = slots ? "the " : "", *what = slots ? "multi-sequence step" : "speculative decoding";
     if (s->attn_fast || s->gemm_fast || s->decode_fast)
         return kr_fail(KR_ERR_STATE, "%s%s is exact-mode only: the attention mode has tolerance bits set (%d)", the, what, s->attn_fast | s->gemm_fast << 1 | s->decode_fast << 2);
-    if (slots && (s->opt_multi_attn_fast || s->opt_multi_attn_fast_paged))
+    if (slots && (s->mopt.attn_fast || s->mopt.attn_fast_paged))
         for (size_t i = 0; i < s->layers.size(); i++)
             if (s->layers[i].attn == ATTN_MLA)
                 return kr_fail(KR_ERR_STATE, "the \"%s\" option covers GQA layers only: layer %zu is MLA (set the option to 0 for the exact step)",
-                               s->opt_multi_attn_fast_paged ? "multi_attn_fast_paged" : "multi_attn_fast", i);
+                               s->mopt.attn_fast_paged ? "multi_attn_fast_paged" : "multi_attn_fast", i);
     kr_engine* e = s->eng;
     if (e->ep) return kr_fail(KR_ERR_STATE, "%s%s does not run under expert parallelism", the, what);
     for (const DLayer& L : s->layers) {
@@ -714,135 +715,94 @@ int kr_exact_refuse(kr_decode_store* s, bool slots) {
         if (slots && L.attn == ATTN_GQA && ((L.hd != 64 && L.hd != 128 && L.hd != 256) || L.nkv < 1 || L.nh % L.nkv || (L.nh / L.nkv) * (L.hd + 64) > 12288))
             return kr_fail(KR_ERR_VALUE, "%s: GQA geometry nh %d nkv %d head_dim %d not covered (head_dim 64 / 128 / 256)", what, L.nh, L.nkv, L.hd);
     }
-    // "multi_mla_fast", behind everything the step refused before the option existed.  A store without an MLA layer: an option that silently does nothing is a
-    // trap.  More than 64 heads, or a geometry outside the flash kernel's: the single-sequence launcher falls back to the exact kernels there
-    // (kr_launch_mla_flash_decode), so there would be no fast step to be identical to
-    if (slots && s->opt_multi_mla_fast) {
-        for (const DLayer& L : s->layers)
-            if (L.attn == ATTN_MLA && !kr_multi_mla_fd_ok(L.nh, L.klr, L.rd))
-                return kr_fail(KR_ERR_VALUE, "multi_mla_fast: MLA geometry heads %d kv_lora_rank %d rope %d not covered (at most 64 heads, kv_lora_rank 512 / 256, rope 64)", L.nh, L.klr, L.rd);
-        if (!has_attn(s, ATTN_MLA)) return kr_fail(KR_ERR_STATE, "the \"multi_mla_fast\" option covers MLA layers only: this store has none (set the option to 0 for the exact step)");
-    }
-    // "multi_extend_mla_flash", behind everything refused before the option existed.  A store without an MLA layer: an option that silently does nothing is a trap.
-    // The run kernel's geometry rule (kr_launch_mla_flash's: kv_lora_rank 512 / 256, rope 64, any head count) is kr_multi_mla_ok's, which the loop above has asked
-    // of every MLA layer.  The LDS windows of the run kernel's instantiations are raised here, once per slot set: a refusal leaves nothing reserved or advanced
-    if (slots && s->opt_multi_extend_mla_flash && !paged_refused(s)) {
-        if (!has_attn(s, ATTN_MLA)) return kr_fail(KR_ERR_STATE, "the \"multi_extend_mla_flash\" option covers MLA layers only: this store has none (set the option to 0 for the exact pass)");
-        if (s->multi && !s->multi->mf_ready) {
-            KR_HIP(hipSetDevice(e->device));
-            for (const DLayer& L : s->layers)
-                if (L.attn == ATTN_MLA && kr_multi_mla_pf_prepare(L.klr, s->multi->kv_fp8, s->multi->pg.paged()))
-                    return kr_fail(KR_ERR_HIP, "multi_extend_mla_flash: LDS window of the run kernel refused (kv_lora_rank %d)", L.klr);
-            s->multi->mf_ready = true;
-        }
-    }
-    // "multi_extend_flash", behind everything refused before the option existed.  An MLA layer: its runs would stay exact beside flash GQA runs, and no
-    // single-sequence pass is like that.  No GQA layer: an option that silently does nothing is a trap.  A geometry outside the prompt pass's flash kernels is an
-    // error, not a fall-back.  The LDS windows of the run kernels are raised here, once per slot set: a refusal leaves nothing reserved or advanced
-    // (it stands back where paged_refused holds, like the clause above and the one below)
-    if (slots && s->opt_multi_extend_flash && !paged_refused(s)) {
-        for (size_t i = 0; i < s->layers.size(); i++)
-            if (s->layers[i].attn == ATTN_MLA)
-                return kr_fail(KR_ERR_STATE, "the \"multi_extend_flash\" option covers GQA layers only: layer %zu is MLA (set the option to 0 for the exact pass)", i);
-        if (!has_attn(s, ATTN_GQA)) return kr_fail(KR_ERR_STATE, "the \"multi_extend_flash\" option covers GQA layers only: this store has none (set the option to 0 for the exact pass)");
-        for (const DLayer& L : s->layers)
-            if (L.attn == ATTN_GQA && !kr_pfm_gqa_flash_ok(L.nh, L.nkv, L.hd))
-                return kr_fail(KR_ERR_VALUE, "multi_extend_flash: GQA geometry nh %d nkv %d head_dim %d not covered (heads per KV head must divide 128, head_dim 64 / 128 / 256)", L.nh, L.nkv, L.hd);
-        if (s->multi && !s->multi->pf_ready) {
-            KR_HIP(hipSetDevice(e->device));
-            for (const DLayer& L : s->layers)
-                if (L.attn == ATTN_GQA && kr_multi_pf_prepare(L.hd, s->multi->kv_fp8, s->multi->pg.paged()))
-                    return kr_fail(KR_ERR_HIP, "multi_extend_flash: LDS window of the run kernel refused (head_dim %d)", L.hd);
-            s->multi->pf_ready = true;
-        }
-    }
-    // "multi_extend_la_chunk", behind everything refused before the option existed, and standing back like the clause above.  No linear-attention layer: an option
-    // that silently does nothing is a trap.  An MLA layer: its runs would stay exact beside chunked linear-attention runs, and no single-sequence pass is like
-    // that.  A layer outside the chunked rule's geometry is an error, not a fall-back to the run kernels.  The LDS windows of the two kernels are raised here, once
-    // per slot set: a refusal leaves nothing advanced
-    if (slots && s->opt_multi_extend_la_chunk && !paged_refused(s)) {
-        if (!has_attn(s, ATTN_LA)) return kr_fail(KR_ERR_STATE, "the \"multi_extend_la_chunk\" option covers linear-attention layers only: this store has none (set the option to 0 for the exact pass)");
-        for (size_t i = 0; i < s->layers.size(); i++)
-            if (s->layers[i].attn == ATTN_MLA)
-                return kr_fail(KR_ERR_STATE, "the \"multi_extend_la_chunk\" option covers linear-attention layers only: layer %zu is MLA (set the option to 0 for the exact pass)", i);
-        for (const DLayer& L : s->layers)
-            if (L.attn == ATTN_LA && !kr_multi_lc_ok(L.dk, L.dv, L.nk, L.nv, s->weights[L.qkvz_wid]->rows))
-                return kr_fail(KR_ERR_VALUE, "multi_extend_la_chunk: linear-attention geometry nk %d nv %d dk %d dv %d not covered (dk = dv = 128, whole value-head groups per key head)", L.nk, L.nv, L.dk, L.dv);
-        if (s->multi && !s->multi->lc_ready) {
-            KR_HIP(hipSetDevice(e->device));
-            if (kr_multi_lc_prepare()) return kr_fail(KR_ERR_HIP, "multi_extend_la_chunk: LDS window of the chunked delta rule's kernels refused");
-            s->multi->lc_ready = true;
-        }
-    }
     return KR_OK;
 }
 int kr_spec_refuse(kr_decode_store* s) { return kr_exact_refuse(s, false); }
 
-// "multi_extend_exact_mfma" (docs/design/28-multi-extend-exact-mfma.md): what multi_refuse (kr_decode_multi.cpp) asks directly behind kr_exact_refuse(s, true), so
-// everything refused before the option existed is refused first and with the same words.  With "multi_extend_flash": two options claim the runs of >= 2 tokens.
-// No GQA layer: an option that silently does nothing is a trap.  A GQA layer outside the matrix-core passes' geometry is an error, not a fall-back to the per-row
-// kernel.  Nothing to prepare: the kernels' static LDS is below the default window.  It stands back where paged_refused holds, like its siblings
-int kr_xm_refuse(kr_decode_store* s) {
-    if (!s->opt_multi_extend_exact_mfma || paged_refused(s)) return KR_OK;
-    if (s->opt_multi_extend_flash)
-        return kr_fail(KR_ERR_STATE, "the \"multi_extend_exact_mfma\" and \"multi_extend_flash\" options both claim the runs of >= 2 tokens of the GQA layers: set one of them to 0");
-    if (!has_attn(s, ATTN_GQA)) return kr_fail(KR_ERR_STATE, "the \"multi_extend_exact_mfma\" option covers GQA layers only: this store has none (set the option to 0)");
-    for (const DLayer& L : s->layers) {
-        if (L.attn != ATTN_GQA) continue;
-        KrPfmGqaArgs g{};
-        g.nh = L.nh; g.nkv = L.nkv; g.hd = L.hd;
-        if (!kr_pfm_gqa_exact_mfma_ok(g))
-            return kr_fail(KR_ERR_VALUE, "multi_extend_exact_mfma: GQA geometry nh %d nkv %d head_dim %d not covered (heads per KV head must divide 32, head_dim 64 / 128 / 256; set the option to 0 for the per-row kernel)", L.nh, L.nkv, L.hd);
+// The slot options' refusals as ONE ordered list (docs/design/39-slot-option-rules.md), walked behind kr_exact_refuse(s, true), so everything refused before
+// an option existed is refused first and with the same words.  The order of the rules, and of the steps within a rule, is what a caller sees when two
+// options refuse one store: it is part of the contract (tests/test_multi_option_refusals_gpu.py).  A rule that is asked refuses, in this order: its rival
+// option being set too (two options claim the same rows); [geo_first: its geometry rule]; [mla_at 1: an MLA layer -- its runs would stay exact beside the
+// tolerance form, and no single-sequence pass is like that]; a store without a layer of its kind (an option that silently does nothing is a trap); [mla_at
+// 2: an MLA layer]; a layer of its kind outside its kernels' geometry (an error, never a fall-back).  stand_back: the rule is not asked where paged_refused
+// holds, so the entry point's paged refusal stays ahead of it.  tail: how the message ends its advice.  prepare / ready: the LDS windows of its run kernels,
+// raised once per slot set -- never by the refusing walk
+struct KrOptRule {
+    const char* name; int KrMultiOpts::*flag; int kind; bool stand_back;
+    const char* rival_name; int KrMultiOpts::*rival; const char* claim;
+    int mla_at; bool geo_first; const char* tail;
+    int (*geo)(const kr_decode_store* s, const DLayer& L);      // KR_OK, or the refusal of this layer
+    int (*prepare)(kr_decode_store* s); bool kr_multi_state::*ready;
+};
+static const char* const kr_kind_words[] = {"", "linear-attention", "GQA", "MLA"};      // by ATTN_*
+static const KrOptRule kr_opt_rules[] = {
+    // more than 64 heads, or a geometry outside the flash kernel's: the single-sequence launcher falls back to the exact kernels there (kr_launch_mla_flash_decode), so there would be no fast step to be identical to
+    {"multi_mla_fast", &KrMultiOpts::mla_fast, ATTN_MLA, false, nullptr, nullptr, nullptr, 0, true, " for the exact step",
+     [](const kr_decode_store*, const DLayer& L) { return kr_multi_mla_fd_ok(L.nh, L.klr, L.rd) ? KR_OK : kr_fail(KR_ERR_VALUE, "multi_mla_fast: MLA geometry heads %d kv_lora_rank %d rope %d not covered (at most 64 heads, kv_lora_rank 512 / 256, rope 64)", L.nh, L.klr, L.rd); },
+     nullptr, nullptr},
+    // the run kernel's geometry rule (kr_launch_mla_flash's: any head count) is kr_multi_mla_ok's, which kr_exact_refuse has asked of every MLA layer
+    {"multi_extend_mla_flash", &KrMultiOpts::extend_mla_flash, ATTN_MLA, true, nullptr, nullptr, nullptr, 0, false, " for the exact pass", nullptr,
+     [](kr_decode_store* s) {
+         for (const DLayer& L : s->layers)
+             if (L.attn == ATTN_MLA && kr_multi_mla_pf_prepare(L.klr, s->multi->kv_fp8, s->multi->pg.paged()))
+                 return kr_fail(KR_ERR_HIP, "multi_extend_mla_flash: LDS window of the run kernel refused (kv_lora_rank %d)", L.klr);
+         return (int)KR_OK;
+     }, &kr_multi_state::mf_ready},
+    {"multi_extend_flash", &KrMultiOpts::extend_flash, ATTN_GQA, true, nullptr, nullptr, nullptr, 1, false, " for the exact pass",
+     [](const kr_decode_store*, const DLayer& L) { return kr_pfm_gqa_flash_ok(L.nh, L.nkv, L.hd) ? KR_OK : kr_fail(KR_ERR_VALUE, "multi_extend_flash: GQA geometry nh %d nkv %d head_dim %d not covered (heads per KV head must divide 128, head_dim 64 / 128 / 256)", L.nh, L.nkv, L.hd); },
+     [](kr_decode_store* s) {
+         for (const DLayer& L : s->layers)
+             if (L.attn == ATTN_GQA && kr_multi_pf_prepare(L.hd, s->multi->kv_fp8, s->multi->pg.paged()))
+                 return kr_fail(KR_ERR_HIP, "multi_extend_flash: LDS window of the run kernel refused (head_dim %d)", L.hd);
+         return (int)KR_OK;
+     }, &kr_multi_state::pf_ready},
+    {"multi_extend_la_chunk", &KrMultiOpts::extend_la_chunk, ATTN_LA, true, nullptr, nullptr, nullptr, 2, false, " for the exact pass",
+     [](const kr_decode_store* s, const DLayer& L) { return kr_multi_lc_ok(L.dk, L.dv, L.nk, L.nv, s->weights[L.qkvz_wid]->rows) ? KR_OK : kr_fail(KR_ERR_VALUE, "multi_extend_la_chunk: linear-attention geometry nk %d nv %d dk %d dv %d not covered (dk = dv = 128, whole value-head groups per key head)", L.nk, L.nv, L.dk, L.dv); },
+     [](kr_decode_store*) { return kr_multi_lc_prepare() ? kr_fail(KR_ERR_HIP, "multi_extend_la_chunk: LDS window of the chunked delta rule's kernels refused") : (int)KR_OK; }, &kr_multi_state::lc_ready},
+    // the exact forms below have nothing to prepare: their kernels' LDS is below the default window
+    {"multi_extend_exact_mfma", &KrMultiOpts::extend_exact_mfma, ATTN_GQA, true, "multi_extend_flash", &KrMultiOpts::extend_flash, "the runs of >= 2 tokens of the GQA layers", 0, false, "",
+     [](const kr_decode_store*, const DLayer& L) {
+         KrPfmGqaArgs g{};
+         g.nh = L.nh; g.nkv = L.nkv; g.hd = L.hd;
+         return kr_pfm_gqa_exact_mfma_ok(g) ? KR_OK : kr_fail(KR_ERR_VALUE, "multi_extend_exact_mfma: GQA geometry nh %d nkv %d head_dim %d not covered (heads per KV head must divide 32, head_dim 64 / 128 / 256; set the option to 0 for the per-row kernel)", L.nh, L.nkv, L.hd);
+     }, nullptr, nullptr},
+    {"multi_extend_mla_exact_mfma", &KrMultiOpts::extend_mla_exact_mfma, ATTN_MLA, true, "multi_extend_mla_flash", &KrMultiOpts::extend_mla_flash, "the runs of >= 2 tokens of the MLA layers", 0, false, "",
+     [](const kr_decode_store*, const DLayer& L) { return kr_mla_exact_mfma_ok(L.nh, L.klr, L.rd) ? KR_OK : kr_fail(KR_ERR_VALUE, "multi_extend_mla_exact_mfma: MLA geometry heads %d kv_lora_rank %d rope %d not covered (the head count must divide 32, kv_lora_rank 512 / 256, rope 64; set the option to 0 for the per-row kernel)", L.nh, L.klr, L.rd); },
+     nullptr, nullptr},
+    // the two splits cover every geometry the one kernel covers, and the pass makes that kernel's checks either way
+    {"multi_attn_exact_split", &KrMultiOpts::attn_exact_split, ATTN_GQA, true, nullptr, nullptr, nullptr, 0, false, "", nullptr, nullptr, nullptr},
+    {"multi_mla_exact_split", &KrMultiOpts::mla_exact_split, ATTN_MLA, true, nullptr, nullptr, nullptr, 0, false, "", nullptr, nullptr, nullptr},
+    {"multi_extend_la_exact", &KrMultiOpts::extend_la_exact, ATTN_LA, true, "multi_extend_la_chunk", &KrMultiOpts::extend_la_chunk, "the long runs of the linear-attention layers", 0, false, "",
+     [](const kr_decode_store* s, const DLayer& L) { return kr_multi_lx_ok(L.dk, L.dv, L.nk, L.nv, s->weights[L.qkvz_wid]->rows) ? KR_OK : kr_fail(KR_ERR_VALUE, "multi_extend_la_exact: linear-attention geometry nk %d nv %d dk %d dv %d not covered (dk 64 / 128, dk <= dv <= 256, dv a multiple of 8, 16-byte in-projection rows, whole value-head groups per key head; set the option to 0 for the run kernels)", L.nk, L.nv, L.dk, L.dv); },
+     nullptr, nullptr},
+};
+// the one walk of the list.  prepare false: the refusals (multi_refuse).  prepare true: every refusal of the call has passed (multi_begin) and the rules that
+// are set and asked raise their LDS windows, once per slot set and outside kr_multi_pass.  Allocates nothing
+int kr_option_rules(kr_decode_store* s, bool prepare) {
+    const bool back = paged_refused(s);
+    for (const KrOptRule& r : kr_opt_rules) {
+        if (!(s->mopt.*r.flag) || (r.stand_back && back)) continue;
+        if (prepare) {
+            if (!r.prepare || !s->multi || s->multi.get()->*r.ready) continue;
+            KR_HIP(hipSetDevice(s->eng->device));
+            if (int rc = r.prepare(s)) return rc;
+            s->multi.get()->*r.ready = true;
+            continue;
+        }
+        const char* kind = kr_kind_words[r.kind];
+        auto geo = [&]() { for (const DLayer& L : s->layers) if (L.attn == r.kind) if (int rc = r.geo(s, L)) return rc; return (int)KR_OK; };
+        auto mla = [&]() {
+            for (size_t i = 0; i < s->layers.size(); i++)
+                if (s->layers[i].attn == ATTN_MLA) return kr_fail(KR_ERR_STATE, "the \"%s\" option covers %s layers only: layer %zu is MLA (set the option to 0%s)", r.name, kind, i, r.tail);
+            return (int)KR_OK;
+        };
+        if (r.rival && s->mopt.*r.rival) return kr_fail(KR_ERR_STATE, "the \"%s\" and \"%s\" options both claim %s: set one of them to 0", r.name, r.rival_name, r.claim);
+        if (r.geo && r.geo_first) if (int rc = geo()) return rc;
+        if (r.mla_at == 1) if (int rc = mla()) return rc;
+        if (!has_attn(s, r.kind)) return kr_fail(KR_ERR_STATE, "the \"%s\" option covers %s layers only: this store has none (set the option to 0%s)", r.name, kind, r.tail);
+        if (r.mla_at == 2) if (int rc = mla()) return rc;
+        if (r.geo && !r.geo_first) if (int rc = geo()) return rc;
     }
-    return KR_OK;
-}
-
-// "multi_extend_mla_exact_mfma" (docs/design/29-multi-extend-mla-exact-mfma.md): what multi_refuse asks behind kr_xm_refuse, so everything refused before the option
-// existed is refused first and with the same words.  With "multi_extend_mla_flash": two options claim the runs of >= 2 tokens of the MLA layers.  No MLA layer: an
-// option that silently does nothing is a trap.  An MLA layer outside the matrix-core passes' geometry (kr_mla_exact_mfma_ok, the prompt pass's own rule) is an
-// error, not a fall-back to the per-row kernel.  Nothing to prepare: the kernels' static LDS is below the default window.  It stands back where the entry point's
-// paged refusal applies, like kr_xm_refuse
-int kr_mla_xm_refuse(kr_decode_store* s) {
-    if (!s->opt_multi_extend_mla_exact_mfma || paged_refused(s)) return KR_OK;
-    if (s->opt_multi_extend_mla_flash)
-        return kr_fail(KR_ERR_STATE, "the \"multi_extend_mla_exact_mfma\" and \"multi_extend_mla_flash\" options both claim the runs of >= 2 tokens of the MLA layers: set one of them to 0");
-    if (!has_attn(s, ATTN_MLA)) return kr_fail(KR_ERR_STATE, "the \"multi_extend_mla_exact_mfma\" option covers MLA layers only: this store has none (set the option to 0)");
-    for (const DLayer& L : s->layers)
-        if (L.attn == ATTN_MLA && !kr_mla_exact_mfma_ok(L.nh, L.klr, L.rd))
-            return kr_fail(KR_ERR_VALUE, "multi_extend_mla_exact_mfma: MLA geometry heads %d kv_lora_rank %d rope %d not covered (the head count must divide 32, kv_lora_rank 512 / 256, rope 64; set the option to 0 for the per-row kernel)", L.nh, L.klr, L.rd);
-    return KR_OK;
-}
-
-// "multi_attn_exact_split" (docs/design/30-multi-attn-exact-split.md): what multi_refuse asks behind kr_mla_xm_refuse, so everything refused before the option existed
-// is refused first and with the same words.  No GQA layer: an option that silently does nothing is a trap.  Nothing else: the three launches cover every geometry
-// the one kernel covers, and the pass makes that kernel's checks either way.  It stands back where the entry point's paged refusal applies, like its siblings
-int kr_xs_refuse(kr_decode_store* s) {
-    if (!s->opt_multi_attn_exact_split || paged_refused(s)) return KR_OK;
-    if (!has_attn(s, ATTN_GQA)) return kr_fail(KR_ERR_STATE, "the \"multi_attn_exact_split\" option covers GQA layers only: this store has none (set the option to 0)");
-    return KR_OK;
-}
-
-// "multi_mla_exact_split" (docs/design/31-multi-mla-exact-split.md): what multi_refuse asks last, behind kr_xs_refuse, so everything refused before the option existed
-// is refused first and with the same words.  No MLA layer: an option that silently does nothing is a trap.  Nothing else: the three launches cover every geometry
-// the one kernel covers, and the pass makes that kernel's checks either way.  It stands back where the entry point's paged refusal applies, like its siblings
-int kr_mla_xs_refuse(kr_decode_store* s) {
-    if (!s->opt_multi_mla_exact_split || paged_refused(s)) return KR_OK;
-    if (!has_attn(s, ATTN_MLA)) return kr_fail(KR_ERR_STATE, "the \"multi_mla_exact_split\" option covers MLA layers only: this store has none (set the option to 0)");
-    return KR_OK;
-}
-
-// "multi_extend_la_exact" (docs/design/36-multi-extend-la-exact.md): what multi_refuse asks behind kr_mla_xs_refuse, so everything refused before the option existed
-// is refused first and with the same words.  With "multi_extend_la_chunk": two options claim the long runs of the linear-attention layers.  No such layer: an
-// option that silently does nothing is a trap.  A layer outside the staged kernels' geometry (kr_launch_pfm_la's own rule) is an error, not a fall-back to the run
-// kernels.  Nothing to prepare: the kernels' LDS is below the default window.  It stands back where the entry point's paged refusal applies, like its siblings
-int kr_la_exact_refuse(kr_decode_store* s) {
-    if (!s->opt_multi_extend_la_exact || paged_refused(s)) return KR_OK;
-    if (s->opt_multi_extend_la_chunk)
-        return kr_fail(KR_ERR_STATE, "the \"multi_extend_la_exact\" and \"multi_extend_la_chunk\" options both claim the long runs of the linear-attention layers: set one of them to 0");
-    if (!has_attn(s, ATTN_LA)) return kr_fail(KR_ERR_STATE, "the \"multi_extend_la_exact\" option covers linear-attention layers only: this store has none (set the option to 0)");
-    for (const DLayer& L : s->layers)
-        if (L.attn == ATTN_LA && !kr_multi_lx_ok(L.dk, L.dv, L.nk, L.nv, s->weights[L.qkvz_wid]->rows))
-            return kr_fail(KR_ERR_VALUE, "multi_extend_la_exact: linear-attention geometry nk %d nv %d dk %d dv %d not covered (dk 64 / 128, dk <= dv <= 256, dv a multiple of 8, 16-byte in-projection rows, whole value-head groups per key head; set the option to 0 for the run kernels)", L.nk, L.nv, L.dk, L.dv);
     return KR_OK;
 }
 
@@ -976,13 +936,7 @@ int kr_multi_pass(kr_decode_store* s, int n, int n_final, const int32_t* d_rows,
     if (int rc = pf_layout(s, (size_t)n, true, true, st, Lo)) return rc;
     // everything the pass decides, from plain values (kr_multi_plan.h, docs/design/32-multi-pass-plan.md); here: allocation, upload and launch
     KrMultiPlanOpts o{};
-    o.attn_fast = s->opt_multi_attn_fast || s->opt_multi_attn_fast_paged; o.mla_fast = s->opt_multi_mla_fast;
-    o.extend_flash = s->opt_multi_extend_flash; o.extend_mla_flash = s->opt_multi_extend_mla_flash; o.extend_la_chunk = s->opt_multi_extend_la_chunk;
-    o.extend_exact_mfma = s->opt_multi_extend_exact_mfma; o.extend_mla_exact_mfma = s->opt_multi_extend_mla_exact_mfma;
-    o.attn_exact_split = s->opt_multi_attn_exact_split; o.attn_exact_split_min = s->opt_multi_attn_exact_split_min;
-    o.mla_exact_split = s->opt_multi_mla_exact_split; o.mla_exact_split_min = s->opt_multi_mla_exact_split_min;
-    o.gqa_split_min = s->gqa_split_min; o.mla_split_min = s->mla_split_min;
-    o.extend_la_exact = s->opt_multi_extend_la_exact; o.la_exact_min = s->opt_multi_extend_la_exact_min;
+    o.opt = s->mopt; o.attn_fast = s->mopt.attn_fast || s->mopt.attn_fast_paged; o.gqa_split_min = s->gqa_split_min; o.mla_split_min = s->mla_split_min;
     o.max_seq = M.max_seq; o.fd_chunk = kr_fd_flash_chunk(M.max_seq); o.mla_chunk = kr_mla_flash_decode_chunk(M.max_seq);
     std::vector<KrMultiPlanLayer> pl_layers;
     for (const DLayer& L : s->layers) pl_layers.push_back(KrMultiPlanLayer{L.attn, L.nh, L.nkv, L.hd, L.klr, L.nv});      // ATTN_* are KR_MP_*

@@ -11,6 +11,7 @@
 
 #include "kr_lc_tiles.h"
 #include "kr_mf_tiles.h"
+#include "kr_multi_opts.h"
 #include "kr_pf_tiles.h"
 #include "kr_xm_tiles.h"
 
@@ -20,11 +21,10 @@ enum { KR_MP_OK = 0, KR_MP_GQA_CHUNKS = 1, KR_MP_MLA_CHUNKS = 2 };          // r
 #define KR_MP_MAX_CHUNKS 1024      // the merge kernels have one thread per chunk
 
 struct KrMultiPlanOpts {
+    KrMultiOpts opt;     // the store's options as they stand, in one assignment (kr_multi_opts.h); the rest is what the pass derives
     bool attn_fast;      // "multi_attn_fast" || "multi_attn_fast_paged"
-    bool mla_fast, extend_flash, extend_mla_flash, extend_la_chunk, extend_exact_mfma, extend_mla_exact_mfma, attn_exact_split, mla_exact_split;
-    int attn_exact_split_min, mla_exact_split_min, gqa_split_min, mla_split_min;
+    int gqa_split_min, mla_split_min;
     int max_seq, fd_chunk, mla_chunk;      // the slots' capacity; kr_fd_flash_chunk(max_seq) and kr_mla_flash_decode_chunk(max_seq): the rules stay beside their kernels
-    bool extend_la_exact; int la_exact_min;      // "multi_extend_la_exact" and its threshold "multi_extend_la_exact_min" (docs/design/36-multi-extend-la-exact.md)
 };
 struct KrMultiPlanLayer { int kind, nh, nkv, hd, klr, nv; };
 struct KrMultiPlanRows { int n, n_final, max_pos; bool verify; const int32_t* counts; const int32_t* positions; };      // counts / positions: host, may be null (a plain step)
@@ -96,13 +96,13 @@ inline int kr_multi_plan(const KrMultiPlanOpts& o, const KrMultiPlanLayer* layer
         }
     }
     // split-KV flash-decode of the unit rows over slots longer than the store's capacity rule ("multi_attn_fast" 16 / 23, "multi_mla_fast" 24)
-    const bool flash = o.attn_fast && has_gqa && o.max_seq > o.gqa_split_min, mla_flash = o.mla_fast && has_mla && o.max_seq > o.mla_split_min;
+    const bool flash = o.attn_fast && has_gqa && o.max_seq > o.gqa_split_min, mla_flash = o.opt.mla_fast && has_mla && o.max_seq > o.mla_split_min;
     // what the runs of >= 2 tokens take.  Flash run kernels (25, 27): the per-row kernels then see the unit rows only, which lie among the first n_final rows, so
     // their score rows and partials are sized by n_final rows at the unit rows' longest position.  Exact matrix-core passes (28, 29): the runs keep their score
-    // rows -- n rows at the pass's longest position.  Flash and matrix-core passes of one kind never meet (kr_xm_refuse, kr_mla_xm_refuse), nor do
-    // "multi_extend_flash" and an MLA layer (kr_exact_refuse)
-    if (any_run && has_gqa) p.gqa_runs = o.extend_flash ? KR_MP_RUNS_FLASH : o.extend_exact_mfma ? KR_MP_RUNS_XM : KR_MP_RUNS_ROWS;
-    if (any_run && has_mla) p.mla_runs = o.extend_mla_flash ? KR_MP_RUNS_FLASH : o.extend_mla_exact_mfma ? KR_MP_RUNS_XM : KR_MP_RUNS_ROWS;
+    // rows -- n rows at the pass's longest position.  Flash and matrix-core passes of one kind never meet, nor do "multi_extend_flash"
+    // and an MLA layer (the rule list of kr_option_rules, kr_decode_prefill.cpp)
+    if (any_run && has_gqa) p.gqa_runs = o.opt.extend_flash ? KR_MP_RUNS_FLASH : o.opt.extend_exact_mfma ? KR_MP_RUNS_XM : KR_MP_RUNS_ROWS;
+    if (any_run && has_mla) p.mla_runs = o.opt.extend_mla_flash ? KR_MP_RUNS_FLASH : o.opt.extend_mla_exact_mfma ? KR_MP_RUNS_XM : KR_MP_RUNS_ROWS;
     const bool pf = p.gqa_runs == KR_MP_RUNS_FLASH, mf = p.mla_runs == KR_MP_RUNS_FLASH, xm = p.gqa_runs == KR_MP_RUNS_XM, xl = p.mla_runs == KR_MP_RUNS_XM;
     p.attn_rows = p.mla_rows = r.n; p.attn_pos = p.mla_pos = r.max_pos;
     if (pf) { p.attn_rows = r.n_final; p.attn_pos = unit_pos; }
@@ -128,8 +128,8 @@ inline int kr_multi_plan(const KrMultiPlanOpts& o, const KrMultiPlanLayer* layer
     p.score_bytes = (size_t)p.attn_rows * nh_max * p.sc_ld * 4;
     p.n_logits = r.verify ? r.n : r.n_final;      // a verify pass: the lm_head over every token row
     // the exact per-slot attention as three launches (30, 31): a pass-level choice by the longest attention of the per-row kernels; -1: no unit row, nothing launched
-    p.xs_split = o.attn_exact_split && has_gqa && p.attn_pos + 1 >= o.attn_exact_split_min;
-    p.mla_xs_split = o.mla_exact_split && has_mla && p.mla_pos + 1 >= o.mla_exact_split_min;
+    p.xs_split = o.opt.attn_exact_split && has_gqa && p.attn_pos + 1 >= o.opt.attn_exact_split_min;
+    p.mla_xs_split = o.opt.mla_exact_split && has_mla && p.mla_pos + 1 >= o.opt.mla_exact_split_min;
     std::vector<int32_t> one;
     for (int l = 0; l < n_layers; l++) {
         const KrMultiPlanLayer& L = layers[l];
@@ -149,7 +149,7 @@ inline int kr_multi_plan(const KrMultiPlanOpts& o, const KrMultiPlanLayer* layer
         p.xm_inv_bytes = (sc_rows * 4 + 255) & ~(size_t)255; p.xm_tmax_bytes = sc_rows * (size_t)(p.sc_ld / 32) * 4;
     }
     // chunked delta rule (26): one table for every linear-attention layer -- the chunked runs, then their sub-chunks -- and one scratch, sized by the widest layer
-    if (o.extend_la_chunk && !r.verify && r.counts && nv_max) {
+    if (o.opt.extend_la_chunk && !r.verify && r.counts && nv_max) {
         std::vector<int32_t> lr, lt;
         const KrLcStats ls = kr_lc_build(r.n_final, r.counts, lr, lt);
         if (ls.n_runs) {
@@ -158,9 +158,9 @@ inline int kr_multi_plan(const KrMultiPlanOpts& o, const KrMultiPlanLayer* layer
         }
     }
     // exact staged linear attention (36): one set of tables for every linear-attention layer -- the staged runs, their conv tiles, their gated-norm tiles
-    if (o.extend_la_exact && !r.verify && r.counts && nv_max) {
+    if (o.opt.extend_la_exact && !r.verify && r.counts && nv_max) {
         std::vector<int32_t> xr, x16, x8;
-        const KrLxStats xs = kr_lx_build(r.n_final, r.counts, o.la_exact_min, xr, x16, x8);
+        const KrLxStats xs = kr_lx_build(r.n_final, r.counts, o.opt.extend_la_exact_min, xr, x16, x8);
         if (xs.n_runs) {
             p.lx_runs = kr_mp_append(p.tables, xr); p.lx_t16 = kr_mp_append(p.tables, x16); p.lx_t8 = kr_mp_append(p.tables, x8);
             p.lx_nruns = xs.n_runs; p.lx_short = xs.n_short;

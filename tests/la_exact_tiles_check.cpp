@@ -67,8 +67,8 @@ static KrMultiPlan plan_of(const std::vector<int32_t>& counts, bool on, int min,
     std::vector<int32_t> pos;
     for (int c : counts) { n += c; pos.push_back(10 + c - 1); }
     KrMultiPlanOpts o{};
-    o.extend_la_exact = on; o.la_exact_min = min; o.extend_la_chunk = la_chunk; o.max_seq = 2048; o.gqa_split_min = 1 << 20; o.mla_split_min = 1 << 20;
-    o.attn_exact_split_min = 512; o.mla_exact_split_min = 512; o.fd_chunk = 128; o.mla_chunk = 64;
+    o.opt.extend_la_exact = on; o.opt.extend_la_exact_min = min; o.opt.extend_la_chunk = la_chunk; o.max_seq = 2048; o.gqa_split_min = 1 << 20; o.mla_split_min = 1 << 20;
+    o.opt.attn_exact_split_min = 512; o.opt.mla_exact_split_min = 512; o.fd_chunk = 128; o.mla_chunk = 64;
     const KrMultiPlanLayer layers[3] = {{la_layers ? KR_MP_LA : KR_MP_OTHER, 0, 0, 0, 0, 4}, {KR_MP_GQA, 4, 2, 64, 0, 0}, {la_layers ? KR_MP_LA : KR_MP_OTHER, 0, 0, 0, 0, 8}};
     KrMultiPlan p;
     const KrMultiPlanRows rows{n, n_final, 10 + 1024, verify, with_counts ? counts.data() : nullptr, with_counts ? pos.data() : nullptr};

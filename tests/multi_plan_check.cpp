@@ -15,7 +15,7 @@ static const KrMultiPlanLayer GQA_8_2_64{KR_MP_GQA, 8, 2, 64, 0, 0}, MLA_16_512{
 
 static KrMultiPlanOpts opts(int max_seq, int fd_chunk, int mla_chunk) {
     KrMultiPlanOpts o{};
-    o.attn_exact_split_min = 512; o.mla_exact_split_min = 512; o.gqa_split_min = 1024; o.mla_split_min = 512;      // the defaults
+    o.opt.attn_exact_split_min = 512; o.opt.mla_exact_split_min = 512; o.gqa_split_min = 1024; o.mla_split_min = 512;      // the defaults
     o.max_seq = max_seq; o.fd_chunk = fd_chunk; o.mla_chunk = mla_chunk;
     return o;
 }
@@ -45,7 +45,7 @@ static bool no_run_option(const KrMultiPlan& p, const KrMultiPlanRows& r) {     
 static void case_a_f() {
     // case A: flash run kernels with unit rows
     KrMultiPlanOpts o = opts(2048, 128, 64);
-    o.attn_fast = true; o.extend_flash = true;
+    o.attn_fast = true; o.opt.extend_flash = true;
     Pass a; a.counts = {1, 3, 1}; a.positions = {700, 10, 5};
     const KrMultiPlanRows ra = a.rows();
     CHECK(ra.n == 5 && ra.n_final == 3 && ra.max_pos == 700);
@@ -56,15 +56,15 @@ static void case_a_f() {
     std::puts("case A ok");
     // case B: no unit row
     Pass b; b.counts = {2, 3}; b.positions = {0, 10};
-    o.attn_exact_split = true;
+    o.opt.attn_exact_split = true;
     for (int mn : {1, 2, 512}) {
-        o.attn_exact_split_min = mn;
+        o.opt.attn_exact_split_min = mn;
         p = plan(o, {GQA_8_2_64}, b.rows());
         CHECK(p.n_unit == 0 && p.attn_pos == -1 && p.attn_rows == 2 && !p.row_attn && p.fd_chunks == 0 && p.fd_o_bytes == 0 && p.fd_ml_bytes == 0 && !p.need_scores && !p.xs_split);
     }
     std::puts("case B ok");
     // case F: a verify pass takes no run option -- first A ...
-    o.attn_exact_split = false; a.verify = true;
+    o.opt.attn_exact_split = false; a.verify = true;
     const KrMultiPlanRows rf = a.rows();
     p = plan(o, {GQA_8_2_64}, rf);
     CHECK(no_run_option(p, rf) && p.n_logits == 5 && p.fd_chunks == 6 && p.fd_o_bytes == (size_t)5 * 6 * 512 * 4);
@@ -73,7 +73,7 @@ static void case_a_f() {
 static void case_c_d() {
     // case C: a mixed store keeps the score rows
     KrMultiPlanOpts o = opts(256, 128, 64);
-    o.extend_mla_flash = true;
+    o.opt.extend_mla_flash = true;
     Pass c; c.counts = {1, 4}; c.positions = {40, 100};
     const KrMultiPlanRows r = c.rows();
     CHECK(r.n == 5 && r.max_pos == 103);
@@ -92,7 +92,7 @@ static void case_c_d() {
 static void case_e_f() {
     // case E: matrix-core passes under flash
     KrMultiPlanOpts o = opts(2048, 128, 64);
-    o.attn_fast = true; o.extend_exact_mfma = true;
+    o.attn_fast = true; o.opt.extend_exact_mfma = true;
     Pass e; e.counts = {1, 3}; e.positions = {700, 10};
     const KrMultiPlanRows r = e.rows();
     KrMultiPlan p = plan(o, {GQA_8_2_64}, r);
@@ -108,10 +108,10 @@ static void case_e_f() {
     CHECK(no_run_option(p, rf) && p.n_logits == 4 && !p.need_scores && p.sc_ld == 704);      // under flash no per-row kernel reads score rows; 701 rounds to 704 at 32 too
     // ... and the MLA run options and the chunked delta rule likewise
     KrMultiPlanOpts om = opts(2048, 128, 64);
-    om.extend_mla_exact_mfma = true;
+    om.opt.extend_mla_exact_mfma = true;
     p = plan(om, {MLA_16_512}, rf);
     CHECK(no_run_option(p, rf) && p.need_scores && p.sc_ld == 704 && p.n_logits == 4);
-    om.extend_mla_exact_mfma = false; om.extend_mla_flash = true; om.extend_la_chunk = true;
+    om.opt.extend_mla_exact_mfma = false; om.opt.extend_mla_flash = true; om.opt.extend_la_chunk = true;
     Pass lc; lc.counts = {70, 1}; lc.positions = {0, 9}; lc.verify = true;
     const KrMultiPlanRows rl = lc.rows();
     p = plan(om, {LA_NV16, MLA_16_512}, rl);      // (a store the refusals do not allow; the plan's rule holds whatever the store)
@@ -125,7 +125,7 @@ static void case_e_f() {
 static void case_g_h() {
     // case G: a plain step gives no counts
     KrMultiPlanOpts o = opts(2048, 128, 64);
-    o.attn_fast = true; o.extend_flash = true; o.extend_la_chunk = true;
+    o.attn_fast = true; o.opt.extend_flash = true; o.opt.extend_la_chunk = true;
     KrMultiPlanRows r{3, 3, 700, false, nullptr, nullptr};
     KrMultiPlan p = plan(o, {LA_NV16, GQA_8_2_64}, r);
     CHECK(no_run_option(p, r) && p.n_unit == 3 && p.n_logits == 3 && p.fd_chunks == 6);
@@ -136,13 +136,13 @@ static void case_g_h() {
     std::puts("case G ok");
     // case H: the split thresholds
     o = opts(2048, 128, 64);
-    o.attn_exact_split = true; o.mla_exact_split = true;
+    o.opt.attn_exact_split = true; o.opt.mla_exact_split = true;
     r = KrMultiPlanRows{1, 1, 510, false, nullptr, nullptr};
     CHECK(!plan(o, {GQA_8_2_64}, r).xs_split && !plan(o, {MLA_16_512}, r).mla_xs_split);
     r.max_pos = 511;
     CHECK(plan(o, {GQA_8_2_64}, r).xs_split && plan(o, {MLA_16_512}, r).mla_xs_split);
     CHECK(!plan(o, {GQA_8_2_64}, r).mla_xs_split && !plan(o, {MLA_16_512}, r).xs_split);      // no layer of the kind: off
-    o.extend_mla_flash = true; o.mla_exact_split_min = 1;
+    o.opt.extend_mla_flash = true; o.opt.mla_exact_split_min = 1;
     Pass b; b.counts = {2}; b.positions = {600};
     p = plan(o, {MLA_16_512}, b.rows());
     CHECK(p.mla_pos == -1 && !p.mla_xs_split && !p.mla_row_attn);      // no unit row: nothing launched, nothing split
@@ -159,7 +159,7 @@ static void case_i() {
     KrMultiPlanRows under = r; under.max_pos = 262143;
     CHECK(plan(o, {GQA_8_2_64}, under).fd_chunks == 1024);
     o = opts(20000, 128, 128);
-    o.mla_fast = true;
+    o.opt.mla_fast = true;
     const KrMultiPlanRows rm{1, 1, 131072, false, nullptr, nullptr};
     p = plan(o, {MLA_16_512}, rm, KR_MP_MLA_CHUNKS);
     CHECK(p.mla_pos == 131072 && p.mla_chunks == 1025 && p.mla_chunk == 128);
@@ -172,7 +172,7 @@ static void case_i() {
 static void case_j() {
     // case J: a width two options ask for is built once
     KrMultiPlanOpts o = opts(256, 128, 64);
-    o.extend_exact_mfma = true; o.extend_mla_exact_mfma = true;
+    o.opt.extend_exact_mfma = true; o.opt.extend_mla_exact_mfma = true;
     Pass j; j.counts = {3, 1}; j.positions = {10, 20};
     const KrMultiPlanLayer mla4{KR_MP_MLA, 4, 0, 0, 512, 0};      // G = 4, as GQA(8, 2, 64)
     KrMultiPlan p = plan(o, {GQA_8_2_64, mla4}, j.rows());
@@ -201,12 +201,12 @@ static void case_k() {
         for (int k = 0; has_mla && k < 1 + rnd(2); k++) layers.push_back(KrMultiPlanLayer{KR_MP_MLA, gs[rnd(6)], 0, 0, rnd(2) ? 512 : 256, 0});
         if (has_la && rnd(2)) layers.push_back(KrMultiPlanLayer{KR_MP_OTHER, 0, 0, 0, 0, 0});
         KrMultiPlanOpts o = opts(64 << rnd(8), 128, 64);
-        o.attn_fast = !has_mla && rnd(2); o.mla_fast = has_mla && rnd(2);
-        o.extend_flash = has_gqa && !has_mla && rnd(2); o.extend_exact_mfma = has_gqa && !o.extend_flash && rnd(2);
-        o.extend_mla_flash = has_mla && rnd(2); o.extend_mla_exact_mfma = has_mla && !o.extend_mla_flash && rnd(2);
-        o.extend_la_chunk = has_la && rnd(2);
-        o.attn_exact_split = has_gqa && rnd(2); o.mla_exact_split = has_mla && rnd(2);
-        o.attn_exact_split_min = 1 + rnd(600); o.mla_exact_split_min = 1 + rnd(600);
+        o.attn_fast = !has_mla && rnd(2); o.opt.mla_fast = has_mla && rnd(2);
+        o.opt.extend_flash = has_gqa && !has_mla && rnd(2); o.opt.extend_exact_mfma = has_gqa && !o.opt.extend_flash && rnd(2);
+        o.opt.extend_mla_flash = has_mla && rnd(2); o.opt.extend_mla_exact_mfma = has_mla && !o.opt.extend_mla_flash && rnd(2);
+        o.opt.extend_la_chunk = has_la && rnd(2);
+        o.opt.attn_exact_split = has_gqa && rnd(2); o.opt.mla_exact_split = has_mla && rnd(2);
+        o.opt.attn_exact_split_min = 1 + rnd(600); o.opt.mla_exact_split_min = 1 + rnd(600);
         Pass ps; ps.verify = rnd(8) == 0;
         int T = 0;
         for (int i = 0, nf = 1 + rnd(16); i < nf; i++) {

@@ -25,9 +25,10 @@ def _lib():
 
 
 def test_the_options_are_known_everywhere():
+    from tests.util import option_field
     dec = _src("kr_decode.cpp")
     for o in (OPT, MIN):
-        assert '!strcmp(name, "%s")' % o in dec and "opt_%s" % o in _src("kr_decode_internal.h")
+        assert '!strcmp(name, "%s")' % o in dec and option_field(o) == o[len("multi_"):]
     assert "if (value < 1) return kr_fail(KR_ERR_VALUE" in dec[dec.index('"%s"))' % MIN):][:300]
     from krasis_amd.decode_store import CpuDecodeStore
     assert OPT in CpuDecodeStore.set_option.__doc__ and MIN in CpuDecodeStore.set_option.__doc__
@@ -40,17 +41,22 @@ def test_the_options_are_known_everywhere():
 
 
 def test_the_refusal_stands_behind_its_siblings():
-    multi = _src("kr_decode_multi.cpp")
-    body = multi[multi.index("int multi_refuse(kr_decode_store* s) {"):]
-    body = body[:body.index("\n}\n")]
-    assert body.index("kr_exact_refuse(s, true)") < body.index("kr_xm_refuse(s)") < body.index("kr_mla_xm_refuse(s)") < body.index("kr_xs_refuse(s)")
+    from tests.util import FLAGS, recorded_refusal, rule_place_seen, rule_row
     pre = _src("kr_decode_prefill.cpp")
-    mine = pre[pre.index("int kr_xs_refuse(kr_decode_store* s) {"):]
-    mine = mine[:mine.index("\n}\n")]
-    assert "KR_ERR_STATE" in mine and "covers GQA layers only: this store has none" in mine and "graph_ok" not in mine
-    assert "|| paged_refused(s)) return KR_OK;" in mine
+    row = rule_row(OPT)      # "has none" and nothing else: no rival, no MLA step, no geometry rule, nothing to prepare; stands back
+    assert row == '{"multi_attn_exact_split", &KrMultiOpts::attn_exact_split, ATTN_GQA, true, nullptr, nullptr, nullptr, 0, false, "", nullptr, nullptr, nullptr},'
+    walk = pre[pre.index("int kr_option_rules("):]
+    assert "graph_ok" not in walk[:walk.index("\n}\n")]
+    assert pre.count("bool paged_refused(") == 1 and pre.count("for (const KrOptRule& r : kr_opt_rules)") == 1 and "(r.stand_back && back)) continue;" in pre      # one predicate, one walker: stands back where the entry point's paged refusal applies
+    body = _src("kr_decode_multi.cpp")
+    body = body[body.index("int multi_refuse("):body.index("int need_slots(")]
+    assert body.index("kr_spec_pending_fail(s)") < body.index("kr_exact_refuse(s, true)") < body.index("return kr_option_rules(s, false);")
+    assert FLAGS.index("multi_extend_exact_mfma") < FLAGS.index("multi_extend_mla_exact_mfma") < FLAGS.index(OPT)      # behind its siblings, as the recorded pairs show
+    assert rule_place_seen(OPT) >= 8
+    assert recorded_refusal("mla/flat", OPT) == 'RuntimeError: the "multi_attn_exact_split" option covers GQA layers only: this store has none (set the option to 0)'
+    assert recorded_refusal("gqa/flat", OPT) == "ok" and recorded_refusal("hybrid/paged", OPT) == "ok" and recorded_refusal("gqa-3-per-kv/flat", OPT) == "ok"
     # the pass-level choice, by the longest attention of the per-row kernels: the plan's (docs/design/32-multi-pass-plan.md)
-    assert "o.attn_exact_split_min = s->opt_multi_attn_exact_split_min;" in pre and "p.attn_pos + 1 >= o.attn_exact_split_min" in _src("kr_multi_plan.h")
+    assert "o.opt = s->mopt;" in pre and "p.attn_pos + 1 >= o.opt.attn_exact_split_min" in _src("kr_multi_plan.h")
     assert case_passed("H") and case_passed("B") and "m.xs_split = pl.xs_split;" in pre
 
 

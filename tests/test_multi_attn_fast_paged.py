@@ -50,14 +50,21 @@ def test_launcher_dispatches_and_prepares_the_paged_instantiations():
 
 def test_the_option_is_known_everywhere():
     assert '!strcmp(name, "%s")' % OPT in _src("kr_decode.cpp")
-    assert "opt_%s" % OPT in _src("kr_decode_internal.h")
+    from tests.util import option_field, recorded_refusal
+    assert option_field(OPT) == "attn_fast_paged" and option_field("multi_attn_fast") == "attn_fast"
     pre = _src("kr_decode_prefill.cpp")
-    assert "o.attn_fast = s->opt_multi_attn_fast || s->opt_multi_attn_fast_paged;" in pre      # either option: one flag of the plan (docs/design/32-multi-pass-plan.md)
+    assert "o.attn_fast = s->mopt.attn_fast || s->mopt.attn_fast_paged;" in pre      # either option: one flag of the plan (docs/design/32-multi-pass-plan.md)
     assert "o.attn_fast && has_gqa && o.max_seq > o.gqa_split_min" in _src("kr_multi_plan.h") and case_passed("A") and case_passed("I")
-    assert "slots && (s->opt_multi_attn_fast || s->opt_multi_attn_fast_paged)" in pre      # the MLA refusal covers either option
+    assert "slots && (s->mopt.attn_fast || s->mopt.attn_fast_paged)" in pre      # the MLA refusal covers either option
     refuse = re.search(r"int paged_refuse\(kr_decode_store\* s\) \{(.*?)\n\}", _src("kr_decode_multi.cpp"), re.S).group(1)
     assert "if (paged_refused(s))" in refuse and "paged slots" in refuse
-    assert "bool paged_refused(const kr_decode_store* s) { return s->multi && s->multi->pg.paged() && s->opt_multi_attn_fast && !s->opt_multi_attn_fast_paged; }" in pre
+    assert pre.count("bool paged_refused(") == 1 and pre.count("for (const KrOptRule& r : kr_opt_rules)") == 1      # one predicate, one walker of the rule list
+    assert "bool paged_refused(const kr_decode_store* s) { return s->multi && s->multi->pg.paged() && s->mopt.attn_fast && !s->mopt.attn_fast_paged; }" in pre
+    # as a caller sees it: either option names itself on an MLA store, the paged one governs when both are set; paged slots refuse "multi_attn_fast" alone
+    assert 'the "multi_attn_fast_paged" option covers GQA layers only: layer 0 is MLA' in recorded_refusal("mla/paged", OPT)
+    assert 'the "multi_attn_fast_paged" option covers GQA layers only: layer 0 is MLA' in recorded_refusal("mla/flat", "multi_attn_fast", OPT)
+    assert recorded_refusal("gqa/paged", "multi_attn_fast").startswith('RuntimeError: "multi_attn_fast" does not read paged slots')
+    assert recorded_refusal("gqa/paged", OPT) == "ok" and recorded_refusal("gqa/paged", "multi_attn_fast", OPT) == "ok" and recorded_refusal("gqa/flat", "multi_attn_fast") == "ok"
     header = open(os.path.join(ROOT, "include", "krasis_hip.h")).read()
     assert header.count('"%s"' % OPT) >= 3
     from krasis_amd.decode_store import CpuDecodeStore

@@ -27,7 +27,8 @@ def _lib():
 
 def test_the_option_is_known_everywhere():
     assert '!strcmp(name, "%s")' % OPT in _src("kr_decode.cpp")
-    assert "opt_%s" % OPT in _src("kr_decode_internal.h")
+    from tests.util import option_field
+    assert option_field(OPT) == "extend_exact_mfma"
     header = open(os.path.join(ROOT, "include", "krasis_hip.h")).read()
     assert '"%s"' % OPT in header and DOC in header
     from krasis_amd.decode_store import CpuDecodeStore
@@ -43,19 +44,24 @@ def test_the_option_is_known_everywhere():
 
 
 def test_the_refusal_is_a_function_of_its_own_behind_every_earlier_clause():
+    from tests.util import recorded_refusal, rule_place_seen, rule_row
     pre = _src("kr_decode_prefill.cpp")
     span = pre[pre.index("int kr_exact_refuse("):pre.index("int kr_spec_refuse(")]
-    assert OPT not in span                                                    # kr_exact_refuse is as it was
-    mine = pre[pre.index("int kr_xm_refuse("):]
-    mine = mine[:mine.index("\n}\n")]
-    assert re.search(r'KR_ERR_STATE[^;]*multi_extend_exact_mfma[^;]*multi_extend_flash', mine)      # both run options: the message names both
-    assert re.search(r"KR_ERR_STATE[^;]*has none", mine) and re.search(r"KR_ERR_VALUE[^;]*not covered", mine)
-    assert mine.count(OPT) >= 4 and "kr_pfm_gqa_exact_mfma_ok(g)" in mine     # every message names the option; the prompt pass's own geometry rule
-    assert "|| paged_refused(s)) return KR_OK;" in mine and _src("kr_decode_prefill.cpp").count("pg.paged() && s->opt_multi_attn_fast && !s->opt_multi_attn_fast_paged") == 1      # stands back where the entry point's paged refusal applies
-    multi = _src("kr_decode_multi.cpp")
-    body = multi[multi.index("int multi_refuse("):]
-    body = body[:body.index("\n}\n")]
-    assert body.index("kr_spec_pending_fail(s)") < body.index("kr_exact_refuse(s, true)") < body.index("kr_xm_refuse(s)")
+    assert OPT not in span and "multi_extend" not in span                     # kr_exact_refuse holds the base clauses only
+    row = rule_row(OPT)
+    assert row.startswith('{"multi_extend_exact_mfma", &KrMultiOpts::extend_exact_mfma, ATTN_GQA, true, "multi_extend_flash", &KrMultiOpts::extend_flash, "the runs of >= 2 tokens of the GQA layers", 0, false, "",')
+    assert re.search(r"KR_ERR_VALUE[^;]*not covered", row) and "kr_pfm_gqa_exact_mfma_ok(g)" in row and row.rstrip().endswith("nullptr, nullptr},")      # the prompt pass's own geometry rule; nothing to prepare
+    assert pre.count("bool paged_refused(") == 1 and pre.count("for (const KrOptRule& r : kr_opt_rules)") == 1 and "(r.stand_back && back)) continue;" in pre      # one predicate, one walker: stands back where the entry point's paged refusal applies
+    body = _src("kr_decode_multi.cpp")
+    body = body[body.index("int multi_refuse("):body.index("int need_slots(")]
+    assert body.index("kr_spec_pending_fail(s)") < body.index("kr_exact_refuse(s, true)") < body.index("return kr_option_rules(s, false);")
+    # as a caller sees it: both run options -- the message names both, ahead of "has none" and only once the rival's own rule has passed; every message names the option
+    assert rule_place_seen(OPT) >= 8
+    assert recorded_refusal("gqa/flat", OPT, "multi_extend_flash") == 'RuntimeError: the "multi_extend_exact_mfma" and "multi_extend_flash" options both claim the runs of >= 2 tokens of the GQA layers: set one of them to 0'
+    assert recorded_refusal("la/flat", OPT, "multi_extend_flash") == recorded_refusal("la/flat", "multi_extend_flash")
+    assert recorded_refusal("la/flat", OPT) == 'RuntimeError: the "multi_extend_exact_mfma" option covers GQA layers only: this store has none (set the option to 0)'
+    assert recorded_refusal("gqa-3-per-kv/flat", OPT).startswith("ValueError: multi_extend_exact_mfma: GQA geometry nh 6 nkv 2 head_dim 64 not covered (heads per KV head must divide 32")
+    assert recorded_refusal("gqa/flat", OPT) == "ok" and recorded_refusal("hybrid/paged", OPT) == "ok"
 
 
 def test_one_body_two_callers():
@@ -97,7 +103,7 @@ def test_the_launcher_and_the_pass():
     assert mine.rstrip().endswith("return kr_launch_multi_xm(a, x, B, st);")
     pre = _src("kr_decode_prefill.cpp")
     plan = _src("kr_multi_plan.h")      # the pass's decisions are the plan's (docs/design/32-multi-pass-plan.md): its check program's cases stand for the lines once pinned here
-    assert "o.extend_exact_mfma = s->opt_multi_extend_exact_mfma;" in pre and case_passed("F")      # never in a verify pass
+    assert "o.opt = s->mopt;" in pre and "o.opt.extend_exact_mfma ? KR_MP_RUNS_XM" in _src("kr_multi_plan.h") and case_passed("F")      # never in a verify pass
     assert "plan.need_scores && M.scores.ensure(plan.score_bytes)" in pre and case_passed("A") and "(has_mla && !mla_flash && p.mla_row_attn)" in plan and case_passed("D")
     assert case_passed("E") and case_passed("K")                              # the row stride: a multiple of 64 under the option, of 32 otherwise
     tiles = re.sub(r"//.*", "", _src("kr_xm_tiles.h"))

@@ -19,7 +19,8 @@ def _src(name):
 
 def test_the_option_is_known_everywhere():
     assert '!strcmp(name, "%s")' % OPT in _src("kr_decode.cpp")
-    assert "opt_%s" % OPT in _src("kr_decode_internal.h")
+    from tests.util import option_field
+    assert option_field(OPT) == "extend_flash"
     header = open(os.path.join(ROOT, "include", "krasis_hip.h")).read()
     assert '"%s"' % OPT in header and "25-multi-extend-flash.md" in header
     from krasis_amd.decode_store import CpuDecodeStore
@@ -33,20 +34,30 @@ def test_the_option_is_known_everywhere():
 
 
 def test_refusals_sit_behind_every_earlier_clause_and_name_the_option():
+    from tests.util import recorded_refusal, rule_row
     pre = _src("kr_decode_prefill.cpp")
-    refuse = pre[pre.index("int kr_exact_refuse("):pre.index("int kr_spec_refuse(")]
-    mine = refuse.index("slots && s->opt_%s && !paged_refused" % OPT)        # stands back where the entry point's paged refusal applies
-    for earlier in ("is exact-mode only: the attention mode has tolerance bits set", "slots && (s->opt_multi_attn_fast || s->opt_multi_attn_fast_paged)",
-                    "does not run under expert parallelism", "slots && s->opt_multi_mla_fast"):
-        assert refuse.index(earlier) < mine, earlier
-    tail = refuse[mine:]
-    assert tail.count('\\"%s\\"' % OPT) == 2 and tail.count(OPT + ":") == 2      # MLA layer, no GQA layer | geometry, LDS window
-    assert re.search(r"KR_ERR_STATE[^;]*is MLA", tail) and re.search(r"KR_ERR_STATE[^;]*has none", tail)
-    assert re.search(r"KR_ERR_VALUE[^;]*not covered", tail) and re.search(r"KR_ERR_HIP[^;]*LDS window", tail)
-    assert "kr_pfm_gqa_flash_ok(L.nh, L.nkv, L.hd)" in tail                   # the prompt pass's own geometry rule
-    assert "kr_multi_pf_prepare(L.hd, s->multi->kv_fp8, s->multi->pg.paged())" in tail and "pf_ready" in tail      # windows once per slot set, outside the pass
+    row = rule_row(OPT)
+    # stands back where the entry point's paged refusal applies; no rival; an MLA layer is refused ahead of "has none"; geometry last
+    assert row.startswith('{"multi_extend_flash", &KrMultiOpts::extend_flash, ATTN_GQA, true, nullptr, nullptr, nullptr, 1, false, " for the exact pass",')
+    assert row.count(OPT + ":") == 2                                           # geometry, LDS window; the two KR_ERR_STATE refusals take the row's name
+    assert re.search(r"KR_ERR_VALUE[^;]*not covered", row) and re.search(r"KR_ERR_HIP[^;]*LDS window", row)
+    assert "kr_pfm_gqa_flash_ok(L.nh, L.nkv, L.hd)" in row                    # the prompt pass's own geometry rule
+    assert "kr_multi_pf_prepare(L.hd, s->multi->kv_fp8, s->multi->pg.paged())" in row and row.rstrip().endswith("&kr_multi_state::pf_ready},")      # windows once per slot set, outside the pass
+    walk = pre[pre.index("int kr_option_rules("):]
+    assert re.search(r"KR_ERR_STATE[^;]*layer %zu is MLA", walk) and re.search(r"KR_ERR_STATE[^;]*this store has none", walk)
+    # behind every earlier clause, as a caller sees it: the attention-mode bit, the GQA flash-decode options' MLA clause and "multi_mla_fast" speak first
+    assert "the attention mode has tolerance bits set" in recorded_refusal("mla/flat", OPT, mode=True)
+    assert 'the "multi_attn_fast" option covers GQA layers only' in recorded_refusal("mla/flat", "multi_attn_fast", OPT)
+    assert 'the "multi_mla_fast" option covers MLA layers only: this store has none' in recorded_refusal("la/flat", "multi_mla_fast", OPT)
+    assert 'the "multi_extend_mla_flash" option covers MLA layers only: this store has none' in recorded_refusal("la/flat", "multi_extend_mla_flash", OPT)
+    # its own steps: on an MLA-only store "layer 0 is MLA" comes before "has none"; the geometry rule behind both
+    assert recorded_refusal("mla/flat", OPT) == 'RuntimeError: the "multi_extend_flash" option covers GQA layers only: layer 0 is MLA (set the option to 0 for the exact pass)'
+    assert recorded_refusal("la/flat", OPT) == 'RuntimeError: the "multi_extend_flash" option covers GQA layers only: this store has none (set the option to 0 for the exact pass)'
+    assert recorded_refusal("gqa-3-per-kv/flat", OPT).startswith("ValueError: multi_extend_flash: GQA geometry nh 6 nkv 2 head_dim 64 not covered")
+    assert recorded_refusal("la/flat", OPT, "multi_extend_la_chunk") == recorded_refusal("la/flat", OPT)      # ahead of the next rule
     # paged slots under "multi_attn_fast" alone are still refused by the entry points
-    assert "if (paged_refused(s))" in _src("kr_decode_multi.cpp") and _src("kr_decode_prefill.cpp").count("pg.paged() && s->opt_multi_attn_fast && !s->opt_multi_attn_fast_paged") == 1      # the entry points' refusal and its siblings' standing back: one predicate
+    assert "if (paged_refused(s))" in _src("kr_decode_multi.cpp") and pre.count("bool paged_refused(") == 1 and pre.count("for (const KrOptRule& r : kr_opt_rules)") == 1      # one predicate, one walker
+    assert recorded_refusal("la/paged", "multi_attn_fast", OPT).startswith('RuntimeError: "multi_attn_fast" does not read paged slots')
 
 
 def test_one_body_two_callers():
@@ -113,8 +124,8 @@ def test_the_batched_launcher_keeps_its_lines_and_gains_the_run_path():
     assert "return a.pf_runs && a.pf_runs[3 * b + 2] >= 2;" in hdr          # null pointer: no row is skipped
     pre = _src("kr_decode_prefill.cpp")
     plan = _src("kr_multi_plan.h")      # the pass's decisions are the plan's (docs/design/32-multi-pass-plan.md): its check program's cases stand for the lines once pinned here
-    assert "o.attn_fast = s->opt_multi_attn_fast || s->opt_multi_attn_fast_paged;" in pre and "o.attn_fast && has_gqa && o.max_seq > o.gqa_split_min" in plan
-    assert "o.extend_flash = s->opt_multi_extend_flash;" in pre and case_passed("F")      # never in a verify pass
+    assert "o.attn_fast = s->mopt.attn_fast || s->mopt.attn_fast_paged;" in pre and "o.attn_fast && has_gqa && o.max_seq > o.gqa_split_min" in plan
+    assert "o.opt = s->mopt;" in pre and "o.opt.extend_flash ? KR_MP_RUNS_FLASH" in plan and case_passed("F")      # never in a verify pass
     assert case_passed("A") and case_passed("B")                             # scratch of the per-row kernels sized by the unit rows
     assert "plan.need_scores && M.scores.ensure(plan.score_bytes)" in pre and "p.score_bytes = (size_t)p.attn_rows * nh_max * p.sc_ld * 4;" in plan and case_passed("K")
 

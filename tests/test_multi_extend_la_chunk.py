@@ -25,7 +25,8 @@ def _code(text):
 
 def test_the_option_is_known_everywhere():
     assert '!strcmp(name, "%s")' % OPT in _src("kr_decode.cpp")
-    assert "opt_%s" % OPT in _src("kr_decode_internal.h")
+    from tests.util import option_field
+    assert option_field(OPT) == "extend_la_chunk"
     header = open(os.path.join(ROOT, "include", "krasis_hip.h")).read()
     assert '"%s"' % OPT in header and DOC in header
     from krasis_amd.decode_store import CpuDecodeStore
@@ -78,23 +79,34 @@ def test_one_body_two_callers():
 
 
 def test_refusal_clause_is_last_and_names_the_option():
+    from tests.util import FLAGS, recorded_refusal, rule_row
     pre = _src("kr_decode_prefill.cpp")
-    refuse = pre[pre.index("int kr_exact_refuse("):pre.index("int kr_spec_refuse(")]
-    mine = refuse.index("slots && s->opt_%s && !paged_refused" % OPT)        # stands back where the entry point's paged refusal applies
-    for earlier in ("is exact-mode only: the attention mode has tolerance bits set", "does not run under expert parallelism", "slots && s->opt_multi_mla_fast",
-                    "slots && s->opt_multi_extend_flash && !paged_refused", "s->multi->pf_ready = true;"):
-        assert refuse.index(earlier) < mine, earlier
-    tail = refuse[mine:]
-    assert "s->opt_" not in tail[10:].replace("s->opt_%s" % OPT, "")          # no clause of another option behind it
-    assert tail.count('\\"%s\\"' % OPT) == 2 and tail.count(OPT + ":") == 2   # no such layer, MLA layer | geometry, LDS window
-    assert '\\"multi_extend_flash\\"' not in tail and "multi_extend_flash:" not in tail
-    assert re.search(r"KR_ERR_STATE[^;]*has none", tail) and re.search(r"KR_ERR_STATE[^;]*is MLA", tail)
-    assert re.search(r"KR_ERR_VALUE[^;]*not covered", tail) and re.search(r"KR_ERR_HIP[^;]*LDS window", tail)
-    assert "kr_multi_lc_prepare()" in tail and "lc_ready" in tail            # windows once per slot set, outside the pass
-    assert "kr_multi_lc_ok(L.dk, L.dv, L.nk, L.nv," in tail
+    row = rule_row(OPT)
+    # stands back where the entry point's paged refusal applies; no rival; "has none" ahead of the MLA step; geometry last
+    assert row.startswith('{"multi_extend_la_chunk", &KrMultiOpts::extend_la_chunk, ATTN_LA, true, nullptr, nullptr, nullptr, 2, false, " for the exact pass",')
+    assert FLAGS.index(OPT) == 5 and FLAGS[:5] == ("multi_attn_fast", "multi_attn_fast_paged", "multi_mla_fast", "multi_extend_mla_flash", "multi_extend_flash")      # the last of the tolerance forms; the exact forms stand behind it
+    assert row.count(OPT + ":") == 2                                          # geometry, LDS window; "has none" and "is MLA" take the row's name
+    assert '"multi_extend_flash"' not in row and "multi_extend_flash:" not in row
+    walk = pre[pre.index("int kr_option_rules("):]
+    assert re.search(r"KR_ERR_STATE[^;]*this store has none", walk) and re.search(r"KR_ERR_STATE[^;]*layer %zu is MLA", walk)
+    assert walk.index("if (r.mla_at == 1)") < walk.index("if (!has_attn(s, r.kind))") < walk.index("if (r.mla_at == 2)")
+    assert re.search(r"KR_ERR_VALUE[^;]*not covered", row) and re.search(r"KR_ERR_HIP[^;]*LDS window", row)
+    assert "kr_multi_lc_prepare()" in row and row.rstrip().endswith("&kr_multi_state::lc_ready},")      # windows once per slot set, outside the pass
+    assert "kr_multi_lc_ok(L.dk, L.dv, L.nk, L.nv," in row
+    # as a caller sees it: behind the attention-mode bit, "multi_mla_fast" and "multi_extend_flash"; "has none" on an MLA-only store (not "is MLA"); ahead of
+    # every exact form
+    none = 'RuntimeError: the "multi_extend_la_chunk" option covers linear-attention layers only: this store has none (set the option to 0 for the exact pass)'
+    assert recorded_refusal("mla/flat", OPT) == none and recorded_refusal("gqa/flat", OPT) == none and recorded_refusal("la/flat", OPT) == "ok"
+    assert "the attention mode has tolerance bits set" in recorded_refusal("gqa/flat", OPT, mode=True)
+    assert 'the "multi_mla_fast" option' in recorded_refusal("gqa/flat", "multi_mla_fast", OPT)
+    assert 'the "multi_extend_flash" option covers GQA layers only: layer 0 is MLA' in recorded_refusal("mla/flat", "multi_extend_flash", OPT)
+    for later in FLAGS[6:]:
+        assert recorded_refusal("gqa/flat" if "mla" in later or "la_exact" in later else "mla/flat", OPT, later) == none, later
+    assert recorded_refusal("hybrid-dk64/flat", OPT).startswith("ValueError: multi_extend_la_chunk: linear-attention geometry nk 2 nv 4 dk 64 dv 64 not covered")
+    assert recorded_refusal("gqa/paged", "multi_attn_fast", OPT).startswith('RuntimeError: "multi_attn_fast" does not read paged slots')
     assert "return dk == LC_D && dv == LC_D" in _src("kr_multi_la_chunk.hip")
     # the pass: never in a verify pass, the table with the other tables of the pass, the scratch ahead of the layer loop
-    assert "o.extend_la_chunk = s->opt_%s;" % OPT in pre and "o.extend_la_chunk && !r.verify && r.counts" in _src("kr_multi_plan.h")
+    assert "o.opt = s->mopt;" in pre and "o.opt.extend_la_chunk && !r.verify && r.counts" in _src("kr_multi_plan.h")
     assert case_passed("F") and case_passed("G") and case_passed("K")      # a plain step and a verify pass have no table (docs/design/32-multi-pass-plan.md)
     p = pre[pre.index("int kr_multi_pass("):]
     assert p.index("kr_multi_plan(o, ") < p.index("M.lc_scratch.ensure(") < p.index("run_layer(s, cx, l)")

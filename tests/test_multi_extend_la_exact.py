@@ -1,5 +1,5 @@
 """The "multi_extend_la_exact" option (docs/design/36-multi-extend-la-exact.md) without a GPU: both options are parsed and documented in every layer, the refusal
-is a function of its own asked behind kr_mla_xs_refuse, the four kernels are one text in the device header with two callers, the run kernels leave a staged run
+is the last rule of the ordered rule list, asked behind the "multi_mla_exact_split" rule, the four kernels are one text in the device header with two callers, the run kernels leave a staged run
 ahead of their first barrier, the new field of KrMultiLaArgs stands ahead of the chunked rule's, no C-ABI symbol was added, and the table builder and the plan
 pass their stand-alone check under AddressSanitizer and UBSan in a child process."""
 import os
@@ -35,12 +35,13 @@ def _lib():
 
 
 def test_the_options_are_parsed_and_documented():
+    from tests.util import option_field
     dec = _src("kr_decode.cpp")
     for o in (OPT, MIN):
-        assert '!strcmp(name, "%s")' % o in dec and "opt_%s" % o in _src("kr_decode_internal.h")
+        assert '!strcmp(name, "%s")' % o in dec and option_field(o) == o[len("multi_"):]
     parse = dec[dec.index('"%s"))' % MIN):][:400]
     assert "if (value < 2 || value > 1024) return kr_fail(KR_ERR_VALUE" in parse and MIN in parse[20:]      # 2 .. 1024, the message names the option
-    assert re.search(r"int opt_%s = 0;" % OPT, _src("kr_decode_internal.h"))                                 # off by default
+    assert re.search(r"int extend_la_exact = 0;", _src("kr_multi_opts.h")) and re.search(r"int extend_la_exact_min = 8;", _src("kr_multi_opts.h"))                                 # off by default
     header = open(os.path.join(ROOT, "include", "krasis_hip.h")).read()
     assert '"%s"' % OPT in header and '"%s"' % MIN in header and DOC in header
     from krasis_amd.decode_store import CpuDecodeStore
@@ -63,23 +64,24 @@ def test_the_options_are_parsed_and_documented():
 
 
 def test_the_refusal_is_a_function_of_its_own_behind_its_siblings():
+    from tests.util import FLAGS, recorded_refusal, rule_place_seen, rule_row
     pre = _src("kr_decode_prefill.cpp")
     span = pre[pre.index("int kr_exact_refuse("):pre.index("int kr_spec_refuse(")]
-    assert OPT not in span                                                    # kr_exact_refuse is as it was
-    mine = _body(pre, "int kr_la_exact_refuse(kr_decode_store* s) {")
-    assert mine.splitlines()[1].strip() == "if (!s->opt_%s || paged_refused(s)) return KR_OK;" % OPT      # its first line
-    assert re.search(r'KR_ERR_STATE[^;]*multi_extend_la_exact[^;]*multi_extend_la_chunk', mine)            # both options: the message names both
-    assert re.search(r"KR_ERR_STATE[^;]*has none", mine) and re.search(r"KR_ERR_VALUE[^;]*not covered", mine)
-    assert mine.count("kr_fail(") == 3 and mine.count(OPT) >= 4 and mine.count("has_attn(s, ATTN_LA)") == 1      # every message names the option
-    assert "kr_multi_lx_ok(L.dk, L.dv, L.nk, L.nv, s->weights[L.qkvz_wid]->rows)" in mine
-    order = [pre.index(f) for f in ("int kr_mla_xs_refuse(", "int kr_la_exact_refuse(")]
-    assert order == sorted(order)
+    assert OPT not in span and "multi_extend" not in span                     # kr_exact_refuse holds the base clauses only
+    row = rule_row(OPT)
+    assert row.startswith('{"multi_extend_la_exact", &KrMultiOpts::extend_la_exact, ATTN_LA, true, "multi_extend_la_chunk", &KrMultiOpts::extend_la_chunk, "the long runs of the linear-attention layers", 0, false, "",')
+    assert re.search(r"KR_ERR_VALUE[^;]*not covered", row) and row.count("kr_fail(") == 1 and row.count(OPT) == 2 and row.rstrip().endswith("nullptr, nullptr},")      # the row's name, which the walk puts into both KR_ERR_STATE messages, and the geometry message; nothing to prepare
+    assert "kr_multi_lx_ok(L.dk, L.dv, L.nk, L.nv, s->weights[L.qkvz_wid]->rows)" in row
+    assert pre.count("bool paged_refused(") == 1 and pre.count("for (const KrOptRule& r : kr_opt_rules)") == 1 and "(r.stand_back && back)) continue;" in pre      # one predicate, one walker: stands back where the entry point's paged refusal applies
     body = _body(_src("kr_decode_multi.cpp"), "int multi_refuse(kr_decode_store* s) {")
-    order = [body.index(c) for c in ("kr_spec_pending_fail(s)", "kr_exact_refuse(s, true)", "kr_xm_refuse(s)", "kr_mla_xm_refuse(s)", "kr_xs_refuse(s)", "kr_mla_xs_refuse(s)",
-                                     "kr_la_exact_refuse(s)")]
+    order = [body.index(c) for c in ("kr_spec_pending_fail(s)", "kr_exact_refuse(s, true)", "return kr_option_rules(s, false);")]
     assert order == sorted(order)
-    assert "if (int rc = kr_mla_xs_refuse(s)) return rc; return kr_la_exact_refuse(s);" in body            # asked only when the sibling ahead of it passed
-    assert "int kr_la_exact_refuse(kr_decode_store* s);" in _src("kr_decode_internal.h")
+    # the last rule of the list: asked only when every sibling ahead of it passed, "multi_mla_exact_split" among them; both options: the message names both
+    assert FLAGS[-1] == OPT and rule_place_seen(OPT) >= 8
+    assert recorded_refusal("gqa/flat", "multi_mla_exact_split", OPT) == recorded_refusal("gqa/flat", "multi_mla_exact_split") != recorded_refusal("gqa/flat", OPT)
+    assert recorded_refusal("la/flat", OPT, "multi_extend_la_chunk") == 'RuntimeError: the "multi_extend_la_exact" and "multi_extend_la_chunk" options both claim the long runs of the linear-attention layers: set one of them to 0'
+    assert recorded_refusal("gqa/flat", OPT) == 'RuntimeError: the "multi_extend_la_exact" option covers linear-attention layers only: this store has none (set the option to 0)'
+    assert recorded_refusal("la/flat", OPT) == "ok" and recorded_refusal("hybrid/paged", OPT) == "ok" and recorded_refusal("hybrid-dk64/flat", OPT) == "ok"
     # the geometry rule is kr_launch_pfm_la's
     lx = _src("kr_multi_la_exact.hip")
     assert "return (dk == 64 || dk == 128) && dv >= dk && dv <= 256 && dv % 8 == 0 && nk >= 1 && nv == nk * (nv / nk) && ld_qkvz % 4 == 0;" in lx
@@ -158,12 +160,12 @@ def test_the_run_kernels_leave_staged_runs_and_option_off_launches_what_it_launc
     assert "if (x && x->n_short == 0) return kr_launch_multi_la_exact(a, *x, runs, st);" in launch           # not launched when every run is staged
     assert launch.index("x->n_short == 0") < launch.index("kr_multi_la_conv_kernel<false>") < launch.index("if (x) return kr_launch_multi_la_exact(a, *x, runs, st);")
     pre = _src("kr_decode_prefill.cpp")
-    assert "if (pl.lx_nruns) m.lx_min = s->opt_%s;" % MIN in pre and "cx.mp->plan.lx_nruns ? &x : nullptr" in pre      # option off: 0 and null
-    assert "o.extend_la_exact = s->opt_%s; o.la_exact_min = s->opt_%s;" % (OPT, MIN) in pre
+    assert "if (pl.lx_nruns) m.lx_min = s->mopt.extend_la_exact_min;" in pre and "cx.mp->plan.lx_nruns ? &x : nullptr" in pre      # option off: 0 and null
+    assert "o.opt = s->mopt;" in pre[pre.index("int kr_multi_pass("):]
     plan = _src("kr_multi_plan.h")
-    assert "o.extend_la_exact && !r.verify && r.counts && nv_max" in plan and _code(plan).count("kr_lx_build(") == 1
-    opts = re.search(r"struct KrMultiPlanOpts \{(.*?)\n\};", plan, re.S).group(1)
-    assert opts.rstrip().splitlines()[-1].strip().startswith("bool extend_la_exact; int la_exact_min;")      # behind the fields existing callers may name in order
+    assert "o.opt.extend_la_exact && !r.verify && r.counts && nv_max" in plan and "o.opt.extend_la_exact_min, xr, x16, x8)" in plan and _code(plan).count("kr_lx_build(") == 1
+    opts = re.search(r"struct KrMultiOpts \{(.*?)\n\};", _src("kr_multi_opts.h"), re.S).group(1)
+    assert [l.strip().split(";")[0] for l in opts.rstrip().splitlines()[-2:]] == ["int extend_la_exact = 0", "int extend_la_exact_min = 8"]      # behind the fields existing callers may name in order
     assert "KrMpSpan lx_runs, lx_t16, lx_t8;" in plan
     tiles = _code(_src("kr_lc_tiles.h"))
     assert "inline KrLxStats kr_lx_build(" in tiles and "hip" not in tiles.lower() and "__device__" not in tiles

@@ -1,5 +1,5 @@
 """The "multi_extend_mla_exact_mfma" option (docs/design/29-multi-extend-mla-exact-mfma.md) without a GPU: the option is known in every layer, the refusal is a
-function of its own behind kr_xm_refuse, the new launcher checks before it launches and ends with the w_vc projection, no C-ABI symbol was added, and the new
+rule of the ordered rule list behind the GQA option's, the new launcher checks before it launches and ends with the w_vc projection, no C-ABI symbol was added, and the new
 kernels are in the library.  (The option adds no host-only helper: its tile tables are kr_pf_tiles.h / kr_xm_tiles.h at the widths 64 / nh and 32 / nh, which
 tests/xm_tiles_check.cpp checks for every width from 1 to 64.)"""
 import os
@@ -32,7 +32,8 @@ def _body(text, head):
 
 def test_the_option_is_known_everywhere():
     assert '!strcmp(name, "%s")' % OPT in _src("kr_decode.cpp")
-    assert "opt_%s" % OPT in _src("kr_decode_internal.h")
+    from tests.util import option_field
+    assert option_field(OPT) == "extend_mla_exact_mfma"
     header = open(os.path.join(ROOT, "include", "krasis_hip.h")).read()
     assert '"%s"' % OPT in header and DOC in header
     from krasis_amd.decode_store import CpuDecodeStore
@@ -52,17 +53,25 @@ def test_the_option_is_known_everywhere():
 
 
 def test_the_refusal_is_a_function_of_its_own_behind_every_earlier_clause():
+    from tests.util import recorded_refusal, rule_place_seen, rule_row
     pre = _src("kr_decode_prefill.cpp")
     span = pre[pre.index("int kr_exact_refuse("):pre.index("int kr_spec_refuse(")]
-    assert OPT not in span                                                    # kr_exact_refuse is as it was
-    assert OPT not in _body(pre, "int kr_xm_refuse(")                         # and so is the GQA option's check
-    mine = _body(pre, "int kr_mla_xm_refuse(")
-    assert re.search(r'KR_ERR_STATE[^;]*multi_extend_mla_exact_mfma[^;]*multi_extend_mla_flash', mine)      # both run options: the message names both
-    assert re.search(r"KR_ERR_STATE[^;]*has none", mine) and re.search(r"KR_ERR_VALUE[^;]*divide 32", mine)
-    assert mine.count(OPT) >= 4 and "kr_mla_exact_mfma_ok(L.nh, L.klr, L.rd)" in mine      # every message names the option; the prompt pass's own geometry rule
-    assert "|| paged_refused(s)) return KR_OK;" in mine and _src("kr_decode_prefill.cpp").count("pg.paged() && s->opt_multi_attn_fast && !s->opt_multi_attn_fast_paged") == 1      # stands back where the entry point's paged refusal applies
-    body = _body(_src("kr_decode_multi.cpp"), "int multi_refuse(")
-    assert body.index("kr_spec_pending_fail(s)") < body.index("kr_exact_refuse(s, true)") < body.index("kr_xm_refuse(s)") < body.index("kr_mla_xm_refuse(s)")
+    assert OPT not in span and "multi_extend" not in span                     # kr_exact_refuse holds the base clauses only
+    assert OPT not in rule_row("multi_extend_exact_mfma")                     # and the GQA option's rule knows nothing of this one
+    row = rule_row(OPT)
+    assert row.startswith('{"multi_extend_mla_exact_mfma", &KrMultiOpts::extend_mla_exact_mfma, ATTN_MLA, true, "multi_extend_mla_flash", &KrMultiOpts::extend_mla_flash, "the runs of >= 2 tokens of the MLA layers", 0, false, "",')
+    assert re.search(r"KR_ERR_VALUE[^;]*divide 32", row) and "kr_mla_exact_mfma_ok(L.nh, L.klr, L.rd)" in row and row.rstrip().endswith("nullptr, nullptr},")      # the prompt pass's own geometry rule; nothing to prepare
+    assert pre.count("bool paged_refused(") == 1 and pre.count("for (const KrOptRule& r : kr_opt_rules)") == 1 and "(r.stand_back && back)) continue;" in pre      # one predicate, one walker: stands back where the entry point's paged refusal applies
+    body = _src("kr_decode_multi.cpp")
+    body = body[body.index("int multi_refuse("):body.index("int need_slots(")]
+    assert body.index("kr_spec_pending_fail(s)") < body.index("kr_exact_refuse(s, true)") < body.index("return kr_option_rules(s, false);")
+    # as a caller sees it: both run options -- the message names both; every message names the option; behind the GQA option's rule
+    assert rule_place_seen(OPT) >= 8
+    assert recorded_refusal("mla/flat", OPT, "multi_extend_mla_flash") == 'RuntimeError: the "multi_extend_mla_exact_mfma" and "multi_extend_mla_flash" options both claim the runs of >= 2 tokens of the MLA layers: set one of them to 0'
+    assert recorded_refusal("la/flat", OPT) == 'RuntimeError: the "multi_extend_mla_exact_mfma" option covers MLA layers only: this store has none (set the option to 0)'
+    assert recorded_refusal("la/flat", OPT, "multi_extend_exact_mfma") == recorded_refusal("la/flat", "multi_extend_exact_mfma")
+    assert recorded_refusal("mla-3-heads/flat", OPT).startswith("ValueError: multi_extend_mla_exact_mfma: MLA geometry heads 3 kv_lora_rank 256 rope 64 not covered (the head count must divide 32")
+    assert recorded_refusal("mla/flat", OPT) == "ok" and recorded_refusal("mla/paged", OPT) == "ok"
 
 
 def test_the_scores_body_is_a_header_of_its_own():
@@ -96,7 +105,7 @@ def test_the_launcher_and_the_pass():
     assert "(a.nh + KR_MM_HG - 1) / KR_MM_HG, n_runs)" in mine                # the per-row kernel over the first n_runs rows
     assert mine.rstrip().endswith("kr_launch_mla_wvc(m, st, B);\n    return 0;")      # ends with the w_vc projection over all rows
     pre = _src("kr_decode_prefill.cpp")
-    assert "o.extend_mla_exact_mfma = s->opt_multi_extend_mla_exact_mfma;" in pre and case_passed("F") and case_passed("K")      # never in a verify pass (docs/design/32-multi-pass-plan.md)
+    assert "o.opt = s->mopt;" in pre and "o.opt.extend_mla_exact_mfma ? KR_MP_RUNS_XM" in _src("kr_multi_plan.h") and case_passed("F") and case_passed("K")      # never in a verify pass (docs/design/32-multi-pass-plan.md)
     assert case_passed("J")                                                   # the tables at 64 / nh and 32 / nh, shared with a GQA layer of the same group size
     assert "kr_launch_multi_mla_xm(m, multi_xm_args(P, L.nh, 1), P.runs, P.nruns, P.plan.n_unit, Cc, st)" in pre
 

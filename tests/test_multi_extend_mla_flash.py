@@ -26,7 +26,8 @@ def _code(text):
 
 def test_the_option_is_known_everywhere():
     assert '!strcmp(name, "%s")' % OPT in _src("kr_decode.cpp")
-    assert "opt_%s" % OPT in _src("kr_decode_internal.h")
+    from tests.util import option_field
+    assert option_field(OPT) == "extend_mla_flash"
     header = open(os.path.join(ROOT, "include", "krasis_hip.h")).read()
     assert header.count('"%s"' % OPT) >= 2 and DOC in header               # the option's paragraph and kr_decode_extend_multi's comment
     from krasis_amd.decode_store import CpuDecodeStore
@@ -84,23 +85,26 @@ def test_one_body_with_a_row_map_and_two_kinds_of_caller():
 
 
 def test_refusal_clause_stands_between_its_neighbours_and_names_the_option():
+    from tests.util import FLAGS, recorded_refusal, rule_row
     pre = _src("kr_decode_prefill.cpp")
-    refuse = pre[pre.index("int kr_exact_refuse("):pre.index("int kr_spec_refuse(")]
-    mine = refuse.index("slots && s->opt_%s && !paged_refused" % OPT)        # stands back where the entry point's paged refusal applies
-    for earlier in ("is exact-mode only: the attention mode has tolerance bits set", "slots && (s->opt_multi_attn_fast || s->opt_multi_attn_fast_paged)",
-                    "does not run under expert parallelism", "slots && s->opt_multi_mla_fast", "multi_mla_fast: MLA geometry heads"):
-        assert refuse.index(earlier) < mine, earlier
-    assert pre.index("bool paged_refused(const kr_decode_store* s) {") < pre.index("int kr_exact_refuse(")      # the predicate, stated once ahead of its users
-    nxt = refuse.index("slots && s->opt_multi_extend_flash && !paged_refused")
-    assert mine < nxt < refuse.index("slots && s->opt_multi_extend_la_chunk && !paged_refused")
-    clause = refuse[mine:nxt]
-    clause = clause[:clause.rindex("    // \"multi_extend_flash\"")]            # up to the next clause's comment
-    assert "multi_extend_flash" not in clause and "multi_extend_la_chunk" not in clause
-    assert clause.count('\\"%s\\"' % OPT) == 1 and clause.count(OPT + ":") == 1      # no MLA layer | LDS window
-    assert re.search(r"KR_ERR_STATE[^;]*has none", clause) and re.search(r"KR_ERR_HIP[^;]*LDS window", clause)
-    assert "kr_multi_mla_pf_prepare(L.klr, s->multi->kv_fp8, s->multi->pg.paged())" in clause and "mf_ready" in clause      # windows once per slot set, outside the pass
+    row = rule_row(OPT)
+    # stands back where the entry point's paged refusal applies; no rival, no MLA step, no geometry rule of its own
+    assert row.startswith('{"multi_extend_mla_flash", &KrMultiOpts::extend_mla_flash, ATTN_MLA, true, nullptr, nullptr, nullptr, 0, false, " for the exact pass", nullptr,')
+    assert pre.index("bool paged_refused(const kr_decode_store* s) {") < pre.index("int kr_exact_refuse(") < pre.index("int kr_option_rules(")      # the predicate, stated once ahead of its users
+    assert FLAGS.index("multi_mla_fast") < FLAGS.index(OPT) < FLAGS.index("multi_extend_flash") < FLAGS.index("multi_extend_la_chunk")      # the order test_multi_pass_plan.py holds the table to
+    assert "multi_extend_flash" not in row and "multi_extend_la_chunk" not in row
+    assert row.count(OPT + ":") == 1 and re.search(r"KR_ERR_HIP[^;]*LDS window", row)      # LDS window; "has none" takes the row's name
+    assert "kr_multi_mla_pf_prepare(L.klr, s->multi->kv_fp8, s->multi->pg.paged())" in row and row.rstrip().endswith("&kr_multi_state::mf_ready},")      # windows once per slot set, outside the pass
     assert "mf_ready" not in pre[pre.index("int kr_multi_pass("):]           # never inside the pass
-    assert "if (paged_refused(s))" in _src("kr_decode_multi.cpp") and _src("kr_decode_prefill.cpp").count("pg.paged() && s->opt_multi_attn_fast && !s->opt_multi_attn_fast_paged") == 1      # the entry points' refusal and its siblings' standing back: one predicate
+    assert "if (paged_refused(s))" in _src("kr_decode_multi.cpp") and pre.count("bool paged_refused(") == 1 and pre.count("for (const KrOptRule& r : kr_opt_rules)") == 1      # one predicate, one walker
+    # between its neighbours, as a caller sees it on a store that refuses both
+    none = 'RuntimeError: the "multi_extend_mla_flash" option covers MLA layers only: this store has none (set the option to 0 for the exact pass)'
+    assert recorded_refusal("gqa/flat", OPT) == none and recorded_refusal("mla/flat", OPT) == "ok"
+    assert 'the "multi_mla_fast" option covers MLA layers only: this store has none' in recorded_refusal("la/flat", "multi_mla_fast", OPT)
+    assert recorded_refusal("la/flat", OPT, "multi_extend_flash") == none and recorded_refusal("gqa/flat", OPT, "multi_extend_la_chunk") == none
+    assert "the attention mode has tolerance bits set" in recorded_refusal("gqa/flat", OPT, mode=True)
+    assert 'the "multi_attn_fast" option covers GQA layers only' in recorded_refusal("mla/flat", "multi_attn_fast", OPT)
+    assert recorded_refusal("gqa/paged", "multi_attn_fast", OPT).startswith('RuntimeError: "multi_attn_fast" does not read paged slots')
 
 
 def test_new_fields_at_the_end_and_per_row_kernels_leave_longer_runs():
@@ -127,7 +131,7 @@ def test_new_fields_at_the_end_and_per_row_kernels_leave_longer_runs():
     assert "a.mf_nruns);" in runs and "kr_launch_multi_mla_fd(a, a.mf_nruns, st)" in runs and "kr_launch_multi_mla_pf_flash(a, st)" in runs
     assert runs.index("kr_launch_multi_mla_pf_flash(a, st)") < runs.index("kr_launch_mla_wvc_mfma(")
     pre = _src("kr_decode_prefill.cpp")
-    assert "o.extend_mla_flash = s->opt_multi_extend_mla_flash;" in pre and case_passed("F") and case_passed("K")      # never in a verify pass (docs/design/32-multi-pass-plan.md)
+    assert "o.opt = s->mopt;" in pre and "o.opt.extend_mla_flash ? KR_MP_RUNS_FLASH" in _src("kr_multi_plan.h") and case_passed("F") and case_passed("K")      # never in a verify pass (docs/design/32-multi-pass-plan.md)
     assert case_passed("C") and case_passed("D")                             # the per-row MLA kernels see the unit rows only; a mixed store keeps the score rows
 
 

@@ -30,9 +30,10 @@ def _lib():
 
 
 def test_the_options_are_known_everywhere():
+    from tests.util import option_field
     dec = _src("kr_decode.cpp")
     for o in (OPT, MIN):
-        assert '!strcmp(name, "%s")' % o in dec and "opt_%s" % o in _src("kr_decode_internal.h")
+        assert '!strcmp(name, "%s")' % o in dec and option_field(o) == o[len("multi_"):]
     assert "if (value < 1) return kr_fail(KR_ERR_VALUE" in dec[dec.index('"%s"))' % MIN):][:300]
     from krasis_amd.decode_store import CpuDecodeStore
     assert OPT in CpuDecodeStore.set_option.__doc__ and MIN in CpuDecodeStore.set_option.__doc__
@@ -50,18 +51,26 @@ def test_the_options_are_known_everywhere():
 
 
 def test_the_refusal_is_asked_last():
-    body = _body(_src("kr_decode_multi.cpp"), "int multi_refuse(kr_decode_store* s) {")
-    order = [body.index(c) for c in ("kr_spec_pending_fail(s)", "kr_exact_refuse(s, true)", "kr_xm_refuse(s)", "kr_mla_xm_refuse(s)", "kr_xs_refuse(s)", "kr_mla_xs_refuse(s)")]
-    assert order == sorted(order)
-    assert body.rstrip().splitlines()[-1].strip().startswith("return kr_mla_xs_refuse(s);")      # last: everything refused before is refused first, with its words
+    from tests.util import FLAGS, recorded_refusal, rule_place_seen, rule_row
     pre = _src("kr_decode_prefill.cpp")
-    mine = _body(pre, "int kr_mla_xs_refuse(kr_decode_store* s) {")
-    assert "KR_ERR_STATE" in mine and "covers MLA layers only: this store has none" in mine and "graph_ok" not in mine
-    assert "|| paged_refused(s)) return KR_OK;" in mine and pre.count("pg.paged() && s->opt_multi_attn_fast && !s->opt_multi_attn_fast_paged") == 1      # stands back where the entry point's paged refusal applies
+    assert pre.count("bool paged_refused(") == 1 and pre.count("for (const KrOptRule& r : kr_opt_rules)") == 1 and "(r.stand_back && back)) continue;" in pre      # one predicate, one walker: stands back where the entry point's paged refusal applies
+    body = _body(_src("kr_decode_multi.cpp"), "int multi_refuse(kr_decode_store* s) {")
+    order = [body.index(c) for c in ("kr_spec_pending_fail(s)", "kr_exact_refuse(s, true)", "return kr_option_rules(s, false);")]
+    assert order == sorted(order)
+    row = rule_row(OPT)      # "has none" and nothing else: no rival, no MLA step, no geometry rule, nothing to prepare; stands back
+    assert row == '{"multi_mla_exact_split", &KrMultiOpts::mla_exact_split, ATTN_MLA, true, nullptr, nullptr, nullptr, 0, false, "", nullptr, nullptr, nullptr},'
+    walk = pre[pre.index("int kr_option_rules("):]
+    assert "graph_ok" not in walk[:walk.index("\n}\n")]
+    # last of the options that existed then, ahead of "multi_extend_la_exact" alone: everything refused before is refused first, with its words
+    assert FLAGS[-2:] == (OPT, "multi_extend_la_exact") and rule_place_seen(OPT) >= 8
+    mine = 'RuntimeError: the "multi_mla_exact_split" option covers MLA layers only: this store has none (set the option to 0)'
+    assert recorded_refusal("gqa/flat", OPT) == mine and recorded_refusal("gqa/flat", OPT, "multi_extend_la_exact") == mine
+    assert recorded_refusal("la/flat", OPT, "multi_attn_exact_split") == recorded_refusal("la/flat", "multi_attn_exact_split")
+    assert recorded_refusal("mla/flat", OPT) == "ok" and recorded_refusal("mla/paged", OPT) == "ok" and recorded_refusal("mla-3-heads/flat", OPT) == "ok"
     # the pass-level choice: the plan's (docs/design/32-multi-pass-plan.md)
-    assert "o.mla_exact_split_min = s->opt_multi_mla_exact_split_min;" in pre and "o.mla_exact_split && has_mla && p.mla_pos + 1 >= o.mla_exact_split_min" in _src("kr_multi_plan.h")
+    assert "o.opt = s->mopt;" in pre and "o.opt.mla_exact_split && has_mla && p.mla_pos + 1 >= o.opt.mla_exact_split_min" in _src("kr_multi_plan.h")
     assert case_passed("H") and "m.xs_split = pl.mla_xs_split;" in pre
-    assert "int kr_mla_xs_refuse(kr_decode_store* s);" in _src("kr_decode_internal.h")
+    assert "int kr_option_rules(kr_decode_store* s, bool prepare);" in _src("kr_decode_internal.h")
 
 
 def test_the_three_sites_take_the_split_behind_their_own_checks():

@@ -65,17 +65,27 @@ def test_launcher_dispatches_and_prepares_the_paged_instantiations():
 
 def test_the_option_is_known_everywhere():
     assert '!strcmp(name, "%s")' % OPT in _src("kr_decode.cpp")
-    assert "opt_%s" % OPT in _src("kr_decode_internal.h")
+    from tests.util import option_field, recorded_refusal, rule_row
+    assert option_field(OPT) == "mla_fast"
     pre = _src("kr_decode_prefill.cpp")
     plan = _src("kr_multi_plan.h")
-    assert "o.mla_fast = s->opt_multi_mla_fast;" in pre and "o.mla_fast && has_mla && o.max_seq > o.mla_split_min" in plan
+    assert "o.opt.mla_fast && has_mla && o.max_seq > o.mla_split_min" in plan
     # the two GQA options keep their clauses, ahead of the new option's
-    assert "o.attn_fast = s->opt_multi_attn_fast || s->opt_multi_attn_fast_paged;" in pre
-    assert plan.index("o.attn_fast && has_gqa && o.max_seq > o.gqa_split_min") < plan.index("o.mla_fast && has_mla && o.max_seq > o.mla_split_min")
+    assert "o.attn_fast = s->mopt.attn_fast || s->mopt.attn_fast_paged;" in pre
+    assert plan.index("o.attn_fast && has_gqa && o.max_seq > o.gqa_split_min") < plan.index("o.opt.mla_fast && has_mla && o.max_seq > o.mla_split_min")
     refuse = pre[pre.index("int kr_exact_refuse("):pre.index("int kr_spec_refuse(")]
-    assert refuse.index("slots && (s->opt_multi_attn_fast || s->opt_multi_attn_fast_paged)") < refuse.index("slots && s->opt_multi_mla_fast")
-    assert refuse.index("does not run under expert parallelism") < refuse.index("slots && s->opt_multi_mla_fast")
-    assert refuse.count(OPT + ":") + refuse.count('\\"%s\\"' % OPT) >= 2   # both refusals name the option
+    assert refuse.index("slots && (s->mopt.attn_fast || s->mopt.attn_fast_paged)") < refuse.index("does not run under expert parallelism")
+    # its rule is the first of the list, which is walked behind every base clause; it alone does not stand back, and its geometry rule is asked ahead of "has none"
+    row = rule_row(OPT)
+    assert pre.index("int kr_spec_refuse(") < pre.index("static const KrOptRule kr_opt_rules[] = {") < pre.index(row[:40])
+    assert row.startswith('{"multi_mla_fast", &KrMultiOpts::mla_fast, ATTN_MLA, false, nullptr, nullptr, nullptr, 0, true, " for the exact step",')
+    assert row.count(OPT + ":") + row.count('"%s"' % OPT) >= 2   # both refusals name the option
+    # where the order is seen: on an MLA-only store the GQA options' clause speaks ahead of this option's rule; on a store without MLA layers the option
+    # refuses, also on paged slots under "multi_attn_fast" alone; the attention-mode bit speaks ahead of it
+    assert 'the "multi_attn_fast" option covers GQA layers only: layer 0 is MLA' in recorded_refusal("mla/flat", "multi_attn_fast", OPT)
+    none = 'RuntimeError: the "multi_mla_fast" option covers MLA layers only: this store has none (set the option to 0 for the exact step)'
+    assert recorded_refusal("gqa/flat", OPT) == none and recorded_refusal("hybrid/paged", "multi_attn_fast", OPT) == none and recorded_refusal("mla/flat", OPT) == "ok"
+    assert "the attention mode has tolerance bits set" in recorded_refusal("la/flat", OPT, mode=True)
     header = open(os.path.join(ROOT, "include", "krasis_hip.h")).read()
     assert header.count('"%s"' % OPT) >= 3
     from krasis_amd.decode_store import CpuDecodeStore

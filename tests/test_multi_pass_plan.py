@@ -48,7 +48,9 @@ def test_the_planner_is_host_only():
     src = _src("kr_multi_plan.h")
     code = re.sub(r"//.*", "", src)
     assert "hip" not in code.lower() and "__device__" not in code
-    assert set(re.findall(r"#include [<\"]([^>\"]+)[>\"]", src)) == {"stddef.h", "stdint.h", "vector", "kr_lc_tiles.h", "kr_mf_tiles.h", "kr_pf_tiles.h", "kr_xm_tiles.h"}
+    assert set(re.findall(r"#include [<\"]([^>\"]+)[>\"]", src)) == {"stddef.h", "stdint.h", "vector", "kr_lc_tiles.h", "kr_mf_tiles.h", "kr_multi_opts.h", "kr_pf_tiles.h", "kr_xm_tiles.h"}
+    opts = _src("kr_multi_opts.h")      # the options value the plan is handed whole: host only, nothing included
+    assert "hip" not in re.sub(r"//.*", "", opts).lower() and "#include" not in opts and "kr_multi_opts.h" in _src("Makefile")
     assert "kr_multi_plan.h" in _src("Makefile")
     pre = _src("kr_decode_prefill.cpp")
     assert '#include "kr_multi_plan.h"' in pre
@@ -90,19 +92,45 @@ def test_chunk_has_one_batched_pass_member_and_three_arg_functions():
 
 
 def test_the_refusals_share_one_predicate_and_one_loop():
+    from tests.util import FLAGS, recorded_refusal
     pre = _src("kr_decode_prefill.cpp")
-    assert pre.count("pg.paged() && s->opt_multi_attn_fast && !s->opt_multi_attn_fast_paged") == 1      # the predicate's one copy ...
-    assert "bool paged_refused(const kr_decode_store* s) { return s->multi && s->multi->pg.paged() && s->opt_multi_attn_fast && !s->opt_multi_attn_fast_paged; }" in pre
-    assert "pg.paged() && s->opt_multi_attn_fast" not in _src("kr_decode_multi.cpp")
-    for fn in ("int kr_xm_refuse(", "int kr_mla_xm_refuse(", "int kr_xs_refuse(", "int kr_mla_xs_refuse("):
-        body = pre[pre.index(fn):]
-        body = body[:body.index("\n}\n")]
-        assert "|| paged_refused(s)) return KR_OK;" in body and body.count("has_attn(s, ATTN_") == 1, fn
+    assert pre.count("pg.paged() && s->mopt.attn_fast && !s->mopt.attn_fast_paged") == 1      # the predicate's one copy ...
+    assert "bool paged_refused(const kr_decode_store* s) { return s->multi && s->multi->pg.paged() && s->mopt.attn_fast && !s->mopt.attn_fast_paged; }" in pre
+    assert pre.count("bool paged_refused(") == 1 and "pg.paged() && s->mopt.attn_fast" not in _src("kr_decode_multi.cpp")
+    # ... asked once, by the one walker of the one rule list: nine rules, in the order a caller sees (tests/test_multi_option_refusals_gpu.py)
+    assert pre.count("paged_refused(s)") == 1 and pre.count("for (const KrOptRule& r : kr_opt_rules)") == 1 and pre.count("kr_opt_rules") == 2
+    walk = pre[pre.index("int kr_option_rules("):]
+    walk = walk[:walk.index("\n}\n")]
+    assert "const bool back = paged_refused(s);" in walk and "(r.stand_back && back)) continue;" in walk and walk.count("has_attn(s, r.kind)") == 1
+    table = pre[pre.index("static const KrOptRule kr_opt_rules[] = {"):pre.index("int kr_option_rules(")]
+    assert re.findall(r'\n    \{"(multi_\w+)", &KrMultiOpts::(\w+), ATTN_\w+, (true|false),', table) == [(f, f[len("multi_"):], "false" if f == "multi_mla_fast" else "true") for f in FLAGS[2:]]
     exact = pre[pre.index("int kr_exact_refuse("):pre.index("int kr_spec_refuse(")]
-    assert exact.count("!paged_refused(s)") == 3 and exact.count("has_attn(s, ATTN_") == 4
+    assert "paged_refused" not in exact and "has_attn" not in exact and "hipSetDevice" not in exact and "_prepare(" not in exact      # base clauses only, and no work
     refuse = re.search(r"int paged_refuse\(kr_decode_store\* s\) \{(.*?)\n\}", _src("kr_decode_multi.cpp"), re.S).group(1)
     assert "if (paged_refused(s))" in refuse
     hdr = _src("kr_decode_internal.h")
     assert "bool paged_refused(const kr_decode_store* s);" in hdr and "bool has_attn(const kr_decode_store* s, int kind);" in hdr
-    order = [pre.index(f) for f in ("int kr_exact_refuse(", "int kr_xm_refuse(", "int kr_mla_xm_refuse(", "int kr_xs_refuse(", "int kr_mla_xs_refuse(")]
-    assert order == sorted(order)      # five functions, in the order multi_refuse asks them
+    assert "int kr_option_rules(kr_decode_store* s, bool prepare);" in hdr and not re.search(r"int kr_\w+_refuse\((?!kr_decode_store\* s(, bool slots)?\);)", hdr)
+    assert len(re.findall(r"\nint kr_\w*refuse\(", pre)) == 2      # kr_exact_refuse and kr_spec_refuse: the five option functions are gone
+    # what standing back gives a caller: on paged slots under "multi_attn_fast" alone the entry point's words come back whatever else is set, except that
+    # "multi_mla_fast" does not stand back
+    for store in ("la/paged", "gqa/paged", "hybrid/paged"):
+        for f in FLAGS[3:]:
+            assert recorded_refusal(store, "multi_attn_fast", f).startswith('RuntimeError: "multi_attn_fast" does not read paged slots'), (store, f)
+        assert 'the "multi_mla_fast" option covers MLA layers only: this store has none' in recorded_refusal(store, "multi_attn_fast", "multi_mla_fast")
+
+
+def test_preparing_is_not_refusing():
+    """the LDS windows are raised by the walk's second visit, which multi_begin makes once every refusal has passed; the refusing visit does no work"""
+    pre, multi = _src("kr_decode_prefill.cpp"), _src("kr_decode_multi.cpp")
+    walk = pre[pre.index("int kr_option_rules("):]
+    walk = walk[:walk.index("\n}\n")]
+    prep = walk[walk.index("if (prepare) {"):walk.index("const char* kind")]
+    assert "hipSetDevice" in prep and "r.prepare(s)" in prep and prep.rstrip().endswith("continue;\n        }") and "hipSetDevice" not in walk.replace(prep, "")
+    begin = multi[multi.index("int multi_begin("):multi.index("int slot_in_range(")]
+    assert begin.index("if (int rc = multi_refuse(s)) return rc;") < begin.index("return kr_option_rules(s, true);")
+    refuse = multi[multi.index("int multi_refuse("):multi.index("int need_slots(")]
+    order = [refuse.index(w) for w in ("kr_spec_pending_fail(s)", "kr_exact_refuse(s, true)", "return kr_option_rules(s, false);")]
+    assert order == sorted(order) and refuse.count("return") == 3
+    p = pre[pre.index("int kr_multi_pass("):]
+    assert "kr_option_rules" not in p and "pf_prepare" not in p and "lc_prepare" not in p      # never inside the pass
