@@ -463,7 +463,7 @@ __global__ void __launch_bounds__(256) kr_route_fused_decode_kernel(const KrRout
 // ------------------------------------------------------------------------------------------
 void kr_launch_route_logits_decode(const void* gate_cm, int gate_bf16, const float* x, const float* bias, float* logits,
                                    int m, int E, int H, hipStream_t st) {
-    dim3 grid((E / 4 + 3) / 4, m);
+    dim3 grid(((E + 3) / 4 + 3) / 4, m);      // a wave per block of 4 experts, the last block may be partial (E = 130: 33 blocks)
     const size_t lds = (size_t)16 * (H / 16 + 4) * 4;
     if (gate_bf16) hipLaunchKernelGGL(kr_route_logits_decode_kernel<true>, grid, dim3(256), lds, st, gate_cm, x, bias, logits, E, H);
     else hipLaunchKernelGGL(kr_route_logits_decode_kernel<false>, grid, dim3(256), lds, st, gate_cm, x, bias, logits, E, H);
@@ -490,7 +490,7 @@ int kr_launch_route_fused_decode(const void* gate_cm, int gate_bf16, const float
     a.x = x; a.hid_in = hid_in; a.res_in = res_in; a.norm_w = norm_w; a.hid_out = hid_out; a.res_out = res_out; a.eps = eps; a.bias_one = bias_one; a.H = H;
     const int nv = (E + 63) / 64;
     if (H % 128 || topk > 32) return 1;
-    dim3 grid((E / 4 + 3) / 4);
+    dim3 grid(((E + 3) / 4 + 3) / 4);      // as kr_launch_route_logits_decode: E / 4 left the experts of a partial last block without logits
     const size_t sel_f = (size_t)(2 * E + 33 + 33 + 32 + 32 + 4);
     const size_t norm_f = (size_t)16 * (H / 16 + 4) + (size_t)H + 4 + (size_t)8 * (H / 8 + 4);
     const size_t lds = (norm_f > sel_f ? norm_f : sel_f) * 4;

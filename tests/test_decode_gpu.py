@@ -15,13 +15,34 @@ def _ptr(a):
     return a.ctypes.data
 
 
+class _NoDevice:
+    """build(oracle_only=True): stands in for the store and the engine.  It knows the calls build() makes and nothing else; each does nothing and returns None
+    (the ids a store hands out are only ever passed back to it)"""
+    CALLS = ("configure", "set_routing_config", "set_moe_store", "store_weight_f32", "store_norm_weight", "configure_decode", "add_decode_la_layer",
+             "add_decode_gqa_layer", "set_decode_layer_dense", "set_decode_layer_moe", "load_unified_expert", "set_route_weight_f32", "set_decode_rope",
+             "finalize_decode", "set_decode_state")
+
+    def __init__(self, *a, **k):
+        pass
+
+    def __getattr__(self, name):
+        if name not in self.CALLS:
+            raise AttributeError("build(oracle_only=True) has no device: %s" % name)
+        return lambda *a, **k: None
+
+
 def build(seed=0, norm_bias_one=True, scoring=1, rsf=1.0, with_dense=False, wbits=4, kv_max=32, hd=64, nh=4, dims=None, kinds=None, la_heads=(2, 4), peaked=False, gguf=False,
-          la_dkdv=(128, 128)):
+          la_dkdv=(128, 128), emb_spikes=(), out_scale=0.05, oracle_only=False):
     """peaked=True: a model whose next-token distribution is PEAKED without training -- large embeddings, lm_head tied to them (x 0.05): the logit of the
     current token stands ~8 above the rest, the layers (attention, router, experts) perturb it by an amount comparable to the noise floor, so on a token
     stream with repeats the perplexity is O(10) and a routing flip or a tolerance-mode rounding difference shows up in it (tests/test_tolerance_peaked_gpu.py).
-    wbits: 4 | 8 for every matrix, or a callable matrix name -> 4 | 8 (names: lm_head, qkvz, ba, out, q, k, v, o, gate, up, down, experts, sgu, sd, sg)"""
+    wbits: 4 | 8 for every matrix, or a callable matrix name -> 4 | 8 (names: lm_head, qkvz, ba, out, q, k, v, o, gate, up, down, experts, sgu, sd, sg)
+    out_scale: standard deviation of the out / o projection's weights; 0.0 makes the attention branch add exactly nothing to the residual in every mode.
+    emb_spikes: (row, index) pairs -- that element of the embedding row is set so that it holds 90 % of the row's energy (draws nothing from the generator).
+    oracle_only=True: no device store and no engine are made (_NoDevice stands in for both): the oracle side alone, for tests without a GPU"""
     from krasis_amd import CpuDecodeStore, KrasisEngine, ModelConfig
+    if oracle_only:
+        CpuDecodeStore = KrasisEngine = _NoDevice
     rng = np.random.default_rng(seed)
     H, V, E, k, I, SI = dims or (256, 512, 16, 4, 128, 128)
     (nk, nv), (dk, dv) = la_heads, la_dkdv
@@ -29,6 +50,9 @@ def build(seed=0, norm_bias_one=True, scoring=1, rsf=1.0, with_dense=False, wbit
     kinds = kinds or (["la", "gqa", "la"] + (["gqa"] if with_dense else []))
     nL = len(kinds)
     emb = ((rng.random((V, H)) - 0.5) * (3.0 if peaked else 0.2)).astype(F)
+    for row, idx in emb_spikes:
+        emb[row, idx] = 0.0
+        emb[row, idx] = F(np.sqrt(9.0 * float((emb[row].astype(np.float64) ** 2).sum())))
     eng = KrasisEngine(); eng.configure(ModelConfig(H, I, E, k, nL, 0, rsf))
     eng.set_routing_config("softmax" if scoring == 1 else "sigmoid", True, k, E, H)
     st = CpuDecodeStore(128, True, norm_bias_one); st.set_moe_store(eng)
@@ -61,7 +85,7 @@ def build(seed=0, norm_bias_one=True, scoring=1, rsf=1.0, with_dense=False, wbit
         L = dict(in_norm=n_in[1], post_norm=n_post[1], attn=kind)
         if kind == "la":
             hr = nv // nk; group_dim = 2 * dk + 2 * dv * hr; conv_dim = 2 * nk * dk + nv * dv
-            qkvz = W("qkvz", nk * group_dim, H, 0.08); ba = W("ba", nk * 2 * hr, H, 0.3); out = W("out", H, nv * dv)
+            qkvz = W("qkvz", nk * group_dim, H, 0.08); ba = W("ba", nk * 2 * hr, H, 0.3); out = W("out", H, nv * dv, out_scale)
             conv_w = (rng.standard_normal(conv_dim * 4) * 0.4).astype(F); a_log = (rng.random(nv) * 1.5 - 1.0).astype(F)
             dt_bias = (rng.random(nv) - 0.5).astype(F); norm_w = (rng.random(nv * dv) + 0.5).astype(F)
             keep += [conv_w, a_log, dt_bias, norm_w]
@@ -73,7 +97,7 @@ def build(seed=0, norm_bias_one=True, scoring=1, rsf=1.0, with_dense=False, wbit
             L.update(qkvz=qkvz[1], ba=ba[1], out=out[1], conv_w=conv_w, a_log=a_log, dt_bias=dt_bias, norm_w=norm_w, nk=nk, nv=nv, dk=dk, dv=dv,
                      scale=scale, conv_state=cs.copy(), recur_state=rs.copy())
         else:
-            q = W("q", nh * hd * 2, H, 0.08); kk = W("k", nkv * hd, H, 0.08); v = W("v", nkv * hd, H, 0.08); o = W("o", H, nh * hd)
+            q = W("q", nh * hd * 2, H, 0.08); kk = W("k", nkv * hd, H, 0.08); v = W("v", nkv * hd, H, 0.08); o = W("o", H, nh * hd, out_scale)
             qn = (rng.random(hd) + 0.5).astype(F); kn = (rng.random(nkv * hd) + 0.5).astype(F); keep += [qn, kn]   # shared vs per-head norm weights
             sm = F(1.0 / np.sqrt(hd))
             st.add_decode_gqa_layer(n_in[0], n_post[0], q[0], kk[0], v[0], o[0], _ptr(qn), qn.size, _ptr(kn), kn.size, True, nh, nkv, hd, float(sm))
@@ -297,6 +321,22 @@ def test_decode_step_production_widths_bit_exact(dims, hd, nh):
         ref = orc.step(tok, pos)
         assert np.array_equal(logits.view(np.uint32), ref.view(np.uint32)), (pos, float(np.max(np.abs(logits - ref))))
         tok = O.sample_greedy(ref)
+
+
+def test_router_logits_of_a_partial_expert_block_bit_exact():
+    """E = 130: the 33rd block of four experts holds two.  The router launch must give experts 128 and 129 their logits: all 130 logits, the ids and the
+    weights of the exact step against the oracle, bit for bit, on tokens of which the oracle routes four to expert 128 or 129"""
+    from tests import decode_f64 as M
+    st, eng, orc, keep, d = build(dims=(256, 512, 130, 6, 128, 128), kinds=["gqa"], seed=57)
+    lg = np.empty(d["V"], F); hit = 0
+    for tok in (3, 9, 21, 37, 52, 101):
+        d["reset"](); st.decode_step(tok, 6, lg.ctypes.data)
+        ref = M.step(orc, tok, 6, M.Ref())
+        logits, ids, w = st.read_router(130, 6)
+        assert np.array_equal(logits.view(np.uint32), ref["router_logits"].view(np.uint32)), tok
+        assert np.array_equal(ids, ref["router_ids"]) and np.array_equal(w.view(np.uint32), ref["router_w"].view(np.uint32)), tok
+        hit += int(bool(np.isin(ref["router_ids"], (128, 129)).any()))
+    assert hit >= 4, "too few tokens routed to expert 128 or 129: the partial block was not exercised"
 
 
 def test_generate_batch_greedy_matches_oracle():
