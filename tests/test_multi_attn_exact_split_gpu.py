@@ -6,14 +6,10 @@ passes and generation, on flat, paged and forked slots, FP16 and E4M3 caches.  T
 The reference is never the new path: it is the same call with the option off on equally filled slots and, in test 1, also the store's own decode_step on each
 sequence alone (computed once per geometry and shared).  Every comparison is on ids and u32 / stored-row bit patterns.  Every test sets
 "multi_attn_exact_split_min" to 1, so these small caches take the split."""
-import functools
-
 import numpy as np
 import pytest
 
-from tests.test_decode_gpu import build
-from tests.test_multi_paged_gpu import _state_error
-from tests.test_speculative_gpu import _same, _snap
+from tests.slots import Gqa, bits as _bits, cached, equal, fill_upto, off_on, options_reset, pages as _pages, slot_state, state_error, store_cache
 
 pytestmark = pytest.mark.gpu
 U = np.uint32
@@ -41,43 +37,23 @@ _stores = []
 ALL_OPTS = (OPT, "multi_extend_exact_mfma", "multi_extend_flash", "multi_attn_fast", "multi_attn_fast_paged")
 
 
-@pytest.fixture(autouse=True)
-def options_off_afterwards():
-    yield
-    for st in _stores:
-        for o in ALL_OPTS:
-            st.set_option(o, 0)
-        st.set_option(MIN, 1)
-        st.set_attention_mode(False)
+options_off_afterwards = options_reset(_stores, ALL_OPTS + ((MIN, 1),))
 
 
-def _bits(x):
-    return np.ascontiguousarray(x).view(U).copy()
-
-
-def _pages(n, pt):
-    return (n + pt - 1) // pt
-
-
-@functools.lru_cache(maxsize=None)
+@store_cache(_stores, MIN)
 def _model(hd, nh, fp8, kv_max=KV_MAX, kinds=("gqa", "gqa")):
     """one store per geometry, built once and shared"""
-    st, eng, orc, keep, d = build(seed=3, hd=hd, nh=nh, kv_max=kv_max, kinds=list(kinds))
-    if fp8:
-        st.set_kv_dtype(True); d["fp8"] = True
-    st.set_option(MIN, 1)
-    _stores.append(st)
-    return st, (eng, orc, keep), d
+    return Gqa.build(fp8, seed=3, hd=hd, nh=nh, kv_max=kv_max, kinds=list(kinds))
 
 
-@functools.lru_cache(maxsize=None)
+@cached
 def _seq(hd, nh, fp8, kv_max=KV_MAX):
     """the one token sequence of a geometry: row p of every test consumes token p behind the prefix [0, p)"""
     d = _model(hd, nh, fp8, kv_max)[2]
     return tuple(int(x) for x in np.random.default_rng(hd + nh + kv_max).integers(0, d["V"], kv_max))
 
 
-@functools.lru_cache(maxsize=None)
+@cached
 def _single(hd, nh, fp8, kv_max=KV_MAX):
     """the single-sequence reference, computed once and never modified: the sequence by the store's own exact prompt pass, the token at every position of POS by
     decode_step -> {position: (logits bits, greedy id)}, and the K / V rows of the whole sequence"""
@@ -90,59 +66,16 @@ def _single(hd, nh, fp8, kv_max=KV_MAX):
         st.decode_step(seq[p], p)
         out[p] = (_bits(st.read_logits()), st.last_token())
         at = p + 1
-    return out, _snap(st, d, kv_max)
-
-
-def _fill(st, d, seq, want):
-    """want = [(slot, n)]: the first n tokens of seq, by the exact prompt pass on the store's own sequence, into the slot (GQA stores: one pass serves every n)"""
-    st.reset_decode_state(d["kv_max"])
-    top = max(n for _, n in want)
-    if top:
-        st.prefill(list(seq[:top]), 0)
-    for s, n in want:
-        st.save_slot(s, n)
-
-
-def _slot_state(st, d, slot, upto):
-    st.reset_decode_state(d["kv_max"])
-    st.load_slot(slot, upto)
-    return _snap(st, d, upto)
-
-
-def _upto(snap, n):
-    return [(k, li, a[:n], b[:n]) for k, li, a, b in snap]
-
-
-def _equal(a, b, where=""):
-    """two results (ids, logits, slot states) of one scenario: bit for bit"""
-    assert [int(x) for x in a[0]] == [int(x) for x in b[0]], ("ids", where)
-    assert np.array_equal(_bits(a[1]), _bits(b[1])), ("logits", where)
-    assert len(a[2]) == len(b[2])
-    for x, y in zip(a[2], b[2]):
-        _same(x, y)
-
-
-def _off_on(st, scenario, **other):
-    """scenario(st) -> (ids, logits, states) on slots it creates and fills itself, once with the option off and once with it on; `other` options stay set for both"""
-    out = []
-    for on in (0, 1):
-        for o, v in other.items():
-            st.set_option(o, v)
-        st.set_option(OPT, on)
-        out.append(scenario(st))
-        st.set_option(OPT, 0)
-        for o in other:
-            st.set_option(o, 0)
-    return out
+    return out, Gqa.snap(st, d, kv_max)
 
 
 def _steps(st, d, seq, pos, n_slots=16, kv_max=KV_MAX, **slots_kw):
     """one step_multi: row i consumes token pos[i] of seq at position pos[i] in slot SLOTS[i] -> (ids, logits, states)"""
     st.create_slots(n_slots, kv_max, **slots_kw)
     slots = SLOTS[:len(pos)]
-    _fill(st, d, seq, list(zip(slots, pos)))
+    fill_upto(st, d, seq, list(zip(slots, pos)))
     ids, lg = st.step_multi(slots, [seq[p] for p in pos], list(pos), logits=True)
-    return ids, lg, [_slot_state(st, d, s, p + 1) for s, p in zip(slots, pos)]
+    return ids, lg, [slot_state(Gqa, st, d, s, p + 1) for s, p in zip(slots, pos)]
 
 
 # ---- 1: on == off == decode_step on each sequence alone ----------------------------------------------------------------------------------------------------
@@ -160,12 +93,12 @@ def test_step_multi_equals_option_off_and_decode_step(hd, nh, fp8, kv_max):
         took.append(st.multi_path_counts()["xs_split"])
         return out
 
-    off, on = _off_on(st, counted)
+    off, on = off_on(st, OPT, counted)
     assert took == [0, 1], ("xs_split", took)
-    _equal(on, off)
+    equal(Gqa, on, off)
     for i, p in enumerate(pos):
         assert np.array_equal(_bits(on[1][i]), single[p][0]) and int(on[0][i]) == single[p][1], ("decode_step", p)
-        _same(on[2][i], _upto(snap, p + 1))
+        Gqa.same(on[2][i], Gqa.upto(snap, p + 1))
 
 
 # ---- 2: mixed passes through extend_multi -------------------------------------------------------------------------------------------------------------------
@@ -189,14 +122,14 @@ def test_mixed_passes_through_extend_multi(hd, nh, fp8, other):
         for rows in (MIXED, RUNS_ONLY, UNITS_ONLY):
             slots = SLOTS[at:at + len(rows)]
             at += len(rows)
-            _fill(st, d, seq, [(s, p) for s, (p, _) in zip(slots, rows)])
+            fill_upto(st, d, seq, [(s, p) for s, (p, _) in zip(slots, rows)])
             i, lg = st.extend_multi(slots, [list(seq[p:p + c]) for p, c in rows], [p for p, _ in rows], logits=True)
             ids += list(i); lgs.append(lg)
-            states += [_slot_state(st, d, s, p + c) for s, (p, c) in zip(slots, rows)]
+            states += [slot_state(Gqa, st, d, s, p + c) for s, (p, c) in zip(slots, rows)]
         return ids, np.concatenate(lgs), states
 
-    off, on = _off_on(st, scenario, **({other: 1} if other else {}))
-    _equal(on, off, other)
+    off, on = off_on(st, OPT, scenario, **({other: 1} if other else {}))
+    equal(Gqa, on, off, other)
 
 
 # ---- 3: verify ----------------------------------------------------------------------------------------------------------------------------------------------
@@ -214,7 +147,7 @@ def test_verify_and_commit(hd, nh, fp8, sample):
     def scenario(st):
         st.create_slots(16, KV_MAX)
         slots = SLOTS[:len(VERIFY_POS)]
-        _fill(st, d, seq, list(zip(slots, VERIFY_POS)))
+        fill_upto(st, d, seq, list(zip(slots, VERIFY_POS)))
         if sample:
             for i, s in enumerate(slots):
                 st.set_slot_sampler(s, seq[VERIFY_POS[i]], 0.8, 40, 0.95, 0.5, 100 + i)
@@ -234,10 +167,10 @@ def test_verify_and_commit(hd, nh, fp8, sample):
             g2, nm2 = verify(slots, [list(seq[p:p + 3]) for p in VERIFY_POS], VERIFY_POS)
             ids += [x for row, m in zip(g2, nm2) for x in row[:m + 1]] + list(nm2)
         st.commit_multi(keep)
-        return ids, np.zeros(1, np.float32), [_slot_state(st, d, s, p + k) for s, p, k in zip(slots, VERIFY_POS, keep)]
+        return ids, np.zeros(1, np.float32), [slot_state(Gqa, st, d, s, p + k) for s, p, k in zip(slots, VERIFY_POS, keep)]
 
-    off, on = _off_on(st, scenario)
-    _equal(on, off, "verify + commit")
+    off, on = off_on(st, OPT, scenario)
+    equal(Gqa, on, off, "verify + commit")
 
 
 # ---- 4: generation ------------------------------------------------------------------------------------------------------------------------------------------
@@ -253,16 +186,16 @@ def test_generate_multi_across_a_tile_edge(hd, nh, fp8, lookup):
     def scenario(st):
         st.create_slots(16, KV_MAX)
         slots = SLOTS[:len(starts)]
-        _fill(st, d, seq, list(zip(slots, starts)))
+        fill_upto(st, d, seq, list(zip(slots, starts)))
         firsts = [seq[p] for p in starts]
         if lookup:
             toks = st.generate_multi_lookup(slots, firsts, starts, 8, contexts=[list(seq[:p + 1]) for p in starts])
         else:
             toks = st.generate_multi(slots, firsts, starts, 8)
-        return [x for row in toks for x in row], np.zeros(1, np.float32), [_slot_state(st, d, s, p + 8) for s, p in zip(slots, starts)]
+        return [x for row in toks for x in row], np.zeros(1, np.float32), [slot_state(Gqa, st, d, s, p + 8) for s, p in zip(slots, starts)]
 
-    off, on = _off_on(st, scenario)
-    _equal(on, off, "generate")
+    off, on = off_on(st, OPT, scenario)
+    equal(Gqa, on, off, "generate")
 
 
 # ---- 5: paged slots -----------------------------------------------------------------------------------------------------------------------------------------
@@ -294,21 +227,21 @@ def test_paged_and_forked_slots(hd, nh, fp8, page_tokens):
         ids, lg = st.step_multi([slot_of[p] for p in POS], [seq[p] for p in POS], list(POS), logits=True)
         used = [int(x) for x in st.slot_page_ids(slot_of[far])[0][:_pages(far + 1, pt)]]
         assert min(used) >= 0 and used != list(range(used[0], used[0] + len(used))), ("the long slot's pages are consecutive", used)
-        states = [_slot_state(st, d, slot_of[p], p + 1) for p in POS]
+        states = [slot_state(Gqa, st, d, slot_of[p], p + 1) for p in POS]
         for p in others:
             st.trim_slot(slot_of[p], 0)
         st.trim_slot(dst, 0)
         st.fork_slot(slot_of[far], [dst], fork_at)
         ids2, lg2 = st.step_multi([dst], [seq[fork_at]], [fork_at], logits=True)
-        states += [_slot_state(st, d, dst, fork_at + 1), _slot_state(st, d, slot_of[far], far + 1)]
+        states += [slot_state(Gqa, st, d, dst, fork_at + 1), slot_state(Gqa, st, d, slot_of[far], far + 1)]
         return list(ids) + list(ids2), np.concatenate([lg, lg2]), states
 
-    off, on = _off_on(st, scenario)
-    _equal(on, off, ("paged", pt))
+    off, on = off_on(st, OPT, scenario)
+    equal(Gqa, on, off, ("paged", pt))
     for i, p in enumerate(POS):
         assert np.array_equal(_bits(on[1][i]), single[p][0]), ("decode_step", p)
-    _same(on[2][-1], _upto(snap, far + 1))              # the fork's src: untouched
-    _same(on[2][-2], _upto(snap, fork_at + 1))          # the dst: the same sequence, one row behind the fork point
+    Gqa.same(on[2][-1], Gqa.upto(snap, far + 1))              # the fork's src: untouched
+    Gqa.same(on[2][-2], Gqa.upto(snap, fork_at + 1))          # the dst: the same sequence, one row behind the fork point
 
 
 # ---- 6: a hybrid store --------------------------------------------------------------------------------------------------------------------------------------
@@ -322,13 +255,13 @@ def test_hybrid_store(fp8):
     def scenario(st):
         st.create_slots(6, KV_MAX)
         for s, p in zip(slots, pos):
-            _fill(st, d, seq, [(s, p)])      # the recurrent state belongs to its prefix: one pass each
+            fill_upto(st, d, seq, [(s, p)])      # the recurrent state belongs to its prefix: one pass each
         ids, lg = st.step_multi(slots, [seq[p] for p in pos], pos, logits=True)
         ids2, lg2 = st.step_multi(slots, list(ids), [p + 1 for p in pos], logits=True)
-        return list(ids) + list(ids2), np.concatenate([lg, lg2]), [_slot_state(st, d, s, p + 2) for s, p in zip(slots, pos)]
+        return list(ids) + list(ids2), np.concatenate([lg, lg2]), [slot_state(Gqa, st, d, s, p + 2) for s, p in zip(slots, pos)]
 
-    off, on = _off_on(st, scenario)
-    _equal(on, off, "hybrid")
+    off, on = off_on(st, OPT, scenario)
+    equal(Gqa, on, off, "hybrid")
 
 
 # ---- 7: stale scratch ---------------------------------------------------------------------------------------------------------------------------------------
@@ -342,13 +275,13 @@ def test_short_call_after_a_long_one(hd, nh, fp8):
     def scenario(st):
         st.create_slots(16, KV_MAX)
         long_pos, short_pos = [KV_MAX - 1, 2 * SCORE_TILE], [5, 40, 31]
-        _fill(st, d, seq, list(zip([2, 4, 1, 6, 3], long_pos + short_pos)))
+        fill_upto(st, d, seq, list(zip([2, 4, 1, 6, 3], long_pos + short_pos)))
         st.step_multi([2, 4], [seq[p] for p in long_pos], long_pos)
         ids, lg = st.step_multi([1, 6, 3], [seq[p] for p in short_pos], short_pos, logits=True)
-        return ids, lg, [_slot_state(st, d, s, p + 1) for s, p in zip([1, 6, 3], short_pos)]
+        return ids, lg, [slot_state(Gqa, st, d, s, p + 1) for s, p in zip([1, 6, 3], short_pos)]
 
-    off, on = _off_on(st, scenario)
-    _equal(on, off, "short after long")
+    off, on = off_on(st, OPT, scenario)
+    equal(Gqa, on, off, "short after long")
 
 
 # ---- 8: the threshold ---------------------------------------------------------------------------------------------------------------------------------------
@@ -367,9 +300,9 @@ def test_threshold_above_and_below_the_call():
     st.set_option(MIN, 1)
     one = _steps(st, d, seq, pos)
     st.set_option(OPT, 0)
-    _equal(above, off, "above")
-    _equal(at, off, "at")
-    _equal(one, off, "1")
+    equal(Gqa, above, off, "above")
+    equal(Gqa, at, off, "at")
+    equal(Gqa, one, off, "1")
 
 
 def test_minimum_below_one_is_a_value_error():
@@ -391,19 +324,19 @@ def _refused_then_fine(st, d, arm, refuse, clear):
     """a slot holding a prefix (filled with nothing set); after arm() every batched call is refused by refuse(call); after clear() the slot's state is what it was
     and the run succeeds"""
     st.create_slots(2, 20)
-    _fill(st, d, [3, 1, 4], [(1, 3)])
-    before = _slot_state(st, d, 1, 3)
+    fill_upto(st, d, [3, 1, 4], [(1, 3)])
+    before = slot_state(Gqa, st, d, 1, 3)
     arm()
     for call in _calls(st, d["V"]):
         refuse(call)
     clear()
-    _same(_slot_state(st, d, 1, 3), before)
+    Gqa.same(slot_state(Gqa, st, d, 1, 3), before)
     st.extend_multi([1], [[1, 2, 3]], [3])
 
 
 def test_store_without_gqa_layers_is_refused():
     st, _, d = _model(64, 4, False, kv_max=32, kinds=("la", "la"))
-    _refused_then_fine(st, d, lambda: st.set_option(OPT, 1), lambda call: _state_error(call, OPT, "has none"), lambda: st.set_option(OPT, 0))
+    _refused_then_fine(st, d, lambda: st.set_option(OPT, 1), lambda call: state_error(call, OPT, "has none"), lambda: st.set_option(OPT, 0))
 
 
 def test_mode_bits_stay_refused_with_their_old_text():
@@ -412,7 +345,7 @@ def test_mode_bits_stay_refused_with_their_old_text():
     def arm():
         st.set_option(OPT, 1); st.set_attention_mode(True)
 
-    _refused_then_fine(st, d, arm, lambda call: _state_error(call, "exact-mode only"), lambda: st.set_attention_mode(False))      # the option itself stays set
+    _refused_then_fine(st, d, arm, lambda call: state_error(call, "exact-mode only"), lambda: st.set_attention_mode(False))      # the option itself stays set
     st.set_option(OPT, 0)
 
 
@@ -429,6 +362,6 @@ def test_long_slots_under_multi_attn_fast(paged):
     fast = "multi_attn_fast_paged" if paged else "multi_attn_fast"
     scenario = lambda st: _steps(st, d, seq, pos, n_slots=16, kv_max=LONG_KV, **kw)
     exact = scenario(st)
-    fd, both = _off_on(st, scenario, **{fast: 1})
-    _equal(both, fd, fast)
+    fd, both = off_on(st, OPT, scenario, **{fast: 1})
+    equal(Gqa, both, fd, fast)
     assert any(not np.array_equal(_bits(fd[1][r]), _bits(exact[1][r])) for r in range(len(pos)))      # the flash-decode did run

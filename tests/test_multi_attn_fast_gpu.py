@@ -10,8 +10,8 @@ import functools
 import numpy as np
 import pytest
 
+from tests.slots import Gqa, Mla, toks as _toks
 from tests.test_decode_gpu import build
-from tests.test_speculative_gpu import _same, _snap
 
 pytestmark = pytest.mark.gpu
 F = np.float32
@@ -22,10 +22,6 @@ MODELS = [(256, 16, False), (128, 8, True), (64, 4, False)]
 # one position | a full 64-position tile and the position after it | a full 128-position chunk and a chunk of one position | several chunks, ragged tail
 LENS = (0, 63, 64, 127, 128, 700, 1150)
 N_STEPS = 3
-
-
-def _prompt(rng, d, n):
-    return [int(x) for x in rng.integers(0, d["V"], n)]
 
 
 def _start(st, d, prompt):
@@ -46,7 +42,7 @@ def _fast_reference(st, d, prompt, first, n_steps):
             st.decode_step(tok, pos)
             out.append((st.read_logits().view(U).copy(), st.last_token()))
             tok = out[-1][1]; pos += 1
-        snap = _snap(st, d, pos)
+        snap = Gqa.snap(st, d, pos)
     finally:
         st.set_attention_mode(False)
     return out, snap
@@ -66,7 +62,7 @@ def _model(hd, nh, fp8):
     if fp8:
         st.set_kv_dtype(True); d["fp8"] = True
     rng = np.random.default_rng(hd + nh)
-    prompts = [_prompt(rng, d, n) for n in LENS]
+    prompts = [_toks(rng, d, n) for n in LENS]
     firsts = [int(x) for x in rng.integers(0, d["V"], len(prompts))]
     refs = [_fast_reference(st, d, p, f, N_STEPS) for p, f in zip(prompts, firsts)]
     return st, (eng, orc, keep), d, prompts, firsts, refs
@@ -108,7 +104,7 @@ def test_row_equals_single_sequence_fast_step(hd, nh, fp8, slot_seq, option_off_
     for i, (_, snap) in enumerate(refs):
         st.reset_decode_state(d["kv_max"])
         st.load_slot(slots[i], pos[i])
-        _same(_snap(st, d, pos[i]), snap)
+        Gqa.same(Gqa.snap(st, d, pos[i]), snap)
 
 
 def test_batch_composition(option_off_afterwards):
@@ -191,9 +187,9 @@ def test_short_slots_keep_the_exact_step(option_off_afterwards):
         assert ids0 == ids1 and np.array_equal(lg0, lg1)
     st.set_option("multi_attn_fast", 0)
     for j, i in enumerate(short):
-        st.reset_decode_state(d["kv_max"]); st.load_slot(j, LENS[i] + N_STEPS); a = _snap(st, d, LENS[i] + N_STEPS)
+        st.reset_decode_state(d["kv_max"]); st.load_slot(j, LENS[i] + N_STEPS); a = Gqa.snap(st, d, LENS[i] + N_STEPS)
         st.reset_decode_state(d["kv_max"]); st.load_slot(n + j, LENS[i] + N_STEPS)
-        _same(_snap(st, d, LENS[i] + N_STEPS), a)
+        Gqa.same(Gqa.snap(st, d, LENS[i] + N_STEPS), a)
 
 
 @pytest.mark.parametrize("sampled", [False, True])
@@ -211,7 +207,7 @@ def test_generate_multi_equals_generate_batch_in_fast_mode(sampled, option_off_a
         try:
             T, K, TP, PEN = params[i]
             out = st.generate_batch(first[i], len(P[i]), max_tokens, T, K, TP, stop_ids, PEN, rng_seed=seeds[i])
-            return out, _snap(st, d, len(P[i]) + len(out))
+            return out, Gqa.snap(st, d, len(P[i]) + len(out))
         finally:
             st.set_attention_mode(False)
 
@@ -232,7 +228,7 @@ def test_generate_multi_equals_generate_batch_in_fast_mode(sampled, option_off_a
         end = len(P[i]) + len(out[i])
         st.reset_decode_state(d["kv_max"])
         st.load_slot(slots[i], end)
-        _same(_snap(st, d, end), ref[i][1])
+        Gqa.same(Gqa.snap(st, d, end), ref[i][1])
 
 
 def test_mla_stores_are_refused_under_the_option():
@@ -241,11 +237,11 @@ def test_mla_stores_are_refused_under_the_option():
     import tests.test_multi_mla_gpu as MM
     st, eng, keep, d = MM._build(kv_max=48)
     rng = np.random.default_rng(3)
-    prompt = MM._prompt(rng, d, 20)
-    ref, _ = MM._reference(st, d, prompt, 2, 1)
+    prompt = _toks(rng, d, 20)
+    ref, _ = Mla.reference(st, d, prompt, 2, 1)
     st.create_slots(2, 40)
     MM._fill_slots(st, d, [prompt], [[1]])
-    want_slot = MM._snap(st, d, 20)
+    want_slot = Mla.snap(st, d, 20)
     st.decode_step(5, 20)                                                   # the store's own logits / last token: must survive the refusals
     want_lg, want_tok = st.read_logits().view(U).copy(), st.last_token()
     st.set_option("multi_attn_fast", 1)
@@ -256,7 +252,7 @@ def test_mla_stores_are_refused_under_the_option():
         assert np.array_equal(st.read_logits().view(U), want_lg) and st.last_token() == want_tok
     st.set_option("multi_attn_fast", 0)
     st.reset_decode_state(d["kv_max"]); st.load_slot(1, 20)
-    MM._same(MM._snap(st, d, 20), want_slot)
+    Mla.same(Mla.snap(st, d, 20), want_slot)
     ids, lg = st.step_multi([1], [2], [20], logits=True)
     assert np.array_equal(lg[0].view(U), ref[0][0]) and ids[0] == ref[0][1]
 
@@ -269,7 +265,7 @@ def test_mode_bits_stay_refused_and_the_option_is_isolated(option_off_afterwards
     exact_lg, exact_tok = st.read_logits().view(U).copy(), st.last_token()
     st.create_slots(2, 1200)
     _fill_slots(st, d, [prompts[i]], [[0, 1]])
-    want = _snap(st, d, 700)
+    want = Gqa.snap(st, d, 700)
     st.decode_step(9, 700)
     want_lg, want_tok = st.read_logits().view(U).copy(), st.last_token()
     st.set_option("multi_attn_fast", 1)
@@ -282,7 +278,7 @@ def test_mode_bits_stay_refused_and_the_option_is_isolated(option_off_afterwards
         st.set_attention_mode(False)
     for s in (0, 1):
         st.reset_decode_state(d["kv_max"]); st.load_slot(s, 700)
-        _same(_snap(st, d, 700), want)
+        Gqa.same(Gqa.snap(st, d, 700), want)
     # the option touches the batched steps only: the store's own exact step and prompt pass keep their bits with it set
     _start(st, d, prompts[i])
     st.decode_step(firsts[i], 700)

@@ -14,9 +14,8 @@ import pytest
 
 from tests import test_multi_attn_fast_gpu as FL
 from tests import test_multi_paged_scale_gpu as SC
-from tests.test_multi_attn_fast_gpu import KV_MAX, LENS, MODELS, N_STEPS, _fast_reference, _fill_slots, _get, _start
-from tests.test_multi_paged_gpu import Gqa, _slot_state, _state_error, _toks
-from tests.test_speculative_gpu import _same, _snap
+from tests.slots import Gqa, Mla, bits as _bits, options_reset, pages as _pages, slot_state, state_error, toks as _toks
+from tests.test_multi_attn_fast_gpu import LENS, MODELS, N_STEPS, _fast_reference, _fill_slots, _get
 
 pytestmark = pytest.mark.gpu
 F = np.float32
@@ -28,19 +27,7 @@ LONG = LENS.index(1150)
 _stores = []                                     # stores this file built itself (the flat suite's are reached through FL._built)
 
 
-@pytest.fixture(autouse=True)
-def options_off_afterwards():
-    yield
-    for st in [FL._model(*key)[0] for key in MODELS if key in FL._built] + _stores:
-        st.set_option(OPT, 0); st.set_option("multi_attn_fast", 0); st.set_attention_mode(False)
-
-
-def _pages(n, pt):
-    return (n + pt - 1) // pt
-
-
-def _bits(lg):
-    return lg.view(U).copy()
+options_off_afterwards = options_reset(lambda: [FL._model(*key)[0] for key in MODELS if key in FL._built] + _stores, (OPT, "multi_attn_fast"))
 
 
 # ---- 1: rows equal the single-sequence fast step ------------------------------------------------------------------------------------------------------------
@@ -70,7 +57,7 @@ def test_row_equals_single_sequence_fast_step(hd, nh, fp8, page_tokens):
         toks = [ref[k][1] for ref, _ in refs]; pos = [p + 1 for p in pos]
     st.set_option(OPT, 0)
     for i, (_, snap) in enumerate(refs):
-        _same(_slot_state(Gqa, st, d, slots[i], pos[i]), snap)
+        Gqa.same(slot_state(Gqa, st, d, slots[i], pos[i]), snap)
 
 
 # ---- 2: the rest of a page does not leak in -----------------------------------------------------------------------------------------------------------------
@@ -113,7 +100,7 @@ def _entry_points(st, d, paged, prompts, firsts, refs, runs, page_tokens=32):
     _fill_slots(st, d, [P, prompts[LENS.index(700)], P[:100], P[:1000]], [[A], [B], [C], [D]])
     st.set_option(OPT if paged else "multi_attn_fast", 1)
     out = []
-    state = lambda s, n: _slot_state(Gqa, st, d, s, n)
+    state = lambda s, n: slot_state(Gqa, st, d, s, n)
     # runs of 70 tokens from position 100 (over the chunk edge at 128 and into three more pages), of one token, and of 130 tokens
     ids, lg = st.extend_multi([C, B, D], [P[100:170], [firsts[LENS.index(700)]], P[1000:1130]], [100, 700, 1000], logits=True)
     out.append(("extend", list(ids), _bits(lg)))
@@ -171,7 +158,7 @@ def test_every_entry_point_equals_the_flat_run(hd, nh, fp8):
         _equal(g[1:], f[1:], g[0])
     assert got[1][2][0] == 2 and got[1][1][0] == [refs[LONG][0][k][1] for k in range(3)]      # the verify of the long row against the single-sequence fast reference
     for a, b in zip(states, flat_states):
-        _same(a, b)
+        Gqa.same(a, b)
 
 
 # ---- 4: forked slots ----------------------------------------------------------------------------------------------------------------------------------------
@@ -200,7 +187,7 @@ def _fork_run(st, d, paged, pt, prompts, firsts, toks, new):
     ids, lg = st.step_multi([SRC] + DSTS, [firsts[LONG], toks[2], toks[3]], [1150, REWIND + len(new), FORK + 1], logits=True)
     out.append((list(ids), _bits(lg)))
     st.set_option(OPT, 0); st.set_option("multi_attn_fast", 0)
-    return out, [_slot_state(Gqa, st, d, s, n) for s, n in ((SRC, 1151), (DSTS[0], REWIND + len(new) + 1), (DSTS[1], FORK + 2))]
+    return out, [slot_state(Gqa, st, d, s, n) for s, n in ((SRC, 1151), (DSTS[0], REWIND + len(new) + 1), (DSTS[1], FORK + 2))]
 
 
 @pytest.mark.parametrize("page_tokens", [32, 64])
@@ -216,7 +203,7 @@ def test_forked_slots(page_tokens):
     for (ids, lg), (fids, flg) in zip(got, flat):
         assert ids == fids and np.array_equal(lg, flg)
     for a, b in zip(states, flat_states):
-        _same(a, b)
+        Gqa.same(a, b)
     assert np.array_equal(got[2][1][0], refs[LONG][0][0][0]) and got[2][0][0] == refs[LONG][0][0][1]
 
 
@@ -271,7 +258,7 @@ def test_short_paged_slots_keep_the_exact_step():
         assert ids0 == ids1 and np.array_equal(lg0, lg1)
     st.set_option(OPT, 0)
     for j, i in enumerate(short):
-        _same(_slot_state(Gqa, st, d, j, LENS[i] + N_STEPS), _slot_state(Gqa, st, d, n + j, LENS[i] + N_STEPS))
+        Gqa.same(slot_state(Gqa, st, d, j, LENS[i] + N_STEPS), slot_state(Gqa, st, d, n + j, LENS[i] + N_STEPS))
 
 
 # ---- 7: the stated tolerance against the exact paged step ---------------------------------------------------------------------------------------------------
@@ -324,7 +311,7 @@ def _long_model(hd, nh, fp8):
             for k in range(2):
                 st.decode_step(tok, n + k)
                 out.append((_bits(st.read_logits()), st.last_token())); tok = out[-1][1]
-            refs.append((out, _snap(st, d, n + 2)))
+            refs.append((out, Gqa.snap(st, d, n + 2)))
         finally:
             st.set_attention_mode(False)
     return st, keep, d, states, firsts, refs
@@ -356,7 +343,7 @@ def test_long_rows(hd, nh, fp8, page_tokens):
         toks = got; pos = [p + 1 for p in pos]
     st.set_option(OPT, 0)
     for i, (_, snap) in enumerate(refs):
-        _same(_slot_state(Gqa, st, d, slots[i], pos[i]), snap)
+        Gqa.same(slot_state(Gqa, st, d, slots[i], pos[i]), snap)
 
 
 # ---- 9: chunks of 256 positions -----------------------------------------------------------------------------------------------------------------------------
@@ -384,7 +371,7 @@ def test_chunk_of_256_positions():
         toks = ids; pos = [p + 1 for p in pos]
     st.set_option(OPT, 0)
     for i, s in enumerate((2, 0)):
-        _same(_slot_state(Gqa, st, d, s, pos[i]), refs[i][1])
+        Gqa.same(slot_state(Gqa, st, d, s, pos[i]), refs[i][1])
 
 
 # ---- 10: refusals and unchanged behaviour -------------------------------------------------------------------------------------------------------------------
@@ -395,11 +382,11 @@ def test_mla_stores_are_refused_under_the_option(paged):
     st, eng, keep, d = MM._build(kv_max=48)
     _stores.append(st)
     rng = np.random.default_rng(3)
-    prompt = MM._prompt(rng, d, 20)
-    ref, _ = MM._reference(st, d, prompt, 2, 1)
+    prompt = _toks(rng, d, 20)
+    ref, _ = Mla.reference(st, d, prompt, 2, 1)
     st.create_slots(2, 40, **(dict(page_tokens=32, n_pages=4) if paged else {}))
     MM._fill_slots(st, d, [prompt], [[1]])
-    want_slot = MM._snap(st, d, 20)
+    want_slot = Mla.snap(st, d, 20)
     before = st.slot_pages()
     st.decode_step(5, 20)
     want_lg, want_tok = _bits(st.read_logits()), st.last_token()
@@ -408,12 +395,12 @@ def test_mla_stores_are_refused_under_the_option(paged):
         for call in (lambda: st.step_multi([1], [2], [20]), lambda: st.generate_multi([1], [2], [20], 2), lambda: st.step_multi_sample([1], [2], [20]),
                      lambda: st.extend_multi([0], [[1, 2]], [0]), lambda: st.verify_multi([1], [[2, 3]], [20]), lambda: st.generate_multi_lookup([1], [2], [20], 2),
                      lambda: st.generate_multi([1], [2], [20], 2, temperature=0.6, rng_seeds=3)):
-            _state_error(call, OPT)
+            state_error(call, OPT)
             assert np.array_equal(st.read_logits().view(U), want_lg) and st.last_token() == want_tok
             assert st.slot_pages() == before
     st.set_option(OPT, 0); st.set_option("multi_attn_fast", 0)
     st.reset_decode_state(d["kv_max"]); st.load_slot(1, 20)
-    MM._same(MM._snap(st, d, 20), want_slot)
+    Mla.same(Mla.snap(st, d, 20), want_slot)
     ids, lg = st.step_multi([1], [2], [20], logits=True)
     assert np.array_equal(lg[0].view(U), ref[0][0]) and ids[0] == ref[0][1]
 
@@ -427,22 +414,22 @@ def test_options_across_flat_and_paged_slots():
     pt = 32
     st.create_slots(2, SLOT_SEQ, page_tokens=pt, n_pages=2 * _pages(700, pt) + 1)      # 700 positions = 22 pages that end at position 703: position 704 needs a 23rd
     _fill_slots(st, d, [prompts[i]], [[0, 1]])
-    want = _slot_state(Gqa, st, d, 0, 700)
+    want = slot_state(Gqa, st, d, 0, 700)
     before = st.slot_pages()
     assert before["free"] == 1
     st.set_option("multi_attn_fast", 1)
     for call in (lambda: st.step_multi([1], [2], [700]), lambda: st.extend_multi([0], [[1, 2]], [700]), lambda: st.generate_multi([1], [2], [700], 4),
                  lambda: st.verify_multi([1], [[2, 3]], [700]), lambda: st.generate_multi_lookup([1], [2], [700], 4)):
-        _state_error(call, "multi_attn_fast", "paged")
+        state_error(call, "multi_attn_fast", "paged")
     assert st.slot_pages() == before
     st.set_option(OPT, 1)                                                   # both set: the new one governs
     # each slot needs its 23rd page for positions [700, 705): two pages, one is free -- refused whole
-    _state_error(lambda: st.extend_multi([0, 1], [_toks(np.random.default_rng(1), d, 5)] * 2, [700, 700]), "row 1", "slot 1")
+    state_error(lambda: st.extend_multi([0, 1], [_toks(np.random.default_rng(1), d, 5)] * 2, [700, 700]), "row 1", "slot 1")
     assert st.slot_pages() == before
-    _state_error(lambda: st.step_multi([0, 1], [3, 4], [704, 704]), "row 1", "slot 1")      # the same as a step: both rows at the first position of a 23rd page
+    state_error(lambda: st.step_multi([0, 1], [3, 4], [704, 704]), "row 1", "slot 1")      # the same as a step: both rows at the first position of a 23rd page
     assert st.slot_pages() == before
     for s in (0, 1):
-        _same(_slot_state(Gqa, st, d, s, 700), want)
+        Gqa.same(slot_state(Gqa, st, d, s, 700), want)
     ids, lg = st.step_multi([0], [firsts[i]], [700], logits=True)
     assert np.array_equal(lg[0].view(U), refs[i][0][0][0]) and ids[0] == refs[i][0][0][1]
     st.set_option("multi_attn_fast", 0)                                     # the new option alone

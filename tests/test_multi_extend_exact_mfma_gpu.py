@@ -10,9 +10,7 @@ import functools
 import numpy as np
 import pytest
 
-from tests.test_decode_gpu import build
-from tests.test_multi_paged_gpu import _state_error
-from tests.test_speculative_gpu import _same, _snap
+from tests.slots import Gqa, bits as _bits, equal, fill_prefix, off_on, options_reset, pages as _pages, slot_state, state_error, store_cache, toks as _toks
 
 pytestmark = pytest.mark.gpu
 U = np.uint32
@@ -30,35 +28,13 @@ _stores = []
 ALL_OPTS = (OPT, "multi_extend_flash", "multi_extend_la_chunk", "multi_attn_fast", "multi_attn_fast_paged")
 
 
-@pytest.fixture(autouse=True)
-def options_off_afterwards():
-    yield
-    for st in _stores:
-        for o in ALL_OPTS:
-            st.set_option(o, 0)
-        st.set_attention_mode(False)
+options_off_afterwards = options_reset(_stores, ALL_OPTS)
 
 
-def _toks(rng, d, n):
-    return [int(x) for x in rng.integers(0, d["V"], n)]
-
-
-def _bits(x):
-    return np.ascontiguousarray(x).view(U).copy()
-
-
-def _pages(n, pt):
-    return (n + pt - 1) // pt
-
-
-@functools.lru_cache(maxsize=None)
+@store_cache(_stores)
 def _model(hd, nh, fp8, kv_max=KV_MAX, kinds=("gqa", "gqa")):
     """one store per geometry, built once and shared"""
-    st, eng, orc, keep, d = build(seed=3, hd=hd, nh=nh, kv_max=kv_max, kinds=list(kinds))
-    if fp8:
-        st.set_kv_dtype(True); d["fp8"] = True
-    _stores.append(st)
-    return st, (eng, orc, keep), d
+    return Gqa.build(fp8, seed=3, hd=hd, nh=nh, kv_max=kv_max, kinds=list(kinds))
 
 
 def _exact_run(st, d, prefix, run):
@@ -67,7 +43,7 @@ def _exact_run(st, d, prefix, run):
     if prefix:
         st.prefill(prefix, 0)
     tok = st.prefill(run, len(prefix))
-    return dict(prefix=prefix, run=run, pos0=len(prefix), end=len(prefix) + len(run), lg=_bits(st.read_logits()), tok=tok, snap=_snap(st, d, len(prefix) + len(run)))
+    return dict(prefix=prefix, run=run, pos0=len(prefix), end=len(prefix) + len(run), lg=_bits(st.read_logits()), tok=tok, snap=Gqa.snap(st, d, len(prefix) + len(run)))
 
 
 @functools.lru_cache(maxsize=None)
@@ -76,44 +52,6 @@ def _refs(hd, nh, fp8):
     st, _, d = _model(hd, nh, fp8)
     rng = np.random.default_rng(hd + nh)
     return [_exact_run(st, d, _toks(rng, d, p), _toks(rng, d, c)) for p, c in CASES]
-
-
-def _fill(st, d, prefix, slots):
-    """the prefix, by the exact prompt pass on the store's own sequence, into every slot of `slots`"""
-    st.reset_decode_state(d["kv_max"])
-    if prefix:
-        st.prefill(prefix, 0)
-    for s in slots:
-        st.save_slot(s, len(prefix))
-
-
-def _slot_state(st, d, slot, upto):
-    st.reset_decode_state(d["kv_max"])
-    st.load_slot(slot, upto)
-    return _snap(st, d, upto)
-
-
-def _equal(a, b, where=""):
-    """two results (ids, logits, slot states) of one scenario: bit for bit"""
-    assert list(a[0]) == list(b[0]), ("ids", where)
-    assert np.array_equal(_bits(a[1]), _bits(b[1])), ("logits", where)
-    assert len(a[2]) == len(b[2])
-    for x, y in zip(a[2], b[2]):
-        _same(x, y)
-
-
-def _off_on(st, scenario, **other):
-    """scenario(st) -> (ids, logits, states) on slots it creates and fills itself, once with the option off and once with it on; `other` options stay set for both"""
-    out = []
-    for on in (0, 1):
-        for o, v in other.items():
-            st.set_option(o, v)
-        st.set_option(OPT, on)
-        out.append(scenario(st))
-        st.set_option(OPT, 0)
-        for o in other:
-            st.set_option(o, 0)
-    return out
 
 
 # ---- 1: on == off == the single-sequence exact prompt pass --------------------------------------------------------------------------------------------------
@@ -127,9 +65,9 @@ def test_runs_equal_option_off_and_single_sequence_prefill(hd, nh, fp8, slot_seq
     def scenario(st):
         st.create_slots(8, slot_seq)
         for ref, s in zip(refs, SLOTS):
-            _fill(st, d, ref["prefix"], [s])
+            fill_prefix(st, d, ref["prefix"], [s])
         ids, lg = st.extend_multi(SLOTS, [r["run"] for r in refs], [r["pos0"] for r in refs], logits=True)
-        return ids, lg, [_slot_state(st, d, s, r["end"]) for r, s in zip(refs, SLOTS)]
+        return ids, lg, [slot_state(Gqa, st, d, s, r["end"]) for r, s in zip(refs, SLOTS)]
 
     took = []      # not vacuous: the pass took the option's form in the on-leg and not in the off-leg (multi_path_counts)
 
@@ -139,12 +77,12 @@ def test_runs_equal_option_off_and_single_sequence_prefill(hd, nh, fp8, slot_seq
         took.append(st.multi_path_counts()["gqa_xm"])
         return out
 
-    off, on = _off_on(st, counted)
+    off, on = off_on(st, OPT, counted)
     assert took == [0, 1], ("gqa_xm", took)
-    _equal(on, off)
+    equal(Gqa, on, off)
     for i, ref in enumerate(refs):
         assert np.array_equal(_bits(on[1][i]), ref["lg"]) and on[0][i] == ref["tok"], ("single-sequence prefill", i)
-        _same(on[2][i], ref["snap"])
+        Gqa.same(on[2][i], ref["snap"])
 
 
 # ---- 2: cuts ------------------------------------------------------------------------------------------------------------------------------------------------
@@ -158,19 +96,19 @@ def test_cuts_give_the_bits_of_one_call(hd, nh, fp8):
     st.set_option(OPT, 1)
     for cuts in ([2, 40, 128], [1, 169]):
         st.create_slots(2, KV_MAX)
-        _fill(st, d, ref["prefix"], [1])
+        fill_prefix(st, d, ref["prefix"], [1])
         at = 0
         for c in cuts:
             ids, lg = st.extend_multi([1], [run[at:at + c]], [p0 + at], logits=True)
             at += c
         assert np.array_equal(_bits(lg[0]), ref["lg"]) and ids[0] == ref["tok"], cuts
-        _same(_slot_state(st, d, 1, ref["end"]), ref["snap"])
+        Gqa.same(slot_state(Gqa, st, d, 1, ref["end"]), ref["snap"])
     st.create_slots(2, KV_MAX)
-    _fill(st, d, ref["prefix"], [1])
+    fill_prefix(st, d, ref["prefix"], [1])
     tok = st.prefill_slot(1, run, p0, chunk=64)
     st.set_option(OPT, 0)
     assert tok == ref["tok"]
-    _same(_slot_state(st, d, 1, ref["end"]), ref["snap"])
+    Gqa.same(slot_state(Gqa, st, d, 1, ref["end"]), ref["snap"])
 
 
 # ---- 3: mixed passes ----------------------------------------------------------------------------------------------------------------------------------------
@@ -179,9 +117,9 @@ def _mixed(st, d, refs, rows, slot_seq=KV_MAX, **slots_kw):
     st.create_slots(8, slot_seq, **slots_kw)
     slots = list(range(1, 1 + len(rows)))
     for (kind, i), s in zip(rows, slots):
-        _fill(st, d, refs[i]["prefix"], [s])
+        fill_prefix(st, d, refs[i]["prefix"], [s])
     ids, lg = st.extend_multi(slots, [refs[i]["run"][:1] if k == "u" else refs[i]["run"] for k, i in rows], [refs[i]["pos0"] for _, i in rows], logits=True)
-    return ids, lg, [_slot_state(st, d, s, refs[i]["pos0"] + (1 if k == "u" else len(refs[i]["run"]))) for (k, i), s in zip(rows, slots)]
+    return ids, lg, [slot_state(Gqa, st, d, s, refs[i]["pos0"] + (1 if k == "u" else len(refs[i]["run"]))) for (k, i), s in zip(rows, slots)]
 
 
 @pytest.mark.parametrize("hd,nh,fp8", MODELS)
@@ -191,19 +129,19 @@ def test_mixed_passes(hd, nh, fp8):
     st, _, d = _model(hd, nh, fp8)
     refs = _refs(hd, nh, fp8)
     for rows in ([("u", 5), ("r", 1), ("u", 0), ("u", 1), ("r", 3)], [("r", 2), ("r", 0), ("r", 4)]):
-        off, on = _off_on(st, lambda st: _mixed(st, d, refs, rows))
-        _equal(on, off, rows)
+        off, on = off_on(st, OPT, lambda st: _mixed(st, d, refs, rows))
+        equal(Gqa, on, off, rows)
 
     def steps(st):
         st.create_slots(8, KV_MAX)
         pick, slots = [1, 3, 5], [3, 0, 5]
         for i, s in zip(pick, slots):
-            _fill(st, d, refs[i]["prefix"], [s])
+            fill_prefix(st, d, refs[i]["prefix"], [s])
         ids, lg = st.step_multi(slots, [refs[i]["run"][0] for i in pick], [refs[i]["pos0"] for i in pick], logits=True)
-        return ids, lg, [_slot_state(st, d, s, refs[i]["pos0"] + 1) for i, s in zip(pick, slots)]
+        return ids, lg, [slot_state(Gqa, st, d, s, refs[i]["pos0"] + 1) for i, s in zip(pick, slots)]
 
-    off, on = _off_on(st, steps)
-    _equal(on, off, "step_multi")
+    off, on = off_on(st, OPT, steps)
+    equal(Gqa, on, off, "step_multi")
 
 
 def test_verify_and_commit_are_untouched():
@@ -214,16 +152,16 @@ def test_verify_and_commit_are_untouched():
         st.create_slots(8, KV_MAX)
         pick, slots = [1, 2, 3], [3, 0, 5]
         for i, s in zip(pick, slots):
-            _fill(st, d, refs[i]["prefix"], [s])
+            fill_prefix(st, d, refs[i]["prefix"], [s])
         pos = [refs[i]["pos0"] for i in pick]
         drafts = [refs[i]["run"][:3] for i in pick]
         greedy, nm = st.verify_multi(slots, drafts, pos)
         keep = [min(m + 1, 2) for m in nm]
         st.commit_multi(keep)
-        return [g for row in greedy for g in row] + list(nm), np.zeros(1, np.float32), [_slot_state(st, d, s, p + k) for s, p, k in zip(slots, pos, keep)]
+        return [g for row in greedy for g in row] + list(nm), np.zeros(1, np.float32), [slot_state(Gqa, st, d, s, p + k) for s, p, k in zip(slots, pos, keep)]
 
-    off, on = _off_on(st, scenario)
-    _equal(on, off, "verify + commit")
+    off, on = off_on(st, OPT, scenario)
+    equal(Gqa, on, off, "verify + commit")
 
 
 # ---- 4: paged slots -----------------------------------------------------------------------------------------------------------------------------------------
@@ -243,28 +181,28 @@ def test_paged_and_forked_slots(hd, nh, fp8, page_tokens):
         need = sum(_pages(r["end"], pt) for r in refs) + 2 * _pages(ref["end"], pt)
         st.create_slots(8, KV_MAX, page_tokens=pt, n_pages=need + 2)
         for r, s in list(zip(refs, SLOTS))[:LONGEST]:
-            _fill(st, d, r["prefix"], [s])
+            fill_prefix(st, d, r["prefix"], [s])
         st.reset_decode_state(d["kv_max"]); st.save_slot(spare, min(100, pt))
-        _fill(st, d, ref["prefix"], [SLOTS[LONGEST]])
+        fill_prefix(st, d, ref["prefix"], [SLOTS[LONGEST]])
         st.reset_decode_state(d["kv_max"]); st.save_slot(dst, 1)
         st.trim_slot(spare, 0)
         ids, lg = st.extend_multi(SLOTS, [r["run"] for r in refs], [r["pos0"] for r in refs], logits=True)
         used = [int(x) for x in st.slot_page_ids(SLOTS[LONGEST])[0][:_pages(ref["end"], pt)]]
         assert min(used) >= 0 and used != list(range(used[0], used[0] + len(used))), ("the longest run's pages are consecutive", used)
-        states = [_slot_state(st, d, s, r["end"]) for r, s in zip(refs, SLOTS)]
+        states = [slot_state(Gqa, st, d, s, r["end"]) for r, s in zip(refs, SLOTS)]
         for s in SLOTS[:LONGEST]:
             st.trim_slot(s, 0)
         st.trim_slot(dst, 0)
         st.trim_slot(SLOTS[LONGEST], ref["pos0"])
         st.fork_slot(SLOTS[LONGEST], [dst], ref["pos0"])
         ids2, lg2 = st.extend_multi([dst], [ref["run"]], [ref["pos0"]], logits=True)
-        states += [_slot_state(st, d, dst, ref["end"]), _slot_state(st, d, SLOTS[LONGEST], ref["pos0"])]
+        states += [slot_state(Gqa, st, d, dst, ref["end"]), slot_state(Gqa, st, d, SLOTS[LONGEST], ref["pos0"])]
         return list(ids) + list(ids2), np.concatenate([lg, lg2]), states
 
-    off, on = _off_on(st, scenario)
-    _equal(on, off, ("paged", pt))
-    _same(on[2][-1], [(k, li, a[:ref["pos0"]], b[:ref["pos0"]]) for k, li, a, b in ref["snap"]])      # the fork's src: untouched
-    _same(on[2][-2], ref["snap"])
+    off, on = off_on(st, OPT, scenario)
+    equal(Gqa, on, off, ("paged", pt))
+    Gqa.same(on[2][-1], [(k, li, a[:ref["pos0"]], b[:ref["pos0"]]) for k, li, a, b in ref["snap"]])      # the fork's src: untouched
+    Gqa.same(on[2][-2], ref["snap"])
 
 
 # ---- 5: a hybrid store --------------------------------------------------------------------------------------------------------------------------------------
@@ -280,15 +218,15 @@ def test_hybrid_store_and_the_chunked_delta_rule(fp8):
         st.create_slots(4, KV_MAX)
         slots = [2, 0, 3]
         for p, s in zip(prefixes, slots):
-            _fill(st, d, p, [s])
+            fill_prefix(st, d, p, [s])
         ids, lg = st.extend_multi(slots, runs, [len(p) for p in prefixes], logits=True)
         ids2, lg2 = st.step_multi(slots, list(ids), [len(p) + len(r) for p, r in zip(prefixes, runs)], logits=True)
-        return list(ids) + list(ids2), np.concatenate([lg, lg2]), [_slot_state(st, d, s, len(p) + len(r) + 1) for s, p, r in zip(slots, prefixes, runs)]
+        return list(ids) + list(ids2), np.concatenate([lg, lg2]), [slot_state(Gqa, st, d, s, len(p) + len(r) + 1) for s, p, r in zip(slots, prefixes, runs)]
 
-    off, on = _off_on(st, scenario)
-    _equal(on, off, "hybrid")
-    lc, both = _off_on(st, scenario, multi_extend_la_chunk=1)
-    _equal(both, lc, "hybrid + multi_extend_la_chunk")
+    off, on = off_on(st, OPT, scenario)
+    equal(Gqa, on, off, "hybrid")
+    lc, both = off_on(st, OPT, scenario, multi_extend_la_chunk=1)
+    equal(Gqa, both, lc, "hybrid + multi_extend_la_chunk")
 
 
 # ---- 6: long slots, flash-decode unit rows ------------------------------------------------------------------------------------------------------------------
@@ -311,16 +249,16 @@ def test_long_slots_with_flash_decode_unit_rows(paged):
     def scenario(st):
         st.create_slots(5, LONG_KV, **kw)
         for p, s in zip(prefixes, slots):
-            _fill(st, d, p, [s])
+            fill_prefix(st, d, p, [s])
         ids, lg = st.extend_multi(slots, runs, [p for p, _ in cases], logits=True)
-        return ids, lg, [_slot_state(st, d, s, p + c) for s, (p, c) in zip(slots, cases)]
+        return ids, lg, [slot_state(Gqa, st, d, s, p + c) for s, (p, c) in zip(slots, cases)]
 
     exact = scenario(st)                                                    # every option off
-    fd, both = _off_on(st, scenario, **{fast: 1})
+    fd, both = off_on(st, OPT, scenario, **{fast: 1})
     for r, (p, c) in enumerate(cases):
         want = fd if c == 1 else exact
         assert both[0][r] == want[0][r] and np.array_equal(_bits(both[1][r]), _bits(want[1][r])), ("row", r, "unit" if c == 1 else "run")
-        _same(both[2][r], want[2][r])
+        Gqa.same(both[2][r], want[2][r])
     assert any(not np.array_equal(_bits(fd[1][r]), _bits(exact[1][r])) for r, (_, c) in enumerate(cases) if c == 1)      # the flash-decode did run on the unit rows
 
 
@@ -335,13 +273,13 @@ def test_short_call_after_a_long_one(hd, nh, fp8):
     def scenario(st):
         st.create_slots(8, KV_MAX)
         for i, s in zip([5, 3, 1, 0], [2, 4, 1, 6]):
-            _fill(st, d, refs[i]["prefix"], [s])
+            fill_prefix(st, d, refs[i]["prefix"], [s])
         st.extend_multi([2, 4], [refs[5]["run"], refs[3]["run"]], [refs[5]["pos0"], refs[3]["pos0"]])
         ids, lg = st.extend_multi([1, 6], [refs[1]["run"][:7], refs[0]["run"]], [refs[1]["pos0"], refs[0]["pos0"]], logits=True)
-        return ids, lg, [_slot_state(st, d, 1, refs[1]["pos0"] + 7), _slot_state(st, d, 6, refs[0]["end"])]
+        return ids, lg, [slot_state(Gqa, st, d, 1, refs[1]["pos0"] + 7), slot_state(Gqa, st, d, 6, refs[0]["end"])]
 
-    off, on = _off_on(st, scenario)
-    _equal(on, off, "short after long")
+    off, on = off_on(st, OPT, scenario)
+    equal(Gqa, on, off, "short after long")
 
 
 # ---- 8: refusals --------------------------------------------------------------------------------------------------------------------------------------------
@@ -355,13 +293,13 @@ def _refused_then_fine(st, d, arm, refuse, clear):
     """a slot holding a prefix (filled with nothing set); after arm() every batched call is refused by refuse(call); after clear() the slot's state is what it was
     and the run succeeds"""
     st.create_slots(2, 20)
-    _fill(st, d, [3, 1, 4], [1])
-    before = _slot_state(st, d, 1, 3)
+    fill_prefix(st, d, [3, 1, 4], [1])
+    before = slot_state(Gqa, st, d, 1, 3)
     arm()
     for call in _calls(st, d["V"]):
         refuse(call)
     clear()
-    _same(_slot_state(st, d, 1, 3), before)
+    Gqa.same(slot_state(Gqa, st, d, 1, 3), before)
     st.extend_multi([1], [[1, 2, 3]], [3])
 
 
@@ -371,13 +309,13 @@ def test_both_run_options_are_refused():
     def arm():
         st.set_option(OPT, 1); st.set_option("multi_extend_flash", 1)
 
-    _refused_then_fine(st, d, arm, lambda call: _state_error(call, OPT, "multi_extend_flash"), lambda: st.set_option("multi_extend_flash", 0))      # the option itself stays set
+    _refused_then_fine(st, d, arm, lambda call: state_error(call, OPT, "multi_extend_flash"), lambda: st.set_option("multi_extend_flash", 0))      # the option itself stays set
     st.set_option(OPT, 0)
 
 
 def test_store_without_gqa_layers_is_refused():
     st, _, d = _model(64, 4, False, kv_max=32, kinds=("la", "la"))
-    _refused_then_fine(st, d, lambda: st.set_option(OPT, 1), lambda call: _state_error(call, OPT, "has none"), lambda: st.set_option(OPT, 0))
+    _refused_then_fine(st, d, lambda: st.set_option(OPT, 1), lambda call: state_error(call, OPT, "has none"), lambda: st.set_option(OPT, 0))
 
 
 def test_group_of_three_heads_is_refused_not_run_by_the_per_row_kernel():
@@ -402,5 +340,5 @@ def test_mode_bits_stay_refused_with_their_old_text():
     def arm():
         st.set_option(OPT, 1); st.set_attention_mode(True)
 
-    _refused_then_fine(st, d, arm, lambda call: _state_error(call, "exact-mode only"), lambda: st.set_attention_mode(False))      # the option itself stays set
+    _refused_then_fine(st, d, arm, lambda call: state_error(call, "exact-mode only"), lambda: st.set_attention_mode(False))      # the option itself stays set
     st.set_option(OPT, 0)

@@ -12,9 +12,7 @@ import functools
 import numpy as np
 import pytest
 
-from tests.test_decode_gpu import build
-from tests.test_multi_paged_gpu import _state_error
-from tests.test_speculative_gpu import _same, _snap
+from tests.slots import Gqa, bits as _bits, fill_prefix, options_reset, pages as _pages, slot_state, state_error, store_cache, toks as _toks
 
 pytestmark = pytest.mark.gpu
 F = np.float32
@@ -32,33 +30,13 @@ LONGEST = 5                                                                 # th
 _stores = []
 
 
-@pytest.fixture(autouse=True)
-def options_off_afterwards():
-    yield
-    for st in _stores:
-        st.set_option(OPT, 0); st.set_option("multi_attn_fast", 0); st.set_option("multi_attn_fast_paged", 0); st.set_attention_mode(False)
+options_off_afterwards = options_reset(_stores, (OPT, "multi_attn_fast", "multi_attn_fast_paged"))
 
 
-def _toks(rng, d, n):
-    return [int(x) for x in rng.integers(0, d["V"], n)]
-
-
-def _bits(x):
-    return np.ascontiguousarray(x).view(U).copy()
-
-
-def _pages(n, pt):
-    return (n + pt - 1) // pt
-
-
-@functools.lru_cache(maxsize=None)
+@store_cache(_stores)
 def _model(hd, nh, fp8, kv_max=KV_MAX, kinds=("gqa", "gqa")):
     """one store per geometry, built once and shared"""
-    st, eng, orc, keep, d = build(seed=3, hd=hd, nh=nh, kv_max=kv_max, kinds=list(kinds))
-    if fp8:
-        st.set_kv_dtype(True); d["fp8"] = True
-    _stores.append(st)
-    return st, (eng, orc, keep), d
+    return Gqa.build(fp8, seed=3, hd=hd, nh=nh, kv_max=kv_max, kinds=list(kinds))
 
 
 def _fast_run(st, d, prefix, run):
@@ -69,7 +47,7 @@ def _fast_run(st, d, prefix, run):
         st.prefill(prefix, 0)
     st.set_attention_mode(True)
     tok = st.prefill(run, len(prefix))
-    ref = dict(prefix=prefix, run=run, pos0=len(prefix), end=len(prefix) + len(run), lg=_bits(st.read_logits()), tok=tok, snap=_snap(st, d, len(prefix) + len(run)))
+    ref = dict(prefix=prefix, run=run, pos0=len(prefix), end=len(prefix) + len(run), lg=_bits(st.read_logits()), tok=tok, snap=Gqa.snap(st, d, len(prefix) + len(run)))
     st.set_attention_mode(False)
     return ref
 
@@ -82,25 +60,10 @@ def _refs(hd, nh, fp8):
     return [_fast_run(st, d, _toks(rng, d, p), _toks(rng, d, c)) for p, c in CASES]
 
 
-def _fill(st, d, prefix, slots):
-    """the prefix, by the exact prompt pass on the store's own sequence, into every slot of `slots`"""
-    st.reset_decode_state(d["kv_max"])
-    if prefix:
-        st.prefill(prefix, 0)
-    for s in slots:
-        st.save_slot(s, len(prefix))
-
-
-def _slot_state(st, d, slot, upto):
-    st.reset_decode_state(d["kv_max"])
-    st.load_slot(slot, upto)
-    return _snap(st, d, upto)
-
-
 def _assert_run(st, d, ref, slot, tok, lg, where=""):
     assert np.array_equal(_bits(lg), ref["lg"]), ("logits", where, ref["pos0"], len(ref["run"]))
     assert tok == ref["tok"], ("id", where, ref["pos0"])
-    _same(_slot_state(st, d, slot, ref["end"]), ref["snap"])
+    Gqa.same(slot_state(Gqa, st, d, slot, ref["end"]), ref["snap"])
 
 
 # ---- 1: a run equals the single-sequence flash prompt pass ---------------------------------------------------------------------------------------------------
@@ -112,7 +75,7 @@ def test_run_equals_single_sequence_fast_prompt_pass(hd, nh, fp8, slot_seq):
     refs = _refs(hd, nh, fp8)
     st.create_slots(8, slot_seq)
     for ref, s in zip(refs, SLOTS):
-        _fill(st, d, ref["prefix"], [s])
+        fill_prefix(st, d, ref["prefix"], [s])
     st.set_option(OPT, 1)
     ids, lg = st.extend_multi(SLOTS, [r["run"] for r in refs], [r["pos0"] for r in refs], logits=True)
     st.set_option(OPT, 0)
@@ -128,7 +91,7 @@ def test_cuts_of_two_or_more_tokens_give_the_same_bits(hd, nh, fp8):
     st, _, d = _model(hd, nh, fp8)
     ref = _refs(hd, nh, fp8)[4]
     st.create_slots(2, KV_MAX)
-    _fill(st, d, ref["prefix"], [1])
+    fill_prefix(st, d, ref["prefix"], [1])
     st.set_option(OPT, 1)
     run, p0 = ref["run"], ref["pos0"]
     st.extend_multi([1], [run[:2]], [p0])
@@ -145,11 +108,11 @@ def _mixed(st, d, refs, units, longs, slot_seq, on, **slots_kw):
     st.create_slots(8, slot_seq, **slots_kw)
     slots = list(range(1, 1 + len(rows)))
     for (kind, i), s in zip(rows, slots):
-        _fill(st, d, refs[i]["prefix"], [s])
+        fill_prefix(st, d, refs[i]["prefix"], [s])
     st.set_option(OPT, 1 if on else 0)
     ids, lg = st.extend_multi(slots, [refs[i]["run"][:1] if k == "u" else refs[i]["run"] for k, i in rows], [refs[i]["pos0"] for _, i in rows], logits=True)
     st.set_option(OPT, 0)
-    states = [_slot_state(st, d, s, refs[i]["pos0"] + 1) for (k, i), s in zip(rows, slots) if k == "u"]
+    states = [slot_state(Gqa, st, d, s, refs[i]["pos0"] + 1) for (k, i), s in zip(rows, slots) if k == "u"]
     return rows, slots, ids, lg, states
 
 
@@ -165,7 +128,7 @@ def test_mixed_pass(hd, nh, fp8):
     for r, ((kind, i), s) in enumerate(zip(rows, slots)):
         if kind == "u":
             assert np.array_equal(_bits(lg1[r]), _bits(lg0[r])) and ids1[r] == ids0[r], ("unit row", r)
-            _same(states1[u], states0[u]); u += 1
+            Gqa.same(states1[u], states0[u]); u += 1
         else:
             _assert_run(st, d, refs[i], s, ids1[r], lg1[r], ("run", r))
 
@@ -196,7 +159,7 @@ def test_mixed_pass_over_long_slots_with_flash_decode_rows(paged):
     for r, ((kind, i), s) in enumerate(zip(rows, slots)):
         if kind == "u":
             assert np.array_equal(_bits(lg1[r]), _bits(lg0[r])) and ids1[r] == ids0[r], ("unit row", r)
-            _same(states1[u], states0[u]); u += 1
+            Gqa.same(states1[u], states0[u]); u += 1
         else:
             _assert_run(st, d, refs[i], s, ids1[r], lg1[r], ("run", r))
 
@@ -216,9 +179,9 @@ def test_paged_slots_equal_flat_slots(hd, nh, fp8, page_tokens):
     need = sum(_pages(r["end"], pt) for r in refs) + 2 * _pages(refs[LONGEST]["end"], pt)
     st.create_slots(8, KV_MAX, page_tokens=pt, n_pages=need + 2)
     for ref, s in list(zip(refs, SLOTS))[:LONGEST]:
-        _fill(st, d, ref["prefix"], [s])
+        fill_prefix(st, d, ref["prefix"], [s])
     st.reset_decode_state(d["kv_max"]); st.save_slot(spare, min(100, pt))      # a page between the short slots and the longest run's prefix ...
-    _fill(st, d, refs[LONGEST]["prefix"], [SLOTS[LONGEST]])
+    fill_prefix(st, d, refs[LONGEST]["prefix"], [SLOTS[LONGEST]])
     st.reset_decode_state(d["kv_max"]); st.save_slot(dsts[0], 1)            # ... and the page right behind that prefix stays held during the call
     st.trim_slot(spare, 0)                                                  # the page before it comes back as a hole: lowest free id first
     st.set_option(OPT, 1)
@@ -241,7 +204,7 @@ def test_paged_slots_equal_flat_slots(hd, nh, fp8, page_tokens):
     st.set_option(OPT, 0)
     for r, s in enumerate(dsts):
         _assert_run(st, d, ref, s, ids[r], lg[r], ("fork dst", s))
-    _same(_slot_state(st, d, SLOTS[LONGEST], ref["pos0"]), [(k, li, a[:ref["pos0"]], b[:ref["pos0"]]) for k, li, a, b in ref["snap"]])      # src untouched
+    Gqa.same(slot_state(Gqa, st, d, SLOTS[LONGEST], ref["pos0"]), [(k, li, a[:ref["pos0"]], b[:ref["pos0"]]) for k, li, a, b in ref["snap"]])      # src untouched
 
 
 @pytest.mark.parametrize("hd,nh,fp8", [(128, 8, True)])
@@ -251,15 +214,15 @@ def test_pool_one_page_short_fails_whole(hd, nh, fp8):
     pt, pick = 32, [3, 4]
     st.create_slots(4, KV_MAX, page_tokens=pt, n_pages=sum(_pages(refs[i]["end"], pt) for i in pick) - 1)
     for i, s in zip(pick, [2, 0]):
-        _fill(st, d, refs[i]["prefix"], [s])
+        fill_prefix(st, d, refs[i]["prefix"], [s])
     before = st.slot_pages()
-    states = [_slot_state(st, d, s, refs[i]["pos0"]) for i, s in zip(pick, [2, 0])]
+    states = [slot_state(Gqa, st, d, s, refs[i]["pos0"]) for i, s in zip(pick, [2, 0])]
     st.set_option(OPT, 1)
-    _state_error(lambda: st.extend_multi([2, 0], [refs[i]["run"] for i in pick], [refs[i]["pos0"] for i in pick]), "does not fit the page pool")
+    state_error(lambda: st.extend_multi([2, 0], [refs[i]["run"] for i in pick], [refs[i]["pos0"] for i in pick]), "does not fit the page pool")
     st.set_option(OPT, 0)
     assert st.slot_pages() == before
     for (i, s), want in zip(zip(pick, [2, 0]), states):
-        _same(_slot_state(st, d, s, refs[i]["pos0"]), want)
+        Gqa.same(slot_state(Gqa, st, d, s, refs[i]["pos0"]), want)
 
 
 # ---- 5: nothing past the end is read -------------------------------------------------------------------------------------------------------------------------
@@ -316,9 +279,9 @@ def test_full_chunk_of_1024_tokens():
     one = _fast_run(st, d, prefix, run)
     st.set_prefill_chunk(0)
     assert np.array_equal(one["lg"], ref["lg"]) and one["tok"] == ref["tok"]
-    _same(one["snap"], ref["snap"])
+    Gqa.same(one["snap"], ref["snap"])
     st.create_slots(2, 1200)
-    _fill(st, d, prefix, [1])
+    fill_prefix(st, d, prefix, [1])
     st.set_option(OPT, 1)
     ids, lg = st.extend_multi([1], [run], [100], logits=True)
     st.set_option(OPT, 0)
@@ -337,7 +300,7 @@ def test_hybrid_store_within_the_prompt_flash_bound(fp8):
     out = []
     for on in (0, 1):
         st.create_slots(2, KV_MAX)
-        _fill(st, d, prefix, [1])
+        fill_prefix(st, d, prefix, [1])
         st.set_option(OPT, on)
         ids, lg = st.extend_multi([1], [run], [37], logits=True)
         ids2, lg2 = st.step_multi([1], [ids[0]], [37 + 170], logits=True)
@@ -356,7 +319,7 @@ def _unchanged_calls(st, d, refs, on):
     pick, slots = [1, 2, 3], [3, 0, 5]
     st.create_slots(8, KV_MAX)
     for i, s in zip(pick, slots):
-        _fill(st, d, refs[i]["prefix"], [s, s + 1])
+        fill_prefix(st, d, refs[i]["prefix"], [s, s + 1])
     st.set_option(OPT, on)
     pos = [refs[i]["pos0"] for i in pick]
     firsts = [refs[i]["run"][0] for i in pick]
@@ -370,11 +333,11 @@ def _unchanged_calls(st, d, refs, on):
     keep = [min(m + 1, 2) for m in nm]
     st.commit_multi(keep)
     out["verify"] = (greedy, list(nm))
-    out["states"] = [_slot_state(st, d, s, e + k) for s, e, k in zip(slots, end, keep)]
+    out["states"] = [slot_state(Gqa, st, d, s, e + k) for s, e, k in zip(slots, end, keep)]
     twins = [s + 1 for s in slots]
     out["plain"] = st.generate_multi(twins, firsts, pos, 8)
     for i, s in zip(pick, twins):
-        _fill(st, d, refs[i]["prefix"], [s])
+        fill_prefix(st, d, refs[i]["prefix"], [s])
     out["lookup"] = st.generate_multi_lookup(twins, firsts, pos, 8, contexts=[refs[i]["prefix"] + [refs[i]["run"][0]] for i in pick])
     st.set_option(OPT, 0)
     return out
@@ -387,7 +350,7 @@ def test_unit_runs_and_verify_passes_keep_their_bits():
     assert on["step"][0] == off["step"][0] and np.array_equal(on["step"][1], off["step"][1])
     assert on["gen"] == off["gen"] and on["verify"] == off["verify"] and on["plain"] == off["plain"]
     for a, b in zip(on["states"], off["states"]):
-        _same(a, b)
+        Gqa.same(a, b)
     assert on["lookup"] == on["plain"]                                      # speculation stays exact under the option
 
 
@@ -405,7 +368,7 @@ def test_mla_store_is_refused():
     st.create_slots(2, 20)
     st.set_option(OPT, 1)
     for call in _calls(st, d["V"]):
-        _state_error(call, OPT, "MLA")
+        state_error(call, OPT, "MLA")
     st.set_option(OPT, 0)
     st.step_multi([1], [1], [0])
 
@@ -415,7 +378,7 @@ def test_store_without_gqa_layers_is_refused():
     st.create_slots(2, 20)
     st.set_option(OPT, 1)
     for call in _calls(st, d["V"]):
-        _state_error(call, OPT, "has none")
+        state_error(call, OPT, "has none")
     st.set_option(OPT, 0)
     st.step_multi([1], [1], [0])
 
@@ -433,7 +396,7 @@ def test_group_of_six_heads_is_refused_not_run_exactly():
     st.create_slots(2, 32, page_tokens=32, n_pages=2)
     st.set_option("multi_attn_fast", 1)
     for call in _calls(st, d["V"]):
-        _state_error(call, "does not read paged slots")
+        state_error(call, "does not read paged slots")
     st.set_option("multi_attn_fast", 0)
     st.set_option(OPT, 0)
     st.create_slots(2, 20)
@@ -447,18 +410,18 @@ def test_mode_bits_stay_refused_and_option_zero_is_the_exact_pass():
 
     def run():
         st.create_slots(2, KV_MAX)
-        _fill(st, d, ref["prefix"], [1])
+        fill_prefix(st, d, ref["prefix"], [1])
         ids, lg = st.extend_multi([1], [ref["run"]], [ref["pos0"]], logits=True)
-        return ids[0], _bits(lg[0]), _slot_state(st, d, 1, ref["end"])
+        return ids[0], _bits(lg[0]), slot_state(Gqa, st, d, 1, ref["end"])
 
     exact = run()
     st.set_option(OPT, 1)
     st.create_slots(2, KV_MAX)
     st.set_attention_mode(True)
     for call in _calls(st, d["V"]):
-        _state_error(call, "exact-mode only")
+        state_error(call, "exact-mode only")
     st.set_attention_mode(False)
     st.set_option(OPT, 0)
     again = run()
     assert again[0] == exact[0] and np.array_equal(again[1], exact[1])
-    _same(again[2], exact[2])
+    Gqa.same(again[2], exact[2])

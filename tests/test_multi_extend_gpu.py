@@ -7,8 +7,9 @@ import numpy as np
 import pytest
 
 from krasis_amd._lib import KR_EXTEND_MAX_TOKENS
+from tests.slots import Gqa, Mla, slot_state, toks as _toks
 from tests.test_decode_gpu import build
-from tests.test_speculative_gpu import CFGS, _same, _snap
+from tests.test_speculative_gpu import CFGS
 from tests.test_multi_seq_gpu import DV64, LA4
 from tests import test_multi_mla_gpu as mla
 
@@ -22,15 +23,11 @@ SEQS = [(0, 1), (0, 9), (7, 5), (23, 1), (2, 3)]
 SLOTS = [3, 0, 6, 2, 5]                                          # slot numbers do not follow the rows
 
 
-def _toks(rng, d, n):
-    return [int(x) for x in rng.integers(0, d["V"], n)]
-
-
 def _logits(st):
     return st.read_logits().view(U).copy()
 
 
-def _reference(st, d, prompt, run, fill=(), snap=_snap, via_prefill=False):
+def _run_reference(st, d, prompt, run, fill=(), K=Gqa, via_prefill=False):
     """decode_step alone from zero state: the prompt (saved into the slots `fill`), then the run -> logits bits and id after its last token, the
     state snapshot, and the (logits, id) of one further step on that id"""
     st.reset_decode_state(d["kv_max"])
@@ -44,29 +41,23 @@ def _reference(st, d, prompt, run, fill=(), snap=_snap, via_prefill=False):
     pos = len(prompt)
     for t in run:
         st.decode_step(t, pos); pos += 1
-    ref = dict(lg=_logits(st), tok=st.last_token(), snap=snap(st, d, pos), pos=pos)
+    ref = dict(lg=_logits(st), tok=st.last_token(), snap=K.snap(st, d, pos), pos=pos)
     st.decode_step(ref["tok"], pos)
     ref["next"] = (_logits(st), st.last_token())
     return ref
 
 
-def _slot_state(st, d, slot, pos, snap=_snap):
-    st.reset_decode_state(d["kv_max"])
-    st.load_slot(slot, pos)
-    return snap(st, d, pos)
-
-
-def _assert_rows(st, d, refs, slots, ids, lg, same=_same, snap=_snap):
+def _assert_rows(st, d, refs, slots, ids, lg, K=Gqa):
     for i, (ref, s) in enumerate(zip(refs, slots)):
         assert np.array_equal(lg[i].view(U), ref["lg"]), ("logits", i)
         assert ids[i] == ref["tok"], ("id", i)
-        same(_slot_state(st, d, s, ref["pos"], snap), ref["snap"])
+        K.same(slot_state(K, st, d, s, ref["pos"]), ref["snap"])
 
 
 def _setup(st, d, rng, seqs, slots):
     prompts = [_toks(rng, d, p) for p, _ in seqs]
     runs = [_toks(rng, d, r) for _, r in seqs]
-    refs = [_reference(st, d, p, r, [s]) for p, r, s in zip(prompts, runs, slots)]
+    refs = [_run_reference(st, d, p, r, [s]) for p, r, s in zip(prompts, runs, slots)]
     return prompts, runs, refs
 
 
@@ -103,7 +94,7 @@ def test_cut_invariance(cfg):
     st.create_slots(4, 40)
     rng = np.random.default_rng(11)
     prompt, stream = _toks(rng, d, 6), _toks(rng, d, 12)
-    ref = _reference(st, d, prompt, stream, [0, 1, 2])
+    ref = _run_reference(st, d, prompt, stream, [0, 1, 2])
     p0 = len(prompt)
     a = st.extend_multi([0], [stream], [p0], logits=True)
     st.extend_multi([1], [stream[:5]], [p0])
@@ -121,7 +112,7 @@ def test_positions_across_1024_e4m3_head_dim_256():
     rng = np.random.default_rng(256)
     prompts, runs = [_toks(rng, d, 1019), _toks(rng, d, 3)], [_toks(rng, d, 9), _toks(rng, d, 2)]
     # the prompts through the prompt pass (held to decode_step by the prompt-pass tests); the runs by decode_step
-    refs = [_reference(st, d, p, r, fill, via_prefill=True) for p, r, fill in zip(prompts, runs, ([0, 2, 4], [1, 3, 5]))]
+    refs = [_run_reference(st, d, p, r, fill, via_prefill=True) for p, r, fill in zip(prompts, runs, ([0, 2, 4], [1, 3, 5]))]
     pos = [len(p) for p in prompts]
     assert pos[0] + len(runs[0]) - 1 == 1027
     ids, lg = st.extend_multi([0, 1], runs, pos, logits=True)
@@ -140,7 +131,7 @@ def test_positions_across_1024_e4m3_head_dim_256():
         st.set_option("multi_attn_fast", 0)
     for i in (0, 1):
         end = pos[i] + len(runs[i])
-        _same(_slot_state(st, d, 2 + i, end), _slot_state(st, d, 4 + i, end))
+        Gqa.same(slot_state(Gqa, st, d, 2 + i, end), slot_state(Gqa, st, d, 4 + i, end))
 
 
 @pytest.mark.parametrize("fp8", [False, True])
@@ -152,9 +143,9 @@ def test_mla(cfg, fp8):
     seqs, slots = [(0, 1), (5, 6), (11, 17)], [2, 0, 3]
     prompts = [_toks(rng, d, p) for p, _ in seqs]
     runs = [_toks(rng, d, r) for _, r in seqs]
-    refs = [_reference(st, d, p, r, [s], snap=mla._snap) for p, r, s in zip(prompts, runs, slots)]
+    refs = [_run_reference(st, d, p, r, [s], K=Mla) for p, r, s in zip(prompts, runs, slots)]
     ids, lg = st.extend_multi(slots, runs, [len(p) for p in prompts], logits=True)
-    _assert_rows(st, d, refs, slots, ids, lg, same=mla._same, snap=mla._snap)
+    _assert_rows(st, d, refs, slots, ids, lg, K=Mla)
 
 
 def test_sampled_row_draws_once_on_the_last_token():
@@ -162,7 +153,7 @@ def test_sampled_row_draws_once_on_the_last_token():
     st.create_slots(2, 40)
     rng = np.random.default_rng(21)
     prompt, run = _toks(rng, d, 4), _toks(rng, d, 5)
-    _reference(st, d, prompt, [], [0, 1])
+    _run_reference(st, d, prompt, [], [0, 1])
     for s in (0, 1):
         st.set_slot_sampler(s, prompt[-1], 0.8, 20, 0.9, 0.5, 1234567)
     p0 = len(prompt)
@@ -185,7 +176,7 @@ def test_refusals_leave_everything_as_it_was():
     st.save_slot(1, 20)
     st.fill_state_synthetic(d["kv_max"], seed=6)
     st.save_slot(2, 10)
-    state = lambda: (_slot_state(st, d, 1, 20), _slot_state(st, d, 2, 10))
+    state = lambda: (slot_state(Gqa, st, d, 1, 20), slot_state(Gqa, st, d, 2, 10))
     want = state()
     V = d["V"]
     refused = [
@@ -200,7 +191,7 @@ def test_refusals_leave_everything_as_it_was():
             st.extend_multi(*args)
         got = state()
         for g, w in zip(got, want):
-            _same(g, w)
+            Gqa.same(g, w)
     st.set_attention_mode(fast=True)                                                        # a tolerance bit
     try:
         with pytest.raises(RuntimeError, match="exact-mode only"):
@@ -208,7 +199,7 @@ def test_refusals_leave_everything_as_it_was():
     finally:
         st.set_attention_mode(False)
     for g, w in zip(state(), want):
-        _same(g, w)
+        Gqa.same(g, w)
 
 
 def test_prefill_slot_equals_prefill_and_leaves_the_store_alone():
@@ -218,12 +209,12 @@ def test_prefill_slot_equals_prefill_and_leaves_the_store_alone():
     toks, own = _toks(rng, d, 21), _toks(rng, d, 6)
     st.reset_decode_state(d["kv_max"])
     st.prefill(toks, 0)
-    want_id, want = st.last_token(), _snap(st, d, 21)
+    want_id, want = st.last_token(), Gqa.snap(st, d, 21)
     st.reset_decode_state(d["kv_max"])
     st.prefill(own, 0)                                                     # the store's own sequence: something else
-    before = (_logits(st), st.last_token(), _snap(st, d, 48))
+    before = (_logits(st), st.last_token(), Gqa.snap(st, d, 48))
     assert st.prefill_slot(1, toks, chunk=8) == want_id
-    after = (_logits(st), st.last_token(), _snap(st, d, 48))
+    after = (_logits(st), st.last_token(), Gqa.snap(st, d, 48))
     assert np.array_equal(before[0], after[0]) and before[1] == after[1]
-    _same(after[2], before[2])
-    _same(_slot_state(st, d, 1, 21), want)
+    Gqa.same(after[2], before[2])
+    Gqa.same(slot_state(Gqa, st, d, 1, 21), want)

@@ -15,9 +15,7 @@ import functools
 import numpy as np
 import pytest
 
-from tests.test_decode_gpu import build
-from tests.test_multi_paged_gpu import _state_error
-from tests.test_speculative_gpu import _same, _snap
+from tests.slots import Gqa, bits as _bits, fill_prefix, options_reset, pages as _pages, slot_state, state_error, store_cache, toks as _toks
 
 pytestmark = pytest.mark.gpu
 U = np.uint32
@@ -35,33 +33,13 @@ SLOTS = [5, 0, 7, 2, 6]                                                     # sl
 _stores = []
 
 
-@pytest.fixture(autouse=True)
-def options_off_afterwards():
-    yield
-    for st in _stores:
-        st.set_option(OPT, 0); st.set_option(FLASH, 0); st.set_option("multi_attn_fast", 0); st.set_attention_mode(False); st.set_prefill_chunk(0)
+options_off_afterwards = options_reset(_stores, (OPT, FLASH, "multi_attn_fast"), prefill_chunk=True)
 
 
-def _toks(rng, d, n):
-    return [int(x) for x in rng.integers(0, d["V"], n)]
-
-
-def _bits(x):
-    return np.ascontiguousarray(x).view(U).copy()
-
-
-def _pages(n, pt):
-    return (n + pt - 1) // pt
-
-
-@functools.lru_cache(maxsize=None)
+@store_cache(_stores)
 def _model(kinds, la_heads=(2, 4), fp8=False, kv_max=KV_MAX, la_dkdv=(128, 128)):
     """one store per model, built once and shared"""
-    st, eng, orc, keep, d = build(seed=3, hd=64, nh=4, kv_max=kv_max, kinds=list(kinds), la_heads=la_heads, la_dkdv=la_dkdv)
-    if fp8:
-        st.set_kv_dtype(True); d["fp8"] = True
-    _stores.append(st)
-    return st, (eng, orc, keep), d
+    return Gqa.build(fp8, seed=3, hd=64, nh=4, kv_max=kv_max, kinds=list(kinds), la_heads=la_heads, la_dkdv=la_dkdv)
 
 
 def _fast_run(st, d, prefix, run):
@@ -72,7 +50,7 @@ def _fast_run(st, d, prefix, run):
         st.prefill(prefix, 0)
     st.set_attention_mode(True)
     tok = st.prefill(run, len(prefix))
-    ref = dict(prefix=prefix, run=run, pos0=len(prefix), end=len(prefix) + len(run), lg=_bits(st.read_logits()), tok=tok, snap=_snap(st, d, len(prefix) + len(run)))
+    ref = dict(prefix=prefix, run=run, pos0=len(prefix), end=len(prefix) + len(run), lg=_bits(st.read_logits()), tok=tok, snap=Gqa.snap(st, d, len(prefix) + len(run)))
     st.set_attention_mode(False)
     return ref
 
@@ -85,25 +63,10 @@ def _refs(kinds, la_heads, fp8=False):
     return [_fast_run(st, d, _toks(rng, d, p), _toks(rng, d, c)) for p, c in CASES]
 
 
-def _fill(st, d, prefix, slots):
-    """the prefix, by the exact prompt pass on the store's own sequence, into every slot of `slots`"""
-    st.reset_decode_state(d["kv_max"])
-    if prefix:
-        st.prefill(prefix, 0)
-    for s in slots:
-        st.save_slot(s, len(prefix))
-
-
-def _slot_state(st, d, slot, upto):
-    st.reset_decode_state(d["kv_max"])
-    st.load_slot(slot, upto)
-    return _snap(st, d, upto)
-
-
 def _assert_run(st, d, ref, slot, tok, lg, where=""):
     assert np.array_equal(_bits(lg), ref["lg"]), ("logits", where, ref["pos0"], len(ref["run"]))
     assert tok == ref["tok"], ("id", where, ref["pos0"])
-    _same(_slot_state(st, d, slot, ref["end"]), ref["snap"])
+    Gqa.same(slot_state(Gqa, st, d, slot, ref["end"]), ref["snap"])
 
 
 def _rel(a, b):
@@ -115,8 +78,8 @@ def _crowded_call(st, d, refs, on):
     """the five runs of CASES, two unit rows and a run of 63 tokens in one extend_multi, slots scrambled; slots 4 and 9 hold state and are not in the call"""
     st.create_slots(10, KV_MAX)
     for ref, s in zip(refs, SLOTS):
-        _fill(st, d, ref["prefix"], [s])
-    _fill(st, d, refs[1]["prefix"], [3]); _fill(st, d, refs[2]["prefix"], [8, 4]); _fill(st, d, refs[4]["prefix"], [1, 9])
+        fill_prefix(st, d, ref["prefix"], [s])
+    fill_prefix(st, d, refs[1]["prefix"], [3]); fill_prefix(st, d, refs[2]["prefix"], [8, 4]); fill_prefix(st, d, refs[4]["prefix"], [1, 9])
     slots = [3, SLOTS[0], SLOTS[1], 1, SLOTS[2], 8, SLOTS[3], SLOTS[4]]
     runs = [refs[1]["run"][:1], refs[0]["run"], refs[1]["run"], refs[4]["run"][:63], refs[2]["run"], refs[2]["run"][:1], refs[3]["run"], refs[4]["run"]]
     pos = [refs[1]["pos0"], refs[0]["pos0"], refs[1]["pos0"], refs[4]["pos0"], refs[2]["pos0"], refs[2]["pos0"], refs[3]["pos0"], refs[4]["pos0"]]
@@ -132,15 +95,15 @@ def test_runs_equal_the_fast_prompt_pass_and_short_runs_keep_their_bits(la_heads
     refs = _refs(LA, la_heads)
     short = {0: 3, 3: 1, 5: 8}                                              # call row -> slot of the unit rows and the 63-token run
     slots, runs, pos, ids0, lg0 = _crowded_call(st, d, refs, 0)
-    off = {r: _slot_state(st, d, s, pos[r] + len(runs[r])) for r, s in short.items()}
-    idle = [_slot_state(st, d, 4, refs[2]["pos0"]), _slot_state(st, d, 9, refs[4]["pos0"])]
+    off = {r: slot_state(Gqa, st, d, s, pos[r] + len(runs[r])) for r, s in short.items()}
+    idle = [slot_state(Gqa, st, d, 4, refs[2]["pos0"]), slot_state(Gqa, st, d, 9, refs[4]["pos0"])]
     slots, runs, pos, ids1, lg1 = _crowded_call(st, d, refs, 1)
     for row, case in ((1, 0), (2, 1), (4, 2), (6, 3), (7, 4)):
         _assert_run(st, d, refs[case], slots[row], ids1[row], lg1[row], ("case", case))
     for r, s in short.items():
         assert ids1[r] == ids0[r] and np.array_equal(_bits(lg1[r]), _bits(lg0[r])), ("short run", r)
-        _same(_slot_state(st, d, s, pos[r] + len(runs[r])), off[r])
-    _same(_slot_state(st, d, 4, refs[2]["pos0"]), idle[0]); _same(_slot_state(st, d, 9, refs[4]["pos0"]), idle[1])
+        Gqa.same(slot_state(Gqa, st, d, s, pos[r] + len(runs[r])), off[r])
+    Gqa.same(slot_state(Gqa, st, d, 4, refs[2]["pos0"]), idle[0]); Gqa.same(slot_state(Gqa, st, d, 9, refs[4]["pos0"]), idle[1])
 
 
 # ---- 2: hybrid store with both options: the fast prefill, flat, paged and forked -------------------------------------------------------------------------------
@@ -153,22 +116,22 @@ def test_hybrid_store_with_both_options_equals_the_fast_prefill(fp8):
     for paged in (False, True):
         kw = dict(page_tokens=32, n_pages=4 * _pages(ref["end"], 32) + 2) if paged else {}
         st.create_slots(6, KV_MAX, **kw)
-        _fill(st, d, ref["prefix"], [4, 2])
+        fill_prefix(st, d, ref["prefix"], [4, 2])
         st.set_option(OPT, 1); st.set_option(FLASH, 1)
         ids, lg = st.extend_multi([4], [ref["run"]], [ref["pos0"]], logits=True)
         _assert_run(st, d, ref, 4, ids[0], lg[0], ("paged" if paged else "flat"))
         if paged:
-            src = _slot_state(st, d, 2, ref["pos0"])
+            src = slot_state(Gqa, st, d, 2, ref["pos0"])
             st.fork_slot(2, [0, 5], ref["pos0"])
             ids, lg = st.extend_multi([5, 0], [ref["run"], ref["run"]], [ref["pos0"]] * 2, logits=True)
             for r, s in enumerate([5, 0]):
                 _assert_run(st, d, ref, s, ids[r], lg[r], ("fork dst", s))
-            _same(_slot_state(st, d, 2, ref["pos0"]), src)                  # the fork's src is untouched
+            Gqa.same(slot_state(Gqa, st, d, 2, ref["pos0"]), src)                  # the fork's src is untouched
         st.set_option(OPT, 0); st.set_option(FLASH, 0)
     # every run of 2 .. 63 tokens equals the fast prefill too: the single-sequence fast pass keeps the exact rule below 64 tokens
     short = _fast_run(st, d, ref["prefix"], ref["run"][:63])
     st.create_slots(2, KV_MAX)
-    _fill(st, d, ref["prefix"], [1])
+    fill_prefix(st, d, ref["prefix"], [1])
     st.set_option(OPT, 1); st.set_option(FLASH, 1)
     ids, lg = st.extend_multi([1], [ref["run"][:63]], [ref["pos0"]], logits=True)
     st.set_option(OPT, 0); st.set_option(FLASH, 0)
@@ -178,14 +141,14 @@ def test_hybrid_store_with_both_options_equals_the_fast_prefill(fp8):
 # ---- 3: cuts ---------------------------------------------------------------------------------------------------------------------------------------------------
 def _one_call(st, d, prefix, run, on, cuts=None):
     st.create_slots(2, KV_MAX)
-    _fill(st, d, prefix, [1])
+    fill_prefix(st, d, prefix, [1])
     st.set_option(OPT, on)
     p = len(prefix)
     for n in (cuts or [len(run)]):
         ids, lg = st.extend_multi([1], [run[p - len(prefix):p - len(prefix) + n]], [p], logits=True)
         p += n
     st.set_option(OPT, 0)
-    return ids[0], lg[0].copy(), _slot_state(st, d, 1, p)
+    return ids[0], lg[0].copy(), slot_state(Gqa, st, d, 1, p)
 
 
 @pytest.mark.parametrize("la_heads", [(2, 4), (1, 8)])
@@ -198,7 +161,7 @@ def test_cuts_at_multiples_of_64_give_the_bits_of_one_call(la_heads):
     one = _one_call(st, d, prefix, run, 1)
     two = _one_call(st, d, prefix, run, 1, [64, 128])
     assert two[0] == one[0] and np.array_equal(_bits(two[1]), _bits(one[1]))
-    _same(two[2], one[2])
+    Gqa.same(two[2], one[2])
     exact = _one_call(st, d, prefix, run, 0)
     other = _one_call(st, d, prefix, run, 1, [100, 92])
     r = _rel(other[1], exact[1])
@@ -218,9 +181,9 @@ def test_full_chunk_of_1024_tokens():
     one = _fast_run(st, d, prefix, run)
     st.set_prefill_chunk(0)
     assert np.array_equal(one["lg"], ref["lg"]) and one["tok"] == ref["tok"]
-    _same(one["snap"], ref["snap"])
+    Gqa.same(one["snap"], ref["snap"])
     st.create_slots(2, 1200)
-    _fill(st, d, prefix, [1])
+    fill_prefix(st, d, prefix, [1])
     st.set_option(OPT, 1); st.set_option(FLASH, 1)
     ids, lg = st.extend_multi([1], [run], [100], logits=True)
     st.set_option(OPT, 0); st.set_option(FLASH, 0)
@@ -238,7 +201,7 @@ def test_on_against_off_within_the_stated_bound(kinds, fp8, bound):
     out = []
     for on in (0, 1):
         st.create_slots(2, KV_MAX)
-        _fill(st, d, prefix, [1])
+        fill_prefix(st, d, prefix, [1])
         st.set_option(OPT, on)
         ids, lg = st.extend_multi([1], [run], [37], logits=True)
         ids2, lg2 = st.step_multi([1], [ids[0]], [37 + 170], logits=True)
@@ -257,7 +220,7 @@ def _unchanged_calls(st, d, refs, on):
     pick, slots = [1, 2, 4], [3, 0, 5]
     st.create_slots(8, KV_MAX)
     for i, s in zip(pick, slots):
-        _fill(st, d, refs[i]["prefix"], [s, s + 1])
+        fill_prefix(st, d, refs[i]["prefix"], [s, s + 1])
     st.set_option(OPT, on)
     pos = [refs[i]["pos0"] for i in pick]
     firsts = [refs[i]["run"][0] for i in pick]
@@ -271,17 +234,17 @@ def _unchanged_calls(st, d, refs, on):
     keep = [min(m + 1, 2) for m in nm]
     st.commit_multi(keep)
     out["verify"] = (greedy, list(nm))
-    out["states"] = [_slot_state(st, d, s, e + k) for s, e, k in zip(slots, end, keep)]
+    out["states"] = [slot_state(Gqa, st, d, s, e + k) for s, e, k in zip(slots, end, keep)]
     twins = [s + 1 for s in slots]
     out["plain"] = st.generate_multi(twins, firsts, pos, 8)
     for i, s in zip(pick, twins):
-        _fill(st, d, refs[i]["prefix"], [s])
+        fill_prefix(st, d, refs[i]["prefix"], [s])
     out["lookup"] = st.generate_multi_lookup(twins, firsts, pos, 8, contexts=[refs[i]["prefix"] + [refs[i]["run"][0]] for i in pick])
     for i, s in zip(pick, twins):
-        _fill(st, d, refs[i]["prefix"], [s])
+        fill_prefix(st, d, refs[i]["prefix"], [s])
     ids, lg = st.extend_multi(twins, [refs[i]["run"][:n] for i, n in zip(pick, (63, 2, 40))], pos, logits=True)
     out["short"] = (list(ids), _bits(lg))
-    out["short_states"] = [_slot_state(st, d, s, p + n) for s, p, n in zip(twins, pos, (63, 2, 40))]
+    out["short_states"] = [slot_state(Gqa, st, d, s, p + n) for s, p, n in zip(twins, pos, (63, 2, 40))]
     st.set_option(OPT, 0)
     return out
 
@@ -294,7 +257,7 @@ def test_short_runs_and_verify_passes_keep_their_bits():
     assert on["gen"] == off["gen"] and on["verify"] == off["verify"] and on["plain"] == off["plain"] and on["lookup"] == off["lookup"]
     assert on["short"][0] == off["short"][0] and np.array_equal(on["short"][1], off["short"][1])
     for a, b in zip(on["states"] + on["short_states"], off["states"] + off["short_states"]):
-        _same(a, b)
+        Gqa.same(a, b)
     assert on["lookup"] == on["plain"]                                      # speculation stays exact under the option
 
 
@@ -310,7 +273,7 @@ def test_store_without_linear_attention_layers_is_refused():
     st.create_slots(2, 20)
     st.set_option(OPT, 1)
     for call in _calls(st, d["V"]):
-        _state_error(call, OPT, "has none")
+        state_error(call, OPT, "has none")
     st.set_option(OPT, 0)
     st.step_multi([1], [1], [0])
 
@@ -322,7 +285,7 @@ def test_mla_store_is_refused():
     st.create_slots(2, 20)
     st.set_option(OPT, 1)
     for call in _calls(st, d["V"]):
-        _state_error(call, OPT)
+        state_error(call, OPT)
     st.set_option(OPT, 0)
     st.step_multi([1], [1], [0])
 
@@ -332,15 +295,15 @@ def test_key_width_64_is_refused_not_run_exactly():
     rng = np.random.default_rng(5)
     prefix, run = _toks(rng, d, 5), _toks(rng, d, 70)
     st.create_slots(2, 100)
-    _fill(st, d, prefix, [1])
-    before = _slot_state(st, d, 1, 5)
+    fill_prefix(st, d, prefix, [1])
+    before = slot_state(Gqa, st, d, 1, 5)
     st.set_option(OPT, 1)
     for call in list(_calls(st, d["V"])) + [lambda: st.extend_multi([1], [run], [5])]:
         with pytest.raises(ValueError) as e:
             call()
         assert OPT in str(e.value) and "not covered" in str(e.value), str(e.value)
     st.set_option(OPT, 0)                                                   # (load_slot is a slot call too: refused while the option stands)
-    _same(_slot_state(st, d, 1, 5), before)                                 # nothing ran
+    Gqa.same(slot_state(Gqa, st, d, 1, 5), before)                                 # nothing ran
     ids, lg = st.extend_multi([1], [run], [5], logits=True)                 # the slot the refusals left behind takes the exact pass
     got = (ids[0], lg[0].copy())
     want = _one_call(st, d, prefix, run, 0)
@@ -353,12 +316,12 @@ def test_mode_bits_and_the_paged_refusal_come_first():
     st.create_slots(2, KV_MAX)
     st.set_attention_mode(True)
     for call in _calls(st, d["V"]):
-        _state_error(call, "exact-mode only")
+        state_error(call, "exact-mode only")
     st.set_attention_mode(False)
     # "multi_attn_fast" alone on paged slots is still refused with the words it had
     st.create_slots(2, 32, page_tokens=32, n_pages=2)
     st.set_option("multi_attn_fast", 1)
     for call in _calls(st, d["V"]):
-        _state_error(call, "does not read paged slots")
+        state_error(call, "does not read paged slots")
     st.set_option("multi_attn_fast", 0)
     st.set_option(OPT, 0)

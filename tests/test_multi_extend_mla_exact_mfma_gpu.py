@@ -11,8 +11,7 @@ import functools
 import numpy as np
 import pytest
 
-import tests.test_multi_mla_gpu as MM
-from tests.test_multi_paged_gpu import Mla, _slot_state, _state_error
+from tests.slots import Gqa, Mla, bits as _bits, equal, fill_prefix, off_on, options_reset, pages as _pages, slot_state, state_error, store_cache, toks as _toks
 
 pytestmark = pytest.mark.gpu
 U = np.uint32
@@ -31,40 +30,20 @@ _stores = []
 ALL_OPTS = (OPT, "multi_extend_mla_flash", "multi_mla_fast", "multi_extend_exact_mfma", "multi_extend_la_chunk")
 
 
-@pytest.fixture(autouse=True)
-def options_off_afterwards():
-    yield
-    for st in _stores:
-        for o in ALL_OPTS:
-            st.set_option(o, 0)
-        st.set_attention_mode(False)
+options_off_afterwards = options_reset(_stores, ALL_OPTS)
 
 
-def _toks(rng, d, n):
-    return [int(x) for x in rng.integers(0, d["V"], n)]
-
-
-def _bits(x):
-    return np.ascontiguousarray(x).view(U).copy()
-
-
-def _pages(n, pt):
-    return (n + pt - 1) // pt
-
-
-@functools.lru_cache(maxsize=None)
+@store_cache(_stores)
 def _model(klr, nh, lora, fp8, kv_max=KV_MAX):
     """one store per geometry, built once and shared"""
-    st, eng, keep, d = MM._build(fp8, seed=3, klr=klr, nh=nh, lora=lora, kv_max=kv_max)
-    _stores.append(st)
-    return st, (eng, keep), d
+    return Mla.build(fp8, seed=3, klr=klr, nh=nh, lora=lora, kv_max=kv_max)
 
 
 def _exact_run(st, d, prefix, run):
     """the single-sequence reference: prefix and run by the store's own exact prompt pass from zero state -> logits bits, id, snapshot"""
-    MM._start(st, d, prefix)
+    Mla.start(st, d, prefix)
     tok = st.prefill(run, len(prefix))
-    return dict(prefix=prefix, run=run, pos0=len(prefix), end=len(prefix) + len(run), lg=_bits(st.read_logits()), tok=tok, snap=MM._snap(st, d, len(prefix) + len(run)))
+    return dict(prefix=prefix, run=run, pos0=len(prefix), end=len(prefix) + len(run), lg=_bits(st.read_logits()), tok=tok, snap=Mla.snap(st, d, len(prefix) + len(run)))
 
 
 @functools.lru_cache(maxsize=None)
@@ -73,40 +52,6 @@ def _refs(klr, nh, lora, fp8):
     st, _, d = _model(klr, nh, lora, fp8)
     rng = np.random.default_rng(klr + nh)
     return [_exact_run(st, d, _toks(rng, d, p), _toks(rng, d, c)) for p, c in CASES]
-
-
-def _fill(st, d, prefix, slots):
-    """the prefix, by the exact prompt pass on the store's own sequence, into every slot of `slots`"""
-    MM._start(st, d, prefix)
-    for s in slots:
-        st.save_slot(s, len(prefix))
-
-
-def _state(st, d, slot, upto):
-    return _slot_state(Mla, st, d, slot, upto)
-
-
-def _equal(a, b, where=""):
-    """two results (ids, logits, slot states) of one scenario: bit for bit"""
-    assert list(a[0]) == list(b[0]), ("ids", where)
-    assert np.array_equal(_bits(a[1]), _bits(b[1])), ("logits", where)
-    assert len(a[2]) == len(b[2])
-    for x, y in zip(a[2], b[2]):
-        MM._same(x, y)
-
-
-def _off_on(st, scenario, **other):
-    """scenario(st) -> (ids, logits, states) on slots it creates and fills itself, once with the option off and once with it on; `other` options stay set for both"""
-    out = []
-    for on in (0, 1):
-        for o, v in other.items():
-            st.set_option(o, v)
-        st.set_option(OPT, on)
-        out.append(scenario(st))
-        st.set_option(OPT, 0)
-        for o in other:
-            st.set_option(o, 0)
-    return out
 
 
 # ---- 1: on == off == the single-sequence exact prompt pass --------------------------------------------------------------------------------------------------
@@ -120,9 +65,9 @@ def test_runs_equal_option_off_and_single_sequence_prefill(key, slot_seq):
     def scenario(st):
         st.create_slots(8, slot_seq)
         for ref, s in zip(refs, SLOTS):
-            _fill(st, d, ref["prefix"], [s])
+            fill_prefix(st, d, ref["prefix"], [s])
         ids, lg = st.extend_multi(SLOTS, [r["run"] for r in refs], [r["pos0"] for r in refs], logits=True)
-        return ids, lg, [_state(st, d, s, r["end"]) for r, s in zip(refs, SLOTS)]
+        return ids, lg, [slot_state(Mla, st, d, s, r["end"]) for r, s in zip(refs, SLOTS)]
 
     took = []      # not vacuous: the pass took the option's form in the on-leg and not in the off-leg (multi_path_counts)
 
@@ -132,12 +77,12 @@ def test_runs_equal_option_off_and_single_sequence_prefill(key, slot_seq):
         took.append(st.multi_path_counts()["mla_xm"])
         return out
 
-    off, on = _off_on(st, counted)
+    off, on = off_on(st, OPT, counted)
     assert took == [0, 1], ("mla_xm", took)
-    _equal(on, off)
+    equal(Mla, on, off)
     for i, ref in enumerate(refs):
         assert np.array_equal(_bits(on[1][i]), ref["lg"]) and on[0][i] == ref["tok"], ("single-sequence prefill", i)
-        MM._same(on[2][i], ref["snap"])
+        Mla.same(on[2][i], ref["snap"])
 
 
 # ---- 2: cuts ------------------------------------------------------------------------------------------------------------------------------------------------
@@ -151,19 +96,19 @@ def test_cuts_give_the_bits_of_one_call(key):
     st.set_option(OPT, 1)
     for cuts in ([2, 40, 128], [1, 169]):
         st.create_slots(2, KV_MAX)
-        _fill(st, d, ref["prefix"], [1])
+        fill_prefix(st, d, ref["prefix"], [1])
         at = 0
         for c in cuts:
             ids, lg = st.extend_multi([1], [run[at:at + c]], [p0 + at], logits=True)
             at += c
         assert np.array_equal(_bits(lg[0]), ref["lg"]) and ids[0] == ref["tok"], cuts
-        MM._same(_state(st, d, 1, ref["end"]), ref["snap"])
+        Mla.same(slot_state(Mla, st, d, 1, ref["end"]), ref["snap"])
     st.create_slots(2, KV_MAX)
-    _fill(st, d, ref["prefix"], [1])
+    fill_prefix(st, d, ref["prefix"], [1])
     tok = st.prefill_slot(1, run, p0, chunk=64)
     st.set_option(OPT, 0)
     assert tok == ref["tok"]
-    MM._same(_state(st, d, 1, ref["end"]), ref["snap"])
+    Mla.same(slot_state(Mla, st, d, 1, ref["end"]), ref["snap"])
 
 
 # ---- 3: mixed passes ----------------------------------------------------------------------------------------------------------------------------------------
@@ -172,9 +117,9 @@ def _mixed(st, d, refs, rows, slot_seq=KV_MAX, **slots_kw):
     st.create_slots(8, slot_seq, **slots_kw)
     slots = list(range(1, 1 + len(rows)))
     for (kind, i), s in zip(rows, slots):
-        _fill(st, d, refs[i]["prefix"], [s])
+        fill_prefix(st, d, refs[i]["prefix"], [s])
     ids, lg = st.extend_multi(slots, [refs[i]["run"][:1] if k == "u" else refs[i]["run"] for k, i in rows], [refs[i]["pos0"] for _, i in rows], logits=True)
-    return ids, lg, [_state(st, d, s, refs[i]["pos0"] + (1 if k == "u" else len(refs[i]["run"]))) for (k, i), s in zip(rows, slots)]
+    return ids, lg, [slot_state(Mla, st, d, s, refs[i]["pos0"] + (1 if k == "u" else len(refs[i]["run"]))) for (k, i), s in zip(rows, slots)]
 
 
 @pytest.mark.parametrize("key", MODELS)
@@ -184,19 +129,19 @@ def test_mixed_passes(key):
     st, _, d = _model(*key)
     refs = _refs(*key)
     for rows in ([("u", 5), ("r", 1), ("u", 0), ("u", 1), ("r", 3)], [("r", 2), ("r", 0), ("r", 4)]):
-        off, on = _off_on(st, lambda st: _mixed(st, d, refs, rows))
-        _equal(on, off, rows)
+        off, on = off_on(st, OPT, lambda st: _mixed(st, d, refs, rows))
+        equal(Mla, on, off, rows)
 
     def steps(st):
         st.create_slots(8, KV_MAX)
         pick, slots = [1, 3, 5], [3, 0, 5]
         for i, s in zip(pick, slots):
-            _fill(st, d, refs[i]["prefix"], [s])
+            fill_prefix(st, d, refs[i]["prefix"], [s])
         ids, lg = st.step_multi(slots, [refs[i]["run"][0] for i in pick], [refs[i]["pos0"] for i in pick], logits=True)
-        return ids, lg, [_state(st, d, s, refs[i]["pos0"] + 1) for i, s in zip(pick, slots)]
+        return ids, lg, [slot_state(Mla, st, d, s, refs[i]["pos0"] + 1) for i, s in zip(pick, slots)]
 
-    off, on = _off_on(st, steps)
-    _equal(on, off, "step_multi")
+    off, on = off_on(st, OPT, steps)
+    equal(Mla, on, off, "step_multi")
 
 
 def test_verify_and_commit_are_untouched():
@@ -208,16 +153,16 @@ def test_verify_and_commit_are_untouched():
         st.create_slots(8, KV_MAX)
         pick, slots = [1, 2, 3], [3, 0, 5]
         for i, s in zip(pick, slots):
-            _fill(st, d, refs[i]["prefix"], [s])
+            fill_prefix(st, d, refs[i]["prefix"], [s])
         pos = [refs[i]["pos0"] for i in pick]
         drafts = [refs[i]["run"][:3] for i in pick]
         greedy, nm = st.verify_multi(slots, drafts, pos)
         keep = [min(m + 1, 2) for m in nm]
         st.commit_multi(keep)
-        return [g for row in greedy for g in row] + list(nm), np.zeros(1, np.float32), [_state(st, d, s, p + k) for s, p, k in zip(slots, pos, keep)]
+        return [g for row in greedy for g in row] + list(nm), np.zeros(1, np.float32), [slot_state(Mla, st, d, s, p + k) for s, p, k in zip(slots, pos, keep)]
 
-    off, on = _off_on(st, scenario)
-    _equal(on, off, "verify + commit")
+    off, on = off_on(st, OPT, scenario)
+    equal(Mla, on, off, "verify + commit")
 
 
 # ---- 4: paged and forked slots ------------------------------------------------------------------------------------------------------------------------------
@@ -237,28 +182,28 @@ def test_paged_and_forked_slots(key, page_tokens):
         need = sum(_pages(r["end"], pt) for r in refs) + 2 * _pages(ref["end"], pt)
         st.create_slots(8, KV_MAX, page_tokens=pt, n_pages=need + 2)
         for r, s in list(zip(refs, SLOTS))[:LONGEST]:
-            _fill(st, d, r["prefix"], [s])
+            fill_prefix(st, d, r["prefix"], [s])
         st.reset_decode_state(d["kv_max"]); st.save_slot(spare, min(100, pt))
-        _fill(st, d, ref["prefix"], [SLOTS[LONGEST]])
+        fill_prefix(st, d, ref["prefix"], [SLOTS[LONGEST]])
         st.reset_decode_state(d["kv_max"]); st.save_slot(dst, 1)
         st.trim_slot(spare, 0)
         ids, lg = st.extend_multi(SLOTS, [r["run"] for r in refs], [r["pos0"] for r in refs], logits=True)
         used = [int(x) for x in st.slot_page_ids(SLOTS[LONGEST])[0][:_pages(ref["end"], pt)]]
         assert min(used) >= 0 and used != list(range(used[0], used[0] + len(used))), ("the longest run's pages are consecutive", used)
-        states = [_state(st, d, s, r["end"]) for r, s in zip(refs, SLOTS)]
+        states = [slot_state(Mla, st, d, s, r["end"]) for r, s in zip(refs, SLOTS)]
         for s in SLOTS[:LONGEST]:
             st.trim_slot(s, 0)
         st.trim_slot(dst, 0)
         st.trim_slot(SLOTS[LONGEST], ref["pos0"])
         st.fork_slot(SLOTS[LONGEST], [dst], ref["pos0"])
         ids2, lg2 = st.extend_multi([dst], [ref["run"]], [ref["pos0"]], logits=True)
-        states += [_state(st, d, dst, ref["end"]), _state(st, d, SLOTS[LONGEST], ref["pos0"])]
+        states += [slot_state(Mla, st, d, dst, ref["end"]), slot_state(Mla, st, d, SLOTS[LONGEST], ref["pos0"])]
         return list(ids) + list(ids2), np.concatenate([lg, lg2]), states
 
-    off, on = _off_on(st, scenario)
-    _equal(on, off, ("paged", pt))
-    MM._same(on[2][-1], [(a[:ref["pos0"]], b[:ref["pos0"]]) for a, b in ref["snap"]])      # the fork's src: untouched
-    MM._same(on[2][-2], ref["snap"])
+    off, on = off_on(st, OPT, scenario)
+    equal(Mla, on, off, ("paged", pt))
+    Mla.same(on[2][-1], [(a[:ref["pos0"]], b[:ref["pos0"]]) for a, b in ref["snap"]])      # the fork's src: untouched
+    Mla.same(on[2][-2], ref["snap"])
 
 
 # ---- 5: long slots, flash-decode unit rows ------------------------------------------------------------------------------------------------------------------
@@ -281,16 +226,16 @@ def test_long_slots_with_flash_decode_unit_rows(paged):
     def scenario(st):
         st.create_slots(5, LONG_KV, **kw)
         for p, s in zip(prefixes, slots):
-            _fill(st, d, p, [s])
+            fill_prefix(st, d, p, [s])
         ids, lg = st.extend_multi(slots, runs, [p for p, _ in cases], logits=True)
-        return ids, lg, [_state(st, d, s, p + c) for s, (p, c) in zip(slots, cases)]
+        return ids, lg, [slot_state(Mla, st, d, s, p + c) for s, (p, c) in zip(slots, cases)]
 
     exact = scenario(st)                                                    # every option off
-    fd, both = _off_on(st, scenario, multi_mla_fast=1)
+    fd, both = off_on(st, OPT, scenario, multi_mla_fast=1)
     for r, (p, c) in enumerate(cases):
         want = fd if c == 1 else exact
         assert both[0][r] == want[0][r] and np.array_equal(_bits(both[1][r]), _bits(want[1][r])), ("row", r, "unit" if c == 1 else "run")
-        MM._same(both[2][r], want[2][r])
+        Mla.same(both[2][r], want[2][r])
     assert any(not np.array_equal(_bits(fd[1][r]), _bits(exact[1][r])) for r, (_, c) in enumerate(cases) if c == 1)      # the flash-decode did run on the unit rows
 
 
@@ -305,13 +250,13 @@ def test_short_call_after_a_long_one(key):
     def scenario(st):
         st.create_slots(8, KV_MAX)
         for i, s in zip([5, 3, 1, 0], [2, 4, 1, 6]):
-            _fill(st, d, refs[i]["prefix"], [s])
+            fill_prefix(st, d, refs[i]["prefix"], [s])
         st.extend_multi([2, 4], [refs[5]["run"], refs[3]["run"]], [refs[5]["pos0"], refs[3]["pos0"]])
         ids, lg = st.extend_multi([1, 6], [refs[1]["run"][:7], refs[0]["run"]], [refs[1]["pos0"], refs[0]["pos0"]], logits=True)
-        return ids, lg, [_state(st, d, 1, refs[1]["pos0"] + 7), _state(st, d, 6, refs[0]["end"])]
+        return ids, lg, [slot_state(Mla, st, d, 1, refs[1]["pos0"] + 7), slot_state(Mla, st, d, 6, refs[0]["end"])]
 
-    off, on = _off_on(st, scenario)
-    _equal(on, off, "short after long")
+    off, on = off_on(st, OPT, scenario)
+    equal(Mla, on, off, "short after long")
 
 
 # ---- 7: refusals --------------------------------------------------------------------------------------------------------------------------------------------
@@ -344,22 +289,21 @@ def test_both_mla_run_options_are_refused():
     def arm():
         st.set_option(OPT, 1); st.set_option("multi_extend_mla_flash", 1)
 
-    _refused_then_fine(st, d, lambda s, p: _state(st, d, s, p), arm, lambda call: _state_error(call, OPT, "multi_extend_mla_flash"),
+    _refused_then_fine(st, d, lambda s, p: slot_state(Mla, st, d, s, p), arm, lambda call: state_error(call, OPT, "multi_extend_mla_flash"),
                        lambda: st.set_option("multi_extend_mla_flash", 0))      # the option itself stays set
     st.set_option(OPT, 0)
 
 
 def test_store_without_mla_layers_is_refused():
     from tests.test_decode_gpu import build
-    from tests.test_speculative_gpu import _snap
     st, eng, orc, keep, d = build(seed=3, kv_max=32)                        # linear attention + GQA
     _stores.append(st)
 
     def state(slot, upto):
         st.reset_decode_state(d["kv_max"]); st.load_slot(slot, upto)
-        return [tuple(x for x in row if isinstance(x, np.ndarray)) for row in _snap(st, d, upto)]
+        return [tuple(x for x in row if isinstance(x, np.ndarray)) for row in Gqa.snap(st, d, upto)]
 
-    _refused_then_fine(st, d, state, lambda: st.set_option(OPT, 1), lambda call: _state_error(call, OPT, "has none"), lambda: st.set_option(OPT, 0))
+    _refused_then_fine(st, d, state, lambda: st.set_option(OPT, 1), lambda call: state_error(call, OPT, "has none"), lambda: st.set_option(OPT, 0))
 
 
 def test_three_heads_are_refused_not_run_by_the_per_row_kernel():
@@ -372,7 +316,7 @@ def test_three_heads_are_refused_not_run_by_the_per_row_kernel():
             call()
         assert OPT in str(e.value) and "divide 32" in str(e.value), str(e.value)
 
-    _refused_then_fine(st, d, lambda s, p: _state(st, d, s, p), lambda: st.set_option(OPT, 1), refuse, lambda: st.set_option(OPT, 0))
+    _refused_then_fine(st, d, lambda s, p: slot_state(Mla, st, d, s, p), lambda: st.set_option(OPT, 1), refuse, lambda: st.set_option(OPT, 0))
     st.create_slots(2, 20)
     got = st.extend_multi([1], [[1, 2, 3]], [0], logits=True)
     assert got[0] == want[0] and np.array_equal(_bits(got[1]), _bits(want[1]))
@@ -384,5 +328,5 @@ def test_mode_bits_stay_refused_with_their_old_text():
     def arm():
         st.set_option(OPT, 1); st.set_attention_mode(True)
 
-    _refused_then_fine(st, d, lambda s, p: _state(st, d, s, p), arm, lambda call: _state_error(call, "exact-mode only"), lambda: st.set_attention_mode(False))      # the option itself stays set
+    _refused_then_fine(st, d, lambda s, p: slot_state(Mla, st, d, s, p), arm, lambda call: state_error(call, "exact-mode only"), lambda: st.set_attention_mode(False))      # the option itself stays set
     st.set_option(OPT, 0)

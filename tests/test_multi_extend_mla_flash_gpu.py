@@ -13,8 +13,7 @@ import functools
 import numpy as np
 import pytest
 
-import tests.test_multi_mla_gpu as MM
-from tests.test_multi_paged_gpu import Mla, _slot_state, _state_error
+from tests.slots import Mla, bits as _bits, options_reset, pages as _pages, slot_state, state_error, store_cache, toks as _toks
 
 pytestmark = pytest.mark.gpu
 F = np.float32
@@ -33,38 +32,19 @@ R170 = 4                                                                    # th
 _stores = []
 
 
-@pytest.fixture(autouse=True)
-def options_off_afterwards():
-    yield
-    for st in _stores:
-        st.set_option(OPT, 0); st.set_option("multi_mla_fast", 0); st.set_option("multi_extend_flash", 0); st.set_option("multi_extend_la_chunk", 0)
-        st.set_attention_mode(False)
+options_off_afterwards = options_reset(_stores, (OPT, "multi_mla_fast", "multi_extend_flash", "multi_extend_la_chunk"))
 
 
-def _toks(rng, d, n):
-    return [int(x) for x in rng.integers(0, d["V"], n)]
-
-
-def _bits(x):
-    return np.ascontiguousarray(x).view(U).copy()
-
-
-def _pages(n, pt):
-    return (n + pt - 1) // pt
-
-
-@functools.lru_cache(maxsize=None)
+@store_cache(_stores)
 def _model(klr, nh, lora, fp8, kv_max=KV_MAX):
     """one store per geometry, built once and shared"""
-    st, eng, keep, d = MM._build(fp8, seed=3, klr=klr, nh=nh, lora=lora, kv_max=kv_max)
-    _stores.append(st)
-    return st, (eng, keep), d
+    return Mla.build(fp8, seed=3, klr=klr, nh=nh, lora=lora, kv_max=kv_max)
 
 
 def _start(st, d, prefix):
     """the store's own sequence = prefix, by the EXACT prompt pass from zero state"""
     st.set_attention_mode(False)
-    MM._start(st, d, prefix)
+    Mla.start(st, d, prefix)
 
 
 def _fast_run(st, d, prefix, run):
@@ -73,7 +53,7 @@ def _fast_run(st, d, prefix, run):
     st.set_attention_mode(True)
     try:
         tok = st.prefill(run, len(prefix))
-        ref = dict(prefix=prefix, run=run, pos0=len(prefix), end=len(prefix) + len(run), lg=_bits(st.read_logits()), tok=tok, snap=MM._snap(st, d, len(prefix) + len(run)))
+        ref = dict(prefix=prefix, run=run, pos0=len(prefix), end=len(prefix) + len(run), lg=_bits(st.read_logits()), tok=tok, snap=Mla.snap(st, d, len(prefix) + len(run)))
     finally:
         st.set_attention_mode(False)
     return ref
@@ -85,7 +65,7 @@ def _fast_unit(st, d, prefix, tok):
     st.set_attention_mode(True)
     try:
         st.decode_step(tok, len(prefix))
-        ref = dict(prefix=prefix, run=[tok], pos0=len(prefix), end=len(prefix) + 1, lg=_bits(st.read_logits()), tok=st.last_token(), snap=MM._snap(st, d, len(prefix) + 1))
+        ref = dict(prefix=prefix, run=[tok], pos0=len(prefix), end=len(prefix) + 1, lg=_bits(st.read_logits()), tok=st.last_token(), snap=Mla.snap(st, d, len(prefix) + 1))
     finally:
         st.set_attention_mode(False)
     return ref
@@ -106,14 +86,10 @@ def _fill(st, d, prefix, slots):
         st.save_slot(s, len(prefix))
 
 
-def _state(st, d, slot, upto):
-    return _slot_state(Mla, st, d, slot, upto)
-
-
 def _assert_run(st, d, ref, slot, tok, lg, where=""):
     assert np.array_equal(_bits(lg), ref["lg"]), ("logits", where, ref["pos0"], len(ref["run"]))
     assert tok == ref["tok"], ("id", where, ref["pos0"])
-    MM._same(_state(st, d, slot, ref["end"]), ref["snap"])
+    Mla.same(slot_state(Mla, st, d, slot, ref["end"]), ref["snap"])
 
 
 # ---- 1: a run equals the single-sequence flash prompt pass ---------------------------------------------------------------------------------------------------
@@ -163,7 +139,7 @@ def test_prefill_slot_in_chunks_equals_the_run():
     tok = st.prefill_slot(1, ref["run"], ref["pos0"], chunk=64)
     st.set_option(OPT, 0)
     assert tok == ref["tok"]
-    MM._same(_state(st, d, 1, ref["end"]), ref["snap"])
+    Mla.same(slot_state(Mla, st, d, 1, ref["end"]), ref["snap"])
 
 
 # ---- 3: unit rows beside runs --------------------------------------------------------------------------------------------------------------------------------
@@ -176,7 +152,7 @@ def _mixed(st, d, refs, rows, slot_seq, on, **slots_kw):
     st.set_option(OPT, 1 if on else 0)
     ids, lg = st.extend_multi(slots, [refs[i]["run"][:1] if k == "u" else refs[i]["run"] for k, i in rows], [refs[i]["pos0"] for _, i in rows], logits=True)
     st.set_option(OPT, 0)
-    states = [_state(st, d, s, refs[i]["pos0"] + 1) for (k, i), s in zip(rows, slots) if k == "u"]
+    states = [slot_state(Mla, st, d, s, refs[i]["pos0"] + 1) for (k, i), s in zip(rows, slots) if k == "u"]
     return slots, ids, lg, states
 
 
@@ -192,7 +168,7 @@ def test_mixed_pass(key):
     for r, ((kind, i), s) in enumerate(zip(rows, slots)):
         if kind == "u":
             assert np.array_equal(_bits(lg1[r]), _bits(lg0[r])) and ids1[r] == ids0[r], ("unit row", r)
-            MM._same(states1[u], states0[u]); u += 1
+            Mla.same(states1[u], states0[u]); u += 1
         else:
             _assert_run(st, d, refs[i], s, ids1[r], lg1[r], ("run", r))
 
@@ -225,7 +201,7 @@ def test_mixed_pass_over_long_slots_with_flash_decode_rows(paged):
     for r, ((kind, i), s) in enumerate(zip(rows, slots)):
         if kind == "u":
             assert np.array_equal(_bits(lg[r]), refs[i]["lg"]) and ids[r] == refs[i]["tok"], ("unit row", r)
-            MM._same(states[u], refs[i]["snap"]); u += 1
+            Mla.same(states[u], refs[i]["snap"]); u += 1
         else:
             _assert_run(st, d, refs[i], s, ids[r], lg[r], ("run", r))
 
@@ -281,7 +257,7 @@ def test_run_over_a_forked_slot(key, page_tokens):
     for r, s in enumerate(dsts):
         _assert_run(st, d, ref, s, ids[r], lg[r], ("fork dst", s))
         assert st.slot_page_ids(s)[0][:full] == tables[0][0][:full]         # still the shared pages
-    MM._same(_state(st, d, src, ref["pos0"]), [(a[:ref["pos0"]], b[:ref["pos0"]]) for a, b in ref["snap"]])      # src untouched
+    Mla.same(slot_state(Mla, st, d, src, ref["pos0"]), [(a[:ref["pos0"]], b[:ref["pos0"]]) for a, b in ref["snap"]])      # src untouched
 
 
 # ---- 7: a pool one page short --------------------------------------------------------------------------------------------------------------------------------
@@ -294,13 +270,13 @@ def test_pool_one_page_short_fails_whole():
     for i, s in zip(pick, slots):
         _fill(st, d, refs[i]["prefix"], [s])
     before = st.slot_pages()
-    states = [_state(st, d, s, refs[i]["pos0"]) for i, s in zip(pick, slots)]
+    states = [slot_state(Mla, st, d, s, refs[i]["pos0"]) for i, s in zip(pick, slots)]
     st.set_option(OPT, 1)
-    _state_error(lambda: st.extend_multi(slots, [refs[i]["run"] for i in pick], [refs[i]["pos0"] for i in pick]), "does not fit the page pool")
+    state_error(lambda: st.extend_multi(slots, [refs[i]["run"] for i in pick], [refs[i]["pos0"] for i in pick]), "does not fit the page pool")
     st.set_option(OPT, 0)
     assert st.slot_pages() == before
     for (i, s), want in zip(zip(pick, slots), states):
-        MM._same(_state(st, d, s, refs[i]["pos0"]), want)
+        Mla.same(slot_state(Mla, st, d, s, refs[i]["pos0"]), want)
 
 
 # ---- 8: nothing past the end is read -------------------------------------------------------------------------------------------------------------------------
@@ -357,7 +333,7 @@ def test_full_chunk_of_1024_tokens():
     one = _fast_run(st, d, prefix, run)
     st.set_prefill_chunk(0)
     assert np.array_equal(one["lg"], ref["lg"]) and one["tok"] == ref["tok"]
-    MM._same(one["snap"], ref["snap"])
+    Mla.same(one["snap"], ref["snap"])
     st.create_slots(2, 1100)
     _fill(st, d, prefix, [1])
     st.set_option(OPT, 1)
@@ -416,7 +392,7 @@ def _unchanged_calls(st, d, refs, on):
     keep = [min(m + 1, 2) for m in nm]
     st.commit_multi(keep)
     out["verify"] = (greedy, list(nm))
-    out["states"] = [_state(st, d, s, e + k) for s, e, k in zip(slots, end, keep)]
+    out["states"] = [slot_state(Mla, st, d, s, e + k) for s, e, k in zip(slots, end, keep)]
     twins = [s + 1 for s in slots]
     out["plain"] = st.generate_multi(twins, firsts, pos, 8)
     for i, s in zip(pick, twins):
@@ -436,7 +412,7 @@ def test_unit_runs_and_verify_passes_keep_their_bits():
     assert on["unit"][0] == on["step"][0] and np.array_equal(on["unit"][1], on["step"][1])
     assert on["gen"] == off["gen"] and on["verify"] == off["verify"] and on["plain"] == off["plain"]
     for a, b in zip(on["states"], off["states"]):
-        MM._same(a, b)
+        Mla.same(a, b)
     assert on["lookup"] == on["plain"]                                      # speculation stays exact under the option
 
 
@@ -455,7 +431,7 @@ def test_store_without_mla_layers_is_refused():
     want = st.extend_multi([1], [[1, 2, 3]], [0], logits=True)
     st.set_option(OPT, 1)
     for call in _calls(st, d["V"]):
-        _state_error(call, OPT, "has none")
+        state_error(call, OPT, "has none")
     st.set_option(OPT, 0)
     st.create_slots(2, 20)
     got = st.extend_multi([1], [[1, 2, 3]], [0], logits=True)
@@ -471,29 +447,29 @@ def test_other_refusals_stay_and_option_zero_is_the_exact_pass():
         st.create_slots(2, KV_MAX)
         _fill(st, d, ref["prefix"], [1])
         ids, lg = st.extend_multi([1], [ref["run"]], [ref["pos0"]], logits=True)
-        return ids[0], _bits(lg[0]), _state(st, d, 1, ref["end"])
+        return ids[0], _bits(lg[0]), slot_state(Mla, st, d, 1, ref["end"])
 
     exact = run()
     st.set_option(OPT, 1)
     st.create_slots(2, KV_MAX)
     st.set_attention_mode(True)                                             # the mode bits stay refused
     for call in _calls(st, d["V"]):
-        _state_error(call, "exact-mode only")
+        state_error(call, "exact-mode only")
     st.set_attention_mode(False)
     st.set_option("multi_extend_flash", 1)                                  # the GQA run option keeps its refusal of a store with an MLA layer, and its words
     for call in _calls(st, d["V"]):
-        _state_error(call, '"multi_extend_flash" option covers GQA layers only', "is MLA")
+        state_error(call, '"multi_extend_flash" option covers GQA layers only', "is MLA")
     st.set_option("multi_extend_flash", 0)
     st.set_option("multi_extend_la_chunk", 1)                               # so does the linear-attention one
     for call in _calls(st, d["V"]):
-        _state_error(call, '"multi_extend_la_chunk" option covers linear-attention layers only')
+        state_error(call, '"multi_extend_la_chunk" option covers linear-attention layers only')
     st.set_option("multi_extend_la_chunk", 0)
     st.create_slots(2, KV_MAX, page_tokens=32, n_pages=4)                   # "multi_attn_fast" on an MLA store is refused first, with the words it had
     st.set_option("multi_attn_fast", 1)
     for call in _calls(st, d["V"]):
-        _state_error(call, '"multi_attn_fast" option covers GQA layers only')
+        state_error(call, '"multi_attn_fast" option covers GQA layers only')
     st.set_option("multi_attn_fast", 0)
     st.set_option(OPT, 0)
     again = run()
     assert again[0] == exact[0] and np.array_equal(again[1], exact[1])
-    MM._same(again[2], exact[2])
+    Mla.same(again[2], exact[2])

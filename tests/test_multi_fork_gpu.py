@@ -6,10 +6,9 @@ import numpy as np
 import pytest
 
 from tests import test_multi_mla_gpu as mla
-from tests import test_multi_seq_gpu as seq
 from tests.test_decode_gpu import build
-from tests.test_multi_paged_gpu import PT, Gqa, Mla, _pages, _slot_state, _state_error, _toks
-from tests.test_speculative_gpu import _same
+from tests.slots import Gqa, Mla, pages as _pages, slot_state, state_error, toks as _toks
+from tests.test_multi_paged_gpu import PT
 
 pytestmark = pytest.mark.gpu
 U = np.uint32
@@ -50,7 +49,7 @@ def _fork_then_steps(K, st, d, n_prompt, n_pages=10, n_steps=40):
     st.create_slots(4, 120, page_tokens=PT, n_pages=n_pages)
     st.prefill_slot(SRC, prompt, chunk=24)
     free = st.slot_pages()["free"]
-    assert free == n_pages - _pages(n_prompt)
+    assert free == n_pages - _pages(n_prompt, PT)
     src_ids = _ids(st, SRC)
     st.fork_slot(SRC, DSTS, n_prompt)
     full, part = n_prompt // PT, n_prompt % PT
@@ -63,16 +62,16 @@ def _fork_then_steps(K, st, d, n_prompt, n_pages=10, n_steps=40):
         edge = [ids[full] for ids, _ in got]
         assert len(set(edge)) == 3 and min(edge) >= 0 and [refc[full] for _, refc in got] == [1, 1, 1]
     assert st.slot_pages()["free"] == free - (2 if part else 0)
-    assert st.slot_pages()["per_slot"] == [_pages(n_prompt), 0, _pages(n_prompt), _pages(n_prompt)]
+    assert st.slot_pages()["per_slot"] == [_pages(n_prompt, PT), 0, _pages(n_prompt, PT), _pages(n_prompt, PT)]
     toks, pos = _steps(st, ALL, firsts, [n_prompt] * 3, refs, 1)
     if not part:      # the first step maps one page per slot
         assert st.slot_pages()["free"] == free - 3 and [_ids(st, s)[1][full] for s in ALL] == [1, 1, 1]
     toks, pos = _steps(st, ALL, toks, pos, refs, n_steps - 1, 1)
     for ids, refc in (_ids(st, s) for s in ALL):      # appending never touched the shared pages
         assert ids[:full] == src_ids[0][:full] and refc[:full] == [3] * full
-    assert st.slot_pages()["free"] == n_pages - full - 3 * (_pages(pos[0]) - full)
+    assert st.slot_pages()["free"] == n_pages - full - 3 * (_pages(pos[0], PT) - full)
     for i, (_, snap) in enumerate(refs):
-        K.same(_slot_state(K, st, d, ALL[i], pos[i]), snap)
+        K.same(slot_state(K, st, d, ALL[i], pos[i]), snap)
 
 
 @pytest.mark.parametrize("fp8", [False, True])
@@ -102,7 +101,7 @@ def test_short_forks_share_nothing(K):
     st.fork_slot(1, 0, 0)                                         # an int for dsts
     assert st.slot_pages()["free"] == 8 and _ids(st, 0) == ([-1] * 4, [0] * 4)
     toks, pos = _steps(st, [0], firsts[:1], [0], [fresh], 4)      # the dst equals a fresh slot
-    K.same(_slot_state(K, st, d, 0, 4), fresh[1])
+    K.same(slot_state(K, st, d, 0, 4), fresh[1])
     st.trim_slot(0, 0)
     st.prefill_slot(SRC, prompt, chunk=24)
     st.fork_slot(SRC, DSTS, 31)
@@ -111,7 +110,7 @@ def test_short_forks_share_nothing(K):
     assert st.slot_pages()["free"] == 5
     toks, pos = _steps(st, ALL, firsts, [31] * 3, refs, 5)        # over position 32
     for i, (_, snap) in enumerate(refs):
-        K.same(_slot_state(K, st, d, ALL[i], pos[i]), snap)
+        K.same(slot_state(K, st, d, ALL[i], pos[i]), snap)
 
 
 # ---- 4: rows at or past the fork point read as zero ------------------------------------------------------------------------------------------------------
@@ -134,7 +133,7 @@ def test_rows_past_the_fork_point_are_zero(K, fp8):
         K.start(st, d, prompt)                                    # the store's rows are non-zero before the load
         st.load_slot(0, 96)
         out.append(K.snap(st, d, 96))
-        src = _slot_state(K, st, d, SRC, 90)
+        src = slot_state(K, st, d, SRC, 90)
         n_checked = 0
         for got, ref, own in zip(out[-1], want, src):
             for a, b, c in zip(_rows(K, got), _rows(K, ref), _rows(K, own)):
@@ -166,8 +165,8 @@ def test_write_below_the_fork_point_copies_the_page(cfg, fp8):
     assert after[1] == [2, 1, 1, 0] and src[0][:2] == before[0][:2] and src[1] == [2, 1, 1, 0]      # the old page 1 has one reference fewer
     assert st.slot_pages()["free"] == free - 1
     _steps(st, [SRC, 0], firsts, [70, 60], [src_ref, dst_ref], 6)
-    Mla.same(_slot_state(Mla, st, d, SRC, 76), src_ref[1])
-    Mla.same(_slot_state(Mla, st, d, 0, 66), dst_ref[1])
+    Mla.same(slot_state(Mla, st, d, SRC, 76), src_ref[1])
+    Mla.same(slot_state(Mla, st, d, 0, 66), dst_ref[1])
 
 
 # ---- 6: speculation on forked slots ----------------------------------------------------------------------------------------------------------------------
@@ -186,9 +185,9 @@ def _speculation(K, st, d, paged, prompt, firsts):
         else:
             T = st.generate_multi_lookup(ALL, firsts, pos, 14, ctx, 7, 2)
         if paged:      # what the call mapped past each row's end went back; the whole page below the fork point is still shared
-            assert [st.slot_pages()["per_slot"][s] for s in ALL] == [_pages(len(prompt) + len(t)) for t in T]
+            assert [st.slot_pages()["per_slot"][s] for s in ALL] == [_pages(len(prompt) + len(t), PT) for t in T]
             assert all(_ids(st, s)[1][0] == 3 for s in ALL)
-        out.append((T, dict(st.last_multi_lookup_stats), [_slot_state(K, st, d, s, len(prompt) + len(t)) for s, t in zip(ALL, T)],
+        out.append((T, dict(st.last_multi_lookup_stats), [slot_state(K, st, d, s, len(prompt) + len(t)) for s, t in zip(ALL, T)],
                     [st.slot_sampler_state(s) for s in ALL]))
     return out
 
@@ -231,7 +230,7 @@ def test_last_reference_frees(K, fp8):
     assert _ids(st, 0)[1] == [2, 2, 1, 0] and _ids(st, 0)[0][:2] == _ids(st, 3)[0][:2]
     toks, pos = _steps(st, DSTS, firsts, [70, 70], refs, 3)
     for i, (_, snap) in enumerate(refs):
-        K.same(_slot_state(K, st, d, DSTS[i], 73), snap)
+        K.same(slot_state(K, st, d, DSTS[i], 73), snap)
     st.trim_slot(0, 0)
     assert st.slot_pages()["free"] == 3 and _ids(st, 3)[1] == [1, 1, 1, 0]
     st.trim_slot(3, 0)
@@ -259,7 +258,7 @@ def test_pages_of_the_dsts_count_towards_the_fork(K):
     fill(5)                                                       # nothing free, two to come: one page short
     before = _tables(st)
     assert before[1]["free"] == 0
-    _state_error(lambda: st.fork_slot(SRC, dsts, 70), "3 more pages", "2 of 5")
+    state_error(lambda: st.fork_slot(SRC, dsts, 70), "3 more pages", "2 of 5")
     assert _tables(st) == before                                  # nothing was released, nothing mapped
     _steps(st, [SRC, 0], [firsts[0], firsts[4]], [70, 33], [refs[0], other_ref], 1)
     fill(6)                                                       # one free and two to come: it fits only because of them
@@ -271,7 +270,7 @@ def test_pages_of_the_dsts_count_towards_the_fork(K):
     slots = [SRC] + dsts
     _steps(st, slots, firsts[:4], [70] * 4, refs, 2)
     for i, (_, snap) in enumerate(refs):
-        K.same(_slot_state(K, st, d, slots[i], 72), snap)
+        K.same(slot_state(K, st, d, slots[i], 72), snap)
 
 
 # ---- 9: a private copy that the pool cannot give refuses the whole call ---------------------------------------------------------------------------------
@@ -287,13 +286,13 @@ def test_copy_on_write_without_a_free_page_is_refused_whole(K):
     before = _tables(st)
     assert before[1]["free"] == 0
     # row 1 writes position 40 of slot 0, inside shared page 1: it needs a private copy and there is no page
-    _state_error(lambda: st.step_multi([SRC, 0], [first, first], [70, 40]), "row 1", "slot 0", "0 of 4")
-    _state_error(lambda: st.verify_multi([0], [[first, first]], [62]), "row 0")
-    _state_error(lambda: st.generate_multi([SRC, 0], [first, first], [70, 50], 4), "row 1")
+    state_error(lambda: st.step_multi([SRC, 0], [first, first], [70, 40]), "row 1", "slot 0", "0 of 4")
+    state_error(lambda: st.verify_multi([0], [[first, first]], [62]), "row 0")
+    state_error(lambda: st.generate_multi([SRC, 0], [first, first], [70, 50], 4), "row 1")
     assert _tables(st) == before
     _steps(st, [SRC, 0], [first, first], [70, 70], [ref, ref], 2)      # row 0 of the refused call had not advanced: both slots still step as the reference
-    K.same(_slot_state(K, st, d, SRC, 72), ref[1])
-    K.same(_slot_state(K, st, d, 0, 72), ref[1])
+    K.same(slot_state(K, st, d, SRC, 72), ref[1])
+    K.same(slot_state(K, st, d, 0, 72), ref[1])
 
 
 # ---- 10: n-best sampling is a fork and four seeds --------------------------------------------------------------------------------------------------------
@@ -345,8 +344,8 @@ def test_refusals_change_nothing():
         def unchanged():
             if paged:
                 assert _tables(st) == before
-            _same(_slot_state(Gqa, st, d, SRC, 40), want)
-            _same(_slot_state(Gqa, st, d, 0, 20), want0)
+            Gqa.same(slot_state(Gqa, st, d, SRC, 40), want)
+            Gqa.same(slot_state(Gqa, st, d, 0, 20), want0)
 
         for src, dsts in bad:
             with pytest.raises(ValueError):
@@ -365,13 +364,13 @@ def test_refusals_change_nothing():
         unchanged()
         st.verify_multi([SRC], [[2, 3, 4]], [40])                 # pending: fork is refused with the other slot calls
         pending = _tables(st) if paged else None
-        _state_error(lambda: st.fork_slot(SRC, [0], 40), "pending")
+        state_error(lambda: st.fork_slot(SRC, [0], 40), "pending")
         if paged:
             assert _tables(st) == pending
         st.commit_multi([0])
         unchanged()
         if not paged:
-            _state_error(lambda: st.slot_page_ids(0), "flat")
+            state_error(lambda: st.slot_page_ids(0), "flat")
 
 
 # ---- 11b: a fork whose source page still waits for its own copy ------------------------------------------------------------------------------------------
@@ -402,9 +401,9 @@ def test_fork_out_of_a_page_whose_copy_is_still_queued(fp8):
         for a, b in zip(layer, ref_layer):
             assert np.array_equal(a[:40], b) and not a[40:].any()
     _steps(st, [3], [first], [40], [ref], 4)
-    Mla.same(_slot_state(Mla, st, d, 3, 44), ref[1])
-    Mla.same(_slot_state(Mla, st, d, 0, 70), whole)             # slot 0 holds the whole prompt, page 0 with the rows of page 3
-    Mla.same(_slot_state(Mla, st, d, SRC, 70), whole)
+    Mla.same(slot_state(Mla, st, d, 3, 44), ref[1])
+    Mla.same(slot_state(Mla, st, d, 0, 70), whole)             # slot 0 holds the whole prompt, page 0 with the rows of page 3
+    Mla.same(slot_state(Mla, st, d, SRC, 70), whole)
 
 
 # ---- 11c: the copy kernel at every split, on one pool ----------------------------------------------------------------------------------------------------
@@ -442,7 +441,7 @@ def test_production_width_fork_in_pages_of_64():
     st, eng, orc, keep, d = build(seed=23, dims=(2048, 512, 72, 10, 512, 512), hd=256, nh=16, kv_max=160, kinds=["la", "gqa"])
     rng = np.random.default_rng(81)
     prompt, firsts = _toks(rng, d, 126), _toks(rng, d, 3)
-    refs = [seq._reference(st, d, prompt, f, 4) for f in firsts]
+    refs = [Gqa.reference(st, d, prompt, f, 4) for f in firsts]
     st.create_slots(3, 150, page_tokens=64, n_pages=7)
     st.prefill_slot(1, prompt, chunk=50)
     st.fork_slot(1, [0, 2], 126)
@@ -450,4 +449,4 @@ def test_production_width_fork_in_pages_of_64():
     toks, pos = _steps(st, [1, 0, 2], firsts, [126] * 3, refs, 4)
     assert st.slot_pages() == dict(page_tokens=64, n_pages=7, free=0, per_slot=[3, 3, 3])
     for i, (_, snap) in enumerate(refs):
-        _same(_slot_state(Gqa, st, d, [1, 0, 2][i], 130), snap)
+        Gqa.same(slot_state(Gqa, st, d, [1, 0, 2][i], 130), snap)

@@ -7,13 +7,10 @@ query path, a ragged last head group included.  There is no tolerance in this fi
 The reference is never the new path: it is the same call with the option off on equally filled slots and, in test 1, also the store's own decode_step on each
 sequence alone (computed once per geometry and shared).  Every comparison is on ids and u32 / stored-row bit patterns.  Every test sets
 "multi_mla_exact_split_min" to 1, so these small caches take the split."""
-import functools
-
 import numpy as np
 import pytest
 
-import tests.test_multi_mla_gpu as MM
-from tests.test_multi_paged_gpu import Mla, _slot_state, _state_error
+from tests.slots import Gqa, Mla, bits as _bits, cached, equal, fill_upto, off_on, options_reset, pages as _pages, slot_state, state_error, store_cache
 
 pytestmark = pytest.mark.gpu
 U = np.uint32
@@ -47,54 +44,24 @@ _stores = []
 ALL_OPTS = (OPT, "multi_extend_mla_exact_mfma", "multi_extend_mla_flash", "multi_mla_fast")
 
 
-@pytest.fixture(autouse=True)
-def options_off_afterwards():
-    yield
-    for st in _stores:
-        for o in ALL_OPTS:
-            st.set_option(o, 0)
-        st.set_option(MIN, 1)
-        st.set_attention_mode(False)
+options_off_afterwards = options_reset(_stores, ALL_OPTS + ((MIN, 1),))
 
 
-def _bits(x):
-    return np.ascontiguousarray(x).view(U).copy()
-
-
-def _pages(n, pt):
-    return (n + pt - 1) // pt
-
-
+@store_cache(_stores, MIN)
 def _model(klr, nh, lora, fp8, kv_max=KV_MAX):
-    return _model_c(klr, nh, lora, fp8, kv_max)      # one cache entry however the call spells kv_max
+    """one store per geometry, built once and shared (one cache entry however the call spells kv_max)"""
+    return Mla.build(fp8, seed=3, klr=klr, nh=nh, lora=lora, kv_max=kv_max)
 
 
-@functools.lru_cache(maxsize=None)
-def _model_c(klr, nh, lora, fp8, kv_max):
-    """one store per geometry, built once and shared"""
-    st, eng, keep, d = MM._build(fp8, seed=3, klr=klr, nh=nh, lora=lora, kv_max=kv_max)
-    st.set_option(MIN, 1)
-    _stores.append(st)
-    return st, (eng, keep), d
-
-
+@cached
 def _seq(klr, nh, lora, fp8, kv_max=KV_MAX):
-    return _seq_c(klr, nh, lora, fp8, kv_max)      # one cache entry however the call spells kv_max
-
-
-@functools.lru_cache(maxsize=None)
-def _seq_c(klr, nh, lora, fp8, kv_max):
     """the one token sequence of a geometry: row p of every test consumes token p behind the prefix [0, p)"""
     d = _model(klr, nh, lora, fp8, kv_max)[2]
     return tuple(int(x) for x in np.random.default_rng(klr + nh + kv_max).integers(0, d["V"], kv_max))
 
 
+@cached
 def _single(klr, nh, lora, fp8, kv_max=KV_MAX):
-    return _single_c(klr, nh, lora, fp8, kv_max)      # one cache entry however the call spells kv_max
-
-
-@functools.lru_cache(maxsize=None)
-def _single_c(klr, nh, lora, fp8, kv_max):
     """the single-sequence reference, computed once and never modified: the sequence by the store's own exact prompt pass, the token at every position of POS by
     decode_step -> {position: (logits bits, greedy id)}, and the latent / rope-key rows of the whole sequence"""
     st, _, d = _model(klr, nh, lora, fp8, kv_max)
@@ -106,57 +73,16 @@ def _single_c(klr, nh, lora, fp8, kv_max):
         st.decode_step(seq[p], p)
         out[p] = (_bits(st.read_logits()), st.last_token())
         at = p + 1
-    return out, MM._snap(st, d, kv_max)
-
-
-def _fill(st, d, seq, want):
-    """want = [(slot, n)]: the first n tokens of seq, by the exact prompt pass on the store's own sequence, into the slot (one pass serves every n)"""
-    st.reset_decode_state(d["kv_max"])
-    top = max(n for _, n in want)
-    if top:
-        st.prefill(list(seq[:top]), 0)
-    for s, n in want:
-        st.save_slot(s, n)
-
-
-def _state(st, d, slot, upto):
-    return _slot_state(Mla, st, d, slot, upto)
-
-
-def _upto(snap, n):
-    return [(a[:n], b[:n]) for a, b in snap]
-
-
-def _equal(a, b, where=""):
-    """two results (ids, logits, slot states) of one scenario: bit for bit"""
-    assert [int(x) for x in a[0]] == [int(x) for x in b[0]], ("ids", where)
-    assert np.array_equal(_bits(a[1]), _bits(b[1])), ("logits", where)
-    assert len(a[2]) == len(b[2])
-    for x, y in zip(a[2], b[2]):
-        MM._same(x, y)
-
-
-def _off_on(st, scenario, **other):
-    """scenario(st) -> (ids, logits, states) on slots it creates and fills itself, once with the option off and once with it on; `other` options stay set for both"""
-    out = []
-    for on in (0, 1):
-        for o, v in other.items():
-            st.set_option(o, v)
-        st.set_option(OPT, on)
-        out.append(scenario(st))
-        st.set_option(OPT, 0)
-        for o in other:
-            st.set_option(o, 0)
-    return out
+    return out, Mla.snap(st, d, kv_max)
 
 
 def _steps(st, d, seq, pos, n_slots=16, kv_max=KV_MAX, **slots_kw):
     """one step_multi: row i consumes token pos[i] of seq at position pos[i] in slot SLOTS[i] -> (ids, logits, states)"""
     st.create_slots(n_slots, kv_max, **slots_kw)
     slots = SLOTS[:len(pos)]
-    _fill(st, d, seq, list(zip(slots, pos)))
+    fill_upto(st, d, seq, list(zip(slots, pos)))
     ids, lg = st.step_multi(slots, [seq[p] for p in pos], list(pos), logits=True)
-    return ids, lg, [_state(st, d, s, p + 1) for s, p in zip(slots, pos)]
+    return ids, lg, [slot_state(Mla, st, d, s, p + 1) for s, p in zip(slots, pos)]
 
 
 # ---- 1: on == off == decode_step on each sequence alone ----------------------------------------------------------------------------------------------------
@@ -174,12 +100,12 @@ def test_step_multi_equals_option_off_and_decode_step(key, kv_max):
         took.append(st.multi_path_counts()["mla_xs_split"])
         return out
 
-    off, on = _off_on(st, counted)
+    off, on = off_on(st, OPT, counted)
     assert took == [0, 1], ("mla_xs_split", took)
-    _equal(on, off)
+    equal(Mla, on, off)
     for i, p in enumerate(pos):
         assert np.array_equal(_bits(on[1][i]), single[p][0]) and int(on[0][i]) == single[p][1], ("decode_step", p)
-        MM._same(on[2][i], _upto(snap, p + 1))
+        Mla.same(on[2][i], Mla.upto(snap, p + 1))
 
 
 # ---- 2: mixed passes through extend_multi -------------------------------------------------------------------------------------------------------------------
@@ -204,14 +130,14 @@ def test_mixed_passes_through_extend_multi(key, other):
         for rows in (MIXED, RUNS_ONLY, UNITS_ONLY):
             slots = SLOTS[at:at + len(rows)]
             at += len(rows)
-            _fill(st, d, seq, [(s, p) for s, (p, _) in zip(slots, rows)])
+            fill_upto(st, d, seq, [(s, p) for s, (p, _) in zip(slots, rows)])
             i, lg = st.extend_multi(slots, [list(seq[p:p + c]) for p, c in rows], [p for p, _ in rows], logits=True)
             ids += list(i); lgs.append(lg)
-            states += [_state(st, d, s, p + c) for s, (p, c) in zip(slots, rows)]
+            states += [slot_state(Mla, st, d, s, p + c) for s, (p, c) in zip(slots, rows)]
         return ids, np.concatenate(lgs), states
 
-    off, on = _off_on(st, scenario, **({other: 1} if other else {}))
-    _equal(on, off, other)
+    off, on = off_on(st, OPT, scenario, **({other: 1} if other else {}))
+    equal(Mla, on, off, other)
 
 
 # ---- 3: verify ----------------------------------------------------------------------------------------------------------------------------------------------
@@ -229,7 +155,7 @@ def test_verify_and_commit(key, sample):
     def scenario(st):
         st.create_slots(16, KV_MAX)
         slots = SLOTS[:len(VERIFY_POS)]
-        _fill(st, d, seq, list(zip(slots, VERIFY_POS)))
+        fill_upto(st, d, seq, list(zip(slots, VERIFY_POS)))
         if sample:
             for i, s in enumerate(slots):
                 st.set_slot_sampler(s, seq[VERIFY_POS[i]], 0.8, 40, 0.95, 0.5, 100 + i)
@@ -249,10 +175,10 @@ def test_verify_and_commit(key, sample):
             g2, nm2 = verify(slots, [list(seq[p:p + 3]) for p in VERIFY_POS], VERIFY_POS)
             ids += [x for row, m in zip(g2, nm2) for x in row[:m + 1]] + list(nm2)
         st.commit_multi(keep)
-        return ids, np.zeros(1, np.float32), [_state(st, d, s, p + k) for s, p, k in zip(slots, VERIFY_POS, keep)]
+        return ids, np.zeros(1, np.float32), [slot_state(Mla, st, d, s, p + k) for s, p, k in zip(slots, VERIFY_POS, keep)]
 
-    off, on = _off_on(st, scenario)
-    _equal(on, off, "verify + commit")
+    off, on = off_on(st, OPT, scenario)
+    equal(Mla, on, off, "verify + commit")
 
 
 # ---- 4: generation ------------------------------------------------------------------------------------------------------------------------------------------
@@ -268,16 +194,16 @@ def test_generate_multi_across_a_tile_edge(key, lookup):
     def scenario(st):
         st.create_slots(16, KV_MAX)
         slots = SLOTS[:len(starts)]
-        _fill(st, d, seq, list(zip(slots, starts)))
+        fill_upto(st, d, seq, list(zip(slots, starts)))
         firsts = [seq[p] for p in starts]
         if lookup:
             toks = st.generate_multi_lookup(slots, firsts, starts, 8, contexts=[list(seq[:p + 1]) for p in starts])
         else:
             toks = st.generate_multi(slots, firsts, starts, 8)
-        return [x for row in toks for x in row], np.zeros(1, np.float32), [_state(st, d, s, p + 8) for s, p in zip(slots, starts)]
+        return [x for row in toks for x in row], np.zeros(1, np.float32), [slot_state(Mla, st, d, s, p + 8) for s, p in zip(slots, starts)]
 
-    off, on = _off_on(st, scenario)
-    _equal(on, off, "generate")
+    off, on = off_on(st, OPT, scenario)
+    equal(Mla, on, off, "generate")
 
 
 # ---- 5: paged slots -----------------------------------------------------------------------------------------------------------------------------------------
@@ -309,21 +235,21 @@ def test_paged_and_forked_slots(key, page_tokens):
         ids, lg = st.step_multi([slot_of[p] for p in POS], [seq[p] for p in POS], list(POS), logits=True)
         used = [int(x) for x in st.slot_page_ids(slot_of[far])[0][:_pages(far + 1, pt)]]
         assert min(used) >= 0 and used != list(range(used[0], used[0] + len(used))), ("the long slot's pages are consecutive", used)
-        states = [_state(st, d, slot_of[p], p + 1) for p in POS]
+        states = [slot_state(Mla, st, d, slot_of[p], p + 1) for p in POS]
         for p in others:
             st.trim_slot(slot_of[p], 0)
         st.trim_slot(dst, 0)
         st.fork_slot(slot_of[far], [dst], fork_at)
         ids2, lg2 = st.step_multi([dst], [seq[fork_at]], [fork_at], logits=True)
-        states += [_state(st, d, dst, fork_at + 1), _state(st, d, slot_of[far], far + 1)]
+        states += [slot_state(Mla, st, d, dst, fork_at + 1), slot_state(Mla, st, d, slot_of[far], far + 1)]
         return list(ids) + list(ids2), np.concatenate([lg, lg2]), states
 
-    off, on = _off_on(st, scenario)
-    _equal(on, off, ("paged", pt))
+    off, on = off_on(st, OPT, scenario)
+    equal(Mla, on, off, ("paged", pt))
     for i, p in enumerate(POS):
         assert np.array_equal(_bits(on[1][i]), single[p][0]), ("decode_step", p)
-    MM._same(on[2][-1], _upto(snap, far + 1))              # the fork's src: untouched
-    MM._same(on[2][-2], _upto(snap, fork_at + 1))          # the dst: the same sequence, one row behind the fork point
+    Mla.same(on[2][-1], Mla.upto(snap, far + 1))              # the fork's src: untouched
+    Mla.same(on[2][-2], Mla.upto(snap, fork_at + 1))          # the dst: the same sequence, one row behind the fork point
 
 
 # ---- 6: stale scratch ---------------------------------------------------------------------------------------------------------------------------------------
@@ -337,13 +263,13 @@ def test_short_call_after_a_long_one(key):
     def scenario(st):
         st.create_slots(16, KV_MAX)
         long_pos, short_pos = [KV_MAX - 1, FAR], [5, 40, 31]
-        _fill(st, d, seq, list(zip([2, 4, 1, 6, 3], long_pos + short_pos)))
+        fill_upto(st, d, seq, list(zip([2, 4, 1, 6, 3], long_pos + short_pos)))
         st.step_multi([2, 4], [seq[p] for p in long_pos], long_pos)
         ids, lg = st.step_multi([1, 6, 3], [seq[p] for p in short_pos], short_pos, logits=True)
-        return ids, lg, [_state(st, d, s, p + 1) for s, p in zip([1, 6, 3], short_pos)]
+        return ids, lg, [slot_state(Mla, st, d, s, p + 1) for s, p in zip([1, 6, 3], short_pos)]
 
-    off, on = _off_on(st, scenario)
-    _equal(on, off, "short after long")
+    off, on = off_on(st, OPT, scenario)
+    equal(Mla, on, off, "short after long")
 
 
 # ---- 7: the threshold ---------------------------------------------------------------------------------------------------------------------------------------
@@ -363,9 +289,9 @@ def test_threshold_above_at_and_one():
     st.set_option(MIN, 1)
     one = _steps(st, d, seq, pos)
     st.set_option(OPT, 0)
-    _equal(above, off, "above")
-    _equal(at, off, "at")
-    _equal(one, off, "1")
+    equal(Mla, above, off, "above")
+    equal(Mla, at, off, "at")
+    equal(Mla, one, off, "1")
 
 
 def test_minimum_below_one_is_a_value_error():
@@ -402,15 +328,14 @@ def _refused_then_fine(st, d, state, arm, refuse, clear):
 
 def test_store_without_mla_layers_is_refused():
     from tests.test_decode_gpu import build
-    from tests.test_speculative_gpu import _snap
     st, eng, orc, keep, d = build(seed=3, kv_max=32)                        # linear attention + GQA
     _stores.append(st)
 
     def state(slot, upto):
         st.reset_decode_state(d["kv_max"]); st.load_slot(slot, upto)
-        return [tuple(x for x in row if isinstance(x, np.ndarray)) for row in _snap(st, d, upto)]
+        return [tuple(x for x in row if isinstance(x, np.ndarray)) for row in Gqa.snap(st, d, upto)]
 
-    _refused_then_fine(st, d, state, lambda: st.set_option(OPT, 1), lambda call: _state_error(call, OPT, "covers MLA layers only: this store has none"),
+    _refused_then_fine(st, d, state, lambda: st.set_option(OPT, 1), lambda call: state_error(call, OPT, "covers MLA layers only: this store has none"),
                        lambda: st.set_option(OPT, 0))
 
 
@@ -420,7 +345,7 @@ def test_mode_bits_stay_refused_with_their_old_text():
     def arm():
         st.set_option(OPT, 1); st.set_attention_mode(True)
 
-    _refused_then_fine(st, d, lambda s, p: _state(st, d, s, p), arm, lambda call: _state_error(call, "exact-mode only"), lambda: st.set_attention_mode(False))      # the option itself stays set
+    _refused_then_fine(st, d, lambda s, p: slot_state(Mla, st, d, s, p), arm, lambda call: state_error(call, "exact-mode only"), lambda: st.set_attention_mode(False))      # the option itself stays set
     st.set_option(OPT, 0)
 
 
@@ -435,6 +360,6 @@ def test_long_slots_under_multi_mla_fast(paged):
     kw = dict(page_tokens=64, n_pages=sum(_pages(p + 1, 64) for p in pos) + 2) if paged else {}
     scenario = lambda st: _steps(st, d, seq, pos, n_slots=16, kv_max=LONG_KV, **kw)
     exact = scenario(st)
-    fd, both = _off_on(st, scenario, multi_mla_fast=1)
-    _equal(both, fd, "multi_mla_fast")
+    fd, both = off_on(st, OPT, scenario, multi_mla_fast=1)
+    equal(Mla, both, fd, "multi_mla_fast")
     assert any(not np.array_equal(_bits(fd[1][r]), _bits(exact[1][r])) for r in range(len(pos)))      # the flash-decode did run

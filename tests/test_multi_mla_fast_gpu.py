@@ -5,13 +5,11 @@ the latent and rope-key rows it appends, whatever rows share the launch, whateve
 FP16 and E4M3 caches.  Over shorter slots the step is the exact one, bit for bit.  Against the exact batched step the logits stay within the project's
 bound for this operator (docs/design/02-numerics.md section 2b, tests/test_attn_fast_gpu.py: max |on - off| <= 3e-3 max |off| with FP16 caches, 5e-3 with
 E4M3).  The reference everywhere is the single-sequence fast step or the option-off step; the option-on path is never compared with itself."""
-import functools
-
 import numpy as np
 import pytest
 
 import tests.test_multi_mla_gpu as MM
-from tests.test_multi_paged_gpu import Mla, _slot_state, _state_error, _toks
+from tests.slots import Gqa, Mla, bits as _bits, cached, options_reset, pages as _pages, slot_state, state_error, toks as _toks
 
 pytestmark = pytest.mark.gpu
 F = np.float32
@@ -30,25 +28,13 @@ N_STEPS = 3
 _stores = []
 
 
-@pytest.fixture(autouse=True)
-def options_off_afterwards():
-    yield
-    for st in _stores:
-        st.set_option(OPT, 0); st.set_option("multi_attn_fast", 0); st.set_option("multi_attn_fast_paged", 0); st.set_attention_mode(False)
-
-
-def _bits(lg):
-    return lg.view(U).copy()
-
-
-def _pages(n, pt):
-    return (n + pt - 1) // pt
+options_off_afterwards = options_reset(_stores, (OPT, "multi_attn_fast", "multi_attn_fast_paged"))
 
 
 def _start(st, d, prompt):
     """the store's own sequence = prompt, by the EXACT prompt pass (zero state first)"""
     st.set_attention_mode(False)
-    MM._start(st, d, prompt)
+    Mla.start(st, d, prompt)
 
 
 def _fast_steps(st, d, prompt, tokens):
@@ -60,7 +46,7 @@ def _fast_steps(st, d, prompt, tokens):
         for tok in tokens:
             st.decode_step(tok, pos)
             out.append((_bits(st.read_logits()), st.last_token())); pos += 1
-        snap = MM._snap(st, d, pos)
+        snap = Mla.snap(st, d, pos)
     finally:
         st.set_attention_mode(False)
     return out, snap
@@ -76,7 +62,7 @@ def _fast_reference(st, d, prompt, first, n_steps):
             st.decode_step(tok, pos)
             out.append((_bits(st.read_logits()), st.last_token()))
             tok = out[-1][1]; pos += 1
-        snap = MM._snap(st, d, pos)
+        snap = Mla.snap(st, d, pos)
     finally:
         st.set_attention_mode(False)
     return out, snap
@@ -89,16 +75,16 @@ def _fill_slots(st, d, prompts, slot_lists):
             st.save_slot(s, len(p))
 
 
-@functools.lru_cache(maxsize=None)
+@cached
 def _model(klr, nh, lora, fp8, kv_max=KV_MAX, lens=LENS, n_steps=N_STEPS):
     """one store per geometry, its sequences and their single-sequence fast references: computed once, shared by the tests, never modified"""
-    st, eng, keep, d = MM._build(fp8, seed=3, klr=klr, nh=nh, lora=lora, kv_max=kv_max)
+    st, keep, d = Mla.build(fp8, seed=3, klr=klr, nh=nh, lora=lora, kv_max=kv_max)
     _stores.append(st)
     rng = np.random.default_rng(klr + nh)
-    prompts = [MM._prompt(rng, d, n) for n in lens]
+    prompts = [_toks(rng, d, n) for n in lens]
     firsts = [int(x) for x in rng.integers(0, d["V"], len(prompts))]
     refs = [_fast_reference(st, d, p, f, n_steps) for p, f in zip(prompts, firsts)]
-    return st, (eng, keep), d, prompts, firsts, refs
+    return st, keep, d, prompts, firsts, refs
 
 
 def _steps_against_refs(st, slots, firsts, refs, lens, n_steps=N_STEPS):
@@ -124,7 +110,7 @@ def test_row_equals_single_sequence_fast_step(key, slot_seq):
     pos = _steps_against_refs(st, slots, firsts, refs, LENS)
     st.set_option(OPT, 0)
     for i, (_, snap) in enumerate(refs):
-        MM._same(_slot_state(Mla, st, d, slots[i], pos[i]), snap)
+        Mla.same(slot_state(Mla, st, d, slots[i], pos[i]), snap)
 
 
 # ---- 2: batch composition -----------------------------------------------------------------------------------------------------------------------------------
@@ -186,7 +172,7 @@ def test_paged_row_equals_single_sequence_fast_step(key, page_tokens):
     pos = _steps_against_refs(st, slots, firsts, refs, LENS)
     st.set_option(OPT, 0)
     for i, (_, snap) in enumerate(refs):
-        MM._same(_slot_state(Mla, st, d, slots[i], pos[i]), snap)
+        Mla.same(slot_state(Mla, st, d, slots[i], pos[i]), snap)
 
 
 def _fork_run(st, d, paged, pt, prompts, firsts, toks, new):
@@ -214,7 +200,7 @@ def _fork_run(st, d, paged, pt, prompts, firsts, toks, new):
     ids, lg = st.step_multi([SRC] + DSTS, [firsts[LONG], toks[2], toks[3]], [650, REWIND + len(new), FORK + 1], logits=True)
     out.append((list(ids), _bits(lg)))
     st.set_option(OPT, 0)
-    return out, [_slot_state(Mla, st, d, s, n) for s, n in ((SRC, 651), (DSTS[0], REWIND + len(new) + 1), (DSTS[1], FORK + 2))]
+    return out, [slot_state(Mla, st, d, s, n) for s, n in ((SRC, 651), (DSTS[0], REWIND + len(new) + 1), (DSTS[1], FORK + 2))]
 
 
 @pytest.mark.parametrize("page_tokens", [32, 64])
@@ -230,7 +216,7 @@ def test_forked_slots(page_tokens):
     for (ids, lg), (fids, flg) in zip(got, flat):
         assert ids == fids and np.array_equal(lg, flg)
     for a, b in zip(states, flat_states):
-        MM._same(a, b)
+        Mla.same(a, b)
     assert np.array_equal(got[2][1][0], refs[LONG][0][0][0]) and got[2][0][0] == refs[LONG][0][0][1]
 
 
@@ -280,13 +266,13 @@ def test_pool_one_page_short_fails_whole():
     _fill_slots(st, d, [prompts[i32], prompts[i64]], [[0], [1]])
     before = st.slot_pages()
     assert before["free"] == 1
-    want = [_slot_state(Mla, st, d, 0, 32), _slot_state(Mla, st, d, 1, 64)]
+    want = [slot_state(Mla, st, d, 0, 32), slot_state(Mla, st, d, 1, 64)]
     st.set_option(OPT, 1)
-    _state_error(lambda: st.step_multi([0, 1], [firsts[i32], firsts[i64]], [32, 64]), "row 1", "slot 1")
-    _state_error(lambda: st.extend_multi([0, 1], [[1, 2], [3, 4]], [32, 64]), "row 1", "slot 1")
+    state_error(lambda: st.step_multi([0, 1], [firsts[i32], firsts[i64]], [32, 64]), "row 1", "slot 1")
+    state_error(lambda: st.extend_multi([0, 1], [[1, 2], [3, 4]], [32, 64]), "row 1", "slot 1")
     assert st.slot_pages() == before
     st.set_option(OPT, 0)
-    MM._same(_slot_state(Mla, st, d, 0, 32), want[0]); MM._same(_slot_state(Mla, st, d, 1, 64), want[1])
+    Mla.same(slot_state(Mla, st, d, 0, 32), want[0]); Mla.same(slot_state(Mla, st, d, 1, 64), want[1])
     st.set_option(OPT, 1)
     ids, lg = st.step_multi([1], [firsts[i64]], [64], logits=True)
     assert np.array_equal(lg[0].view(U), refs[i64][0][0][0]) and ids[0] == refs[i64][0][0][1]
@@ -314,7 +300,7 @@ def test_every_entry_point_equals_that_many_fast_steps(page_tokens):
         st.set_attention_mode(True)
         try:
             out = st.generate_batch(firsts[q], LENS[q], max_tokens)
-            return out, MM._snap(st, d, LENS[q] + len(out))
+            return out, Mla.snap(st, d, LENS[q] + len(out))
         finally:
             st.set_attention_mode(False)
 
@@ -334,11 +320,11 @@ def test_every_entry_point_equals_that_many_fast_steps(page_tokens):
     st.set_option(OPT, 0)
     ends = [LENS[q] + len(run) for q, run in zip(seqs, runs)]
     for r, (_, snap) in enumerate(want):
-        MM._same(_slot_state(Mla, st, d, r, ends[r]), snap)
-    MM._same(_slot_state(Mla, st, d, 4, 100), want_fresh[1])
-    MM._same(_slot_state(Mla, st, d, 3, 302), want_v[1])
+        Mla.same(slot_state(Mla, st, d, r, ends[r]), snap)
+    Mla.same(slot_state(Mla, st, d, 4, 100), want_fresh[1])
+    Mla.same(slot_state(Mla, st, d, 3, 302), want_v[1])
     for s, q, (T, snap) in zip((5, 6), (LONG, i63), want_g):
-        MM._same(_slot_state(Mla, st, d, s, LENS[q] + len(T)), snap)
+        Mla.same(slot_state(Mla, st, d, s, LENS[q] + len(T)), snap)
     # the lookup loop: the same tokens as the plain loop, from fresh copies of the two slots
     _fill_slots(st, d, [prompts[LONG], prompts[i63]], [[5], [6]])
     st.set_option(OPT, 1)
@@ -346,7 +332,7 @@ def test_every_entry_point_equals_that_many_fast_steps(page_tokens):
     assert out == [T for T, _ in want_g]
     st.set_option(OPT, 0)
     for s, q, (T, snap) in zip((5, 6), (LONG, i63), want_g):
-        MM._same(_slot_state(Mla, st, d, s, LENS[q] + len(T)), snap)
+        Mla.same(slot_state(Mla, st, d, s, LENS[q] + len(T)), snap)
 
 
 # ---- 5: chunks of 128 positions -----------------------------------------------------------------------------------------------------------------------------
@@ -365,7 +351,7 @@ def test_chunk_of_128_positions(page_tokens):
     pos = _steps_against_refs(st, [2, 0], firsts, refs, lens, 2)
     st.set_option(OPT, 0)
     for i, s in enumerate((2, 0)):
-        MM._same(_slot_state(Mla, st, d, s, pos[i]), refs[i][1])
+        Mla.same(slot_state(Mla, st, d, s, pos[i]), refs[i][1])
 
 
 # ---- 6: short slots -----------------------------------------------------------------------------------------------------------------------------------------
@@ -390,7 +376,7 @@ def test_short_slots_keep_the_exact_step(page_tokens):
         assert ids0 == ids1 and np.array_equal(lg0, lg1)
     st.set_option(OPT, 0)
     for j, i in enumerate(short):
-        MM._same(_slot_state(Mla, st, d, j, LENS[i] + N_STEPS), _slot_state(Mla, st, d, n + j, LENS[i] + N_STEPS))
+        Mla.same(slot_state(Mla, st, d, j, LENS[i] + N_STEPS), slot_state(Mla, st, d, n + j, LENS[i] + N_STEPS))
 
 
 # ---- 7: the stated tolerance against the exact batched step -------------------------------------------------------------------------------------------------
@@ -433,7 +419,6 @@ def _calls(st, s, pos):
 
 def test_a_store_without_mla_layers_is_refused():
     """an option that silently does nothing is a trap: on a GQA + linear-attention store every batched call raises KR_ERR_STATE naming the option"""
-    from tests.test_multi_paged_gpu import Gqa
     st, keep, d = Gqa.build(False, seed=3, kv_max=48)
     _stores.append(st)
     rng = np.random.default_rng(3)
@@ -441,17 +426,17 @@ def test_a_store_without_mla_layers_is_refused():
     Gqa.start(st, d, prompt)
     st.create_slots(2, 40, page_tokens=32, n_pages=4)
     st.save_slot(1, 20)
-    want = _slot_state(Gqa, st, d, 1, 20)
+    want = slot_state(Gqa, st, d, 1, 20)
     before = st.slot_pages()
     st.decode_step(5, 20)
     want_lg, want_tok = _bits(st.read_logits()), st.last_token()
     st.set_option(OPT, 1)
     for call in _calls(st, 1, 20):
-        _state_error(call, OPT)
+        state_error(call, OPT)
         assert np.array_equal(st.read_logits().view(U), want_lg) and st.last_token() == want_tok
         assert st.slot_pages() == before
     st.set_option(OPT, 0)
-    Gqa.same(_slot_state(Gqa, st, d, 1, 20), want)
+    Gqa.same(slot_state(Gqa, st, d, 1, 20), want)
     st.step_multi([1], [2], [20])
 
 
@@ -460,11 +445,11 @@ def test_more_than_64_heads_are_refused():
     st, eng, keep, d = MM._build(kv_max=48, nh=65)
     _stores.append(st)
     rng = np.random.default_rng(3)
-    prompt = MM._prompt(rng, d, 20)
-    ref, _ = MM._reference(st, d, prompt, 2, 1)
+    prompt = _toks(rng, d, 20)
+    ref, _ = Mla.reference(st, d, prompt, 2, 1)
     st.create_slots(2, 40, page_tokens=32, n_pages=4)
     MM._fill_slots(st, d, [prompt], [[1]])
-    want = _slot_state(Mla, st, d, 1, 20)
+    want = slot_state(Mla, st, d, 1, 20)
     before = st.slot_pages()
     st.decode_step(5, 20)
     want_lg, want_tok = _bits(st.read_logits()), st.last_token()
@@ -475,7 +460,7 @@ def test_more_than_64_heads_are_refused():
         assert np.array_equal(st.read_logits().view(U), want_lg) and st.last_token() == want_tok
         assert st.slot_pages() == before
     st.set_option(OPT, 0)
-    MM._same(_slot_state(Mla, st, d, 1, 20), want)
+    Mla.same(slot_state(Mla, st, d, 1, 20), want)
     ids, lg = st.step_multi([1], [2], [20], logits=True)
     assert np.array_equal(lg[0].view(U), ref[0][0]) and ids[0] == ref[0][1]
 
@@ -490,7 +475,7 @@ def test_other_refusals_stay_and_the_option_is_isolated():
     exact_lg, exact_tok = _bits(st.read_logits()), st.last_token()
     st.create_slots(2, KV_MAX, page_tokens=32, n_pages=2 * _pages(310, 32))
     _fill_slots(st, d, [prompts[i]], [[0, 1]])
-    want = _slot_state(Mla, st, d, 0, 300)
+    want = slot_state(Mla, st, d, 0, 300)
     before = st.slot_pages()
     st.decode_step(9, 300)
     want_lg, want_tok = _bits(st.read_logits()), st.last_token()
@@ -503,18 +488,18 @@ def test_other_refusals_stay_and_the_option_is_isolated():
     for name in ("multi_attn_fast", "multi_attn_fast_paged"):
         st.set_option(name, 1)
         for call in _calls(st, 0, 300):
-            _state_error(call, '"%s" option covers GQA layers only' % name)
+            state_error(call, '"%s" option covers GQA layers only' % name)
             unchanged()
         st.set_option(name, 0)
     for bits in [dict(fast=True), dict(fast=False, gemm_fast=True), dict(fast=False, decode_fast=True)]:
         st.set_attention_mode(**bits)
         for call in _calls(st, 0, 300):
-            _state_error(call, "exact-mode only")
+            state_error(call, "exact-mode only")
             unchanged()
         st.set_attention_mode(False)
     st.set_option(OPT, 0)
     for s in (0, 1):
-        MM._same(_slot_state(Mla, st, d, s, 300), want)
+        Mla.same(slot_state(Mla, st, d, s, 300), want)
     st.set_option(OPT, 1)
     # the option touches the batched calls only: the store's own exact step and prompt pass keep their bits with it set
     _start(st, d, prompts[i])

@@ -6,7 +6,7 @@ tests/test_mla_gpu.py holds to the CPU oracle bit for bit; the batched step is n
 import numpy as np
 import pytest
 
-from tests.test_mla_gpu import build
+from tests.slots import Mla, toks as _toks
 
 pytestmark = pytest.mark.gpu
 F = np.float32
@@ -16,56 +16,13 @@ CFGS = [dict(), dict(lora=True, seed=2), dict(klr=256, nh=3, seed=4)]
 
 
 def _build(fp8=False, **cfg):
-    st, eng, orc, keep, d = build(**cfg)
-    d["fp8"] = fp8
-    if fp8:
-        st.set_kv_dtype(True)
+    st, (eng, keep), d = Mla.build(fp8, **cfg)
     return st, eng, keep, d
-
-
-def _prompt(rng, d, n):
-    return [int(x) for x in rng.integers(0, d["V"], n)]
-
-
-def _start(st, d, prompt):
-    """the store's own sequence = prompt (build leaves random caches: zero state first, then the prompt pass)"""
-    st.reset_decode_state(d["kv_max"])
-    if prompt:
-        st.prefill(prompt, 0)
-
-
-def _snap(st, d, pos):
-    """rows [0, pos) of the latent and the rope-key cache of every layer, as stored (uint16: FP16, uint8: E4M3)"""
-    t = np.uint8 if d["fp8"] else np.uint16
-    out = []
-    for li in range(d["nL"]):
-        ck = np.empty((d["kv_max"], d["klr"]), t); kp = np.empty((d["kv_max"], d["rd"]), t)
-        st.get_decode_state(li, ck, kp, None, None)
-        out.append((ck[:pos].copy(), kp[:pos].copy()))
-    return out
-
-
-def _same(got, want):
-    assert len(got) == len(want)
-    for li, ((ck, kp), (rck, rkp)) in enumerate(zip(got, want)):
-        assert np.array_equal(ck, rck), ("latent rows", li)
-        assert np.array_equal(kp, rkp), ("rope-key rows", li)
-
-
-def _reference(st, d, prompt, first, n_steps):
-    """decode_step alone: per step (logits bits, greedy id); then the caches after the steps"""
-    _start(st, d, prompt)
-    out, tok, pos = [], first, len(prompt)
-    for _ in range(n_steps):
-        st.decode_step(tok, pos)
-        out.append((st.read_logits().view(U).copy(), st.last_token()))
-        tok = out[-1][1]; pos += 1
-    return out, _snap(st, d, pos)
 
 
 def _fill_slots(st, d, prompts, slot_lists):
     for p, slots in zip(prompts, slot_lists):
-        _start(st, d, p)
+        Mla.start(st, d, p)
         for s in slots:
             st.save_slot(s, len(p))
 
@@ -86,18 +43,18 @@ def _steps_against_refs(st, d, refs, slots, firsts, pos, n_steps):
 def test_step_multi_equals_decode_step_alone(cfg, fp8):
     st, eng, keep, d = _build(fp8, kv_max=64, **cfg)
     rng = np.random.default_rng(5)
-    prompts = [_prompt(rng, d, n) for n in (1, 40, 7, 23, 12)] + [[]]      # the last slot starts at zero state, position 0
+    prompts = [_toks(rng, d, n) for n in (1, 40, 7, 23, 12)] + [[]]      # the last slot starts at zero state, position 0
     firsts = [int(x) for x in rng.integers(0, d["V"], len(prompts))]
-    refs = [_reference(st, d, p, f, 5) for p, f in zip(prompts, firsts)]
+    refs = [Mla.reference(st, d, p, f, 5) for p, f in zip(prompts, firsts)]
     st.create_slots(len(prompts) + 2, 60)
     slots = [3, 0, 6, 2, 5, 1]                                              # slot numbers need not follow the rows
     _fill_slots(st, d, prompts, [[s] for s in slots])
     toks, pos = _steps_against_refs(st, d, refs, slots, firsts, [len(p) for p in prompts], 4)
     for i, (ref, _) in enumerate(refs):
-        ref_after4 = _reference(st, d, prompts[i], firsts[i], 4)[1]
+        ref_after4 = Mla.reference(st, d, prompts[i], firsts[i], 4)[1]
         st.reset_decode_state(d["kv_max"])
         st.load_slot(slots[i], pos[i])
-        _same(_snap(st, d, pos[i]), ref_after4)
+        Mla.same(Mla.snap(st, d, pos[i]), ref_after4)
         st.decode_step(toks[i], pos[i])                                     # the store continues the sequence identically
         assert np.array_equal(st.read_logits().view(U), ref[4][0]) and st.last_token() == ref[4][1], i
 
@@ -107,9 +64,9 @@ def test_batch_sizes_and_row_order():
     st, eng, keep, d = _build(kv_max=48)
     rng = np.random.default_rng(9)
     n_seq = 64
-    prompts = [_prompt(rng, d, int(rng.integers(1, 9))) for _ in range(n_seq)]
+    prompts = [_toks(rng, d, int(rng.integers(1, 9))) for _ in range(n_seq)]
     firsts = [int(x) for x in rng.integers(0, d["V"], n_seq)]
-    refs = [_reference(st, d, p, f, 1)[0][0] for p, f in zip(prompts, firsts)]
+    refs = [Mla.reference(st, d, p, f, 1)[0][0] for p, f in zip(prompts, firsts)]
     batches = [1, 31, 32, 33, 64]
     perm = [int(x) for x in rng.permutation(64)]
     groups, base = [], 0
@@ -137,9 +94,9 @@ def test_long_caches(cfg, fp8, kv_max, lens, cap):
     slot capacity different from the store's kv_max_seq."""
     st, eng, keep, d = _build(fp8, kv_max=kv_max, **cfg)
     rng = np.random.default_rng(kv_max)
-    prompts = [_prompt(rng, d, n) for n in lens]
+    prompts = [_toks(rng, d, n) for n in lens]
     firsts = [int(x) for x in rng.integers(0, d["V"], 3)]
-    refs = [_reference(st, d, p, f, 2) for p, f in zip(prompts, firsts)]
+    refs = [Mla.reference(st, d, p, f, 2) for p, f in zip(prompts, firsts)]
     st.create_slots(3, cap)
     slots = [2, 0, 1]
     _fill_slots(st, d, prompts, [[s] for s in slots])
@@ -147,24 +104,24 @@ def test_long_caches(cfg, fp8, kv_max, lens, cap):
     for i, (_, snap) in enumerate(refs):
         st.reset_decode_state(kv_max)
         st.load_slot(slots[i], pos[i])
-        _same(_snap(st, d, pos[i]), snap)
+        Mla.same(Mla.snap(st, d, pos[i]), snap)
 
 
 def test_generate_multi_equals_generate_greedy():
     st, eng, keep, d = _build(kv_max=64)
     rng = np.random.default_rng(13)
-    prompts = [_prompt(rng, d, n) for n in (5, 17, 2, 30)]
+    prompts = [_toks(rng, d, n) for n in (5, 17, 2, 30)]
     firsts = [int(x) for x in rng.integers(0, d["V"], 4)]
     max_tokens = 9
     free = []
     for p, f in zip(prompts, firsts):
-        _start(st, d, p); free.append(st.generate_batch(f, len(p), max_tokens))
+        Mla.start(st, d, p); free.append(st.generate_batch(f, len(p), max_tokens))
     stop_ids = [free[0][2], free[2][5]]                                     # rows end at different steps; rows without them reach max_tokens
     ref_toks, ref_snaps = [], []
     for p, f in zip(prompts, firsts):
-        _start(st, d, p)
+        Mla.start(st, d, p)
         T = st.generate_batch(f, len(p), max_tokens, stop_ids=stop_ids)
-        ref_toks.append(T); ref_snaps.append(_snap(st, d, len(p) + len(T)))
+        ref_toks.append(T); ref_snaps.append(Mla.snap(st, d, len(p) + len(T)))
     assert len({len(T) for T in ref_toks}) > 1 and max(len(T) for T in ref_toks) == max_tokens
     st.create_slots(4, 64)
     slots = [1, 3, 0, 2]
@@ -174,24 +131,24 @@ def test_generate_multi_equals_generate_greedy():
     for i, p in enumerate(prompts):
         st.reset_decode_state(d["kv_max"])
         st.load_slot(slots[i], len(p) + len(out[i]))
-        _same(_snap(st, d, len(p) + len(out[i])), ref_snaps[i])
+        Mla.same(Mla.snap(st, d, len(p) + len(out[i])), ref_snaps[i])
 
 
 def test_generate_multi_sampled_equals_generate_batch():
     """the server defaults (temperature 0.6, top_k 50, top_p 0.95) with fixed seeds, plus one penalised-greedy row"""
     st, eng, keep, d = _build(kv_max=64)
     rng = np.random.default_rng(21)
-    prompts = [_prompt(rng, d, n) for n in (5, 17, 2, 30)]
+    prompts = [_toks(rng, d, n) for n in (5, 17, 2, 30)]
     firsts = [int(x) for x in rng.integers(0, d["V"], len(prompts))]
     params = [(0.6, 50, 0.95, 0.0), (0.6, 50, 0.95, 0.0), (0.0, 0, 1.0, 1.5), (0.6, 50, 0.95, 0.0)]
     seeds = [0x1234567, 0x9E3779B9, 77, 5]
     max_tokens = 9
     ref_toks, ref_snaps = [], []
     for i, p in enumerate(prompts):
-        _start(st, d, p)
+        Mla.start(st, d, p)
         T, K, P, PEN = params[i]
         out = st.generate_batch(firsts[i], len(p), max_tokens, T, K, P, (), PEN, rng_seed=seeds[i])
-        ref_toks.append(out); ref_snaps.append(_snap(st, d, len(p) + len(out)))
+        ref_toks.append(out); ref_snaps.append(Mla.snap(st, d, len(p) + len(out)))
     slots = [1, 3, 0, 2]
     st.create_slots(4, 64)
     _fill_slots(st, d, prompts, [[s] for s in slots])
@@ -202,7 +159,7 @@ def test_generate_multi_sampled_equals_generate_batch():
     for i, p in enumerate(prompts):
         st.reset_decode_state(d["kv_max"])
         st.load_slot(slots[i], len(p) + len(out[i]))
-        _same(_snap(st, d, len(p) + len(out[i])), ref_snaps[i])
+        Mla.same(Mla.snap(st, d, len(p) + len(out[i])), ref_snaps[i])
 
 
 @pytest.mark.parametrize("graph", [True, False])
@@ -210,12 +167,12 @@ def test_steps_leave_the_store_sequence_alone(graph):
     st, eng, keep, d = _build(kv_max=48)
     st.set_use_graph(graph)
     rng = np.random.default_rng(17)
-    prompt = _prompt(rng, d, 6)
-    toks = _prompt(rng, d, 5)
-    ref, _ = _reference(st, d, prompt, toks[0], 5)
+    prompt = _toks(rng, d, 6)
+    toks = _toks(rng, d, 5)
+    ref, _ = Mla.reference(st, d, prompt, toks[0], 5)
     st.create_slots(3, 48)
-    _fill_slots(st, d, [_prompt(rng, d, 3), _prompt(rng, d, 9)], [[0], [2]])
-    _start(st, d, prompt)
+    _fill_slots(st, d, [_toks(rng, d, 3), _toks(rng, d, 9)], [[0], [2]])
+    Mla.start(st, d, prompt)
     tok, pos, mpos = toks[0], len(prompt), [3, 9]
     for k in range(5):
         st.decode_step(tok, pos)
@@ -230,13 +187,13 @@ def test_steps_leave_the_store_sequence_alone(graph):
 def test_save_load_round_trip(fp8):
     st, eng, keep, d = _build(fp8, kv_max=40)
     st.fill_state_synthetic(d["kv_max"], seed=3)
-    want = _snap(st, d, 29)
+    want = Mla.snap(st, d, 29)
     esz = 1 if fp8 else 2
     assert st.create_slots(2, 36) == 2 * 36 * (d["klr"] + d["rd"]) * esz * d["nL"]      # bytes_out counts both halves of every MLA layer
     st.save_slot(1, 29)
     st.reset_decode_state(d["kv_max"])
     st.load_slot(1, 29)
-    _same(_snap(st, d, 29), want)
+    Mla.same(Mla.snap(st, d, 29), want)
 
 
 def test_refusals_change_nothing():
@@ -246,11 +203,11 @@ def test_refusals_change_nothing():
     st.create_slots(3, 24)
     st.fill_state_synthetic(d["kv_max"], seed=5)
     st.save_slot(1, 20)
-    want = _snap(st, d, 20)
+    want = Mla.snap(st, d, 20)
 
     def unchanged():
         st.reset_decode_state(d["kv_max"]); st.load_slot(1, 20)
-        _same(_snap(st, d, 20), want)
+        Mla.same(Mla.snap(st, d, 20), want)
 
     V = d["V"]
     bad_steps = [([1, 1], [2, 3], [20, 20]),      # a slot named twice
@@ -332,13 +289,13 @@ def test_v2lite_widths():
     """DeepSeek-V2-Lite widths: hidden 2048, 16 heads, kv_lora_rank 512, top-6 of 16"""
     st, eng, keep, d = _build(kv_max=160, dims=(2048, 512, 16, 6, 256, 512), nh=16, seed=9)
     rng = np.random.default_rng(2)
-    prompts = [_prompt(rng, d, n) for n in (90, 3, 41)]
+    prompts = [_toks(rng, d, n) for n in (90, 3, 41)]
     firsts = [int(x) for x in rng.integers(0, d["V"], 3)]
-    refs = [_reference(st, d, p, f, 2) for p, f in zip(prompts, firsts)]
+    refs = [Mla.reference(st, d, p, f, 2) for p, f in zip(prompts, firsts)]
     st.create_slots(3, 150)
     _fill_slots(st, d, prompts, [[0], [1], [2]])
     toks, pos = _steps_against_refs(st, d, refs, [0, 1, 2], firsts, [len(p) for p in prompts], 2)
     for i, (_, snap) in enumerate(refs):
         st.reset_decode_state(d["kv_max"])
         st.load_slot(i, pos[i])
-        _same(_snap(st, d, pos[i]), snap)
+        Mla.same(Mla.snap(st, d, pos[i]), snap)

@@ -6,9 +6,8 @@ import functools
 import numpy as np
 import pytest
 
+from tests.slots import Gqa, slot_state, toks as _toks
 from tests.test_decode_gpu import build
-from tests.test_speculative_gpu import _same, _snap
-from tests.test_multi_extend_gpu import _slot_state, _toks
 from tests.test_multi_verify_gpu import _fill
 from tests.test_multi_verify_sample_gpu import _smp_same
 
@@ -29,7 +28,7 @@ def _model():
 
 
 def _states(st, d, slots, pos, grown=(0, 0)):
-    return [_slot_state(st, d, s, p + g) for s, p, g in zip(slots, pos, grown)]
+    return [slot_state(Gqa, st, d, s, p + g) for s, p, g in zip(slots, pos, grown)]
 
 
 def _twin_samplers(st, firsts):
@@ -43,7 +42,7 @@ def test_no_tokens_greedy_touches_nothing():
     before, smp = _states(st, d, A, pos, (1, 1)), [st.slot_sampler_state(a) for a in A]      # with the row a stray step would append
     assert st.generate_multi(A, firsts, pos, 0) == [[], []]
     for x, y in zip(_states(st, d, A, pos, (1, 1)), before):
-        _same(x, y)
+        Gqa.same(x, y)
     for a, s in zip(A, smp):
         _smp_same(st.slot_sampler_state(a), s)
 
@@ -60,7 +59,7 @@ def test_no_tokens_sampled_starts_the_samplers():
         assert np.array_equal(seen, want) and rng == seed
         _smp_same((seen, rng), st.slot_sampler_state(b))
     for x, y in zip(_states(st, d, A, pos, (1, 1)), before):
-        _same(x, y)
+        Gqa.same(x, y)
 
 
 @pytest.mark.parametrize("sampled", [False, True])
@@ -79,7 +78,7 @@ def test_lookup_without_drafting_is_the_plain_loop(sampled):
     assert got == want
     grown = [len(w) for w in want]
     for x, y in zip(_states(st, d, A, pos, grown), _states(st, d, B, pos, grown)):
-        _same(x, y)
+        Gqa.same(x, y)
     for a, b, s in zip(A, B, smp_before):                        # the samplers went the twins' way; the greedy form leaves them alone
         _smp_same(st.slot_sampler_state(a), st.slot_sampler_state(b) if sampled else s)
     assert st.last_multi_lookup_stats == {"passes": max(grown), "accepted": [0, 0]}      # a pass per token of the longest row
@@ -93,7 +92,7 @@ def test_a_stop_id_as_the_first_token_of_a_row(form):
         st.reset_decode_state(d["kv_max"])
         st.prefill(prompts[i], 0)
         T = st.generate_batch(first, pos[i], N_TOK, stop_ids=stops)
-        return T, _snap(st, d, pos[i] + len(T))
+        return T, Gqa.snap(st, d, pos[i] + len(T))
 
     stop = alone(0, firsts[0], ())[0][0]
     # row 1 starts with the first token after which it never emits row 0's first one
@@ -107,4 +106,4 @@ def test_a_stop_id_as_the_first_token_of_a_row(form):
         got = st.generate_multi_lookup(A, firsts, pos, N_TOK, contexts=[[firsts[i]] + alone(i, firsts[i], ())[0] for i in range(2)], max_draft=4, stop_ids=(stop,))
     assert got == [T for T, _ in refs]
     for x, (T, snap) in zip(_states(st, d, A, pos, [len(T) for T, _ in refs]), refs):
-        _same(x, snap)
+        Gqa.same(x, snap)

@@ -12,6 +12,7 @@ import re
 
 import pytest
 
+from tests.slots import Gqa, Mla
 from tests.util import FLAGS as ALL_FLAGS, refusal_case as key, slot_option_refusals
 
 pytestmark = pytest.mark.gpu
@@ -21,12 +22,10 @@ LAYOUTS = ("flat", "paged")
 
 
 def _gqa(**kw):
-    from tests.test_multi_paged_gpu import Gqa
     return Gqa.build(kv_max=MAX_SEQ + 8, **kw)
 
 
 def _mla(**kw):
-    from tests.test_multi_paged_gpu import Mla
     return Mla.build(kv_max=MAX_SEQ + 8, **kw)
 
 

@@ -18,7 +18,7 @@ did not, and a scripted run must show exactly the forms that were switched on.  
 import numpy as np
 import pytest
 
-from tests.test_multi_paged_gpu import Gqa, Mla, _slot_state
+from tests.slots import Gqa, Mla, slot_state
 from tests.test_multi_paged_random_gpu import Driver
 
 pytestmark = pytest.mark.gpu
@@ -231,7 +231,7 @@ def replay(drv, st, with_sets, want_states, want_samplers):
         got_seen, got_state = st.slot_sampler_state(s)
         assert np.array_equal(got_seen, seen) and got_state == state, (tag, "sampler state", s)
     for s, want in want_states.items():
-        K.same(_slot_state(K, st, d, s, len(hist[s])), want)
+        K.same(slot_state(K, st, d, s, len(hist[s])), want)
 
 
 MODELS = {      # name -> (helpers, build arguments, rewinds, layer kinds, pages of the pool)
@@ -275,7 +275,7 @@ def test_random_call_orders_under_random_option_sets(model, seed):
         # every live slot's final state against the single-sequence path, and the samplers as they stand
         want_states = drv.reference_states()
         for s, want in want_states.items():
-            K.same(_slot_state(K, st, d, s, len(drv.hist[s])), want)
+            K.same(slot_state(K, st, d, s, len(drv.hist[s])), want)
         want_samplers = [st.slot_sampler_state(s) for s in range(N_SLOTS)]
         replay(drv, st, False, want_states, want_samplers)
         replay(drv, st, True, want_states, want_samplers)
@@ -349,7 +349,7 @@ def _scenario(K, st, d):
                                                      top_p=[0.95, 1.0], presence_penalty=[0.3, 0.5], rng_seeds=[11, 12]), 8)
     out.append(dict(st.last_multi_lookup_stats))
     samplers = [st.slot_sampler_state(s) for s in range(6)]
-    states = {s: _slot_state(K, st, d, s, len(h[s])) for s in range(6) if h[s]}
+    states = {s: slot_state(K, st, d, s, len(h[s])) for s in range(6) if h[s]}
     return out, h, states, samplers
 
 

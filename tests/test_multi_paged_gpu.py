@@ -6,65 +6,13 @@ also runs on flat slots of the same store.  The paged path is never compared wit
 import numpy as np
 import pytest
 
-from krasis_amd._lib import KrasisHipError
 from tests import test_multi_mla_gpu as mla
-from tests import test_multi_seq_gpu as seq
+from tests.slots import Gqa, Mla, pages as _pages, slot_state, state_error, toks as _toks
 from tests.test_decode_gpu import build
-from tests.test_speculative_gpu import _same, _snap
 
 pytestmark = pytest.mark.gpu
 U = np.uint32
 PT = 32
-
-
-class Gqa:
-    """the hybrid linear-attention + GQA test model and its single-sequence reference helpers"""
-    reference = staticmethod(seq._reference)
-    start = staticmethod(seq._start)
-    snap = staticmethod(_snap)
-    same = staticmethod(_same)
-
-    @staticmethod
-    def build(fp8=False, **kw):
-        st, eng, orc, keep, d = build(**kw)
-        if fp8:
-            st.set_kv_dtype(True); d["fp8"] = True
-        return st, (eng, orc, keep), d
-
-
-class Mla:
-    reference = staticmethod(mla._reference)
-    start = staticmethod(mla._start)
-    snap = staticmethod(mla._snap)
-    same = staticmethod(mla._same)
-
-    @staticmethod
-    def build(fp8=False, **kw):
-        st, eng, keep, d = mla._build(fp8, **kw)
-        return st, (eng, keep), d
-
-
-def _toks(rng, d, n):
-    return [int(x) for x in rng.integers(0, d["V"], n)]
-
-
-def _pages(n):
-    return (n + PT - 1) // PT
-
-
-def _slot_state(K, st, d, slot, pos):
-    st.reset_decode_state(d["kv_max"])
-    st.load_slot(slot, pos)
-    return K.snap(st, d, pos)
-
-
-def _state_error(call, *needles):
-    """the call is refused with KR_ERR_STATE (RuntimeError, not a HIP failure) and its message names every needle"""
-    with pytest.raises(RuntimeError) as e:
-        call()
-    assert not isinstance(e.value, KrasisHipError), e.value
-    for s in needles:
-        assert s in str(e.value), (s, str(e.value))
 
 
 # ---- 1, 2: prompts enter by prefill_slot in chunks that straddle page edges, then 40 steps cross positions 32, 64 and 96 at different steps ---------------
@@ -92,7 +40,7 @@ def _prefill_then_steps(K, st, d, n_pages, page_tokens=PT, lens=(0, 31, 70), n_s
     assert [pages["per_slot"][s] for s in slots] == [(p + page_tokens - 1) // page_tokens for p in pos]
     assert pages["free"] == n_pages - sum(pages["per_slot"])
     for i, (_, snap) in enumerate(refs):
-        K.same(_slot_state(K, st, d, slots[i], pos[i]), snap)
+        K.same(slot_state(K, st, d, slots[i], pos[i]), snap)
 
 
 @pytest.mark.parametrize("fp8", [False, True])
@@ -130,12 +78,12 @@ def _scattered(K, st, d, paged, seqs, probe):
         steps.append((lg.view(U).copy(), list(ids)))
         toks = ids; pos = [p + 1 for p in pos]
     if paged:
-        assert st.slot_pages()["per_slot"] == [_pages(pos[0]), _pages(pos[1]), 0, 0]
-    states = [_slot_state(K, st, d, 0, pos[0]), _slot_state(K, st, d, 1, pos[1])]
+        assert st.slot_pages()["per_slot"] == [_pages(pos[0], PT), _pages(pos[1], PT), 0, 0]
+    states = [slot_state(K, st, d, 0, pos[0]), slot_state(K, st, d, 1, pos[1])]
     st.trim_slot(1, 0)                                         # pages 1 and 2 go back, holding sequence b's rows
     ids, lg = st.step_multi([3], [probe], [40], logits=True)   # a never-filled slot at position 40 maps them: they must read as zero
     if paged:
-        assert st.slot_pages()["per_slot"] == [_pages(pos[0]), 0, 0, 2]
+        assert st.slot_pages()["per_slot"] == [_pages(pos[0], PT), 0, 0, 2]
     return out, steps, states, (lg.view(U).copy(), list(ids))
 
 
@@ -181,27 +129,27 @@ def test_small_pool_refuses_the_ninth_page(K):
     before = st.slot_pages()
     assert before["per_slot"] == [3, 2, 2, 1] and before["free"] == 0
     # slot 3 from position 25 over position 32 needs a ninth page: row 1 of the call
-    _state_error(lambda: st.extend_multi([0, 3], [[toks[0]], [toks[3]] + _toks(rng, d, 7)], [pos[0], pos[3]]), "row 1", "slot 3")
-    _state_error(lambda: st.generate_multi([0, 3], [toks[0], toks[3]], [pos[0], pos[3]], 8), "row 1")
-    _state_error(lambda: st.verify_multi([3], [[toks[3]] + _toks(rng, d, 7)], [pos[3]]), "row 0")
+    state_error(lambda: st.extend_multi([0, 3], [[toks[0]], [toks[3]] + _toks(rng, d, 7)], [pos[0], pos[3]]), "row 1", "slot 3")
+    state_error(lambda: st.generate_multi([0, 3], [toks[0], toks[3]], [pos[0], pos[3]], 8), "row 1")
+    state_error(lambda: st.verify_multi([3], [[toks[3]] + _toks(rng, d, 7)], [pos[3]]), "row 0")
     assert st.slot_pages() == before
     ids, lg = st.step_multi(slots, toks, pos, logits=True)    # the next legal step
     for i, (ref, _) in enumerate(refs):
         assert np.array_equal(lg[i].view(U), ref[5][0]) and ids[i] == ref[5][1], i
     pos = [p + 1 for p in pos]
     for i, (_, snap) in enumerate(refs):
-        K.same(_slot_state(K, st, d, slots[i], pos[i]), snap)
+        K.same(slot_state(K, st, d, slots[i], pos[i]), snap)
     # save_slot: the store's own sequence of 40 positions into slot 3 needs a second page there
     K.start(st, d, prompts[1])
     want = K.snap(st, d, 40)
-    _state_error(lambda: st.save_slot(3, 40), "slot 3")
+    state_error(lambda: st.save_slot(3, 40), "slot 3")
     assert st.slot_pages() == before
     K.same(K.snap(st, d, 40), want)
     st.trim_slot(2, 0)
     st.save_slot(3, 40)
     assert st.slot_pages()["per_slot"] == [3, 2, 0, 2]
-    K.same(_slot_state(K, st, d, 3, 40), want)
-    K.same(_slot_state(K, st, d, 0, pos[0]), refs[0][1])      # the other slots are where they were
+    K.same(slot_state(K, st, d, 3, 40), want)
+    K.same(slot_state(K, st, d, 0, pos[0]), refs[0][1])      # the other slots are where they were
 
 
 # ---- 5: speculation ------------------------------------------------------------------------------------------------------------------------------------
@@ -221,14 +169,14 @@ def _speculation(K, st, d, paged, prompts, runs):
                     st.set_slot_sampler(s, runs[i][0], SAMPLER["temperature"][i], SAMPLER["top_k"][i], SAMPLER["top_p"][i], SAMPLER["presence_penalty"][i], SAMPLER["rng_seeds"][i])
             ids, nm = (st.verify_multi_sample if sample else st.verify_multi)(slots, runs, list(SPEC_LENS))
             if paged:                                          # the drafted positions are mapped, and stay mapped over the commit
-                assert [st.slot_pages()["per_slot"][s] for s in slots] == [_pages(n + 8) for n in SPEC_LENS]
+                assert [st.slot_pages()["per_slot"][s] for s in slots] == [_pages(n + 8, PT) for n in SPEC_LENS]
                 with pytest.raises(RuntimeError):
                     st.trim_slot(0, 0)                         # refused while the verify is pending
             keep = [keep_of(m) for m in nm]
             st.commit_multi(keep)
             if paged:
-                assert [st.slot_pages()["per_slot"][s] for s in slots] == [_pages(n + 8) for n in SPEC_LENS]
-            out.append(([g[:m + 1] for g, m in zip(ids, nm)], nm, [_slot_state(K, st, d, s, n + k) for s, n, k in zip(slots, SPEC_LENS, keep)],
+                assert [st.slot_pages()["per_slot"][s] for s in slots] == [_pages(n + 8, PT) for n in SPEC_LENS]
+            out.append(([g[:m + 1] for g, m in zip(ids, nm)], nm, [slot_state(K, st, d, s, n + k) for s, n, k in zip(slots, SPEC_LENS, keep)],
                         [st.slot_sampler_state(s) for s in slots]))
     for sampler in (None, SAMPLER):
         new(); fill()
@@ -238,8 +186,8 @@ def _speculation(K, st, d, paged, prompts, runs):
         else:
             T = st.generate_multi_lookup(slots, firsts, list(SPEC_LENS), 14, ctx, 7, 2)
         if paged:
-            assert [st.slot_pages()["per_slot"][s] for s in slots] == [_pages(n + len(t)) for n, t in zip(SPEC_LENS, T)]
-        out.append((T, dict(st.last_multi_lookup_stats), [_slot_state(K, st, d, s, n + len(t)) for s, n, t in zip(slots, SPEC_LENS, T)],
+            assert [st.slot_pages()["per_slot"][s] for s in slots] == [_pages(n + len(t), PT) for n, t in zip(SPEC_LENS, T)]
+        out.append((T, dict(st.last_multi_lookup_stats), [slot_state(K, st, d, s, n + len(t)) for s, n, t in zip(slots, SPEC_LENS, T)],
                     [st.slot_sampler_state(s) for s in slots]))
     return out
 
@@ -305,10 +253,10 @@ def test_generate_gives_back_what_it_mapped(K):
         final = [n + len(t) for n, t in zip(lens, T)]
         if paged:
             pages = st.slot_pages()
-            assert pages["per_slot"] == [_pages(final[0]), _pages(final[1]), 4], pages
+            assert pages["per_slot"] == [_pages(final[0], PT), _pages(final[1], PT), 4], pages
             assert pages["free"] == 15 - sum(pages["per_slot"])
         for s in range(3):
-            K.same(_slot_state(K, st, d, s, final[s]), snaps[s])
+            K.same(slot_state(K, st, d, s, final[s]), snaps[s])
         outs.append(T)
     assert outs[0] == outs[1]
 
@@ -324,12 +272,12 @@ def test_save_load_round_trip(K, fp8):
     st.create_slots(2, 100, page_tokens=PT, n_pages=5)
     st.save_slot(1, 33)
     assert st.slot_pages()["per_slot"] == [0, 2]
-    K.same(_slot_state(K, st, d, 1, 33), want[33])
+    K.same(slot_state(K, st, d, 1, 33), want[33])
     K.start(st, d, prompt)
     st.save_slot(0, 95)
     assert st.slot_pages()["per_slot"] == [3, 2] and st.slot_pages()["free"] == 0
-    K.same(_slot_state(K, st, d, 0, 95), want[95])
-    K.same(_slot_state(K, st, d, 1, 33), want[33])
+    K.same(slot_state(K, st, d, 0, 95), want[95])
+    K.same(slot_state(K, st, d, 1, 33), want[33])
     st.trim_slot(0, 40)                                        # page 2 (positions 64 ..) is gone: its rows load as zero, the others as saved
     assert st.slot_pages()["per_slot"] == [2, 2]
     K.start(st, d, prompt)                                     # the store's rows are non-zero before the load
@@ -351,7 +299,7 @@ def test_production_width_pages_of_64():
     rng = np.random.default_rng(2)
     prompts = [_toks(rng, d, n) for n in (126, 3, 62)]
     firsts = _toks(rng, d, 3)
-    refs = [seq._reference(st, d, p, f, 4) for p, f in zip(prompts, firsts)]
+    refs = [Gqa.reference(st, d, p, f, 4) for p, f in zip(prompts, firsts)]
     st.create_slots(3, 150, page_tokens=64, n_pages=6)
     for s, p in enumerate(prompts):
         st.prefill_slot(s, p, chunk=50)
@@ -364,7 +312,7 @@ def test_production_width_pages_of_64():
         toks = ids; pos = [p + 1 for p in pos]
     assert st.slot_pages() == dict(page_tokens=64, n_pages=6, free=0, per_slot=[3, 1, 2])
     for i, (_, snap) in enumerate(refs):
-        _same(_slot_state(Gqa, st, d, i, pos[i]), snap)
+        Gqa.same(slot_state(Gqa, st, d, i, pos[i]), snap)
 
 
 # ---- 9: refusals ---------------------------------------------------------------------------------------------------------------------------------------
@@ -373,16 +321,16 @@ def test_refusals_change_nothing():
     st.create_slots(3, 100)
     st.fill_state_synthetic(d["kv_max"], seed=5)
     st.save_slot(1, 40)
-    want = _snap(st, d, 40)
+    want = Gqa.snap(st, d, 40)
     assert st.slot_pages() == dict(page_tokens=0, n_pages=0, free=0, per_slot=[0, 0, 0])      # flat slots
     for bad in (dict(page_tokens=0, n_pages=4), dict(page_tokens=24, n_pages=4), dict(page_tokens=16, n_pages=4), dict(page_tokens=48, n_pages=4),
                 dict(page_tokens=32, n_pages=0)):
         with pytest.raises(ValueError) as e:
             st.create_slots(3, 100, **bad)
         assert ("n_pages" if bad["n_pages"] == 0 else "page_tokens") in str(e.value)
-        _same(_slot_state(Gqa, st, d, 1, 40), want)            # the earlier slots are still there
+        Gqa.same(slot_state(Gqa, st, d, 1, 40), want)            # the earlier slots are still there
     st.trim_slot(1, 0)                                          # flat slots: a no-op that still checks its arguments
-    _same(_slot_state(Gqa, st, d, 1, 40), want)
+    Gqa.same(slot_state(Gqa, st, d, 1, 40), want)
     for slot, n in ((3, 0), (-1, 0), (1, -1), (1, 101)):
         with pytest.raises(ValueError):
             st.trim_slot(slot, n)
@@ -395,7 +343,7 @@ def test_refusals_change_nothing():
 
     def unchanged():
         assert st.slot_pages() == before
-        _same(_slot_state(Gqa, st, d, 1, 40), want)
+        Gqa.same(slot_state(Gqa, st, d, 1, 40), want)
 
     for slot, n in ((3, 0), (-1, 0), (1, -1), (1, 101)):
         with pytest.raises(ValueError):
@@ -405,18 +353,18 @@ def test_refusals_change_nothing():
     calls = [lambda: st.step_multi([1], [2], [40]), lambda: st.extend_multi([0], [[1, 2]], [0]), lambda: st.generate_multi([1], [2], [40], 4),
              lambda: st.verify_multi([1], [[2, 3]], [40]), lambda: st.generate_multi_lookup([1], [2], [40], 4)]
     for call in calls:
-        _state_error(call, "multi_attn_fast", "paged")
+        state_error(call, "multi_attn_fast", "paged")
     unchanged()
     st.set_option("multi_attn_fast", 0)
     st.verify_multi([1], [[2, 3, 4]], [40])                     # pending: trim is refused with the other slot calls
     pending = st.slot_pages()
-    _state_error(lambda: st.trim_slot(1, 0), "pending")
+    state_error(lambda: st.trim_slot(1, 0), "pending")
     assert st.slot_pages() == pending
     st.commit_multi([0])
-    _same(_slot_state(Gqa, st, d, 1, 40), want)
+    Gqa.same(slot_state(Gqa, st, d, 1, 40), want)
     st.set_kv_dtype(True)                                       # the pools hold FP16 rows, the store now E4M3
     st.reset_decode_state(d["kv_max"])
     for call in (lambda: st.step_multi([1], [2], [40]), lambda: st.load_slot(1, 40), lambda: st.trim_slot(1, 0), lambda: st.slot_pages()):
-        _state_error(call, "E4M3")
+        state_error(call, "E4M3")
     st.set_kv_dtype(False)
     unchanged()

@@ -10,7 +10,7 @@ import pytest
 
 from krasis_amd._lib import KrasisHipError
 from tests import test_multi_mla_gpu as mla
-from tests.test_multi_paged_gpu import Gqa, Mla, _slot_state
+from tests.slots import Gqa, Mla, slot_state
 
 pytestmark = pytest.mark.gpu
 U = np.uint32
@@ -190,7 +190,7 @@ class Driver:
                 ids, lg = self.out[-1]
                 assert np.array_equal(st.read_logits().view(U), lg[sl.index(s)]) and st.last_token() == ids[sl.index(s)], ("checkpoint", s)
             want = K.snap(st, d, n)
-            K.same(_slot_state(K, st, d, s, n), want)
+            K.same(slot_state(K, st, d, s, n), want)
 
     def drive(self):
         done = 0

@@ -12,7 +12,8 @@ import numpy as np
 import pytest
 
 from oracle import oracle as O
-from tests.test_multi_paged_gpu import Gqa, Mla, _prefill_then_steps, _slot_state, _toks
+from tests.slots import Gqa, Mla, pages as _pages, slot_state, toks as _toks
+from tests.test_multi_paged_gpu import _prefill_then_steps
 
 pytestmark = pytest.mark.gpu
 F = np.float32
@@ -81,10 +82,6 @@ def _decode_reference(K, st, d, state, first, pos, n_steps):
     return out, K.snap(st, d, pos + n_steps)
 
 
-def _pages(n, pt):
-    return (n + pt - 1) // pt
-
-
 # ---- 1, 2: long rows ---------------------------------------------------------------------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
 def _long_model(kind, key):
@@ -130,7 +127,7 @@ def _long_rows(kind, key, page_tokens):
     pages = st.slot_pages()
     assert [pages["per_slot"][s] for s in slots] == [_pages(p, pt) for p in pos] and pages["free"] == 0
     for i, (_, snap) in enumerate(refs):
-        K.same(_slot_state(K, st, d, slots[i], pos[i]), snap)
+        K.same(slot_state(K, st, d, slots[i], pos[i]), snap)
 
 
 @pytest.mark.parametrize("page_tokens", [32, 256])
@@ -198,7 +195,7 @@ def _extend_many(K, st, d, paged, prompts, page_tokens):
     if paged:
         pages = st.slot_pages()
         assert [pages["per_slot"][s] for s in slots] == [_pages(len(p), page_tokens) for p in prompts] and pages["free"] == 0
-    return ids, lg.view(U).copy(), [_slot_state(K, st, d, s, len(p)) for s, p in zip(slots, prompts)]
+    return ids, lg.view(U).copy(), [slot_state(K, st, d, s, len(p)) for s, p in zip(slots, prompts)]
 
 
 @pytest.mark.parametrize("page_tokens", [32, 64])
@@ -262,7 +259,7 @@ def _fork_run(K, st, d, paged, state, firsts, new):
         assert st.slot_pages()["free"] == n_pages - (full + 1) - 3 - 1
     out.append(st.step_multi([SRC, DSTS[0]], [firsts[3], firsts[4]], [N_FORK, REWIND + N_NEW], logits=True))
     out[-1] = (list(out[-1][0]), out[-1][1].view(U).copy())
-    states = [_slot_state(K, st, d, SRC, N_FORK + 1), _slot_state(K, st, d, DSTS[0], REWIND + N_NEW + 1), _slot_state(K, st, d, DSTS[1], N_FORK + 3)]
+    states = [slot_state(K, st, d, SRC, N_FORK + 1), slot_state(K, st, d, DSTS[0], REWIND + N_NEW + 1), slot_state(K, st, d, DSTS[1], N_FORK + 3)]
     return out, states
 
 
@@ -333,7 +330,7 @@ def test_table_one_entry_over_the_lds_budget_is_refused_at_creation(hd, nh):
         ids, lg = st.step_multi([1], toks, pos, logits=True)
         assert np.array_equal(lg[0].view(U), ref[0][k][0]) and ids[0] == ref[0][k][1], k
         toks = ids; pos = [p + 1 for p in pos]
-    Gqa.same(_slot_state(Gqa, st, d, 1, 42), ref[1])
+    Gqa.same(slot_state(Gqa, st, d, 1, 42), ref[1])
 
 
 @pytest.mark.parametrize("hd,nh", [(256, 16), (64, 4)])

@@ -7,9 +7,10 @@ import numpy as np
 import pytest
 
 from oracle import oracle as O
+from tests.slots import Gqa, toks as _toks
 from tests.test_decode_gpu import build
-from tests.test_multi_seq_gpu import _fill_slots, _prompt, _start
-from tests.test_speculative_gpu import CFGS, _same, _snap
+from tests.test_multi_seq_gpu import _fill_slots
+from tests.test_speculative_gpu import CFGS
 
 pytestmark = pytest.mark.gpu
 F = np.float32
@@ -78,13 +79,13 @@ def _gen_params(n):
 def test_generate_multi_sampled_equals_generate_batch(cfg):
     st, eng, orc, keep, d = build(kv_max=64, **cfg)
     rng = np.random.default_rng(21)
-    prompts = [_prompt(rng, d, n) for n in (5, 17, 2, 30, 9)]
+    prompts = [_toks(rng, d, n) for n in (5, 17, 2, 30, 9)]
     firsts = [int(x) for x in rng.integers(0, d["V"], len(prompts))]
     params, seeds = _gen_params(len(prompts))
     max_tokens = 9
 
     def alone(i, stop_ids):
-        _start(st, d, prompts[i])
+        Gqa.start(st, d, prompts[i])
         T, K, P, PEN = params[i]
         return st.generate_batch(firsts[i], len(prompts[i]), max_tokens, T, K, P, stop_ids, PEN, rng_seed=seeds[i])
 
@@ -93,7 +94,7 @@ def test_generate_multi_sampled_equals_generate_batch(cfg):
     ref_toks, ref_snaps = [], []
     for i, p in enumerate(prompts):
         T = alone(i, stop_ids)
-        ref_toks.append(T); ref_snaps.append(_snap(st, d, len(p) + len(T)))
+        ref_toks.append(T); ref_snaps.append(Gqa.snap(st, d, len(p) + len(T)))
     assert len({len(T) for T in ref_toks}) > 1
     slots = [1, 4, 0, 2, 3]
     for loop in (0, 1):
@@ -107,7 +108,7 @@ def test_generate_multi_sampled_equals_generate_batch(cfg):
         for i, p in enumerate(prompts):
             st.reset_decode_state(d["kv_max"])
             st.load_slot(slots[i], len(p) + len(out[i]))
-            _same(_snap(st, d, len(p) + len(out[i])), ref_snaps[i])
+            Gqa.same(Gqa.snap(st, d, len(p) + len(out[i])), ref_snaps[i])
     st.set_option("multi_sample_loop", 0)
 
 
@@ -120,11 +121,11 @@ def test_continuous_batching(loop):
     rng = np.random.default_rng(33)
     reqs = [(0, 8, (0.6, 50, 0.95, 0.0), 11), (0, 3, (0.0, 0, 1.0, 0.0), 12), (2, 6, (0.9, 10, 0.95, 0.7), 13),
             (2, 4, (0.0, 0, 1.0, 1.5), 14), (5, 5, (1.3, 0, 0.8, 0.0), 15), (5, 3, (1.0, 1, 1.0, 0.0), 16)]
-    prompts = [_prompt(rng, d, int(n)) for n in rng.integers(1, 20, len(reqs))]
+    prompts = [_toks(rng, d, int(n)) for n in rng.integers(1, 20, len(reqs))]
     firsts = [int(x) for x in rng.integers(0, d["V"], len(reqs))]
     refs = []
     for q, (_, L, (T, K, P, PEN), seed) in enumerate(reqs):
-        _start(st, d, prompts[q])
+        Gqa.start(st, d, prompts[q])
         refs.append(st.generate_batch(firsts[q], len(prompts[q]), L, T, K, P, (), PEN, rng_seed=seed))
     slot_of = [4, 1, 5, 0, 3, 2]
     st.create_slots(12, 64)
@@ -154,12 +155,12 @@ def test_continuous_batching(loop):
 def test_steps_leave_the_store_sampler_alone():
     st, eng, orc, keep, d = build(kv_max=48)
     rng = np.random.default_rng(41)
-    prompt, others = _prompt(rng, d, 6), [_prompt(rng, d, 4), _prompt(rng, d, 11)]
+    prompt, others = _toks(rng, d, 6), [_toks(rng, d, 4), _toks(rng, d, 11)]
     tok0, pos = 17, len(prompt)
     smp = dict(temperature=0.6, top_k=50, top_p=0.95, presence_penalty=0.5)
 
     def run(between):
-        _start(st, d, prompt)
+        Gqa.start(st, d, prompt)
         st.decode_step(tok0, pos)
         a = st.sample(**smp, rng_seed=0xC0FFEE, reset_seen=True)
         between()
@@ -170,7 +171,7 @@ def test_steps_leave_the_store_sampler_alone():
     ref = run(lambda: None)
     st.create_slots(2, 48)
     _fill_slots(st, d, others, [[0], [1]])
-    _start(st, d, prompt)
+    Gqa.start(st, d, prompt)
 
     def multi_steps():
         st.set_slot_sampler(0, 3, 0.6, 50, 0.95, 0.5, 99)
@@ -194,13 +195,13 @@ def test_refusals_change_nothing():
     st.create_slots(3, 24)
     st.fill_state_synthetic(d["kv_max"], seed=5)
     st.save_slot(1, 20)
-    want = _snap(st, d, 20)
+    want = Gqa.snap(st, d, 20)
     first, seed, smp = 9, 0x5EED, (0.6, 50, 0.95, 0.5)
     st.set_slot_sampler(1, first, *smp, seed)
 
     def unchanged():
         st.reset_decode_state(d["kv_max"]); st.load_slot(1, 20)
-        _same(_snap(st, d, 20), want)
+        Gqa.same(Gqa.snap(st, d, 20), want)
 
     V = d["V"]
     for bad in (dict(slot=3), dict(slot=-1), dict(slot=1, temperature=-0.5)):

@@ -1,7 +1,7 @@
 """Slot export and import (kr_decode_slots_export / kr_decode_slots_import, docs/design/38-slot-swap.md): a slot's complete state goes out to host memory as one
 self-describing image and comes back into any slot of any compatible slot set, bit for bit -- flat or paged, any page size and placement, pages shared by fork.
 Every assertion is on ids, byte arrays and u32 bit patterns, and the reference is never the new path: it is the single-sequence path (K.reference), the state
-read back through load_slot + get_decode_state (_slot_state), or the same calls without a swap in between."""
+read back through load_slot + get_decode_state (slots.slot_state), or the same calls without a swap in between."""
 import functools
 
 import numpy as np
@@ -9,7 +9,8 @@ import pytest
 
 from krasis_amd.decode_store import slot_image_info
 from tests import test_multi_mla_gpu as mla
-from tests.test_multi_paged_gpu import PT, Gqa, Mla, _pages, _slot_state, _state_error, _toks
+from tests.slots import Gqa, Mla, pages as _pages, slot_state, state_error, toks as _toks
+from tests.test_multi_paged_gpu import PT
 
 pytestmark = pytest.mark.gpu
 U = np.uint32
@@ -94,7 +95,7 @@ def _export_three_ways(K, st, d, P, F, name, n):
         img = st.export_slot(slot, n + 5)
         info = slot_image_info(img)
         assert (info["seq_len"], info["kv_fp8"], info["has_sampler"]) == (n + 5, bool(d.get("fp8")), False)
-        _image_equals_state(K, img, _slot_state(K, st, d, slot, n + 5))
+        _image_equals_state(K, img, slot_state(K, st, d, slot, n + 5))
         if geo:
             assert _tables(st, 4) == before
         out.append(img)
@@ -129,8 +130,8 @@ def _round_trip(K, st, d, P, F, R, src, dst):
         assert all(i >= 0 for i in ids[:n]) and all(i < 0 for i in ids[n:]) and refs[:n] == [1] * n
         assert not set(ids[:n]) & set(st.slot_page_ids(0)[0][:2])
     _, pos = _steps(st, [1], tok, [75], 40, [R["a"]], [5])
-    K.same(_slot_state(K, st, d, 1, pos[0]), R["a"][1])
-    K.same(_slot_state(K, st, d, 0, 40), R["b40"])      # the bystander kept its bits
+    K.same(slot_state(K, st, d, 1, pos[0]), R["a"][1])
+    K.same(slot_state(K, st, d, 0, 40), R["b40"])      # the bystander kept its bits
     return img
 
 
@@ -171,7 +172,7 @@ def test_several_slots_in_one_call(kind, fp8):
     for s, n, img in zip(slots, lens, many):
         assert img.tobytes() == st.export_slot(s, n).tobytes(), (s, n)
         assert slot_image_info(img) == dict(seq_len=n, kv_fp8=bool(d.get("fp8")), has_sampler=True, geometry=slot_image_info(many[0])["geometry"])
-        _image_equals_state(K, img, _slot_state(K, st, d, s, n), sampler=1)
+        _image_equals_state(K, img, slot_state(K, st, d, s, n), sampler=1)
     empty = _sections(many[0])      # seq_len 0: only linear-attention state and the sampler
     kinds = d["kinds"] if K is Gqa else ["mla"] * d["nL"]
     for li, kind_ in enumerate(kinds):
@@ -194,7 +195,7 @@ def test_several_slots_in_one_call(kind, fp8):
         assert st.slot_pages()["per_slot"] == [2, 0, 0, 1]
         for s, n, img in zip([1, 3, 0], lens, many):
             assert st.export_slot(s, n).tobytes() == img.tobytes(), (together, s)
-        K.same(_slot_state(K, st, d, 0, 70), R["a70"])
+        K.same(slot_state(K, st, d, 0, 70), R["a70"])
         seen2, rng2 = st.slot_sampler_state(0)
         assert rng2 == 77 and np.array_equal(seen2, seen)
 
@@ -218,9 +219,9 @@ def test_export_and_import_beside_shared_pages(kind, fp8):
     ids, refs = st.slot_page_ids(3)
     assert refs == [1, 1, 0, 0] and not set(ids[:2]) & set(st.slot_page_ids(0)[0][:3])
     assert st.slot_page_ids(0)[1][:3] == [2, 2, 1] and st.slot_page_ids(2)[1][:3] == [2, 2, 1]
-    K.same(_slot_state(K, st, d, 3, 40), R["b40"])
-    K.same(_slot_state(K, st, d, 0, 70), R["a70"])
-    K.same(_slot_state(K, st, d, 2, 70), R["a70"])
+    K.same(slot_state(K, st, d, 3, 40), R["b40"])
+    K.same(slot_state(K, st, d, 0, 70), R["a70"])
+    K.same(slot_state(K, st, d, 2, 70), R["a70"])
     _steps(st, [2, 0, 3], [F["a"], F["a"], F["b"]], [70, 70, 40], 3, [R["a"], R["a"], R["b"]], [0, 0, 0])      # slot 2's next steps match its reference, and so do the others'
 
 
@@ -233,17 +234,17 @@ def test_an_import_that_does_not_fit_changes_nothing(kind, fp8):
     img = st.export_slot(0, 70)
     before = _tables(st, 4)
     assert before[1]["free"] == 0 and before[1]["per_slot"] == [3, 2, 1, 0]
-    state = _slot_state(K, st, d, 1, 40)
+    state = slot_state(K, st, d, 1, 40)
     # three pages needed, none free, two come back with the target: one short
-    _state_error(lambda: st.import_slot(1, img), "pages", "3 pages", "2 of 6")
+    state_error(lambda: st.import_slot(1, img), "pages", "3 pages", "2 of 6")
     assert _tables(st, 4) == before
-    K.same(_slot_state(K, st, d, 1, 40), state); K.same(state, R["b40"])
+    K.same(slot_state(K, st, d, 1, 40), state); K.same(state, R["b40"])
     _steps(st, [1], [F["b"]], [40], 2, [R["b"]], [0])      # positions 40 and 41 lie in its second page: no page needed
     st.trim_slot(2, 0)      # one page free: alone it would not do, with the target's own two it does
     assert st.slot_pages()["free"] == 1
     assert st.import_slot(1, img) == 70
     assert st.slot_pages()["per_slot"] == [3, 3, 0, 0] and st.slot_pages()["free"] == 0 and st.slot_page_ids(1)[1] == [1, 1, 1, 0]
-    K.same(_slot_state(K, st, d, 1, 70), R["a70"])
+    K.same(slot_state(K, st, d, 1, 70), R["a70"])
     _steps(st, [0, 1], [F["a"]] * 2, [70, 70], 3, [R["a"], R["a"]], [0, 0])
 
 
@@ -320,7 +321,7 @@ def test_refusals_change_nothing(K, cfg, other):
         hot.append(img)
 
     def snapshot():
-        arrays = [x for s, n in ((0, 40), (1, 20)) for pair in _pairs(K, _slot_state(K, st, d, s, n)) for x in pair]
+        arrays = [x for s, n in ((0, 40), (1, 20)) for pair in _pairs(K, slot_state(K, st, d, s, n)) for x in pair]
         return _tables(st, 3), arrays + [st.slot_sampler_state(s)[0] for s in range(3)], [st.slot_sampler_state(s)[1] for s in range(3)]
 
     def same(a, b):
@@ -353,8 +354,8 @@ def test_refusals_change_nothing(K, cfg, other):
             st.set_option("slot_swap_chunk_bytes", v)
     same(snapshot(), before)
     st.verify_multi([0], [[first, first]], [40])      # between a verify over slots and its commit nothing else runs on them
-    _state_error(lambda: st.import_slot(1, good), "pending")
-    _state_error(lambda: st.export_slot(0, 40), "pending")
+    state_error(lambda: st.import_slot(1, good), "pending")
+    state_error(lambda: st.export_slot(0, 40), "pending")
     st.commit_multi([1])
     assert st.import_slot(2, st.export_slot(0, 41)) == 41 and st.import_slot(1, good) == 40      # and after the commit both run
 
@@ -367,16 +368,16 @@ def test_preempt_and_resume(kind, fp8):
     st.create_slots(3, MAXSEQ, page_tokens=PT, n_pages=5)
     st.prefill_slot(0, P["a40"], chunk=24); st.prefill_slot(1, P["b"], chunk=24)
     (ta, tb), _ = _steps(st, [0, 1], [F["a40"], F["b"]], [40, 40], 10, [R["a40"], R["b"]], [0, 0])
-    _state_error(lambda: st.prefill_slot(2, P["c"], chunk=40), "pages")      # no room for the newcomer
+    state_error(lambda: st.prefill_slot(2, P["c"], chunk=40), "pages")      # no room for the newcomer
     image_a = st.export_slot(0, 50, release=True)      # A leaves the device
     st.prefill_slot(2, P["c"], chunk=40)
     (tb, tc), _ = _steps(st, [1, 2], [tb, F["c"]], [50, 40], 5, [R["b"], R["c"]], [10, 0])
     _steps(st, [2], [tc], [45], 15, [R["c"]], [5])      # C decodes to its end
-    K.same(_slot_state(K, st, d, 2, 60), R["c"][1])
+    K.same(slot_state(K, st, d, 2, 60), R["c"][1])
     st.trim_slot(2, 0)
     assert st.import_slot(2, image_a) == 50      # A comes back, into another slot, and goes on beside B
     (ta, tb), _ = _steps(st, [2, 1], [ta, tb], [50, 55], 5, [R["a40"], R["b"]], [10, 15])      # B's last steps
     _steps(st, [2], [ta], [55], 15, [R["a40"]], [15])      # A finishes, across position 64: a third page
-    K.same(_slot_state(K, st, d, 2, 70), R["a40"][1])
-    K.same(_slot_state(K, st, d, 1, 60), R["b"][1])
-    assert _pages(70) == 3 and st.slot_pages()["per_slot"] == [0, 2, 3] and st.slot_pages()["free"] == 0
+    K.same(slot_state(K, st, d, 2, 70), R["a40"][1])
+    K.same(slot_state(K, st, d, 1, 60), R["b"][1])
+    assert _pages(70, PT) == 3 and st.slot_pages()["per_slot"] == [0, 2, 3] and st.slot_pages()["free"] == 0

@@ -8,10 +8,10 @@ import numpy as np
 import pytest
 
 from krasis_amd._lib import KR_VERIFY_MAX
+from tests.slots import Gqa, Mla, slot_state, toks as _toks
 from tests.test_decode_gpu import build
-from tests.test_speculative_gpu import CFGS, _same, _snap
+from tests.test_speculative_gpu import CFGS
 from tests.test_multi_seq_gpu import DV64, LA4
-from tests.test_multi_extend_gpu import _slot_state, _toks
 from tests import test_multi_mla_gpu as mla
 
 pytestmark = pytest.mark.gpu
@@ -19,7 +19,7 @@ F = np.float32
 U = np.uint32
 
 
-def _trace(st, d, prompt, first, n, fill=(), snap=_snap):
+def _trace(st, d, prompt, first, n, fill=(), K=Gqa):
     """decode_step alone from zero state: the prompt (saved into the slots `fill`), then n greedy steps from `first`.  toks[k] = the token step k
     consumes (toks[0] = first, toks[k + 1] = the id step k gives), lg[k] = the logits bits after step k, snaps[k] = the state after k steps"""
     st.reset_decode_state(d["kv_max"])
@@ -28,10 +28,10 @@ def _trace(st, d, prompt, first, n, fill=(), snap=_snap):
     p0 = len(prompt)
     for s in fill:
         st.save_slot(s, p0)
-    tr = dict(p0=p0, toks=[first], lg=[], snaps=[snap(st, d, p0)])
+    tr = dict(p0=p0, toks=[first], lg=[], snaps=[K.snap(st, d, p0)])
     for k in range(n):
         st.decode_step(tr["toks"][k], p0 + k)
-        tr["lg"].append(st.read_logits().view(U).copy()); tr["toks"].append(st.last_token()); tr["snaps"].append(snap(st, d, p0 + k + 1))
+        tr["lg"].append(st.read_logits().view(U).copy()); tr["toks"].append(st.last_token()); tr["snaps"].append(K.snap(st, d, p0 + k + 1))
     return tr
 
 
@@ -46,17 +46,17 @@ def _wrong_at(tr, c, j, V):
     return run
 
 
-def _check_slot(st, d, slot, tr, k, snap=_snap, same=_same):
-    same(_slot_state(st, d, slot, tr["p0"] + k, snap), tr["snaps"][k])
+def _check_slot(st, d, slot, tr, k, K=Gqa):
+    K.same(slot_state(K, st, d, slot, tr["p0"] + k), tr["snaps"][k])
 
 
 ROWS = [(0, 1), (0, 9), (7, 5), (23, 1), (2, 16)]              # (tokens already in the slot, run length)
 SLOTS = [3, 0, 6, 2, 5]                                          # slot numbers do not follow the rows
 
 
-def _all_right(st, d, snap=_snap, same=_same, rows=ROWS, slots=SLOTS, seed=5):
+def _all_right(st, d, K=Gqa, rows=ROWS, slots=SLOTS, seed=5):
     rng = np.random.default_rng(seed)
-    trs = [_trace(st, d, _toks(rng, d, p), _toks(rng, d, 1)[0], c + 1, [s], snap) for (p, c), s in zip(rows, slots)]
+    trs = [_trace(st, d, _toks(rng, d, p), _toks(rng, d, 1)[0], c + 1, [s], K) for (p, c), s in zip(rows, slots)]
     runs = [_right(tr, c) for tr, (_, c) in zip(trs, rows)]
     greedy, nm = st.verify_multi(slots, runs, [tr["p0"] for tr in trs])
     for i, (tr, (_, c)) in enumerate(zip(trs, rows)):
@@ -64,7 +64,7 @@ def _all_right(st, d, snap=_snap, same=_same, rows=ROWS, slots=SLOTS, seed=5):
         assert nm[i] == c - 1, ("n_match", i)
     st.commit_multi([c for _, c in rows])
     for tr, (_, c), s in zip(trs, rows, slots):
-        _check_slot(st, d, s, tr, c, snap, same)
+        _check_slot(st, d, s, tr, c, K)
     ids, lg = st.step_multi(slots, [g[-1] for g in greedy], [tr["p0"] + c for tr, (_, c) in zip(trs, rows)], logits=True)
     for i, (tr, (_, c)) in enumerate(zip(trs, rows)):      # the slots continue as the sequences do
         assert np.array_equal(lg[i].view(U), tr["lg"][c]) and ids[i] == tr["toks"][c + 1], i
@@ -133,7 +133,7 @@ def test_independence_of_rows_and_the_single_sequence_verify():
         run = _right(tr, c) if j is None else _wrong_at(tr, c, j, d["V"])
         g, m = st.verify_multi([alone_slot], [run], [p])
         st.commit_multi([m[0] + 1])
-        alone.append((g[0], m[0], _slot_state(st, d, alone_slot, p + m[0] + 1)))
+        alone.append((g[0], m[0], slot_state(Gqa, st, d, alone_slot, p + m[0] + 1)))
         st.reset_decode_state(d["kv_max"]); st.load_slot(s, p)
         single.append(st.verify(run, p))
         st.commit(1)
@@ -146,7 +146,7 @@ def test_independence_of_rows_and_the_single_sequence_verify():
     for r, i in enumerate(order):
         assert greedy[r] == alone[i][0] and nm[r] == alone[i][1], ("alone", i)
         assert (greedy[r], nm[r]) == tuple(single[i]), ("single-sequence verify", i)
-        _same(_slot_state(st, d, slots[i], pos[i] + nm[r] + 1), alone[i][2])
+        Gqa.same(slot_state(Gqa, st, d, slots[i], pos[i] + nm[r] + 1), alone[i][2])
     assert [m for _, m, _ in alone] == [0, 3, 4, 0, 1, 10]
 
 
@@ -164,7 +164,7 @@ def test_cut_invariance_with_the_extend(cfg):
     st.commit_multi([4])
     got = st.extend_multi([0], [run[4:]], [p0 + 4], logits=True)
     assert got[0] == want[0] and np.array_equal(got[1].view(U), want[1].view(U))
-    _same(_slot_state(st, d, 0, p0 + 9), _slot_state(st, d, 1, p0 + 9))
+    Gqa.same(slot_state(Gqa, st, d, 0, p0 + 9), slot_state(Gqa, st, d, 1, p0 + 9))
     _check_slot(st, d, 0, tr, 9)
 
 
@@ -178,7 +178,7 @@ def test_fp8_kv():
 def test_mla():
     st, eng, keep, d = mla._build(False, kv_max=64, **mla.CFGS[1])
     st.create_slots(8, 60)
-    _all_right(st, d, snap=mla._snap, same=mla._same)
+    _all_right(st, d, K=Mla)
 
 
 def test_multi_attn_fast_option():
@@ -199,7 +199,7 @@ def test_multi_attn_fast_option():
         assert greedy[0] == ids and nm == [8]
         st.commit_multi([6])
         st.extend_multi([1], [run[:6]], [p0])
-        _same(_slot_state(st, d, 0, p0 + 6), _slot_state(st, d, 1, p0 + 6))
+        Gqa.same(slot_state(Gqa, st, d, 0, p0 + 6), slot_state(Gqa, st, d, 1, p0 + 6))
         a = st.step_multi([0], [run[6]], [p0 + 6], logits=True)
         b = st.step_multi([1], [run[6]], [p0 + 6], logits=True)
         assert a[0] == b[0] == [ids[6]] and np.array_equal(a[1].view(U), b[1].view(U))
@@ -240,7 +240,7 @@ def test_generate_multi_lookup_equals_generate_multi(max_draft):
         got = st.generate_multi_lookup(A, firsts, pos, n_tok, contexts=ctx, max_draft=max_draft, stop_ids=stops)
         assert got == want
         for a, b, p, w in zip(A, B, pos, want):
-            _same(_slot_state(st, d, a, p + len(w)), _slot_state(st, d, b, p + len(w)))
+            Gqa.same(slot_state(Gqa, st, d, a, p + len(w)), slot_state(Gqa, st, d, b, p + len(w)))
         stats = st.last_multi_lookup_stats
         if repeat:                                             # it did speculate
             assert stats["passes"] < n_tok and all(a > 0 for a in stats["accepted"]), stats
@@ -255,7 +255,7 @@ def test_generate_multi_lookup_without_contexts():
     want = st.generate_multi([1, 3], firsts, [3, 8], 20)
     assert st.generate_multi_lookup([0, 2], firsts, [3, 8], 20) == want
     for a, b, p in ((0, 1, 3), (2, 3, 8)):
-        _same(_slot_state(st, d, a, p + 20), _slot_state(st, d, b, p + 20))
+        Gqa.same(slot_state(Gqa, st, d, a, p + 20), slot_state(Gqa, st, d, b, p + 20))
 
 
 def test_refusals_and_the_pending_state():
@@ -269,12 +269,12 @@ def test_refusals_and_the_pending_state():
     st.save_slot(1, 20)
     st.fill_state_synthetic(d["kv_max"], seed=6)
     st.save_slot(2, 10)
-    state = lambda: (_slot_state(st, d, 1, 20), _slot_state(st, d, 2, 10))
+    state = lambda: (slot_state(Gqa, st, d, 1, 20), slot_state(Gqa, st, d, 2, 10))
     want = state()
 
     def unchanged():
         for g, w in zip(state(), want):
-            _same(g, w)
+            Gqa.same(g, w)
 
     V = d["V"]
     refused = [
@@ -335,7 +335,7 @@ def test_the_store_sequence_is_untouched_and_steps_while_pending():
     own = _toks(rng, d, 6)
     st.reset_decode_state(d["kv_max"])
     st.prefill(own, 0)                                         # the store's own sequence: something else
-    own_state = lambda: (st.read_logits().view(U).copy(), st.last_token(), _snap(st, d, 48))
+    own_state = lambda: (st.read_logits().view(U).copy(), st.last_token(), Gqa.snap(st, d, 48))
     before = own_state()
     st.decode_step(before[1], 6)
     stepped = own_state()
@@ -344,10 +344,10 @@ def test_the_store_sequence_is_untouched_and_steps_while_pending():
     greedy, nm = st.verify_multi([1], [_right(tr, 6)], [7])
     after = own_state()
     assert np.array_equal(before[0], after[0]) and before[1] == after[1]
-    _same(after[2], before[2])
+    Gqa.same(after[2], before[2])
     st.decode_step(after[1], 6)                                # the store's own entry points run while the slots wait for their commit
     st.commit_multi([5])
     after = own_state()
     assert np.array_equal(stepped[0], after[0]) and stepped[1] == after[1]
-    _same(after[2], stepped[2])
+    Gqa.same(after[2], stepped[2])
     _check_slot(st, d, 1, tr, 5)

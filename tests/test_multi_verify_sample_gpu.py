@@ -9,10 +9,9 @@ import numpy as np
 import pytest
 
 from krasis_amd._lib import KR_VERIFY_MAX
+from tests.slots import Gqa, Mla, slot_state, toks as _toks
 from tests.test_decode_gpu import build
-from tests.test_speculative_gpu import _same, _snap
 from tests.test_multi_seq_gpu import LA4
-from tests.test_multi_extend_gpu import _slot_state, _toks
 from tests.test_multi_sample_gpu import ROW_PARAMS, _gen_params, _oracle_row
 from tests.test_multi_verify_gpu import ROWS, SLOTS, _fill, _wrong_at
 from tests import test_multi_mla_gpu as mla
@@ -142,7 +141,7 @@ def _smp_same(a, b):
     assert np.array_equal(a[0], b[0]), "seen bitmap"
 
 
-def _strace(st, d, prompt, first, n, test_slot, ref_slot, params, seed, at=(), snap=_snap):
+def _strace(st, d, prompt, first, n, test_slot, ref_slot, params, seed, at=(), K=Gqa):
     """the prompt into both slots, the same sampler on both; the reference slot then draws n tokens by step_multi_sample, one at a time.  toks[k] = the
     token step k consumes, smp[k] = the reference's sampler after k steps, snaps[k] (k in `at`) = its slot state after k steps"""
     st.reset_decode_state(d["kv_max"])
@@ -155,22 +154,22 @@ def _strace(st, d, prompt, first, n, test_slot, ref_slot, params, seed, at=(), s
     tr = dict(p0=p0, toks=[first], smp=[st.slot_sampler_state(ref_slot)], snaps={}, ref=ref_slot)
     for k in range(n + 1):
         if k in at:
-            tr["snaps"][k] = _slot_state(st, d, ref_slot, p0 + k, snap)
+            tr["snaps"][k] = slot_state(K, st, d, ref_slot, p0 + k)
         if k < n:
             tr["toks"].append(st.step_multi_sample([ref_slot], [tr["toks"][k]], [p0 + k])[0])
             tr["smp"].append(st.slot_sampler_state(ref_slot))
     return tr
 
 
-def _check(st, d, slot, tr, k, snap=_snap, same=_same):
-    same(_slot_state(st, d, slot, tr["p0"] + k, snap), tr["snaps"][k])
+def _check(st, d, slot, tr, k, K=Gqa):
+    K.same(slot_state(K, st, d, slot, tr["p0"] + k), tr["snaps"][k])
     _smp_same(st.slot_sampler_state(slot), tr["smp"][k])
 
 
-def _all_right(st, d, snap=_snap, same=_same):
+def _all_right(st, d, K=Gqa):
     rng = np.random.default_rng(5)
     params, seeds = _gen_params(len(ROWS))
-    trs = [_strace(st, d, _toks(rng, d, p), _toks(rng, d, 1)[0], c + 1, s, 7 + i, params[i], seeds[i], (c,), snap)
+    trs = [_strace(st, d, _toks(rng, d, p), _toks(rng, d, 1)[0], c + 1, s, 7 + i, params[i], seeds[i], (c,), K)
            for i, ((p, c), s) in enumerate(zip(ROWS, SLOTS))]
     runs = [tr["toks"][:c] for tr, (_, c) in zip(trs, ROWS)]
     ids, nm = st.verify_multi_sample(SLOTS, runs, [tr["p0"] for tr in trs])
@@ -179,7 +178,7 @@ def _all_right(st, d, snap=_snap, same=_same):
         assert nm[i] == c - 1, ("n_match", i)
     st.commit_multi([c for _, c in ROWS])
     for tr, (_, c), s in zip(trs, ROWS, SLOTS):
-        _check(st, d, s, tr, c, snap, same)
+        _check(st, d, s, tr, c, K)
     nxt = st.step_multi_sample(SLOTS, [g[-1] for g in ids], [tr["p0"] + c for tr, (_, c) in zip(trs, ROWS)])
     assert nxt == [tr["toks"][c + 1] for tr, (_, c) in zip(trs, ROWS)]        # the slots and their samplers continue as the references do
 
@@ -189,15 +188,15 @@ def _all_right(st, d, snap=_snap, same=_same):
 def test_all_drafts_right(cfg, loop):
     if cfg.get("mla"):
         st, eng, keep, d = mla._build(False, kv_max=64, **mla.CFGS[1])
-        snap, same = mla._snap, mla._same
+        K = Mla
     else:
         st, eng, orc, keep, d = build(kv_max=64, **{k: v for k, v in cfg.items() if k != "fp8"})
-        snap, same = _snap, _same
+        K = Gqa
         if cfg.get("fp8"):
             st.set_kv_dtype(True); d["fp8"] = True
     st.set_option("multi_sample_loop", loop)
     st.create_slots(12, 60)
-    _all_right(st, d, snap, same)
+    _all_right(st, d, K)
 
 
 @pytest.mark.parametrize("loop", [0, 1])
@@ -258,7 +257,7 @@ def test_the_verify_writes_nothing():
     st.set_slot_sampler(1, 4, 0.0, 0, 1.0, 1.5, 98)
     st.set_slot_sampler(2, 5, 1.3, 0, 0.8, 0.0, 97)
     plen = [len(o) for o in others]
-    state = lambda: [(_slot_state(st, d, s, p), st.slot_sampler_state(s)) for s, p in zip(range(3), plen)]
+    state = lambda: [(slot_state(Gqa, st, d, s, p), st.slot_sampler_state(s)) for s, p in zip(range(3), plen)]
     before = state()
 
     def run(between):
@@ -281,7 +280,7 @@ def test_the_verify_writes_nothing():
     assert got[0] == ref[0] and got[2] == ref[2] and got[4] == ref[4]
     assert np.array_equal(got[1], ref[1]) and np.array_equal(got[3], ref[3])
     for (sa, ma), (sb, mb) in zip(state(), before):
-        _same(sa, sb); _smp_same(ma, mb)
+        Gqa.same(sa, sb); _smp_same(ma, mb)
 
 
 def test_independence_of_rows():
@@ -300,7 +299,7 @@ def test_independence_of_rows():
         st.reset_decode_state(d["kv_max"]); st.load_slot(s, p); st.save_slot(6 + i, p)
         g, m = st.verify_multi_sample([6 + i], [run], [p])
         st.commit_multi([m[0] + 1])
-        alone.append((g[0][:m[0] + 1], m[0], _slot_state(st, d, 6 + i, p + m[0] + 1), st.slot_sampler_state(6 + i)))
+        alone.append((g[0][:m[0] + 1], m[0], slot_state(Gqa, st, d, 6 + i, p + m[0] + 1), st.slot_sampler_state(6 + i)))
         runs.append(run); pos.append(p)
     assert [m for _, m, _, _ in alone] == [0, 3, 4, 0, 1, 10]
     order = [5, 2, 0, 4, 1, 3]
@@ -309,7 +308,7 @@ def test_independence_of_rows():
     st.commit_multi([m + 1 for m in nm])
     for r, i in enumerate(order):
         assert nm[r] == alone[i][1] and ids[r][:nm[r] + 1] == alone[i][0], ("alone", i)
-        _same(_slot_state(st, d, slots[i], pos[i] + nm[r] + 1), alone[i][2])
+        Gqa.same(slot_state(Gqa, st, d, slots[i], pos[i] + nm[r] + 1), alone[i][2])
         _smp_same(st.slot_sampler_state(slots[i]), alone[i][3])
 
 
@@ -338,7 +337,7 @@ def _lookup_equals_generate(st, d, n_rows, max_draft, cases, check_stats):
         got = st.generate_multi_lookup_sample(A, firsts, pos, n_tok, contexts=ctx, max_draft=max_draft, stop_ids=stops, **smp)
         assert got == want
         for a, b, p, w in zip(A, B, pos, want):
-            _same(_slot_state(st, d, a, p + len(w)), _slot_state(st, d, b, p + len(w)))
+            Gqa.same(slot_state(Gqa, st, d, a, p + len(w)), slot_state(Gqa, st, d, b, p + len(w)))
             _smp_same(st.slot_sampler_state(a), st.slot_sampler_state(b))
         if repeat:
             check_stats(st.last_multi_lookup_stats, n_tok)
@@ -410,12 +409,12 @@ def test_refusals_and_the_pending_state():
     st.save_slot(2, 10)
     st.set_slot_sampler(1, 2, 0.6, 50, 0.95, 0.5, 0x5EED)
     st.set_slot_sampler(2, 5, 0.0, 0, 1.0, 1.5, 3)
-    state = lambda: (_slot_state(st, d, 1, 20), _slot_state(st, d, 2, 10))
+    state = lambda: (slot_state(Gqa, st, d, 1, 20), slot_state(Gqa, st, d, 2, 10))
     want, want_smp = state(), [st.slot_sampler_state(s) for s in (1, 2)]
 
     def unchanged():                                           # (load_slot inside: only while nothing is pending)
         for g, w in zip(state(), want):
-            _same(g, w)
+            Gqa.same(g, w)
 
     def samplers_unchanged():
         for s, w in zip((1, 2), want_smp):

@@ -10,10 +10,11 @@ import functools
 import numpy as np
 import pytest
 
+from tests.slots import Gqa, Mla, options_reset, slot_state
 from tests.test_decode_gpu import MIXED, build
-from tests.test_multi_mla_gpu import CFGS as MLA_CFGS, _build as build_mla, _same as mla_same, _snap as mla_snap
+from tests.test_multi_mla_gpu import CFGS as MLA_CFGS, _build as build_mla
 from tests.test_multi_seq_gpu import DV64, LA4
-from tests.test_speculative_gpu import CFGS, _same, _snap
+from tests.test_speculative_gpu import CFGS
 
 pytestmark = pytest.mark.gpu
 F = np.float32
@@ -24,17 +25,11 @@ ptr = lambda a: a.ctypes.data
 _stores = []
 
 
-@pytest.fixture(autouse=True)
-def options_off_afterwards():
-    yield
-    for st in _stores:
-        for o in (OPT, "multi_attn_exact_split", "gguf_exact_pass", GROUP):
-            st.set_option(o, 0)
-        st.set_option(MAX, 16)
-        st.set_attention_mode(False)
+options_off_afterwards = options_reset(_stores, (OPT, "multi_attn_exact_split", "gguf_exact_pass", GROUP, (MAX, 16)))
 
 
-def _bits(x):
+def _f32_bits(x):
+    """unlike slots.bits, this one casts to f32 first"""
     return np.ascontiguousarray(x, F).view(U).copy()
 
 
@@ -81,7 +76,7 @@ def test_matmul_rows_equals_matmul_row_by_row(bits, K):
         ref = _row_by_row(st, wid[bits, K, N], xs[K], N)      # once per matrix, shared by every row count
         for R in ROWS:
             got = _rows(st, wid[bits, K, N], xs[K][:R], N)
-            assert np.array_equal(_bits(got), _bits(ref[:R])), (bits, K, N, R)
+            assert np.array_equal(_f32_bits(got), _f32_bits(ref[:R])), (bits, K, N, R)
 
 
 @pytest.mark.parametrize("group", [0, 1, 3, 4, 8, 16])
@@ -94,7 +89,7 @@ def test_matmul_rows_k4096_row_groups(bits, group):
     ref = _row_by_row(st, wid[bits, K, N], xs[K], N)
     st.set_option(GROUP, group)
     for R in (16, 15, 5):
-        assert np.array_equal(_bits(_rows(st, wid[bits, K, N], xs[K][:R], N)), _bits(ref[:R])), (bits, group, R)
+        assert np.array_equal(_f32_bits(_rows(st, wid[bits, K, N], xs[K][:R], N)), _f32_bits(ref[:R])), (bits, group, R)
 
 
 @pytest.mark.parametrize("bits", [4, 8])
@@ -112,8 +107,8 @@ def test_matmul_rows_zero_rows_and_extreme_values(bits):
     x[3] = ext
     ref = _row_by_row(st, wid[bits, K, N], x, N)
     got = _rows(st, wid[bits, K, N], x, N)
-    assert np.array_equal(_bits(got), _bits(ref))
-    assert not np.any(_bits(got[1])) and not np.any(_bits(got[6]))                 # +0.0 exactly
+    assert np.array_equal(_f32_bits(got), _f32_bits(ref))
+    assert not np.any(_f32_bits(got[1])) and not np.any(_f32_bits(got[6]))                 # +0.0 exactly
 
 
 def test_matmul_rows_refuses_bad_row_counts():
@@ -142,7 +137,7 @@ def _verify_on_off(st, reset, snap, same, V, first=11, start=5, kv_extra=0):
         ref = []
         for i, t in enumerate(toks[:n_ok]):
             st.decode_step(t, start + i)
-            ref.append((_bits(st.read_logits()), st.last_token(), snap(start + i + 1)))
+            ref.append((_f32_bits(st.read_logits()), st.last_token(), snap(start + i + 1)))
         res = {}
         for on in (0, 1):
             st.set_option(OPT, on)
@@ -152,7 +147,7 @@ def _verify_on_off(st, reset, snap, same, V, first=11, start=5, kv_extra=0):
                 greedy, m = st.verify(toks, start)
                 assert m == n_ok - 1 and greedy[:n_ok] == T[:n_ok], (n, wrong, on, greedy, m)
                 st.commit(k)
-                lg, tok = _bits(st.read_logits()), st.last_token()
+                lg, tok = _f32_bits(st.read_logits()), st.last_token()
                 assert np.array_equal(lg, ref[k - 1][0]) and tok == ref[k - 1][1], ("decode_step", n, wrong, on, k)
                 same(snap(start + k), ref[k - 1][2])
                 out.append((list(greedy), m, lg))
@@ -170,14 +165,14 @@ K10 = dict(dims=(256, 512, 512, 10, 128, 128), seed=6)           # 512 experts, 
 def test_verify_equals_decode_step_and_option_off(cfg):
     st, eng, orc, keep, d = build(**cfg)
     _stores.append(st)
-    _verify_on_off(st, d["reset"], lambda upto: _snap(st, d, upto), _same, d["V"])
+    _verify_on_off(st, d["reset"], lambda upto: Gqa.snap(st, d, upto), Gqa.same, d["V"])
 
 
 def test_verify_mla_lora():
     st, eng, keep, d = build_mla(kv_max=32, **MLA_CFGS[1])
     assert MLA_CFGS[1].get("lora")
     _stores.append(st)
-    _verify_on_off(st, lambda: st.reset_decode_state(d["kv_max"]), lambda upto: mla_snap(st, d, upto), mla_same, d["V"], start=0)
+    _verify_on_off(st, lambda: st.reset_decode_state(d["kv_max"]), lambda upto: Mla.snap(st, d, upto), Mla.same, d["V"], start=0)
 
 
 # ---- 3: slots: every call equals the same call with the option off -------------------------------------------------------------------------------------------
@@ -210,12 +205,6 @@ def _fill(st, d, seq, want):
         st.save_slot(s, n)
 
 
-def _slot_state(st, d, slot, upto, mla=False):
-    st.reset_decode_state(d["kv_max"])
-    st.load_slot(slot, upto)
-    return mla_snap(st, d, upto) if mla else _snap(st, d, upto)
-
-
 def _create(st, n, paged=False, **_):
     if paged:
         st.create_slots(n, KV_MAX, page_tokens=PAGE, n_pages=n * (KV_MAX // PAGE))
@@ -238,10 +227,10 @@ def _off_on(st, scenario, split=False, max_rows=16, **_):
 
 def _equal(a, b, where, mla=False):
     assert [int(x) for x in a[0]] == [int(x) for x in b[0]], ("ids", where)
-    assert np.array_equal(_bits(a[1]), _bits(b[1])), ("logits", where)
+    assert np.array_equal(_f32_bits(a[1]), _f32_bits(b[1])), ("logits", where)
     assert len(a[2]) == len(b[2])
     for x, y in zip(a[2], b[2]):
-        (mla_same if mla else _same)(x, y)
+        (Mla if mla else Gqa).same(x, y)
     assert len(a[3]) == len(b[3])
     for x, y in zip(a[3], b[3]):
         assert np.array_equal(x, y), ("sampler state", where)
@@ -271,7 +260,7 @@ def test_step_multi(B, var):
         ids2, lg2 = st.step_multi(slots, list(ids), [p + 1 for p in pos], logits=True)      # a second step over what the first appended
         took.append(st.multi_path_counts()["few"])
         st.set_option(OPT, 0)
-        return list(ids) + list(ids2), np.concatenate([lg, lg2]), [_slot_state(st, d, s, p + 2) for s, p in zip(slots, pos)], []
+        return list(ids) + list(ids2), np.concatenate([lg, lg2]), [slot_state(Gqa, st, d, s, p + 2) for s, p in zip(slots, pos)], []
 
     off, on = _off_on(st, scenario, **var)
     assert took == [0, 2], ("few", took)
@@ -289,7 +278,7 @@ def test_extend_multi_sixteen_rows(var):
         arm()
         ids, lg = st.extend_multi(slots, [list(seq[p:p + c]) for p, c in zip(pos, counts)], pos, logits=True)
         st.set_option(OPT, 0)
-        return ids, lg, [_slot_state(st, d, s, p + c) for s, p, c in zip(slots, pos, counts)], []
+        return ids, lg, [slot_state(Gqa, st, d, s, p + c) for s, p, c in zip(slots, pos, counts)], []
 
     off, on = _off_on(st, scenario, **var)
     _equal(on, off, ("extend_multi", var))
@@ -321,7 +310,7 @@ def test_verify_multi_and_commit(var):
         st.commit_multi(keep)
         st.set_option(OPT, 0)
         ids = [x for row, m in zip(g1, nm1) for x in row[:m + 1]] + list(nm1) + [x for row, m in zip(g2, nm2) for x in row[:m + 1]] + list(nm2)
-        return ids, np.zeros(1, F), [_slot_state(st, d, s, p + k) for s, p, k in zip(slots, pos, keep)], []
+        return ids, np.zeros(1, F), [slot_state(Gqa, st, d, s, p + k) for s, p, k in zip(slots, pos, keep)], []
 
     off, on = _off_on(st, scenario, **var)
     _equal(on, off, ("verify_multi", var))
@@ -346,7 +335,7 @@ def test_step_multi_sample(var):
         for s in slots:
             seen, rng_state = st.slot_sampler_state(s)
             extra += [np.asarray(seen), np.asarray([rng_state], np.uint64)]
-        return list(ids) + list(ids2), np.concatenate([lg, lg2]), [_slot_state(st, d, s, p + 2) for s, p in zip(slots, pos)], extra
+        return list(ids) + list(ids2), np.concatenate([lg, lg2]), [slot_state(Gqa, st, d, s, p + 2) for s, p in zip(slots, pos)], extra
 
     off, on = _off_on(st, scenario, **var)
     _equal(on, off, ("step_multi_sample", var))
@@ -365,7 +354,7 @@ def test_step_and_extend_multi_mla(fp8):
         ids, lg = st.extend_multi(slots, [list(seq[p:p + c]) for p, c in zip(pos, counts)], pos, logits=True)
         ids2, lg2 = st.step_multi(slots, list(ids), [p + c for p, c in zip(pos, counts)], logits=True)
         st.set_option(OPT, 0)
-        return list(ids) + list(ids2), np.concatenate([lg, lg2]), [_slot_state(st, d, s, p + c + 1, mla=True) for s, p, c in zip(slots, pos, counts)], []
+        return list(ids) + list(ids2), np.concatenate([lg, lg2]), [slot_state(Mla, st, d, s, p + c + 1) for s, p, c in zip(slots, pos, counts)], []
 
     off, on = _off_on(st, scenario)
     _equal(on, off, ("mla", fp8), mla=True)
@@ -393,7 +382,7 @@ def test_step_multi_other_geometries(cfg):
         arm()
         ids, lg = st.step_multi(slots, [seq[p] for p in pos], pos, logits=True)
         st.set_option(OPT, 0)
-        return ids, lg, [_slot_state(st, d, s, p + 1) for s, p in zip(slots, pos)], []
+        return ids, lg, [slot_state(Gqa, st, d, s, p + 1) for s, p in zip(slots, pos)], []
 
     off, on = _off_on(st, scenario)
     _equal(on, off, ("geometry", sorted(cfg)))
@@ -411,7 +400,7 @@ def test_row_maximum_boundary(T, max_rows):
         arm()
         ids, lg = st.step_multi(slots, [seq[p] for p in pos], pos, logits=True)
         st.set_option(OPT, 0)
-        return ids, lg, [_slot_state(st, d, s, p + 1) for s, p in zip(slots, pos)], []
+        return ids, lg, [slot_state(Gqa, st, d, s, p + 1) for s, p in zip(slots, pos)], []
 
     off, on = _off_on(st, scenario, max_rows=max_rows)
     _equal(on, off, ("boundary", T, max_rows))
@@ -422,7 +411,7 @@ def test_gguf_exact_pass_verify():
     """a store whose routed experts are native GGUF blocks, under "gguf_exact_pass": the routed experts keep their pass, the dense matrices switch; verify of 5"""
     st, eng, orc, keep, d = build(gguf=True, dims=(256, 512, 8, 3, 256, 128), seed=11)
     st.set_option("gguf_exact_pass", 1)
-    _verify_on_off(st, d["reset"], lambda upto: _snap(st, d, upto), _same, d["V"])      # runs of 1, 2, 5 and 16 tokens; every row's logits through commit(k)
+    _verify_on_off(st, d["reset"], lambda upto: Gqa.snap(st, d, upto), Gqa.same, d["V"])      # runs of 1, 2, 5 and 16 tokens; every row's logits through commit(k)
     st.set_option("gguf_exact_pass", 0)
 
 
@@ -450,10 +439,10 @@ def test_gemm_fast_prefill_keeps_its_bits():
         st.set_option(OPT, on)
         st.reset_decode_state(d["kv_max"])
         tok = st.prefill(list(seq[:8]), 0)
-        res.append((tok, _bits(st.read_logits()), _snap(st, d, 8)))
+        res.append((tok, _f32_bits(st.read_logits()), Gqa.snap(st, d, 8)))
         st.set_option(OPT, 0); st.set_attention_mode(False)
     assert res[0][0] == res[1][0] and np.array_equal(res[0][1], res[1][1])
-    _same(res[0][2], res[1][2])
+    Gqa.same(res[0][2], res[1][2])
 
 
 def test_exact_prefill_of_few_tokens_equals_option_off_and_decode_step():
@@ -462,11 +451,11 @@ def test_exact_prefill_of_few_tokens_equals_option_off_and_decode_step():
     st.reset_decode_state(d["kv_max"])
     for i, t in enumerate(seq[:8]):
         st.decode_step(t, i)
-    ref = (st.last_token(), _bits(st.read_logits()), _snap(st, d, 8))
+    ref = (st.last_token(), _f32_bits(st.read_logits()), Gqa.snap(st, d, 8))
     for on in (0, 1):
         st.set_option(OPT, on)
         st.reset_decode_state(d["kv_max"])
         tok = st.prefill(list(seq[:8]), 0)
-        assert tok == ref[0] and np.array_equal(_bits(st.read_logits()), ref[1]), on
-        _same(_snap(st, d, 8), ref[2])
+        assert tok == ref[0] and np.array_equal(_f32_bits(st.read_logits()), ref[1]), on
+        Gqa.same(Gqa.snap(st, d, 8), ref[2])
         st.set_option(OPT, 0)

@@ -7,32 +7,11 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from tests.slots import Gqa
 from tests.test_decode_gpu import build
 
 pytestmark = pytest.mark.gpu
 F = np.float32
-
-
-def _snap(st, d, upto):
-    """conv + recurrent states of every linear-attention layer (u32 bits), KV rows [0, upto) of every GQA layer"""
-    out = []
-    for li, kind in enumerate(d["kinds"]):
-        if kind == "la":
-            cs = np.empty(d["conv_dim"] * 4, F); rs = np.empty(d["nv"] * d["dk"] * d["dv"], F)
-            st.get_decode_state(li, None, None, cs, rs); out.append(("la", li, cs.view(np.uint32).copy(), rs.view(np.uint32).copy()))
-        else:
-            esz = np.uint8 if d.get("fp8") else np.uint16
-            kc = np.empty((d["kv_max"], d["nkv"] * d["hd"]), esz); vc = np.empty_like(kc)
-            st.get_decode_state(li, kc, vc, None, None); out.append(("kv", li, kc[:upto].copy(), vc[:upto].copy()))
-    return out
-
-
-def _same(a, b):
-    assert len(a) == len(b)
-    for x, y in zip(a, b):
-        assert x[0] == y[0] and x[1] == y[1]
-        assert np.array_equal(x[2], y[2]), (x[0], x[1], "conv" if x[0] == "la" else "k")
-        assert np.array_equal(x[3], y[3]), (x[0], x[1], "recur" if x[0] == "la" else "v")
 
 
 def _sequential(st, d, toks, start):
@@ -40,7 +19,7 @@ def _sequential(st, d, toks, start):
     out = []
     for i, t in enumerate(toks):
         st.decode_step(t, start + i)
-        out.append((st.read_logits().view(np.uint32).copy(), st.last_token(), _snap(st, d, start + i + 1)))
+        out.append((st.read_logits().view(np.uint32).copy(), st.last_token(), Gqa.snap(st, d, start + i + 1)))
     return out
 
 
@@ -48,7 +27,7 @@ def _check_state(st, d, ref, n_keep, start):
     lg, tok, snap = ref[n_keep - 1]
     assert np.array_equal(st.read_logits().view(np.uint32), lg)
     assert st.last_token() == tok
-    _same(_snap(st, d, start + n_keep), snap)
+    Gqa.same(Gqa.snap(st, d, start + n_keep), snap)
 
 
 CFGS = [dict(), dict(norm_bias_one=False, scoring=0, rsf=2.5), dict(with_dense=True), dict(wbits=8, with_dense=True), dict(la_dkdv=(64, 64), seed=4)]
@@ -112,7 +91,7 @@ def test_truncated_commit():
 
 
 def _state_after(st, d, upto):
-    return st.last_token(), st.read_logits().view(np.uint32).copy(), _snap(st, d, upto)
+    return st.last_token(), st.read_logits().view(np.uint32).copy(), Gqa.snap(st, d, upto)
 
 
 def _compare_lookup(st, d, reset, first, start, max_tokens, context, max_draft, ngram_max, stop_ids=()):
@@ -124,7 +103,7 @@ def _compare_lookup(st, d, reset, first, start, max_tokens, context, max_draft, 
     assert out == ref, (out, ref)
     tok, lg, snap = _state_after(st, d, start + len(out))
     assert tok == ref_state[0] and np.array_equal(lg, ref_state[1])
-    _same(snap, ref_state[2])
+    Gqa.same(snap, ref_state[2])
     return ref, st.last_lookup_stats
 
 
@@ -199,7 +178,7 @@ def test_generate_lookup_at_the_cache_boundary():
         assert got == ref, (got, ref)
         tok, lg, snap = _state_after(st, d, kv)
         assert tok == ref_state[0] and np.array_equal(lg, ref_state[1])
-        _same(snap, ref_state[2])
+        Gqa.same(snap, ref_state[2])
     assert ref[0] != 0 and "kv_max_seq" in ref[1]
 
 
