@@ -33,6 +33,7 @@ struct KrPfChunkTiles {
     int C, t0, pos0;
     __device__ __forceinline__ KrPfChunkTiles(const Args& a, int Ck, int tq) : C(Ck), t0(blockIdx.x * tq), pos0(a.pos0) {}
     __device__ __forceinline__ int row(int t) const { return t; }
+    static __device__ __forceinline__ const void* cache(const Args& a, int h) { return h ? a.v_cache : a.k_cache; }
 };
 
 // ------------------------------------------------------------------------------------------------------------------------------------

@@ -39,11 +39,23 @@ struct DLayer {
 // MLA: compressed-KV rows [n][max_seq][klr] and rope-key rows [n][max_seq][rd] (docs/design/15-multi-mla.md)
 struct kr_multi_state {
     int n_slots = 0, max_seq = 0, kv_fp8 = 0;
-    std::vector<DevBuf> a, b;                  // per layer: LA conv / recurrent state, GQA K / V, MLA latent / rope-key rows
-    std::vector<size_t> a_stride, b_stride;    // per layer: bytes per slot
-    std::vector<size_t> a_row, b_row;          // per GQA / MLA layer: bytes of one cache row of a / b (one position; a slot is max_seq of them, a page page_tokens)
-    // paged slots (kr_decode_slots_create_paged, docs/design/21-paged-slots.md): a / b of a GQA or MLA layer are then pools [n_pages][page_tokens][row] shared by
-    // all slots and a_stride / b_stride the bytes of one page.  pg: the free list, the page table and the queue of mappings the device has not seen yet, all on
+    // one record per store layer (docs/design/40-slot-cache-view.md).  kind = the layer's ATTN_*; buf[0] / buf[1] = LA conv / recurrent state, GQA K / V rows, MLA
+    // latent / rope-key rows; unit[h] = the bytes of one unit of buf[h]: a slot, or on paged slots a page of a GQA / MLA layer; row[h] = the bytes of one row: one
+    // position of a GQA / MLA cache (a slot is max_seq of them, a page page_tokens), the whole state of a linear-attention layer (its unit is one row)
+    struct Layer {
+        int kind = ATTN_NONE; DevBuf buf[2]; size_t unit[2] = {0, 0}, row[2] = {0, 0};
+        bool cached() const { return kind == ATTN_GQA || kind == ATTN_MLA; }      // rows per position: what pages hold, and what a sequence length cuts
+    };
+    std::vector<Layer> layers;
+    // the cache view of a layer (kr_slot_cache.h): what the args builders hand to the kernels and every host-side walk of the slots asks
+    KrSlotCache cache(size_t li) const {
+        const Layer& l = layers[li];
+        KrSlotCache c{{l.buf[0].p, l.buf[1].p}, {l.unit[0], l.unit[1]}, {l.row[0], l.row[1]}, {nullptr, 0, 0}, kv_fp8};
+        if (pg.paged() && l.cached()) c.pg = KrSlotPages{(const int*)pg_table.p, pg.stride, pg.shift};
+        return c;
+    }
+    // paged slots (kr_decode_slots_create_paged, docs/design/21-paged-slots.md): the buffers of a GQA or MLA layer are then pools [n_pages][page_tokens][row] shared by
+    // all slots, their unit a page.  pg: the free list, the page table and the queue of mappings the device has not seen yet, all on
     // the host: the pool owns the queue and prunes it whenever entries are given back; pg_flush only carries out its plan.  pg_table: the table's device copy;
     // pg_pools: KrPagePoolDev of every pool; pg_new: the ids of the pages a pass has to zero
     KrPagePool pg; DevBuf pg_table, pg_pools, pg_new; int pg_npools = 0;

@@ -66,6 +66,21 @@ int multi_begin(kr_decode_store* s) {
 int slot_in_range(kr_decode_store* s, int slot) {
     return slot < 0 || slot >= s->multi->n_slots ? kr_fail(KR_ERR_VALUE, "slot %d out of range [0, %d)", slot, s->multi->n_slots) : KR_OK;
 }
+// "distinct slots, each in range", entry by entry: entry i of a call names `slot`; seen = the slots its earlier entries named ([n_slots], zeroed by the caller).
+// The refusal opens with what the caller calls the entry: open, i, close -- "row 3:" or "dsts[3]:"
+int slot_once(const kr_multi_state& M, std::vector<char>& seen, const char* open, int i, const char* close, int slot) {
+    if (slot < 0 || slot >= M.n_slots) return kr_fail(KR_ERR_VALUE, "%s%d%s slot %d out of range [0, %d)", open, i, close, slot, M.n_slots);
+    if (seen[(size_t)slot]++) return kr_fail(KR_ERR_VALUE, "%s%d%s slot %d is named twice", open, i, close, slot);
+    return KR_OK;
+}
+// flat slots: rows [0, n) of half h of `slot` hold data -- copied from slot `from`, or (from < 0) left as they are -- and the rest of the slot reads as zero
+int slot_rows(const KrSlotCache& c, int h, size_t slot, size_t n, int from, hipStream_t st) {
+    char* d = kr_slot_base<false>(c, h, slot);
+    const size_t head = n * c.row[h];
+    if (from >= 0 && head) KR_HIP(hipMemcpyAsync(d, kr_slot_base<false>(c, h, (size_t)from), head, hipMemcpyDeviceToDevice, st));
+    if (c.unit[h] > head) KR_HIP(hipMemsetAsync(d + head, 0, c.unit[h] - head, st));
+    return KR_OK;
+}
 // ---- paged slots (docs/design/21-paged-slots.md): the GQA / MLA rows live in pools of pages shared by all slots; M.pg is the allocator and the table
 // "multi_attn_fast" reads flat slots only: with that option alone every batched call on paged slots is refused (an option that silently does nothing is a
 // trap); "multi_attn_fast_paged" is the option that reads both kinds (docs/design/23-multi-attn-fast-paged.md)
@@ -156,8 +171,7 @@ int check_args(kr_decode_store* s, const Rows& r, int extra) {
     total = 0;
     for (int i = 0; i < r.n; i++) {
         const int slot = r.slots[i], pos = r.positions[i];
-        if (slot < 0 || slot >= M.n_slots) return kr_fail(KR_ERR_VALUE, "row %d: slot %d out of range [0, %d)", i, slot, M.n_slots);
-        if (seen[(size_t)slot]++) return kr_fail(KR_ERR_VALUE, "row %d: slot %d is named twice", i, slot);
+        if (int rc = slot_once(M, seen, "row ", i, ":", slot)) return rc;
         for (int t = 0; t < r.cnt(i); t++) {
             const int tk = r.tokens[(size_t)total + t];
             if (tk < 0 || tk >= s->vocab) return kr_fail(KR_ERR_VALUE, "row %d: token %d of its run, id %d, out of range (vocab %d)", i, t, tk, s->vocab);
@@ -351,44 +365,50 @@ int slot_copy(kr_decode_store* s, int slot, int seq_len, bool save) {
     if (int rc = pg_flush(M, st)) return rc;
     for (size_t i = 0; i < s->layers.size(); i++) {
         DLayer& L = s->layers[i];
-        if (paged && (L.attn == ATTN_GQA || L.attn == ATTN_MLA)) {      // page by page; a page that is not mapped reads as zero (load only: save has mapped them)
-            const size_t row[2] = {M.a_row[i], M.b_row[i]};
+        if (L.attn == ATTN_NONE) continue;
+        const KrSlotCache c = M.cache(i);
+        const bool cached = M.layers[i].cached();
+        void* own[2] = {cached ? L.kv_k.p : L.conv_state.p, cached ? L.kv_v.p : L.recur_state.p};      // the store's own sequence: its cache rows, or its two states
+        if (c.pg.table) {      // page by page; a page that is not mapped reads as zero (load only: save has mapped them)
             for (int j = 0; j < M.pg.pages_of(seq_len); j++) {
                 const int pg = M.pg.row(slot)[j];
-                const size_t r0 = (size_t)j << M.pg.shift, nr = std::min((size_t)M.pg.page_tokens, (size_t)seq_len - r0);
+                const size_t r0 = (size_t)j * M.pg.page_tokens, nr = std::min((size_t)M.pg.page_tokens, (size_t)seq_len - r0);
                 for (int h = 0; h < 2; h++) {
-                    char* own = (char*)(h ? L.kv_v.p : L.kv_k.p) + r0 * row[h];
-                    char* pool = (char*)(h ? M.b[i].p : M.a[i].p) + (size_t)std::max(pg, 0) * (h ? M.b_stride[i] : M.a_stride[i]);
-                    if (pg < 0) KR_HIP(hipMemsetAsync(own, 0, nr * row[h], st));
-                    else KR_HIP(hipMemcpyAsync(save ? pool : own, save ? own : pool, nr * row[h], hipMemcpyDeviceToDevice, st));
+                    char* mine = (char*)own[h] + r0 * c.row[h];
+                    char* pool = kr_slot_base<false>(c, h, (size_t)kr_slot_page_id(pg));
+                    if (pg < 0) KR_HIP(hipMemsetAsync(mine, 0, nr * c.row[h], st));
+                    else KR_HIP(hipMemcpyAsync(save ? pool : mine, save ? mine : pool, nr * c.row[h], hipMemcpyDeviceToDevice, st));
                 }
             }
             continue;
         }
-        char* a = (char*)M.a[i].p + (size_t)slot * M.a_stride[i];
-        char* b = (char*)M.b[i].p + (size_t)slot * M.b_stride[i];
-        void *sa, *sb; size_t na, nb;
-        if (L.attn == ATTN_LA) { sa = L.conv_state.p; sb = L.recur_state.p; na = M.a_stride[i]; nb = M.b_stride[i]; }
-        else if (L.attn == ATTN_GQA || L.attn == ATTN_MLA) { sa = L.kv_k.p; sb = L.kv_v.p; na = (size_t)seq_len * M.a_row[i]; nb = (size_t)seq_len * M.b_row[i]; }
-        else continue;
-        if (na) KR_HIP(hipMemcpyAsync(save ? (void*)a : sa, save ? sa : (void*)a, na, hipMemcpyDeviceToDevice, st));
-        if (nb) KR_HIP(hipMemcpyAsync(save ? (void*)b : sb, save ? sb : (void*)b, nb, hipMemcpyDeviceToDevice, st));
+        for (int h = 0; h < 2; h++) {      // rows [0, seq_len) of a cache, or the one row that a linear-attention state is; nothing else of the slot is touched
+            char* mine = kr_slot_base<false>(c, h, (size_t)slot);
+            const size_t nb = (cached ? (size_t)seq_len : 1) * c.row[h];
+            if (nb) KR_HIP(hipMemcpyAsync(save ? (void*)mine : own[h], save ? own[h] : (void*)mine, nb, hipMemcpyDeviceToDevice, st));
+        }
     }
     KR_HIP(hipStreamSynchronize(st));
+    return KR_OK;
+}
+// the samplers of every slot, on the first call that needs them (kr_decode_slot_sampler, or the import of an image that carries one): zero seen sets, zero
+// states, greedy parameters
+int ensure_samplers(kr_decode_store* s, hipStream_t st) {
+    kr_multi_state& M = *s->multi;
+    if (!M.smp.empty()) return KR_OK;
+    const size_t words = ((size_t)s->vocab + 31) / 32;
+    if (M.smp_seen.ensure((size_t)M.n_slots * words * 4) || M.smp_rng.ensure((size_t)M.n_slots * 8)) return kr_fail(KR_ERR_HIP, "hipMalloc of the slot samplers failed");
+    KR_HIP(hipMemsetAsync(M.smp_seen.p, 0, M.smp_seen.bytes, st));
+    KR_HIP(hipMemsetAsync(M.smp_rng.p, 0, M.smp_rng.bytes, st));
+    M.smp_words = words;
+    M.smp.assign((size_t)M.n_slots, kr_multi_state::Sampler());
     return KR_OK;
 }
 // the start of kr_decode_generate for one slot (generate_core): seen = {first_token} (if in range), xorshift64 state = rng_seed (0: the wall clock,
 // distinct per slot), parameters kept.  Arguments checked; allocates every slot's sampler state on the first call.
 int set_sampler(kr_decode_store* s, int slot, int first_token, float temperature, int top_k, float top_p, float presence_penalty, uint64_t rng_seed, hipStream_t st) {
     kr_multi_state& M = *s->multi;
-    if (M.smp.empty()) {      // swap_samplers (slot import) allocates the same way: keep the two alike
-        const size_t words = ((size_t)s->vocab + 31) / 32;
-        if (M.smp_seen.ensure((size_t)M.n_slots * words * 4) || M.smp_rng.ensure((size_t)M.n_slots * 8)) return kr_fail(KR_ERR_HIP, "hipMalloc of the slot samplers failed");
-        KR_HIP(hipMemsetAsync(M.smp_seen.p, 0, M.smp_seen.bytes, st));
-        KR_HIP(hipMemsetAsync(M.smp_rng.p, 0, M.smp_rng.bytes, st));
-        M.smp_words = words;
-        M.smp.assign((size_t)M.n_slots, kr_multi_state::Sampler());
-    }
+    if (int rc = ensure_samplers(s, st)) return rc;
     std::vector<uint32_t> seen(M.smp_words, 0u);
     if (first_token >= 0 && first_token < s->vocab) seen[(size_t)first_token >> 5] |= 1u << (first_token & 31);
     if (rng_seed == 0) {
@@ -420,7 +440,8 @@ int verify_records(kr_decode_store* s, size_t T, hipStream_t st) {
         const DLayer& L = s->layers[li];
         if (L.attn != ATTN_LA) continue;
         KrMultiLaCommit E{};
-        E.conv_state = (float*)M.a[li].p; E.conv_stride = M.a_stride[li] / 4; E.recur = (float*)M.b[li].p; E.recur_stride = M.b_stride[li] / 4;
+        const KrSlotCache c = M.cache(li);      // the two states, a slot each; strides in floats (as multi_la_args)
+        E.conv_state = (float*)c.base[0]; E.conv_stride = c.unit[0] / 4; E.recur = (float*)c.base[1]; E.recur_stride = c.unit[1] / 4;
         E.nk = L.nk; E.nv = L.nv; E.dk = L.dk; E.dv = L.dv; E.hr = L.nv / L.nk;
         E.rec_x = take(T * ((size_t)2 * L.nk * L.dk + (size_t)L.nv * L.dv)); E.rec_k = take(T * (size_t)L.nk * L.dk); E.rec_v = take(T * (size_t)L.nv * L.dv);
         E.rec_ge = take(T * (size_t)L.nv); E.rec_be = take(T * (size_t)L.nv);
@@ -631,18 +652,21 @@ static int slots_create(kr_decode_store* s, int n_slots, int max_seq, int page_t
     M->n_slots = n_slots; M->max_seq = max_seq; M->kv_fp8 = s->kv_fp8;
     const size_t nl = s->layers.size(), seq_rows = paged ? (size_t)page_tokens : (size_t)max_seq;      // rows per slot, or per page
     std::vector<KrPagePoolDev> pools, la_pools;
-    M->a.resize(nl); M->b.resize(nl); M->a_stride.assign(nl, 0); M->b_stride.assign(nl, 0); M->a_row.assign(nl, 0); M->b_row.assign(nl, 0);
+    M->layers.resize(nl);
     size_t total = 0;
     for (size_t i = 0; i < nl; i++) {
         const DLayer& L = s->layers[i];
-        if (L.attn == ATTN_LA) { M->a_stride[i] = (size_t)(2 * L.nk * L.dk + L.nv * L.dv) * L.kd * 4; M->b_stride[i] = (size_t)L.nv * L.dk * L.dv * 4; }
-        else if (L.attn == ATTN_GQA) M->a_row[i] = M->b_row[i] = (size_t)L.nkv * L.hd * (s->kv_fp8 ? 1 : 2);
-        else if (L.attn == ATTN_MLA) { M->a_row[i] = (size_t)L.klr * (s->kv_fp8 ? 1 : 2); M->b_row[i] = (size_t)L.rd * (s->kv_fp8 ? 1 : 2); }
-        if (L.attn == ATTN_GQA || L.attn == ATTN_MLA) { M->a_stride[i] = seq_rows * M->a_row[i]; M->b_stride[i] = seq_rows * M->b_row[i]; }
-        const bool pooled = paged && (L.attn == ATTN_GQA || L.attn == ATTN_MLA);
+        kr_multi_state::Layer& R = M->layers[i];
+        const size_t esz = s->kv_fp8 ? 1 : 2;
+        R.kind = L.attn;
+        if (L.attn == ATTN_LA) { R.row[0] = (size_t)(2 * L.nk * L.dk + L.nv * L.dv) * L.kd * 4; R.row[1] = (size_t)L.nv * L.dk * L.dv * 4; }
+        else if (L.attn == ATTN_GQA) R.row[0] = R.row[1] = (size_t)L.nkv * L.hd * esz;
+        else if (L.attn == ATTN_MLA) { R.row[0] = (size_t)L.klr * esz; R.row[1] = (size_t)L.rd * esz; }
+        const bool pooled = paged && R.cached();
         for (int h = 0; h < 2; h++) {
-            DevBuf& d = h ? M->b[i] : M->a[i];
-            const size_t stride = h ? M->b_stride[i] : M->a_stride[i], bytes = stride * (size_t)(pooled ? n_pages : n_slots);
+            DevBuf& d = R.buf[h];
+            R.unit[h] = (R.cached() ? seq_rows : 1) * R.row[h];
+            const size_t stride = R.unit[h], bytes = stride * (size_t)(pooled ? n_pages : n_slots);
             if (!bytes) continue;
             if (pooled && stride % 16) return kr_fail(KR_ERR_VALUE, "layer %zu: a page of %zu bytes is not a multiple of 16", i, stride);
             if (d.ensure(bytes)) return kr_fail(KR_ERR_HIP, "hipMalloc of %d sequence slots (%zu MiB so far) failed", n_slots, (total + bytes) >> 20);
@@ -763,9 +787,8 @@ extern "C" int kr_decode_slot_fork(kr_decode_store* s, int src, int n_dst, const
     if (!dsts) return kr_fail(KR_ERR_VALUE, "null dsts");
     std::vector<char> seen((size_t)M.n_slots, 0);
     for (int i = 0; i < n_dst; i++) {
-        if (dsts[i] < 0 || dsts[i] >= M.n_slots) return kr_fail(KR_ERR_VALUE, "dsts[%d]: slot %d out of range [0, %d)", i, dsts[i], M.n_slots);
         if (dsts[i] == src) return kr_fail(KR_ERR_VALUE, "dsts[%d]: slot %d is src", i, src);
-        if (seen[(size_t)dsts[i]]++) return kr_fail(KR_ERR_VALUE, "dsts[%d]: slot %d is named twice", i, dsts[i]);
+        if (int rc = slot_once(M, seen, "dsts[", i, "]:", dsts[i])) return rc;
     }
     if (seq_len < 0 || seq_len > M.max_seq) return kr_fail(KR_ERR_VALUE, "seq_len %d outside [0, %d] (slot max_seq)", seq_len, M.max_seq);
     const bool paged = M.pg.paged();
@@ -785,17 +808,11 @@ extern "C" int kr_decode_slot_fork(kr_decode_store* s, int src, int n_dst, const
         for (int i = 0; i < n_dst; i++) if (int rc = pg_upload(M, dsts[i], 0, M.pg.stride - 1, st)) return rc;
     }
     for (size_t li = 0; li < s->layers.size() && !paged; li++) {      // flat slots: rows [0, seq_len) copied, the rest zeroed
-        const DLayer& L = s->layers[li];
-        if (L.attn != ATTN_GQA && L.attn != ATTN_MLA) continue;
-        for (int h = 0; h < 2; h++) {
-            const size_t stride = h ? M.b_stride[li] : M.a_stride[li], head = (h ? M.b_row[li] : M.a_row[li]) * (size_t)seq_len;
-            char* base = (char*)(h ? M.b[li].p : M.a[li].p);
-            for (int i = 0; i < n_dst; i++) {
-                char* d = base + (size_t)dsts[i] * stride;
-                if (head) KR_HIP(hipMemcpyAsync(d, base + (size_t)src * stride, head, hipMemcpyDeviceToDevice, st));
-                if (stride > head) KR_HIP(hipMemsetAsync(d + head, 0, stride - head, st));
-            }
-        }
+        if (!M.layers[li].cached()) continue;
+        const KrSlotCache c = M.cache(li);
+        for (int h = 0; h < 2; h++)
+            for (int i = 0; i < n_dst; i++)
+                if (int rc = slot_rows(c, h, (size_t)dsts[i], (size_t)seq_len, src, st)) return rc;
     }
     if (M.la_npools) {      // conv and recurrent state of every linear-attention layer: one launch, a slot being the page
         std::vector<int32_t> ids((size_t)3 * n_dst);
@@ -820,10 +837,10 @@ KrSlotGeo swap_geo(const kr_decode_store* s) {
     KrSlotGeo g;
     g.kv_fp8 = M.kv_fp8; g.hidden = s->hidden; g.vocab = s->vocab;
     for (size_t i = 0; i < s->layers.size(); i++) {
-        const int attn = s->layers[i].attn;
+        const kr_multi_state::Layer& R = M.layers[i];      // the image names a cache by its row bytes and a linear-attention layer by its state bytes
         KrSlotLayerGeo x{KR_SLOT_NONE, 0, 0, 0, 0};
-        if (attn == ATTN_LA) x = KrSlotLayerGeo{KR_SLOT_LA, 0, 0, M.a_stride[i], M.b_stride[i]};
-        else if (attn == ATTN_GQA || attn == ATTN_MLA) x = KrSlotLayerGeo{attn == ATTN_GQA ? KR_SLOT_GQA : KR_SLOT_MLA, M.a_row[i], M.b_row[i], 0, 0};
+        if (R.kind == ATTN_LA) x = KrSlotLayerGeo{KR_SLOT_LA, 0, 0, R.unit[0], R.unit[1]};
+        else if (R.cached()) x = KrSlotLayerGeo{R.kind == ATTN_GQA ? KR_SLOT_GQA : KR_SLOT_MLA, R.row[0], R.row[1], 0, 0};
         g.layers.push_back(x);
     }
     return g;
@@ -833,10 +850,7 @@ int swap_slots_ok(const kr_multi_state& M, int n, const int32_t* slots) {
     if (n < 1 || n > M.n_slots) return kr_fail(KR_ERR_VALUE, "%d slots, must be in [1, %d] (n_slots)", n, M.n_slots);
     if (!slots) return kr_fail(KR_ERR_VALUE, "null slots");
     std::vector<char> seen((size_t)M.n_slots, 0);
-    for (int i = 0; i < n; i++) {
-        if (slots[i] < 0 || slots[i] >= M.n_slots) return kr_fail(KR_ERR_VALUE, "row %d: slot %d out of range [0, %d)", i, slots[i], M.n_slots);
-        if (seen[(size_t)slots[i]]++) return kr_fail(KR_ERR_VALUE, "row %d: slot %d is named twice", i, slots[i]);
-    }
+    for (int i = 0; i < n; i++) if (int rc = slot_once(M, seen, "row ", i, ":", slots[i])) return rc;
     return KR_OK;
 }
 // the staging buffers, the second stream and the events, on first use and whenever the half size changes (nothing is in flight: every call drains its streams)
@@ -854,19 +868,6 @@ int swap_ensure(kr_decode_store* s) {
     }
     return KR_OK;
 }
-// the samplers of every slot, as the first kr_decode_slot_sampler call allocates them: zero seen sets, zero states, greedy parameters.  The twin of the allocation
-// block at the head of set_sampler (which this change leaves as it was): a new sampler buffer or another seen-set layout goes into both
-int swap_samplers(kr_decode_store* s, hipStream_t st) {
-    kr_multi_state& M = *s->multi;
-    if (!M.smp.empty()) return KR_OK;
-    const size_t words = ((size_t)s->vocab + 31) / 32;
-    if (M.smp_seen.ensure((size_t)M.n_slots * words * 4) || M.smp_rng.ensure((size_t)M.n_slots * 8)) return kr_fail(KR_ERR_HIP, "hipMalloc of the slot samplers failed");
-    KR_HIP(hipMemsetAsync(M.smp_seen.p, 0, M.smp_seen.bytes, st));
-    KR_HIP(hipMemsetAsync(M.smp_rng.p, 0, M.smp_rng.bytes, st));
-    M.smp_words = words;
-    M.smp.assign((size_t)M.n_slots, kr_multi_state::Sampler());
-    return KR_OK;
-}
 // one staged range: bytes [r0, r1) of row `row`'s image, its pieces [p0, p1) of the call's list
 struct SwapRange { int row; uint64_t r0, r1; size_t p0, p1; };
 // the pools and the pieces of a call -> the device, and the ranges: every image's payload in chunks of the half size
@@ -874,7 +875,7 @@ int swap_plan(kr_decode_store* s, int n, const int32_t* slots, const std::vector
     kr_multi_state& M = *s->multi;
     const size_t nl = s->layers.size();
     std::vector<KrPagePoolDev> pools(2 * nl + 2, KrPagePoolDev{nullptr, 0});
-    for (size_t i = 0; i < nl; i++) { pools[2 * i] = KrPagePoolDev{M.a[i].p, M.a_stride[i]}; pools[2 * i + 1] = KrPagePoolDev{M.b[i].p, M.b_stride[i]}; }
+    for (size_t i = 0; i < nl; i++) for (int h = 0; h < 2; h++) pools[2 * i + h] = KrPagePoolDev{M.layers[i].buf[h].p, M.layers[i].unit[h]};
     pools[2 * nl] = KrPagePoolDev{M.smp_rng.p, 8}; pools[2 * nl + 1] = KrPagePoolDev{M.smp_seen.p, M.smp_words * 4};
     std::vector<KrSlotPiece> pieces;
     for (int i = 0; i < n; i++) {
@@ -1052,7 +1053,7 @@ extern "C" int kr_decode_slots_import(kr_decode_store* s, int n, const int32_t* 
     if (int rc = swap_ensure(s)) return rc;
     if (int rc = order_after_store(s, st)) return rc;
     SwapDrain drain{st, M.sw_stream};
-    if (any_sampler) if (int rc = swap_samplers(s, st)) return rc;
+    if (any_sampler) if (int rc = ensure_samplers(s, st)) return rc;
     if (paged) {      // the named slots release what they held (as kr_decode_slot_trim(slot, 0)), then map fresh pages, one reference each: an import never shares
         for (int i = 0; i < n; i++) for (int j = 0; j < M.pg.stride; j++) M.pg.drop(slots[i], j, nullptr);
         M.pg.prune();
@@ -1064,11 +1065,8 @@ extern "C" int kr_decode_slots_import(kr_decode_store* s, int n, const int32_t* 
     for (int i = 0; i < n; i++) {
         const size_t slot = (size_t)slots[i];
         for (size_t li = 0; li < s->layers.size() && !paged; li++) {      // flat slots: rows [seq_len, max_seq) zeroed, as fork does
-            if (s->layers[li].attn != ATTN_GQA && s->layers[li].attn != ATTN_MLA) continue;
-            for (int hb = 0; hb < 2; hb++) {
-                const size_t stride = hb ? M.b_stride[li] : M.a_stride[li], head = (hb ? M.b_row[li] : M.a_row[li]) * (size_t)lens[(size_t)i];
-                if (stride > head) KR_HIP(hipMemsetAsync((char*)(hb ? M.b[li].p : M.a[li].p) + slot * stride + head, 0, stride - head, st));
-            }
+            if (!M.layers[li].cached()) continue;
+            for (int hb = 0; hb < 2; hb++) if (int rc = slot_rows(M.cache(li), hb, slot, (size_t)lens[(size_t)i], -1, st)) return rc;
         }
         if (M.smp.empty()) continue;
         kr_multi_state::Sampler p;

@@ -130,7 +130,8 @@ static KrMultiLaArgs multi_la_args(kr_decode_store* s, size_t li, const Scratch&
     KrMultiLaArgs m{};
     m.qkvz = qkvz; m.ld_qkvz = s->weights[L.qkvz_wid]->rows; m.ba = B.pb; m.ld_ba = s->weights[L.ba_wid]->rows;
     m.conv_w = (const float*)L.conv_w.p; m.a_log = (const float*)L.a_log.p; m.dt_bias = (const float*)L.dt_bias.p; m.norm_w = (const float*)L.la_norm_w.p;
-    m.conv_state = (float*)M.a[li].p; m.conv_stride = M.a_stride[li] / 4; m.recur = (float*)M.b[li].p; m.recur_stride = M.b_stride[li] / 4;
+    const KrSlotCache c = M.cache(li);      // the two states, a slot each: the kernels take their strides in floats
+    m.conv_state = (float*)c.base[0]; m.conv_stride = c.unit[0] / 4; m.recur = (float*)c.base[1]; m.recur_stride = c.unit[1] / 4;
     m.conv_out = B.cv; m.out = B.attn; m.ld_out = s->weights[L.out_wid]->cols; m.nk = L.nk; m.nv = L.nv; m.dk = L.dk; m.dv = L.dv; m.hr = L.nv / L.nk; m.scale = L.la_scale; m.eps = s->eps;
     if (P.verify) {
         const KrMultiLaCommit& R = M.v_host[(size_t)M.v_la_of[li]];
@@ -156,9 +157,8 @@ static KrMultiGqaArgs multi_gqa_args(kr_decode_store* s, size_t li, const Scratc
     m.q_norm = L.q_norm_len ? (const float*)L.q_norm.p : nullptr; m.k_norm = L.k_norm_len ? (const float*)L.k_norm.p : nullptr;
     m.q_norm_per_head = L.q_norm_len == L.nh * L.hd; m.k_norm_per_head = L.k_norm_len == L.nkv * L.hd;
     m.rope_cos = (const float*)s->rope_cos.p; m.rope_sin = (const float*)s->rope_sin.p; m.rope_half = s->rope_half;
-    m.k_cache = M.a[li].p; m.v_cache = M.b[li].p; m.slot_elems = M.a_row[li] ? M.a_stride[li] / M.a_row[li] * L.nkv * L.hd : 0; m.kv_fp8 = M.kv_fp8;
+    m.kv = M.cache(li);
     m.q_out = B.q; m.gate = B.gate; m.attn_out = B.attn; m.scores = (float*)M.scores.p; m.sc_ld = pl.sc_ld;
-    if (M.pg.paged()) { m.page_table = (const int*)M.pg_table.p; m.page_stride = M.pg.stride; m.page_shift = M.pg.shift; }      // paged slots: a / b are pools
     m.gated = L.gated; m.nh = L.nh; m.nkv = L.nkv; m.hd = L.hd; m.eps = s->eps; m.sm_scale = L.sm_scale;
     m.xs_split = pl.xs_split;      // "multi_attn_exact_split": the exact per-slot attention as three launches
     if (pl.fd_chunks) { m.fd_o = (float*)M.fd_o.p; m.fd_ml = (float*)M.fd_ml.p; m.fd_chunk = pl.fd_chunk; m.fd_chunks = pl.fd_chunks; }      // "multi_attn_fast", long slots
@@ -174,10 +174,9 @@ static KrMultiMlaArgs multi_mla_args(kr_decode_store* s, size_t li, const Scratc
     m.slots = P.slots; m.positions = P.pos; m.kv_out = B.pb; m.ld_kv = s->weights[L.kva_wid]->rows; m.q_full = B.pa; m.ld_q = L.nh * (L.nd + L.rd);
     m.kv_a_norm = (const float*)L.kv_a_norm.p; m.w_kc = (const float*)L.w_kc.p; m.w_vc = (const float*)L.w_vc.p;
     m.rope_cos = (const float*)L.mla_cos.p; m.rope_sin = (const float*)L.mla_sin.p;
-    m.ckv_cache = M.a[li].p; m.kpe_cache = M.b[li].p; m.ckv_stride = M.a_stride[li]; m.kpe_stride = M.b_stride[li]; m.kv_fp8 = M.kv_fp8;
+    m.kv = M.cache(li);
     m.q_abs = B.q; m.q_pe = B.z; m.attn_lat = B.recur; m.v_proj = B.attn; m.scores = (float*)M.scores.p; m.sc_ld = pl.sc_ld;
     m.nh = L.nh; m.klr = L.klr; m.nd = L.nd; m.rd = L.rd; m.vhd = L.vhd; m.eps = s->eps; m.sm_scale = L.sm_scale;
-    if (M.pg.paged()) { m.page_table = (const int*)M.pg_table.p; m.page_stride = M.pg.stride; m.page_shift = M.pg.shift; }      // paged slots: the strides are a page's bytes
     m.xs_split = pl.mla_xs_split;      // "multi_mla_exact_split": the exact per-slot attention as three launches
     if (pl.mla_chunks) { m.fd_o = (float*)M.fd_o.p; m.fd_ml = (float*)M.fd_ml.p; m.fd_chunk = pl.mla_chunk; m.fd_chunks = pl.mla_chunks; }      // "multi_mla_fast", long slots
     if (pl.mla_runs == KR_MP_RUNS_FLASH) {      // "multi_extend_mla_flash": the runs of >= 2 tokens take the run kernel, the per-row kernels the first nruns rows

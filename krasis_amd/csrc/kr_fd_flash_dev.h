@@ -6,6 +6,7 @@
 #include "kr_device.h"
 #include "kr_libm.h"
 #include "kr_exact_dev.h"
+#include "kr_slot_cache.h"
 
 typedef _Float16 v8h __attribute__((ext_vector_type(8)));
 typedef float v16f __attribute__((ext_vector_type(16)));
@@ -30,7 +31,7 @@ __device__ __forceinline__ int fa_vslot(int pp) { return (pp & ~6) | ((pp & 2) <
 // FA_TK * (HD * 2 + 16) + HD * (FA_TK * 2 + 16) bytes.  Writes the chunk's un-normalised O to fd_o [nkv][n_chunks][G][HD] and (max in log2 units, sum) to
 // fd_ml [nh][n_chunks][2]; leaves at once when the chunk starts past the sequence.
 // PAGED (docs/design/23-multi-attn-fast-paged.md): k_cache / v_cache are pools of pages of 1 << psh positions (psh >= 5) and position p of the sequence is row
-// (ptab[p >> psh] << psh) | (p & mask) of them.  A tile of FA_TK positions starts at a multiple of FA_TK, so it lies in one page, or in two at 32
+// kr_slot_row (kr_slot_cache.h) of them.  A tile of FA_TK positions starts at a multiple of FA_TK, so it lies in one page, or in two at 32
 // positions per page: the two page ids are workgroup-uniform and their byte offsets stay in scalar registers; a lane adds its row's offset inside the page.
 // Only the three cache addresses differ from the flat instantiation: the order of every operation is the same.
 template <int HD, bool FP8, bool PAGED = false>
@@ -73,10 +74,11 @@ __device__ __forceinline__ void kr_fd_flash_body(int seq, int c, int kvh, const 
     // min(p0 + 32, pend - 1), which holds every clamped position of rows 32 .. 63 (the last position itself where the tile ends before them).  Both positions
     // lie in [pbeg, pend), so both entries were mapped by the host before the pass; -1 is never turned into an address all the same
     const size_t rowb = (size_t)kvs * esz;
-    const int pmask = (1 << psh) - 1;
+    const int pmask = kr_slot_mask(psh);
     auto tile_pages = [&](int p0, size_t& lo, size_t& hi) {
-        const int i0 = __builtin_amdgcn_readfirstlane(max(ptab[p0 >> psh], 0)), i1 = __builtin_amdgcn_readfirstlane(max(ptab[min(p0 + 32, pend - 1) >> psh], 0));
-        lo = ((size_t)i0 << psh) * rowb; hi = ((size_t)i1 << psh) * rowb;
+        const int i0 = __builtin_amdgcn_readfirstlane(kr_slot_page_id(ptab[kr_slot_entry(p0, psh)]));
+        const int i1 = __builtin_amdgcn_readfirstlane(kr_slot_page_id(ptab[kr_slot_entry(min(p0 + 32, pend - 1), psh)]));
+        lo = kr_slot_page_row(i0, 0, psh, pmask) * rowb; hi = kr_slot_page_row(i1, 0, psh, pmask) * rowb;
     };
     auto load_k = [&](int p0) {
         [[maybe_unused]] size_t lo = 0, hi = 0;
@@ -84,7 +86,7 @@ __device__ __forceinline__ void kr_fd_flash_body(int seq, int c, int kvh, const 
 #pragma unroll
         for (int j = 0; j < KCH; j++) {
             const int cc = tid + j * 256, row = cc / CPR, dc = cc % CPR, p = min(p0 + row, pend - 1);     // clamped: rows past the end are masked below
-            if constexpr (PAGED) pk[j] = *reinterpret_cast<const u32x4*>(kc + (row >= 32 ? hi : lo) + (size_t)(p & pmask) * rowb + dc * 16);
+            if constexpr (PAGED) pk[j] = *reinterpret_cast<const u32x4*>(kc + (row >= 32 ? hi : lo) + (size_t)kr_slot_in_page(p, pmask) * rowb + dc * 16);
             else pk[j] = *reinterpret_cast<const u32x4*>(kc + (size_t)p * kvs * esz + dc * 16);
         }
     };
@@ -99,7 +101,7 @@ __device__ __forceinline__ void kr_fd_flash_body(int seq, int c, int kvh, const 
                 u32x4 va, vb;
                 if constexpr (PAGED) {      // p is even: p and p + 1 share a page, and so do their clamped forms
                     const int pa = min(p, pend - 1), pb = min(p + 1, pend - 1);
-                    const unsigned char* ra = vc + (pp >= 16 ? hi : lo) + (size_t)(pa & pmask) * rowb + dc * 16;
+                    const unsigned char* ra = vc + (pp >= 16 ? hi : lo) + (size_t)kr_slot_in_page(pa, pmask) * rowb + dc * 16;
                     va = *reinterpret_cast<const u32x4*>(ra); vb = *reinterpret_cast<const u32x4*>(ra + (size_t)(pb - pa) * rowb);
                 } else {
                     va = *reinterpret_cast<const u32x4*>(vc + (size_t)min(p, pend - 1) * kvs * esz + dc * 16);

@@ -18,6 +18,7 @@
 #pragma once
 #include "kr_device.h"
 #include "kr_libm.h"
+#include "kr_slot_cache.h"
 
 typedef _Float16 v8h __attribute__((ext_vector_type(8)));
 typedef float v16f __attribute__((ext_vector_type(16)));
@@ -40,7 +41,7 @@ __device__ __forceinline__ uint32_t mf_f2h2(float a, float b) { return __builtin
 // fd_o [chunk][row][KLR] and (max in log2 units, sum) at fd_ml [row][n_chunks][2] for kr_fd_merge2_body (kr_fd_flash_dev.h); one that starts past the
 // current length leaves at once.
 // PAGED (docs/design/24-multi-mla-fast.md): ckv_cache / kpe_cache are pools of pages of 1 << psh positions (psh >= 5) and position p is row
-// (ptab[p >> psh] << psh) | (p & mask) of both.  A tile of MF_TK positions starts at a multiple of MF_TK, so it lies in ONE page: the page id is
+// kr_slot_row (kr_slot_cache.h) of both.  A tile of MF_TK positions starts at a multiple of MF_TK, so it lies in ONE page: the page id is
 // workgroup-uniform and the page's byte offsets in the two pools stay in scalar registers; a lane adds its row's offset inside the page.  Only the cache
 // addresses differ from the flat instantiation: the order of every operation is the same.
 // RowMap (docs/design/27-multi-extend-mla-flash.md): the rows above are the caller's own count from 0; rmap(row) is where that row lies in q_abs / q_pe / attn_lat.
@@ -99,13 +100,13 @@ __device__ __forceinline__ void kr_mla_flash_body(const float* q_abs, const floa
     const unsigned char* cc = reinterpret_cast<const unsigned char*>(ckv_cache);
     const unsigned char* cr = reinterpret_cast<const unsigned char*>(kpe_cache);
     constexpr int esz = FP8 ? 1 : 2;
-    [[maybe_unused]] const int pmask = (1 << psh) - 1;
+    [[maybe_unused]] const int pmask = kr_slot_mask(psh);
     u32x4 pa[UPT], pb[UPT];
     auto load_tile = [&](int p0) {
         // PAGED: p0 < kv_end at every call, so the entry of its page was mapped by the host before the pass; -1 is never turned into an address all the same
         [[maybe_unused]] size_t pgc = 0, pgr = 0;               // byte offsets of the tile's page in the latent pool and in the rope-key pool
         if constexpr (PAGED) {
-            const size_t r0 = (size_t)__builtin_amdgcn_readfirstlane(max(ptab[p0 >> psh], 0)) << psh;
+            const size_t r0 = kr_slot_page_row(__builtin_amdgcn_readfirstlane(kr_slot_page_id(ptab[kr_slot_entry(p0, psh)])), 0, psh, pmask);      // the page's first row
             pgc = r0 * (size_t)(KLR * esz); pgr = r0 * (size_t)(RD * esz);
         }
 #pragma unroll
@@ -116,7 +117,7 @@ __device__ __forceinline__ void kr_mla_flash_body(const float* q_abs, const floa
                 const size_t ld = (size_t)(dc < CPC ? KLR : RD) * esz;
                 if constexpr (PAGED) {      // p is even: p and p + 1 share the page
                     const unsigned char* base = dc < CPC ? cc + pgc + (size_t)dc * 16 : cr + pgr + (size_t)(dc - CPC) * 16;
-                    const size_t off = (size_t)(p & pmask) * ld;
+                    const size_t off = (size_t)kr_slot_in_page(p, pmask) * ld;
                     if (p < kv_end) pa[j] = *reinterpret_cast<const u32x4*>(base + off);
                     if (p + 1 < kv_end) pb[j] = *reinterpret_cast<const u32x4*>(base + off + ld);
                 } else {

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "kr_slot_cache.h"
 #include "kr_slot_image.h"
 
 // linear attention over runs of consecutive tokens per slot (the decode step's kr_la_step_kernel arithmetic per token); a step is runs of one token
@@ -80,7 +81,7 @@ struct KrMultiGqaArgs {
     const float *q_in, *k_in, *v_in; int ld_q, ld_k, ld_v;
     const float *q_norm, *k_norm; int q_norm_per_head, k_norm_per_head;
     const float *rope_cos, *rope_sin; int rope_half;
-    void *k_cache, *v_cache; size_t slot_elems; int kv_fp8;   // slot s: cache + s * slot_elems elements, [max_seq][nkv * hd]
+    KrSlotCache kv;                            // the layer's K / V rows of nkv * hd elements (kr_slot_cache.h): flat slots [max_seq][nkv * hd], or pools of pages under kv.pg
     float *q_out, *gate, *attn_out;            // [B][nh * hd]
     float* scores; int sc_ld;                  // scratch [B][nh][sc_ld], sc_ld >= the longest row's pos + 1 rounded up to 32
     // "multi_attn_exact_split" (kr_multi_split.hip, docs/design/30-multi-attn-exact-split.md): non-zero = wherever a launcher below would launch the exact per-slot
@@ -89,12 +90,9 @@ struct KrMultiGqaArgs {
     int xs_split;
     int gated, nh, nkv, hd; float eps, sm_scale;
     // "multi_attn_fast" (kr_multi_flash.hip): split-KV partials [B][nkv][fd_chunks][G][hd] and (max, sum) [B][nh][fd_chunks][2]; fd_chunk positions per
-    // chunk, fd_chunks = the longest row's chunk count.  Null: the exact per-slot kernel (scores is not read when they are set).  With page_table set
+    // chunk, fd_chunks = the longest row's chunk count.  Null: the exact per-slot kernel (scores is not read when they are set).  With kv.pg.table set
     // ("multi_attn_fast_paged", docs/design/23-multi-attn-fast-paged.md) the chunk pass reads the pools through the table
     float *fd_o, *fd_ml; int fd_chunk, fd_chunks;
-    // paged slots (docs/design/21-paged-slots.md): page_table [n_slots][page_stride] on the device, -1 = unmapped; k_cache / v_cache are then pools
-    // [n_pages][1 << page_shift][nkv * hd] and position s of slot b is row (page_table[b][s >> page_shift] << page_shift) | (s & mask).  Null: flat slots
-    const int* page_table; int page_stride, page_shift;
     // "multi_extend_flash" (kr_multi_pf_flash.hip, docs/design/25-multi-extend-flash.md), a pass with a run of >= 2 tokens: pf_runs = the pass's run table,
     // pf_nruns x [slot, off, cnt] (above); pf_tiles = pf_ntiles x [run, t0], the query tiles of the runs of >= 2 tokens (kr_pf_tiles.h); pf_units = the number
     // of runs of one token.  The prep launch covers all B rows; the per-row attention kernels above run over the first pf_nruns rows and leave those of a run
@@ -134,7 +132,7 @@ void kr_launch_multi_xm_pv(const KrMultiGqaArgs& a, const KrMultiXmArgs& x, hipS
 #define KR_MULTI_GQA_LDS_MAX (64 * 1024)
 size_t kr_multi_gqa_lds_bytes(int G, int hd, int page_stride);
 // the flash-decode form of the attention launch (after the prep launch): geometry test, the LDS window of its kernel (once, outside the step; non-zero =
-// refused; the paged instantiations are kernels of their own), the chunk pass + merge over n_chunks chunks (0: launched; a.page_table set: through the table)
+// refused; the paged instantiations are kernels of their own), the chunk pass + merge over n_chunks chunks (0: launched; a.kv.pg.table set: through the table)
 int kr_multi_fd_ok(int nh, int nkv, int hd);
 int kr_multi_fd_prepare(int hd, int fp8, int paged);
 int kr_launch_multi_fd(const KrMultiGqaArgs& a, int B, int n_chunks, hipStream_t st);
@@ -146,7 +144,7 @@ struct KrMultiMlaArgs {
     const float* kv_out; int ld_kv;            // kv_a projection rows [B][ld_kv], [klr | rd] each
     const float* q_full; int ld_q;             // q (or q_b) projection rows [B][ld_q], per head [nd | rd]
     const float *kv_a_norm, *w_kc, *w_vc, *rope_cos, *rope_sin;
-    void *ckv_cache, *kpe_cache; size_t ckv_stride, kpe_stride; int kv_fp8;   // slot s: cache + s * stride BYTES, [max_seq][klr] / [max_seq][rd], FP16 or E4M3
+    KrSlotCache kv;                            // the layer's latent rows [klr] (half 0) and rope-key rows [rd] (half 1), FP16 or E4M3 (kr_slot_cache.h); paged: a stage of KR_MM_ROWS rows lies in one page
     float *q_abs, *q_pe, *attn_lat, *v_proj;   // [B][nh * klr], [B][nh * rd], [B][nh * klr], [B][nh * vhd]
     float* scores; int sc_ld;                  // scratch [B][nh][sc_ld], sc_ld >= the longest row's pos + 1 rounded up to 32
     int nh, klr, nd, rd, vhd; float eps, sm_scale;
@@ -155,11 +153,9 @@ struct KrMultiMlaArgs {
     // attention kernel it launches the scores / softmax / weighted-sum kernels of kr_launch_multi_mla_split over the same rows instead -- the same bits, the same
     // checks first.  0 (the option is off, or the pass is below "multi_mla_exact_split_min"): the one kernel, as ever
     int xs_split;
-    // paged slots, as KrMultiGqaArgs: ckv_cache / kpe_cache are pools [n_pages][1 << page_shift][klr] / [..][rd]; a stage of KR_MM_ROWS rows lies in one page
-    const int* page_table; int page_stride, page_shift;
     // "multi_mla_fast" (kr_multi_mla_flash.hip, docs/design/24-multi-mla-fast.md): split-KV partials [B][fd_chunks][nh][klr] and (max, sum) [B][nh][fd_chunks][2];
     // fd_chunk positions per chunk, fd_chunks = the longest row's chunk count.  Null: the exact per-slot kernel (scores is not read when they are set).  With
-    // page_table set the chunk pass reads the pools through the table
+    // kv.pg.table set the chunk pass reads the pools through the table
     float *fd_o, *fd_ml; int fd_chunk, fd_chunks;
     // "multi_extend_mla_flash" (kr_multi_mla_pf_flash.hip, docs/design/27-multi-extend-mla-flash.md), a non-verify pass with a run of >= 2 tokens: mf_runs = the
     // pass's run table, mf_nruns x [slot, off, cnt] (above); mf_tiles = mf_ntiles x [run, tile_row], the tiles of 64 (token, head) query rows of the runs of >= 2
@@ -181,7 +177,7 @@ int kr_launch_multi_mla(const KrMultiMlaArgs& a, int B, hipStream_t st);
 int kr_launch_multi_mla_split(const KrMultiMlaArgs& a, int rows, hipStream_t st);
 // the flash-decode form of the attention launch (after the prep launch): geometry test (at most 64 heads = one query tile), the LDS window of its kernel
 // (once per slot set, outside the pass; non-zero = refused; every instantiation is a kernel of its own), the chunk pass + merge over a.fd_chunks chunks
-// (0: launched; a.page_table set: through the table)
+// (0: launched; a.kv.pg.table set: through the table)
 int kr_multi_mla_fd_ok(int nh, int klr, int rd);
 int kr_multi_mla_fd_prepare(int klr, int fp8, int paged);
 int kr_launch_multi_mla_fd(const KrMultiMlaArgs& a, int B, hipStream_t st);

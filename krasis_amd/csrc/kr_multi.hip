@@ -272,13 +272,12 @@ __global__ void __launch_bounds__(256) kr_multi_gqa_prep_kernel(const KrMultiGqa
     if (d < hd) {
         if (is_q) a.q_out[(size_t)row * a.nh * hd + (size_t)h * hd + d] = val;
         else {
-            size_t o;
-            if constexpr (PAGED) {
-                const int pg = max(a.page_table[(size_t)a.slots[row] * a.page_stride + (pos >> a.page_shift)], 0);      // mapped by the host before the pass
-                o = (((size_t)pg << a.page_shift) | (size_t)(pos & ((1 << a.page_shift) - 1))) * a.nkv * hd + (size_t)h * hd + d;
-            } else o = (size_t)a.slots[row] * a.slot_elems + (size_t)pos * a.nkv * hd + (size_t)h * hd + d;
-            kr_kv_store(a.k_cache, o, val, a.kv_fp8);
-            kr_kv_store(a.v_cache, o, a.v_in[(size_t)row * a.ld_v + (size_t)h * hd + d], a.kv_fp8);
+            // element of (the row's position, this KV head, d): the slot's first element (paged: the pool's), then the position's row (mapped by the host before the pass)
+            const size_t slot = (size_t)a.slots[row];
+            const size_t o = (kr_slot_base_off<PAGED>(a.kv, 0, slot) >> (a.kv.fp8 ? 0 : 1))
+                           + kr_slot_row<PAGED>(pos, PAGED ? kr_slot_table_row(a.kv.pg, slot) : nullptr, a.kv.pg.shift) * a.nkv * hd + (size_t)h * hd + d;
+            kr_kv_store(a.kv.base[0], o, val, a.kv.fp8);
+            kr_kv_store(a.kv.base[1], o, a.v_in[(size_t)row * a.ld_v + (size_t)h * hd + d], a.kv.fp8);
         }
     }
 }
@@ -302,17 +301,17 @@ __global__ void __launch_bounds__(256) kr_multi_gqa_attn_kernel(const KrMultiGqa
     const int kvh = blockIdx.x, row = blockIdx.y, t = threadIdx.x, lane = t & 63, w = t >> 6;
     if (kr_m_row_in_run(a, row)) return;      // "multi_extend_flash": the last token of a run of >= 2, attended to by the run kernels (workgroup-uniform, ahead of every barrier)
     const int pos = a.positions[row], seq = pos + 1, kvs = a.nkv * HD;
-    const size_t kv0 = PAGED ? (size_t)kvh * HD : (size_t)a.slots[row] * a.slot_elems + (size_t)kvh * HD;      // element of (position 0, this KV head) in the slot (paged: in a page)
+    const size_t kv0 = kr_slot_base_off<PAGED>(a.kv, 0, (size_t)a.slots[row]) / (FP8 ? 1 : 2) + (size_t)kvh * HD;      // element of (position 0, this KV head) in the slot (paged: in a page)
     const int* pgt = reinterpret_cast<const int*>(pt + (size_t)G * KR_MG_PT);      // PAGED: [ceil(seq / page_tokens)] page ids of the slot
-    const int psh = PAGED ? a.page_shift : 0, pmask = (1 << psh) - 1;
+    const int psh = PAGED ? a.kv.pg.shift : 0, pmask = kr_slot_mask(psh);
     if constexpr (PAGED) {
-        const int* src = a.page_table + (size_t)a.slots[row] * a.page_stride;
+        const int* src = kr_slot_table_row(a.kv.pg, (size_t)a.slots[row]);
         int* dst = reinterpret_cast<int*>(pt + (size_t)G * KR_MG_PT);
-        for (int i = t; i < ((seq + pmask) >> psh); i += 256) dst[i] = max(src[i], 0);      // every page of [0, seq) was mapped by the host before the pass
+        for (int i = t; i < kr_slot_entries(seq, psh, pmask); i += 256) dst[i] = kr_slot_page_id(src[i]);      // every page of [0, seq) was mapped by the host before the pass
     }
     // element of (position s, this KV head)
     auto kvat = [&](int s) -> size_t {
-        if constexpr (PAGED) return kv0 + (((size_t)pgt[s >> psh] << psh) | (size_t)(s & pmask)) * kvs;
+        if constexpr (PAGED) return kv0 + kr_slot_page_row(pgt[kr_slot_entry(s, psh)], s, psh, pmask) * kvs;
         else return kv0 + (size_t)s * kvs;
     };
     float* sc = a.scores + ((size_t)row * a.nh + (size_t)kvh * G) * a.sc_ld;        // [G][sc_ld]
@@ -325,7 +324,7 @@ __global__ void __launch_bounds__(256) kr_multi_gqa_attn_kernel(const KrMultiGqa
         for (int s = grp; s < seq; s += 32) {
             float kr[NB];
 #pragma unroll
-            for (int e = 0; e < NB; e++) kr[e] = kr_kv_load(a.k_cache, kvat(s) + e * 8 + l, FP8);
+            for (int e = 0; e < NB; e++) kr[e] = kr_kv_load(a.kv.base[0], kvat(s) + e * 8 + l, FP8);
             for (int g = 0; g < G; g++) {
                 float acc = 0.0f;
 #pragma unroll
@@ -361,7 +360,7 @@ __global__ void __launch_bounds__(256) kr_multi_gqa_attn_kernel(const KrMultiGqa
             for (int s1 = 0; s1 < n; s1 += 16) {
                 float v[16];
 #pragma unroll
-                for (int u = 0; u < 16; u++) v[u] = kr_kv_load(a.v_cache, kvat(s0 + min(s1 + u, n - 1)) + d, FP8);
+                for (int u = 0; u < 16; u++) v[u] = kr_kv_load(a.kv.base[1], kvat(s0 + min(s1 + u, n - 1)) + d, FP8);
 #pragma unroll
                 for (int u = 0; u < 16; u++) {
 #pragma unroll
@@ -390,32 +389,29 @@ size_t kr_multi_gqa_lds_bytes(int G, int hd, int page_stride) {
 
 static int multi_gqa_runs(const KrMultiGqaArgs& a, int B, size_t lds, hipStream_t st);      // below
 int kr_launch_multi_gqa(const KrMultiGqaArgs& a, int B, hipStream_t st) {
-    if ((a.hd != 64 && a.hd != 128 && a.hd != 256) || a.nkv < 1 || a.nh % a.nkv || a.sc_ld % 32) return 1;
+    if ((a.hd != 64 && a.hd != 128 && a.hd != 256) || a.nkv < 1 || a.nh % a.nkv || a.sc_ld % 32 || !kr_slot_stage_fits(a.kv.pg, 32)) return 1;
     const int G = a.nh / a.nkv;
-    const size_t lds = kr_multi_gqa_lds_bytes(G, a.hd, a.page_table ? a.page_stride : 0);
+    const size_t lds = kr_multi_gqa_lds_bytes(G, a.hd, a.kv.pg.table ? a.kv.pg.stride : 0);
     if (a.pf_tiles) return multi_gqa_runs(a, B, lds, st);
     if (a.fd_o) {
         // "multi_attn_fast" / "multi_attn_fast_paged": the same prep launch, then split-KV flash-decode over the slots, flat or paged (kr_multi_flash.hip)
         if (!kr_multi_fd_ok(a.nh, a.nkv, a.hd) || !a.fd_ml || a.fd_chunks < 1 || a.fd_chunks > 1024) return 1;
-        if (a.page_table) {
-            if (a.page_stride < 1 || a.page_shift < 5) return 1;
-            hipLaunchKernelGGL(kr_multi_gqa_prep_kernel<true>, dim3(a.nh + a.nkv, B), dim3(256), 0, st, a);
-        } else hipLaunchKernelGGL(kr_multi_gqa_prep_kernel<false>, dim3(a.nh + a.nkv, B), dim3(256), 0, st, a);
+        if (a.kv.pg.table) hipLaunchKernelGGL(kr_multi_gqa_prep_kernel<true>, dim3(a.nh + a.nkv, B), dim3(256), 0, st, a);
+        else hipLaunchKernelGGL(kr_multi_gqa_prep_kernel<false>, dim3(a.nh + a.nkv, B), dim3(256), 0, st, a);
         return kr_launch_multi_fd(a, B, a.fd_chunks, st);
     }
     if (lds > KR_MULTI_GQA_LDS_MAX) return 1;
 #define KR_MGA(NB_, F_, P_) hipLaunchKernelGGL((kr_multi_gqa_attn_kernel<NB_, F_, P_>), dim3(a.nkv, B), dim3(256), lds, st, a)
 #define KR_MGA_HD(F_, P_) do { if (a.hd == 256) KR_MGA(32, F_, P_); else if (a.hd == 128) KR_MGA(16, F_, P_); else KR_MGA(8, F_, P_); } while (0)
-    if (a.page_table) {
-        if (a.page_stride < 1 || a.page_shift < 5) return 1;
+    if (a.kv.pg.table) {
         hipLaunchKernelGGL(kr_multi_gqa_prep_kernel<true>, dim3(a.nh + a.nkv, B), dim3(256), 0, st, a);
         if (a.xs_split) return kr_launch_multi_gqa_split(a, B, st);      // "multi_attn_exact_split": the same bits from three launches (kr_multi_split.hip)
-        if (a.kv_fp8) KR_MGA_HD(true, true); else KR_MGA_HD(false, true);
+        if (a.kv.fp8) KR_MGA_HD(true, true); else KR_MGA_HD(false, true);
         return 0;
     }
     hipLaunchKernelGGL(kr_multi_gqa_prep_kernel<false>, dim3(a.nh + a.nkv, B), dim3(256), 0, st, a);
     if (a.xs_split) return kr_launch_multi_gqa_split(a, B, st);
-    if (a.kv_fp8) KR_MGA_HD(true, false); else KR_MGA_HD(false, false);
+    if (a.kv.fp8) KR_MGA_HD(true, false); else KR_MGA_HD(false, false);
 #undef KR_MGA_HD
 #undef KR_MGA
     return 0;
@@ -426,11 +422,10 @@ int kr_launch_multi_gqa(const KrMultiGqaArgs& a, int B, hipStream_t st) {
 // leave at once), and not at all without a unit row; then the run kernels over the query tiles
 static int multi_gqa_runs(const KrMultiGqaArgs& a, int B, size_t lds, hipStream_t st) {
     // every check first: the prep launch appends rows to the slots, and a layer fails whole
-    if (a.pf_nruns < 1 || a.pf_nruns > B || a.pf_units < 0 || a.pf_units >= a.pf_nruns || !kr_multi_pf_args_ok(a)) return 1;
-    if (a.page_table && (a.page_stride < 1 || a.page_shift < 5)) return 1;
+    if (a.pf_nruns < 1 || a.pf_nruns > B || a.pf_units < 0 || a.pf_units >= a.pf_nruns || !kr_multi_pf_args_ok(a)) return 1;      // its last clause is the page check
     if (a.pf_units && a.fd_o && (!kr_multi_fd_ok(a.nh, a.nkv, a.hd) || !a.fd_ml || a.fd_chunk < 64 || a.fd_chunks < 1 || a.fd_chunks > 1024)) return 1;
     if (a.pf_units && !a.fd_o && lds > KR_MULTI_GQA_LDS_MAX) return 1;
-    if (a.page_table) hipLaunchKernelGGL(kr_multi_gqa_prep_kernel<true>, dim3(a.nh + a.nkv, B), dim3(256), 0, st, a);
+    if (a.kv.pg.table) hipLaunchKernelGGL(kr_multi_gqa_prep_kernel<true>, dim3(a.nh + a.nkv, B), dim3(256), 0, st, a);
     else hipLaunchKernelGGL(kr_multi_gqa_prep_kernel<false>, dim3(a.nh + a.nkv, B), dim3(256), 0, st, a);
     if (a.pf_units) {
         if (a.fd_o) {
@@ -440,8 +435,8 @@ static int multi_gqa_runs(const KrMultiGqaArgs& a, int B, size_t lds, hipStream_
         } else {
 #define KR_MGR(NB_, F_, P_) hipLaunchKernelGGL((kr_multi_gqa_attn_kernel<NB_, F_, P_>), dim3(a.nkv, a.pf_nruns), dim3(256), lds, st, a)
 #define KR_MGR_HD(F_, P_) do { if (a.hd == 256) KR_MGR(32, F_, P_); else if (a.hd == 128) KR_MGR(16, F_, P_); else KR_MGR(8, F_, P_); } while (0)
-            if (a.page_table) { if (a.kv_fp8) KR_MGR_HD(true, true); else KR_MGR_HD(false, true); }
-            else { if (a.kv_fp8) KR_MGR_HD(true, false); else KR_MGR_HD(false, false); }
+            if (a.kv.pg.table) { if (a.kv.fp8) KR_MGR_HD(true, true); else KR_MGR_HD(false, true); }
+            else { if (a.kv.fp8) KR_MGR_HD(true, false); else KR_MGR_HD(false, false); }
 #undef KR_MGR_HD
 #undef KR_MGR
         }
@@ -457,11 +452,11 @@ int kr_launch_multi_gqa_xm(const KrMultiGqaArgs& a0, const KrMultiXmArgs& x, con
     a.pf_runs = runs; a.pf_nruns = n_runs; a.pf_units = units; a.pf_tiles = nullptr; a.pf_ntiles = 0;
     // every check first: the prep launch appends rows to the slots, and a layer fails whole
     if ((a.hd != 64 && a.hd != 128 && a.hd != 256) || a.nkv < 1 || a.nh % a.nkv || a.sc_ld % 32) return 1;
-    const size_t lds = kr_multi_gqa_lds_bytes(a.nh / a.nkv, a.hd, a.page_table ? a.page_stride : 0);
+    const size_t lds = kr_multi_gqa_lds_bytes(a.nh / a.nkv, a.hd, a.kv.pg.table ? a.kv.pg.stride : 0);
     if (n_runs < 1 || n_runs > B || units < 0 || units >= n_runs || !kr_multi_xm_args_ok(a, x)) return 1;
     if (units && a.fd_o && (!kr_multi_fd_ok(a.nh, a.nkv, a.hd) || !a.fd_ml || a.fd_chunk < 64 || a.fd_chunks < 1 || a.fd_chunks > 1024)) return 1;
     if (units && !a.fd_o && lds > KR_MULTI_GQA_LDS_MAX) return 1;
-    if (a.page_table) hipLaunchKernelGGL(kr_multi_gqa_prep_kernel<true>, dim3(a.nh + a.nkv, B), dim3(256), 0, st, a);
+    if (a.kv.pg.table) hipLaunchKernelGGL(kr_multi_gqa_prep_kernel<true>, dim3(a.nh + a.nkv, B), dim3(256), 0, st, a);
     else hipLaunchKernelGGL(kr_multi_gqa_prep_kernel<false>, dim3(a.nh + a.nkv, B), dim3(256), 0, st, a);
     if (units) {
         if (a.fd_o) {
@@ -471,8 +466,8 @@ int kr_launch_multi_gqa_xm(const KrMultiGqaArgs& a0, const KrMultiXmArgs& x, con
         } else {
 #define KR_MGX(NB_, F_, P_) hipLaunchKernelGGL((kr_multi_gqa_attn_kernel<NB_, F_, P_>), dim3(a.nkv, n_runs), dim3(256), lds, st, a)
 #define KR_MGX_HD(F_, P_) do { if (a.hd == 256) KR_MGX(32, F_, P_); else if (a.hd == 128) KR_MGX(16, F_, P_); else KR_MGX(8, F_, P_); } while (0)
-            if (a.page_table) { if (a.kv_fp8) KR_MGX_HD(true, true); else KR_MGX_HD(false, true); }
-            else { if (a.kv_fp8) KR_MGX_HD(true, false); else KR_MGX_HD(false, false); }
+            if (a.kv.pg.table) { if (a.kv.fp8) KR_MGX_HD(true, true); else KR_MGX_HD(false, true); }
+            else { if (a.kv.fp8) KR_MGX_HD(true, false); else KR_MGX_HD(false, false); }
 #undef KR_MGX_HD
 #undef KR_MGX
         }
@@ -499,14 +494,11 @@ __global__ void __launch_bounds__(64) kr_multi_mla_prep_kernel(const KrMultiMlaA
         return;
     }
     const size_t slot = (size_t)a.slots[row];
-    if constexpr (PAGED) {      // ckv_stride / kpe_stride = bytes of one page; the rope tables are still read at the position itself
-        const size_t pg = (size_t)max(a.page_table[slot * a.page_stride + (pos >> a.page_shift)], 0);      // mapped by the host before the pass
-        kr_mla_append_row<FP8>(a.kv_out + (size_t)row * a.ld_kv, a.kv_a_norm, a.rope_cos, a.rope_sin, (char*)a.ckv_cache + pg * a.ckv_stride,
-                               (char*)a.kpe_cache + pg * a.kpe_stride, pos, a.klr, a.rd, a.eps, sh, pos & ((1 << a.page_shift) - 1));
-    } else {
-        kr_mla_append_row<FP8>(a.kv_out + (size_t)row * a.ld_kv, a.kv_a_norm, a.rope_cos, a.rope_sin, (char*)a.ckv_cache + slot * a.ckv_stride,
-                               (char*)a.kpe_cache + slot * a.kpe_stride, pos, a.klr, a.rd, a.eps, sh);
-    }
+    // the unit that holds the position and the row inside it: the slot and the position, or (PAGED) the page, mapped by the host before the pass; the rope
+    // tables are read at the position itself either way
+    size_t u = slot; int at = -1;
+    if constexpr (PAGED) { u = (size_t)kr_slot_page_id(kr_slot_table_row(a.kv.pg, slot)[kr_slot_entry(pos, a.kv.pg.shift)]); at = kr_slot_in_page(pos, kr_slot_mask(a.kv.pg.shift)); }
+    kr_mla_append_row<FP8>(a.kv_out + (size_t)row * a.ld_kv, a.kv_a_norm, a.rope_cos, a.rope_sin, kr_slot_base<false>(a.kv, 0, u), kr_slot_base<false>(a.kv, 1, u), pos, a.klr, a.rd, a.eps, sh, at);
 }
 
 // Attention of KR_MM_HG heads of row b over the slot's rows [0, pos].  grid (ceil(nh / KR_MM_HG), B), 512 threads.  The latent + rope rows are
@@ -537,17 +529,17 @@ __global__ void __launch_bounds__(512) kr_multi_mla_attn_kernel(const KrMultiMla
     const int seq = a.positions[row] + 1, nst = (seq + ROWS - 1) / ROWS;
     const size_t slot = (size_t)a.slots[row];
     float* sc = a.scores + ((size_t)row * a.nh + hg0) * a.sc_ld;                  // [nhg][sc_ld]
-    const __amdgpu_buffer_rsrc_t srd_c = __builtin_amdgcn_make_buffer_rsrc((char*)a.ckv_cache + (PAGED ? 0 : slot * a.ckv_stride), 0, PAGED ? 0 : seq * klr * esz, 0x00020000);
-    const __amdgpu_buffer_rsrc_t srd_r = __builtin_amdgcn_make_buffer_rsrc((char*)a.kpe_cache + (PAGED ? 0 : slot * a.kpe_stride), 0, PAGED ? 0 : seq * rd * esz, 0x00020000);
-    // PAGED: the page of stage s0 (a multiple of ROWS) -> its id made wave-uniform for the descriptors (-1: none) and the rows of it that are below seq
-    const int psh = PAGED ? a.page_shift : 0, pmask = (1 << psh) - 1;
-    const int* ptab = PAGED ? a.page_table + slot * a.page_stride : nullptr;
-    auto page_of = [&](int s0, int& nrec) -> int {
+    const __amdgpu_buffer_rsrc_t srd_c = __builtin_amdgcn_make_buffer_rsrc(kr_slot_base<PAGED>(a.kv, 0, slot), 0, PAGED ? 0 : seq * klr * esz, 0x00020000);
+    const __amdgpu_buffer_rsrc_t srd_r = __builtin_amdgcn_make_buffer_rsrc(kr_slot_base<PAGED>(a.kv, 1, slot), 0, PAGED ? 0 : seq * rd * esz, 0x00020000);
+    // PAGED: the descriptor of half h (rows of rb bytes) for stage s0, a multiple of ROWS: its page's id made wave-uniform (-1: none), the page's rows below seq
+    const int psh = PAGED ? a.kv.pg.shift : 0, pmask = kr_slot_mask(psh);
+    const int* ptab = PAGED ? kr_slot_table_row(a.kv.pg, slot) : nullptr;
+    auto page_srd = [&](int h, int rb, int s0) {
         int pg = -1;
-        if (s0 < seq) pg = ptab[s0 >> psh];
+        if (s0 < seq) pg = ptab[kr_slot_entry(s0, psh)];
         pg = __builtin_amdgcn_readfirstlane(pg);
-        nrec = pg >= 0 ? min(1 << psh, seq - (s0 & ~pmask)) : 0;
-        return max(pg, 0);
+        const int nrec = pg >= 0 ? min(pmask + 1, seq - (s0 - kr_slot_in_page(s0, pmask))) : 0;
+        return __builtin_amdgcn_make_buffer_rsrc(kr_slot_base<false>(a.kv, h, (size_t)kr_slot_page_id(pg)), 0, nrec * rb, 0x00020000);
     };
     // unconditional loads: rows at or past the current length are outside the descriptors and read as zero
     struct Regs { u32x4 c[NLC]; u32x4 r; };
@@ -555,11 +547,7 @@ __global__ void __launch_bounds__(512) kr_multi_mla_attn_kernel(const KrMultiMla
     const bool has_r = t < ROWS * CPR_R;
     auto issue_c = [&](Regs& R, int s0) {
         __amdgpu_buffer_rsrc_t srd = srd_c; int r0 = s0;      // the descriptor and the first row of the stage inside it
-        if constexpr (PAGED) {
-            int nrec; const int pg = page_of(s0, nrec);
-            srd = __builtin_amdgcn_make_buffer_rsrc((char*)a.ckv_cache + (size_t)pg * a.ckv_stride, 0, nrec * klr * esz, 0x00020000);
-            r0 = s0 & pmask;
-        }
+        if constexpr (PAGED) { srd = page_srd(0, klr * esz, s0); r0 = kr_slot_in_page(s0, pmask); }
 #pragma unroll
         for (int i = 0; i < NLC; i++) {
             const int c = t + 512 * i, r = c / CPR_C, col = c % CPR_C;
@@ -568,11 +556,7 @@ __global__ void __launch_bounds__(512) kr_multi_mla_attn_kernel(const KrMultiMla
     };
     auto issue_r = [&](Regs& R, int s0) {
         __amdgpu_buffer_rsrc_t srd = srd_r; int r0 = s0;
-        if constexpr (PAGED) {
-            int nrec; const int pg = page_of(s0, nrec);
-            srd = __builtin_amdgcn_make_buffer_rsrc((char*)a.kpe_cache + (size_t)pg * a.kpe_stride, 0, nrec * rd * esz, 0x00020000);
-            r0 = s0 & pmask;
-        }
+        if constexpr (PAGED) { srd = page_srd(1, rd * esz, s0); r0 = kr_slot_in_page(s0, pmask); }
         R.r = __builtin_amdgcn_raw_buffer_load_b128(srd, has_r ? (r0 + rrow) * rd * esz + rcol * 16 : 0x7FFFFFF0, 0, 0);
     };
     auto commit_c = [&](const Regs& R) {
@@ -690,9 +674,9 @@ static int multi_mla_runs(KrMultiMlaArgs& a, int B, hipStream_t st) {
 #define KR_MRP(F_, P_) hipLaunchKernelGGL((kr_multi_mla_prep_kernel<F_, P_>), pg, dim3(64), 0, st, a)
 #define KR_MRA(F_, NBC_, P_) hipLaunchKernelGGL((kr_multi_mla_attn_kernel<F_, NBC_, P_>), ag, dim3(512), (kr_multi_mla_lds<F_, NBC_>()), st, a)
 #define KR_MRA_ALL(P_) do { \
-    if (a.kv_fp8) { KR_MRP(true, P_); if (!rows) break; if (a.klr == 512) KR_MRA(true, 64, P_); else KR_MRA(true, 32, P_); } \
+    if (a.kv.fp8) { KR_MRP(true, P_); if (!rows) break; if (a.klr == 512) KR_MRA(true, 64, P_); else KR_MRA(true, 32, P_); } \
     else { KR_MRP(false, P_); if (!rows) break; if (a.klr == 512) KR_MRA(false, 64, P_); else KR_MRA(false, 32, P_); } } while (0)
-    if (a.page_table) KR_MRA_ALL(true); else KR_MRA_ALL(false);
+    if (a.kv.pg.table) KR_MRA_ALL(true); else KR_MRA_ALL(false);
 #undef KR_MRA_ALL
 #undef KR_MRA
 #undef KR_MRP
@@ -710,7 +694,7 @@ static int multi_mla_runs(KrMultiMlaArgs& a, int B, hipStream_t st) {
 int kr_launch_multi_mla(const KrMultiMlaArgs& a_in, int B, hipStream_t st) {
     KrMultiMlaArgs a = a_in;
     if (!kr_multi_mla_ok(a.klr, a.nd, a.rd) || a.nh < 1 || a.sc_ld % 32) return 1;
-    if (a.page_table && (a.page_stride < 1 || (1 << a.page_shift) < KR_MM_ROWS)) return 1;      // a stage must not straddle a page
+    if (!kr_slot_stage_fits(a.kv.pg, KR_MM_ROWS)) return 1;      // a stage must not straddle a page
     static_assert(kr_multi_mla_lds<false, 64>() <= 64 * 1024, "the attention kernel stays inside the default 64 KiB LDS window");
     // "multi_mla_fast" (a.fd_o set): the same absorption and prep launch, then split-KV flash-decode over the slots, flat or paged
     // (kr_multi_mla_flash.hip) in place of the attention kernel; checked before anything is launched
@@ -722,9 +706,9 @@ int kr_launch_multi_mla(const KrMultiMlaArgs& a_in, int B, hipStream_t st) {
 #define KR_MMP(F_, P_) hipLaunchKernelGGL((kr_multi_mla_prep_kernel<F_, P_>), pg, dim3(64), 0, st, a)
 #define KR_MMA(F_, NBC_, P_) hipLaunchKernelGGL((kr_multi_mla_attn_kernel<F_, NBC_, P_>), ag, dim3(512), (kr_multi_mla_lds<F_, NBC_>()), st, a)
 #define KR_MMA_ALL(P_) do { \
-    if (a.kv_fp8) { KR_MMP(true, P_); if (a.fd_o) break; if (a.xs_split) break; if (a.klr == 512) KR_MMA(true, 64, P_); else KR_MMA(true, 32, P_); } \
+    if (a.kv.fp8) { KR_MMP(true, P_); if (a.fd_o) break; if (a.xs_split) break; if (a.klr == 512) KR_MMA(true, 64, P_); else KR_MMA(true, 32, P_); } \
     else { KR_MMP(false, P_); if (a.fd_o) break; if (a.xs_split) break; if (a.klr == 512) KR_MMA(false, 64, P_); else KR_MMA(false, 32, P_); } } while (0)
-    if (a.page_table) KR_MMA_ALL(true); else KR_MMA_ALL(false);
+    if (a.kv.pg.table) KR_MMA_ALL(true); else KR_MMA_ALL(false);
 #undef KR_MMA_ALL
 #undef KR_MMA
 #undef KR_MMP
@@ -748,7 +732,7 @@ int kr_launch_multi_mla_xm(const KrMultiMlaArgs& a0, const KrMultiXmArgs& x, con
     a.mf_runs = runs; a.mf_nruns = n_runs; a.mf_units = units; a.mf_tiles = nullptr; a.mf_ntiles = 0;
     // every check first: the prep launch appends rows to the slots, and a layer fails whole
     if (!kr_multi_mla_ok(a.klr, a.nd, a.rd) || a.nh < 1 || a.sc_ld % 32) return 1;
-    if (a.page_table && (a.page_stride < 1 || (1 << a.page_shift) < KR_MM_ROWS)) return 1;      // a stage of the per-row kernel must not straddle a page
+    if (!kr_slot_stage_fits(a.kv.pg, KR_MM_ROWS)) return 1;      // a stage of the per-row kernel must not straddle a page
     if (n_runs < 1 || n_runs > B || units < 0 || units >= n_runs || !kr_multi_mla_xm_args_ok(a, x)) return 1;
     if (units && a.fd_o && (!kr_multi_mla_fd_ok(a.nh, a.klr, a.rd) || !a.fd_ml || a.fd_chunk < 32 || a.fd_chunk % 32 || a.fd_chunks < 1 || a.fd_chunks > 1024)) return 1;
     a.absorb_done = B >= 32 && kr_launch_mla_absorb_mfma(a.q_full, a.ld_q, a.nd + a.rd, a.nd, a.w_kc, a.klr, a.q_abs, B, a.nh, st) == 0;
@@ -757,9 +741,9 @@ int kr_launch_multi_mla_xm(const KrMultiMlaArgs& a0, const KrMultiXmArgs& x, con
 #define KR_MXP(F_, P_) hipLaunchKernelGGL((kr_multi_mla_prep_kernel<F_, P_>), pg, dim3(64), 0, st, a)
 #define KR_MXR(F_, NBC_, P_) hipLaunchKernelGGL((kr_multi_mla_attn_kernel<F_, NBC_, P_>), ag, dim3(512), (kr_multi_mla_lds<F_, NBC_>()), st, a)
 #define KR_MXR_ALL(P_) do { \
-    if (a.kv_fp8) { KR_MXP(true, P_); if (!rows) break; if (a.klr == 512) KR_MXR(true, 64, P_); else KR_MXR(true, 32, P_); } \
+    if (a.kv.fp8) { KR_MXP(true, P_); if (!rows) break; if (a.klr == 512) KR_MXR(true, 64, P_); else KR_MXR(true, 32, P_); } \
     else { KR_MXP(false, P_); if (!rows) break; if (a.klr == 512) KR_MXR(false, 64, P_); else KR_MXR(false, 32, P_); } } while (0)
-    if (a.page_table) KR_MXR_ALL(true); else KR_MXR_ALL(false);
+    if (a.kv.pg.table) KR_MXR_ALL(true); else KR_MXR_ALL(false);
 #undef KR_MXR_ALL
 #undef KR_MXR
 #undef KR_MXP

@@ -17,15 +17,10 @@ __global__ void __launch_bounds__(256) kr_multi_fd_flash_kernel(const KrMultiGqa
     const int b = blockIdx.z;
     if (kr_m_row_in_run(a, b)) return;      // "multi_extend_flash": the run kernels' row (workgroup-uniform, ahead of every barrier)
     const int seq = a.positions[b] + 1;
-    if constexpr (PAGED) {
-        kr_fd_flash_body<HD, FP8, true>(seq, blockIdx.x, blockIdx.y, a.q_out + (size_t)b * a.nh * HD, a.k_cache, a.v_cache, a.fd_o + (size_t)b * a.nh * n_chunks * HD,
-                                        a.fd_ml + (size_t)b * a.nh * n_chunks * 2, a.nh, a.nkv, a.sm_scale, n_chunks, chunk,
-                                        a.page_table + (size_t)a.slots[b] * a.page_stride, a.page_shift);
-    } else {
-        const size_t base = (size_t)a.slots[b] * a.slot_elems * (FP8 ? 1 : 2);      // bytes to the slot's row 0
-        kr_fd_flash_body<HD, FP8>(seq, blockIdx.x, blockIdx.y, a.q_out + (size_t)b * a.nh * HD, (const char*)a.k_cache + base, (const char*)a.v_cache + base,
-                                  a.fd_o + (size_t)b * a.nh * n_chunks * HD, a.fd_ml + (size_t)b * a.nh * n_chunks * 2, a.nh, a.nkv, a.sm_scale, n_chunks, chunk);
-    }
+    const size_t slot = (size_t)a.slots[b];      // flat: the slot's row 0 of both caches; PAGED: the pools and the slot's row of the table
+    kr_fd_flash_body<HD, FP8, PAGED>(seq, blockIdx.x, blockIdx.y, a.q_out + (size_t)b * a.nh * HD, kr_slot_base<PAGED>(a.kv, 0, slot), kr_slot_base<PAGED>(a.kv, 1, slot),
+                                     a.fd_o + (size_t)b * a.nh * n_chunks * HD, a.fd_ml + (size_t)b * a.nh * n_chunks * 2, a.nh, a.nkv, a.sm_scale, n_chunks, chunk,
+                                     PAGED ? kr_slot_table_row(a.kv.pg, slot) : nullptr, PAGED ? a.kv.pg.shift : 0);
 }
 
 // grid (nh, B), 1024 threads: head h of row b merges the row's own ceil((positions[b] + 1) / chunk) chunks, gates, and writes row b of attn_out (f32: the
@@ -57,15 +52,15 @@ int kr_multi_fd_prepare(int hd, int fp8, int paged) {
 
 int kr_launch_multi_fd(const KrMultiGqaArgs& a, int B, int n_chunks, hipStream_t st) {
     if (!kr_multi_fd_ok(a.nh, a.nkv, a.hd) || !a.fd_o || !a.fd_ml || a.fd_chunk < FA_TK || n_chunks < 1 || n_chunks > 1024) return 1;
-    if (a.page_table && (a.page_stride < 1 || a.page_shift < 5)) return 1;      // a tile of FA_TK positions lies in at most two pages
+    if (!kr_slot_stage_fits(a.kv.pg, 32)) return 1;      // a tile of FA_TK positions lies in at most two pages
     const size_t lds = multi_fd_lds(a.hd);
     const dim3 fg(n_chunks, a.nkv, B), mg(a.nh, B);
-#define KR_MFF(H_, F_) do { if (a.page_table) hipLaunchKernelGGL((kr_multi_fd_flash_kernel<H_, F_, true>), fg, dim3(256), lds, st, a, n_chunks, a.fd_chunk); \
+#define KR_MFF(H_, F_) do { if (a.kv.pg.table) hipLaunchKernelGGL((kr_multi_fd_flash_kernel<H_, F_, true>), fg, dim3(256), lds, st, a, n_chunks, a.fd_chunk); \
                             else hipLaunchKernelGGL((kr_multi_fd_flash_kernel<H_, F_, false>), fg, dim3(256), lds, st, a, n_chunks, a.fd_chunk); } while (0)
 #define KR_MFM(H_) hipLaunchKernelGGL(kr_multi_fd_merge_kernel<H_>, mg, dim3(1024), 0, st, a, n_chunks, a.fd_chunk)
-    if (a.hd == 256) { if (a.kv_fp8) KR_MFF(256, true); else KR_MFF(256, false); KR_MFM(256); }
-    else if (a.hd == 128) { if (a.kv_fp8) KR_MFF(128, true); else KR_MFF(128, false); KR_MFM(128); }
-    else { if (a.kv_fp8) KR_MFF(64, true); else KR_MFF(64, false); KR_MFM(64); }
+    if (a.hd == 256) { if (a.kv.fp8) KR_MFF(256, true); else KR_MFF(256, false); KR_MFM(256); }
+    else if (a.hd == 128) { if (a.kv.fp8) KR_MFF(128, true); else KR_MFF(128, false); KR_MFM(128); }
+    else { if (a.kv.fp8) KR_MFF(64, true); else KR_MFF(64, false); KR_MFM(64); }
 #undef KR_MFF
 #undef KR_MFM
     return 0;

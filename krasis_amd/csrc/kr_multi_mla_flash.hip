@@ -23,13 +23,8 @@ __global__ void __launch_bounds__(256) kr_multi_mla_flash_kernel(const KrMultiMl
     float* fd_o = a.fd_o + (size_t)b * n_chunks * a.nh * KLR;
     float* fd_ml = a.fd_ml + (size_t)b * a.nh * n_chunks * 2;
     const size_t slot = (size_t)a.slots[b];
-    if constexpr (PAGED) {
-        kr_mla_flash_body<KLR, FP8, true, true>(q_abs, q_pe, a.ckv_cache, a.kpe_cache, pos, 1, a.nh, a.sm_scale, nullptr, fd_o, fd_ml, 0, c, n_chunks, chunk_tiles,
-                                                a.page_table + slot * a.page_stride, a.page_shift);
-    } else {
-        kr_mla_flash_body<KLR, FP8, true>(q_abs, q_pe, (const char*)a.ckv_cache + slot * a.ckv_stride, (const char*)a.kpe_cache + slot * a.kpe_stride, pos, 1, a.nh,
-                                          a.sm_scale, nullptr, fd_o, fd_ml, 0, c, n_chunks, chunk_tiles);
-    }
+    kr_mla_flash_body<KLR, FP8, true, PAGED>(q_abs, q_pe, kr_slot_base<PAGED>(a.kv, 0, slot), kr_slot_base<PAGED>(a.kv, 1, slot), pos, 1, a.nh, a.sm_scale, nullptr, fd_o,
+                                             fd_ml, 0, c, n_chunks, chunk_tiles, PAGED ? kr_slot_table_row(a.kv.pg, slot) : nullptr, PAGED ? a.kv.pg.shift : 0);
 }
 
 // grid (nh, B), 1024 threads: head h of row b merges the row's own ceil((positions[b] + 1) / chunk) chunks and writes row b of attn_lat -- what
@@ -60,15 +55,15 @@ int kr_multi_mla_fd_prepare(int klr, int fp8, int paged) {
 
 int kr_launch_multi_mla_fd(const KrMultiMlaArgs& a, int B, hipStream_t st) {
     if (!kr_multi_mla_fd_ok(a.nh, a.klr, a.rd) || !a.fd_o || !a.fd_ml || a.fd_chunk < MF_TK || a.fd_chunk % MF_TK || a.fd_chunks < 1 || a.fd_chunks > 1024) return 1;
-    if (a.page_table && (a.page_stride < 1 || (1 << a.page_shift) < MF_TK)) return 1;      // a tile of MF_TK positions lies in one page
+    if (!kr_slot_stage_fits(a.kv.pg, MF_TK)) return 1;      // a tile of MF_TK positions lies in one page
     const int n_chunks = a.fd_chunks;
     const dim3 fg(n_chunks, B), mg(a.nh, B);
 #define KR_MMF(K_, F_) do { const size_t lds = kr_mla_flash_lds<K_>(); \
-                            if (a.page_table) hipLaunchKernelGGL((kr_multi_mla_flash_kernel<K_, F_, true>), fg, dim3(256), lds, st, a, n_chunks, a.fd_chunk / MF_TK); \
+                            if (a.kv.pg.table) hipLaunchKernelGGL((kr_multi_mla_flash_kernel<K_, F_, true>), fg, dim3(256), lds, st, a, n_chunks, a.fd_chunk / MF_TK); \
                             else hipLaunchKernelGGL((kr_multi_mla_flash_kernel<K_, F_, false>), fg, dim3(256), lds, st, a, n_chunks, a.fd_chunk / MF_TK); } while (0)
 #define KR_MMM(K_) hipLaunchKernelGGL(kr_multi_mla_merge_kernel<K_>, mg, dim3(1024), 0, st, a, n_chunks, a.fd_chunk)
-    if (a.klr == 512) { if (a.kv_fp8) KR_MMF(512, true); else KR_MMF(512, false); KR_MMM(512); }
-    else { if (a.kv_fp8) KR_MMF(256, true); else KR_MMF(256, false); KR_MMM(256); }
+    if (a.klr == 512) { if (a.kv.fp8) KR_MMF(512, true); else KR_MMF(512, false); KR_MMM(512); }
+    else { if (a.kv.fp8) KR_MMF(256, true); else KR_MMF(256, false); KR_MMM(256); }
 #undef KR_MMF
 #undef KR_MMM
     return 0;

@@ -28,13 +28,8 @@ __global__ void __launch_bounds__(256) kr_multi_mla_pf_flash_kernel(const KrMult
     const size_t slot = (size_t)a.mf_runs[3 * run];
     const int pos0 = a.positions[kr_m_run_row(run, off, cnt, 0)];
     const KrMfRunRows rows{run, off, cnt, a.nh};
-    if constexpr (PAGED) {
-        kr_mla_flash_body<KLR, FP8, false, true>(a.q_abs, a.q_pe, a.ckv_cache, a.kpe_cache, pos0, cnt, a.nh, a.sm_scale, a.attn_lat, nullptr, nullptr, tile_row, 0, 0, 0,
-                                                 a.page_table + slot * a.page_stride, a.page_shift, rows);
-    } else {
-        kr_mla_flash_body<KLR, FP8, false>(a.q_abs, a.q_pe, (const char*)a.ckv_cache + slot * a.ckv_stride, (const char*)a.kpe_cache + slot * a.kpe_stride, pos0, cnt, a.nh,
-                                           a.sm_scale, a.attn_lat, nullptr, nullptr, tile_row, 0, 0, 0, nullptr, 0, rows);
-    }
+    kr_mla_flash_body<KLR, FP8, false, PAGED>(a.q_abs, a.q_pe, kr_slot_base<PAGED>(a.kv, 0, slot), kr_slot_base<PAGED>(a.kv, 1, slot), pos0, cnt, a.nh, a.sm_scale, a.attn_lat,
+                                              nullptr, nullptr, tile_row, 0, 0, 0, PAGED ? kr_slot_table_row(a.kv.pg, slot) : nullptr, PAGED ? a.kv.pg.shift : 0, rows);
 }
 
 static_assert(KR_PAGE_MIN_TOKENS % MF_TK == 0, "a tile of MF_TK positions lies in one page");
@@ -55,16 +50,16 @@ int kr_multi_mla_pf_prepare(int klr, int fp8, int paged) {
 int kr_multi_mla_pf_args_ok(const KrMultiMlaArgs& a) {
     if (a.rd != 64 || (a.klr != 512 && a.klr != 256) || a.nh < 1) return 0;      // kr_launch_mla_flash's rule
     if (!a.mf_runs || !a.mf_tiles || a.mf_ntiles < 1 || !a.attn_lat) return 0;
-    return !(a.page_table && (a.page_stride < 1 || (1 << a.page_shift) < MF_TK));      // a tile of MF_TK positions lies in one page
+    return kr_slot_stage_fits(a.kv.pg, MF_TK);      // a tile of MF_TK positions lies in one page
 }
 int kr_launch_multi_mla_pf_flash(const KrMultiMlaArgs& a, hipStream_t st) {
     if (!kr_multi_mla_pf_args_ok(a)) return 1;
     const dim3 grid(a.mf_ntiles);
 #define KR_MMR(K_, F_) do { const size_t lds = kr_mla_flash_lds<K_>(); \
-                            if (a.page_table) hipLaunchKernelGGL((kr_multi_mla_pf_flash_kernel<K_, F_, true>), grid, dim3(256), lds, st, a); \
+                            if (a.kv.pg.table) hipLaunchKernelGGL((kr_multi_mla_pf_flash_kernel<K_, F_, true>), grid, dim3(256), lds, st, a); \
                             else hipLaunchKernelGGL((kr_multi_mla_pf_flash_kernel<K_, F_, false>), grid, dim3(256), lds, st, a); } while (0)
-    if (a.klr == 512) { if (a.kv_fp8) KR_MMR(512, true); else KR_MMR(512, false); }
-    else { if (a.kv_fp8) KR_MMR(256, true); else KR_MMR(256, false); }
+    if (a.klr == 512) { if (a.kv.fp8) KR_MMR(512, true); else KR_MMR(512, false); }
+    else { if (a.kv.fp8) KR_MMR(256, true); else KR_MMR(256, false); }
 #undef KR_MMR
     return 0;
 }

@@ -30,15 +30,15 @@
 #define KR_MLS_NPR (KR_MLS_HP * KR_MLS_PT / 256) // probabilities of a stage per thread
 static_assert(KR_PAGE_MIN_TOKENS % KR_MLS_ROWS == 0 && KR_MLS_TILE % KR_MLS_ROWS == 0, "a stage of the scores kernel lies in one page and in one tile");
 
-// base of position s of the row's slot in a cache whose slot (PAGED: page) is `stride` bytes and whose rows are RB bytes.  PAGED: through the slot's table slice, one
+// base of position s of the row's slot in half H of the layer's cache, whose rows are RB bytes.  PAGED: through the slot's table slice, one
 // entry per call -- a workgroup reads only the entries of the positions it loads (every page of [0, seq) was mapped by the host before the pass: max(., 0) as in the
 // unsplit kernel)
-template <int RB, bool PAGED>
-__device__ __forceinline__ const unsigned char* kr_mls_row(const KrMultiMlaArgs& a, const void* cache, size_t stride, int slot, int s) {
-    if constexpr (PAGED) {
-        const int pg = max(a.page_table[(size_t)slot * a.page_stride + (s >> a.page_shift)], 0);
-        return reinterpret_cast<const unsigned char*>(cache) + (size_t)pg * stride + (size_t)(s & ((1 << a.page_shift) - 1)) * RB;
-    } else return reinterpret_cast<const unsigned char*>(cache) + (size_t)slot * stride + (size_t)s * RB;
+template <int H, int RB, bool PAGED>
+__device__ __forceinline__ const unsigned char* kr_mls_row(const KrMultiMlaArgs& a, int slot, int s) {
+    if constexpr (PAGED) {      // the page's base, then the row inside it: a page is a unit of the pool
+        const int pg = kr_slot_page_id(kr_slot_table_row(a.kv.pg, (size_t)slot)[kr_slot_entry(s, a.kv.pg.shift)]);
+        return reinterpret_cast<const unsigned char*>(kr_slot_base<false>(a.kv, H, (size_t)pg)) + (size_t)kr_slot_in_page(s, kr_slot_mask(a.kv.pg.shift)) * RB;
+    } else return reinterpret_cast<const unsigned char*>(kr_slot_base<false>(a.kv, H, (size_t)slot)) + (size_t)s * RB;
 }
 // element j of a 16-byte chunk held in registers (j a constant after unrolling: shifts, no addressing)
 template <bool FP8> __device__ __forceinline__ float kr_mls_chunk_elem(const u32x4& r, int j) {
@@ -75,8 +75,8 @@ __global__ void __launch_bounds__(512) kr_multi_mla_split_scores_kernel(const Kr
         for (int i = 0; i < NLD; i++) {
             const int u = t + 512 * i, r = u / CPR, c = u % CPR;
             if (u < ROWS * CPR && s0 + r < tend) {
-                const unsigned char* src = c < CPR_C ? kr_mls_row<klr * esz, PAGED>(a, a.ckv_cache, a.ckv_stride, slot, s0 + r) + c * 16
-                                                     : kr_mls_row<rd * esz, PAGED>(a, a.kpe_cache, a.kpe_stride, slot, s0 + r) + (c - CPR_C) * 16;
+                const unsigned char* src = c < CPR_C ? kr_mls_row<0, klr * esz, PAGED>(a, slot, s0 + r) + c * 16
+                                                     : kr_mls_row<1, rd * esz, PAGED>(a, slot, s0 + r) + (c - CPR_C) * 16;
                 rg[i] = *reinterpret_cast<const u32x4*>(src);
             }
         }
@@ -193,7 +193,7 @@ __global__ void __launch_bounds__(256) kr_multi_mla_split_pv_kernel(const KrMult
 #pragma unroll
         for (int k = 0; k < KR_MLS_NPR; k++) pr[k] = 0.0f;
         auto issue = [&](int s0) {
-            if (loader && s0 + lr < seq) rg = *reinterpret_cast<const u32x4*>(kr_mls_row<klr * esz, PAGED>(a, a.ckv_cache, a.ckv_stride, slot, s0 + lr) + (size_t)j0 * esz + lc * 16);
+            if (loader && s0 + lr < seq) rg = *reinterpret_cast<const u32x4*>(kr_mls_row<0, klr * esz, PAGED>(a, slot, s0 + lr) + (size_t)j0 * esz + lc * 16);
             if (s0 + ps < seq) {
 #pragma unroll
                 for (int k = 0; k < KR_MLS_NPR; k++) { const int h = gp + pg + 4 * k; if (h < nh) pr[k] = sc[(size_t)h * a.sc_ld + s0 + ps]; }
@@ -236,15 +236,15 @@ __global__ void __launch_bounds__(256) kr_multi_mla_split_pv_kernel(const KrMult
 // static and inside the default window, whatever the head count
 int kr_launch_multi_mla_split(const KrMultiMlaArgs& a, int rows, hipStream_t st) {
     if (!kr_multi_mla_ok(a.klr, a.nd, a.rd) || a.nh < 1 || !a.scores || a.sc_ld < 32 || a.sc_ld % 32 || rows < 1) return 1;
-    if (a.page_table && (a.page_stride < 1 || (1 << a.page_shift) < KR_MLS_ROWS)) return 1;      // a stage of the scores kernel must not straddle a page
+    if (!kr_slot_stage_fits(a.kv.pg, KR_MLS_ROWS)) return 1;      // a stage of the scores kernel must not straddle a page
     const dim3 gs((a.sc_ld + KR_MLS_TILE - 1) / KR_MLS_TILE, (a.nh + KR_MLS_HG - 1) / KR_MLS_HG, rows), gm((a.nh + 3) / 4, rows), gp(a.klr / KR_MLS_DS, rows);
 #define KR_MLSL(F_, NBC_, P_) do { \
         hipLaunchKernelGGL((kr_multi_mla_split_scores_kernel<F_, NBC_, P_>), gs, dim3(512), 0, st, a); \
         hipLaunchKernelGGL(kr_multi_mla_split_softmax_kernel, gm, dim3(256), 0, st, a); \
         hipLaunchKernelGGL((kr_multi_mla_split_pv_kernel<F_, NBC_, P_>), gp, dim3(256), 0, st, a); } while (0)
 #define KR_MLSL_KLR(F_, P_) do { if (a.klr == 512) KR_MLSL(F_, 64, P_); else KR_MLSL(F_, 32, P_); } while (0)
-    if (a.page_table) { if (a.kv_fp8) KR_MLSL_KLR(true, true); else KR_MLSL_KLR(false, true); }
-    else { if (a.kv_fp8) KR_MLSL_KLR(true, false); else KR_MLSL_KLR(false, false); }
+    if (a.kv.pg.table) { if (a.kv.fp8) KR_MLSL_KLR(true, true); else KR_MLSL_KLR(false, true); }
+    else { if (a.kv.fp8) KR_MLSL_KLR(true, false); else KR_MLSL_KLR(false, false); }
 #undef KR_MLSL_KLR
 #undef KR_MLSL
     return 0;

@@ -37,10 +37,10 @@ __global__ void __launch_bounds__(256) kr_multi_mla_xm_scores_kernel(const KrMul
     const int* tl = x.tiles_a + 2 * blockIdx.y;
     const int run = tl[0], t0 = tl[1], slot = a.mf_runs[3 * run];
     const KrMlaXmRunRows rows{run, a.mf_runs[3 * run + 1], a.mf_runs[3 * run + 2]};
-    const char* kb = reinterpret_cast<const char*>(ROPE ? a.kpe_cache : a.ckv_cache) + (PAGED ? 0 : (size_t)slot * (ROPE ? a.kpe_stride : a.ckv_stride));
-    const int* ptab = PAGED ? a.page_table + (size_t)slot * a.page_stride : nullptr;
+    const char* kb = kr_slot_base<PAGED>(a.kv, ROPE ? 1 : 0, (size_t)slot);
+    const int* ptab = PAGED ? kr_slot_table_row(a.kv.pg, (size_t)slot) : nullptr;
     kr_xm_mla_scores_body<FP8, ROPE, PAGED>(ROPE ? a.q_pe : a.q_abs, kb, a.nh, ROPE ? a.rd : a.klr, a.positions[rows(0)], rows.cnt, t0, blockIdx.x * 64, rows, ptab,
-                                            a.page_shift, a.sm_scale, a.scores, a.sc_ld, x.tmax, As, Bs);
+                                            a.kv.pg.shift, a.sm_scale, a.scores, a.sc_ld, x.tmax, As, Bs);
 }
 
 // pass C for kv_lora_rank 512: grid (x.n_c query tiles of 32 / nh tokens), 256 threads; a = the KrMultiGqaArgs view (nkv = 1, hd = 512, gated = 0)
@@ -51,10 +51,9 @@ __global__ void __launch_bounds__(256) kr_multi_mla_xm_pv512_kernel(const KrMult
     const int* tl = x.tiles_c + 2 * blockIdx.x;
     const int run = tl[0], t0 = tl[1], slot = a.pf_runs[3 * run];
     const KrMlaXmRunRows rows{run, a.pf_runs[3 * run + 1], a.pf_runs[3 * run + 2]};
-    const size_t base = PAGED ? 0 : (size_t)slot * a.slot_elems * (FP8 ? 1 : 2);      // bytes to the slot's row 0
-    const KrXmSeq q{a.q_out, a.gate, a.attn_out, (const char*)a.k_cache + base, (const char*)a.v_cache + base, a.gated, a.nh, a.nkv, a.positions[rows(0)], rows.cnt, a.sm_scale};
-    const int* ptab = PAGED ? a.page_table + (size_t)slot * a.page_stride : nullptr;
-    kr_xm_pv_body<FP8, 512, 32, PAGED>(q, t0, 0, rows, ptab, a.page_shift, a.scores, a.sc_ld, x.inv, Ps, Vs);
+    const KrXmSeq q{a.q_out, a.gate, a.attn_out, kr_slot_base<PAGED>(a.kv, 0, (size_t)slot), kr_slot_base<PAGED>(a.kv, 1, (size_t)slot), a.gated, a.nh, a.nkv, a.positions[rows(0)], rows.cnt, a.sm_scale};
+    const int* ptab = PAGED ? kr_slot_table_row(a.kv.pg, (size_t)slot) : nullptr;
+    kr_xm_pv_body<FP8, 512, 32, PAGED>(q, t0, 0, rows, ptab, a.kv.pg.shift, a.scores, a.sc_ld, x.inv, Ps, Vs);
 }
 
 // what kr_launch_multi_mla_xm_attn checks: asked before anything of the layer is queued (a.mf_runs set, a.mf_tiles null)
@@ -62,7 +61,7 @@ int kr_multi_mla_xm_args_ok(const KrMultiMlaArgs& a, const KrMultiXmArgs& x) {
     if (!kr_mla_exact_mfma_ok(a.nh, a.klr, a.rd)) return 0;
     if (!a.mf_runs || a.mf_tiles || !a.scores || a.sc_ld < 64 || a.sc_ld % 64) return 0;      // the row maxima are per 32 positions, a 256-wide pass C reads stages of 64 score columns
     if (!x.tiles_a || !x.tiles_c || x.n_a < 1 || x.n_c < 1 || x.n_a > 65535 || !x.inv || !x.tmax || x.kv_end < 2 || x.kv_end > a.sc_ld) return 0;
-    return !(a.page_table && (a.page_stride < 1 || a.page_shift < 5));
+    return kr_slot_stage_fits(a.kv.pg, 32);
 }
 // passes A (two launches), B and C alone (after the prep launch)
 int kr_launch_multi_mla_xm_attn(const KrMultiMlaArgs& a, const KrMultiXmArgs& x, int B, hipStream_t st) {
@@ -70,21 +69,20 @@ int kr_launch_multi_mla_xm_attn(const KrMultiMlaArgs& a, const KrMultiXmArgs& x,
     const dim3 ga((x.kv_end + 63) / 64, x.n_a);
 #define KR_MXA(F_, R_, P_) hipLaunchKernelGGL((kr_multi_mla_xm_scores_kernel<F_, R_, P_>), ga, dim3(256), 0, st, a, x)
 #define KR_MXA2(F_, P_) do { KR_MXA(F_, true, P_); KR_MXA(F_, false, P_); } while (0)
-    if (a.page_table) { if (a.kv_fp8) KR_MXA2(true, true); else KR_MXA2(false, true); }
-    else { if (a.kv_fp8) KR_MXA2(true, false); else KR_MXA2(false, false); }
+    if (a.kv.pg.table) { if (a.kv.fp8) KR_MXA2(true, true); else KR_MXA2(false, true); }
+    else { if (a.kv.fp8) KR_MXA2(true, false); else KR_MXA2(false, false); }
 #undef KR_MXA2
 #undef KR_MXA
     // the GQA view of the layer: one KV head whose K = V rows are the latent rows
     KrMultiGqaArgs g{};
-    g.slots = a.slots; g.positions = a.positions; g.k_cache = a.ckv_cache; g.v_cache = a.ckv_cache; g.slot_elems = a.ckv_stride / (a.kv_fp8 ? 1 : 2); g.kv_fp8 = a.kv_fp8;
+    g.slots = a.slots; g.positions = a.positions; g.kv = a.kv; g.kv.base[1] = a.kv.base[0]; g.kv.unit[1] = a.kv.unit[0]; g.kv.row[1] = a.kv.row[0];
     g.attn_out = a.attn_lat; g.scores = a.scores; g.sc_ld = a.sc_ld; g.gated = 0; g.nh = a.nh; g.nkv = 1; g.hd = a.klr; g.sm_scale = a.sm_scale;
-    g.page_table = a.page_table; g.page_stride = a.page_stride; g.page_shift = a.page_shift;
     g.pf_runs = a.mf_runs; g.pf_nruns = a.mf_nruns; g.pf_units = a.mf_units; g.pf_tiles = nullptr; g.pf_ntiles = 0;
     kr_launch_multi_xm_softmax(g, x, B, st);
     if (a.klr == 256) { kr_launch_multi_xm_pv(g, x, st); return 0; }
-#define KR_MXC(F_) do { if (a.page_table) hipLaunchKernelGGL((kr_multi_mla_xm_pv512_kernel<F_, true>), dim3(x.n_c), dim3(256), 0, st, g, x); \
+#define KR_MXC(F_) do { if (a.kv.pg.table) hipLaunchKernelGGL((kr_multi_mla_xm_pv512_kernel<F_, true>), dim3(x.n_c), dim3(256), 0, st, g, x); \
                         else hipLaunchKernelGGL((kr_multi_mla_xm_pv512_kernel<F_, false>), dim3(x.n_c), dim3(256), 0, st, g, x); } while (0)
-    if (a.kv_fp8) KR_MXC(true); else KR_MXC(false);
+    if (a.kv.fp8) KR_MXC(true); else KR_MXC(false);
 #undef KR_MXC
     return 0;
 }

@@ -33,10 +33,11 @@ struct KrPfSlotTiles {
         const int slot = a.pf_runs[3 * run];
         off = a.pf_runs[3 * run + 1]; C = a.pf_runs[3 * run + 2];
         pos0 = a.positions[row(0)];
-        cache_off = PAGED_ ? 0 : (size_t)slot * a.slot_elems * (FP8 ? 1 : 2);      // bytes to the slot's row 0
-        ptab = PAGED_ ? a.page_table + (size_t)slot * a.page_stride : nullptr; psh = a.page_shift;
+        cache_off = kr_slot_base_off<PAGED>(a.kv, 0, (size_t)slot);      // bytes to the slot's row 0
+        ptab = PAGED_ ? kr_slot_table_row(a.kv.pg, (size_t)slot) : nullptr; psh = a.kv.pg.shift;
     }
     __device__ __forceinline__ int row(int t) const { return kr_m_run_row(run, off, C, t); }
+    static __device__ __forceinline__ const void* cache(const Args& a, int h) { return a.kv.base[h]; }
 };
 
 // the wave-specialised body for tile (run, t0) of KV head kvh
@@ -44,13 +45,8 @@ template <int HD, bool FP8, bool PAGED>
 __device__ __forceinline__ void kr_multi_pf_tile(const KrMultiGqaArgs& a, int run, int t0, int kvh) {
     const int slot = a.pf_runs[3 * run], off = a.pf_runs[3 * run + 1], cnt = a.pf_runs[3 * run + 2];
     const KrPfRunRows rows{run, off, cnt};
-    KrPfFlashTile q{a.q_out, a.gate, a.attn_out, a.k_cache, a.v_cache, a.gated, a.nh, a.nkv, a.positions[rows(0)], a.sm_scale};
-    if constexpr (PAGED) kr_pfm_flashw_body<HD, FP8, true>(q, cnt, t0, kvh, rows, a.page_table + (size_t)slot * a.page_stride, a.page_shift);
-    else {
-        const size_t base = (size_t)slot * a.slot_elems * (FP8 ? 1 : 2);      // bytes to the slot's row 0
-        q.k_cache = (const char*)a.k_cache + base; q.v_cache = (const char*)a.v_cache + base;
-        kr_pfm_flashw_body<HD, FP8>(q, cnt, t0, kvh, rows);
-    }
+    const KrPfFlashTile q{a.q_out, a.gate, a.attn_out, kr_slot_base<PAGED>(a.kv, 0, (size_t)slot), kr_slot_base<PAGED>(a.kv, 1, (size_t)slot), a.gated, a.nh, a.nkv, a.positions[rows(0)], a.sm_scale};
+    kr_pfm_flashw_body<HD, FP8, PAGED>(q, cnt, t0, kvh, rows, PAGED ? kr_slot_table_row(a.kv.pg, (size_t)slot) : nullptr, PAGED ? a.kv.pg.shift : 0);
 }
 
 // grid (tiles of the pass, nkv), 512 threads: the wave-specialised form takes the table from its end (within a run: the tiles that see the most positions first).
@@ -77,19 +73,19 @@ int kr_multi_pf_prepare(int hd, int fp8, int paged) {
 
 int kr_multi_pf_args_ok(const KrMultiGqaArgs& a) {
     if (!kr_pfm_gqa_flash_ok(a.nh, a.nkv, a.hd) || !a.pf_runs || !a.pf_tiles || a.pf_ntiles < 1) return 0;
-    return !(a.page_table && (a.page_stride < 1 || a.page_shift < 5));      // a tile of FA_TK positions lies in at most two pages
+    return kr_slot_stage_fits(a.kv.pg, 32);      // a tile of FA_TK positions lies in at most two pages
 }
 int kr_launch_multi_pf_flash(const KrMultiGqaArgs& a, hipStream_t st) {
     if (!kr_multi_pf_args_ok(a)) return 1;
     const dim3 grid(a.pf_ntiles, a.nkv);
     // head_dim >= 128 takes the wave-specialised form: kr_launch_pfm_gqa_flash's rule, part of the bit-identity
-#define KR_MPW(H_, F_) do { if (a.page_table) hipLaunchKernelGGL((kr_multi_pf_flashw_kernel<H_, F_, true>), grid, dim3(512), kr_pfm_flashw_lds(H_), st, a); \
+#define KR_MPW(H_, F_) do { if (a.kv.pg.table) hipLaunchKernelGGL((kr_multi_pf_flashw_kernel<H_, F_, true>), grid, dim3(512), kr_pfm_flashw_lds(H_), st, a); \
                             else hipLaunchKernelGGL((kr_multi_pf_flashw_kernel<H_, F_, false>), grid, dim3(512), kr_pfm_flashw_lds(H_), st, a); } while (0)
-#define KR_MPF(H_, F_) do { if (a.page_table) hipLaunchKernelGGL((kr_pfm_gqa_flash_kernel<H_, F_, KrPfSlotTiles<F_, true>>), grid, dim3(256), kr_pfm_flash_lds(H_), st, a, 0); \
+#define KR_MPF(H_, F_) do { if (a.kv.pg.table) hipLaunchKernelGGL((kr_pfm_gqa_flash_kernel<H_, F_, KrPfSlotTiles<F_, true>>), grid, dim3(256), kr_pfm_flash_lds(H_), st, a, 0); \
                             else hipLaunchKernelGGL((kr_pfm_gqa_flash_kernel<H_, F_, KrPfSlotTiles<F_, false>>), grid, dim3(256), kr_pfm_flash_lds(H_), st, a, 0); } while (0)
-    if (a.hd == 256) { if (a.kv_fp8) KR_MPW(256, true); else KR_MPW(256, false); }
-    else if (a.hd == 128) { if (a.kv_fp8) KR_MPW(128, true); else KR_MPW(128, false); }
-    else { if (a.kv_fp8) KR_MPF(64, true); else KR_MPF(64, false); }
+    if (a.hd == 256) { if (a.kv.fp8) KR_MPW(256, true); else KR_MPW(256, false); }
+    else if (a.hd == 128) { if (a.kv.fp8) KR_MPW(128, true); else KR_MPW(128, false); }
+    else { if (a.kv.fp8) KR_MPF(64, true); else KR_MPF(64, false); }
 #undef KR_MPW
 #undef KR_MPF
     return 0;

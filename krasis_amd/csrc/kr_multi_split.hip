@@ -28,10 +28,7 @@
 template <int HD, int ESZ, bool PAGED>
 __device__ __forceinline__ size_t kr_ms_row_off(const KrMultiGqaArgs& a, int slot, int kvh, int s) {
     const size_t kvs = (size_t)a.nkv * HD;
-    if constexpr (PAGED) {
-        const int pg = max(a.page_table[(size_t)slot * a.page_stride + (s >> a.page_shift)], 0);
-        return ((((size_t)pg << a.page_shift) | (size_t)(s & ((1 << a.page_shift) - 1))) * kvs + (size_t)kvh * HD) * ESZ;
-    } else return ((size_t)slot * a.slot_elems + (size_t)s * kvs + (size_t)kvh * HD) * ESZ;
+    return (kr_slot_base_off<PAGED>(a.kv, 0, (size_t)slot) / ESZ + kr_slot_row<PAGED>(s, PAGED ? kr_slot_table_row(a.kv.pg, (size_t)slot) : nullptr, a.kv.pg.shift) * kvs + (size_t)kvh * HD) * ESZ;
 }
 template <bool FP8> __device__ __forceinline__ float kr_ms_elem(const unsigned char* row, int i) {
     if (FP8) return kr_e4m3_to_f32(row[i]);
@@ -59,7 +56,7 @@ __global__ void __launch_bounds__(256) kr_multi_split_scores_kernel(const KrMult
     const int tend = min(seq, t0 + KR_MS_TILE), G = a.nh / a.nkv, slot = a.slots[row];
     float* qs = sm;                                                             // [G][8][QLD]: lane l's elements e * 8 + l of a head side by side, for 16-byte reads
     unsigned char* stage = reinterpret_cast<unsigned char*>(qs + (size_t)G * 8 * QLD);      // [KR_MS_KROWS][PITCH]
-    const unsigned char* kc = reinterpret_cast<const unsigned char*>(a.k_cache);
+    const unsigned char* kc = reinterpret_cast<const unsigned char*>(a.kv.base[0]);
     u32x4 rg[NLD];
     auto issue = [&](int s0) {
 #pragma unroll
@@ -154,7 +151,7 @@ __global__ void __launch_bounds__(256) kr_multi_split_pv_kernel(const KrMultiGqa
     const int kvh = blockIdx.x / NSL, d0 = (blockIdx.x % NSL) * KR_MS_DS, row = blockIdx.y, t = threadIdx.x;
     if (kr_m_row_in_run(a, row)) return;      // the run kernels' row (workgroup-uniform, ahead of every barrier)
     const int seq = a.positions[row] + 1, G = a.nh / a.nkv, slot = a.slots[row];
-    const unsigned char* vc = reinterpret_cast<const unsigned char*>(a.v_cache);
+    const unsigned char* vc = reinterpret_cast<const unsigned char*>(a.kv.base[1]);
     const float* sc = a.scores + ((size_t)row * a.nh + (size_t)kvh * G) * a.sc_ld;
     const int lr = t / CPS, lc = t % CPS;      // this thread's row and chunk of a stage
     const bool loader = t < KR_MS_PT * CPS;
@@ -222,9 +219,9 @@ size_t kr_multi_split_lds_bytes(int G, int hd, int kv_fp8) {      // the scores 
 // table) for G >= 4, and 20352 bytes at most for G < 4; the P.V launch asks 256 G + 8704
 int kr_launch_multi_gqa_split(const KrMultiGqaArgs& a, int rows, hipStream_t st) {
     if ((a.hd != 64 && a.hd != 128 && a.hd != 256) || a.nkv < 1 || a.nh % a.nkv || a.sc_ld < 32 || a.sc_ld % 32 || rows < 1) return 1;
-    if (a.page_table && (a.page_stride < 1 || a.page_shift < 5)) return 1;
+    if (!kr_slot_stage_fits(a.kv.pg, 32)) return 1;
     const int G = a.nh / a.nkv;
-    const size_t lds_s = kr_multi_split_lds_bytes(G, a.hd, a.kv_fp8), lds_p = (size_t)G * KR_MS_PT * 4;
+    const size_t lds_s = kr_multi_split_lds_bytes(G, a.hd, a.kv.fp8), lds_p = (size_t)G * KR_MS_PT * 4;
     if (lds_s > 64 * 1024 || lds_p + sizeof(float) * KR_MS_DS * KR_MS_VLD > 64 * 1024) return 1;
     const dim3 gs((a.sc_ld + KR_MS_TILE - 1) / KR_MS_TILE, a.nkv, rows), gm((a.nh + 3) / 4, rows), gp(a.nkv * (a.hd / KR_MS_DS), rows);
 #define KR_MSL(NB_, F_, P_) do { \
@@ -232,8 +229,8 @@ int kr_launch_multi_gqa_split(const KrMultiGqaArgs& a, int rows, hipStream_t st)
         hipLaunchKernelGGL(kr_multi_split_softmax_kernel, gm, dim3(256), 0, st, a); \
         hipLaunchKernelGGL((kr_multi_split_pv_kernel<NB_, F_, P_>), gp, dim3(256), lds_p, st, a); } while (0)
 #define KR_MSL_HD(F_, P_) do { if (a.hd == 256) KR_MSL(32, F_, P_); else if (a.hd == 128) KR_MSL(16, F_, P_); else KR_MSL(8, F_, P_); } while (0)
-    if (a.page_table) { if (a.kv_fp8) KR_MSL_HD(true, true); else KR_MSL_HD(false, true); }
-    else { if (a.kv_fp8) KR_MSL_HD(true, false); else KR_MSL_HD(false, false); }
+    if (a.kv.pg.table) { if (a.kv.fp8) KR_MSL_HD(true, true); else KR_MSL_HD(false, true); }
+    else { if (a.kv.fp8) KR_MSL_HD(true, false); else KR_MSL_HD(false, false); }
 #undef KR_MSL_HD
 #undef KR_MSL
     return 0;

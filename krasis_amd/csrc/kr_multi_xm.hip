@@ -36,9 +36,8 @@ struct KrXmSlotTile {
         t0 = tl[1];
         const int slot = a.pf_runs[3 * run];
         rows = KrXmRunRows{run, a.pf_runs[3 * run + 1], a.pf_runs[3 * run + 2]};
-        const size_t base = PAGED ? 0 : (size_t)slot * a.slot_elems * (FP8 ? 1 : 2);      // bytes to the slot's row 0
-        q = KrXmSeq{a.q_out, a.gate, a.attn_out, (const char*)a.k_cache + base, (const char*)a.v_cache + base, a.gated, a.nh, a.nkv, a.positions[rows(0)], rows.cnt, a.sm_scale};
-        ptab = PAGED ? a.page_table + (size_t)slot * a.page_stride : nullptr;
+        q = KrXmSeq{a.q_out, a.gate, a.attn_out, kr_slot_base<PAGED>(a.kv, 0, (size_t)slot), kr_slot_base<PAGED>(a.kv, 1, (size_t)slot), a.gated, a.nh, a.nkv, a.positions[rows(0)], rows.cnt, a.sm_scale};
+        ptab = PAGED ? kr_slot_table_row(a.kv.pg, (size_t)slot) : nullptr;
     }
 };
 
@@ -49,7 +48,7 @@ __global__ void __launch_bounds__(256, 2) kr_multi_xm_scores_kernel(const KrMult
     __shared__ __attribute__((aligned(16))) float Qs[64 * XM_LDF];
     __shared__ __attribute__((aligned(16))) float Ks[64 * XM_LDF];
     const KrXmSlotTile<FP8, PAGED> tl(a, x.tiles_a + 2 * blockIdx.y);
-    kr_xm_scores_body<FP8, PAGED>(tl.q, a.hd, tl.t0, blockIdx.x * 64, blockIdx.z, tl.rows, tl.ptab, a.page_shift, a.scores, a.sc_ld, x.tmax, Qs, Ks);
+    kr_xm_scores_body<FP8, PAGED>(tl.q, a.hd, tl.t0, blockIdx.x * 64, blockIdx.z, tl.rows, tl.ptab, a.kv.pg.shift, a.scores, a.sc_ld, x.tmax, Qs, Ks);
 }
 
 // pass B: one wave per (pass row, head), seq = positions[row] + 1.  A row b < pf_nruns whose run has one token is a unit row of the per-row kernels and leaves at
@@ -95,7 +94,7 @@ __global__ void __launch_bounds__(256) kr_multi_xm_pv_kernel(const KrMultiGqaArg
     __shared__ __attribute__((aligned(16))) float Ps[32 * (64 + 4)];
     __shared__ __attribute__((aligned(16))) char Vs[64 * (HD * (FP8 ? 1 : 2) + 64)];
     const KrXmSlotTile<FP8, PAGED> tl(a, x.tiles_c + 2 * blockIdx.x);
-    kr_xm_pv_body<FP8, HD, 64, PAGED>(tl.q, tl.t0, blockIdx.y, tl.rows, tl.ptab, a.page_shift, a.scores, a.sc_ld, x.inv, Ps, Vs);
+    kr_xm_pv_body<FP8, HD, 64, PAGED>(tl.q, tl.t0, blockIdx.y, tl.rows, tl.ptab, a.kv.pg.shift, a.scores, a.sc_ld, x.inv, Ps, Vs);
 }
 
 // what kr_launch_multi_xm checks: asked before anything of the layer is queued
@@ -105,7 +104,7 @@ int kr_multi_xm_args_ok(const KrMultiGqaArgs& a, const KrMultiXmArgs& x) {
     if (a.nkv < 1 || !kr_pfm_gqa_exact_mfma_ok(g)) return 0;
     if (!a.pf_runs || a.pf_tiles || !a.scores || a.sc_ld < 64 || a.sc_ld % 64) return 0;      // pass C reads stages of 64 score columns
     if (!x.tiles_a || !x.tiles_c || x.n_a < 1 || x.n_c < 1 || x.n_a > 65535 || !x.inv || !x.tmax || x.kv_end < 2 || x.kv_end > a.sc_ld) return 0;
-    return !(a.page_table && (a.page_stride < 1 || a.page_shift < 5));
+    return kr_slot_stage_fits(a.kv.pg, 32);
 }
 // passes B and C on their own: the MLA runs of "multi_extend_mla_exact_mfma" take them behind a scores pass of their own (kr_multi_mla_xm.hip) through a view of
 // the layer with nkv = 1, hd = kv_lora_rank 256.  The caller has checked what kr_multi_xm_args_ok checks
@@ -115,19 +114,19 @@ void kr_launch_multi_xm_softmax(const KrMultiGqaArgs& a, const KrMultiXmArgs& x,
 }
 void kr_launch_multi_xm_pv(const KrMultiGqaArgs& a, const KrMultiXmArgs& x, hipStream_t st) {
     const dim3 gc(x.n_c, a.nkv);
-#define KR_XC(F_, H_) do { if (a.page_table) hipLaunchKernelGGL((kr_multi_xm_pv_kernel<F_, H_, true>), gc, dim3(256), 0, st, a, x); \
+#define KR_XC(F_, H_) do { if (a.kv.pg.table) hipLaunchKernelGGL((kr_multi_xm_pv_kernel<F_, H_, true>), gc, dim3(256), 0, st, a, x); \
                            else hipLaunchKernelGGL((kr_multi_xm_pv_kernel<F_, H_, false>), gc, dim3(256), 0, st, a, x); } while (0)
-    if (a.hd == 256) { if (a.kv_fp8) KR_XC(true, 256); else KR_XC(false, 256); }
-    else if (a.hd == 128) { if (a.kv_fp8) KR_XC(true, 128); else KR_XC(false, 128); }
-    else { if (a.kv_fp8) KR_XC(true, 64); else KR_XC(false, 64); }
+    if (a.hd == 256) { if (a.kv.fp8) KR_XC(true, 256); else KR_XC(false, 256); }
+    else if (a.hd == 128) { if (a.kv.fp8) KR_XC(true, 128); else KR_XC(false, 128); }
+    else { if (a.kv.fp8) KR_XC(true, 64); else KR_XC(false, 64); }
 #undef KR_XC
 }
 int kr_launch_multi_xm(const KrMultiGqaArgs& a, const KrMultiXmArgs& x, int B, hipStream_t st) {
     if (!kr_multi_xm_args_ok(a, x) || B < 1) return 1;
     const dim3 ga((x.kv_end + 63) / 64, x.n_a, a.nkv);
 #define KR_XA(F_, P_) hipLaunchKernelGGL((kr_multi_xm_scores_kernel<F_, P_>), ga, dim3(256), 0, st, a, x)
-    if (a.page_table) { if (a.kv_fp8) KR_XA(true, true); else KR_XA(false, true); }
-    else { if (a.kv_fp8) KR_XA(true, false); else KR_XA(false, false); }
+    if (a.kv.pg.table) { if (a.kv.fp8) KR_XA(true, true); else KR_XA(false, true); }
+    else { if (a.kv.fp8) KR_XA(true, false); else KR_XA(false, false); }
 #undef KR_XA
     kr_launch_multi_xm_softmax(a, x, B, st);
     kr_launch_multi_xm_pv(a, x, st);

@@ -36,20 +36,21 @@ inline size_t kr_pfm_flashw_lds(int hd) { return (size_t)FA_TK * (hd * 2 + 16) +
 struct KrPfRowsIdentity { __device__ __forceinline__ int operator()(int t) const { return t; } };
 
 // PAGED (as kr_fd_flash_body, docs/design/23-multi-attn-fast-paged.md): k_cache / v_cache are pools of pages of 1 << psh positions (psh >= 5) and position p of
-// the sequence is row (ptab[p >> psh] << psh) | (p & mask) of them.  A tile of FA_TK positions starts at a multiple of FA_TK, so it lies in one page, or in two
+// the sequence is row kr_slot_row (kr_slot_cache.h) of them.  A tile of FA_TK positions starts at a multiple of FA_TK, so it lies in one page, or in two
 // at 32 positions per page.  lo = the byte offset of the page of p0 .. p0 + 31, hi = that of the page of min(p0 + 32, kv_end - 1), which holds every position of
 // rows 32 .. 63 that is loaded, clamped ones included.  Both positions lie in [0, kv_end): the host mapped their pages before the pass; -1 is never turned into
 // an address all the same.  The ids are workgroup-uniform and stay in scalar registers
 __device__ __forceinline__ void kr_pf_tile_pages(const int* ptab, int psh, int p0, int kv_end, size_t rowb, size_t& lo, size_t& hi) {
-    const int i0 = __builtin_amdgcn_readfirstlane(max(ptab[p0 >> psh], 0)), i1 = __builtin_amdgcn_readfirstlane(max(ptab[min(p0 + 32, kv_end - 1) >> psh], 0));
-    lo = ((size_t)i0 << psh) * rowb; hi = ((size_t)i1 << psh) * rowb;
+    const int i0 = __builtin_amdgcn_readfirstlane(kr_slot_page_id(ptab[kr_slot_entry(p0, psh)]));
+    const int i1 = __builtin_amdgcn_readfirstlane(kr_slot_page_id(ptab[kr_slot_entry(min(p0 + 32, kv_end - 1), psh)]));
+    lo = kr_slot_page_row(i0, 0, psh, 0) * rowb; hi = kr_slot_page_row(i1, 0, psh, 0) * rowb;      // the pages' first rows
 }
 
 // ---- the four-wave form (head_dim 64): 256 threads, grid (tiles, nkv), dynamic LDS FA_TK * (HD * 2 + 16) + HD * (FA_TK * 2 + 16) bytes.
 // This form is ONE KERNEL TEMPLATE for both callers, not an inlined device function: compiled as a callee inlined into a one-line kernel the register
 // allocator splits the same text differently (130 + 64 instead of 158 + 32 VGPRs + AGPRs, the E4M3 instantiation 2 instead of 3 waves per SIMD), as a kernel of
 // its own it keeps the allocation it always had.  Tiles says where the workgroup's tile lies: its argument structure Tiles::Args (with the members q_out, gate,
-// attn_out, k_cache, v_cache, gated, nh, nkv, sm_scale), constructed from (a, Ck, tokens per tile) with C, t0, pos0, row(t) = the row of token t, and, for
+// attn_out, gated, nh, nkv, sm_scale; Tiles::cache(a, h) = its K (0) / V (1) rows), constructed from (a, Ck, tokens per tile) with C, t0, pos0, row(t) = the row of token t, and, for
 // Tiles::SLOTS, cache_off = bytes to the sequence's row 0, for Tiles::PAGED, ptab / psh.  KrPfChunkTiles (kr_attn_flash.hip): the prompt pass's chunk, every
 // member a compile-time identity, Ck = the chunk's tokens; KrPfSlotTiles<FP8, PAGED> (kr_multi_pf_flash.hip): a run of a batched pass, from its tile table
 template <int HD, bool FP8, class Tiles>
@@ -96,12 +97,12 @@ __global__ void __launch_bounds__(256) kr_pfm_gqa_flash_kernel(const typename Ti
     float m_run = -__builtin_inff(), l_run = 0.0f;
 
     // ---- tile staging: global -> registers (issued one tile ahead) -> LDS
-    const unsigned char* kc = reinterpret_cast<const unsigned char*>(a.k_cache) + (size_t)kvh * HD * esz;
-    const unsigned char* vc = reinterpret_cast<const unsigned char*>(a.v_cache) + (size_t)kvh * HD * esz;
+    const unsigned char* kc = reinterpret_cast<const unsigned char*>(Tiles::cache(a, 0)) + (size_t)kvh * HD * esz;
+    const unsigned char* vc = reinterpret_cast<const unsigned char*>(Tiles::cache(a, 1)) + (size_t)kvh * HD * esz;
     if constexpr (Tiles::SLOTS) { kc += tl.cache_off; vc += tl.cache_off; }
     [[maybe_unused]] const size_t rowb = (size_t)kvs * esz;
     [[maybe_unused]] int pmask = 0;
-    if constexpr (PAGED) pmask = (1 << tl.psh) - 1;
+    if constexpr (PAGED) pmask = kr_slot_mask(tl.psh);
     u32x4 pk[KCH], pva[VPT], pvb[VPT];
     auto load_k = [&](int p0) {
         [[maybe_unused]] size_t lo = 0, hi = 0;
@@ -109,7 +110,7 @@ __global__ void __launch_bounds__(256) kr_pfm_gqa_flash_kernel(const typename Ti
 #pragma unroll
         for (int j = 0; j < KCH; j++) {
             const int c = tid + j * 256, row = c / CPR, dc = c % CPR, p = p0 + row;
-            if constexpr (PAGED) pk[j] = p < kv_end ? *reinterpret_cast<const u32x4*>(kc + (row >= 32 ? hi : lo) + (size_t)(p & pmask) * rowb + dc * 16) : u32x4{0, 0, 0, 0};
+            if constexpr (PAGED) pk[j] = p < kv_end ? *reinterpret_cast<const u32x4*>(kc + (row >= 32 ? hi : lo) + (size_t)kr_slot_in_page(p, pmask) * rowb + dc * 16) : u32x4{0, 0, 0, 0};
             else pk[j] = p < kv_end ? *reinterpret_cast<const u32x4*>(kc + (size_t)p * kvs * esz + dc * 16) : u32x4{0, 0, 0, 0};
         }
     };
@@ -122,7 +123,7 @@ __global__ void __launch_bounds__(256) kr_pfm_gqa_flash_kernel(const typename Ti
             pva[j] = u32x4{0, 0, 0, 0}; pvb[j] = u32x4{0, 0, 0, 0};
             if (u < VUN) {
                 if constexpr (PAGED) {      // p is even: p and p + 1 share a page
-                    const unsigned char* ra = vc + (pp >= 16 ? hi : lo) + (size_t)(p & pmask) * rowb + dc * 16;
+                    const unsigned char* ra = vc + (pp >= 16 ? hi : lo) + (size_t)kr_slot_in_page(p, pmask) * rowb + dc * 16;
                     if (p < kv_end) pva[j] = *reinterpret_cast<const u32x4*>(ra);
                     if (p + 1 < kv_end) pvb[j] = *reinterpret_cast<const u32x4*>(ra + rowb);
                 } else {
@@ -301,15 +302,15 @@ __device__ __forceinline__ void kr_pfm_flashw_body(const Args& a, int C, int t0,
     chunk_t stg[NCH];
     const unsigned char* cache = reinterpret_cast<const unsigned char*>(wave < 4 ? a.k_cache : a.v_cache) + (size_t)kvh * HD * esz + sdc * (FP8 ? 8 : 16);
     const size_t rowb = (size_t)kvs * esz;                       // bytes between cache rows (wave-uniform)
-    [[maybe_unused]] const int pmask = (1 << psh) - 1;
+    [[maybe_unused]] const int pmask = kr_slot_mask(psh);
     auto stage_load = [&](int p0, bool zero_past_end) {
         // PAGED: thread row srow + RSTEP j of the tile lies in the tile's first half (page lo) for j < NCH / 2 and in its second (page hi) otherwise
         [[maybe_unused]] size_t lo = 0, hi = 0;
         if constexpr (PAGED) kr_pf_tile_pages(ptab, psh, p0, kv_end, rowb, lo, hi);
         if (p0 + FA_TK <= kv_end) {                             // whole tile inside the cache rows this workgroup may see: one 64-bit multiply per tile, then row steps
             if constexpr (PAGED) {                              // ... per half: each has its page's base
-                const unsigned char* rl = cache + lo + (size_t)((p0 + srow) & pmask) * rowb;
-                const unsigned char* rh = cache + hi + (size_t)((p0 + 32 + srow) & pmask) * rowb;
+                const unsigned char* rl = cache + lo + (size_t)kr_slot_in_page(p0 + srow, pmask) * rowb;
+                const unsigned char* rh = cache + hi + (size_t)kr_slot_in_page(p0 + 32 + srow, pmask) * rowb;
 #pragma unroll
                 for (int j = 0; j < NCH; j++) stg[j] = *reinterpret_cast<const chunk_t*>((j < NCH / 2 ? rl : rh) + (size_t)(RSTEP * (j < NCH / 2 ? j : j - NCH / 2)) * rowb);
             } else {
@@ -322,7 +323,7 @@ __device__ __forceinline__ void kr_pfm_flashw_body(const Args& a, int C, int t0,
             for (int j = 0; j < NCH; j++) {
                 const int p = p0 + srow + RSTEP * j;
                 chunk_t v;
-                if constexpr (PAGED) v = *reinterpret_cast<const chunk_t*>(cache + (j < NCH / 2 ? lo : hi) + (size_t)(min(p, kv_end - 1) & pmask) * rowb);
+                if constexpr (PAGED) v = *reinterpret_cast<const chunk_t*>(cache + (j < NCH / 2 ? lo : hi) + (size_t)kr_slot_in_page(min(p, kv_end - 1), pmask) * rowb);
                 else v = *reinterpret_cast<const chunk_t*>(cache + (size_t)min(p, kv_end - 1) * rowb);
                 stg[j] = (zero_past_end && p >= kv_end) ? chunk_t{} : v;      // K rows past the end are masked by the causal test; V rows meet P = 0 and must be finite
             }

@@ -10,6 +10,7 @@
 
 #include "kr_device.h"
 #include "kr_libm.h"
+#include "kr_slot_cache.h"
 
 typedef float xm_v16f __attribute__((ext_vector_type(16)));
 typedef float xm_f4 __attribute__((ext_vector_type(4)));
@@ -23,13 +24,10 @@ struct KrXmSeq {
 };
 // the prompt pass: token t of the chunk is row t
 struct KrXmRowsIdentity { __device__ __forceinline__ int operator()(int t) const { return t; } };
-// cache row of position p.  PAGED: ptab = the slot's row of the page table, 1 << psh tokens a page; every page of the positions a tile reads was mapped by the
-// host before the pass (-1 is clamped to page 0 all the same: a read, never a fault)
+// cache row of position p: kr_slot_row (kr_slot_cache.h) under the name the passes call it by.  PAGED: ptab = the slot's row of the page table, 1 << psh tokens a
+// page; every page of the positions a tile reads was mapped by the host before the pass (-1 is clamped to page 0 all the same: a read, never a fault)
 template <bool PAGED>
-__device__ __forceinline__ size_t kr_xm_cache_row(int p, const int* ptab, int psh) {
-    if constexpr (PAGED) return ((size_t)max(ptab[p >> psh], 0) << psh) | (size_t)(p & ((1 << psh) - 1));
-    else return (size_t)p;
-}
+__device__ __forceinline__ size_t kr_xm_cache_row(int p, const int* ptab, int psh) { return kr_slot_row<PAGED>(p, ptab, psh); }
 
 // ------------------------------------------------------------------------------------------------------------------------------------
 // pass A, one workgroup of 4 waves = 2 x 2 blocks of 32 queries x 32 positions: the position tile at p_lo, the query tile at token t0 (64 / group tokens) of KV

@@ -23,10 +23,10 @@ def test_paging_is_a_template_parameter_of_the_body_and_the_kernel():
     assert "const int* ptab = nullptr" in body.group(2) and "int psh = 0" in body.group(2)
     dev = _src("kr_fd_flash_dev.h")
     assert dev.count("if constexpr (PAGED)") >= 4                          # the table walk, and the three cache addresses (K, and V's pair)
-    assert "__builtin_amdgcn_readfirstlane(max(ptab[" in dev                # page ids: clamped, workgroup-uniform, in scalar registers
+    assert "__builtin_amdgcn_readfirstlane(kr_slot_page_id(ptab[" in dev                # page ids: clamped, workgroup-uniform, in scalar registers
     kernel = re.search(r"template <([^>]*)>\s*__global__ void __launch_bounds__\(256\) kr_multi_fd_flash_kernel\(", _src("kr_multi_flash.hip"))
     assert kernel and "bool PAGED" in kernel.group(1)
-    assert "a.page_table + (size_t)a.slots[b] * a.page_stride, a.page_shift" in _src("kr_multi_flash.hip")
+    assert "kr_fd_flash_body<HD, FP8, PAGED>(" in _src("kr_multi_flash.hip") and "PAGED ? kr_slot_table_row(a.kv.pg, slot) : nullptr, PAGED ? a.kv.pg.shift : 0" in _src("kr_multi_flash.hip")
     single = _src("kr_attn_flash.hip")
     assert "kr_fd_flash_body<HD, FP8>(" in single and "page" not in re.search(r"kr_fd_flash_body<HD, FP8>\([^;]*;", single).group(0)
     merge = re.search(r"template <([^>]*)>\s*__global__ void __launch_bounds__\(1024\) kr_multi_fd_merge_kernel\(", _src("kr_multi_flash.hip"))
@@ -35,7 +35,7 @@ def test_paging_is_a_template_parameter_of_the_body_and_the_kernel():
 
 def test_launcher_dispatches_and_prepares_the_paged_instantiations():
     flash = _src("kr_multi_flash.hip")
-    assert re.search(r"if \(a\.page_table\) hipLaunchKernelGGL\(\(kr_multi_fd_flash_kernel<H_, F_, true>\)", flash)
+    assert re.search(r"if \(a\.kv\.pg\.table\) hipLaunchKernelGGL\(\(kr_multi_fd_flash_kernel<H_, F_, true>\)", flash)
     assert re.search(r"int kr_multi_fd_prepare\(int hd, int fp8, int paged\)", flash)
     assert "kr_lds_optin(paged ? multi_fd_fn<true>(hd, fp8) : multi_fd_fn<false>(hd, fp8), lds)" in flash
     for hd in (256, 128, 64):
@@ -44,7 +44,7 @@ def test_launcher_dispatches_and_prepares_the_paged_instantiations():
     multi = _src("kr_multi.hip")
     fd = multi[multi.index("if (a.fd_o) {"):multi.index("if (lds > KR_MULTI_GQA_LDS_MAX)")]
     assert "kr_multi_gqa_prep_kernel<true>" in fd and "kr_multi_gqa_prep_kernel<false>" in fd and "return kr_launch_multi_fd(" in fd
-    assert not re.search(r"if \(a\.page_table\) return 1;", fd)            # the early return is gone
+    assert not re.search(r"if \(a\.kv\.pg\.table\) return 1;", fd)            # the early return is gone
     assert "kr_multi_fd_prepare(L.hd, M.kv_fp8, M.pg.paged())" in _src("kr_decode_prefill.cpp")
 
 

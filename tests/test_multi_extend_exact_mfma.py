@@ -68,7 +68,7 @@ def test_one_body_two_callers():
     dev = _src("kr_xm_dev.h")
     assert re.search(r"template <bool FP8, bool PAGED, class Rows>\s*__device__ __forceinline__ void kr_xm_scores_body\(", dev)
     assert re.search(r"template <bool FP8, int HD, int PS, bool PAGED, class Rows>[^\n]*\s*__device__ __forceinline__ void kr_xm_pv_body\(", dev)
-    assert dev.count("__builtin_amdgcn_mfma_f32_32x32x2f32") == 2 and "max(ptab[p >> psh], 0)" in dev
+    assert dev.count("__builtin_amdgcn_mfma_f32_32x32x2f32") == 2 and "kr_slot_row<PAGED>(p, ptab, psh)" in dev
     assert "asm" not in re.sub(r"//.*", "", dev) and "__shared__" not in dev
     single = _src("kr_attn_exact_mfma.hip")
     assert "kr_xm_scores_body<FP8, false>(" in single and "kr_xm_pv_body<FP8, HD, PS, false>(" in single and single.count("KrXmRowsIdentity()") == 2
@@ -79,7 +79,7 @@ def test_one_body_two_callers():
     multi = _src("kr_multi_xm.hip")
     code = re.sub(r"//.*", "", multi)
     assert "kr_xm_scores_body<FP8, PAGED>(" in multi and "kr_xm_pv_body<FP8, HD, 64, PAGED>(" in multi
-    assert "kr_m_run_row(i, off, cnt, t)" in multi and "a.page_table + (size_t)slot * a.page_stride" in multi
+    assert "kr_m_run_row(i, off, cnt, t)" in multi and "kr_slot_table_row(a.kv.pg, (size_t)slot)" in multi
     assert "__builtin_amdgcn_mfma" not in code and "asm" not in code and "extern __shared__" not in code      # no matrix-core text of its own, static LDS only
     for hd in (64, 128, 256):
         assert "KR_XC(true, %d)" % hd in multi and "KR_XC(false, %d)" % hd in multi

@@ -71,7 +71,7 @@ def test_one_body_two_callers():
     assert m and "bool PAGED = false" in m.group(1) and "class RowMap" in m.group(1)
     assert "const int* ptab = nullptr" in m.group(2) and "int psh = 0" in m.group(2)
     assert dev.count("if constexpr (PAGED)") >= 6                           # the four-wave form's K and V loads, the wave-specialised form's fast and clamped path
-    assert "__builtin_amdgcn_readfirstlane(max(ptab[" in dev                # page ids: clamped, workgroup-uniform, in scalar registers
+    assert "__builtin_amdgcn_readfirstlane(kr_slot_page_id(ptab[" in dev                # page ids: clamped, workgroup-uniform, in scalar registers
     assert "__shared__ int" not in dev                                      # no LDS holds the table
     single = _src("kr_attn_flash.hip")
     ahead = single.split("kr_fd_flash_kernel")[0]                           # everything ahead of the decode kernels
@@ -92,8 +92,8 @@ def test_one_body_two_callers():
     assert m and "bool PAGED_" in m.group(1) and "static constexpr bool PAGED = PAGED_" in multi
     assert "kr_pfm_gqa_flash_kernel<H_, F_, KrPfSlotTiles<F_, true>>" in multi and "kr_pfm_gqa_flash_kernel<H_, F_, KrPfSlotTiles<F_, false>>" in multi
     assert "__launch_bounds__(256)" not in multi                            # no four-wave kernel of its own
-    assert "kr_pfm_flashw_body<HD, FP8, true>(" in multi and "kr_pfm_flashw_body<HD, FP8>(" in multi
-    assert multi.count("a.page_table + (size_t)slot * a.page_stride") == 2
+    assert "kr_pfm_flashw_body<HD, FP8, PAGED>(" in multi      # one call, flat or paged
+    assert multi.count("kr_slot_table_row(a.kv.pg, (size_t)slot)") == 2
     assert "kr_m_run_row(i, off, cnt, t)" in multi and "kr_m_run_row(run, off, C, t)" in multi      # the flatten of 17-multi-extend.md
     assert "asm" not in re.sub(r"//.*", "", multi)                          # no inline assembly beyond what the moved bodies hold
     # the form is chosen by the single-sequence launcher's rule
@@ -119,7 +119,7 @@ def test_the_batched_launcher_keeps_its_lines_and_gains_the_run_path():
     assert flash.count("if (kr_m_row_in_run(a, b)) return;") == 2
     hdr = _src("kr_multi.h")
     body = re.search(r"struct KrMultiGqaArgs \{(.*?)\n\};", hdr, re.S).group(1)
-    assert "const int* page_table; int page_stride, page_shift;" in body
+    assert "KrSlotCache kv;" in body      # the page table travels in the cache view (kr_slot_cache.h)
     assert body.rstrip().endswith("const int* pf_runs; const int* pf_tiles; int pf_nruns, pf_ntiles, pf_units;")      # new fields at the end
     assert "return a.pf_runs && a.pf_runs[3 * b + 2] >= 2;" in hdr          # null pointer: no row is skipped
     pre = _src("kr_decode_prefill.cpp")

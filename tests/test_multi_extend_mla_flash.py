@@ -66,9 +66,9 @@ def test_one_body_with_a_row_map_and_two_kinds_of_caller():
     multi = _src("kr_multi_mla_pf_flash.hip")
     kernel = re.search(r"template <([^>]*)>\s*__global__ void __launch_bounds__\(256\) kr_multi_mla_pf_flash_kernel\(const KrMultiMlaArgs a\)", multi)
     assert kernel and kernel.group(1) == "int KLR, bool FP8, bool PAGED"
-    assert "kr_mla_flash_body<KLR, FP8, false, true>(" in multi and "kr_mla_flash_body<KLR, FP8, false>(" in multi
-    assert "a.page_table + slot * a.page_stride, a.page_shift, rows" in multi
-    assert "(const char*)a.ckv_cache + slot * a.ckv_stride, (const char*)a.kpe_cache + slot * a.kpe_stride" in multi
+    assert "kr_mla_flash_body<KLR, FP8, false, PAGED>(" in multi      # one call, flat or paged
+    assert "PAGED ? kr_slot_table_row(a.kv.pg, slot) : nullptr, PAGED ? a.kv.pg.shift : 0, rows" in multi
+    assert "kr_slot_base<PAGED>(a.kv, 0, slot), kr_slot_base<PAGED>(a.kv, 1, slot)" in multi
     assert "return kr_m_run_row(run, off, cnt, t) * nh + (g - t * nh);" in multi and "a.positions[kr_m_run_row(run, off, cnt, 0)]" in multi
     kcode = _code(multi[multi.index("kr_multi_mla_pf_flash_kernel(const KrMultiMlaArgs a)"):multi.index("static_assert")])
     assert "return;" not in kcode and "__syncthreads" not in kcode           # every workgroup has a tile: no exit ahead of the body's barriers
@@ -110,7 +110,7 @@ def test_refusal_clause_stands_between_its_neighbours_and_names_the_option():
 def test_new_fields_at_the_end_and_per_row_kernels_leave_longer_runs():
     hdr = _src("kr_multi.h")
     body = re.search(r"struct KrMultiMlaArgs \{(.*?)\n\};", hdr, re.S).group(1)
-    assert "const int* page_table; int page_stride, page_shift;" in body and "float *fd_o, *fd_ml; int fd_chunk, fd_chunks;" in body
+    assert "KrSlotCache kv;" in body and "float *fd_o, *fd_ml; int fd_chunk, fd_chunks;" in body
     assert body.rstrip().endswith("const int* mf_runs; const int* mf_tiles; int mf_nruns, mf_ntiles, mf_units;")
     assert "kr_m_row_in_run(const KrMultiMlaArgs& a, int b) { return a.mf_runs && a.mf_runs[3 * b + 2] >= 2; }" in hdr      # null pointer: no row is skipped
     multi = _src("kr_multi.hip")

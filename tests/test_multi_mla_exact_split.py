@@ -76,9 +76,9 @@ def test_the_refusal_is_asked_last():
 def test_the_three_sites_take_the_split_behind_their_own_checks():
     multi = _src("kr_multi.hip")
     assert multi.count("kr_launch_multi_mla_split(") == 3      # kr_launch_multi_mla (flat and paged: one call behind KR_MMA_ALL), multi_mla_runs, kr_launch_multi_mla_xm
-    sites = {"int kr_launch_multi_mla(const KrMultiMlaArgs& a_in, int B, hipStream_t st) {": ("kr_launch_multi_mla_split(a, B, st)", ("kr_multi_mla_ok(", "a.sc_ld % 32", "a.page_stride < 1", "kr_multi_mla_fd_ok(")),
+    sites = {"int kr_launch_multi_mla(const KrMultiMlaArgs& a_in, int B, hipStream_t st) {": ("kr_launch_multi_mla_split(a, B, st)", ("kr_multi_mla_ok(", "a.sc_ld % 32", "kr_slot_stage_fits(a.kv.pg, KR_MM_ROWS)", "kr_multi_mla_fd_ok(")),
              "static int multi_mla_runs(KrMultiMlaArgs& a, int B, hipStream_t st) {": ("kr_launch_multi_mla_split(a, a.mf_nruns, st)", ("kr_multi_mla_pf_args_ok(a)", "kr_multi_mla_fd_ok(", "!a.scores || a.sc_ld < 32")),
-             "int kr_launch_multi_mla_xm(": ("kr_launch_multi_mla_split(a, n_runs, st)", ("kr_multi_mla_ok(", "a.sc_ld % 32", "a.page_stride < 1", "kr_multi_mla_xm_args_ok(a, x)", "kr_multi_mla_fd_ok("))}
+             "int kr_launch_multi_mla_xm(": ("kr_launch_multi_mla_split(a, n_runs, st)", ("kr_multi_mla_ok(", "a.sc_ld % 32", "kr_slot_stage_fits(a.kv.pg, KR_MM_ROWS)", "kr_multi_mla_xm_args_ok(a, x)", "kr_multi_mla_fd_ok("))}
     for fn, (site, checks) in sites.items():
         body = _body(multi, fn)
         assert body.count("kr_launch_multi_mla_split(") == 1 and site in body, fn
@@ -89,7 +89,7 @@ def test_the_three_sites_take_the_split_behind_their_own_checks():
         assert "!a.fd_o && a.xs_split && kr_launch_multi_mla_split(" in body, fn      # the flash-decode pair takes the rows first: the flag is not read
     # multi_mla_runs is reached from kr_launch_multi_mla only, behind that function's checks
     outer = _body(multi, "int kr_launch_multi_mla(const KrMultiMlaArgs& a_in, int B, hipStream_t st) {")
-    assert outer.index("a.page_stride < 1") < outer.index("if (a.mf_tiles) return multi_mla_runs(a, B, st);")
+    assert outer.index("kr_slot_stage_fits(a.kv.pg, KR_MM_ROWS)") < outer.index("if (a.mf_tiles) return multi_mla_runs(a, B, st);")
     hdr = _src("kr_multi.h")
     assert "int kr_launch_multi_mla_split(const KrMultiMlaArgs& a, int rows, hipStream_t st);" in hdr
     struct = re.search(r"struct KrMultiMlaArgs \{(.*?)\n\};", hdr, re.S).group(1)

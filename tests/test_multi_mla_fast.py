@@ -24,7 +24,7 @@ def test_paging_is_a_template_parameter_of_the_body_and_the_kernel():
     assert body and "bool SPLIT" in body.group(1) and "bool PAGED = false" in body.group(1)
     assert "const int* ptab = nullptr" in body.group(2) and "int psh = 0" in body.group(2)
     assert dev.count("if constexpr (PAGED)") >= 2                          # the table entry of the tile, and the cache addresses
-    assert "__builtin_amdgcn_readfirstlane(max(ptab[p0 >> psh], 0))" in dev     # one page id per tile: clamped, workgroup-uniform, in scalar registers
+    assert "__builtin_amdgcn_readfirstlane(kr_slot_page_id(ptab[kr_slot_entry(p0, psh)]))" in dev     # one page id per tile: clamped, workgroup-uniform, in scalar registers
     code = re.sub(r"//[^\n]*", "", dev)
     assert "asm(" not in code and "asm volatile" not in code
     assert code.count("ptab") == 2                                          # the parameter and that one read: no LDS copy of the table
@@ -35,8 +35,8 @@ def test_paging_is_a_template_parameter_of_the_body_and_the_kernel():
     multi = _src("kr_multi_mla_flash.hip")
     kernel = re.search(r"template <([^>]*)>\s*__global__ void __launch_bounds__\(256\) kr_multi_mla_flash_kernel\(", multi)
     assert kernel and "bool PAGED" in kernel.group(1)
-    assert "kr_mla_flash_body<KLR, FP8, true, true>(" in multi and "kr_mla_flash_body<KLR, FP8, true>(" in multi
-    assert "a.page_table + slot * a.page_stride, a.page_shift" in multi
+    assert "kr_mla_flash_body<KLR, FP8, true, PAGED>(" in multi      # one call, flat or paged
+    assert "PAGED ? kr_slot_table_row(a.kv.pg, slot) : nullptr, PAGED ? a.kv.pg.shift : 0" in multi
     merge = re.search(r"template <([^>]*)>\s*__global__ void __launch_bounds__\(1024\) kr_multi_mla_merge_kernel\(([^)]*)\)", multi)
     assert merge and "PAGED" not in merge.group(1) and "page" not in merge.group(2)      # partials are indexed by row, not by slot
     assert "kr_fd_merge2_body<KLR>(a.positions[b] + 1, blockIdx.x," in multi
@@ -44,7 +44,7 @@ def test_paging_is_a_template_parameter_of_the_body_and_the_kernel():
 
 def test_launcher_dispatches_and_prepares_the_paged_instantiations():
     multi = _src("kr_multi_mla_flash.hip")
-    assert re.search(r"if \(a\.page_table\) hipLaunchKernelGGL\(\(kr_multi_mla_flash_kernel<K_, F_, true>\)", multi)
+    assert re.search(r"if \(a\.kv\.pg\.table\) hipLaunchKernelGGL\(\(kr_multi_mla_flash_kernel<K_, F_, true>\)", multi)
     assert re.search(r"int kr_multi_mla_fd_prepare\(int klr, int fp8, int paged\)", multi)
     assert "kr_lds_optin(paged ? multi_mla_fd_fn<true>(klr, fp8) : multi_mla_fd_fn<false>(klr, fp8), lds)" in multi
     for klr in (512, 256):

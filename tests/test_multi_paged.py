@@ -70,7 +70,8 @@ def test_paging_is_a_template_parameter_of_the_four_kernels():
         assert m and "bool PAGED" in m.group(1), kernel
     for struct in ("KrMultiGqaArgs", "KrMultiMlaArgs"):
         body = re.search(r"struct %s \{(.*?)\n\};" % struct, open(os.path.join(CSRC, "kr_multi.h")).read(), re.S).group(1)
-        assert "const int* page_table; int page_stride, page_shift;" in body, struct
+        assert "KrSlotCache kv;" in body, struct      # the page table travels in the cache view (kr_slot_cache.h)
+    assert "struct KrSlotPages { const int* table; int stride, shift; };" in open(os.path.join(CSRC, "kr_slot_cache.h")).read()
 
 
 def test_the_allocator_is_host_only_and_in_the_build():
@@ -91,3 +92,15 @@ def test_allocator_program_under_sanitizers(tmp_path):
                            "-I", CSRC, "-o", exe, os.path.join(ROOT, "tests", "page_pool_check.cpp")])      # runtimes inside the program: no library order to get wrong
     run = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     assert run.returncode == 0 and "page pool ok" in run.stdout, run.stdout
+
+
+def test_slot_cache_view_program_under_sanitizers(tmp_path):
+    """the page map against its longhand formula at page sizes 32 to 256, the flat case, the byte bases and the stage predicate on both sides of its
+    boundary: tests/slot_cache_check.cpp with its own main, compiled alone with -fsanitize=address,undefined and run as a child process"""
+    cxx = shutil.which("g++") or shutil.which("c++")
+    assert cxx, "no host C++ compiler"
+    exe = str(tmp_path / "slot_cache_check")
+    subprocess.check_call([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan",
+                           "-I", CSRC, "-o", exe, os.path.join(ROOT, "tests", "slot_cache_check.cpp")])
+    run = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert run.returncode == 0 and "slot cache ok" in run.stdout, run.stdout
