@@ -98,9 +98,16 @@ int kr_upload_expert_bf16(kr_engine* e, int layer, int expert, int inter, const 
  * words and bf16 scales in [0.005,0.05] -- the distribution of bench_decode_synthetic (decode.rs:4379-4392),
  * generated by a counter hash on the GPU instead of one serial xorshift stream. */
 int kr_fill_layer_synthetic(kr_engine* e, int layer, int bits, uint64_t seed);
-/* the native-GGUF twin: every routed expert of the layer as Q4_K (12) / Q8_0 (8) blocks with the block distribution SURVEY 8d defines
- * (raw quant / scale bytes, d = f16((0.005 + u * 0.045) / 63), dmin = f16(8 d); Q8_0: d = f16((0.005 + u * 0.045) / 127)) */
+/* the native-GGUF twin: every routed expert of the layer as Q4_K (12) / Q8_0 (8) / Q5_0 (6) / Q6_K (14) blocks with the block distribution SURVEY 8d defines
+ * (raw quant / scale bytes, d = f16((0.005 + u * 0.045) / 63), dmin = f16(8 d); Q8_0: d = f16((0.005 + u * 0.045) / 127); Q5_0: d = f16((0.005 + u * 0.045) / 15);
+ * Q6_K: d = f16((0.005 + u * 0.045) / 31 / 127)) */
 int kr_fill_layer_synthetic_gguf(kr_engine* e, int layer, int gate_up_type, int down_type, uint64_t seed);
+/* The Q5_0 (6) / Q6_K (14) kernels as a stand-alone operator: y[N] = W x for N rows of raw row-major GGUF blocks and an f32 vector x[K], all host pointers;
+ * K a multiple of the block size (32 / 256), at most 15360; any N >= 1.  parts 0: the reference's serial f32 chain per row (gguf_kernels.rs:572-635), bit for
+ * bit what the exact MoE kernels compute for such a matrix.  parts 1 | 2: the tolerance tile of KR_DECODE_FAST (8 lanes per row, the reference's terms,
+ * tree-ordered sums) over the whole row, or over two slices of its blocks whose results are added -- what the two k-waves of the mode's gate|up launch do.
+ * Re-tiles into a scratch matrix, one launch, copies back; keeps no state on the engine.  Anything else: KR_ERR_VALUE. */
+int kr_gguf_matvec(kr_engine* e, int type, const uint8_t* blocks, int N, int K, const float* x, float* y, int parts);
 /* Read one expert back in the reference layout (inverse re-tiling); used by parity tests at full size. */
 int kr_download_expert_unified(kr_engine* e, int layer, int expert, void* w13, uint16_t* w13_scales,
                                void* w2, uint16_t* w2_scales);
@@ -351,6 +358,10 @@ int kr_decode_set_attention_mode(kr_decode_store* s, int mode);
  * topk - 1 - y in routed grid row y, so that the slots with the longest select are handed out first; with 0 row y serves slot y; without the per-slot select
  * the value changes nothing.  Scheduling only, no workgroup reads another's output inside the launch; same bits either way
  * (tests/test_decode_fast_stragglers_gpu.py).  A/B and test hook.
+ * "gguf_scalar_tiles" (default 1; docs/design/41-gguf-scalar-tiles.md): KR_DECODE_FAST, native-GGUF MoE layers with a Q5_0 or Q6_K matrix: with 1 the routed
+ * slots of the mode's gate|up and down launches walk such a matrix with the f32 tiles (the reference's terms d (q - 16) x / (d sc)(q - 32) x from the f32
+ * activation vector, 8 lanes per row, tree-ordered sums; nothing is quantised, as in the reference); with 0 such a layer leaves the mode's three MoE
+ * launches for the exact block kernels and a combine launch, as before the tiles existed.  Refuses nothing.  A/B and test hook.
  * "pass_few_rows" (default 0; docs/design/34-pass-few-rows.md): with 1, a multi-row pass of T <= "pass_few_rows_max" token rows -- T = n_tokens for
  * kr_decode_prefill / kr_decode_prefill_nll / kr_decode_verify, the sum of the counts for the slot entry points; decided per pass, never per chunk -- runs every
  * projection (q|k|v, qkvz|ba, out / o, the MLA kv_a / q / q_a / q_b, the shared expert, the dense MLP, the all-row lm_head) on the few-row streaming matvec

@@ -12,6 +12,7 @@
 //   kr_launch_fw13    scoring + top-k (decode.rs:4088, wave-parallel; ids identical to the exact kernel for identical logits unless two leaders
 //                     tie, then the reference's heap order is emulated) in the prologue of the gate|up matvec; silu(g) * u in its epilogue
 //                     (lean routing rule: a routed workgroup selects the id of its own rank only, an extra grid row publishes ids / weights: KrFmoeArgs::slot_select)
+//                     (native GGUF experts: the block kernels' products per routed slot; Q5_0 / Q6_K blocks: the reference's f32 terms, kr_gguf_dev.h)
 //   kr_launch_fw2     INT16 quantisation of the expert hidden, down matvec of all k (+ shared) experts of one column tile in ONE workgroup
 //                     and the weighted combine (moe.rs:661-667, decode.rs:3343-3402) -- the MoE output lands in the hidden buffer
 #pragma once
@@ -63,6 +64,8 @@ struct KrFmoeArgs {
                               // extra grid row publishes ids / wts (docs/design/33-slot-select.md); 0 = every workgroup runs the full select, workgroup (0, 0) publishes
     int slot_rows_late_first; // w13 launch under the per-slot select: routed grid row y serves slot topk - 1 - y, so that the slots with the longest select start first
                               // (docs/design/35-launch-stragglers.md); 0 = row y serves slot y.  Scheduling only: same bits
+    int gguf_scalar_tiles;    // "gguf_scalar_tiles": Q5_0 (K % 32 == 0) / Q6_K (K % 256 == 0) matrices are accepted too -- the f32 tiles gg_tile_q5_0 / gg_tile_q6k: the reference's terms
+                              // d (q - 16) x / (d sc)(q - 32) x from bf16(act_f32) resp. silu(gate) * up kept as f32, nothing quantised (docs/design/41-gguf-scalar-tiles.md); 0 = such a layer is refused
 };
 int kr_fmoe_check(const KrFmoeArgs& a);      // 0 when both launches below cover the geometry
 int kr_launch_fw13(const KrFmoeArgs& a, hipStream_t st);

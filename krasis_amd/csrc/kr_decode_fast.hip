@@ -829,7 +829,16 @@ __device__ __forceinline__ bool kr_f_slot_select(const float* logits, int E, int
 // (gate tile t and up tile t + I / 8 of the same hidden column), 2 waves split K; epilogue h = silu(g) * u (avx2.rs:2331-2333, decode.rs:1731-1733).
 // ---------------------------------------------------------------------------------------------------------------------------------
 // (leading scalars = what the select wave and the image copy need for their first requests, preloaded into SGPRs: see kr_fdm_kernel)
-template <int BITS, int NU>
+// bytes of the activation image at the head of the gate|up launch's dynamic LDS (the select's scratch follows): the largest form a workgroup of the launch may build
+__host__ __device__ static inline size_t kr_fw13_img_bytes(int H, bool w8, bool gguf, bool gs) {
+    size_t n = kr_lds_bytes(H, w8);
+    if (gguf && gg_lds_bytes(H, false) > n) n = gg_lds_bytes(H, false);
+    if (gs && (size_t)H * 4 > n) n = (size_t)H * 4;
+    return n;
+}
+// GS: the routed experts' gate | up blocks are Q5_0 / Q6_K (gg_tile_q5_0 / gg_tile_q6k: the reference's terms from the f32 vector, nothing quantised): waves 1-3 leave
+// bf16(hidden) as f32 at the head of the dynamic LDS instead of the per-32 image
+template <int BITS, int NU, bool GS = false>
 __global__ void __launch_bounds__(256) kr_fw13_kernel(const float* p_logits, const float* p_esc, const void* p_img_bf16, int p_E, int p_topk, int p_scoring, int p_norm, int p_H, int p_I, int p_gguf, int p_pub,
                                                       const KrFmoeArgs fa) {
     const KrMoeArgs& a = fa.m;
@@ -857,8 +866,9 @@ __global__ void __launch_bounds__(256) kr_fw13_kernel(const float* p_logits, con
     const int tw = wave >> 1, ks = wave & 1;
     const KrActLds L = kr_carve_lds(kr_fsm, p_H, BITS == 8);
     const bool gg = p_gguf && !shared;                  // routed slot on native GGUF blocks: per-32 activation image instead of the per-128 one
-    const GgAct GA = gg_carve(reinterpret_cast<char*>(kr_fsm), p_H);
-    const size_t img_bytes = p_gguf ? (kr_lds_bytes(p_H, BITS == 8) > gg_lds_bytes(p_H, false) ? kr_lds_bytes(p_H, BITS == 8) : gg_lds_bytes(p_H, false)) : kr_lds_bytes(p_H, BITS == 8);
+    GgAct GA = gg_carve(reinterpret_cast<char*>(kr_fsm), p_H);
+    if constexpr (GS) GA.f32v = reinterpret_cast<float*>(kr_fsm);
+    const size_t img_bytes = kr_fw13_img_bytes(p_H, BITS == 8, p_gguf != 0, GS);
     KR_FSTAMP(4, 0); KR_FWG(4, 0); KR_FSTAMPY(7, 13, ylast);
     if (shared) kr_f_image_copy<BITS>(a.act_img, p_H, kr_fsm, L, t, 256);
     else if (wave > 0) {
@@ -868,7 +878,10 @@ __global__ void __launch_bounds__(256) kr_fw13_kernel(const float* p_logits, con
                 kr_load8(fa.act_f32, c, v);
 #pragma unroll
                 for (int i = 0; i < 8; i++) v[i] = kr_bf16_to_f32(kr_f32_to_bf16(v[i]));
-                gg_quant_store(v, c, GA);
+                if constexpr (GS) {
+                    float4* o = reinterpret_cast<float4*>(GA.f32v + c * 8);
+                    o[0] = make_float4(v[0], v[1], v[2], v[3]); o[1] = make_float4(v[4], v[5], v[6], v[7]);
+                } else gg_quant_store(v, c, GA);
             }
         } else kr_f_image_copy<BITS>(p_img_bf16, p_H, kr_fsm, L, t - 64, 192);
     } else {
@@ -902,7 +915,12 @@ __global__ void __launch_bounds__(256) kr_fw13_kernel(const float* p_logits, con
         const GgMat gm = gg_expert_mat(fa.ggate, e), um = gg_expert_mat(fa.gup, e);
         const int ntp = gm.N / 8, unit = blockIdx.x * TW + tw;
         float ag = 0.0f, au = 0.0f;
-        if (unit < ntp) {
+        if constexpr (GS) {
+            if (unit < ntp) {
+                if (gm.type == GG_Q6_K) { ag = gg_tile_q6k(gm, unit, GA, lane, ks, KS); au = gg_tile_q6k(um, unit, GA, lane, ks, KS); }
+                else { ag = gg_tile_q5_0(gm, unit, GA, lane, ks, KS); au = gg_tile_q5_0(um, unit, GA, lane, ks, KS); }
+            }
+        } else if (unit < ntp) {
             if (gm.type == GG_Q4_K) ag = gg_tile_q4k(gm, unit, GA, lane, ks, KS); else if (gm.type == GG_Q8_0) ag = gg_tile_q8_0(gm, unit, GA, lane, ks, KS); else ag = gg_tile_q4_0(gm, unit, GA, lane, ks, KS);
             if (um.type == GG_Q4_K) au = gg_tile_q4k(um, unit, GA, lane, ks, KS); else if (um.type == GG_Q8_0) au = gg_tile_q8_0(um, unit, GA, lane, ks, KS); else au = gg_tile_q4_0(um, unit, GA, lane, ks, KS);
         }
@@ -965,7 +983,8 @@ __global__ void __launch_bounds__(256) kr_fw13_kernel(const float* p_logits, con
 // decode.rs:3364-3374) into its own LDS region, walks the I / 128 groups and leaves 8 column values; 8 lanes then form
 // rsf * sum_i w_i y_i (routing order, moe.rs:661-667) + shared * sigmoid(gate) (decode.rs:3379-3402).
 // ---------------------------------------------------------------------------------------------------------------------------------
-template <int BITS, int NU, bool MULTI>
+// GS: the routed experts' down blocks are Q5_0 / Q6_K: a routed slot's wave leaves its expert hidden as f32 in its LDS region and runs gg_tile_q5_0 / gg_tile_q6k
+template <int BITS, int NU, bool MULTI, bool GS = false>
 __global__ void __launch_bounds__(1024) kr_fw2_kernel(const float* p_gu, const int32_t* p_ids, const float* p_wts, int p_gu_ld, int p_topk, int slot_lds, int pr_, int ps_, const KrFmoeArgs fa) {
     const KrMoeArgs& a = fa.m;
     const int pr = MULTI ? pr_ : 1, ps = MULTI ? ps_ : 1;      // MULTI = false: one wave per slot, the part arithmetic below folds away (the headline shapes: every cycle of this launch is on the token's path)
@@ -1015,14 +1034,25 @@ __global__ void __launch_bounds__(1024) kr_fw2_kernel(const float* p_gu, const i
     } else skip = fa.shared_skip != 0;
     if (gg) {
         // ---- native GGUF down projection: per-32 INT16 image of the hidden (f32::round, gguf_kernels.rs:143), the block kernel's row tile, result into the combine below
-        const GgAct GA = gg_carve(reinterpret_cast<char*>(kr_fsm) + (size_t)slot * slot_lds, inter);
+        GgAct GA = gg_carve(reinterpret_cast<char*>(kr_fsm) + (size_t)slot * slot_lds, inter);
+        if constexpr (GS) GA.f32v = reinterpret_cast<float*>(reinterpret_cast<char*>(kr_fsm) + (size_t)slot * slot_lds);
         const float* hg = a.gu + (size_t)slot * a.gu_ld;
         float accg = 0.0f;
         if (!skip && valid) {
-            for (int c = lane; c < inter / 8; c += 64) { float v[8]; kr_load8(hg, c, v); gg_quant_store(v, c, GA); }
-            kr_f_wave_sync();
             const GgMat dm = gg_expert_mat(fa.gdown, (int)ee);
-            accg = dm.type == GG_Q4_K ? gg_tile_q4k(dm, tile, GA, lane) : dm.type == GG_Q8_0 ? gg_tile_q8_0(dm, tile, GA, lane) : gg_tile_q4_0(dm, tile, GA, lane);
+            if constexpr (GS) {      // silu(gate) * up as the gate|up launch left it: the reference quantises nothing on this path
+                for (int c = lane; c < inter / 8; c += 64) {
+                    float v[8]; kr_load8(hg, c, v);
+                    float4* o = reinterpret_cast<float4*>(GA.f32v + c * 8);
+                    o[0] = make_float4(v[0], v[1], v[2], v[3]); o[1] = make_float4(v[4], v[5], v[6], v[7]);
+                }
+                kr_f_wave_sync();
+                accg = dm.type == GG_Q6_K ? gg_tile_q6k(dm, tile, GA, lane) : gg_tile_q5_0(dm, tile, GA, lane);
+            } else {
+                for (int c = lane; c < inter / 8; c += 64) { float v[8]; kr_load8(hg, c, v); gg_quant_store(v, c, GA); }
+                kr_f_wave_sync();
+                accg = dm.type == GG_Q4_K ? gg_tile_q4k(dm, tile, GA, lane) : dm.type == GG_Q8_0 ? gg_tile_q8_0(dm, tile, GA, lane) : gg_tile_q4_0(dm, tile, GA, lane);
+            }
         }
         if (l8 == 0) s_y[vslot][cl] = accg;                 // (GGUF routed slots: pr = 1, the launcher sees to it)
         if (lane == 0) s_wt[slot] = valid ? wt : 0.0f;
@@ -1512,9 +1542,15 @@ static bool kr_fmoe_ok(const KrFmoeArgs& fa) {
     const KrMoeArgs& a = fa.m;
     const bool has_shared = a.n_slots > a.topk;
     if (a.B != 1 || a.n_slots > 16 || a.topk > 15 || a.E > 512 || a.act_mode != KR_ACT_SILU_FUSED) return false;
-    if (fa.gguf) {      // routed experts on native GGUF blocks: the integer block kernels only, a transposed shared expert (if any) of one bit width
-        auto ok_mat = [&](const GgMat& g, int K, int N) { return (g.type == GG_Q4_K ? K % 256 == 0 : ((g.type == GG_Q8_0 || g.type == GG_Q4_0) && K % 32 == 0)) && g.K == K && g.N == N && N % 8 == 0; };
+    if (fa.gguf) {      // routed experts on native GGUF blocks: the integer block kernels, the f32 tiles of Q5_0 / Q6_K ("gguf_scalar_tiles"), a transposed shared expert (if any) of one bit width
+        auto ok_type = [&](int t, int K) {
+            if (t == GG_Q4_K) return K % 256 == 0;
+            if (t == GG_Q8_0 || t == GG_Q4_0) return K % 32 == 0;
+            return fa.gguf_scalar_tiles != 0 && (t == GG_Q6_K ? K % 256 == 0 : (t == GG_Q5_0 && K % 32 == 0));
+        };
+        auto ok_mat = [&](const GgMat& g, int K, int N) { return ok_type(g.type, K) && g.K == K && g.N == N && N % 8 == 0; };
         if (!fa.act_f32 || !ok_mat(fa.ggate, a.H, a.I) || !ok_mat(fa.gup, a.H, a.I) || !ok_mat(fa.gdown, a.I, a.H) || a.H % 128) return false;
+        if (gg_scalar_type(fa.ggate.type) != gg_scalar_type(fa.gup.type)) return false;      // gate and up of one kind: one activation form per gate|up workgroup
         if (has_shared) {
             if (!a.act_img || a.sw13.bits != a.sw2.bits || a.I_shared % 128 || a.sw13.ng * 128 != a.H || a.sw2.ng * 128 != a.I_shared) return false;
             if (a.sgate.q && (a.sgate.bits != a.sw13.bits || a.sgate.ng != a.sw13.ng || !a.gate_out)) return false;
@@ -1536,13 +1572,19 @@ static size_t kr_fw2_slot_lds(const KrFmoeArgs& fa) {
     const bool has_shared = a.n_slots > a.topk;
     const int imax = has_shared && a.I_shared > a.I ? a.I_shared : a.I;
     size_t n = fa.gguf ? (has_shared ? kr_lds_bytes(a.I_shared, a.sw2.bits == 8) : 0) : kr_lds_bytes(imax, a.w2.bits == 8);
-    if (fa.gguf) { const size_t g = (gg_lds_bytes(a.I, false) + 15) & ~(size_t)15; if (g > n) n = g; }
+    if (fa.gguf) { const size_t g = gg_scalar_type(fa.gdown.type) ? ((size_t)a.I * 4 + 15) & ~(size_t)15 : (gg_lds_bytes(a.I, false) + 15) & ~(size_t)15; if (g > n) n = g; }
     return n;
+}
+static size_t kr_fw13_lds(const KrFmoeArgs& fa) {
+    const KrMoeArgs& a = fa.m;
+    const int wbits = fa.gguf && a.n_slots <= a.topk ? 4 : (fa.gguf ? a.sw13 : a.w13).bits;      // (as kr_launch_fw13 picks the template)
+    return kr_fw13_img_bytes(a.H, wbits == 8, fa.gguf != 0, fa.gguf && gg_scalar_type(fa.ggate.type)) + (size_t)(2 * a.E + 33 + 33 + 32 + 32 + 4 + 136) * 4;
 }
 int kr_fmoe_check(const KrFmoeArgs& fa) {
     if (!kr_fmoe_ok(fa)) return 1;
     const KrMoeArgs& a = fa.m;
     // kr_fw2_kernel takes slot_lds * n_slots of dynamic LDS and no opt-in is made for it: past the 64 KiB every kernel may use the layer falls back to the exact MoE kernels
+    if (fa.gguf && gg_scalar_type(fa.ggate.type) && kr_fw13_lds(fa) > KR_FW2_LDS_MAX) return 1;      // the gate|up launch with the f32 vector of a Q5_0 / Q6_K gate
     return kr_fw2_slot_lds(fa) * a.n_slots > KR_FW2_LDS_MAX ? 1 : 0;
 }
 
@@ -1560,15 +1602,17 @@ int kr_launch_fw13(const KrFmoeArgs& fa, hipStream_t st) {
     dim3 grid((ntp + 1) / 2, a.n_slots + (per_slot ? 1 : 0));
     const KrMatDev& wm = fa.gguf ? a.sw13 : a.w13;      // GGUF routed experts: the template follows the (transposed) shared expert; INT4 form when there is none
     const int wbits = fa.gguf && !has_shared ? 4 : wm.bits;
-    size_t img = kr_lds_bytes(a.H, wbits == 8);
-    if (fa.gguf && gg_lds_bytes(a.H, false) > img) img = gg_lds_bytes(a.H, false);
-    const size_t lds = img + (size_t)(2 * a.E + 33 + 33 + 32 + 32 + 4 + 136) * 4;
+    const bool gs = fa.gguf && gg_scalar_type(fa.ggate.type);
+    const size_t lds = kr_fw13_lds(fa);
     const int units = fa.gguf && !has_shared ? 0 : (wbits == 4 ? wm.ngp : wm.ng);
     const bool even = !fa.gguf && (a.w13.bits == 8 || (a.w13.ng % 2) == 0) && units % 2 == 0;
     const int nu = even ? units / 2 : 0;
 #define KR_FW13(B_, N_) hipLaunchKernelGGL((kr_fw13_kernel<B_, N_>), grid, dim3(256), lds, st, fa.logits, fa.esc, a.act_img_bf16, a.E, a.topk, fa.scoring, fa.norm_topk, a.H, a.I, fa.gguf, pub, fa)
-    if (wbits == 4) { if (nu == 4) KR_FW13(4, 4); else if (nu == 8) KR_FW13(4, 8); else KR_FW13(4, 0); }
+#define KR_FW13_GS(B_) hipLaunchKernelGGL((kr_fw13_kernel<B_, 0, true>), grid, dim3(256), lds, st, fa.logits, fa.esc, a.act_img_bf16, a.E, a.topk, fa.scoring, fa.norm_topk, a.H, a.I, fa.gguf, pub, fa)
+    if (gs) { if (wbits == 4) KR_FW13_GS(4); else KR_FW13_GS(8); }
+    else if (wbits == 4) { if (nu == 4) KR_FW13(4, 4); else if (nu == 8) KR_FW13(4, 8); else KR_FW13(4, 0); }
     else { if (nu == 8) KR_FW13(8, 8); else KR_FW13(8, 0); }
+#undef KR_FW13_GS
 #undef KR_FW13
     return 0;
 }
@@ -1597,9 +1641,12 @@ int kr_launch_fw2(const KrFmoeArgs& fa, hipStream_t st) {
     }
     const bool multi = pr > 1 || ps > 1;
 #define KR_FW2(B_, N_, M_) hipLaunchKernelGGL((kr_fw2_kernel<B_, N_, M_>), grid, dim3(64 * (a.topk * pr + ps)), slot_lds * a.n_slots, st, a.gu, a.ids, a.wts, a.gu_ld, a.topk, (int)slot_lds, pr, ps, fa)
-    if (multi) { if (wbits == 4) KR_FW2(4, 0, true); else KR_FW2(8, 0, true); }      // (several waves per slot only with the guarded form)
+#define KR_FW2_GS(B_, M_) hipLaunchKernelGGL((kr_fw2_kernel<B_, 0, M_, true>), grid, dim3(64 * (a.topk * pr + ps)), slot_lds * a.n_slots, st, a.gu, a.ids, a.wts, a.gu_ld, a.topk, (int)slot_lds, pr, ps, fa)
+    if (fa.gguf && gg_scalar_type(fa.gdown.type)) { if (wbits == 4) { if (multi) KR_FW2_GS(4, true); else KR_FW2_GS(4, false); } else { if (multi) KR_FW2_GS(8, true); else KR_FW2_GS(8, false); } }
+    else if (multi) { if (wbits == 4) KR_FW2(4, 0, true); else KR_FW2(8, 0, true); }      // (several waves per slot only with the guarded form)
     else if (wbits == 4) { if (nu == 2) KR_FW2(4, 2, false); else if (nu == 4) KR_FW2(4, 4, false); else if (nu == 6) KR_FW2(4, 6, false); else if (nu == 8) KR_FW2(4, 8, false); else KR_FW2(4, 0, false); }
     else { if (nu == 4) KR_FW2(8, 4, false); else if (nu == 8) KR_FW2(8, 8, false); else KR_FW2(8, 0, false); }
+#undef KR_FW2_GS
 #undef KR_FW2
     return 0;
 }

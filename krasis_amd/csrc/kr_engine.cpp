@@ -361,7 +361,6 @@ static int ggml_block_elems(int t) { return (t == GG_Q4_K || t == GG_Q6_K) ? 256
 static void retile_gguf(int type, const uint8_t* src, int K, int N, uint8_t* dq, uint8_t* dh) {
     const int nt = (N + 7) / 8; const size_t bb = ggml_block_bytes(type); const int nb = K / ggml_block_elems(type);
     const size_t row_bytes = (size_t)nb * bb;
-    if (type == GG_Q5_0 || type == GG_Q6_K) { memcpy(dq, src, (size_t)N * row_bytes); return; }
     memset(dq, 0, gg_q_bytes(type, K, N)); memset(dh, 0, gg_h_bytes(type, K, N));
     for (int t = 0; t < nt; t++) for (int r = 0; r < 8; r++) {
         const int row = t * 8 + r; if (row >= N) continue;
@@ -383,6 +382,27 @@ static void retile_gguf(int type, const uint8_t* src, int K, int N, uint8_t* dq,
                 for (int l = 0; l < 8; l++) {
                     uint8_t* o = dq + (((size_t)t * nbg + bg) * 64 + r * 8 + l) * 16 + u * 4;
                     o[0] = qs[2 * l]; o[1] = qs[2 * l + 1]; o[2] = qs[16 + 2 * l]; o[3] = qs[17 + 2 * l];
+                }
+            }
+        } else if (type == GG_Q5_0) {      // block = {f16 d, u32 qh, qs[16]}: the records of Q4_0, the header carries the eight d, then the eight qh
+            const int nbg = (nb + 7) / 8;
+            for (int b = 0; b < nb; b++) {
+                const uint8_t* blk = rp + (size_t)b * 22; const uint8_t* qs = blk + 6; const int bg = b / 8, u = b % 8;
+                uint8_t* hd = dh + (((size_t)t * nbg + bg) * 8 + r) * 48;
+                memcpy(hd + u * 2, blk, 2); memcpy(hd + 16 + u * 4, blk + 2, 4);
+                for (int l = 0; l < 8; l++) {
+                    uint8_t* o = dq + (((size_t)t * nbg + bg) * 64 + r * 8 + l) * 16 + u * 2;
+                    o[0] = qs[2 * l]; o[1] = qs[2 * l + 1];
+                }
+            }
+        } else if (type == GG_Q6_K) {      // block = {ql[128], qh[64], scales[16], f16 d}: per half and lane l the 12 bytes ql[4l..], ql[32 + 4l..], qh[4l..] of that half
+            for (int b = 0; b < nb; b++) {
+                const uint8_t* blk = rp + (size_t)b * 210;
+                uint8_t* hd = dh + (((size_t)t * nb + b) * 8 + r) * 20;
+                memcpy(hd, blk + 192, 16); memcpy(hd + 16, blk + 208, 2);
+                for (int hf = 0; hf < 2; hf++) for (int l = 0; l < 8; l++) {
+                    uint8_t* o = dq + ((((size_t)t * nb + b) * 2 + hf) * 64 + r * 8 + l) * 12;
+                    memcpy(o, blk + hf * 64 + 4 * l, 4); memcpy(o + 4, blk + hf * 64 + 32 + 4 * l, 4); memcpy(o + 8, blk + 128 + hf * 32 + 4 * l, 4);
                 }
             }
         } else {  // Q4_0
@@ -451,11 +471,11 @@ extern "C" int kr_upload_expert_gguf(kr_engine* e, int layer, int expert, int in
     return KR_OK;
 }
 
-// synthetic native-GGUF experts for a whole layer (Q4_K or Q8_0 blocks, both projections), generated on the GPU -- the GGUF twin of
+// synthetic native-GGUF experts for a whole layer (Q4_K, Q8_0, Q5_0 or Q6_K blocks per projection), generated on the GPU -- the GGUF twin of
 // kr_fill_layer_synthetic with the block distribution SURVEY 8d defines
 extern "C" int kr_fill_layer_synthetic_gguf(kr_engine* e, int layer, int gate_up_type, int down_type, uint64_t seed) {
     if (int rc = check_layer(e, layer)) return rc;
-    for (int t : {gate_up_type, down_type}) if (t != GG_Q4_K && t != GG_Q8_0) return kr_fail(KR_ERR_VALUE, "synthetic GGUF fill supports Q4_K (12) and Q8_0 (8), got %d", t);
+    for (int t : {gate_up_type, down_type}) if (t != GG_Q4_K && t != GG_Q8_0 && t != GG_Q5_0 && t != GG_Q6_K) return kr_fail(KR_ERR_VALUE, "synthetic GGUF fill supports Q4_K (12), Q8_0 (8), Q5_0 (6) and Q6_K (14), got %d", t);
     KR_HIP(hipSetDevice(e->device));
     Layer& L = e->layers[layer];
     const int H = e->cfg.hidden_size, I = e->cfg.moe_intermediate_size, E = e->cfg.n_routed_experts;
@@ -470,6 +490,32 @@ extern "C" int kr_fill_layer_synthetic_gguf(kr_engine* e, int layer, int gate_up
     }
     KR_HIP(hipStreamSynchronize(e->stream));
     L.gguf = true; L.inter = I; std::fill(L.present.begin(), L.present.end(), 1);
+    return KR_OK;
+}
+
+// The Q5_0 / Q6_K kernels as a stand-alone operator a test can hold (the precedent: kr_decode_matmul_rows): raw row-major blocks and an f32 vector on the host,
+// re-tiled into a scratch matrix, ONE launch of the device functions the MoE kernels call, y copied back.  Nothing stays on the engine.
+extern "C" int kr_gguf_matvec(kr_engine* e, int type, const uint8_t* blocks, int N, int K, const float* x, float* y, int parts) {
+    if (!e) return kr_fail(KR_ERR_VALUE, "null engine");
+    if (!blocks || !x || !y) return kr_fail(KR_ERR_VALUE, "null pointer argument");
+    if (type != GG_Q5_0 && type != GG_Q6_K) return kr_fail(KR_ERR_VALUE, "kr_gguf_matvec: type %d is neither Q5_0 (6) nor Q6_K (14)", type);
+    if (parts < 0 || parts > 2) return kr_fail(KR_ERR_VALUE, "kr_gguf_matvec: parts %d (0 = exact chain, 1 | 2 = tolerance tile)", parts);
+    if (N < 1 || K < 1 || K % ggml_block_elems(type) || K > 15360) return kr_fail(KR_ERR_VALUE, "kr_gguf_matvec: shape N %d, K %d (K: a multiple of %d, at most 15360)", N, K, ggml_block_elems(type));
+    std::lock_guard<std::mutex> lk(e->mu);
+    KR_HIP(hipSetDevice(e->device));
+    GgMat m{}; m.type = type; m.K = K; m.N = N; m.q_stride = gg_q_bytes(type, K, N); m.h_stride = gg_h_bytes(type, K, N);
+    std::vector<uint8_t> dq(m.q_stride), dh(m.h_stride);
+    retile_gguf(type, blocks, K, N, dq.data(), dh.data());
+    DevBuf q, h, xd, yd;
+    if (q.ensure(m.q_stride) || h.ensure(m.h_stride) || xd.ensure((size_t)K * 4) || yd.ensure((size_t)N * 4)) return kr_fail(KR_ERR_HIP, "hipMalloc of the scratch matrix failed");
+    KR_HIP(hipMemcpy(q.p, dq.data(), m.q_stride, hipMemcpyHostToDevice));
+    KR_HIP(hipMemcpy(h.p, dh.data(), m.h_stride, hipMemcpyHostToDevice));
+    KR_HIP(hipMemcpy(xd.p, x, (size_t)K * 4, hipMemcpyHostToDevice));
+    m.q = q.p; m.h = h.p;
+    if (kr_launch_gguf_matvec(m, (const float*)xd.p, (float*)yd.p, parts, e->stream)) return kr_fail(KR_ERR_VALUE, "kr_gguf_matvec: launch refused (type %d, N %d, K %d, parts %d)", type, N, K, parts);
+    KR_HIP(hipGetLastError());
+    KR_HIP(hipStreamSynchronize(e->stream));
+    KR_HIP(hipMemcpy(y, yd.p, (size_t)N * 4, hipMemcpyDeviceToHost));
     return KR_OK;
 }
 

@@ -19,6 +19,8 @@ struct GgMoeArgs {
 void kr_launch_gguf_moe(const GgMoeArgs& a, hipStream_t st);
 size_t gg_q_bytes(int type, int K, int N);
 size_t gg_h_bytes(int type, int K, int N);
+// one Q5_0 / Q6_K matrix against an f32 vector (kr_gguf_matvec): parts 0 = the exact row chain, 1 | 2 = the tolerance tile over the whole row / two slices; non-zero: refused
+int kr_launch_gguf_matvec(const GgMat& m, const float* x, float* y, int parts, hipStream_t st);
 
 // ---- prompt pass: GGUF blocks on the int8-MFMA grouped GEMM (kr_gguf_prefill.hip) ----
 struct KrPfSort;

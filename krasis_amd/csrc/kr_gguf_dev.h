@@ -218,7 +218,112 @@ __device__ __forceinline__ float gg_tile_q4_0(const GgMat& m, int tile, const Gg
     return kr_hsum8(acc) - corr;
 }
 
-__device__ __forceinline__ bool gg_int_path(int t) { return t == GG_Q4_K || t == GG_Q8_0 || t == GG_Q4_0; }
+// ---- Q5_0 / Q6_K: the reference has no integer form for them (scalar f32 rows, gguf_kernels.rs:572-635: nothing is quantised on this path), so the tiles below
+//      form the reference's TERMS from the f32 activation vector A.f32v (16-byte aligned) and give up its serial row chain: lane l of a row owns the slice the
+//      layout hands it (kr_gguf.hip header), keeps its terms in two f32 chains in block order (one packed accumulator: elements of even and of odd index),
+//      then kr_hsum8.  Tolerance form only (KR_DECODE_FAST, kr_gguf_matvec parts 1 | 2); the exact chain is gg_row_scalar (kr_gguf.hip).  Records and
+//      headers are requested in batches, as in gg_tile_q4k; [part, parts) slices the block groups (Q5_0) / super-blocks (Q6_K). ----
+typedef float gg_f32x2 __attribute__((ext_vector_type(2)));
+#define GG_PF5 2      // Q5_0: block groups (8 blocks each) requested ahead -- per lane 4 record + 12 header words a group
+#define GG_PF6 4      // Q6_K: super-blocks requested ahead -- per lane 6 record + 5 header words a block (the down launch of the mode has 128 registers a lane)
+
+// Q5_0 term d * (q - 16) * x (gguf_kernels.rs:585-592) on elements {2l, 2l+1} and {16+2l, 17+2l} of every block
+__device__ __forceinline__ float gg_tile_q5_0(const GgMat& m, int tile, const GgAct& A, int lane, int part = 0, int parts = 1) {
+    const int l = lane & 7, row = lane >> 3;
+    const int nb = m.K / 32, nbg = (nb + 7) / 8, per = (nbg + parts - 1) / parts, g_lo = part * per, g_hi = g_lo + per < nbg ? g_lo + per : nbg;
+    const u32x4* q = reinterpret_cast<const u32x4*>(m.q) + (size_t)tile * nbg * 64 + lane;
+    const u32x4* h = reinterpret_cast<const u32x4*>(m.h) + ((size_t)tile * nbg * 8 + row) * 3;
+    gg_f32x2 acc = {0.0f, 0.0f};
+    for (int g0 = g_lo; g0 < g_hi; g0 += GG_PF5) {
+        u32x4 wv[GG_PF5], hv[GG_PF5][3];
+#pragma unroll
+        for (int v = 0; v < GG_PF5; v++) {
+            const int gg = g0 + v < g_hi ? g0 + v : (g_hi > 0 ? g_hi - 1 : 0);
+            wv[v] = kr_ldg_nt(q + (size_t)gg * 64);
+#pragma unroll
+            for (int i = 0; i < 3; i++) hv[v][i] = kr_ldg_nt(h + (size_t)gg * 24 + i);
+        }
+#pragma unroll
+        for (int v = 0; v < GG_PF5; v++) {
+            const int bg = g0 + v;
+            if (bg < g_hi) {
+                const uint32_t wb[4] = {wv[v].x, wv[v].y, wv[v].z, wv[v].w}, db[4] = {hv[v][0].x, hv[v][0].y, hv[v][0].z, hv[v][0].w};
+                const uint32_t hb[8] = {hv[v][1].x, hv[v][1].y, hv[v][1].z, hv[v][1].w, hv[v][2].x, hv[v][2].y, hv[v][2].z, hv[v][2].w};
+#pragma unroll
+                for (int u = 0; u < 8; u++) {
+                    const int s = bg * 8 + u;
+                    if (s < nb) {
+                        const uint32_t two = (wb[u >> 1] >> ((u & 1) * 16)) & 0xFFFFu;      // bytes qs[2l], qs[2l+1]
+                        const uint32_t hq = hb[u] >> (2 * l);                                  // bits 0, 1, 16, 17: the fifth bits of elements 2l, 2l+1, 16+2l, 17+2l
+                        const float d = gg_f16((db[u >> 1] >> ((u & 1) * 16)) & 0xFFFFu);
+                        const gg_f32x2 dd = {d, d};
+                        const gg_f32x2 q_lo = {(float)(int)((two & 0xFu) | ((hq & 1u) << 4)) - 16.0f, (float)(int)(((two >> 8) & 0xFu) | ((hq & 2u) << 3)) - 16.0f};
+                        const gg_f32x2 q_hi = {(float)(int)(((two >> 4) & 0xFu) | (((hq >> 16) & 1u) << 4)) - 16.0f, (float)(int)(((two >> 12) & 0xFu) | (((hq >> 17) & 1u) << 4)) - 16.0f};
+                        const gg_f32x2 x_lo = *reinterpret_cast<const gg_f32x2*>(A.f32v + s * 32 + 2 * l), x_hi = *reinterpret_cast<const gg_f32x2*>(A.f32v + s * 32 + 16 + 2 * l);
+                        acc += (dd * q_lo) * x_lo;
+                        acc += (dd * q_hi) * x_hi;
+                    }
+                }
+            }
+        }
+    }
+    return kr_hsum8(acc.x + acc.y);
+}
+
+// four consecutive elements of one 32-wide run of a Q6_K half: 6-bit codes in the bytes of `codes`, one scale product s = d * sc (gguf_kernels.rs:612-630)
+__device__ __forceinline__ void gg_q6k_four(gg_f32x2& acc, float s, uint32_t codes, const float* x) {
+    const float4 xv = *reinterpret_cast<const float4*>(x);
+    const gg_f32x2 ss = {s, s};
+    const gg_f32x2 q01 = {(float)(codes & 0xFFu) - 32.0f, (float)((codes >> 8) & 0xFFu) - 32.0f}, q23 = {(float)((codes >> 16) & 0xFFu) - 32.0f, (float)(codes >> 24) - 32.0f};
+    const gg_f32x2 x01 = {xv.x, xv.y}, x23 = {xv.z, xv.w};
+    acc += (ss * q01) * x01;
+    acc += (ss * q23) * x23;
+}
+
+// Q6_K term (d * sc) * (q - 32) * x: lane l owns, per half, l' in [4l, 4l + 4) of the reference's inner loop -- 16 elements, scale index is = l / 4 throughout.
+// The 6-bit unpack runs on whole words: four codes at a time from one ql word and one qh word.
+__device__ __forceinline__ float gg_tile_q6k(const GgMat& m, int tile, const GgAct& A, int lane, int part = 0, int parts = 1) {
+    const int l = lane & 7, row = lane >> 3;
+    const int nb = m.K / 256, per = (nb + parts - 1) / parts, b_lo = part * per, b_hi = b_lo + per < nb ? b_lo + per : nb;
+    const uint32_t* q = reinterpret_cast<const uint32_t*>(m.q) + ((size_t)tile * nb * 128 + lane) * 3;      // [block][half][8 rows][8 lanes] x 12 B
+    const uint32_t* h = reinterpret_cast<const uint32_t*>(m.h) + ((size_t)tile * nb * 8 + row) * 5;          // [block][8 rows] x 20 B
+    const int sh = (l >> 2) * 8;
+    gg_f32x2 acc = {0.0f, 0.0f};
+    for (int b0 = b_lo; b0 < b_hi; b0 += GG_PF6) {
+        uint32_t wv[GG_PF6][2][3], hv[GG_PF6][5];
+#pragma unroll
+        for (int u = 0; u < GG_PF6; u++) {
+            const int bb = b0 + u < b_hi ? b0 + u : (b_hi > 0 ? b_hi - 1 : 0);
+#pragma unroll
+            for (int i = 0; i < 6; i++) wv[u][i / 3][i % 3] = kr_ldg_nt(q + ((size_t)bb * 128 + (i / 3) * 64) * 3 + i % 3);
+#pragma unroll
+            for (int i = 0; i < 5; i++) hv[u][i] = kr_ldg_nt(h + (size_t)bb * 40 + i);
+        }
+#pragma unroll
+        for (int u = 0; u < GG_PF6; u++) {
+            const int b = b0 + u;
+            if (b < b_hi) {
+                const float d = gg_f16(hv[u][4] & 0xFFFFu);
+#pragma unroll
+                for (int hf = 0; hf < 2; hf++) {
+                    const uint32_t s01 = hv[u][2 * hf] >> sh, s23 = hv[u][2 * hf + 1] >> sh;      // scale bytes is + {0, 2} and is + {4, 6} of this half
+                    const float s0 = d * (float)(int8_t)(s01 & 0xFFu), s1 = d * (float)(int8_t)((s01 >> 16) & 0xFFu);
+                    const float s2 = d * (float)(int8_t)(s23 & 0xFFu), s3 = d * (float)(int8_t)((s23 >> 16) & 0xFFu);
+                    const uint32_t a = wv[u][hf][0], bq = wv[u][hf][1], c = wv[u][hf][2];         // ql[4l..], ql[32 + 4l..], qh[4l..] of the half
+                    const float* in = A.f32v + b * 256 + hf * 128 + 4 * l;
+                    gg_q6k_four(acc, s0, (a & 0x0F0F0F0Fu) | ((c & 0x03030303u) << 4), in);
+                    gg_q6k_four(acc, s1, (bq & 0x0F0F0F0Fu) | ((c & 0x0C0C0C0Cu) << 2), in + 32);
+                    gg_q6k_four(acc, s2, ((a >> 4) & 0x0F0F0F0Fu) | (c & 0x30303030u), in + 64);
+                    gg_q6k_four(acc, s3, ((bq >> 4) & 0x0F0F0F0Fu) | ((c >> 2) & 0x30303030u), in + 96);
+                }
+            }
+        }
+    }
+    return kr_hsum8(acc.x + acc.y);
+}
+
+__host__ __device__ static inline bool gg_int_path(int t) { return t == GG_Q4_K || t == GG_Q8_0 || t == GG_Q4_0; }
+__host__ __device__ static inline bool gg_scalar_type(int t) { return t == GG_Q5_0 || t == GG_Q6_K; }
 
 __device__ __forceinline__ GgMat gg_expert_mat(const GgMat& base, int e) {
     GgMat m = base;

@@ -344,7 +344,8 @@ __global__ void __launch_bounds__(256, 2) kr_gpf_gemm_kernel(const GpfGemmArgs a
 
 // ------------------------------------------------------------------------------------------
 // synthetic GGUF experts (SURVEY 8d defines the distribution the reference's generator lacks): quant bytes and the 12 packed scale bytes
-// are raw hash words, d = f16((0.005 + u * 0.045) / 63), dmin = f16(8 d); Q8_0: d = f16((0.005 + u * 0.045) / 127)
+// are raw hash words, d = f16((0.005 + u * 0.045) / 63), dmin = f16(8 d); Q8_0: d = f16((0.005 + u * 0.045) / 127); Q5_0: d = f16((0.005 + u * 0.045) / 15), raw qh words;
+// Q6_K: d = f16((0.005 + u * 0.045) / 31 / 127), raw scale bytes
 // ------------------------------------------------------------------------------------------
 __device__ __forceinline__ uint64_t gpf_mix(uint64_t x) {
     x += 0x9E3779B97F4A7C15ull; x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull; x = (x ^ (x >> 27)) * 0x94D049BB133111EBull; return x ^ (x >> 31);
@@ -361,6 +362,21 @@ __global__ void kr_gpf_fill_h_kernel(char* h, size_t n_rec, int type, uint64_t s
             const uint32_t db = __half_as_ushort(__float2half(d)), mb = __half_as_ushort(__float2half(d * 8.0f));
             u32x4 o = {db | (mb << 16), (uint32_t)(r0 >> 32), (uint32_t)r1, (uint32_t)(r1 >> 32)};
             *reinterpret_cast<u32x4*>(h + i * 16) = o;
+        } else if (type == GG_Q5_0) {   // 8 x f16 d = f16((0.005 + u * 0.045) / 15), then 8 x u32 qh (raw words)
+            uint32_t w[12];
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const uint64_t r = gpf_mix((seed ^ (0xD5ull << 56)) + i * 8 + k);
+                w[k] = (uint32_t)__half_as_ushort(__float2half(dval((uint32_t)r, 15.0f))) | ((uint32_t)__half_as_ushort(__float2half(dval((uint32_t)(r >> 32), 15.0f))) << 16);
+                const uint64_t r2 = gpf_mix((seed ^ (0xD5ull << 56)) + i * 8 + 4 + k);
+                w[4 + 2 * k] = (uint32_t)r2; w[5 + 2 * k] = (uint32_t)(r2 >> 32);
+            }
+#pragma unroll
+            for (int k = 0; k < 3; k++) { u32x4 o = {w[4 * k], w[4 * k + 1], w[4 * k + 2], w[4 * k + 3]}; *reinterpret_cast<u32x4*>(h + i * 48 + k * 16) = o; }
+        } else if (type == GG_Q6_K) {   // 16 scale bytes (raw words), d = f16((0.005 + u * 0.045) / 31 / 127), 2 bytes of padding
+            uint32_t* o = reinterpret_cast<uint32_t*>(h + i * 20);
+            o[0] = (uint32_t)r0; o[1] = (uint32_t)(r0 >> 32); o[2] = (uint32_t)r1; o[3] = (uint32_t)(r1 >> 32);
+            o[4] = (uint32_t)__half_as_ushort(__float2half(dval((uint32_t)r2, 31.0f) / 127.0f));
         } else {   // Q8_0: 4 x f16 d
             const uint32_t a = __half_as_ushort(__float2half(dval((uint32_t)r0, 127.0f))), b = __half_as_ushort(__float2half(dval((uint32_t)(r0 >> 32), 127.0f)));
             const uint32_t c = __half_as_ushort(__float2half(dval((uint32_t)r2, 127.0f))), d2 = __half_as_ushort(__float2half(dval((uint32_t)(r2 >> 32), 127.0f)));
@@ -371,7 +387,7 @@ __global__ void kr_gpf_fill_h_kernel(char* h, size_t n_rec, int type, uint64_t s
 }
 void kr_launch_gpf_fill_synth(void* q, size_t q_bytes, void* h, size_t h_bytes, int type, uint64_t seed, hipStream_t st) {
     hipLaunchKernelGGL(kr_gpf_fill_q_kernel, dim3(2048), dim3(256), 0, st, (uint32_t*)q, q_bytes / 4, seed);
-    hipLaunchKernelGGL(kr_gpf_fill_h_kernel, dim3(512), dim3(256), 0, st, (char*)h, h_bytes / (type == GG_Q4_K ? 16 : 8), type, seed ^ 0x5DEECE66Dull);
+    hipLaunchKernelGGL(kr_gpf_fill_h_kernel, dim3(512), dim3(256), 0, st, (char*)h, h_bytes / (type == GG_Q4_K ? 16 : type == GG_Q5_0 ? 48 : type == GG_Q6_K ? 20 : 8), type, seed ^ 0x5DEECE66Dull);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -405,6 +405,10 @@ class CpuDecodeStore:
         slot and speculation calls accept a store with such layers; slower than the default int8-MFMA form on long prompts; refused together with
         gemm_fast; nothing changes for other weight forms (docs/design/20-gguf-exact-pass.md).  "gguf_exact_grouped" (default 1): 0 makes that pass
         take the streaming block kernels for every type (A/B and test hook, same bits).
+        "gguf_scalar_tiles" (default 1): decode steps under decode_fast on native-GGUF MoE layers with a Q5_0 or Q6_K matrix -- with 1 the routed
+        slots of the mode's gate|up and down launches walk such a matrix with the f32 tiles (the reference's terms from the f32 activation vector, 8
+        lanes per row, tree-ordered sums); with 0 such a layer leaves the mode's three MoE launches for the exact block kernels and a combine launch
+        (A/B and test hook; refuses nothing; docs/design/41-gguf-scalar-tiles.md).
         "pass_few_rows" (default 0): with 1 a multi-row pass of at most "pass_few_rows_max" token rows (prefill / prefill_nll / verify: the number of
         tokens; the slot calls: the sum of their counts) runs every projection on a few-row form of the decode step's streaming matvec and the INT4 /
         INT8 routed experts as the step's three launches.  Every call gives, bit for bit, what it gives with the option off; passes under gemm_fast,
