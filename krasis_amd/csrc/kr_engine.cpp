@@ -900,7 +900,7 @@ static int gg_ensure_ws(kr_engine* e, GgufSet& g, hipStream_t st) {
     return KR_OK;
 }
 
-// KR_GEMM_FAST / kr_moe_set_gemm_mode(1) on a native Q4_K layer: the tolerance GEMM's copy of (gate | up) and of down, built once
+// KR_GEMM_FAST / kr_moe_set_gemm_mode(1) on a native Q4_K / Q8_0 matrix: the tolerance GEMM's copy of (gate | up) and of down, built once
 static int gg_ensure_fast(kr_engine* e, GgufSet& a, GgufSet* b, hipStream_t st) {     // b: second matrix appended on N (up after gate), or null
     if (a.fq.p || !a.allocated()) return KR_OK;
     const int N = a.N + (b ? b->N : 0);
@@ -920,12 +920,30 @@ static int gg_ensure_fast(kr_engine* e, GgufSet& a, GgufSet* b, hipStream_t st) 
     e->weight_bytes += (a.fq_stride + 2 * a.fqs_stride) * a.count;
     return KR_OK;
 }
+// The KR_GEMM_FAST form of one projection: GG_FAST_COPY = the re-tiled copy above (Q4_K over whole super-blocks, Q8_0 over whole 128-k groups -- V2-Lite's down
+// projection: K = 1408 = 11 groups), GG_FAST_NATIVE = the lane records as they are (Q6_K, Q5_0: kr_gguf_prefill_h.hip, no copy), GG_FAST_NONE = neither.
+enum { GG_FAST_NONE = 0, GG_FAST_COPY = 1, GG_FAST_NATIVE = 2 };
+static int gg_fast_form(const GgufSet& g, int K) {
+    if (g.N % 8) return GG_FAST_NONE;
+    if ((g.type == GG_Q4_K && K % 256 == 0) || (g.type == GG_Q8_0 && K % 128 == 0)) return GG_FAST_COPY;
+    return kr_gfh_type_supported(g.type, K, g.N) ? GG_FAST_NATIVE : GG_FAST_NONE;
+}
 static bool gg_fast_ok(const Layer& L, int H, bool use_shared) {
-    // Q4_K over k ranges of whole super-blocks, Q8_0 over whole 128-k groups (V2-Lite's down projection: K = 1408 = 11 groups); gate and up of one type
-    auto q4 = [](const GgufSet& g, int K) { return ((g.type == GG_Q4_K && K % 256 == 0) || (g.type == GG_Q8_0 && K % 128 == 0)) && g.N % 8 == 0; };
-    bool ok = q4(L.g_gate, H) && q4(L.g_up, H) && L.g_gate.type == L.g_up.type && q4(L.g_down, L.inter) && L.inter % 32 == 0 && L.inter <= 2048;
-    if (use_shared) ok = ok && q4(L.gs_gate, H) && q4(L.gs_up, H) && L.gs_gate.type == L.gs_up.type && q4(L.gs_down, L.shared_inter) && L.shared_inter % 32 == 0 && L.shared_inter <= 2048;
+    // every projection has a form; gate and up of one type (one copy, or two launches of one kernel into the halves of gu)
+    auto has = [](const GgufSet& g, int K) { return gg_fast_form(g, K) != GG_FAST_NONE; };
+    bool ok = has(L.g_gate, H) && has(L.g_up, H) && L.g_gate.type == L.g_up.type && has(L.g_down, L.inter) && L.inter % 32 == 0 && L.inter <= 2048;
+    if (use_shared) ok = ok && has(L.gs_gate, H) && has(L.gs_up, H) && L.gs_gate.type == L.gs_up.type && has(L.gs_down, L.shared_inter) && L.shared_inter % 32 == 0 && L.shared_inter <= 2048;
     return ok;
+}
+// the copies of a layer gg_fast_ok accepted: copy-form matrices only
+static int gg_ensure_fast_layer(kr_engine* e, Layer& L, bool use_shared, hipStream_t st) {
+    const int H = e->cfg.hidden_size;
+    if (gg_fast_form(L.g_gate, H) == GG_FAST_COPY) if (int rc = gg_ensure_fast(e, L.g_gate, &L.g_up, st)) return rc;
+    if (gg_fast_form(L.g_down, L.inter) == GG_FAST_COPY) if (int rc = gg_ensure_fast(e, L.g_down, nullptr, st)) return rc;
+    if (!use_shared) return KR_OK;
+    if (gg_fast_form(L.gs_gate, H) == GG_FAST_COPY) if (int rc = gg_ensure_fast(e, L.gs_gate, &L.gs_up, st)) return rc;
+    if (gg_fast_form(L.gs_down, L.shared_inter) == GG_FAST_COPY) if (int rc = gg_ensure_fast(e, L.gs_down, nullptr, st)) return rc;
+    return KR_OK;
 }
 // Everything moe_prefill_gguf / moe_prefill_gguf_fast would build lazily for one layer, built NOW on `st`.  The whole-model prompt pass calls this for every
 // MoE layer on its main stream before the start event (kr_decode_prefill.cpp prefill_impl): with several chunks in flight on several streams, a lazy build
@@ -935,12 +953,7 @@ int kr_moe_prefill_prepare(kr_engine* e, int layer, int fast, int routed_only, h
     if (!L.gguf || gguf_exact) return KR_OK;      // KR_PF_SET_GGUF_EXACT: the exact forms read the blocks as they are, no sums and no copies
     std::lock_guard<std::mutex> lk(e->mu);
     const bool use_shared = L.gguf_shared && !routed_only;
-    if (fast && gg_fast_ok(L, e->cfg.hidden_size, use_shared)) {
-        if (int rc = gg_ensure_fast(e, L.g_gate, &L.g_up, st)) return rc;
-        if (int rc = gg_ensure_fast(e, L.g_down, nullptr, st)) return rc;
-        if (use_shared) { if (int rc = gg_ensure_fast(e, L.gs_gate, &L.gs_up, st)) return rc; if (int rc = gg_ensure_fast(e, L.gs_down, nullptr, st)) return rc; }
-        return KR_OK;
-    }
+    if (fast && gg_fast_ok(L, e->cfg.hidden_size, use_shared)) return gg_ensure_fast_layer(e, L, use_shared, st);
     bool mfma = kr_gpf_type_supported(L.g_gate.type, e->cfg.hidden_size) && kr_gpf_type_supported(L.g_down.type, L.inter);
     if (use_shared) mfma = mfma && kr_gpf_type_supported(L.gs_gate.type, e->cfg.hidden_size) && kr_gpf_type_supported(L.gs_down.type, L.shared_inter);
     if (!mfma) return KR_OK;
@@ -948,17 +961,18 @@ int kr_moe_prefill_prepare(kr_engine* e, int layer, int fast, int routed_only, h
     if (use_shared) for (GgufSet* g : {&L.gs_gate, &L.gs_up, &L.gs_down}) if (int rc = gg_ensure_ws(e, *g, st)) return rc;
     return KR_OK;
 }
-// the prompt pass of a native Q4_K layer in the tolerance form: f16 rows (+ their per-32 sums) x nibbles de-quantized in registers with the
-// sub-block scale folded in, offsets as extra k-columns, libm SiLU like expert_forward_gguf (gguf_kernels.rs:690-756).  Same sort / combine as the exact path.
+// the prompt pass of a native GGUF layer in the tolerance form: f16 rows (+ their per-32 sums) x codes de-quantized in registers with the (sub-)block
+// scale folded in (Q4_K: offsets as extra k-columns), libm SiLU like expert_forward_gguf (gguf_kernels.rs:690-756).  Same sort / combine as the exact path.
 static int moe_prefill_gguf_fast(kr_engine* e, Layer& L, const void* x_bf16, const int32_t* ids, const float* wts, void* out, int M, int topk,
                                  int out_dtype, int routed_only, int set, hipStream_t st) {
     kr_engine::PfSet& P = e->pf[set % KR_PF_MAX_DEPTH];
     const int H = e->cfg.hidden_size, I = L.inter, E = e->cfg.n_routed_experts;
     const bool use_shared = L.gguf_shared && !routed_only;
     const int SI = L.shared_inter;
-    if (int rc = gg_ensure_fast(e, L.g_gate, &L.g_up, st)) return rc;
-    if (int rc = gg_ensure_fast(e, L.g_down, nullptr, st)) return rc;
-    if (use_shared) { if (int rc = gg_ensure_fast(e, L.gs_gate, &L.gs_up, st)) return rc; if (int rc = gg_ensure_fast(e, L.gs_down, nullptr, st)) return rc; }
+    if (int rc = gg_ensure_fast_layer(e, L, use_shared, st)) return rc;
+    // per projection: the copy through the tolerance GEMM of kr_prefill_h.hip, or the native records through kr_launch_gfh_gemm (Q6_K, Q5_0)
+    const bool n13 = gg_fast_form(L.g_gate, H) == GG_FAST_NATIVE, n2 = gg_fast_form(L.g_down, I) == GG_FAST_NATIVE;
+    const bool sn13 = use_shared && gg_fast_form(L.gs_gate, H) == GG_FAST_NATIVE, sn2 = use_shared && gg_fast_form(L.gs_down, SI) == GG_FAST_NATIVE;
     const int pairs = e->pf_pairs > 0 ? e->pf_pairs : KR_PF_PAIRS;
     const int CHmax = pairs / topk > 64 ? pairs / topk : 64;
     const int CH = M < CHmax ? M : CHmax;
@@ -989,13 +1003,24 @@ static int moe_prefill_gguf_fast(kr_engine* e, Layer& L, const void* x_bf16, con
         run = run < 1 ? 1 : (run > 4 ? 4 : run);
         kr_launch_pf_sort(idc, mc, topk, E, so, st);
         kr_launch_pfh_rows_bf16(xc, mc, H, H, (uint16_t*)P.xf.p, (float*)P.xfm.p, st, (uint16_t*)P.xs.p);
+        if (n13) {      // gate and up into the two halves of gu, then the activation pass
+            kr_launch_gfh_gemm(L.g_gate.view(), (const uint16_t*)P.xf.p, (const float*)P.xfm.p, &so, topk, 1, tiles_bound, 0, P.gu.p, 2 * I, 0, 0, run, st);
+            kr_launch_gfh_gemm(L.g_up.view(), (const uint16_t*)P.xf.p, (const float*)P.xfm.p, &so, topk, 1, tiles_bound, 0, P.gu.p, 2 * I, I, 0, run, st);
+            kr_launch_pfh_act((const float*)P.gu.p, mc * topk, I, 2 * I, 3 /* libm SiLU */, 0.0f, 0.0f, (uint16_t*)P.hf.p, (float*)P.hfm.p, st, (uint16_t*)P.hs.p);
+        } else
         kr_launch_pfh_w13_act(w13, (const uint16_t*)P.xf.p, (const float*)P.xfm.p, &so, topk, 1, tiles_bound, 0, (float*)P.gu.p, mc * topk, 3 /* libm SiLU */, 0.0f, 0.0f,
                               (uint16_t*)P.hf.p, (float*)P.hfm.p, st, run, (const uint16_t*)P.xs.p, (uint16_t*)P.hs.p);
-        kr_launch_pfh_gemm(w2, (const uint16_t*)P.hf.p, (const float*)P.hfm.p, &so, topk, 0, tiles_bound, 0, (float*)P.eo.p, H, st, 0, 2 /* f16 rows */, run, (const uint16_t*)P.hs.p);
+        if (n2) kr_launch_gfh_gemm(L.g_down.view(), (const uint16_t*)P.hf.p, (const float*)P.hfm.p, &so, topk, 0, tiles_bound, 0, P.eo.p, H, 0, 1 /* f16 rows */, run, st);
+        else kr_launch_pfh_gemm(w2, (const uint16_t*)P.hf.p, (const float*)P.hfm.p, &so, topk, 0, tiles_bound, 0, (float*)P.eo.p, H, st, 0, 2 /* f16 rows */, run, (const uint16_t*)P.hs.p);
         if (use_shared) {
+            if (sn13) {
+                kr_launch_gfh_gemm(L.gs_gate.view(), (const uint16_t*)P.xf.p, (const float*)P.xfm.p, nullptr, topk, 0, 0, mc, P.sgu.p, 2 * SI, 0, 0, 1, st);
+                kr_launch_gfh_gemm(L.gs_up.view(), (const uint16_t*)P.xf.p, (const float*)P.xfm.p, nullptr, topk, 0, 0, mc, P.sgu.p, 2 * SI, SI, 0, 1, st);
+            } else
             kr_launch_pfh_gemm(L.gs_gate.fast_view(), (const uint16_t*)P.xf.p, (const float*)P.xfm.p, nullptr, topk, 0, 0, mc, (float*)P.sgu.p, 2 * SI, st, 0, 0, 1, (const uint16_t*)P.xs.p);
             kr_launch_pfh_act((const float*)P.sgu.p, mc, SI, 2 * SI, 3, 0.0f, 0.0f, (uint16_t*)P.shf.p, (float*)P.shfm.p, st, (uint16_t*)P.shs.p);
-            kr_launch_pfh_gemm(L.gs_down.fast_view(), (const uint16_t*)P.shf.p, (const float*)P.shfm.p, nullptr, topk, 0, 0, mc, (float*)P.seo.p, H, st, 0, 0, 1, (const uint16_t*)P.shs.p);
+            if (sn2) kr_launch_gfh_gemm(L.gs_down.view(), (const uint16_t*)P.shf.p, (const float*)P.shfm.p, nullptr, topk, 0, 0, mc, P.seo.p, H, 0, 0, 1, st);
+            else kr_launch_pfh_gemm(L.gs_down.fast_view(), (const uint16_t*)P.shf.p, (const float*)P.shfm.p, nullptr, topk, 0, 0, mc, (float*)P.seo.p, H, st, 0, 0, 1, (const uint16_t*)P.shs.p);
         }
         kr_launch_pf_combine_f16rows((const uint16_t*)P.eo.p, (const float*)P.hfm.p, so.pair_row, wc, mc, topk, H, use_shared ? (const float*)P.seo.p : nullptr, e->cfg.routed_scaling_factor,
                                      (char*)out + (size_t)m0 * H * ob, out_dtype == KR_OUT_BF16, st);

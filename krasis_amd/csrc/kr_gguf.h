@@ -36,6 +36,12 @@ void kr_launch_gpf_gemm(const GgMat& m, const void* ws, size_t ws_stride, const 
 void kr_launch_gq_repack(const GgMat& m, int n_experts, void* q_out, size_t q_stride, void* qs_out, void* qo_out, size_t qs_stride, int tile_off, int tiles_out, hipStream_t st);
 // Q8_0 -> the tolerance GEMM's INT8 operand form (INT8 lane tiles + one f16 scale per 32-wide block)
 void kr_launch_gq8_repack(const GgMat& m, int n_experts, void* q_out, size_t q_stride, void* qs_out, size_t qs_stride, int tile_off, hipStream_t st);
+// ---- KR_GEMM_FAST on the NATIVE lane records (kr_gguf_prefill_h.hip): Q6_K (K % 256 == 0) and Q5_0 (K % 32 == 0), N % 8 == 0; no derived copy ----
+// a_h / a_mul: the f16 rows and row multipliers of kr_launch_pfh_rows_bf16 / kr_launch_pfh_act.  sort == nullptr: dense rows (single_expert_rows) of expert 0.
+// out: f32 rows (multiplier applied) or, out_f16, f16 rows of raw accumulators for kr_launch_pf_combine_f16rows; columns [col_off, col_off + N) of rows out_ld apart
+bool kr_gfh_type_supported(int type, int K, int N);
+void kr_launch_gfh_gemm(const GgMat& m, const uint16_t* a_h, const float* a_mul, const KrPfSort* sort, int topk, int gather_tokens, int max_tiles,
+                        int single_expert_rows, void* out, int out_ld, int col_off, int out_f16, int run, hipStream_t st);
 void kr_launch_gpf_fill_synth(void* q, size_t q_bytes, void* h, size_t h_bytes, int type, uint64_t seed, hipStream_t st);
 
 // ---- the exact grouped pass (kr_gguf_group.hip): rows sorted by expert in groups of kr_ggg_group_rows(), one activation image per row, the block kernels' chains per row ----
