@@ -108,6 +108,11 @@ int kr_fill_layer_synthetic_gguf(kr_engine* e, int layer, int gate_up_type, int 
  * tree-ordered sums) over the whole row, or over two slices of its blocks whose results are added -- what the two k-waves of the mode's gate|up launch do.
  * Re-tiles into a scratch matrix, one launch, copies back; keeps no state on the engine.  Anything else: KR_ERR_VALUE. */
 int kr_gguf_matvec(kr_engine* e, int type, const uint8_t* blocks, int N, int K, const float* x, float* y, int parts);
+/* The grouped Q5_0 (6) / Q6_K (14) kernel of the exact pass ("gguf_exact_grouped_scalar") as a stand-alone operator: y[M][N] = x[M][K] W^T for N rows of raw
+ * row-major GGUF blocks and M f32 rows, all host pointers.  The rows go through the kernel in groups of 8 (M = 11: a group of 8 and a group of 3); every
+ * y[m][n] carries the bits of kr_gguf_matvec(parts 0) on row m alone, whatever shares its group.  Refuses what kr_gguf_matvec refuses, and M < 1, with
+ * KR_ERR_VALUE.  Re-tiles into a scratch matrix and copies back; keeps no state on the engine. */
+int kr_gguf_matmul_rows(kr_engine* e, int type, const uint8_t* blocks, int N, int K, const float* x, int M, float* y);
 /* Read one expert back in the reference layout (inverse re-tiling); used by parity tests at full size. */
 int kr_download_expert_unified(kr_engine* e, int layer, int expert, void* w13, uint16_t* w13_scales,
                                void* w2, uint16_t* w2_scales);
@@ -350,6 +355,10 @@ int kr_decode_set_attention_mode(kr_decode_store* s, int mode);
  * speculation entry points, which otherwise refuse a store with such layers, accept it.  Slower than the default form on long prompts.  A prompt pass
  * with the option and KR_GEMM_FAST both set is refused (KR_ERR_STATE).  Stores without native GGUF layers are unaffected.
  * "gguf_exact_grouped" (default 1): 0 = that pass through the streaming block kernels for every block type (A/B and test hook; same bits).
+ * "gguf_exact_grouped_scalar" (default 0; docs/design/43-gguf-exact-grouped-scalar.md): under "gguf_exact_pass", with 1 a Q6_K / Q5_0 projection takes a grouped
+ * kernel of its own (an expert's records read and unpacked once per group of 8 rows, the reference's serial f32 chain per row) and a Q4_K / Q8_0 projection of the
+ * same layer keeps its grouped kernel; with 0 a layer that holds a Q6_K or Q5_0 matrix streams whole, as before the option existed.  Same bits either way; refuses
+ * nothing.  Measured on 4-layer models: 1.9 .. 2.2x faster on a 2048-token prompt and 1.14 .. 1.26x at 64 rows, 1 .. 3 % slower at 16 rows -- hence off by default.
  * "slot_select" (default 1; docs/design/33-slot-select.md): KR_DECODE_FAST, MoE layers under the lean routing rule (softmax scoring, no score
  * correction, renormalised weights; E <= 512): with 1 every routed workgroup of the gate|up launch selects the expert id of its own rank only and one
  * extra grid row publishes ids and weights for the down launch; with 0 every workgroup runs the full top-k select and workgroup (0, 0) publishes.  Same
@@ -718,6 +727,7 @@ enum {
     KR_MPC_GGUF_GROUPED,    /* ... that took the grouped form ("gguf_exact_grouped" 1), not the streaming kernels */
     KR_MPC_SEQ_PASSES,      /* prompt / verify passes of the store's own sequence (kr_decode_prefill*, kr_decode_verify) */
     KR_MPC_SEQ_FEW,         /* ... that took the few-row kernels */
+    KR_MPC_GGUF_GROUPED_SCALAR, /* batched passes over slots in which a MoE layer took the grouped Q6_K / Q5_0 kernel for some projection ("gguf_exact_grouped_scalar") */
     KR_MPC_COUNT
 };
 int kr_decode_multi_path_counts(kr_decode_store* s, int64_t* out, int n, int reset);

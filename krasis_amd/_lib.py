@@ -18,7 +18,7 @@ KR_EXTEND_MAX_TOKENS = 1024                    # multi-sequence extend: tokens p
 # every symbol include/krasis_hip.h declares (checked by tests/test_abi.py without a GPU)
 SYMBOLS = [
     "kr_last_error", "kr_version", "kr_alloc_count_total", "kr_engine_create", "kr_engine_destroy", "kr_engine_get_config",
-    "kr_engine_device_bytes", "kr_upload_expert_unified", "kr_upload_expert_bf16", "kr_upload_expert_gguf", "kr_fill_layer_synthetic", "kr_fill_layer_synthetic_gguf", "kr_gguf_matvec",
+    "kr_engine_device_bytes", "kr_upload_expert_unified", "kr_upload_expert_bf16", "kr_upload_expert_gguf", "kr_fill_layer_synthetic", "kr_fill_layer_synthetic_gguf", "kr_gguf_matvec", "kr_gguf_matmul_rows",
     "kr_download_expert_unified", "kr_marlin_repack", "kr_marlin_unpack", "kr_upload_expert_marlin", "kr_download_expert_marlin", "kr_moe_forward", "kr_moe_prefill", "kr_set_routing_config", "kr_set_routing_weights", "kr_set_routing_weights_synthetic",
     "kr_route_topk", "kr_forward_moe_routed", "kr_reduce_sum_bf16", "kr_combine_rows", "kr_ep_unique_id", "kr_ep_init", "kr_ep_destroy", "kr_moe_prefill_ep", "kr_ep_comm_ranks", "kr_ep_max_int", "kr_ep_allreduce_f32", "kr_ep_loopback_create", "kr_ep_loopback_destroy", "kr_ep_init_loopback", "kr_moe_set_prefill_pairs", "kr_moe_set_gemm_mode", "kr_synchronize", "kr_set_profiling",
     "kr_get_profile", "kr_decode_create", "kr_decode_set_moe_store", "kr_decode_destroy", "kr_decode_store_weight_f32", "kr_decode_store_weight_synthetic",
@@ -91,6 +91,8 @@ def load_library() -> C.CDLL:
     lib.kr_fill_layer_synthetic_gguf.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint64]
     if hasattr(lib, "kr_gguf_matvec"):      # (KRASIS_HIP_LIB may name a build from before the operator: the A/B legs of tools/probes/gguf_scalar_tiles.py)
         lib.kr_gguf_matvec.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+    if hasattr(lib, "kr_gguf_matmul_rows"):      # (an older build under KRASIS_HIP_LIB: the A/B legs of tools/probes/gguf_exact_grouped_scalar.py)
+        lib.kr_gguf_matmul_rows.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
     lib.kr_download_expert_unified.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.kr_marlin_repack.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     lib.kr_marlin_unpack.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]

@@ -115,7 +115,17 @@ static bool pass_few_rows(const kr_decode_store* s, int T) {
     return kr_rows_use(s->opt_pass_few_rows, s->opt_pass_few_rows_max, T, s->gemm_fast ? KR_ROWS_MODE_GEMM_FAST : 0);
 }
 static int gguf_exact_bits(const kr_decode_store* s) {
-    return s->opt_gguf_exact_pass ? KR_PF_SET_GGUF_EXACT | (s->opt_gguf_exact_grouped ? 0 : KR_PF_SET_GGUF_STREAM) : 0;
+    return s->opt_gguf_exact_pass ? KR_PF_SET_GGUF_EXACT | (s->opt_gguf_exact_grouped ? 0 : KR_PF_SET_GGUF_STREAM) | (s->opt_gguf_exact_grouped_scalar ? KR_PF_SET_GGUF_SCALAR : 0) : 0;
+}
+// a MoE layer of the store takes the grouped row-chain kernel for some projection under the store's options: the dispatcher's own predicate (kr_moe_gguf_exact_forms)
+static bool gguf_grouped_scalar(const kr_decode_store* s) {
+    if (!s->eng || s->own_eng) return false;
+    for (const DLayer& L : s->layers) {
+        if (L.mlp != MLP_MOE) continue;
+        const int f = kr_moe_gguf_exact_forms(s->eng, L.moe_layer, gguf_exact_bits(s));
+        if ((f & 3) == KR_GGX_ROWS || (f >> 2) == KR_GGX_ROWS) return true;
+    }
+    return false;
 }
 static bool has_gguf_moe(const kr_decode_store* s) {
     const kr_engine* e = s->eng;
@@ -919,7 +929,7 @@ static void multi_path_count(kr_decode_store* s, const KrMultiPlan& pl, bool ver
     c[KR_MPC_FD] += pl.fd_chunks > 0; c[KR_MPC_MLA_FD] += pl.mla_chunks > 0;
     c[KR_MPC_GQA_FLASH] += pl.gqa_runs == KR_MP_RUNS_FLASH; c[KR_MPC_MLA_FLASH] += pl.mla_runs == KR_MP_RUNS_FLASH; c[KR_MPC_LC] += pl.lc_nruns > 0;
     c[KR_MPC_RUNS] += pl.any_run;
-    if (has_gguf_moe(s) && (gguf_exact_bits(s) & KR_PF_SET_GGUF_EXACT)) { c[KR_MPC_GGUF_EXACT]++; c[KR_MPC_GGUF_GROUPED] += !(gguf_exact_bits(s) & KR_PF_SET_GGUF_STREAM); }
+    if (has_gguf_moe(s) && (gguf_exact_bits(s) & KR_PF_SET_GGUF_EXACT)) { c[KR_MPC_GGUF_EXACT]++; c[KR_MPC_GGUF_GROUPED] += !(gguf_exact_bits(s) & KR_PF_SET_GGUF_STREAM); c[KR_MPC_GGUF_GROUPED_SCALAR] += gguf_grouped_scalar(s); }
 }
 extern "C" int kr_decode_multi_path_counts(kr_decode_store* s, int64_t* out, int n, int reset) {
     if (!s || n < 0 || n > KR_MPC_COUNT || (n > 0 && !out)) return kr_fail(KR_ERR_VALUE, "kr_decode_multi_path_counts: null store, null out or n %d outside [0, %d]", n, (int)KR_MPC_COUNT);

@@ -519,6 +519,47 @@ extern "C" int kr_gguf_matvec(kr_engine* e, int type, const uint8_t* blocks, int
     return KR_OK;
 }
 
+// The grouped Q5_0 / Q6_K kernel of the exact pass as a stand-alone operator (docs/design/43-gguf-exact-grouped-scalar.md): raw row-major blocks and M f32 rows on the
+// host, the matrix re-tiled as kr_gguf_matvec does, the rows sorted as the one expert's (groups of kr_ggg_group_rows(): M = 11 is a group of 8 and one of 3), one
+// launch of kr_ggs_kernel per 16 384 rows, y[M][N] copied back.  Nothing stays on the engine.
+extern "C" int kr_gguf_matmul_rows(kr_engine* e, int type, const uint8_t* blocks, int N, int K, const float* x, int M, float* y) {
+    if (!e) return kr_fail(KR_ERR_VALUE, "kr_gguf_matmul_rows: null engine");
+    if (!blocks || !x || !y) return kr_fail(KR_ERR_VALUE, "kr_gguf_matmul_rows: null pointer argument");
+    if (type != GG_Q5_0 && type != GG_Q6_K) return kr_fail(KR_ERR_VALUE, "kr_gguf_matmul_rows: type %d is neither Q5_0 (6) nor Q6_K (14)", type);
+    if (N < 1 || K < 1 || K % ggml_block_elems(type) || K > 15360) return kr_fail(KR_ERR_VALUE, "kr_gguf_matmul_rows: shape N %d, K %d (K: a multiple of %d, at most 15360)", N, K, ggml_block_elems(type));
+    if (M < 1) return kr_fail(KR_ERR_VALUE, "kr_gguf_matmul_rows: M %d rows (at least 1)", M);
+    std::lock_guard<std::mutex> lk(e->mu);
+    KR_HIP(hipSetDevice(e->device));
+    GgMat m{}; m.type = type; m.K = K; m.N = N; m.q_stride = gg_q_bytes(type, K, N); m.h_stride = gg_h_bytes(type, K, N);
+    std::vector<uint8_t> dq(m.q_stride), dh(m.h_stride);
+    retile_gguf(type, blocks, K, N, dq.data(), dh.data());
+    const int R = kr_ggg_group_rows(), CH = M < 16384 ? M : 16384, max_tiles = CH / R + 2;
+    const size_t n_i32 = 3 + 3 * (size_t)max_tiles + 4 + 2 * (size_t)CH;
+    DevBuf q, h, xd, yd, ids, i32;
+    if (q.ensure(m.q_stride) || h.ensure(m.h_stride) || xd.ensure((size_t)CH * K * 4) || yd.ensure((size_t)CH * N * 4) || ids.ensure((size_t)CH * 4) || i32.ensure(n_i32 * 4))
+        return kr_fail(KR_ERR_HIP, "kr_gguf_matmul_rows: hipMalloc of the scratch matrix failed");
+    KR_HIP(hipMemcpy(q.p, dq.data(), m.q_stride, hipMemcpyHostToDevice));
+    KR_HIP(hipMemcpy(h.p, dh.data(), m.h_stride, hipMemcpyHostToDevice));
+    const std::vector<int32_t> zero(CH, 0);      // every row is a row of expert 0
+    KR_HIP(hipMemcpy(ids.p, zero.data(), (size_t)CH * 4, hipMemcpyHostToDevice));
+    m.q = q.p; m.h = h.p;
+    int* ib = (int*)i32.p;
+    KrPfSort so{};
+    so.counts = ib; so.offsets = ib + 1; so.cursor = ib + 2; ib += 3;
+    so.tile_expert = ib; so.tile_row0 = ib + max_tiles; so.tile_rows = ib + 2 * max_tiles; ib += 3 * max_tiles;
+    so.n_tiles = ib; ib += 4; so.row_pair = ib; so.pair_row = ib + CH;
+    for (int m0 = 0; m0 < M; m0 += CH) {
+        const int mc = M - m0 < CH ? M - m0 : CH;
+        KR_HIP(hipMemcpy(xd.p, x + (size_t)m0 * K, (size_t)mc * K * 4, hipMemcpyHostToDevice));
+        kr_launch_pf_sort((const int32_t*)ids.p, mc, 1, 1, so, e->stream, R);
+        kr_launch_ggs_gemm(m, nullptr, xd.p, 0, K, &so, 1, 1, 1, mc, 1, (float*)yd.p, N, e->stream);
+        KR_HIP(hipGetLastError());
+        KR_HIP(hipStreamSynchronize(e->stream));
+        KR_HIP(hipMemcpy(y + (size_t)m0 * N, yd.p, (size_t)mc * N * 4, hipMemcpyDeviceToHost));
+    }
+    return KR_OK;
+}
+
 // stage an argument that may live on the host
 static int stage_in(kr_engine* e, DevBuf& buf, const void* p, size_t bytes, const void** dev) {
     if (is_device_ptr(p)) { *dev = p; return KR_OK; }
@@ -1095,19 +1136,33 @@ static int moe_prefill_gguf(kr_engine* e, Layer& L, int layer, const void* x_bf1
     return KR_OK;
 }
 
-// KR_PF_SET_GGUF_EXACT (the decode store's "gguf_exact_pass"): every row with the bits of the decode step's block kernels (docs/design/20-gguf-exact-pass.md).
-// Q4_K / Q8_0 layers: rows sorted by expert, one activation image per row, the grouped kernels of kr_gguf_group.hip; any other layer (Q4_0 / Q5_0 / Q6_K, a k
-// that is no multiple of 32) or `stream`: the streaming kernels of kr_gguf.hip over the rows.  Routed experts only: the weighted sum in routing order, no rsf
-// (the caller's epilogue applies its own, as the decode step's next norm does).  Scratch is the chunk's own set: several chunks may be in flight.
-static int moe_prefill_gguf_exact(kr_engine* e, Layer& L, const void* x_bf16, const int32_t* ids, const float* wts, void* out, int M, int topk,
-                                  int out_dtype, int routed_only, int set, int stream, hipStream_t st) {
+// KR_PF_SET_GGUF_EXACT (the decode store's "gguf_exact_pass"): every row with the bits of the decode step's block kernels (docs/design/20-gguf-exact-pass.md,
+// 43-gguf-exact-grouped-scalar.md).  Per projection: Q4_K / Q8_0 take the grouped kernels of kr_gguf_group.hip over one activation image per row, Q6_K / Q5_0
+// (KR_PF_SET_GGUF_SCALAR) the grouped row-chain kernel of the same file over f32 rows; gate and up are of one type.  Any other layer (Q4_0, a k that is no multiple
+// of the block size, row counts that do not match, a Q6_K / Q5_0 matrix without the bit) or KR_PF_SET_GGUF_STREAM: the streaming kernels of kr_gguf.hip over the
+// rows.  Routed experts only: the weighted sum in routing order, no rsf (the caller's epilogue applies its own, as the decode step's next norm does).  Scratch is
+// the chunk's own set: several chunks may be in flight.
+static int ggx_proj_form(int type, int K, bool scalar) {
+    if (kr_ggg_type_supported(type, K)) return KR_GGX_IMAGE;
+    return scalar && kr_ggs_type_supported(type, K) ? KR_GGX_ROWS : 0;
+}
+int kr_moe_gguf_exact_forms(const kr_engine* e, int layer, int set) {
+    if (!e || layer < 0 || layer >= (int)e->layers.size()) return 0;
+    const Layer& L = e->layers[layer];
+    if (!L.gguf || !(set & KR_PF_SET_GGUF_EXACT) || (set & KR_PF_SET_GGUF_STREAM)) return 0;
+    const int H = e->cfg.hidden_size, I = L.inter;
+    if (L.g_up.type != L.g_gate.type || L.g_gate.N != I || L.g_up.N != I || L.g_down.N != H) return 0;
+    const int f13 = ggx_proj_form(L.g_gate.type, H, set & KR_PF_SET_GGUF_SCALAR), f2 = ggx_proj_form(L.g_down.type, I, set & KR_PF_SET_GGUF_SCALAR);
+    return f13 && f2 ? f13 | f2 << 2 : 0;
+}
+static int moe_prefill_gguf_exact(kr_engine* e, Layer& L, int layer, const void* x_bf16, const int32_t* ids, const float* wts, void* out, int M, int topk,
+                                  int out_dtype, int routed_only, int set, int bits, hipStream_t st) {
     const int H = e->cfg.hidden_size, I = L.inter, E = e->cfg.n_routed_experts;
     if (L.gguf_shared && !routed_only) return kr_fail(KR_ERR_VALUE, "the exact GGUF pass covers routed experts only (routed_only = 1)");
     kr_engine::PfSet& P = e->pf[set % KR_PF_MAX_DEPTH];
     const size_t ob = out_dtype == KR_OUT_BF16 ? 2 : 4;
-    const bool grouped = !stream && kr_ggg_type_supported(L.g_gate.type, H) && L.g_up.type == L.g_gate.type && kr_ggg_type_supported(L.g_down.type, I) &&
-                         L.g_gate.N == I && L.g_up.N == I && L.g_down.N == H;
-    if (!grouped) {      // grid z = rows: 16 384 per pass
+    const int forms = kr_moe_gguf_exact_forms(e, layer, bits), f13 = forms & 3, f2 = forms >> 2;
+    if (!forms) {      // grid z = rows: 16 384 per pass
         const int CH = M < 16384 ? M : 16384;
         if (P.gu.ensure((size_t)CH * topk * 2 * I * 4) || P.eo.ensure((size_t)CH * topk * H * 4)) return kr_fail(KR_ERR_HIP, "hipMalloc of prefill scratch failed");
         for (int m0 = 0; m0 < M; m0 += CH) {
@@ -1133,7 +1188,9 @@ static int moe_prefill_gguf_exact(kr_engine* e, Layer& L, const void* x_bf16, co
     const size_t np = (size_t)CH * topk;
     const int max_tiles = (int)(np / R) + E + 1;
     const size_t n_i32 = 3 * (size_t)E + 3 * (size_t)max_tiles + 4 + 2 * np;
-    if (P.i32.ensure(n_i32 * 4) || P.xh.ensure((size_t)CH * kr_ggg_image_stride(H)) || P.hh.ensure(np * kr_ggg_image_stride(I)) || P.gu.ensure(np * 2 * I * 4) || P.eo.ensure(np * H * 4))
+    // xh: the token rows' images (an image form on gate | up only: the row chains read the bf16 rows); hh: the hidden rows as images or as f32 rows
+    if (P.i32.ensure(n_i32 * 4) || (f13 == KR_GGX_IMAGE && P.xh.ensure((size_t)CH * kr_ggg_image_stride(H))) ||
+        P.hh.ensure(f2 == KR_GGX_IMAGE ? np * kr_ggg_image_stride(I) : np * I * 4) || P.gu.ensure(np * 2 * I * 4) || P.eo.ensure(np * H * 4))
         return kr_fail(KR_ERR_HIP, "hipMalloc of prefill scratch failed");
     int* ib = (int*)P.i32.p;
     KrPfSort so{};
@@ -1146,10 +1203,17 @@ static int moe_prefill_gguf_exact(kr_engine* e, Layer& L, const void* x_bf16, co
         const uint16_t* xc = (const uint16_t*)x_bf16 + (size_t)m0 * H;
         const int32_t* idc = ids + (size_t)m0 * topk; const float* wc = wts + (size_t)m0 * topk;
         kr_launch_pf_sort(idc, mc, topk, E, so, st, R);
-        kr_launch_ggg_image_x(xc, mc, H, P.xh.p, st);
-        kr_launch_ggg_gemm(gate, &up, P.xh.p, &so, topk, 1, mc * topk, E, (float*)P.gu.p, 2 * I, st);
-        kr_launch_ggg_image_h((const float*)P.gu.p, mc * topk, I, 2 * I, &so, P.hh.p, st);
-        kr_launch_ggg_gemm(down, nullptr, P.hh.p, &so, topk, 0, mc * topk, E, (float*)P.eo.p, H, st);
+        if (f13 == KR_GGX_IMAGE) {
+            kr_launch_ggg_image_x(xc, mc, H, P.xh.p, st);
+            kr_launch_ggg_gemm(gate, &up, P.xh.p, &so, topk, 1, mc * topk, E, (float*)P.gu.p, 2 * I, st);
+        } else kr_launch_ggs_gemm(gate, &up, xc, 1, H, &so, topk, 1, 0, mc * topk, E, (float*)P.gu.p, 2 * I, st);
+        if (f2 == KR_GGX_IMAGE) {
+            kr_launch_ggg_image_h((const float*)P.gu.p, mc * topk, I, 2 * I, &so, P.hh.p, st);
+            kr_launch_ggg_gemm(down, nullptr, P.hh.p, &so, topk, 0, mc * topk, E, (float*)P.eo.p, H, st);
+        } else {
+            kr_launch_ggs_hidden((const float*)P.gu.p, mc * topk, I, 2 * I, &so, (float*)P.hh.p, st);
+            kr_launch_ggs_gemm(down, nullptr, P.hh.p, 0, I, &so, topk, 0, 0, mc * topk, E, (float*)P.eo.p, H, st);
+        }
         kr_launch_pf_combine((const float*)P.eo.p, so.pair_row, wc, mc, topk, H, nullptr, 1.0f, (char*)out + (size_t)m0 * H * ob, out_dtype == KR_OUT_BF16, st);
     }
     KR_HIP(hipGetLastError());
@@ -1222,11 +1286,12 @@ int kr_moe_prefill_set(kr_engine* e, int layer, const void* x_bf16, const int32_
     std::lock_guard<std::mutex> lk(e->mu);
     KR_HIP(hipSetDevice(e->device));
     const bool fast = e->gemm_fast || (set & KR_PF_SET_FAST);
-    const bool gguf_exact = set & KR_PF_SET_GGUF_EXACT, gguf_stream = set & KR_PF_SET_GGUF_STREAM, few_rows = set & KR_PF_SET_ROWS;
+    const bool gguf_exact = set & KR_PF_SET_GGUF_EXACT, few_rows = set & KR_PF_SET_ROWS;
+    const int gguf_bits = set & (KR_PF_SET_GGUF_EXACT | KR_PF_SET_GGUF_STREAM | KR_PF_SET_GGUF_SCALAR);
     set &= 0xFF;
     if (L.gguf && gguf_exact) {
         if (fast) return kr_fail(KR_ERR_STATE, "the exact GGUF pass (\"gguf_exact_pass\") does not run together with the tolerance GEMMs (KR_GEMM_FAST)");
-        return moe_prefill_gguf_exact(e, L, x_bf16, ids, wts, out, M, topk, out_dtype, routed_only, set, gguf_stream, st);
+        return moe_prefill_gguf_exact(e, L, layer, x_bf16, ids, wts, out, M, topk, out_dtype, routed_only, set, gguf_bits, st);
     }
     if (L.gguf) {      // native GGUF blocks: the exact int8-MFMA form, or (tolerance mode, Q4_K layers) f16 MFMA on the re-tiled copy
         if (fast && gg_fast_ok(L, e->cfg.hidden_size, L.gguf_shared && !routed_only)) return moe_prefill_gguf_fast(e, L, x_bf16, ids, wts, out, M, topk, out_dtype, routed_only, set, st);

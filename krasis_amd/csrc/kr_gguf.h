@@ -44,10 +44,16 @@ void kr_launch_gfh_gemm(const GgMat& m, const uint16_t* a_h, const float* a_mul,
                         int single_expert_rows, void* out, int out_ld, int col_off, int out_f16, int run, hipStream_t st);
 void kr_launch_gpf_fill_synth(void* q, size_t q_bytes, void* h, size_t h_bytes, int type, uint64_t seed, hipStream_t st);
 
-// ---- the exact grouped pass (kr_gguf_group.hip): rows sorted by expert in groups of kr_ggg_group_rows(), one activation image per row, the block kernels' chains per row ----
+// ---- the exact grouped pass (kr_gguf_group.hip): rows sorted by expert in groups of kr_ggg_group_rows(); Q4_K / Q8_0: one activation image per row, the block kernels' chains per row ----
 bool kr_ggg_type_supported(int type, int K);        // Q4_K with K % 256 == 0, Q8_0 with K % 32 == 0
 int kr_ggg_group_rows();                            // rows per tile the sort's tile table must be built with
 size_t kr_ggg_image_stride(int K);                  // bytes of one row's image: {AH4, AL4} per sub-block and AVX lane, f32 scale and i32 sum per sub-block
 void kr_launch_ggg_image_x(const uint16_t* x_bf16, int M, int K, void* img, hipStream_t st);                                     // images of M bf16 rows
 void kr_launch_ggg_image_h(const float* gu, int pairs, int I, int gu_ld, const KrPfSort* sort, void* img, hipStream_t st);       // images of silu(gate) * up of the sorted rows
 void kr_launch_ggg_gemm(const GgMat& m0, const GgMat* m1, const void* img, const KrPfSort* sort, int topk, int gather_tokens, int pairs, int n_experts, float* out, int out_ld, hipStream_t st);
+// ... Q6_K / Q5_0 (docs/design/43-gguf-exact-grouped-scalar.md): the same sort, the row chains of gg_row_q6k / gg_row_q5_0 over f32 activation rows staged in LDS, no image
+bool kr_ggs_type_supported(int type, int K);        // Q6_K with K % 256 == 0, Q5_0 with K % 32 == 0
+void kr_launch_ggs_hidden(const float* gu, int pairs, int I, int gu_ld, const KrPfSort* sort, float* hid, hipStream_t st);       // f32 silu(gate) * up of the sorted rows, [pairs][I]
+// x: bf16 or f32 activation rows x_ld elements apart; gather_tokens: sorted row r reads row row_pair[r] / topk; out_pairs: it writes out row row_pair[r], not r
+void kr_launch_ggs_gemm(const GgMat& m0, const GgMat* m1, const void* x, int x_bf16, size_t x_ld, const KrPfSort* sort, int topk, int gather_tokens, int out_pairs, int pairs,
+                        int n_experts, float* out, int out_ld, hipStream_t st);

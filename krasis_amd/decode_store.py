@@ -405,6 +405,10 @@ class CpuDecodeStore:
         slot and speculation calls accept a store with such layers; slower than the default int8-MFMA form on long prompts; refused together with
         gemm_fast; nothing changes for other weight forms (docs/design/20-gguf-exact-pass.md).  "gguf_exact_grouped" (default 1): 0 makes that pass
         take the streaming block kernels for every type (A/B and test hook, same bits).
+        "gguf_exact_grouped_scalar" (default 0): under "gguf_exact_pass", with 1 a Q6_K / Q5_0 projection takes a grouped kernel of its own (records read
+        and unpacked once per group of 8 rows, the reference's serial f32 chain per row) beside the Q4_K / Q8_0 grouped kernels; with 0 a layer that
+        holds such a matrix streams whole, as before.  Same bits; refuses nothing; faster on prompts and at 64 rows, 1 .. 3 % slower at 16 rows, hence off by
+        default (docs/design/43-gguf-exact-grouped-scalar.md).
         "gguf_scalar_tiles" (default 1): decode steps under decode_fast on native-GGUF MoE layers with a Q5_0 or Q6_K matrix -- with 1 the routed
         slots of the mode's gate|up and down launches walk such a matrix with the f32 tiles (the reference's terms from the f32 activation vector, 8
         lanes per row, tree-ordered sums); with 0 such a layer leaves the mode's three MoE launches for the exact block kernels and a combine launch
@@ -818,7 +822,8 @@ class CpuDecodeStore:
         return seen, rng.value
 
     MULTI_PATH_COUNTS = ("passes", "verify", "few", "xs_split", "mla_xs_split", "gqa_xm", "mla_xm", "lx", "lx_runs", "lx_short", "fd", "mla_fd",
-                         "gqa_flash", "mla_flash", "lc", "runs", "gguf_exact", "gguf_grouped", "seq_passes", "seq_few")      # KR_MPC_* of krasis_hip.h, in order
+                         "gqa_flash", "mla_flash", "lc", "runs", "gguf_exact", "gguf_grouped", "seq_passes", "seq_few",
+                         "gguf_grouped_scalar")      # KR_MPC_* of krasis_hip.h, in order
 
     def multi_path_counts(self, reset: bool = False) -> dict:
         """kr_decode_multi_path_counts (test aid): which forms the multi-row passes of this store took so far -- host-side counters, one count per batched

@@ -159,6 +159,21 @@ class KrasisEngine:
         check(self._lib.kr_gguf_matvec(self._h, int(type), _addr(blocks), int(N), int(K), _addr(x), _addr(y), int(parts)))
         return y
 
+    def gguf_matmul_rows(self, type: int, blocks: np.ndarray, N: int, K: int, X: np.ndarray) -> np.ndarray:
+        """Y[M, N] = X W^T for N rows of raw row-major Q5_0 (6) / Q6_K (14) blocks and f32 rows X[M, K], through the grouped kernel the exact GGUF pass
+        runs for such a matrix ("gguf_exact_grouped_scalar"): the rows in groups of 8, every Y[m, n] with the bits of gguf_matvec(parts=0) on row m
+        alone.  Other types or shapes, M < 1: ValueError.  Keeps no state on the engine."""
+        self._need()
+        blocks = np.ascontiguousarray(blocks, np.uint8); X = np.ascontiguousarray(X, np.float32)
+        if X.ndim != 2:
+            raise ValueError("kr_gguf_matmul_rows: X must be [M, K]")
+        M = X.shape[0]
+        if type in (6, 14) and (blocks.size != int(N) * (int(K) // (32 if type == 6 else 256)) * (22 if type == 6 else 210) or X.shape[1] != int(K)):
+            raise ValueError("kr_gguf_matmul_rows: blocks / X do not hold N x K")
+        Y = np.empty((M, max(int(N), 0)), np.float32)
+        check(self._lib.kr_gguf_matmul_rows(self._h, int(type), _addr(blocks), int(N), int(K), _addr(X), int(M), _addr(Y)))
+        return Y
+
     def download_expert(self, layer: int, expert: int, bits: int = 4, w2_bits: Optional[int] = None):
         """Read an expert back in the reference layout (inverse re-tiling)."""
         self._need()
