@@ -278,6 +278,9 @@ int kr_decode_set_kv_dtype(kr_decode_store* s, int kv_dtype);
 int kr_decode_set_attention_mode(kr_decode_store* s, int mode);
 /* Options by name.  Test / tuning hooks: "gqa_stream", "pfm_timing", ... (see kr_decode.cpp); "multi_attn_fast": see kr_decode_step_multi;
  * "multi_attn_fast_paged" (default 0; docs/design/23-multi-attn-fast-paged.md): "multi_attn_fast" for flat and paged slots alike, see kr_decode_step_multi.
+ * "multi_attn_fast_paged" = 2 (docs/design/44-multi-attn-fast-share.md): everything 1 means, and rows of a pass that read the same cache rows for a full
+ * chunk -- slots forked from one prefix, the token rows of one slot -- share a workgroup of the chunk pass: the bits of 1 from fewer tile loads.  Any other
+ * non-zero value means 1.
  * "multi_mla_fast" (default 0; docs/design/24-multi-mla-fast.md): the MLA layers of every batched entry point run split-KV flash-decode over slots of
  * max_seq > 512, flat or paged: row i carries the bits of kr_decode_step under KR_ATTN_FAST on that sequence alone; shorter slots keep the exact step.
  * Refused on a store without MLA layers (KR_ERR_STATE) and on MLA layers of more than 64 heads (KR_ERR_VALUE); see kr_decode_step_multi.
@@ -490,7 +493,10 @@ int kr_decode_slot_load(kr_decode_store* s, int slot, int seq_len);
    slots of max_seq > 1024 the flash-decode reads the pools through the slots' page tables and row i carries the bits of the same call on flat slots of
    the same n_slots and max_seq under "multi_attn_fast", for any page_tokens, any placement of the pages and pages shared by kr_decode_slot_fork; paged
    slots of max_seq <= 1024 keep the exact paged step; on flat slots it is "multi_attn_fast"; with both set it governs.  Its refusals are those of
-   "multi_attn_fast", and the page pool behaves as without it.
+   "multi_attn_fast", and the page pool behaves as without it.  With "multi_attn_fast_paged" = 2 the chunk pass also puts up to min(8, 32 / (nh / nkv))
+   rows into one workgroup wherever a chunk is full for each of them and they name the same cache rows for it (the same slot; on paged slots the same
+   pages): every row keeps the bits of value 1, the refusals are the same, and KR_MPC_FD_SHARED counts the passes that held such a group.  A pass whose
+   runs take the run kernels of "multi_extend_flash" keeps the one-row chunk kernel (docs/design/44-multi-attn-fast-share.md).
    kr_decode_set_option(s, "multi_mla_fast", 1) (default 0; docs/design/24-multi-mla-fast.md) is the counterpart for MLA layers, one option for flat and
    paged slots: over slots of max_seq > 512 the MLA layers of every batched entry point run split-KV flash-decode on the f16 matrix cores (through the
    page tables on paged slots, pages shared by kr_decode_slot_fork included) and row i carries the bits of kr_decode_step under KR_ATTN_FAST on that
@@ -728,6 +734,7 @@ enum {
     KR_MPC_SEQ_PASSES,      /* prompt / verify passes of the store's own sequence (kr_decode_prefill*, kr_decode_verify) */
     KR_MPC_SEQ_FEW,         /* ... that took the few-row kernels */
     KR_MPC_GGUF_GROUPED_SCALAR, /* batched passes over slots in which a MoE layer took the grouped Q6_K / Q5_0 kernel for some projection ("gguf_exact_grouped_scalar") */
+    KR_MPC_FD_SHARED,       /* batched passes over slots in which a GQA layer ran a flash-decode item of two or more rows ("multi_attn_fast_paged" = 2) */
     KR_MPC_COUNT
 };
 int kr_decode_multi_path_counts(kr_decode_store* s, int64_t* out, int n, int reset);

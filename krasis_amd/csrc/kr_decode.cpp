@@ -1057,7 +1057,7 @@ extern "C" int kr_decode_set_option(kr_decode_store* s, const char* name, int va
     if (!strcmp(name, "generate_lookahead")) { s->opt_gen_lookahead = value != 0; return KR_OK; }
     if (!strcmp(name, "multi_sample_loop")) { s->opt_multi_sample_loop = value != 0; return KR_OK; }
     if (!strcmp(name, "multi_attn_fast")) { s->mopt.attn_fast = value != 0; return KR_OK; }
-    if (!strcmp(name, "multi_attn_fast_paged")) { s->mopt.attn_fast_paged = value != 0; return KR_OK; }    // "multi_attn_fast" that also reads paged slots, through the page table (docs/design/23-multi-attn-fast-paged.md); on flat slots the same thing
+    if (!strcmp(name, "multi_attn_fast_paged")) { s->mopt.attn_fast_paged = value == 2 ? 2 : value != 0; return KR_OK; }    // "multi_attn_fast" that also reads paged slots, through the page table (docs/design/23-multi-attn-fast-paged.md); on flat slots the same thing.  2: that, and rows that read the same cache rows for a chunk share a workgroup of the chunk pass (docs/design/44-multi-attn-fast-share.md)
     if (!strcmp(name, "multi_mla_fast")) { s->mopt.mla_fast = value != 0; return KR_OK; }                  // the MLA layers of every batched step run split-KV flash-decode over slots longer than mla_split_min, flat or paged (docs/design/24-multi-mla-fast.md)
     if (!strcmp(name, "multi_extend_la_chunk")) { s->mopt.extend_la_chunk = value != 0; return KR_OK; }    // a run of >= 64 tokens entering a slot (extend_multi / prefill_slot) takes the prompt pass's chunked delta rule in its linear-attention layers (docs/design/26-multi-extend-la-chunk.md)
     if (!strcmp(name, "multi_extend_exact_mfma")) { s->mopt.extend_exact_mfma = value != 0; return KR_OK; }     // a run of >= 2 tokens entering a slot (extend_multi / prefill_slot) takes the exact prompt pass's matrix-core scores, softmax and P.V over the slot, flat or paged: same bits as the per-row kernel (docs/design/28-multi-extend-exact-mfma.md)

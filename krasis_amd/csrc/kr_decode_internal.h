@@ -64,6 +64,9 @@ struct kr_multi_state {
     DevBuf la_pools, fk_ids; int la_npools = 0;
     DevBuf rows, ids, logits, scores, scratch; // step: [slots | tokens | positions] (device), greedy ids, [n][vocab] logits, attention scores, the arena
     DevBuf fd_o, fd_ml; bool fd_ready = false; // "multi_attn_fast": split-KV partials [n][nkv][chunks][G][hd] and (max, sum) [n][nh][chunks][2] of one GQA layer, sized by the step's longest row; the kernels' LDS windows are raised
+    // "multi_attn_fast_paged" = 2 (docs/design/44-multi-attn-fast-share.md): the item list of a pass's flash-decode rows (kr_fd_share.h) on the device, and the pinned
+    // host buffer of fds_cap bytes its one upload per pass reads; fds_ready: the LDS windows of the grouped chunk kernels are raised
+    DevBuf fds_items; int32_t* fds_pinned = nullptr; size_t fds_cap = 0; bool fds_ready = false;
     DevBuf tiles;                              // every tile table of a pass, one upload (kr_multi_plan.h: the plan's vector; its spans are relative to this buffer)
     bool pf_ready = false, mf_ready = false, lc_ready = false;   // "multi_extend_flash" / "multi_extend_mla_flash" / "multi_extend_la_chunk": the LDS windows of the run kernels are raised (kr_option_rules, once per slot set)
     DevBuf lc_scratch;                         // "multi_extend_la_chunk": the rule's scratch of one layer, sized by the pass's sub-chunks
@@ -93,6 +96,7 @@ struct kr_multi_state {
         for (hipEvent_t e : sw_ev) if (e) (void)hipEventDestroy(e);
         if (sw_stream) (void)hipStreamDestroy(sw_stream);
         if (sw_pinned) (void)hipHostFree(sw_pinned);
+        if (fds_pinned) (void)hipHostFree(fds_pinned);
     }
 };
 
@@ -176,6 +180,7 @@ int kr_standalone_cancelled(kr_decode_store* s);
 // take the verify form (no state stored; records into the layers of s->multi->v_host), and the logits of all n_rows rows -> s->multi->logits [n_rows][vocab]
 // h_counts / h_positions (host, optional): the n_runs run lengths and first positions as the caller gave them -- what the plan (kr_multi_plan.h) builds the
 // tables of the run options from and sizes the per-row kernels' scratch by; null counts: every run has one token
+// h_rows (host, optional): [slots | tokens | positions] of the n_rows pass rows as d_rows holds them -- what "multi_attn_fast_paged" = 2 builds its item list from
 int kr_multi_pass(kr_decode_store* s, int n_rows, int n_runs, const int32_t* d_rows, const int32_t* d_runs, int max_pos, hipStream_t st, bool verify = false,
-                  const int32_t* h_counts = nullptr, const int32_t* h_positions = nullptr);
+                  const int32_t* h_counts = nullptr, const int32_t* h_positions = nullptr, const int32_t* h_rows = nullptr);
 void kr_standalone_set_elapsed(kr_decode_store* s, double sec);   // kr_engine.cpp: per (group, column) nibble sums for the int8-MFMA GEMM

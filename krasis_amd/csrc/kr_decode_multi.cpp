@@ -260,9 +260,9 @@ std::vector<int32_t> lay_rows(const Rows& r, size_t& T, int& max_pos, std::vecto
     }
     return h;
 }
-int put_rows(kr_multi_state& M, const Rows& r, hipStream_t st, size_t& T, int& max_pos, std::vector<int>* row_of = nullptr) {
+int put_rows(kr_multi_state& M, const Rows& r, hipStream_t st, size_t& T, int& max_pos, std::vector<int32_t>& h, std::vector<int>* row_of = nullptr) {
     if (M.rows.ensure((size_t)3 * (KR_EXTEND_MAX_TOKENS + KR_MULTI_MAX) * 4)) return kr_fail(KR_ERR_HIP, "hipMalloc of the step's row buffers failed");
-    const std::vector<int32_t> h = lay_rows(r, T, max_pos, row_of);
+    h = lay_rows(r, T, max_pos, row_of);
     KR_HIP(hipMemcpyAsync(M.rows.p, h.data(), h.size() * 4, hipMemcpyHostToDevice, st));      // pageable source: staged before the call returns
     return KR_OK;
 }
@@ -287,12 +287,12 @@ int sample_runs(kr_multi_state& M, const float* logits, int vocab, const std::ve
 }
 // what step_impl and verify_impl open with: the rows to the device, then the pass's sampler rows -- one per run, or in the verify form one per token row
 // with the (run, t) table -- and the scratch for them.  sr stays empty when the pass is greedy: sample unset, or no slot of it has a sampler that draws
-struct Pass { size_t T = 0; int max_pos = 0; std::vector<KrMsRow> sr; std::vector<KrMsAt> at; };
+struct Pass { size_t T = 0; int max_pos = 0; std::vector<KrMsRow> sr; std::vector<KrMsAt> at; std::vector<int32_t> rows; };      // rows: the host's copy of what went to M.rows
 int open_pass(kr_decode_store* s, const Rows& r, bool sample, bool verify, hipStream_t st, Pass& p) {
     kr_multi_state& M = *s->multi;
     std::vector<int> row_of;
     if (int rc = pg_flush(M, st)) return rc;      // paged slots: the table entries and zeroed pages of this pass's rows, ahead of the pass
-    if (int rc = put_rows(M, r, st, p.T, p.max_pos, verify ? &row_of : nullptr)) return rc;
+    if (int rc = put_rows(M, r, st, p.T, p.max_pos, p.rows, verify ? &row_of : nullptr)) return rc;
     std::vector<KrMsRow> per_run;
     bool greedy = true;
     if (sample) for (int i = 0; i < r.n; i++) { per_run.push_back(sample_row(s, r.slots[i])); greedy &= per_run.back().mode == KR_MS_GREEDY; }
@@ -314,7 +314,7 @@ int step_impl(kr_decode_store* s, const Rows& r, int32_t* next_out, float* logit
     if (int rc = open_pass(s, r, sample, false, st, p)) return rc;
     const bool greedy = p.sr.empty();
     if (!greedy) KR_HIP(hipMemcpyAsync(M.smp_rows.p, p.sr.data(), p.sr.size() * sizeof(KrMsRow), hipMemcpyHostToDevice, st));
-    if (int rc = kr_multi_pass(s, (int)p.T, n, (const int32_t*)M.rows.p, (const int32_t*)M.rows.p + 3 * p.T, p.max_pos, st, false, r.counts, r.positions)) return fail_pass(st, rc);
+    if (int rc = kr_multi_pass(s, (int)p.T, n, (const int32_t*)M.rows.p, (const int32_t*)M.rows.p + 3 * p.T, p.max_pos, st, false, r.counts, r.positions, p.rows.data())) return fail_pass(st, rc);
     const size_t V = (size_t)s->vocab;
     if (greedy) kr_launch_multi_argmax((const float*)M.logits.p, V, (int)V, n, (int*)M.ids.p, st);
     else if (kr_launch_multi_sample(sampler_args(M, (const float*)M.logits.p, s->vocab, n, p.sr, (uint32_t*)M.smp_seen.p, M.smp_words, (uint64_t*)M.smp_rng.p, (int*)M.ids.p), st))
@@ -466,7 +466,7 @@ int verify_impl(kr_decode_store* s, const Rows& r, int32_t* ids_out, int32_t* n_
         return kr_fail(KR_ERR_HIP, "hipMalloc of the verify's row buffers failed");
     if (int rc = verify_records(s, T, st)) return fail_pass(st, rc);
     const int32_t* d_rows = (const int32_t*)M.rows.p;
-    if (int rc = kr_multi_pass(s, (int)T, n, d_rows, d_rows + 3 * T, p.max_pos, st, true)) return fail_pass(st, rc);
+    if (int rc = kr_multi_pass(s, (int)T, n, d_rows, d_rows + 3 * T, p.max_pos, st, true, nullptr, nullptr, p.rows.data())) return fail_pass(st, rc);
     const size_t V = (size_t)s->vocab;
     if (greedy) kr_launch_multi_argmax((const float*)M.logits.p, V, (int)V, (int)T, (int*)M.ids.p, st);
     else if (int rc = sample_runs(M, (const float*)M.logits.p, s->vocab, p.sr, p.at, d_rows, (uint32_t*)M.smp_seen.p, M.smp_words, (uint64_t*)M.smp_rng.p, (int*)M.ids.p, st))

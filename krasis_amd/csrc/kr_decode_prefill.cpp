@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/krasis_hip.h"
+#include "kr_fd_share.h"
 #include "kr_multi_plan.h"
 #include "kr_rows_plan.h"
 #include "kr_decode_internal.h"
@@ -50,6 +51,7 @@ struct MultiPass {      // the batched pass over device slots: row b = slot slot
     const int32_t* tables; float* lc_scratch; float *xm_inv, *xm_tmax;      // device
     const int32_t *slots, *pos, *runs; int nruns;                           // device
     bool verify;      // kr_decode_verify_multi's pass: linear-attention layers record instead of storing state (docs/design/18-multi-verify.md)
+    KrMultiFdShare fds;      // "multi_attn_fast_paged" = 2: the pass's item list (device; n_items 0: none), one for every GQA layer (docs/design/44-multi-attn-fast-share.md)
     const int32_t* table(KrMpSpan sp) const { return sp.off < 0 ? nullptr : tables + sp.off; }
 };
 struct Chunk {      // one chunk of the prompt in flight: its arena, stream and running flags
@@ -252,9 +254,9 @@ static int run_layer(kr_decode_store* s, Chunk& cx, size_t li) {
             if (oc != L.nh * L.hd) return kr_fail(KR_ERR_VALUE, "o_proj cols %d != nh*hd", oc);
             const KrMultiGqaArgs m = multi_gqa_args(s, li, B, P);
             if (P.plan.gqa_runs == KR_MP_RUNS_XM) {      // "multi_extend_exact_mfma": the runs of >= 2 tokens take the three exact matrix-core passes, the per-row kernels the first nruns rows
-                if (kr_launch_multi_gqa_xm(m, multi_xm_args(P, L.nh, L.nkv), P.runs, P.nruns, P.plan.n_unit, Cc, st))
+                if (kr_launch_multi_gqa_xm(m, multi_xm_args(P, L.nh, L.nkv), P.runs, P.nruns, P.plan.n_unit, Cc, st, &P.fds))
                     return kr_fail(KR_ERR_VALUE, "multi_extend_exact_mfma: unsupported GQA geometry for the multi-sequence step (nh %d nkv %d head_dim %d)", L.nh, L.nkv, L.hd);
-            } else if (kr_launch_multi_gqa(m, Cc, st)) return kr_fail(KR_ERR_VALUE, "unsupported GQA geometry for the multi-sequence step");
+            } else if (kr_launch_multi_gqa(m, Cc, st, &P.fds)) return kr_fail(KR_ERR_VALUE, "unsupported GQA geometry for the multi-sequence step");
         } else {
             KrPfmGqaArgs a{};
             a.q_in = B.pa; a.k_in = B.pb; a.v_in = B.pc; a.ld_q = nq; a.ld_k = nk_; a.ld_v = nv_;
@@ -919,7 +921,7 @@ extern "C" int kr_decode_commit(kr_decode_store* s, int n_keep) {
 // kr_decode_multi_path_counts: one batched pass that was queued, by the values the sections of run_layer branch on -- the plan, the pass's few-row flag, the
 // GGUF bits of the store.  The position split is counted where its three launches exist: the launchers (kr_multi.hip) give flash-decode rows the flash-decode
 // kernels whatever the flag says, and under the flash or matrix-core run forms they launch the per-row attention for the unit rows only.  Host only
-static void multi_path_count(kr_decode_store* s, const KrMultiPlan& pl, bool verify, bool few) {
+static void multi_path_count(kr_decode_store* s, const KrMultiPlan& pl, bool verify, bool few, bool shared) {
     int64_t* c = s->path_counts;
     c[KR_MPC_PASSES]++; c[KR_MPC_VERIFY] += verify; c[KR_MPC_FEW] += few;
     c[KR_MPC_XS_SPLIT] += pl.xs_split && !pl.fd_chunks && (pl.gqa_runs == KR_MP_RUNS_ROWS || pl.n_unit > 0);
@@ -929,6 +931,7 @@ static void multi_path_count(kr_decode_store* s, const KrMultiPlan& pl, bool ver
     c[KR_MPC_FD] += pl.fd_chunks > 0; c[KR_MPC_MLA_FD] += pl.mla_chunks > 0;
     c[KR_MPC_GQA_FLASH] += pl.gqa_runs == KR_MP_RUNS_FLASH; c[KR_MPC_MLA_FLASH] += pl.mla_runs == KR_MP_RUNS_FLASH; c[KR_MPC_LC] += pl.lc_nruns > 0;
     c[KR_MPC_RUNS] += pl.any_run;
+    c[KR_MPC_FD_SHARED] += shared;
     if (has_gguf_moe(s) && (gguf_exact_bits(s) & KR_PF_SET_GGUF_EXACT)) { c[KR_MPC_GGUF_EXACT]++; c[KR_MPC_GGUF_GROUPED] += !(gguf_exact_bits(s) & KR_PF_SET_GGUF_STREAM); c[KR_MPC_GGUF_GROUPED_SCALAR] += gguf_grouped_scalar(s); }
 }
 extern "C" int kr_decode_multi_path_counts(kr_decode_store* s, int64_t* out, int n, int reset) {
@@ -938,8 +941,46 @@ extern "C" int kr_decode_multi_path_counts(kr_decode_store* s, int64_t* out, int
     return KR_OK;
 }
 
+// "multi_attn_fast_paged" = 2 (docs/design/44-multi-attn-fast-share.md): the item list of the pass's flash-decode rows (kr_fd_share.h) -> the device, one asynchronous
+// copy from the slot set's pinned buffer ahead of the pass.  The callers have mapped every page the rows read and given every row a page of its own where it
+// writes (pg_reserve_rows), so the host table is what the device copy will hold when the attention launches run.  h_rows = [slots | tokens | positions] of the n
+// pass rows on the host.  The per-row kernels see all n rows, or under the matrix-core run passes the first n_final, those of a run of >= 2 tokens leaving at
+// once; the flash run kernels' passes keep the one-row kernel.  One list serves every GQA layer: it is cut for the layer with the most heads per KV head.
+// fds.n_items stays 0 where nothing can share: the pass is then the pass of value 1
+static int multi_fd_share(kr_decode_store* s, const KrMultiPlan& plan, int n, int n_final, const int32_t* h_counts, const int32_t* h_rows, hipStream_t st, KrMultiFdShare& fds) {
+    kr_multi_state& M = *s->multi;
+    if (s->mopt.attn_fast_paged != 2 || !plan.fd_chunks || !h_rows || plan.gqa_runs == KR_MP_RUNS_FLASH) return KR_OK;
+    int width = KR_FDS_MAX_ROWS;
+    for (const DLayer& L : s->layers) if (L.attn == ATTN_GQA) width = std::min(width, kr_fd_share_width(L.nh / L.nkv));
+    const bool runs = plan.gqa_runs == KR_MP_RUNS_XM;
+    std::vector<int32_t> in_run;
+    if (runs) for (int i = 0; i < n_final; i++) in_run.push_back(h_counts[i] >= 2);
+    const KrFdShareRows rows{runs ? n_final : n, h_rows, h_rows + 2 * (size_t)n, runs ? in_run.data() : nullptr, M.pg.paged() ? M.pg.table.data() : nullptr, M.pg.stride, M.pg.shift};
+    std::vector<int32_t> items;
+    const int n_items = kr_fd_share_build(rows, plan.fd_chunk, width, items);
+    if (!n_items) return KR_OK;
+    if (!M.fds_ready) {
+        for (const DLayer& L : s->layers)
+            if (L.attn == ATTN_GQA && kr_multi_fd_share_prepare(L.hd, M.kv_fp8, M.pg.paged()))
+                return kr_fail(KR_ERR_HIP, "multi_attn_fast_paged: LDS window of the grouped flash-decode kernel refused (head_dim %d)", L.hd);
+        M.fds_ready = true;
+    }
+    const size_t bytes = items.size() * 4;
+    if (bytes > M.fds_cap) {      // every call on the slots returns with its stream idle: no copy still reads the old buffer
+        if (M.fds_pinned) { (void)hipHostFree(M.fds_pinned); M.fds_pinned = nullptr; M.fds_cap = 0; }
+        const size_t cap = std::max(bytes * 2, (size_t)65536);
+        KR_HIP(hipHostMalloc((void**)&M.fds_pinned, cap, hipHostMallocDefault));
+        M.fds_cap = cap;
+    }
+    if (M.fds_items.ensure(M.fds_cap)) return kr_fail(KR_ERR_HIP, "hipMalloc of the multi-sequence pass's flash-decode item list failed");
+    memcpy(M.fds_pinned, items.data(), bytes);
+    KR_HIP(hipMemcpyAsync(M.fds_items.p, M.fds_pinned, bytes, hipMemcpyHostToDevice, st));
+    fds = KrMultiFdShare{(const int*)M.fds_items.p, n_items, width};
+    return KR_OK;
+}
+
 int kr_multi_pass(kr_decode_store* s, int n, int n_final, const int32_t* d_rows, const int32_t* d_runs, int max_pos, hipStream_t st, bool verify,
-                  const int32_t* h_counts, const int32_t* h_positions) {
+                  const int32_t* h_counts, const int32_t* h_positions, const int32_t* h_rows) {
     kr_multi_state& M = *s->multi;
     PfLayout Lo;
     if (int rc = pf_layout(s, (size_t)n, true, true, st, Lo)) return rc;
@@ -982,8 +1023,10 @@ int kr_multi_pass(kr_decode_store* s, int n, int n_final, const int32_t* d_rows,
         if (M.tiles.ensure(std::max(plan.tables.size() * 4, (size_t)65536))) return kr_fail(KR_ERR_HIP, "hipMalloc of the multi-sequence pass's query tiles failed");
         KR_HIP(hipMemcpyAsync(M.tiles.p, plan.tables.data(), plan.tables.size() * 4, hipMemcpyHostToDevice, st));      // pageable source: staged before the call returns
     }
+    KrMultiFdShare fds{nullptr, 0, 0};
+    if (int rc = multi_fd_share(s, plan, n, n_final, h_counts, h_rows, st, fds)) return rc;
     const MultiPass mp{plan, (const int32_t*)M.tiles.p, (float*)M.lc_scratch.p, (float*)M.xm_rows.p, (float*)((char*)M.xm_rows.p + plan.xm_inv_bytes),
-                       d_rows, d_rows + 2 * n, d_runs, n_final, verify};
+                       d_rows, d_rows + 2 * n, d_runs, n_final, verify, fds};
     Chunk cx{};
     const bool few = pass_few_rows(s, n);
     cx.B = pf_carve(Lo, (char*)M.scratch.p); cx.B.H = s->hidden; cx.B.few = few; cx.B.few_group = s->opt_pass_few_rows_group; cx.scores = nullptr; cx.tok = d_rows + n; cx.Cc = n; cx.pos0 = 0; cx.set = KR_PF_MAX_DEPTH - 1;
@@ -992,6 +1035,6 @@ int kr_multi_pass(kr_decode_store* s, int n, int n_final, const int32_t* d_rows,
         if (int rc = run_layer(s, cx, l)) return rc;
     cx.Cc = plan.n_logits;
     if (int rc = final_rows(s, cx, (float*)M.logits.p)) return rc;
-    multi_path_count(s, plan, mp.verify, few);
+    multi_path_count(s, plan, mp.verify, few, fds.n_items > 0);
     return KR_OK;
 }

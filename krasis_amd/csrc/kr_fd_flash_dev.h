@@ -34,9 +34,14 @@ __device__ __forceinline__ int fa_vslot(int pp) { return (pp & ~6) | ((pp & 2) <
 // kr_slot_row (kr_slot_cache.h) of them.  A tile of FA_TK positions starts at a multiple of FA_TK, so it lies in one page, or in two at 32
 // positions per page: the two page ids are workgroup-uniform and their byte offsets stay in scalar registers; a lane adds its row's offset inside the page.
 // Only the three cache addresses differ from the flat instantiation: the order of every operation is the same.
-template <int HD, bool FP8, bool PAGED = false>
+// SHARE (docs/design/44-multi-attn-fast-share.md): the 32 columns hold the G heads of up to 32 / G ROWS of a batched pass that read the same cache rows for
+// this chunk: column n31 = (row share_rows[n31 / G], head n31 % G), live while n31 / G < n_share.  q_heads, fd_o and fd_ml are then the pass's buffers, a row b at
+// b * nh * HD, b * nh * n_chunks * HD and b * nh * n_chunks * 2, inside as above.  share_rows is workgroup-uniform: its loads are scalar.  Every per-column
+// quantity below depends on its column alone, so a column carries the bits it carries in a workgroup of its own; only the three addresses of a column differ
+template <int HD, bool FP8, bool PAGED = false, bool SHARE = false>
 __device__ __forceinline__ void kr_fd_flash_body(int seq, int c, int kvh, const float* q_heads, const void* k_cache, const void* v_cache, float* fd_o, float* fd_ml,
-                                                 int nh, int nkv, float sm_scale, int n_chunks, int chunk, const int* ptab = nullptr, int psh = 0) {
+                                                 int nh, int nkv, float sm_scale, int n_chunks, int chunk, const int* ptab = nullptr, int psh = 0, const int* share_rows = nullptr,
+                                                 int n_share = 0) {
     constexpr int KSTEPS = HD / 16, DB = HD / 32, DBW = DB >= 4 ? DB / 4 : 1, LDK = HD * 2 + 16, LDV = FA_TK * 2 + 16;
     constexpr int CPR = FP8 ? HD / 16 : HD / 8, KCH = FA_TK * CPR / 256, VUN = (FA_TK / 2) * CPR, VPT = (VUN + 255) / 256;
     extern __shared__ __attribute__((aligned(16))) char fa_smem[];
@@ -46,12 +51,21 @@ __device__ __forceinline__ void kr_fd_flash_body(int seq, int c, int kvh, const 
     const int pbeg = c * chunk;
     if (pbeg >= seq) return;
     const int pend = min(seq, pbeg + chunk), n_tiles = (pend - pbeg + FA_TK - 1) / FA_TK;
-    const bool row_ok = n31 < G;
-    const int h = kvh * G + (row_ok ? n31 : 0);
+    const bool row_ok = SHARE ? n31 / G < n_share : n31 < G;
+    const int hg = SHARE ? n31 % G : n31;      // the column's head inside the group
+    const int h = kvh * G + (row_ok ? hg : 0);
+    [[maybe_unused]] size_t rb = 0;              // SHARE: the column's row of the pass (a dead column: any row of the item)
+    if constexpr (SHARE) {
+        int b = share_rows[0];
+#pragma unroll
+        for (int i = 1; i < 8; i++) if (n31 / G == i) b = share_rows[i];
+        rb = (size_t)b;
+    }
     const int kvs = nkv * HD, esz = FP8 ? 1 : 2;
     v8h qf[KSTEPS];
     {
         const float* q = q_heads + (size_t)h * HD + 8 * khalf;
+        if constexpr (SHARE) q += rb * nh * HD;
         const float sc = sm_scale * 1.4426950408889634f;
 #pragma unroll
         for (int ks = 0; ks < KSTEPS; ks++) {
@@ -212,7 +226,8 @@ __device__ __forceinline__ void kr_fd_flash_body(int seq, int c, int kvh, const 
     }
     // ---- partials: accumulator rows 4 g4 .. 4 g4 + 3 of block db are dims 32 (wave DBW + db) + 8 g4 + 4 khalf + 0..3, column = head n31
     if (row_ok) {
-        float* po = fd_o + (((size_t)kvh * n_chunks + c) * G + n31) * HD;
+        float* po = fd_o + (((size_t)kvh * n_chunks + c) * G + hg) * HD;
+        if constexpr (SHARE) po += rb * nh * n_chunks * HD;
         if (wave * DBW < DB) {
 #pragma unroll
             for (int db = 0; db < DBW; db++)
@@ -221,7 +236,11 @@ __device__ __forceinline__ void kr_fd_flash_body(int seq, int c, int kvh, const 
                     *reinterpret_cast<float4*>(po + 32 * (wave * DBW + db) + 8 * g4 + 4 * khalf) =
                         make_float4(oacc[db][4 * g4], oacc[db][4 * g4 + 1], oacc[db][4 * g4 + 2], oacc[db][4 * g4 + 3]);
         }
-        if (wave == 0 && khalf == 0) { float* ml = fd_ml + ((size_t)(kvh * G + n31) * n_chunks + c) * 2; ml[0] = m_run; ml[1] = l_run; }
+        if (wave == 0 && khalf == 0) {
+            float* ml = fd_ml + ((size_t)(kvh * G + hg) * n_chunks + c) * 2;
+            if constexpr (SHARE) ml += rb * nh * n_chunks * 2;
+            ml[0] = m_run; ml[1] = l_run;
+        }
     }
 }
 

@@ -103,7 +103,10 @@ struct KrMultiGqaArgs {
 // row b < pf_nruns is the last token of a run of >= 2 tokens: not a row of the per-row attention kernels (workgroup-uniform; false whenever pf_runs is null)
 __device__ __forceinline__ bool kr_m_row_in_run(const KrMultiGqaArgs& a, int b) { return a.pf_runs && a.pf_runs[3 * b + 2] >= 2; }
 // 0: launched; 1: geometry not covered (hd 64 / 128 / 256, nh % nkv == 0), or the dynamic LDS below is over KR_MULTI_GQA_LDS_MAX
-int kr_launch_multi_gqa(const KrMultiGqaArgs& a, int B, hipStream_t st);
+// sh (optional, "multi_attn_fast_paged" = 2): a non-empty item list gives the flash-decode rows the grouped chunk kernel; the run kernels' passes
+// ("multi_extend_flash") keep the one-row kernel for their unit rows
+struct KrMultiFdShare;
+int kr_launch_multi_gqa(const KrMultiGqaArgs& a, int B, hipStream_t st, const KrMultiFdShare* sh = nullptr);
 // "multi_attn_exact_split": the three launches over the first `rows` rows of the pass (after the prep launch), in place of the exact per-slot attention kernel over
 // those rows; the rows of runs of >= 2 tokens leave at once as they do there.  0: launched; 1: geometry not covered (what kr_launch_multi_gqa checks)
 int kr_launch_multi_gqa_split(const KrMultiGqaArgs& a, int rows, hipStream_t st);
@@ -122,7 +125,7 @@ struct KrMultiXmArgs { const int* tiles_a; const int* tiles_c; int n_a, n_c; flo
 // set -- over the first n_runs rows when units > 0 (the rows of longer runs leave at once), then passes A, B and C.  runs = the pass's run table, n_runs x [slot,
 // off, cnt]; units = its runs of one token; a.pf_* as the caller left them (null / 0): the launcher sets them on its copy.  a.scores covers all B rows at a.sc_ld, a
 // multiple of 64 above the pass's largest position.  0: launched; 1: something not covered, nothing queued
-int kr_launch_multi_gqa_xm(const KrMultiGqaArgs& a, const KrMultiXmArgs& x, const int* runs, int n_runs, int units, int B, hipStream_t st);
+int kr_launch_multi_gqa_xm(const KrMultiGqaArgs& a, const KrMultiXmArgs& x, const int* runs, int n_runs, int units, int B, hipStream_t st, const KrMultiFdShare* sh = nullptr);
 int kr_multi_xm_args_ok(const KrMultiGqaArgs& a, const KrMultiXmArgs& x);      // what kr_launch_multi_xm checks (a.pf_runs set, a.pf_tiles null)
 int kr_launch_multi_xm(const KrMultiGqaArgs& a, const KrMultiXmArgs& x, int B, hipStream_t st);      // passes A, B, C alone (after the prep launch)
 void kr_launch_multi_xm_softmax(const KrMultiGqaArgs& a, const KrMultiXmArgs& x, int B, hipStream_t st);      // pass B alone: what kr_launch_multi_xm launches second
@@ -136,6 +139,13 @@ size_t kr_multi_gqa_lds_bytes(int G, int hd, int page_stride);
 int kr_multi_fd_ok(int nh, int nkv, int hd);
 int kr_multi_fd_prepare(int hd, int fp8, int paged);
 int kr_launch_multi_fd(const KrMultiGqaArgs& a, int B, int n_chunks, hipStream_t st);
+// "multi_attn_fast_paged" = 2 (kr_multi_flash_share.hip, docs/design/44-multi-attn-fast-share.md): the pass's item list on the device, n_items x [c, n_rows, rows[8]]
+// (kr_fd_share.h), cut for at most `width` rows per item.  What the grouped chunk pass needs beside KrMultiGqaArgs travels here (that struct does not grow).  The
+// launch: the grouped chunk kernel over (n_items, nkv) in place of the one-row chunk kernel, then the same merge over B rows; a layer with more heads per KV
+// head than the list was cut for is refused (1), nothing queued.  The LDS window of its kernels: once per slot set, outside the pass; non-zero = refused
+struct KrMultiFdShare { const int* items; int n_items, width; };
+int kr_multi_fd_share_prepare(int hd, int fp8, int paged);
+int kr_launch_multi_fd_share(const KrMultiGqaArgs& a, const KrMultiFdShare& sh, int B, int n_chunks, hipStream_t st);
 
 // MLA, one token per row: rope of q_pe, latent RMSNorm + rope of k_pe, both rows appended to the row's slot, attention over the slot's rows [0, pos]
 // in the latent space, w_kc absorption before and w_vc projection after (the row-wise launches of the prompt pass)

@@ -388,7 +388,7 @@ size_t kr_multi_gqa_lds_bytes(int G, int hd, int page_stride) {
 }
 
 static int multi_gqa_runs(const KrMultiGqaArgs& a, int B, size_t lds, hipStream_t st);      // below
-int kr_launch_multi_gqa(const KrMultiGqaArgs& a, int B, hipStream_t st) {
+int kr_launch_multi_gqa(const KrMultiGqaArgs& a, int B, hipStream_t st, const KrMultiFdShare* sh) {
     if ((a.hd != 64 && a.hd != 128 && a.hd != 256) || a.nkv < 1 || a.nh % a.nkv || a.sc_ld % 32 || !kr_slot_stage_fits(a.kv.pg, 32)) return 1;
     const int G = a.nh / a.nkv;
     const size_t lds = kr_multi_gqa_lds_bytes(G, a.hd, a.kv.pg.table ? a.kv.pg.stride : 0);
@@ -398,6 +398,7 @@ int kr_launch_multi_gqa(const KrMultiGqaArgs& a, int B, hipStream_t st) {
         if (!kr_multi_fd_ok(a.nh, a.nkv, a.hd) || !a.fd_ml || a.fd_chunks < 1 || a.fd_chunks > 1024) return 1;
         if (a.kv.pg.table) hipLaunchKernelGGL(kr_multi_gqa_prep_kernel<true>, dim3(a.nh + a.nkv, B), dim3(256), 0, st, a);
         else hipLaunchKernelGGL(kr_multi_gqa_prep_kernel<false>, dim3(a.nh + a.nkv, B), dim3(256), 0, st, a);
+        if (sh && sh->n_items) return kr_launch_multi_fd_share(a, *sh, B, a.fd_chunks, st);      // "multi_attn_fast_paged" = 2: rows that share cache rows share a workgroup (kr_multi_flash_share.hip)
         return kr_launch_multi_fd(a, B, a.fd_chunks, st);
     }
     if (lds > KR_MULTI_GQA_LDS_MAX) return 1;
@@ -447,7 +448,7 @@ static int multi_gqa_runs(const KrMultiGqaArgs& a, int B, size_t lds, hipStream_
 // "multi_extend_exact_mfma", a non-verify pass with a run of >= 2 tokens (docs/design/28-multi-extend-exact-mfma.md): the prep launch over all B rows as ever; the
 // per-row attention kernels over the first n_runs rows, where every unit row lies (kr_m_row_in_run: the rows of longer runs leave at once), and not at all without
 // a unit row; then the three exact passes over the runs' query tiles (kr_multi_xm.hip).  pf_tiles stays null: kr_launch_multi_gqa never comes here by itself
-int kr_launch_multi_gqa_xm(const KrMultiGqaArgs& a0, const KrMultiXmArgs& x, const int* runs, int n_runs, int units, int B, hipStream_t st) {
+int kr_launch_multi_gqa_xm(const KrMultiGqaArgs& a0, const KrMultiXmArgs& x, const int* runs, int n_runs, int units, int B, hipStream_t st, const KrMultiFdShare* sh) {
     KrMultiGqaArgs a = a0;
     a.pf_runs = runs; a.pf_nruns = n_runs; a.pf_units = units; a.pf_tiles = nullptr; a.pf_ntiles = 0;
     // every check first: the prep launch appends rows to the slots, and a layer fails whole
@@ -460,7 +461,7 @@ int kr_launch_multi_gqa_xm(const KrMultiGqaArgs& a0, const KrMultiXmArgs& x, con
     else hipLaunchKernelGGL(kr_multi_gqa_prep_kernel<false>, dim3(a.nh + a.nkv, B), dim3(256), 0, st, a);
     if (units) {
         if (a.fd_o) {
-            if (kr_launch_multi_fd(a, n_runs, a.fd_chunks, st)) return 1;
+            if (sh && sh->n_items ? kr_launch_multi_fd_share(a, *sh, n_runs, a.fd_chunks, st) : kr_launch_multi_fd(a, n_runs, a.fd_chunks, st)) return 1;
         } else if (a.xs_split) {      // "multi_attn_exact_split": the unit rows' attention as three launches
             if (kr_launch_multi_gqa_split(a, n_runs, st)) return 1;
         } else {

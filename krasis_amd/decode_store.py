@@ -326,6 +326,9 @@ class CpuDecodeStore:
         "multi_attn_fast" alone reads flat slots only and is refused on paged ones; "multi_attn_fast_paged" (default 0) is the same option for both
         kinds: on paged slots the flash-decode reads the page pool through the slots' tables, row i bit-identical to the same call on flat slots
         under "multi_attn_fast"; on flat slots it is "multi_attn_fast"; with both set it governs (docs/design/23-multi-attn-fast-paged.md).
+        "multi_attn_fast_paged" = 2: that, and rows of a pass that read the same cache rows for a full chunk (slots forked from one prefix, the token
+        rows of one slot in verify_multi) share a workgroup of the chunk pass -- the bits of value 1 from fewer tile loads; multi_path_counts()
+        ["fd_shared"] counts the passes that held such a group (docs/design/44-multi-attn-fast-share.md).
         "multi_mla_fast" (default 0): the counterpart for MLA layers, one option for flat and paged slots -- with 1 the MLA layers of every batched call
         run split-KV flash-decode over slots of max_seq > 512, row i bit-identical to decode_step under set_attention_mode(True) on that sequence alone;
         shorter slots keep the exact step; GQA and linear-attention layers are untouched; a store without MLA layers, or an MLA layer of more than 64
@@ -532,7 +535,8 @@ class CpuDecodeStore:
         With page_tokens and n_pages (kr_decode_slots_create_paged, docs/design/21-paged-slots.md) the GQA / MLA rows live in a pool of n_pages pages of
         page_tokens positions (a power of two, at least 32) shared by all slots: same results bit for bit, capacity bounded by the pool; a call that
         needs more pages than are free fails with KR_ERR_STATE and changes nothing.  Of the two split-KV options, paged slots take
-        "multi_attn_fast_paged"; "multi_attn_fast" alone is refused on them (set_option).  "multi_mla_fast", the split-KV option of MLA layers, reads flat
+        "multi_attn_fast_paged"; "multi_attn_fast" alone is refused on them (set_option); "multi_attn_fast_paged" = 2 also lets slots that share
+        pages (fork_slot) share the flash-decode's tile loads.  "multi_mla_fast", the split-KV option of MLA layers, reads flat
         and paged slots alike (over slots of max_seq > 512)."""
         self._need()
         if (page_tokens is None) != (n_pages is None):
@@ -650,7 +654,8 @@ class CpuDecodeStore:
         (logits, id, the KV row -- or MLA latent and rope-key rows -- it appends to the slot).  Returns the greedy ids, or (ids, logits f32 [n, vocab]) with logits=True.
         After set_option("multi_attn_fast", 1), over slots of max_seq > 1024: row i is bit-identical to decode_step under set_attention_mode(True) on that
         sequence alone instead (GQA attention as split-KV flash-decode; logits within 1e-3 of the exact step relative to their largest magnitude).
-        On paged slots that takes set_option("multi_attn_fast_paged", 1), which gives the same bits through the page table.
+        On paged slots that takes set_option("multi_attn_fast_paged", 1), which gives the same bits through the page table.  With "multi_attn_fast_paged" = 2
+        rows that read the same cache rows for a full chunk (forked slots, flat or paged token rows of one slot) share a workgroup: the same bits again.
         After set_option("multi_mla_fast", 1), over flat or paged slots of max_seq > 512, the same holds for MLA layers: their attention runs as split-KV
         flash-decode and row i is bit-identical to decode_step under set_attention_mode(True) on that sequence alone (logits within 3e-3 of the exact
         step with FP16 caches, 5e-3 with E4M3, relative to their largest magnitude)."""
@@ -823,7 +828,7 @@ class CpuDecodeStore:
 
     MULTI_PATH_COUNTS = ("passes", "verify", "few", "xs_split", "mla_xs_split", "gqa_xm", "mla_xm", "lx", "lx_runs", "lx_short", "fd", "mla_fd",
                          "gqa_flash", "mla_flash", "lc", "runs", "gguf_exact", "gguf_grouped", "seq_passes", "seq_few",
-                         "gguf_grouped_scalar")      # KR_MPC_* of krasis_hip.h, in order
+                         "gguf_grouped_scalar", "fd_shared")      # KR_MPC_* of krasis_hip.h, in order
 
     def multi_path_counts(self, reset: bool = False) -> dict:
         """kr_decode_multi_path_counts (test aid): which forms the multi-row passes of this store took so far -- host-side counters, one count per batched
