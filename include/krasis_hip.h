@@ -98,19 +98,19 @@ int kr_upload_expert_bf16(kr_engine* e, int layer, int expert, int inter, const 
  * words and bf16 scales in [0.005,0.05] -- the distribution of bench_decode_synthetic (decode.rs:4379-4392),
  * generated by a counter hash on the GPU instead of one serial xorshift stream. */
 int kr_fill_layer_synthetic(kr_engine* e, int layer, int bits, uint64_t seed);
-/* the native-GGUF twin: every routed expert of the layer as Q4_K (12) / Q8_0 (8) / Q5_0 (6) / Q6_K (14) blocks with the block distribution SURVEY 8d defines
+/* the native-GGUF twin: every routed expert of the layer as Q4_K (12) / Q5_K (13: Q4_K's rule with d halved) / Q8_0 (8) / Q5_0 (6) / Q6_K (14) blocks with the block distribution SURVEY 8d defines
  * (raw quant / scale bytes, d = f16((0.005 + u * 0.045) / 63), dmin = f16(8 d); Q8_0: d = f16((0.005 + u * 0.045) / 127); Q5_0: d = f16((0.005 + u * 0.045) / 15);
  * Q6_K: d = f16((0.005 + u * 0.045) / 31 / 127)) */
 int kr_fill_layer_synthetic_gguf(kr_engine* e, int layer, int gate_up_type, int down_type, uint64_t seed);
-/* The Q5_0 (6) / Q6_K (14) kernels as a stand-alone operator: y[N] = W x for N rows of raw row-major GGUF blocks and an f32 vector x[K], all host pointers;
- * K a multiple of the block size (32 / 256), at most 15360; any N >= 1.  parts 0: the reference's serial f32 chain per row (gguf_kernels.rs:572-635), bit for
- * bit what the exact MoE kernels compute for such a matrix.  parts 1 | 2: the tolerance tile of KR_DECODE_FAST (8 lanes per row, the reference's terms,
+/* The Q5_0 (6) / Q5_K (13) / Q6_K (14) kernels as a stand-alone operator: y[N] = W x for N rows of raw row-major GGUF blocks and an f32 vector x[K], all host pointers;
+ * K a multiple of the block size (32 / 256 / 256), at most 15360; any N >= 1.  parts 0: the reference's serial f32 chain per row (gguf_kernels.rs:572-635; Q5_K: its
+ * scalar Q4_K row, :495-532, over dequant_q5_k's values, docs/design/45-gguf-q5k.md), bit for bit what the exact MoE kernels compute for such a matrix.  parts 1 | 2: the tolerance tile of KR_DECODE_FAST (8 lanes per row, the reference's terms,
  * tree-ordered sums) over the whole row, or over two slices of its blocks whose results are added -- what the two k-waves of the mode's gate|up launch do.
  * Re-tiles into a scratch matrix, one launch, copies back; keeps no state on the engine.  Anything else: KR_ERR_VALUE. */
 int kr_gguf_matvec(kr_engine* e, int type, const uint8_t* blocks, int N, int K, const float* x, float* y, int parts);
 /* The grouped Q5_0 (6) / Q6_K (14) kernel of the exact pass ("gguf_exact_grouped_scalar") as a stand-alone operator: y[M][N] = x[M][K] W^T for N rows of raw
  * row-major GGUF blocks and M f32 rows, all host pointers.  The rows go through the kernel in groups of 8 (M = 11: a group of 8 and a group of 3); every
- * y[m][n] carries the bits of kr_gguf_matvec(parts 0) on row m alone, whatever shares its group.  Refuses what kr_gguf_matvec refuses, and M < 1, with
+ * y[m][n] carries the bits of kr_gguf_matvec(parts 0) on row m alone, whatever shares its group.  Refuses what kr_gguf_matvec refuses, Q5_K (13: no grouped form) and M < 1, with
  * KR_ERR_VALUE.  Re-tiles into a scratch matrix and copies back; keeps no state on the engine. */
 int kr_gguf_matmul_rows(kr_engine* e, int type, const uint8_t* blocks, int N, int K, const float* x, int M, float* y);
 /* Read one expert back in the reference layout (inverse re-tiling); used by parity tests at full size. */

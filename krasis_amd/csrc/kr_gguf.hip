@@ -1,5 +1,5 @@
 // kr_gguf.hip -- native GGUF block experts on gfx950: Q4_K / Q8_0 / Q4_0 with INT16 activations (exact integer dots),
-// Q5_0 / Q6_K through the reference's scalar f32 form.  Replaces src/gguf_kernels.rs (matvec_q4_k_avx2 :271, matvec_q8_0_avx2 :379,
+// Q5_0 / Q6_K through the reference's scalar f32 form, Q5_K through the same form over dequant_q5_k's values (gguf.rs:740).  Replaces src/gguf_kernels.rs (matvec_q4_k_avx2 :271, matvec_q8_0_avx2 :379,
 // matvec_q4_0_avx2 :436, scalar fallbacks :495-635, quantize_*_to_int16 :110-172, expert_forward_gguf :690) and moe_forward_gguf
 // (src/moe.rs:990) bit for bit: the 8 AVX lanes of a row are 8 GPU lanes that see exactly the bytes their AVX twin sees
 // (bytes {2l, 2l+1, 16+2l, 16+2l+1} of every 32-byte chunk), run the same per-sub-block fma chain and the same hsum tree.
@@ -7,6 +7,9 @@
 // HBM layout (built at upload from the raw row-major GGUF blocks, kr_engine.cpp::retile_gguf; one copy, nothing keeps the raw blocks):
 //   Q4_K  q[rows/8][blocks][8 rows][8 lanes] x 16 B  : lane record = 4 chunks j x bytes {qs[32j+2l], qs[32j+2l+1], qs[32j+16+2l], qs[32j+17+2l]}
 //         h[rows/8][blocks][8 rows] x 16 B           : {f16 d, f16 dmin, 12 scale bytes}
+//   Q5_K  q as Q4_K, unchanged (low nibbles of chunk j = elements 64j + p, high nibbles = elements 64j + 32 + p, p = the byte's position in the 32-byte chunk)
+//         h[rows/8][blocks][8 rows] x 48 B           : Q4_K's 16 B, then eight u32, one per lane l: {qh[2l], qh[2l+1], qh[16+2l], qh[17+2l]} -- byte i carries the fifth
+//         bits of byte i of every chunk of lane l's record: bit 2j for the low nibble, bit 2j + 1 for the high nibble.  176 B per block, as in the file
 //   Q8_0  q[rows/8][blocks/4][8][8] x 16 B (4 blocks x 4 bytes), h[rows/8][blocks/4][8] x 8 B (4 x f16 d)
 //   Q4_0  q[rows/8][blocks/8][8][8] x 16 B (8 blocks x 2 bytes), h[rows/8][blocks/8][8] x 16 B (8 x f16 d)
 //   Q5_0  q as Q4_0: lane l's record of a group of 8 blocks = 8 x bytes {qs[2l], qs[2l+1]}, the nibbles of elements {2l, 2l+1, 16+2l, 17+2l}
@@ -16,7 +19,8 @@
 //         h[rows/8][blocks][8 rows] x 20 B           : {16 scale bytes, f16 d, 2 bytes of padding}
 //   Who reads what (Q5_0 / Q6_K): a wave of the tolerance tiles (kr_gguf_dev.h: 8 rows x 8 lanes) reads 1024 B (Q5_0, per block group) / 768 B (Q6_K, per block and
 //   half) of contiguous records; the one lane per row of the exact kernel below finds its row's eight lane records side by side -- 128 B per Q5_0 block group, and
-//   for Q6_K the 96 B of half 0, then 768 B further the 96 B of half 1 -- and reads them with 16-byte loads.
+//   for Q6_K the 96 B of half 0, then 768 B further the 96 B of half 1 -- and reads them with 16-byte loads.  Q5_K: a wave reads the 1024 B of a block's records and,
+//   per lane, the 16 B head and one fifth-bit word of its row's header; the one lane reads 128 B of records and the 48 B header in three 16-byte loads.
 #include "kr_gguf_dev.h"
 
 // ---- scalar f32 rows (gguf_kernels.rs:572-635): one lane per row walks the reference's serial chain -- the same terms in the same order, mul, mul, add, no
@@ -115,12 +119,62 @@ __device__ __forceinline__ float gg_row_q6k(const GgMat& m, int r, const float* 
     }
     return sum;
 }
-__device__ __forceinline__ float gg_row_scalar(const GgMat& m, int r, const float* x) { return m.type == GG_Q6_K ? gg_row_q6k(m, r, x) : gg_row_q5_0(m, r, x); }
+// Q5_K: the reference's scalar Q4_K row (q4_k_block_dot_scalar / matvec_q4_k_scalar, gguf_kernels.rs:495-532) over dequant_q5_k's values (gguf.rs:740-803): per
+// super-block s = 0, s += ((d sc_j) q - (dmin mn_j)) x_k for k = 0 .. 255 in element order, then sum += s.  Element 64j + 32 hi + p sits in record (p & 15) >> 1, word j,
+// byte (p & 1) + 2 (p >> 4), nibble hi; its fifth bit is bit 2j + hi of the same byte of that record's header word.
+#define GG_PFR5K 2
+__device__ __forceinline__ float gg_row_q5k(const GgMat& m, int r, const float* x) {
+    const int tile = r >> 3, row = r & 7, nb = m.K / 256;
+    const u32x4* q = reinterpret_cast<const u32x4*>(m.q) + ((size_t)tile * nb * 8 + row) * 8;                // the row's eight lane records of a block side by side
+    const u32x4* h = reinterpret_cast<const u32x4*>(m.h) + ((size_t)tile * nb * 8 + row) * 3;
+    float sum = 0.0f;
+    for (int b0 = 0; b0 < nb; b0 += GG_PFR5K) {
+        u32x4 wv[GG_PFR5K][8], hv[GG_PFR5K][3];
+#pragma unroll
+        for (int u = 0; u < GG_PFR5K; u++) {
+            const int bb = b0 + u < nb ? b0 + u : nb - 1;
+#pragma unroll
+            for (int l = 0; l < 8; l++) wv[u][l] = kr_ldg_nt(q + (size_t)bb * 64 + l);
+#pragma unroll
+            for (int i = 0; i < 3; i++) hv[u][i] = kr_ldg_nt(h + (size_t)bb * 24 + i);
+        }
+#pragma unroll
+        for (int u = 0; u < GG_PFR5K; u++) {
+            const int b = b0 + u;
+            if (b < nb) {
+                uint32_t w[8][4];
+#pragma unroll
+                for (int l = 0; l < 8; l++) { w[l][0] = wv[u][l].x; w[l][1] = wv[u][l].y; w[l][2] = wv[u][l].z; w[l][3] = wv[u][l].w; }
+                const uint32_t f[8] = {hv[u][1].x, hv[u][1].y, hv[u][1].z, hv[u][1].w, hv[u][2].x, hv[u][2].y, hv[u][2].z, hv[u][2].w};
+                const float d = gg_f16(hv[u][0].x & 0xFFFFu), dmin = gg_f16(hv[u][0].x >> 16);
+                const float* in = x + b * 256;
+                float s = 0.0f;
+#pragma unroll
+                for (int js = 0; js < 8; js++) {      // sub-block js = 2 j + hi
+                    const int j = js >> 1, hi = js & 1;
+                    int sc, mn;
+                    gg_scale_min_k4(js, hv[u][0].y, hv[u][0].z, hv[u][0].w, sc, mn);
+                    const float d1 = d * (float)sc, m1 = dmin * (float)mn;
+#pragma unroll
+                    for (int p = 0; p < 32; p++) {
+                        const int l = (p & 15) >> 1, sft = ((p & 1) + 2 * (p >> 4)) * 8;
+                        const uint32_t q4 = (w[l][j] >> (sft + 4 * hi)) & 0xFu, q5 = (f[l] >> (sft + js)) & 1u;
+                        const float wk = d1 * (float)(q4 + 16u * q5) - m1;
+                        s += wk * in[js * 32 + p];
+                    }
+                }
+                sum += s;
+            }
+        }
+    }
+    return sum;
+}
+__device__ __forceinline__ float gg_row_scalar(const GgMat& m, int r, const float* x) { return m.type == GG_Q6_K ? gg_row_q6k(m, r, x) : m.type == GG_Q5_K ? gg_row_q5k(m, r, x) : gg_row_q5_0(m, r, x); }
 
 // rows of one workgroup: the integer types take `tiles_per_wg` 8-row tiles on four waves, the scalar types one row per thread (GG_BLOCK rows)
 __device__ __forceinline__ int gg_wg_tiles(int type, int tiles_per_wg) { return gg_int_path(type) ? tiles_per_wg : GG_BLOCK / 8; }
 
-// SC: the launch holds a Q5_0 / Q6_K matrix.  The kernels without one carry no scalar-row code: the integer types keep their registers and their occupancy
+// SC: the launch holds a Q5_0 / Q5_K / Q6_K matrix.  The kernels without one carry no scalar-row code: the integer types keep their registers and their occupancy
 template <bool SC>
 __device__ __forceinline__ void gg_run_rows(const GgMat& m, const GgAct& A, float* out, int row_base_out, int tile0, int ntiles_wg) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -215,7 +269,7 @@ void kr_launch_gguf_moe(const GgMoeArgs& a, hipStream_t st) {
     }
 }
 
-// ---- kr_gguf_matvec: y = W x of one Q5_0 / Q6_K matrix with the device functions above as one launch.  parts 0: the exact chain, one lane per row, GG_BLOCK rows a
+// ---- kr_gguf_matvec: y = W x of one Q5_0 / Q5_K / Q6_K matrix with the device functions above as one launch.  parts 0: the exact chain, one lane per row, GG_BLOCK rows a
 //      workgroup; parts 1 | 2: the tolerance tile, one 8-row tile per wave, the row's blocks walked whole or as two slices whose results are added (what the two
 //      k-waves of the mode's gate|up launch do) ----
 __global__ void __launch_bounds__(GG_BLOCK) kr_gguf_matvec_kernel(const GgMat m, const float* x, float* y, int parts) {
@@ -230,13 +284,13 @@ __global__ void __launch_bounds__(GG_BLOCK) kr_gguf_matvec_kernel(const GgMat m,
     GgAct A{}; A.f32v = xs;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, tile = blockIdx.x * (GG_BLOCK / 64) + wave;
     if (tile >= (m.N + 7) / 8) return;
-    float r = m.type == GG_Q6_K ? gg_tile_q6k(m, tile, A, lane, 0, parts) : gg_tile_q5_0(m, tile, A, lane, 0, parts);
-    if (parts == 2) r = r + (m.type == GG_Q6_K ? gg_tile_q6k(m, tile, A, lane, 1, 2) : gg_tile_q5_0(m, tile, A, lane, 1, 2));
+    float r = gg_tile_scalar(m, tile, A, lane, 0, parts);
+    if (parts == 2) r = r + gg_tile_scalar(m, tile, A, lane, 1, 2);
     const int row = tile * 8 + (lane >> 3);
     if ((lane & 7) == 0 && row < m.N) y[row] = r;
 }
 int kr_launch_gguf_matvec(const GgMat& m, const float* x, float* y, int parts, hipStream_t st) {
-    if (!gg_scalar_type(m.type) || parts < 0 || parts > 2 || m.N < 1 || m.K < 1 || m.K % (m.type == GG_Q6_K ? 256 : 32) || (size_t)m.K * 4 > 60 * 1024) return 1;
+    if (!gg_scalar_type(m.type) || parts < 0 || parts > 2 || m.N < 1 || m.K < 1 || m.K % (m.type == GG_Q5_0 ? 32 : 256) || (size_t)m.K * 4 > 60 * 1024) return 1;
     const int rows_wg = parts == 0 ? GG_BLOCK : 8 * (GG_BLOCK / 64);
     hipLaunchKernelGGL(kr_gguf_matvec_kernel, dim3((m.N + rows_wg - 1) / rows_wg), dim3(GG_BLOCK), (size_t)m.K * 4, st, m, x, y, parts);
     return 0;
@@ -245,7 +299,7 @@ int kr_launch_gguf_matvec(const GgMat& m, const float* x, float* y, int parts, h
 size_t gg_q_bytes(int type, int K, int N) {
     const size_t nt = (size_t)(N + 7) / 8;
     switch (type) {
-        case GG_Q4_K: return nt * (K / 256) * 64 * 16;
+        case GG_Q4_K: case GG_Q5_K: return nt * (K / 256) * 64 * 16;
         case GG_Q8_0: return nt * (((K / 32) + 3) / 4) * 64 * 16;
         case GG_Q4_0: return nt * (((K / 32) + 7) / 8) * 64 * 16;
         case GG_Q5_0: return nt * (((K / 32) + 7) / 8) * 64 * 16;
@@ -257,6 +311,7 @@ size_t gg_h_bytes(int type, int K, int N) {
     const size_t nt = (size_t)(N + 7) / 8;
     switch (type) {
         case GG_Q4_K: return nt * (K / 256) * 8 * 16;
+        case GG_Q5_K: return nt * (K / 256) * 8 * 48;
         case GG_Q8_0: return nt * (((K / 32) + 3) / 4) * 8 * 8;
         case GG_Q4_0: return nt * (((K / 32) + 7) / 8) * 8 * 16;
         case GG_Q5_0: return nt * (((K / 32) + 7) / 8) * 8 * 48;

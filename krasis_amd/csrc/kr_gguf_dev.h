@@ -322,8 +322,64 @@ __device__ __forceinline__ float gg_tile_q6k(const GgMat& m, int tile, const GgA
     return kr_hsum8(acc.x + acc.y);
 }
 
+// ---- Q5_K (docs/design/45-gguf-q5k.md): the reference de-quantizes the type (gguf.rs:740-803) and has no matvec for it; the value is w = (d sc_j) (q4 + 16 q5) - (dmin mn_j) with
+//      dequant_q5_k's roundings, the exact chain is the scalar Q4_K row over these values (gg_row_q5k, kr_gguf.hip).  The tile: lane l owns Q4_K's record -- per chunk j of 64
+//      elements one word, bytes {qs[32j+2l], qs[32j+2l+1], qs[32j+16+2l], qs[32j+17+2l]}, low nibbles = elements 64j + p, high nibbles = elements 64j + 32 + p -- and ONE header
+//      word whose byte i carries the fifth bits of byte i of every chunk (bit 2j: low nibble, bit 2j + 1: high nibble).  Four codes at a time on whole words: two nibble masks
+//      per chunk word, the fifth bits shifted under 0x10101010.  Values against A.f32v in one packed accumulator in block order, then kr_hsum8; [part, parts) slices super-blocks. ----
+#define GG_PF5K 4     // super-blocks requested ahead -- per lane 4 record + 5 header words a block
+// four codes (the bytes of `codes`) of one sub-block against the pairs x[0..1] (elements 2l, 2l + 1) and x[16..17] (elements 16 + 2l, 17 + 2l)
+__device__ __forceinline__ void gg_q5k_four(gg_f32x2& acc, float d1, float m1, uint32_t codes, const float* x) {
+    const gg_f32x2 dd = {d1, d1}, mm = {m1, m1};
+    const gg_f32x2 q01 = {(float)(codes & 0xFFu), (float)((codes >> 8) & 0xFFu)}, q23 = {(float)((codes >> 16) & 0xFFu), (float)(codes >> 24)};
+    const gg_f32x2 x01 = *reinterpret_cast<const gg_f32x2*>(x), x23 = *reinterpret_cast<const gg_f32x2*>(x + 16);
+    acc += (dd * q01 - mm) * x01;
+    acc += (dd * q23 - mm) * x23;
+}
+__device__ __forceinline__ float gg_tile_q5k(const GgMat& m, int tile, const GgAct& A, int lane, int part = 0, int parts = 1) {
+    const int l = lane & 7, row = lane >> 3;
+    const int nb = m.K / 256, per = (nb + parts - 1) / parts, b_lo = part * per, b_hi = b_lo + per < nb ? b_lo + per : nb;
+    const u32x4* q = reinterpret_cast<const u32x4*>(m.q) + (size_t)tile * nb * 64 + lane;
+    const u32x4* h = reinterpret_cast<const u32x4*>(m.h) + ((size_t)tile * nb * 8 + row) * 3;               // [block][8 rows] x 48 B
+    gg_f32x2 acc = {0.0f, 0.0f};
+    for (int b0 = b_lo; b0 < b_hi; b0 += GG_PF5K) {
+        u32x4 wv[GG_PF5K], hv[GG_PF5K]; uint32_t fv[GG_PF5K];
+#pragma unroll
+        for (int u = 0; u < GG_PF5K; u++) {
+            const int bb = b0 + u < b_hi ? b0 + u : (b_hi > 0 ? b_hi - 1 : 0);
+            wv[u] = kr_ldg_nt(q + (size_t)bb * 64); hv[u] = kr_ldg_nt(h + (size_t)bb * 24);
+            fv[u] = kr_ldg_nt(reinterpret_cast<const uint32_t*>(h + (size_t)bb * 24 + 1) + l);
+        }
+#pragma unroll
+        for (int u = 0; u < GG_PF5K; u++) {
+            const int b = b0 + u;
+            if (b < b_hi) {
+                const u32x4 hd = hv[u];
+                const float d = gg_f16(hd.x & 0xFFFFu), dmin = gg_f16(hd.x >> 16);
+                const uint32_t wj[4] = {wv[u].x, wv[u].y, wv[u].z, wv[u].w}, f = fv[u];
+                // fifth bits of chunk j under the mask 0x10101010: bit 2j (low nibbles), bit 2j + 1 (high nibbles) of every byte of f
+                const uint32_t f_lo[4] = {(f << 4) & 0x10101010u, (f << 2) & 0x10101010u, f & 0x10101010u, (f >> 2) & 0x10101010u};
+                const uint32_t f_hi[4] = {(f << 3) & 0x10101010u, (f << 1) & 0x10101010u, (f >> 1) & 0x10101010u, (f >> 3) & 0x10101010u};
+#pragma unroll
+                for (int j = 0; j < 4; j++) {
+                    int sc_lo, mn_lo, sc_hi, mn_hi;
+                    gg_scale_min_k4(2 * j, hd.y, hd.z, hd.w, sc_lo, mn_lo); gg_scale_min_k4(2 * j + 1, hd.y, hd.z, hd.w, sc_hi, mn_hi);
+                    const float* in = A.f32v + b * 256 + j * 64 + 2 * l;
+                    gg_q5k_four(acc, d * (float)sc_lo, dmin * (float)mn_lo, (wj[j] & 0x0F0F0F0Fu) | f_lo[j], in);
+                    gg_q5k_four(acc, d * (float)sc_hi, dmin * (float)mn_hi, ((wj[j] >> 4) & 0x0F0F0F0Fu) | f_hi[j], in + 32);
+                }
+            }
+        }
+    }
+    return kr_hsum8(acc.x + acc.y);
+}
+
 __host__ __device__ static inline bool gg_int_path(int t) { return t == GG_Q4_K || t == GG_Q8_0 || t == GG_Q4_0; }
-__host__ __device__ static inline bool gg_scalar_type(int t) { return t == GG_Q5_0 || t == GG_Q6_K; }
+__host__ __device__ static inline bool gg_scalar_type(int t) { return t == GG_Q5_0 || t == GG_Q5_K || t == GG_Q6_K; }
+// one 8-row tile of a scalar type in the tolerance form
+__device__ __forceinline__ float gg_tile_scalar(const GgMat& m, int tile, const GgAct& A, int lane, int part = 0, int parts = 1) {
+    return m.type == GG_Q6_K ? gg_tile_q6k(m, tile, A, lane, part, parts) : m.type == GG_Q5_K ? gg_tile_q5k(m, tile, A, lane, part, parts) : gg_tile_q5_0(m, tile, A, lane, part, parts);
+}
 
 __device__ __forceinline__ GgMat gg_expert_mat(const GgMat& base, int e) {
     GgMat m = base;

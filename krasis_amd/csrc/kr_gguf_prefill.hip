@@ -345,7 +345,7 @@ __global__ void __launch_bounds__(256, 2) kr_gpf_gemm_kernel(const GpfGemmArgs a
 // ------------------------------------------------------------------------------------------
 // synthetic GGUF experts (SURVEY 8d defines the distribution the reference's generator lacks): quant bytes and the 12 packed scale bytes
 // are raw hash words, d = f16((0.005 + u * 0.045) / 63), dmin = f16(8 d); Q8_0: d = f16((0.005 + u * 0.045) / 127); Q5_0: d = f16((0.005 + u * 0.045) / 15), raw qh words;
-// Q6_K: d = f16((0.005 + u * 0.045) / 31 / 127), raw scale bytes
+// Q6_K: d = f16((0.005 + u * 0.045) / 31 / 127), raw scale bytes; Q5_K: Q4_K's rule with d halved (d = f16((0.005 + u * 0.045) / 126), dmin = f16(16 d): Q4_K's offsets), raw fifth-bit words
 // ------------------------------------------------------------------------------------------
 __device__ __forceinline__ uint64_t gpf_mix(uint64_t x) {
     x += 0x9E3779B97F4A7C15ull; x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull; x = (x ^ (x >> 27)) * 0x94D049BB133111EBull; return x ^ (x >> 31);
@@ -362,6 +362,17 @@ __global__ void kr_gpf_fill_h_kernel(char* h, size_t n_rec, int type, uint64_t s
             const uint32_t db = __half_as_ushort(__float2half(d)), mb = __half_as_ushort(__float2half(d * 8.0f));
             u32x4 o = {db | (mb << 16), (uint32_t)(r0 >> 32), (uint32_t)r1, (uint32_t)(r1 >> 32)};
             *reinterpret_cast<u32x4*>(h + i * 16) = o;
+        } else if (type == GG_Q5_K) {   // Q4_K's rule with d halved (the codes reach 31): d = f16((0.005 + u * 0.045) / 126), dmin = f16(16 d); then the 8 fifth-bit words, raw
+            const float d = __half2float(__float2half(dval((uint32_t)r0, 126.0f)));
+            const uint32_t db = __half_as_ushort(__float2half(d)), mb = __half_as_ushort(__float2half(d * 16.0f));
+            u32x4 o = {db | (mb << 16), (uint32_t)(r0 >> 32), (uint32_t)r1, (uint32_t)(r1 >> 32)};
+            *reinterpret_cast<u32x4*>(h + i * 48) = o;
+#pragma unroll
+            for (int k = 0; k < 2; k++) {
+                const uint64_t ra = gpf_mix((seed ^ (0xD5ull << 56)) + i * 4 + 2 * k), rb = gpf_mix((seed ^ (0xD5ull << 56)) + i * 4 + 2 * k + 1);
+                u32x4 f = {(uint32_t)ra, (uint32_t)(ra >> 32), (uint32_t)rb, (uint32_t)(rb >> 32)};
+                *reinterpret_cast<u32x4*>(h + i * 48 + 16 + k * 16) = f;
+            }
         } else if (type == GG_Q5_0) {   // 8 x f16 d = f16((0.005 + u * 0.045) / 15), then 8 x u32 qh (raw words)
             uint32_t w[12];
 #pragma unroll
@@ -387,7 +398,7 @@ __global__ void kr_gpf_fill_h_kernel(char* h, size_t n_rec, int type, uint64_t s
 }
 void kr_launch_gpf_fill_synth(void* q, size_t q_bytes, void* h, size_t h_bytes, int type, uint64_t seed, hipStream_t st) {
     hipLaunchKernelGGL(kr_gpf_fill_q_kernel, dim3(2048), dim3(256), 0, st, (uint32_t*)q, q_bytes / 4, seed);
-    hipLaunchKernelGGL(kr_gpf_fill_h_kernel, dim3(512), dim3(256), 0, st, (char*)h, h_bytes / (type == GG_Q4_K ? 16 : type == GG_Q5_0 ? 48 : type == GG_Q6_K ? 20 : 8), type, seed ^ 0x5DEECE66Dull);
+    hipLaunchKernelGGL(kr_gpf_fill_h_kernel, dim3(512), dim3(256), 0, st, (char*)h, h_bytes / (type == GG_Q4_K ? 16 : type == GG_Q5_0 || type == GG_Q5_K ? 48 : type == GG_Q6_K ? 20 : 8), type, seed ^ 0x5DEECE66Dull);
 }
 
 // ------------------------------------------------------------------------------------------

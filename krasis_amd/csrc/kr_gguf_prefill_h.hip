@@ -79,13 +79,21 @@ __device__ __forceinline__ void gfh_bytes4(uint32_t codes, v2h off, v2h s01, v2h
     r23 = (__builtin_bit_cast(v2h, t1) + off) * s23;
 }
 
+// Q5_K: 4 code bytes of one sub-block -> 4 f16 values code * s + nm, s = 16 d sc, nm = -16 dmin mn, one rounding each (v_pk_fma_f16)
+__device__ __forceinline__ void gfh_q5k4(uint32_t codes, v2h off, v2h s, v2h nm, v2h& r01, v2h& r23) {
+    const uint32_t Kc = 0x64646464u;
+    const uint32_t t0 = __builtin_amdgcn_perm(Kc, codes, 0x04010400u), t1 = __builtin_amdgcn_perm(Kc, codes, 0x04030402u);
+    r01 = __builtin_elementwise_fma(__builtin_bit_cast(v2h, t0) + off, s, nm);
+    r23 = __builtin_elementwise_fma(__builtin_bit_cast(v2h, t1) + off, s, nm);
+}
+
 template <int TYPE>
 __global__ void __launch_bounds__(256, 2) kr_gfh_gemm_kernel(const KrGfhArgs a) {
-    static_assert(TYPE == GG_Q6_K || TYPE == GG_Q5_0, "lane-record form of Q6_K and Q5_0");
-    constexpr bool Q6 = TYPE == GG_Q6_K;
+    static_assert(TYPE == GG_Q6_K || TYPE == GG_Q5_0 || TYPE == GG_Q5_K, "lane-record form of Q6_K, Q5_0 and Q5_K");
+    constexpr bool Q6 = TYPE == GG_Q6_K, Q5K = TYPE == GG_Q5_K;      // Q5_K shares Q5_0's stage geometry: 16-byte records, 48-byte headers, the same As / Bs maps
     constexpr int LDA = GFH_LDA, BS_BYTES = Q6 ? 16 * GFH_T6 : GFH_BN * GFH_LDB5;
     constexpr int NBC = Q6 ? 6 : 4;               // 16-byte record chunks per thread per stage
-    constexpr int NHW = Q6 ? 5 : 12;              // header words per lane per stage
+    constexpr int NHW = Q6 ? 5 : Q5K ? 8 : 12;    // header words per lane per stage (Q5_K: the 16-byte head and the fifth-bit words of the lane's four records)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* As = smem;
     char* Bs = As + GFH_BM * LDA;
@@ -151,6 +159,12 @@ __global__ void __launch_bounds__(256, 2) kr_gfh_gemm_kernel(const KrGfhArgs a) 
             const uint32_t* hp = reinterpret_cast<const uint32_t*>(wh + hbase + (size_t)st * 160);
 #pragma unroll
             for (int i = 0; i < 5; i++) ph[i] = kr_ldg_nt(hp + i);
+        } else if constexpr (Q5K) {
+            const char* hp = wh + hbase + (size_t)st * 384;
+            const u32x4 v = kr_ldg_nt(reinterpret_cast<const u32x4*>(hp));
+            ph[0] = v.x; ph[1] = v.y; ph[2] = v.z; ph[3] = v.w;
+#pragma unroll
+            for (int t = 0; t < 4; t++) ph[4 + t] = kr_ldg_nt(reinterpret_cast<const uint32_t*>(hp + 16) + 2 * t + khalf);      // record l = 2 t + khalf
         } else {
             const u32x4* hp = reinterpret_cast<const u32x4*>(wh + hbase + (size_t)st * 384);
 #pragma unroll
@@ -217,6 +231,16 @@ __global__ void __launch_bounds__(256, 2) kr_gfh_gemm_kernel(const KrGfhArgs a) 
                 sc[2 * w] = (__builtin_bit_cast(v2h, __builtin_amdgcn_perm(0x64646464u, x, 0x04010400u)) + o8) * d16;
                 sc[2 * w + 1] = (__builtin_bit_cast(v2h, __builtin_amdgcn_perm(0x64646464u, x, 0x04030402u)) + o8) * d16;
             }
+        } else if constexpr (Q5K) {      // sc[js] = (16 d sc_js, -16 dmin mn_js), js < 8: each the exact product of two f16 values rounded once
+            const v2h dm16 = __builtin_bit_cast(v2h, hw[0]) * c16;
+#pragma unroll
+            for (int js = 0; js < 8; js++) {
+                const uint32_t b_lo = (hw[1] >> ((js & 3) * 8)) & 0xFFu, b_mid = (hw[2] >> ((js & 3) * 8)) & 0xFFu, b_hi = (hw[3] >> ((js & 3) * 8)) & 0xFFu;
+                // get_scale_min_k4: bytes j, j + 4 (j < 4) | bytes j + 4, j - 4, j (j >= 4) of the 12 scale bytes hw[1..3]
+                const uint32_t scq = js < 4 ? (b_lo & 63u) : ((b_hi & 0xFu) | ((b_lo >> 6) << 4)), mnq = js < 4 ? (b_mid & 63u) : ((b_hi >> 4) | ((b_mid >> 6) << 4));
+                const v2h q = {(_Float16)(float)scq, (_Float16)-(float)mnq};
+                sc[js] = q * dm16;
+            }
         } else {
 #pragma unroll
             for (int f = 0; f < 4; f++) {
@@ -258,6 +282,22 @@ __global__ void __launch_bounds__(256, 2) kr_gfh_gemm_kernel(const KrGfhArgs a) 
                 gfh_bytes4(((ql >> 4) & 0x0F0F0F0Fu) | (qh & 0x30303030u), o, S(2), S(2), r0, r1);
                 gfh_bytes4(((qm >> 4) & 0x0F0F0F0Fu) | ((qh >> 2) & 0x30303030u), o, S(3), S(3), r2, r3);
                 bf[1] = v8h{r0.x, r0.y, r1.x, r1.y, r2.x, r2.y, r3.x, r3.y};
+            } else if constexpr (Q5K) {
+                // word j of the record = chunk j: low nibbles the four values of sub-block 2 j, high nibbles those of sub-block 2 j + 1, in the order As holds them;
+                // the fifth bits come from the record's header word under one mask per (chunk, nibble), as in gg_tile_q5k
+                const uint32_t fb = hw[4 + (hr >> 1)];
+                const v2h o = {(_Float16)-1024.0f, (_Float16)-1024.0f};
+#pragma unroll
+                for (int ff = 0; ff < 2; ff++) {
+                    const int j = 2 * (hr & 1) + ff;
+                    const uint32_t w = br[buf][ff];
+                    const uint32_t f_lo = (j < 2 ? fb << (4 - 2 * j) : fb >> (2 * j - 4)) & 0x10101010u, f_hi = (j < 2 ? fb << (3 - 2 * j) : fb >> (2 * j - 3)) & 0x10101010u;
+                    const uint32_t lo = (w & 0x0F0F0F0Fu) | f_lo, hi = ((w >> 4) & 0x0F0F0F0Fu) | f_hi;
+                    const v2h s_lo = {sc[2 * j].x, sc[2 * j].x}, m_lo = {sc[2 * j].y, sc[2 * j].y}, s_hi = {sc[2 * j + 1].x, sc[2 * j + 1].x}, m_hi = {sc[2 * j + 1].y, sc[2 * j + 1].y};
+                    gfh_q5k4(lo, o, s_lo, m_lo, r0, r1);
+                    gfh_q5k4(hi, o, s_hi, m_hi, r2, r3);
+                    bf[ff] = v8h{r0.x, r0.y, r1.x, r1.y, r2.x, r2.y, r3.x, r3.y};
+                }
             } else {
                 const int t = hr >> 1, sh = 4 * t + 2 * khalf;      // 2 l
                 const v2h o = {(_Float16)-1040.0f, (_Float16)-1040.0f};
@@ -314,7 +354,7 @@ __global__ void __launch_bounds__(256, 2) kr_gfh_gemm_kernel(const KrGfhArgs a) 
 }
 
 bool kr_gfh_type_supported(int type, int K, int N) {
-    return ((type == GG_Q6_K && K % 256 == 0) || (type == GG_Q5_0 && K % 32 == 0)) && K > 0 && N > 0 && N % 8 == 0;
+    return (((type == GG_Q6_K || type == GG_Q5_K) && K % 256 == 0) || (type == GG_Q5_0 && K % 32 == 0)) && K > 0 && N > 0 && N % 8 == 0;
 }
 
 template <int TYPE>
@@ -339,5 +379,5 @@ void kr_launch_gfh_gemm(const GgMat& m, const uint16_t* a_h, const float* a_mul,
     a.run = (single_expert_rows > 0 || run < 1) ? 1 : run;
     const int mt = single_expert_rows > 0 ? (single_expert_rows + GFH_BM - 1) / GFH_BM : max_tiles;
     if (mt <= 0) return;
-    if (m.type == GG_Q6_K) gfh_launch<GG_Q6_K>(a, mt, st); else gfh_launch<GG_Q5_0>(a, mt, st);
+    if (m.type == GG_Q6_K) gfh_launch<GG_Q6_K>(a, mt, st); else if (m.type == GG_Q5_K) gfh_launch<GG_Q5_K>(a, mt, st); else gfh_launch<GG_Q5_0>(a, mt, st);
 }
