@@ -358,7 +358,7 @@ int kr_decode_set_attention_mode(kr_decode_store* s, int mode);
  * speculation entry points, which otherwise refuse a store with such layers, accept it.  Slower than the default form on long prompts.  A prompt pass
  * with the option and KR_GEMM_FAST both set is refused (KR_ERR_STATE).  Stores without native GGUF layers are unaffected.
  * "gguf_exact_grouped" (default 1): 0 = that pass through the streaming block kernels for every block type (A/B and test hook; same bits).
- * "gguf_exact_grouped_scalar" (default 0; docs/design/43-gguf-exact-grouped-scalar.md): under "gguf_exact_pass", with 1 a Q6_K / Q5_0 projection takes a grouped
+ * "gguf_exact_grouped_scalar" (default 0; docs/design/43-gguf-exact-grouped-scalar.md): under "gguf_exact_pass", with 1 a Q6_K / Q5_0 / Q5_K projection takes a grouped
  * kernel of its own (an expert's records read and unpacked once per group of 8 rows, the reference's serial f32 chain per row) and a Q4_K / Q8_0 projection of the
  * same layer keeps its grouped kernel; with 0 a layer that holds a Q6_K or Q5_0 matrix streams whole, as before the option existed.  Same bits either way; refuses
  * nothing.  Measured on 4-layer models: 1.9 .. 2.2x faster on a 2048-token prompt and 1.14 .. 1.26x at 64 rows, 1 .. 3 % slower at 16 rows -- hence off by default.
@@ -733,7 +733,7 @@ enum {
     KR_MPC_GGUF_GROUPED,    /* ... that took the grouped form ("gguf_exact_grouped" 1), not the streaming kernels */
     KR_MPC_SEQ_PASSES,      /* prompt / verify passes of the store's own sequence (kr_decode_prefill*, kr_decode_verify) */
     KR_MPC_SEQ_FEW,         /* ... that took the few-row kernels */
-    KR_MPC_GGUF_GROUPED_SCALAR, /* batched passes over slots in which a MoE layer took the grouped Q6_K / Q5_0 kernel for some projection ("gguf_exact_grouped_scalar") */
+    KR_MPC_GGUF_GROUPED_SCALAR, /* batched passes over slots in which a MoE layer took the grouped Q6_K / Q5_0 / Q5_K kernel for some projection ("gguf_exact_grouped_scalar") */
     KR_MPC_FD_SHARED,       /* batched passes over slots in which a GQA layer ran a flash-decode item of two or more rows ("multi_attn_fast_paged" = 2) */
     KR_MPC_COUNT
 };

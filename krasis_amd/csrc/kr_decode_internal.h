@@ -124,7 +124,7 @@ struct kr_decode_store {
     int opt_multi_sample_loop = 0;               // kr_decode_set_option("multi_sample_loop"): every sampled row of a multi-sequence step takes the single-row sampler, one row after another (A/B and test hook; same tokens)
     int opt_gguf_exact_pass = 0;                 // kr_decode_set_option("gguf_exact_pass"): every multi-row pass runs native-GGUF MoE layers through the exact forms (KR_PF_SET_GGUF_EXACT, docs/design/20-gguf-exact-pass.md): a row carries the bits of kr_decode_step, and the slot / speculation entry points accept such a store
     int opt_gguf_exact_grouped = 1;              // ... 0 = through the streaming kernels for every block type (A/B and test hook; same bits)
-    int opt_gguf_exact_grouped_scalar = 0;       // ... 1 = Q6_K / Q5_0 projections take the grouped row-chain kernel (KR_PF_SET_GGUF_SCALAR, docs/design/43-gguf-exact-grouped-scalar.md); 0 = a layer that holds one streams whole, as before.  Same bits; off by default: measured ahead at 64 rows and on prompts, 1 .. 3 % behind at 16 rows
+    int opt_gguf_exact_grouped_scalar = 0;       // ... 1 = Q6_K / Q5_0 / Q5_K projections take the grouped row-chain kernel (KR_PF_SET_GGUF_SCALAR, docs/design/43-gguf-exact-grouped-scalar.md); 0 = a layer that holds one streams whole, as before.  Same bits; off by default: measured ahead at 64 rows and on prompts, 1 .. 3 % behind at 16 rows
     KrMultiOpts mopt;                            // kr_decode_set_option("multi_..."): the opt-in forms of the batched pass over device slots, each described on its field (kr_multi_opts.h)
     int opt_pass_few_rows = 0;                   // kr_decode_set_option("pass_few_rows"): a multi-row pass of at most opt_pass_few_rows_max token rows (prefill / verify: n_tokens; slot entry points: the sum of the counts) runs its projections on the few-row streaming matvec (kr_rows_matvec.hip) and its INT4 / INT8 routed experts as the decode step's three launches -- bit for bit what it gives without the option (docs/design/34-pass-few-rows.md); KR_GEMM_FAST passes and larger passes keep their GEMMs
     int opt_pass_few_rows_max = 16;              // kr_decode_set_option("pass_few_rows_max"), 1 .. 16: the most token rows of a pass that takes the few-row kernels (a measured default: profiles/pass_few_rows.txt)

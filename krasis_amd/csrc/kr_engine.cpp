@@ -522,13 +522,13 @@ extern "C" int kr_gguf_matvec(kr_engine* e, int type, const uint8_t* blocks, int
     return KR_OK;
 }
 
-// The grouped Q5_0 / Q6_K kernel of the exact pass as a stand-alone operator (docs/design/43-gguf-exact-grouped-scalar.md): raw row-major blocks and M f32 rows on the
+// The grouped Q5_0 / Q5_K / Q6_K kernel of the exact pass as a stand-alone operator (docs/design/43-gguf-exact-grouped-scalar.md, 46-gguf-q5k-grouped.md): raw row-major blocks and M f32 rows on the
 // host, the matrix re-tiled as kr_gguf_matvec does, the rows sorted as the one expert's (groups of kr_ggg_group_rows(): M = 11 is a group of 8 and one of 3), one
 // launch of kr_ggs_kernel per 16 384 rows, y[M][N] copied back.  Nothing stays on the engine.
 extern "C" int kr_gguf_matmul_rows(kr_engine* e, int type, const uint8_t* blocks, int N, int K, const float* x, int M, float* y) {
     if (!e) return kr_fail(KR_ERR_VALUE, "kr_gguf_matmul_rows: null engine");
     if (!blocks || !x || !y) return kr_fail(KR_ERR_VALUE, "kr_gguf_matmul_rows: null pointer argument");
-    if (type != GG_Q5_0 && type != GG_Q6_K) return kr_fail(KR_ERR_VALUE, "kr_gguf_matmul_rows: type %d is neither Q5_0 (6) nor Q6_K (14)", type);
+    if (type != GG_Q5_0 && type != GG_Q5_K && type != GG_Q6_K) return kr_fail(KR_ERR_VALUE, "kr_gguf_matmul_rows: type %d is none of Q5_0 (6), Q5_K (13), Q6_K (14)", type);
     if (N < 1 || K < 1 || K % ggml_block_elems(type) || K > 15360) return kr_fail(KR_ERR_VALUE, "kr_gguf_matmul_rows: shape N %d, K %d (K: a multiple of %d, at most 15360)", N, K, ggml_block_elems(type));
     if (M < 1) return kr_fail(KR_ERR_VALUE, "kr_gguf_matmul_rows: M %d rows (at least 1)", M);
     std::lock_guard<std::mutex> lk(e->mu);
@@ -1140,9 +1140,9 @@ static int moe_prefill_gguf(kr_engine* e, Layer& L, int layer, const void* x_bf1
 }
 
 // KR_PF_SET_GGUF_EXACT (the decode store's "gguf_exact_pass"): every row with the bits of the decode step's block kernels (docs/design/20-gguf-exact-pass.md,
-// 43-gguf-exact-grouped-scalar.md).  Per projection: Q4_K / Q8_0 take the grouped kernels of kr_gguf_group.hip over one activation image per row, Q6_K / Q5_0
+// 43-gguf-exact-grouped-scalar.md, 46-gguf-q5k-grouped.md).  Per projection: Q4_K / Q8_0 take the grouped kernels of kr_gguf_group.hip over one activation image per row, Q6_K / Q5_0 / Q5_K
 // (KR_PF_SET_GGUF_SCALAR) the grouped row-chain kernel of the same file over f32 rows; gate and up are of one type.  Any other layer (Q4_0, a k that is no multiple
-// of the block size, row counts that do not match, a Q6_K / Q5_0 matrix without the bit) or KR_PF_SET_GGUF_STREAM: the streaming kernels of kr_gguf.hip over the
+// of the block size, row counts that do not match, a Q6_K / Q5_0 / Q5_K matrix without the bit) or KR_PF_SET_GGUF_STREAM: the streaming kernels of kr_gguf.hip over the
 // rows.  Routed experts only: the weighted sum in routing order, no rsf (the caller's epilogue applies its own, as the decode step's next norm does).  Scratch is
 // the chunk's own set: several chunks may be in flight.
 static int ggx_proj_form(int type, int K, bool scalar) {

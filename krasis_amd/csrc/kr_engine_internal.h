@@ -141,10 +141,10 @@ int kr_moe_prefill_rows(kr_engine* e, int layer, const void* rows_bf16, const in
 #define KR_PF_SET_GGUF_EXACT 0x200    // or-ed into `set`: a native-GGUF layer takes the exact pass (kr_gguf_group.hip; the decode store's "gguf_exact_pass"): every row with the decode step's bits
 #define KR_PF_SET_GGUF_STREAM 0x400   // ... through the streaming kernels of kr_gguf.hip for every block type ("gguf_exact_grouped" 0: A/B and test hook, same bits)
 #define KR_PF_SET_ROWS 0x800          // or-ed into `set`: an INT4 / INT8-g128 layer with M <= 16 and no shared expert in the call runs as the decode step's three launches over the bf16 rows (kr_launch_moe_w13 / _w2 / _combine, B = M; the decode store's "pass_few_rows"): the same bits, 3 launches instead of 8
-#define KR_PF_SET_GGUF_SCALAR 0x1000  // ... with the grouped kernel for Q6_K / Q5_0 projections ("gguf_exact_grouped_scalar" 1; 0: a layer that holds one streams whole, as before; same bits)
+#define KR_PF_SET_GGUF_SCALAR 0x1000  // ... with the grouped kernel for Q6_K / Q5_0 / Q5_K projections ("gguf_exact_grouped_scalar" 1; 0: a layer that holds one streams whole, as before; same bits)
 // the form each projection of a native-GGUF layer takes in the exact pass under these `set` bits: 0 = the whole layer streams, else KR_GGX_* of gate | up in bits 0-1 and of
 // down in bits 2-3.  The dispatcher (moe_prefill_gguf_exact) and the decode store's KR_MPC_GGUF_GROUPED_SCALAR counter both ask this function
-enum { KR_GGX_IMAGE = 1 /* Q4_K / Q8_0: kr_ggg_kernel over activation images */, KR_GGX_ROWS = 2 /* Q6_K / Q5_0: kr_ggs_kernel over f32 rows */ };
+enum { KR_GGX_IMAGE = 1 /* Q4_K / Q8_0: kr_ggg_kernel over activation images */, KR_GGX_ROWS = 2 /* Q6_K / Q5_0 / Q5_K: kr_ggs_kernel over f32 rows */ };
 int kr_moe_gguf_exact_forms(const kr_engine* e, int layer, int set);
 int kr_moe_prefill_set(kr_engine* e, int layer, const void* x_bf16, const int32_t* ids, const float* wts, void* out, int M, int topk,
                        int out_dtype, int routed_only, int set, hipStream_t st);

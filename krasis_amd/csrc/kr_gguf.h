@@ -51,8 +51,8 @@ size_t kr_ggg_image_stride(int K);                  // bytes of one row's image:
 void kr_launch_ggg_image_x(const uint16_t* x_bf16, int M, int K, void* img, hipStream_t st);                                     // images of M bf16 rows
 void kr_launch_ggg_image_h(const float* gu, int pairs, int I, int gu_ld, const KrPfSort* sort, void* img, hipStream_t st);       // images of silu(gate) * up of the sorted rows
 void kr_launch_ggg_gemm(const GgMat& m0, const GgMat* m1, const void* img, const KrPfSort* sort, int topk, int gather_tokens, int pairs, int n_experts, float* out, int out_ld, hipStream_t st);
-// ... Q6_K / Q5_0 (docs/design/43-gguf-exact-grouped-scalar.md): the same sort, the row chains of gg_row_q6k / gg_row_q5_0 over f32 activation rows staged in LDS, no image
-bool kr_ggs_type_supported(int type, int K);        // Q6_K with K % 256 == 0, Q5_0 with K % 32 == 0
+// ... Q6_K / Q5_0 / Q5_K (docs/design/43-gguf-exact-grouped-scalar.md, 46-gguf-q5k-grouped.md): the same sort, the row chains of gg_row_q6k / gg_row_q5_0 / gg_row_q5k over f32 activation rows staged in LDS, no image
+bool kr_ggs_type_supported(int type, int K);        // Q6_K / Q5_K with K % 256 == 0, Q5_0 with K % 32 == 0
 void kr_launch_ggs_hidden(const float* gu, int pairs, int I, int gu_ld, const KrPfSort* sort, float* hid, hipStream_t st);       // f32 silu(gate) * up of the sorted rows, [pairs][I]
 // x: bf16 or f32 activation rows x_ld elements apart; gather_tokens: sorted row r reads row row_pair[r] / topk; out_pairs: it writes out row row_pair[r], not r
 void kr_launch_ggs_gemm(const GgMat& m0, const GgMat* m1, const void* x, int x_bf16, size_t x_ld, const KrPfSort* sort, int topk, int gather_tokens, int out_pairs, int pairs,

@@ -7,8 +7,8 @@
 // A wave's lanes are 8 output rows x 8 AVX lanes as in gg_tile_*; a lane loads a block's record and header once and runs gg_pair_q4k / gg_sub_q8_0 (the
 // streaming tiles' own bodies) against each row's image staged in LDS: GGG_R independent (acc, corr) chains per lane, each with the order of blocks,
 // sub-blocks and lo / hi halves, the kr_hsum8 tree and the `- corr` of the decode step.  Rows never meet: a row's bits do not depend on its group.
-// Q6_K / Q5_0 projections have a grouped form of their own further down (kr_ggs_kernel, docs/design/43-gguf-exact-grouped-scalar.md): no image, one lane per
-// output row, the serial f32 chains of gg_row_q6k / gg_row_q5_0 over the group's f32 rows staged in LDS, behind the same sort.
+// Q6_K / Q5_0 / Q5_K projections have a grouped form of their own further down (kr_ggs_kernel, docs/design/43-gguf-exact-grouped-scalar.md, 46-gguf-q5k-grouped.md):
+// no image, one lane per output row, the serial f32 chains of gg_row_q6k / gg_row_q5_0 / gg_row_q5k over the group's f32 rows staged in LDS, behind the same sort.
 //
 // Image of one row (global, stride ggg_image_stride(K)): rec [K/32][8 lanes]{AH4, AL4}, then scale f32 [K/32], then sum i32 [K/32] -- gg_carve's layout.
 // LDS stage: GGG_STAGE sub-blocks (= GG_PF Q4_K super-blocks, one request batch of the streaming tile) of GGG_R rows, 72 B per sub-block: 36 864 B.
@@ -192,7 +192,7 @@ __global__ void __launch_bounds__(GG_BLOCK) kr_ggg_kernel(const GggArgs a) {
     }
 }
 
-// ---- Q6_K / Q5_0 in the grouped form (docs/design/43-gguf-exact-grouped-scalar.md).  The contract is gg_row_q6k / gg_row_q5_0 of kr_gguf.hip: per
+// ---- Q6_K / Q5_0 / Q5_K in the grouped form (docs/design/43-gguf-exact-grouped-scalar.md; Q5_K further down).  The contract is gg_row_q6k / gg_row_q5_0 of kr_gguf.hip: per
 // (activation row, output row) ONE serial f32 chain over k, each term (s * (float)(q - c)) * x then sum += term -- mul, mul, add, nothing contracted.  The first
 // product does not depend on the activation row, nor do the record loads and the 5- / 6-bit unpack: a lane owns one output row, loads and unpacks its records once
 // and feeds GGG_R chains, one per row of the group, each in the reference's k order.  The group's activation rows sit in LDS as f32, [k][GGG_R rows], a stage of
@@ -200,11 +200,16 @@ __global__ void __launch_bounds__(GG_BLOCK) kr_ggg_kernel(const GggArgs a) {
 // v_pk_mul_f32 / v_pk_add_f32 (component-wise the same IEEE operations).  A unit is 256 k -- a Q6_K super-block (12 + 5 loads, the addresses of gg_row_q6k) or a
 // Q5_0 block group (8 + 3, the last one ragged) -- requested one unit ahead of its use; the sums stay in registers across stages.  NR = 2 / 4 / 8 chains are
 // compiled: a workgroup takes the smallest that holds its group's rows (a decode step's groups mostly hold one row).
+// Q5_K (docs/design/46-gguf-q5k-grouped.md): the contract is gg_row_q5k -- w = (d sc_j) (float)(q4 + 16 q5) - (dmin mn_j), per super-block s = 0, s += w_k x_k over
+// its 256 k in element order, then sum += s: a chain of two levels, so a lane carries NR partial sums s beside its NR sums and folds them at the end of every unit
+// (a unit is one super-block: the row's eight lane records and its 48-byte header, 8 + 3 loads, the addresses of gg_row_q5k; K % 256 == 0, no ragged unit).  The
+// weights do not depend on the activation row and only the order of a chain's adds is fixed, so a sub-block's 32 values are formed word-wise -- a record word and
+// its fifth-bit word give four finished 5-bit codes under one mask-or, one byte-to-float conversion each -- and then walked in element order into the chains.
 #define GGS_STAGE 1024     // k per LDS stage: GGG_R rows x 4 KiB
-#define GGS_UNIT 256       // k per request: a Q6_K super-block, a Q5_0 group of 8 blocks
+#define GGS_UNIT 256       // k per request: a Q6_K / Q5_K super-block, a Q5_0 group of 8 blocks
 typedef float ggs_f32x4 __attribute__((ext_vector_type(4)));
 
-bool kr_ggs_type_supported(int type, int K) { return (type == GG_Q6_K && K > 0 && K % 256 == 0) || (type == GG_Q5_0 && K > 0 && K % 32 == 0); }
+bool kr_ggs_type_supported(int type, int K) { return ((type == GG_Q6_K || type == GG_Q5_K) && K > 0 && K % 256 == 0) || (type == GG_Q5_0 && K > 0 && K % 32 == 0); }
 
 struct GgsArgs {
     GgMat m0, m1;               // gate and up side by side (m1.N == 0: one projection), N rows each
@@ -264,8 +269,21 @@ __device__ __forceinline__ void ggs_term(float w, int k, gg_f32x2 (&sum)[NR / 2]
     }
 }
 
+// The NR chains of a lane pass one empty statement together: no instruction, but no chain's next add may be placed before every chain's previous one.  Q5_K's weights
+// are formed apart from the terms, and without this the compiler walks a whole unit chain pair by chain pair with the 256 weights kept beside it (8 KB of scratch)
+// `k` (the stage offset that the group after next reads through) passes it too: the LDS reads run at most one group of terms ahead of the adds, not a whole unit
+template <int NR>
+__device__ __forceinline__ void ggs_tie(gg_f32x2 (&sum)[NR / 2], int& k) {
+    if (NR == 2) asm("" : "+v"(sum[0]), "+v"(k));
+    if (NR == 4) asm("" : "+v"(sum[0]), "+v"(sum[1]), "+v"(k));
+    if (NR == 8) asm("" : "+v"(sum[0]), "+v"(sum[1]), "+v"(sum[2]), "+v"(sum[3]), "+v"(k));
+}
+// ... and the block scales that the next sub-block's weights are formed from pass one with a chain, half a sub-block ahead: 48 weights in registers, not 256
+__device__ __forceinline__ void ggs_tie_scales(gg_f32x2& sum0, float& d, float& dmin) { asm("" : "+v"(sum0), "+v"(d), "+v"(dmin)); }
+
 // the records of one unit of a lane's output row: Q6_K wv[0 .. 12) = two halves x six 16-byte words, hv = {16 scale bytes, f16 d}; Q5_0 wv[0 .. 8) = the eight
-// lane records of a block group, hv[0 .. 3) as words = {8 x f16 d, 8 x u32 qh}
+// lane records of a block group, hv[0 .. 3) as words = {8 x f16 d, 8 x u32 qh}; Q5_K wv[0 .. 8) = the eight lane records of a super-block, hv[0 .. 3) as words =
+// {f16 d | f16 dmin, 12 scale bytes, 8 x u32 fifth bits (one word per lane record)}.  Q5_0 and Q5_K units have one shape and, with K % 256 == 0, the same addresses
 template <int TYPE> struct GgsUnit { u32x4 wv[TYPE == GG_Q6_K ? 12 : 8]; uint32_t hv[TYPE == GG_Q6_K ? 5 : 12]; };
 
 template <int TYPE>
@@ -279,7 +297,7 @@ __device__ __forceinline__ void ggs_request(const GgMat& m, int r, int unit, Ggs
         for (int i = 0; i < 12; i++) R.wv[i] = kr_ldg_nt(q + ((size_t)unit * 2 + i / 6) * 48 + i % 6);
 #pragma unroll
         for (int i = 0; i < 5; i++) R.hv[i] = kr_ldg_nt(h + (size_t)unit * 40 + i);
-    } else {
+    } else {      // Q5_0 block groups and Q5_K super-blocks: 8 records of 16 B and a 48-byte header per 256 k
         const int nbg = (m.K / 32 + 7) / 8;
         const u32x4* q = reinterpret_cast<const u32x4*>(m.q) + ((size_t)tile * nbg * 8 + row) * 8;
         const u32x4* h = reinterpret_cast<const u32x4*>(m.h) + ((size_t)tile * nbg * 8 + row) * 3;
@@ -317,6 +335,35 @@ __device__ __forceinline__ void ggs_consume(const GgsUnit<TYPE>& R, int unit, in
                 ggs_term<NR>(s3 * (float)(q3 - 32), io + 96 + l, sum);
             }
         }
+    } else if (TYPE == GG_Q5_K) {
+        float d[2], dmin[2];     // d and dmin, for the even and the odd sub-blocks (ggs_tie_scales)
+        d[0] = d[1] = gg_f16(R.hv[0] & 0xFFFFu); dmin[0] = dmin[1] = gg_f16(R.hv[0] >> 16);
+        gg_f32x2 s[NR / 2];      // the super-block's partial sums, the inner level of gg_row_q5k's chain
+#pragma unroll
+        for (int i = 0; i < NR / 2; i++) s[i] = gg_f32x2{0.0f, 0.0f};
+        int kb[2] = {ks, ks};    // ks, for the even and the odd groups of eight terms (ggs_tie)
+#pragma unroll
+        for (int js = 0; js < 8; js++) {      // sub-block js = 2 j + hi: nibble hi of word j of every record, fifth bit 2 j + hi of every byte of the record's header word
+            const int j = js >> 1, hi = js & 1;
+            int sc, mn;
+            gg_scale_min_k4(js, R.hv[1], R.hv[2], R.hv[3], sc, mn);
+            const float d1 = d[hi] * (float)sc, m1 = dmin[hi] * (float)mn;
+            uint32_t c[8];       // four finished codes per word: byte b of c[l] is element p = 2 l + (b & 1) + 16 (b >> 1)
+#pragma unroll
+            for (int l = 0; l < 8; l++) {
+                const uint32_t wj = j == 0 ? R.wv[l].x : j == 1 ? R.wv[l].y : j == 2 ? R.wv[l].z : R.wv[l].w;
+                c[l] = ((wj >> (4 * hi)) & 0x0F0F0F0Fu) | (((R.hv[4 + l] >> js) & 0x01010101u) << 4);
+            }
+#pragma unroll
+            for (int p = 0; p < 32; p++) {
+                const float q = (float)((c[(p & 15) >> 1] >> (8 * ((p & 1) + 2 * (p >> 4)))) & 0xFFu);
+                ggs_term<NR>(d1 * q - m1, kb[(p >> 3) & 1] + js * 32 + p, s);
+                if ((p & 7) == 7) ggs_tie<NR>(s, kb[(p >> 3) & 1]);
+                if (p == 15) ggs_tie_scales(s[0], d[hi ^ 1], dmin[hi ^ 1]);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < NR / 2; i++) sum[i] = sum[i] + s[i];
     } else {
         uint32_t w[8][4];
 #pragma unroll
@@ -417,7 +464,7 @@ void kr_launch_ggg_gemm(const GgMat& m0, const GgMat* m1, const void* img, const
 void kr_launch_ggs_hidden(const float* gu, int pairs, int I, int gu_ld, const KrPfSort* sort, float* hid, hipStream_t st) {
     hipLaunchKernelGGL(kr_ggs_hidden_kernel, dim3(pairs), dim3(GG_BLOCK), 0, st, gu, I, gu_ld, sort->n_tiles, hid);
 }
-// Q6_K / Q5_0 (kr_ggs_type_supported), the same sort.  x: activation rows x_ld elements apart, bf16 or f32; gather_tokens / out_pairs as in GgsArgs
+// Q6_K / Q5_0 / Q5_K (kr_ggs_type_supported), the same sort.  x: activation rows x_ld elements apart, bf16 or f32; gather_tokens / out_pairs as in GgsArgs
 void kr_launch_ggs_gemm(const GgMat& m0, const GgMat* m1, const void* x, int x_bf16, size_t x_ld, const KrPfSort* sort, int topk, int gather_tokens, int out_pairs, int pairs,
                         int n_experts, float* out, int out_ld, hipStream_t st) {
     GgsArgs a{};
@@ -432,5 +479,6 @@ void kr_launch_ggs_gemm(const GgMat& m0, const GgMat* m1, const void* x, int x_b
     const dim3 grid((total + rows_wg - 1) / rows_wg, max_groups);
     const size_t lds = (size_t)GGS_STAGE * GGG_R * 4;
     if (m0.type == GG_Q6_K) hipLaunchKernelGGL(kr_ggs_kernel<GG_Q6_K>, grid, dim3(rows_wg), lds, st, a);
+    else if (m0.type == GG_Q5_K) hipLaunchKernelGGL(kr_ggs_kernel<GG_Q5_K>, grid, dim3(rows_wg), lds, st, a);
     else hipLaunchKernelGGL(kr_ggs_kernel<GG_Q5_0>, grid, dim3(rows_wg), lds, st, a);
 }

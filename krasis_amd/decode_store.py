@@ -408,7 +408,7 @@ class CpuDecodeStore:
         slot and speculation calls accept a store with such layers; slower than the default int8-MFMA form on long prompts; refused together with
         gemm_fast; nothing changes for other weight forms (docs/design/20-gguf-exact-pass.md).  "gguf_exact_grouped" (default 1): 0 makes that pass
         take the streaming block kernels for every type (A/B and test hook, same bits).
-        "gguf_exact_grouped_scalar" (default 0): under "gguf_exact_pass", with 1 a Q6_K / Q5_0 projection takes a grouped kernel of its own (records read
+        "gguf_exact_grouped_scalar" (default 0): under "gguf_exact_pass", with 1 a Q6_K / Q5_0 / Q5_K projection takes a grouped kernel of its own (records read
         and unpacked once per group of 8 rows, the reference's serial f32 chain per row) beside the Q4_K / Q8_0 grouped kernels; with 0 a layer that
         holds such a matrix streams whole, as before.  Same bits; refuses nothing; faster on prompts and at 64 rows, 1 .. 3 % slower at 16 rows, hence off by
         default (docs/design/43-gguf-exact-grouped-scalar.md).

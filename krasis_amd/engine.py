@@ -160,7 +160,7 @@ class KrasisEngine:
         return y
 
     def gguf_matmul_rows(self, type: int, blocks: np.ndarray, N: int, K: int, X: np.ndarray) -> np.ndarray:
-        """Y[M, N] = X W^T for N rows of raw row-major Q5_0 (6) / Q6_K (14) blocks and f32 rows X[M, K], through the grouped kernel the exact GGUF pass
+        """Y[M, N] = X W^T for N rows of raw row-major Q5_0 (6) / Q5_K (13) / Q6_K (14) blocks and f32 rows X[M, K], through the grouped kernel the exact GGUF pass
         runs for such a matrix ("gguf_exact_grouped_scalar"): the rows in groups of 8, every Y[m, n] with the bits of gguf_matvec(parts=0) on row m
         alone.  Other types or shapes, M < 1: ValueError.  Keeps no state on the engine."""
         self._need()
@@ -168,7 +168,7 @@ class KrasisEngine:
         if X.ndim != 2:
             raise ValueError("kr_gguf_matmul_rows: X must be [M, K]")
         M = X.shape[0]
-        if type in (6, 14) and (blocks.size != int(N) * (int(K) // (32 if type == 6 else 256)) * (22 if type == 6 else 210) or X.shape[1] != int(K)):
+        if type in (6, 13, 14) and (blocks.size != int(N) * (int(K) // (32 if type == 6 else 256)) * {6: 22, 13: 176, 14: 210}[type] or X.shape[1] != int(K)):
             raise ValueError("kr_gguf_matmul_rows: blocks / X do not hold N x K")
         Y = np.empty((M, max(int(N), 0)), np.float32)
         check(self._lib.kr_gguf_matmul_rows(self._h, int(type), _addr(blocks), int(N), int(K), _addr(X), int(M), _addr(Y)))

@@ -23,7 +23,8 @@ sys.path.insert(0, ROOT)
 
 ROUNDS, LAYERS, POS, P_TOKENS = 3, 4, 512, 2048
 N_STEP, N_PREFILL = 10, 3
-SHAPES = {"qcn": ("build_qcn", "QCN", 14), "v2lite": ("build_v2lite", "V2L", 6)}
+SHAPES = {"qcn": ("build_qcn", "QCN", 12, 14), "v2lite": ("build_v2lite", "V2L", 12, 6)}      # bench.py builder, its dims, ggml types of gate | up and of down
+SCRIPT = os.path.abspath(__file__)      # what a visit runs: a probe that brings other SHAPES (gguf_q5k_grouped.py) names itself
 LEGS = ("step_multi 16 rows", "step_multi 64 rows", f"prefill {P_TOKENS} tokens")
 
 
@@ -33,9 +34,9 @@ def visit(shape, profile=False):
     import torch
     import bench
     from krasis_amd import KrasisEngine
-    build, dims, down_t = SHAPES[shape]
+    build, dims, gu_t, down_t = SHAPES[shape]
     fill = KrasisEngine.fill_synthetic_gguf
-    KrasisEngine.fill_synthetic_gguf = lambda self, gate_up_type=12, down_type=12, **kw: fill(self, 12, down_t, **kw)      # bench.py's model with another down type
+    KrasisEngine.fill_synthetic_gguf = lambda self, gate_up_type=12, down_type=12, **kw: fill(self, gu_t, down_t, **kw)      # bench.py's model with other block types
     try:
         eng, st, keep = getattr(bench, build)(0, 0, LAYERS, rope_len=P_TOKENS + 64, kv_fp8=True, gguf=True)
     finally:
@@ -104,7 +105,7 @@ def main():
                 env.pop("KRASIS_HIP_LIB", None)
                 if lib:
                     env["KRASIS_HIP_LIB"] = lib
-                p = subprocess.run([sys.executable, os.path.abspath(__file__), "--visit", shape], env=env, capture_output=True, text=True, timeout=240)
+                p = subprocess.run([sys.executable, SCRIPT, "--visit", shape], env=env, capture_output=True, text=True, timeout=240)
                 if p.returncode:      # nothing more on the GPU after a visit that failed
                     sys.exit(f"visit {shape} round {r} library {lib or 'this tree'} ended with {p.returncode}\n{p.stdout[-2000:]}\n{p.stderr[-2000:]}")
                 res = json.loads(next(ln for ln in p.stdout.splitlines() if ln.startswith("VISIT "))[6:])
@@ -113,7 +114,7 @@ def main():
                     for o, v in ts.items():
                         col = "parent build" if lib else f"this tree, option {o}"
                         cols.setdefault(col, {}).setdefault(leg, []).append(v)
-        log(f"{shape}: Q4_K gate | up, type {SHAPES[shape][2]} down, {LAYERS} layers, E4M3 KV, gguf_exact_pass; {ROUNDS} rounds of alternating processes; last token of every prefill: {sorted(lasts)}")
+        log(f"{shape}: type {SHAPES[shape][2]} gate | up, type {SHAPES[shape][3]} down, {LAYERS} layers, E4M3 KV, gguf_exact_pass; {ROUNDS} rounds of alternating processes; last token of every prefill: {sorted(lasts)}")
         assert len(lasts) == 1, lasts
         for leg in LEGS:
             for col in sorted(cols):
