@@ -100,11 +100,11 @@ int kr_upload_expert_bf16(kr_engine* e, int layer, int expert, int inter, const 
 int kr_fill_layer_synthetic(kr_engine* e, int layer, int bits, uint64_t seed);
 /* the native-GGUF twin: every routed expert of the layer as Q4_K (12) / Q5_K (13: Q4_K's rule with d halved) / Q8_0 (8) / Q5_0 (6) / Q6_K (14) blocks with the block distribution SURVEY 8d defines
  * (raw quant / scale bytes, d = f16((0.005 + u * 0.045) / 63), dmin = f16(8 d); Q8_0: d = f16((0.005 + u * 0.045) / 127); Q5_0: d = f16((0.005 + u * 0.045) / 15);
- * Q6_K: d = f16((0.005 + u * 0.045) / 31 / 127)) */
+ * Q6_K: d = f16((0.005 + u * 0.045) / 31 / 127); Q3_K (11): raw code, hmask and scale bytes, d = f16((0.005 + u * 0.045) * 15 / 128): max |w| = 128 d as Q4_K's 63 * 15 d) */
 int kr_fill_layer_synthetic_gguf(kr_engine* e, int layer, int gate_up_type, int down_type, uint64_t seed);
-/* The Q5_0 (6) / Q5_K (13) / Q6_K (14) kernels as a stand-alone operator: y[N] = W x for N rows of raw row-major GGUF blocks and an f32 vector x[K], all host pointers;
- * K a multiple of the block size (32 / 256 / 256), at most 15360; any N >= 1.  parts 0: the reference's serial f32 chain per row (gguf_kernels.rs:572-635; Q5_K: its
- * scalar Q4_K row, :495-532, over dequant_q5_k's values, docs/design/45-gguf-q5k.md), bit for bit what the exact MoE kernels compute for such a matrix.  parts 1 | 2: the tolerance tile of KR_DECODE_FAST (8 lanes per row, the reference's terms,
+/* The Q5_0 (6) / Q3_K (11) / Q5_K (13) / Q6_K (14) kernels as a stand-alone operator: y[N] = W x for N rows of raw row-major GGUF blocks and an f32 vector x[K], all host pointers;
+ * K a multiple of the block size (32 / 256 / 256 / 256), at most 15360; any N >= 1.  parts 0: the reference's serial f32 chain per row (gguf_kernels.rs:572-635; Q5_K: its
+ * scalar Q4_K row, :495-532, over dequant_q5_k's values, docs/design/45-gguf-q5k.md; Q3_K: the same row over the values of ggml's block definition, docs/design/47-gguf-q3k.md), bit for bit what the exact MoE kernels compute for such a matrix.  parts 1 | 2: the tolerance tile of KR_DECODE_FAST (8 lanes per row, the reference's terms,
  * tree-ordered sums) over the whole row, or over two slices of its blocks whose results are added -- what the two k-waves of the mode's gate|up launch do.
  * Re-tiles into a scratch matrix, one launch, copies back; keeps no state on the engine.  Anything else: KR_ERR_VALUE. */
 int kr_gguf_matvec(kr_engine* e, int type, const uint8_t* blocks, int N, int K, const float* x, float* y, int parts);

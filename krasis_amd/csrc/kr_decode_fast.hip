@@ -919,6 +919,7 @@ __global__ void __launch_bounds__(256) kr_fw13_kernel(const float* p_logits, con
             if (unit < ntp) {
                 if (gm.type == GG_Q6_K) { ag = gg_tile_q6k(gm, unit, GA, lane, ks, KS); au = gg_tile_q6k(um, unit, GA, lane, ks, KS); }
                 else if (gm.type == GG_Q5_K) { ag = gg_tile_q5k(gm, unit, GA, lane, ks, KS); au = gg_tile_q5k(um, unit, GA, lane, ks, KS); }
+                else if (gm.type == GG_Q3_K) { ag = gg_tile_q3k(gm, unit, GA, lane, ks, KS); au = gg_tile_q3k(um, unit, GA, lane, ks, KS); }
                 else { ag = gg_tile_q5_0(gm, unit, GA, lane, ks, KS); au = gg_tile_q5_0(um, unit, GA, lane, ks, KS); }
             }
         } else if (unit < ntp) {
@@ -1547,7 +1548,7 @@ static bool kr_fmoe_ok(const KrFmoeArgs& fa) {
         auto ok_type = [&](int t, int K) {
             if (t == GG_Q4_K) return K % 256 == 0;
             if (t == GG_Q8_0 || t == GG_Q4_0) return K % 32 == 0;
-            return fa.gguf_scalar_tiles != 0 && (t == GG_Q6_K || t == GG_Q5_K ? K % 256 == 0 : (t == GG_Q5_0 && K % 32 == 0));
+            return fa.gguf_scalar_tiles != 0 && (t == GG_Q6_K || t == GG_Q5_K || t == GG_Q3_K ? K % 256 == 0 : (t == GG_Q5_0 && K % 32 == 0));
         };
         auto ok_mat = [&](const GgMat& g, int K, int N) { return ok_type(g.type, K) && g.K == K && g.N == N && N % 8 == 0; };
         if (!fa.act_f32 || !ok_mat(fa.ggate, a.H, a.I) || !ok_mat(fa.gup, a.H, a.I) || !ok_mat(fa.gdown, a.I, a.H) || a.H % 128) return false;

@@ -355,8 +355,8 @@ extern "C" int kr_download_expert_unified(kr_engine* e, int layer, int expert, v
 }
 
 // ---- native GGUF blocks: raw row-major [rows][K/blk] -> lane-tiled records (kr_gguf.hip header comment) ----
-static size_t ggml_block_bytes(int t) { return t == GG_Q4_K ? 144 : t == GG_Q5_K ? 176 : t == GG_Q8_0 ? 34 : t == GG_Q4_0 ? 18 : t == GG_Q5_0 ? 22 : t == GG_Q6_K ? 210 : 0; }
-static int ggml_block_elems(int t) { return (t == GG_Q4_K || t == GG_Q5_K || t == GG_Q6_K) ? 256 : 32; }
+static size_t ggml_block_bytes(int t) { return t == GG_Q3_K ? 110 : t == GG_Q4_K ? 144 : t == GG_Q5_K ? 176 : t == GG_Q8_0 ? 34 : t == GG_Q4_0 ? 18 : t == GG_Q5_0 ? 22 : t == GG_Q6_K ? 210 : 0; }
+static int ggml_block_elems(int t) { return (t == GG_Q3_K || t == GG_Q4_K || t == GG_Q5_K || t == GG_Q6_K) ? 256 : 32; }
 
 static void retile_gguf(int type, const uint8_t* src, int K, int N, uint8_t* dq, uint8_t* dh) {
     const int nt = (N + 7) / 8; const size_t bb = ggml_block_bytes(type); const int nb = K / ggml_block_elems(type);
@@ -375,6 +375,17 @@ static void retile_gguf(int type, const uint8_t* src, int K, int N, uint8_t* dq,
                 for (int l = 0; l < 8; l++) {
                     uint8_t* o = dq + (((size_t)t * nb + b) * 64 + r * 8 + l) * 16;
                     for (int j = 0; j < 4; j++) { o[4 * j] = qs[32 * j + 2 * l]; o[4 * j + 1] = qs[32 * j + 2 * l + 1]; o[4 * j + 2] = qs[32 * j + 16 + 2 * l]; o[4 * j + 3] = qs[32 * j + 17 + 2 * l]; }
+                }
+            }
+        } else if (type == GG_Q3_K) {      // block = {hmask[32], qs[64], scales[12], f16 d}: lane l's record = words qs[32n + {2l, 2l+1, 16+2l, 17+2l}], n = 0, 1, then hmask[{2l, 2l+1, 16+2l, 17+2l}]
+            for (int b = 0; b < nb; b++) {
+                const uint8_t* blk = rp + (size_t)b * 110; const uint8_t* hm = blk; const uint8_t* qs = blk + 32;
+                uint8_t* hd = dh + (((size_t)t * nb + b) * 8 + r) * 16;
+                memcpy(hd, blk + 96, 14);
+                for (int l = 0; l < 8; l++) {
+                    uint8_t* o = dq + (((size_t)t * nb + b) * 64 + r * 8 + l) * 12;
+                    for (int n = 0; n < 2; n++) { o[4 * n] = qs[32 * n + 2 * l]; o[4 * n + 1] = qs[32 * n + 2 * l + 1]; o[4 * n + 2] = qs[32 * n + 16 + 2 * l]; o[4 * n + 3] = qs[32 * n + 17 + 2 * l]; }
+                    o[8] = hm[2 * l]; o[9] = hm[2 * l + 1]; o[10] = hm[16 + 2 * l]; o[11] = hm[17 + 2 * l];
                 }
             }
         } else if (type == GG_Q8_0) {
@@ -474,11 +485,11 @@ extern "C" int kr_upload_expert_gguf(kr_engine* e, int layer, int expert, int in
     return KR_OK;
 }
 
-// synthetic native-GGUF experts for a whole layer (Q4_K, Q5_K, Q8_0, Q5_0 or Q6_K blocks per projection), generated on the GPU -- the GGUF twin of
+// synthetic native-GGUF experts for a whole layer (Q3_K, Q4_K, Q5_K, Q8_0, Q5_0 or Q6_K blocks per projection), generated on the GPU -- the GGUF twin of
 // kr_fill_layer_synthetic with the block distribution SURVEY 8d defines
 extern "C" int kr_fill_layer_synthetic_gguf(kr_engine* e, int layer, int gate_up_type, int down_type, uint64_t seed) {
     if (int rc = check_layer(e, layer)) return rc;
-    for (int t : {gate_up_type, down_type}) if (t != GG_Q4_K && t != GG_Q5_K && t != GG_Q8_0 && t != GG_Q5_0 && t != GG_Q6_K) return kr_fail(KR_ERR_VALUE, "synthetic GGUF fill supports Q4_K (12), Q5_K (13), Q8_0 (8), Q5_0 (6) and Q6_K (14), got %d", t);
+    for (int t : {gate_up_type, down_type}) if (t != GG_Q3_K && t != GG_Q4_K && t != GG_Q5_K && t != GG_Q8_0 && t != GG_Q5_0 && t != GG_Q6_K) return kr_fail(KR_ERR_VALUE, "synthetic GGUF fill supports Q3_K (11), Q4_K (12), Q5_K (13), Q8_0 (8), Q5_0 (6) and Q6_K (14), got %d", t);
     KR_HIP(hipSetDevice(e->device));
     Layer& L = e->layers[layer];
     const int H = e->cfg.hidden_size, I = e->cfg.moe_intermediate_size, E = e->cfg.n_routed_experts;
@@ -496,12 +507,12 @@ extern "C" int kr_fill_layer_synthetic_gguf(kr_engine* e, int layer, int gate_up
     return KR_OK;
 }
 
-// The Q5_0 / Q5_K / Q6_K kernels as a stand-alone operator a test can hold (the precedent: kr_decode_matmul_rows): raw row-major blocks and an f32 vector on the host,
+// The Q5_0 / Q3_K / Q5_K / Q6_K kernels as a stand-alone operator a test can hold (the precedent: kr_decode_matmul_rows): raw row-major blocks and an f32 vector on the host,
 // re-tiled into a scratch matrix, ONE launch of the device functions the MoE kernels call, y copied back.  Nothing stays on the engine.
 extern "C" int kr_gguf_matvec(kr_engine* e, int type, const uint8_t* blocks, int N, int K, const float* x, float* y, int parts) {
     if (!e) return kr_fail(KR_ERR_VALUE, "null engine");
     if (!blocks || !x || !y) return kr_fail(KR_ERR_VALUE, "null pointer argument");
-    if (type != GG_Q5_0 && type != GG_Q5_K && type != GG_Q6_K) return kr_fail(KR_ERR_VALUE, "kr_gguf_matvec: type %d is none of Q5_0 (6), Q5_K (13), Q6_K (14)", type);
+    if (type != GG_Q5_0 && type != GG_Q3_K && type != GG_Q5_K && type != GG_Q6_K) return kr_fail(KR_ERR_VALUE, "kr_gguf_matvec: type %d is none of Q5_0 (6), Q3_K (11), Q5_K (13), Q6_K (14)", type);
     if (parts < 0 || parts > 2) return kr_fail(KR_ERR_VALUE, "kr_gguf_matvec: parts %d (0 = exact chain, 1 | 2 = tolerance tile)", parts);
     if (N < 1 || K < 1 || K % ggml_block_elems(type) || K > 15360) return kr_fail(KR_ERR_VALUE, "kr_gguf_matvec: shape N %d, K %d (K: a multiple of %d, at most 15360)", N, K, ggml_block_elems(type));
     std::lock_guard<std::mutex> lk(e->mu);
@@ -934,7 +945,7 @@ int kr_ensure_wsum(kr_engine* e, MatSet& ms, hipStream_t st) {
 #define KR_PF_PAIRS 81920
 
 // ---- native GGUF layers (moe_forward_gguf, moe.rs:990): Q4_K / Q8_0 blocks on the int8-MFMA grouped GEMM (kr_gguf_prefill.hip); layers
-//      whose block types have no MFMA form (Q4_0 / Q5_0 / Q5_K / Q6_K) walk the batch through the streaming kernels.  The caller holds e->mu.
+//      whose block types have no MFMA form (Q4_0 / Q5_0 / Q3_K / Q5_K / Q6_K) walk the batch through the streaming kernels.  The caller holds e->mu.
 static int gg_ensure_ws(kr_engine* e, GgufSet& g, hipStream_t st) {
     if (g.ws.p || !g.allocated()) return KR_OK;
     g.ws_stride = kr_gpf_ws_bytes(g.type, g.K, g.N);
@@ -965,7 +976,7 @@ static int gg_ensure_fast(kr_engine* e, GgufSet& a, GgufSet* b, hipStream_t st) 
     return KR_OK;
 }
 // The KR_GEMM_FAST form of one projection: GG_FAST_COPY = the re-tiled copy above (Q4_K over whole super-blocks, Q8_0 over whole 128-k groups -- V2-Lite's down
-// projection: K = 1408 = 11 groups), GG_FAST_NATIVE = the lane records as they are (Q6_K, Q5_K, Q5_0: kr_gguf_prefill_h.hip, no copy), GG_FAST_NONE = neither.
+// projection: K = 1408 = 11 groups), GG_FAST_NATIVE = the lane records as they are (Q6_K, Q5_K, Q3_K, Q5_0: kr_gguf_prefill_h.hip, no copy), GG_FAST_NONE = neither.
 enum { GG_FAST_NONE = 0, GG_FAST_COPY = 1, GG_FAST_NATIVE = 2 };
 static int gg_fast_form(const GgufSet& g, int K) {
     if (g.N % 8) return GG_FAST_NONE;
@@ -1014,7 +1025,7 @@ static int moe_prefill_gguf_fast(kr_engine* e, Layer& L, const void* x_bf16, con
     const bool use_shared = L.gguf_shared && !routed_only;
     const int SI = L.shared_inter;
     if (int rc = gg_ensure_fast_layer(e, L, use_shared, st)) return rc;
-    // per projection: the copy through the tolerance GEMM of kr_prefill_h.hip, or the native records through kr_launch_gfh_gemm (Q6_K, Q5_K, Q5_0)
+    // per projection: the copy through the tolerance GEMM of kr_prefill_h.hip, or the native records through kr_launch_gfh_gemm (Q6_K, Q5_K, Q3_K, Q5_0)
     const bool n13 = gg_fast_form(L.g_gate, H) == GG_FAST_NATIVE, n2 = gg_fast_form(L.g_down, I) == GG_FAST_NATIVE;
     const bool sn13 = use_shared && gg_fast_form(L.gs_gate, H) == GG_FAST_NATIVE, sn2 = use_shared && gg_fast_form(L.gs_down, SI) == GG_FAST_NATIVE;
     const int pairs = e->pf_pairs > 0 ? e->pf_pairs : KR_PF_PAIRS;

@@ -4,7 +4,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
-enum { GG_Q4_0 = 2, GG_Q5_0 = 6, GG_Q8_0 = 8, GG_Q4_K = 12, GG_Q5_K = 13, GG_Q6_K = 14 };   // GGML type ids (gguf.rs:15-31)
+enum { GG_Q4_0 = 2, GG_Q5_0 = 6, GG_Q8_0 = 8, GG_Q3_K = 11, GG_Q4_K = 12, GG_Q5_K = 13, GG_Q6_K = 14 };   // GGML type ids (gguf.rs:15-31)
 
 struct GgMat {          // one projection [K -> N rows] of one (or all) expert(s) in the lane-tiled GGUF layout
     const void* q; const void* h; int type, K, N; size_t q_stride, h_stride;
@@ -19,7 +19,7 @@ struct GgMoeArgs {
 void kr_launch_gguf_moe(const GgMoeArgs& a, hipStream_t st);
 size_t gg_q_bytes(int type, int K, int N);
 size_t gg_h_bytes(int type, int K, int N);
-// one Q5_0 / Q5_K / Q6_K matrix against an f32 vector (kr_gguf_matvec): parts 0 = the exact row chain, 1 | 2 = the tolerance tile over the whole row / two slices; non-zero: refused
+// one Q5_0 / Q3_K / Q5_K / Q6_K matrix against an f32 vector (kr_gguf_matvec): parts 0 = the exact row chain, 1 | 2 = the tolerance tile over the whole row / two slices; non-zero: refused
 int kr_launch_gguf_matvec(const GgMat& m, const float* x, float* y, int parts, hipStream_t st);
 
 // ---- prompt pass: GGUF blocks on the int8-MFMA grouped GEMM (kr_gguf_prefill.hip) ----
@@ -36,7 +36,7 @@ void kr_launch_gpf_gemm(const GgMat& m, const void* ws, size_t ws_stride, const 
 void kr_launch_gq_repack(const GgMat& m, int n_experts, void* q_out, size_t q_stride, void* qs_out, void* qo_out, size_t qs_stride, int tile_off, int tiles_out, hipStream_t st);
 // Q8_0 -> the tolerance GEMM's INT8 operand form (INT8 lane tiles + one f16 scale per 32-wide block)
 void kr_launch_gq8_repack(const GgMat& m, int n_experts, void* q_out, size_t q_stride, void* qs_out, size_t qs_stride, int tile_off, hipStream_t st);
-// ---- KR_GEMM_FAST on the NATIVE lane records (kr_gguf_prefill_h.hip): Q6_K / Q5_K (K % 256 == 0) and Q5_0 (K % 32 == 0), N % 8 == 0; no derived copy ----
+// ---- KR_GEMM_FAST on the NATIVE lane records (kr_gguf_prefill_h.hip): Q6_K / Q5_K / Q3_K (K % 256 == 0) and Q5_0 (K % 32 == 0), N % 8 == 0; no derived copy ----
 // a_h / a_mul: the f16 rows and row multipliers of kr_launch_pfh_rows_bf16 / kr_launch_pfh_act.  sort == nullptr: dense rows (single_expert_rows) of expert 0.
 // out: f32 rows (multiplier applied) or, out_f16, f16 rows of raw accumulators for kr_launch_pf_combine_f16rows; columns [col_off, col_off + N) of rows out_ld apart
 bool kr_gfh_type_supported(int type, int K, int N);

@@ -1,5 +1,5 @@
 // kr_gguf.hip -- native GGUF block experts on gfx950: Q4_K / Q8_0 / Q4_0 with INT16 activations (exact integer dots),
-// Q5_0 / Q6_K through the reference's scalar f32 form, Q5_K through the same form over dequant_q5_k's values (gguf.rs:740).  Replaces src/gguf_kernels.rs (matvec_q4_k_avx2 :271, matvec_q8_0_avx2 :379,
+// Q5_0 / Q6_K through the reference's scalar f32 form, Q5_K through the same form over dequant_q5_k's values (gguf.rs:740), Q3_K over the values of ggml's block definition (docs/design/47-gguf-q3k.md).  Replaces src/gguf_kernels.rs (matvec_q4_k_avx2 :271, matvec_q8_0_avx2 :379,
 // matvec_q4_0_avx2 :436, scalar fallbacks :495-635, quantize_*_to_int16 :110-172, expert_forward_gguf :690) and moe_forward_gguf
 // (src/moe.rs:990) bit for bit: the 8 AVX lanes of a row are 8 GPU lanes that see exactly the bytes their AVX twin sees
 // (bytes {2l, 2l+1, 16+2l, 16+2l+1} of every 32-byte chunk), run the same per-sub-block fma chain and the same hsum tree.
@@ -10,6 +10,10 @@
 //   Q5_K  q as Q4_K, unchanged (low nibbles of chunk j = elements 64j + p, high nibbles = elements 64j + 32 + p, p = the byte's position in the 32-byte chunk)
 //         h[rows/8][blocks][8 rows] x 48 B           : Q4_K's 16 B, then eight u32, one per lane l: {qh[2l], qh[2l+1], qh[16+2l], qh[17+2l]} -- byte i carries the fifth
 //         bits of byte i of every chunk of lane l's record: bit 2j for the low nibble, bit 2j + 1 for the high nibble.  176 B per block, as in the file
+//   Q3_K  q[rows/8][blocks][8 rows][8 lanes] x 12 B  : lane record = words n = 0, 1: bytes qs[32n + {2l, 2l+1, 16+2l, 17+2l}] (bits 2j of a byte = the low two bits of
+//         element 128n + 32j + p, p = the byte's position in the 32 bytes), word 2: hmask[{2l, 2l+1, 16+2l, 17+2l}] (bit 4n + j = the high bit of the same element)
+//         h[rows/8][blocks][8 rows] x 16 B           : {12 scale bytes, f16 d, 2 bytes of padding}.  112 B per block against 110 in the file; the one lane per row of the
+//         exact kernel reads the row's 96 B of records in six 16-byte loads and the header in one, a lane of the tolerance tile its 12 B record and the header
 //   Q8_0  q[rows/8][blocks/4][8][8] x 16 B (4 blocks x 4 bytes), h[rows/8][blocks/4][8] x 8 B (4 x f16 d)
 //   Q4_0  q[rows/8][blocks/8][8][8] x 16 B (8 blocks x 2 bytes), h[rows/8][blocks/8][8] x 16 B (8 x f16 d)
 //   Q5_0  q as Q4_0: lane l's record of a group of 8 blocks = 8 x bytes {qs[2l], qs[2l+1]}, the nibbles of elements {2l, 2l+1, 16+2l, 17+2l}
@@ -169,12 +173,60 @@ __device__ __forceinline__ float gg_row_q5k(const GgMat& m, int r, const float* 
     }
     return sum;
 }
-__device__ __forceinline__ float gg_row_scalar(const GgMat& m, int r, const float* x) { return m.type == GG_Q6_K ? gg_row_q6k(m, r, x) : m.type == GG_Q5_K ? gg_row_q5k(m, r, x) : gg_row_q5_0(m, r, x); }
+// Q3_K (docs/design/47-gguf-q3k.md): the same two-level chain over w = (d sc_s) q, the values kr_gguf_dev.h defines: per super-block s = 0, s += w_k x_k for k = 0 .. 255 in
+// element order, then sum += s.  Element 128 n + 32 j + p sits in record (p & 15) >> 1, byte (p & 1) + 2 (p >> 4): its low two bits at bit 2j of word n, its high bit at bit
+// 4n + j of word 2.  The row's eight 12-byte records are 96 B side by side: six 16-byte loads, and one for the header.
+#define GG_PFR3K 2
+__device__ __forceinline__ float gg_row_q3k(const GgMat& m, int r, const float* x) {
+    const int tile = r >> 3, row = r & 7, nb = m.K / 256;
+    const u32x4* q = reinterpret_cast<const u32x4*>(m.q) + ((size_t)tile * nb * 8 + row) * 6;
+    const u32x4* h = reinterpret_cast<const u32x4*>(m.h) + (size_t)tile * nb * 8 + row;
+    float sum = 0.0f;
+    for (int b0 = 0; b0 < nb; b0 += GG_PFR3K) {
+        u32x4 wv[GG_PFR3K][6], hv[GG_PFR3K];
+#pragma unroll
+        for (int u = 0; u < GG_PFR3K; u++) {
+            const int bb = b0 + u < nb ? b0 + u : nb - 1;
+#pragma unroll
+            for (int i = 0; i < 6; i++) wv[u][i] = kr_ldg_nt(q + (size_t)bb * 48 + i);
+            hv[u] = kr_ldg_nt(h + (size_t)bb * 8);
+        }
+#pragma unroll
+        for (int u = 0; u < GG_PFR3K; u++) {
+            const int b = b0 + u;
+            if (b < nb) {
+                uint32_t w[24];      // record l: words 3l (qs, n = 0), 3l + 1 (qs, n = 1), 3l + 2 (hmask)
+#pragma unroll
+                for (int i = 0; i < 6; i++) { w[4 * i] = wv[u][i].x; w[4 * i + 1] = wv[u][i].y; w[4 * i + 2] = wv[u][i].z; w[4 * i + 3] = wv[u][i].w; }
+                const float d = gg_f16(hv[u].w & 0xFFFFu);
+                const float* in = x + b * 256;
+                float s = 0.0f;
+#pragma unroll
+                for (int c = 0; c < 8; c++) {      // chunk c = 4 n + j
+                    const int n = c >> 2, j = c & 3;
+                    const float d0 = d * (float)gg_q3k_scale(2 * c, hv[u].x, hv[u].y, hv[u].z), d1 = d * (float)gg_q3k_scale(2 * c + 1, hv[u].x, hv[u].y, hv[u].z);
+#pragma unroll
+                    for (int p = 0; p < 32; p++) {
+                        const int l = (p & 15) >> 1, sft = ((p & 1) + 2 * (p >> 4)) * 8;
+                        const int qv = (int)(((w[3 * l + n] >> (sft + 2 * j)) & 3u) | (((w[3 * l + 2] >> (sft + c)) & 1u) << 2)) - 4;
+                        const float wk = (p < 16 ? d0 : d1) * (float)qv;
+                        s += wk * in[c * 32 + p];
+                    }
+                }
+                sum += s;
+            }
+        }
+    }
+    return sum;
+}
+__device__ __forceinline__ float gg_row_scalar(const GgMat& m, int r, const float* x) {
+    return m.type == GG_Q6_K ? gg_row_q6k(m, r, x) : m.type == GG_Q5_K ? gg_row_q5k(m, r, x) : m.type == GG_Q3_K ? gg_row_q3k(m, r, x) : gg_row_q5_0(m, r, x);
+}
 
 // rows of one workgroup: the integer types take `tiles_per_wg` 8-row tiles on four waves, the scalar types one row per thread (GG_BLOCK rows)
 __device__ __forceinline__ int gg_wg_tiles(int type, int tiles_per_wg) { return gg_int_path(type) ? tiles_per_wg : GG_BLOCK / 8; }
 
-// SC: the launch holds a Q5_0 / Q5_K / Q6_K matrix.  The kernels without one carry no scalar-row code: the integer types keep their registers and their occupancy
+// SC: the launch holds a Q5_0 / Q3_K / Q5_K / Q6_K matrix.  The kernels without one carry no scalar-row code: the integer types keep their registers and their occupancy
 template <bool SC>
 __device__ __forceinline__ void gg_run_rows(const GgMat& m, const GgAct& A, float* out, int row_base_out, int tile0, int ntiles_wg) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -269,7 +321,7 @@ void kr_launch_gguf_moe(const GgMoeArgs& a, hipStream_t st) {
     }
 }
 
-// ---- kr_gguf_matvec: y = W x of one Q5_0 / Q5_K / Q6_K matrix with the device functions above as one launch.  parts 0: the exact chain, one lane per row, GG_BLOCK rows a
+// ---- kr_gguf_matvec: y = W x of one Q5_0 / Q3_K / Q5_K / Q6_K matrix with the device functions above as one launch.  parts 0: the exact chain, one lane per row, GG_BLOCK rows a
 //      workgroup; parts 1 | 2: the tolerance tile, one 8-row tile per wave, the row's blocks walked whole or as two slices whose results are added (what the two
 //      k-waves of the mode's gate|up launch do) ----
 __global__ void __launch_bounds__(GG_BLOCK) kr_gguf_matvec_kernel(const GgMat m, const float* x, float* y, int parts) {
@@ -304,13 +356,14 @@ size_t gg_q_bytes(int type, int K, int N) {
         case GG_Q4_0: return nt * (((K / 32) + 7) / 8) * 64 * 16;
         case GG_Q5_0: return nt * (((K / 32) + 7) / 8) * 64 * 16;
         case GG_Q6_K: return nt * (K / 256) * 2 * 64 * 12;
+        case GG_Q3_K: return nt * (K / 256) * 64 * 12;
         default: return 0;
     }
 }
 size_t gg_h_bytes(int type, int K, int N) {
     const size_t nt = (size_t)(N + 7) / 8;
     switch (type) {
-        case GG_Q4_K: return nt * (K / 256) * 8 * 16;
+        case GG_Q4_K: case GG_Q3_K: return nt * (K / 256) * 8 * 16;
         case GG_Q5_K: return nt * (K / 256) * 8 * 48;
         case GG_Q8_0: return nt * (((K / 32) + 3) / 4) * 8 * 8;
         case GG_Q4_0: return nt * (((K / 32) + 7) / 8) * 8 * 16;

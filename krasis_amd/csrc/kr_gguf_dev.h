@@ -374,11 +374,69 @@ __device__ __forceinline__ float gg_tile_q5k(const GgMat& m, int tile, const GgA
     return kr_hsum8(acc.x + acc.y);
 }
 
+// ---- Q3_K (docs/design/47-gguf-q3k.md): the reference has neither a de-quantizer nor a matvec for the type; from ggml's block {hmask[32], qs[64], scales[12], f16 d} the value
+//      of element 128 n + 32 j + p is w = (d sc_s) q, q = ((qs[32n + p] >> 2j) & 3 | hmask[p] bit (4n + j) << 2) - 4, s = 8n + 2j + (p >> 4), sc_s the 6-bit scale minus 32, two
+//      rounded f32 products; the exact chain is the scalar Q4_K row over these values (gg_row_q3k, kr_gguf.hip).  The tile: lane l owns a 12-byte record -- words n = 0, 1 =
+//      qs[32n + {2l, 2l+1, 16+2l, 17+2l}], word 2 = hmask[{2l, 2l+1, 16+2l, 17+2l}] -- the elements {2l, 2l+1, 16+2l, 17+2l} of each of the block's eight 32-element chunks
+//      c = 4n + j.  Four codes at a time on whole words: two bits of word n under 0x03030303, bit c of every hmask byte under 0x04040404; bytes 0, 1 belong to sub-block 2c,
+//      bytes 2, 3 to sub-block 2c + 1.  Values against A.f32v in one packed accumulator in block order, then kr_hsum8; [part, parts) slices super-blocks. ----
+#define GG_PF3K 4     // super-blocks requested ahead -- per lane 3 record + 4 header words a block
+// the four 6-bit scales 4g .. 4g + 3 (g < 4) of a Q3_K block as the bytes of one word, 32 not yet subtracted; s0, s1, s2: the 12 scale bytes as words
+__device__ __forceinline__ uint32_t gg_q3k_scales4(int g, uint32_t s0, uint32_t s1, uint32_t s2) {
+    const uint32_t lo = ((g & 1 ? s1 : s0) >> (g & 2 ? 4 : 0)) & 0x0F0F0F0Fu;
+    return lo | (((s2 >> (2 * g)) & 0x03030303u) << 4);
+}
+// scale s < 16 of a Q3_K block, in -32 .. 31
+__device__ __forceinline__ int gg_q3k_scale(int s, uint32_t s0, uint32_t s1, uint32_t s2) { return (int)((gg_q3k_scales4(s >> 2, s0, s1, s2) >> ((s & 3) * 8)) & 0xFFu) - 32; }
+// four codes (the bytes of `codes`, 0 .. 7) of one chunk: bytes 0, 1 (sub-block scale d_lo) against x[0..1], bytes 2, 3 (d_hi) against x[16..17]
+__device__ __forceinline__ void gg_q3k_four(gg_f32x2& acc, float d_lo, float d_hi, uint32_t codes, const float* x) {
+    const gg_f32x2 dl = {d_lo, d_lo}, dh = {d_hi, d_hi};
+    const gg_f32x2 q01 = {(float)(codes & 0xFFu) - 4.0f, (float)((codes >> 8) & 0xFFu) - 4.0f}, q23 = {(float)((codes >> 16) & 0xFFu) - 4.0f, (float)(codes >> 24) - 4.0f};
+    const gg_f32x2 x01 = *reinterpret_cast<const gg_f32x2*>(x), x23 = *reinterpret_cast<const gg_f32x2*>(x + 16);
+    acc += (dl * q01) * x01;
+    acc += (dh * q23) * x23;
+}
+__device__ __forceinline__ float gg_tile_q3k(const GgMat& m, int tile, const GgAct& A, int lane, int part = 0, int parts = 1) {
+    const int l = lane & 7, row = lane >> 3;
+    const int nb = m.K / 256, per = (nb + parts - 1) / parts, b_lo = part * per, b_hi = b_lo + per < nb ? b_lo + per : nb;
+    const uint32_t* q = reinterpret_cast<const uint32_t*>(m.q) + ((size_t)tile * nb * 64 + lane) * 3;      // [block][8 rows][8 lanes] x 12 B
+    const u32x4* h = reinterpret_cast<const u32x4*>(m.h) + (size_t)tile * nb * 8 + row;                     // [block][8 rows] x 16 B
+    gg_f32x2 acc = {0.0f, 0.0f};
+    for (int b0 = b_lo; b0 < b_hi; b0 += GG_PF3K) {
+        uint32_t wv[GG_PF3K][3]; u32x4 hv[GG_PF3K];
+#pragma unroll
+        for (int u = 0; u < GG_PF3K; u++) {
+            const int bb = b0 + u < b_hi ? b0 + u : (b_hi > 0 ? b_hi - 1 : 0);
+#pragma unroll
+            for (int i = 0; i < 3; i++) wv[u][i] = kr_ldg_nt(q + (size_t)bb * 192 + i);
+            hv[u] = kr_ldg_nt(h + (size_t)bb * 8);
+        }
+#pragma unroll
+        for (int u = 0; u < GG_PF3K; u++) {
+            const int b = b0 + u;
+            if (b < b_hi) {
+                const u32x4 hd = hv[u];
+                const float d = gg_f16(hd.w & 0xFFFFu);
+                const uint32_t hm = wv[u][2];
+#pragma unroll
+                for (int c = 0; c < 8; c++) {      // chunk c = 4 n + j: sub-blocks 2c, 2c + 1 = bytes (2c & 3), (2c & 3) + 1 of scale word c >> 1
+                    const uint32_t s4 = gg_q3k_scales4(c >> 1, hd.x, hd.y, hd.z) >> ((c & 1) * 16);
+                    const float d_lo = d * (float)((int)(s4 & 0xFFu) - 32), d_hi = d * (float)((int)((s4 >> 8) & 0xFFu) - 32);
+                    const uint32_t codes = ((wv[u][c >> 2] >> (2 * (c & 3))) & 0x03030303u) | (((hm >> c) & 0x01010101u) << 2);
+                    gg_q3k_four(acc, d_lo, d_hi, codes, A.f32v + b * 256 + c * 32 + 2 * l);
+                }
+            }
+        }
+    }
+    return kr_hsum8(acc.x + acc.y);
+}
+
 __host__ __device__ static inline bool gg_int_path(int t) { return t == GG_Q4_K || t == GG_Q8_0 || t == GG_Q4_0; }
-__host__ __device__ static inline bool gg_scalar_type(int t) { return t == GG_Q5_0 || t == GG_Q5_K || t == GG_Q6_K; }
+__host__ __device__ static inline bool gg_scalar_type(int t) { return t == GG_Q5_0 || t == GG_Q3_K || t == GG_Q5_K || t == GG_Q6_K; }
 // one 8-row tile of a scalar type in the tolerance form
 __device__ __forceinline__ float gg_tile_scalar(const GgMat& m, int tile, const GgAct& A, int lane, int part = 0, int parts = 1) {
-    return m.type == GG_Q6_K ? gg_tile_q6k(m, tile, A, lane, part, parts) : m.type == GG_Q5_K ? gg_tile_q5k(m, tile, A, lane, part, parts) : gg_tile_q5_0(m, tile, A, lane, part, parts);
+    return m.type == GG_Q6_K ? gg_tile_q6k(m, tile, A, lane, part, parts) : m.type == GG_Q5_K ? gg_tile_q5k(m, tile, A, lane, part, parts)
+         : m.type == GG_Q3_K ? gg_tile_q3k(m, tile, A, lane, part, parts) : gg_tile_q5_0(m, tile, A, lane, part, parts);
 }
 
 __device__ __forceinline__ GgMat gg_expert_mat(const GgMat& base, int e) {

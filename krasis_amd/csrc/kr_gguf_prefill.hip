@@ -345,7 +345,8 @@ __global__ void __launch_bounds__(256, 2) kr_gpf_gemm_kernel(const GpfGemmArgs a
 // ------------------------------------------------------------------------------------------
 // synthetic GGUF experts (SURVEY 8d defines the distribution the reference's generator lacks): quant bytes and the 12 packed scale bytes
 // are raw hash words, d = f16((0.005 + u * 0.045) / 63), dmin = f16(8 d); Q8_0: d = f16((0.005 + u * 0.045) / 127); Q5_0: d = f16((0.005 + u * 0.045) / 15), raw qh words;
-// Q6_K: d = f16((0.005 + u * 0.045) / 31 / 127), raw scale bytes; Q5_K: Q4_K's rule with d halved (d = f16((0.005 + u * 0.045) / 126), dmin = f16(16 d): Q4_K's offsets), raw fifth-bit words
+// Q6_K: d = f16((0.005 + u * 0.045) / 31 / 127), raw scale bytes; Q5_K: Q4_K's rule with d halved (d = f16((0.005 + u * 0.045) / 126), dmin = f16(16 d): Q4_K's offsets), raw fifth-bit words;
+// Q3_K: raw code, hmask and scale bytes, d = f16((0.005 + u * 0.045) * 15 / 128) -- Q4_K's d times 945 / 128, so that max |w| = 32 * 4 d stays at Q4_K's 63 * 15 d
 // ------------------------------------------------------------------------------------------
 __device__ __forceinline__ uint64_t gpf_mix(uint64_t x) {
     x += 0x9E3779B97F4A7C15ull; x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull; x = (x ^ (x >> 27)) * 0x94D049BB133111EBull; return x ^ (x >> 31);
@@ -373,6 +374,10 @@ __global__ void kr_gpf_fill_h_kernel(char* h, size_t n_rec, int type, uint64_t s
                 u32x4 f = {(uint32_t)ra, (uint32_t)(ra >> 32), (uint32_t)rb, (uint32_t)(rb >> 32)};
                 *reinterpret_cast<u32x4*>(h + i * 48 + 16 + k * 16) = f;
             }
+        } else if (type == GG_Q3_K) {   // 12 scale bytes (raw words), then d = f16((0.005 + u * 0.045) * 15 / 128) and 2 bytes of padding: max |w| = 128 d = Q4_K's 63 * 15 d
+            const uint32_t db = __half_as_ushort(__float2half(dval((uint32_t)(r1 >> 32), 128.0f / 15.0f)));
+            u32x4 o = {(uint32_t)r0, (uint32_t)(r0 >> 32), (uint32_t)r1, db};
+            *reinterpret_cast<u32x4*>(h + i * 16) = o;
         } else if (type == GG_Q5_0) {   // 8 x f16 d = f16((0.005 + u * 0.045) / 15), then 8 x u32 qh (raw words)
             uint32_t w[12];
 #pragma unroll
@@ -398,7 +403,7 @@ __global__ void kr_gpf_fill_h_kernel(char* h, size_t n_rec, int type, uint64_t s
 }
 void kr_launch_gpf_fill_synth(void* q, size_t q_bytes, void* h, size_t h_bytes, int type, uint64_t seed, hipStream_t st) {
     hipLaunchKernelGGL(kr_gpf_fill_q_kernel, dim3(2048), dim3(256), 0, st, (uint32_t*)q, q_bytes / 4, seed);
-    hipLaunchKernelGGL(kr_gpf_fill_h_kernel, dim3(512), dim3(256), 0, st, (char*)h, h_bytes / (type == GG_Q4_K ? 16 : type == GG_Q5_0 || type == GG_Q5_K ? 48 : type == GG_Q6_K ? 20 : 8), type, seed ^ 0x5DEECE66Dull);
+    hipLaunchKernelGGL(kr_gpf_fill_h_kernel, dim3(512), dim3(256), 0, st, (char*)h, h_bytes / (type == GG_Q4_K || type == GG_Q3_K ? 16 : type == GG_Q5_0 || type == GG_Q5_K ? 48 : type == GG_Q6_K ? 20 : 8), type, seed ^ 0x5DEECE66Dull);
 }
 
 // ------------------------------------------------------------------------------------------

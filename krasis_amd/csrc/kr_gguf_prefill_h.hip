@@ -41,7 +41,13 @@
 // is that rounding); Q5_0 16 d, exact.  The factor 16 keeps small scales out of the f16 subnormals (Q6_K's d is ~1e-5 for weights of ~0.05).  Products are
 // accumulated by the MFMA in f32.  Neither type has an offset term once the code is centred: no per-32 sums of A, no extra k columns.
 //
-// Limits: Q6_K K % 256 == 0, Q5_0 K % 32 == 0 (the last block group may be ragged: its missing blocks get scale 0, its A chunks re-read the head of the
+// Q5_K and Q3_K (docs/design/45-gguf-q5k.md, 47-gguf-q3k.md) came later and share Q5_0's A image.  Q3_K: 12-byte records, q[rows/8][blocks][8 rows][8 lanes], and 16-byte
+// headers; lane l of a super-block holds elements {2l, 2l + 1, 16 + 2l, 17 + 2l} of each 32-element chunk c < 8, so a row's 256 values are laid [record l][chunk c][4 values] --
+// Q5_0's image with "block u" read as "chunk c", the same four 4-byte pieces per 16-byte chunk of A.  Bs holds a tile's 768 B verbatim, [16 tiles][784], as Q6_K's does.  The
+// 3-bit code (two bits of a qs word, one bit of the hmask word) goes under the exponent of 1024.0 and 1028 is subtracted: q - 4, exact; the scale 16 d sc (sc the 6-bit scale
+// minus 32, formed the same way with 1056) is rounded once to f16.  33 792 + 12 544 + 768 = 47 104 B of LDS.
+//
+// Limits: Q6_K, Q5_K, Q3_K K % 256 == 0, Q5_0 K % 32 == 0 (the last block group may be ragged: its missing blocks get scale 0, its A chunks re-read the head of the
 // stage), N % 8 == 0, K % 8 == 0 rows of at most 4 GiB in all (32-bit row offsets, as the sibling).  Loads are never masked: a row past the tile reads row 0,
 // a column tile past the last re-reads the last; the stores are guarded.
 #include <hip/hip_runtime.h>
@@ -54,6 +60,7 @@
 #include "kr_prefill.h"
 #include "kr_gguf.h"
 #include "kr_pfh_dev.h"
+#include "kr_gguf_dev.h"               // gg_q3k_scales4
 
 #define GFH_BM 64
 #define GFH_BN 128
@@ -61,6 +68,7 @@
 #define GFH_LDA (GFH_KS * 2 + 16)      // bytes per A row of a stage
 #define GFH_T6 1552                    // Q6_K: bytes per 8-column tile of a stage (2 halves x 768 B + 16)
 #define GFH_LDB5 144                   // Q5_0: bytes per column of a stage (8 records x 16 B + 16)
+#define GFH_T3 784                     // Q3_K: bytes per 8-column tile of a stage (768 B + 16: tile stride = 4 banks mod 64, as GFH_T6)
 
 struct KrGfhArgs {
     GgMat m;
@@ -89,11 +97,14 @@ __device__ __forceinline__ void gfh_q5k4(uint32_t codes, v2h off, v2h s, v2h nm,
 
 template <int TYPE>
 __global__ void __launch_bounds__(256, 2) kr_gfh_gemm_kernel(const KrGfhArgs a) {
-    static_assert(TYPE == GG_Q6_K || TYPE == GG_Q5_0 || TYPE == GG_Q5_K, "lane-record form of Q6_K, Q5_0 and Q5_K");
+    static_assert(TYPE == GG_Q6_K || TYPE == GG_Q5_0 || TYPE == GG_Q5_K || TYPE == GG_Q3_K, "lane-record form of Q6_K, Q5_0, Q5_K and Q3_K");
     constexpr bool Q6 = TYPE == GG_Q6_K, Q5K = TYPE == GG_Q5_K;      // Q5_K shares Q5_0's stage geometry: 16-byte records, 48-byte headers, the same As / Bs maps
-    constexpr int LDA = GFH_LDA, BS_BYTES = Q6 ? 16 * GFH_T6 : GFH_BN * GFH_LDB5;
-    constexpr int NBC = Q6 ? 6 : 4;               // 16-byte record chunks per thread per stage
-    constexpr int NHW = Q6 ? 5 : Q5K ? 8 : 12;    // header words per lane per stage (Q5_K: the 16-byte head and the fifth-bit words of the lane's four records)
+    constexpr bool Q3K = TYPE == GG_Q3_K;                            // Q3_K: Q5_0's As map (its "block u" = the 32-element chunk c), tile-wise Bs of 12-byte records as Q6_K
+    constexpr int LDA = GFH_LDA, BS_BYTES = Q6 ? 16 * GFH_T6 : Q3K ? 16 * GFH_T3 : GFH_BN * GFH_LDB5;
+    constexpr int NBC = Q6 ? 6 : Q3K ? 3 : 4;     // 16-byte record chunks per thread per stage
+    constexpr int NHW = Q6 ? 5 : Q5K ? 8 : Q3K ? 4 : 12;    // header words per lane per stage (Q5_K: the 16-byte head and the fifth-bit words of the lane's four records; Q3_K: the 16-byte header)
+    constexpr int TB = Q6 ? 1536 : Q3K ? 768 : 1024;        // record bytes of an 8-column tile per stage
+    constexpr int HB = Q6 ? 20 : Q3K ? 16 : 48;             // header bytes of a column per stage
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* As = smem;
     char* Bs = As + GFH_BM * LDA;
@@ -132,17 +143,17 @@ __global__ void __launch_bounds__(256, 2) kr_gfh_gemm_kernel(const KrGfhArgs a) 
     int col[1] = {n0 + wave * 32 + n31};
     const int lc = wave * 32 + n31, cc = col[0] < N ? col[0] : N - 1;
     // this lane's column: header base (bytes, without the stage term) and record base inside Bs
-    const uint32_t hbase = Q6 ? (uint32_t)(((cc >> 3) * nst * 8 + (cc & 7)) * 20) : (uint32_t)(((cc >> 3) * nst * 8 + (cc & 7)) * 48);
-    const int bcol = Q6 ? (lc >> 3) * GFH_T6 + (lc & 7) * 96 : lc * GFH_LDB5;
+    const uint32_t hbase = (uint32_t)(((cc >> 3) * nst * 8 + (cc & 7)) * HB);
+    const int bcol = Q6 ? (lc >> 3) * GFH_T6 + (lc & 7) * 96 : Q3K ? (lc >> 3) * GFH_T3 + (lc & 7) * 96 : lc * GFH_LDB5;
 
-    // record chunks of a stage: Q6_K 16 tiles x 96 chunks (a tile's super-block is 1536 contiguous bytes), Q5_0 16 tiles x 64 chunks (1024 bytes)
+    // record chunks of a stage: Q6_K 16 tiles x 96 chunks (a tile's super-block is 1536 contiguous bytes), Q5_0 16 tiles x 64 chunks (1024 bytes), Q3_K 16 tiles x 48 chunks (768 bytes)
     uint32_t bsrc[NBC], bdst[NBC];
 #pragma unroll
     for (int j = 0; j < NBC; j++) {
-        const int idx = tid + j * 256, t8 = Q6 ? idx / 96 : idx >> 6, c = Q6 ? idx - t8 * 96 : idx & 63;
+        const int idx = tid + j * 256, t8 = Q6 ? idx / 96 : Q3K ? idx / 48 : idx >> 6, c = Q6 ? idx - t8 * 96 : Q3K ? idx - t8 * 48 : idx & 63;
         int tile = (n0 >> 3) + t8; tile = tile < last_tile ? tile : last_tile;
-        bsrc[j] = (uint32_t)tile * (uint32_t)nst * (Q6 ? 1536u : 1024u) + (uint32_t)c * 16u;
-        bdst[j] = Q6 ? (uint32_t)(t8 * GFH_T6 + c * 16) : (uint32_t)((t8 * 8 + (c >> 3)) * GFH_LDB5 + (c & 7) * 16);
+        bsrc[j] = (uint32_t)tile * (uint32_t)nst * (uint32_t)TB + (uint32_t)c * 16u;
+        bdst[j] = Q6 ? (uint32_t)(t8 * GFH_T6 + c * 16) : Q3K ? (uint32_t)(t8 * GFH_T3 + c * 16) : (uint32_t)((t8 * 8 + (c >> 3)) * GFH_LDB5 + (c & 7) * 16);
     }
     // A chunks: load j of a thread = row 8 j + (tid >> 5), chunk ck = tid & 31 of the stage's 32 (whole 128-byte lines per 8 lanes, as the sibling)
     const int arow = tid >> 5, ck = tid & 31;
@@ -154,11 +165,14 @@ __global__ void __launch_bounds__(256, 2) kr_gfh_gemm_kernel(const KrGfhArgs a) 
     uint32_t ph[NHW], hw[NHW];
     auto load_B = [&](int st) {
 #pragma unroll
-        for (int j = 0; j < NBC; j++) pb[j] = kr_ldg_nt(reinterpret_cast<const u32x4*>(wq + bsrc[j] + (size_t)st * (Q6 ? 1536 : 1024)));
+        for (int j = 0; j < NBC; j++) pb[j] = kr_ldg_nt(reinterpret_cast<const u32x4*>(wq + bsrc[j] + (size_t)st * TB));
         if constexpr (Q6) {
             const uint32_t* hp = reinterpret_cast<const uint32_t*>(wh + hbase + (size_t)st * 160);
 #pragma unroll
             for (int i = 0; i < 5; i++) ph[i] = kr_ldg_nt(hp + i);
+        } else if constexpr (Q3K) {
+            const u32x4 v = kr_ldg_nt(reinterpret_cast<const u32x4*>(wh + hbase + (size_t)st * 128));
+            ph[0] = v.x; ph[1] = v.y; ph[2] = v.z; ph[3] = v.w;
         } else if constexpr (Q5K) {
             const char* hp = wh + hbase + (size_t)st * 384;
             const u32x4 v = kr_ldg_nt(reinterpret_cast<const u32x4*>(hp));
@@ -220,7 +234,7 @@ __global__ void __launch_bounds__(256, 2) kr_gfh_gemm_kernel(const KrGfhArgs a) 
     auto stage_mfma = [&](int st, auto nsa) {
         constexpr int NSA = decltype(nsa)::value;
         const v2h c16 = {(_Float16)16.0f, (_Float16)16.0f};
-        v2h sc[8];              // Q6_K: the 16 scales 16 d sc_j as f16 pairs (j = 2 p, 2 p + 1); Q5_0: sc[f] = 16 (d_2f, d_2f+1), f < 4
+        v2h sc[8];              // Q6_K, Q3_K: the 16 scales 16 d sc_j as f16 pairs (j = 2 p, 2 p + 1); Q5_0: sc[f] = 16 (d_2f, d_2f+1), f < 4
         if constexpr (Q6) {
             const uint32_t dw = hw[4] & 0xFFFFu;
             const v2h d16 = __builtin_bit_cast(v2h, dw | (dw << 16)) * c16;
@@ -230,6 +244,16 @@ __global__ void __launch_bounds__(256, 2) kr_gfh_gemm_kernel(const KrGfhArgs a) 
                 const uint32_t x = hw[w] ^ 0x80808080u;      // (1024 + (b ^ 0x80)) - 1152 = the signed byte
                 sc[2 * w] = (__builtin_bit_cast(v2h, __builtin_amdgcn_perm(0x64646464u, x, 0x04010400u)) + o8) * d16;
                 sc[2 * w + 1] = (__builtin_bit_cast(v2h, __builtin_amdgcn_perm(0x64646464u, x, 0x04030402u)) + o8) * d16;
+            }
+        } else if constexpr (Q3K) {      // sc[2 g], sc[2 g + 1] = 16 d (sc_4g .. sc_4g+3): the four 6-bit scales of group g as one word, each byte under the exponent of 1024.0, minus 1056
+            const uint32_t dw = hw[3] & 0xFFFFu;
+            const v2h d16 = __builtin_bit_cast(v2h, dw | (dw << 16)) * c16;
+            const v2h o32 = {(_Float16)-1056.0f, (_Float16)-1056.0f};
+#pragma unroll
+            for (int g = 0; g < 4; g++) {
+                const uint32_t x = gg_q3k_scales4(g, hw[0], hw[1], hw[2]);
+                sc[2 * g] = (__builtin_bit_cast(v2h, __builtin_amdgcn_perm(0x64646464u, x, 0x04010400u)) + o32) * d16;
+                sc[2 * g + 1] = (__builtin_bit_cast(v2h, __builtin_amdgcn_perm(0x64646464u, x, 0x04030402u)) + o32) * d16;
             }
         } else if constexpr (Q5K) {      // sc[js] = (16 d sc_js, -16 dmin mn_js), js < 8: each the exact product of two f16 values rounded once
             const v2h dm16 = __builtin_bit_cast(v2h, hw[0]) * c16;
@@ -252,7 +276,7 @@ __global__ void __launch_bounds__(256, 2) kr_gfh_gemm_kernel(const KrGfhArgs a) 
         v8h af[2][NSA][2];
         uint32_t br[2][3];
         auto rd = [&](int hr, int buf) {
-            // Q6_K: hr = 4 half + t; Q5_0: hr = 2 t + (record half); record l = 2 t + khalf
+            // Q6_K: hr = 4 half + t; Q5_0, Q5_K, Q3_K: hr = 2 t + (record half); record l = 2 t + khalf
             const int t = Q6 ? (hr & 3) : (hr >> 1), l = 2 * t + khalf;
             const int aoff = Q6 ? (hr >> 2) * 256 + l * 32 : l * 64 + (hr & 1) * 32;
 #pragma unroll
@@ -263,6 +287,9 @@ __global__ void __launch_bounds__(256, 2) kr_gfh_gemm_kernel(const KrGfhArgs a) 
             if constexpr (Q6) {
                 const uint32_t* p = reinterpret_cast<const uint32_t*>(Bs + bcol + (hr >> 2) * 768 + l * 12);
                 br[buf][0] = p[0]; br[buf][1] = p[1]; br[buf][2] = p[2];
+            } else if constexpr (Q3K) {      // half n = hr & 1 of the record: its qs word and the hmask word
+                const uint32_t* p = reinterpret_cast<const uint32_t*>(Bs + bcol + l * 12);
+                br[buf][0] = p[hr & 1]; br[buf][1] = p[2];
             } else {
                 const u32x2 p = *reinterpret_cast<const u32x2*>(Bs + bcol + l * 16 + (hr & 1) * 8);
                 br[buf][0] = p.x; br[buf][1] = p.y;
@@ -282,6 +309,19 @@ __global__ void __launch_bounds__(256, 2) kr_gfh_gemm_kernel(const KrGfhArgs a) 
                 gfh_bytes4(((ql >> 4) & 0x0F0F0F0Fu) | (qh & 0x30303030u), o, S(2), S(2), r0, r1);
                 gfh_bytes4(((qm >> 4) & 0x0F0F0F0Fu) | ((qh >> 2) & 0x30303030u), o, S(3), S(3), r2, r3);
                 bf[1] = v8h{r0.x, r0.y, r1.x, r1.y, r2.x, r2.y, r3.x, r3.y};
+            } else if constexpr (Q3K) {
+                // word n = hr & 1 of the record holds the chunks c = 4 n + j: bits 2j of its bytes and bit c of the hmask bytes are the four codes of chunk c in the order As
+                // holds them; bytes 0, 1 belong to sub-block 2 c, bytes 2, 3 to sub-block 2 c + 1 = the pair sc[c].  Fragment ff = chunks 4 n + 2 ff, 4 n + 2 ff + 1
+                const int n = hr & 1;
+                const uint32_t w = br[buf][0], hm = br[buf][1];
+                const v2h o = {(_Float16)-1028.0f, (_Float16)-1028.0f};
+#pragma unroll
+                for (int ff = 0; ff < 2; ff++) {
+                    const int c0 = 4 * n + 2 * ff, c1 = c0 + 1;
+                    gfh_bytes4(((w >> (4 * ff)) & 0x03030303u) | (((hm >> c0) & 0x01010101u) << 2), o, v2h{sc[c0].x, sc[c0].x}, v2h{sc[c0].y, sc[c0].y}, r0, r1);
+                    gfh_bytes4(((w >> (4 * ff + 2)) & 0x03030303u) | (((hm >> c1) & 0x01010101u) << 2), o, v2h{sc[c1].x, sc[c1].x}, v2h{sc[c1].y, sc[c1].y}, r2, r3);
+                    bf[ff] = v8h{r0.x, r0.y, r1.x, r1.y, r2.x, r2.y, r3.x, r3.y};
+                }
             } else if constexpr (Q5K) {
                 // word j of the record = chunk j: low nibbles the four values of sub-block 2 j, high nibbles those of sub-block 2 j + 1, in the order As holds them;
                 // the fifth bits come from the record's header word under one mask per (chunk, nibble), as in gg_tile_q5k
@@ -354,12 +394,12 @@ __global__ void __launch_bounds__(256, 2) kr_gfh_gemm_kernel(const KrGfhArgs a) 
 }
 
 bool kr_gfh_type_supported(int type, int K, int N) {
-    return (((type == GG_Q6_K || type == GG_Q5_K) && K % 256 == 0) || (type == GG_Q5_0 && K % 32 == 0)) && K > 0 && N > 0 && N % 8 == 0;
+    return (((type == GG_Q6_K || type == GG_Q5_K || type == GG_Q3_K) && K % 256 == 0) || (type == GG_Q5_0 && K % 32 == 0)) && K > 0 && N > 0 && N % 8 == 0;
 }
 
 template <int TYPE>
 static void gfh_launch(const KrGfhArgs& a, int mt, hipStream_t st) {
-    const size_t lds = (size_t)GFH_BM * GFH_LDA + (TYPE == GG_Q6_K ? (size_t)16 * GFH_T6 : (size_t)GFH_BN * GFH_LDB5) + 3 * GFH_BM * 4;
+    const size_t lds = (size_t)GFH_BM * GFH_LDA + (TYPE == GG_Q6_K ? (size_t)16 * GFH_T6 : TYPE == GG_Q3_K ? (size_t)16 * GFH_T3 : (size_t)GFH_BN * GFH_LDB5) + 3 * GFH_BM * 4;
     (void)kr_lds_optin((const void*)kr_gfh_gemm_kernel<TYPE>, 64 * 1024);      // per (kernel, device)
     const int ncb = (a.m.N + GFH_BN - 1) / GFH_BN;
     dim3 grid;
@@ -379,5 +419,5 @@ void kr_launch_gfh_gemm(const GgMat& m, const uint16_t* a_h, const float* a_mul,
     a.run = (single_expert_rows > 0 || run < 1) ? 1 : run;
     const int mt = single_expert_rows > 0 ? (single_expert_rows + GFH_BM - 1) / GFH_BM : max_tiles;
     if (mt <= 0) return;
-    if (m.type == GG_Q6_K) gfh_launch<GG_Q6_K>(a, mt, st); else if (m.type == GG_Q5_K) gfh_launch<GG_Q5_K>(a, mt, st); else gfh_launch<GG_Q5_0>(a, mt, st);
+    if (m.type == GG_Q6_K) gfh_launch<GG_Q6_K>(a, mt, st); else if (m.type == GG_Q5_K) gfh_launch<GG_Q5_K>(a, mt, st); else if (m.type == GG_Q3_K) gfh_launch<GG_Q3_K>(a, mt, st); else gfh_launch<GG_Q5_0>(a, mt, st);
 }

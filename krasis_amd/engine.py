@@ -141,20 +141,21 @@ class KrasisEngine:
         self._cpu_bits = self._gpu_bits = bits
 
     def fill_synthetic_gguf(self, gate_up_type: int = 12, down_type: int = 12, seed: int = 0x12345678ABCDEF01, layers: Optional[Sequence[int]] = None) -> None:
-        """Synthetic native-GGUF experts (ggml type ids: Q4_K = 12, Q5_K = 13, Q8_0 = 8, Q5_0 = 6, Q6_K = 14) with the block distribution SURVEY 8d defines, generated on the GPU."""
+        """Synthetic native-GGUF experts (ggml type ids: Q3_K = 11, Q4_K = 12, Q5_K = 13, Q8_0 = 8, Q5_0 = 6, Q6_K = 14) with the block distribution SURVEY 8d defines, generated on the GPU."""
         self._need()
         for layer in (layers if layers is not None else range(self._cfg.num_moe_layers)):
             check(self._lib.kr_fill_layer_synthetic_gguf(self._h, layer, gate_up_type, down_type, (seed + layer * 0x9E3779B97F4A7C15) & (2**64 - 1)))
         self._has_gguf = True
 
     def gguf_matvec(self, type: int, blocks: np.ndarray, N: int, K: int, x: np.ndarray, parts: int = 0) -> np.ndarray:
-        """y[N] = W x for N rows of raw row-major Q5_0 (6) / Q5_K (13) / Q6_K (14) blocks and an f32 vector x[K], through the kernels the MoE paths run for such
-        a matrix.  parts 0: the reference's serial f32 chain per row, bit for bit (Q5_K: its scalar Q4_K row over dequant_q5_k's values); parts 1 | 2: the tolerance tile of KR_DECODE_FAST over the whole
+        """y[N] = W x for N rows of raw row-major Q5_0 (6) / Q3_K (11) / Q5_K (13) / Q6_K (14) blocks and an f32 vector x[K], through the kernels the MoE paths run for such
+        a matrix.  parts 0: the reference's serial f32 chain per row, bit for bit (Q5_K: its scalar Q4_K row over dequant_q5_k's values; Q3_K: the same row over the values
+        of ggml's block definition, docs/design/47-gguf-q3k.md); parts 1 | 2: the tolerance tile of KR_DECODE_FAST over the whole
         row / over two slices of its blocks whose results are added.  Other types, parts or shapes: ValueError.  Keeps no state on the engine."""
         self._need()
         blocks = np.ascontiguousarray(blocks, np.uint8); x = np.ascontiguousarray(x, np.float32)
         y = np.empty(max(int(N), 0), np.float32)
-        if type in (6, 13, 14) and (blocks.size != int(N) * (int(K) // (32 if type == 6 else 256)) * {6: 22, 13: 176, 14: 210}[type] or x.size != int(K)):
+        if type in (6, 11, 13, 14) and (blocks.size != int(N) * (int(K) // (32 if type == 6 else 256)) * {6: 22, 11: 110, 13: 176, 14: 210}[type] or x.size != int(K)):
             raise ValueError("gguf_matvec: blocks / x do not hold N x K")
         check(self._lib.kr_gguf_matvec(self._h, int(type), _addr(blocks), int(N), int(K), _addr(x), _addr(y), int(parts)))
         return y

@@ -36,8 +36,9 @@ GGUF_DEFAULT_ALIGNMENT = 32
 GGML_BLOCK = {0: (1, 4), 1: (1, 2), 30: (1, 2), 2: (32, 18), 3: (32, 20), 6: (32, 22), 7: (32, 24), 8: (32, 34), 9: (32, 40), 10: (256, 84),
               11: (256, 110), 12: (256, 144), 13: (256, 176), 14: (256, 210), 15: (256, 276)}
 # Q4_0, Q5_0, Q8_0, Q4_K, Q5_K, Q6_K: block kernels exist (csrc/kr_gguf.hip == gguf_kernels.rs; Q5_K, for which the reference has a de-quantizer and no matvec:
-# its scalar Q4_K row over dequant_q5_k's values, docs/design/45-gguf-q5k.md)
-NATIVE_TYPES = {2, 6, 8, 12, 13, 14}
+# its scalar Q4_K row over dequant_q5_k's values, docs/design/45-gguf-q5k.md; Q3_K, for which it has neither: the same row over the values of ggml's block
+# definition, docs/design/47-gguf-q3k.md)
+NATIVE_TYPES = {2, 6, 8, 11, 12, 13, 14}
 
 
 @dataclass
@@ -282,8 +283,8 @@ class GgufFile:
 def load_from_gguf(engine, gguf_path: str, config_json: Optional[str] = None, gguf_native: bool = True, max_layers: Optional[int] = None,
                    start_layer: Optional[int] = None, cfg: Optional[MoeConfig] = None, group_size: int = 128) -> MoeConfig:
     """KrasisEngine.load(gguf_path=...) (moe.rs:1538 -> weights/mod.rs:3251).
-    `gguf_native=True` keeps the file's blocks (Q4_K / Q5_K / Q8_0 / Q4_0 / Q5_0 / Q6_K) and runs the native block kernels: `Q4_K_M` files (Q4_K gate / up,
-    Q4_K or Q6_K down), `Q5_K_M` files (Q5_K gate / up, Q5_K or Q6_K down, layer by layer), `Q6_K` and `Q8_0` files.
+    `gguf_native=True` keeps the file's blocks (Q3_K / Q4_K / Q5_K / Q8_0 / Q4_0 / Q5_0 / Q6_K) and runs the native block kernels: `Q4_K_M` files (Q4_K gate / up,
+    Q4_K or Q6_K down), `Q5_K_M` files (Q5_K gate / up, Q5_K or Q6_K down, layer by layer), `Q3_K_S` / `Q3_K_M` / `Q3_K_L` files (Q3_K gate / up), `Q6_K` and `Q8_0` files.
     `gguf_native=False` is the reference's default (the only GGUF mode its CLI reaches): every expert tensor is de-quantized to f32
     (gguf.rs:872), rounded to bf16 and re-quantized to INT4 / INT8-g128 with the expert quantizer (weights/mod.rs:3592-3760, :4063-4113);
     the width is chosen once for the whole file -- the widest mapping of any gate tensor for w13, of any down tensor for w2
